@@ -8,12 +8,21 @@ feature batch).  Inputs and outputs are device resident
 quantized once on rank 0 and broadcast over RCCL at load time only; there is no collective in the
 timed region (frames are independent: weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: setup, W warm-up steps, the K timed steps, the outputs of the last timed
+step if --dump-outputs is given, and the JSON line (`value`, `ms_per_step`, `multi_gpu`, `end_to_end`, `setup`).  Every
+other leg (single_stream and those listed below, the other layer-0 flavour, the pair-free net, config1_1000, and at N > 1
+the 125 000-frame shard and the host-fed legs) runs only with --full.
+--dump-outputs DIR writes a fixed, seeded sample of the soft-max rows of the last timed step as DIR/probs_sample.npy
+(float32, at most 32 MB over all ranks; `_rank<r>` suffix at N > 1) and their frame indices as probs_sample_rows.npy
+(float64); inputs and weights are seeded, so two builds can be compared output for output.
 
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) starts its own N ranks: it re-executes itself under
 torch.distributed.run on 127.0.0.1 with a free port and passes the exit code on.  Every N runs the SAME 10 000 frames per
-GPU per step; at N > 1 a second value is reported for 125 000 frames per GPU (BASELINE configs[4]: 1 M frames over 8 GPUs).
+GPU per step; at N > 1 with --full a second value is reported for 125 000 frames per GPU (BASELINE configs[4]: 1 M frames
+over 8 GPUs).
 `--share-device` puts every rank on device 0 (a one-GPU box: the launch, rendezvous, broadcast and timing protocol with a
 real scorer; the blob then travels over gloo, RCCL refuses two ranks on one device); `--stub-scorer` runs the same
 protocol without any GPU (gloo, host buffers, a scorer that only fills its output) -- the CPU test of the launch logic.
@@ -21,13 +30,14 @@ protocol without any GPU (gloo, host buffers, a scorer that only fills its outpu
 The K timed steps are submitted to the scoring loop (fdnn_server_*, in-flight depth 2: the
 HBM-bound soft-max scale of step i runs under the VALU-bound layer 0 of step i+1, every step a
 complete pass with its own output buffer) and the clock stops when the last result is complete.
-The same K steps back to back on one stream (fdnn_calculate_device) are reported as `single_stream`.
+With --full, the same K steps back to back on one stream (fdnn_calculate_device) are reported as `single_stream`.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with
+Rank 0 prints ONE JSON line with
+  end_to_end           value against the int8-MFMA ceiling of the whole net (60 M frames/s)
+and, with --full,
   roofline             the kernel class with the largest share of the step, live HIP-event times
   roofline_kernels     all four classes (layer 0, hidden int8 GEMM, output int8 GEMM, soft-max scale)
   roofline_int8_gemm   the hidden-layer int8 GEMM by name (the MFMA kernel the net is made of)
-  end_to_end           value against the int8-MFMA ceiling of the whole net (60 M frames/s)
   lazy_40pct           BASELINE configs[3]: LazyContext contract, 40 % mask with 3 % churn, same batch
   small_batch          one 100-frame utterance / one 8-frame block per call, device resident: us per call, weight-stream
                        GB/s against the 8 TB/s HBM figure (the regime of the reference's own callers)
@@ -226,6 +236,28 @@ def timed_steps(submit, drain, fence, warmup: int, steps: int) -> float:
     return time.perf_counter() - t0
 
 
+DUMP_BYTES = 32 << 20  # --dump-outputs: soft-max rows written over all ranks
+
+
+def dump_outputs(out_dir: str, probs, rank: int, world: int) -> None:
+    """--dump-outputs: a fixed, seeded sample of the rows of `probs` ([n][O] fp32, a torch tensor on any device or a
+    numpy array: what the caller of the timed path receives) as out_dir/probs_sample.npy, their frame indices as
+    probs_sample_rows.npy (float64).  Same arguments -> same rows, so that two builds can be compared row for row."""
+    n, O = int(probs.shape[0]), int(probs.shape[1])
+    rows = max(1, min(n, DUMP_BYTES // (4 * O * world)))
+    idx = np.sort(np.random.default_rng(20240611).choice(n, size=rows, replace=False))
+    if isinstance(probs, np.ndarray):
+        sample = probs[idx]
+    else:
+        import torch
+
+        sample = probs[torch.from_numpy(idx).to(probs.device)].cpu().numpy()
+    suffix = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"probs_sample{suffix}.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    np.save(os.path.join(out_dir, f"probs_sample_rows{suffix}.npy"), idx.astype(np.float64))
+
+
 def max_over_ranks(dist, world: int, elapsed: float, dev) -> float:
     if world == 1:
         return elapsed
@@ -362,24 +394,29 @@ def stub_main(args, rank: int, world: int) -> None:
 
     own = timed_steps(submit, lambda: None, fence, args.warmup, args.steps)
     elapsed = max_over_ranks(dist, world, own, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     rep = rank_report(dist, world, rank, digest, n * args.steps / own, "cpu (stub)", device_key="cpu", shared=True)
-    # the two host-fed legs of the N-rank line, with the stub scorer: per-rank caller threads, and one process over N "devices"
-    bufs = [np.empty((100, O), dtype=np.float32) for _ in range(4)]
+    extra = {}
+    if args.full:
+        # the two host-fed legs of the N-rank line, with the stub scorer: per-rank caller threads, and one process over N "devices"
+        bufs = [np.empty((100, O), dtype=np.float32) for _ in range(4)]
 
-    def make_caller(t):
-        def body():
-            for _ in range(10):
-                bufs[t].fill(1.0 / O)
-        return body
+        def make_caller(t):
+            def body():
+                for _ in range(10):
+                    bufs[t].fill(1.0 / O)
+            return body
 
-    host_fed = host_fed_leg(make_caller, 4, 10, 100, fence, dist, world, dev)
-    one_process = None
-    if rank == 0:
-        t0 = time.perf_counter()
-        for _ in range(3):
-            for _d in range(world):
-                out.fill(1.0 / O)
-        one_process = {"devices": world, "frames_per_s_whole_node": round(3 * world * n / (time.perf_counter() - t0), 1), "stub": True}
+        host_fed = host_fed_leg(make_caller, 4, 10, 100, fence, dist, world, dev)
+        one_process = None
+        if rank == 0:
+            t0 = time.perf_counter()
+            for _ in range(3):
+                for _d in range(world):
+                    out.fill(1.0 / O)
+            one_process = {"devices": world, "frames_per_s_whole_node": round(3 * world * n / (time.perf_counter() - t0), 1), "stub": True}
+        extra = {"host_fed": host_fed, "one_process_group": one_process}
     fence()
     if rank == 0:
         print(json.dumps({
@@ -389,7 +426,7 @@ def stub_main(args, rank: int, world: int) -> None:
             "dtype": "none (stub scorer)", "data": "synthetic",
             "config": {"workload": "STUB: launch / rendezvous / broadcast / timing protocol only, no scorer, no GPU", "frames_per_gpu": n,
                        "global_frames": world * n, "parallelism": f"frame-sharded x{world}, replicated weights"},
-            "multi_gpu": rep, "host_fed": host_fed, "one_process_group": one_process, "stub": True}), flush=True)
+            "multi_gpu": rep, **extra, "full": bool(args.full), "stub": True}), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -403,7 +440,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--frames", type=int, default=0,
                     help="frames per GPU per step; default 10 000 at every N (BASELINE configs[2]), so that the 1 -> N ratio "
-                         "compares like with like; at N > 1 the 125 000-frame shard of configs[4] is timed as a second value "
+                         "compares like with like; at N > 1 with --full the 125 000-frame shard of configs[4] is timed as a second value "
                          "(`config4_125k_per_gpu`, skip with --no-config4)")
     ap.add_argument("--no-config4", action="store_true", help="N > 1: skip the 125 000-frames-per-GPU leg")
     ap.add_argument("--share-device", action="store_true",
@@ -423,14 +460,24 @@ def main() -> None:
     ap.add_argument("--no-nosat", action="store_true", help="skip the pair-free-net extra")
     ap.add_argument("--no-small", action="store_true", help="skip the small-batch (100- and 8-frame call) leg")
     ap.add_argument("--no-serving", action="store_true", help="skip the 100-frame-utterance serving leg")
-    ap.add_argument("--host-fed", action="store_true", help="N = 1: also run the N > 1 host-fed legs (per-rank caller threads, one-process group)")
+    ap.add_argument("--host-fed", action="store_true", help="with --full at N = 1: also run the N > 1 host-fed legs (per-rank caller threads, "
+                                                            "one-process group)")
     ap.add_argument("--clock-ramp-s", type=float, default=0.5, help="seconds of untimed load before the W warm-up steps (setup)")
     ap.add_argument("--single-stream-only", action="store_true",
                     help="profiling runs (tools/profile_round.sh): only the back-to-back single-stream steps, so that rocprofv3's "
                          "per-kernel averages are not mixed with the overlapped legs")
     ap.add_argument("--l0-fma", action="store_true",
                     help="layer 0 with the fused multiply-add numerics of a -march=native reference build (fp32 MFMA)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: single_stream, per-kernel roofline, other layer-0 flavour, pair-free "
+                         "net, lazy_40pct, small batches, config1_1000, serving, cpu_baseline; at N > 1 config4_125k_per_gpu and the "
+                         "host-fed legs (the --no-* options skip single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded sample of the last timed step's soft-max rows as DIR/probs_sample.npy (float32) "
+                         "and their frame indices as DIR/probs_sample_rows.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -529,6 +576,8 @@ def main() -> None:
             step_single()
         fence()
         el = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outs[0], rank, world)
         if rank == 0:
             print(json.dumps({"mode": "single-stream-only", "frames_per_s": round(world * n * args.steps / el, 1),
                               "ms_per_step": round(el / args.steps * 1e3, 4), "steps": args.steps, "frames_per_gpu": n}), flush=True)
@@ -561,6 +610,54 @@ def main() -> None:
         assert abs(row_sum - 1.0) < 1e-3, row_sum
         for o in outs[1:]:
             assert torch.equal(o, outs[0]), "in-flight steps disagree"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % depth], rank, world)
+
+    # ---- the headline line; everything after it in this function runs only with --full
+    value = world * n * args.steps / elapsed
+    head = {
+        "metric": "acoustic frames/sec (whole node), 7x2048->8000 nnet",
+        "value": round(value, 1),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "multi_gpu": multi,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int8 (u8 activations x s8 weights -> int32; fp32 layer 0 and soft-max)",
+        "data": "synthetic",
+        "config": {
+            "workload": f"BASELINE configs[2]{'' if world == 1 else ' on every GPU (configs[4] as config4_125k_per_gpu with --full)'}: synthetic Kaldi nnet "
+                        f"432 -> 7x2048 -> 8000 ({args.mode} weights, seed 1), {n}-frame batch per GPU, full soft-max, device-resident in/out",
+            "frames_per_gpu": n, "global_frames": world * n, "parallelism": f"frame-sharded x{world}, replicated weights",
+            "layer0_numerics": "fused (reference built -march=native)" if args.l0_fma else "unfused (reference built -msse4, canonical)",
+            "steps_in_flight": depth,
+            "submission": "fdnn_server_submit_device: every step a complete pass into its own output buffer (dense and batched-lazy "
+                          "steps alike scale their soft-max inside the output kernel)",
+        },
+        "x_realtime_per_gpu": round(value / world / 100.0, 1),
+        "int8_tops_end_to_end": round(INT8_OPS_PER_FRAME * value / world / 1e12, 1),
+        "end_to_end": {"bound": "mfma", "achieved": round(value / world, 1), "peak": round(ROOFLINE_FRAMES_PER_S, 1), "unit": "frames/s per GPU",
+                       "frac": round(value / world / ROOFLINE_FRAMES_PER_S, 4),
+                       "note": "5 POP/s int8 / 83.1 M int8 ops per frame (layers 1..7); layer 0 (2 % of the MACs, fp32 in the reference) runs as "
+                               "six int8 digit products + an exact fix and takes about a fifth of the step; the 32 KB per frame of "
+                               "probabilities leave from inside the output kernel"},
+        "setup": {"clock_ramp_steps": ramp_steps, "clock_ramp_s": args.clock_ramp_s,
+                  "note": "untimed forward passes before the W warm-up steps, so that short runs see sustained clocks"},
+        "full": bool(args.full),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        srv.close()
+        dnn.delete()
+        if world > 1 or force_coll:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same K steps back to back on one stream
     for _ in range(args.warmup):
@@ -1012,7 +1109,6 @@ def main() -> None:
                         break
             return total if found else None
 
-        step_ms = elapsed / steps * 1e3
         kinds = []
 
         def add(key, kernel, bound, work_per_launch, peak, unit, scale, alg_bytes, pmc_prefix):
@@ -1083,50 +1179,19 @@ def main() -> None:
                 break
             except Exception:  # noqa: BLE001
                 continue
-        value = world * n * steps / elapsed
         res = {
-            "metric": "acoustic frames/sec (whole node), 7x2048->8000 nnet",
-            "value": round(value, 1),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "multi_gpu": multi,
+            **head,
             "config4_125k_per_gpu": config4,
             "host_fed": host_fed,
             "one_process_group": one_process,
-            "steps": steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(step_ms, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int8 (u8 activations x s8 weights -> int32; fp32 layer 0 and soft-max)",
-            "data": "synthetic",
-            "config": {
-                "workload": f"BASELINE configs[2]{'' if world == 1 else ' on every GPU (configs[4] as config4_125k_per_gpu)'}: synthetic Kaldi nnet 432 -> 7x2048 -> 8000 "
-                            f"({args.mode} weights, seed 1), {n}-frame batch per GPU, full soft-max, device-resident in/out",
-                "frames_per_gpu": n, "global_frames": world * n, "parallelism": f"frame-sharded x{world}, replicated weights",
-                "layer0_numerics": "fused (reference built -march=native)" if args.l0_fma else "unfused (reference built -msse4, canonical)",
-                "steps_in_flight": depth,
-                "submission": "fdnn_server_submit_device: every step a complete pass into its own output buffer (dense and batched-lazy "
-                              "steps alike scale their soft-max inside the output kernel)",
-            },
-            "x_realtime_per_gpu": round(value / world / 100.0, 1),
-            "int8_tops_end_to_end": round(INT8_OPS_PER_FRAME * value / world / 1e12, 1),
             "single_stream": {"frames_per_s": round(world * n * steps / single_elapsed, 1), "ms_per_step": round(single_elapsed / steps * 1e3, 4),
                               "note": "the same K steps as back-to-back fdnn_calculate_device calls on one stream (no overlap between steps)"},
             "roofline": dict(dominant, note="largest share of the step; times from HIP events on the launch stream, which add ~4 us per "
                                             "bracketed launch; `traffic` is replayed from the committed PMC passes (traffic_replayed_from), frac / avg_launch_ms are live"),
             "roofline_int8_gemm": gemm,
             "roofline_kernels": kinds,
-            "end_to_end": {"bound": "mfma", "achieved": round(value / world, 1), "peak": round(ROOFLINE_FRAMES_PER_S, 1), "unit": "frames/s per GPU",
-                           "frac": round(value / world / ROOFLINE_FRAMES_PER_S, 4),
-                           "note": "5 POP/s int8 / 83.1 M int8 ops per frame (layers 1..7); layer 0 (2 % of the MACs, fp32 in the reference) runs as "
-                                   "six int8 digit products + an exact fix and takes about a fifth of the step; the 32 KB per frame of "
-                                   "probabilities leave from inside the output kernel"},
             "traffic_source": pmc_file,
             "rocprof": rocprof,
-            "setup": {"clock_ramp_steps": ramp_steps, "clock_ramp_s": args.clock_ramp_s,
-                      "note": "untimed forward passes before the W warm-up steps, so that short runs see sustained clocks"},
             "kernel_ms_per_step": {k: round(v["ms"] / steps, 4) for k, v in prof.items()},
             "other_layer0_flavour": None if alt is None else {
                 "layer0_numerics": "unfused (canonical)" if args.l0_fma else "fused (reference built -march=native), fp32 MFMA",

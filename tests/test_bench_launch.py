@@ -25,7 +25,7 @@ def _run(extra, env_drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MA
 
 
 def test_bench_starts_its_own_two_ranks():
-    res = _run(["--gpus", "2"])
+    res = _run(["--gpus", "2", "--full"])
     assert res["n_gpus"] == 2 and res["steps"] == 5 and res["warmup"] == 2 and res["scaling"] == "weak"
     m = res["multi_gpu"]
     assert m["ranks"] == 2 and m["collective_backend"] == "gloo" and m["rccl_ranks"] == 0
@@ -46,6 +46,32 @@ def test_bench_starts_its_own_two_ranks():
 def test_bench_single_rank_needs_no_launcher():
     res = _run(["--gpus", "1"])
     assert res["n_gpus"] == 1 and res["multi_gpu"]["ranks"] == 1 and res["multi_gpu"]["blob_sha256_all_equal"]
+
+
+def test_plain_run_is_the_headline_only():
+    """Without --full the line carries the headline and none of the other legs."""
+    res = _run(["--gpus", "2"])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in res
+    assert res["full"] is False and res["steps"] == 5 and res["ms_per_step"] > 0
+    assert "host_fed" not in res and "one_process_group" not in res
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    import numpy as np
+
+    for run in ("a", "b"):
+        res = _run(["--gpus", "1", "--dump-outputs", str(tmp_path / run)])
+        assert res["full"] is False
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["probs_sample.npy", "probs_sample_rows.npy"] and sorted(os.listdir(tmp_path / "b")) == files
+    for name in files:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)  # same arguments, same outputs
+    probs = np.load(tmp_path / "a" / "probs_sample.npy")
+    rows = np.load(tmp_path / "a" / "probs_sample_rows.npy")
+    assert probs.shape == (256, 100) and rows.shape == (256,)  # the stub's whole 256 x 100 output fits the budget
+    assert np.allclose(probs.sum(1), 1.0, atol=1e-5)
 
 
 def test_bench_refuses_a_mismatched_launcher():

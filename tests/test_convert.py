@@ -13,8 +13,6 @@ from conftest import golden
 from fast_dnn_amd import convert as CV
 from fast_dnn_amd import formats as F
 
-REF_DATA = "/root/reference/data"
-
 
 def test_feature_text_rows_match_the_reference_bin(tmp_path):
     g = golden("feat_text_head.npz")
@@ -30,18 +28,21 @@ def test_feature_text_rows_match_the_reference_bin(tmp_path):
         assert (al[:, frames.shape[1]:] == 0).all()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference data files not present")
 @pytest.mark.parametrize("text,binary", [("16khz", "16khz.bin"), ("8khz", "8khz.aligned.bin")])
-def test_whole_feature_file_byte_identical(text, binary):
-    raw = open(os.path.join(REF_DATA, binary), "rb").read()
+def test_whole_feature_file_byte_identical(text, binary, tmp_path):
+    g = golden("feat_files.npz")  # the reference's data files, whole (tests/golden/make_convert_golden.py)
+    raw = g[binary.replace(".", "_")].tobytes()
+    text_path, bin_path = tmp_path / text, tmp_path / binary
+    text_path.write_bytes(g[text].tobytes())
+    bin_path.write_bytes(raw)
     n_header, dim = struct.unpack(">ii", raw[:8])
-    (_, frames), = CV.load_feature_text(os.path.join(REF_DATA, text))
+    (_, frames), = CV.load_feature_text(str(text_path))
     got = CV.feature_matrix_bytes(CV.align_features(frames, 4), n_header)
     assert got == raw
     # the off-by-one of serializeDataMatrix shows in the reference's own file whenever it was cut
     rows_in_file = (len(raw) - 8) // (4 * dim)
     assert rows_in_file in (n_header, n_header + 1)
-    assert F.read_feature_bin(os.path.join(REF_DATA, binary)).shape == (n_header, dim)
+    assert F.read_feature_bin(str(bin_path)).shape == (n_header, dim)
 
 
 def test_header_vs_rows_quirk():

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $ROOT/gpurun_out
 timeout -k 5 240 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -o p -- \
-  python $ROOT/bench.py --no-cpu-baseline --steps 10 --warmup 2 ${BENCH_ARGS:-} > /dev/null 2> $ROOT/gpurun_out/pmc_$TAG.log
+  python $ROOT/bench.py --full --no-cpu-baseline --steps 10 --warmup 2 ${BENCH_ARGS:-} > /dev/null 2> "$(dirname "$OUT")/pmc_$TAG.log"
 echo "rocprofv3 rc=$?"
 python - "$OUT/p_counter_collection.csv" <<'PY'
 import csv, sys, collections
