@@ -120,6 +120,19 @@ SIGNATURES = {
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_profile_begin": (C.c_int, [C.c_void_p]),
     "fdnn_profile_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "fdnn_model_set_splice": (C.c_int, [C.c_void_p, _c_i32p, C.c_int, C.c_int]),
+    "fdnn_model_get_splice": (C.c_int, [C.c_void_p, _c_i32p, C.c_int, _c_i32p]),
+    "fdnn_calculate_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_f32p]),
+    "fdnn_calculate_raw_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_i32p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_lazy_bits_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_f32p]),
+    "fdnn_ctx_forward_hidden_raw": (C.c_int, [C.c_void_p, _c_f32p]),
+    "fdnn_stream_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "fdnn_stream_free": (None, [C.c_void_p]),
+    "fdnn_stream_reset": (C.c_int, [C.c_void_p]),
+    "fdnn_stream_position": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "fdnn_stream_push": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_f32p, _c_i32p]),
+    "fdnn_stream_ctx": (C.c_void_p, [C.c_void_p]),
+    "fdnn_server_submit_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_void_p, _c_f32p, C.POINTER(C.c_uint64)]),
     "fdnn_host_model_load": (C.c_int, [C.c_char_p, C.c_float, C.POINTER(C.c_void_p)]),
     "fdnn_host_model_free": (None, [C.c_void_p]),
     "fdnn_host_model_layers": (C.c_int, [C.c_void_p]),
@@ -236,17 +249,27 @@ def set_ppo(mode: int) -> None:
 class LazyContext:
     """``QuantizedDnn.LazyContext`` (QuantizedDnn.java:72-98)."""
 
-    def __init__(self, dnn: "QuantizedDnn", handle: int, input_vector_count: int):
+    def __init__(self, dnn: "QuantizedDnn", handle: int, input_vector_count: int, owned: bool = True):
         self.dnn = dnn
         self.handle = handle
         self.inputVectorCount = input_vector_count
         self.currentVectorIndex = 0
+        self._owned = owned  # False: a view of a context that belongs to a SpliceStream
 
     def calculateUntilOutput(self, input) -> None:
         x = _f32(input)
         if x.shape != (self.inputVectorCount, self.dnn.inputDimension()):
             raise ValueError(f"expected {self.inputVectorCount}x{self.dnn.inputDimension()} frames, got {x.shape}")
         _check(lib().fdnn_ctx_forward_hidden(self.handle, x.ctypes.data_as(_c_f32p)))
+
+    def calculateUntilOutputRaw(self, raw) -> None:
+        """calculateUntilOutput on the context's inputVectorCount RAW frames of one utterance, spliced on the device
+        (QuantizedDnn.setSplice): the same hidden activations as calculateUntilOutput on the host-spliced rows."""
+        r = _f32(raw)
+        spec = self.dnn.spliceSpec()
+        if spec is not None and r.shape != (self.inputVectorCount, spec[1]):
+            raise ValueError(f"expected {self.inputVectorCount}x{spec[1]} raw frames, got {r.shape}")
+        _check(lib().fdnn_ctx_forward_hidden_raw(self.handle, r.ctypes.data_as(_c_f32p)))
 
     def calculateForOutputNodes(self, activeNodesMask) -> np.ndarray:
         mask = np.ascontiguousarray(activeNodesMask, dtype=np.int8)
@@ -312,8 +335,58 @@ class LazyContext:
         return out
 
     def delete(self) -> None:
-        if self.handle:
+        if self.handle and self._owned:
             lib().fdnn_ctx_free(self.handle)
+        self.handle = None
+
+
+class SpliceStream:
+    """An utterance scored as its raw frames arrive (``fdnn_stream_*``): every push returns the rows it completes, in
+    order; ``end=True`` flushes the rest, right-clamped to the last frame.  Made by ``QuantizedDnn.newStream``; it keeps
+    the model's splice spec of that moment."""
+
+    def __init__(self, dnn: "QuantizedDnn", maxChunk: int):
+        spec = dnn.spliceSpec()
+        h = C.c_void_p()
+        _check(lib().fdnn_stream_create(dnn.nativeDnnHandle, int(maxChunk), C.byref(h)))
+        self.handle = h.value
+        self.dnn = dnn
+        self.maxChunk = int(maxChunk)
+        self.offsets, self.rawDim = spec
+        self.right = max(0, max(self.offsets))
+
+    def _push(self, raw, end: bool, out):
+        r = np.ascontiguousarray(raw, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != self.rawDim:
+            raise ValueError(f"raw frames must be [n][{self.rawDim}], got {r.shape}")
+        n = C.c_int(0)
+        _check(lib().fdnn_stream_push(self.handle, r.ctypes.data_as(_c_f32p), r.shape[0], int(bool(end)),
+                                      out.ctypes.data_as(_c_f32p) if out is not None else None, C.byref(n)))
+        return int(n.value)
+
+    def push(self, raw, end: bool = False) -> np.ndarray:
+        """raw [n][rawDim] -> the soft-max rows of the frames this push completes ([k][outputDimension])."""
+        out = np.empty((len(raw) + self.right, self.dnn.outputDimension()), dtype=np.float32)
+        return out[:self._push(raw, end, out)]
+
+    def pushHidden(self, raw, end: bool = False) -> LazyContext:
+        """Hidden layers only: a LazyContext view whose frames are exactly the frames this push completes (valid until
+        the next push; the stream owns it)."""
+        k = self._push(raw, end, None)
+        return LazyContext(self.dnn, lib().fdnn_stream_ctx(self.handle), k, owned=False)
+
+    def reset(self) -> None:
+        _check(lib().fdnn_stream_reset(self.handle))
+
+    def position(self):
+        """(raw frames pushed, rows emitted) since the utterance started."""
+        p, e = C.c_int64(), C.c_int64()
+        _check(lib().fdnn_stream_position(self.handle, C.byref(p), C.byref(e)))
+        return int(p.value), int(e.value)
+
+    def close(self) -> None:
+        if self.handle:
+            lib().fdnn_stream_free(self.handle)
             self.handle = None
 
 
@@ -431,6 +504,30 @@ class ScoringServer:
         _check(lib().fdnn_server_submit_lazy_bits(self.handle, x.ctypes.data_as(_c_f32p), x.shape[0], C.c_void_p(b.ctypes.data),
                                                   out.ctypes.data_as(_c_f32p), C.byref(t)))
         self._keep[int(t.value)] = (x, b, out)
+        return int(t.value), out
+
+    def submitRaw(self, raw, bits=None, out=None):
+        """Raw feature frames [n][rawDim] of one utterance (the model's splice spec, QuantizedDnn.setSplice): coalesced
+        with the other callers' raw utterances, each keeping its own edges; ``bits`` selects the lazy contract (as
+        ``submitLazy``) -> (ticket, out array)."""
+        r = np.ascontiguousarray(raw, dtype=np.float32)
+        spec = self.dnn.spliceSpec()
+        if spec is not None and (r.ndim != 2 or r.shape[1] != spec[1]):
+            raise ValueError(f"raw frames must be [n][{spec[1]}], got {r.shape}")
+        n, O = r.shape[0], self.dnn.outputDimension()
+        b = None
+        if bits is not None:
+            b = np.ascontiguousarray(bits, dtype=np.uint64)
+            if b.shape != (n, (O + 63) // 64):
+                raise ValueError(f"bits must be {n} x {(O + 63) // 64} uint64, got {b.shape}")
+        if out is None:
+            out = np.empty((n, O), dtype=np.float32)
+        elif out.dtype != np.float32 or out.shape != (n, O) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous float32 array of shape {(n, O)}")
+        t = C.c_uint64()
+        _check(lib().fdnn_server_submit_raw(self.handle, r.ctypes.data_as(_c_f32p), n, C.c_void_p(b.ctypes.data) if b is not None else None,
+                                            out.ctypes.data_as(_c_f32p), C.byref(t)))
+        self._keep[int(t.value)] = (r, b, out)
         return int(t.value), out
 
     def wait(self, ticket: int) -> None:
@@ -559,6 +656,60 @@ class QuantizedDnn:
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))
+
+    # -- raw feature frames (the <Splice> block on the device) ------------------
+    def setSplice(self, offsets, rawDim: int = 0) -> None:
+        """Frame offsets of the feature transform's <Splice> block (convert.load_splice_offsets) and the raw frame width;
+        ``setSplice([], 0)`` clears the spec.  Set it before the model is used from several threads."""
+        o = np.ascontiguousarray(list(offsets), dtype=np.int32)
+        _check(lib().fdnn_model_set_splice(self.nativeDnnHandle, o.ctypes.data_as(_c_i32p) if o.size else None, int(o.size), int(rawDim)))
+
+    def spliceSpec(self):
+        """(offsets, rawDim), or None without a spec."""
+        buf = np.zeros(64, dtype=np.int32)
+        d = C.c_int32(0)
+        k = lib().fdnn_model_get_splice(self.nativeDnnHandle, buf.ctypes.data_as(_c_i32p), 64, C.byref(d))
+        if k < 0:
+            _check(k)
+        return ([int(v) for v in buf[:k]], int(d.value)) if k else None
+
+    def calculateRaw(self, raw) -> np.ndarray:
+        """``calculate`` on raw frames [n][rawDim] of one utterance, spliced on the device: one soft-max row per frame,
+        bit-identical to ``calculate(convert.splice_frames(raw, offsets, inputDimension()))``."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError(f"raw frames must be [n][rawDim], got {r.shape}")
+        out = np.empty((r.shape[0], self.outputDimension()), dtype=np.float32)
+        _check(lib().fdnn_calculate_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], out.ctypes.data_as(_c_f32p)))
+        return out
+
+    def calculateRawDevice(self, d_raw: int, n: int, d_out: int, segStarts=None, stream: int = 0) -> None:
+        """Device-resident raw frames [n][rawDim] -> d_out [n][outputDimension], enqueued on ``stream``; ``segStarts``
+        (first 0, ascending) cuts the frames into utterances with edges of their own."""
+        seg = None
+        if segStarts is not None:
+            seg = np.ascontiguousarray(list(segStarts), dtype=np.int32)
+        _check(lib().fdnn_calculate_raw_device(self.nativeDnnHandle, C.c_void_p(d_raw), int(n), seg.ctypes.data_as(_c_i32p) if seg is not None else None,
+                                               int(seg.size) if seg is not None else 0, C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def calculateLazyRaw(self, raw, bits, out=None) -> np.ndarray:
+        """``calculateLazy(bits=...)`` on raw frames (one call, rows back compacted)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError(f"raw frames must be [n][rawDim], got {r.shape}")
+        n, O = r.shape[0], self.outputDimension()
+        b = np.ascontiguousarray(bits, dtype=np.uint64)
+        if b.shape != (n, (O + 63) // 64):
+            raise ValueError("bits must be [frames][ceil(outputDimension / 64)] uint64")
+        if out is None:
+            out = np.empty((n, O), dtype=np.float32)
+        _check(lib().fdnn_calculate_lazy_bits_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), n, r.shape[1], C.c_void_p(b.ctypes.data),
+                                                  out.ctypes.data_as(_c_f32p)))
+        return out
+
+    def newStream(self, maxChunk: int) -> SpliceStream:
+        """A stream of raw frames, pushed in chunks of at most ``maxChunk`` frames (``SpliceStream``)."""
+        return SpliceStream(self, maxChunk)
 
     # -- lazy path ----------------------------------------------------------
     def getNewLazyContext(self, inputVectorCount: int, batchSize: int = 8) -> LazyContext:

@@ -10,6 +10,8 @@ produce the files the native half reads:
 * ``load_feature_text``        <- ``BatchData.loadMultipleFromText`` (src/java/suskun/nn/BatchData.java:141-180)
 * ``align_features`` / ``feature_matrix_bytes`` <- ``BatchData.alignDimension`` (:92-97) and
                                   ``serializeDataMatrix`` (:100-139)
+* ``load_splice_offsets`` / ``splice_frames`` <- the ``<Splice>`` block the reference reads and drops
+                                  (FeedForwardNetwork.java:97-100): what its callers do on the host, defined here once
 
 The ``.bin`` writers themselves live in ``formats.py``.  No JDK exists in this image, so the
 Java code cannot be run here: the feature-text path is pinned byte-for-byte against the
@@ -116,6 +118,39 @@ def load_feature_transform_text(path: str) -> Tuple[np.ndarray, np.ndarray]:
     if len(blocks) != 2:
         raise ValueError(f"Unexpected feature transformation vector size : {len(blocks)}")
     return _floats(blocks[0]), _floats(blocks[1])
+
+
+def load_splice_offsets(transform_path: str):
+    """The frame offsets of the transform's ``<Splice>`` block (read from its bracket: the header's numbers are
+    dimensions), or ``None`` when it has none.  ``load_feature_transform_text`` drops the block, as the reference does."""
+    with open(transform_path, "r", encoding="utf-8") as fh:
+        whole = fh.read()
+    at = whole.find("<Splice>")
+    if at < 0:
+        return None
+    m = _BLOCK.search(whole, at)
+    if m is None:
+        raise ValueError(f"{transform_path}: <Splice> without a [ ... ] block")
+    return [int(t) for t in m.group(1).split()]
+
+
+def splice_frames(raw: np.ndarray, offsets, width: int, stream: bool = False) -> np.ndarray:
+    """The host definition of splicing: row t is ``raw[f(t + o)]`` for every offset o, side by side, then zeros up to
+    ``width`` (``BatchData.alignDimension``); f clamps to the first and last frame (Kaldi's edge rule).  ``stream=True``
+    returns only the rows whose right context has arrived (t + max(o, 0) < n), as a stream emits them before its end."""
+    raw = np.asarray(raw, dtype=np.float32)
+    if raw.ndim != 2:
+        raise ValueError(f"raw frames must be [n][dim], got {raw.shape}")
+    offs = np.asarray(list(offsets), dtype=np.int64)
+    n, d = raw.shape
+    if offs.size == 0 or offs.size * d > width:
+        raise ValueError(f"{offs.size} x {d} spliced values do not fit a width of {width}")
+    rows = max(0, n - max(int(offs.max()), 0)) if stream else n
+    out = np.zeros((rows, width), dtype=np.float32)
+    if rows:
+        idx = np.clip(np.arange(rows)[:, None] + offs[None, :], 0, n - 1)
+        out[:, : offs.size * d] = raw[idx].reshape(rows, offs.size * d)
+    return out
 
 
 def load_kaldi_nnet_text(network_path: str, transform_path: str) -> FloatNet:

@@ -240,6 +240,73 @@ int calculate_on_one_device(fdnn_model *m, const float *x, int n, int dim, int b
 
 }  // namespace fdnn
 
+namespace {
+
+// Rows [0, n) of one call over the group: score(replica, a, b) scores rows [a, b) on that replica.
+int group_run(fdnn_group *g, int n, const std::function<int(fdnn_model *, int, int)> &score) {
+  fdnn_model *leader = g->models[0];
+  const int world = int(g->models.size());
+  // small call: whole, on one replica (round robin), on the caller's thread
+  if (world == 1 || n < g->split_min) {
+    const unsigned r = world == 1 ? 0u : g->next_replica.fetch_add(1, std::memory_order_relaxed) % unsigned(world);
+    fdnn_model *m = g->models[r];
+    m->l0_fma = leader->l0_fma;  // one numeric flavour per group
+    return score(m, 0, n);
+  }
+  // large call: contiguous shards over as many replicas as keep a shard at shard_min frames or more, each on its
+  // device's persistent worker; the caller waits
+  const int use = std::max(1, std::min(world, n / std::max(1, g->shard_min)));
+  start_workers(g);
+  const unsigned first = g->next_replica.fetch_add(unsigned(use), std::memory_order_relaxed);
+  std::vector<int> rcs(size_t(use), FDNN_OK);
+  std::vector<std::string> msgs(static_cast<size_t>(use));
+  std::mutex done_mu;
+  std::condition_variable done_cv;
+  int left = use;
+  for (int k = 0; k < use; ++k) {
+    const int r = int((first + unsigned(k)) % unsigned(world));
+    int a, b;
+    fdnn::frame_shard(n, use, k, &a, &b);
+    GroupWorker *w = g->workers[size_t(r)];
+    auto job = [&, k, r, a, b] {
+      if (b > a) {
+        fdnn_model *m = g->models[size_t(r)];
+        m->l0_fma = leader->l0_fma;
+        rcs[size_t(k)] = score(m, a, b);
+        if (rcs[size_t(k)]) msgs[size_t(k)] = fdnn_last_error();  // thread-local: carry it to the caller
+      }
+      std::lock_guard<std::mutex> lk(done_mu);
+      if (--left == 0) done_cv.notify_all();
+    };
+    {
+      std::lock_guard<std::mutex> lk(w->mu);
+      w->jobs.emplace_back(job);
+    }
+    w->cv.notify_one();
+  }
+  {
+    std::unique_lock<std::mutex> lk(done_mu);
+    done_cv.wait(lk, [&] { return left == 0; });
+  }
+  for (int k = 0; k < use; ++k)
+    if (rcs[size_t(k)])
+      return fail(rcs[size_t(k)], "device " + std::to_string(g->devices[size_t((first + unsigned(k)) % unsigned(world))]) + ": " + msgs[size_t(k)]);
+  return FDNN_OK;
+}
+
+}  // namespace
+
+namespace fdnn {
+
+// fdnn_calculate_raw on an attached group: each replica uploads only the raw frames its shard references (shard + halo),
+// spliced by the leader's spec (whatever a replica holds itself)
+int group_calculate_raw(fdnn_group *g, const SpliceRef &spec, const float *raw, int n, float *out) {
+  const size_t O = size_t(g->models[0]->hm.hdr.out_dim);
+  return group_run(g, n, [&](fdnn_model *m, int a, int b) { return calculate_raw_rows(m, spec, raw, n, a, b, out + size_t(a) * O); });
+}
+
+}  // namespace fdnn
+
 extern "C" {
 
 int fdnn_group_load(const char *path, float cutoff, const int *devices, int n_devices, fdnn_group **out) {
@@ -344,53 +411,9 @@ int fdnn_group_calculate(fdnn_group *g, const float *x, int n, int dim, int batc
   const int D = leader->hm.hdr.in_dim, O = leader->hm.hdr.out_dim;
   if (dim != D)
     return fail(FDNN_E_ARG, "input vector size " + std::to_string(dim) + " must be equal with network input size " + std::to_string(D));
-  const int world = int(g->models.size());
-  // small call: whole, on one replica (round robin), on the caller's thread
-  if (world == 1 || n < g->split_min) {
-    const unsigned r = world == 1 ? 0u : g->next_replica.fetch_add(1, std::memory_order_relaxed) % unsigned(world);
-    fdnn_model *m = g->models[r];
-    m->l0_fma = leader->l0_fma;  // one numeric flavour per group
-    return fdnn::calculate_on_one_device(m, x, n, dim, batch_hint, out);
-  }
-  // large call: contiguous shards over as many replicas as keep a shard at shard_min frames or more, each on its
-  // device's persistent worker; the caller waits
-  const int use = std::max(1, std::min(world, n / std::max(1, g->shard_min)));
-  start_workers(g);
-  const unsigned first = g->next_replica.fetch_add(unsigned(use), std::memory_order_relaxed);
-  std::vector<int> rcs(size_t(use), FDNN_OK);
-  std::vector<std::string> msgs(static_cast<size_t>(use));
-  std::mutex done_mu;
-  std::condition_variable done_cv;
-  int left = use;
-  for (int k = 0; k < use; ++k) {
-    const int r = int((first + unsigned(k)) % unsigned(world));
-    int a, b;
-    fdnn::frame_shard(n, use, k, &a, &b);
-    GroupWorker *w = g->workers[size_t(r)];
-    auto job = [&, k, r, a, b] {
-      if (b > a) {
-        fdnn_model *m = g->models[size_t(r)];
-        m->l0_fma = leader->l0_fma;
-        rcs[size_t(k)] = fdnn::calculate_on_one_device(m, x + size_t(a) * D, b - a, dim, batch_hint, out + size_t(a) * O);
-        if (rcs[size_t(k)]) msgs[size_t(k)] = fdnn_last_error();  // thread-local: carry it to the caller
-      }
-      std::lock_guard<std::mutex> lk(done_mu);
-      if (--left == 0) done_cv.notify_all();
-    };
-    {
-      std::lock_guard<std::mutex> lk(w->mu);
-      w->jobs.emplace_back(job);
-    }
-    w->cv.notify_one();
-  }
-  {
-    std::unique_lock<std::mutex> lk(done_mu);
-    done_cv.wait(lk, [&] { return left == 0; });
-  }
-  for (int k = 0; k < use; ++k)
-    if (rcs[size_t(k)])
-      return fail(rcs[size_t(k)], "device " + std::to_string(g->devices[size_t((first + unsigned(k)) % unsigned(world))]) + ": " + msgs[size_t(k)]);
-  return FDNN_OK;
+  return group_run(g, n, [&](fdnn_model *m, int a, int b) {
+    return fdnn::calculate_on_one_device(m, x + size_t(a) * D, b - a, dim, batch_hint, out + size_t(a) * O);
+  });
 }
 
 // Where the worker thread of replica `index` pinned itself ("" = no worker yet / not pinned).  Diagnostics.
@@ -413,6 +436,7 @@ void fdnn_group_shard(int n, int world, int rank, int *start, int *stop) {
 int fdnn_group_attach(fdnn_group *g) {
   if (!g) return fail(FDNN_E_ARG, "null group");
   g->models[0]->group = g;  // fdnn_calculate(leader, ...) now shards over the group; fdnn_model_free(leader) frees it
+  for (fdnn_model *m : g->models) m->splice = g->models[0]->splice;  // (a spec set on the leader before it led the group)
   return FDNN_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -38,6 +39,15 @@ struct DeviceGuard {
   }
 };
 
+// A splice spec (fdnn_model_set_splice): the <Splice> frame offsets and the raw frame width D.  Immutable once made: the
+// model holds the current one, and every raw call, stream and queued server submission holds the one it started with.
+struct SpliceSpec {
+  std::vector<int> offsets;
+  int raw_dim = 0;
+  int left = 0, right = 0;  // max(-o, 0), max(o, 0): the context a row reads before and after its own frame
+};
+using SpliceRef = std::shared_ptr<const SpliceSpec>;
+
 }  // namespace fdnn
 
 struct fdnn_model {
@@ -59,6 +69,7 @@ struct fdnn_model {
   int l0_fma = 0;
   int l0_kernel = 0;  // fdnn_debug_set_l0_kernel
   int l0_list_cap = 0;  // fdnn_debug_set_l0_list_cap: > 0 caps the flagged-output list of contexts created afterwards (tests)
+  fdnn::SpliceRef splice;  // fdnn_model_set_splice (null = no spec: the raw entry points refuse)
   std::mutex mu;
   std::vector<fdnn_ctx *> pool;  // idle contexts owned by the model (fdnn_calculate*)
   struct fdnn_server *batcher = nullptr;  // fdnn_model_enable_batcher: fdnn_calculate goes through it
@@ -85,6 +96,8 @@ struct fdnn_ctx {
                                   // stream_is_durable) -- after the last record: recorded when ANOTHER stream asks (ctx_enter)
   hipStream_t durable[3] = {nullptr, nullptr, nullptr};  // streams of the context's owner (the scoring loop's), besides `stream`
   float *d_x = nullptr;           // [n][D]
+  float *d_raw = nullptr;         // raw feature frames of the *_raw entry points (first raw call allocates)
+  size_t raw_cap = 0;             // ... floats
   float *d_xt = nullptr;          // [4][l0_j_pad][xt_ld] layer-0 frame image (shifted, scaled, chain-major)
   int xt_ld = 0;
   float *d_l0park = nullptr;      // [xt_ld][l0_h_ld] partial chain sums parked by the layer-0 kernel
@@ -179,6 +192,33 @@ constexpr int kChunkTailSplit = 2048;
 // kChunkTailSplit frames past a whole round away as a batch of their own.  Without: as assume_chained says.
 std::vector<std::pair<int, int>> frame_chunks(int n, const fdnn_model *m = nullptr, bool assume_chained = true);
 bool hidden_layers_chain(const fdnn_model *m, int n);
+// ---------------------------------------------------------------- raw feature frames (fdnn_splice.hip)
+// A run of rows of one utterance: rows [row, next segment's row) read raw frames clamp(center + (t - row) + o, lo, hi) of the
+// raw buffer (lo / hi: the buffer indices of the utterance's first and last frame).
+struct SpliceSeg {
+  int row, center, lo, hi;
+};
+// FDNN_E_STATE without a spec, FDNN_E_ARG when raw_dim is not its D (raw_dim < 0: any)
+int splice_check(const SpliceRef &spec, int raw_dim);
+// Room for `frames` raw frames of width raw_dim (c->d_raw) and, on a lean context, the frame buffer c->d_x; allocated on
+// the first raw call.
+int ctx_raw_reserve(fdnn_ctx *c, size_t frames, int raw_dim);
+// Splices rows [row0, row0 + rows) into d_x [rows][input_dim] (row row0 first) from raw [raw_frames][spec.raw_dim]; segs
+// ascending by row, the first at or before row0.  Tables longer than one launch's go as several launches.
+void splice_rows(const SpliceSpec &spec, int input_dim, const float *raw, int raw_frames, const std::vector<SpliceSeg> &segs,
+                 int row0, int rows, float *d_x, hipStream_t s);
+// The raw frames rows [a, b) of an n-frame utterance reference: [*fa, *fb) (the halo of the offsets, clamped to it).
+void splice_halo(const SpliceSpec &spec, int n, int a, int b, int *fa, int *fb);
+// Rows [a, b) of one n-frame utterance (host raw frames) into out[b - a][O], spliced by `spec`: through the model's batcher
+// when it has one, else the raw frames those rows reference travel once and are spliced and scored chunk by chunk.
+// fdnn_calculate_raw on one device, and a group replica's shard.
+int calculate_raw_rows(fdnn_model *m, const SpliceRef &spec, const float *raw, int n, int a, int b, float *out);
+int group_calculate_raw(fdnn_group *g, const SpliceRef &spec, const float *raw, int n, float *out);  // fdnn_group.cpp
+// Rows [a, b) of an n-frame raw utterance through the scoring loop (fdnn_server.cpp); bits (may be null) and out hold
+// those rows only.
+int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *raw, int n, int a, int b, const uint64_t *bits,
+                           float *out, uint64_t *ticket);
+
 // Ordering between the streams a context is used on.  An event record costs 3-4 us of queue time behind the kernel it
 // follows, so a context whose work went to a stream that is certain to exist later -- its own, its owner's, or the null
 // stream -- only NOTES that (done_pending); the record is made when a different stream next needs the order (ctx_enter),

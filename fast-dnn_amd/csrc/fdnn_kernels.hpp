@@ -212,4 +212,17 @@ void launch_fastdiv_check(float coef, float rcp, unsigned long long *d_mismatch,
 // s8 <-> u8 view of activations for taps / read-back.
 void launch_xor80(const int8_t *in, uint8_t *out, size_t count, hipStream_t s);
 
+// Splicing raw feature frames into rows (fdnn_splice.hip).  Passed by value: the offsets and the launch's segment table are
+// kernel arguments (1.8 KB).  Segment g covers rows [seg_row[g], seg_row[g + 1]); its row t reads the raw frames
+// clamp(seg_center[g] + (t - seg_row[g]) + o, seg_lo[g], seg_hi[g]) of the raw buffer, one per offset o.
+constexpr int kSpliceMaxOffsets = 64;
+constexpr int kSpliceMaxSegs = 96;  // per launch: longer tables go as several launches
+struct SpliceArgs {
+  int offsets[kSpliceMaxOffsets];
+  int count, raw_dim, input_dim, n_segs;
+  int seg_row[kSpliceMaxSegs], seg_center[kSpliceMaxSegs], seg_lo[kSpliceMaxSegs], seg_hi[kSpliceMaxSegs];
+};
+// rows [row0, row0 + rows) into x[rows][input_dim] (x holds row row0 first); raw [raw_frames][raw_dim]
+void launch_splice(const float *raw, int raw_frames, float *x, int row0, int rows, const SpliceArgs &a, hipStream_t s);
+
 }  // namespace fdnn

@@ -162,6 +162,7 @@ void destroy_ctx(fdnn_ctx *c) {
     hipStreamSynchronize(c->stream);
   }
   hipFree(c->d_x);
+  hipFree(c->d_raw);
   hipFree(c->d_xt);
   hipFree(c->d_l0park);
   hipFree(c->d_scr_count);
@@ -897,6 +898,40 @@ void release_ctx(fdnn_ctx *c, hipStream_t s) {
   }
 }
 
+// The dense pass over the context's frames in c->d_x (c->n of them) into the host's `out`, synchronising s.
+static int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
+  fdnn_model *m = c->m;
+  const int n = c->n;
+  const size_t O = size_t(m->hm.hdr.out_dim);
+  const unsigned long long unwritten_before = m->h_fuse_fault ? __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) >> 32 : 0ull;
+  int rc = run_hidden(c, c->d_x, s, nullptr);
+  if (!rc) rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
+  if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
+  if (rc) hipStreamSynchronize(s);
+  // copy_out has synchronised: did a fused soft-max workgroup of THIS pass sit out its bounded wait?  fdnn_gemm.hip's
+  // tiles finish such a frame tile after the fact, fdnn_ppo.hip's leave the half's rows unwritten (and say so through the
+  // same word): the output layer runs again -- unfused now, model_may_fuse has seen the word -- over the activations that
+  // are still in the context.  (The word's upper half counts such halves.  Callers of the *_device entry points observe
+  // fdnn_model_fuse_giveups after their own synchronisation: INTEGRATION.md.)
+  if (!rc && m->h_fuse_fault && (__atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) >> 32) != unwritten_before) {
+    const bool saved = c->no_fuse;
+    c->no_fuse = true;  // (whatever FDNN_FUSE_NORM says)
+    rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
+    c->no_fuse = saved;
+    if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
+    if (rc) hipStreamSynchronize(s);
+  }
+  // copy_out has synchronised: did this pass's chained launch run into its wait bound?  Then what it computed on may not have
+  // been written -- run the pass again, layer by layer (run_hidden sees the flag, re-zeroes the counters, stops chaining)
+  if (!rc && c->h_chain_fault && __atomic_load_n(c->h_chain_fault, __ATOMIC_RELAXED) != 0 && !c->chain_broken) {
+    rc = run_hidden(c, c->d_x, s, nullptr);
+    if (!rc) rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
+    if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
+    if (rc) hipStreamSynchronize(s);
+  }
+  return rc;
+}
+
 // fdnn_calculate on the model's own device (the group path calls this per shard).
 int calculate_on_one_device(fdnn_model *m, const float *x, int n, int dim, int batch_hint, float *out) {
   (void)batch_hint;
@@ -920,37 +955,102 @@ int calculate_on_one_device(fdnn_model *m, const float *x, int n, int dim, int b
   hipStream_t s = c->stream;
   hipError_t e = ctx_enter(c, s);
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x, sizeof(float) * size_t(n) * dim, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    const unsigned long long unwritten_before = m->h_fuse_fault ? __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) >> 32 : 0ull;
-    rc = run_hidden(c, c->d_x, s, nullptr);
-    if (!rc) rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
-    if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * h.out_dim, s);
-    if (rc) hipStreamSynchronize(s);
-    // copy_out has synchronised: did a fused soft-max workgroup of THIS pass sit out its bounded wait?  fdnn_gemm.hip's
-    // tiles finish such a frame tile after the fact, fdnn_ppo.hip's leave the half's rows unwritten (and say so through the
-    // same word): the output layer runs again -- unfused now, model_may_fuse has seen the word -- over the activations that
-    // are still in the context.  (The word's upper half counts such halves.  Callers of the *_device entry points observe
-    // fdnn_model_fuse_giveups after their own synchronisation: INTEGRATION.md.)
-    if (!rc && m->h_fuse_fault && (__atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) >> 32) != unwritten_before) {
-      const bool saved = c->no_fuse;
-      c->no_fuse = true;  // (whatever FDNN_FUSE_NORM says)
-      rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
-      c->no_fuse = saved;
-      if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * h.out_dim, s);
-      if (rc) hipStreamSynchronize(s);
-    }
-    // copy_out has synchronised: did this pass's chained launch run into its wait bound?  Then what it computed on may not have
-    // been written -- run the pass again, layer by layer (run_hidden sees the flag, re-zeroes the counters, stops chaining)
-    if (!rc && c->h_chain_fault && __atomic_load_n(c->h_chain_fault, __ATOMIC_RELAXED) != 0 && !c->chain_broken) {
-      rc = run_hidden(c, c->d_x, s, nullptr);
-      if (!rc) rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
-      if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * h.out_dim, s);
-      if (rc) hipStreamSynchronize(s);
-    }
-  }
+  if (e == hipSuccess) rc = dense_pass_to_host(c, out, s);
   release_ctx(c, s);
   if (rc) return rc;
   if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate: ") + hipGetErrorString(e));
+  return FDNN_OK;
+}
+
+// ---------------------------------------------------------------- raw feature frames
+int splice_check(const SpliceRef &spec, int raw_dim) {
+  if (!spec) return fail(FDNN_E_STATE, "no splice spec set (fdnn_model_set_splice)");
+  if (raw_dim >= 0 && raw_dim != spec->raw_dim)
+    return fail(FDNN_E_ARG, "raw frame width " + std::to_string(raw_dim) + " is not the splice spec's " + std::to_string(spec->raw_dim));
+  return FDNN_OK;
+}
+
+int ctx_raw_reserve(fdnn_ctx *c, size_t frames, int raw_dim) {
+  const fdnn_model *m = c->m;
+  if (!c->d_x) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_x), sizeof(float) * size_t(c->cap) * m->hm.hdr.in_dim));
+  const size_t D = size_t(raw_dim);  // (a pooled context's last raw call may have had another width)
+  if (c->raw_cap < frames * D) {
+    if (c->d_raw) HIP_TRY(hipFree(c->d_raw));  // (the context's earlier work is ordered before: callers hold it)
+    c->d_raw = nullptr;
+    c->raw_cap = 0;
+    const size_t cap = std::max(frames, size_t(c->cap)) * D;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_raw), sizeof(float) * cap));
+    c->raw_cap = cap;
+  }
+  return FDNN_OK;
+}
+
+void splice_halo(const SpliceSpec &spec, int n, int a, int b, int *fa, int *fb) {
+  *fa = std::max(0, a - spec.left);
+  *fb = std::min(n, b + spec.right);
+}
+
+void splice_rows(const SpliceSpec &spec, int input_dim, const float *raw, int raw_frames, const std::vector<SpliceSeg> &segs,
+                 int row0, int rows, float *d_x, hipStream_t s) {
+  fdnn::SpliceArgs a{};
+  a.count = int(spec.offsets.size());
+  a.raw_dim = spec.raw_dim;
+  a.input_dim = input_dim;
+  std::copy(spec.offsets.begin(), spec.offsets.end(), a.offsets);
+  // the segment holding row0, then launch by launch up to kSpliceMaxSegs segments each
+  size_t g = size_t(std::upper_bound(segs.begin(), segs.end(), row0, [](int r, const SpliceSeg &sg) { return r < sg.row; }) - segs.begin());
+  g = g ? g - 1 : 0;
+  const int end = row0 + rows;
+  int r = row0;
+  while (r < end && g < segs.size()) {
+    a.n_segs = 0;
+    for (size_t k = g; k < segs.size() && a.n_segs < fdnn::kSpliceMaxSegs && (k == g || segs[k].row < end); ++k) {
+      a.seg_row[a.n_segs] = segs[k].row;
+      a.seg_center[a.n_segs] = segs[k].center;
+      a.seg_lo[a.n_segs] = segs[k].lo;
+      a.seg_hi[a.n_segs] = segs[k].hi;
+      ++a.n_segs;
+    }
+    const size_t next = g + size_t(a.n_segs);
+    const int stop = next < segs.size() ? std::min(end, segs[next].row) : end;
+    fdnn::launch_splice(raw, raw_frames, d_x + size_t(r - row0) * a.input_dim, r, stop - r, a, s);
+    r = stop;
+    g = next;
+  }
+}
+
+int calculate_raw_rows(fdnn_model *m, const SpliceRef &spec, const float *raw, int n, int a, int b, float *out) {
+  if (b <= a) return FDNN_OK;
+  if (m->batcher) {  // coalesced with the other callers' raw utterances (fdnn_server.cpp), each with its own edges
+    uint64_t ticket = 0;
+    int rc = server_submit_raw_rows(m->batcher, spec, raw, n, a, b, nullptr, out, &ticket);
+    if (!rc) rc = fdnn_server_wait(m->batcher, ticket);
+    return rc;
+  }
+  DeviceGuard g(m->device);
+  const size_t D = size_t(spec->raw_dim), O = size_t(m->hm.hdr.out_dim);
+  int fa, fb;
+  splice_halo(*spec, n, a, b, &fa, &fb);
+  const std::vector<SpliceSeg> segs{SpliceSeg{a, a - fa, -fa, n - 1 - fa}};
+  const auto chunks = frame_chunks(b - a, m);
+  int cap = 0;  // the scratch only has to hold the largest chunk
+  for (const auto &ch : chunks) cap = std::max(cap, ch.second);
+  fdnn_ctx *c = nullptr;
+  int rc = acquire_ctx(m, cap, &c);
+  if (rc) return rc;
+  hipStream_t s = c->stream;
+  hipError_t e = ctx_enter(c, s);
+  if (e == hipSuccess) rc = ctx_raw_reserve(c, size_t(fb - fa), spec->raw_dim);
+  // the raw frames travel once; every chunk splices its rows from them
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(c->d_raw, raw + size_t(fa) * D, sizeof(float) * size_t(fb - fa) * D, hipMemcpyHostToDevice, s);
+  for (size_t i = 0; e == hipSuccess && !rc && i < chunks.size(); ++i) {
+    c->n = chunks[i].second;
+    splice_rows(*spec, m->hm.hdr.in_dim, c->d_raw, fb - fa, segs, a + chunks[i].first, c->n, c->d_x, s);
+    rc = dense_pass_to_host(c, out + size_t(chunks[i].first) * O, s);
+  }
+  release_ctx(c, s);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate_raw: ") + hipGetErrorString(e));
   return FDNN_OK;
 }
 
@@ -1594,6 +1694,289 @@ int fdnn_calculate_lazy_bits_device(fdnn_model *m, const float *d_x, int n, cons
   release_ctx(c, s);
   if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate_lazy_bits_device: ") + hipGetErrorString(e));
   return rc;
+}
+
+// ---------------------------------------------------------------- raw feature frames (the <Splice> block on the device)
+int fdnn_model_set_splice(fdnn_model *m, const int *offsets, int count, int raw_dim) {
+  if (!m) return fail(FDNN_E_ARG, "null model");
+  fdnn::SpliceRef spec;  // (a new object: streams, queued submissions and calls in progress keep the one they hold)
+  if (count != 0 || raw_dim != 0) {  // (count == 0 with raw_dim == 0 clears the spec; an empty spec of some width is an error)
+    if (count < 1 || count > fdnn::kSpliceMaxOffsets) return fail(FDNN_E_ARG, "a splice spec has 1 .. 64 offsets");
+    if (!offsets) return fail(FDNN_E_ARG, "null offsets");
+    for (int i = 0; i < count; ++i)
+      if (offsets[i] < -64 || offsets[i] > 64) return fail(FDNN_E_ARG, "splice offsets must lie in -64 .. 64");
+    const int in_dim = m->hm.hdr.in_dim;
+    if (raw_dim < 1 || (long long)count * raw_dim > in_dim)
+      return fail(FDNN_E_ARG, std::to_string(count) + " x " + std::to_string(raw_dim) + " spliced values do not fit the input width " +
+                                  std::to_string(in_dim));
+    auto sp = std::make_shared<fdnn::SpliceSpec>();
+    sp->offsets.assign(offsets, offsets + count);
+    sp->raw_dim = raw_dim;
+    for (int o : sp->offsets) {
+      sp->left = std::max(sp->left, -o);
+      sp->right = std::max(sp->right, o);
+    }
+    spec = sp;
+  }
+  // one spec for the whole group when the model leads one (the replicas score its shards; fdnn_group_attach copies the
+  // leader's spec to them as well, and a sharded call hands every replica the leader's)
+  const int replicas = m->group ? fdnn_group_size(m->group) : 1;
+  for (int r = 0; r < replicas; ++r) (m->group ? fdnn_group_model(m->group, r) : m)->splice = spec;
+  return FDNN_OK;
+}
+
+int fdnn_model_get_splice(const fdnn_model *m, int *offsets, int cap, int *raw_dim) {
+  if (!m || cap < 0 || (cap > 0 && !offsets)) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  const int count = spec ? int(spec->offsets.size()) : 0;
+  for (int i = 0; i < cap && i < count; ++i) offsets[i] = spec->offsets[size_t(i)];
+  if (raw_dim) *raw_dim = spec ? spec->raw_dim : 0;
+  return count;
+}
+
+int fdnn_calculate_raw(fdnn_model *m, const float *raw, int n, int raw_dim, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  int rc = fdnn::splice_check(spec, raw_dim);
+  if (rc) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
+  // as fdnn_calculate: sharded over an attached group first (each replica uploads its shard + halo, through its own batcher
+  // when it has one), else through the model's batcher, else on the model's device
+  if (m->group) return fdnn::group_calculate_raw(m->group, spec, raw, n, out);
+  return fdnn::calculate_raw_rows(m, spec, raw, n, 0, n, out);
+}
+
+int fdnn_calculate_raw_device(fdnn_model *m, const float *d_raw, int n, const int *seg_starts, int n_segs, float *d_out, void *stream) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  int rc = fdnn::splice_check(spec, -1);
+  if (rc) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!d_raw || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  std::vector<fdnn::SpliceSeg> segs;
+  if (!seg_starts) {
+    segs.push_back(fdnn::SpliceSeg{0, 0, 0, n - 1});
+  } else {
+    if (n_segs < 1 || seg_starts[0] != 0) return fail(FDNN_E_ARG, "a segment table starts with 0");
+    for (int k = 0; k < n_segs; ++k) {
+      const int a = seg_starts[k], b = k + 1 < n_segs ? seg_starts[k + 1] : n;
+      if (b <= a || b > n) return fail(FDNN_E_ARG, "segment starts must ascend strictly and lie below n");
+      segs.push_back(fdnn::SpliceSeg{a, a, a, b - 1});
+    }
+  }
+  DeviceGuard g(m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  fdnn_ctx *c = nullptr;
+  const auto chunks = fdnn::frame_chunks(n, m);
+  int cap = 0;
+  for (const auto &ch : chunks) cap = std::max(cap, ch.second);
+  rc = acquire_ctx(m, cap, &c);
+  if (rc) return rc;
+  const hipError_t e = ctx_enter(c, s);
+  if (e == hipSuccess) {
+    const size_t O = size_t(m->hm.hdr.out_dim);
+    for (const auto &ch : chunks) {  // each chunk's rows spliced into the context's frame buffer, then scored as usual
+      c->n = ch.second;
+      fdnn::splice_rows(*spec, m->hm.hdr.in_dim, d_raw, n, segs, ch.first, ch.second, c->d_x, s);
+      rc = run_hidden(c, c->d_x, s, nullptr);
+      if (!rc) rc = run_output(c, 0, ch.second, nullptr, d_out + size_t(ch.first) * O, s, nullptr);
+      if (rc) break;
+    }
+  }
+  release_ctx(c, s);
+  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate_raw_device: ") + hipGetErrorString(e));
+  return rc;
+}
+
+int fdnn_calculate_lazy_bits_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const uint64_t *bits, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  int rc = fdnn::splice_check(spec, raw_dim);
+  if (rc) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!raw || !out || !bits) return fail(FDNN_E_ARG, "null buffer");
+  if (m->batcher) {
+    uint64_t ticket = 0;
+    rc = fdnn::server_submit_raw_rows(m->batcher, spec, raw, n, 0, n, bits, out, &ticket);
+    if (!rc) rc = fdnn_server_wait(m->batcher, ticket);
+    return rc;
+  }
+  DeviceGuard g(m->device);
+  const size_t O = size_t(m->hm.hdr.out_dim), wpr = (O + 63) / 64, D = size_t(raw_dim);
+  const std::vector<fdnn::SpliceSeg> segs{fdnn::SpliceSeg{0, 0, 0, n - 1}};
+  fdnn_ctx *c = nullptr;
+  rc = acquire_ctx(m, std::min(n, fdnn::kChunkFrames), &c);
+  if (rc) return rc;
+  hipStream_t s = c->stream;
+  hipError_t e = ctx_enter(c, s);
+  if (e == hipSuccess) rc = fdnn::ctx_raw_reserve(c, size_t(n), raw_dim);
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(c->d_raw, raw, sizeof(float) * size_t(n) * D, hipMemcpyHostToDevice, s);
+  for (int first = 0; first < n && e == hipSuccess && !rc; first += fdnn::kChunkFrames) {  // (chunks as fdnn_calculate_lazy_bits)
+    const int cnt = std::min(fdnn::kChunkFrames, n - first);
+    c->n = cnt;
+    fdnn::splice_rows(*spec, m->hm.hdr.in_dim, c->d_raw, n, segs, first, cnt, c->d_x, s);
+    e = hipMemcpyAsync(c->d_mask_bits, bits + size_t(first) * wpr, sizeof(uint64_t) * size_t(cnt) * wpr, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) break;
+    rc = run_hidden(c, c->d_x, s, nullptr);
+    if (!rc) rc = run_output(c, 0, cnt, nullptr, c->d_out, s, nullptr, nullptr, nullptr, nullptr, c->d_mask_bits);
+    if (!rc) rc = lazy_copy_out(c, cnt, c->d_mask_bits, bits + size_t(first) * wpr, out + size_t(first) * O, s);
+    if (rc) hipStreamSynchronize(s);
+  }
+  release_ctx(c, s);
+  if (!rc && e != hipSuccess) rc = fail(FDNN_E_DEVICE, std::string("fdnn_calculate_lazy_bits_raw: ") + hipGetErrorString(e));
+  return rc;
+}
+
+int fdnn_ctx_forward_hidden_raw(fdnn_ctx *c, const float *raw) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  const fdnn::SpliceRef spec = c->m->splice;
+  int rc = fdnn::splice_check(spec, -1);
+  if (rc) return rc;
+  if (c->n == 0) {
+    c->last = 0;
+    return FDNN_OK;
+  }
+  if (!raw) return fail(FDNN_E_ARG, "null argument");
+  DeviceGuard g(c->m->device);
+  const size_t D = size_t(spec->raw_dim);
+  HIP_TRY(ctx_enter(c, c->stream));
+  rc = fdnn::ctx_raw_reserve(c, size_t(c->n), spec->raw_dim);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->d_raw, raw, sizeof(float) * size_t(c->n) * D, hipMemcpyHostToDevice, c->stream));
+  fdnn::splice_rows(*spec, c->m->hm.hdr.in_dim, c->d_raw, c->n, {fdnn::SpliceSeg{0, 0, 0, c->n - 1}}, 0, c->n, c->d_x, c->stream);
+  rc = run_hidden(c, c->d_x, c->stream, nullptr);
+  ctx_leave(c, c->stream);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return FDNN_OK;
+}
+
+}  // extern "C"
+
+// A stream of raw frames (fdnn_stream_*).  Its device buffer holds global frames [base, base + len): the frames still to be
+// read by rows not emitted yet -- at most L + R of them between pushes (L / R: the left / right context of the offsets) --
+// and the push's new ones.  Before a push the kept frames move to the front of the other buffer of a pair (device to
+// device, L + R frames): nothing is uploaded twice.
+struct fdnn_stream {
+  fdnn_model *m = nullptr;
+  fdnn_ctx *c = nullptr;  // the stream's own context: max_chunk + R frames
+  fdnn::SpliceRef spec;   // the model's spec when the stream was made: every push splices with it
+  int raw_dim = 0, max_chunk = 0, left = 0, right = 0;
+  float *d_buf[2] = {nullptr, nullptr};
+  int cur = 0;
+  long long base = 0, len = 0, pushed = 0, emitted = 0;
+  bool ended = false;
+};
+
+extern "C" {
+
+int fdnn_stream_create(fdnn_model *m, int max_chunk, fdnn_stream **out) {
+  if (!m || !out) return fail(FDNN_E_ARG, "null argument");
+  *out = nullptr;
+  const fdnn::SpliceRef spec = m->splice;
+  int rc = fdnn::splice_check(spec, -1);
+  if (rc) return rc;
+  if (max_chunk < 1) return fail(FDNN_E_ARG, "max_chunk must be positive");
+  DeviceGuard g(m->device);
+  fdnn_stream *s = new fdnn_stream();
+  s->m = m;
+  s->spec = spec;
+  s->raw_dim = spec->raw_dim;
+  s->max_chunk = max_chunk;
+  s->left = spec->left;
+  s->right = spec->right;
+  rc = fdnn::make_ctx(m, max_chunk + s->right, &s->c);
+  const size_t frames = size_t(max_chunk) + size_t(s->left) + size_t(s->right);
+  for (int k = 0; k < 2 && !rc; ++k)
+    if (hipMalloc(reinterpret_cast<void **>(&s->d_buf[k]), sizeof(float) * frames * size_t(s->raw_dim)) != hipSuccess)
+      rc = fail(FDNN_E_NOMEM, "stream buffer of " + std::to_string(frames) + " raw frames");
+  if (rc) {
+    fdnn_stream_free(s);
+    return rc;
+  }
+  s->c->n = 0;
+  *out = s;
+  return FDNN_OK;
+}
+
+void fdnn_stream_free(fdnn_stream *s) {
+  if (!s) return;
+  DeviceGuard g(s->m->device);
+  if (s->c) fdnn::destroy_ctx(s->c);  // (synchronises the stream's work)
+  hipFree(s->d_buf[0]);
+  hipFree(s->d_buf[1]);
+  delete s;
+}
+
+int fdnn_stream_reset(fdnn_stream *s) {
+  if (!s) return fail(FDNN_E_ARG, "null stream");
+  s->base = s->len = s->pushed = s->emitted = 0;
+  s->ended = false;
+  return FDNN_OK;
+}
+
+int fdnn_stream_position(const fdnn_stream *s, int64_t *pushed, int64_t *emitted) {
+  if (!s) return fail(FDNN_E_ARG, "null stream");
+  if (pushed) *pushed = s->pushed;
+  if (emitted) *emitted = s->emitted;
+  return FDNN_OK;
+}
+
+fdnn_ctx *fdnn_stream_ctx(fdnn_stream *s) { return s ? s->c : nullptr; }
+
+int fdnn_stream_push(fdnn_stream *s, const float *raw, int n_raw, int end, float *out, int *n_out) {
+  if (!s || !n_out) return fail(FDNN_E_ARG, "null argument");
+  *n_out = 0;
+  if (s->ended) return fail(FDNN_E_STATE, "the stream has ended: fdnn_stream_reset starts the next utterance");
+  if (n_raw < 0 || n_raw > s->max_chunk) return fail(FDNN_E_ARG, "a push holds 0 .. max_chunk raw frames");
+  if (n_raw > 0 && !raw) return fail(FDNN_E_ARG, "null raw frames");
+  fdnn_model *m = s->m;
+  fdnn_ctx *c = s->c;
+  DeviceGuard g(m->device);
+  const size_t D = size_t(s->raw_dim);
+  hipStream_t st = c->stream;
+  HIP_TRY(fdnn::ctx_enter(c, st));
+  // keep what rows not emitted yet still read: frames from emitted - L on
+  const long long keep = std::max(s->base, s->emitted - s->left);
+  if (keep > s->base) {
+    const long long kept = s->base + s->len - keep;
+    if (kept > 0)
+      HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur ^ 1], s->d_buf[s->cur] + size_t(keep - s->base) * D, sizeof(float) * size_t(kept) * D,
+                             hipMemcpyDeviceToDevice, st));
+    s->cur ^= 1;
+    s->base = keep;
+    s->len = kept;
+  }
+  if (n_raw > 0)
+    HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur] + size_t(s->len) * D, raw, sizeof(float) * size_t(n_raw) * D, hipMemcpyHostToDevice, st));
+  s->len += n_raw;
+  s->pushed += n_raw;
+  // complete rows: t + R has arrived; at the end of the stream every row, right-clamped to the last frame
+  const long long upto = end ? s->pushed : std::max(s->emitted, s->pushed - s->right);
+  const int rows = int(upto - s->emitted);
+  int rc = FDNN_OK;
+  c->n = rows;
+  c->last = rows ? -1 : 0;
+  if (rows > 0) {
+    const int lo = int(std::max(-s->base, -(1LL << 30)));  // global frame 0 -- the left clamp -- as a buffer index
+    const std::vector<fdnn::SpliceSeg> segs{fdnn::SpliceSeg{0, int(s->emitted - s->base), lo, int(s->pushed - 1 - s->base)}};
+    fdnn::splice_rows(*s->spec, m->hm.hdr.in_dim, s->d_buf[s->cur], int(s->len), segs, 0, rows, c->d_x, st);
+    if (out) {
+      rc = dense_pass_to_host(c, out, st);  // (synchronises)
+    } else {
+      rc = run_hidden(c, c->d_x, st, nullptr);  // hidden layers only: the context's lazy entry points take it from here
+      if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(FDNN_E_DEVICE, "fdnn_stream_push: stream synchronisation");
+    }
+  } else if (hipStreamSynchronize(st) != hipSuccess) {  // (the caller's raw frames have been read when the push returns)
+    rc = fail(FDNN_E_DEVICE, "fdnn_stream_push: stream synchronisation");
+  }
+  fdnn::ctx_leave(c, st);
+  if (rc) return rc;
+  s->emitted = upto;
+  s->ended = end != 0;
+  *n_out = rows;
+  return FDNN_OK;
 }
 
 // ---------------------------------------------------------------- taps

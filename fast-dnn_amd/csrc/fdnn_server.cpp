@@ -73,7 +73,27 @@ struct Request {
   int taken = 0;  // frames already packed into earlier batches
   const uint64_t *bits = nullptr;  // fdnn_server_submit_lazy_bits: [n][ceil(O / 64)] (then masks is null)
   int most = 0;                    // ... and the largest number of active nodes in any of its rows (counted by the submitter)
+  // raw submissions (then x is null): rows [raw_a, raw_a + n) of the raw_n-frame utterance at `raw`, spliced on the device by
+  // the spec the request was submitted with
+  const float *raw = nullptr;
+  fdnn::SpliceRef spec;
+  int raw_n = 0, raw_a = 0;
 };
+
+// The widest row of a bit-mask request, counted on the submitting thread: the batch's compacted row length follows from it.
+int widest_row(const uint64_t *bits, int n, size_t O) {
+  const size_t wpr = (O + 63) / 64;
+  const uint64_t tail_mask = (O & 63) ? ((uint64_t(1) << (O & 63)) - 1) : ~uint64_t(0);
+  int most = 0;
+  for (int f = 0; f < n; ++f) {
+    const uint64_t *row = bits + size_t(f) * wpr;
+    int k = 0;
+    for (size_t w = 0; w + 1 < wpr; ++w) k += __builtin_popcountll(row[w]);
+    k += __builtin_popcountll(row[wpr - 1] & tail_mask);
+    most = std::max(most, k);
+  }
+  return most;
+}
 
 // what a host batch carries: requests of different kinds do not share a batch, except that dense callers may ride in a
 // byte-mask batch (all active)
@@ -99,6 +119,17 @@ struct Slot {
   size_t comp_floats = 0;
   int stride = 0;                 // current batch: floats per compacted row (0: the rows leave whole)
   std::vector<Piece> pieces;
+  // raw batches (one spec per batch): per piece the raw frames it references, staged back to back in h_raw (frames
+  // request), and the batch's segment table (one segment per piece: its own utterance's edges)
+  float *h_raw = nullptr;
+  size_t h_raw_floats = 0;
+  struct RawSrc {
+    int first, count, at;  // frames [first, first + count) of the piece's utterance, at frame `at` of h_raw
+  };
+  std::vector<RawSrc> raw_src;
+  fdnn::SpliceRef spec;
+  std::vector<fdnn::SpliceSeg> segs;
+  int raw_frames = 0;
   int frames = 0;
   int pieces_left = 0;            // pieces of the current host batch not copied out yet
   bool in_flight = false;         // host batch enqueued, not yet scattered
@@ -306,7 +337,13 @@ bool stage_one(fdnn_server *s, std::unique_lock<std::mutex> &lk) {
   lk.unlock();
   const fdnn::BlobHeader &h = s->m->hm.hdr;
   const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64;
-  std::memcpy(sl.h_x + size_t(r0) * D, r.x + size_t(r.taken) * D, sizeof(float) * size_t(r.n) * D);
+  if (r.raw) {
+    const size_t RD = size_t(sl.spec->raw_dim);
+    const Slot::RawSrc src = sl.raw_src[size_t(i)];
+    std::memcpy(sl.h_raw + size_t(src.at) * RD, r.raw + size_t(src.first) * RD, sizeof(float) * size_t(src.count) * RD);
+  } else {
+    std::memcpy(sl.h_x + size_t(r0) * D, r.x + size_t(r.taken) * D, sizeof(float) * size_t(r.n) * D);
+  }
   if (kind == kBits && sl.h_bits) {  // (only bit-mask requests are in such a batch)
     std::memcpy(sl.h_bits + size_t(r0) * wpr, r.bits + size_t(r.taken) * wpr, sizeof(uint64_t) * size_t(r.n) * wpr);
   } else if (any_mask) {
@@ -364,12 +401,18 @@ void packer_loop(fdnn_server *s) {
     // a batch carries bit-mask requests only, or none (dense and byte-mask callers share batches as before: the dense rows
     // of such a batch get all-active masks); a request of the other sort waits for the next batch
     int kind = kDense;
+    bool raw = false;  // a batch carries raw-frame requests only, or none
+    sl.raw_src.clear();
+    sl.segs.clear();
+    int raw_frames = 0;
     while (!s->queue.empty() && rows < s->max_frames) {
       Request &r = s->queue.front();
       const int rk = kind_of(r);
-      if (rows == 0)
+      if (rows == 0) {
         kind = rk;
-      else if ((rk == kBits) != (kind == kBits))
+        raw = r.raw != nullptr;
+        sl.spec = r.spec;
+      } else if ((rk == kBits) != (kind == kBits) || (r.raw != nullptr) != raw || r.spec != sl.spec)
         break;
       else if (rk == kBytes)
         kind = kBytes;
@@ -390,10 +433,19 @@ void packer_loop(fdnn_server *s) {
           if (last) it->second.closed = true;
         }
       }
+      if (raw) {  // the raw frames this piece's rows reference, and where they are staged
+        const int u0 = r.raw_a + part.taken;  // the piece's first row as a frame of its utterance
+        int fa, fb;
+        fdnn::splice_halo(*r.spec, r.raw_n, u0, u0 + take, &fa, &fb);
+        sl.raw_src.push_back(Slot::RawSrc{fa, fb - fa, raw_frames});
+        sl.segs.push_back(fdnn::SpliceSeg{rows, raw_frames + u0 - fa, raw_frames - fa, raw_frames + r.raw_n - 1 - fa});
+        raw_frames += fb - fa;
+      }
       rows += take;
       if (last) s->queue.pop_front();
     }
     sl.frames = rows;
+    sl.raw_frames = raw_frames;
     // compacted return (bit-mask batches): worth it while a row is at most 3/4 active nodes
     const size_t stride = size_t(most) + 1;
     sl.stride = kind == kBits && stride * 4 <= O * 3 ? int(stride) : 0;
@@ -449,6 +501,15 @@ void packer_loop(fdnn_server *s) {
         }
       }
     }
+    const size_t raw_floats = raw ? size_t(raw_frames) * size_t(sl.spec->raw_dim) : 0;
+    if (e == hipSuccess && raw && sl.h_raw_floats < raw_floats) {  // raw staging: grows to the largest raw batch
+      if (sl.h_raw) hipHostFree(sl.h_raw);
+      sl.h_raw = nullptr;
+      sl.h_raw_floats = 0;
+      e = hipHostMalloc(reinterpret_cast<void **>(&sl.h_raw), sizeof(float) * raw_floats, hipHostMallocDefault);
+      if (e == hipSuccess) sl.h_raw_floats = raw_floats;
+    }
+    if (e == hipSuccess && raw && fdnn::ctx_raw_reserve(sl.ctx, size_t(raw_frames), sl.spec->raw_dim)) e = hipErrorOutOfMemory;
     if (e == hipSuccess) {  // the pieces' copies: this thread and whoever is blocked in fdnn_server_wait, piece by piece
       lk.lock();
       s->stage.sl = &sl;
@@ -476,7 +537,13 @@ void packer_loop(fdnn_server *s) {
       std::lock_guard<std::mutex> order(s->mu);  // launch order against device submissions
       fdnn_ctx *c = sl.ctx;
       const bool bits = kind == kBits;
-      e = hipMemcpyAsync(c->d_x, sl.h_x, sizeof(float) * size_t(rows) * D, hipMemcpyHostToDevice, sl.stream);
+      if (raw) {  // only the raw frames cross PCIe; the rows are spliced on the device, each piece within its utterance
+        e = hipMemcpyAsync(c->d_raw, sl.h_raw, sizeof(float) * size_t(sl.raw_frames) * size_t(sl.spec->raw_dim), hipMemcpyHostToDevice,
+                           sl.stream);
+        if (e == hipSuccess) fdnn::splice_rows(*sl.spec, int(D), c->d_raw, sl.raw_frames, sl.segs, 0, rows, c->d_x, sl.stream);
+      } else {
+        e = hipMemcpyAsync(c->d_x, sl.h_x, sizeof(float) * size_t(rows) * D, hipMemcpyHostToDevice, sl.stream);
+      }
       if (e == hipSuccess && bits)
         e = hipMemcpyAsync(c->d_mask_bits, sl.h_bits, sizeof(uint64_t) * size_t(rows) * wpr, hipMemcpyHostToDevice, sl.stream);
       else if (e == hipSuccess && any_mask)
@@ -583,6 +650,42 @@ int start_host_side(fdnn_server *s) {
 
 }  // namespace
 
+namespace fdnn {
+
+int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *raw, int n, int a, int b, const uint64_t *bits,
+                           float *out, uint64_t *ticket) {
+  int rc = splice_check(spec, -1);
+  if (rc) return rc;
+  if (n <= 0 || a < 0 || b > n || b <= a) return fail(FDNN_E_ARG, "frame count must be positive");
+  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
+  rc = start_host_side(s);
+  if (rc) return rc;
+  const int most = bits ? widest_row(bits, b - a, size_t(s->m->hm.hdr.out_dim)) : 0;
+  uint64_t t;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    t = s->next_ticket++;
+  }
+  {
+    std::lock_guard<std::mutex> lk(s->qmu);
+    s->pending.emplace(t, TicketState{});
+    Request r{t, nullptr, nullptr, out, b - a, 0};
+    r.bits = bits;
+    r.most = most;
+    r.raw = raw;
+    r.spec = spec;
+    r.raw_n = n;
+    r.raw_a = a;
+    s->queue.push_back(r);
+  }
+  s->n_requests++;
+  s->qcv.notify_all();
+  *ticket = t;
+  return FDNN_OK;
+}
+
+}  // namespace fdnn
+
 extern "C" {
 
 int fdnn_server_create(fdnn_model *m, int max_frames, int depth, fdnn_server **out) {
@@ -655,6 +758,7 @@ void fdnn_server_free(fdnn_server *s) {
     if (sl.ctx) fdnn::destroy_ctx(sl.ctx);
     if (sl.h_x) hipHostFree(sl.h_x);
     if (sl.h_mask) hipHostFree(sl.h_mask);
+    if (sl.h_raw) hipHostFree(sl.h_raw);
     if (sl.h_bits && sl.h_bits_pageable) std::free(sl.h_bits);
     else if (sl.h_bits) hipHostFree(sl.h_bits);
     if (sl.d_comp) hipFree(sl.d_comp);
@@ -750,17 +854,7 @@ int fdnn_server_submit_lazy_bits(fdnn_server *s, const float *x, int n, const ui
   if (!x || !out || !bits) return fail(FDNN_E_ARG, "null buffer");
   int rc = start_host_side(s);
   if (rc) return rc;
-  // the widest row of the request, counted here (on the caller's thread) for the batch's compacted row length
-  const size_t O = size_t(s->m->hm.hdr.out_dim), wpr = (O + 63) / 64;
-  const uint64_t tail_mask = (O & 63) ? ((uint64_t(1) << (O & 63)) - 1) : ~uint64_t(0);
-  int most = 0;
-  for (int f = 0; f < n; ++f) {
-    const uint64_t *row = bits + size_t(f) * wpr;
-    int k = 0;
-    for (size_t w = 0; w + 1 < wpr; ++w) k += __builtin_popcountll(row[w]);
-    k += __builtin_popcountll(row[wpr - 1] & tail_mask);
-    most = std::max(most, k);
-  }
+  const int most = widest_row(bits, n, size_t(s->m->hm.hdr.out_dim));
   uint64_t t;
   {
     std::lock_guard<std::mutex> lk(s->mu);
@@ -778,6 +872,11 @@ int fdnn_server_submit_lazy_bits(fdnn_server *s, const float *x, int n, const ui
   s->qcv.notify_all();
   *ticket = t;
   return FDNN_OK;
+}
+
+int fdnn_server_submit_raw(fdnn_server *s, const float *raw, int n, const uint64_t *bits, float *out, uint64_t *ticket) {
+  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
+  return fdnn::server_submit_raw_rows(s, s->m->splice, raw, n, 0, n, bits, out, ticket);
 }
 
 int fdnn_server_wait(fdnn_server *s, uint64_t ticket) {

@@ -121,6 +121,68 @@ FDNN_API int fdnn_calculate_lazy(fdnn_model *m, const float *x, int n, int dim, 
 FDNN_API int fdnn_calculate_lazy_bits(fdnn_model *m, const float *x, int n, int dim, const uint64_t *bits, float *out);
 FDNN_API int fdnn_calculate_lazy_bits_device(fdnn_model *m, const float *d_x, int n, const uint64_t *d_bits, float *d_out, void *stream);
 
+/* ------------------------------------------------------------------ raw feature frames: the <Splice> block on the device
+ * Every net this library runs reads SPLICED rows: row t is the raw feature frames t + o_0 .. t + o_{C-1} side by side
+ * (a Kaldi nnet1 final.feature_transform starts with <Splice> [ -5 .. 5 ]; the reference's converter reads that block and
+ * drops it, FeedForwardNetwork.java:97-100, so its callers splice on the host: 11 copies of every frame over PCIe).
+ * With a splice spec set, the entry points below take the RAW frames and build the rows on the device.
+ *
+ *   spec       offsets o_0 .. o_{C-1} (1 <= C <= 64, each |o| <= 64, any order, duplicates allowed) and the raw frame
+ *              width D, with C * D <= input_dim (the padded layer-0 width).
+ *   row t      raw[f(t + o_0)] || ... || raw[f(t + o_{C-1})], then zeros up to input_dim (BatchData.alignDimension).
+ *   f          whole utterance: the frame index clamped to the utterance's first and last frame (Kaldi's edge rule).
+ *              stream: frame 0 of the stream is the left clamp; frame t is complete once raw frame t + max(o, 0) has
+ *              arrived; at the end of the stream the rest is flushed, right-clamped to the last frame.
+ *   results    the rows are copies, so every result is BIT-IDENTICAL to the same entry point on the host-spliced rows
+ *              (convert.splice_frames).
+ *
+ * Every raw entry point returns FDNN_E_STATE while no spec is set and FDNN_E_ARG when raw_dim is not the spec's D.  Raw
+ * frames are row-major [n][D] fp32; one raw frame gives one output row.
+ *
+ * fdnn_model_set_splice  sets the spec; count == 0 with raw_dim == 0 clears it (count == 0 with a width is FDNN_E_ARG).  Like fdnn_model_set_l0_fma: set it before the model is used
+ *   from several threads.  On a group-attached model it applies to every replica (fdnn_group_attach hands the leader's
+ *   spec to the replicas, and a sharded call splices every shard by the leader's).  A call in progress, a stream and a
+ *   queued server submission keep the spec they started with.  Contexts that never splice do not grow;
+ *   a context allocates its raw buffer (and, in the scoring loop, its frame buffer) on its first raw call.
+ * fdnn_model_get_splice  copies up to `cap` offsets and D (raw_dim may be NULL); returns the offset count (0: no spec).
+ * fdnn_calculate_raw     one utterance, host to host, n output rows; n == 0 is a no-op.  Routed like fdnn_calculate:
+ *   sharded over an attached group first, each replica uploading only the raw frames its rows reference (its shard plus
+ *   the halo), and through the batcher of the model that scores the rows when one is on (fdnn_model_enable_batcher /
+ *   FDNN_BATCHER).  A large utterance's raw frames are uploaded
+ *   once and spliced chunk by chunk (fdnn_debug_frame_chunks) before each chunk's hidden layers.
+ * fdnn_calculate_raw_device  device buffers d_raw [n][D], d_out [n][output_dim]; seg_starts (host, n_segs entries, first
+ *   0, strictly ascending) cuts the n frames into utterances, each with its own edges; NULL = one utterance.  Enqueued on
+ *   `stream`, not synchronised.
+ * fdnn_calculate_lazy_bits_raw  the one-call lazy contract (fdnn_calculate_lazy_bits) on raw frames, rows back compacted.
+ * fdnn_ctx_forward_hidden_raw   calculateUntilOutput on fdnn_ctx_frame_count(c) raw frames of one utterance; then
+ *   fdnn_ctx_output*, fdnn_ctx_lazy_output* and fdnn_ctx_read_hidden work unchanged. */
+FDNN_API int fdnn_model_set_splice(fdnn_model *m, const int *offsets, int count, int raw_dim);
+FDNN_API int fdnn_model_get_splice(const fdnn_model *m, int *offsets, int cap, int *raw_dim);
+FDNN_API int fdnn_calculate_raw(fdnn_model *m, const float *raw, int n, int raw_dim, float *out);
+FDNN_API int fdnn_calculate_raw_device(fdnn_model *m, const float *d_raw, int n, const int *seg_starts, int n_segs, float *d_out,
+                                       void *stream);
+FDNN_API int fdnn_calculate_lazy_bits_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const uint64_t *bits, float *out);
+FDNN_API int fdnn_ctx_forward_hidden_raw(fdnn_ctx *c, const float *raw);
+
+/* Streams: an utterance scored as it arrives, chunk by chunk (a real-time recogniser's feed).  The stream keeps the spec
+ * it was created with, and its last max(-o, 0) + max(o, 0) raw frames on the device (never uploaded twice).
+ * fdnn_stream_create     max_chunk: the most raw frames one push may carry.
+ * fdnn_stream_reset      the next push starts a new utterance (also after a push with `end`, which closes the stream:
+ *                        a further push without a reset is FDNN_E_STATE).
+ * fdnn_stream_position   raw frames pushed and rows emitted since the utterance started.
+ * fdnn_stream_push       n_raw (0 .. max_chunk) raw frames; scores the frames this push completes, in order, into out
+ *   [*n_out][output_dim] (at most n_raw + max(o, 0) rows).  end != 0 flushes the rest (n_raw = 0 is a flush only).  With
+ *   out == NULL only the hidden layers run: fdnn_stream_ctx(s) is then a context (owned by the stream; do not free it)
+ *   whose frames 0 .. *n_out - 1 are exactly those frames, for the lazy entry points -- the reference's LazyContext
+ *   protocol (calculateUntilOutput, then per-frame masks; QuantizedDnn.java:72-107), chunk by chunk.  Host-synchronous. */
+typedef struct fdnn_stream fdnn_stream;
+FDNN_API int fdnn_stream_create(fdnn_model *m, int max_chunk, fdnn_stream **out);
+FDNN_API void fdnn_stream_free(fdnn_stream *s);
+FDNN_API int fdnn_stream_reset(fdnn_stream *s);
+FDNN_API int fdnn_stream_position(const fdnn_stream *s, int64_t *pushed, int64_t *emitted);
+FDNN_API int fdnn_stream_push(fdnn_stream *s, const float *raw, int n_raw, int end, float *out, int *n_out);
+FDNN_API fdnn_ctx *fdnn_stream_ctx(fdnn_stream *s);
+
 /* ------------------------------------------------------------------ contexts / lazy path
  * fdnn_ctx_create <- getContext / jni_dnn.cc:64-77 (CalculationContext ctor,
  *   dnn.cc:194-215): device scratch for n frames. */
@@ -201,6 +263,12 @@ FDNN_API int fdnn_server_submit(fdnn_server *s, const float *x, int n, const int
  * own `out` by the thread that waits for the ticket.  x / bits / out must stay valid until the ticket completes.
  * (LazyContext.calculateUntilOutput + calculateForOutputNodes per frame, QuantizedDnn.java:72-107, for many callers.) */
 FDNN_API int fdnn_server_submit_lazy_bits(fdnn_server *s, const float *x, int n, const uint64_t *bits, float *out, uint64_t *ticket);
+/* Raw feature frames through the loop (see "raw feature frames" above): raw [n][D]; bits NULL = dense rows, else the
+ * compacted lazy return of fdnn_server_submit_lazy_bits.  Raw utterances are coalesced with one another, each keeping its
+ * own edges (the batch's segment table); only the raw frames travel.  Bit-identical to the same utterance through
+ * fdnn_calculate_raw / fdnn_calculate_lazy_bits_raw.  raw / bits / out must stay valid until the ticket completes.  A
+ * submission is spliced by the model's spec at the time it was submitted. */
+FDNN_API int fdnn_server_submit_raw(fdnn_server *s, const float *raw, int n, const uint64_t *bits, float *out, uint64_t *ticket);
 FDNN_API int fdnn_server_wait(fdnn_server *s, uint64_t ticket);
 FDNN_API int fdnn_server_drain(fdnn_server *s);
 FDNN_API int fdnn_server_stats(fdnn_server *s, uint64_t *batches, uint64_t *frames, uint64_t *requests,
