@@ -63,6 +63,11 @@ SIGNATURES = {
     "fdnn_model_chain_faults": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_set_pp": (C.c_int, [C.c_int, C.c_int]),
     "fdnn_debug_set_ppo": (C.c_int, [C.c_int]),
+    "fdnn_debug_launch_name_count": (C.c_int, []),
+    "fdnn_debug_launch_name": (C.c_char_p, [C.c_int, C.POINTER(C.c_int)]),
+    "fdnn_debug_launch_record": (C.c_int, [C.c_int]),
+    "fdnn_debug_launch_reset": (C.c_int, []),
+    "fdnn_debug_launch_counts": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_debug_raise_fuse_fault": (C.c_int, [C.c_void_p, C.c_int]),
     "fdnn_device_shared": (C.c_int, [C.c_int]),
     "fdnn_debug_set_fuse": (C.c_int, [C.c_int]),
@@ -244,6 +249,41 @@ def set_ppo(mode: int) -> None:
     """How a large dense batch's output layer runs when its soft-max is fused (process-wide; results are bit-identical):
     1 = the role-split kernel (fdnn_ppo.hip) whenever the shape allows, 0 = the in-phase fused tiles, -1 = default."""
     _check(lib().fdnn_debug_set_ppo(int(mode)))
+
+
+LAUNCH_ABLATION, LAUNCH_LOAD_TIME = 1, 2  # flags of launch_names()
+
+
+def launch_names() -> dict:
+    """The launch recorder's table: name of every host launch branch -> flags (LAUNCH_ABLATION: the branch exists only in
+    measurement builds, LAUNCH_LOAD_TIME: the kernel runs at model load).  Needs no device."""
+    L = lib()
+    out = {}
+    for i in range(L.fdnn_debug_launch_name_count()):
+        flags = C.c_int(0)
+        name = L.fdnn_debug_launch_name(i, C.byref(flags)).decode()
+        out[name] = flags.value
+    return out
+
+
+def launch_record(on: bool = True) -> None:
+    """Count launches per name from here on (process-wide, every thread); off by default."""
+    _check(lib().fdnn_debug_launch_record(1 if on else 0))
+
+
+def launch_reset() -> None:
+    _check(lib().fdnn_debug_launch_reset())
+
+
+def launch_counts(nonzero: bool = True) -> dict:
+    """name -> launches counted since the last launch_reset() (only the names that ran unless nonzero=False)."""
+    L = lib()
+    n = L.fdnn_debug_launch_name_count()
+    buf = (C.c_ulonglong * n)()
+    if L.fdnn_debug_launch_counts(buf, n) != n:
+        raise RuntimeError("launch table changed size")
+    names = list(launch_names())
+    return {names[i]: int(buf[i]) for i in range(n) if buf[i] or not nonzero}
 
 
 class LazyContext:

@@ -578,6 +578,7 @@ void launch_chain_cfg(const QChainParams &p, hipStream_t s) {
   const int grid = static_cast<int>(std::min<long>(tiles, static_cast<long>(cus[dev & 63].load(std::memory_order_relaxed)) * per_cu));
   bool any_fix = false;
   for (int i = 0; i < p.n_layers; ++i) any_fix = any_fix || p.layer[i].fix_ent != nullptr;
+  note_launch(NF == 4 ? (any_fix ? kLn_chain_ft256_fix : kLn_chain_ft256_nofix) : (any_fix ? kLn_chain_ft320_fix : kLn_chain_ft320_nofix));
   hipLaunchKernelGGL(any_fix ? k : k_nofix, dim3(grid), dim3(Cfg::THREADS), kLds, s, p);
 }
 

@@ -1106,9 +1106,26 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
+// the tile shape's name in the launch recorder's table (fdnn_note.hpp)
+constexpr int gemm_shape(int NF, int WN, int BK, int STAGES, bool FAST, int WM) {
+  return !FAST     ? gs_tdiv
+         : WM == 1 ? gs_ft32w1
+         : WM == 2 ? gs_ft128nt128
+         : WN == 2 ? (NF == 4 ? gs_ft256 : gs_ft320)
+         : NF == 1 ? (BK == 128 ? gs_ft32 : gs_ft32bk64)
+         : NF == 2 ? (BK == 128 ? gs_ft64 : gs_ft64bk64)
+         : NF == 5 ? gs_ft160
+         : BK == 128 ? gs_ft128bk128
+         : STAGES == 6 ? gs_ft128bk64x6
+                       : gs_ft128;
+}
+
 template <int NF, int WN, int BK, int STAGES, bool OUTPUT, bool FAST = true, int WM = 4>
 void launch_cfg(const QGemmParams &p, hipStream_t s) {
   using Cfg = GemmCfg<NF, WN, BK, STAGES, WM>;
+  const auto note = [](int branch) {
+    if (g_launch_note_on.load(std::memory_order_relaxed)) note_launch(gemm_launch_name(OUTPUT, gemm_shape(NF, WN, BK, STAGES, FAST, WM), branch));
+  };
   const int MT = p.rows_pad / Cfg::G_BM, NT = p.n_pad / Cfg::FT;
   const int blocks = 8 * MT * ((NT + 7) / 8);
   auto k_prod = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, false, false, false, WM>;
@@ -1155,26 +1172,38 @@ void launch_cfg(const QGemmParams &p, hipStream_t s) {
   if (kCanFuse && p.fuse_s != nullptr) {
     // fused soft-max: the node tiles of a frame tile are consecutive blocks (what a workgroup that gave up waiting left
     // unscaled is scaled by its frame tile's last workgroup: one launch)
-    if ((p.rows & 31) != 0)
+    if ((p.rows & 31) != 0) {
+      note(p.mask ? gb_fused_masked_anyw : gb_fused_anyw);
       hipLaunchKernelGGL(p.mask ? k_fused_masked_anyw : k_fused_anyw, dim3(MT * NT), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-    else if (kNoFix && p.fix_ent == nullptr)
+    } else if (kNoFix && p.fix_ent == nullptr) {
+      note(p.mask ? gb_fused_masked_nofix : gb_fused_nofix);
       hipLaunchKernelGGL(p.mask ? k_fused_masked_nofix : k_fused_nofix, dim3(MT * NT), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-    else
+    } else {
+      note(p.mask ? gb_fused_masked : gb_fused);
       hipLaunchKernelGGL(p.mask ? k_fused_masked : k_fused, dim3(MT * NT), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  } else if (p.tap_acc)
+    }
+  } else if (p.tap_acc) {
+    note(gb_tap);
     hipLaunchKernelGGL(k_tap, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  else if (OUTPUT && p.mask == nullptr && (p.rows & 31) == 0)
+  } else if (OUTPUT && p.mask == nullptr && (p.rows & 31) == 0) {
+    note(gb_plain);
     hipLaunchKernelGGL(k_plain, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  else if (OUTPUT && p.mask == nullptr)
+  } else if (OUTPUT && p.mask == nullptr) {
+    note(gb_anyw);
     hipLaunchKernelGGL(k_anyw, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  else if (OUTPUT && p.mask != nullptr && (p.rows & 3) == 0)
+  } else if (OUTPUT && p.mask != nullptr && (p.rows & 3) == 0) {
+    note(gb_masked);
     hipLaunchKernelGGL(k_masked, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  else if (OUTPUT && p.mask != nullptr)  // 8001 nodes: 0.33 ms against 0.41 through the general epilogue
+  } else if (OUTPUT && p.mask != nullptr) {  // 8001 nodes: 0.33 ms against 0.41 through the general epilogue
+    note(gb_masked_anyw);
     hipLaunchKernelGGL(k_masked_anyw, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  else if (kNoFix && !OUTPUT && p.fix_ent == nullptr)
+  } else if (kNoFix && !OUTPUT && p.fix_ent == nullptr) {
+    note(gb_prod_nofix);
     hipLaunchKernelGGL(k_prod_nofix, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  else
+  } else {
+    note(gb_prod);
     hipLaunchKernelGGL(k_prod, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
+  }
 }
 
 template <bool OUTPUT>

@@ -314,13 +314,17 @@ __global__ __launch_bounds__(256) void lazy_compact_kernel(const float *out, con
 }  // namespace
 
 void launch_lazy_compact(const float *out, const uint64_t *bits, float *comp, int n, int rows, int stride, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(lazy_compact_kernel, dim3((n + 3) / 4), dim3(256), 0, s, out, bits, comp, n, rows, (rows + 63) / 64, stride);
+  if (n <= 0) return;
+  note_launch(kLn_compact);
+  hipLaunchKernelGGL(lazy_compact_kernel, dim3((n + 3) / 4), dim3(256), 0, s, out, bits, comp, n, rows, (rows + 63) / 64, stride);
 }
 
 void launch_mask_unpack(const uint64_t *bits, int8_t *mask, int n, int rows, hipStream_t s) {
   const long long total = static_cast<long long>(n) * rows;
   const int blocks = static_cast<int>(std::min<long long>((total + 255) / 256, 256 * 16));
-  if (blocks > 0) hipLaunchKernelGGL(mask_unpack_kernel, dim3(blocks), dim3(256), 0, s, bits, mask, n, rows, (rows + 63) / 64);
+  if (blocks <= 0) return;
+  note_launch(kLn_maskunpack);
+  hipLaunchKernelGGL(mask_unpack_kernel, dim3(blocks), dim3(256), 0, s, bits, mask, n, rows, (rows + 63) / 64);
 }
 
 void launch_mask_pack(const int8_t *mask, uint64_t *bits, int n, int rows, hipStream_t s) {
@@ -328,10 +332,13 @@ void launch_mask_pack(const int8_t *mask, uint64_t *bits, int n, int rows, hipSt
   const long long total = static_cast<long long>(n) * wpr * 4;
   const int blocks = static_cast<int>(std::min<long long>((total + 255) / 256, 256 * 16));
   if (blocks <= 0) return;
-  if (rows % 64 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0)
+  if (rows % 64 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0) {
+    note_launch(kLn_maskpack_flat);
     hipLaunchKernelGGL(mask_pack_flat_kernel, dim3(std::min(blocks, 256 * 8)), dim3(256), 0, s, mask, bits, total);
-  else
+  } else {
+    note_launch(kLn_maskpack_rows);
     hipLaunchKernelGGL(mask_pack_kernel, dim3(blocks), dim3(256), 0, s, mask, bits, n, rows, wpr);
+  }
 }
 
 void launch_normalize(float *out, float *dst, const float *partial, int n, int partial_ld, int rows, int n_partial, hipStream_t s,
@@ -342,24 +349,29 @@ void launch_normalize(float *out, float *dst, const float *partial, int n, int p
       const char *e = FDNN_TUNE_ENV("FDNN_NORM_BG_WGS");
       return e ? std::max(1, std::atoi(e)) : 256;  // sweep, 2 steps in flight: 192-256 best (+7-8 % over one stream), 512 +4 %, 1024 +2 %
     }();
+    note_launch(kLn_norm_bg);
     hipLaunchKernelGGL(normalize_bg_kernel, dim3(std::min(n, wgs)), dim3(256), 0, s, out, dst, partial, n, partial_ld, rows, n_partial);
     return;
   }
   const bool small_ok = n <= 1024 && (rows & 3) == 0 && rows <= 8192 && (n_partial >> 2) <= 64 &&
                         ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
   if (small_ok) {
+    note_launch(kLn_norm_small);
     hipLaunchKernelGGL(normalize_small_kernel, dim3(n), dim3(256), 0, s, out, dst, partial, n, partial_ld, rows, n_partial);
     return;
   }
+  note_launch(kLn_norm_rows);
   hipLaunchKernelGGL(normalize_kernel, dim3(n), dim3(256), 0, s, out, dst, partial, n, partial_ld, rows, n_partial);
 }
 
 void launch_fastdiv_check(float coef, float rcp, unsigned long long *d_mismatch, hipStream_t s) {
+  note_launch(kLn_fastdiv_check);
   hipLaunchKernelGGL(fastdiv_check_kernel, dim3(2048), dim3(256), 0, s, coef, rcp, d_mismatch);
 }
 
 void launch_xor80(const int8_t *in, uint8_t *out, size_t count, hipStream_t s) {
   if (!count) return;
+  note_launch(kLn_xor80);
   hipLaunchKernelGGL(xor80_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, s, in, out, count);
 }
 

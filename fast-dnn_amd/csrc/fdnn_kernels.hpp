@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "fdnn_note.hpp"
+
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv.  Everything else -- tile-shape
 // overrides, thresholds and kernel choices that the sweeps under tools/ turn -- exists only in measurement builds

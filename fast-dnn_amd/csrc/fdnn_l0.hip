@@ -184,6 +184,12 @@ __global__ __launch_bounds__(256, TI <= 4 ? 4 : 2) void l0_valu_kernel(L0Params 
 template <int TI, int BK>
 void launch_valu(const L0Params &p, hipStream_t s) {
   dim3 grid(l0_grid((p.H + 63) / 64, (p.n_rows + 16 * TI - 1) / (16 * TI)));
+  // (the fused flavour reaches these tiles only in measurement builds: FDNN_L0_FMA_VALU)
+  const int tile = TI == 1 ? 0 : TI == 2 ? 1 : 2;
+  static const int names[3][2][2] = {{{kLn_l0_tile16_prod, kLn_l0_tile16_tap}, {kLn_l0_tile16_fma_prod, kLn_l0_tile16_fma_tap}},
+                                     {{kLn_l0_tile32_prod, kLn_l0_tile32_tap}, {kLn_l0_tile32_fma_prod, kLn_l0_tile32_fma_tap}},
+                                     {{kLn_l0_tile64_prod, kLn_l0_tile64_tap}, {kLn_l0_tile64_fma_prod, kLn_l0_tile64_fma_tap}}};
+  note_launch(names[tile][p.fma ? 1 : 0][p.tap_lin ? 1 : 0]);
   if (p.tap_lin) {
     if (p.fma)
       hipLaunchKernelGGL((l0_valu_kernel<TI, BK, true, true>), grid, dim3(256), 0, s, p);
@@ -457,6 +463,7 @@ void launch_l0_small(const L0Params &p, hipStream_t s) {
     attr_set.fetch_or(dev_bit, std::memory_order_release);
   }
   dim3 grid(static_cast<unsigned>((p.H + 31) / 32) * static_cast<unsigned>((p.n_rows + 31) / 32));
+  note_launch(p.tap_lin ? kLn_l0_small_tap : kLn_l0_small_prod);
   if (p.tap_lin)
     hipLaunchKernelGGL(kt, grid, dim3(512), g.lds, s, p, g.sc, g.sc_magic, g.ch_magic);
   else
@@ -698,6 +705,9 @@ __global__ __launch_bounds__(256) void l0_image_kernel(const float *src, const f
 template <int JC, int TN>
 void launch_chain_tn(const L0Params &p, hipStream_t s) {
   const int cols = (p.n_rows + 127) / 128 * 128;
+  note_launch(kLn_l0_image_frames,
+              JC == 12 ? (TN == 64 ? (p.tap_lin ? kLn_l0_chain_jc12_tn64_tap : kLn_l0_chain_jc12_tn64_prod) : (p.tap_lin ? kLn_l0_chain_jc12_tn128_tap : kLn_l0_chain_jc12_tn128_prod))
+                       : (TN == 64 ? (p.tap_lin ? kLn_l0_chain_jc16_tn64_tap : kLn_l0_chain_jc16_tn64_prod) : (p.tap_lin ? kLn_l0_chain_jc16_tn128_tap : kLn_l0_chain_jc16_tn128_prod)));
   hipLaunchKernelGGL(l0_image_kernel, dim3(cols / 64, (p.j_pad * 4 + 63) / 64), dim3(256), 0, s, p.x, p.shift, p.scale, p.xt, p.n,
                      p.D, p.j_pad, p.n_ld);
   dim3 grid(l0_grid(p.h_ld / TN, cols / 128));
@@ -1194,6 +1204,7 @@ void launch_mfma(const L0Params &p, hipStream_t s) {
     attr_set.fetch_or(dev_bit, std::memory_order_release);
   }
   dim3 grid(l0_grid((p.H + Cfg::TN - 1) / Cfg::TN, (p.n_rows + Cfg::TF - 1) / Cfg::TF));
+  note_launch(p.tap_lin ? kLn_l0_mfma_tap : kLn_l0_mfma_prod);
   hipLaunchKernelGGL(p.tap_lin ? k_tap : k_prod, grid, dim3(Cfg::THREADS), Cfg::LDS, s, p);
 }
 
@@ -1214,6 +1225,7 @@ void launch_screened_cfg(const L0Params &p, hipStream_t s) {
     attr_set.fetch_or(dev_bit, std::memory_order_release);
   }
   const int node_tiles = (p.H + 127) / 128, frame_tiles = (p.n_rows + Cfg::TF - 1) / Cfg::TF;
+  note_launch(WFR == 4 ? kLn_l0_screen_f128 : kLn_l0_screen_f64, kLn_l0_fix_tiles);
   hipLaunchKernelGGL(k_scr, dim3(l0_grid(node_tiles, frame_tiles)), dim3(Cfg::THREADS), Cfg::LDS, s, p);
   hipLaunchKernelGGL(l0_fix_kernel, dim3(node_tiles * frame_tiles), dim3(kFixThreads), 2 * sizeof(float) * p.D + (kFixThreads / 64) * FDNN_L0_FIX_DEPTH * 1024, s, p, Cfg::TF);
 }
@@ -1315,6 +1327,7 @@ void launch_l0(const L0Params &p, hipStream_t s) {
       if (nb >= 5) FDNN_FIX_LAUNCH(5, T_, 4); else FDNN_FIX_LAUNCH(3, T_, 4);        \
     }                                                                                \
   } while (0)
+    note_launch(thr == 512 ? kLn_l0_fixlist_t512 : lpo == 8 ? (nb >= 3 ? kLn_l0_fixlist_lpo8 : kLn_l0_fixlist_nb2_lpo8) : (nb >= 5 ? kLn_l0_fixlist_nb5_lpo4 : kLn_l0_fixlist_lpo4));
     if (thr == 512) FDNN_FIX_LAUNCH_T(512); else FDNN_FIX_LAUNCH_T(256);
 #undef FDNN_FIX_LAUNCH_T
 #undef FDNN_FIX_LAUNCH
@@ -1369,6 +1382,7 @@ int l0_chunk_rows(int D) {
 }
 
 void launch_l0_weight_image(const float *w, float *wt, int H, int D, int j_pad, int h_ld, hipStream_t s) {
+  note_launch(kLn_l0_image_weights);
   hipLaunchKernelGGL(l0_image_kernel, dim3(h_ld / 64, (j_pad * 4 + 63) / 64), dim3(256), 0, s, w, nullptr, nullptr, wt, H, D, j_pad,
                      h_ld);
 }

@@ -691,12 +691,15 @@ void launch_l0_split(const L0Params &p, hipStream_t s) {
   }
   const int frame_tiles = (p.n_rows + kSTF - 1) / kSTF;
   const int dig_rows = frame_tiles * kSTF;  // every row a matrix tile will read (<= n_ld)
+  note_launch(kLn_l0_digits);
   hipLaunchKernelGGL(l0_digits_kernel, dim3(dig_rows / kDigFrames), dim3(256), dig_lds, s, p, KC, J, JP);
   if (p.dbg_t != nullptr && p.dbg_dd != nullptr) {  // the tests' instance (128-node tiles)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(l0_split_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SplitCfg<2>::LDS);
+    note_launch(kLn_l0_split_n128_probe);
     hipLaunchKernelGGL((l0_split_kernel<2, true>), dim3(static_cast<unsigned>(p.h_ld / 128) * ((frame_tiles + 7) / 8) * 8), dim3(512), SplitCfg<2>::LDS, s, p, KC, JP / 32);
     return;
   }
+  note_launch(wn_cfg == 2 ? kLn_l0_split_n128 : kLn_l0_split_n64);
   if (wn_cfg == 2)
     hipLaunchKernelGGL(l0_split_kernel<2>, dim3(static_cast<unsigned>(p.h_ld / 128) * ((frame_tiles + 7) / 8) * 8), dim3(512), SplitCfg<2>::LDS, s, p, KC, JP / 32);
   else

@@ -581,6 +581,7 @@ void launch_qpp_hidden(const QGemmParams &p, hipStream_t s) {
   const int MT = p.rows_pad / kBM, NP = p.n_pad / kFT;
   const long t_end = 8L * ((NP + 7) / 8) * MT;  // (a multiple of 8: workgroup b and its later tiles b + grid, ... stay on one XCD's list)
   const int grid = static_cast<int>(std::min<long>(t_end, std::max(8, n_cu / 8 * 8)));
+  note_launch(p.fix_ent ? kLn_pp_hid_fix : kLn_pp_hid_nofix);
   hipLaunchKernelGGL(p.fix_ent ? k : k_nofix, dim3(grid), dim3(512), 0, s, p);
 }
 

@@ -770,6 +770,7 @@ void launch_qppo_output(const QGemmParams &p, hipStream_t s) {
   }
   const int NP = p.n_pad / kFT;
   const int slots = std::max(1, std::min(n_cu / kMT, NP));  // frame pairs in flight: every one has all its 32 node tiles resident
+  note_launch(p.fix_ent ? kLn_ppo_out_fix : kLn_ppo_out_nofix);
   hipLaunchKernelGGL(p.fix_ent ? k : k_nofix, dim3(slots * kMT), dim3(512), 0, s, p);
 }
 

@@ -1133,6 +1133,32 @@ void lazy_expand_rows_from(float *out, const float *comp, int count, size_t O, s
 using namespace fdnn;
 
 // =====================================================================  C-ABI
+// ---- the launch recorder (fdnn_note.hpp)
+namespace fdnn {
+const LaunchNameInfo kLaunchNames[kLaunchNameCount] = {
+#define FDNN_X(id, name, flags) {name, flags},
+    FDNN_LAUNCH_NAMES(FDNN_X)
+#undef FDNN_X
+#define FDNN_G(out, shape, branch, name, abl) {name, abl},
+        FDNN_GEMM_LAUNCH_NAMES(FDNN_G)
+#undef FDNN_G
+};
+std::atomic<int> g_launch_note_on{0};
+std::atomic<unsigned long long> g_launch_count[kLaunchNameCount];
+int gemm_launch_name(bool output, int shape, int branch) {
+  static const struct {
+    int out, shape, branch, id;
+  } known[] = {
+#define FDNN_G(out, shape, branch, name, abl) {out, gs_##shape, gb_##branch, kLn_gemm_##out##_##shape##_##branch},
+      FDNN_GEMM_LAUNCH_NAMES(FDNN_G)
+#undef FDNN_G
+  };
+  for (const auto &k : known)
+    if (k.out == (output ? 1 : 0) && k.shape == shape && k.branch == branch) return k.id;
+  return kLn_unlisted;
+}
+}  // namespace fdnn
+
 extern "C" {
 
 const char *fdnn_last_error(void) { return g_err.c_str(); }
@@ -1335,6 +1361,31 @@ int fdnn_debug_set_ppo(int mode) {
   if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "ppo mode must be -1, 0 or 1");
   fdnn::qppo_set_mode(mode);
   return FDNN_OK;
+}
+
+// ---- the launch recorder (fdnn_note.hpp)
+int fdnn_debug_launch_name_count(void) { return fdnn::kLaunchNameCount; }
+
+const char *fdnn_debug_launch_name(int index, int *flags) {
+  if (index < 0 || index >= fdnn::kLaunchNameCount) return nullptr;
+  if (flags) *flags = fdnn::kLaunchNames[index].flags;
+  return fdnn::kLaunchNames[index].name;
+}
+
+int fdnn_debug_launch_record(int on) {
+  fdnn::g_launch_note_on.store(on ? 1 : 0, std::memory_order_relaxed);
+  return FDNN_OK;
+}
+
+int fdnn_debug_launch_reset(void) {
+  for (auto &c : fdnn::g_launch_count) c.store(0, std::memory_order_relaxed);
+  return FDNN_OK;
+}
+
+int fdnn_debug_launch_counts(unsigned long long *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  for (int i = 0; i < fdnn::kLaunchNameCount && i < cap; ++i) out[i] = fdnn::g_launch_count[i].load(std::memory_order_relaxed);
+  return fdnn::kLaunchNameCount;
 }
 
 int fdnn_debug_set_chain(int mode, int min_frames) {

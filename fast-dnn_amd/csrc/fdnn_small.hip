@@ -417,12 +417,16 @@ void launch_small_cfg(const QGemmParams &p, hipStream_t s) {
   const int tpg = (n_tiles + groups - 1) / groups;
   groups = (n_tiles + tpg - 1) / tpg;
   const int blocks = 8 * ((MT + 7) / 8) * groups;
-  if (p.tap_acc)
+  if (p.tap_acc) {
+    note_launch(OUTPUT ? kLn_small_out_tap : NTM == 1 ? kLn_small_hid_nt32_tap : kLn_small_hid_nt64_tap);
     hipLaunchKernelGGL(k_tap, dim3(blocks), dim3(kSmThreads), kSmLds, s, p, groups, tpg);
-  else if (OUTPUT && p.mask)
+  } else if (OUTPUT && p.mask) {
+    note_launch(kLn_small_out_masked);
     hipLaunchKernelGGL(k_masked, dim3(blocks), dim3(kSmThreads), kSmLds, s, p, groups, tpg);
-  else
+  } else {
+    note_launch(OUTPUT ? kLn_small_out_prod : NTM == 1 ? kLn_small_hid_nt32_prod : kLn_small_hid_nt64_prod);
     hipLaunchKernelGGL(k_prod, dim3(blocks), dim3(kSmThreads), kSmLds, s, p, groups, tpg);
+  }
 }
 
 }  // namespace

@@ -79,6 +79,7 @@ void launch_splice(const float *raw, int raw_frames, float *x, int row0, int row
     const int cnt = std::min(step, rows - r);
     const long long total = static_cast<long long>(cnt) * q4;
     const int blocks = static_cast<int>(std::min<long long>((total + 255) / 256, 256 * 16));
+    note_launch(kLn_splice);
     hipLaunchKernelGGL(splice_kernel, dim3(blocks), dim3(256), 0, s, raw, x + static_cast<size_t>(r) * a.input_dim, row0 + r, cnt,
                        raw_frames, a);
   }

@@ -388,6 +388,21 @@ FDNN_API int fdnn_debug_set_pp(int mode, int min_frames);
  * CalculateOutput + SoftMax::apply, src/cpp/dnn.cc:428-454, :534-544, is what is being computed. */
 FDNN_API int fdnn_debug_set_ppo(int mode);
 
+/* The launch recorder (tests and the tools under tools/): every host launch site of a compute kernel has a stable name for the
+ * branch it takes ("gemm.out.ft320.fused_masked", "small.hid.nt64.prod", "chain.ft320.nofix", "l0.fixlist.lpo8", "norm.bg", ...),
+ * kept in one static table that can be read with no device present.  fdnn_debug_launch_name_count: entries of the table;
+ * fdnn_debug_launch_name: the name of entry `index` (null outside the table) and, where `flags` is not null, 1 if the branch
+ * exists only in measurement builds (-DFDNN_ABLATION), 2 if the kernel runs at model load.  fdnn_debug_launch_record(1 / 0)
+ * switches counting on / off for the whole process (off by default: a launch then pays one relaxed load);
+ * fdnn_debug_launch_reset zeroes the counts; fdnn_debug_launch_counts copies the first `cap` of them, in table order, and
+ * returns the table's size.  The counts are process-wide relaxed atomics: launches of scoring-loop, group and stream worker
+ * threads are counted like the caller's own.  Recording changes no selection rule and no kernel. */
+FDNN_API int fdnn_debug_launch_name_count(void);
+FDNN_API const char *fdnn_debug_launch_name(int index, int *flags);
+FDNN_API int fdnn_debug_launch_record(int on);
+FDNN_API int fdnn_debug_launch_reset(void);
+FDNN_API int fdnn_debug_launch_counts(unsigned long long *out, int cap);
+
 /* Tests: write the word a fused soft-max workgroup raises (in host memory) when it gives up waiting for its frame tile's
  * siblings -- 1: as if a launch of this model had just done so (from the next call on the model runs the unfused soft-max
  * and says so once on stderr), 0: forget it.  The production path needs no call: fdnn_gemm.hip / fdnn_ppo.hip raise it. */

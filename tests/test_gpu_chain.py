@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from fast_dnn_amd import api, formats as F
+from dispatch_ledger import chain_tile, launched
 from oracle.oracle import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -34,8 +35,10 @@ def test_chained_hidden_layers_equal_one_launch_per_layer(net_model_path, chain_
     flows into the next layer here): the last hidden layer's u8 bytes, all of them, from both forms."""
     dnn = api.QuantizedDnn.loadFromFile(net_model_path)
     x = F.synth_features(n, 432, seed=300 + n % 97)
-    a = hidden_bytes(dnn, x, 0)
-    b = hidden_bytes(dnn, x, 1)
+    a, ran_a = launched(hidden_bytes, dnn, x, 0)
+    b, ran_b = launched(hidden_bytes, dnn, x, 1)
+    assert "chain.ft%d.fix" % chain_tile(n) in ran_b and not any(k.startswith("gemm.hid.") for k in ran_b), ran_b
+    assert not any(k.startswith("chain.") for k in ran_a) and any(k.startswith("gemm.hid.") for k in ran_a), ran_a
     assert a.shape == (n, 2048) and np.array_equal(a, b)
     assert dnn.deviceCounters(8)[3] == 0  # no wait ran into its bound
     dnn.delete()
@@ -49,7 +52,9 @@ def test_chained_hidden_layers_against_the_oracle(net_model_path, chain_mode):
     rng = np.random.default_rng(5)
     idx = np.array(sorted({min(n - 1, int(t0 + d)) for t0 in range(0, n, 320) for d in (0, int(rng.integers(1, 319)), 319)}))
     dnn = api.QuantizedDnn.loadFromFile(net_model_path)
-    got = hidden_bytes(dnn, x, 1)[idx]
+    got, ran = launched(hidden_bytes, dnn, x, 1)
+    assert "chain.ft256.fix" in ran and not any(k.startswith("gemm.hid.") for k in ran), ran  # (12 000 frames pad less on 256-frame tiles)
+    got = got[idx]
     _, taps = Oracle(net_model_path).calculate(x[idx], taps=True)
     assert np.array_equal(got, taps["u8_acts"][-1])
     dnn.delete()
@@ -70,8 +75,10 @@ def test_chain_on_a_net_with_every_pair_saturating(tmp_models, chain_mode):
     dnn = api.QuantizedDnn.loadFromFile(p)
     n = 1500
     x = F.synth_features(n, 432, seed=8)
-    a = hidden_bytes(dnn, x, 0)
-    b = hidden_bytes(dnn, x, 1)
+    a, ran_a = launched(hidden_bytes, dnn, x, 0)
+    b, ran_b = launched(hidden_bytes, dnn, x, 1)
+    assert "chain.ft320.fix" in ran_b and not any(k.startswith("gemm.hid.") for k in ran_b), ran_b
+    assert "gemm.hid.ft32.w1.prod" in ran_a and not any(k.startswith("chain.") for k in ran_a), ran_a
     assert np.array_equal(a, b)
     _, taps = Oracle(p).calculate(x[:64], taps=True)
     assert np.array_equal(b[:64], taps["u8_acts"][-1])
@@ -126,8 +133,13 @@ def test_default_rule_picks_the_chain_only_where_it_saves_task_times(net_model_p
     for n in (10000, 12000):
         x = F.synth_features(n, 432, seed=n)
         api.set_chain(0)
-        a = dnn.calculate(x)
+        a, ran_a = launched(dnn.calculate, x)
         api.set_chain(-1)
-        b = dnn.calculate(x)
+        b, ran_b = launched(dnn.calculate, x)
+        assert not any(k.startswith("chain.") for k in ran_a), ran_a
+        # the documented rule on a 256-CU device: 10 000 frames are 8 x 32 = 256 tasks per layer, a whole round -- one launch
+        # per layer; 12 000 are 8 x 38 = 304, 208 CUs idle in the second round -- the chain
+        assert any(k.startswith("chain.") for k in ran_b) == (n == 12000), (n, ran_b)
+        assert any(k.startswith("gemm.hid.") for k in ran_b) == (n == 10000), (n, ran_b)
         assert np.array_equal(a, b)
     dnn.delete()

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from fast_dnn_amd import api, formats as F
+from dispatch_ledger import launched
 from oracle.oracle import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -92,7 +93,11 @@ def test_every_output_next_to_a_rounding_boundary(tmp_models, kind):
     assert near[0].mean() > 0.95 and near.mean() > 0.5  # the construction works: the batch crowds the boundaries
     dnn = api.QuantizedDnn.loadFromFile(p)
     dnn.setInputLayerKernel(kind)
-    got, recomputed = dnn.layer0(x)
+    (got, recomputed), ran = launched(dnn.layer0, x)
+    if kind == 3:  # the fp32 screen and its per-tile exact recomputation
+        assert {k for k in ran if k.startswith("l0.")} == {"l0.screen.f128", "l0.fix.tiles"}, ran
+    else:          # the int8 screen (64-node tiles at this size) and the list-driven recomputation
+        assert {k for k in ran if k.startswith("l0.")} == {"l0.digits", "l0.split.n64", "l0.fixlist.lpo8"}, ran
     bad = np.argwhere(got != wt["u8_acts"][0])
     assert bad.size == 0, (len(bad), bad[:8].tolist())
     assert recomputed >= 0.5 * x.shape[0] * H  # nearly everything had to take the exact path

@@ -10,6 +10,7 @@ import pytest
 
 from conftest import golden
 from fast_dnn_amd import api, formats as F
+from dispatch_ledger import launched
 from oracle.oracle import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -472,7 +473,13 @@ def test_big_batch_small_net_takes_the_8_wave_shapes(tmp_models, hidden):
     x = F.synth_features(n, 432, seed=12)
     want, wt = Oracle(p).calculate(x, taps=True)
     dnn = api.QuantizedDnn.loadFromFile(p)
-    got = dnn.calculate(x)
+    got, ran = launched(dnn.calculate, x)
+    # the 8-wave shapes did run: per layer (fdnn_gemm.hip) or, where the default rule chains the hidden layers of such a
+    # batch (64- and 144-wide layers: their padded K is a multiple of 128), as the chained kernel's tiles of the same shape
+    eight_wave = {"gemm.hid.ft256.prod", "gemm.hid.ft320.prod", "chain.ft256.fix", "chain.ft320.fix"}
+    hidden_ran = {k for k in ran if k.startswith(("gemm.hid.", "chain.", "small.hid.", "pp."))}
+    assert hidden_ran and hidden_ran <= eight_wave, ran
+    assert {k for k in ran if k.startswith(("gemm.out.", "small.out."))} <= {"gemm.out.ft256.fused_anyw", "gemm.out.ft320.fused_anyw", "gemm.out.ft256.anyw", "gemm.out.ft320.anyw"}, ran
     assert np.abs(got - want).max() <= TIGHT
     t = dnn.forwardTaps(x[:700])  # taps for a slice (the tap kernels are separate instances)
     assert (t["u8_acts"] == wt["u8_acts"][:, :700]).all()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from fast_dnn_amd import api, formats as F
+from dispatch_ledger import launched
 from oracle.oracle import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -38,8 +39,10 @@ def test_role_split_layers_equal_the_in_phase_tiles(net_model_path, modes, n):
     per workgroup (20 557 frames = 65 pairs x 8 node tiles on 256 workgroups: the steady state of the alternation)."""
     dnn = api.QuantizedDnn.loadFromFile(net_model_path)
     x = F.synth_features(n, 432, seed=500 + n % 89)
-    a = hidden_bytes(dnn, x, 0)
-    b = hidden_bytes(dnn, x, 1)
+    a, ran_a = launched(hidden_bytes, dnn, x, 0)
+    b, ran_b = launched(hidden_bytes, dnn, x, 1)
+    assert "pp.hid.fix" in ran_b and not any(k.startswith("gemm.hid.") or k.startswith("small.hid.") for k in ran_b), ran_b
+    assert not any(k.startswith("pp.") for k in ran_a) and any(k.startswith("gemm.hid.") or k.startswith("small.hid.") for k in ran_a), ran_a
     assert a.shape == (n, 2048) and np.array_equal(a, b)
     dnn.delete()
 
@@ -49,7 +52,8 @@ def test_role_split_layers_every_row_against_the_oracle(net_model_path, modes):
     n = 10000
     x = F.synth_features(n, 432, seed=21)
     dnn = api.QuantizedDnn.loadFromFile(net_model_path)
-    got = hidden_bytes(dnn, x, 1)
+    got, ran = launched(hidden_bytes, dnn, x, 1)
+    assert "pp.hid.fix" in ran and not any(k.startswith("gemm.hid.") for k in ran), ran
     want = Oracle(net_model_path).hidden_acts_mt(x)
     assert np.array_equal(got, want)
     dnn.delete()
@@ -63,8 +67,10 @@ def test_role_split_on_layers_without_saturating_pairs(tmp_models, modes):
     dnn = api.QuantizedDnn.loadFromFile(p)
     n = 5000
     x = F.synth_features(n, 432, seed=3)
-    a = hidden_bytes(dnn, x, 0)
-    b = hidden_bytes(dnn, x, 1)
+    a, ran_a = launched(hidden_bytes, dnn, x, 0)
+    b, ran_b = launched(hidden_bytes, dnn, x, 1)
+    assert "pp.hid.nofix" in ran_b and "pp.hid.fix" not in ran_b and not any(k.startswith("gemm.hid.") for k in ran_b), ran_b
+    assert "gemm.hid.ft256.prod_nofix" in ran_a and not any(k.startswith("pp.") for k in ran_a), ran_a
     assert np.array_equal(a, b)
     assert np.array_equal(b, Oracle(p).hidden_acts_mt(x))
     dnn.delete()
@@ -86,8 +92,10 @@ def test_role_split_with_corrections_firing_in_every_k_step(tmp_models, modes):
     dnn = api.QuantizedDnn.loadFromFile(p)
     n = 700
     x = F.synth_features(n, 432, seed=8)
-    a = hidden_bytes(dnn, x, 0)
-    b = hidden_bytes(dnn, x, 1)
+    a, ran_a = launched(hidden_bytes, dnn, x, 0)
+    b, ran_b = launched(hidden_bytes, dnn, x, 1)
+    assert "pp.hid.fix" in ran_b and not any(k.startswith("small.hid.") for k in ran_b), ran_b
+    assert "small.hid.nt64.prod" in ran_a and not any(k.startswith("pp.") for k in ran_a), ran_a
     assert np.array_equal(a, b)
     orc = Oracle(p)
     _, taps = orc.calculate(x[:32], taps=True)

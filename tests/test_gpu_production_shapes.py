@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from fast_dnn_amd import api, formats as F
+from dispatch_ledger import chain_tile, launched
 from oracle.oracle import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -252,6 +253,9 @@ def test_layer0_128_node_tile_still_bit_exact():
 
     env = dict(os.environ, FDNN_L0_TN="128")
     here = os.path.dirname(os.path.abspath(__file__))
+    # the switch does select the 128-node tile in a child: the ledger's case for it (oracle parity + the names launched)
+    import dispatch_ledger as L
+    assert "l0.chain.jc12.tn128.prod" in L.run_case_in_child(L.by_id("l0.chain12.tn128.n700"))
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_parity.py"), "-q", "-x", "-m", "gpu", "-k",
                         "input_widths or tiny_golden or blob_export or ragged_batch"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
@@ -344,12 +348,19 @@ def test_mid_size_batches_on_the_128_node_shape(net_model_path, n):
     orc = Oracle(net_model_path)
     want, wt = orc.calculate(x[idx], taps=True)
     dnn = api.QuantizedDnn.loadFromFile(net_model_path)
-    ctx = dnn.getNewLazyContext(n)
-    ctx.calculateUntilOutput(x)
-    hid = ctx.hiddenActivations()
-    ctx.delete()
+    def hidden():
+        ctx = dnn.getNewLazyContext(n)
+        ctx.calculateUntilOutput(x)
+        h = ctx.hiddenActivations()
+        ctx.delete()
+        return h
+
+    hid, ran = launched(hidden)
+    assert {k for k in ran if k.startswith(("gemm.hid.", "small.hid.", "chain.", "pp."))} == {"gemm.hid.ft128.nt128.prod"}, ran
     assert (hid[idx] == wt["u8_acts"][-1]).all()
-    acc, p = dnn.productionOutputAcc(x, 64, probs=True)
+    (acc, p), ran = launched(dnn.productionOutputAcc, x, 64, probs=True)
+    assert {k for k in ran if k.startswith("gemm.hid.")} == {"gemm.hid.ft128.nt128.prod"}, ran
+    assert {k for k in ran if k.startswith(("gemm.out.", "small.out.", "ppo."))} <= {"gemm.out.ft256.fused", "gemm.out.ft320.fused", "gemm.out.ft256.plain", "gemm.out.ft320.plain"}, ran  # the 256-node tiles
     dnn.delete()
     assert np.abs(p[idx] - want).max() <= TIGHT
     _, wt64 = orc.calculate(x[::64], taps=True)
@@ -373,6 +384,7 @@ from fast_dnn_amd import api, formats as F
 x = F.synth_features(10000, 432, seed=41)
 masks = F.generate_masks_fast(10000, 8000, 0.40, 0.03, seed=3)
 dnn = api.QuantizedDnn.loadFromFile({net_model_path!r})
+api.launch_record(True)
 def dense():
     return dnn.calculate(x)
 def lazy():
@@ -386,6 +398,7 @@ if sys.argv[2] == "dense-first":
 else:
     q = lazy(); p = dense()
 print("GIVEUPS", dnn.fuseGiveups())
+print("RAN", " ".join(sorted(api.launch_counts())))
 dnn.delete()
 np.save(sys.argv[1], np.concatenate([p[::7], q[::7]]))
 """
@@ -402,6 +415,14 @@ np.save(sys.argv[1], np.concatenate([p[::7], q[::7]]))
         assert (gave_up > 0) == tag.startswith("giveup"), (tag, gave_up)
         if tag.startswith("giveup"):
             assert r.stderr.count("sat out its bounded wait") == 1
+        # each side ran what its tag says: the fused instances (dense: the role-split kernel) without a scale pass, or
+        # the plain / masked instances followed by the scale pass
+        ran = set(r.stdout.split("RAN")[1].split("\n")[0].split())
+        outs_ran = {k for k in ran if k.startswith(("gemm.out.", "ppo.", "norm."))}
+        if tag == "fused":
+            assert outs_ran == {"ppo.out.fix", "gemm.out.ft320.fused_masked"}, ran
+        elif tag == "unfused":
+            assert outs_ran == {"gemm.out.ft320.plain", "gemm.out.ft320.masked", "norm.rows"}, ran
         outs.append(np.load(f))
     assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2]) and np.array_equal(outs[0], outs[3])
     assert np.abs(outs[0].sum(1, dtype=np.float64) - 1).max() < 1e-4
@@ -417,7 +438,10 @@ def test_both_screening_kernels_are_bit_exact(net_model_path, kind):
     x = F.synth_features(n, 432, seed=12)
     dnn = api.QuantizedDnn.loadFromFile(net_model_path)
     dnn.setInputLayerKernel(kind)
-    got, recomputed = dnn.layer0(x)
+    (got, recomputed), ran = launched(dnn.layer0, x)
+    l0_ran = {k for k in ran if k.startswith("l0.")}
+    if not os.environ.get("FDNN_L0_NO_SCREEN") and not os.environ.get("FDNN_L0_NO_SPLIT"):
+        assert l0_ran == ({"l0.digits", "l0.split.n128", "l0.fixlist.lpo4"} if kind == 4 else {"l0.screen.f128", "l0.fix.tiles"}), (kind, ran)
     screened = not os.environ.get("FDNN_L0_NO_SCREEN") and not (kind == 4 and os.environ.get("FDNN_L0_NO_SPLIT"))
     if screened:  # (diagnosis switches take the screening paths out: the bytes below must still be right)
         assert 0 < recomputed < 0.05 * n * 2048, recomputed
@@ -768,6 +792,9 @@ def test_layers_without_saturating_pairs_take_the_walk_free_instances(tmp_models
     x = F.synth_features(n, 432, seed=19)
     masks = F.generate_masks_fast(n, topo[-1], 0.40, 0.03, seed=23)
     idx = np.array(sorted(set(np.linspace(0, n - 1, 24).astype(int)) | {319, 320, n - 1}))
+    # frame tile of the 2048-node output layer (qgemm_frame_tile's cost model, 8 node tiles): 10 000 frames are one round of
+    # 320-frame tiles; 12 000 are two rounds either way, and the 256-frame tiles' rounds are cheaper
+    out_tile = 320 if n == 10000 else 256
     for name, net in (("clean", clean), ("mixed", mixed)):
         p = os.path.join(tmp_models, f"nofix_{name}.bin")
         F.write_model_bin(p, net)
@@ -782,9 +809,21 @@ def test_layers_without_saturating_pairs_take_the_walk_free_instances(tmp_models
         for mode in (0, 1):
             api.set_chain(mode, 1)
             ctx = dnn.getNewLazyContext(n)
-            ctx.calculateUntilOutput(x)
+            _, ran = launched(ctx.calculateUntilOutput, x)
+            hidden_ran = {k for k in ran if k.startswith(("gemm.hid.", "chain.", "pp.", "small.hid."))}
+            if mode == 0:    # a launch per layer: the walk-free instance for every pair-free layer, the walk for the third layer of `mixed`
+                assert hidden_ran == ({"gemm.hid.ft256.prod_nofix"} if name == "clean" else {"gemm.hid.ft256.prod_nofix", "gemm.hid.ft256.prod"}), (name, ran)
+            else:            # chained: one kernel for all layers -- walk-free only if no layer has pairs
+                assert hidden_ran == {"chain.ft%d.%s" % (chain_tile(n), "nofix" if name == "clean" else "fix")}, (name, ran)
             hid[mode] = ctx.hiddenActivations()[idx].copy()
-            lazy = ctx.calculateForOutputNodesBatch(masks)[idx].copy() if mode == 0 else None
+            lazy = None
+            if mode == 0:
+                lazy, ran = launched(ctx.calculateForOutputNodesBatch, masks)
+                lazy = lazy[idx].copy()
+                # the masked instance of the layer's tile: fused and, for the pair-free output layer of `clean`, walk-free
+                # (or the scale-pass form where this process may not fuse: FDNN_FUSE_NORM=0, a second process on the device)
+                assert {k for k in ran if k.startswith(("gemm.out.", "small.out."))} in (
+                    {"gemm.out.ft%d.fused_masked%s" % (out_tile, "_nofix" if name == "clean" else "")}, {"gemm.out.ft%d.masked" % out_tile}), (name, ran)
             ctx.delete()
             if lazy is not None:
                 assert np.abs(lazy - orc.lazy(x[idx], masks[idx])).max() <= TIGHT, name

@@ -9,6 +9,9 @@ import numpy as np, torch
 from fast_dnn_amd import api, formats as F
 from oracle.oracle import Oracle
 
+api.launch_record(True)  # which kernel instances the run reaches is printed at the end (information only)
+api.launch_reset()
+
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
 p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "fdnn_net_seed1_gauss.bin")
@@ -52,4 +55,6 @@ for case in range(cases):
     worst = max(worst, err, lerr)
     if case % 10 == 9:
         print(f"{case + 1} cases, worst soft-max error {worst:.2e}, {time.time() - t0:.0f} s", flush=True)
+_names = api.launch_names()
+print(f"launched {len(api.launch_counts())} distinct kernel instances of the {sum(1 for f in _names.values() if not f & api.LAUNCH_ABLATION)} the shipped library can launch (tests/dispatch_ledger.py covers them case by case)")
 print(f"net-size fuzz ok: {cases} cases in {time.time() - t0:.0f} s, worst soft-max error {worst:.2e}")

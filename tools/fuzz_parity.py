@@ -1,6 +1,6 @@
 """Randomised parity run against the CPU oracle (test infrastructure): random topologies (input
 width x4, hidden x16, any output width), weight scales from no saturating pairs to most pairs
-saturating, both layer-0 flavours, random batch sizes across every kernel-selection branch, random masks.
+saturating, both layer-0 flavours, random batch sizes across the kernel-selection rules (how many instances a run reached is printed at its end), random masks.
 Checked per case: every layer's u8 activations and int32 accumulators through the tap kernels
 (bit-exact), the production kernels' last hidden layer (hiddenActivations, bit-exact), dense and
 lazy soft-max (<= 2e-6), and the dense and masked results through the scoring loop (bit-identical to the calls).
@@ -10,6 +10,9 @@ sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import numpy as np
 from fast_dnn_amd import api, formats as F
 from oracle.oracle import Oracle
+
+api.launch_record(True)  # which kernel instances the run reaches is printed at the end (information only)
+api.launch_reset()
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 2024)
@@ -80,4 +83,6 @@ for case in range(cases):
     worst = max(worst, err, lerr)
     if case % 10 == 9:
         print(f"{case + 1} cases, worst soft-max error {worst:.2e}, {time.time() - t0:.0f} s", flush=True)
+_names = api.launch_names()
+print(f"launched {len(api.launch_counts())} distinct kernel instances of the {sum(1 for f in _names.values() if not f & api.LAUNCH_ABLATION)} the shipped library can launch (tests/dispatch_ledger.py covers them case by case)")
 print(f"fuzz ok: {cases} cases in {time.time() - t0:.0f} s, worst soft-max error {worst:.2e}")
