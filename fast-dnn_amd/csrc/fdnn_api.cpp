@@ -1,0 +1,712 @@
+// fdnn_api.cpp -- the scoring C-ABI (include/fdnn.h): model load / free / queries, calculation contexts, the one-call
+// entry points (dense, lazy, raw frames) and streams of raw frames.  Argument checks and the choice of a chunk list; the
+// passes themselves are fdnn_runtime.cpp's.
+#include <hip/hip_runtime.h>
+#include <emmintrin.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "fdnn_internal.hpp"
+
+using namespace fdnn;
+
+namespace fdnn {
+
+int calculate_on_one_device(fdnn_model *m, const float *x, int n, int dim, int batch_hint, float *out) {
+  (void)batch_hint;
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;  // QuantizedDnn.java:154-156
+  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  if (m->batcher) {  // coalesced with the other callers' utterances (fdnn_server.cpp)
+    uint64_t ticket = 0;
+    return batcher_wait(m->batcher, fdnn_server_submit(m->batcher, x, n, nullptr, out, &ticket), &ticket);
+  }
+  return score_chunks(m, {{0, n}}, {.who = "fdnn_calculate", .x = x, .out = out});
+}
+
+int calculate_raw_rows(fdnn_model *m, const SpliceRef &spec, const float *raw, int n, int a, int b, float *out) {
+  if (b <= a) return FDNN_OK;
+  if (m->batcher) {  // coalesced with the other callers' raw utterances (fdnn_server.cpp), each with its own edges
+    uint64_t ticket = 0;
+    return batcher_wait(m->batcher, server_submit_raw_rows(m->batcher, spec, raw, n, a, b, nullptr, out, &ticket), &ticket);
+  }
+  int fa, fb;  // the raw frames those rows reference travel once
+  splice_halo(*spec, n, a, b, &fa, &fb);
+  const std::vector<SpliceSeg> segs{SpliceSeg{a, a - fa, -fa, n - 1 - fa}};
+  return score_chunks(m, frame_chunks(b - a, m),
+                      {.who = "fdnn_calculate_raw", .spec = spec.get(), .segs = &segs, .raw = raw + size_t(fa) * size_t(spec->raw_dim), .raw_frames = fb - fa, .row0 = a, .out = out});
+}
+
+}  // namespace fdnn
+
+// what upload_model / build_l0_image allocated for a model (any of it may be missing: a load that failed half way)
+static void free_device_side(fdnn_model *m) {
+  hipFree(m->d_blob);
+  hipFree(m->d_w0t);
+  hipFree(m->d_w0norm);
+  hipFree(m->d_w0d);
+  hipFree(m->d_w0stat);
+  hipFree(m->d_lutpair);
+  hipFree(m->d_l0_stats);
+  if (m->h_fuse_fault) hipHostFree(m->h_fuse_fault);
+}
+
+extern "C" {
+
+const char *fdnn_version(void) { return "fast-dnn_amd 0.1 (gfx950)"; }
+
+int fdnn_device_count(void) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess) return 0;
+  return count;
+}
+
+int fdnn_model_load_on(const char *path, float cutoff, int device, fdnn_model **out) {
+  if (!path || !out) return fail(FDNN_E_ARG, "null argument");
+  *out = nullptr;
+  fdnn_model *m = new fdnn_model();
+  std::string msg;
+  int rc = fdnn::load_host_model(path, cutoff, &m->hm, &msg);
+  if (rc) {
+    delete m;
+    return fail(rc, msg);
+  }
+  m->device = device;
+  rc = upload_model(m);
+  if (!rc) (void)fdnn_device_shared(device);  // take (or find taken) the device's process marker now, not at the first large call
+  if (rc) {
+    free_device_side(m);
+    delete m;
+    return rc;
+  }
+  if (const char *env = std::getenv("FDNN_BATCHER")) {  // max_frames[:depth[:linger_us]]
+    int mf = 0, depth = 2, linger = 0;
+    if (std::sscanf(env, "%d:%d:%d", &mf, &depth, &linger) >= 1 && mf > 0) {
+      rc = fdnn_model_enable_batcher(m, mf, depth, linger);
+      if (rc) {
+        fdnn_model_free(m);
+        return rc;
+      }
+    }
+  }
+  *out = m;
+  return FDNN_OK;
+}
+
+int fdnn_model_load(const char *path, float cutoff, fdnn_model **out) {
+  // FDNN_DEVICES="0,1,2,3" or "all": one replica per listed device, weights distributed at load,
+  // fdnn_calculate on the returned handle shards its frames over them (fdnn_group.cpp) -- how the
+  // unmodified Java class reaches every GPU of the node.
+  if (const char *env = std::getenv("FDNN_DEVICES")) {
+    std::vector<int> devs;
+    if (std::strcmp(env, "all") == 0) {
+      for (int d = 0; d < fdnn_device_count(); ++d) devs.push_back(d);
+    } else {
+      for (const char *q = env; *q;) {
+        char *end = nullptr;
+        const long v = std::strtol(q, &end, 10);
+        if (end == q) break;
+        devs.push_back(int(v));
+        q = (*end == ',') ? end + 1 : end;
+      }
+    }
+    if (devs.size() > 1) {
+      if (!out) return fail(FDNN_E_ARG, "null argument");
+      fdnn_group *g = nullptr;
+      int rc = fdnn_group_load(path, cutoff, devs.data(), int(devs.size()), &g);
+      if (rc) return rc;
+      fdnn_group_attach(g);
+      *out = fdnn_group_model(g, 0);
+      return FDNN_OK;
+    }
+    if (devs.size() == 1) return fdnn_model_load_on(path, cutoff, devs[0], out);
+  }
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  return fdnn_model_load_on(path, cutoff, dev, out);
+}
+
+int fdnn_model_enable_batcher(fdnn_model *m, int max_frames, int depth, int linger_us) {
+  if (!m) return fail(FDNN_E_ARG, "null model");
+  if (m->batcher) return fail(FDNN_E_STATE, "the model already has a batcher");
+  fdnn_server *srv = nullptr;
+  int rc = fdnn_server_create(m, max_frames, depth, &srv);
+  if (!rc) rc = fdnn_server_set_linger_us(srv, linger_us);
+  if (rc) {
+    fdnn_server_free(srv);
+    return rc;
+  }
+  m->batcher = srv;
+  return FDNN_OK;
+}
+
+void fdnn_model_free(fdnn_model *m) {
+  if (!m) return;
+  if (m->group) {  // the leader of an attached group: the group owns every replica, this one included
+    fdnn_group_free(m->group);
+    return;
+  }
+  if (m->batcher) fdnn_server_free(m->batcher);
+  m->batcher = nullptr;
+  for (fdnn_ctx *c : m->pool) destroy_ctx(c);
+  m->pool.clear();
+  {
+    DeviceGuard g(m->device);
+    free_device_side(m);
+  }
+  delete m;
+}
+
+int fdnn_model_input_dim(const fdnn_model *m) { return m ? m->hm.hdr.in_dim : -1; }
+int fdnn_model_output_dim(const fdnn_model *m) { return m ? m->hm.hdr.out_dim : -1; }
+int fdnn_model_hidden_dim(const fdnn_model *m) { return m ? m->hm.hdr.hidden : -1; }
+int fdnn_model_layer_count(const fdnn_model *m) { return m ? m->hm.hdr.n_q + 1 : -1; }  // jni_dnn.cc:155
+int fdnn_model_device(const fdnn_model *m) { return m ? m->device : -1; }
+
+int fdnn_model_layer_dim(const fdnn_model *m, int index) {
+  if (!m) return -1;
+  const BlobHeader &h = m->hm.hdr;
+  if (index < 0) return -1;
+  if (index == 0) return h.hidden;           // input_layer()->node_count(), jni_dnn.cc:144-146
+  if (index >= h.n_q) return -1;             // layers()[index] must exist (see fdnn.h)
+  return h.q[index].rows;                    // layers()[index]->node_count(), jni_dnn.cc:147
+}
+
+int fdnn_model_set_l0_fma(fdnn_model *m, int on) {
+  if (!m) return fail(FDNN_E_ARG, "null model");
+  m->l0_fma = on ? 1 : 0;
+  return FDNN_OK;
+}
+
+int fdnn_device_shared(int device) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(FDNN_E_ARG, "no such device");
+  return device_marker_state(device) == 1 ? 0 : 1;
+}
+
+// ---------------------------------------------------------------- contexts
+int fdnn_ctx_create(fdnn_model *m, int n, int batch_hint, fdnn_ctx **out) {
+  (void)batch_hint;  // frame blocking is a CPU cache device; results never depend on it
+  if (!m || !out) return fail(FDNN_E_ARG, "null argument");
+  if (n < 0) return fail(FDNN_E_ARG, "negative frame count");
+  return make_ctx(m, n, out);
+}
+
+void fdnn_ctx_free(fdnn_ctx *c) {
+  if (!c) return;
+  destroy_ctx(c);
+}
+
+int fdnn_ctx_frame_count(const fdnn_ctx *c) { return c ? c->n : -1; }
+int fdnn_ctx_output_dim(const fdnn_ctx *c) { return c ? c->m->hm.hdr.out_dim : -1; }
+
+int fdnn_ctx_forward_hidden_device(fdnn_ctx *c, const float *d_x, void *stream) {
+  if (!c || (!d_x && c->n)) return fail(FDNN_E_ARG, "null argument");
+  if (c->n == 0) {
+    c->last = 0;
+    return FDNN_OK;
+  }
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  return run_hidden(c, d_x, s, nullptr);
+}
+
+int fdnn_ctx_forward_hidden(fdnn_ctx *c, const float *x) {
+  if (!c || (!x && c->n)) return fail(FDNN_E_ARG, "null argument");
+  if (c->n == 0) {
+    c->last = 0;
+    return FDNN_OK;
+  }
+  DeviceGuard g(c->m->device);
+  const BlobHeader &h = c->m->hm.hdr;
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_x, x, sizeof(float) * size_t(c->n) * h.in_dim, hipMemcpyHostToDevice, c->stream));
+  int rc = run_hidden(c, c->d_x, c->stream, nullptr);
+  use.leave();
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return FDNN_OK;
+}
+
+int fdnn_ctx_lazy_output_batch_device(fdnn_ctx *c, int first, int count, const int8_t *d_masks, float *d_out,
+                                      void *stream) {
+  if (!c || !d_out) return fail(FDNN_E_ARG, "null argument");
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  return run_output(c, {.first = first, .count = count, .d_masks = d_masks, .d_out = d_out}, s);
+}
+
+// masks [count][O] bytes (non-zero = active, dnn.cc:361) -> bits [count][ceil(O / 64)], 16 bytes per step
+static void pack_mask_rows(const int8_t *masks, int count, size_t O, uint64_t *bits) {
+  const size_t wpr = (O + 63) / 64;
+  const __m128i zero = _mm_setzero_si128();
+  for (int f = 0; f < count; ++f) {
+    const int8_t *mrow = masks + size_t(f) * O;
+    uint64_t *brow = bits + size_t(f) * wpr;
+    size_t k = 0;
+    for (size_t w = 0; w < wpr; ++w) {
+      uint64_t word = 0;
+      for (int q = 0; q < 4 && k + 16 <= O; ++q, k += 16) {
+        const __m128i v = _mm_loadu_si128(reinterpret_cast<const __m128i *>(mrow + k));
+        word |= uint64_t(uint32_t(~_mm_movemask_epi8(_mm_cmpeq_epi8(v, zero))) & 0xffffu) << (16 * q);
+      }
+      const size_t base = 64 * w;
+      for (; k < O && k < base + 64; ++k) word |= uint64_t(mrow[k] != 0) << (k - base);
+      brow[w] = word;
+    }
+  }
+}
+
+int fdnn_ctx_lazy_output_batch(fdnn_ctx *c, int first, int count, const int8_t *masks, float *out) {
+  if (!c || !out || !masks) return fail(FDNN_E_ARG, "null argument");
+  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
+  if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
+  if (count == 0) return FDNN_OK;
+  DeviceGuard g(c->m->device);
+  const BlobHeader &h = c->m->hm.hdr;
+  const size_t O = size_t(h.out_dim);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  if (count <= kPinFrames) {  // the per-frame protocol: no copy commands (see fdnn_ctx)
+    std::memcpy(c->h_mask_pin, masks, size_t(count) * O);
+    // (blocks of 1..8 frames go through the small GEMM kernel's 32-frame tile, which reads the mask bytes straight from the
+    // host-mapped staging; nets the small kernel cannot take -- K > 2048, no validated fast division -- fall to the large
+    // tiles behind a mask_pack pass over the same staging)
+    const int rc = run_output(c, {.first = first, .count = count, .d_masks = c->d_mask_pin, .d_out = c->d_out, .d_final = c->d_out_pin}, c->stream);
+    use.leave();
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->h_out_pin, sizeof(float) * size_t(count) * O);
+    return FDNN_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_mask, masks, size_t(count) * O, hipMemcpyHostToDevice, c->stream));
+  c->mask_bits_packed = false;
+  int rc = run_output(c, {.first = first, .count = count, .d_masks = c->d_mask, .d_out = c->d_out}, c->stream);
+  if (!rc) {
+    // the same masks as bits, for the compacted return (lazy_copy_out): on the host while the GPU computes, on the device
+    // by the pack kernel (a large batch's output kernel has run it already)
+    const size_t wpr = (O + 63) / 64;
+    std::vector<uint64_t> hb(size_t(count) * wpr, 0);
+    pack_mask_rows(masks, count, O, hb.data());
+    if (!c->mask_bits_packed) fdnn::launch_mask_pack(c->d_mask, c->d_mask_bits, count, int(O), c->stream);  // (a large batch's output kernel has)
+    rc = lazy_copy_out(c, count, c->d_mask_bits, hb.data(), out, c->stream);
+  }
+  return rc;
+}
+
+int fdnn_ctx_lazy_output_batch_bits_device(fdnn_ctx *c, int first, int count, const uint64_t *d_bits, float *d_out, void *stream) {
+  if (!c || !d_out || !d_bits) return fail(FDNN_E_ARG, "null argument");
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  return run_output(c, {.first = first, .count = count, .d_bits = d_bits, .d_out = d_out}, s);
+}
+
+int fdnn_ctx_lazy_output_batch_bits(fdnn_ctx *c, int first, int count, const uint64_t *bits, float *out) {
+  if (!c || !out || !bits) return fail(FDNN_E_ARG, "null argument");
+  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
+  if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
+  if (count == 0) return FDNN_OK;
+  DeviceGuard g(c->m->device);
+  const BlobHeader &h = c->m->hm.hdr;
+  const size_t O = size_t(h.out_dim), wpr = (O + 63) / 64;
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_mask_bits, bits, sizeof(uint64_t) * size_t(count) * wpr, hipMemcpyHostToDevice, c->stream));
+  int rc = run_output(c, {.first = first, .count = count, .d_bits = c->d_mask_bits, .d_out = c->d_out}, c->stream);
+  if (!rc) rc = lazy_copy_out(c, count, c->d_mask_bits, bits, out, c->stream);
+  return rc;
+}
+
+int fdnn_ctx_lazy_output(fdnn_ctx *c, int frame, const int8_t *mask, float *out) {
+  return fdnn_ctx_lazy_output_batch(c, frame, 1, mask, out);
+}
+
+int fdnn_ctx_output_device(fdnn_ctx *c, float *d_out, void *stream) {
+  if (!c || !d_out) return fail(FDNN_E_ARG, "null argument");
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  return run_output(c, {.count = c->n, .d_out = d_out}, s);
+}
+
+int fdnn_ctx_output(fdnn_ctx *c, float *out) {
+  if (!c || !out) return fail(FDNN_E_ARG, "null argument");
+  if (c->n == 0) return FDNN_OK;
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  int rc = run_output(c, {.count = c->n, .d_out = c->d_out}, c->stream);
+  use.leave();
+  if (rc) return rc;
+  return copy_out(out, c->d_out, sizeof(float) * size_t(c->n) * c->m->hm.hdr.out_dim, c->stream);
+}
+
+int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
+  if (!c || !out) return fail(FDNN_E_ARG, "null argument");
+  if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");
+  if (c->n == 0) return FDNN_OK;
+  DeviceGuard g(c->m->device);
+  std::vector<int8_t> tmp(size_t(c->n) * c->act_ld);
+  HIP_TRY(ctx_enter(c, c->stream));  // the hidden layers may have been enqueued on a caller's stream
+  HIP_TRY(hipMemcpyAsync(tmp.data(), c->d_act[c->last], tmp.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  unpack_act_rows(tmp.data(), size_t(c->act_ld), c->n, c->m->hm.hdr.hidden, out);
+  return FDNN_OK;
+}
+
+// ---------------------------------------------------------------- dense path
+int fdnn_calculate_device(fdnn_model *m, const float *d_x, int n, float *d_out, void *stream) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;
+  if (!d_x || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_device", .d_x = d_x, .d_out = d_out, .stream = static_cast<hipStream_t>(stream)});
+}
+
+int fdnn_calculate(fdnn_model *m, const float *x, int n, int dim, int batch_hint, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;  // QuantizedDnn.java:154-156
+  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
+  if (m->group) return fdnn_group_calculate(m->group, x, n, dim, batch_hint, out);  // sharded over the node's devices
+  return fdnn::calculate_on_one_device(m, x, n, dim, batch_hint, out);
+}
+
+// One-call lazy scoring: hidden layers + masked output + compacted return in ONE call and ONE stream synchronisation
+// (a LazyContext costs two calls and two synchronisations per utterance: calculateUntilOutput, then the masked rows).
+int fdnn_calculate_lazy_bits(fdnn_model *m, const float *x, int n, int dim, const uint64_t *bits, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;
+  if (!x || !out || !bits) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  if (m->batcher) {  // coalesced with the other callers' lazy utterances (fdnn_server.cpp), rows back compacted
+    uint64_t ticket = 0;
+    return batcher_wait(m->batcher, fdnn_server_submit_lazy_bits(m->batcher, x, n, bits, out, &ticket), &ticket);
+  }
+  // (very large calls: chunk by chunk, as the dense call)
+  return score_chunks(m, stride_chunks(n), {.who = "fdnn_calculate_lazy_bits", .x = x, .bits = bits, .out = out});
+}
+
+int fdnn_calculate_lazy(fdnn_model *m, const float *x, int n, int dim, const int8_t *masks, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;
+  if (!masks) return fail(FDNN_E_ARG, "null buffer");
+  const size_t O = size_t(m->hm.hdr.out_dim), wpr = (O + 63) / 64;
+  std::vector<uint64_t> hb(size_t(n) * wpr);
+  pack_mask_rows(masks, n, O, hb.data());
+  return fdnn_calculate_lazy_bits(m, x, n, dim, hb.data(), out);
+}
+
+int fdnn_calculate_lazy_bits_device(fdnn_model *m, const float *d_x, int n, const uint64_t *d_bits, float *d_out, void *stream) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;
+  if (!d_x || !d_out || !d_bits) return fail(FDNN_E_ARG, "null buffer");
+  return score_chunks(m, frame_chunks(n, m),
+                      {.who = "fdnn_calculate_lazy_bits_device", .d_x = d_x, .d_bits = d_bits, .d_out = d_out, .stream = static_cast<hipStream_t>(stream)});
+}
+
+// ---------------------------------------------------------------- raw feature frames (the <Splice> block on the device)
+int fdnn_model_set_splice(fdnn_model *m, const int *offsets, int count, int raw_dim) {
+  if (!m) return fail(FDNN_E_ARG, "null model");
+  fdnn::SpliceRef spec;  // (a new object: streams, queued submissions and calls in progress keep the one they hold)
+  if (count != 0 || raw_dim != 0) {  // (count == 0 with raw_dim == 0 clears the spec; an empty spec of some width is an error)
+    if (count < 1 || count > fdnn::kSpliceMaxOffsets) return fail(FDNN_E_ARG, "a splice spec has 1 .. 64 offsets");
+    if (!offsets) return fail(FDNN_E_ARG, "null offsets");
+    for (int i = 0; i < count; ++i)
+      if (offsets[i] < -64 || offsets[i] > 64) return fail(FDNN_E_ARG, "splice offsets must lie in -64 .. 64");
+    const int in_dim = m->hm.hdr.in_dim;
+    if (raw_dim < 1 || (long long)count * raw_dim > in_dim)
+      return fail(FDNN_E_ARG, std::to_string(count) + " x " + std::to_string(raw_dim) + " spliced values do not fit the input width " +
+                                  std::to_string(in_dim));
+    auto sp = std::make_shared<fdnn::SpliceSpec>();
+    sp->offsets.assign(offsets, offsets + count);
+    sp->raw_dim = raw_dim;
+    for (int o : sp->offsets) {
+      sp->left = std::max(sp->left, -o);
+      sp->right = std::max(sp->right, o);
+    }
+    spec = sp;
+  }
+  // one spec for the whole group when the model leads one (the replicas score its shards; fdnn_group_attach copies the
+  // leader's spec to them as well, and a sharded call hands every replica the leader's)
+  const int replicas = m->group ? fdnn_group_size(m->group) : 1;
+  for (int r = 0; r < replicas; ++r) (m->group ? fdnn_group_model(m->group, r) : m)->splice = spec;
+  return FDNN_OK;
+}
+
+int fdnn_model_get_splice(const fdnn_model *m, int *offsets, int cap, int *raw_dim) {
+  if (!m || cap < 0 || (cap > 0 && !offsets)) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  const int count = spec ? int(spec->offsets.size()) : 0;
+  for (int i = 0; i < cap && i < count; ++i) offsets[i] = spec->offsets[size_t(i)];
+  if (raw_dim) *raw_dim = spec ? spec->raw_dim : 0;
+  return count;
+}
+
+int fdnn_calculate_raw(fdnn_model *m, const float *raw, int n, int raw_dim, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  int rc = fdnn::splice_check(spec, raw_dim);
+  if (rc) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
+  // as fdnn_calculate: sharded over an attached group first (each replica uploads its shard + halo, through its own batcher
+  // when it has one), else through the model's batcher, else on the model's device
+  if (m->group) return fdnn::group_calculate_raw(m->group, spec, raw, n, out);
+  return fdnn::calculate_raw_rows(m, spec, raw, n, 0, n, out);
+}
+
+int fdnn_calculate_raw_device(fdnn_model *m, const float *d_raw, int n, const int *seg_starts, int n_segs, float *d_out, void *stream) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  int rc = fdnn::splice_check(spec, -1);
+  if (rc) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!d_raw || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  std::vector<fdnn::SpliceSeg> segs;
+  if (!seg_starts) {
+    segs.push_back(fdnn::SpliceSeg{0, 0, 0, n - 1});
+  } else {
+    if (n_segs < 1 || seg_starts[0] != 0) return fail(FDNN_E_ARG, "a segment table starts with 0");
+    for (int k = 0; k < n_segs; ++k) {
+      const int a = seg_starts[k], b = k + 1 < n_segs ? seg_starts[k + 1] : n;
+      if (b <= a || b > n) return fail(FDNN_E_ARG, "segment starts must ascend strictly and lie below n");
+      segs.push_back(fdnn::SpliceSeg{a, a, a, b - 1});
+    }
+  }
+  // each chunk's rows spliced into the context's frame buffer, then scored as usual
+  return score_chunks(m, frame_chunks(n, m),
+                      {.who = "fdnn_calculate_raw_device", .spec = spec.get(), .segs = &segs, .d_raw = d_raw, .raw_frames = n, .d_out = d_out, .stream = static_cast<hipStream_t>(stream)});
+}
+
+int fdnn_calculate_lazy_bits_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const uint64_t *bits, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  int rc = fdnn::splice_check(spec, raw_dim);
+  if (rc) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!raw || !out || !bits) return fail(FDNN_E_ARG, "null buffer");
+  if (m->batcher) {
+    uint64_t ticket = 0;
+    return batcher_wait(m->batcher, server_submit_raw_rows(m->batcher, spec, raw, n, 0, n, bits, out, &ticket), &ticket);
+  }
+  const std::vector<SpliceSeg> segs{SpliceSeg{0, 0, 0, n - 1}};
+  return score_chunks(m, stride_chunks(n),  // (chunks as fdnn_calculate_lazy_bits)
+                      {.who = "fdnn_calculate_lazy_bits_raw", .spec = spec.get(), .segs = &segs, .raw = raw, .raw_frames = n, .bits = bits, .out = out});
+}
+
+int fdnn_ctx_forward_hidden_raw(fdnn_ctx *c, const float *raw) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  const fdnn::SpliceRef spec = c->m->splice;
+  int rc = fdnn::splice_check(spec, -1);
+  if (rc) return rc;
+  if (c->n == 0) {
+    c->last = 0;
+    return FDNN_OK;
+  }
+  if (!raw) return fail(FDNN_E_ARG, "null argument");
+  DeviceGuard g(c->m->device);
+  const size_t D = size_t(spec->raw_dim);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  rc = fdnn::ctx_raw_reserve(c, size_t(c->n), spec->raw_dim);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->d_raw, raw, sizeof(float) * size_t(c->n) * D, hipMemcpyHostToDevice, c->stream));
+  fdnn::splice_rows(*spec, c->m->hm.hdr.in_dim, c->d_raw, c->n, {fdnn::SpliceSeg{0, 0, 0, c->n - 1}}, 0, c->n, c->d_x, c->stream);
+  rc = run_hidden(c, c->d_x, c->stream, nullptr);
+  use.leave();
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return FDNN_OK;
+}
+
+}  // extern "C"
+
+// A stream of raw frames (fdnn_stream_*).  Its device buffer holds global frames [base, base + len): the frames still to be
+// read by rows not emitted yet -- at most L + R of them between pushes (L / R: the left / right context of the offsets) --
+// and the push's new ones.  Before a push the kept frames move to the front of the other buffer of a pair (device to
+// device, L + R frames): nothing is uploaded twice.
+struct fdnn_stream {
+  fdnn_model *m = nullptr;
+  fdnn_ctx *c = nullptr;  // the stream's own context: max_chunk + R frames
+  fdnn::SpliceRef spec;   // the model's spec when the stream was made: every push splices with it
+  int raw_dim = 0, max_chunk = 0, left = 0, right = 0;
+  float *d_buf[2] = {nullptr, nullptr};
+  int cur = 0;
+  long long base = 0, len = 0, pushed = 0, emitted = 0;
+  bool ended = false;
+};
+
+extern "C" {
+
+int fdnn_stream_create(fdnn_model *m, int max_chunk, fdnn_stream **out) {
+  if (!m || !out) return fail(FDNN_E_ARG, "null argument");
+  *out = nullptr;
+  const fdnn::SpliceRef spec = m->splice;
+  int rc = fdnn::splice_check(spec, -1);
+  if (rc) return rc;
+  if (max_chunk < 1) return fail(FDNN_E_ARG, "max_chunk must be positive");
+  DeviceGuard g(m->device);
+  fdnn_stream *s = new fdnn_stream();
+  s->m = m;
+  s->spec = spec;
+  s->raw_dim = spec->raw_dim;
+  s->max_chunk = max_chunk;
+  s->left = spec->left;
+  s->right = spec->right;
+  rc = fdnn::make_ctx(m, max_chunk + s->right, &s->c);
+  const size_t frames = size_t(max_chunk) + size_t(s->left) + size_t(s->right);
+  for (int k = 0; k < 2 && !rc; ++k)
+    if (hipMalloc(reinterpret_cast<void **>(&s->d_buf[k]), sizeof(float) * frames * size_t(s->raw_dim)) != hipSuccess)
+      rc = fail(FDNN_E_NOMEM, "stream buffer of " + std::to_string(frames) + " raw frames");
+  if (rc) {
+    fdnn_stream_free(s);
+    return rc;
+  }
+  s->c->n = 0;
+  *out = s;
+  return FDNN_OK;
+}
+
+void fdnn_stream_free(fdnn_stream *s) {
+  if (!s) return;
+  DeviceGuard g(s->m->device);
+  if (s->c) fdnn::destroy_ctx(s->c);  // (synchronises the stream's work)
+  hipFree(s->d_buf[0]);
+  hipFree(s->d_buf[1]);
+  delete s;
+}
+
+int fdnn_stream_reset(fdnn_stream *s) {
+  if (!s) return fail(FDNN_E_ARG, "null stream");
+  s->base = s->len = s->pushed = s->emitted = 0;
+  s->ended = false;
+  return FDNN_OK;
+}
+
+int fdnn_stream_position(const fdnn_stream *s, int64_t *pushed, int64_t *emitted) {
+  if (!s) return fail(FDNN_E_ARG, "null stream");
+  if (pushed) *pushed = s->pushed;
+  if (emitted) *emitted = s->emitted;
+  return FDNN_OK;
+}
+
+fdnn_ctx *fdnn_stream_ctx(fdnn_stream *s) { return s ? s->c : nullptr; }
+
+int fdnn_stream_push(fdnn_stream *s, const float *raw, int n_raw, int end, float *out, int *n_out) {
+  if (!s || !n_out) return fail(FDNN_E_ARG, "null argument");
+  *n_out = 0;
+  if (s->ended) return fail(FDNN_E_STATE, "the stream has ended: fdnn_stream_reset starts the next utterance");
+  if (n_raw < 0 || n_raw > s->max_chunk) return fail(FDNN_E_ARG, "a push holds 0 .. max_chunk raw frames");
+  if (n_raw > 0 && !raw) return fail(FDNN_E_ARG, "null raw frames");
+  fdnn_model *m = s->m;
+  fdnn_ctx *c = s->c;
+  DeviceGuard g(m->device);
+  const size_t D = size_t(s->raw_dim);
+  hipStream_t st = c->stream;
+  CtxUse use;  // (left when the push returns: every way out below has synchronised or failed)
+  HIP_TRY(use.enter(c, st));
+  // keep what rows not emitted yet still read: frames from emitted - L on
+  const long long keep = std::max(s->base, s->emitted - s->left);
+  if (keep > s->base) {
+    const long long kept = s->base + s->len - keep;
+    if (kept > 0)
+      HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur ^ 1], s->d_buf[s->cur] + size_t(keep - s->base) * D, sizeof(float) * size_t(kept) * D,
+                             hipMemcpyDeviceToDevice, st));
+    s->cur ^= 1;
+    s->base = keep;
+    s->len = kept;
+  }
+  if (n_raw > 0)
+    HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur] + size_t(s->len) * D, raw, sizeof(float) * size_t(n_raw) * D, hipMemcpyHostToDevice, st));
+  s->len += n_raw;
+  s->pushed += n_raw;
+  // complete rows: t + R has arrived; at the end of the stream every row, right-clamped to the last frame
+  const long long upto = end ? s->pushed : std::max(s->emitted, s->pushed - s->right);
+  const int rows = int(upto - s->emitted);
+  int rc = FDNN_OK;
+  c->n = rows;
+  c->last = rows ? -1 : 0;
+  if (rows > 0) {
+    const int lo = int(std::max(-s->base, -(1LL << 30)));  // global frame 0 -- the left clamp -- as a buffer index
+    const std::vector<fdnn::SpliceSeg> segs{fdnn::SpliceSeg{0, int(s->emitted - s->base), lo, int(s->pushed - 1 - s->base)}};
+    fdnn::splice_rows(*s->spec, m->hm.hdr.in_dim, s->d_buf[s->cur], int(s->len), segs, 0, rows, c->d_x, st);
+    if (out) {
+      rc = dense_pass_to_host(c, out, st);  // (synchronises)
+    } else {
+      rc = run_hidden(c, c->d_x, st, nullptr);  // hidden layers only: the context's lazy entry points take it from here
+      if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(FDNN_E_DEVICE, "fdnn_stream_push: stream synchronisation");
+    }
+  } else if (hipStreamSynchronize(st) != hipSuccess) {  // (the caller's raw frames have been read when the push returns)
+    rc = fail(FDNN_E_DEVICE, "fdnn_stream_push: stream synchronisation");
+  }
+  if (rc) return rc;
+  s->emitted = upto;
+  s->ended = end != 0;
+  *n_out = rows;
+  return FDNN_OK;
+}
+
+// ---------------------------------------------------------------- weight blob exchange
+int fdnn_model_blob_size(const fdnn_model *m, size_t *bytes) {
+  if (!m || !bytes) return fail(FDNN_E_ARG, "null argument");
+  *bytes = m->hm.blob.size();
+  return FDNN_OK;
+}
+
+int fdnn_model_export_blob(const fdnn_model *m, void *d_dst, size_t capacity, void *stream) {
+  if (!m || !d_dst) return fail(FDNN_E_ARG, "null argument");
+  if (capacity < m->hm.blob.size()) return fail(FDNN_E_ARG, "destination smaller than the blob");
+  DeviceGuard g(m->device);
+  HIP_TRY(hipMemcpyAsync(d_dst, m->d_blob, m->hm.blob.size(), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  return FDNN_OK;
+}
+
+int fdnn_model_import_blob(const void *d_src, size_t bytes, int device, fdnn_model **out) {
+  if (!d_src || !out) return fail(FDNN_E_ARG, "null argument");
+  *out = nullptr;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+    return fail(FDNN_E_DEVICE, "no HIP device available: this library has no CPU path");
+  if (device < 0 || device >= count) return fail(FDNN_E_ARG, "device index out of range");
+  DeviceGuard g(device);
+  std::vector<uint8_t> host(bytes);
+  HIP_TRY(hipMemcpy(host.data(), d_src, bytes, hipMemcpyDeviceToHost));
+  fdnn_model *m = new fdnn_model();
+  std::string msg;
+  int rc = fdnn::adopt_blob(std::move(host), &m->hm, &msg);
+  if (rc) {
+    delete m;
+    return fail(rc, msg);
+  }
+  m->device = device;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->d_blob), bytes);
+  if (e == hipSuccess) e = hipMemcpy(m->d_blob, d_src, bytes, hipMemcpyDeviceToDevice);
+  if (e != hipSuccess) {
+    if (m->d_blob) hipFree(m->d_blob);
+    delete m;
+    return fail(FDNN_E_DEVICE, std::string("blob import: ") + hipGetErrorString(e));
+  }
+  rc = build_l0_image(m);
+  if (rc) {
+    free_device_side(m);
+    delete m;
+    return rc;
+  }
+  *out = m;
+  return FDNN_OK;
+}
+
+}  // extern "C"

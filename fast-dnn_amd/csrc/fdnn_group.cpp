@@ -236,8 +236,6 @@ void frame_shard(int n, int world, int r, int *start, int *stop) {
   *stop = *start + base + (r < extra ? 1 : 0);
 }
 
-int calculate_on_one_device(fdnn_model *m, const float *x, int n, int dim, int batch_hint, float *out);  // fdnn_runtime.cpp
-
 }  // namespace fdnn
 
 namespace {

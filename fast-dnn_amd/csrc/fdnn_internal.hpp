@@ -1,6 +1,8 @@
 // fdnn_internal.hpp -- what the runtime's translation units share: the model / context objects
 // behind the opaque C-ABI handles and the enqueue helpers over them (fdnn_runtime.cpp), used by
-// the multi-stream server loop (fdnn_server.cpp).  Not installed; the boundary is include/fdnn.h.
+// the scoring C-ABI (fdnn_api.cpp), the debug / profiling / host-model calls (fdnn_debug.cpp),
+// the multi-stream server loop (fdnn_server.cpp) and the device group (fdnn_group.cpp).
+// Not installed; the boundary is include/fdnn.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -162,22 +164,43 @@ struct Taps {
 // submissions bring their buffers; the host path allocates what it needs in alloc_host_side)
 int make_ctx(fdnn_model *m, int n, fdnn_ctx **out, bool lean = false);
 void destroy_ctx(fdnn_ctx *c);
+int upload_model(fdnn_model *m);    // blob to the device, division check, then build_l0_image
+int build_l0_image(fdnn_model *m);  // the layer-0 weight images and the model's counters, from m->d_blob
+// Layer 0 of the context's n frames into d_act[0] (fdnn_debug_layer0* run it alone).
+void run_layer0(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps);
 // CalculateUntilLastHiddenLayer (dnn.cc:402-424) enqueued on s.
 int run_hidden(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps);
 // CalculateOutput / LazyOutputActivations (dnn.cc:428-454, :355-392) over frames [first, first+count):
-// the output GEMM (exp(z) rows + partial sums) on s, then the soft-max scale -- on s, or, when
-// `tail` is given, on that stream behind an event (`gemm_done`) recorded on s, so that the
-// HBM-bound scale pass can run under the next batch's layer 0.
-int run_output(fdnn_ctx *c, int first, int count, const int8_t *d_masks, float *d_out, hipStream_t s, const Taps *taps,
-               float *d_final = nullptr, hipStream_t tail = nullptr, hipEvent_t gemm_done = nullptr, const uint64_t *d_bits = nullptr);
-// (d_bits: the masks of the same frames as BITS, [count][ceil(O / 64)], bit b of word w = node 64 w + b; then d_masks may be
-// null -- large batches read the words as they are, small ones unpack them into the context's byte mask first)
+// the output GEMM (exp(z) rows + partial sums) on s, then the soft-max scale.  What a call does beyond "all of the
+// context's frames, dense, in place" is named in an OutputCall: every field defaults to null / zero.
+struct OutputCall {
+  int first = 0, count = 0;           // frames [first, first + count) of the context
+  const int8_t *d_masks = nullptr;    // [count][O] bytes, non-zero = active (null: dense, or d_bits)
+  const uint64_t *d_bits = nullptr;   // the masks of the same frames as BITS, [count][ceil(O / 64)], bit b of word w = node
+                                      // 64 w + b; then d_masks may be null -- large batches read the words as they are,
+                                      // small ones unpack them into the context's byte mask first
+  float *d_out = nullptr;             // [count][O]: exp(z) rows, scaled in place unless d_final says otherwise
+  float *d_final = nullptr;           // where the probabilities go (null: in place in d_out)
+  hipStream_t tail = nullptr;         // with gemm_done: the scale pass goes to this stream, behind that event recorded on
+  hipEvent_t gemm_done = nullptr;     // s, so that the HBM-bound pass can run under the next batch's layer 0
+  const Taps *taps = nullptr;
+};
+int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s);
 // Will run_output scale the soft-max inside the output kernel for such a call (dense, large batch)?  Then there is no
 // scale pass to hide under the next batch's layer 0.
 bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks);
+// Device -> pageable host memory, pre-faulting large destinations; synchronises s.
+int copy_out(void *dst, const void *d_src, size_t bytes, hipStream_t s);
+// The dense pass over the context's frames in c->d_x (c->n of them) into the host's `out`, synchronising s; re-runs what a
+// fused soft-max or chained launch that sat out its bounded wait left wrong.
+int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s);
+// Lazy results of `count` frames (c->d_out) to a host caller, compacted over PCIe where that pays; d_bits / bits: the
+// frames' masks on the device / on the host.  Synchronises s.
+int lazy_copy_out(fdnn_ctx *c, int count, const uint64_t *d_bits, const uint64_t *bits, float *out, hipStream_t s);
 // Host half of a compacted lazy return: expands `count` compacted rows sitting in the tail of out[count][O] (fdnn_runtime.cpp).
 void lazy_expand_rows(float *out, int count, size_t O, size_t stride, const uint64_t *bits);
 void lazy_expand_rows_from(float *out, const float *comp, int count, size_t O, size_t stride, const uint64_t *bits);  // rows in a buffer of their own
+void lazy_expand_force_scalar(bool on);  // fdnn_debug_lazy_expand: the scalar expansion where AVX-512 would be used
 // A pass over a very large batch runs as chunks (frames are independent: a chunk is a batch of its own, and the scratch
 // context only has to hold one).  kRoundFrames = 32 frame tiles of 320 = one workgroup per CU in the 2048-wide hidden
 // layers; a chunk is two rounds.  Measured, 125 000 frames (the 8-GPU shard of BASELINE configs[4]), fused soft-max:
@@ -192,6 +215,22 @@ constexpr int kChunkTailSplit = 2048;
 // kChunkTailSplit frames past a whole round away as a batch of their own.  Without: as assume_chained says.
 std::vector<std::pair<int, int>> frame_chunks(int n, const fdnn_model *m = nullptr, bool assume_chained = true);
 bool hidden_layers_chain(const fdnn_model *m, int n);
+std::vector<std::pair<int, int>> stride_chunks(int n);  // kChunkFrames strides, no tail split: the host lazy forms
+// "input vector size ... must be equal with network input size ..." (QuantizedDnn.java:157-161)
+int check_input_width(const fdnn_model *m, int dim);
+// The second half of a call through a model's batcher: `submitted` is what the submit call returned, *ticket what it filled in.
+inline int batcher_wait(fdnn_server *b, int submitted, const uint64_t *ticket) { return submitted ? submitted : fdnn_server_wait(b, *ticket); }
+// fdnn_calculate on the model's own device (the group path calls this per shard).
+int calculate_on_one_device(fdnn_model *m, const float *x, int n, int dim, int batch_hint, float *out);
+// [n][ld] s8 activations (u8 - 128, as the kernels keep them) -> [n][H] u8
+inline void unpack_act_rows(const int8_t *src, size_t ld, int n, int H, uint8_t *dst) {
+  for (int f = 0; f < n; ++f)
+    for (int i = 0; i < H; ++i) dst[size_t(f) * H + i] = uint8_t(src[size_t(f) * ld + i]) ^ 0x80;
+}
+// The soft-max fusing switches (run_output): this process's device marker (1 = ours or cannot tell, 0 = another process's)
+// and fdnn_debug_set_fuse's override (-1 = by environment / marker, 0 = never, 1 = always).
+int device_marker_state(int device);
+void set_fuse_override(int mode);
 // ---------------------------------------------------------------- raw feature frames (fdnn_splice.hip)
 // A run of rows of one utterance: rows [row, next segment's row) read raw frames clamp(center + (t - row) + o, lo, hi) of the
 // raw buffer (lo / hi: the buffer indices of the utterance's first and last frame).
@@ -219,6 +258,31 @@ int group_calculate_raw(fdnn_group *g, const SpliceRef &spec, const float *raw, 
 int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *raw, int n, int a, int b, const uint64_t *bits,
                            float *out, uint64_t *ticket);
 
+// ---------------------------------------------------------------- one scoring pass for every pooled entry point
+// Hidden + output layers over `chunks` ((offset, count) pairs of the call's rows) on ONE pooled context, large enough for
+// the largest chunk, and one stream.  The struct says where the rows come from, which mask applies and where the results
+// go; one of each group, the rest null.  Pointers are to the call's row 0: the pass adds the chunk's offset.
+struct ScorePass {
+  const char *who = "";  // the entry point's name, for the text of a device error
+  // rows: as they are on the device, from the host (uploaded chunk by chunk), or raw frames spliced chunk by chunk into
+  // the context's frame buffer -- raw frames on the device, or on the host (uploaded once, before the first chunk)
+  const float *d_x = nullptr;
+  const float *x = nullptr;
+  const SpliceSpec *spec = nullptr;
+  const std::vector<SpliceSeg> *segs = nullptr;
+  const float *d_raw = nullptr, *raw = nullptr;
+  int raw_frames = 0;  // frames in the raw buffer
+  int row0 = 0;        // the splice row of the call's row 0
+  // mask: none, bits on the device, or bits on the host (uploaded chunk by chunk)
+  const uint64_t *d_bits = nullptr, *bits = nullptr;
+  // results: device rows, enqueued on `stream` (the caller's) -- or host rows on the context's own stream, synchronised:
+  // dense through dense_pass_to_host and its re-run rules, with host bits through lazy_copy_out
+  float *d_out = nullptr;
+  hipStream_t stream = nullptr;
+  float *out = nullptr;
+};
+int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, const ScorePass &p);
+
 // Ordering between the streams a context is used on.  An event record costs 3-4 us of queue time behind the kernel it
 // follows, so a context whose work went to a stream that is certain to exist later -- its own, its owner's, or the null
 // stream -- only NOTES that (done_pending); the record is made when a different stream next needs the order (ctx_enter),
@@ -227,6 +291,34 @@ hipError_t ctx_enter(fdnn_ctx *c, hipStream_t s);
 void ctx_leave(fdnn_ctx *c, hipStream_t s);
 bool stream_is_durable(const fdnn_ctx *c, hipStream_t s);
 void ctx_wait_host(fdnn_ctx *c);  // host-side wait for everything ctx_leave covered
+void release_ctx(fdnn_ctx *c);    // a pooled context (score_chunks) back to its model's pool
+// One use of a context on a stream: enter() is ctx_enter; whichever way the scope is left, the work enqueued in between is
+// noted as the context's last (ctx_leave on `s`: a use that ends on another stream than it entered on names it first) and
+// a pooled context goes back to its pool.  A use whose enter() failed has enqueued nothing and leaves the notes alone.
+struct CtxUse {
+  fdnn_ctx *c = nullptr;
+  hipStream_t s = nullptr;
+  int n_after = -1;  // >= 0: the context's frame count on the way out (a pass that went chunk by chunk)
+  bool entered = false;
+  CtxUse() = default;
+  CtxUse(const CtxUse &) = delete;
+  CtxUse &operator=(const CtxUse &) = delete;
+  hipError_t enter(fdnn_ctx *ctx, hipStream_t stream) {
+    c = ctx;
+    s = stream;
+    const hipError_t e = ctx_enter(c, s);
+    entered = e == hipSuccess;
+    return e;
+  }
+  void leave() {  // (the destructor's work, for a use that ends before its scope does: then the destructor does nothing)
+    if (!c) return;
+    if (n_after >= 0) c->n = n_after;
+    if (entered) ctx_leave(c, s);
+    if (c->pooled) release_ctx(c);
+    c = nullptr;
+  }
+  ~CtxUse() { leave(); }
+};
 // The per-device chain of fused soft-max launches (run_output) notes its last launch the same way: a stream that is about
 // to be destroyed must be retired from it first.
 void fuse_chain_retire_stream(int device, hipStream_t s);

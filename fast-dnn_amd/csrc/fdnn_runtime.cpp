@@ -1,4 +1,5 @@
-// fdnn_runtime.cpp -- device model, calculation contexts and the C-ABI (include/fdnn.h).
+// fdnn_runtime.cpp -- device model, calculation contexts and the passes over them; the C-ABI that drives them
+// (include/fdnn.h) is fdnn_api.cpp, the debug / profiling / host-model calls fdnn_debug.cpp.
 //
 // Host-side counterpart of the reference's QuantizedDnn (dnn.h:106-142) and
 // CalculationContext (dnn.h:144-208, dnn.cc:194-215, :402-454), re-designed for
@@ -8,20 +9,17 @@
 // (MultiThreadedStressTest.java:48-69) never share scratch.
 #include <hip/hip_runtime.h>
 #include <immintrin.h>
-#include <emmintrin.h>
 #include <fcntl.h>
-#include <cerrno>
 #include <sys/file.h>
-#include <sys/stat.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cerrno>
 #include <cstring>
 #include <limits>
 #include <mutex>
@@ -42,27 +40,7 @@ int fail(int code, const std::string &msg) {
 }
 }  // namespace fdnn
 
-using fdnn::DeviceGuard;
-using fdnn::fail;
-using fdnn::round_up;
-using fdnn::Taps;
-using fdnn::ctx_enter;
-using fdnn::ctx_leave;
-using fdnn::destroy_ctx;
-using fdnn::make_ctx;
-using fdnn::run_hidden;
-using fdnn::run_output;
-
-struct fdnn_host_model {
-  fdnn::HostModel hm;
-};
-
 namespace fdnn {
-
-using fdnn::BlobHeader;
-using fdnn::QLayerDesc;
-
-int build_l0_image(fdnn_model *m);
 
 int upload_model(fdnn_model *m) {
   int count = 0;
@@ -511,7 +489,7 @@ int run_hidden(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) {
 // The chained hidden-layer kernel needs no such care: its tasks only ever wait for tasks drawn earlier (fdnn_chain.hip).
 // FDNN_FUSE_NORM=0 / 1 in the environment forces the unfused / fused path regardless.  Two containers that share a GPU but
 // not /dev/shm cannot see each other: set FDNN_FUSE_NORM=0 there.
-static int device_marker_state(int device) {  // 1 = this process owns the device's marker (or cannot tell), 0 = another process does
+int device_marker_state(int device) {  // 1 = this process owns the device's marker (or cannot tell), 0 = another process does
   static std::mutex mu;
   static int state[64];
   static bool known[64];
@@ -545,6 +523,7 @@ static int device_marker_state(int device) {  // 1 = this process owns the devic
   return state[d];
 }
 static std::atomic<int> g_fuse_override{-1};  // fdnn_debug_set_fuse: -1 = by environment / device marker, 0 = never, 1 = always
+void set_fuse_override(int mode) { g_fuse_override.store(mode, std::memory_order_relaxed); }
 // The model's own evidence (see fdnn_model::h_fuse_fault): once a fused launch of this model has given up, it does not fuse again.
 static bool model_may_fuse(fdnn_model *m) {
   if (!m->h_fuse_fault || __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) == 0) return true;
@@ -598,8 +577,12 @@ void fuse_chain_retire_stream(int device, hipStream_t s) {
   }
 }
 
-int run_output(fdnn_ctx *c, int first, int count, const int8_t *d_masks, float *d_out, hipStream_t s, const Taps *taps,
-               float *d_final, hipStream_t tail, hipEvent_t gemm_done, const uint64_t *d_bits) {  // d_final: where the probabilities go (default: in place in d_out)
+int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
+  const int first = oc.first, count = oc.count;
+  const int8_t *d_masks = oc.d_masks;
+  const uint64_t *d_bits = oc.d_bits;
+  float *const d_out = oc.d_out, *const d_final = oc.d_final;
+  const Taps *const taps = oc.taps;
   fdnn_model *m = c->m;
   const BlobHeader &h = m->hm.hdr;
   const QLayerDesc &d = h.q[h.n_q - 1];
@@ -705,10 +688,10 @@ int run_output(fdnn_ctx *c, int first, int count, const int8_t *d_masks, float *
     }
   }
   hipStream_t ns = s;
-  if (tail && gemm_done) {  // the scale pass goes to the tail stream, behind the GEMM (fused: nothing is left to run
-    HIP_TRY(hipEventRecord(gemm_done, s));  // there, but the caller records its completion event on the tail stream)
-    HIP_TRY(hipStreamWaitEvent(tail, gemm_done, 0));
-    ns = tail;
+  if (oc.tail && oc.gemm_done) {  // the scale pass goes to the tail stream, behind the GEMM (fused: nothing is left to run
+    HIP_TRY(hipEventRecord(oc.gemm_done, s));  // there, but the caller records its completion event on the tail stream)
+    HIP_TRY(hipStreamWaitEvent(oc.tail, oc.gemm_done, 0));
+    ns = oc.tail;
   }
   if (!fused) {
     ProfScope ps(m, ns, FDNN_PROF_NORMALIZE);
@@ -766,7 +749,7 @@ int copy_out(void *dst, const void *d_src, size_t bytes, hipStream_t s) {
 
 // pool: idle contexts with capacity >= n.  The hand-over event orders a reuse
 // on another stream behind the previous user's kernels.
-int acquire_ctx(fdnn_model *m, int n, fdnn_ctx **out) {
+static int acquire_ctx(fdnn_model *m, int n, fdnn_ctx **out) {
   fdnn_ctx *c = nullptr;
   {
     std::lock_guard<std::mutex> lk(m->mu);
@@ -789,12 +772,6 @@ int acquire_ctx(fdnn_model *m, int n, fdnn_ctx **out) {
   return FDNN_OK;
 }
 
-// A context's scratch is touched from two kinds of streams: the caller's (the *_device entry
-// points) and the context's own (the host-pointer entry points; created non-blocking, so not even
-// the NULL stream orders it).  Every entry point therefore starts by making its stream wait for
-// the context's last enqueued work and ends by recording it: calculateUntilOutputDevice(stream)
-// followed by calculateForOutputNodes() or hiddenActivations() reads finished activations
-// without the caller synchronising anything.  On one stream both calls are no-ops for the device.
 // Would run_hidden chain the int8 hidden layers of an n-frame batch of this model?  (The context-independent part of its
 // decision: taps and a context whose chain faulted are the caller's business.)
 bool hidden_layers_chain(const fdnn_model *m, int n) {
@@ -846,7 +823,12 @@ std::vector<std::pair<int, int>> frame_chunks(int n, const fdnn_model *m, bool a
   return out;
 }
 
-
+// A context's scratch is touched from two kinds of streams: the caller's (the *_device entry
+// points) and the context's own (the host-pointer entry points; created non-blocking, so not even
+// the NULL stream orders it).  Every entry point therefore starts by making its stream wait for
+// the context's last enqueued work and ends by recording it: calculateUntilOutputDevice(stream)
+// followed by calculateForOutputNodes() or hiddenActivations() reads finished activations
+// without the caller synchronising anything.  On one stream both calls are no-ops for the device.
 bool stream_is_durable(const fdnn_ctx *c, hipStream_t s) {
   return s == nullptr || s == c->stream || s == c->durable[0] || s == c->durable[1] || s == c->durable[2];
 }
@@ -878,8 +860,7 @@ void ctx_wait_host(fdnn_ctx *c) {
     hipEventSynchronize(c->done);
 }
 
-void release_ctx(fdnn_ctx *c, hipStream_t s) {
-  ctx_leave(c, s);
+void release_ctx(fdnn_ctx *c) {
   fdnn_model *m = c->m;
   fdnn_ctx *victim = nullptr;
   {
@@ -899,13 +880,13 @@ void release_ctx(fdnn_ctx *c, hipStream_t s) {
 }
 
 // The dense pass over the context's frames in c->d_x (c->n of them) into the host's `out`, synchronising s.
-static int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
+int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
   fdnn_model *m = c->m;
   const int n = c->n;
   const size_t O = size_t(m->hm.hdr.out_dim);
   const unsigned long long unwritten_before = m->h_fuse_fault ? __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) >> 32 : 0ull;
   int rc = run_hidden(c, c->d_x, s, nullptr);
-  if (!rc) rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
+  if (!rc) rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
   if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
   if (rc) hipStreamSynchronize(s);
   // copy_out has synchronised: did a fused soft-max workgroup of THIS pass sit out its bounded wait?  fdnn_gemm.hip's
@@ -916,7 +897,7 @@ static int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
   if (!rc && m->h_fuse_fault && (__atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) >> 32) != unwritten_before) {
     const bool saved = c->no_fuse;
     c->no_fuse = true;  // (whatever FDNN_FUSE_NORM says)
-    rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
+    rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
     c->no_fuse = saved;
     if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
     if (rc) hipStreamSynchronize(s);
@@ -925,41 +906,11 @@ static int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
   // been written -- run the pass again, layer by layer (run_hidden sees the flag, re-zeroes the counters, stops chaining)
   if (!rc && c->h_chain_fault && __atomic_load_n(c->h_chain_fault, __ATOMIC_RELAXED) != 0 && !c->chain_broken) {
     rc = run_hidden(c, c->d_x, s, nullptr);
-    if (!rc) rc = run_output(c, 0, n, nullptr, c->d_out, s, nullptr);
+    if (!rc) rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
     if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
     if (rc) hipStreamSynchronize(s);
   }
   return rc;
-}
-
-// fdnn_calculate on the model's own device (the group path calls this per shard).
-int calculate_on_one_device(fdnn_model *m, const float *x, int n, int dim, int batch_hint, float *out) {
-  (void)batch_hint;
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  if (n == 0) return FDNN_OK;  // QuantizedDnn.java:154-156
-  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
-  const BlobHeader &h = m->hm.hdr;
-  if (dim != h.in_dim)  // QuantizedDnn.java:157-161
-    return fail(FDNN_E_ARG, "input vector size " + std::to_string(dim) + " must be equal with network input size " +
-                                std::to_string(h.in_dim));
-  if (m->batcher) {  // coalesced with the other callers' utterances (fdnn_server.cpp)
-    uint64_t ticket = 0;
-    int brc = fdnn_server_submit(m->batcher, x, n, nullptr, out, &ticket);
-    if (!brc) brc = fdnn_server_wait(m->batcher, ticket);
-    return brc;
-  }
-  DeviceGuard g(m->device);
-  fdnn_ctx *c = nullptr;
-  int rc = acquire_ctx(m, n, &c);
-  if (rc) return rc;
-  hipStream_t s = c->stream;
-  hipError_t e = ctx_enter(c, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x, sizeof(float) * size_t(n) * dim, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) rc = dense_pass_to_host(c, out, s);
-  release_ctx(c, s);
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate: ") + hipGetErrorString(e));
-  return FDNN_OK;
 }
 
 // ---------------------------------------------------------------- raw feature frames
@@ -1019,38 +970,89 @@ void splice_rows(const SpliceSpec &spec, int input_dim, const float *raw, int ra
   }
 }
 
-int calculate_raw_rows(fdnn_model *m, const SpliceRef &spec, const float *raw, int n, int a, int b, float *out) {
-  if (b <= a) return FDNN_OK;
-  if (m->batcher) {  // coalesced with the other callers' raw utterances (fdnn_server.cpp), each with its own edges
-    uint64_t ticket = 0;
-    int rc = server_submit_raw_rows(m->batcher, spec, raw, n, a, b, nullptr, out, &ticket);
-    if (!rc) rc = fdnn_server_wait(m->batcher, ticket);
-    return rc;
+// Lazy results to a host caller.  Every inactive node of a row reads the same 1 / total (dnn.cc:366-369, :389), so what
+// crosses PCIe is the active nodes' probabilities and that one value per frame (lazy_compact_kernel); the rows are
+// rebuilt on the host inside the caller's array: the compacted block lands in its tail, and the rows are expanded front to
+// back (row f's place never reaches the compacted rows of later frames; its own is copied aside first).  d_bits: the
+// masks of the `count` frames on the device; bits: the same on the host.  With mostly active masks (> 3/4) the plain copy
+// is used.  Synchronises the stream.
+int lazy_copy_out(fdnn_ctx *c, int count, const uint64_t *d_bits, const uint64_t *bits, float *out, hipStream_t s) {
+  const size_t O = size_t(c->m->hm.hdr.out_dim), wpr = (O + 63) / 64;
+  static const bool no_compact = FDNN_TUNE_ENV("FDNN_LAZY_NO_COMPACT") != nullptr;
+  size_t most = 0;
+  const uint64_t tail_mask = (O & 63) ? ((uint64_t(1) << (O & 63)) - 1) : ~uint64_t(0);
+  for (int f = 0; f < count; ++f) {
+    size_t k = 0;
+    const uint64_t *row = bits + size_t(f) * wpr;
+    for (size_t w = 0; w + 1 < wpr; ++w) k += size_t(__builtin_popcountll(row[w]));
+    k += size_t(__builtin_popcountll(row[wpr - 1] & tail_mask));
+    most = std::max(most, k);
   }
+  const size_t stride = most + 1;
+  if (no_compact || stride * 4 > O * 3) return copy_out(out, c->d_out, sizeof(float) * size_t(count) * O, s);
+  if (c->comp_floats < size_t(count) * stride) {
+    if (c->d_comp) HIP_TRY(hipFree(c->d_comp));
+    c->d_comp = nullptr;
+    c->comp_floats = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_comp), sizeof(float) * size_t(count) * stride));
+    c->comp_floats = size_t(count) * stride;
+  }
+  fdnn::launch_lazy_compact(c->d_out, d_bits, c->d_comp, count, int(O), int(stride), s);
+  float *land = out + size_t(count) * O - size_t(count) * stride;
+  HIP_TRY(hipMemcpyAsync(land, c->d_comp, sizeof(float) * size_t(count) * stride, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  fdnn::lazy_expand_rows(out, count, O, stride, bits);
+  return FDNN_OK;
+}
+
+// ---------------------------------------------------------------- the scoring pass of every pooled entry point
+std::vector<std::pair<int, int>> stride_chunks(int n) {
+  std::vector<std::pair<int, int>> out;
+  for (int first = 0; first < n; first += kChunkFrames) out.emplace_back(first, std::min(kChunkFrames, n - first));
+  return out;
+}
+
+int check_input_width(const fdnn_model *m, int dim) {
+  if (dim == m->hm.hdr.in_dim) return FDNN_OK;
+  return fail(FDNN_E_ARG, "input vector size " + std::to_string(dim) + " must be equal with network input size " + std::to_string(m->hm.hdr.in_dim));
+}
+
+int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, const ScorePass &p) {
+  const BlobHeader &h = m->hm.hdr;
+  const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64;
   DeviceGuard g(m->device);
-  const size_t D = size_t(spec->raw_dim), O = size_t(m->hm.hdr.out_dim);
-  int fa, fb;
-  splice_halo(*spec, n, a, b, &fa, &fb);
-  const std::vector<SpliceSeg> segs{SpliceSeg{a, a - fa, -fa, n - 1 - fa}};
-  const auto chunks = frame_chunks(b - a, m);
   int cap = 0;  // the scratch only has to hold the largest chunk
   for (const auto &ch : chunks) cap = std::max(cap, ch.second);
   fdnn_ctx *c = nullptr;
   int rc = acquire_ctx(m, cap, &c);
   if (rc) return rc;
-  hipStream_t s = c->stream;
-  hipError_t e = ctx_enter(c, s);
-  if (e == hipSuccess) rc = ctx_raw_reserve(c, size_t(fb - fa), spec->raw_dim);
-  // the raw frames travel once; every chunk splices its rows from them
-  if (e == hipSuccess && !rc) e = hipMemcpyAsync(c->d_raw, raw + size_t(fa) * D, sizeof(float) * size_t(fb - fa) * D, hipMemcpyHostToDevice, s);
-  for (size_t i = 0; e == hipSuccess && !rc && i < chunks.size(); ++i) {
-    c->n = chunks[i].second;
-    splice_rows(*spec, m->hm.hdr.in_dim, c->d_raw, fb - fa, segs, a + chunks[i].first, c->n, c->d_x, s);
-    rc = dense_pass_to_host(c, out + size_t(chunks[i].first) * O, s);
+  hipStream_t s = p.d_out ? p.stream : c->stream;
+  CtxUse use;  // (also on the error paths: the context goes back to the pool)
+  hipError_t e = use.enter(c, s);
+  if (e == hipSuccess && p.raw) {  // host raw frames travel once; every chunk splices its rows from them
+    rc = ctx_raw_reserve(c, size_t(p.raw_frames), p.spec->raw_dim);
+    if (!rc) e = hipMemcpyAsync(c->d_raw, p.raw, sizeof(float) * size_t(p.raw_frames) * size_t(p.spec->raw_dim), hipMemcpyHostToDevice, s);
   }
-  release_ctx(c, s);
+  for (size_t i = 0; e == hipSuccess && !rc && i < chunks.size(); ++i) {  // frames are independent: a chunk is a batch of its own
+    const size_t off = size_t(chunks[i].first);
+    const int cnt = chunks[i].second;
+    c->n = cnt;
+    if (p.spec) splice_rows(*p.spec, h.in_dim, p.raw ? c->d_raw : p.d_raw, p.raw_frames, *p.segs, p.row0 + int(off), cnt, c->d_x, s);
+    if (p.x) e = hipMemcpyAsync(c->d_x, p.x + off * D, sizeof(float) * size_t(cnt) * D, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && p.bits) e = hipMemcpyAsync(c->d_mask_bits, p.bits + off * wpr, sizeof(uint64_t) * size_t(cnt) * wpr, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) break;
+    if (p.out && !p.bits) {
+      rc = dense_pass_to_host(c, p.out + off * O, s);
+      continue;
+    }
+    const uint64_t *d_bits = p.bits ? c->d_mask_bits : p.d_bits ? p.d_bits + off * wpr : nullptr;
+    rc = run_hidden(c, p.d_x ? p.d_x + off * D : c->d_x, s, nullptr);
+    if (!rc) rc = run_output(c, {.count = cnt, .d_bits = d_bits, .d_out = p.d_out ? p.d_out + off * O : c->d_out}, s);
+    if (!rc && p.out) rc = lazy_copy_out(c, cnt, d_bits, p.bits + off * wpr, p.out + off * O, s);
+    if (rc && p.out) hipStreamSynchronize(s);
+  }
   if (rc) return rc;
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate_raw: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string(p.who) + ": " + hipGetErrorString(e));
   return FDNN_OK;
 }
 
@@ -1102,6 +1104,7 @@ __attribute__((target("avx512f,popcnt"))) static void expand_row_avx512(float *r
 }
 
 static std::atomic<bool> g_expand_scalar{false};  // fdnn_debug_lazy_expand, mode 1
+void lazy_expand_force_scalar(bool on) { g_expand_scalar.store(on, std::memory_order_relaxed); }
 static void expand_row(float *row, const float *vals, const uint64_t *brow, size_t O) {
   static const bool wide = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("popcnt");
   if (wide && !g_expand_scalar.load(std::memory_order_relaxed))
@@ -1130,1286 +1133,4 @@ void lazy_expand_rows_from(float *out, const float *comp, int count, size_t O, s
 
 }  // namespace fdnn
 
-using namespace fdnn;
-
-// =====================================================================  C-ABI
-// ---- the launch recorder (fdnn_note.hpp)
-namespace fdnn {
-const LaunchNameInfo kLaunchNames[kLaunchNameCount] = {
-#define FDNN_X(id, name, flags) {name, flags},
-    FDNN_LAUNCH_NAMES(FDNN_X)
-#undef FDNN_X
-#define FDNN_G(out, shape, branch, name, abl) {name, abl},
-        FDNN_GEMM_LAUNCH_NAMES(FDNN_G)
-#undef FDNN_G
-};
-std::atomic<int> g_launch_note_on{0};
-std::atomic<unsigned long long> g_launch_count[kLaunchNameCount];
-int gemm_launch_name(bool output, int shape, int branch) {
-  static const struct {
-    int out, shape, branch, id;
-  } known[] = {
-#define FDNN_G(out, shape, branch, name, abl) {out, gs_##shape, gb_##branch, kLn_gemm_##out##_##shape##_##branch},
-      FDNN_GEMM_LAUNCH_NAMES(FDNN_G)
-#undef FDNN_G
-  };
-  for (const auto &k : known)
-    if (k.out == (output ? 1 : 0) && k.shape == shape && k.branch == branch) return k.id;
-  return kLn_unlisted;
-}
-}  // namespace fdnn
-
-extern "C" {
-
-const char *fdnn_last_error(void) { return g_err.c_str(); }
-const char *fdnn_version(void) { return "fast-dnn_amd 0.1 (gfx950)"; }
-
-int fdnn_device_count(void) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess) return 0;
-  return count;
-}
-
-int fdnn_model_load_on(const char *path, float cutoff, int device, fdnn_model **out) {
-  if (!path || !out) return fail(FDNN_E_ARG, "null argument");
-  *out = nullptr;
-  fdnn_model *m = new fdnn_model();
-  std::string msg;
-  int rc = fdnn::load_host_model(path, cutoff, &m->hm, &msg);
-  if (rc) {
-    delete m;
-    return fail(rc, msg);
-  }
-  m->device = device;
-  rc = upload_model(m);
-  if (!rc) (void)fdnn_device_shared(device);  // take (or find taken) the device's process marker now, not at the first large call
-  if (rc) {
-    if (m->d_blob) hipFree(m->d_blob);
-    if (m->d_w0t) hipFree(m->d_w0t);
-    if (m->d_w0norm) hipFree(m->d_w0norm);
-    if (m->d_w0d) hipFree(m->d_w0d);
-    if (m->d_w0stat) hipFree(m->d_w0stat);
-    if (m->d_lutpair) hipFree(m->d_lutpair);
-    if (m->d_l0_stats) hipFree(m->d_l0_stats);
-    if (m->h_fuse_fault) hipHostFree(m->h_fuse_fault);
-    delete m;
-    return rc;
-  }
-  if (const char *env = std::getenv("FDNN_BATCHER")) {  // max_frames[:depth[:linger_us]]
-    int mf = 0, depth = 2, linger = 0;
-    if (std::sscanf(env, "%d:%d:%d", &mf, &depth, &linger) >= 1 && mf > 0) {
-      rc = fdnn_model_enable_batcher(m, mf, depth, linger);
-      if (rc) {
-        fdnn_model_free(m);
-        return rc;
-      }
-    }
-  }
-  *out = m;
-  return FDNN_OK;
-}
-
-int fdnn_model_load(const char *path, float cutoff, fdnn_model **out) {
-  // FDNN_DEVICES="0,1,2,3" or "all": one replica per listed device, weights distributed at load,
-  // fdnn_calculate on the returned handle shards its frames over them (fdnn_group.cpp) -- how the
-  // unmodified Java class reaches every GPU of the node.
-  if (const char *env = std::getenv("FDNN_DEVICES")) {
-    std::vector<int> devs;
-    if (std::strcmp(env, "all") == 0) {
-      for (int d = 0; d < fdnn_device_count(); ++d) devs.push_back(d);
-    } else {
-      for (const char *q = env; *q;) {
-        char *end = nullptr;
-        const long v = std::strtol(q, &end, 10);
-        if (end == q) break;
-        devs.push_back(int(v));
-        q = (*end == ',') ? end + 1 : end;
-      }
-    }
-    if (devs.size() > 1) {
-      if (!out) return fail(FDNN_E_ARG, "null argument");
-      fdnn_group *g = nullptr;
-      int rc = fdnn_group_load(path, cutoff, devs.data(), int(devs.size()), &g);
-      if (rc) return rc;
-      fdnn_group_attach(g);
-      *out = fdnn_group_model(g, 0);
-      return FDNN_OK;
-    }
-    if (devs.size() == 1) return fdnn_model_load_on(path, cutoff, devs[0], out);
-  }
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  return fdnn_model_load_on(path, cutoff, dev, out);
-}
-
-int fdnn_model_enable_batcher(fdnn_model *m, int max_frames, int depth, int linger_us) {
-  if (!m) return fail(FDNN_E_ARG, "null model");
-  if (m->batcher) return fail(FDNN_E_STATE, "the model already has a batcher");
-  fdnn_server *srv = nullptr;
-  int rc = fdnn_server_create(m, max_frames, depth, &srv);
-  if (!rc) rc = fdnn_server_set_linger_us(srv, linger_us);
-  if (rc) {
-    fdnn_server_free(srv);
-    return rc;
-  }
-  m->batcher = srv;
-  return FDNN_OK;
-}
-
-void fdnn_model_free(fdnn_model *m) {
-  if (!m) return;
-  if (m->group) {  // the leader of an attached group: the group owns every replica, this one included
-    fdnn_group_free(m->group);
-    return;
-  }
-  if (m->batcher) fdnn_server_free(m->batcher);
-  m->batcher = nullptr;
-  for (fdnn_ctx *c : m->pool) destroy_ctx(c);
-  m->pool.clear();
-  {
-    DeviceGuard g(m->device);
-    hipFree(m->d_blob);
-    hipFree(m->d_w0t);
-    hipFree(m->d_w0norm);
-    hipFree(m->d_w0d);
-    hipFree(m->d_w0stat);
-    hipFree(m->d_lutpair);
-    hipFree(m->d_l0_stats);
-    if (m->h_fuse_fault) hipHostFree(m->h_fuse_fault);
-  }
-  delete m;
-}
-
-int fdnn_model_input_dim(const fdnn_model *m) { return m ? m->hm.hdr.in_dim : -1; }
-int fdnn_model_output_dim(const fdnn_model *m) { return m ? m->hm.hdr.out_dim : -1; }
-int fdnn_model_hidden_dim(const fdnn_model *m) { return m ? m->hm.hdr.hidden : -1; }
-int fdnn_model_layer_count(const fdnn_model *m) { return m ? m->hm.hdr.n_q + 1 : -1; }  // jni_dnn.cc:155
-int fdnn_model_device(const fdnn_model *m) { return m ? m->device : -1; }
-
-int fdnn_model_layer_dim(const fdnn_model *m, int index) {
-  if (!m) return -1;
-  const BlobHeader &h = m->hm.hdr;
-  if (index < 0) return -1;
-  if (index == 0) return h.hidden;           // input_layer()->node_count(), jni_dnn.cc:144-146
-  if (index >= h.n_q) return -1;             // layers()[index] must exist (see fdnn.h)
-  return h.q[index].rows;                    // layers()[index]->node_count(), jni_dnn.cc:147
-}
-
-int fdnn_model_set_l0_fma(fdnn_model *m, int on) {
-  if (!m) return fail(FDNN_E_ARG, "null model");
-  m->l0_fma = on ? 1 : 0;
-  return FDNN_OK;
-}
-
-int fdnn_debug_set_l0_kernel(fdnn_model *m, int kind) {
-  if (!m) return fail(FDNN_E_ARG, "null model");
-  if (kind < 0 || kind > 4) return fail(FDNN_E_ARG, "layer-0 kernel kind must be 0 .. 4");
-  m->l0_kernel = kind;
-  return FDNN_OK;
-}
-
-int fdnn_device_shared(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(FDNN_E_ARG, "no such device");
-  return device_marker_state(device) == 1 ? 0 : 1;
-}
-
-int fdnn_debug_set_fuse(int mode) {
-  if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "fuse mode must be -1, 0 or 1");
-  g_fuse_override.store(mode, std::memory_order_relaxed);
-  return FDNN_OK;
-}
-
-int fdnn_debug_lazy_expand(float *out, const float *comp, int count, int O, int stride, const uint64_t *bits, int mode) {
-  if (!out || !comp || !bits || count < 0 || O <= 0 || stride <= 0 || stride > O + 1 || mode < 0 || mode > 2) return fail(FDNN_E_ARG, "bad argument");
-  g_expand_scalar.store(mode == 1, std::memory_order_relaxed);
-  if (mode == 2) {
-    if (stride > O) return fail(FDNN_E_ARG, "the in-place form needs stride <= O");
-    std::memmove(out + size_t(count) * size_t(O) - size_t(count) * size_t(stride), comp, sizeof(float) * size_t(count) * size_t(stride));
-    fdnn::lazy_expand_rows(out, count, size_t(O), size_t(stride), bits);
-  } else {
-    fdnn::lazy_expand_rows_from(out, comp, count, size_t(O), size_t(stride), bits);
-  }
-  g_expand_scalar.store(false, std::memory_order_relaxed);
-  return FDNN_OK;
-}
-
-int fdnn_debug_set_l0_list_cap(fdnn_model *m, int cap) {
-  if (!m || cap < 0) return fail(FDNN_E_ARG, "bad argument");
-  std::lock_guard<std::mutex> lk(m->mu);
-  for (fdnn_ctx *c : m->pool) destroy_ctx(c);  // pooled contexts carry the old capacity
-  m->pool.clear();
-  m->l0_list_cap = cap;
-  return FDNN_OK;
-}
-
-int fdnn_debug_set_pp(int mode, int min_frames) {
-  if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "pp mode must be -1, 0 or 1");
-  fdnn::qpp_set_mode(mode, min_frames);
-  return FDNN_OK;
-}
-
-int fdnn_debug_raise_fuse_fault(fdnn_model *m, int value) {
-  if (!m) return fail(FDNN_E_ARG, "null model");
-  if (!m->h_fuse_fault) return fail(FDNN_E_STATE, "this model has no fault word");
-  __atomic_store_n(m->h_fuse_fault, value ? 1ull : 0ull, __ATOMIC_RELAXED);
-  if (!value) m->fuse_fault_said = false;
-  return FDNN_OK;
-}
-
-int fdnn_debug_set_ppo(int mode) {
-  if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "ppo mode must be -1, 0 or 1");
-  fdnn::qppo_set_mode(mode);
-  return FDNN_OK;
-}
-
-// ---- the launch recorder (fdnn_note.hpp)
-int fdnn_debug_launch_name_count(void) { return fdnn::kLaunchNameCount; }
-
-const char *fdnn_debug_launch_name(int index, int *flags) {
-  if (index < 0 || index >= fdnn::kLaunchNameCount) return nullptr;
-  if (flags) *flags = fdnn::kLaunchNames[index].flags;
-  return fdnn::kLaunchNames[index].name;
-}
-
-int fdnn_debug_launch_record(int on) {
-  fdnn::g_launch_note_on.store(on ? 1 : 0, std::memory_order_relaxed);
-  return FDNN_OK;
-}
-
-int fdnn_debug_launch_reset(void) {
-  for (auto &c : fdnn::g_launch_count) c.store(0, std::memory_order_relaxed);
-  return FDNN_OK;
-}
-
-int fdnn_debug_launch_counts(unsigned long long *out, int cap) {
-  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
-  for (int i = 0; i < fdnn::kLaunchNameCount && i < cap; ++i) out[i] = fdnn::g_launch_count[i].load(std::memory_order_relaxed);
-  return fdnn::kLaunchNameCount;
-}
-
-int fdnn_debug_set_chain(int mode, int min_frames) {
-  if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "chain mode must be -1, 0 or 1");
-  fdnn::qchain_set_mode(mode, min_frames);
-  return FDNN_OK;
-}
-
-int fdnn_debug_chain_clocks(fdnn_ctx *c, long long *out, int cap_tasks) {
-  if (!c || cap_tasks <= 0) return fail(FDNN_E_ARG, "bad argument");
-  DeviceGuard g(c->m->device);
-  const size_t words = 8 + size_t(cap_tasks) * 10;
-  if (!out) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_chain_clk) hipFree(c->d_chain_clk);
-    c->d_chain_clk = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_chain_clk), words * sizeof(long long)));
-    HIP_TRY(hipMemset(c->d_chain_clk, 0, words * sizeof(long long)));
-    HIP_TRY(hipDeviceSynchronize());
-    c->chain_clk_cap = cap_tasks;
-    return FDNN_OK;
-  }
-  if (!c->d_chain_clk || cap_tasks > c->chain_clk_cap) return fail(FDNN_E_STATE, "no clock buffer of that size");
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, c->d_chain_clk, words * sizeof(long long), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemset(c->d_chain_clk, 0, 8 * sizeof(long long)));
-  HIP_TRY(hipDeviceSynchronize());
-  return FDNN_OK;
-}
-
-// ---------------------------------------------------------------- contexts
-int fdnn_ctx_create(fdnn_model *m, int n, int batch_hint, fdnn_ctx **out) {
-  (void)batch_hint;  // frame blocking is a CPU cache device; results never depend on it
-  if (!m || !out) return fail(FDNN_E_ARG, "null argument");
-  if (n < 0) return fail(FDNN_E_ARG, "negative frame count");
-  return make_ctx(m, n, out);
-}
-
-void fdnn_ctx_free(fdnn_ctx *c) {
-  if (!c) return;
-  destroy_ctx(c);
-}
-
-int fdnn_ctx_frame_count(const fdnn_ctx *c) { return c ? c->n : -1; }
-int fdnn_ctx_output_dim(const fdnn_ctx *c) { return c ? c->m->hm.hdr.out_dim : -1; }
-
-int fdnn_ctx_forward_hidden_device(fdnn_ctx *c, const float *d_x, void *stream) {
-  if (!c || (!d_x && c->n)) return fail(FDNN_E_ARG, "null argument");
-  if (c->n == 0) {
-    c->last = 0;
-    return FDNN_OK;
-  }
-  DeviceGuard g(c->m->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(ctx_enter(c, s));
-  int rc = run_hidden(c, d_x, s, nullptr);
-  ctx_leave(c, s);
-  return rc;
-}
-
-int fdnn_ctx_forward_hidden(fdnn_ctx *c, const float *x) {
-  if (!c || (!x && c->n)) return fail(FDNN_E_ARG, "null argument");
-  if (c->n == 0) {
-    c->last = 0;
-    return FDNN_OK;
-  }
-  DeviceGuard g(c->m->device);
-  const BlobHeader &h = c->m->hm.hdr;
-  HIP_TRY(ctx_enter(c, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_x, x, sizeof(float) * size_t(c->n) * h.in_dim, hipMemcpyHostToDevice, c->stream));
-  int rc = run_hidden(c, c->d_x, c->stream, nullptr);
-  ctx_leave(c, c->stream);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return FDNN_OK;
-}
-
-int fdnn_ctx_lazy_output_batch_device(fdnn_ctx *c, int first, int count, const int8_t *d_masks, float *d_out,
-                                      void *stream) {
-  if (!c || !d_out) return fail(FDNN_E_ARG, "null argument");
-  DeviceGuard g(c->m->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(ctx_enter(c, s));
-  int rc = run_output(c, first, count, d_masks, d_out, s, nullptr);
-  ctx_leave(c, s);
-  return rc;
-}
-
-static int lazy_copy_out(fdnn_ctx *c, int count, const uint64_t *d_bits, const uint64_t *bits, float *out, hipStream_t s);
-
-// masks [count][O] bytes (non-zero = active, dnn.cc:361) -> bits [count][ceil(O / 64)], 16 bytes per step
-static void pack_mask_rows(const int8_t *masks, int count, size_t O, uint64_t *bits) {
-  const size_t wpr = (O + 63) / 64;
-  const __m128i zero = _mm_setzero_si128();
-  for (int f = 0; f < count; ++f) {
-    const int8_t *mrow = masks + size_t(f) * O;
-    uint64_t *brow = bits + size_t(f) * wpr;
-    size_t k = 0;
-    for (size_t w = 0; w < wpr; ++w) {
-      uint64_t word = 0;
-      for (int q = 0; q < 4 && k + 16 <= O; ++q, k += 16) {
-        const __m128i v = _mm_loadu_si128(reinterpret_cast<const __m128i *>(mrow + k));
-        word |= uint64_t(uint32_t(~_mm_movemask_epi8(_mm_cmpeq_epi8(v, zero))) & 0xffffu) << (16 * q);
-      }
-      const size_t base = 64 * w;
-      for (; k < O && k < base + 64; ++k) word |= uint64_t(mrow[k] != 0) << (k - base);
-      brow[w] = word;
-    }
-  }
-}
-
-int fdnn_ctx_lazy_output_batch(fdnn_ctx *c, int first, int count, const int8_t *masks, float *out) {
-  if (!c || !out || !masks) return fail(FDNN_E_ARG, "null argument");
-  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
-  if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
-  if (count == 0) return FDNN_OK;
-  DeviceGuard g(c->m->device);
-  const BlobHeader &h = c->m->hm.hdr;
-  const size_t O = size_t(h.out_dim);
-  HIP_TRY(ctx_enter(c, c->stream));
-  if (count <= kPinFrames) {  // the per-frame protocol: no copy commands (see fdnn_ctx)
-    std::memcpy(c->h_mask_pin, masks, size_t(count) * O);
-    // (blocks of 1..8 frames go through the small GEMM kernel's 32-frame tile, which reads the mask bytes straight from the
-    // host-mapped staging; nets the small kernel cannot take -- K > 2048, no validated fast division -- fall to the large
-    // tiles behind a mask_pack pass over the same staging)
-    const int rc = run_output(c, first, count, c->d_mask_pin, c->d_out, c->stream, nullptr, c->d_out_pin);
-    ctx_leave(c, c->stream);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(out, c->h_out_pin, sizeof(float) * size_t(count) * O);
-    return FDNN_OK;
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_mask, masks, size_t(count) * O, hipMemcpyHostToDevice, c->stream));
-  c->mask_bits_packed = false;
-  int rc = run_output(c, first, count, c->d_mask, c->d_out, c->stream, nullptr);
-  if (!rc) {
-    // the same masks as bits, for the compacted return (lazy_copy_out): on the host while the GPU computes, on the device
-    // by the pack kernel (a large batch's output kernel has run it already)
-    const size_t wpr = (O + 63) / 64;
-    std::vector<uint64_t> hb(size_t(count) * wpr, 0);
-    pack_mask_rows(masks, count, O, hb.data());
-    if (!c->mask_bits_packed) fdnn::launch_mask_pack(c->d_mask, c->d_mask_bits, count, int(O), c->stream);  // (a large batch's output kernel has)
-    rc = lazy_copy_out(c, count, c->d_mask_bits, hb.data(), out, c->stream);
-  }
-  ctx_leave(c, c->stream);
-  return rc;
-}
-
-int fdnn_ctx_lazy_output_batch_bits_device(fdnn_ctx *c, int first, int count, const uint64_t *d_bits, float *d_out, void *stream) {
-  if (!c || !d_out || !d_bits) return fail(FDNN_E_ARG, "null argument");
-  DeviceGuard g(c->m->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(ctx_enter(c, s));
-  int rc = run_output(c, first, count, nullptr, d_out, s, nullptr, nullptr, nullptr, nullptr, d_bits);
-  ctx_leave(c, s);
-  return rc;
-}
-
-// Lazy results to a host caller.  Every inactive node of a row reads the same 1 / total (dnn.cc:366-369, :389), so what
-// crosses PCIe is the active nodes' probabilities and that one value per frame (lazy_compact_kernel); the rows are
-// rebuilt on the host inside the caller's array: the compacted block lands in its tail, and the rows are expanded front to
-// back (row f's place never reaches the compacted rows of later frames; its own is copied aside first).  d_bits: the
-// masks of the `count` frames on the device; bits: the same on the host.  With mostly active masks (> 3/4) the plain copy
-// is used.  Synchronises the stream.
-static int lazy_copy_out(fdnn_ctx *c, int count, const uint64_t *d_bits, const uint64_t *bits, float *out, hipStream_t s) {
-  const size_t O = size_t(c->m->hm.hdr.out_dim), wpr = (O + 63) / 64;
-  static const bool no_compact = FDNN_TUNE_ENV("FDNN_LAZY_NO_COMPACT") != nullptr;
-  size_t most = 0;
-  const uint64_t tail_mask = (O & 63) ? ((uint64_t(1) << (O & 63)) - 1) : ~uint64_t(0);
-  for (int f = 0; f < count; ++f) {
-    size_t k = 0;
-    const uint64_t *row = bits + size_t(f) * wpr;
-    for (size_t w = 0; w + 1 < wpr; ++w) k += size_t(__builtin_popcountll(row[w]));
-    k += size_t(__builtin_popcountll(row[wpr - 1] & tail_mask));
-    most = std::max(most, k);
-  }
-  const size_t stride = most + 1;
-  if (no_compact || stride * 4 > O * 3) return copy_out(out, c->d_out, sizeof(float) * size_t(count) * O, s);
-  if (c->comp_floats < size_t(count) * stride) {
-    if (c->d_comp) HIP_TRY(hipFree(c->d_comp));
-    c->d_comp = nullptr;
-    c->comp_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_comp), sizeof(float) * size_t(count) * stride));
-    c->comp_floats = size_t(count) * stride;
-  }
-  fdnn::launch_lazy_compact(c->d_out, d_bits, c->d_comp, count, int(O), int(stride), s);
-  float *land = out + size_t(count) * O - size_t(count) * stride;
-  HIP_TRY(hipMemcpyAsync(land, c->d_comp, sizeof(float) * size_t(count) * stride, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  fdnn::lazy_expand_rows(out, count, O, stride, bits);
-  return FDNN_OK;
-}
-
-int fdnn_ctx_lazy_output_batch_bits(fdnn_ctx *c, int first, int count, const uint64_t *bits, float *out) {
-  if (!c || !out || !bits) return fail(FDNN_E_ARG, "null argument");
-  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
-  if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
-  if (count == 0) return FDNN_OK;
-  DeviceGuard g(c->m->device);
-  const BlobHeader &h = c->m->hm.hdr;
-  const size_t O = size_t(h.out_dim), wpr = (O + 63) / 64;
-  HIP_TRY(ctx_enter(c, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_mask_bits, bits, sizeof(uint64_t) * size_t(count) * wpr, hipMemcpyHostToDevice, c->stream));
-  int rc = run_output(c, first, count, nullptr, c->d_out, c->stream, nullptr, nullptr, nullptr, nullptr, c->d_mask_bits);
-  if (!rc) rc = lazy_copy_out(c, count, c->d_mask_bits, bits, out, c->stream);
-  ctx_leave(c, c->stream);
-  return rc;
-}
-
-int fdnn_ctx_lazy_output(fdnn_ctx *c, int frame, const int8_t *mask, float *out) {
-  return fdnn_ctx_lazy_output_batch(c, frame, 1, mask, out);
-}
-
-int fdnn_ctx_output_device(fdnn_ctx *c, float *d_out, void *stream) {
-  if (!c || !d_out) return fail(FDNN_E_ARG, "null argument");
-  DeviceGuard g(c->m->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(ctx_enter(c, s));
-  int rc = run_output(c, 0, c->n, nullptr, d_out, s, nullptr);
-  ctx_leave(c, s);
-  return rc;
-}
-
-int fdnn_ctx_output(fdnn_ctx *c, float *out) {
-  if (!c || !out) return fail(FDNN_E_ARG, "null argument");
-  if (c->n == 0) return FDNN_OK;
-  DeviceGuard g(c->m->device);
-  HIP_TRY(ctx_enter(c, c->stream));
-  int rc = run_output(c, 0, c->n, nullptr, c->d_out, c->stream, nullptr);
-  ctx_leave(c, c->stream);
-  if (rc) return rc;
-  return copy_out(out, c->d_out, sizeof(float) * size_t(c->n) * c->m->hm.hdr.out_dim, c->stream);
-}
-
-int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
-  if (!c || !out) return fail(FDNN_E_ARG, "null argument");
-  if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");
-  if (c->n == 0) return FDNN_OK;
-  DeviceGuard g(c->m->device);
-  const int H = c->m->hm.hdr.hidden;
-  std::vector<int8_t> tmp(size_t(c->n) * c->act_ld);
-  HIP_TRY(ctx_enter(c, c->stream));  // the hidden layers may have been enqueued on a caller's stream
-  HIP_TRY(hipMemcpyAsync(tmp.data(), c->d_act[c->last], tmp.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int f = 0; f < c->n; ++f)
-    for (int i = 0; i < H; ++i) out[size_t(f) * H + i] = uint8_t(tmp[size_t(f) * c->act_ld + i]) ^ 0x80;
-  return FDNN_OK;
-}
-
-// ---------------------------------------------------------------- dense path
-int fdnn_calculate_device(fdnn_model *m, const float *d_x, int n, float *d_out, void *stream) {
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  if (n == 0) return FDNN_OK;
-  if (!d_x || !d_out) return fail(FDNN_E_ARG, "null buffer");
-  DeviceGuard g(m->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  fdnn_ctx *c = nullptr;
-  const auto chunks = fdnn::frame_chunks(n, m);
-  int cap = 0;  // the scratch only has to hold the largest chunk
-  for (const auto &ch : chunks) cap = std::max(cap, ch.second);
-  int rc = acquire_ctx(m, cap, &c);
-  if (rc) return rc;
-  const hipError_t e = ctx_enter(c, s);
-  if (e == hipSuccess) {
-    const size_t D = size_t(m->hm.hdr.in_dim), O = size_t(m->hm.hdr.out_dim);
-    for (const auto &ch : chunks) {  // frames are independent: a chunk is a batch of its own
-      c->n = ch.second;
-      rc = run_hidden(c, d_x + size_t(ch.first) * D, s, nullptr);
-      if (!rc) rc = run_output(c, 0, ch.second, nullptr, d_out + size_t(ch.first) * O, s, nullptr);
-      if (rc) break;
-    }
-  }
-  release_ctx(c, s);  // also on the error paths: the context goes back to the pool
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate_device: ") + hipGetErrorString(e));
-  return rc;
-}
-
-int fdnn_calculate(fdnn_model *m, const float *x, int n, int dim, int batch_hint, float *out) {
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  if (n == 0) return FDNN_OK;  // QuantizedDnn.java:154-156
-  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
-  if (m->group) return fdnn_group_calculate(m->group, x, n, dim, batch_hint, out);  // sharded over the node's devices
-  return fdnn::calculate_on_one_device(m, x, n, dim, batch_hint, out);
-}
-
-// One-call lazy scoring: hidden layers + masked output + compacted return in ONE call and ONE stream synchronisation
-// (a LazyContext costs two calls and two synchronisations per utterance: calculateUntilOutput, then the masked rows).
-int fdnn_calculate_lazy_bits(fdnn_model *m, const float *x, int n, int dim, const uint64_t *bits, float *out) {
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  if (n == 0) return FDNN_OK;
-  if (!x || !out || !bits) return fail(FDNN_E_ARG, "null buffer");
-  const BlobHeader &h = m->hm.hdr;
-  if (dim != h.in_dim)
-    return fail(FDNN_E_ARG, "input vector size " + std::to_string(dim) + " must be equal with network input size " + std::to_string(h.in_dim));
-  if (m->batcher) {  // coalesced with the other callers' lazy utterances (fdnn_server.cpp), rows back compacted
-    uint64_t ticket = 0;
-    int brc = fdnn_server_submit_lazy_bits(m->batcher, x, n, bits, out, &ticket);
-    if (!brc) brc = fdnn_server_wait(m->batcher, ticket);
-    return brc;
-  }
-  DeviceGuard g(m->device);
-  const size_t wpr = (size_t(h.out_dim) + 63) / 64;
-  int rc = FDNN_OK;
-  for (int first = 0; first < n && !rc; first += fdnn::kChunkFrames) {  // (very large calls: chunk by chunk, as the dense call)
-    const int cnt = std::min(fdnn::kChunkFrames, n - first);
-    fdnn_ctx *c = nullptr;
-    rc = acquire_ctx(m, cnt, &c);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    hipError_t e = ctx_enter(c, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x + size_t(first) * dim, sizeof(float) * size_t(cnt) * dim, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_mask_bits, bits + size_t(first) * wpr, sizeof(uint64_t) * size_t(cnt) * wpr, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-      rc = run_hidden(c, c->d_x, s, nullptr);
-      if (!rc) rc = run_output(c, 0, cnt, nullptr, c->d_out, s, nullptr, nullptr, nullptr, nullptr, c->d_mask_bits);
-      if (!rc) rc = lazy_copy_out(c, cnt, c->d_mask_bits, bits + size_t(first) * wpr, out + size_t(first) * h.out_dim, s);
-      if (rc) hipStreamSynchronize(s);
-    }
-    release_ctx(c, s);
-    if (!rc && e != hipSuccess) rc = fail(FDNN_E_DEVICE, std::string("fdnn_calculate_lazy_bits: ") + hipGetErrorString(e));
-  }
-  return rc;
-}
-
-int fdnn_calculate_lazy(fdnn_model *m, const float *x, int n, int dim, const int8_t *masks, float *out) {
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  if (n == 0) return FDNN_OK;
-  if (!masks) return fail(FDNN_E_ARG, "null buffer");
-  const size_t O = size_t(m->hm.hdr.out_dim), wpr = (O + 63) / 64;
-  std::vector<uint64_t> hb(size_t(n) * wpr);
-  pack_mask_rows(masks, n, O, hb.data());
-  return fdnn_calculate_lazy_bits(m, x, n, dim, hb.data(), out);
-}
-
-int fdnn_calculate_lazy_bits_device(fdnn_model *m, const float *d_x, int n, const uint64_t *d_bits, float *d_out, void *stream) {
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  if (n == 0) return FDNN_OK;
-  if (!d_x || !d_out || !d_bits) return fail(FDNN_E_ARG, "null buffer");
-  DeviceGuard g(m->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  fdnn_ctx *c = nullptr;
-  const auto chunks = fdnn::frame_chunks(n, m);
-  int cap = 0;
-  for (const auto &ch : chunks) cap = std::max(cap, ch.second);
-  int rc = acquire_ctx(m, cap, &c);
-  if (rc) return rc;
-  const hipError_t e = ctx_enter(c, s);
-  if (e == hipSuccess) {
-    const size_t D = size_t(m->hm.hdr.in_dim), O = size_t(m->hm.hdr.out_dim), wpr = (O + 63) / 64;
-    for (const auto &ch : chunks) {
-      c->n = ch.second;
-      rc = run_hidden(c, d_x + size_t(ch.first) * D, s, nullptr);
-      if (!rc) rc = run_output(c, 0, ch.second, nullptr, d_out + size_t(ch.first) * O, s, nullptr, nullptr, nullptr, nullptr, d_bits + size_t(ch.first) * wpr);
-      if (rc) break;
-    }
-  }
-  release_ctx(c, s);
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate_lazy_bits_device: ") + hipGetErrorString(e));
-  return rc;
-}
-
-// ---------------------------------------------------------------- raw feature frames (the <Splice> block on the device)
-int fdnn_model_set_splice(fdnn_model *m, const int *offsets, int count, int raw_dim) {
-  if (!m) return fail(FDNN_E_ARG, "null model");
-  fdnn::SpliceRef spec;  // (a new object: streams, queued submissions and calls in progress keep the one they hold)
-  if (count != 0 || raw_dim != 0) {  // (count == 0 with raw_dim == 0 clears the spec; an empty spec of some width is an error)
-    if (count < 1 || count > fdnn::kSpliceMaxOffsets) return fail(FDNN_E_ARG, "a splice spec has 1 .. 64 offsets");
-    if (!offsets) return fail(FDNN_E_ARG, "null offsets");
-    for (int i = 0; i < count; ++i)
-      if (offsets[i] < -64 || offsets[i] > 64) return fail(FDNN_E_ARG, "splice offsets must lie in -64 .. 64");
-    const int in_dim = m->hm.hdr.in_dim;
-    if (raw_dim < 1 || (long long)count * raw_dim > in_dim)
-      return fail(FDNN_E_ARG, std::to_string(count) + " x " + std::to_string(raw_dim) + " spliced values do not fit the input width " +
-                                  std::to_string(in_dim));
-    auto sp = std::make_shared<fdnn::SpliceSpec>();
-    sp->offsets.assign(offsets, offsets + count);
-    sp->raw_dim = raw_dim;
-    for (int o : sp->offsets) {
-      sp->left = std::max(sp->left, -o);
-      sp->right = std::max(sp->right, o);
-    }
-    spec = sp;
-  }
-  // one spec for the whole group when the model leads one (the replicas score its shards; fdnn_group_attach copies the
-  // leader's spec to them as well, and a sharded call hands every replica the leader's)
-  const int replicas = m->group ? fdnn_group_size(m->group) : 1;
-  for (int r = 0; r < replicas; ++r) (m->group ? fdnn_group_model(m->group, r) : m)->splice = spec;
-  return FDNN_OK;
-}
-
-int fdnn_model_get_splice(const fdnn_model *m, int *offsets, int cap, int *raw_dim) {
-  if (!m || cap < 0 || (cap > 0 && !offsets)) return fail(FDNN_E_ARG, "bad argument");
-  const fdnn::SpliceRef spec = m->splice;
-  const int count = spec ? int(spec->offsets.size()) : 0;
-  for (int i = 0; i < cap && i < count; ++i) offsets[i] = spec->offsets[size_t(i)];
-  if (raw_dim) *raw_dim = spec ? spec->raw_dim : 0;
-  return count;
-}
-
-int fdnn_calculate_raw(fdnn_model *m, const float *raw, int n, int raw_dim, float *out) {
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  const fdnn::SpliceRef spec = m->splice;
-  int rc = fdnn::splice_check(spec, raw_dim);
-  if (rc) return rc;
-  if (n == 0) return FDNN_OK;
-  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
-  // as fdnn_calculate: sharded over an attached group first (each replica uploads its shard + halo, through its own batcher
-  // when it has one), else through the model's batcher, else on the model's device
-  if (m->group) return fdnn::group_calculate_raw(m->group, spec, raw, n, out);
-  return fdnn::calculate_raw_rows(m, spec, raw, n, 0, n, out);
-}
-
-int fdnn_calculate_raw_device(fdnn_model *m, const float *d_raw, int n, const int *seg_starts, int n_segs, float *d_out, void *stream) {
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  const fdnn::SpliceRef spec = m->splice;
-  int rc = fdnn::splice_check(spec, -1);
-  if (rc) return rc;
-  if (n == 0) return FDNN_OK;
-  if (!d_raw || !d_out) return fail(FDNN_E_ARG, "null buffer");
-  std::vector<fdnn::SpliceSeg> segs;
-  if (!seg_starts) {
-    segs.push_back(fdnn::SpliceSeg{0, 0, 0, n - 1});
-  } else {
-    if (n_segs < 1 || seg_starts[0] != 0) return fail(FDNN_E_ARG, "a segment table starts with 0");
-    for (int k = 0; k < n_segs; ++k) {
-      const int a = seg_starts[k], b = k + 1 < n_segs ? seg_starts[k + 1] : n;
-      if (b <= a || b > n) return fail(FDNN_E_ARG, "segment starts must ascend strictly and lie below n");
-      segs.push_back(fdnn::SpliceSeg{a, a, a, b - 1});
-    }
-  }
-  DeviceGuard g(m->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  fdnn_ctx *c = nullptr;
-  const auto chunks = fdnn::frame_chunks(n, m);
-  int cap = 0;
-  for (const auto &ch : chunks) cap = std::max(cap, ch.second);
-  rc = acquire_ctx(m, cap, &c);
-  if (rc) return rc;
-  const hipError_t e = ctx_enter(c, s);
-  if (e == hipSuccess) {
-    const size_t O = size_t(m->hm.hdr.out_dim);
-    for (const auto &ch : chunks) {  // each chunk's rows spliced into the context's frame buffer, then scored as usual
-      c->n = ch.second;
-      fdnn::splice_rows(*spec, m->hm.hdr.in_dim, d_raw, n, segs, ch.first, ch.second, c->d_x, s);
-      rc = run_hidden(c, c->d_x, s, nullptr);
-      if (!rc) rc = run_output(c, 0, ch.second, nullptr, d_out + size_t(ch.first) * O, s, nullptr);
-      if (rc) break;
-    }
-  }
-  release_ctx(c, s);
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fdnn_calculate_raw_device: ") + hipGetErrorString(e));
-  return rc;
-}
-
-int fdnn_calculate_lazy_bits_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const uint64_t *bits, float *out) {
-  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
-  const fdnn::SpliceRef spec = m->splice;
-  int rc = fdnn::splice_check(spec, raw_dim);
-  if (rc) return rc;
-  if (n == 0) return FDNN_OK;
-  if (!raw || !out || !bits) return fail(FDNN_E_ARG, "null buffer");
-  if (m->batcher) {
-    uint64_t ticket = 0;
-    rc = fdnn::server_submit_raw_rows(m->batcher, spec, raw, n, 0, n, bits, out, &ticket);
-    if (!rc) rc = fdnn_server_wait(m->batcher, ticket);
-    return rc;
-  }
-  DeviceGuard g(m->device);
-  const size_t O = size_t(m->hm.hdr.out_dim), wpr = (O + 63) / 64, D = size_t(raw_dim);
-  const std::vector<fdnn::SpliceSeg> segs{fdnn::SpliceSeg{0, 0, 0, n - 1}};
-  fdnn_ctx *c = nullptr;
-  rc = acquire_ctx(m, std::min(n, fdnn::kChunkFrames), &c);
-  if (rc) return rc;
-  hipStream_t s = c->stream;
-  hipError_t e = ctx_enter(c, s);
-  if (e == hipSuccess) rc = fdnn::ctx_raw_reserve(c, size_t(n), raw_dim);
-  if (e == hipSuccess && !rc) e = hipMemcpyAsync(c->d_raw, raw, sizeof(float) * size_t(n) * D, hipMemcpyHostToDevice, s);
-  for (int first = 0; first < n && e == hipSuccess && !rc; first += fdnn::kChunkFrames) {  // (chunks as fdnn_calculate_lazy_bits)
-    const int cnt = std::min(fdnn::kChunkFrames, n - first);
-    c->n = cnt;
-    fdnn::splice_rows(*spec, m->hm.hdr.in_dim, c->d_raw, n, segs, first, cnt, c->d_x, s);
-    e = hipMemcpyAsync(c->d_mask_bits, bits + size_t(first) * wpr, sizeof(uint64_t) * size_t(cnt) * wpr, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) break;
-    rc = run_hidden(c, c->d_x, s, nullptr);
-    if (!rc) rc = run_output(c, 0, cnt, nullptr, c->d_out, s, nullptr, nullptr, nullptr, nullptr, c->d_mask_bits);
-    if (!rc) rc = lazy_copy_out(c, cnt, c->d_mask_bits, bits + size_t(first) * wpr, out + size_t(first) * O, s);
-    if (rc) hipStreamSynchronize(s);
-  }
-  release_ctx(c, s);
-  if (!rc && e != hipSuccess) rc = fail(FDNN_E_DEVICE, std::string("fdnn_calculate_lazy_bits_raw: ") + hipGetErrorString(e));
-  return rc;
-}
-
-int fdnn_ctx_forward_hidden_raw(fdnn_ctx *c, const float *raw) {
-  if (!c) return fail(FDNN_E_ARG, "null argument");
-  const fdnn::SpliceRef spec = c->m->splice;
-  int rc = fdnn::splice_check(spec, -1);
-  if (rc) return rc;
-  if (c->n == 0) {
-    c->last = 0;
-    return FDNN_OK;
-  }
-  if (!raw) return fail(FDNN_E_ARG, "null argument");
-  DeviceGuard g(c->m->device);
-  const size_t D = size_t(spec->raw_dim);
-  HIP_TRY(ctx_enter(c, c->stream));
-  rc = fdnn::ctx_raw_reserve(c, size_t(c->n), spec->raw_dim);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_raw, raw, sizeof(float) * size_t(c->n) * D, hipMemcpyHostToDevice, c->stream));
-  fdnn::splice_rows(*spec, c->m->hm.hdr.in_dim, c->d_raw, c->n, {fdnn::SpliceSeg{0, 0, 0, c->n - 1}}, 0, c->n, c->d_x, c->stream);
-  rc = run_hidden(c, c->d_x, c->stream, nullptr);
-  ctx_leave(c, c->stream);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return FDNN_OK;
-}
-
-}  // extern "C"
-
-// A stream of raw frames (fdnn_stream_*).  Its device buffer holds global frames [base, base + len): the frames still to be
-// read by rows not emitted yet -- at most L + R of them between pushes (L / R: the left / right context of the offsets) --
-// and the push's new ones.  Before a push the kept frames move to the front of the other buffer of a pair (device to
-// device, L + R frames): nothing is uploaded twice.
-struct fdnn_stream {
-  fdnn_model *m = nullptr;
-  fdnn_ctx *c = nullptr;  // the stream's own context: max_chunk + R frames
-  fdnn::SpliceRef spec;   // the model's spec when the stream was made: every push splices with it
-  int raw_dim = 0, max_chunk = 0, left = 0, right = 0;
-  float *d_buf[2] = {nullptr, nullptr};
-  int cur = 0;
-  long long base = 0, len = 0, pushed = 0, emitted = 0;
-  bool ended = false;
-};
-
-extern "C" {
-
-int fdnn_stream_create(fdnn_model *m, int max_chunk, fdnn_stream **out) {
-  if (!m || !out) return fail(FDNN_E_ARG, "null argument");
-  *out = nullptr;
-  const fdnn::SpliceRef spec = m->splice;
-  int rc = fdnn::splice_check(spec, -1);
-  if (rc) return rc;
-  if (max_chunk < 1) return fail(FDNN_E_ARG, "max_chunk must be positive");
-  DeviceGuard g(m->device);
-  fdnn_stream *s = new fdnn_stream();
-  s->m = m;
-  s->spec = spec;
-  s->raw_dim = spec->raw_dim;
-  s->max_chunk = max_chunk;
-  s->left = spec->left;
-  s->right = spec->right;
-  rc = fdnn::make_ctx(m, max_chunk + s->right, &s->c);
-  const size_t frames = size_t(max_chunk) + size_t(s->left) + size_t(s->right);
-  for (int k = 0; k < 2 && !rc; ++k)
-    if (hipMalloc(reinterpret_cast<void **>(&s->d_buf[k]), sizeof(float) * frames * size_t(s->raw_dim)) != hipSuccess)
-      rc = fail(FDNN_E_NOMEM, "stream buffer of " + std::to_string(frames) + " raw frames");
-  if (rc) {
-    fdnn_stream_free(s);
-    return rc;
-  }
-  s->c->n = 0;
-  *out = s;
-  return FDNN_OK;
-}
-
-void fdnn_stream_free(fdnn_stream *s) {
-  if (!s) return;
-  DeviceGuard g(s->m->device);
-  if (s->c) fdnn::destroy_ctx(s->c);  // (synchronises the stream's work)
-  hipFree(s->d_buf[0]);
-  hipFree(s->d_buf[1]);
-  delete s;
-}
-
-int fdnn_stream_reset(fdnn_stream *s) {
-  if (!s) return fail(FDNN_E_ARG, "null stream");
-  s->base = s->len = s->pushed = s->emitted = 0;
-  s->ended = false;
-  return FDNN_OK;
-}
-
-int fdnn_stream_position(const fdnn_stream *s, int64_t *pushed, int64_t *emitted) {
-  if (!s) return fail(FDNN_E_ARG, "null stream");
-  if (pushed) *pushed = s->pushed;
-  if (emitted) *emitted = s->emitted;
-  return FDNN_OK;
-}
-
-fdnn_ctx *fdnn_stream_ctx(fdnn_stream *s) { return s ? s->c : nullptr; }
-
-int fdnn_stream_push(fdnn_stream *s, const float *raw, int n_raw, int end, float *out, int *n_out) {
-  if (!s || !n_out) return fail(FDNN_E_ARG, "null argument");
-  *n_out = 0;
-  if (s->ended) return fail(FDNN_E_STATE, "the stream has ended: fdnn_stream_reset starts the next utterance");
-  if (n_raw < 0 || n_raw > s->max_chunk) return fail(FDNN_E_ARG, "a push holds 0 .. max_chunk raw frames");
-  if (n_raw > 0 && !raw) return fail(FDNN_E_ARG, "null raw frames");
-  fdnn_model *m = s->m;
-  fdnn_ctx *c = s->c;
-  DeviceGuard g(m->device);
-  const size_t D = size_t(s->raw_dim);
-  hipStream_t st = c->stream;
-  HIP_TRY(fdnn::ctx_enter(c, st));
-  // keep what rows not emitted yet still read: frames from emitted - L on
-  const long long keep = std::max(s->base, s->emitted - s->left);
-  if (keep > s->base) {
-    const long long kept = s->base + s->len - keep;
-    if (kept > 0)
-      HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur ^ 1], s->d_buf[s->cur] + size_t(keep - s->base) * D, sizeof(float) * size_t(kept) * D,
-                             hipMemcpyDeviceToDevice, st));
-    s->cur ^= 1;
-    s->base = keep;
-    s->len = kept;
-  }
-  if (n_raw > 0)
-    HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur] + size_t(s->len) * D, raw, sizeof(float) * size_t(n_raw) * D, hipMemcpyHostToDevice, st));
-  s->len += n_raw;
-  s->pushed += n_raw;
-  // complete rows: t + R has arrived; at the end of the stream every row, right-clamped to the last frame
-  const long long upto = end ? s->pushed : std::max(s->emitted, s->pushed - s->right);
-  const int rows = int(upto - s->emitted);
-  int rc = FDNN_OK;
-  c->n = rows;
-  c->last = rows ? -1 : 0;
-  if (rows > 0) {
-    const int lo = int(std::max(-s->base, -(1LL << 30)));  // global frame 0 -- the left clamp -- as a buffer index
-    const std::vector<fdnn::SpliceSeg> segs{fdnn::SpliceSeg{0, int(s->emitted - s->base), lo, int(s->pushed - 1 - s->base)}};
-    fdnn::splice_rows(*s->spec, m->hm.hdr.in_dim, s->d_buf[s->cur], int(s->len), segs, 0, rows, c->d_x, st);
-    if (out) {
-      rc = dense_pass_to_host(c, out, st);  // (synchronises)
-    } else {
-      rc = run_hidden(c, c->d_x, st, nullptr);  // hidden layers only: the context's lazy entry points take it from here
-      if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(FDNN_E_DEVICE, "fdnn_stream_push: stream synchronisation");
-    }
-  } else if (hipStreamSynchronize(st) != hipSuccess) {  // (the caller's raw frames have been read when the push returns)
-    rc = fail(FDNN_E_DEVICE, "fdnn_stream_push: stream synchronisation");
-  }
-  fdnn::ctx_leave(c, st);
-  if (rc) return rc;
-  s->emitted = upto;
-  s->ended = end != 0;
-  *n_out = rows;
-  return FDNN_OK;
-}
-
-// ---------------------------------------------------------------- taps
-int fdnn_debug_forward_taps(fdnn_model *m, const float *x, int n, const int8_t *masks, float *l0_lin, uint8_t *u8_acts,
-                            int32_t *acc_hid, int32_t *acc_out, float *logits, float *probs) {
-  if (!m || !x || n <= 0) return fail(FDNN_E_ARG, "bad argument");
-  DeviceGuard g(m->device);
-  const BlobHeader &h = m->hm.hdr;
-  const size_t H = size_t(h.hidden), O = size_t(h.out_dim), N = size_t(n);
-  const int n_hidden = h.n_q;  // fp32 layer + (n_q - 1) int8 hidden layers
-  fdnn_ctx *c = nullptr;
-  int rc = make_ctx(m, n, &c);
-  if (rc) return rc;
-  Taps t{};
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-  };
-  alloc(reinterpret_cast<void **>(&t.l0_lin), sizeof(float) * N * H);
-  alloc(reinterpret_cast<void **>(&t.u8_acts), size_t(n_hidden) * N * H);
-  alloc(reinterpret_cast<void **>(&t.acc_hid), sizeof(int32_t) * size_t(std::max(n_hidden - 1, 1)) * N * H);
-  alloc(reinterpret_cast<void **>(&t.acc_out), sizeof(int32_t) * N * O);
-  alloc(reinterpret_cast<void **>(&t.logits), sizeof(float) * N * O);
-  hipStream_t s = c->stream;
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x, sizeof(float) * N * h.in_dim, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && masks) e = hipMemcpyAsync(c->d_mask, masks, N * O, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    rc = run_hidden(c, c->d_x, s, &t);
-    if (!rc) rc = run_output(c, 0, n, masks ? c->d_mask : nullptr, c->d_out, s, &t);
-  }
-  auto fetch = [&](void *dst, const void *src, size_t bytes) {
-    if (dst && e == hipSuccess && !rc) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
-  };
-  fetch(l0_lin, t.l0_lin, sizeof(float) * N * H);
-  fetch(u8_acts, t.u8_acts, size_t(n_hidden) * N * H);
-  fetch(acc_hid, t.acc_hid, sizeof(int32_t) * size_t(n_hidden - 1) * N * H);
-  fetch(acc_out, t.acc_out, sizeof(int32_t) * N * O);
-  fetch(logits, t.logits, sizeof(float) * N * O);
-  fetch(probs, c->d_out, sizeof(float) * N * O);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(t.l0_lin);
-  hipFree(t.u8_acts);
-  hipFree(t.acc_hid);
-  hipFree(t.acc_out);
-  hipFree(t.logits);
-  fdnn_ctx_free(c);
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("taps: ") + hipGetErrorString(e));
-  return FDNN_OK;
-}
-
-int fdnn_debug_frame_chunks(int n, int *chunks, int cap) { return fdnn_debug_frame_chunks_for(n, 1, chunks, cap); }
-
-int fdnn_debug_frame_chunks_for(int n, int chained, int *chunks, int cap) {
-  if (n <= 0 || !chunks || cap <= 0) return -1;
-  const auto v = fdnn::frame_chunks(n, nullptr, chained != 0);
-  if (static_cast<int>(v.size()) > cap) return -1;
-  for (size_t i = 0; i < v.size(); ++i) {
-    chunks[2 * i] = v[i].first;
-    chunks[2 * i + 1] = v[i].second;
-  }
-  return static_cast<int>(v.size());
-}
-
-int fdnn_debug_production_acc_out(fdnn_model *m, const float *x, int n, int stride, const int8_t *masks, int32_t *acc, float *probs) {
-  if (!m || !x || !acc || n <= 0 || stride <= 0) return fail(FDNN_E_ARG, "bad argument");
-  DeviceGuard g(m->device);
-  const BlobHeader &h = m->hm.hdr;
-  const size_t O = size_t(h.out_dim), N = size_t(n), NP = size_t((n + stride - 1) / stride);
-  fdnn_ctx *c = nullptr;
-  int rc = make_ctx(m, n, &c);
-  if (rc) return rc;
-  Taps t{};  // only the probe: hidden layers and output layer run their production instances
-  t.probe_stride = stride;
-  hipStream_t s = c->stream;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&t.acc_probe), sizeof(int32_t) * NP * O);
-  if (e == hipSuccess) e = hipMemsetAsync(t.acc_probe, 0xff, sizeof(int32_t) * NP * O, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x, sizeof(float) * N * h.in_dim, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && masks) e = hipMemcpyAsync(c->d_mask, masks, N * O, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    rc = run_hidden(c, c->d_x, s, nullptr);
-    if (!rc) rc = run_output(c, 0, n, masks ? c->d_mask : nullptr, c->d_out, s, &t);
-  }
-  if (e == hipSuccess && !rc) e = hipMemcpyAsync(acc, t.acc_probe, sizeof(int32_t) * NP * O, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && !rc && probs) e = hipMemcpyAsync(probs, c->d_out, sizeof(float) * N * O, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(t.acc_probe);
-  fdnn_ctx_free(c);
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("acc probe: ") + hipGetErrorString(e));
-  return FDNN_OK;
-}
-
-int fdnn_debug_device_counters(fdnn_model *m, unsigned long long *out, int n) {  // raw device counter words (kernel clock stamps of timing builds live at [4..])
-  if (!m || !out || n < 0 || n > 32) return fail(FDNN_E_ARG, "bad argument");
-  if (!m->d_l0_stats) return fail(FDNN_E_STATE, "no counters");
-  DeviceGuard g(m->device);
-  const hipError_t e = hipMemcpy(out, m->d_l0_stats, sizeof(unsigned long long) * size_t(n), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("device counters: ") + hipGetErrorString(e));
-  return FDNN_OK;
-}
-
-int fdnn_model_chain_faults(fdnn_model *m, unsigned long long *faults) {
-  if (!m || !faults) return fail(FDNN_E_ARG, "null argument");
-  *faults = 0;
-  if (!m->d_l0_stats) return FDNN_OK;
-  DeviceGuard g(m->device);
-  const hipError_t e = hipMemcpy(faults, m->d_l0_stats + 3, sizeof(*faults), hipMemcpyDeviceToHost);  // (synchronizes with the device)
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("chain_faults: ") + hipGetErrorString(e));
-  return FDNN_OK;
-}
-
-int fdnn_model_fuse_giveups(fdnn_model *m, unsigned long long *tiles) {
-  if (!m || !tiles) return fail(FDNN_E_ARG, "null argument");
-  *tiles = 0;
-  if (!m->d_l0_stats) return FDNN_OK;
-  DeviceGuard g(m->device);
-  const hipError_t e = hipMemcpy(tiles, m->d_l0_stats + 2, sizeof(*tiles), hipMemcpyDeviceToHost);  // (synchronizes with the device)
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("fuse_giveups: ") + hipGetErrorString(e));
-  return FDNN_OK;
-}
-
-int fdnn_debug_layer0(fdnn_model *m, const float *x, int n, uint8_t *u8_out, unsigned long long *recomputed) {
-  if (!m || !x || !u8_out || n <= 0) return fail(FDNN_E_ARG, "bad argument");
-  DeviceGuard g(m->device);
-  const BlobHeader &h = m->hm.hdr;
-  fdnn_ctx *c = nullptr;
-  int rc = make_ctx(m, n, &c);
-  if (rc) return rc;
-  unsigned long long before[2] = {0, 0}, after[2] = {0, 0};
-  hipError_t e = hipMemcpy(before, m->d_l0_stats, sizeof(before), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x, sizeof(float) * size_t(n) * h.in_dim, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    run_layer0(c, c->d_x, c->stream, nullptr);  // the PRODUCTION instance (no taps): screened path for large batches
-    e = hipGetLastError();
-  }
-  const size_t act_ld = size_t(c->act_ld);
-  std::vector<int8_t> tmp(size_t(n) * act_ld);
-  if (e == hipSuccess) e = hipMemcpyAsync(tmp.data(), c->d_act[0], tmp.size(), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipMemcpy(after, m->d_l0_stats, sizeof(after), hipMemcpyDeviceToHost);
-  fdnn_ctx_free(c);
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("layer 0: ") + hipGetErrorString(e));
-  for (int f = 0; f < n; ++f)
-    for (int i = 0; i < h.hidden; ++i) u8_out[size_t(f) * h.hidden + i] = uint8_t(tmp[size_t(f) * act_ld + i]) ^ 0x80;
-  if (recomputed) *recomputed = after[1] - before[1];
-  return FDNN_OK;
-}
-
-int fdnn_debug_layer0_screen(fdnn_model *m, const float *x, int n, uint8_t *u8_out, float *t_out, float *dd_out, unsigned long long *recomputed) {
-  if (!m || !x || !u8_out || !t_out || !dd_out || n <= 0) return fail(FDNN_E_ARG, "bad argument");
-  if (!m->d_w0d) return fail(FDNN_E_STATE, "this model's input layer has no int8 screening (input width outside 64..496)");
-  DeviceGuard g(m->device);
-  const BlobHeader &h = m->hm.hdr;
-  fdnn_ctx *c = nullptr;
-  int rc = make_ctx(m, n, &c);
-  if (rc) return rc;
-  const size_t outs = size_t(n) * h.hidden;
-  unsigned long long before[2] = {0, 0}, after[2] = {0, 0};
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_l0_dbg_t), outs * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->d_l0_dbg_dd), outs * sizeof(float));
-  if (e == hipSuccess) e = hipMemset(c->d_l0_dbg_t, 0xff, outs * sizeof(float));  // NaN: an output the screening kernel did not visit
-  if (e == hipSuccess) e = hipMemset(c->d_l0_dbg_dd, 0xff, outs * sizeof(float));
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(before, m->d_l0_stats, sizeof(before), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x, sizeof(float) * size_t(n) * h.in_dim, hipMemcpyHostToDevice, c->stream);
-  const int kernel_before = m->l0_kernel;
-  if (e == hipSuccess) {
-    if (m->l0_kernel == 0) m->l0_kernel = 4;  // the int8 screening whatever the batch size
-    run_layer0(c, c->d_x, c->stream, nullptr);
-    m->l0_kernel = kernel_before;
-    e = hipGetLastError();
-  }
-  const size_t act_ld = size_t(c->act_ld);
-  std::vector<int8_t> tmp(size_t(n) * act_ld);
-  if (e == hipSuccess) e = hipMemcpyAsync(tmp.data(), c->d_act[0], tmp.size(), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(t_out, c->d_l0_dbg_t, outs * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dd_out, c->d_l0_dbg_dd, outs * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipMemcpy(after, m->d_l0_stats, sizeof(after), hipMemcpyDeviceToHost);
-  fdnn_ctx_free(c);
-  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("layer 0 (screen debug): ") + hipGetErrorString(e));
-  for (int f = 0; f < n; ++f)
-    for (int i = 0; i < h.hidden; ++i) u8_out[size_t(f) * h.hidden + i] = uint8_t(tmp[size_t(f) * act_ld + i]) ^ 0x80;
-  if (recomputed) *recomputed = after[1] - before[1];
-  return FDNN_OK;
-}
-
-// ---------------------------------------------------------------- per-kernel timing
-int fdnn_profile_begin(fdnn_model *m) {
-  if (!m) return fail(FDNN_E_ARG, "null model");
-  std::lock_guard<std::mutex> lk(m->mu);
-  for (auto &r : m->prof) {
-    hipEventDestroy(r.a);
-    hipEventDestroy(r.b);
-  }
-  m->prof.clear();
-  m->profiling = true;
-  return FDNN_OK;
-}
-
-int fdnn_profile_end(fdnn_model *m, double *ms, int *launches) {
-  if (!m || !ms || !launches) return fail(FDNN_E_ARG, "null argument");
-  DeviceGuard g(m->device);
-  std::vector<fdnn_model::ProfRec> recs;
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    m->profiling = false;
-    recs.swap(m->prof);
-  }
-  for (int k = 0; k < FDNN_PROF_KINDS; ++k) {
-    ms[k] = 0.0;
-    launches[k] = 0;
-  }
-  int rc = FDNN_OK;
-  for (auto &r : recs) {
-    float t = 0.0f;
-    hipError_t e = hipEventSynchronize(r.b);
-    if (e == hipSuccess) e = hipEventElapsedTime(&t, r.a, r.b);
-    if (e == hipSuccess) {
-      ms[r.kind] += t;
-      launches[r.kind]++;
-    } else {
-      rc = fail(FDNN_E_DEVICE, std::string("profile: ") + hipGetErrorString(e));
-    }
-    hipEventDestroy(r.a);
-    hipEventDestroy(r.b);
-  }
-  return rc;
-}
-
-// ---------------------------------------------------------------- weight blob exchange
-int fdnn_model_blob_size(const fdnn_model *m, size_t *bytes) {
-  if (!m || !bytes) return fail(FDNN_E_ARG, "null argument");
-  *bytes = m->hm.blob.size();
-  return FDNN_OK;
-}
-
-int fdnn_model_export_blob(const fdnn_model *m, void *d_dst, size_t capacity, void *stream) {
-  if (!m || !d_dst) return fail(FDNN_E_ARG, "null argument");
-  if (capacity < m->hm.blob.size()) return fail(FDNN_E_ARG, "destination smaller than the blob");
-  DeviceGuard g(m->device);
-  HIP_TRY(hipMemcpyAsync(d_dst, m->d_blob, m->hm.blob.size(), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return FDNN_OK;
-}
-
-int fdnn_model_import_blob(const void *d_src, size_t bytes, int device, fdnn_model **out) {
-  if (!d_src || !out) return fail(FDNN_E_ARG, "null argument");
-  *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return fail(FDNN_E_DEVICE, "no HIP device available: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(FDNN_E_ARG, "device index out of range");
-  DeviceGuard g(device);
-  std::vector<uint8_t> host(bytes);
-  HIP_TRY(hipMemcpy(host.data(), d_src, bytes, hipMemcpyDeviceToHost));
-  fdnn_model *m = new fdnn_model();
-  std::string msg;
-  int rc = fdnn::adopt_blob(std::move(host), &m->hm, &msg);
-  if (rc) {
-    delete m;
-    return fail(rc, msg);
-  }
-  m->device = device;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->d_blob), bytes);
-  if (e == hipSuccess) e = hipMemcpy(m->d_blob, d_src, bytes, hipMemcpyDeviceToDevice);
-  if (e != hipSuccess) {
-    if (m->d_blob) hipFree(m->d_blob);
-    delete m;
-    return fail(FDNN_E_DEVICE, std::string("blob import: ") + hipGetErrorString(e));
-  }
-  rc = build_l0_image(m);
-  if (rc) {
-    hipFree(m->d_blob);
-    if (m->d_w0t) hipFree(m->d_w0t);
-    if (m->d_w0norm) hipFree(m->d_w0norm);
-    if (m->d_w0d) hipFree(m->d_w0d);
-    if (m->d_w0stat) hipFree(m->d_w0stat);
-    if (m->d_lutpair) hipFree(m->d_lutpair);
-    if (m->d_l0_stats) hipFree(m->d_l0_stats);
-    delete m;
-    return rc;
-  }
-  *out = m;
-  return FDNN_OK;
-}
-
-// ---------------------------------------------------------------- host-only helpers
-int fdnn_host_model_load(const char *path, float cutoff, fdnn_host_model **out) {
-  if (!path || !out) return fail(FDNN_E_ARG, "null argument");
-  *out = nullptr;
-  fdnn_host_model *hm = new fdnn_host_model();
-  std::string msg;
-  int rc = fdnn::load_host_model(path, cutoff, &hm->hm, &msg);
-  if (rc) {
-    delete hm;
-    return fail(rc, msg);
-  }
-  *out = hm;
-  return FDNN_OK;
-}
-
-void fdnn_host_model_free(fdnn_host_model *hm) { delete hm; }
-int fdnn_host_model_layers(const fdnn_host_model *hm) { return hm ? hm->hm.hdr.n_affine : -1; }
-
-int fdnn_host_model_layer_in(const fdnn_host_model *hm, int j) {
-  if (!hm || j < 0 || j >= hm->hm.hdr.n_affine) return -1;
-  return j == 0 ? hm->hm.hdr.in_dim : hm->hm.hdr.q[j - 1].cols;
-}
-
-int fdnn_host_model_layer_out(const fdnn_host_model *hm, int j) {
-  if (!hm || j < 0 || j >= hm->hm.hdr.n_affine) return -1;
-  return j == 0 ? hm->hm.hdr.hidden : hm->hm.hdr.q[j - 1].rows;
-}
-
-float fdnn_host_model_multiplier(const fdnn_host_model *hm, int j) {
-  if (!hm || j < 1 || j >= hm->hm.hdr.n_affine) return 0.0f;
-  return hm->hm.hdr.q[j - 1].mult;
-}
-
-int fdnn_host_model_weights_q(const fdnn_host_model *hm, int j, int8_t *out) {
-  if (!hm || !out || j < 1 || j >= hm->hm.hdr.n_affine) return fail(FDNN_E_ARG, "bad layer index");
-  const QLayerDesc &d = hm->hm.hdr.q[j - 1];
-  const int8_t *w = hm->hm.wq(j - 1);
-  for (int r = 0; r < d.rows; ++r) std::memcpy(out + size_t(r) * d.cols, w + size_t(r) * d.cols_pad, size_t(d.cols));
-  return FDNN_OK;
-}
-
-int fdnn_host_model_bias(const fdnn_host_model *hm, int j, float *out) {
-  if (!hm || !out || j < 0 || j >= hm->hm.hdr.n_affine) return fail(FDNN_E_ARG, "bad layer index");
-  if (j == 0)
-    std::memcpy(out, hm->hm.b0(), sizeof(float) * size_t(hm->hm.hdr.hidden));
-  else
-    std::memcpy(out, hm->hm.bias(j - 1), sizeof(float) * size_t(hm->hm.hdr.q[j - 1].rows));
-  return FDNN_OK;
-}
-
-int fdnn_host_model_wsum128(const fdnn_host_model *hm, int j, int32_t *out) {
-  if (!hm || !out || j < 1 || j >= hm->hm.hdr.n_affine) return fail(FDNN_E_ARG, "bad layer index");
-  std::memcpy(out, hm->hm.wsum(j - 1), sizeof(int32_t) * size_t(hm->hm.hdr.q[j - 1].rows));
-  return FDNN_OK;
-}
-
-long long fdnn_host_model_risky_pairs(const fdnn_host_model *hm, int j) {
-  if (!hm || j < 1 || j >= hm->hm.hdr.n_affine) return -1;
-  return hm->hm.hdr.q[j - 1].n_fix;
-}
-
-size_t fdnn_host_model_blob_size(const fdnn_host_model *hm) { return hm ? hm->hm.blob.size() : 0; }
-
-int fdnn_host_model_blob(const fdnn_host_model *hm, void *out, size_t capacity) {
-  if (!hm || !out) return fail(FDNN_E_ARG, "null argument");
-  if (capacity < hm->hm.blob.size()) return fail(FDNN_E_ARG, "destination smaller than the blob");
-  std::memcpy(out, hm->hm.blob.data(), hm->hm.blob.size());
-  return FDNN_OK;
-}
-
-int fdnn_host_blob_check(const void *bytes, size_t size, int *input_dim, int *hidden_dim, int *output_dim,
-                         int *n_affine) {
-  if (!bytes) return fail(FDNN_E_ARG, "null argument");
-  std::vector<uint8_t> copy(static_cast<const uint8_t *>(bytes), static_cast<const uint8_t *>(bytes) + size);
-  fdnn::HostModel hm;
-  std::string msg;
-  int rc = fdnn::adopt_blob(std::move(copy), &hm, &msg);
-  if (rc) return fail(rc, msg);
-  if (input_dim) *input_dim = hm.hdr.in_dim;
-  if (hidden_dim) *hidden_dim = hm.hdr.hidden;
-  if (output_dim) *output_dim = hm.hdr.out_dim;
-  if (n_affine) *n_affine = hm.hdr.n_affine;
-  return FDNN_OK;
-}
-
-int fdnn_host_sigmoid_lut(uint8_t *out) {
-  if (!out) return fail(FDNN_E_ARG, "null argument");
-  fdnn::build_sigmoid_lut(out);
-  return FDNN_OK;
-}
-
-int fdnn_host_quantize(const float *w, int rows, int cols, float cutoff, int8_t *out, float *multiplier) {
-  if (!w || !out || !multiplier || rows <= 0 || cols <= 0) return fail(FDNN_E_ARG, "bad argument");
-  fdnn::quantize_layer(w, rows, cols, cutoff, out, multiplier);
-  return FDNN_OK;
-}
-
-}  // extern "C"
+extern "C" const char *fdnn_last_error(void) { return g_err.c_str(); }

@@ -217,12 +217,14 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const float *d_x, int n, const int8_
   c->l0_chain_only = !small && overlap && !all_fused;  // see fdnn_ctx: an overlapped scale pass needs room beside layer 0
   hipStream_t cs = small ? sl.stream : s->s_main;
   if (after) HIP_TRY(hipStreamWaitEvent(cs, after, 0));
-  HIP_TRY(fdnn::ctx_enter(c, cs));
+  fdnn::CtxUse use;  // every way out notes the stream the batch ends on and puts the batch's frame count back
+  use.n_after = n;
+  HIP_TRY(use.enter(c, cs));
   int rc = FDNN_OK;
-  hipStream_t end = cs;
+  hipStream_t &end = use.s;  // the stream the batch's last work goes to
   if (small) {
     rc = fdnn::run_hidden(c, d_x, cs, nullptr);
-    if (!rc) rc = fdnn::run_output(c, 0, n, d_masks, d_out, cs, nullptr, nullptr, nullptr, nullptr, d_bits);
+    if (!rc) rc = fdnn::run_output(c, {.count = n, .d_masks = d_masks, .d_bits = d_bits, .d_out = d_out}, cs);
   } else {
     // very large batches go chunk by chunk (fdnn::frame_chunks), and the chunks overlap like batches do: chunk j's
     // scale pass runs on the tail stream under chunk j+1's layer 0.  One context serves all chunks, so the compute
@@ -230,27 +232,25 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const float *d_x, int n, const int8_
     // read them: it waits for `tail_done` there.
     const size_t D = size_t(s->m->hm.hdr.in_dim), O = size_t(s->m->hm.hdr.out_dim), wpr = (O + 63) / 64;
     bool first = true;
+    end = overlap ? s->s_tail : cs;
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
       const auto &ch = chunks[ci];
       c->n = ch.second;
       rc = fdnn::run_hidden(c, d_x + size_t(ch.first) * D, cs, nullptr);
       if (rc) break;
       if (!first && overlap) HIP_TRY(hipStreamWaitEvent(cs, sl.tail_done, 0));
-      rc = fdnn::run_output(c, 0, ch.second, d_masks ? d_masks + size_t(ch.first) * O : nullptr, d_out + size_t(ch.first) * O, cs,
-                            nullptr, nullptr, overlap ? s->s_tail : nullptr, overlap ? sl.gemm_done : nullptr,
-                            d_bits ? d_bits + size_t(ch.first) * wpr : nullptr);
+      rc = fdnn::run_output(c, {.count = ch.second, .d_masks = d_masks ? d_masks + size_t(ch.first) * O : nullptr,
+                                .d_bits = d_bits ? d_bits + size_t(ch.first) * wpr : nullptr, .d_out = d_out + size_t(ch.first) * O,
+                                .tail = overlap ? s->s_tail : nullptr, .gemm_done = overlap ? sl.gemm_done : nullptr}, cs);
       if (rc) break;
       // (without the overlap everything is on the compute stream, in order; a record is 3-4 us of queue time)
       if (overlap && ci + 1 < chunks.size()) HIP_TRY(hipEventRecord(sl.tail_done, s->s_tail));
       first = false;
     }
-    c->n = n;
-    end = overlap ? s->s_tail : cs;
   }
   // bit-mask host batches: the rows compacted (active probabilities + one value per frame) for the trip over PCIe
   if (!rc && d_bits && d_comp && stride > 0)
     fdnn::launch_lazy_compact(d_out, d_bits, d_comp, n, s->m->hm.hdr.out_dim, stride, end);
-  fdnn::ctx_leave(c, end);
   if (rc) return rc;
   *last_stream = end;
   return FDNN_OK;

@@ -453,7 +453,7 @@ _FT128_FUSED = ("fdnn_gemm.hip:1359 (qgemm_fused_ok: the row sums of at most 32 
                 "i.e. with rows_pad / 256 * n_pad / 128 <= 256 and no taps: the 128-byte-step shape (gemm.out.ft128.bk128.*) takes every such launch")
 _FT128_HID = ("fdnn_model.cpp:346 (hidden width <= 32 768 = 128 node tiles) and fdnn_gemm.hip:1298-1320: for such a layer frame tile 128 comes only from "
               "qgemm_frame_tile's first loop, where rows_pad / 256 * ceil(n / 128) <= 256 < rows_pad / 256 * ceil(n / 64) puts rows_pad / 128 * ceil(n / 128) "
-              "in (256, 512] and qgemm_node_tile (:1369-1370, fdnn_runtime.cpp:333-335) answers 128: the 2 x 2-wave shape (gemm.hid.ft128.nt128.*), taps included; "
+              "in (256, 512] and qgemm_node_tile (:1369-1370, fdnn_runtime.cpp:311-313) answers 128: the 2 x 2-wave shape (gemm.hid.ft128.nt128.*), taps included; "
               "the true-divide layers (also frame tile 128) take their own shape")
 _FT160 = ("fdnn_gemm.hip:1306-1319 (qgemm_frame_tile's cost model, the only source of 160; :1269 is the shape's only launch; FDNN_FRAME_TILE is read only in "
           "-DFDNN_ABLATION builds): ceil(n / 256) <= ceil(n / 160) gives the 256-frame candidate at most as many blocks, hence at most twice the rounds "

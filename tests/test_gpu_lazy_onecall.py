@@ -88,3 +88,34 @@ def test_one_call_lazy_from_many_threads(mid_model_path):
         h.join()
     assert not bad
     dnn.delete()
+
+
+def test_host_lazy_forms_across_a_chunk_boundary(mid_model_path):
+    """One frame more than a chunk (kChunkFrames = 20 480): the host forms score such a call as two chunks on one pooled
+    context -- second upload of rows and bits, second compacted return at its offset in the caller's array -- and must
+    return the bytes of the same rows scored as two calls of 20 480 and 1 frames; the device form (frame_chunks: the same two
+    chunks, at offsets into the caller's device buffers) likewise."""
+    import torch
+
+    from conftest import golden
+    from fast_dnn_amd import convert as CV
+
+    n, cut, O = 20480 + 1, 20480, 1000
+    x = np.ascontiguousarray(np.resize(golden("tiny.npz")["x16"], (n, 432)))
+    bits = F.pack_mask_bits(F.generate_masks_fast(n, O, 0.40, 0.03, seed=7))
+    dnn = api.QuantizedDnn.loadFromFile(mid_model_path)
+    want = np.concatenate([dnn.calculateLazy(x[:cut], bits=bits[:cut]), dnn.calculateLazy(x[cut:], bits=bits[cut:])])
+    assert np.array_equal(dnn.calculateLazy(x, bits=bits), want)
+    dx, db = torch.from_numpy(x).cuda(), torch.from_numpy(bits.view(np.int64)).cuda()
+    od = torch.zeros((n, O), dtype=torch.float32, device="cuda")
+    dnn.calculate_lazy_bits_device(dx.data_ptr(), n, db.data_ptr(), od.data_ptr(), 0)
+    torch.cuda.synchronize()
+    assert np.array_equal(od.cpu().numpy(), want)
+    # raw frames: the rows the spec splices from them, scored as two calls
+    offsets, raw_dim = list(range(-5, 6)), 39
+    dnn.setSplice(offsets, raw_dim)
+    raw = np.ascontiguousarray(x[:, :raw_dim])
+    rows = CV.splice_frames(raw, offsets, 432)
+    want_raw = np.concatenate([dnn.calculateLazy(rows[:cut], bits=bits[:cut]), dnn.calculateLazy(rows[cut:], bits=bits[cut:])])
+    assert np.array_equal(dnn.calculateLazyRaw(raw, bits), want_raw)
+    dnn.delete()
