@@ -33,6 +33,7 @@
 // on the ds_read_b128 fragment reads, so every 16-lane read group hits 16
 // distinct 16-byte slots (the k-loop's reads are conflict free; what SQ_LDS_BANK_CONFLICT shows for this
 // kernel -- 1.2 M cycles per hidden launch -- are the epilogue's table byte gathers and tile transposition).
+#include <array>
 #include <atomic>
 
 #include "fdnn_device.hpp"
@@ -1114,108 +1115,102 @@ constexpr int gemm_shape(int NF, int WN, int BK, int STAGES, bool FAST, int WM) 
          : WN == 2 ? (NF == 4 ? gs_ft256 : gs_ft320)
          : NF == 1 ? (BK == 128 ? gs_ft32 : gs_ft32bk64)
          : NF == 2 ? (BK == 128 ? gs_ft64 : gs_ft64bk64)
-         : NF == 5 ? gs_ft160
          : BK == 128 ? gs_ft128bk128
          : STAGES == 6 ? gs_ft128bk64x6
                        : gs_ft128;
 }
 
-template <int NF, int WN, int BK, int STAGES, bool OUTPUT, bool FAST = true, int WM = 4>
+// One tile shape, one direction: the instances it may start, by branch.  An instance exists -- is compiled, gets its LDS
+// attribute, can be launched -- exactly where the table below names it; the selection under the table picks among those.
+// TAPS = false: a shape whose launch site takes no tap launches (launch_qgemm `case 128`).
+template <int NF, int WN, int BK, int STAGES, bool OUTPUT, bool FAST = true, int WM = 4, bool TAPS = true>
 void launch_cfg(const QGemmParams &p, hipStream_t s) {
   using Cfg = GemmCfg<NF, WN, BK, STAGES, WM>;
-  const auto note = [](int branch) {
-    if (g_launch_note_on.load(std::memory_order_relaxed)) note_launch(gemm_launch_name(OUTPUT, gemm_shape(NF, WN, BK, STAGES, FAST, WM), branch));
-  };
-  const int MT = p.rows_pad / Cfg::G_BM, NT = p.n_pad / Cfg::FT;
-  const int blocks = 8 * MT * ((NT + 7) / 8);
-  auto k_prod = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, false, false, false, WM>;
-  auto k_tap = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, true, FAST, false, false, false, WM>;
-  auto k_plain = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, OUTPUT, false, false, WM>;  // hidden layers: same as k_prod
-  auto k_masked = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, OUTPUT, OUTPUT, false, WM>;
-  auto k_anyw = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, OUTPUT, false, OUTPUT, WM>;
-  auto k_masked_anyw = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, OUTPUT, OUTPUT, OUTPUT, WM>;
-  constexpr bool kCanFuse = OUTPUT && FAST && WM == 4 && NF >= 4;  // the 8-wave shapes and the 4-wave 128- / 160-frame shapes (two workgroups per CU)
-  auto k_fused = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, kCanFuse, false, false, WM, kCanFuse>;  // (= k_plain where it cannot)
-  auto k_fused_masked = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, kCanFuse, kCanFuse, false, WM, kCanFuse>;
-  auto k_fused_anyw = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, kCanFuse, false, kCanFuse, WM, kCanFuse>;  // widths % 32 != 0
-  auto k_fused_masked_anyw = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, kCanFuse, kCanFuse, kCanFuse, WM, kCanFuse>;
-  // layers without saturating pairs, the 8-wave production shapes: no entry walk in the loop (the other shapes: the same kernels)
+  using Kernel = void (*)(QGemmParams);
+  // the fused soft-max: the 8-wave shapes and the 4-wave 128-frame shapes of small launches (two workgroups per CU).  The
+  // 3-stage 64-byte-step shape is the 128-frame tile of launches of more than 256 workgroups, which qgemm_fused_ok refuses.
+  constexpr bool kCanFuse = OUTPUT && FAST && WM == 4 && NF >= 4 && (BK == 128 || STAGES == 6);
+  // layers without saturating pairs, the 8-wave production shapes: no entry walk in the loop
 #ifdef FDNN_NO_NOFIX  // (measurement builds: the instances with the walk for every layer)
   constexpr bool kNoFix = false;
 #else
   constexpr bool kNoFix = FAST && WM == 4 && WN == 2 && NF >= 4;
 #endif
-  auto k_prod_nofix = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, false, false, false, WM, false, kNoFix && !OUTPUT>;
-  auto k_fused_nofix = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, kCanFuse, false, false, WM, kCanFuse, kNoFix && kCanFuse>;
-  auto k_fused_masked_nofix = qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, false, FAST, kCanFuse, kCanFuse, false, WM, kCanFuse, kNoFix && kCanFuse>;
+#define FDNN_K(TAP, PLAIN, MASKED, ANYW, FUSED, NOFIX) qgemm_kernel<NF, WN, BK, STAGES, OUTPUT, TAP, FAST, PLAIN, MASKED, ANYW, WM, FUSED, NOFIX>
+  static const auto kernels = [] {
+    std::array<Kernel, gb_count> k{};
+    if constexpr (TAPS) k[gb_tap] = FDNN_K(true, false, false, false, false, false);
+    if constexpr (!OUTPUT) {
+      k[gb_prod] = FDNN_K(false, false, false, false, false, false);
+      if constexpr (kNoFix) k[gb_prod_nofix] = FDNN_K(false, false, false, false, false, true);
+    } else {
+      k[gb_plain] = FDNN_K(false, true, false, false, false, false);
+      k[gb_anyw] = FDNN_K(false, true, false, true, false, false);  // widths % 32 != 0
+      k[gb_masked] = FDNN_K(false, true, true, false, false, false);
+      k[gb_masked_anyw] = FDNN_K(false, true, true, true, false, false);  // 8001 nodes: 0.33 ms against 0.41 through the general epilogue
+    }
+    if constexpr (kCanFuse) {
+      k[gb_fused] = FDNN_K(false, true, false, false, true, false);
+      k[gb_fused_anyw] = FDNN_K(false, true, false, true, true, false);
+      k[gb_fused_masked] = FDNN_K(false, true, true, false, true, false);
+      k[gb_fused_masked_anyw] = FDNN_K(false, true, true, true, true, false);
+      if constexpr (kNoFix) {
+        k[gb_fused_nofix] = FDNN_K(false, true, false, false, true, true);
+        k[gb_fused_masked_nofix] = FDNN_K(false, true, true, false, true, true);
+      }
+    }
+    return k;
+  }();
+#undef FDNN_K
   // the attribute is per device: a process may hold models on several GPUs
   static std::atomic<unsigned long long> attr_set{0};
   int dev = 0;
   (void)hipGetDevice(&dev);
   const unsigned long long dev_bit = 1ull << (dev & 63);
   if (!(attr_set.load(std::memory_order_acquire) & dev_bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_prod), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_tap), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_masked), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_anyw), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_masked_anyw), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_masked), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_anyw), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_masked_anyw), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_prod_nofix), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_nofix), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_masked_nofix), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
+    for (const Kernel k : kernels)
+      if (k) hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
     attr_set.fetch_or(dev_bit, std::memory_order_release);
   }
+  const int MT = p.rows_pad / Cfg::G_BM, NT = p.n_pad / Cfg::FT;
+  int branch, blocks = 8 * MT * ((NT + 7) / 8);
   if (kCanFuse && p.fuse_s != nullptr) {
     // fused soft-max: the node tiles of a frame tile are consecutive blocks (what a workgroup that gave up waiting left
     // unscaled is scaled by its frame tile's last workgroup: one launch)
-    if ((p.rows & 31) != 0) {
-      note(p.mask ? gb_fused_masked_anyw : gb_fused_anyw);
-      hipLaunchKernelGGL(p.mask ? k_fused_masked_anyw : k_fused_anyw, dim3(MT * NT), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-    } else if (kNoFix && p.fix_ent == nullptr) {
-      note(p.mask ? gb_fused_masked_nofix : gb_fused_nofix);
-      hipLaunchKernelGGL(p.mask ? k_fused_masked_nofix : k_fused_nofix, dim3(MT * NT), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-    } else {
-      note(p.mask ? gb_fused_masked : gb_fused);
-      hipLaunchKernelGGL(p.mask ? k_fused_masked : k_fused, dim3(MT * NT), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-    }
-  } else if (p.tap_acc) {
-    note(gb_tap);
-    hipLaunchKernelGGL(k_tap, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  } else if (OUTPUT && p.mask == nullptr && (p.rows & 31) == 0) {
-    note(gb_plain);
-    hipLaunchKernelGGL(k_plain, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  } else if (OUTPUT && p.mask == nullptr) {
-    note(gb_anyw);
-    hipLaunchKernelGGL(k_anyw, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  } else if (OUTPUT && p.mask != nullptr && (p.rows & 3) == 0) {
-    note(gb_masked);
-    hipLaunchKernelGGL(k_masked, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  } else if (OUTPUT && p.mask != nullptr) {  // 8001 nodes: 0.33 ms against 0.41 through the general epilogue
-    note(gb_masked_anyw);
-    hipLaunchKernelGGL(k_masked_anyw, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
-  } else if (kNoFix && !OUTPUT && p.fix_ent == nullptr) {
-    note(gb_prod_nofix);
-    hipLaunchKernelGGL(k_prod_nofix, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
+    blocks = MT * NT;
+    if ((p.rows & 31) != 0)
+      branch = p.mask ? gb_fused_masked_anyw : gb_fused_anyw;
+    else if (kNoFix && p.fix_ent == nullptr)
+      branch = p.mask ? gb_fused_masked_nofix : gb_fused_nofix;
+    else
+      branch = p.mask ? gb_fused_masked : gb_fused;
+  } else if (TAPS && p.tap_acc) {
+    branch = gb_tap;
+  } else if (OUTPUT) {
+    if (p.mask == nullptr)
+      branch = (p.rows & 31) == 0 ? gb_plain : gb_anyw;
+    else
+      branch = (p.rows & 3) == 0 ? gb_masked : gb_masked_anyw;
   } else {
-    note(gb_prod);
-    hipLaunchKernelGGL(k_prod, dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
+    branch = kNoFix && p.fix_ent == nullptr ? gb_prod_nofix : gb_prod;
   }
+  if (g_launch_note_on.load(std::memory_order_relaxed)) note_launch(gemm_launch_name(OUTPUT, gemm_shape(NF, WN, BK, STAGES, FAST, WM), branch));
+  hipLaunchKernelGGL(kernels[branch], dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
 }
+
+// a 128-frame launch of at most 256 workgroups, every one with a CU of its own (no taps): the one latency-bound k-loop per
+// launch takes whole cache lines per step (128-byte k-steps); every other 128-frame launch the 64-byte-step shape
+inline bool ft128_one_round(const QGemmParams &p) { return static_cast<long>(p.rows_pad / 256) * (p.n_pad / 128) <= 256 && !p.tap_acc; }
 
 template <bool OUTPUT>
 void launch_qgemm(const QGemmParams &p, hipStream_t s) {
-  if (!p.fastdiv) {  // layer whose coefficient failed the exact-division check (e.g. 127/0 = inf)
-    launch_cfg<4, 1, 64, 3, OUTPUT, false>(p, s);
-    return;
-  }
-  static const int small_bk = [] {
+  if (!p.fastdiv) return launch_cfg<4, 1, 64, 3, OUTPUT, false>(p, s);  // layer whose coefficient failed the exact-division check (e.g. 127/0 = inf)
+#ifdef FDNN_ABLATION  // measurement builds: FDNN_SMALL_BK=64 gives the three small-launch shapes 64-byte k-steps in a 6-stage ring
+  static const bool bk64 = [] {
     const char *e = FDNN_TUNE_ENV("FDNN_SMALL_BK");
-    return e ? std::atoi(e) : 128;
+    return e && std::atoi(e) != 128;
   }();
+#endif
   switch (p.frame_tile) {
     // few frames: 32- / 64-frame tiles put four / two times as many workgroups on the chip; 128-byte
     // k-steps (3-stage ring) halve the barriers of the latency-bound loop: 16.6 vs 21 us per
@@ -1228,48 +1223,40 @@ void launch_qgemm(const QGemmParams &p, hipStream_t s) {
     // layers 101-110 -> 88-98 us from 8 to 700 frames (tools/batch_sweep.py; up to three workgroups per CU, beyond that
     // the extra activation traffic loses).  Hidden layers only: the output layer's exp / transposition epilogue makes its
     // narrow tiles slower (27 vs 21 us).
-    case 32: {
-      static const int force_wm = [] {
-        const char *e = FDNN_TUNE_ENV("FDNN_SMALL_WM");
-        return e ? std::atoi(e) : 0;
-      }();
-      const long wgs256 = static_cast<long>(p.rows_pad / 256) * (p.n_pad / 32);
-      const int wm = force_wm ? force_wm : (!OUTPUT && wgs256 * 4 <= 768) ? 1 : 4;
-      if (small_bk == 128 && wm == 1)
-        launch_cfg<1, 1, 128, 4, OUTPUT, true, 1>(p, s);
-      else if (small_bk == 128)
-        launch_cfg<1, 1, 128, FDNN_SMALL_STAGES, OUTPUT>(p, s);
-      else
-        launch_cfg<1, 1, 64, 6, OUTPUT>(p, s);
-      break;
-    }
+    case 32:
+#ifdef FDNN_ABLATION
+      if (bk64) return launch_cfg<1, 1, 64, 6, OUTPUT>(p, s);
+#endif
+      if constexpr (!OUTPUT) {
+        bool one_wave = static_cast<long>(p.rows_pad / 256) * (p.n_pad / 32) * 4 <= 768;
+#ifdef FDNN_ABLATION
+        static const int force_wm = [] {  // FDNN_SMALL_WM=1 / 4: one wave per workgroup or four, whatever the launch's size
+          const char *e = FDNN_TUNE_ENV("FDNN_SMALL_WM");
+          return e ? std::atoi(e) : 0;
+        }();
+        if (force_wm) one_wave = force_wm == 1;
+#endif
+        if (one_wave) return launch_cfg<1, 1, 128, 4, false, true, 1>(p, s);
+      }
+      return launch_cfg<1, 1, 128, FDNN_SMALL_STAGES, OUTPUT>(p, s);
     case 64:
-      if (small_bk == 128)
-        launch_cfg<2, 1, 128, 3, OUTPUT>(p, s);
-      else
-        launch_cfg<2, 1, 64, 6, OUTPUT>(p, s);
-      break;
-    // 4 waves, 64-byte k-step, 3-stage ring, two workgroups per CU; when every workgroup has
-    // a CU of its own anyway (small batches: one latency-bound k-loop per launch) a 6-stage
-    // ring hides twice the load latency per step
+#ifdef FDNN_ABLATION
+      if (bk64) return launch_cfg<2, 1, 64, 6, OUTPUT>(p, s);
+#endif
+      return launch_cfg<2, 1, 128, 3, OUTPUT>(p, s);
     case 128:
-      if (p.node_tile == 128) {  // 128 nodes x 128 frames, 2 x 2 waves, double-buffered 128-byte k-steps, two workgroups per CU
-        launch_cfg<2, 2, 128, 2, OUTPUT, true, 2>(p, s);
-        break;
+      if constexpr (!OUTPUT) {  // 128 nodes x 128 frames, 2 x 2 waves, double-buffered 128-byte k-steps, two workgroups per CU
+        if (p.node_tile == 128) return launch_cfg<2, 2, 128, 2, false, true, 2>(p, s);
       }
-      if (static_cast<long>(p.rows_pad / 256) * (p.n_pad / 128) <= 256 && !p.tap_acc) {
-        if (small_bk == 128)
-          launch_cfg<4, 1, 128, 3, OUTPUT>(p, s);
-        else
-          launch_cfg<4, 1, 64, 6, OUTPUT>(p, s);
-      }
-      else
-        launch_cfg<4, 1, 64, 3, OUTPUT>(p, s);
-      break;
-    case 160: launch_cfg<5, 1, 64, 3, OUTPUT>(p, s); break;
+      // 4 waves, 3-stage ring, two workgroups per CU
+      if (!ft128_one_round(p)) return launch_cfg<4, 1, 64, 3, OUTPUT>(p, s);
+#ifdef FDNN_ABLATION
+      if (bk64) return launch_cfg<4, 1, 64, 6, OUTPUT, true, 4, false>(p, s);
+#endif
+      return launch_cfg<4, 1, 128, 3, OUTPUT, true, 4, false>(p, s);
     // 8 waves, 128-byte k-step (whole cache lines), double buffer, one workgroup per CU
-    case 256: launch_cfg<4, 2, 128, 2, OUTPUT>(p, s); break;
-    default: launch_cfg<5, 2, 128, 2, OUTPUT>(p, s); break;  // 320
+    case 256: return launch_cfg<4, 2, 128, 2, OUTPUT>(p, s);
+    default: return launch_cfg<5, 2, 128, 2, OUTPUT>(p, s);  // 320
   }
 }
 
@@ -1288,7 +1275,7 @@ int qgemm_frame_tile(int rows_pad, int n) {
     const char *e = FDNN_TUNE_ENV("FDNN_FRAME_TILE");
     return e ? std::atoi(e) : 0;
   }();
-  if (forced == 32 || forced == 64 || forced == 128 || forced == 160 || forced == 256 || forced == 320) return forced;
+  if (forced == 32 || forced == 64 || forced == 128 || forced == 256 || forced == 320) return forced;
   const int mt = rows_pad / 256;
   // Few frames: while every workgroup gets a CU of its own the launch is one k-loop deep and
   // latency bound, so the smallest tile that still fits in one round wins -- it has the shortest
@@ -1303,7 +1290,7 @@ int qgemm_frame_tile(int rows_pad, int n) {
     int ft, slots;
     double eff;
   };
-  const Cand cands[] = {{128, 512, 0.55}, {160, 512, 0.55}, {256, 256, 1.0}, {320, 256, 1.0}};
+  const Cand cands[] = {{128, 512, 0.55}, {256, 256, 1.0}, {320, 256, 1.0}};
   int best = 128;
   double best_cost = -1.0;
   for (const Cand &c : cands) {
@@ -1334,38 +1321,41 @@ bool qgemm_small_pick(int rows_pad, int K, int n, int fastdiv, bool output) {
   return n <= lim && qgemm_small_ok(K, fastdiv);
 }
 
-// Mid-size batches of the hidden layers: when the layer is between one and two rounds of 128 x 128 tiles (2 049 .. 4 096
-// frames on a 2048-node layer), the four-wave 128 x 128 shape -- two workgroups per CU, so one's prologue / epilogue
-// hides under the other's k-loop -- beats the 256-node tiles of the same area (tools/batch_sweep.py, six hidden layers:
-// 140 vs 158 us at 2 560 frames, 141 vs 158 at 3 000, 151 vs 162 at 4 000; it loses below (123 vs 119 at 2 000: one
-// workgroup per CU again) and above (229 vs 202 at 5 000), and on the 8000-node output layer).  Returns 128 or 256;
-// with 128 the frame tile is 128 as well.
 bool qgemm_fused_ok(const QGemmParams &p) {
   static const bool off = [] {
     const char *e = std::getenv("FDNN_FUSE_NORM");
     return e && std::atoi(e) == 0;
   }();
   if (off || p.small || p.node_tile != 256 || !p.fastdiv || (p.mask && !p.mask_bits) || p.tap_acc || p.tap_logit) return false;
-  if (p.frame_tile != 320 && p.frame_tile != 256 && p.frame_tile != 160 && p.frame_tile != 128) return false;
+  if (p.frame_tile != 320 && p.frame_tile != 256 && p.frame_tile != 128) return false;
+  // the 128-frame tiles of more than one round have no fused form: none can come about here, where MT <= 32 below and
+  // qgemm_frame_tile's cost model prefers 128 from 129 node tiles up (a forced FDNN_FRAME_TILE apart)
+  if (p.frame_tile == 128 && !ft128_one_round(p)) return false;
   const int MT = p.rows_pad / 256;
   int L = 1;
   while (L < MT) L <<= 1;
   // the epilogue's LDS: one 32 x 64 float tile per wave, then 4 partial rows + the inverses + L rows of S, below the
-  // table / bias area (GemmCfg::FIX_OFF: two 128-byte-step stages for the 8-wave shapes, three 64-byte-step stages
-  // for the 4-wave ones)
+  // table / bias area (GemmCfg::FIX_OFF: two 128-byte-step stages for the 8-wave shapes, at least three 64-byte-step
+  // stages for the 4-wave ones)
   const bool eight = p.frame_tile >= 256;
   const long need = 8192 + (eight ? 8 : 4) * 32 * 68 * 4 + (5L * p.frame_tile + 4 + static_cast<long>(L) * p.frame_tile) * 4;
   const long have = static_cast<long>(256 + p.frame_tile) * (eight ? 128 * 2 : 64 * 3);
   return L <= 32 && need <= have;
 }
 
+// Mid-size batches of the hidden layers: when the layer is between one and two rounds of 128 x 128 tiles (2 049 .. 4 096
+// frames on a 2048-node layer), the four-wave 128 x 128 shape -- two workgroups per CU, so one's prologue / epilogue
+// hides under the other's k-loop -- beats the 256-node tiles of the same area (tools/batch_sweep.py, six hidden layers:
+// 140 vs 158 us at 2 560 frames, 141 vs 158 at 3 000, 151 vs 162 at 4 000; it loses below (123 vs 119 at 2 000: one
+// workgroup per CU again) and above (229 vs 202 at 5 000), and on the 8000-node output layer).  Returns 128 or 256;
+// with 128 the frame tile is 128 as well.
 int qgemm_node_tile(int rows_pad, int n, bool output) {
   static const int forced = [] {
     const char *e = FDNN_TUNE_ENV("FDNN_NODE_TILE");
     return e ? std::atoi(e) : 0;
   }();
-  if (forced == 128 || forced == 256) return forced;
   if (output) return 256;
+  if (forced == 128 || forced == 256) return forced;
   const long tiles = static_cast<long>(rows_pad / 128) * ((n + 127) / 128);
   return (tiles > 256 && tiles <= 512) ? 128 : 256;
 }

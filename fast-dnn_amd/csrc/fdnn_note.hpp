@@ -8,15 +8,16 @@
 
 namespace fdnn {
 
-// GEMM tile shapes of launch_qgemm (fdnn_gemm.hip), in the order of its switch; the last three exist only where a
-// measurement build (-DFDNN_ABLATION) sets FDNN_SMALL_BK
-enum GemmShape { gs_tdiv, gs_ft32w1, gs_ft32, gs_ft64, gs_ft128nt128, gs_ft128bk128, gs_ft128, gs_ft160, gs_ft256, gs_ft320, gs_ft32bk64, gs_ft64bk64, gs_ft128bk64x6 };
+// GEMM tile shapes of launch_qgemm (fdnn_gemm.hip), in the order of its switch; the last three are compiled only in a
+// measurement build (-DFDNN_ABLATION), which takes them where FDNN_SMALL_BK is set
+enum GemmShape { gs_tdiv, gs_ft32w1, gs_ft32, gs_ft64, gs_ft128nt128, gs_ft128bk128, gs_ft128, gs_ft256, gs_ft320, gs_ft32bk64, gs_ft64bk64, gs_ft128bk64x6 };
 // branches of launch_cfg
 enum GemmBranch {
-  gb_tap, gb_prod, gb_prod_nofix, gb_plain, gb_anyw, gb_masked, gb_masked_anyw, gb_fused, gb_fused_masked, gb_fused_anyw, gb_fused_masked_anyw, gb_fused_nofix, gb_fused_masked_nofix
+  gb_tap, gb_prod, gb_prod_nofix, gb_plain, gb_anyw, gb_masked, gb_masked_anyw, gb_fused, gb_fused_masked, gb_fused_anyw, gb_fused_masked_anyw, gb_fused_nofix, gb_fused_masked_nofix, gb_count
 };
 
-// G(output layer, shape, branch, name, ablation-only): the instances of fdnn_gemm.hip a launch can reach
+// G(output layer, shape, branch, name, ablation-only): the instances of fdnn_gemm.hip -- launch_cfg compiles exactly these
+// (92 rows, 23 of them in measurement builds only; with the 64 names below: 156, 34 of them ablation-only)
 #define FDNN_GEMM_LAUNCH_NAMES(G) \
   G(0, tdiv, tap, "gemm.hid.tdiv.tap", 0) \
   G(0, tdiv, prod, "gemm.hid.tdiv.prod", 0) \
@@ -43,11 +44,6 @@ enum GemmBranch {
   G(1, ft64, masked_anyw, "gemm.out.ft64.masked_anyw", 0) \
   G(0, ft128nt128, tap, "gemm.hid.ft128.nt128.tap", 0) \
   G(0, ft128nt128, prod, "gemm.hid.ft128.nt128.prod", 0) \
-  G(1, ft128nt128, tap, "gemm.out.ft128.nt128.tap", 0) \
-  G(1, ft128nt128, plain, "gemm.out.ft128.nt128.plain", 0) \
-  G(1, ft128nt128, anyw, "gemm.out.ft128.nt128.anyw", 0) \
-  G(1, ft128nt128, masked, "gemm.out.ft128.nt128.masked", 0) \
-  G(1, ft128nt128, masked_anyw, "gemm.out.ft128.nt128.masked_anyw", 0) \
   G(0, ft128bk128, prod, "gemm.hid.ft128.bk128.prod", 0) \
   G(1, ft128bk128, plain, "gemm.out.ft128.bk128.plain", 0) \
   G(1, ft128bk128, anyw, "gemm.out.ft128.bk128.anyw", 0) \
@@ -64,21 +60,6 @@ enum GemmBranch {
   G(1, ft128, anyw, "gemm.out.ft128.anyw", 0) \
   G(1, ft128, masked, "gemm.out.ft128.masked", 0) \
   G(1, ft128, masked_anyw, "gemm.out.ft128.masked_anyw", 0) \
-  G(1, ft128, fused, "gemm.out.ft128.fused", 0) \
-  G(1, ft128, fused_masked, "gemm.out.ft128.fused_masked", 0) \
-  G(1, ft128, fused_anyw, "gemm.out.ft128.fused_anyw", 0) \
-  G(1, ft128, fused_masked_anyw, "gemm.out.ft128.fused_masked_anyw", 0) \
-  G(0, ft160, tap, "gemm.hid.ft160.tap", 0) \
-  G(0, ft160, prod, "gemm.hid.ft160.prod", 0) \
-  G(1, ft160, tap, "gemm.out.ft160.tap", 0) \
-  G(1, ft160, plain, "gemm.out.ft160.plain", 0) \
-  G(1, ft160, anyw, "gemm.out.ft160.anyw", 0) \
-  G(1, ft160, masked, "gemm.out.ft160.masked", 0) \
-  G(1, ft160, masked_anyw, "gemm.out.ft160.masked_anyw", 0) \
-  G(1, ft160, fused, "gemm.out.ft160.fused", 0) \
-  G(1, ft160, fused_masked, "gemm.out.ft160.fused_masked", 0) \
-  G(1, ft160, fused_anyw, "gemm.out.ft160.fused_anyw", 0) \
-  G(1, ft160, fused_masked_anyw, "gemm.out.ft160.fused_masked_anyw", 0) \
   G(0, ft256, tap, "gemm.hid.ft256.tap", 0) \
   G(0, ft256, prod, "gemm.hid.ft256.prod", 0) \
   G(0, ft256, prod_nofix, "gemm.hid.ft256.prod_nofix", 0) \
@@ -214,7 +195,7 @@ struct LaunchNameInfo {
   const char *name;
   int flags;
 };
-extern const LaunchNameInfo kLaunchNames[kLaunchNameCount];  // fdnn_runtime.cpp
+extern const LaunchNameInfo kLaunchNames[kLaunchNameCount];  // fdnn_debug.cpp
 extern std::atomic<int> g_launch_note_on;
 extern std::atomic<unsigned long long> g_launch_count[kLaunchNameCount];
 
@@ -229,6 +210,6 @@ inline void note_launch(int id, int id2) {
     g_launch_count[id2].fetch_add(1, std::memory_order_relaxed);
   }
 }
-int gemm_launch_name(bool output, int shape, int branch);  // fdnn_runtime.cpp; kLn_unlisted where the list lacks the combination
+int gemm_launch_name(bool output, int shape, int branch);  // fdnn_debug.cpp; kLn_unlisted where the list lacks the combination
 
 }  // namespace fdnn

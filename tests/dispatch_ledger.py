@@ -6,7 +6,8 @@ which case covers which names:
   * CASES      every case names a net, a batch size, an entry point, the process-wide modes it sets, the names it exists
                for (`must`) and -- in EXPECT -- the exact set of names its recorded span launches;
   * EXCLUDED   names no case launches, each with the reason: ablation-only (the flag in the library's table), or
-               unreachable in the shipped build, with the file and lines that show it.
+               unreachable in the shipped build, with the file and lines that show it.  (156 names: 34 ablation-only,
+               4 excluded, 118 launched by the cases.)
 
 tests/test_dispatch_ledger_host.py (no GPU) asserts  union(EXPECT) | EXCLUDED == the library's table,  so a new launch
 branch without a case fails everywhere; tests/test_gpu_dispatch_ledger.py runs every case with the recorder on and
@@ -441,34 +442,27 @@ EXPECT = {
 }
 
 # Names no case launches.  Ablation-only names (flag 1 in the library's table: the branch needs a -DFDNN_ABLATION build)
-# are excluded by that flag; the names below are unreachable in the shipped build for the reason given.
-# What the arguments share: (a) qgemm_frame_tile (fdnn_gemm.hip:1286-1320) returns 128 either from its first loop (:1298-1299: where
+# are excluded by that flag; the names below are unreachable in the shipped build for the reason given.  The library compiles
+# only the instances its table names (launch_cfg, fdnn_gemm.hip:1140-1163), and what no selection can reach has been deleted;
+# what is left here is the hidden-layer side of the two four-wave 128-frame shapes, which launch_qgemm's `case 128`
+# (fdnn_gemm.hip:1247-1256) keeps as the arms of a 256-node, 128-frame hidden launch -- what a measurement build's forced
+# FDNN_NODE_TILE=256 takes; without them the switch would need an error path.
+# The argument: (a) qgemm_frame_tile (fdnn_gemm.hip:1273-1307) returns 128 either from its first loop (:1285-1286: where
 # rows_pad / 256 * ceil(n / 128) <= 256) or from the cost model below it, and from the cost model only for layers of 129 node
 # tiles or more (33 024 padded rows): tests/test_dispatch_ledger_host.py evaluates frame_tile_model() for every width the loader
 # accepts (fdnn_model.cpp:315, :374: 2^19 output nodes) up to the frame count beyond which the 128-frame tiles' 465 per 512 tiles
 # can no longer undercut 320 per 256 tiles of 320 frames whatever the rounding; (b) hidden layers are at most 32 768 wide
-# (fdnn_model.cpp:346, :374), 128 node tiles.
-_FT128_FUSED = ("fdnn_gemm.hip:1359 (qgemm_fused_ok: the row sums of at most 32 node tiles) and :1255-1268 (launch_qgemm `case 128`): a fused launch has "
-                "rows_pad / 256 <= 32, where frame tile 128 comes only from qgemm_frame_tile's first loop (the cost model yields 128 from 129 node tiles up), "
-                "i.e. with rows_pad / 256 * n_pad / 128 <= 256 and no taps: the 128-byte-step shape (gemm.out.ft128.bk128.*) takes every such launch")
-_FT128_HID = ("fdnn_model.cpp:346 (hidden width <= 32 768 = 128 node tiles) and fdnn_gemm.hip:1298-1320: for such a layer frame tile 128 comes only from "
+# (fdnn_model.cpp:346, :374), 128 node tiles.  (The same statement keeps qgemm_fused_ok's 128-frame clause, fdnn_gemm.hip:1333,
+# from ever refusing a launch: a fused launch has at most 32 node tiles.)
+_FT128_HID = ("fdnn_model.cpp:346 (hidden width <= 32 768 = 128 node tiles) and fdnn_gemm.hip:1285-1306: for such a layer frame tile 128 comes only from "
               "qgemm_frame_tile's first loop, where rows_pad / 256 * ceil(n / 128) <= 256 < rows_pad / 256 * ceil(n / 64) puts rows_pad / 128 * ceil(n / 128) "
-              "in (256, 512] and qgemm_node_tile (:1369-1370, fdnn_runtime.cpp:311-313) answers 128: the 2 x 2-wave shape (gemm.hid.ft128.nt128.*), taps included; "
+              "in (256, 512] and qgemm_node_tile (:1359-1360, fdnn_runtime.cpp:311-313) answers 128: the 2 x 2-wave shape (gemm.hid.ft128.nt128.*), taps included; "
               "the true-divide layers (also frame tile 128) take their own shape")
-_FT160 = ("fdnn_gemm.hip:1306-1319 (qgemm_frame_tile's cost model, the only source of 160; :1269 is the shape's only launch; FDNN_FRAME_TILE is read only in "
-          "-DFDNN_ABLATION builds): ceil(n / 256) <= ceil(n / 160) gives the 256-frame candidate at most as many blocks, hence at most twice the rounds "
-          "(256 slots against 512): cost 256 * rounds256 <= 512 * rounds160 < 160 * 2 / 0.55 * rounds160 = 582 * rounds160 for every layer and batch, "
-          "so 160 is never the minimum")
-_NT128_OUT = "fdnn_gemm.hip:1368 (qgemm_node_tile): `if (output) return 256;` -- the 128 x 128 shape is a hidden-layer shape"
 EXCLUDED = {
-    "unlisted": "fdnn_gemm.hip:1172-1207 (launch_cfg) against fdnn_note.hpp FDNN_GEMM_LAUNCH_NAMES: every branch of the launcher names a listed (shape, branch); "
+    "unlisted": "fdnn_gemm.hip:1140-1198 (launch_cfg) against fdnn_note.hpp FDNN_GEMM_LAUNCH_NAMES: every branch of the launcher names a listed (shape, branch); "
                 "the catch-all counts a launch only if the table and the launcher disagree",
-    **{f"gemm.out.ft128.{b}": _FT128_FUSED for b in ("fused", "fused_masked", "fused_anyw", "fused_masked_anyw")},
     **{f"gemm.hid.ft128.{b}": _FT128_HID for b in ("prod", "tap")},
     "gemm.hid.ft128.bk128.prod": _FT128_HID,
-    **{f"gemm.hid.ft160.{b}": _FT160 for b in ("tap", "prod")},
-    **{f"gemm.out.ft160.{b}": _FT160 for b in ("tap", "plain", "anyw", "masked", "masked_anyw", "fused", "fused_masked", "fused_anyw", "fused_masked_anyw")},
-    **{f"gemm.out.ft128.nt128.{b}": _NT128_OUT for b in ("tap", "plain", "anyw", "masked", "masked_anyw")},
 }
 
 
@@ -502,7 +496,7 @@ def frame_tile_model(mt, n):
     for t in (32, 64, 128):
         ft = np.where((ft == 0) & (mt * (-(-n // t)) <= 256), t, ft)
     best, best_cost = np.full(n.shape, 128, dtype=np.int64), np.full(n.shape, -1.0)
-    for t, slots, eff in ((128, 512, 0.55), (160, 512, 0.55), (256, 256, 1.0), (320, 256, 1.0)):
+    for t, slots, eff in ((128, 512, 0.55), (256, 256, 1.0), (320, 256, 1.0)):
         rounds = -(-(mt * (-(-n // t))) // slots)
         cost = rounds * t * (2.0 if slots == 512 else 1.0) / eff
         take = (best_cost < 0) | (cost < best_cost) | ((cost == best_cost) & (t > best))

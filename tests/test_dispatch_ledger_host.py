@@ -45,19 +45,18 @@ def test_row_sample_of_the_big_net_cases():
 
 
 def test_the_frame_tile_arguments_of_the_exclusions_hold_for_every_layer_the_loader_accepts():
-    """The exclusions of the 160-frame shape and of the hidden / fused forms of the 64-byte-step 128-frame shape rest on two
-    statements about qgemm_frame_tile, restated in dispatch_ledger.frame_tile_model: it never returns 160, and its cost model
-    returns 128 only for layers of 129 node tiles or more.  Every width the loader accepts (2^19 nodes = 2048 node tiles),
-    every frame count up to 392 + 100 345 / mt; beyond that no rounding can help the 128-frame tiles:
-    cost128 >= 465 * mt * n / 65 536 and cost320 <= mt * n / 256 + 1.25 * mt + 320, so 128 can undercut 320 only for
-    n < 392 + 100 345 / mt.  (160 is never returned for any n: the ledger gives the argument; here it is evaluated.)"""
+    """The exclusions of the hidden-layer forms of the four-wave 128-frame shapes rest on a statement about qgemm_frame_tile,
+    restated in dispatch_ledger.frame_tile_model: its cost model returns 128 only for layers of 129 node tiles or more (and
+    nothing but 128, 256 or 320).  Every width the loader accepts (2^19 nodes = 2048 node tiles), every frame count up to
+    392 + 100 345 / mt; beyond that no rounding can help the 128-frame tiles: cost128 >= 465 * mt * n / 65 536 and
+    cost320 <= mt * n / 256 + 1.25 * mt + 320, so 128 can undercut 320 only for n < 392 + 100 345 / mt."""
     import numpy as np
 
     lowest = None
     for mt in range(1, 2049):
         n = np.arange(1, 392 + 100345 // mt + 2)
         ft, from_model = L.frame_tile_model(mt, n)
-        assert not (ft == 160).any(), mt
+        assert np.isin(ft, (32, 64, 128, 256, 320)).all(), mt
         if ((ft == 128) & from_model).any():
             lowest = mt if lowest is None else lowest
             assert mt >= 129, mt
