@@ -16,6 +16,7 @@
 #include "../../include/fdnn.h"
 #include "fdnn_kernels.hpp"
 #include "fdnn_model.hpp"
+#include "fdnn_splice_spec.hpp"  // SpliceSpec, SpliceRef, SpliceSeg, splice_halo
 
 namespace fdnn {
 
@@ -40,15 +41,6 @@ struct DeviceGuard {
     if (ok) hipSetDevice(prev);
   }
 };
-
-// A splice spec (fdnn_model_set_splice): the <Splice> frame offsets and the raw frame width D.  Immutable once made: the
-// model holds the current one, and every raw call, stream and queued server submission holds the one it started with.
-struct SpliceSpec {
-  std::vector<int> offsets;
-  int raw_dim = 0;
-  int left = 0, right = 0;  // max(-o, 0), max(o, 0): the context a row reads before and after its own frame
-};
-using SpliceRef = std::shared_ptr<const SpliceSpec>;
 
 }  // namespace fdnn
 
@@ -232,11 +224,6 @@ inline void unpack_act_rows(const int8_t *src, size_t ld, int n, int H, uint8_t 
 int device_marker_state(int device);
 void set_fuse_override(int mode);
 // ---------------------------------------------------------------- raw feature frames (fdnn_splice.hip)
-// A run of rows of one utterance: rows [row, next segment's row) read raw frames clamp(center + (t - row) + o, lo, hi) of the
-// raw buffer (lo / hi: the buffer indices of the utterance's first and last frame).
-struct SpliceSeg {
-  int row, center, lo, hi;
-};
 // FDNN_E_STATE without a spec, FDNN_E_ARG when raw_dim is not its D (raw_dim < 0: any)
 int splice_check(const SpliceRef &spec, int raw_dim);
 // Room for `frames` raw frames of width raw_dim (c->d_raw) and, on a lean context, the frame buffer c->d_x; allocated on
@@ -246,8 +233,6 @@ int ctx_raw_reserve(fdnn_ctx *c, size_t frames, int raw_dim);
 // ascending by row, the first at or before row0.  Tables longer than one launch's go as several launches.
 void splice_rows(const SpliceSpec &spec, int input_dim, const float *raw, int raw_frames, const std::vector<SpliceSeg> &segs,
                  int row0, int rows, float *d_x, hipStream_t s);
-// The raw frames rows [a, b) of an n-frame utterance reference: [*fa, *fb) (the halo of the offsets, clamped to it).
-void splice_halo(const SpliceSpec &spec, int n, int a, int b, int *fa, int *fb);
 // Rows [a, b) of one n-frame utterance (host raw frames) into out[b - a][O], spliced by `spec`: through the model's batcher
 // when it has one, else the raw frames those rows reference travel once and are spliced and scored chunk by chunk.
 // fdnn_calculate_raw on one device, and a group replica's shard.

@@ -936,11 +936,6 @@ int ctx_raw_reserve(fdnn_ctx *c, size_t frames, int raw_dim) {
   return FDNN_OK;
 }
 
-void splice_halo(const SpliceSpec &spec, int n, int a, int b, int *fa, int *fb) {
-  *fa = std::max(0, a - spec.left);
-  *fb = std::min(n, b + spec.right);
-}
-
 void splice_rows(const SpliceSpec &spec, int input_dim, const float *raw, int raw_frames, const std::vector<SpliceSeg> &segs,
                  int row0, int rows, float *d_x, hipStream_t s) {
   fdnn::SpliceArgs a{};

@@ -33,26 +33,20 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "fdnn_internal.hpp"
+#include "fdnn_server_plan.hpp"
 
 using fdnn::DeviceGuard;
 using fdnn::fail;
+using namespace fdnn::plan;  // Request, Piece, BatchPlan, plan_batch: what a batch contains
 
 namespace {
 
 // below this many frames a batch leaves most CUs idle: run it on its own stream next to others
 constexpr int kSmallBatch = 2560;
-
-struct Piece {  // one caller's rows inside a coalesced batch
-  uint64_t ticket;
-  float *out;      // caller's destination of these rows
-  int row0, rows;  // rows [row0, row0 + rows) of the batch
-  bool last;       // the ticket's final piece
-  int state = 0;   // 0 batch in flight, 1 rows ready in the slot's pinned buffer, 2 being copied out, 3 done
-  const uint64_t *bits = nullptr;  // lazy submissions with bit masks: the caller's words of these rows (compacted return)
-};
 
 struct TicketState {
   int status = 0;      // 0 running, != 0 failed with that fdnn_status
@@ -64,41 +58,41 @@ struct TicketState {
   // that is over -- the packer still reads the caller's frames and the copy threads still write the caller's rows
 };
 
-struct Request {
-  uint64_t ticket;
-  const float *x;
-  const int8_t *masks;  // may be null
-  float *out;
-  int n;
-  int taken = 0;  // frames already packed into earlier batches
-  const uint64_t *bits = nullptr;  // fdnn_server_submit_lazy_bits: [n][ceil(O / 64)] (then masks is null)
-  int most = 0;                    // ... and the largest number of active nodes in any of its rows (counted by the submitter)
-  // raw submissions (then x is null): rows [raw_a, raw_a + n) of the raw_n-frame utterance at `raw`, spliced on the device by
-  // the spec the request was submitted with
-  const float *raw = nullptr;
-  fdnn::SpliceRef spec;
-  int raw_n = 0, raw_a = 0;
-};
-
-// The widest row of a bit-mask request, counted on the submitting thread: the batch's compacted row length follows from it.
-int widest_row(const uint64_t *bits, int n, size_t O) {
-  const size_t wpr = (O + 63) / 64;
-  const uint64_t tail_mask = (O & 63) ? ((uint64_t(1) << (O & 63)) - 1) : ~uint64_t(0);
-  int most = 0;
-  for (int f = 0; f < n; ++f) {
-    const uint64_t *row = bits + size_t(f) * wpr;
-    int k = 0;
-    for (size_t w = 0; w + 1 < wpr; ++w) k += __builtin_popcountll(row[w]);
-    k += __builtin_popcountll(row[wpr - 1] & tail_mask);
-    most = std::max(most, k);
+// One staging buffer of a slot, pinned host memory or device memory: reserve() grows it, the slot's end frees it.
+template <class T, bool kDevice = false>
+struct Buf {
+  T *p = nullptr;
+  size_t count = 0;       // elements
+  bool pageable = false;  // from malloc: pinned memory was refused (reserve(n, true))
+  Buf() = default;
+  Buf(const Buf &) = delete;
+  ~Buf() { release(); }
+  void swap(Buf &o) { std::swap(p, o.p); std::swap(count, o.count); std::swap(pageable, o.pageable); }
+  void release() {
+    if (p && pageable) std::free(p);
+    else if (p && kDevice) hipFree(p);
+    else if (p) hipHostFree(p);
+    p = nullptr;
+    count = 0;
+    pageable = false;
   }
-  return most;
-}
-
-// what a host batch carries: requests of different kinds do not share a batch, except that dense callers may ride in a
-// byte-mask batch (all active)
-enum BatchKind { kDense = 0, kBytes = 1, kBits = 2 };
-inline int kind_of(const Request &r) { return r.bits ? kBits : r.masks ? kBytes : kDense; }
+  // Room for n elements: a buffer that is too small is freed, then allocated anew.  pageable_ok: where pinned memory is
+  // refused, malloc serves (the error is cleared; the copy to the device is then a synchronous one).
+  hipError_t reserve(size_t n, bool pageable_ok = false) {
+    if (n <= count) return hipSuccess;
+    release();
+    hipError_t e = kDevice ? hipMalloc(reinterpret_cast<void **>(&p), sizeof(T) * n)
+                           : hipHostMalloc(reinterpret_cast<void **>(&p), sizeof(T) * n, hipHostMallocDefault);
+    if (e != hipSuccess && pageable_ok) {
+      (void)hipGetLastError();
+      pageable = (p = static_cast<T *>(std::malloc(sizeof(T) * n))) != nullptr;
+      e = p ? hipSuccess : hipErrorOutOfMemory;
+    }
+    if (e != hipSuccess) p = nullptr;
+    count = p ? n : 0;
+    return e;
+  }
+};
 
 struct Slot {
   fdnn_ctx *ctx = nullptr;
@@ -106,32 +100,18 @@ struct Slot {
   hipEvent_t gemm_done = nullptr, tail_done = nullptr, staged = nullptr, done = nullptr;
   uint64_t ticket = 0;            // device submissions: the ticket this slot last carried
   bool used = false;              // `done` has been recorded at least once
-  // host submissions (allocated on first use)
-  float *h_x = nullptr, *d_out = nullptr;
-  float *h_out = nullptr;         // whole-row batches of several callers: the rows' landing area on the host (pinned; ONE transfer
-  size_t h_out_floats = 0;        // per batch at the link's rate instead of one pageable copy per caller), allocated on first use
-  bool rows_on_host = false;      // current batch: its rows have been brought to h_out
-  int8_t *h_mask = nullptr;
-  uint64_t *h_bits = nullptr;     // bit-mask batches: the batch's words (pinned; first such batch allocates)
-  bool h_bits_pageable = false;   // ... from malloc: pinned memory was refused
-  float *d_comp = nullptr;        // ... its compacted result rows [rows][stride]
-  float *h_comp = nullptr;        // ... and where they land on the host (pinned): ONE transfer per batch, behind the compaction
-  size_t comp_floats = 0;
-  int stride = 0;                 // current batch: floats per compacted row (0: the rows leave whole)
-  std::vector<Piece> pieces;
-  // raw batches (one spec per batch): per piece the raw frames it references, staged back to back in h_raw (frames
-  // request), and the batch's segment table (one segment per piece: its own utterance's edges)
-  float *h_raw = nullptr;
-  size_t h_raw_floats = 0;
-  struct RawSrc {
-    int first, count, at;  // frames [first, first + count) of the piece's utterance, at frame `at` of h_raw
-  };
-  std::vector<RawSrc> raw_src;
-  fdnn::SpliceRef spec;
-  std::vector<fdnn::SpliceSeg> segs;
-  int raw_frames = 0;
-  int frames = 0;
-  int pieces_left = 0;            // pieces of the current host batch not copied out yet
+  // host submissions: staging, sized in max_frames units (h_x, h_mask, d_out with the host side, the rest on first use)
+  Buf<float> h_x;
+  Buf<int8_t> h_mask;
+  Buf<float, true> d_out;
+  Buf<float> h_out;               // whole-row batches of several callers: where the rows land on the host, ONE transfer per batch
+  Buf<uint64_t> h_bits;           // bit-mask batches: the batch's words (pageable where pinned memory is refused)
+  Buf<float, true> d_comp;        // ... its compacted result rows [rows][stride]
+  Buf<float> h_comp;              // ... and where they land on the host: ONE transfer per batch, behind the compaction
+  Buf<float> h_raw;               // raw batches: the pieces' raw frames back to back; grows to the largest raw batch
+  BatchPlan batch;                // the current host batch: its pieces, where their frames are staged, how its rows return
+  bool rows_on_host = false;      // its rows have been brought to h_out
+  int pieces_left = 0;            // pieces not copied out yet
   bool in_flight = false;         // host batch enqueued, not yet scattered
 };
 
@@ -159,10 +139,6 @@ struct fdnn_server {
   // the longest stage of the loop; pieces are handed out one by one under qmu (stage_one).
   struct StageJob {
     Slot *sl = nullptr;
-    const std::vector<Request> *taken = nullptr;
-    std::vector<int> row0;
-    int kind = 0;
-    bool any_mask = false;
     int next = 0, done = 0, total = 0;
   } stage;
   bool staging = false;
@@ -180,9 +156,9 @@ int alloc_host_side(fdnn_server *s) {
   const fdnn::BlobHeader &h = s->m->hm.hdr;
   for (Slot &sl : s->slots) {
     const size_t n = size_t(s->max_frames);
-    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&sl.h_x), sizeof(float) * n * h.in_dim, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&sl.h_mask), n * h.out_dim, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&sl.d_out), sizeof(float) * n * h.out_dim);
+    hipError_t e = sl.h_x.reserve(n * h.in_dim);
+    if (e == hipSuccess) e = sl.h_mask.reserve(n * h.out_dim);
+    if (e == hipSuccess) e = sl.d_out.reserve(n * h.out_dim);
     // the slot's context was made lean: the device-side landing buffers of host batches live here
     if (e == hipSuccess && !sl.ctx->d_x) e = hipMalloc(reinterpret_cast<void **>(&sl.ctx->d_x), sizeof(float) * n * h.in_dim);
     if (e == hipSuccess && !sl.ctx->d_mask) e = hipMalloc(reinterpret_cast<void **>(&sl.ctx->d_mask), n * h.out_dim);
@@ -194,10 +170,19 @@ int alloc_host_side(fdnn_server *s) {
 
 // Enqueue one batch that is already on the device.  Large batches: compute on the shared main
 // stream, soft-max scale on the tail stream; small ones: everything on the slot's stream.
-// `after` (may be null) is an event the compute must wait for (the batch's H2D copy);
-// returns with `sl.done` recorded behind the last kernel.
-int enqueue_batch(fdnn_server *s, Slot &sl, const float *d_x, int n, const int8_t *d_masks, float *d_out, hipEvent_t after,
-                  hipStream_t *last_stream, const uint64_t *d_bits = nullptr, float *d_comp = nullptr, int stride = 0) {
+// Returns with *last_stream the stream the batch's last work went to.
+struct BatchCall {
+  const float *d_x = nullptr;
+  int n = 0;
+  const int8_t *d_masks = nullptr;  // one mask or none
+  const uint64_t *d_bits = nullptr;
+  float *d_out = nullptr;
+  hipEvent_t after = nullptr;  // (may be null) an event the compute must wait for: the batch's H2D copy
+  float *d_comp = nullptr;     // bit-mask host batches: the rows compacted, `stride` floats each
+  int stride = 0;
+};
+int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *last_stream) {
+  const int n = b.n;
   fdnn_ctx *c = sl.ctx;
   c->n = n;
   c->last = -1;
@@ -213,18 +198,18 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const float *d_x, int n, const int8_
   }();
   const std::vector<std::pair<int, int>> chunks = small ? std::vector<std::pair<int, int>>{} : fdnn::frame_chunks(n, c->m);
   bool all_fused = !small;
-  for (const auto &ch : chunks) all_fused = all_fused && (d_bits || fdnn::output_will_fuse(c, ch.second, d_masks));  // (a short tail chunk may take the unfused kernels)
+  for (const auto &ch : chunks) all_fused = all_fused && (b.d_bits || fdnn::output_will_fuse(c, ch.second, b.d_masks));  // (a short tail chunk may take the unfused kernels)
   c->l0_chain_only = !small && overlap && !all_fused;  // see fdnn_ctx: an overlapped scale pass needs room beside layer 0
   hipStream_t cs = small ? sl.stream : s->s_main;
-  if (after) HIP_TRY(hipStreamWaitEvent(cs, after, 0));
+  if (b.after) HIP_TRY(hipStreamWaitEvent(cs, b.after, 0));
   fdnn::CtxUse use;  // every way out notes the stream the batch ends on and puts the batch's frame count back
   use.n_after = n;
   HIP_TRY(use.enter(c, cs));
   int rc = FDNN_OK;
   hipStream_t &end = use.s;  // the stream the batch's last work goes to
   if (small) {
-    rc = fdnn::run_hidden(c, d_x, cs, nullptr);
-    if (!rc) rc = fdnn::run_output(c, {.count = n, .d_masks = d_masks, .d_bits = d_bits, .d_out = d_out}, cs);
+    rc = fdnn::run_hidden(c, b.d_x, cs, nullptr);
+    if (!rc) rc = fdnn::run_output(c, {.count = n, .d_masks = b.d_masks, .d_bits = b.d_bits, .d_out = b.d_out}, cs);
   } else {
     // very large batches go chunk by chunk (fdnn::frame_chunks), and the chunks overlap like batches do: chunk j's
     // scale pass runs on the tail stream under chunk j+1's layer 0.  One context serves all chunks, so the compute
@@ -236,11 +221,11 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const float *d_x, int n, const int8_
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
       const auto &ch = chunks[ci];
       c->n = ch.second;
-      rc = fdnn::run_hidden(c, d_x + size_t(ch.first) * D, cs, nullptr);
+      rc = fdnn::run_hidden(c, b.d_x + size_t(ch.first) * D, cs, nullptr);
       if (rc) break;
       if (!first && overlap) HIP_TRY(hipStreamWaitEvent(cs, sl.tail_done, 0));
-      rc = fdnn::run_output(c, {.count = ch.second, .d_masks = d_masks ? d_masks + size_t(ch.first) * O : nullptr,
-                                .d_bits = d_bits ? d_bits + size_t(ch.first) * wpr : nullptr, .d_out = d_out + size_t(ch.first) * O,
+      rc = fdnn::run_output(c, {.count = ch.second, .d_masks = b.d_masks ? b.d_masks + size_t(ch.first) * O : nullptr,
+                                .d_bits = b.d_bits ? b.d_bits + size_t(ch.first) * wpr : nullptr, .d_out = b.d_out + size_t(ch.first) * O,
                                 .tail = overlap ? s->s_tail : nullptr, .gemm_done = overlap ? sl.gemm_done : nullptr}, cs);
       if (rc) break;
       // (without the overlap everything is on the compute stream, in order; a record is 3-4 us of queue time)
@@ -249,24 +234,37 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const float *d_x, int n, const int8_
     }
   }
   // bit-mask host batches: the rows compacted (active probabilities + one value per frame) for the trip over PCIe
-  if (!rc && d_bits && d_comp && stride > 0)
-    fdnn::launch_lazy_compact(d_out, d_bits, d_comp, n, s->m->hm.hdr.out_dim, stride, end);
-  if (rc) return rc;
-  *last_stream = end;
-  return FDNN_OK;
+  if (!rc && b.d_bits && b.d_comp && b.stride > 0)
+    fdnn::launch_lazy_compact(b.d_out, b.d_bits, b.d_comp, n, s->m->hm.hdr.out_dim, b.stride, end);
+  if (!rc) *last_stream = end;
+  return rc;
 }
 
 // A batch carrying `ticket` failed: whatever of that request is still queued will never be packed (the packer would read
 // caller memory that the caller, told of the failure, is free to release).  Call with qmu held.
 void drop_queued_rest(fdnn_server *s, uint64_t ticket) {
-  for (auto it = s->queue.begin(); it != s->queue.end();) {
-    if (it->ticket == ticket)
-      it = s->queue.erase(it);
-    else
-      ++it;
-  }
+  s->queue.erase(std::remove_if(s->queue.begin(), s->queue.end(), [&](const Request &r) { return r.ticket == ticket; }), s->queue.end());
   auto t = s->pending.find(ticket);
   if (t != s->pending.end()) t->second.closed = true;
+}
+
+// The slot's batch is lost (nothing usable was enqueued, or the device failed under it): its tickets fail with `status`,
+// the slot is free again.  Call with qmu held.  Marking the pieces done is safe wherever the batch failed: fdnn_server_wait
+// looks at a slot's pieces only while in_flight, and that is cleared in this same critical section.
+void fail_batch(fdnn_server *s, Slot &sl, int status) {
+  for (Piece &p : sl.batch.pieces) {
+    p.state = 3;
+    auto it = s->pending.find(p.ticket);
+    if (it != s->pending.end()) {
+      it->second.status = status;
+      it->second.failed++;
+      drop_queued_rest(s, p.ticket);
+    }
+  }
+  sl.pieces_left = 0;
+  sl.in_flight = false;
+  s->slot_cv.notify_all();
+  s->done_cv.notify_all();
 }
 
 // Hands rows back to their callers.  The rows of a finished batch sit in the slot's device buffer; whoever gets
@@ -276,34 +274,32 @@ void drop_queued_rest(fdnn_server *s, uint64_t ticket) {
 // dropped around each memcpy.  `only_ticket` = 0 takes any ready piece of the slot.
 void copy_ready_pieces(fdnn_server *s, std::unique_lock<std::mutex> &lk, Slot &sl, uint64_t only_ticket) {
   const size_t O = size_t(s->m->hm.hdr.out_dim);
-  for (size_t i = 0; i < sl.pieces.size(); ++i) {
-    Piece &p = sl.pieces[i];
+  for (size_t i = 0; i < sl.batch.pieces.size(); ++i) {
+    Piece &p = sl.batch.pieces[i];
     if (p.state != 1 || (only_ticket && p.ticket != only_ticket)) continue;
     p.state = 2;
     const Piece job = p;  // the vector is stable while in_flight, but copy what the unlocked part needs anyway
     lk.unlock();
     // straight from the slot's device buffer into the caller's memory, on the copying thread's own stream: no pinned
     // bounce buffer and no second pass over the 32 KB per frame
-    hipError_t ce;
-    const size_t stride = size_t(sl.stride);  // (stable while the slot is in flight)
+    hipError_t ce = hipSuccess;
+    const size_t stride = size_t(sl.batch.stride);  // (stable while the slot is in flight)
     if (job.bits && stride > 0) {
       // lazy rows, compacted: the batch's rows arrived in the slot's pinned buffer with the batch (one transfer, enqueued
       // behind the compaction); THIS thread -- the caller's own, normally, so that sixteen callers work side by side --
       // expands its rows into the caller's block (fdnn::lazy_expand_rows_from)
-      ce = hipSuccess;
-      fdnn::lazy_expand_rows_from(job.out, sl.h_comp + size_t(job.row0) * stride, job.rows, O, stride, job.bits);
+      fdnn::lazy_expand_rows_from(job.out, sl.h_comp.p + size_t(job.row0) * stride, job.rows, O, stride, job.bits);
     } else if (sl.rows_on_host) {
       // whole rows of a coalesced batch: they came to the slot's pinned buffer with the batch; this thread moves its own
-      ce = hipSuccess;
-      std::memcpy(job.out, sl.h_out + size_t(job.row0) * O, sizeof(float) * size_t(job.rows) * O);
+      std::memcpy(job.out, sl.h_out.p + size_t(job.row0) * O, sizeof(float) * size_t(job.rows) * O);
     } else {
       DeviceGuard dg(s->m->device);
-      ce = hipMemcpyAsync(job.out, sl.d_out + size_t(job.row0) * O, sizeof(float) * size_t(job.rows) * O, hipMemcpyDeviceToHost,
+      ce = hipMemcpyAsync(job.out, sl.d_out.p + size_t(job.row0) * O, sizeof(float) * size_t(job.rows) * O, hipMemcpyDeviceToHost,
                           hipStreamPerThread);
       if (ce == hipSuccess) ce = hipStreamSynchronize(hipStreamPerThread);
     }
     lk.lock();
-    sl.pieces[i].state = 3;
+    sl.batch.pieces[i].state = 3;
     auto it = s->pending.find(job.ticket);
     bool finished = false;
     if (it != s->pending.end()) {
@@ -331,265 +327,186 @@ bool stage_one(fdnn_server *s, std::unique_lock<std::mutex> &lk) {
   if (!s->staging || s->stage.next >= s->stage.total) return false;
   const int i = s->stage.next++;
   Slot &sl = *s->stage.sl;
-  const Request r = (*s->stage.taken)[size_t(i)];
-  const int r0 = s->stage.row0[size_t(i)], kind = s->stage.kind;
-  const bool any_mask = s->stage.any_mask;
+  const Request r = sl.batch.taken[size_t(i)];
+  const int r0 = sl.batch.pieces[size_t(i)].row0, kind = sl.batch.kind;
+  const bool any_mask = sl.batch.any_mask;
   lk.unlock();
   const fdnn::BlobHeader &h = s->m->hm.hdr;
   const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64;
   if (r.raw) {
-    const size_t RD = size_t(sl.spec->raw_dim);
-    const Slot::RawSrc src = sl.raw_src[size_t(i)];
-    std::memcpy(sl.h_raw + size_t(src.at) * RD, r.raw + size_t(src.first) * RD, sizeof(float) * size_t(src.count) * RD);
+    const size_t RD = size_t(sl.batch.spec->raw_dim);
+    const RawSrc src = sl.batch.raw_src[size_t(i)];
+    std::memcpy(sl.h_raw.p + size_t(src.at) * RD, r.raw + size_t(src.first) * RD, sizeof(float) * size_t(src.count) * RD);
   } else {
-    std::memcpy(sl.h_x + size_t(r0) * D, r.x + size_t(r.taken) * D, sizeof(float) * size_t(r.n) * D);
+    std::memcpy(sl.h_x.p + size_t(r0) * D, r.x + size_t(r.taken) * D, sizeof(float) * size_t(r.n) * D);
   }
-  if (kind == kBits && sl.h_bits) {  // (only bit-mask requests are in such a batch)
-    std::memcpy(sl.h_bits + size_t(r0) * wpr, r.bits + size_t(r.taken) * wpr, sizeof(uint64_t) * size_t(r.n) * wpr);
+  if (kind == kBits && sl.h_bits.p) {  // (only bit-mask requests are in such a batch)
+    std::memcpy(sl.h_bits.p + size_t(r0) * wpr, r.bits + size_t(r.taken) * wpr, sizeof(uint64_t) * size_t(r.n) * wpr);
   } else if (any_mask) {
     if (r.masks)
-      std::memcpy(sl.h_mask + size_t(r0) * O, r.masks + size_t(r.taken) * O, size_t(r.n) * O);
+      std::memcpy(sl.h_mask.p + size_t(r0) * O, r.masks + size_t(r.taken) * O, size_t(r.n) * O);
     else
-      std::memset(sl.h_mask + size_t(r0) * O, 1, size_t(r.n) * O);  // dense caller inside a lazy batch: all active
+      std::memset(sl.h_mask.p + size_t(r0) * O, 1, size_t(r.n) * O);  // dense caller inside a lazy batch: all active
   }
   lk.lock();
   if (++s->stage.done == s->stage.total) s->stage_cv.notify_all();
   return true;
 }
 
-// Packs queued requests into batches and enqueues them.
-void packer_loop(fdnn_server *s) {
-  DeviceGuard g(s->m->device);
-  const fdnn::BlobHeader &h = s->m->hm.hdr;
-  const size_t D = size_t(h.in_dim), O = size_t(h.out_dim);
-  for (;;) {
-    std::unique_lock<std::mutex> lk(s->qmu);
-    s->qcv.wait(lk, [&] { return s->stop || !s->queue.empty(); });
-    if (s->stop && s->queue.empty()) return;
-    bool gpu_busy = false;  // lingering only pays while an earlier batch keeps the device busy: an idle server launches at once
-    for (const Slot &sl : s->slots) gpu_busy |= sl.in_flight;
-    if (s->linger_us > 0 && !s->stop && gpu_busy) {  // give concurrent callers a moment to join the batch
+// The packer's steps, in packer_loop's order.  Work to pack (false: the loop ends with nothing queued).  Call with qmu held.
+bool wait_for_work(fdnn_server *s, std::unique_lock<std::mutex> &lk) {
+  s->qcv.wait(lk, [&] { return s->stop || !s->queue.empty(); });
+  if (s->stop && s->queue.empty()) return false;
+  // lingering only pays while an earlier batch keeps the device busy: an idle server launches at once
+  const bool gpu_busy = std::any_of(s->slots.begin(), s->slots.end(), [](const Slot &sl) { return sl.in_flight; });
+  if (s->linger_us > 0 && !s->stop && gpu_busy)  // give concurrent callers a moment to join the batch, unless it is full
+    s->qcv.wait_for(lk, std::chrono::microseconds(s->linger_us), [&] {
       size_t have = 0;
       for (const Request &r : s->queue) have += size_t(r.n - r.taken);
-      if (have < size_t(s->max_frames))
-        s->qcv.wait_for(lk, std::chrono::microseconds(s->linger_us), [&] {
-          size_t hv = 0;
-          for (const Request &r : s->queue) hv += size_t(r.n - r.taken);
-          return s->stop || hv >= size_t(s->max_frames);
-        });
-    }
-    // a free slot (its previous host batch scattered)
-    int si = -1;
-    s->slot_cv.wait(lk, [&] {
-      for (int k = 0; k < s->depth; ++k) {
-        const int cand = int((s->host_next_slot + uint64_t(k)) % uint64_t(s->depth));
-        if (!s->slots[size_t(cand)].in_flight) {
-          si = cand;
-          return true;
-        }
-      }
-      return s->stop;
+      return s->stop || have >= size_t(s->max_frames);
     });
+  return true;
+}
+
+// A free slot (its previous host batch scattered), the oldest first; -1: the loop ends.  Call with qmu held.
+int claim_slot(fdnn_server *s, std::unique_lock<std::mutex> &lk) {
+  int si = -1;
+  s->slot_cv.wait(lk, [&] {
+    for (int k = 0; k < s->depth && si < 0; ++k) {
+      const int cand = int((s->host_next_slot + uint64_t(k)) % uint64_t(s->depth));
+      if (!s->slots[size_t(cand)].in_flight) si = cand;
+    }
+    return si >= 0 || s->stop;
+  });
+  return si;
+}
+
+// The next batch becomes the slot's, and its pieces are entered with their tickets.  One hold of qmu for all of it:
+// fdnn_server_wait reads an in-flight slot's pieces.
+void plan_into_slot(fdnn_server *s, Slot &sl) {
+  sl.batch = plan_batch(s->queue, s->max_frames, size_t(s->m->hm.hdr.out_dim));
+  for (const Piece &p : sl.batch.pieces) {
+    auto it = s->pending.find(p.ticket);
+    if (it == s->pending.end()) continue;
+    it->second.created++;
+    if (p.last) it->second.closed = true;
+  }
+  sl.pieces_left = int(sl.batch.pieces.size());
+  sl.in_flight = true;
+}
+
+// The staging buffers this batch needs beyond the slot's fixed ones, each by its own rule.
+hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
+  const size_t O = size_t(s->m->hm.hdr.out_dim), frames = size_t(s->max_frames);
+  BatchPlan &b = sl.batch;
+  // Whole rows of a batch that several callers share (1 GB of pinned memory per slot at most) go to the host in one transfer;
+  // a single caller's batch, or one for which no pinned memory is to be had, leaves by per-caller copies from the device.
+  sl.rows_on_host = b.stride == 0 && b.taken.size() > 1 && frames * O * sizeof(float) <= (size_t(1) << 30) &&
+                    sl.h_out.reserve(frames * O) == hipSuccess;
+  if (b.kind == kBits) {
+    // (advisor, round 5) no pinned memory to be had: pageable staging, the batch is not lost
+    if (sl.h_bits.reserve(frames * ((O + 63) / 64), /*pageable_ok=*/true) != hipSuccess) return hipErrorOutOfMemory;
+    const size_t need = frames * (O * 3 / 4 + 1);
+    if (b.stride > 0 && sl.d_comp.count < need) {
+      // both halves or neither, the old pair kept until the new one stands; a failure is not the batch's: its rows go back whole
+      Buf<float, true> d_new;
+      Buf<float> h_new;
+      if (d_new.reserve(need) == hipSuccess && h_new.reserve(need) == hipSuccess) {
+        sl.d_comp.swap(d_new);
+        sl.h_comp.swap(h_new);
+      } else {
+        (void)hipGetLastError();
+        b.stride = 0;
+      }
+    }
+  }
+  if (!b.raw) return hipSuccess;
+  const hipError_t e = sl.h_raw.reserve(size_t(b.raw_frames) * size_t(b.spec->raw_dim));
+  if (e == hipSuccess && fdnn::ctx_raw_reserve(sl.ctx, size_t(b.raw_frames), b.spec->raw_dim)) return hipErrorOutOfMemory;
+  return e;
+}
+
+// The pieces' frames and masks into the slot's pinned buffers: this thread and whoever is blocked in fdnn_server_wait,
+// piece by piece (stage_one).
+void stage_batch(fdnn_server *s, Slot &sl) {
+  std::unique_lock<std::mutex> lk(s->qmu);
+  s->stage.sl = &sl;
+  s->stage.next = s->stage.done = 0;
+  s->stage.total = int(sl.batch.taken.size());
+  s->staging = true;
+  if (s->stage.total > 1) s->done_cv.notify_all();
+  while (stage_one(s, lk)) continue;
+  s->stage_cv.wait(lk, [&] { return s->stage.done == s->stage.total; });
+  s->staging = false;
+}
+
+// Copy in, compute, copy back -- all asynchronous, in launch order against device submissions (s->mu).  *rc: what
+// enqueue_batch said; the rows leave the slot later, piece by piece (copy_ready_pieces).
+hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
+  const fdnn::BlobHeader &h = s->m->hm.hdr;
+  const BatchPlan &b = sl.batch;
+  const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64, rows = size_t(b.rows);
+  std::lock_guard<std::mutex> order(s->mu);
+  fdnn_ctx *c = sl.ctx;
+  const bool bits = b.kind == kBits;
+  hipError_t e;
+  if (b.raw) {  // only the raw frames cross PCIe; the rows are spliced on the device, each piece within its utterance
+    const size_t raw_floats = size_t(b.raw_frames) * size_t(b.spec->raw_dim);
+    e = hipMemcpyAsync(c->d_raw, sl.h_raw.p, sizeof(float) * raw_floats, hipMemcpyHostToDevice, sl.stream);
+    if (e == hipSuccess) fdnn::splice_rows(*b.spec, int(D), c->d_raw, b.raw_frames, b.segs, 0, b.rows, c->d_x, sl.stream);
+  } else {
+    e = hipMemcpyAsync(c->d_x, sl.h_x.p, sizeof(float) * rows * D, hipMemcpyHostToDevice, sl.stream);
+  }
+  if (e == hipSuccess && bits)
+    e = hipMemcpyAsync(c->d_mask_bits, sl.h_bits.p, sizeof(uint64_t) * rows * wpr, hipMemcpyHostToDevice, sl.stream);
+  else if (e == hipSuccess && b.any_mask)
+    e = hipMemcpyAsync(c->d_mask, sl.h_mask.p, rows * O, hipMemcpyHostToDevice, sl.stream);
+  if (e == hipSuccess) e = hipEventRecord(sl.staged, sl.stream);
+  if (e != hipSuccess) return e;
+  hipStream_t last = sl.stream;
+  *rc = enqueue_batch(s, sl, {.d_x = c->d_x, .n = b.rows, .d_masks = !bits && b.any_mask ? c->d_mask : nullptr,
+                              .d_bits = bits ? c->d_mask_bits : nullptr, .d_out = sl.d_out.p, .after = sl.staged,
+                              .d_comp = sl.d_comp.p, .stride = b.stride}, &last);
+  if (*rc) return hipSuccess;
+  if (last != sl.stream) {  // results leave on the slot's stream, behind the tail stream's scale pass
+    e = hipEventRecord(sl.gemm_done, last);  // (gemm_done is free again: the scale pass already waits on its earlier record)
+    if (e == hipSuccess) e = hipStreamWaitEvent(sl.stream, sl.gemm_done, 0);
+  }
+  if (e == hipSuccess && bits && b.stride > 0)  // compacted rows: to the host with the batch
+    e = hipMemcpyAsync(sl.h_comp.p, sl.d_comp.p, sizeof(float) * rows * size_t(b.stride), hipMemcpyDeviceToHost, sl.stream);
+  else if (e == hipSuccess && sl.rows_on_host)
+    e = hipMemcpyAsync(sl.h_out.p, sl.d_out.p, sizeof(float) * rows * O, hipMemcpyDeviceToHost, sl.stream);
+  if (e == hipSuccess) e = hipEventRecord(sl.done, sl.stream);
+  return e;
+}
+
+// Packs queued requests into batches and enqueues them: wait, claim a slot, plan, reserve, stage, launch, account.
+void packer_loop(fdnn_server *s) {
+  DeviceGuard g(s->m->device);
+  for (;;) {
+    std::unique_lock<std::mutex> lk(s->qmu);
+    if (!wait_for_work(s, lk)) return;
+    const int si = claim_slot(s, lk);
     if (si < 0) return;
     Slot &sl = s->slots[size_t(si)];
-    // take requests, whole or in part, until the batch is full
-    std::vector<Request> taken;
-    sl.pieces.clear();
-    int rows = 0, most = 0;
-    bool any_mask = false;
-    const size_t wpr = (O + 63) / 64;
-    // a batch carries bit-mask requests only, or none (dense and byte-mask callers share batches as before: the dense rows
-    // of such a batch get all-active masks); a request of the other sort waits for the next batch
-    int kind = kDense;
-    bool raw = false;  // a batch carries raw-frame requests only, or none
-    sl.raw_src.clear();
-    sl.segs.clear();
-    int raw_frames = 0;
-    while (!s->queue.empty() && rows < s->max_frames) {
-      Request &r = s->queue.front();
-      const int rk = kind_of(r);
-      if (rows == 0) {
-        kind = rk;
-        raw = r.raw != nullptr;
-        sl.spec = r.spec;
-      } else if ((rk == kBits) != (kind == kBits) || (r.raw != nullptr) != raw || r.spec != sl.spec)
-        break;
-      else if (rk == kBytes)
-        kind = kBytes;
-      most = std::max(most, r.most);
-      const int take = std::min(r.n - r.taken, s->max_frames - rows);
-      Request part = r;
-      part.taken = r.taken;
-      part.n = take;  // rows of this request in THIS batch
-      taken.push_back(part);
-      any_mask |= r.masks != nullptr;
-      r.taken += take;
-      const bool last = r.taken == r.n;
-      sl.pieces.push_back(Piece{r.ticket, r.out + size_t(part.taken) * O, rows, take, last, 0, r.bits ? r.bits + size_t(part.taken) * wpr : nullptr});
-      {
-        auto it = s->pending.find(r.ticket);
-        if (it != s->pending.end()) {
-          it->second.created++;
-          if (last) it->second.closed = true;
-        }
-      }
-      if (raw) {  // the raw frames this piece's rows reference, and where they are staged
-        const int u0 = r.raw_a + part.taken;  // the piece's first row as a frame of its utterance
-        int fa, fb;
-        fdnn::splice_halo(*r.spec, r.raw_n, u0, u0 + take, &fa, &fb);
-        sl.raw_src.push_back(Slot::RawSrc{fa, fb - fa, raw_frames});
-        sl.segs.push_back(fdnn::SpliceSeg{rows, raw_frames + u0 - fa, raw_frames - fa, raw_frames + r.raw_n - 1 - fa});
-        raw_frames += fb - fa;
-      }
-      rows += take;
-      if (last) s->queue.pop_front();
-    }
-    sl.frames = rows;
-    sl.raw_frames = raw_frames;
-    // compacted return (bit-mask batches): worth it while a row is at most 3/4 active nodes
-    const size_t stride = size_t(most) + 1;
-    sl.stride = kind == kBits && stride * 4 <= O * 3 ? int(stride) : 0;
-    sl.pieces_left = int(sl.pieces.size());
-    sl.in_flight = true;
+    plan_into_slot(s, sl);
     s->host_next_slot = uint64_t(si) + 1;
     lk.unlock();
-
-    // stage (pinned), copy, compute, copy back -- all asynchronous from here
-    hipError_t e = hipSuccess;
-    // Whole rows of a batch that several callers share (and that is not too large to pin: 1 GB of pinned memory per slot at
-    // most) go to the host in one transfer; a single caller's batch is copied by that caller straight into its memory.
-    const bool compacted = kind == kBits && sl.stride > 0;
-    sl.rows_on_host = false;
-    if (!compacted && taken.size() > 1 && size_t(s->max_frames) * O * sizeof(float) <= (size_t(1) << 30)) {
-      const size_t need = size_t(s->max_frames) * O;
-      if (sl.h_out_floats < need) {
-        e = hipHostMalloc(reinterpret_cast<void **>(&sl.h_out), sizeof(float) * need, hipHostMallocDefault);
-        if (e == hipSuccess) sl.h_out_floats = need;
-      }
-      sl.rows_on_host = e == hipSuccess;
-      e = hipSuccess;  // (no pinned memory to be had: the per-caller copies as before)
-    }
-    if (kind == kBits) {  // staging of the first bit-mask batch of this slot
-      if (!sl.h_bits) {
-        const size_t bytes = sizeof(uint64_t) * size_t(s->max_frames) * wpr;
-        if (hipHostMalloc(reinterpret_cast<void **>(&sl.h_bits), bytes, hipHostMallocDefault) != hipSuccess) {
-          // (advisor, round 5) no pinned memory to be had: pageable staging -- the copy to the device is then a synchronous
-          // one, the batch is not lost
-          (void)hipGetLastError();
-          sl.h_bits = static_cast<uint64_t *>(std::malloc(bytes));
-          sl.h_bits_pageable = sl.h_bits != nullptr;
-          if (!sl.h_bits) e = hipErrorOutOfMemory;
-        }
-      }
-      const size_t need = size_t(s->max_frames) * (O * 3 / 4 + 1);
-      if (e == hipSuccess && sl.stride > 0 && sl.comp_floats < need) {
-        // both halves or neither: a device buffer without its pinned landing place was leaked by the next batch's attempt,
-        // and a failure here is not the batch's -- its rows go back uncompacted (per-caller copies)
-        float *d_new = nullptr, *h_new = nullptr;
-        hipError_t ec = hipMalloc(reinterpret_cast<void **>(&d_new), sizeof(float) * need);
-        if (ec == hipSuccess) ec = hipHostMalloc(reinterpret_cast<void **>(&h_new), sizeof(float) * need, hipHostMallocDefault);
-        if (ec == hipSuccess) {
-          if (sl.d_comp) hipFree(sl.d_comp);
-          if (sl.h_comp) hipHostFree(sl.h_comp);
-          sl.d_comp = d_new;
-          sl.h_comp = h_new;
-          sl.comp_floats = need;
-        } else {
-          (void)hipGetLastError();
-          if (d_new) hipFree(d_new);
-          sl.stride = 0;
-        }
-      }
-    }
-    const size_t raw_floats = raw ? size_t(raw_frames) * size_t(sl.spec->raw_dim) : 0;
-    if (e == hipSuccess && raw && sl.h_raw_floats < raw_floats) {  // raw staging: grows to the largest raw batch
-      if (sl.h_raw) hipHostFree(sl.h_raw);
-      sl.h_raw = nullptr;
-      sl.h_raw_floats = 0;
-      e = hipHostMalloc(reinterpret_cast<void **>(&sl.h_raw), sizeof(float) * raw_floats, hipHostMallocDefault);
-      if (e == hipSuccess) sl.h_raw_floats = raw_floats;
-    }
-    if (e == hipSuccess && raw && fdnn::ctx_raw_reserve(sl.ctx, size_t(raw_frames), sl.spec->raw_dim)) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) {  // the pieces' copies: this thread and whoever is blocked in fdnn_server_wait, piece by piece
-      lk.lock();
-      s->stage.sl = &sl;
-      s->stage.taken = &taken;
-      s->stage.row0.clear();
-      int r0 = 0;
-      for (const Request &r : taken) {
-        s->stage.row0.push_back(r0);
-        r0 += r.n;
-      }
-      s->stage.kind = kind;
-      s->stage.any_mask = any_mask;
-      s->stage.next = s->stage.done = 0;
-      s->stage.total = int(taken.size());
-      s->staging = true;
-      if (taken.size() > 1) s->done_cv.notify_all();
-      while (stage_one(s, lk)) {
-      }
-      s->stage_cv.wait(lk, [&] { return s->stage.done == s->stage.total; });
-      s->staging = false;
-      lk.unlock();
-    }
     int rc = FDNN_OK;
+    hipError_t e = reserve_buffers(s, sl);
     if (e == hipSuccess) {
-      std::lock_guard<std::mutex> order(s->mu);  // launch order against device submissions
-      fdnn_ctx *c = sl.ctx;
-      const bool bits = kind == kBits;
-      if (raw) {  // only the raw frames cross PCIe; the rows are spliced on the device, each piece within its utterance
-        e = hipMemcpyAsync(c->d_raw, sl.h_raw, sizeof(float) * size_t(sl.raw_frames) * size_t(sl.spec->raw_dim), hipMemcpyHostToDevice,
-                           sl.stream);
-        if (e == hipSuccess) fdnn::splice_rows(*sl.spec, int(D), c->d_raw, sl.raw_frames, sl.segs, 0, rows, c->d_x, sl.stream);
-      } else {
-        e = hipMemcpyAsync(c->d_x, sl.h_x, sizeof(float) * size_t(rows) * D, hipMemcpyHostToDevice, sl.stream);
-      }
-      if (e == hipSuccess && bits)
-        e = hipMemcpyAsync(c->d_mask_bits, sl.h_bits, sizeof(uint64_t) * size_t(rows) * wpr, hipMemcpyHostToDevice, sl.stream);
-      else if (e == hipSuccess && any_mask)
-        e = hipMemcpyAsync(c->d_mask, sl.h_mask, size_t(rows) * O, hipMemcpyHostToDevice, sl.stream);
-      if (e == hipSuccess) e = hipEventRecord(sl.staged, sl.stream);
-      hipStream_t last = sl.stream;
-      if (e == hipSuccess)
-        rc = enqueue_batch(s, sl, c->d_x, rows, !bits && any_mask ? c->d_mask : nullptr, sl.d_out, sl.staged, &last, bits ? c->d_mask_bits : nullptr,
-                           sl.d_comp, sl.stride);
-      if (e == hipSuccess && !rc) {
-        if (last != sl.stream) {  // results leave on the slot's stream, behind the tail stream's scale pass
-          e = hipEventRecord(sl.gemm_done, last);  // (gemm_done is free again: the scale pass already waits on its earlier record)
-          if (e == hipSuccess) e = hipStreamWaitEvent(sl.stream, sl.gemm_done, 0);
-        }
-        if (e == hipSuccess && bits && sl.stride > 0)  // compacted rows: to the host with the batch
-          e = hipMemcpyAsync(sl.h_comp, sl.d_comp, sizeof(float) * size_t(rows) * size_t(sl.stride), hipMemcpyDeviceToHost, sl.stream);
-        else if (e == hipSuccess && sl.rows_on_host)
-          e = hipMemcpyAsync(sl.h_out, sl.d_out, sizeof(float) * size_t(rows) * O, hipMemcpyDeviceToHost, sl.stream);
-        if (e == hipSuccess) e = hipEventRecord(sl.done, sl.stream);  // the rows leave later, piece by piece (copy_ready_pieces)
-      }
+      stage_batch(s, sl);
+      e = launch_batch(s, sl, &rc);
     }
     if (e != hipSuccess) rc = fail(FDNN_E_DEVICE, std::string("server batch: ") + hipGetErrorString(e));
     s->n_batches++;
-    s->n_frames += uint64_t(rows);
-    if (taken.size() > 1) s->n_coalesced += taken.size();
-    {
-      std::lock_guard<std::mutex> lk2(s->qmu);
-      if (rc) {  // nothing usable was enqueued: fail the tickets, free the slot
-        sl.in_flight = false;
-        sl.pieces_left = 0;
-        for (const Piece &p : sl.pieces) {
-          auto it = s->pending.find(p.ticket);
-          if (it != s->pending.end()) {
-            it->second.status = rc;
-            it->second.failed++;
-            drop_queued_rest(s, p.ticket);
-          }
-        }
-      } else {
-        s->flying.push_back(si);
-      }
-    }
+    s->n_frames += uint64_t(sl.batch.rows);
+    if (sl.batch.taken.size() > 1) s->n_coalesced += sl.batch.taken.size();
+    lk.lock();
     if (rc) {
-      s->done_cv.notify_all();
-      s->slot_cv.notify_all();
+      fail_batch(s, sl, rc);
     } else {
+      s->flying.push_back(si);
       s->qcv.notify_all();  // wakes the finisher
     }
   }
@@ -605,33 +522,18 @@ void finisher_loop(fdnn_server *s) {
       // (the finisher outlives the packer: at shutdown the packer still drains the queue, and a batch it enqueues after the
       // finisher had gone would never be marked ready or scattered)
       s->qcv.wait(lk, [&] { return (s->stop && s->packer_done) || !s->flying.empty(); });
-      if (s->flying.empty()) {
-        if (s->stop && s->packer_done) return;
-        continue;
-      }
+      if (s->flying.empty()) return;  // stopped, and the packer has gone
       si = s->flying.front();
       s->flying.pop_front();
     }
     Slot &sl = s->slots[size_t(si)];
     const hipError_t e = hipEventSynchronize(sl.done);
     std::unique_lock<std::mutex> lk(s->qmu);
-    if (e != hipSuccess) {  // the batch is lost: fail its tickets, free the slot
-      for (Piece &p : sl.pieces) {
-        p.state = 3;
-        auto it = s->pending.find(p.ticket);
-        if (it != s->pending.end()) {
-          it->second.status = FDNN_E_DEVICE;
-          it->second.failed++;
-          drop_queued_rest(s, p.ticket);
-        }
-      }
-      sl.pieces_left = 0;
-      sl.in_flight = false;
-      s->slot_cv.notify_all();
-      s->done_cv.notify_all();
+    if (e != hipSuccess) {
+      fail_batch(s, sl, FDNN_E_DEVICE);
       continue;
     }
-    for (Piece &p : sl.pieces) p.state = 1;
+    for (Piece &p : sl.batch.pieces) p.state = 1;
     s->done_cv.notify_all();             // callers blocked in wait() copy their own rows ...
     copy_ready_pieces(s, lk, sl, 0);     // ... and this thread takes whatever nobody has claimed
   }
@@ -648,6 +550,25 @@ int start_host_side(fdnn_server *s) {
   return FDNN_OK;
 }
 
+// The common end of the host submit entry points: a ticket for the request, and the request into the packer's queue.
+int submit_host(fdnn_server *s, Request r, uint64_t *ticket) {
+  const int rc = start_host_side(s);
+  if (rc) return rc;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    r.ticket = s->next_ticket++;
+  }
+  {
+    std::lock_guard<std::mutex> lk(s->qmu);
+    s->pending.emplace(r.ticket, TicketState{});
+    s->queue.push_back(r);
+  }
+  s->n_requests++;
+  s->qcv.notify_all();
+  *ticket = r.ticket;
+  return FDNN_OK;
+}
+
 }  // namespace
 
 namespace fdnn {
@@ -658,30 +579,9 @@ int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *r
   if (rc) return rc;
   if (n <= 0 || a < 0 || b > n || b <= a) return fail(FDNN_E_ARG, "frame count must be positive");
   if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
-  rc = start_host_side(s);
-  if (rc) return rc;
   const int most = bits ? widest_row(bits, b - a, size_t(s->m->hm.hdr.out_dim)) : 0;
-  uint64_t t;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    t = s->next_ticket++;
-  }
-  {
-    std::lock_guard<std::mutex> lk(s->qmu);
-    s->pending.emplace(t, TicketState{});
-    Request r{t, nullptr, nullptr, out, b - a, 0};
-    r.bits = bits;
-    r.most = most;
-    r.raw = raw;
-    r.spec = spec;
-    r.raw_n = n;
-    r.raw_a = a;
-    s->queue.push_back(r);
-  }
-  s->n_requests++;
-  s->qcv.notify_all();
-  *ticket = t;
-  return FDNN_OK;
+  return submit_host(s, Request{.out = out, .n = b - a, .bits = bits, .most = most, .raw = raw, .spec = spec, .raw_n = n, .raw_a = a},
+                     ticket);
 }
 
 }  // namespace fdnn
@@ -698,7 +598,7 @@ int fdnn_server_create(fdnn_model *m, int max_frames, int depth, fdnn_server **o
   s->m = m;
   s->max_frames = max_frames;
   s->depth = depth;
-  s->slots.resize(size_t(depth));
+  s->slots = std::vector<Slot>(size_t(depth));
   // the compute stream outranks the tail stream: when layer 0 of batch i+1 and the scale pass of
   // batch i are both runnable, the dispatcher must place layer 0's big workgroups first
   int prio_least = 0, prio_greatest = 0;
@@ -756,24 +656,13 @@ void fdnn_server_free(fdnn_server *s) {
   if (s->s_tail) hipStreamSynchronize(s->s_tail);
   for (Slot &sl : s->slots) {
     if (sl.ctx) fdnn::destroy_ctx(sl.ctx);
-    if (sl.h_x) hipHostFree(sl.h_x);
-    if (sl.h_mask) hipHostFree(sl.h_mask);
-    if (sl.h_raw) hipHostFree(sl.h_raw);
-    if (sl.h_bits && sl.h_bits_pageable) std::free(sl.h_bits);
-    else if (sl.h_bits) hipHostFree(sl.h_bits);
-    if (sl.d_comp) hipFree(sl.d_comp);
-    if (sl.h_comp) hipHostFree(sl.h_comp);
-    if (sl.h_out) hipHostFree(sl.h_out);
-    if (sl.d_out) hipFree(sl.d_out);
-    if (sl.gemm_done) hipEventDestroy(sl.gemm_done);
-    if (sl.tail_done) hipEventDestroy(sl.tail_done);
-    if (sl.staged) hipEventDestroy(sl.staged);
-    if (sl.done) hipEventDestroy(sl.done);
+    for (hipEvent_t ev : {sl.gemm_done, sl.tail_done, sl.staged, sl.done})
+      if (ev) hipEventDestroy(ev);
     if (sl.stream) hipStreamDestroy(sl.stream);
   }
   if (s->s_main) hipStreamDestroy(s->s_main);
   if (s->s_tail) hipStreamDestroy(s->s_tail);
-  delete s;
+  delete s;  // (with the slots' staging buffers)
 }
 
 int fdnn_server_set_linger_us(fdnn_server *s, int microseconds) {
@@ -813,7 +702,7 @@ int fdnn_server_submit_device(fdnn_server *s, const float *d_x, int n, const int
   Slot &sl = s->slots[size_t(si)];
   if (sl.used) HIP_TRY(hipEventSynchronize(sl.done));
   hipStream_t last = nullptr;
-  int rc = enqueue_batch(s, sl, d_x, n, d_masks, d_out, nullptr, &last);
+  int rc = enqueue_batch(s, sl, {.d_x = d_x, .n = n, .d_masks = d_masks, .d_out = d_out}, &last);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(sl.done, last));
   sl.used = true;
@@ -830,48 +719,15 @@ int fdnn_server_submit(fdnn_server *s, const float *x, int n, const int8_t *mask
   if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
   if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
   if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
-  int rc = start_host_side(s);
-  if (rc) return rc;
-  uint64_t t;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    t = s->next_ticket++;
-  }
-  {
-    std::lock_guard<std::mutex> lk(s->qmu);
-    s->pending.emplace(t, TicketState{});
-    s->queue.push_back(Request{t, x, masks, out, n, 0});
-  }
-  s->n_requests++;
-  s->qcv.notify_all();
-  *ticket = t;
-  return FDNN_OK;
+  return submit_host(s, Request{.x = x, .masks = masks, .out = out, .n = n}, ticket);
 }
 
 int fdnn_server_submit_lazy_bits(fdnn_server *s, const float *x, int n, const uint64_t *bits, float *out, uint64_t *ticket) {
   if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
   if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
   if (!x || !out || !bits) return fail(FDNN_E_ARG, "null buffer");
-  int rc = start_host_side(s);
-  if (rc) return rc;
   const int most = widest_row(bits, n, size_t(s->m->hm.hdr.out_dim));
-  uint64_t t;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    t = s->next_ticket++;
-  }
-  {
-    std::lock_guard<std::mutex> lk(s->qmu);
-    s->pending.emplace(t, TicketState{});
-    Request r{t, x, nullptr, out, n, 0};
-    r.bits = bits;
-    r.most = most;
-    s->queue.push_back(r);
-  }
-  s->n_requests++;
-  s->qcv.notify_all();
-  *ticket = t;
-  return FDNN_OK;
+  return submit_host(s, Request{.x = x, .out = out, .n = n, .bits = bits, .most = most}, ticket);
 }
 
 int fdnn_server_submit_raw(fdnn_server *s, const float *raw, int n, const uint64_t *bits, float *out, uint64_t *ticket) {
@@ -895,7 +751,7 @@ int fdnn_server_wait(fdnn_server *s, uint64_t ticket) {
         bool copied = false;
         for (Slot &sl : s->slots) {
           if (!sl.in_flight) continue;
-          for (const Piece &p : sl.pieces)
+          for (const Piece &p : sl.batch.pieces)
             if (p.ticket == ticket && p.state == 1) {
               copy_ready_pieces(s, lk, sl, ticket);
               copied = true;

@@ -11,6 +11,16 @@ from oracle.oracle import Oracle
 
 pytestmark = pytest.mark.gpu
 TIGHT = 2e-6
+LEAK_BOUND = 64 << 20  # device memory that may stay away after create / free (allocator slack)
+
+
+def device_memory_free():
+    """hipMemGetInfo through torch, with torch's own cache emptied."""
+    import torch
+
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    return torch.cuda.mem_get_info()[0]
 
 
 @pytest.mark.parametrize("depth", [1, 2, 4])
@@ -272,15 +282,11 @@ def test_create_and_free_cycles_return_device_memory(mid_model_path):
 
     for _ in range(3):
         cycle()  # pools, caches and the allocator's own slack settle
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    free0, _total = torch.cuda.mem_get_info()
+    free0 = device_memory_free()
     for _ in range(25):
         cycle()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    free1, _total = torch.cuda.mem_get_info()
-    assert free0 - free1 < 64 << 20, f"{(free0 - free1) >> 20} MiB of device memory did not come back after 25 create/free cycles"
+    free1 = device_memory_free()
+    assert free0 - free1 < LEAK_BOUND, f"{(free0 - free1) >> 20} MiB of device memory did not come back after 25 create/free cycles"
 
 
 def test_lazy_bit_mask_submissions_are_coalesced_and_come_back_compacted(mid_model_path):
@@ -402,4 +408,56 @@ def test_lazy_loop_on_the_full_net_with_large_coalesced_batches(net_model_path):
     assert st["coalesced_requests"] > 0 and st["frames"] == 3 * sum(lens)
     assert dnn.fuseGiveups() == 0
     srv.close()
+    dnn.delete()
+
+
+def test_four_kinds_of_submission_share_one_loop(mid_model_path):
+    """One caller thread per kind of host submission -- dense (100 frames: split over two 96-frame batches), byte-masked,
+    bit-masked (130 frames, compacted return) and raw frames with bits -- behind a barrier, three rounds each, on a small
+    loop that lingers: whatever the packer puts together, every result equals the direct call's bit for bit, and closing
+    the loop gives its device memory back (the measure of test_create_and_free_cycles_return_device_memory)."""
+    dnn = api.QuantizedDnn.loadFromFile(mid_model_path)
+    dnn.setSplice(list(range(-5, 6)), 39)
+    O = dnn.outputDimension()
+    xs = [F.synth_features(n, 432, seed=610 + i) for i, n in enumerate((100, 50, 130))]
+    masks = F.generate_masks(50, O, 0.4, 0.03, seed=31)
+    bits = F.pack_mask_bits(F.generate_masks(130, O, 0.4, 0.03, seed=32))
+    raw = np.random.default_rng(613).standard_normal((70, 39)).astype(np.float32) * 3
+    raw_bits = F.pack_mask_bits(F.generate_masks(70, O, 0.4, 0.03, seed=33))
+    ctx = dnn.getNewLazyContext(50)
+    ctx.calculateUntilOutput(xs[1])
+    want = [dnn.calculate(xs[0]), ctx.calculateForOutputNodesBatch(masks), dnn.calculateLazy(xs[2], bits=bits),
+            dnn.calculateLazyRaw(raw, raw_bits)]
+    ctx.delete()
+    free0 = device_memory_free()
+    srv = api.ScoringServer(dnn, max_frames=96, depth=2, linger_us=2000)
+    submit = [lambda: srv.submit(xs[0]), lambda: srv.submit(xs[1], masks), lambda: srv.submitLazy(xs[2], bits),
+              lambda: srv.submitRaw(raw, bits=raw_bits)]
+    barrier = threading.Barrier(len(submit))
+    got, errors = [[] for _ in submit], []
+
+    def caller(k):
+        try:
+            barrier.wait()
+            for _ in range(3):
+                t, out = submit[k]()
+                srv.wait(t)
+                got[k].append(out)
+        except Exception as e:  # noqa: BLE001
+            errors.append(e)
+
+    th = [threading.Thread(target=caller, args=(k,)) for k in range(len(submit))]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert not errors, errors
+    for k, outs in enumerate(got):
+        assert len(outs) == 3
+        for out in outs:
+            assert np.array_equal(out, want[k]), k
+    assert srv.stats()["requests"] == 12
+    srv.close()
+    free1 = device_memory_free()
+    assert free0 - free1 < LEAK_BOUND, f"{(free0 - free1) >> 20} MiB of device memory did not come back when the loop closed"
     dnn.delete()
