@@ -554,28 +554,24 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
 }
 
 template <int NF, int WN, int BK, int STAGES, int WM = 4>
-void launch_chain_cfg(const QChainParams &p, hipStream_t s) {
+void launch_chain_cfg(const QChainParams &p, int n_cu, hipStream_t s) {
   using Cfg = GemmCfg<NF, WN, BK, STAGES, WM>;
   constexpr int kLds = Cfg::LDS + 64;
   static_assert(kLds <= 160 * 1024, "LDS");
   auto k = qchain_kernel<NF, WN, BK, STAGES, WM>;
   auto k_nofix = qchain_kernel<NF, WN, BK, STAGES, WM, true>;
   static std::atomic<unsigned long long> attr_set{0};
-  static std::atomic<int> cus[64];
   int dev = 0;
   (void)hipGetDevice(&dev);
   const unsigned long long dev_bit = 1ull << (dev & 63);
   if (!(attr_set.load(std::memory_order_acquire) & dev_bit)) {
     hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     hipFuncSetAttribute(reinterpret_cast<const void *>(k_nofix), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    int n_cu = 256;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    cus[dev & 63].store(n_cu, std::memory_order_relaxed);
     attr_set.fetch_or(dev_bit, std::memory_order_release);
   }
   const int per_cu = (160 * 1024) / kLds >= 2 && Cfg::THREADS <= 256 ? 2 : 1;
   const long tiles = static_cast<long>(p.rows_pad / Cfg::G_BM) * (p.n_pad / Cfg::FT);
-  const int grid = static_cast<int>(std::min<long>(tiles, static_cast<long>(cus[dev & 63].load(std::memory_order_relaxed)) * per_cu));
+  const int grid = static_cast<int>(std::min<long>(tiles, static_cast<long>(n_cu) * per_cu));
   bool any_fix = false;
   for (int i = 0; i < p.n_layers; ++i) any_fix = any_fix || p.layer[i].fix_ent != nullptr;
   note_launch(NF == 4 ? (any_fix ? kLn_chain_ft256_fix : kLn_chain_ft256_nofix) : (any_fix ? kLn_chain_ft320_fix : kLn_chain_ft320_nofix));
@@ -584,61 +580,11 @@ void launch_chain_cfg(const QChainParams &p, hipStream_t s) {
 
 }  // namespace
 
-int qchain_frame_tile(int rows_pad, int n);
-static std::atomic<int> g_chain_mode{-1}, g_chain_min{0};
-void qchain_set_mode(int mode, int min_frames) {
-  g_chain_mode.store(mode, std::memory_order_relaxed);
-  g_chain_min.store(min_frames, std::memory_order_relaxed);
-}
-
-bool qchain_ok(int rows_pad, int K, int n, int n_layers) {
-  static const int env_mode = [] {
-    const char *e = std::getenv("FDNN_CHAIN");
-    return e ? std::atoi(e) : -1;
-  }();
-  static const int env_min = [] {
-    const char *e = std::getenv("FDNN_CHAIN_MIN");
-    return e ? std::atoi(e) : 9800;
-  }();
-  const int forced = g_chain_mode.load(std::memory_order_relaxed), forced_min = g_chain_min.load(std::memory_order_relaxed);
-  // From ~9 800 frames up -- a round of 256-node x 320-frame tiles and more -- the chain is the faster form at EVERY size
-  // (tools/chain_sweep.py, layer 0 + six hidden layers, chained / per-layer: 10 000 frames 0.98, 10 241 0.88, 12 000 0.86,
-  // 15 360 0.93, 20 480 0.97): its tasks flow across the layers where a launch per layer idles most of the chip in every
-  // partial round.  Below, the per-layer path has better tiles for the size (160- / 128-frame four-wave shapes, two workgroups
-  // per CU) and the chain's 320-frame tasks leave CUs without work: 9 000 frames 1.04, 8 000 1.21, 6 000 1.33, 4 097 1.33.
-  const int mode = forced >= 0 ? forced : env_mode;  // 0: never; otherwise from min_frames up
-  const int min_frames = (forced >= 0 && forced_min > 0) ? forced_min : env_min;
-  if (mode == 0 || n_layers < 2 || n_layers > kMaxChainLayers || K % 128 != 0 || n < min_frames) return false;
-  if (forced == 1) return true;  // (tests / measurements: wherever the shape allows)
-  // ... and only where a launch per layer would run a partly filled round: at whole rounds of 320-frame tiles (10 000 /
-  // 10 240 / 20 480 frames on a 2048-wide net) the two forms are within +-2 % of each other, the sign depending on the box.
-  static const long cus = [] {  // (advisor, round 5: not a hard-coded 256)
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    return static_cast<long>(n_cu);
-  }();
-  const long tiles = static_cast<long>(rows_pad / 256) * ((n + 319) / 320);
-  const long idle = (tiles + cus - 1) / cus * cus - tiles;
-  return idle >= 24;
-}
-
-int qchain_frame_tile(int rows_pad, int n) {
-  (void)rows_pad;
-  static const int forced = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_CHAIN_TILE");
-    return e ? std::atoi(e) : 0;
-  }();
-  if (forced == 256 || forced == 320) return forced;
-  // 320-frame tiles unless the padding they add is worth more than their better operand reuse
-  const int pad320 = (n + 319) / 320 * 320 - n, pad256 = (n + 255) / 256 * 256 - n;
-  return pad256 + 64 < pad320 ? 256 : 320;
-}
-
-void launch_qchain(const QChainParams &p, hipStream_t s) {
+void launch_qchain(const QChainParams &p, int n_cu, hipStream_t s) {
   if (p.frame_tile == 256)
-    launch_chain_cfg<4, 2, 128, 2>(p, s);
+    launch_chain_cfg<4, 2, 128, 2>(p, n_cu, s);
   else
-    launch_chain_cfg<5, 2, 128, 2>(p, s);
+    launch_chain_cfg<5, 2, 128, 2>(p, n_cu, s);
 }
 
 }  // namespace fdnn

@@ -55,7 +55,7 @@ int fdnn_debug_set_l0_kernel(fdnn_model *m, int kind) {
 
 int fdnn_debug_set_fuse(int mode) {
   if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "fuse mode must be -1, 0 or 1");
-  set_fuse_override(mode);
+  fdnn::sel::tuning().fuse_mode = mode;
   return FDNN_OK;
 }
 
@@ -84,7 +84,8 @@ int fdnn_debug_set_l0_list_cap(fdnn_model *m, int cap) {
 
 int fdnn_debug_set_pp(int mode, int min_frames) {
   if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "pp mode must be -1, 0 or 1");
-  fdnn::qpp_set_mode(mode, min_frames);
+  fdnn::sel::tuning().pp_mode = mode;
+  fdnn::sel::tuning().pp_min = min_frames;
   return FDNN_OK;
 }
 
@@ -98,7 +99,7 @@ int fdnn_debug_raise_fuse_fault(fdnn_model *m, int value) {
 
 int fdnn_debug_set_ppo(int mode) {
   if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "ppo mode must be -1, 0 or 1");
-  fdnn::qppo_set_mode(mode);
+  fdnn::sel::tuning().ppo_mode = mode;
   return FDNN_OK;
 }
 
@@ -129,7 +130,8 @@ int fdnn_debug_launch_counts(unsigned long long *out, int cap) {
 
 int fdnn_debug_set_chain(int mode, int min_frames) {
   if (mode < -1 || mode > 1) return fail(FDNN_E_ARG, "chain mode must be -1, 0 or 1");
-  fdnn::qchain_set_mode(mode, min_frames);
+  fdnn::sel::tuning().chain_mode = mode;
+  fdnn::sel::tuning().chain_min = min_frames;
   return FDNN_OK;
 }
 

@@ -1128,7 +1128,7 @@ void launch_cfg(const QGemmParams &p, hipStream_t s) {
   using Cfg = GemmCfg<NF, WN, BK, STAGES, WM>;
   using Kernel = void (*)(QGemmParams);
   // the fused soft-max: the 8-wave shapes and the 4-wave 128-frame shapes of small launches (two workgroups per CU).  The
-  // 3-stage 64-byte-step shape is the 128-frame tile of launches of more than 256 workgroups, which qgemm_fused_ok refuses.
+  // 3-stage 64-byte-step shape is the 128-frame tile of launches of more than 256 workgroups, which sel::fused_ok refuses.
   constexpr bool kCanFuse = OUTPUT && FAST && WM == 4 && NF >= 4 && (BK == 128 || STAGES == 6);
   // layers without saturating pairs, the 8-wave production shapes: no entry walk in the loop
 #ifdef FDNN_NO_NOFIX  // (measurement builds: the instances with the walk for every layer)
@@ -1198,179 +1198,34 @@ void launch_cfg(const QGemmParams &p, hipStream_t s) {
   hipLaunchKernelGGL(kernels[branch], dim3(blocks), dim3(Cfg::THREADS), Cfg::LDS, s, p);
 }
 
-// a 128-frame launch of at most 256 workgroups, every one with a CU of its own (no taps): the one latency-bound k-loop per
-// launch takes whole cache lines per step (128-byte k-steps); every other 128-frame launch the 64-byte-step shape
-inline bool ft128_one_round(const QGemmParams &p) { return static_cast<long>(p.rows_pad / 256) * (p.n_pad / 128) <= 256 && !p.tap_acc; }
-
+// the selected shape (fdnn_select.hpp: gemm_shape) -> its instance
 template <bool OUTPUT>
-void launch_qgemm(const QGemmParams &p, hipStream_t s) {
-  if (!p.fastdiv) return launch_cfg<4, 1, 64, 3, OUTPUT, false>(p, s);  // layer whose coefficient failed the exact-division check (e.g. 127/0 = inf)
+void launch_qgemm(const QGemmParams &p, GemmShape shape, hipStream_t s) {
+  switch (shape) {
+    case gs_tdiv: return launch_cfg<4, 1, 64, 3, OUTPUT, false>(p, s);
+    case gs_ft32w1:
+      if constexpr (!OUTPUT) return launch_cfg<1, 1, 128, 4, false, true, 1>(p, s);
+      [[fallthrough]];
+    case gs_ft32: return launch_cfg<1, 1, 128, FDNN_SMALL_STAGES, OUTPUT>(p, s);
+    case gs_ft64: return launch_cfg<2, 1, 128, 3, OUTPUT>(p, s);
+    case gs_ft128nt128:
+      if constexpr (!OUTPUT) return launch_cfg<2, 2, 128, 2, false, true, 2>(p, s);
+      [[fallthrough]];
+    case gs_ft128: return launch_cfg<4, 1, 64, 3, OUTPUT>(p, s);
+    case gs_ft128bk128: return launch_cfg<4, 1, 128, 3, OUTPUT, true, 4, false>(p, s);
+    case gs_ft256: return launch_cfg<4, 2, 128, 2, OUTPUT>(p, s);
 #ifdef FDNN_ABLATION  // measurement builds: FDNN_SMALL_BK=64 gives the three small-launch shapes 64-byte k-steps in a 6-stage ring
-  static const bool bk64 = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_SMALL_BK");
-    return e && std::atoi(e) != 128;
-  }();
+    case gs_ft32bk64: return launch_cfg<1, 1, 64, 6, OUTPUT>(p, s);
+    case gs_ft64bk64: return launch_cfg<2, 1, 64, 6, OUTPUT>(p, s);
+    case gs_ft128bk64x6: return launch_cfg<4, 1, 64, 6, OUTPUT, true, 4, false>(p, s);
 #endif
-  switch (p.frame_tile) {
-    // few frames: 32- / 64-frame tiles put four / two times as many workgroups on the chip; 128-byte
-    // k-steps (3-stage ring) halve the barriers of the latency-bound loop: 16.6 vs 21 us per
-    // 2048 x 2048 layer.  What is left at this size is mostly the launch itself: a 128-node tile
-    // (half the operand traffic per workgroup) and whole-step fragment prefetch, both tried, left
-    // the 16.6 us untouched.
-    // ... and while the 32-frame tiles leave CUs idle or nearly so, a launch waits for ONE workgroup's operand stream: 288
-    // rows x 2 KiB at the ~70 GB/s one CU's LDS-DMA path moves = 8 of the 17 us of a 2048 x 2048 layer, whatever the frame
-    // count.  64-node tiles (one wave per workgroup) split the same weight rows over four times as many CUs: six hidden
-    // layers 101-110 -> 88-98 us from 8 to 700 frames (tools/batch_sweep.py; up to three workgroups per CU, beyond that
-    // the extra activation traffic loses).  Hidden layers only: the output layer's exp / transposition epilogue makes its
-    // narrow tiles slower (27 vs 21 us).
-    case 32:
-#ifdef FDNN_ABLATION
-      if (bk64) return launch_cfg<1, 1, 64, 6, OUTPUT>(p, s);
-#endif
-      if constexpr (!OUTPUT) {
-        bool one_wave = static_cast<long>(p.rows_pad / 256) * (p.n_pad / 32) * 4 <= 768;
-#ifdef FDNN_ABLATION
-        static const int force_wm = [] {  // FDNN_SMALL_WM=1 / 4: one wave per workgroup or four, whatever the launch's size
-          const char *e = FDNN_TUNE_ENV("FDNN_SMALL_WM");
-          return e ? std::atoi(e) : 0;
-        }();
-        if (force_wm) one_wave = force_wm == 1;
-#endif
-        if (one_wave) return launch_cfg<1, 1, 128, 4, false, true, 1>(p, s);
-      }
-      return launch_cfg<1, 1, 128, FDNN_SMALL_STAGES, OUTPUT>(p, s);
-    case 64:
-#ifdef FDNN_ABLATION
-      if (bk64) return launch_cfg<2, 1, 64, 6, OUTPUT>(p, s);
-#endif
-      return launch_cfg<2, 1, 128, 3, OUTPUT>(p, s);
-    case 128:
-      if constexpr (!OUTPUT) {  // 128 nodes x 128 frames, 2 x 2 waves, double-buffered 128-byte k-steps, two workgroups per CU
-        if (p.node_tile == 128) return launch_cfg<2, 2, 128, 2, false, true, 2>(p, s);
-      }
-      // 4 waves, 3-stage ring, two workgroups per CU
-      if (!ft128_one_round(p)) return launch_cfg<4, 1, 64, 3, OUTPUT>(p, s);
-#ifdef FDNN_ABLATION
-      if (bk64) return launch_cfg<4, 1, 64, 6, OUTPUT, true, 4, false>(p, s);
-#endif
-      return launch_cfg<4, 1, 128, 3, OUTPUT, true, 4, false>(p, s);
-    // 8 waves, 128-byte k-step (whole cache lines), double buffer, one workgroup per CU
-    case 256: return launch_cfg<4, 2, 128, 2, OUTPUT>(p, s);
-    default: return launch_cfg<5, 2, 128, 2, OUTPUT>(p, s);  // 320
+    default: return launch_cfg<5, 2, 128, 2, OUTPUT>(p, s);  // gs_ft320
   }
 }
 
 }  // namespace
 
-int qgemm_debug_flags() {
-  static const int flags = [] {
-    const char *e = std::getenv("FDNN_GEMM_DEBUG") /* test hook: bit 4096 makes fused soft-max tiles give up (tests) */;
-    return e ? std::atoi(e) : 0;
-  }();
-  return flags;
-}
-
-int qgemm_frame_tile(int rows_pad, int n) {
-  static const int forced = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_FRAME_TILE");
-    return e ? std::atoi(e) : 0;
-  }();
-  if (forced == 32 || forced == 64 || forced == 128 || forced == 256 || forced == 320) return forced;
-  const int mt = rows_pad / 256;
-  // Few frames: while every workgroup gets a CU of its own the launch is one k-loop deep and
-  // latency bound, so the smallest tile that still fits in one round wins -- it has the shortest
-  // k-step and puts the most CUs to work (2048 x 2048 layer, 1000 frames: 21 us with 32-frame
-  // tiles = 256 workgroups, 24 us at 64, 31 us at 128; 8000-node output layer, 1000 frames:
-  // 39 us at 128 = 256 workgroups, 47 us at 64, 65 us at 32 = four rounds).
-  for (int ft : {32, 64, 128})
-    if (static_cast<long>(mt) * ((n + ft - 1) / ft) <= 256) return ft;
-  // Cost model: rounds x frames per tile / relative throughput of the kernel shape.
-  // A round fills every CU once (two co-resident workgroups for the 4-wave shapes).
-  struct Cand {
-    int ft, slots;
-    double eff;
-  };
-  const Cand cands[] = {{128, 512, 0.55}, {256, 256, 1.0}, {320, 256, 1.0}};
-  int best = 128;
-  double best_cost = -1.0;
-  for (const Cand &c : cands) {
-    const long blocks = static_cast<long>(mt) * ((n + c.ft - 1) / c.ft);
-    const long rounds = (blocks + c.slots - 1) / c.slots;
-    // a 4-wave workgroup shares its CU with a second one: a round costs two tiles' time
-    const double cost = rounds * c.ft * (c.slots == 512 ? 2.0 : 1.0) / c.eff;
-    if (best_cost < 0 || cost < best_cost || (cost == best_cost && c.ft > best)) {
-      best_cost = cost;
-      best = c.ft;
-    }
-  }
-  return best;
-}
-
-// Batches up to this many frames take the small-batch kernel (fdnn_small.hip) where the layer allows it.  Measured
-// crossovers on the 2048-wide layers (tools/batch_sweep.py, FDNN_SMALL_MAX=0 against the default): six hidden layers
-// (64-node tiles from ~160 frames up) 54 vs 88 us at 256 frames, 68 vs 90 at 512, 93 vs 104 at 1000, 104 vs 118 at
-// 1200, 117 vs 118 at 1500, 137 vs 121 at 2000; the 8000-node output layer 16.5 vs 24.6 at 256, 25.8 vs 26.3 at 512,
-// 44 + 15 (scale pass) vs 40 (fused) at 1000 (a workgroup of the small kernel walks its frame tiles one after the other).
-bool qgemm_small_pick(int rows_pad, int K, int n, int fastdiv, bool output) {
-  static const int small_max = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_SMALL_MAX");
-    return e ? std::atoi(e) : -1;
-  }();
-  (void)rows_pad;
-  const int lim = small_max >= 0 ? small_max : output ? 512 : 1400;
-  return n <= lim && qgemm_small_ok(K, fastdiv);
-}
-
-bool qgemm_fused_ok(const QGemmParams &p) {
-  static const bool off = [] {
-    const char *e = std::getenv("FDNN_FUSE_NORM");
-    return e && std::atoi(e) == 0;
-  }();
-  if (off || p.small || p.node_tile != 256 || !p.fastdiv || (p.mask && !p.mask_bits) || p.tap_acc || p.tap_logit) return false;
-  if (p.frame_tile != 320 && p.frame_tile != 256 && p.frame_tile != 128) return false;
-  // the 128-frame tiles of more than one round have no fused form: none can come about here, where MT <= 32 below and
-  // qgemm_frame_tile's cost model prefers 128 from 129 node tiles up (a forced FDNN_FRAME_TILE apart)
-  if (p.frame_tile == 128 && !ft128_one_round(p)) return false;
-  const int MT = p.rows_pad / 256;
-  int L = 1;
-  while (L < MT) L <<= 1;
-  // the epilogue's LDS: one 32 x 64 float tile per wave, then 4 partial rows + the inverses + L rows of S, below the
-  // table / bias area (GemmCfg::FIX_OFF: two 128-byte-step stages for the 8-wave shapes, at least three 64-byte-step
-  // stages for the 4-wave ones)
-  const bool eight = p.frame_tile >= 256;
-  const long need = 8192 + (eight ? 8 : 4) * 32 * 68 * 4 + (5L * p.frame_tile + 4 + static_cast<long>(L) * p.frame_tile) * 4;
-  const long have = static_cast<long>(256 + p.frame_tile) * (eight ? 128 * 2 : 64 * 3);
-  return L <= 32 && need <= have;
-}
-
-// Mid-size batches of the hidden layers: when the layer is between one and two rounds of 128 x 128 tiles (2 049 .. 4 096
-// frames on a 2048-node layer), the four-wave 128 x 128 shape -- two workgroups per CU, so one's prologue / epilogue
-// hides under the other's k-loop -- beats the 256-node tiles of the same area (tools/batch_sweep.py, six hidden layers:
-// 140 vs 158 us at 2 560 frames, 141 vs 158 at 3 000, 151 vs 162 at 4 000; it loses below (123 vs 119 at 2 000: one
-// workgroup per CU again) and above (229 vs 202 at 5 000), and on the 8000-node output layer).  Returns 128 or 256;
-// with 128 the frame tile is 128 as well.
-int qgemm_node_tile(int rows_pad, int n, bool output) {
-  static const int forced = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_NODE_TILE");
-    return e ? std::atoi(e) : 0;
-  }();
-  if (output) return 256;
-  if (forced == 128 || forced == 256) return forced;
-  const long tiles = static_cast<long>(rows_pad / 128) * ((n + 127) / 128);
-  return (tiles > 256 && tiles <= 512) ? 128 : 256;
-}
-
-void launch_qgemm_hidden(const QGemmParams &p, hipStream_t s) {
-  if (p.small)
-    launch_qgemm_small_hidden(p, s);
-  else
-    launch_qgemm<false>(p, s);
-}
-void launch_qgemm_output(const QGemmParams &p, hipStream_t s) {
-  if (p.small)
-    launch_qgemm_small_output(p, s);
-  else
-    launch_qgemm<true>(p, s);
-}
+void launch_qgemm_hidden(const QGemmParams &p, GemmShape shape, hipStream_t s) { launch_qgemm<false>(p, shape, s); }
+void launch_qgemm_output(const QGemmParams &p, GemmShape shape, hipStream_t s) { launch_qgemm<true>(p, shape, s); }
 
 }  // namespace fdnn

@@ -222,7 +222,6 @@ inline void unpack_act_rows(const int8_t *src, size_t ld, int n, int H, uint8_t 
 // The soft-max fusing switches (run_output): this process's device marker (1 = ours or cannot tell, 0 = another process's)
 // and fdnn_debug_set_fuse's override (-1 = by environment / marker, 0 = never, 1 = always).
 int device_marker_state(int device);
-void set_fuse_override(int mode);
 // ---------------------------------------------------------------- raw feature frames (fdnn_splice.hip)
 // FDNN_E_STATE without a spec, FDNN_E_ARG when raw_dim is not its D (raw_dim < 0: any)
 int splice_check(const SpliceRef &spec, int raw_dim);

@@ -6,9 +6,11 @@
 #include <vector>
 
 #include "fdnn_note.hpp"
+#include "fdnn_select.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
-// FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv.  Everything else -- tile-shape
+// FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
+// runs, in one place (fdnn_select.cpp, into fdnn_select.hpp's Tuning).  Everything else -- tile-shape
 // overrides, thresholds and kernel choices that the sweeps under tools/ turn -- exists only in measurement builds
 // (-DFDNN_ABLATION: tools/build_variant.sh): in the shipped library FDNN_TUNE_ENV is a null pointer, the defaults are
 // constants, and the compile-time ablation branches (FDNN_GEMM_DEBUG, FDNN_L0S_DEBUG, FDNN_CHAIN_CLK, ...) cannot be set.
@@ -72,23 +74,15 @@ struct L0Params {
   float *dbg_dd;
 };
 constexpr int kL0ScreenCap = 4096;  // listed outputs per tile (25 %); a tile that overflows is recomputed whole
-void launch_l0(const L0Params &p, hipStream_t s);
-// fdnn_l0s.hip: is the int8 screening available for this layer shape; bytes of one operand's digit planes; the node half
-// (host code, model load); pre-pass + matrix kernel (launch_l0 follows with the exact recomputation of the flagged outputs)
-bool l0_split_ok(int D, int H);
+void launch_l0(const L0Params &p, const sel::L0Choice &ch, hipStream_t s);  // ch = sel::choose_l0
+// fdnn_l0s.hip: bytes of one operand's digit planes; the node half (host code, model load); pre-pass + matrix kernel
+// (launch_l0 follows with the exact recomputation of the flagged outputs)
 size_t l0_split_plane_bytes(int D, int rows_ld);
-void launch_l0_split(const L0Params &p, hipStream_t s);
+void launch_l0_split(const L0Params &p, int wn_cfg, hipStream_t s);
 void l0_split_build_weights(const float *w, const float *wnorm, const uint8_t *lut2, int H, int D, int h_ld, std::vector<int8_t> *planes,
                             std::vector<float> *stat, std::vector<uint32_t> *half);
 int l0_chunk_rows(int D);
-int l0_chain_node_tile();  // 64 (default: no park scratch needed) or 128 (L0Params::park must be allocated)
 void launch_l0_weight_image(const float *w, float *wt, int H, int D, int j_pad, int h_ld, hipStream_t s);
-
-// Frame tile (32/64/128/160/256/320) the int8 GEMM should use for `n` frames of a layer
-// with rows_pad padded nodes; n_pad = n rounded up to it.
-int qgemm_frame_tile(int rows_pad, int n);
-int qgemm_node_tile(int rows_pad, int n, bool output);  // 256, or 128 where the 128 x 128 shape (frame tile 128) is the better one
-int qgemm_debug_flags();
 
 // int8 layer: C[node][frame] = sum_k W[node][k] * (A[frame][k] + 128), then the
 // layer's epilogue.  W rows are padded to 256, A rows to the frame tile.
@@ -137,36 +131,24 @@ struct QGemmParams {
   int32_t *tap_acc;       // [n][rows]
   float *tap_logit;       // [n][rows]
 };
-// Small batches (fdnn_small.hip): does this layer (K bytes per row, exact-division epilogue validated) have the
-// small-batch shape, and should a batch of n frames take it?
-bool qgemm_small_ok(int K, int fastdiv);
-bool qgemm_small_pick(int rows_pad, int K, int n, int fastdiv, bool output);
-void launch_qgemm_small_hidden(const QGemmParams &p, hipStream_t s);
+// The launchers take what sel::choose_layer chose (fdnn_select.hpp) and the CU count of the model's device where the
+// grid depends on it.  Small batches (fdnn_small.hip; ntm: 32- or 64-node tiles), the tiled shapes (fdnn_gemm.hip):
+void launch_qgemm_small_hidden(const QGemmParams &p, int ntm, hipStream_t s);
 void launch_qgemm_small_output(const QGemmParams &p, hipStream_t s);
-// Fused soft-max available for this launch?  (dense production call, 8-wave shapes, the row sums of all node tiles fit the
-// epilogue's LDS)
-bool qgemm_fused_ok(const QGemmParams &p);
-void launch_qgemm_hidden(const QGemmParams &p, hipStream_t s);
-void launch_qgemm_output(const QGemmParams &p, hipStream_t s);
+void launch_qgemm_hidden(const QGemmParams &p, GemmShape shape, hipStream_t s);
+void launch_qgemm_output(const QGemmParams &p, GemmShape shape, hipStream_t s);
 
 // An int8 hidden layer of a large batch with the two waves of every SIMD in different roles (fdnn_pp.hip): one computes
 // (fragment reads + MFMAs only) while its partner stages that tile's operands and runs the epilogue of the tile it computed
-// before.  256-node x 320-frame tiles (n_pad a multiple of qpp_frame_tile()), K = 2048, validated 3-operation division.
-bool qpp_ok(int rows_pad, int K, int n, bool fastdiv, bool has_fix);
-void qpp_set_mode(int mode, int min_frames);  // fdnn_debug_set_pp
-int qpp_frame_tile();
-void launch_qpp_hidden(const QGemmParams &p, hipStream_t s);
+// before.  256-node x 320-frame tiles (n_pad a multiple of sel::kPpFrameTile), K = 2048, validated 3-operation division.
+void launch_qpp_hidden(const QGemmParams &p, int n_cu, hipStream_t s);
 // fdnn_ppo.hip: the same role split for the OUTPUT layer of a large dense batch, soft-max scaled inside the kernel (the
 // caller holds the device's chain of fused launches: run_output)
-bool qppo_ok(int rows, int rows_pad, int K, int n, bool fastdiv, bool has_fix);
-void qppo_set_mode(int mode);  // -1 default (FDNN_PPO in the environment, else by size), 0 never, 1 whenever the shape allows
-int qppo_frame_tile();
-void launch_qppo_output(const QGemmParams &p, hipStream_t s);
+void launch_qppo_output(const QGemmParams &p, int n_cu, hipStream_t s);
 
 // The int8 HIDDEN layers of a pass in one persistent launch (fdnn_chain.hip): tasks (layer, frame tile, node tile) drawn
 // from per-XCD queues, a task waits only for its own frame tile's node tiles of the layer before.  All hidden layers of
 // a net have the same shape (README.md:10), so one set of sizes serves every layer.
-constexpr int kMaxChainLayers = 8;
 struct QChainLayer {
   const int8_t *w;         // [rows_pad][ldw]
   const float *bias;       // [rows_pad]
@@ -189,10 +171,7 @@ struct QChainParams {
   long long *clk;          // measurement builds (FDNN_CHAIN_CLK): [8 + clk_cap * 10] phase clocks per task, else null
   int clk_cap;
 };
-bool qchain_ok(int rows_pad, int K, int n, int n_layers);
-void qchain_set_mode(int mode, int min_frames);  // fdnn_debug_set_chain
-int qchain_frame_tile(int rows_pad, int n);
-void launch_qchain(const QChainParams &p, hipStream_t s);
+void launch_qchain(const QChainParams &p, int n_cu, hipStream_t s);
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

@@ -424,33 +424,8 @@ __global__ __launch_bounds__(512) void l0_small_kernel(L0Params p, int sc, unsig
 #endif
 }
 
-// LDS the small-batch kernel needs for input width D (0: does not fit, or the division magics are not exact)
-inline unsigned l0_div_magic(int d, int max_c) {
-  const unsigned m = static_cast<unsigned>((0x100000000ull + static_cast<unsigned>(d) - 1) / static_cast<unsigned>(d));
-  for (int c = 0; c <= max_c; ++c)
-    if (static_cast<int>((static_cast<unsigned long long>(c) * m) >> 32) != c / d) return 0;
-  return m;
-}
-struct L0SmallGeom {
-  int sc = 0, lds = 0;
-  unsigned sc_magic = 0, ch_magic = 0;
-};
-inline L0SmallGeom l0_small_geom(int D) {
-  L0SmallGeom g;
-  const int ch = D / 4, sc = ch | 1;
-  const int n_ld = (32 * sc + 63) / 64;
-  const int bytes = 2 * n_ld * 1024 + 2 * ((D * 4 + 1023) & ~1023) + 2048 + 64;
-  if (ch < 2 || bytes > 160 * 1024) return g;  // (ch = 1: the magic 2^32 does not fit 32 bits)
-  g.sc_magic = l0_div_magic(sc, n_ld * 64 + 64);
-  g.ch_magic = l0_div_magic(ch, 32 * ch + 512);
-  if (!g.sc_magic || !g.ch_magic) return g;
-  g.sc = sc;
-  g.lds = bytes;
-  return g;
-}
-
 void launch_l0_small(const L0Params &p, hipStream_t s) {
-  const L0SmallGeom g = l0_small_geom(p.D);
+  const sel::L0SmallGeom g = sel::l0_small_geom(p.D);
   auto k = l0_small_kernel<false>;
   auto kt = l0_small_kernel<true>;
   static std::atomic<unsigned long long> attr_set{0};
@@ -719,8 +694,8 @@ void launch_chain_tn(const L0Params &p, hipStream_t s) {
 }
 
 template <int JC>
-void launch_chain(const L0Params &p, hipStream_t s) {
-  if (l0_chain_node_tile() == 64)
+void launch_chain(const L0Params &p, int tn, hipStream_t s) {
+  if (tn == 64)
     launch_chain_tn<JC, 64>(p, s);
   else
     launch_chain_tn<JC, 128>(p, s);
@@ -1229,15 +1204,8 @@ void launch_screened_cfg(const L0Params &p, hipStream_t s) {
   hipLaunchKernelGGL(k_scr, dim3(l0_grid(node_tiles, frame_tiles)), dim3(Cfg::THREADS), Cfg::LDS, s, p);
   hipLaunchKernelGGL(l0_fix_kernel, dim3(node_tiles * frame_tiles), dim3(kFixThreads), 2 * sizeof(float) * p.D + (kFixThreads / 64) * FDNN_L0_FIX_DEPTH * 1024, s, p, Cfg::TF);
 }
-int l0_screen_wfr() {
-  static const int wfr = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_L0_SCREEN_WFR");
-    return e && std::atoi(e) == 2 ? 2 : 4;
-  }();
-  return wfr;
-}
-void launch_screened(const L0Params &p, hipStream_t s) {
-  if (l0_screen_wfr() == 2)
+void launch_screened(const L0Params &p, int wfr, hipStream_t s) {
+  if (wfr == 2)
     launch_screened_cfg<2>(p, s);
   else
     launch_screened_cfg<4>(p, s);
@@ -1245,79 +1213,19 @@ void launch_screened(const L0Params &p, hipStream_t s) {
 
 }  // namespace
 
-void launch_l0(const L0Params &p, hipStream_t s) {
-  static const bool fma_on_valu = FDNN_TUNE_ENV("FDNN_L0_FMA_VALU") != nullptr;
-  if (p.fma && !fma_on_valu) {
-    // 32-float chunks, 4 x 2 waves (128 x 128 tile).  Measured alternatives at 10 000 frames:
-    // 16-float chunks 0.221 ms, 64-float 0.205, 256-thread workgroups (two per CU) 0.205.
-    launch_mfma<32, 4>(p, s);
-    return;
-  }
-  // Small batches (canonical flavour): the whole-K kernel, 32 x 32 tiles (100 frames: 20 -> 6 us)
-  static const int small_max = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_L0_SMALL_MAX");
-    return e ? std::atoi(e) : 128;  // one round of 32 x 32 tiles on a 2048-node layer; beyond, the (16 | 32) x 64 tiles are as fast
-  }();
-  if (!p.fma && p.kernel == 0 && p.n_rows <= small_max && l0_small_geom(p.D).lds > 0) {
-    launch_l0_small(p, s);
-    return;
-  }
-  // Three bit-identical candidates, chosen by modelled time (432 -> 2048 layer, tools/l0_kind_sweep.py; all three
-  // come in rounds of 256 tiles, one per CU, and a round costs the same full or not):
-  //   screened   fused chains on the matrix pipe + exact recomputation of the few outputs the fusion could change
-  //              (128 x 128 tiles): 74 / 122 / 174 / 234 / 285 us for 1..5 rounds; large batches without taps only
-  //   chain      all-VALU chain kernel (128 frames x 64 nodes): 57 / 82 / 110 / 142 / 171 / 203 us for 1..6 rounds
-  //   tile64     (16 | 32 | 64) x 64 tiles, 4 outputs x 4 chains per thread and frame: 19-23 us up to 400 frames, 33-49 us up to
-  //              1200, then 20 us + 35.5 ns per frame
-  // e.g. 2560 frames: 120 screened, 109 chain; 3000: 110 chain, 125 the others; 6000: 174 screened, 204 chain.
-  static const bool no_screen = FDNN_TUNE_ENV("FDNN_L0_NO_SCREEN") != nullptr;
-  static const bool classic = FDNN_TUNE_ENV("FDNN_L0_CLASSIC") != nullptr;
-  const double work = static_cast<double>(p.D) / 432.0;
-  const long ft128 = (p.n_rows + 127) / 128;
-  const double screened_us = 18.0 + 54.0 * work * static_cast<double>((ft128 * ((p.H + 127) / 128) + 255) / 256);
-  const double chain_us = 27.0 + 30.0 * work * static_cast<double>((ft128 * (p.h_ld / l0_chain_node_tile()) + 255) / 256);
-  const double tile64_us = p.n_rows <= 320    ? 23.0 * work
-                           : p.n_rows <= 1200 ? (17.0 + 0.032 * p.n_rows) * work
-                                              : 20.0 + 0.0355 * work * (p.H / 2048.0) * p.n_rows;
-  const bool can_screen = !p.fma && !no_screen && (p.kernel == 0 || p.kernel == 3) && !p.tap_lin && p.wnorm && p.scr_count && p.scr_list && p.n >= 2048 &&
-                          p.D <= 4096;  // l0_fix_kernel: 8 D bytes of shift / scale + 24 KB of product blocks in dynamic LDS (64 KB without an attribute)
-  const bool can_chain = !p.fma && p.xt && p.wt && p.kernel != 2 && !(classic && p.kernel == 0);
-  // Round 4: the screening on the int8 matrix pipe (fdnn_l0s.hip: exact 24-bit integer images of both operands, eight
-  // int8 MFMA products) + the same exact recomputation of the flagged outputs.  128 x 128 tiles, 1.85 us of matrix-pipe
-  // time per tile and CU at peak: from FDNN_L0_SPLIT_MIN frames up it replaces all of the above.
-  static const bool no_split = FDNN_TUNE_ENV("FDNN_L0_NO_SPLIT") != nullptr;
-  static const int split_min = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_L0_SPLIT_MIN");
-    return e ? std::atoi(e) : 560;  // whole call at 512 / 600 frames: 118 / 140 us with the 64 x 64 tiles, 121 / 136 with the screening
-  }();
-  const bool can_split = !p.fma && !no_split && !no_screen && (p.kernel == 0 || p.kernel == 4) && !p.tap_lin && p.xd && p.xstat && p.wd && p.wstat && p.luthalf && p.glist && p.glist_count &&
-                         p.scr_count && p.scr_list && l0_split_ok(p.D, p.H);
-  if (can_split && (p.kernel == 4 || p.n >= split_min)) {
-    launch_l0_split(p, s);
-    const int node_tiles = p.h_ld / 128, frame_tiles = (p.n_rows + 127) / 128;
-    // Variant by batch size (rocprofv3, us at 1 000 / 4 000 / 10 000 frames; LABBOOK): four lanes per output, three quads per
-    // lane and operand in flight, 256 threads: 8.7 / 11.4 / 23.8; EIGHT lanes per output (a whole 128-byte line per output
-    // and load, five round trips instead of nine): 7.3 / 13.8 / 25.0 -- fewer flagged outputs = a latency chain, many = L2
-    // gathers, where the second set of lanes only costs registers.  FDNN_L0_FIX_NB / _T / _LPO force a variant.
-    static const int force_nb = [] {
-      const char *e = FDNN_TUNE_ENV("FDNN_L0_FIX_NB");
-      return e ? std::atoi(e) : 0;
-    }();
-    static const int force_t = [] {
-      const char *e = FDNN_TUNE_ENV("FDNN_L0_FIX_T");
-      return e ? std::atoi(e) : 0;
-    }();
-    static const int force_lpo = [] {
-      const char *e = FDNN_TUNE_ENV("FDNN_L0_FIX_LPO");
-      return e ? std::atoi(e) : 0;
-    }();
-    const int nb = force_nb ? force_nb : 3;
-    const int thr = force_t == 512 ? 512 : 256;
-    const int lpo = force_lpo ? (force_lpo == 8 ? 8 : 4) : (p.n_rows < 3000 ? 8 : 4);
-    // enough workgroups for 1.5 % flagged in one pass each (0.35 % on the bench batch); more is walked in further passes
-    const long expect = static_cast<long>(p.n_rows) * p.H * 3 / 200 / (thr / lpo) + 8;
-    const int grid = static_cast<int>(std::min<long>((expect + 7) / 8 * 8, 8192));  // (a multiple of 8: l0_fix_list_kernel deals its pieces per XCD)
-    const int tiles = node_tiles * frame_tiles;
+// the choice (fdnn_select.hpp: choose_l0) -> its kernels
+void launch_l0(const L0Params &p, const sel::L0Choice &ch, hipStream_t s) {
+  switch (ch.kind) {
+    case sel::L0Kind::mfma: return launch_mfma<32, 4>(p, s);
+    case sel::L0Kind::small: return launch_l0_small(p, s);
+    case sel::L0Kind::split: {
+      launch_l0_split(p, ch.split_wn, s);
+      const int node_tiles = p.h_ld / 128, frame_tiles = (p.n_rows + 127) / 128;
+      const int nb = ch.fix_nb, thr = ch.fix_threads, lpo = ch.fix_lpo;
+      // enough workgroups for 1.5 % flagged in one pass each (0.35 % on the bench batch); more is walked in further passes
+      const long expect = static_cast<long>(p.n_rows) * p.H * 3 / 200 / (thr / lpo) + 8;
+      const int grid = static_cast<int>(std::min<long>((expect + 7) / 8 * 8, 8192));  // (a multiple of 8: l0_fix_list_kernel deals its pieces per XCD)
+      const int tiles = node_tiles * frame_tiles;
 #define FDNN_FIX_LAUNCH(NB_, T_, L_) hipLaunchKernelGGL((l0_fix_list_kernel<NB_, T_, L_>), dim3(grid), dim3(T_), 2 * sizeof(float) * p.D + (T_ / 64) * NB_ * 1024, s, p, tiles)
 #define FDNN_FIX_LAUNCH_T(T_)                                                        \
   do {                                                                               \
@@ -1327,53 +1235,16 @@ void launch_l0(const L0Params &p, hipStream_t s) {
       if (nb >= 5) FDNN_FIX_LAUNCH(5, T_, 4); else FDNN_FIX_LAUNCH(3, T_, 4);        \
     }                                                                                \
   } while (0)
-    note_launch(thr == 512 ? kLn_l0_fixlist_t512 : lpo == 8 ? (nb >= 3 ? kLn_l0_fixlist_lpo8 : kLn_l0_fixlist_nb2_lpo8) : (nb >= 5 ? kLn_l0_fixlist_nb5_lpo4 : kLn_l0_fixlist_lpo4));
-    if (thr == 512) FDNN_FIX_LAUNCH_T(512); else FDNN_FIX_LAUNCH_T(256);
+      note_launch(thr == 512 ? kLn_l0_fixlist_t512 : lpo == 8 ? (nb >= 3 ? kLn_l0_fixlist_lpo8 : kLn_l0_fixlist_nb2_lpo8) : (nb >= 5 ? kLn_l0_fixlist_nb5_lpo4 : kLn_l0_fixlist_lpo4));
+      if (thr == 512) FDNN_FIX_LAUNCH_T(512); else FDNN_FIX_LAUNCH_T(256);
 #undef FDNN_FIX_LAUNCH_T
 #undef FDNN_FIX_LAUNCH
-    return;
+      return;
+    }
+    case sel::L0Kind::screened: return launch_screened(p, ch.tile, s);
+    case sel::L0Kind::chain: return p.jc == 12 ? launch_chain<12>(p, ch.tile, s) : launch_chain<16>(p, ch.tile, s);
+    case sel::L0Kind::tile64: return ch.tile == 16 ? launch_valu<1, 64>(p, s) : ch.tile == 32 ? launch_valu<2, 32>(p, s) : launch_valu<4, 16>(p, s);
   }
-  if (can_screen && (p.kernel == 3 || (screened_us < (can_chain ? chain_us : tile64_us) && screened_us < tile64_us))) {
-    launch_screened(p, s);
-    return;
-  }
-  const bool chain = can_chain && (p.kernel == 1 || chain_us < tile64_us);
-  if (chain) {
-    if (p.jc == 12)
-      launch_chain<12>(p, s);
-    else
-      launch_chain<16>(p, s);
-    return;
-  }
-  // 64 x 64 tile, 16-float chunks, 4 x 4 outputs per thread.  Measured alternatives: 32-float
-  // chunks 0.448 ms, 8 x 4 outputs per thread 0.468 / 0.477 ms (occupancy 2) against 0.388.
-  static const int t64_bk = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_L0_T64_BK");
-    return e ? std::atoi(e) : 0;
-  }();
-  // Few frames: a 64 x 64 tile is 30-40 us of dependent vector work for ONE workgroup however few of them there are, so
-  // small batches take 16- / 32-frame tiles (more, shorter workgroups).  Measured (tools/l0_kind_sweep.py), 8 / 100 / 256 /
-  // 512 / 1000 frames: 16 x 64 tiles 19 / 21 / 23 / 38 / 60 us, 32 x 64 27 / 30 / 30 / 33 / 49, 64 x 64 43 / 45 / 45 / 45 / 55.
-  if (t64_bk == 164 || (t64_bk == 0 && p.n_rows <= 320))
-    launch_valu<1, 64>(p, s);
-  else if (t64_bk == 232 || (t64_bk == 0 && p.n_rows <= 1200))
-    launch_valu<2, 32>(p, s);
-  else
-    launch_valu<4, 16>(p, s);
-}
-
-// Node tile of the chain kernel: 64 (8 frames x 4 nodes per thread, every partial sum in registers,
-// three workgroups per CU) or 128 (8 x 8, l2 + l3 parked in a global scratch buffer).  Both run
-// at the same speed -- the kernel is bound by vector-instruction issue, 329.8 vs 331.7 us at
-// 10 000 frames (rocprofv3) -- but the 64-wide tile moves 164 MB less through HBM per launch and
-// needs no scratch, which is what the soft-max scale running underneath it in the server loop
-// competes for.  FDNN_L0_TN=128 selects the round-1 shape.
-int l0_chain_node_tile() {
-  static const int tn = [] {
-    const char *e = std::getenv("FDNN_L0_TN") /* test hook: 128 = the round-1 tile shape, kept selectable */;
-    return (e && std::atoi(e) == 128) ? 128 : 64;
-  }();
-  return tn;
 }
 
 int l0_chunk_rows(int D) {

@@ -595,8 +595,6 @@ __global__ __launch_bounds__(256 * WN, 3 - WN) void l0_split_kernel(L0Params p, 
 
 }  // namespace
 
-// D <= 496: 256 P0 + P1 stays inside int32 (2^22 D + 2^15 D < 2^31) and the pre-pass rows fit its LDS
-bool l0_split_ok(int D, int H) { return D >= 64 && D <= 496 && (D & 3) == 0 && (H & 15) == 0; }
 // chains are padded to whole chunk PAIRS (the kernel alternates two fragment register sets): 432 -> 4 x 128 positions, 16 chunks
 int l0_split_chain_pad(int D) { return (D / 4 + 63) / 64 * 64; }
 int l0_split_chunks(int D) { return 4 * l0_split_chain_pad(D) / 32; }
@@ -667,23 +665,15 @@ void l0_split_build_weights(const float *w, const float *wnorm, const uint8_t *l
 }
 
 // pre-pass + matrix kernel; the caller (fdnn_l0.hip: launch_l0) follows with l0_fix_kernel on the same tile lists
-void launch_l0_split(const L0Params &p, hipStream_t s) {
+static_assert(kSTF == 128, "fdnn_select.hpp: choose_l0 counts this kernel's 128-frame tiles");
+// wn_cfg: 1 = 64-node tiles, 2 = 128-node tiles (fdnn_select.hpp: choose_l0)
+void launch_l0_split(const L0Params &p, int wn_cfg, hipStream_t s) {
   const int KC = l0_split_chunks(p.D), J = p.D / 4, JP = l0_split_chain_pad(p.D);
   static std::atomic<unsigned long long> attr_set{0};
   int dev = 0;
   (void)hipGetDevice(&dev);
   const unsigned long long dev_bit = 1ull << (dev & 63);
   const int dig_lds = (kDigFrames * (p.D + 1) + kDigFrames) * 4;
-  // 128-node tiles, one 512-thread workgroup per CU; batches so small that those would leave half the chip idle (up to 128
-  // tiles: 1 024 frames on a 2048-node layer) take 64-node tiles, twice as many workgroups of half the size.  Measured
-  // equal both where both fill the chip (99.2 vs 97.7 us at 10 000 frames) and below (layer 0 at 1 000 frames 40.2 vs 40.4 us:
-  // one tile's latency -- 16 chunks and a 32-output-per-lane epilogue per wave -- either way).  FDNN_L0S_WN=1|2 forces one.
-  static const int wn_forced = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_L0S_WN");
-    return e ? std::atoi(e) : 0;
-  }();
-  const int tiles128 = ((p.n_rows + kSTF - 1) / kSTF) * (p.h_ld / 128);
-  const int wn_cfg = wn_forced == 1 || wn_forced == 2 ? wn_forced : (tiles128 <= 128 ? 1 : 2);
   if (!(attr_set.load(std::memory_order_acquire) & dev_bit)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(l0_split_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, SplitCfg<1>::LDS);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(l0_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, SplitCfg<2>::LDS);

@@ -6,11 +6,11 @@
 #pragma once
 #include <atomic>
 
+#include "fdnn_select.hpp"
+
 namespace fdnn {
 
-// GEMM tile shapes of launch_qgemm (fdnn_gemm.hip), in the order of its switch; the last three are compiled only in a
-// measurement build (-DFDNN_ABLATION), which takes them where FDNN_SMALL_BK is set
-enum GemmShape { gs_tdiv, gs_ft32w1, gs_ft32, gs_ft64, gs_ft128nt128, gs_ft128bk128, gs_ft128, gs_ft256, gs_ft320, gs_ft32bk64, gs_ft64bk64, gs_ft128bk64x6 };
+// (GemmShape, the tile shapes of launch_qgemm: fdnn_select.hpp)
 // branches of launch_cfg
 enum GemmBranch {
   gb_tap, gb_prod, gb_prod_nofix, gb_plain, gb_anyw, gb_masked, gb_masked_anyw, gb_fused, gb_fused_masked, gb_fused_anyw, gb_fused_masked_anyw, gb_fused_nofix, gb_fused_masked_nofix, gb_count

@@ -536,48 +536,11 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
 
 }  // namespace
 
-static std::atomic<int> g_pp_mode{-1}, g_pp_min{0};
-void qpp_set_mode(int mode, int min_frames) {
-  g_pp_mode.store(mode, std::memory_order_relaxed);
-  g_pp_min.store(min_frames, std::memory_order_relaxed);
-}
+static_assert(kFT == sel::kPpFrameTile && kBM == sel::kPpNodeTile && kKT * kBK == sel::kPpK, "fdnn_select.hpp states this kernel's sizes");
 
-// The role-split kernel serves the production shape (K = 2048: 16 ticks per phase, 256-node tiles, validated 3-operation
-// division).  Where it pays today (profiles/LABBOOK.md, round 6): layers WITHOUT saturating pairs from two tiles per
-// workgroup up (16 384 frames on a 2048-wide net: 463 vs 480 us for six layers at 20 000 frames; 260 vs 258 at 10 000, where a
-// workgroup has one tile and nothing hides the second half's epilogue).  With the pair-saturation walk in the compute
-// role's instruction stream -- one wave per SIMD, nothing to cover its latency chain -- it loses (328 vs 279 us on the
-// Gaussian bench net): such layers keep fdnn_gemm.hip's in-phase tiles unless forced (fdnn_debug_set_pp(1, n), FDNN_PP=1).
-bool qpp_ok(int rows_pad, int K, int n, bool fastdiv, bool has_fix) {
-  static const int env_mode = [] {
-    const char *e = std::getenv("FDNN_PP");
-    return e ? std::atoi(e) : -1;
-  }();
-  static const int env_min = [] {
-    const char *e = std::getenv("FDNN_PP_MIN");
-    return e ? std::atoi(e) : 16384;
-  }();
-  const int forced = g_pp_mode.load(std::memory_order_relaxed), forced_min = g_pp_min.load(std::memory_order_relaxed);
-  const int mode = forced >= 0 ? forced : env_mode;
-  const int min_frames = (forced >= 0 && forced_min > 0) ? forced_min : env_min;
-  if (mode == 0 || !fastdiv || K != kKT * kBK || rows_pad % kBM != 0) return false;
-  if (mode != 1 && has_fix) return false;
-  return n >= min_frames;
-}
-
-int qpp_frame_tile() { return kFT; }
-
-void launch_qpp_hidden(const QGemmParams &p, hipStream_t s) {
+void launch_qpp_hidden(const QGemmParams &p, int n_cu, hipStream_t s) {
   auto k = qpp_kernel<false>;
   auto k_nofix = qpp_kernel<true>;
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  int n_cu = cus[dev & 63].load(std::memory_order_relaxed);
-  if (n_cu == 0) {
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    cus[dev & 63].store(n_cu, std::memory_order_relaxed);
-  }
   const int MT = p.rows_pad / kBM, NP = p.n_pad / kFT;
   const long t_end = 8L * ((NP + 7) / 8) * MT;  // (a multiple of 8: workgroup b and its later tiles b + grid, ... stay on one XCD's list)
   const int grid = static_cast<int>(std::min<long>(t_end, std::max(8, n_cu / 8 * 8)));

@@ -728,46 +728,11 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(96))) void q
 
 }  // namespace
 
-static std::atomic<int> g_ppo_mode{-1};
-void qppo_set_mode(int mode) { g_ppo_mode.store(mode, std::memory_order_relaxed); }
+static_assert(kFT == sel::kPpFrameTile && kBM == sel::kPpNodeTile && kKT * kBK == sel::kPpK && kMT == sel::kPpoNodeTiles, "fdnn_select.hpp states this kernel's sizes");
 
-// The role-split fused output kernel serves the dense production call of the 8000-node layer (8192 padded rows = 32 node
-// tiles: the row sums of a half are one 20 KB block; K = 2048; validated 3-operation division; rows % 4 == 0) on a device
-// whose CUs can hold one workgroup per (node tile, frame pair slot): grid = 32 x (CUs / 32).
-bool qppo_ok(int rows, int rows_pad, int K, int n, bool fastdiv, bool has_fix) {
-  static const int env_mode = [] {
-    const char *e = std::getenv("FDNN_PPO");
-    return e ? std::atoi(e) : -1;
-  }();
-  const int forced = g_ppo_mode.load(std::memory_order_relaxed);
-  const int mode = forced >= 0 ? forced : env_mode;
-  if (mode == 0 || !fastdiv || K != kKT * kBK || rows_pad != kMT * kBM || (rows & 3) != 0) return false;
-  if (mode == 1) return true;
-  // By default where it was measured ahead of the in-phase fused tiles (tools/ppo_time.py, several boxes; LABBOOK round 6).
-  // A launch is ceil(pairs / 8) rounds of frame pairs (8 slots of 32 workgroups on 256 CUs); what matters is how full the
-  // last round is and that a workgroup has at least two pairs (a steady state):
-  //   a layer without saturating pairs (trained nets): from 14 pairs when the rounds are >= 3/4 full -- 4 480 frames 102 us
-  //   against 105, 5 120: 105 / 113, 10 000: 191 .. 212 / 218 .. 226, 20 480: 391 / 444; 3 840 (12 pairs): 100 / 95;
-  //   a layer with pairs (the walk runs in a lone compute wave): from 22 pairs when the rounds are >= 4/5 full -- 7 000 frames
-  //   170 / 173, 7 680: 171 / 178, 8 320 .. 8 960: 217 / 224 .. 226, 10 000: 223 / 232, 12 000: 272 / 298, 16 000: 382 / 407;
-  //   8 000 (25 pairs: four rounds, the last with one pair): 216 / 200; 5 120: 123 / 117.
-  const int pairs = (n + kFT - 1) / kFT, rounds = (pairs + 7) / 8;
-  return has_fix ? pairs >= 22 && 5 * pairs >= 4 * 8 * rounds : pairs >= 14 && 4 * pairs >= 3 * 8 * rounds;
-}
-
-int qppo_frame_tile() { return kFT; }
-
-void launch_qppo_output(const QGemmParams &p, hipStream_t s) {
+void launch_qppo_output(const QGemmParams &p, int n_cu, hipStream_t s) {
   auto k = qppo_kernel<false>;
   auto k_nofix = qppo_kernel<true>;
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  int n_cu = cus[dev & 63].load(std::memory_order_relaxed);
-  if (n_cu == 0) {
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    cus[dev & 63].store(n_cu, std::memory_order_relaxed);
-  }
   const int NP = p.n_pad / kFT;
   const int slots = std::max(1, std::min(n_cu / kMT, NP));  // frame pairs in flight: every one has all its 32 node tiles resident
   note_launch(p.fix_ent ? kLn_ppo_out_fix : kLn_ppo_out_nofix);

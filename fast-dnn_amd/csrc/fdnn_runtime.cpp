@@ -106,7 +106,7 @@ int build_l0_image(fdnn_model *m) {
     }
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_w0norm), sizeof(float) * wn.size()));
     HIP_TRY(hipMemcpy(m->d_w0norm, wn.data(), sizeof(float) * wn.size(), hipMemcpyHostToDevice));
-    if (fdnn::l0_split_ok(h.in_dim, h.hidden)) {  // the node half of the int8 screening (fdnn_l0s.hip): digit planes + constants
+    if (sel::l0_split_ok(h.in_dim, h.hidden)) {  // the node half of the int8 screening (fdnn_l0s.hip): digit planes + constants
       std::vector<int8_t> planes;
       std::vector<float> stat;
       std::vector<uint32_t> pairs;
@@ -212,7 +212,7 @@ int make_ctx(fdnn_model *m, int n, fdnn_ctx **out, bool lean) {
     if (e == hipSuccess) e = hipMemset(c->d_glist, 0, sizeof(uint2) * size_t(c->glist_cap));
     if (e == hipSuccess) e = hipMemset(c->d_glist_count, 0, sizeof(uint32_t) * 2);
   }
-  if (fdnn::l0_chain_node_tile() == 128)  // the 64-node tile keeps its partial sums in registers
+  if (sel::tuning().l0_chain_tn == 128)  // the 64-node tile keeps its partial sums in registers
     alloc(reinterpret_cast<void **>(&c->d_l0park), sizeof(float) * size_t(c->xt_ld) * m->l0_h_ld);
   alloc(reinterpret_cast<void **>(&c->d_act[0]), npt * c->act_ld);
   alloc(reinterpret_cast<void **>(&c->d_act[1]), npt * c->act_ld);
@@ -300,20 +300,35 @@ int snapshot_acts(const fdnn_ctx *c, int buf, uint8_t *d_dst, hipStream_t s) {
   return FDNN_OK;
 }
 
+// CUs of a device, asked once per device (256 where the runtime cannot say): the rules and the persistent kernels' grids
+// take it for the model's device
+int device_cus(int device) {
+  static std::atomic<int> cus[64];
+  int n_cu = cus[device & 63].load(std::memory_order_relaxed);
+  if (n_cu == 0) {
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu <= 0) n_cu = 256;
+    cus[device & 63].store(n_cu, std::memory_order_relaxed);
+  }
+  return n_cu;
+}
+
+sel::LayerShape layer_shape(const QLayerDesc &d, bool output) {
+  return {d.rows, d.rows_pad, d.cols_pad - fdnn::kRowSkew, d.fastdiv_ok != 0, d.n_fix > 0, output};
+}
+
 // GEMM descriptor of one int8 layer over `n` frames starting at activation row
-// `act` (frame tile chosen for this n).
-fdnn::QGemmParams prepare_qlayer(fdnn_ctx *c, const QLayerDesc &d, const int8_t *act, int n, hipStream_t s, bool output = false) {
+// `act`, with the tiles of the choice made for this call (sel::choose_layer).
+fdnn::QGemmParams prepare_qlayer(fdnn_ctx *c, const QLayerDesc &d, const int8_t *act, int n, const sel::LayerChoice &ch) {
   fdnn_model *m = c->m;
   const BlobHeader &h = m->hm.hdr;
   const uint8_t *B = m->d_blob;
   fdnn::QGemmParams g{};
-  g.small = fdnn::qgemm_small_pick(d.rows_pad, d.cols_pad - fdnn::kRowSkew, n, d.fastdiv_ok, output) ? 1 : 0;
-  g.frame_tile = g.small ? 32 : d.fastdiv_ok ? fdnn::qgemm_frame_tile(d.rows_pad, n) : 128;  // the true-divide kernel has one shape
-  g.node_tile = (!g.small && d.fastdiv_ok) ? fdnn::qgemm_node_tile(d.rows_pad, n, output) : 256;
-  if (g.node_tile == 128) g.frame_tile = 128;
-  g.debug = fdnn::qgemm_debug_flags();
+  g.small = ch.form == sel::Form::small ? 1 : 0;
+  g.frame_tile = ch.frame_tile;
+  g.node_tile = ch.node_tile;
+  g.debug = sel::tuning().gemm_debug;
   g.n = n;
-  g.n_pad = round_up(n, g.frame_tile);
+  g.n_pad = ch.n_pad;
   if (d.n_fix > 0) {
     g.fix_grp = reinterpret_cast<const int32_t *>(B + d.off_fix_grp);
     g.fix_ent = B + d.off_fix_ent;
@@ -377,9 +392,11 @@ void run_layer0(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) 
   l0.jc = m->l0_jc;
   l0.n_ld = c->xt_ld;
   l0.h_ld = m->l0_h_ld;
+  const sel::L0Call call{l0.D, l0.H, l0.h_ld, l0.n, l0.n_rows, l0.fma != 0, l0.kernel, l0.tap_lin != nullptr, l0.xt && l0.wt, l0.wnorm && l0.scr_count && l0.scr_list,
+                               l0.xd && l0.xstat && l0.wd && l0.wstat && l0.luthalf && l0.glist && l0.glist_count && l0.scr_count && l0.scr_list};
   {
     ProfScope ps(m, s, FDNN_PROF_L0);
-    fdnn::launch_l0(l0, s);
+    fdnn::launch_l0(l0, sel::choose_l0(call, sel::tuning()), s);
   }
 }
 
@@ -402,14 +419,14 @@ int run_hidden(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) {
     (void)hipMemsetAsync(c->d_chain_ctl, 0, sizeof(uint32_t) * 16, s);
     (void)hipMemsetAsync(c->d_chain_done, 0, c->chain_done_bytes, s);
   }
-  bool chain = !taps && n_hid >= 2 && c->d_chain_ctl != nullptr && !c->chain_broken &&
-               fdnn::qchain_ok(h.q[0].rows_pad, h.q[0].cols_pad - fdnn::kRowSkew, c->n, std::min(n_hid, fdnn::kMaxChainLayers));
-  for (int qi = 0; chain && qi < n_hid; ++qi)
-    chain = h.q[qi].fastdiv_ok && h.q[qi].rows == h.q[0].rows && h.q[qi].rows_pad == h.q[0].rows_pad && h.q[qi].cols_pad == h.q[0].cols_pad;
-  if (chain) {
+  const sel::Tuning &tune = sel::tuning();
+  const int n_cu = device_cus(m->device);
+  const sel::HiddenPlan plan = sel::plan_hidden(n_hid, [&](int i) { return layer_shape(h.q[i], false); }, c->n,
+                                                            !taps && c->d_chain_ctl != nullptr && !c->chain_broken, tune, {n_cu});
+  if (plan.chain) {
     const uint8_t *B = m->d_blob;
-    for (int q0 = 0; q0 < n_hid; q0 += fdnn::kMaxChainLayers) {  // (nets deeper than kMaxChainLayers + 1: several chains)
-      const int nl = std::min(fdnn::kMaxChainLayers, n_hid - q0);
+    for (int q0 = 0; q0 < n_hid; q0 += fdnn::kMaxChainLayers) {
+      const int nl = sel::chain_segment(n_hid, q0);
       fdnn::QChainParams g{};
       for (int i = 0; i < nl; ++i) {
         const QLayerDesc &d = h.q[q0 + i];
@@ -432,8 +449,8 @@ int run_hidden(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) {
       g.ldw = h.q[0].cols_pad;
       g.lda = c->act_ld;
       g.n = c->n;
-      g.frame_tile = fdnn::qchain_frame_tile(g.rows_pad, c->n);
-      g.n_pad = round_up(c->n, g.frame_tile);
+      g.frame_tile = plan.frame_tile;
+      g.n_pad = plan.n_pad;
       g.ctl = c->d_chain_ctl;
       g.done = c->d_chain_done;
       g.faults = m->d_l0_stats ? m->d_l0_stats + 3 : nullptr;
@@ -442,7 +459,7 @@ int run_hidden(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) {
       g.clk_cap = c->chain_clk_cap;
       {
         ProfScope ps(m, s, FDNN_PROF_HIDDEN);
-        fdnn::launch_qchain(g, s);
+        fdnn::launch_qchain(g, n_cu, s);
       }
       cur ^= nl & 1;
     }
@@ -451,23 +468,18 @@ int run_hidden(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) {
     return FDNN_OK;
   }
   for (int qi = 0; qi < h.n_q - 1; ++qi) {
-    fdnn::QGemmParams g = prepare_qlayer(c, h.q[qi], c->d_act[cur], c->n, s);
+    sel::LayerCall call{c->n, qi};
+    call.tap_acc = taps && taps->acc_hid;
+    const sel::LayerChoice ch = sel::choose_layer(layer_shape(h.q[qi], false), call, tune);
+    fdnn::QGemmParams g = prepare_qlayer(c, h.q[qi], c->d_act[cur], c->n, ch);
     g.act_out = c->d_act[cur ^ 1];
     g.act_ld = c->act_ld;
-    g.tap_acc = (taps && taps->acc_hid) ? taps->acc_hid + size_t(qi) * c->n * h.hidden : nullptr;
-    // Large batches of the production shape: the role-split kernel (fdnn_pp.hip) -- one wave of each SIMD in the k-loop,
-    // its partner staging that tile's operands and running the epilogue of the tile before.  Identical bytes.
-    static const int pp_only = [] { const char *e = std::getenv("FDNN_PP_ONLY"); return e ? std::atoi(e) : -1; }();
-    const bool pp = !g.tap_acc && fdnn::qpp_ok(g.rows_pad, g.K, c->n, g.fastdiv != 0, g.fix_ent != nullptr) && (pp_only < 0 || pp_only == qi);
-    if (pp) {
-      g.small = 0;
-      g.frame_tile = fdnn::qpp_frame_tile();
-      g.n_pad = round_up(c->n, g.frame_tile);
-    }
+    g.tap_acc = call.tap_acc ? taps->acc_hid + size_t(qi) * c->n * h.hidden : nullptr;
     {
       ProfScope ps(m, s, FDNN_PROF_HIDDEN);
-      if (pp) fdnn::launch_qpp_hidden(g, s);
-      else fdnn::launch_qgemm_hidden(g, s);
+      if (ch.form == sel::Form::pp) fdnn::launch_qpp_hidden(g, n_cu, s);
+      else if (ch.form == sel::Form::small) fdnn::launch_qgemm_small_hidden(g, ch.small_ntm, s);
+      else fdnn::launch_qgemm_hidden(g, ch.shape, s);
     }
     cur ^= 1;
     if (taps && taps->u8_acts) snapshot_acts(c, cur, taps->u8_acts + size_t(qi + 1) * c->n * h.hidden, s);
@@ -522,8 +534,6 @@ int device_marker_state(int device) {  // 1 = this process owns the device's mar
   std::fprintf(stderr, "fast-dnn: another process is scoring on GPU %s: this one runs the unfused soft-max (fdnn_device_shared)\n", bus);
   return state[d];
 }
-static std::atomic<int> g_fuse_override{-1};  // fdnn_debug_set_fuse: -1 = by environment / device marker, 0 = never, 1 = always
-void set_fuse_override(int mode) { g_fuse_override.store(mode, std::memory_order_relaxed); }
 // The model's own evidence (see fdnn_model::h_fuse_fault): once a fused launch of this model has given up, it does not fuse again.
 static bool model_may_fuse(fdnn_model *m) {
   if (!m->h_fuse_fault || __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) == 0) return true;
@@ -534,20 +544,13 @@ static bool model_may_fuse(fdnn_model *m) {
                  "did not show?): this model runs the unfused soft-max from here on (fdnn_model_fuse_giveups counts; FDNN_FUSE_NORM=1 overrides)\n",
                  m->device);
   }
-  static const bool forced_on = [] {
-    const char *e = std::getenv("FDNN_FUSE_NORM");
-    return e && std::atoi(e) != 0;
-  }();
-  return forced_on || g_fuse_override.load(std::memory_order_relaxed) == 1;
+  return sel::tuning().fuse_norm == 1 || sel::tuning().fuse_mode == 1;
 }
 
 static bool process_may_fuse(int device) {
-  const int o = g_fuse_override.load(std::memory_order_relaxed);
+  const int o = sel::tuning().fuse_mode;  // fdnn_debug_set_fuse: -1 = by environment / device marker, 0 = never, 1 = always
   if (o >= 0) return o == 1;
-  static const int forced = [] {
-    const char *e = std::getenv("FDNN_FUSE_NORM");
-    return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
-  }();
+  const int forced = sel::tuning().fuse_norm;
   if (forced >= 0) return forced == 1;
   return device_marker_state(device) == 1;
 }
@@ -577,6 +580,19 @@ void fuse_chain_retire_stream(int device, hipStream_t s) {
   }
 }
 
+// The output layer's choice for `count` frames of this context: what run_output launches and what output_will_fuse answers.
+static sel::LayerChoice choose_output(fdnn_ctx *c, int count, bool byte_mask, bool bit_mask, const Taps *taps, bool ctx_may_fuse) {
+  fdnn_model *m = c->m;
+  sel::LayerCall call{count};
+  call.tap_acc = taps && taps->acc_out;
+  call.tap_logit = taps && taps->logits;
+  call.acc_probe = taps && taps->acc_probe;
+  call.byte_mask = byte_mask;
+  call.bit_mask = bit_mask;
+  call.may_fuse = ctx_may_fuse && process_may_fuse(m->device) && model_may_fuse(m);
+  return sel::choose_layer(layer_shape(m->hm.hdr.q[m->hm.hdr.n_q - 1], true), call, sel::tuning());
+}
+
 int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
   const int first = oc.first, count = oc.count;
   const int8_t *d_masks = oc.d_masks;
@@ -592,12 +608,13 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
   // (One frame and decoder-sized blocks take the small-batch GEMM kernels as well: a row-by-row kernel that skips the
   // masked-out nodes as the reference does, dnn.cc:361-365, was measured against them -- DESIGN.md section 6 -- and lost
   // at every block size from 40 % active nodes up: the call is two launches of latency either way.)
-  fdnn::QGemmParams g = prepare_qlayer(c, d, c->d_act[c->last] + size_t(first) * c->act_ld, count, s, true);
+  const sel::LayerChoice ch = choose_output(c, count, d_masks != nullptr, d_bits != nullptr, taps, !c->no_fuse);
+  fdnn::QGemmParams g = prepare_qlayer(c, d, c->d_act[c->last] + size_t(first) * c->act_ld, count, ch);
   g.out = d_out;
   g.partial = c->d_partial;
-  g.partial_ld = g.n_pad;
+  g.partial_ld = ch.partial_ld;
   if (d_bits && !d_masks) {  // bit-mask entry points
-    if (g.small || (taps && taps->acc_out)) {
+    if (!ch.mask_bits) {  // (the small-batch and the tap instances read bytes)
       if (!c->d_mask) return fail(FDNN_E_STATE, "this context has no byte-mask scratch for a small bit-mask batch");
       ProfScope ps(m, s, FDNN_PROF_OUTPUT);
       fdnn::launch_mask_unpack(d_bits, c->d_mask, count, d.rows, s);
@@ -611,7 +628,7 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
   if (d_bits) {
     g.mask_bits = d_bits;
     g.mask_wpr = (d.rows + 63) / 64;
-  } else if (d_masks && !g.small && !(taps && taps->acc_out)) {
+  } else if (d_masks && ch.mask_bits) {
     // large-batch production instances: the mask travels as bits (one pass over the caller's bytes at HBM speed)
     ProfScope ps(m, s, FDNN_PROF_OUTPUT);
     fdnn::launch_mask_pack(d_masks, c->d_mask_bits, count, d.rows, s);
@@ -623,14 +640,7 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
   g.tap_logit = taps ? taps->logits : nullptr;
   g.acc_probe = taps ? taps->acc_probe : nullptr;
   g.probe_stride = taps ? std::max(1, taps->probe_stride) : 1;
-  const bool fused = !c->no_fuse && process_may_fuse(m->device) && model_may_fuse(m) && fdnn::qgemm_fused_ok(g);  // (taps exclude it; the accumulator probe of the parity tests does not)
-  // the role-split fused kernel (fdnn_ppo.hip): dense, unprobed, the production shape, enough frames for a steady state
-  const bool ppo = fused && !g.mask && !g.mask_bits && !g.acc_probe && fdnn::qppo_ok(d.rows, g.rows_pad, g.K, count, g.fastdiv != 0, g.fix_ent != nullptr);
-  if (ppo) {
-    g.small = 0;
-    g.frame_tile = fdnn::qppo_frame_tile();
-    g.n_pad = round_up(count, g.frame_tile);
-  }
+  const bool fused = ch.fused, ppo = ch.form == sel::Form::ppo;
   if (fused && m->h_fuse_fault && __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) != 0) {
     // (fusing although a launch of this model gave up before -- FDNN_FUSE_NORM=1 / fdnn_debug_set_fuse(1): a workgroup that
     // gave up may have left its exchange counters half counted; they are zeroed in stream order before every such launch)
@@ -644,11 +654,7 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
     g.fuse_flag = c->d_fuse_flag;
     g.fuse_giveups = m->d_l0_stats ? m->d_l0_stats + 2 : nullptr;
     g.fuse_fault = m->d_fuse_fault;
-    static const int stagger = [] {
-      const char *e = FDNN_TUNE_ENV("FDNN_FUSE_STAGGER");
-      return e ? std::atoi(e) : 0;
-    }();
-    g.fuse_stagger = stagger;
+    g.fuse_stagger = sel::tuning().fuse_stagger;
   }
   {
     ProfScope ps(m, s, FDNN_PROF_OUTPUT);
@@ -672,8 +678,8 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
         }
         if (fc.recorded) HIP_TRY(hipStreamWaitEvent(s, fc.ev, 0));
       }
-      if (ppo) fdnn::launch_qppo_output(g, s);
-      else fdnn::launch_qgemm_output(g, s);
+      if (ppo) fdnn::launch_qppo_output(g, device_cus(m->device), s);
+      else fdnn::launch_qgemm_output(g, ch.shape, s);
       fc.last_stream = s;
       if (stream_is_durable(c, s) && !eager) {
         fc.pending = true;
@@ -683,8 +689,10 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
         HIP_TRY(hipEventRecord(fc.ev, s));
         fc.recorded = true;
       }
+    } else if (g.small) {
+      fdnn::launch_qgemm_small_output(g, s);
     } else {
-      fdnn::launch_qgemm_output(g, s);
+      fdnn::launch_qgemm_output(g, ch.shape, s);
     }
   }
   hipStream_t ns = s;
@@ -702,14 +710,7 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
   return FDNN_OK;
 }
 
-bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks) {
-  const BlobHeader &h = c->m->hm.hdr;
-  const QLayerDesc &d = h.q[h.n_q - 1];
-  fdnn::QGemmParams g = prepare_qlayer(c, d, c->d_act[0], count, nullptr, true);
-  g.mask = d_masks;
-  if (d_masks && !g.small) g.mask_bits = c->d_mask_bits;  // (what run_output will do)
-  return process_may_fuse(c->m->device) && model_may_fuse(c->m) && fdnn::qgemm_fused_ok(g);
-}
+bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks) { return choose_output(c, count, d_masks != nullptr, false, nullptr, true).fused; }
 
 // Device -> pageable host memory for large results (the 8000-float rows of a whole batch:
 // 320 MB for 10 000 frames).  hipMemcpy into resident pageable memory runs at ~45 GB/s, but a
@@ -776,18 +777,13 @@ static int acquire_ctx(fdnn_model *m, int n, fdnn_ctx **out) {
 // decision: taps and a context whose chain faulted are the caller's business.)
 bool hidden_layers_chain(const fdnn_model *m, int n) {
   const BlobHeader &h = m->hm.hdr;
-  const int n_hid = h.n_q - 1;
-  if (n_hid < 2) return false;
-  for (int qi = 0; qi < n_hid; ++qi)
-    if (!(h.q[qi].fastdiv_ok && h.q[qi].rows == h.q[0].rows && h.q[qi].rows_pad == h.q[0].rows_pad && h.q[qi].cols_pad == h.q[0].cols_pad)) return false;
-  return fdnn::qchain_ok(h.q[0].rows_pad, h.q[0].cols_pad - fdnn::kRowSkew, n, std::min(n_hid, fdnn::kMaxChainLayers));
+  return sel::plan_hidden(h.n_q - 1, [&](int i) { return layer_shape(h.q[i], false); }, n, true, sel::tuning(), {device_cus(m->device)}).chain;
 }
 
 std::vector<std::pair<int, int>> frame_chunks(int n, const fdnn_model *m, bool assume_chained) {
   std::vector<std::pair<int, int>> out;
   static const int kChunk = [] {  // FDNN_CHUNK_FRAMES: measurement switch (0 = never chunk; otherwise whole rounds)
-    const char *e = std::getenv("FDNN_CHUNK_FRAMES");
-    const int v = e ? std::atoi(e) : kChunkFrames;
+    const int v = sel::tuning().chunk_set ? sel::tuning().chunk_frames : kChunkFrames;
     return v <= 0 ? 0 : std::max(kRoundFrames, v / kRoundFrames * kRoundFrames);
   }();
   // A batch whose hidden layers run as a launch per layer (chaining off, fewer than two int8 hidden layers, a layer without

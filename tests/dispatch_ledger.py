@@ -60,7 +60,7 @@ def _net(kind):
     if parts[0] == "k2304":  # rows longer than the small-batch kernels take (K > 2048): the tiled shapes from one frame up
         return F.synth_net([432, 2304, 2304, 2304, 252], seed=61)
     if parts[0] == "wout":  # an output layer of 129 node tiles behind rows too long for the small-batch kernel: one frame tile of
-        # every output shape is a launch of its own here, and qgemm_frame_tile's cost model prefers the 128-frame tiles (321 .. 384 frames)
+        # every output shape is a launch of its own here, and frame_tile's cost model (fdnn_select.hpp) prefers the 128-frame tiles (321 .. 384 frames)
         return F.synth_net([432, 2304, 2304, 2304, int(parts[1])], seed=71)
     if parts[0] == "d64":
         return F.synth_net([64, 256, 256, 256, 252], seed=41)
@@ -444,19 +444,20 @@ EXPECT = {
 # Names no case launches.  Ablation-only names (flag 1 in the library's table: the branch needs a -DFDNN_ABLATION build)
 # are excluded by that flag; the names below are unreachable in the shipped build for the reason given.  The library compiles
 # only the instances its table names (launch_cfg, fdnn_gemm.hip:1140-1163), and what no selection can reach has been deleted;
-# what is left here is the hidden-layer side of the two four-wave 128-frame shapes, which launch_qgemm's `case 128`
-# (fdnn_gemm.hip:1247-1256) keeps as the arms of a 256-node, 128-frame hidden launch -- what a measurement build's forced
-# FDNN_NODE_TILE=256 takes; without them the switch would need an error path.
-# The argument: (a) qgemm_frame_tile (fdnn_gemm.hip:1273-1307) returns 128 either from its first loop (:1285-1286: where
+# what is left here is the hidden-layer side of the two four-wave 128-frame shapes, which gemm_shape's `case 128`
+# (fdnn_select.hpp:200-203; launch_qgemm, fdnn_gemm.hip:1213-1214) keeps as the arms of a 256-node, 128-frame hidden launch --
+# what a measurement build's forced FDNN_NODE_TILE=256 takes; without them the switch would need an error path.
+# The argument: (a) frame_tile (fdnn_select.hpp:112-145) returns 128 either from its first loop (:122-123: where
 # rows_pad / 256 * ceil(n / 128) <= 256) or from the cost model below it, and from the cost model only for layers of 129 node
-# tiles or more (33 024 padded rows): tests/test_dispatch_ledger_host.py evaluates frame_tile_model() for every width the loader
-# accepts (fdnn_model.cpp:315, :374: 2^19 output nodes) up to the frame count beyond which the 128-frame tiles' 465 per 512 tiles
-# can no longer undercut 320 per 256 tiles of 320 frames whatever the rounding; (b) hidden layers are at most 32 768 wide
-# (fdnn_model.cpp:346, :374), 128 node tiles.  (The same statement keeps qgemm_fused_ok's 128-frame clause, fdnn_gemm.hip:1333,
-# from ever refusing a launch: a fused launch has at most 32 node tiles.)
-_FT128_HID = ("fdnn_model.cpp:346 (hidden width <= 32 768 = 128 node tiles) and fdnn_gemm.hip:1285-1306: for such a layer frame tile 128 comes only from "
-              "qgemm_frame_tile's first loop, where rows_pad / 256 * ceil(n / 128) <= 256 < rows_pad / 256 * ceil(n / 64) puts rows_pad / 128 * ceil(n / 128) "
-              "in (256, 512] and qgemm_node_tile (:1359-1360, fdnn_runtime.cpp:311-313) answers 128: the 2 x 2-wave shape (gemm.hid.ft128.nt128.*), taps included; "
+# tiles or more (33 024 padded rows): tests/host/select_check.cpp (tests/test_select_host.py) evaluates the function itself for
+# every width the loader accepts (fdnn_model.cpp:315, :374: 2^19 output nodes) up to the frame count beyond which the 128-frame
+# tiles' 465 per 512 tiles can no longer undercut 320 per 256 tiles of 320 frames whatever the rounding; (b) hidden layers are at
+# most 32 768 wide (fdnn_model.cpp:346, :374), 128 node tiles.  (The same statement keeps fused_ok's 128-frame clause,
+# fdnn_select.hpp:217, from ever refusing a launch: a fused launch has at most 32 node tiles.)
+_FT128_HID = ("fdnn_model.cpp:346 (hidden width <= 32 768 = 128 node tiles) and fdnn_select.hpp:122-144 (with fdnn_select.cpp: no forced tile in the shipped "
+              "build): for such a layer frame tile 128 comes only from "
+              "frame_tile's first loop, where rows_pad / 256 * ceil(n / 128) <= 256 < rows_pad / 256 * ceil(n / 64) puts rows_pad / 128 * ceil(n / 128) "
+              "in (256, 512] and node_tile (:170-171, choose_layer :268-269) answers 128: the 2 x 2-wave shape (gemm.hid.ft128.nt128.*), taps included; "
               "the true-divide layers (also frame tile 128) take their own shape")
 EXCLUDED = {
     "unlisted": "fdnn_gemm.hip:1140-1198 (launch_cfg) against fdnn_note.hpp FDNN_GEMM_LAUNCH_NAMES: every branch of the launcher names a listed (shape, branch); "
@@ -482,26 +483,9 @@ def launched(fn, *args, **kwargs):
 
 
 def chain_tile(n):
-    """Frame tile of the chained hidden-layer kernel (qchain_frame_tile, fdnn_chain.hip): 320 unless 256-frame tiles pad
+    """Frame tile of the chained hidden-layer kernel (chain_frame_tile, fdnn_select.hpp): 320 unless 256-frame tiles pad
     more than 64 frames less."""
     return 256 if (-n % 256) + 64 < (-n % 320) else 320
-
-
-def frame_tile_model(mt, n):
-    """qgemm_frame_tile (fdnn_gemm.hip) restated over numpy arrays of frame counts n for a layer of mt = rows_pad / 256
-    node tiles -> (frame tile, True where it came out of the cost model).  Only the exclusion arguments below lean on it:
-    tests/test_dispatch_ledger_host.py evaluates it over every layer width the loader accepts."""
-    n = np.asarray(n, dtype=np.int64)
-    ft = np.zeros(n.shape, dtype=np.int64)
-    for t in (32, 64, 128):
-        ft = np.where((ft == 0) & (mt * (-(-n // t)) <= 256), t, ft)
-    best, best_cost = np.full(n.shape, 128, dtype=np.int64), np.full(n.shape, -1.0)
-    for t, slots, eff in ((128, 512, 0.55), (256, 256, 1.0), (320, 256, 1.0)):
-        rounds = -(-(mt * (-(-n // t))) // slots)
-        cost = rounds * t * (2.0 if slots == 512 else 1.0) / eff
-        take = (best_cost < 0) | (cost < best_cost) | ((cost == best_cost) & (t > best))
-        best, best_cost = np.where(take, t, best), np.where(take, cost, best_cost)
-    return np.where(ft == 0, best, ft), ft == 0
 
 
 def sample_rows(n, tile, seed):

@@ -42,25 +42,3 @@ def test_row_sample_of_the_big_net_cases():
         for target in (n / 2, n):
             m = int(round(target / tile)) * tile
             assert all(r in idx for r in (m - 1, m) if 0 <= r < n)
-
-
-def test_the_frame_tile_arguments_of_the_exclusions_hold_for_every_layer_the_loader_accepts():
-    """The exclusions of the hidden-layer forms of the four-wave 128-frame shapes rest on a statement about qgemm_frame_tile,
-    restated in dispatch_ledger.frame_tile_model: its cost model returns 128 only for layers of 129 node tiles or more (and
-    nothing but 128, 256 or 320).  Every width the loader accepts (2^19 nodes = 2048 node tiles), every frame count up to
-    392 + 100 345 / mt; beyond that no rounding can help the 128-frame tiles: cost128 >= 465 * mt * n / 65 536 and
-    cost320 <= mt * n / 256 + 1.25 * mt + 320, so 128 can undercut 320 only for n < 392 + 100 345 / mt."""
-    import numpy as np
-
-    lowest = None
-    for mt in range(1, 2049):
-        n = np.arange(1, 392 + 100345 // mt + 2)
-        ft, from_model = L.frame_tile_model(mt, n)
-        assert np.isin(ft, (32, 64, 128, 256, 320)).all(), mt
-        if ((ft == 128) & from_model).any():
-            lowest = mt if lowest is None else lowest
-            assert mt >= 129, mt
-    assert lowest == 129
-    # and the model is the function the ledger's wide-output cases meet on the device: 129 node tiles, 321 .. 384 frames
-    ft, from_model = L.frame_tile_model(129, np.array([320, 321, 384, 385]))
-    assert ft.tolist() == [320, 128, 128, 256] and from_model.all()

@@ -41,7 +41,7 @@ def device_pass(dnn, x, ppo):
 @pytest.mark.parametrize("n", [1, 320, 321, 513, 640, 641, 2560, 4097, 8500, 10000, 20480 + 77])
 def test_role_split_output_equals_the_in_phase_fused_tiles(net_model_path, modes, n):
     """Sizes: 1, 320 and 321 frames never reach the role-split kernel -- up to 512 frames the 8000-node layer takes the
-    small-batch kernel (qgemm_small_pick), which excludes the fused soft-max and with it this kernel (run_output), whatever
+    small-batch kernel (sel::small_pick), which excludes the fused soft-max and with it this kernel (run_output), whatever
     the switch says: both passes are that kernel, asserted below.  The kernel's own edges: the smallest batch that is not
     small (513 = two pairs, the second nearly empty), exactly two pairs of halves (640), one frame more (641); then exactly
     one pair per slot (2 560), workgroups with different numbers of pairs (4 097 = 13 pairs on 8 slots), an odd number of

@@ -126,7 +126,7 @@ def test_small_net_big_batch_masked_8_wave_tiles(tmp_models, out_dim, n):
     """A net small enough for the oracle to score EVERY frame, with enough frames that
     rows_pad/256 * ceil(n/128) > 256 picks the 8-wave 256/320-frame tiles: the MASKED (+ANYW for a
     width that is not a multiple of four) epilogue with its LDS-staged mask, all frames.
-    12 000 frames -> 256-frame tiles, 20 000 -> 320-frame tiles (qgemm_frame_tile's cost model)."""
+    12 000 frames -> 256-frame tiles, 20 000 -> 320-frame tiles (sel::frame_tile's cost model)."""
     p = os.path.join(tmp_models, f"smallnet_out{out_dim}.bin")
     F.write_model_bin(p, F.synth_net([432, 128, 128, 128, out_dim], seed=90 + out_dim))
     x = F.synth_features(n, 432, seed=out_dim)
@@ -792,7 +792,7 @@ def test_layers_without_saturating_pairs_take_the_walk_free_instances(tmp_models
     x = F.synth_features(n, 432, seed=19)
     masks = F.generate_masks_fast(n, topo[-1], 0.40, 0.03, seed=23)
     idx = np.array(sorted(set(np.linspace(0, n - 1, 24).astype(int)) | {319, 320, n - 1}))
-    # frame tile of the 2048-node output layer (qgemm_frame_tile's cost model, 8 node tiles): 10 000 frames are one round of
+    # frame tile of the 2048-node output layer (sel::frame_tile's cost model, 8 node tiles): 10 000 frames are one round of
     # 320-frame tiles; 12 000 are two rounds either way, and the 256-frame tiles' rounds are cheaper
     out_tile = 320 if n == 10000 else 256
     for name, net in (("clean", clean), ("mixed", mixed)):

@@ -1,5 +1,5 @@
 """Layer-0 time per kernel choice (0 = library's choice, 1 = chain kernel, 2 = 64 x 64-tile kernel, 4 = int8 screening)
-against the batch size, to calibrate launch_l0's choice.  Run on the GPU box."""
+against the batch size, to calibrate choose_l0's choice (fdnn_select.hpp).  Run on the GPU box."""
 import os, sys, time
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import torch
