@@ -45,18 +45,6 @@ int calculate_raw_rows(fdnn_model *m, const SpliceRef &spec, const float *raw, i
 
 }  // namespace fdnn
 
-// what upload_model / build_l0_image allocated for a model (any of it may be missing: a load that failed half way)
-static void free_device_side(fdnn_model *m) {
-  hipFree(m->d_blob);
-  hipFree(m->d_w0t);
-  hipFree(m->d_w0norm);
-  hipFree(m->d_w0d);
-  hipFree(m->d_w0stat);
-  hipFree(m->d_lutpair);
-  hipFree(m->d_l0_stats);
-  if (m->h_fuse_fault) hipHostFree(m->h_fuse_fault);
-}
-
 extern "C" {
 
 const char *fdnn_version(void) { return "fast-dnn_amd 0.1 (gfx950)"; }
@@ -70,32 +58,26 @@ int fdnn_device_count(void) {
 int fdnn_model_load_on(const char *path, float cutoff, int device, fdnn_model **out) {
   if (!path || !out) return fail(FDNN_E_ARG, "null argument");
   *out = nullptr;
-  fdnn_model *m = new fdnn_model();
+  std::unique_ptr<fdnn_model> own(new fdnn_model());  // (a load that fails half way: what it allocated goes with the model)
+  fdnn_model *m = own.get();
   std::string msg;
   int rc = fdnn::load_host_model(path, cutoff, &m->hm, &msg);
-  if (rc) {
-    delete m;
-    return fail(rc, msg);
-  }
+  if (rc) return fail(rc, msg);
   m->device = device;
   rc = upload_model(m);
-  if (!rc) (void)fdnn_device_shared(device);  // take (or find taken) the device's process marker now, not at the first large call
-  if (rc) {
-    free_device_side(m);
-    delete m;
-    return rc;
-  }
+  if (rc) return rc;
+  (void)fdnn_device_shared(device);  // take (or find taken) the device's process marker now, not at the first large call
   if (const char *env = std::getenv("FDNN_BATCHER")) {  // max_frames[:depth[:linger_us]]
     int mf = 0, depth = 2, linger = 0;
     if (std::sscanf(env, "%d:%d:%d", &mf, &depth, &linger) >= 1 && mf > 0) {
       rc = fdnn_model_enable_batcher(m, mf, depth, linger);
       if (rc) {
-        fdnn_model_free(m);
+        fdnn_model_free(own.release());
         return rc;
       }
     }
   }
-  *out = m;
+  *out = own.release();
   return FDNN_OK;
 }
 
@@ -156,10 +138,7 @@ void fdnn_model_free(fdnn_model *m) {
   m->batcher = nullptr;
   for (fdnn_ctx *c : m->pool) destroy_ctx(c);
   m->pool.clear();
-  {
-    DeviceGuard g(m->device);
-    free_device_side(m);
-  }
+  DeviceGuard g(m->device);
   delete m;
 }
 
@@ -283,7 +262,7 @@ int fdnn_ctx_lazy_output_batch(fdnn_ctx *c, int first, int count, const int8_t *
     // (blocks of 1..8 frames go through the small GEMM kernel's 32-frame tile, which reads the mask bytes straight from the
     // host-mapped staging; nets the small kernel cannot take -- K > 2048, no validated fast division -- fall to the large
     // tiles behind a mask_pack pass over the same staging)
-    const int rc = run_output(c, {.first = first, .count = count, .d_masks = c->d_mask_pin, .d_out = c->d_out, .d_final = c->d_out_pin}, c->stream);
+    const int rc = run_output(c, {.first = first, .count = count, .d_masks = c->h_mask_pin.dev, .d_out = c->d_out, .d_final = c->h_out_pin.dev}, c->stream);
     use.leave();
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -543,7 +522,7 @@ struct fdnn_stream {
   fdnn_ctx *c = nullptr;  // the stream's own context: max_chunk + R frames
   fdnn::SpliceRef spec;   // the model's spec when the stream was made: every push splices with it
   int raw_dim = 0, max_chunk = 0, left = 0, right = 0;
-  float *d_buf[2] = {nullptr, nullptr};
+  fdnn::DevBuf<float> d_buf[2];
   int cur = 0;
   long long base = 0, len = 0, pushed = 0, emitted = 0;
   bool ended = false;
@@ -569,7 +548,7 @@ int fdnn_stream_create(fdnn_model *m, int max_chunk, fdnn_stream **out) {
   rc = fdnn::make_ctx(m, max_chunk + s->right, &s->c);
   const size_t frames = size_t(max_chunk) + size_t(s->left) + size_t(s->right);
   for (int k = 0; k < 2 && !rc; ++k)
-    if (hipMalloc(reinterpret_cast<void **>(&s->d_buf[k]), sizeof(float) * frames * size_t(s->raw_dim)) != hipSuccess)
+    if (s->d_buf[k].reserve(frames * size_t(s->raw_dim)) != hipSuccess)
       rc = fail(FDNN_E_NOMEM, "stream buffer of " + std::to_string(frames) + " raw frames");
   if (rc) {
     fdnn_stream_free(s);
@@ -584,8 +563,6 @@ void fdnn_stream_free(fdnn_stream *s) {
   if (!s) return;
   DeviceGuard g(s->m->device);
   if (s->c) fdnn::destroy_ctx(s->c);  // (synchronises the stream's work)
-  hipFree(s->d_buf[0]);
-  hipFree(s->d_buf[1]);
   delete s;
 }
 
@@ -684,28 +661,18 @@ int fdnn_model_import_blob(const void *d_src, size_t bytes, int device, fdnn_mod
   DeviceGuard g(device);
   std::vector<uint8_t> host(bytes);
   HIP_TRY(hipMemcpy(host.data(), d_src, bytes, hipMemcpyDeviceToHost));
-  fdnn_model *m = new fdnn_model();
+  std::unique_ptr<fdnn_model> own(new fdnn_model());
+  fdnn_model *m = own.get();
   std::string msg;
   int rc = fdnn::adopt_blob(std::move(host), &m->hm, &msg);
-  if (rc) {
-    delete m;
-    return fail(rc, msg);
-  }
+  if (rc) return fail(rc, msg);
   m->device = device;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->d_blob), bytes);
+  hipError_t e = m->d_blob.reserve(bytes);
   if (e == hipSuccess) e = hipMemcpy(m->d_blob, d_src, bytes, hipMemcpyDeviceToDevice);
-  if (e != hipSuccess) {
-    if (m->d_blob) hipFree(m->d_blob);
-    delete m;
-    return fail(FDNN_E_DEVICE, std::string("blob import: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("blob import: ") + hipGetErrorString(e));
   rc = build_l0_image(m);
-  if (rc) {
-    free_device_side(m);
-    delete m;
-    return rc;
-  }
-  *out = m;
+  if (rc) return rc;
+  *out = own.release();
   return FDNN_OK;
 }
 

@@ -92,7 +92,7 @@ int fdnn_debug_set_pp(int mode, int min_frames) {
 int fdnn_debug_raise_fuse_fault(fdnn_model *m, int value) {
   if (!m) return fail(FDNN_E_ARG, "null model");
   if (!m->h_fuse_fault) return fail(FDNN_E_STATE, "this model has no fault word");
-  __atomic_store_n(m->h_fuse_fault, value ? 1ull : 0ull, __ATOMIC_RELAXED);
+  __atomic_store_n(m->h_fuse_fault.p, value ? 1ull : 0ull, __ATOMIC_RELAXED);
   if (!value) m->fuse_fault_said = false;
   return FDNN_OK;
 }
@@ -141,15 +141,13 @@ int fdnn_debug_chain_clocks(fdnn_ctx *c, long long *out, int cap_tasks) {
   const size_t words = 8 + size_t(cap_tasks) * 10;
   if (!out) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_chain_clk) hipFree(c->d_chain_clk);
-    c->d_chain_clk = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_chain_clk), words * sizeof(long long)));
-    HIP_TRY(hipMemset(c->d_chain_clk, 0, words * sizeof(long long)));
+    c->d_chain_clk.release();  // (a buffer of exactly this many tasks: the launch derives its task bound from the size)
+    HIP_TRY(c->d_chain_clk.reserve(words));
+    HIP_TRY(c->d_chain_clk.fill(0));
     HIP_TRY(hipDeviceSynchronize());
-    c->chain_clk_cap = cap_tasks;
     return FDNN_OK;
   }
-  if (!c->d_chain_clk || cap_tasks > c->chain_clk_cap) return fail(FDNN_E_STATE, "no clock buffer of that size");
+  if (words > c->d_chain_clk.count) return fail(FDNN_E_STATE, "no clock buffer of that size");
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, c->d_chain_clk, words * sizeof(long long), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemset(c->d_chain_clk, 0, 8 * sizeof(long long)));
@@ -168,16 +166,15 @@ int fdnn_debug_forward_taps(fdnn_model *m, const float *x, int n, const int8_t *
   fdnn_ctx *c = nullptr;
   int rc = make_ctx(m, n, &c);
   if (rc) return rc;
-  Taps t{};
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-  };
-  alloc(reinterpret_cast<void **>(&t.l0_lin), sizeof(float) * N * H);
-  alloc(reinterpret_cast<void **>(&t.u8_acts), size_t(n_hidden) * N * H);
-  alloc(reinterpret_cast<void **>(&t.acc_hid), sizeof(int32_t) * size_t(std::max(n_hidden - 1, 1)) * N * H);
-  alloc(reinterpret_cast<void **>(&t.acc_out), sizeof(int32_t) * N * O);
-  alloc(reinterpret_cast<void **>(&t.logits), sizeof(float) * N * O);
+  fdnn::DevBuf<float> d_l0_lin, d_logits;
+  fdnn::DevBuf<uint8_t> d_u8_acts;
+  fdnn::DevBuf<int32_t> d_acc_hid, d_acc_out;
+  hipError_t e = d_l0_lin.reserve(N * H);
+  if (e == hipSuccess) e = d_u8_acts.reserve(size_t(n_hidden) * N * H);
+  if (e == hipSuccess) e = d_acc_hid.reserve(size_t(std::max(n_hidden - 1, 1)) * N * H);
+  if (e == hipSuccess) e = d_acc_out.reserve(N * O);
+  if (e == hipSuccess) e = d_logits.reserve(N * O);
+  const Taps t{d_l0_lin, d_u8_acts, d_acc_hid, d_acc_out, d_logits};
   hipStream_t s = c->stream;
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x, sizeof(float) * N * h.in_dim, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && masks) e = hipMemcpyAsync(c->d_mask, masks, N * O, hipMemcpyHostToDevice, s);
@@ -195,11 +192,6 @@ int fdnn_debug_forward_taps(fdnn_model *m, const float *x, int n, const int8_t *
   fetch(logits, t.logits, sizeof(float) * N * O);
   fetch(probs, c->d_out, sizeof(float) * N * O);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(t.l0_lin);
-  hipFree(t.u8_acts);
-  hipFree(t.acc_hid);
-  hipFree(t.acc_out);
-  hipFree(t.logits);
   fdnn_ctx_free(c);
   if (rc) return rc;
   if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("taps: ") + hipGetErrorString(e));
@@ -230,7 +222,9 @@ int fdnn_debug_production_acc_out(fdnn_model *m, const float *x, int n, int stri
   Taps t{};  // only the probe: hidden layers and output layer run their production instances
   t.probe_stride = stride;
   hipStream_t s = c->stream;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&t.acc_probe), sizeof(int32_t) * NP * O);
+  fdnn::DevBuf<int32_t> d_probe;
+  hipError_t e = d_probe.reserve(NP * O);
+  t.acc_probe = d_probe;
   if (e == hipSuccess) e = hipMemsetAsync(t.acc_probe, 0xff, sizeof(int32_t) * NP * O, s);
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_x, x, sizeof(float) * N * h.in_dim, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && masks) e = hipMemcpyAsync(c->d_mask, masks, N * O, hipMemcpyHostToDevice, s);
@@ -241,7 +235,6 @@ int fdnn_debug_production_acc_out(fdnn_model *m, const float *x, int n, int stri
   if (e == hipSuccess && !rc) e = hipMemcpyAsync(acc, t.acc_probe, sizeof(int32_t) * NP * O, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && !rc && probs) e = hipMemcpyAsync(probs, c->d_out, sizeof(float) * N * O, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(t.acc_probe);
   fdnn_ctx_free(c);
   if (rc) return rc;
   if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string("acc probe: ") + hipGetErrorString(e));
@@ -284,10 +277,10 @@ static int debug_layer0(fdnn_model *m, const float *x, int n, uint8_t *u8_out, f
   unsigned long long before[2] = {0, 0}, after[2] = {0, 0};
   hipError_t e = hipSuccess;
   if (screen) {
-    e = hipMalloc(reinterpret_cast<void **>(&c->d_l0_dbg_t), outs * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->d_l0_dbg_dd), outs * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(c->d_l0_dbg_t, 0xff, outs * sizeof(float));  // NaN: an output the screening kernel did not visit
-    if (e == hipSuccess) e = hipMemset(c->d_l0_dbg_dd, 0xff, outs * sizeof(float));
+    e = c->d_l0_dbg_t.reserve(outs);
+    if (e == hipSuccess) e = c->d_l0_dbg_dd.reserve(outs);
+    if (e == hipSuccess) e = c->d_l0_dbg_t.fill(0xff);  // NaN: an output the screening kernel did not visit
+    if (e == hipSuccess) e = c->d_l0_dbg_dd.fill(0xff);
     if (e == hipSuccess) e = hipDeviceSynchronize();
   }
   if (e == hipSuccess) e = hipMemcpy(before, m->d_l0_stats, sizeof(before), hipMemcpyDeviceToHost);

@@ -325,6 +325,7 @@ int fdnn_group_load(const char *path, float cutoff, const int *devices, int n_de
   g->bcast = "none";
   const size_t bytes = leader->hm.blob.size();
   // staging buffers for the received blob on every peer (the leader's own d_blob is the source)
+  std::vector<fdnn::DevBuf<uint8_t>> peer_bufs(static_cast<size_t>(n_devices));  // ([0] stays empty)
   std::vector<void *> bufs(size_t(n_devices), nullptr);
   bufs[0] = leader->d_blob;
   hipError_t e = hipSuccess;
@@ -334,7 +335,7 @@ int fdnn_group_load(const char *path, float cutoff, const int *devices, int n_de
       e = hipErrorInvalidDevice;
       break;
     }
-    e = hipMalloc(&bufs[size_t(i)], bytes);
+    if ((e = peer_bufs[size_t(i)].reserve(bytes)) == hipSuccess) bufs[size_t(i)] = peer_bufs[size_t(i)];
   }
   const char *mode = std::getenv("FDNN_GROUP_BCAST");
   const bool want_rccl = mode && std::strcmp(mode, "rccl") == 0;
@@ -370,9 +371,9 @@ int fdnn_group_load(const char *path, float cutoff, const int *devices, int n_de
     }
   }
   for (int i = 1; i < n_devices; ++i)
-    if (bufs[size_t(i)]) {
+    if (peer_bufs[size_t(i)]) {
       DeviceGuard dg(devices[i]);
-      hipFree(bufs[size_t(i)]);
+      peer_bufs[size_t(i)].release();
     }
   if (rc) {
     fdnn_group_free(g);

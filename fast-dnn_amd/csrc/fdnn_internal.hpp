@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/fdnn.h"
+#include "fdnn_buf.hpp"
 #include "fdnn_kernels.hpp"
 #include "fdnn_model.hpp"
 #include "fdnn_splice_spec.hpp"  // SpliceSpec, SpliceRef, SpliceSeg, splice_halo
@@ -47,18 +48,18 @@ struct DeviceGuard {
 struct fdnn_model {
   fdnn::HostModel hm;  // header + host copy of the blob (kept: export, host queries)
   int device = 0;
-  uint8_t *d_blob = nullptr;
-  float *d_w0t = nullptr;  // layer-0 weights as a chain-major image [4][l0_j_pad][l0_h_ld] (fdnn_l0.hip)
-  float *d_w0norm = nullptr;  // [H] ||w_n||_2 rounded up: the node half of the screened layer-0 path's bound
-  int8_t *d_w0d = nullptr;    // int8 screening (fdnn_l0s.hip): the layer-0 weights as three int8 digit planes, MFMA fragment order
-  float *d_w0stat = nullptr;  // [3][l0_h_ld]: 2^8 / c_n, ||w_n||_2, 2^8 b_n
-  uint32_t *d_lutpair = nullptr;  // the sigmoid table as (round-down, round-up) byte pairs
+  fdnn::DevBuf<uint8_t> d_blob;
+  fdnn::DevBuf<float> d_w0t;  // layer-0 weights as a chain-major image [4][l0_j_pad][l0_h_ld] (fdnn_l0.hip)
+  fdnn::DevBuf<float> d_w0norm;  // [H] ||w_n||_2 rounded up: the node half of the screened layer-0 path's bound
+  fdnn::DevBuf<int8_t> d_w0d;    // int8 screening (fdnn_l0s.hip): the layer-0 weights as three int8 digit planes, MFMA fragment order
+  fdnn::DevBuf<float> d_w0stat;  // [3][l0_h_ld]: 2^8 / c_n, ||w_n||_2, 2^8 b_n
+  fdnn::DevBuf<uint32_t> d_lutpair;  // the sigmoid table as (round-down, round-up) byte pairs
   // the device side of "is somebody else scoring on this GPU?".  A fused soft-max workgroup that
   // sits out its bounded wait (tens of milliseconds: its frame tile's siblings were kept off the chip) raises this
   // host-mapped word; from the next call on the model runs the scale-pass path, for good, and says so once.
-  unsigned long long *h_fuse_fault = nullptr, *d_fuse_fault = nullptr;
+  fdnn::Mapped<unsigned long long> h_fuse_fault;  // (.dev: what the kernels get; null where the allocation was refused)
   bool fuse_fault_said = false;
-  unsigned long long *d_l0_stats = nullptr;  // [4] device counters: [1] layer-0 outputs recomputed exactly, [2] fused soft-max tiles that gave up waiting
+  fdnn::DevBuf<unsigned long long> d_l0_stats;  // [4] device counters: [1] layer-0 outputs recomputed exactly, [2] fused soft-max tiles that gave up waiting
   int l0_jc = 0, l0_j_pad = 0, l0_h_ld = 0;
   int l0_fma = 0;
   int l0_kernel = 0;  // fdnn_debug_set_l0_kernel
@@ -89,42 +90,36 @@ struct fdnn_ctx {
   bool done_pending = false;      // work went to done_stream -- a stream that outlives this context's use of it (see
                                   // stream_is_durable) -- after the last record: recorded when ANOTHER stream asks (ctx_enter)
   hipStream_t durable[3] = {nullptr, nullptr, nullptr};  // streams of the context's owner (the scoring loop's), besides `stream`
-  float *d_x = nullptr;           // [n][D]
-  float *d_raw = nullptr;         // raw feature frames of the *_raw entry points (first raw call allocates)
-  size_t raw_cap = 0;             // ... floats
-  float *d_xt = nullptr;          // [4][l0_j_pad][xt_ld] layer-0 frame image (shifted, scaled, chain-major)
+  fdnn::DevBuf<float> d_x;        // [n][D]
+  fdnn::DevBuf<float> d_raw;      // raw feature frames of the *_raw entry points (first raw call allocates)
+  fdnn::DevBuf<float> d_xt;       // [4][l0_j_pad][xt_ld] layer-0 frame image (shifted, scaled, chain-major)
   int xt_ld = 0;
-  float *d_l0park = nullptr;      // [xt_ld][l0_h_ld] partial chain sums parked by the layer-0 kernel
-  uint32_t *d_scr_count = nullptr;  // [frame tiles x node tiles] flagged outputs per tile (kept zero between launches)
-  uint16_t *d_scr_list = nullptr;   // [tiles][kL0ScreenCap]
-  int8_t *d_xd = nullptr;           // int8 screening: the frames' digit planes [chunks][3][xt_ld / 32][1024]
-  float *d_xstat = nullptr;         // [3][xt_ld] row constants written by the pre-pass
-  uint2 *d_glist = nullptr;         // int8 screening: {frame, node} of the launch's flagged outputs
-  uint32_t *d_glist_count = nullptr;  // [2] entries appended, tiles in the whole-tile path
-  int glist_cap = 0;
-  int8_t *d_act[2] = {nullptr, nullptr};  // [n_pad][act_ld] ping/pong, s8 = u8-128
-  float *d_out = nullptr;         // [n][O]
-  float *d_partial = nullptr;     // [rows_pad/64][n_pad]
-  int8_t *d_mask = nullptr;       // [n][O]
-  float *d_fuse_s = nullptr;        // fused soft-max: per-tile row sums [n_pad / tile][rows_pad / 256][tile] floats
-  uint32_t *d_fuse_cnt = nullptr;   // {arrived part 0 .., left at [7]} per frame tile; zero between launches
-  size_t fuse_cnt_bytes = 0, fuse_flag_bytes = 0;
-  uint32_t *d_fuse_flag = nullptr;  // per tile: parts a workgroup left unscaled ("gave up waiting"); zero between launches
-  uint32_t *d_chain_ctl = nullptr;   // chained hidden layers (fdnn_chain.hip): queue heads [0..7], workgroups that left [8]
-  uint32_t *d_chain_done = nullptr;  // [frame tiles][layers of the chain] node tiles finished; zero between launches
-  long long *d_chain_clk = nullptr;  // measurement builds only: per-task phase clocks
+  fdnn::DevBuf<float> d_l0park;   // [xt_ld][l0_h_ld] partial chain sums parked by the layer-0 kernel
+  fdnn::DevBuf<uint32_t> d_scr_count;  // [frame tiles x node tiles] flagged outputs per tile (kept zero between launches)
+  fdnn::DevBuf<uint16_t> d_scr_list;   // [tiles][kL0ScreenCap]
+  fdnn::DevBuf<int8_t> d_xd;        // int8 screening: the frames' digit planes [chunks][3][xt_ld / 32][1024]
+  fdnn::DevBuf<float> d_xstat;      // [3][xt_ld] row constants written by the pre-pass
+  fdnn::DevBuf<uint2> d_glist;      // int8 screening: {frame, node} of the launch's flagged outputs
+  fdnn::DevBuf<uint32_t> d_glist_count;  // [2] entries appended, tiles in the whole-tile path
+  fdnn::DevBuf<int8_t> d_act[2];  // [n_pad][act_ld] ping/pong, s8 = u8-128
+  fdnn::DevBuf<float> d_out;      // [n][O]
+  fdnn::DevBuf<float> d_partial;  // [rows_pad/64][n_pad]
+  fdnn::DevBuf<int8_t> d_mask;    // [n][O]
+  fdnn::DevBuf<float> d_fuse_s;     // fused soft-max: per-tile row sums [n_pad / tile][rows_pad / 256][tile] floats
+  fdnn::DevBuf<uint32_t> d_fuse_cnt;   // {arrived part 0 .., left at [7]} per frame tile; zero between launches
+  fdnn::DevBuf<uint32_t> d_fuse_flag;  // per tile: parts a workgroup left unscaled ("gave up waiting"); zero between launches
+  fdnn::DevBuf<uint32_t> d_chain_ctl;   // chained hidden layers (fdnn_chain.hip): queue heads [0..7], workgroups that left [8]
+  fdnn::DevBuf<uint32_t> d_chain_done;  // [frame tiles][layers of the chain] node tiles finished; zero between launches
+  fdnn::DevBuf<long long> d_chain_clk;  // measurement builds only: 8 words + 10 phase clocks per task (fdnn_debug_chain_clocks)
   // A chained launch whose wait ran into its bound has computed on rows that may not have been written: it raises this
   // host-visible word (fine-grained pinned memory, plain store from the kernel).  run_hidden looks at it before every
   // launch -- counters re-zeroed, the context never chains again -- and the calls that synchronise anyway re-run the pass.
-  unsigned long long *h_chain_fault = nullptr, *d_chain_fault = nullptr;
+  fdnn::Mapped<unsigned long long> h_chain_fault;
   bool chain_broken = false;
-  size_t chain_done_bytes = 0;
-  int chain_clk_cap = 0;
-  float *d_l0_dbg_t = nullptr, *d_l0_dbg_dd = nullptr;  // fdnn_debug_layer0_screen only: the int8 screening's t~ and Dd per output
-  uint64_t *d_mask_bits = nullptr;  // [n][ceil(O/64)] the batched lazy call's mask as bits (launch_mask_pack)
+  fdnn::DevBuf<float> d_l0_dbg_t, d_l0_dbg_dd;  // fdnn_debug_layer0_screen only: the int8 screening's t~ and Dd per output
+  fdnn::DevBuf<uint64_t> d_mask_bits;  // [n][ceil(O/64)] the batched lazy call's mask as bits (launch_mask_pack)
   bool mask_bits_packed = false;    // run_output has packed the current call's byte masks into d_mask_bits
-  float *d_comp = nullptr;          // host lazy batches: compacted result rows (allocated on first use)
-  size_t comp_floats = 0;
+  fdnn::DevBuf<float> d_comp;       // host lazy batches: compacted result rows (allocated on first use)
   int last = -1;                  // d_act index holding the last hidden layer, -1 = not computed
   bool pooled = false;
   bool no_fuse = false;           // this call must not use the fused soft-max
@@ -134,10 +129,9 @@ struct fdnn_ctx {
   // per-frame lazy calls (the JNI contract): host-mapped pinned staging for kPinFrames masks and
   // result rows -- the output kernel reads the mask and the scale kernel writes the probabilities
   // straight through these, so a call is two launches and one stream sync, no copy commands
-  int8_t *h_mask_pin = nullptr, *d_mask_pin = nullptr;
-  float *h_out_pin = nullptr, *d_out_pin = nullptr;
+  fdnn::Mapped<int8_t> h_mask_pin;
+  fdnn::Mapped<float> h_out_pin;
 };
-constexpr int kPinFrames = 8;
 
 
 namespace fdnn {

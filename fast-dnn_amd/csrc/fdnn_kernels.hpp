@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "fdnn_ctx_layout.hpp"  // kMaxFrameTile, kPartialNodes, kL0ScreenCap, l0_split_plane_bytes
 #include "fdnn_note.hpp"
 #include "fdnn_select.hpp"
 
@@ -26,9 +27,6 @@
 #endif
 
 namespace fdnn {
-
-constexpr int kMaxFrameTile = 320;  // largest GEMM frame tile; scratch rows carry this much slack
-constexpr int kPartialNodes = 64;   // nodes covered by one soft-max partial sum
 
 // Layer 0: shift/scale + fp32 affine + bias + sigmoid LUT -> s8 activations.
 struct L0Params {
@@ -73,11 +71,9 @@ struct L0Params {
   float *dbg_t;
   float *dbg_dd;
 };
-constexpr int kL0ScreenCap = 4096;  // listed outputs per tile (25 %); a tile that overflows is recomputed whole
 void launch_l0(const L0Params &p, const sel::L0Choice &ch, hipStream_t s);  // ch = sel::choose_l0
-// fdnn_l0s.hip: bytes of one operand's digit planes; the node half (host code, model load); pre-pass + matrix kernel
+// fdnn_l0s.hip: the node half (host code, model load); pre-pass + matrix kernel
 // (launch_l0 follows with the exact recomputation of the flagged outputs)
-size_t l0_split_plane_bytes(int D, int rows_ld);
 void launch_l0_split(const L0Params &p, int wn_cfg, hipStream_t s);
 void l0_split_build_weights(const float *w, const float *wnorm, const uint8_t *lut2, int H, int D, int h_ld, std::vector<int8_t> *planes,
                             std::vector<float> *stat, std::vector<uint32_t> *half);

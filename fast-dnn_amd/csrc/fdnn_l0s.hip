@@ -596,9 +596,7 @@ __global__ __launch_bounds__(256 * WN, 3 - WN) void l0_split_kernel(L0Params p, 
 }  // namespace
 
 // chains are padded to whole chunk PAIRS (the kernel alternates two fragment register sets): 432 -> 4 x 128 positions, 16 chunks
-int l0_split_chain_pad(int D) { return (D / 4 + 63) / 64 * 64; }
-int l0_split_chunks(int D) { return 4 * l0_split_chain_pad(D) / 32; }
-size_t l0_split_plane_bytes(int D, int rows_ld) { return static_cast<size_t>(l0_split_chunks(D)) * 3 * static_cast<size_t>(rows_ld / 32) * 1024; }
+// (l0_split_chain_pad, l0_split_chunks, l0_split_plane_bytes: fdnn_ctx_layout.hpp, where the context sizes its planes with them)
 size_t l0_split_half_bytes() { return (4 * size_t(kLut2Size) + 15) & ~size_t(15); }
 
 // Model load: the node half.  w [H][D] fp32 -> digit planes in fragment order + per-node constants {r_n, ||w||_2 (the
@@ -666,6 +664,7 @@ void l0_split_build_weights(const float *w, const float *wnorm, const uint8_t *l
 
 // pre-pass + matrix kernel; the caller (fdnn_l0.hip: launch_l0) follows with l0_fix_kernel on the same tile lists
 static_assert(kSTF == 128, "fdnn_select.hpp: choose_l0 counts this kernel's 128-frame tiles");
+static_assert(kSTF == kL0TileFrames, "fdnn_ctx_layout.hpp counts the planes' rows and the per-tile counters in these tiles");
 // wn_cfg: 1 = 64-node tiles, 2 = 128-node tiles (fdnn_select.hpp: choose_l0)
 void launch_l0_split(const L0Params &p, int wn_cfg, hipStream_t s) {
   const int KC = l0_split_chunks(p.D), J = p.D / 4, JP = l0_split_chain_pad(p.D);

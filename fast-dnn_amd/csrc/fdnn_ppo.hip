@@ -729,6 +729,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(96))) void q
 }  // namespace
 
 static_assert(kFT == sel::kPpFrameTile && kBM == sel::kPpNodeTile && kKT * kBK == sel::kPpK && kMT == sel::kPpoNodeTiles, "fdnn_select.hpp states this kernel's sizes");
+static_assert(kHT == kPpoHalfFrames && 2 * kHT == kFT, "fdnn_ctx_layout.hpp sizes the row sums and counters of a half with these");
 
 void launch_qppo_output(const QGemmParams &p, int n_cu, hipStream_t s) {
   auto k = qppo_kernel<false>;

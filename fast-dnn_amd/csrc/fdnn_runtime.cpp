@@ -49,11 +49,11 @@ int upload_model(fdnn_model *m) {
   if (m->device < 0 || m->device >= count) return fail(FDNN_E_ARG, "device index out of range");
   DeviceGuard g(m->device);
   if (!g.ok) return fail(FDNN_E_DEVICE, "hipSetDevice failed");
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_blob), m->hm.blob.size()));
+  HIP_TRY(m->d_blob.reserve(m->hm.blob.size()));
   // exhaustive validation of the 3-op division per layer (see dequant() in fdnn_kernels.hip)
-  unsigned long long *d_bad = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_bad), sizeof(unsigned long long) * fdnn::kMaxQLayers));
-  HIP_TRY(hipMemset(d_bad, 0, sizeof(unsigned long long) * fdnn::kMaxQLayers));
+  DevBuf<unsigned long long> d_bad;
+  HIP_TRY(d_bad.reserve(fdnn::kMaxQLayers));
+  HIP_TRY(d_bad.fill(0));
   BlobHeader &h = m->hm.hdr;
   for (int qi = 0; qi < h.n_q; ++qi) {
     // same coefficient as an earlier layer -> same verdict, skip the sweep
@@ -65,7 +65,6 @@ int upload_model(fdnn_model *m) {
   }
   unsigned long long bad[fdnn::kMaxQLayers];
   HIP_TRY(hipMemcpy(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
-  HIP_TRY(hipFree(d_bad));
   for (int qi = 0; qi < h.n_q; ++qi) {
     int src = qi;
     for (int pj = 0; pj < qi; ++pj)
@@ -87,7 +86,7 @@ int build_l0_image(fdnn_model *m) {
   m->l0_jc = fdnn::l0_chunk_rows(h.in_dim);
   m->l0_j_pad = round_up(h.in_dim / 4, m->l0_jc);
   m->l0_h_ld = round_up(h.hidden, 128);
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_w0t), sizeof(float) * 4 * size_t(m->l0_j_pad) * m->l0_h_ld));
+  HIP_TRY(m->d_w0t.reserve(4 * size_t(m->l0_j_pad) * m->l0_h_ld));
   fdnn::launch_l0_weight_image(reinterpret_cast<const float *>(m->d_blob + h.off_w0), m->d_w0t, h.hidden, h.in_dim, m->l0_j_pad,
                                m->l0_h_ld, nullptr);
   HIP_TRY(hipGetLastError());
@@ -104,29 +103,24 @@ int build_l0_image(fdnn_model *m) {
       if (double(f) < up) f = std::nextafter(f, std::numeric_limits<float>::infinity());
       wn[size_t(i)] = f;  // inf / NaN weights stay inf / NaN: every output of that node is then recomputed exactly
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_w0norm), sizeof(float) * wn.size()));
+    HIP_TRY(m->d_w0norm.reserve(wn.size()));
     HIP_TRY(hipMemcpy(m->d_w0norm, wn.data(), sizeof(float) * wn.size(), hipMemcpyHostToDevice));
     if (sel::l0_split_ok(h.in_dim, h.hidden)) {  // the node half of the int8 screening (fdnn_l0s.hip): digit planes + constants
       std::vector<int8_t> planes;
       std::vector<float> stat;
       std::vector<uint32_t> pairs;
       fdnn::l0_split_build_weights(w0, wn.data(), m->hm.blob.data() + h.off_lut2, h.hidden, h.in_dim, m->l0_h_ld, &planes, &stat, &pairs);
-      HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_lutpair), sizeof(uint32_t) * pairs.size()));
+      HIP_TRY(m->d_lutpair.reserve(pairs.size()));
       HIP_TRY(hipMemcpy(m->d_lutpair, pairs.data(), sizeof(uint32_t) * pairs.size(), hipMemcpyHostToDevice));
-      HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_w0d), planes.size()));
+      HIP_TRY(m->d_w0d.reserve(planes.size()));
       HIP_TRY(hipMemcpy(m->d_w0d, planes.data(), planes.size(), hipMemcpyHostToDevice));
-      HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_w0stat), sizeof(float) * stat.size()));
+      HIP_TRY(m->d_w0stat.reserve(stat.size()));
       HIP_TRY(hipMemcpy(m->d_w0stat, stat.data(), sizeof(float) * stat.size(), hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_l0_stats), 32 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(m->d_l0_stats, 0, 32 * sizeof(unsigned long long)));
-    if (hipHostMalloc(reinterpret_cast<void **>(&m->h_fuse_fault), sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
-      *m->h_fuse_fault = 0;
-      if (hipHostGetDevicePointer(reinterpret_cast<void **>(&m->d_fuse_fault), m->h_fuse_fault, 0) != hipSuccess) m->d_fuse_fault = nullptr;
-    } else {
-      (void)hipGetLastError();
-      m->h_fuse_fault = nullptr;
-    }
+    HIP_TRY(m->d_l0_stats.reserve(32));
+    HIP_TRY(m->d_l0_stats.fill(0));
+    if (m->h_fuse_fault.reserve(1) != hipSuccess) (void)hipGetLastError();  // refused: stays null, the model goes on without
+    if (m->h_fuse_fault) *m->h_fuse_fault.p = 0;
   }
   HIP_TRY(hipDeviceSynchronize());
   return FDNN_OK;
@@ -134,39 +128,11 @@ int build_l0_image(fdnn_model *m) {
 
 void destroy_ctx(fdnn_ctx *c) {
   if (!c) return;
-  DeviceGuard g(c->m->device);
+  DeviceGuard g(c->m->device);  // (for the buffers' destructors too)
   if (c->stream) {
     fuse_chain_retire_stream(c->m->device, c->stream);
     hipStreamSynchronize(c->stream);
   }
-  hipFree(c->d_x);
-  hipFree(c->d_raw);
-  hipFree(c->d_xt);
-  hipFree(c->d_l0park);
-  hipFree(c->d_scr_count);
-  hipFree(c->d_xd);
-  hipFree(c->d_xstat);
-  hipFree(c->d_comp);
-  hipFree(c->d_glist);
-  hipFree(c->d_glist_count);
-  hipFree(c->d_scr_list);
-  hipFree(c->d_act[0]);
-  hipFree(c->d_act[1]);
-  hipFree(c->d_out);
-  hipFree(c->d_partial);
-  hipFree(c->d_mask);
-  hipFree(c->d_mask_bits);
-  hipFree(c->d_fuse_s);
-  hipFree(c->d_fuse_cnt);
-  hipFree(c->d_fuse_flag);
-  hipFree(c->d_chain_ctl);
-  hipFree(c->d_chain_done);
-  hipFree(c->d_chain_clk);
-  if (c->h_chain_fault) hipHostFree(c->h_chain_fault);
-  hipFree(c->d_l0_dbg_t);
-  hipFree(c->d_l0_dbg_dd);
-  if (c->h_mask_pin) hipHostFree(c->h_mask_pin);
-  if (c->h_out_pin) hipHostFree(c->h_out_pin);
   if (c->done) hipEventDestroy(c->done);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
@@ -176,78 +142,56 @@ int make_ctx(fdnn_model *m, int n, fdnn_ctx **out, bool lean) {
   DeviceGuard g(m->device);
   if (!g.ok) return fail(FDNN_E_DEVICE, "hipSetDevice failed");
   const BlobHeader &h = m->hm.hdr;
+  int max_rows_pad = 0;
+  for (int qi = 0; qi < h.n_q; ++qi) max_rows_pad = std::max(max_rows_pad, h.q[qi].rows_pad);
+  const CtxLayout l = ctx_layout({h.in_dim, h.hidden, h.out_dim, max_rows_pad, m->l0_j_pad, m->l0_h_ld, m->d_w0d != nullptr,
+                                  sel::tuning().l0_chain_tn, m->l0_list_cap, lean, n});
   fdnn_ctx *c = new fdnn_ctx();
   c->m = m;
   c->n = n;
-  c->cap = round_up(std::max(n, 1), 64);
-  c->act_ld = round_up(h.hidden, fdnn::kColPad) + fdnn::kRowSkew;
-  int max_rows_pad = 0;
-  for (int qi = 0; qi < h.n_q; ++qi) {
-    max_rows_pad = std::max(max_rows_pad, h.q[qi].rows_pad);
-  }
-  const size_t np = size_t(c->cap);
-  // the GEMMs work on whole frame tiles: every frame-indexed scratch carries one
-  // tile of slack rows (a launch covers [first, first + round_up(count, tile)))
-  const size_t npt = np + fdnn::kMaxFrameTile;
+  c->cap = l.cap;
+  c->act_ld = l.act_ld;
+  c->xt_ld = l.xt_ld;
   hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 16);
+  // one allocation per buffer, in this order; an empty one still gets 16 bytes
+  auto alloc = [&](auto &buf, size_t count) {
+    if (e == hipSuccess) e = buf.reserve(count ? count : 16 / sizeof(*buf.p));
   };
-  if (!lean) alloc(reinterpret_cast<void **>(&c->d_x), sizeof(float) * np * h.in_dim);
-  c->xt_ld = round_up(c->cap, 128);
-  alloc(reinterpret_cast<void **>(&c->d_xt), sizeof(float) * 4 * size_t(m->l0_j_pad) * c->xt_ld);
-  {  // screened layer-0 path: the per-tile lists of outputs to recompute exactly
-    const size_t tiles = size_t(c->xt_ld / 64) * size_t((h.hidden + 127) / 128);  // 64- or 128-frame x 128-node screening tiles
-    alloc(reinterpret_cast<void **>(&c->d_scr_count), sizeof(uint32_t) * tiles);
-    alloc(reinterpret_cast<void **>(&c->d_scr_list), sizeof(uint16_t) * tiles * fdnn::kL0ScreenCap);
-    if (e == hipSuccess) e = hipMemset(c->d_scr_count, 0, sizeof(uint32_t) * tiles);
+  auto zero = [&](auto &buf, size_t count) {  // (a counter array the kernels keep zero; nothing for an empty one)
+    if (e == hipSuccess) e = hipMemset(buf, 0, sizeof(*buf.p) * count);
+  };
+  if (!lean) alloc(c->d_x, l.x);
+  alloc(c->d_xt, l.xt);
+  alloc(c->d_scr_count, l.scr_count);
+  alloc(c->d_scr_list, l.scr_list);
+  zero(c->d_scr_count, l.scr_count);
+  if (m->d_w0d) {
+    alloc(c->d_xd, l.xd);
+    alloc(c->d_xstat, l.xstat);
+    alloc(c->d_glist, size_t(l.glist_cap));
+    alloc(c->d_glist_count, l.glist_count);
+    zero(c->d_glist, size_t(l.glist_cap));
+    zero(c->d_glist_count, l.glist_count);
   }
-  if (m->d_w0d) {  // int8 screening: the frames' digit planes and row constants
-    alloc(reinterpret_cast<void **>(&c->d_xd), fdnn::l0_split_plane_bytes(h.in_dim, c->xt_ld));
-    alloc(reinterpret_cast<void **>(&c->d_xstat), sizeof(float) * 3 * size_t(c->xt_ld));
-    c->glist_cap = int(std::min<size_t>(size_t(c->xt_ld) * size_t(m->l0_h_ld) / 16, size_t(1) << 26));  // 6 % of the outputs
-    if (m->l0_list_cap > 0) c->glist_cap = std::min(c->glist_cap, m->l0_list_cap);  // (tests: fdnn_debug_set_l0_list_cap)
-    alloc(reinterpret_cast<void **>(&c->d_glist), sizeof(uint2) * size_t(c->glist_cap));
-    alloc(reinterpret_cast<void **>(&c->d_glist_count), sizeof(uint32_t) * 2);
-    if (e == hipSuccess) e = hipMemset(c->d_glist, 0, sizeof(uint2) * size_t(c->glist_cap));
-    if (e == hipSuccess) e = hipMemset(c->d_glist_count, 0, sizeof(uint32_t) * 2);
-  }
-  if (sel::tuning().l0_chain_tn == 128)  // the 64-node tile keeps its partial sums in registers
-    alloc(reinterpret_cast<void **>(&c->d_l0park), sizeof(float) * size_t(c->xt_ld) * m->l0_h_ld);
-  alloc(reinterpret_cast<void **>(&c->d_act[0]), npt * c->act_ld);
-  alloc(reinterpret_cast<void **>(&c->d_act[1]), npt * c->act_ld);
-  if (!lean) alloc(reinterpret_cast<void **>(&c->d_out), sizeof(float) * np * h.out_dim);
-  alloc(reinterpret_cast<void **>(&c->d_partial), sizeof(float) * npt * (max_rows_pad / fdnn::kPartialNodes));
-  if (!lean) alloc(reinterpret_cast<void **>(&c->d_mask), np * h.out_dim);
-  alloc(reinterpret_cast<void **>(&c->d_mask_bits), sizeof(uint64_t) * np * size_t((h.out_dim + 63) / 64));
-  {  // fused soft-max (large dense batches): row sums per 256-node tile, counters and flags per tile (kept zero between launches)
-    const size_t mt = size_t(max_rows_pad / 256), tiles = npt / 128 + 2;  // frame tiles of 128 frames and up
-    alloc(reinterpret_cast<void **>(&c->d_fuse_s), sizeof(float) * npt * mt);
-    alloc(reinterpret_cast<void **>(&c->d_fuse_cnt), sizeof(uint32_t) * 8 * tiles);
-    alloc(reinterpret_cast<void **>(&c->d_fuse_flag), sizeof(uint32_t) * tiles * mt);
-    c->fuse_cnt_bytes = sizeof(uint32_t) * 8 * tiles;
-    c->fuse_flag_bytes = sizeof(uint32_t) * tiles * mt;
-    if (e == hipSuccess) e = hipMemset(c->d_fuse_cnt, 0, sizeof(uint32_t) * 8 * tiles);
-    if (e == hipSuccess) e = hipMemset(c->d_fuse_flag, 0, sizeof(uint32_t) * tiles * mt);
-  }
-  {  // chained hidden layers: queue heads + leave counter, per frame tile and layer the finished node tiles (zero between launches)
-    const size_t tiles = npt / 256 + 2;
-    alloc(reinterpret_cast<void **>(&c->d_chain_ctl), sizeof(uint32_t) * 16);
-    alloc(reinterpret_cast<void **>(&c->d_chain_done), sizeof(uint32_t) * tiles * fdnn::kMaxChainLayers);
-    c->chain_done_bytes = sizeof(uint32_t) * tiles * fdnn::kMaxChainLayers;
-    if (e == hipSuccess) e = hipMemset(c->d_chain_ctl, 0, sizeof(uint32_t) * 16);
-    if (e == hipSuccess) e = hipMemset(c->d_chain_done, 0, sizeof(uint32_t) * tiles * fdnn::kMaxChainLayers);
-    if (e == hipSuccess && hipHostMalloc(reinterpret_cast<void **>(&c->h_chain_fault), sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
-      *c->h_chain_fault = 0;
-      if (hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_chain_fault), c->h_chain_fault, 0) != hipSuccess) c->d_chain_fault = nullptr;
-    }
-  }
-  if (e == hipSuccess && !lean)  // (at least one padded row of slack)
-    e = hipHostMalloc(reinterpret_cast<void **>(&c->h_mask_pin), std::max(size_t(kPinFrames) * h.out_dim, size_t(max_rows_pad)), hipHostMallocMapped);
-  if (e == hipSuccess && !lean) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_mask_pin), c->h_mask_pin, 0);
-  if (e == hipSuccess && !lean)
-    e = hipHostMalloc(reinterpret_cast<void **>(&c->h_out_pin), sizeof(float) * kPinFrames * h.out_dim, hipHostMallocMapped);
-  if (e == hipSuccess && !lean) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_out_pin), c->h_out_pin, 0);
+  if (l.l0park) alloc(c->d_l0park, l.l0park);
+  alloc(c->d_act[0], l.act);
+  alloc(c->d_act[1], l.act);
+  if (!lean) alloc(c->d_out, l.out);
+  alloc(c->d_partial, l.partial);
+  if (!lean) alloc(c->d_mask, l.mask);
+  alloc(c->d_mask_bits, l.mask_bits);
+  alloc(c->d_fuse_s, l.fuse_s);
+  alloc(c->d_fuse_cnt, l.fuse_cnt);
+  alloc(c->d_fuse_flag, l.fuse_flag);
+  zero(c->d_fuse_cnt, l.fuse_cnt);
+  zero(c->d_fuse_flag, l.fuse_flag);
+  alloc(c->d_chain_ctl, l.chain_ctl);
+  alloc(c->d_chain_done, l.chain_done);
+  zero(c->d_chain_ctl, l.chain_ctl);
+  zero(c->d_chain_done, l.chain_done);
+  if (e == hipSuccess && c->h_chain_fault.reserve(1) == hipSuccess) *c->h_chain_fault.p = 0;  // (refused: stays null, nobody listens)
+  if (e == hipSuccess && !lean) e = c->h_mask_pin.reserve(l.mask_pin);
+  if (e == hipSuccess && !lean) e = c->h_out_pin.reserve(l.out_pin);
   // The hipMemsets above are ordered on the NULL stream and return before they have run; the context's kernels go to
   // non-blocking streams, which do not wait for it.  Without this wait a new context's first kernels could start first and
   // have their counters (flagged-output list, fused soft-max arrivals) zeroed under them: a partly walked list -- a few
@@ -385,7 +329,7 @@ void run_layer0(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) 
   l0.luthalf = m->d_lutpair;
   l0.glist = c->d_glist;
   l0.glist_count = c->d_glist_count;
-  l0.glist_cap = c->glist_cap;
+  l0.glist_cap = int(c->d_glist.count);
   l0.dbg_t = c->d_l0_dbg_t;
   l0.dbg_dd = c->d_l0_dbg_dd;
   l0.j_pad = m->l0_j_pad;
@@ -414,10 +358,10 @@ int run_hidden(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) {
   // (advisor, round 5) a chained launch of this context ran into its wait bound: its counters are dirty and its results
   // were wrong.  Re-zero the counters in stream order and never chain on this context again; the host-synchronising dense
   // call re-runs its pass (calculate_on_one_device), the others observe fdnn_model_chain_faults.
-  if (c->h_chain_fault && __atomic_load_n(c->h_chain_fault, __ATOMIC_RELAXED) != 0 && !c->chain_broken) {
+  if (c->h_chain_fault && __atomic_load_n(c->h_chain_fault.p, __ATOMIC_RELAXED) != 0 && !c->chain_broken) {
     c->chain_broken = true;
-    (void)hipMemsetAsync(c->d_chain_ctl, 0, sizeof(uint32_t) * 16, s);
-    (void)hipMemsetAsync(c->d_chain_done, 0, c->chain_done_bytes, s);
+    (void)hipMemsetAsync(c->d_chain_ctl, 0, sizeof(uint32_t) * c->d_chain_ctl.count, s);
+    (void)hipMemsetAsync(c->d_chain_done, 0, sizeof(uint32_t) * c->d_chain_done.count, s);
   }
   const sel::Tuning &tune = sel::tuning();
   const int n_cu = device_cus(m->device);
@@ -454,9 +398,9 @@ int run_hidden(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) {
       g.ctl = c->d_chain_ctl;
       g.done = c->d_chain_done;
       g.faults = m->d_l0_stats ? m->d_l0_stats + 3 : nullptr;
-      g.fault_flag = c->d_chain_fault;
+      g.fault_flag = c->h_chain_fault.dev;
       g.clk = c->d_chain_clk;
-      g.clk_cap = c->chain_clk_cap;
+      g.clk_cap = c->d_chain_clk ? int((c->d_chain_clk.count - 8) / 10) : 0;  // [8 + tasks * 10] words
       {
         ProfScope ps(m, s, FDNN_PROF_HIDDEN);
         fdnn::launch_qchain(g, n_cu, s);
@@ -536,7 +480,7 @@ int device_marker_state(int device) {  // 1 = this process owns the device's mar
 }
 // The model's own evidence (see fdnn_model::h_fuse_fault): once a fused launch of this model has given up, it does not fuse again.
 static bool model_may_fuse(fdnn_model *m) {
-  if (!m->h_fuse_fault || __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) == 0) return true;
+  if (!m->h_fuse_fault || __atomic_load_n(m->h_fuse_fault.p, __ATOMIC_RELAXED) == 0) return true;
   if (!m->fuse_fault_said) {
     m->fuse_fault_said = true;
     std::fprintf(stderr,
@@ -641,11 +585,11 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
   g.acc_probe = taps ? taps->acc_probe : nullptr;
   g.probe_stride = taps ? std::max(1, taps->probe_stride) : 1;
   const bool fused = ch.fused, ppo = ch.form == sel::Form::ppo;
-  if (fused && m->h_fuse_fault && __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) != 0) {
+  if (fused && m->h_fuse_fault && __atomic_load_n(m->h_fuse_fault.p, __ATOMIC_RELAXED) != 0) {
     // (fusing although a launch of this model gave up before -- FDNN_FUSE_NORM=1 / fdnn_debug_set_fuse(1): a workgroup that
     // gave up may have left its exchange counters half counted; they are zeroed in stream order before every such launch)
-    HIP_TRY(hipMemsetAsync(c->d_fuse_cnt, 0, c->fuse_cnt_bytes, s));
-    HIP_TRY(hipMemsetAsync(c->d_fuse_flag, 0, c->fuse_flag_bytes, s));
+    HIP_TRY(hipMemsetAsync(c->d_fuse_cnt, 0, sizeof(uint32_t) * c->d_fuse_cnt.count, s));
+    HIP_TRY(hipMemsetAsync(c->d_fuse_flag, 0, sizeof(uint32_t) * c->d_fuse_flag.count, s));
   }
   if (fused) {
     g.final = d_final ? d_final : d_out;
@@ -653,7 +597,7 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
     g.fuse_cnt = c->d_fuse_cnt;
     g.fuse_flag = c->d_fuse_flag;
     g.fuse_giveups = m->d_l0_stats ? m->d_l0_stats + 2 : nullptr;
-    g.fuse_fault = m->d_fuse_fault;
+    g.fuse_fault = m->h_fuse_fault.dev;
     g.fuse_stagger = sel::tuning().fuse_stagger;
   }
   {
@@ -880,7 +824,7 @@ int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
   fdnn_model *m = c->m;
   const int n = c->n;
   const size_t O = size_t(m->hm.hdr.out_dim);
-  const unsigned long long unwritten_before = m->h_fuse_fault ? __atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) >> 32 : 0ull;
+  const unsigned long long unwritten_before = m->h_fuse_fault ? __atomic_load_n(m->h_fuse_fault.p, __ATOMIC_RELAXED) >> 32 : 0ull;
   int rc = run_hidden(c, c->d_x, s, nullptr);
   if (!rc) rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
   if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
@@ -890,7 +834,7 @@ int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
   // same word): the output layer runs again -- unfused now, model_may_fuse has seen the word -- over the activations that
   // are still in the context.  (The word's upper half counts such halves.  Callers of the *_device entry points observe
   // fdnn_model_fuse_giveups after their own synchronisation: INTEGRATION.md.)
-  if (!rc && m->h_fuse_fault && (__atomic_load_n(m->h_fuse_fault, __ATOMIC_RELAXED) >> 32) != unwritten_before) {
+  if (!rc && m->h_fuse_fault && (__atomic_load_n(m->h_fuse_fault.p, __ATOMIC_RELAXED) >> 32) != unwritten_before) {
     const bool saved = c->no_fuse;
     c->no_fuse = true;  // (whatever FDNN_FUSE_NORM says)
     rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
@@ -900,7 +844,7 @@ int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
   }
   // copy_out has synchronised: did this pass's chained launch run into its wait bound?  Then what it computed on may not have
   // been written -- run the pass again, layer by layer (run_hidden sees the flag, re-zeroes the counters, stops chaining)
-  if (!rc && c->h_chain_fault && __atomic_load_n(c->h_chain_fault, __ATOMIC_RELAXED) != 0 && !c->chain_broken) {
+  if (!rc && c->h_chain_fault && __atomic_load_n(c->h_chain_fault.p, __ATOMIC_RELAXED) != 0 && !c->chain_broken) {
     rc = run_hidden(c, c->d_x, s, nullptr);
     if (!rc) rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
     if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
@@ -919,16 +863,10 @@ int splice_check(const SpliceRef &spec, int raw_dim) {
 
 int ctx_raw_reserve(fdnn_ctx *c, size_t frames, int raw_dim) {
   const fdnn_model *m = c->m;
-  if (!c->d_x) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_x), sizeof(float) * size_t(c->cap) * m->hm.hdr.in_dim));
+  if (!c->d_x) HIP_TRY(c->d_x.reserve(size_t(c->cap) * m->hm.hdr.in_dim));
   const size_t D = size_t(raw_dim);  // (a pooled context's last raw call may have had another width)
-  if (c->raw_cap < frames * D) {
-    if (c->d_raw) HIP_TRY(hipFree(c->d_raw));  // (the context's earlier work is ordered before: callers hold it)
-    c->d_raw = nullptr;
-    c->raw_cap = 0;
-    const size_t cap = std::max(frames, size_t(c->cap)) * D;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_raw), sizeof(float) * cap));
-    c->raw_cap = cap;
-  }
+  // (a buffer that is too small is freed first: the context's earlier work is ordered before, callers hold it)
+  if (c->d_raw.count < frames * D) HIP_TRY(c->d_raw.reserve(std::max(frames, size_t(c->cap)) * D));
   return FDNN_OK;
 }
 
@@ -981,13 +919,7 @@ int lazy_copy_out(fdnn_ctx *c, int count, const uint64_t *d_bits, const uint64_t
   }
   const size_t stride = most + 1;
   if (no_compact || stride * 4 > O * 3) return copy_out(out, c->d_out, sizeof(float) * size_t(count) * O, s);
-  if (c->comp_floats < size_t(count) * stride) {
-    if (c->d_comp) HIP_TRY(hipFree(c->d_comp));
-    c->d_comp = nullptr;
-    c->comp_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_comp), sizeof(float) * size_t(count) * stride));
-    c->comp_floats = size_t(count) * stride;
-  }
+  HIP_TRY(c->d_comp.reserve(size_t(count) * stride));
   fdnn::launch_lazy_compact(c->d_out, d_bits, c->d_comp, count, int(O), int(stride), s);
   float *land = out + size_t(count) * O - size_t(count) * stride;
   HIP_TRY(hipMemcpyAsync(land, c->d_comp, sizeof(float) * size_t(count) * stride, hipMemcpyDeviceToHost, s));

@@ -39,6 +39,7 @@
 #include "fdnn_internal.hpp"
 #include "fdnn_server_plan.hpp"
 
+using fdnn::Buf;  // a slot's staging buffers: pinned host memory, or device memory (fdnn_buf.hpp)
 using fdnn::DeviceGuard;
 using fdnn::fail;
 using namespace fdnn::plan;  // Request, Piece, BatchPlan, plan_batch: what a batch contains
@@ -56,42 +57,6 @@ struct TicketState {
   bool closed = false; // the final piece has been packed, or the rest of the request was dropped after a failure
   // a piece is in flight while created > done + failed: wait() does not hand a failed ticket back to its caller before
   // that is over -- the packer still reads the caller's frames and the copy threads still write the caller's rows
-};
-
-// One staging buffer of a slot, pinned host memory or device memory: reserve() grows it, the slot's end frees it.
-template <class T, bool kDevice = false>
-struct Buf {
-  T *p = nullptr;
-  size_t count = 0;       // elements
-  bool pageable = false;  // from malloc: pinned memory was refused (reserve(n, true))
-  Buf() = default;
-  Buf(const Buf &) = delete;
-  ~Buf() { release(); }
-  void swap(Buf &o) { std::swap(p, o.p); std::swap(count, o.count); std::swap(pageable, o.pageable); }
-  void release() {
-    if (p && pageable) std::free(p);
-    else if (p && kDevice) hipFree(p);
-    else if (p) hipHostFree(p);
-    p = nullptr;
-    count = 0;
-    pageable = false;
-  }
-  // Room for n elements: a buffer that is too small is freed, then allocated anew.  pageable_ok: where pinned memory is
-  // refused, malloc serves (the error is cleared; the copy to the device is then a synchronous one).
-  hipError_t reserve(size_t n, bool pageable_ok = false) {
-    if (n <= count) return hipSuccess;
-    release();
-    hipError_t e = kDevice ? hipMalloc(reinterpret_cast<void **>(&p), sizeof(T) * n)
-                           : hipHostMalloc(reinterpret_cast<void **>(&p), sizeof(T) * n, hipHostMallocDefault);
-    if (e != hipSuccess && pageable_ok) {
-      (void)hipGetLastError();
-      pageable = (p = static_cast<T *>(std::malloc(sizeof(T) * n))) != nullptr;
-      e = p ? hipSuccess : hipErrorOutOfMemory;
-    }
-    if (e != hipSuccess) p = nullptr;
-    count = p ? n : 0;
-    return e;
-  }
 };
 
 struct Slot {
@@ -160,8 +125,8 @@ int alloc_host_side(fdnn_server *s) {
     if (e == hipSuccess) e = sl.h_mask.reserve(n * h.out_dim);
     if (e == hipSuccess) e = sl.d_out.reserve(n * h.out_dim);
     // the slot's context was made lean: the device-side landing buffers of host batches live here
-    if (e == hipSuccess && !sl.ctx->d_x) e = hipMalloc(reinterpret_cast<void **>(&sl.ctx->d_x), sizeof(float) * n * h.in_dim);
-    if (e == hipSuccess && !sl.ctx->d_mask) e = hipMalloc(reinterpret_cast<void **>(&sl.ctx->d_mask), n * h.out_dim);
+    if (e == hipSuccess && !sl.ctx->d_x) e = sl.ctx->d_x.reserve(n * h.in_dim);
+    if (e == hipSuccess && !sl.ctx->d_mask) e = sl.ctx->d_mask.reserve(n * h.out_dim);
     if (e != hipSuccess)
       return fail(e == hipErrorOutOfMemory ? FDNN_E_NOMEM : FDNN_E_DEVICE, std::string("server staging: ") + hipGetErrorString(e));
   }

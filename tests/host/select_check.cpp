@@ -15,9 +15,11 @@
 #include <string>
 
 #include "fdnn_select.hpp"
+#include "select_cases.hpp"  // Setting, kSettings, kMaxFrames, tuning_of
 
 using namespace fdnn;
 using namespace fdnn::sel;
+using namespace select_cases;
 
 #define CHECK(cond)                                                          \
   do {                                                                       \
@@ -30,27 +32,6 @@ using namespace fdnn::sel;
 namespace {
 
 // ---------------------------------------------------------------------------------------- the table's cases and driver
-struct Setting {
-  const char *name;
-  int chain_mode, chain_min, pp_mode, pp_min, ppo_mode;  // fdnn_debug_set_chain / _pp / _ppo
-  bool fuse_off;                                         // FDNN_FUSE_NORM=0
-  bool taps, byte_mask, bit_mask;                        // what the call carries
-};
-const Setting kSettings[] = {
-    {"defaults", -1, 0, -1, 0, -1, false, false, false, false},
-    {"chain0", 0, 0, -1, 0, -1, false, false, false, false},
-    {"chain1", 1, 0, -1, 0, -1, false, false, false, false},
-    {"chain1.min5000", 1, 5000, -1, 0, -1, false, false, false, false},
-    {"pp0", -1, 0, 0, 0, -1, false, false, false, false},
-    {"pp1", -1, 0, 1, 0, -1, false, false, false, false},
-    {"pp1.min3000", -1, 0, 1, 3000, -1, false, false, false, false},
-    {"ppo0", -1, 0, -1, 0, 0, false, false, false, false},
-    {"ppo1", -1, 0, -1, 0, 1, false, false, false, false},
-    {"fuse_off", -1, 0, -1, 0, -1, true, false, false, false},
-    {"taps", -1, 0, -1, 0, -1, false, true, false, false},
-    {"byte_mask", -1, 0, -1, 0, -1, false, false, true, false},
-    {"bit_mask", -1, 0, -1, 0, -1, false, false, false, true},
-};
 struct Shape {
   const char *name;
   int rows, rows_pad, K;
@@ -70,7 +51,7 @@ const Shape kShapes[] = {
 };
 const int kHiddenDepths[] = {1, 6, 9};  // int8 hidden layers of the net (9: more than one chained launch holds)
 const int kL0Dims[] = {64, 432, 496, 500, 2048};
-constexpr int kMaxFrames = 70000, kL0Hidden = 2048;
+constexpr int kL0Hidden = 2048;
 
 // what is chosen at one frame count: the part that is constant over long runs of n as text, what moves with every tile
 // (padded frame counts, the chain's tile) as two sums over the run
@@ -138,15 +119,7 @@ struct HeaderEval {
   Tuning t;
   Device dev;  // 256 CUs: what the recording process, without a GPU, assumed
 
-  void configure(const Setting &s) {
-    t = Tuning();
-    t.chain_mode = s.chain_mode;
-    t.chain_min = s.chain_min;
-    t.pp_mode = s.pp_mode;
-    t.pp_min = s.pp_min;
-    t.ppo_mode = s.ppo_mode;
-    if (s.fuse_off) t.fuse_norm = 0;
-  }
+  void configure(const Setting &s) { t = tuning_of(s); }
   static LayerShape shape(const Shape &l) { return {l.rows, l.rows_pad, l.K, l.fastdiv, l.has_fix, l.output}; }
   static LayerCall call(const Shape &l, const Setting &s, int n) {
     LayerCall c{n};

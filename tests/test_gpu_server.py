@@ -257,10 +257,17 @@ def test_create_and_free_cycles_return_device_memory(mid_model_path):
     import torch
 
     x = F.synth_features(700, 432, seed=9)
+    raw = F.synth_features(700, 144, seed=10)
+    bits = F.pack_mask_bits(F.generate_masks_fast(700, 1000, 0.4, 0.03, seed=3))  # 40 % active: the compacted return
 
     def cycle():
         dnn = api.QuantizedDnn.loadFromFile(mid_model_path)
         dnn.calculate(x)
+        # the buffers a context grows on first use: raw frames, compacted lazy rows, the screening's debug planes
+        dnn.setSplice([-2, 0, 3], 144)
+        dnn.calculateRaw(raw)
+        dnn.calculateLazy(x, bits=bits)
+        dnn.layer0Screen(x[:64])
         ctx = dnn.getNewLazyContext(700)
         ctx.calculateUntilOutput(x)
         ctx.calculateForOutputNodes(np.ones(dnn.outputDimension(), dtype=np.int8))
