@@ -12,8 +12,8 @@ which case covers which names:
 tests/test_dispatch_ledger_host.py (no GPU) asserts  union(EXPECT) | EXCLUDED == the library's table,  so a new launch
 branch without a case fails everywhere; tests/test_gpu_dispatch_ledger.py runs every case with the recorder on and
 asserts the launched set in both directions plus parity with the oracle (never with another library path):
-u8 activations and int32 accumulators bit-exact, soft-max <= 2e-6 absolute with the oracle's NaN pattern, masked-out
-entries one value per row.  Weight scales stay <= 0.05 wherever the soft-max is compared (the range tools/fuzz_parity.py
+u8 activations and int32 accumulators bit-exact, tap logits bit-exact, soft-max <= 2e-6 absolute with the oracle's NaN
+pattern AND within tests/softmax_ref.py's relative bound of exp(z - max) / sum in float64, masked-out entries one value per row.  Weight scales stay <= 0.05 wherever the soft-max is compared (the range tools/fuzz_parity.py
 established 2e-6 for); the every-pair-saturating and degenerate nets are compared on integer state only.
 
 Run as a script (`python tests/dispatch_ledger.py --run ID [ID ...]`) it runs cases in this process and prints one JSON
@@ -28,6 +28,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+if os.path.dirname(os.path.abspath(__file__)) not in sys.path:  # (run as a script from another directory)
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import softmax_ref as SR  # noqa: E402
 
 TIGHT = 2e-6  # |p - oracle| per element: the project's soft-max bar (tests/test_gpu_production_shapes.py, tools/fuzz_parity.py)
 
@@ -64,6 +68,30 @@ def _net(kind):
         return F.synth_net([432, 2304, 2304, 2304, int(parts[1])], seed=71)
     if parts[0] == "d64":
         return F.synth_net([64, 256, 256, 256, 252], seed=41)
+    # -- the soft-max range nets (tests/softmax_ref.py, tests/test_gpu_softmax_range.py): a net of the ledger with other output
+    #    biases -- the bias is added after the division, so the logits move and nothing upstream of them does
+    if parts[0] in ("lad", "ladfull"):  # 'lad/W', 'ladfull': a shuffled ladder over [-40, 20]: exp's argument over 87 units, every probability a normal fp32
+        net = _net(f"n256/{parts[1]}/gauss" if parts[0] == "lad" else "full/gauss")
+        net.layers[-1].bias = SR.ladder(net.layers[-1].bias.size, -40.0, 20.0, seed=net.layers[-1].bias.size)
+        return net
+    if parts[0] in ("tail", "tailfull"):  # 'tail/ovf|tot|und', 'tailfull/ovf': the ends of exp's range.  Output weights / 256 (a power of
+        # two: the same int8 weights, a 256 times larger multiplier) leave |acc / coef| below 0.05, so the logits are the biases to that
+        net = _net("n256/256/gauss" if parts[0] == "tail" else "full/gauss")
+        out = net.layers[-1]
+        out.weights = (out.weights / np.float32(256.0)).astype(np.float32)
+        W = out.bias.size
+        rng = np.random.default_rng(W + len(parts[1]))
+        if parts[1] == "ovf":    # four logits at 95: exp is +inf (from 88.73), the total +inf, those four NaN and every other entry 0
+            out.bias = SR.ladder(W, -40.0, 20.0, seed=W + 1)
+            out.bias[rng.choice(W, 4, replace=False)] = 95.0
+        elif parts[1] == "tot":  # 64 logits at 87: every exp finite (6e37), the row total +inf, every entry 0
+            out.bias = SR.ladder(W, -40.0, 20.0, seed=W + 2)
+            out.bias[rng.choice(W, 64, replace=False)] = 87.0
+        elif parts[1] == "und":  # a ladder over [-120, 0]: probabilities below 2^-126 beside normal ones
+            out.bias = SR.ladder(W, -120.0, 0.0, seed=W + 3)
+        else:
+            raise ValueError(kind)
+        return net
     raise ValueError(kind)
 
 
@@ -509,6 +537,14 @@ def _softmax_ok(got, want, what):
     assert err <= TIGHT, f"{what}: soft-max differs from the oracle by {err:.3e} (> {TIGHT})"
 
 
+def _softmax_rel_ok(got, want, orc, acc, what, masks=None, tap=None):
+    """The relative bar beside the absolute one: against exp(z - max) / sum in float64 within softmax_ref.bound, z the
+    reference's fp32 logits rebuilt from the oracle's accumulators (and equal, bit for bit, to its `logits` tap where there is one)."""
+    z = SR.logits(acc, SR.coef_of(orc), orc.layer_bias(orc.n_layers - 1), masks=masks, tap=tap)
+    share = SR.check(got, z, SR.rows_pad_of(orc.out_dim), what, oracle_nan=np.isnan(want))
+    assert share == 0.0, f"{what}: {share:.3%} of the entries lie below 2^-126 and took check()'s weaker rule"
+
+
 def _masked_out_ok(got, masks, what):
     """Masked-out nodes of a row all carry the row's 1 / total (exp(0) / total, dnn.cc:366-369): one value per row."""
     off = masks == 0
@@ -540,8 +576,11 @@ def release_models():
     _MODELS.clear()
 
 
-def run_case(case):
-    """Run one case with the recorder on -> the set of names its span launched.  Raises AssertionError on a parity miss."""
+def run_case(case, detail=None):
+    """Run one case with the recorder on -> the set of names its span launched.  Raises AssertionError on a parity miss.
+    A caller that adds checks of its own (tests/test_gpu_softmax_range.py) passes a dict as `detail` and finds there what the
+    case produced and what the oracle says on the rows compared: got, idx, masks, orc and -- taps: want, wt; otherwise: hid,
+    want, acc (the oracle's dense probabilities and output accumulators)."""
     import contextlib
 
     from fast_dnn_amd import api, formats as F
@@ -554,7 +593,7 @@ def run_case(case):
     D, O = dnn.inputDimension(), dnn.outputDimension()
     n = case.n
     x = F.synth_features(n, D, seed=1000 + n % 977, pad_from=None if D != 432 else 429)
-    big = case.net.startswith("full/")
+    big = "full" in case.net.split("/")[0]  # K = 2048, 8000 outputs: the oracle scores a sample of the rows
     idx = sample_rows(n, case.tile or 320, seed=n) if big else np.arange(n)
     soft = not case.integer_only
     api.set_fuse(case.fuse)
@@ -574,12 +613,18 @@ def run_case(case):
         names = set(LAST_COUNTS)
         # ---- the oracle, on the rows the case compares
         xs = x[idx]
+        if detail is not None:
+            detail.update(got=got, idx=idx, masks=masks, orc=orc)
         if case.entry == "taps":
             want, wt = orc.calculate(xs, taps=True)
+            if detail is not None:
+                detail.update(want=want, wt=wt)
             for k in ("u8_acts", "acc_hid", "acc_out"):
                 assert np.array_equal(got[k], wt[k]), f"{case.id}: {k} differs from the oracle"
             if soft:
+                assert np.array_equal(got["logits"].view(np.uint32), wt["logits"].view(np.uint32)), f"{case.id}: logits differ from the oracle"
                 _softmax_ok(got["probs"], want, case.id)
+                _softmax_rel_ok(got["probs"], want, orc, wt["acc_out"], case.id, tap=wt["logits"])
             return names
         hid = orc.hidden_acts_mt(xs)
         if "hidden" in got:
@@ -587,8 +632,10 @@ def run_case(case):
         if "u8" in got:  # layer 0 alone
             _, wt = orc.calculate(xs, taps=True)
             assert np.array_equal(got["u8"][idx], wt["u8_acts"][0]), f"{case.id}: layer-0 bytes differ from the oracle"
-        if "dense" in got or "acc" in got or "macc" in got:
+        if "dense" in got or "acc" in got or "macc" in got or ("lazy" in got and soft) or detail is not None:
             want, acc = orc.output_mt(hid, want_acc=True)
+            if detail is not None:
+                detail.update(hid=hid, want=want, acc=acc)
             if "acc" in got:
                 assert np.array_equal(got["acc"][idx], acc), f"{case.id}: output accumulators differ from the oracle"
             if "macc" in got:
@@ -596,8 +643,11 @@ def run_case(case):
                 assert np.array_equal(got["macc"][idx][on], acc[on]), f"{case.id}: masked output accumulators differ from the oracle"
             if "dense" in got and soft:
                 _softmax_ok(got["dense"][idx], want, case.id + " dense")
+                _softmax_rel_ok(got["dense"][idx], want, orc, acc, case.id + " dense")
         if "lazy" in got and soft:
-            _softmax_ok(got["lazy"][idx], orc.output_mt(hid, masks=masks[idx]), case.id + " lazy")
+            want_lazy = orc.output_mt(hid, masks=masks[idx])
+            _softmax_ok(got["lazy"][idx], want_lazy, case.id + " lazy")
+            _softmax_rel_ok(got["lazy"][idx], want_lazy, orc, acc, case.id + " lazy", masks=masks[idx])
             _masked_out_ok(got["lazy"][idx], masks[idx], case.id)
         return names
     finally:

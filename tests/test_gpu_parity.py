@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import softmax_ref as SR
 from conftest import golden
 from fast_dnn_amd import api, formats as F
 from dispatch_ledger import launched
@@ -37,8 +38,17 @@ def test_tiny_golden_all_taps(tiny_model_path, x16):
     assert (t["u8_acts"] == g["u8_acts"]).all()
     assert (t["acc_hid"] == g["acc_hid"]).all()
     assert (t["acc_out"] == g["acc_out"]).all()
-    assert np.abs(t["logits"] - g["logits"]).max() <= 1e-6
+    assert np.abs(t["logits"] - g["logits"]).max() <= 1e-6  # (the golden file was made with another libm)
     assert np.abs(t["probs"] - g["probs"]).max() <= TIGHT
+    # ... and against the oracle: logits bit for bit (correctly rounded operations only), probabilities within the relative
+    # bound of the float64 soft-max (tests/softmax_ref.py)
+    orc = Oracle(tiny_model_path)
+    want, wt = orc.calculate(x16, taps=True)
+    assert np.array_equal(t["logits"].view(np.uint32), wt["logits"].view(np.uint32))
+    assert np.array_equal(t["acc_out"], wt["acc_out"]) and np.abs(t["probs"] - want).max() <= TIGHT
+    z = SR.logits(wt["acc_out"], SR.coef_of(orc), orc.layer_bias(orc.n_layers - 1), tap=wt["logits"])
+    SR.check(t["probs"], z, SR.rows_pad_of(orc.out_dim), "tiny", oracle_nan=np.isnan(want))
+    orc.close()
     p = dnn.calculate(x16, 10)
     assert (p == t["probs"]).all()  # taps run the same kernels
     p8 = dnn.calculate(g["x8"], 3)
