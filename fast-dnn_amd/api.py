@@ -121,6 +121,12 @@ SIGNATURES = {
     "fdnn_debug_layer0_screen": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, _c_u8p, _c_f32p, _c_f32p, C.POINTER(C.c_ulonglong)]),
     "fdnn_ctx_lazy_output_batch_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fdnn_ctx_lazy_output_batch_bits_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_ctx_lazy_output_lists": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p]),
+    "fdnn_ctx_lazy_output_lists_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_lazy_lists": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p]),
+    "fdnn_debug_lists_check": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.c_int]),
+    "fdnn_debug_ctx_lists_acc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, _c_i32p, _c_i32p]),
+    "fdnn_debug_lists_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_profile_begin": (C.c_int, [C.c_void_p]),
@@ -286,6 +292,38 @@ def launch_counts(nonzero: bool = True) -> dict:
     return {names[i]: int(buf[i]) for i in range(n) if buf[i] or not nonzero}
 
 
+def _lists(rowPtr, nodes):
+    """(row_ptr, nodes) as C-contiguous int32 arrays; the shapes every list entry point needs."""
+    rp = np.ascontiguousarray(rowPtr, dtype=np.int32)
+    nd = np.ascontiguousarray(nodes, dtype=np.int32)
+    if rp.ndim != 1 or rp.size < 1 or nd.ndim != 1:
+        raise ValueError("rowPtr must be [count + 1] and nodes [nnz]")
+    if int(rp[-1]) > nd.size:  # (the C side reads rowPtr[count] nodes)
+        raise ValueError(f"rowPtr ends at {int(rp[-1])} but there are {nd.size} nodes")
+    return rp, nd
+
+
+def lists_check(rowPtr, nodes, outputDimension: int) -> int:
+    """The validator of the list entry points (``fdnn_debug_lists_check``; host code, no device): 0, or -(row + 1) of the
+    first row whose list is not well formed -- rowPtr starts at 0 and never decreases, a row's nodes ascend strictly
+    inside [0, outputDimension)."""
+    rp = np.ascontiguousarray(rowPtr, dtype=np.int32)
+    nd = np.ascontiguousarray(nodes, dtype=np.int32)
+    if rp.ndim != 1 or rp.size < 1 or nd.ndim != 1:
+        raise ValueError("rowPtr must be [count + 1] and nodes [nnz]")
+    if rp.size > 1 and int(rp.max()) > nd.size:  # never let the C side read past the node array
+        return -(int(np.argmax(rp[1:] > nd.size)) + 1)
+    return int(lib().fdnn_debug_lists_check(rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p), rp.size - 1, int(outputDimension)))
+
+
+def lists_launches():
+    """Process-wide launch counts of the list kernels since load: (score without the pair walk, score with it, finish)."""
+    buf = (C.c_ulonglong * 3)()
+    if lib().fdnn_debug_lists_launches(buf, 3) != 3:
+        raise RuntimeError("fdnn_debug_lists_launches")
+    return tuple(int(v) for v in buf)
+
+
 class LazyContext:
     """``QuantizedDnn.LazyContext`` (QuantizedDnn.java:72-98)."""
 
@@ -333,6 +371,31 @@ class LazyContext:
         _check(lib().fdnn_ctx_lazy_output_batch(self.handle, first, count, masks.ctypes.data_as(_c_i8p),
                                                 out.ctypes.data_as(_c_f32p)))
         return out
+
+    def calculateForOutputNodesLists(self, rowPtr, nodes, first: int = 0):
+        """Lazy output for the LISTED nodes only (``fdnn_ctx_lazy_output_lists``): rows first .. first + count - 1,
+        rowPtr int32 [count + 1], nodes int32 [nnz] ascending inside a row -> (probs [nnz], inactive [count]): the listed
+        nodes' probabilities and, per row, the value every unlisted node reads (``formats.lists_to_rows`` rebuilds rows)."""
+        rp, nd = _lists(rowPtr, nodes)
+        probs = np.empty(int(rp[-1]) if rp[-1] > 0 else 0, dtype=np.float32)
+        inactive = np.empty(rp.size - 1, dtype=np.float32)
+        _check(lib().fdnn_ctx_lazy_output_lists(self.handle, int(first), rp.size - 1, rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p),
+                                                probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p)))
+        return probs, inactive
+
+    def calculateForOutputNodesListsDevice(self, d_rowPtr: int, d_nodes: int, nnz: int, d_probs: int, d_inactive: int, first: int, count: int,
+                                           stream: int = 0) -> None:
+        """The same on device buffers, enqueued on ``stream``, not synchronised; the lists are not validated (fdnn.h)."""
+        _check(lib().fdnn_ctx_lazy_output_lists_device(self.handle, int(first), int(count), C.c_void_p(d_rowPtr), C.c_void_p(d_nodes), int(nnz),
+                                                       C.c_void_p(d_probs), C.c_void_p(d_inactive), C.c_void_p(stream)))
+
+    def listsAccumulators(self, rowPtr, nodes, first: int = 0) -> np.ndarray:
+        """Parity tests: the int32 accumulators of the listed entries as the score kernel holds them (``fdnn_debug_ctx_lists_acc``)."""
+        rp, nd = _lists(rowPtr, nodes)
+        acc = np.zeros(max(int(rp[-1]), 0), dtype=np.int32)
+        _check(lib().fdnn_debug_ctx_lists_acc(self.handle, int(first), rp.size - 1, rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p),
+                                              acc.ctypes.data_as(_c_i32p)))
+        return acc
 
     # device-resident forms (raw device pointers, e.g. ``tensor.data_ptr()``; enqueued on ``stream``)
     def calculateForOutputNodesBatchBits(self, bits, first: int = 0, out=None) -> np.ndarray:
@@ -693,6 +756,23 @@ class QuantizedDnn:
             _check(lib().fdnn_calculate_lazy(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(),
                                              m.ctypes.data_as(_c_i8p), out.ctypes.data_as(_c_f32p)))
         return out
+
+    def calculateLazyLists(self, input, rowPtr, nodes):
+        """One-call lazy scoring of the LISTED nodes only (``fdnn_calculate_lazy_lists``): hidden layers, then per frame the
+        nodes rowPtr / nodes list -> (probs [nnz], inactive [frames]), as ``LazyContext.calculateForOutputNodesLists``."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        rp, nd = _lists(rowPtr, nodes)
+        if rp.size != n + 1:
+            raise ValueError(f"rowPtr must have {n + 1} entries, got {rp.size}")
+        probs = np.empty(max(int(rp[-1]), 0), dtype=np.float32)
+        inactive = np.empty(n, dtype=np.float32)
+        _check(lib().fdnn_calculate_lazy_lists(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(),
+                                               rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p), probs.ctypes.data_as(_c_f32p),
+                                               inactive.ctypes.data_as(_c_f32p)))
+        return probs, inactive
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))

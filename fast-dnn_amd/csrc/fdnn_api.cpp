@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "fdnn_internal.hpp"
+#include "fdnn_lists.hpp"
 
 using namespace fdnn;
 
@@ -307,6 +308,74 @@ int fdnn_ctx_lazy_output_batch_bits(fdnn_ctx *c, int first, int count, const uin
   int rc = run_output(c, {.first = first, .count = count, .d_bits = c->d_mask_bits, .d_out = c->d_out}, c->stream);
   if (!rc) rc = lazy_copy_out(c, count, c->d_mask_bits, bits, out, c->stream);
   return rc;
+}
+
+// ---------------------------------------------------------------- lazy output by active-node lists (fdnn_lists.hip)
+// FDNN_E_ARG naming the first row whose list is not a mask in list form (fdnn_lists.hpp: check)
+static int lists_validate(const int32_t *row_ptr, const int32_t *nodes, int count, int output_dim) {
+  const int bad = lists::check(row_ptr, nodes, count, output_dim);
+  if (!bad) return FDNN_OK;
+  return fail(FDNN_E_ARG, "active list of row " + std::to_string(-bad - 1) + ": row_ptr must start at 0 and never decrease, a row's nodes must ascend strictly inside [0, " +
+                              std::to_string(output_dim) + ")");
+}
+
+static int ctx_lists_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive,
+                          int32_t *acc) {
+  if (!c || !row_ptr) return fail(FDNN_E_ARG, "null argument");
+  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
+  if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
+  if (count == 0) return FDNN_OK;
+  if (int rc = lists_validate(row_ptr, nodes, count, c->m->hm.hdr.out_dim)) return rc;
+  if ((!acc && !inactive) || (row_ptr[count] > 0 && !acc && !probs)) return fail(FDNN_E_ARG, "null result buffer");
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  return lists_to_host(c, first, count, row_ptr, nodes, probs, inactive, acc, c->stream);
+}
+
+int fdnn_ctx_lazy_output_lists(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs,
+                               float *inactive) {
+  return ctx_lists_host(c, first, count, row_ptr, nodes, probs, inactive, nullptr);
+}
+
+int fdnn_debug_ctx_lists_acc(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, int32_t *acc) {
+  if (!acc) return fail(FDNN_E_ARG, "null argument");
+  return ctx_lists_host(c, first, count, row_ptr, nodes, nullptr, nullptr, acc);
+}
+
+int fdnn_ctx_lazy_output_lists_device(fdnn_ctx *c, int first, int count, const int32_t *d_row_ptr, const int32_t *d_nodes, int nnz,
+                                      float *d_probs, float *d_inactive, void *stream) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  return run_lists(c, {first, count, d_row_ptr, d_nodes, nnz, d_probs, d_inactive, nullptr}, s);
+}
+
+int fdnn_debug_lists_check(const int32_t *row_ptr, const int32_t *nodes, int count, int output_dim) {
+  if (!row_ptr || count < 0) return fail(FDNN_E_ARG, "bad argument");
+  return lists::check(row_ptr, nodes, count, output_dim);
+}
+
+int fdnn_debug_lists_launches(unsigned long long *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  unsigned long long v[3];
+  fdnn::lists_launch_counts(v);
+  for (int i = 0; i < 3 && i < cap; ++i) out[i] = v[i];
+  return 3;
+}
+
+// One-call form: hidden layers + lists on a pooled context, a large n chunk by chunk with its slice of the lists rebased.
+int fdnn_calculate_lazy_lists(fdnn_model *m, const float *x, int n, int dim, const int32_t *row_ptr, const int32_t *nodes, float *probs,
+                              float *inactive) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;
+  if (!x || !row_ptr || !inactive) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  if (int rc = lists_validate(row_ptr, nodes, n, m->hm.hdr.out_dim)) return rc;
+  if (row_ptr[n] > 0 && !probs) return fail(FDNN_E_ARG, "null buffer");
+  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_lazy_lists", .x = x, .row_ptr = row_ptr, .nodes = nodes, .probs = probs, .inactive = inactive});
 }
 
 int fdnn_ctx_lazy_output(fdnn_ctx *c, int frame, const int8_t *mask, float *out) {

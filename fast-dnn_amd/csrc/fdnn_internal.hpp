@@ -54,6 +54,10 @@ struct fdnn_model {
   fdnn::DevBuf<int8_t> d_w0d;    // int8 screening (fdnn_l0s.hip): the layer-0 weights as three int8 digit planes, MFMA fragment order
   fdnn::DevBuf<float> d_w0stat;  // [3][l0_h_ld]: 2^8 / c_n, ||w_n||_2, 2^8 b_n
   fdnn::DevBuf<uint32_t> d_lutpair;  // the sigmoid table as (round-down, round-up) byte pairs
+  // lazy output by lists (fdnn_lists.hip): the output layer's saturating pairs indexed per NODE, built at load from the
+  // blob's group-ordered list (fdnn_lists.hpp); both null when the layer has none.  Not part of the blob.
+  fdnn::DevBuf<int32_t> d_lfix_off;     // [O + 1]
+  fdnn::DevBuf<uint32_t> d_lfix_pairs;  // [n_fix] k | w0 << 16 | w1 << 24
   // the device side of "is somebody else scoring on this GPU?".  A fused soft-max workgroup that
   // sits out its bounded wait (tens of milliseconds: its frame tile's siblings were kept off the chip) raises this
   // host-mapped word; from the next call on the model runs the scale-pass path, for good, and says so once.
@@ -120,6 +124,10 @@ struct fdnn_ctx {
   fdnn::DevBuf<uint64_t> d_mask_bits;  // [n][ceil(O/64)] the batched lazy call's mask as bits (launch_mask_pack)
   bool mask_bits_packed = false;    // run_output has packed the current call's byte masks into d_mask_bits
   fdnn::DevBuf<float> d_comp;       // host lazy batches: compacted result rows (allocated on first use)
+  // host list calls (fdnn_ctx_lazy_output_lists, fdnn_calculate_lazy_lists): staging of the lists and their results,
+  // allocated on the first list call and grown by the largest one
+  fdnn::DevBuf<int32_t> d_lrow, d_lnodes;   // [count + 1], [nnz]
+  fdnn::DevBuf<float> d_lprobs, d_linact;   // [nnz], [count]
   int last = -1;                  // d_act index holding the last hidden layer, -1 = not computed
   bool pooled = false;
   bool no_fuse = false;           // this call must not use the fused soft-max
@@ -172,6 +180,23 @@ struct OutputCall {
   const Taps *taps = nullptr;
 };
 int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s);
+// LazyOutputActivations (dnn.cc:355-392) for the LISTED nodes only (fdnn_lists.hip): rows [first, first + count) of the
+// context, their lists and results on the device; enqueued on s.  d_acc (parity tests) may be null.
+struct ListsCall {
+  int first = 0, count = 0;
+  const int32_t *d_row_ptr = nullptr;  // [count + 1]
+  const int32_t *d_nodes = nullptr;    // [nnz]
+  int nnz = 0;
+  float *d_probs = nullptr;            // [nnz]
+  float *d_inactive = nullptr;         // [count]
+  int32_t *d_acc = nullptr;            // [nnz]
+};
+int run_lists(fdnn_ctx *c, const ListsCall &lc, hipStream_t s);
+// The host form of the same: validated lists up, results back, synchronises s.  acc (parity tests) may be null.
+int lists_to_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive,
+                  int32_t *acc, hipStream_t s);
+int build_lists_index(fdnn_model *m);  // the per-node pair index of the output layer, from m->hm (model load / blob import)
+int device_cus(int device);            // CUs of a device, asked once (256 where the runtime cannot say)
 // Will run_output scale the soft-max inside the output kernel for such a call (dense, large batch)?  Then there is no
 // scale pass to hide under the next batch's layer 0.
 bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks);
@@ -253,6 +278,9 @@ struct ScorePass {
   int row0 = 0;        // the splice row of the call's row 0
   // mask: none, bits on the device, or bits on the host (uploaded chunk by chunk)
   const uint64_t *d_bits = nullptr, *bits = nullptr;
+  // lists instead of a mask (host rows only): the call's row_ptr [n + 1] and nodes; results probs [nnz], inactive [n]
+  const int32_t *row_ptr = nullptr, *nodes = nullptr;
+  float *probs = nullptr, *inactive = nullptr;
   // results: device rows, enqueued on `stream` (the caller's) -- or host rows on the context's own stream, synchronised:
   // dense through dense_pass_to_host and its re-run rules, with host bits through lazy_copy_out
   float *d_out = nullptr;

@@ -169,6 +169,30 @@ struct QChainParams {
 };
 void launch_qchain(const QChainParams &p, int n_cu, hipStream_t s);
 
+// Lazy output by active-node lists (fdnn_lists.hip; the lists' contract and the per-node pair index: fdnn_lists.hpp):
+// score writes e = exp(z) of every entry into probs, finish scales each row's entries in place and writes its 1 / total.
+struct ListsParams {
+  const int8_t *w;            // [rows_pad][ldw] the output layer's int8 rows (pad columns zero)
+  const int8_t *a;            // [count][lda] s8 last-hidden activations of the call's rows (pad columns: anything)
+  const float *bias;          // [rows_pad]
+  const int32_t *wsum;        // [rows_pad] 128 * sum_k w
+  const int32_t *fix_off;     // [rows + 1] a node's saturating pairs in fix_pairs; both null: the layer has none
+  const uint32_t *fix_pairs;  // k | w0 << 16 | w1 << 24
+  const int32_t *row_ptr;     // [count + 1]
+  const int32_t *nodes;       // [nnz]
+  float *probs;               // [nnz]
+  float *inactive;            // [count]
+  int32_t *acc;               // [nnz] the int32 accumulators as the score kernel holds them (parity tests), or null
+  int rows, K, ldw, lda, count, nnz;
+  int epg;                    // consecutive entries one 16-lane group scores (lists_entries_per_group)
+  float coef, rcp_coef;
+  int fastdiv;
+};
+void launch_lists_score(const ListsParams &p, hipStream_t s);
+void launch_lists_finish(const ListsParams &p, hipStream_t s);
+int lists_entries_per_group(long long nnz, int n_cu);
+void lists_launch_counts(unsigned long long out[3]);  // launches so far: score without / with the pair walk, finish
+
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the
 // output GEMM's epilogue.

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "fdnn_internal.hpp"
+#include "fdnn_lists.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -122,7 +123,25 @@ int build_l0_image(fdnn_model *m) {
     if (m->h_fuse_fault.reserve(1) != hipSuccess) (void)hipGetLastError();  // refused: stays null, the model goes on without
     if (m->h_fuse_fault) *m->h_fuse_fault.p = 0;
   }
+  if (int rc = build_lists_index(m)) return rc;
   HIP_TRY(hipDeviceSynchronize());
+  return FDNN_OK;
+}
+
+// The output layer's saturating pairs per node, for the list kernels (fdnn_lists.hip): a side buffer of the model, from
+// the blob's group-ordered entries.  The blob, its version and its bytes stay as they are.
+int build_lists_index(fdnn_model *m) {
+  const BlobHeader &h = m->hm.hdr;
+  const QLayerDesc &d = h.q[h.n_q - 1];
+  if (d.n_fix <= 0) return FDNN_OK;
+  std::vector<int32_t> off;
+  std::vector<uint32_t> pairs;
+  lists::build_node_fix_index(reinterpret_cast<const FixEntry *>(m->hm.blob.data() + d.off_fix_ent),
+                              reinterpret_cast<const int32_t *>(m->hm.blob.data() + d.off_fix_grp), d.rows, d.rows_pad, &off, &pairs);
+  HIP_TRY(m->d_lfix_off.reserve(off.size()));
+  HIP_TRY(m->d_lfix_pairs.reserve(std::max<size_t>(pairs.size(), 1)));
+  HIP_TRY(hipMemcpy(m->d_lfix_off, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
+  if (!pairs.empty()) HIP_TRY(hipMemcpy(m->d_lfix_pairs, pairs.data(), sizeof(uint32_t) * pairs.size(), hipMemcpyHostToDevice));
   return FDNN_OK;
 }
 
@@ -654,6 +673,78 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
   return FDNN_OK;
 }
 
+// LazyOutputActivations for the listed nodes only (fdnn_lists.hip): the score kernel over the flat entry array, then one
+// wave per row for the total and the scale.  Nothing of the masked output path runs.
+int run_lists(fdnn_ctx *c, const ListsCall &lc, hipStream_t s) {
+  fdnn_model *m = c->m;
+  const BlobHeader &h = m->hm.hdr;
+  const QLayerDesc &d = h.q[h.n_q - 1];
+  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
+  if (lc.first < 0 || lc.count < 0 || lc.first + lc.count > c->n) return fail(FDNN_E_ARG, "frame range outside the context");
+  if (lc.nnz < 0) return fail(FDNN_E_ARG, "negative entry count");
+  if (lc.count == 0) return FDNN_OK;
+  if (!lc.d_row_ptr || !lc.d_inactive || (lc.nnz > 0 && (!lc.d_nodes || !lc.d_probs))) return fail(FDNN_E_ARG, "null list buffer");
+  const uint8_t *B = m->d_blob;
+  fdnn::ListsParams g{};
+  g.w = reinterpret_cast<const int8_t *>(B + d.off_w);
+  g.a = c->d_act[c->last] + size_t(lc.first) * c->act_ld;
+  g.bias = reinterpret_cast<const float *>(B + d.off_bias);
+  g.wsum = reinterpret_cast<const int32_t *>(B + d.off_wsum);
+  if (d.n_fix > 0) {
+    g.fix_off = m->d_lfix_off;
+    g.fix_pairs = m->d_lfix_pairs;
+  }
+  g.row_ptr = lc.d_row_ptr;
+  g.nodes = lc.d_nodes;
+  g.probs = lc.d_probs;
+  g.inactive = lc.d_inactive;
+  g.acc = lc.d_acc;
+  g.rows = d.rows;
+  g.K = d.cols_pad - fdnn::kRowSkew;
+  g.ldw = d.cols_pad;
+  g.lda = c->act_ld;
+  g.count = lc.count;
+  g.nnz = lc.nnz;
+  g.epg = fdnn::lists_entries_per_group(lc.nnz, device_cus(m->device));
+  g.coef = d.coef;
+  g.rcp_coef = d.rcp_coef;
+  g.fastdiv = d.fastdiv_ok;
+  {
+    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
+    fdnn::launch_lists_score(g, s);
+  }
+  {
+    ProfScope ps(m, s, FDNN_PROF_NORMALIZE);
+    fdnn::launch_lists_finish(g, s);
+  }
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+int lists_to_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive,
+                  int32_t *acc, hipStream_t s) {
+  const size_t nnz = size_t(row_ptr[count]);
+  // (a buffer that is too small is freed and allocated anew: the context's earlier list calls have been synchronised)
+  HIP_TRY(c->d_lrow.reserve(size_t(count) + 1));
+  HIP_TRY(c->d_linact.reserve(size_t(count)));
+  HIP_TRY(c->d_lnodes.reserve(std::max<size_t>(nnz, 1)));
+  HIP_TRY(c->d_lprobs.reserve(std::max<size_t>(nnz, 1)));
+  DevBuf<int32_t> d_acc;
+  if (acc) HIP_TRY(d_acc.reserve(std::max<size_t>(nnz, 1)));
+  HIP_TRY(hipMemcpyAsync(c->d_lrow, row_ptr, sizeof(int32_t) * (size_t(count) + 1), hipMemcpyHostToDevice, s));
+  if (nnz) HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, s));
+  int rc = run_lists(c, {first, count, c->d_lrow, c->d_lnodes, int(nnz), c->d_lprobs, c->d_linact, acc ? d_acc.p : nullptr}, s);
+  if (rc) {
+    hipStreamSynchronize(s);
+    return rc;
+  }
+  if (nnz && probs) HIP_TRY(hipMemcpyAsync(probs, c->d_lprobs, sizeof(float) * nnz, hipMemcpyDeviceToHost, s));
+  if (inactive) HIP_TRY(hipMemcpyAsync(inactive, c->d_linact, sizeof(float) * size_t(count), hipMemcpyDeviceToHost, s));
+  if (nnz && acc) HIP_TRY(hipMemcpyAsync(acc, d_acc, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FDNN_OK;
+}
+
 bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks) { return choose_output(c, count, d_masks != nullptr, false, nullptr, true).fused; }
 
 // Device -> pageable host memory for large results (the 8000-float rows of a whole batch:
@@ -950,6 +1041,7 @@ int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, 
   int rc = acquire_ctx(m, cap, &c);
   if (rc) return rc;
   hipStream_t s = p.d_out ? p.stream : c->stream;
+  std::vector<int32_t> rebased;
   CtxUse use;  // (also on the error paths: the context goes back to the pool)
   hipError_t e = use.enter(c, s);
   if (e == hipSuccess && p.raw) {  // host raw frames travel once; every chunk splices its rows from them
@@ -964,6 +1056,14 @@ int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, 
     if (p.x) e = hipMemcpyAsync(c->d_x, p.x + off * D, sizeof(float) * size_t(cnt) * D, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && p.bits) e = hipMemcpyAsync(c->d_mask_bits, p.bits + off * wpr, sizeof(uint64_t) * size_t(cnt) * wpr, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) break;
+    if (p.row_ptr) {  // the chunk's slice of the lists as lists of its own (synchronises: `rebased` is free for the next chunk)
+      rc = run_hidden(c, c->d_x, s, nullptr);
+      lists::rebase_rows(p.row_ptr, int(off), cnt, &rebased);
+      const size_t e0 = size_t(p.row_ptr[off]);
+      if (!rc) rc = lists_to_host(c, 0, cnt, rebased.data(), p.nodes + e0, p.probs + e0, p.inactive + off, nullptr, s);
+      if (rc) hipStreamSynchronize(s);
+      continue;
+    }
     if (p.out && !p.bits) {
       rc = dense_pass_to_host(c, p.out + off * O, s);
       continue;

@@ -300,3 +300,26 @@ def pack_mask_bits(masks) -> np.ndarray:
     padded = np.zeros((n, wpr * 64), dtype=np.uint8)
     padded[:, :O] = m
     return np.packbits(padded, axis=1, bitorder="little").view("<u8").reshape(n, wpr)
+
+
+def masks_to_lists(masks):
+    """Byte masks [n][O] (non-zero = active) -> (row_ptr int32 [n + 1], nodes int32 [nnz]): every row's active nodes in
+    ascending order, row after row -- the lists of fdnn_ctx_lazy_output_lists."""
+    m = (np.asarray(masks) != 0)
+    if m.ndim != 2:
+        raise ValueError("masks must be [n][O]")
+    row_ptr = np.zeros(m.shape[0] + 1, dtype=np.int32)
+    np.cumsum(m.sum(axis=1), out=row_ptr[1:])
+    nodes = np.nonzero(m)[1].astype(np.int32)  # (row-major order: ascending inside a row)
+    return row_ptr, nodes
+
+
+def lists_to_rows(row_ptr, nodes, probs, inactive, O: int) -> np.ndarray:
+    """The full rows [n][O] of a list call: every listed node its probability, every other node the row's inactive value
+    (LazyOutputActivations' row layout, dnn.cc:366-369, :389)."""
+    row_ptr = np.asarray(row_ptr, dtype=np.int64)
+    n = row_ptr.size - 1
+    out = np.repeat(np.asarray(inactive, dtype=np.float32)[:, None], int(O), axis=1)
+    rows = np.repeat(np.arange(n), np.diff(row_ptr))
+    out[rows, np.asarray(nodes, dtype=np.int64)[:rows.size]] = np.asarray(probs, dtype=np.float32)[:rows.size]
+    return out

@@ -213,6 +213,32 @@ FDNN_API int fdnn_ctx_lazy_output_batch_device(fdnn_ctx *c, int first, int count
  * contribute exp(0) to the sum and all read 1 / total). */
 FDNN_API int fdnn_ctx_lazy_output_batch_bits(fdnn_ctx *c, int first, int count, const uint64_t *bits, float *out);
 FDNN_API int fdnn_ctx_lazy_output_batch_bits_device(fdnn_ctx *c, int first, int count, const uint64_t *d_bits, float *d_out, void *stream);
+/* Lazy output by ACTIVE-NODE LISTS: only the listed nodes are scored (LazyOutputActivations, dnn.cc:355-392, exists to skip
+ * the nodes a decoder does not ask for; the masked entry points above compute the whole layer and mask).  For narrow
+ * active sets -- forced alignment, lattice rescoring, keyword spotting: a few nodes per frame -- and the per-frame protocol.
+ * The caller opts in: nothing is routed here by itself (INTEGRATION.md states the measured crossover).
+ *   lists   for rows first .. first + count - 1 of a context whose hidden layers have run: row_ptr [count + 1] int32,
+ *           row_ptr[0] == 0, non-decreasing, row_ptr[count] == nnz; nodes [nnz] int32, strictly ascending inside a row
+ *           and in [0, output_dim).  Such a list is exactly a mask.
+ *   probs   [nnz]: entry i's probability under the lazy contract -- listed nodes have the logit f32(f32(acc) / coef) +
+ *           bias, every unlisted node the logit 0 and contributes exp(0) = 1 to the total (dnn.cc:366-369).
+ *   inactive [count]: the value every unlisted node of that row reads, 1 / total (dnn.cc:389).  An empty row gives
+ *           1 / output_dim; a row that lists every node is the dense soft-max.
+ * The row total is summed in one fixed order, so a row's bytes do not depend on the batch it was
+ * scored in, its position or the entry point.
+ * fdnn_ctx_lazy_output_lists         host buffers, host-synchronous; validates the lists: FDNN_E_ARG names the row.
+ *   FDNN_E_STATE before the hidden layers, FDNN_E_ARG for rows outside the context (as fdnn_ctx_lazy_output_batch_bits).
+ * fdnn_ctx_lazy_output_lists_device  device buffers, enqueued on `stream`, not synchronised, ordered on the context like
+ *   the other *_device entries.  The lists are NOT validated: a node outside [0, output_dim) is never used as an address,
+ *   its row's entries and inactive value come back NaN; row_ptr values are clamped to [0, nnz].
+ * fdnn_calculate_lazy_lists          one call: pooled context, hidden layers + lists; a large n goes chunk by chunk
+ *   (fdnn_debug_frame_chunks), each chunk with its slice of the lists rebased.  LazyOutputActivations, dnn.cc:355-392. */
+FDNN_API int fdnn_ctx_lazy_output_lists(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs,
+                                        float *inactive);
+FDNN_API int fdnn_ctx_lazy_output_lists_device(fdnn_ctx *c, int first, int count, const int32_t *d_row_ptr, const int32_t *d_nodes,
+                                               int nnz, float *d_probs, float *d_inactive, void *stream);
+FDNN_API int fdnn_calculate_lazy_lists(fdnn_model *m, const float *x, int n, int dim, const int32_t *row_ptr, const int32_t *nodes,
+                                       float *probs, float *inactive);
 /* Dense output layer over the context's hidden activations
  * (CalculateOutput, dnn.cc:428-454). */
 FDNN_API int fdnn_ctx_output(fdnn_ctx *c, float *out);
@@ -402,6 +428,18 @@ FDNN_API const char *fdnn_debug_launch_name(int index, int *flags);
 FDNN_API int fdnn_debug_launch_record(int on);
 FDNN_API int fdnn_debug_launch_reset(void);
 FDNN_API int fdnn_debug_launch_counts(unsigned long long *out, int cap);
+
+/* Lazy output by lists (LazyOutputActivations, dnn.cc:355-392), tests and tools.
+ * fdnn_debug_lists_check     the validator of the host entry points, host code, no device needed: 0, or -(row + 1) of the
+ *   first row whose list is not well formed (row_ptr[0] != 0 answers as row 0).
+ * fdnn_debug_ctx_lists_acc   acc [nnz]: the int32 accumulators as the score kernel of a plain call holds them (a
+ *   wave-uniform branch of the same kernel, not a second one); otherwise as fdnn_ctx_lazy_output_lists (dnn.cc:355-392).
+ * fdnn_debug_lists_launches  process-wide launch counts since load, returns 3: out[0] score kernel without the walk over
+ *   saturating pairs, [1] with it, [2] the finish kernel.  (Not in the launch recorder's table: see fdnn_note.hpp;
+ *   dnn.cc:355-392 is what the kernels compute.) */
+FDNN_API int fdnn_debug_lists_check(const int32_t *row_ptr, const int32_t *nodes, int count, int output_dim);
+FDNN_API int fdnn_debug_ctx_lists_acc(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, int32_t *acc);
+FDNN_API int fdnn_debug_lists_launches(unsigned long long *out, int cap);
 
 /* Tests: write the word a fused soft-max workgroup raises (in host memory) when it gives up waiting for its frame tile's
  * siblings -- 1: as if a launch of this model had just done so (from the next call on the model runs the unfused soft-max
