@@ -127,6 +127,13 @@ SIGNATURES = {
     "fdnn_debug_lists_check": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.c_int]),
     "fdnn_debug_ctx_lists_acc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, _c_i32p, _c_i32p]),
     "fdnn_debug_lists_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_ctx_lazy_output_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p]),
+    "fdnn_ctx_lazy_output_set_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_lazy_set": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p]),
+    "fdnn_debug_set_check": (C.c_int, [_c_i32p, C.c_int, C.c_int]),
+    "fdnn_debug_ctx_set_acc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, C.c_int, _c_i32p]),
+    "fdnn_debug_set_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_set_kernel": (C.c_int, [C.c_int]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_profile_begin": (C.c_int, [C.c_void_p]),
@@ -324,6 +331,39 @@ def lists_launches():
     return tuple(int(v) for v in buf)
 
 
+# The set kernel's tiles (fdnn_set.hpp: kNodeTile, kFrameTile; tests/test_lazy_set_host.py holds the two files together)
+SET_NODE_TILE = 64
+SET_FRAME_TILE = 32
+
+
+def _set(nodes):
+    """The node set as a C-contiguous int32 vector."""
+    nd = np.ascontiguousarray(nodes, dtype=np.int32)
+    if nd.ndim != 1:
+        raise ValueError("nodes must be [len]")
+    return nd
+
+
+def set_check(nodes, outputDimension: int) -> int:
+    """The validator of the set entry points (``fdnn_debug_set_check``; host code, no device): 0, or -1 for a set that does
+    not ascend strictly inside [0, outputDimension)."""
+    nd = _set(nodes)
+    return int(lib().fdnn_debug_set_check(nd.ctypes.data_as(_c_i32p), nd.size, int(outputDimension)))
+
+
+def set_launches():
+    """Process-wide counts since load: (MFMA set kernel without the pair walk, with it, calls served by the list kernels)."""
+    buf = (C.c_ulonglong * 3)()
+    if lib().fdnn_debug_set_launches(buf, 3) != 3:
+        raise RuntimeError("fdnn_debug_set_launches")
+    return tuple(int(v) for v in buf)
+
+
+def set_kernel(mode: int) -> None:
+    """Process-wide (``fdnn_debug_set_kernel``): 0 the default rule, 1 the MFMA kernel where its shape applies, 2 the fallback."""
+    _check(lib().fdnn_debug_set_kernel(int(mode)))
+
+
 class LazyContext:
     """``QuantizedDnn.LazyContext`` (QuantizedDnn.java:72-98)."""
 
@@ -395,6 +435,31 @@ class LazyContext:
         acc = np.zeros(max(int(rp[-1]), 0), dtype=np.int32)
         _check(lib().fdnn_debug_ctx_lists_acc(self.handle, int(first), rp.size - 1, rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p),
                                               acc.ctypes.data_as(_c_i32p)))
+        return acc
+
+    def calculateForOutputNodeSet(self, nodes, first: int = 0, count=None):
+        """Lazy output for ONE node set shared by rows first .. first + count - 1 (``fdnn_ctx_lazy_output_set``; count: up
+        to the context's last row): nodes int32 [len] ascending -> (probs [count][len], inactive [count]), the bytes of
+        ``calculateForOutputNodesLists`` with the set as every row's list."""
+        nd = _set(nodes)
+        count = self.inputVectorCount - int(first) if count is None else int(count)
+        probs = np.empty((max(count, 0), nd.size), dtype=np.float32)
+        inactive = np.empty(max(count, 0), dtype=np.float32)
+        _check(lib().fdnn_ctx_lazy_output_set(self.handle, int(first), count, nd.ctypes.data_as(_c_i32p), nd.size, probs.ctypes.data_as(_c_f32p),
+                                              inactive.ctypes.data_as(_c_f32p)))
+        return probs, inactive
+
+    def calculateForOutputNodeSetDevice(self, d_nodes: int, length: int, d_probs: int, d_inactive: int, first: int, count: int, stream: int = 0) -> None:
+        """The same on device buffers, enqueued on ``stream``, not synchronised; the set is not validated (fdnn.h)."""
+        _check(lib().fdnn_ctx_lazy_output_set_device(self.handle, int(first), int(count), C.c_void_p(d_nodes), int(length), C.c_void_p(d_probs),
+                                                     C.c_void_p(d_inactive), C.c_void_p(stream)))
+
+    def setAccumulators(self, nodes, first: int = 0, count=None) -> np.ndarray:
+        """Parity tests: the int32 accumulators [count][len] as the set kernel holds them (``fdnn_debug_ctx_set_acc``)."""
+        nd = _set(nodes)
+        count = self.inputVectorCount - int(first) if count is None else int(count)
+        acc = np.zeros((max(count, 0), nd.size), dtype=np.int32)
+        _check(lib().fdnn_debug_ctx_set_acc(self.handle, int(first), count, nd.ctypes.data_as(_c_i32p), nd.size, acc.ctypes.data_as(_c_i32p)))
         return acc
 
     # device-resident forms (raw device pointers, e.g. ``tensor.data_ptr()``; enqueued on ``stream``)
@@ -772,6 +837,20 @@ class QuantizedDnn:
         _check(lib().fdnn_calculate_lazy_lists(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(),
                                                rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p), probs.ctypes.data_as(_c_f32p),
                                                inactive.ctypes.data_as(_c_f32p)))
+        return probs, inactive
+
+    def calculateLazySet(self, input, nodes):
+        """One-call lazy scoring of ONE node set for every frame (``fdnn_calculate_lazy_set``): hidden layers, then the set
+        -> (probs [frames][len], inactive [frames]), as ``LazyContext.calculateForOutputNodeSet``."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        nd = _set(nodes)
+        probs = np.empty((n, nd.size), dtype=np.float32)
+        inactive = np.empty(n, dtype=np.float32)
+        _check(lib().fdnn_calculate_lazy_set(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(),
+                                             nd.ctypes.data_as(_c_i32p), nd.size, probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p)))
         return probs, inactive
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:

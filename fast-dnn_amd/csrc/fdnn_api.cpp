@@ -5,6 +5,7 @@
 #include <emmintrin.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -376,6 +377,80 @@ int fdnn_calculate_lazy_lists(fdnn_model *m, const float *x, int n, int dim, con
   if (int rc = lists_validate(row_ptr, nodes, n, m->hm.hdr.out_dim)) return rc;
   if (row_ptr[n] > 0 && !probs) return fail(FDNN_E_ARG, "null buffer");
   return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_lazy_lists", .x = x, .row_ptr = row_ptr, .nodes = nodes, .probs = probs, .inactive = inactive});
+}
+
+// ---------------------------------------------------------------- lazy output for a shared node set (fdnn_set.hip)
+// The set is the one-row list {0, len} (fdnn_lists.hpp: check)
+static int set_validate(const int32_t *nodes, int len, int output_dim) {
+  if (len < 0) return fail(FDNN_E_ARG, "negative set length");
+  const int32_t row_ptr[2] = {0, len};
+  if (!lists::check(row_ptr, nodes, 1, output_dim)) return FDNN_OK;
+  return fail(FDNN_E_ARG, "node set: the nodes must ascend strictly inside [0, " + std::to_string(output_dim) + ")");
+}
+
+static int ctx_set_host(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive, int32_t *acc) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
+  if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
+  if (int rc = set_validate(nodes, len, c->m->hm.hdr.out_dim)) return rc;
+  if (static_cast<long long>(count) * len > INT32_MAX) return fail(FDNN_E_ARG, "count x len must fit an int32");
+  if (count == 0) return FDNN_OK;
+  if ((!acc && !inactive) || (len > 0 && !acc && !probs)) return fail(FDNN_E_ARG, "null result buffer");
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  return set_to_host(c, first, count, nodes, len, probs, inactive, acc, c->stream);
+}
+
+int fdnn_ctx_lazy_output_set(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive) {
+  return ctx_set_host(c, first, count, nodes, len, probs, inactive, nullptr);
+}
+
+int fdnn_debug_ctx_set_acc(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, int32_t *acc) {
+  if (!acc) return fail(FDNN_E_ARG, "null argument");
+  return ctx_set_host(c, first, count, nodes, len, nullptr, nullptr, acc);
+}
+
+int fdnn_ctx_lazy_output_set_device(fdnn_ctx *c, int first, int count, const int32_t *d_nodes, int len, float *d_probs, float *d_inactive,
+                                    void *stream) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  return run_set(c, {first, count, d_nodes, len, d_probs, d_inactive, nullptr}, s);
+}
+
+int fdnn_debug_set_check(const int32_t *nodes, int len, int output_dim) {
+  if (len < 0 || (len > 0 && !nodes)) return fail(FDNN_E_ARG, "bad argument");
+  const int32_t row_ptr[2] = {0, len};
+  return lists::check(row_ptr, nodes, 1, output_dim);
+}
+
+int fdnn_debug_set_launches(unsigned long long *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  unsigned long long v[3];
+  fdnn::set_launch_counts(v);
+  for (int i = 0; i < 3 && i < cap; ++i) out[i] = v[i];
+  return 3;
+}
+
+int fdnn_debug_set_kernel(int mode) {
+  if (mode < 0 || mode > 2) return fail(FDNN_E_ARG, "mode is 0 (the default rule), 1 (the MFMA kernel) or 2 (the list kernels)");
+  fdnn::set_kernel_mode(mode);
+  return FDNN_OK;
+}
+
+// One-call form: hidden layers + the set on a pooled context, a large n chunk by chunk, every chunk with the same set.
+int fdnn_calculate_lazy_set(fdnn_model *m, const float *x, int n, int dim, const int32_t *nodes, int len, float *probs, float *inactive) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = set_validate(nodes, len, m->hm.hdr.out_dim)) return rc;
+  if (static_cast<long long>(n) * len > INT32_MAX) return fail(FDNN_E_ARG, "count x len must fit an int32");
+  if (n == 0) return FDNN_OK;
+  if (!x || !inactive || (len > 0 && !probs)) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  return score_chunks(m, frame_chunks(n, m),
+                      {.who = "fdnn_calculate_lazy_set", .x = x, .probs = probs, .inactive = inactive, .set_nodes = nodes, .set_len = len, .set_given = true});
 }
 
 int fdnn_ctx_lazy_output(fdnn_ctx *c, int frame, const int8_t *mask, float *out) {

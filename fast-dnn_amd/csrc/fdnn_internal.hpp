@@ -128,6 +128,8 @@ struct fdnn_ctx {
   // allocated on the first list call and grown by the largest one
   fdnn::DevBuf<int32_t> d_lrow, d_lnodes;   // [count + 1], [nnz]
   fdnn::DevBuf<float> d_lprobs, d_linact;   // [nnz], [count]
+  // set calls served by the list kernels (run_set's fallback): the set as lists, row_ptr [count + 1] and nodes [count * len]
+  fdnn::DevBuf<int32_t> d_srow, d_snodes;
   int last = -1;                  // d_act index holding the last hidden layer, -1 = not computed
   bool pooled = false;
   bool no_fuse = false;           // this call must not use the fused soft-max
@@ -195,6 +197,19 @@ int run_lists(fdnn_ctx *c, const ListsCall &lc, hipStream_t s);
 // The host form of the same: validated lists up, results back, synchronises s.  acc (parity tests) may be null.
 int lists_to_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive,
                   int32_t *acc, hipStream_t s);
+// The same contract with ONE node set for rows [first, first + count) (fdnn_set.hip): d_nodes [len], d_probs [count][len],
+// d_inactive [count]; enqueued on s.  d_acc [count][len] (parity tests) may be null.
+struct SetCall {
+  int first = 0, count = 0;
+  const int32_t *d_nodes = nullptr;
+  int len = 0;
+  float *d_probs = nullptr;
+  float *d_inactive = nullptr;
+  int32_t *d_acc = nullptr;
+};
+int run_set(fdnn_ctx *c, const SetCall &sc, hipStream_t s);
+// The host form: a validated set up, results back, synchronises s.  acc (parity tests) may be null.
+int set_to_host(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive, int32_t *acc, hipStream_t s);
 int build_lists_index(fdnn_model *m);  // the per-node pair index of the output layer, from m->hm (model load / blob import)
 int device_cus(int device);            // CUs of a device, asked once (256 where the runtime cannot say)
 // Will run_output scale the soft-max inside the output kernel for such a call (dense, large batch)?  Then there is no
@@ -281,6 +296,11 @@ struct ScorePass {
   // lists instead of a mask (host rows only): the call's row_ptr [n + 1] and nodes; results probs [nnz], inactive [n]
   const int32_t *row_ptr = nullptr, *nodes = nullptr;
   float *probs = nullptr, *inactive = nullptr;
+  // or one node set for every row (host rows only): set_given, set_nodes [set_len] (null for an empty set); results
+  // probs [n][set_len], inactive [n]
+  const int32_t *set_nodes = nullptr;
+  int set_len = 0;
+  bool set_given = false;
   // results: device rows, enqueued on `stream` (the caller's) -- or host rows on the context's own stream, synchronised:
   // dense through dense_pass_to_host and its re-run rules, with host bits through lazy_copy_out
   float *d_out = nullptr;

@@ -8,6 +8,7 @@
 #include "fdnn_ctx_layout.hpp"  // kMaxFrameTile, kPartialNodes, kL0ScreenCap, l0_split_plane_bytes
 #include "fdnn_note.hpp"
 #include "fdnn_select.hpp"
+#include "fdnn_set.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -178,12 +179,13 @@ struct ListsParams {
   const int32_t *wsum;        // [rows_pad] 128 * sum_k w
   const int32_t *fix_off;     // [rows + 1] a node's saturating pairs in fix_pairs; both null: the layer has none
   const uint32_t *fix_pairs;  // k | w0 << 16 | w1 << 24
-  const int32_t *row_ptr;     // [count + 1]
+  const int32_t *row_ptr;     // [count + 1]; null (finish only): every row has row_len entries, row r at r * row_len
   const int32_t *nodes;       // [nnz]
   float *probs;               // [nnz]
   float *inactive;            // [count]
   int32_t *acc;               // [nnz] the int32 accumulators as the score kernel holds them (parity tests), or null
   int rows, K, ldw, lda, count, nnz;
+  int row_len;                // the uniform row length of a shared node set (fdnn_set.hip), with row_ptr null
   int epg;                    // consecutive entries one 16-lane group scores (lists_entries_per_group)
   float coef, rcp_coef;
   int fastdiv;
@@ -192,6 +194,31 @@ void launch_lists_score(const ListsParams &p, hipStream_t s);
 void launch_lists_finish(const ListsParams &p, hipStream_t s);
 int lists_entries_per_group(long long nnz, int n_cu);
 void lists_launch_counts(unsigned long long out[3]);  // launches so far: score without / with the pair walk, finish
+
+// Lazy output for a shared node set (fdnn_set.hip; the guard and the tile plan: fdnn_set.hpp): e = exp(z) of (row r, entry j)
+// into probs[r * len + j] on the int8 MFMA; launch_lists_finish with row_ptr null and row_len = len then owns the total.
+struct SetParams {
+  const int8_t *w;            // [rows][ldw] the output layer's int8 rows (pad columns zero)
+  const int8_t *a;            // [count][lda] s8 last-hidden activations of the call's rows
+  const float *bias;          // [rows_pad]
+  const int32_t *wsum;        // [rows_pad] 128 * sum_k w
+  const int32_t *fix_off;     // [rows + 1] a node's saturating pairs in fix_pairs; both null: the layer has none
+  const uint32_t *fix_pairs;  // k | w0 << 16 | w1 << 24
+  const int32_t *nodes;       // [len] the set (not validated: fdnn_set.hpp's guard)
+  float *probs;               // [count][len]
+  int32_t *acc;               // [count][len] the int32 accumulators as the kernel holds them (parity tests), or null
+  int rows, K, ldw, lda, count, len;
+  float coef, rcp_coef;
+  int fastdiv;
+  set::Plan plan;             // set::plan(count, len, CUs)
+};
+void launch_set_score(const SetParams &p, hipStream_t s);
+// The fallback (a layer the MFMA kernel's shape does not apply to, fdnn_debug_set_kernel(2)): the set as lists for the
+// list kernels -- row_ptr[r] = r * len for r in [0, count], rep[r * len + j] = nodes[j].  Counted as set_launch_counts[2].
+void launch_set_expand(const int32_t *nodes, int len, int count, int32_t *row_ptr, int32_t *rep, hipStream_t s);
+void set_launch_counts(unsigned long long out[3]);  // MFMA kernel without / with the pair walk, calls served by the list kernels
+int set_kernel_mode();                              // fdnn_debug_set_kernel: 0 the default rule, 1 MFMA where its shape applies, 2 fallback
+void set_kernel_mode(int mode);
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

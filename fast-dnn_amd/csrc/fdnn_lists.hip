@@ -126,12 +126,15 @@ __global__ __launch_bounds__(kLsThreads) void lists_score_kernel(ListsParams p) 
   }
 }
 
+// UNIFORM: every row has p.row_len entries and there is no row_ptr (a shared node set, fdnn_set.hip): row r is
+// [r * row_len, (r + 1) * row_len).  The order below is the same instruction for instruction.
+template <bool UNIFORM>
 __global__ __launch_bounds__(kLsThreads) void lists_finish_kernel(ListsParams p) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * (kLsThreads / 64) + (threadIdx.x >> 6);
   if (r >= p.count) return;  // (whole waves)
-  const int b = max(0, min(p.nnz, p.row_ptr[r]));
-  const int e = max(b, min(p.nnz, p.row_ptr[r + 1]));
+  const int b = UNIFORM ? r * p.row_len : max(0, min(p.nnz, p.row_ptr[r]));
+  const int e = UNIFORM ? b + p.row_len : max(b, min(p.nnz, p.row_ptr[r + 1]));
   float s = 0.0f;
   for (int i = b + lane; i < e; i += 64) s += p.probs[i];
   s += __shfl_xor(s, 32);
@@ -168,7 +171,11 @@ void launch_lists_finish(const ListsParams &p, hipStream_t s) {
   if (p.count <= 0) return;
   g_lists_launches[2].fetch_add(1, std::memory_order_relaxed);
   const int rows_per_block = kLsThreads / 64;
-  hipLaunchKernelGGL(lists_finish_kernel, dim3((p.count + rows_per_block - 1) / rows_per_block), dim3(kLsThreads), 0, s, p);
+  const dim3 grid((p.count + rows_per_block - 1) / rows_per_block);
+  if (p.row_ptr != nullptr)
+    hipLaunchKernelGGL(lists_finish_kernel<false>, grid, dim3(kLsThreads), 0, s, p);
+  else
+    hipLaunchKernelGGL(lists_finish_kernel<true>, grid, dim3(kLsThreads), 0, s, p);
 }
 
 // Entries per 16-lane group: as many as leave the launch about four workgroups per CU -- one frame's 3 200 entries spread

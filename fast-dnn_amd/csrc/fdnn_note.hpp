@@ -7,6 +7,9 @@
 // Not in the table yet: the two kernels of lazy output by lists (fdnn_lists.hip: score with / without the pair walk, finish).
 // They are counted by a counter of their own (fdnn_debug_lists_launches) because every name here needs a ledger case; a
 // later change that adds those cases can fold them in as "lists.score.fix", "lists.score.nofix" and "lists.finish".
+// Likewise the kernel of lazy output for a shared node set (fdnn_set.hip: with / without the pair walk) and its fallback to
+// the list kernels: fdnn_debug_set_launches counts them; as names they would be "set.score.fix", "set.score.nofix" and
+// "set.fallback" (the set path's finish launch is the list path's and is counted there).
 #pragma once
 #include <atomic>
 

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -675,40 +676,47 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
 
 // LazyOutputActivations for the listed nodes only (fdnn_lists.hip): the score kernel over the flat entry array, then one
 // wave per row for the total and the scale.  Nothing of the masked output path runs.
-int run_lists(fdnn_ctx *c, const ListsCall &lc, hipStream_t s) {
-  fdnn_model *m = c->m;
+// What the list kernels and the set kernel read of the output layer (a context whose hidden layers have run).
+static fdnn::ListsParams output_layer_params(const fdnn_ctx *c, int first) {
+  const fdnn_model *m = c->m;
   const BlobHeader &h = m->hm.hdr;
   const QLayerDesc &d = h.q[h.n_q - 1];
-  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
-  if (lc.first < 0 || lc.count < 0 || lc.first + lc.count > c->n) return fail(FDNN_E_ARG, "frame range outside the context");
-  if (lc.nnz < 0) return fail(FDNN_E_ARG, "negative entry count");
-  if (lc.count == 0) return FDNN_OK;
-  if (!lc.d_row_ptr || !lc.d_inactive || (lc.nnz > 0 && (!lc.d_nodes || !lc.d_probs))) return fail(FDNN_E_ARG, "null list buffer");
   const uint8_t *B = m->d_blob;
   fdnn::ListsParams g{};
   g.w = reinterpret_cast<const int8_t *>(B + d.off_w);
-  g.a = c->d_act[c->last] + size_t(lc.first) * c->act_ld;
+  g.a = c->d_act[c->last] + size_t(first) * c->act_ld;
   g.bias = reinterpret_cast<const float *>(B + d.off_bias);
   g.wsum = reinterpret_cast<const int32_t *>(B + d.off_wsum);
   if (d.n_fix > 0) {
     g.fix_off = m->d_lfix_off;
     g.fix_pairs = m->d_lfix_pairs;
   }
+  g.rows = d.rows;
+  g.K = d.cols_pad - fdnn::kRowSkew;
+  g.ldw = d.cols_pad;
+  g.lda = c->act_ld;
+  g.coef = d.coef;
+  g.rcp_coef = d.rcp_coef;
+  g.fastdiv = d.fastdiv_ok;
+  return g;
+}
+
+int run_lists(fdnn_ctx *c, const ListsCall &lc, hipStream_t s) {
+  fdnn_model *m = c->m;
+  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
+  if (lc.first < 0 || lc.count < 0 || lc.first + lc.count > c->n) return fail(FDNN_E_ARG, "frame range outside the context");
+  if (lc.nnz < 0) return fail(FDNN_E_ARG, "negative entry count");
+  if (lc.count == 0) return FDNN_OK;
+  if (!lc.d_row_ptr || !lc.d_inactive || (lc.nnz > 0 && (!lc.d_nodes || !lc.d_probs))) return fail(FDNN_E_ARG, "null list buffer");
+  fdnn::ListsParams g = output_layer_params(c, lc.first);
   g.row_ptr = lc.d_row_ptr;
   g.nodes = lc.d_nodes;
   g.probs = lc.d_probs;
   g.inactive = lc.d_inactive;
   g.acc = lc.d_acc;
-  g.rows = d.rows;
-  g.K = d.cols_pad - fdnn::kRowSkew;
-  g.ldw = d.cols_pad;
-  g.lda = c->act_ld;
   g.count = lc.count;
   g.nnz = lc.nnz;
   g.epg = fdnn::lists_entries_per_group(lc.nnz, device_cus(m->device));
-  g.coef = d.coef;
-  g.rcp_coef = d.rcp_coef;
-  g.fastdiv = d.fastdiv_ok;
   {
     ProfScope ps(m, s, FDNN_PROF_OUTPUT);
     fdnn::launch_lists_score(g, s);
@@ -734,6 +742,77 @@ int lists_to_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, con
   HIP_TRY(hipMemcpyAsync(c->d_lrow, row_ptr, sizeof(int32_t) * (size_t(count) + 1), hipMemcpyHostToDevice, s));
   if (nnz) HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, s));
   int rc = run_lists(c, {first, count, c->d_lrow, c->d_lnodes, int(nnz), c->d_lprobs, c->d_linact, acc ? d_acc.p : nullptr}, s);
+  if (rc) {
+    hipStreamSynchronize(s);
+    return rc;
+  }
+  if (nnz && probs) HIP_TRY(hipMemcpyAsync(probs, c->d_lprobs, sizeof(float) * nnz, hipMemcpyDeviceToHost, s));
+  if (inactive) HIP_TRY(hipMemcpyAsync(inactive, c->d_linact, sizeof(float) * size_t(count), hipMemcpyDeviceToHost, s));
+  if (nnz && acc) HIP_TRY(hipMemcpyAsync(acc, d_acc, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FDNN_OK;
+}
+
+// LazyOutputActivations for ONE node set shared by rows [first, first + count) (fdnn_set.hip): e = exp(z) of the gathered
+// rows on the int8 MFMA, then the list path's finish kernel with the uniform row stride len.  Where the MFMA kernel's shape
+// does not apply (fdnn_set.hpp: shape_applies) the list kernels serve the call over lists synthesized from the set: the
+// same bytes by construction.
+int run_set(fdnn_ctx *c, const SetCall &sc, hipStream_t s) {
+  fdnn_model *m = c->m;
+  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
+  if (sc.first < 0 || sc.count < 0 || sc.first + sc.count > c->n) return fail(FDNN_E_ARG, "frame range outside the context");
+  if (sc.len < 0 || sc.len > m->hm.hdr.out_dim) return fail(FDNN_E_ARG, "a node set has 0 .. output_dim nodes");
+  const long long nnz = static_cast<long long>(sc.count) * sc.len;
+  if (nnz > INT32_MAX) return fail(FDNN_E_ARG, "count x len must fit an int32");
+  if (sc.count == 0) return FDNN_OK;
+  if (!sc.d_inactive || (sc.len > 0 && (!sc.d_nodes || !sc.d_probs))) return fail(FDNN_E_ARG, "null set buffer");
+  fdnn::ListsParams g = output_layer_params(c, sc.first);
+  g.probs = sc.d_probs;
+  g.inactive = sc.d_inactive;
+  g.acc = sc.d_acc;
+  g.count = sc.count;
+  g.nnz = int(nnz);
+  // the default rule (mode 0) is mode 1's: the MFMA kernel wherever its shape applies
+  const bool mfma = fdnn::set_kernel_mode() != 2 && fdnn::set::shape_applies(g.K, g.rows, g.ldw, g.lda);
+  if (sc.len > 0 && mfma) {
+    fdnn::SetParams p{};
+    p.w = g.w, p.a = g.a, p.bias = g.bias, p.wsum = g.wsum, p.fix_off = g.fix_off, p.fix_pairs = g.fix_pairs;
+    p.nodes = sc.d_nodes, p.probs = sc.d_probs, p.acc = sc.d_acc;
+    p.rows = g.rows, p.K = g.K, p.ldw = g.ldw, p.lda = g.lda, p.count = sc.count, p.len = sc.len;
+    p.coef = g.coef, p.rcp_coef = g.rcp_coef, p.fastdiv = g.fastdiv;
+    p.plan = fdnn::set::plan(sc.count, sc.len, device_cus(m->device));
+    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
+    fdnn::launch_set_score(p, s);
+  } else if (sc.len > 0) {
+    // (a buffer that is too small is freed and allocated anew, which waits for the device: earlier calls have finished)
+    HIP_TRY(c->d_srow.reserve(size_t(sc.count) + 1));
+    HIP_TRY(c->d_snodes.reserve(size_t(nnz)));
+    fdnn::launch_set_expand(sc.d_nodes, sc.len, sc.count, c->d_srow, c->d_snodes, s);
+    g.row_ptr = c->d_srow;
+    g.nodes = c->d_snodes;
+    g.epg = fdnn::lists_entries_per_group(nnz, device_cus(m->device));
+    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
+    fdnn::launch_lists_score(g, s);
+  }
+  if (!g.row_ptr) g.row_len = sc.len;  // the finish kernel's uniform rows: r * len .. (r + 1) * len
+  {
+    ProfScope ps(m, s, FDNN_PROF_NORMALIZE);
+    fdnn::launch_lists_finish(g, s);
+  }
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+int set_to_host(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive, int32_t *acc, hipStream_t s) {
+  if (len < 0 || static_cast<long long>(count) * len > INT32_MAX) return fail(FDNN_E_ARG, "count x len must fit an int32");
+  const size_t nnz = size_t(count) * size_t(len);
+  HIP_TRY(c->d_linact.reserve(std::max<size_t>(size_t(count), 1)));
+  HIP_TRY(c->d_lnodes.reserve(std::max<size_t>(size_t(len), 1)));
+  HIP_TRY(c->d_lprobs.reserve(std::max<size_t>(nnz, 1)));
+  DevBuf<int32_t> d_acc;
+  if (acc) HIP_TRY(d_acc.reserve(std::max<size_t>(nnz, 1)));
+  if (len) HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * size_t(len), hipMemcpyHostToDevice, s));
+  int rc = run_set(c, {first, count, c->d_lnodes, len, c->d_lprobs, c->d_linact, acc ? d_acc.p : nullptr}, s);
   if (rc) {
     hipStreamSynchronize(s);
     return rc;
@@ -1061,6 +1140,12 @@ int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, 
       lists::rebase_rows(p.row_ptr, int(off), cnt, &rebased);
       const size_t e0 = size_t(p.row_ptr[off]);
       if (!rc) rc = lists_to_host(c, 0, cnt, rebased.data(), p.nodes + e0, p.probs + e0, p.inactive + off, nullptr, s);
+      if (rc) hipStreamSynchronize(s);
+      continue;
+    }
+    if (p.set_given) {  // one node set for every chunk: the chunk's rows land at probs + off * len
+      rc = run_hidden(c, c->d_x, s, nullptr);
+      if (!rc) rc = set_to_host(c, 0, cnt, p.set_nodes, p.set_len, p.probs + off * size_t(p.set_len), p.inactive + off, nullptr, s);
       if (rc) hipStreamSynchronize(s);
       continue;
     }

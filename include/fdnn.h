@@ -239,6 +239,28 @@ FDNN_API int fdnn_ctx_lazy_output_lists_device(fdnn_ctx *c, int first, int count
                                                int nnz, float *d_probs, float *d_inactive, void *stream);
 FDNN_API int fdnn_calculate_lazy_lists(fdnn_model *m, const float *x, int n, int dim, const int32_t *row_ptr, const int32_t *nodes,
                                        float *probs, float *inactive);
+/* Lazy output for ONE NODE SET shared by a row range: the list contract above with the same list in every row -- forced
+ * alignment (the transcript's states), keyword spotting, n-best rescoring.  The set's weight rows are read once per frame
+ * tile and scored on the int8 matrix pipe (fdnn_set.hip) instead of once per (row, node).
+ *   nodes    [len] int32, strictly ascending, each in [0, output_dim), 0 <= len <= output_dim
+ *   probs    [count][len] row-major: probs[r][j] = node nodes[j]'s probability in row first + r under the lazy contract
+ *   inactive [count]: the 1 / total every unlisted node of that row reads.  len == 0 gives 1 / output_dim per row and no
+ *            probs; len == output_dim is the dense soft-max.  count x len must fit an int32 (FDNN_E_ARG otherwise).
+ * The result for (row, set) is byte-identical to fdnn_ctx_lazy_output_lists called with the set as every row's list: a
+ * row's bytes depend on the row and the set only, not on first, count or the entry point.  Several utterances in one
+ * context: one call per utterance's row range.
+ * fdnn_ctx_lazy_output_set         host buffers, host-synchronous; validates the set (FDNN_E_ARG for a malformed set or
+ *   rows outside the context, FDNN_E_STATE before the hidden layers).
+ * fdnn_ctx_lazy_output_set_device  device buffers, enqueued on `stream`, not synchronised, ordered on the context like the
+ *   other *_device entries.  The set is NOT validated: a node outside [0, output_dim) is never used as an address, its
+ *   column's e is NaN, so every row's entries and inactive value come back NaN.
+ * fdnn_calculate_lazy_set          one call: pooled context, hidden layers + the set; a large n goes chunk by chunk
+ *   (fdnn_debug_frame_chunks), every chunk with the same set.  LazyOutputActivations, dnn.cc:355-392. */
+FDNN_API int fdnn_ctx_lazy_output_set(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive);
+FDNN_API int fdnn_ctx_lazy_output_set_device(fdnn_ctx *c, int first, int count, const int32_t *d_nodes, int len, float *d_probs,
+                                             float *d_inactive, void *stream);
+FDNN_API int fdnn_calculate_lazy_set(fdnn_model *m, const float *x, int n, int dim, const int32_t *nodes, int len, float *probs,
+                                     float *inactive);
 /* Dense output layer over the context's hidden activations
  * (CalculateOutput, dnn.cc:428-454). */
 FDNN_API int fdnn_ctx_output(fdnn_ctx *c, float *out);
@@ -440,6 +462,21 @@ FDNN_API int fdnn_debug_launch_counts(unsigned long long *out, int cap);
 FDNN_API int fdnn_debug_lists_check(const int32_t *row_ptr, const int32_t *nodes, int count, int output_dim);
 FDNN_API int fdnn_debug_ctx_lists_acc(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, int32_t *acc);
 FDNN_API int fdnn_debug_lists_launches(unsigned long long *out, int cap);
+
+/* Lazy output for a shared node set (LazyOutputActivations, dnn.cc:355-392), tests and tools.
+ * fdnn_debug_set_check     the validator of the host entry points, host code, no device needed: 0, or -1 for a set that is
+ *   not strictly ascending inside [0, output_dim).
+ * fdnn_debug_ctx_set_acc   acc [count][len]: the int32 accumulators as the set kernel holds them (a wave-uniform branch of
+ *   the same kernel, not a second one); otherwise as fdnn_ctx_lazy_output_set (dnn.cc:355-392).
+ * fdnn_debug_set_launches  process-wide counts since load, returns 3: out[0] the MFMA set kernel without the walk over
+ *   saturating pairs, [1] with it, [2] calls served by the list kernels as fallback.  (Not in the launch recorder's table:
+ *   see fdnn_note.hpp.)
+ * fdnn_debug_set_kernel    process-wide: 0 the default rule, 1 always the MFMA kernel where its shape applies, 2 always
+ *   the fallback (the list kernels over the set as lists: the same bytes; dnn.cc:355-392 either way). */
+FDNN_API int fdnn_debug_set_check(const int32_t *nodes, int len, int output_dim);
+FDNN_API int fdnn_debug_ctx_set_acc(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, int32_t *acc);
+FDNN_API int fdnn_debug_set_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_set_kernel(int mode);
 
 /* Tests: write the word a fused soft-max workgroup raises (in host memory) when it gives up waiting for its frame tile's
  * siblings -- 1: as if a launch of this model had just done so (from the next call on the model runs the unfused soft-max
