@@ -51,7 +51,7 @@ def _oracle_dense10k(net_model_path, x):
         orc = Oracle(net_model_path)
         hid = orc.hidden_acts_mt(x)
         probs, acc = orc.output_mt(hid, want_acc=True)
-        _, taps = orc.calculate(x[:8], taps=True)  # (the gauss net does saturate: the fix-up walk is exercised)
+        _, taps = orc.calculate(x[:8], taps=True)  # (the gauss net saturates on about 23 entries, the same ones on every frame: tests/test_gpu_sat_lone_frame.py has the lone-frame events)
         _ORACLE_CACHE["dense10k"] = (hid, probs, acc, taps["sat_events"])
     return _ORACLE_CACHE["dense10k"]
 
