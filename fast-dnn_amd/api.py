@@ -134,6 +134,14 @@ SIGNATURES = {
     "fdnn_debug_ctx_set_acc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, C.c_int, _c_i32p]),
     "fdnn_debug_set_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_debug_set_kernel": (C.c_int, [C.c_int]),
+    "fdnn_ctx_lazy_output_sets": (C.c_int, [C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_f32p, _c_f32p]),
+    "fdnn_ctx_lazy_output_sets_device": (C.c_int, [C.c_void_p, _c_i32p, _c_i32p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_lazy_sets": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_f32p, _c_f32p]),
+    "fdnn_debug_sets_check": (C.c_int, [_c_i32p, _c_i32p, _c_i32p, C.c_int, C.c_int, C.c_int]),
+    "fdnn_debug_ctx_sets_acc": (C.c_int, [C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p]),
+    "fdnn_debug_sets_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_server_submit_lazy_set": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, C.POINTER(C.c_uint64)]),
+    "fdnn_server_submit_raw_set": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, C.POINTER(C.c_uint64)]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_profile_begin": (C.c_int, [C.c_void_p]),
@@ -364,6 +372,44 @@ def set_kernel(mode: int) -> None:
     _check(lib().fdnn_debug_set_kernel(int(mode)))
 
 
+def _sets(segRows, setPtr, nodes):
+    """(seg_rows, set_ptr, nodes) as C-contiguous int32 vectors of the shapes every sets entry point needs -> them, the
+    segment count, the rows and the floats of probs."""
+    sr = np.ascontiguousarray(segRows, dtype=np.int32)
+    sp = np.ascontiguousarray(setPtr, dtype=np.int32)
+    nd = np.ascontiguousarray(nodes, dtype=np.int32)
+    if sr.ndim != 1 or sp.ndim != 1 or nd.ndim != 1 or sr.size != sp.size or sr.size < 1:
+        raise ValueError("segRows and setPtr must be [segments + 1] and nodes [setPtr[-1]]")
+    if sp.size and int(sp.max()) > nd.size:  # (the C side reads setPtr[segments] nodes)
+        raise ValueError(f"setPtr reaches {int(sp.max())} but there are {nd.size} nodes")
+    rows = max(int(sr[-1]) - int(sr[0]), 0)
+    nnz = int((np.maximum(np.diff(sr.astype(np.int64)), 0) * np.maximum(np.diff(sp.astype(np.int64)), 0)).sum())
+    return sr, sp, nd, sr.size - 1, rows, nnz
+
+
+def sets_check(segRows, setPtr, nodes, outputDimension: int, contextRows: int) -> int:
+    """The validator of the sets entry points (``fdnn_debug_sets_check``; host code, no device): 0, or -(s + 1) of the first
+    malformed segment s (malformed tables as a whole answer as segment 0)."""
+    sr = np.ascontiguousarray(segRows, dtype=np.int32)
+    sp = np.ascontiguousarray(setPtr, dtype=np.int32)
+    nd = np.ascontiguousarray(nodes, dtype=np.int32)
+    if sr.ndim != 1 or sp.ndim != 1 or nd.ndim != 1 or sr.size != sp.size or sr.size < 1:
+        raise ValueError("segRows and setPtr must be [segments + 1] and nodes [setPtr[-1]]")
+    if sp.size > 1 and int(sp.max()) > nd.size:  # never let the C side read past the node array
+        return -(int(np.argmax(sp[1:] > nd.size)) + 1)
+    return int(lib().fdnn_debug_sets_check(sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p), sr.size - 1,
+                                           int(outputDimension), int(contextRows)))
+
+
+def sets_launches():
+    """Process-wide counts since load: (launches of the segmented MFMA kernel without the pair walk, with it, calls served
+    by the list kernels)."""
+    buf = (C.c_ulonglong * 3)()
+    if lib().fdnn_debug_sets_launches(buf, 3) != 3:
+        raise RuntimeError("fdnn_debug_sets_launches")
+    return tuple(int(v) for v in buf)
+
+
 class LazyContext:
     """``QuantizedDnn.LazyContext`` (QuantizedDnn.java:72-98)."""
 
@@ -460,6 +506,36 @@ class LazyContext:
         count = self.inputVectorCount - int(first) if count is None else int(count)
         acc = np.zeros((max(count, 0), nd.size), dtype=np.int32)
         _check(lib().fdnn_debug_ctx_set_acc(self.handle, int(first), count, nd.ctypes.data_as(_c_i32p), nd.size, acc.ctypes.data_as(_c_i32p)))
+        return acc
+
+    def calculateForOutputNodeSets(self, segRows, setPtr, nodes):
+        """Lazy output with one node set per SEGMENT of a row range, all in one call (``fdnn_ctx_lazy_output_sets``):
+        segment s is rows segRows[s] .. segRows[s + 1] - 1 with the set nodes[setPtr[s]:setPtr[s + 1]] -> (probs, flat: segment
+        s's block [rows_s][len_s] after the blocks before it, inactive [rows]); ``formats.sets_to_lists`` gives the same
+        layout as lists.  A row's bytes are those of ``calculateForOutputNodeSet`` on its segment alone."""
+        sr, sp, nd, n_segs, rows, nnz = _sets(segRows, setPtr, nodes)
+        probs = np.empty(nnz, dtype=np.float32)
+        inactive = np.empty(rows, dtype=np.float32)
+        _check(lib().fdnn_ctx_lazy_output_sets(self.handle, sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, nd.ctypes.data_as(_c_i32p),
+                                               probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p)))
+        return probs, inactive
+
+    def calculateForOutputNodeSetsDevice(self, segRows, setPtr, d_nodes: int, d_probs: int, d_inactive: int, stream: int = 0) -> None:
+        """The same on device buffers, enqueued on ``stream``, not synchronised; the tables are host arrays and are read before
+        the call returns, the sets are not validated (fdnn.h)."""
+        sr = np.ascontiguousarray(segRows, dtype=np.int32)
+        sp = np.ascontiguousarray(setPtr, dtype=np.int32)
+        if sr.ndim != 1 or sp.ndim != 1 or sr.size != sp.size or sr.size < 1:
+            raise ValueError("segRows and setPtr must be [segments + 1]")
+        _check(lib().fdnn_ctx_lazy_output_sets_device(self.handle, sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), sr.size - 1,
+                                                      C.c_void_p(d_nodes), C.c_void_p(d_probs), C.c_void_p(d_inactive), C.c_void_p(stream)))
+
+    def setsAccumulators(self, segRows, setPtr, nodes) -> np.ndarray:
+        """Parity tests: the int32 accumulators, flat and ragged like probs, as the kernel holds them (``fdnn_debug_ctx_sets_acc``)."""
+        sr, sp, nd, n_segs, rows, nnz = _sets(segRows, setPtr, nodes)
+        acc = np.zeros(nnz, dtype=np.int32)
+        _check(lib().fdnn_debug_ctx_sets_acc(self.handle, sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, nd.ctypes.data_as(_c_i32p),
+                                             acc.ctypes.data_as(_c_i32p)))
         return acc
 
     # device-resident forms (raw device pointers, e.g. ``tensor.data_ptr()``; enqueued on ``stream``)
@@ -698,6 +774,40 @@ class ScoringServer:
         self._keep[int(t.value)] = (r, b, out)
         return int(t.value), out
 
+    def submitLazySet(self, x, nodes, probs=None, inactive=None):
+        """One utterance's frames with ITS node set through the loop (``fdnn_server_submit_lazy_set``): coalesced with the other
+        callers' set submissions, the output layer is scored for the listed nodes only and only [n][len] + [n] floats come
+        back -> (ticket, probs [n][len], inactive [n]), valid after ``wait(ticket)``; the bytes of ``calculateLazySet``."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.dnn.inputDimension():
+            raise ValueError(f"Input vector size {x.shape[-1]} must be equal with network input size {self.dnn.inputDimension()}")
+        return self._submit_set(lib().fdnn_server_submit_lazy_set, x, x.shape[0], nodes, probs, inactive)
+
+    def submitRawSet(self, raw, nodes, probs=None, inactive=None):
+        """The same for raw feature frames [n][rawDim] of one utterance, spliced on the device by the model's splice spec at
+        submit time (``fdnn_server_submit_raw_set``)."""
+        r = np.ascontiguousarray(raw, dtype=np.float32)
+        spec = self.dnn.spliceSpec()
+        if spec is not None and (r.ndim != 2 or r.shape[1] != spec[1]):
+            raise ValueError(f"raw frames must be [n][{spec[1]}], got {r.shape}")
+        return self._submit_set(lib().fdnn_server_submit_raw_set, r, r.shape[0], nodes, probs, inactive)
+
+    def _submit_set(self, fn, frames, n, nodes, probs, inactive):
+        nd = _set(nodes)
+        if probs is None:
+            probs = np.empty((n, nd.size), dtype=np.float32)
+        elif probs.dtype != np.float32 or probs.shape != (n, nd.size) or not probs.flags.c_contiguous:
+            raise ValueError(f"probs must be a C-contiguous float32 array of shape {(n, nd.size)}")
+        if inactive is None:
+            inactive = np.empty(n, dtype=np.float32)
+        elif inactive.dtype != np.float32 or inactive.shape != (n,) or not inactive.flags.c_contiguous:
+            raise ValueError(f"inactive must be a C-contiguous float32 array of shape {(n,)}")
+        t = C.c_uint64()
+        _check(fn(self.handle, frames.ctypes.data_as(_c_f32p), n, nd.ctypes.data_as(_c_i32p), nd.size, probs.ctypes.data_as(_c_f32p),
+                  inactive.ctypes.data_as(_c_f32p), C.byref(t)))
+        self._keep[int(t.value)] = (frames, probs, inactive)  # (the set itself is copied at submit)
+        return int(t.value), probs, inactive
+
     def wait(self, ticket: int) -> None:
         try:
             _check(lib().fdnn_server_wait(self.handle, ticket))
@@ -851,6 +961,22 @@ class QuantizedDnn:
         inactive = np.empty(n, dtype=np.float32)
         _check(lib().fdnn_calculate_lazy_set(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(),
                                              nd.ctypes.data_as(_c_i32p), nd.size, probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p)))
+        return probs, inactive
+
+    def calculateLazySets(self, input, segRows, setPtr, nodes):
+        """One-call lazy scoring with one node set per segment of the frames (``fdnn_calculate_lazy_sets``; segRows must cover
+        [0, frames)): hidden layers, then the sets -> (probs flat, inactive [frames]), as
+        ``LazyContext.calculateForOutputNodeSets``."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        sr, sp, nd, n_segs, rows, nnz = _sets(segRows, setPtr, nodes)
+        probs = np.empty(nnz, dtype=np.float32)
+        inactive = np.empty(n, dtype=np.float32)
+        _check(lib().fdnn_calculate_lazy_sets(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(),
+                                              sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, nd.ctypes.data_as(_c_i32p),
+                                              probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p)))
         return probs, inactive
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:

@@ -453,6 +453,97 @@ int fdnn_calculate_lazy_set(fdnn_model *m, const float *x, int n, int dim, const
                       {.who = "fdnn_calculate_lazy_set", .x = x, .probs = probs, .inactive = inactive, .set_nodes = nodes, .set_len = len, .set_given = true});
 }
 
+// ---------------------------------------------------------------- lazy output for per-segment node sets (fdnn_sets.hip)
+// FDNN_E_ARG names the first malformed segment (fdnn_sets.hpp: check)
+static int sets_validate(const int32_t *seg_rows, const int32_t *set_ptr, const int32_t *nodes, int n_segs, int output_dim, int ctx_rows) {
+  if (n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
+  const int bad = sets::check(seg_rows, set_ptr, nodes, n_segs, output_dim, ctx_rows);
+  if (!bad) return FDNN_OK;
+  return fail(FDNN_E_ARG, "node sets, segment " + std::to_string(-bad - 1) + ": seg_rows must not decrease inside [0, " + std::to_string(ctx_rows) +
+                              "], set_ptr must begin at 0 and not decrease, a set's nodes must ascend strictly inside [0, " +
+                              std::to_string(output_dim) + ")");
+}
+
+static int ctx_sets_host(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *nodes, float *probs,
+                         float *inactive, int32_t *acc) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
+  if (int rc = sets_validate(seg_rows, set_ptr, nodes, n_segs, c->m->hm.hdr.out_dim, c->n)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  const sets::Tables t{seg_rows, set_ptr, n_segs};
+  const long long nnz = sets::total(t);
+  if (nnz > INT32_MAX) return fail(FDNN_E_ARG, "the sum of rows x len over the segments must fit an int32");
+  const int count = seg_rows[n_segs] - seg_rows[0];
+  if (count == 0) return FDNN_OK;
+  if ((!acc && !inactive) || (nnz > 0 && !acc && !probs)) return fail(FDNN_E_ARG, "null result buffer");
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  return sets_to_host(c, seg_rows[0], sets::slice(t, seg_rows[0], seg_rows[n_segs]), nodes, set_ptr[n_segs], probs, inactive, acc, c->stream);
+}
+
+int fdnn_ctx_lazy_output_sets(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *nodes, float *probs,
+                              float *inactive) {
+  return ctx_sets_host(c, seg_rows, set_ptr, n_segs, nodes, probs, inactive, nullptr);
+}
+
+int fdnn_debug_ctx_sets_acc(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *nodes, int32_t *acc) {
+  if (!acc) return fail(FDNN_E_ARG, "null argument");
+  return ctx_sets_host(c, seg_rows, set_ptr, n_segs, nodes, nullptr, nullptr, acc);
+}
+
+// The tables are host memory and are checked (the plan is made from them); the nodes are on the device and are not.
+int fdnn_ctx_lazy_output_sets_device(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *d_nodes,
+                                     float *d_probs, float *d_inactive, void *stream) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
+  if (n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
+  if (n_segs == 0) return FDNN_OK;
+  if (!seg_rows || !set_ptr || seg_rows[0] < 0 || set_ptr[0] != 0) return fail(FDNN_E_ARG, "node sets, segment 0: malformed tables");
+  for (int s = 0; s < n_segs; ++s)
+    if (seg_rows[s + 1] < seg_rows[s] || seg_rows[s + 1] > c->n || set_ptr[s + 1] < set_ptr[s] || set_ptr[s + 1] - set_ptr[s] > c->m->hm.hdr.out_dim)
+      return fail(FDNN_E_ARG, "node sets, segment " + std::to_string(s) + ": malformed tables");
+  const sets::Tables t{seg_rows, set_ptr, n_segs};
+  if (sets::total(t) > INT32_MAX) return fail(FDNN_E_ARG, "the sum of rows x len over the segments must fit an int32");
+  const std::vector<sets::Seg> segs = sets::slice(t, seg_rows[0], seg_rows[n_segs]);
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  SetsCall sc;
+  sc.first = seg_rows[0], sc.segs = &segs, sc.d_nodes = d_nodes, sc.d_probs = d_probs, sc.d_inactive = d_inactive;
+  return run_sets(c, sc, s);
+}
+
+int fdnn_debug_sets_check(const int32_t *seg_rows, const int32_t *set_ptr, const int32_t *nodes, int n_segs, int output_dim, int ctx_rows) {
+  if (n_segs < 0) return fail(FDNN_E_ARG, "bad argument");
+  return sets::check(seg_rows, set_ptr, nodes, n_segs, output_dim, ctx_rows);
+}
+
+int fdnn_debug_sets_launches(unsigned long long *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  unsigned long long v[3];
+  fdnn::sets_launch_counts(v);
+  for (int i = 0; i < 3 && i < cap; ++i) out[i] = v[i];
+  return 3;
+}
+
+// One-call form: hidden layers + the sets on a pooled context, a large n chunk by chunk, every chunk with its slice of the
+// segments (a segment cut in two keeps its set).
+int fdnn_calculate_lazy_sets(fdnn_model *m, const float *x, int n, int dim, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs,
+                             const int32_t *nodes, float *probs, float *inactive) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = sets_validate(seg_rows, set_ptr, nodes, n_segs, m->hm.hdr.out_dim, n)) return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  const sets::Tables t{seg_rows, set_ptr, n_segs};
+  const long long nnz = sets::total(t);
+  if (nnz > INT32_MAX) return fail(FDNN_E_ARG, "the sum of rows x len over the segments must fit an int32");
+  if (!x || !inactive || (nnz > 0 && !probs)) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_lazy_sets", .x = x, .nodes = nodes, .probs = probs, .inactive = inactive, .sets = &t});
+}
+
 int fdnn_ctx_lazy_output(fdnn_ctx *c, int frame, const int8_t *mask, float *out) {
   return fdnn_ctx_lazy_output_batch(c, frame, 1, mask, out);
 }

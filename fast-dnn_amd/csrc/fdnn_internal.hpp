@@ -210,6 +210,23 @@ struct SetCall {
 int run_set(fdnn_ctx *c, const SetCall &sc, hipStream_t s);
 // The host form: a validated set up, results back, synchronises s.  acc (parity tests) may be null.
 int set_to_host(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive, int32_t *acc, hipStream_t s);
+// The same contract with one node set per SEGMENT of rows [first, first + rows of segs) (fdnn_sets.hip): segs as
+// sets::slice returns them -- consecutive rows from 0, blocks from 0 --, d_nodes the sets that set_off indexes, d_probs the
+// ragged blocks, d_inactive one value per row; enqueued on s.  The launch tables travel as kernel arguments, the row pointer
+// of the finish pass through the context's staging buffer (d_srow).  d_acc (parity tests, ragged like d_probs) may be null.
+struct SetsCall {
+  int first = 0;
+  const std::vector<fdnn::sets::Seg> *segs = nullptr;
+  const int32_t *d_nodes = nullptr;
+  float *d_probs = nullptr;
+  float *d_inactive = nullptr;
+  int32_t *d_acc = nullptr;
+};
+int run_sets(fdnn_ctx *c, const SetsCall &sc, hipStream_t s);
+// The host form: segs of validated tables, all `n_nodes` nodes up, the slice's results back (probs: the slice's blocks, one
+// contiguous range), synchronises s.  acc (parity tests) may be null.
+int sets_to_host(fdnn_ctx *c, int first, const std::vector<fdnn::sets::Seg> &segs, const int32_t *nodes, int n_nodes, float *probs,
+                 float *inactive, int32_t *acc, hipStream_t s);
 int build_lists_index(fdnn_model *m);  // the per-node pair index of the output layer, from m->hm (model load / blob import)
 int device_cus(int device);            // CUs of a device, asked once (256 where the runtime cannot say)
 // Will run_output scale the soft-max inside the output kernel for such a call (dense, large batch)?  Then there is no
@@ -301,6 +318,9 @@ struct ScorePass {
   const int32_t *set_nodes = nullptr;
   int set_len = 0;
   bool set_given = false;
+  // or one node set per segment of the rows (host rows only): the call's tables, seg_rows covering [0, n), and all nodes;
+  // results probs (ragged blocks), inactive [n]
+  const fdnn::sets::Tables *sets = nullptr;
   // results: device rows, enqueued on `stream` (the caller's) -- or host rows on the context's own stream, synchronised:
   // dense through dense_pass_to_host and its re-run rules, with host bits through lazy_copy_out
   float *d_out = nullptr;

@@ -9,6 +9,7 @@
 #include "fdnn_note.hpp"
 #include "fdnn_select.hpp"
 #include "fdnn_set.hpp"
+#include "fdnn_sets.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -219,6 +220,19 @@ void launch_set_expand(const int32_t *nodes, int len, int count, int32_t *row_pt
 void set_launch_counts(unsigned long long out[3]);  // MFMA kernel without / with the pair walk, calls served by the list kernels
 int set_kernel_mode();                              // fdnn_debug_set_kernel: 0 the default rule, 1 MFMA where its shape applies, 2 fallback
 void set_kernel_mode(int mode);
+
+// Lazy output for per-segment node sets (fdnn_sets.hip; tables, launches and slices: fdnn_sets.hpp): the set kernel's tile on
+// up to sets::kMaxSegs segments in one launch.  p carries the layer and a / nodes / probs / acc of the call's first row,
+// whole node array and first block (its count, len and plan are not read); l is passed to the kernel by value.
+// launch_lists_finish with the call's synthesized row_ptr then owns the totals.  fdnn_debug_set_kernel's mode applies.
+void launch_sets_score(const SetParams &p, const sets::Launch &l, hipStream_t s);
+// row_ptr[row0_s + r] = out_off_s + r * len_s for the launch's segments (sets::row_ptr), row_set[row0_s + r] = set_off_s
+// unless row_set is null (sets::row_set), and row_ptr[end_row] = end unless end_row < 0 (the call's last launch).
+void launch_sets_rows(const sets::Launch &l, int32_t *row_ptr, int32_t *row_set, int end_row, int end, hipStream_t s);
+// The fallback: the sets as lists for the list kernels -- rep[row_ptr[r] + j] = nodes[row_set[r] + j] for every row r of
+// the call (sets::row_ptr, sets::row_set, both on the device).  Counted as sets_launch_counts[2], once per call.
+void launch_sets_expand(const int32_t *nodes, const int32_t *row_ptr, const int32_t *row_set, int count, int32_t *rep, hipStream_t s);
+void sets_launch_counts(unsigned long long out[3]);  // MFMA launches without / with the pair walk, calls served by the list kernels
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

@@ -10,6 +10,9 @@
 // Likewise the kernel of lazy output for a shared node set (fdnn_set.hip: with / without the pair walk) and its fallback to
 // the list kernels: fdnn_debug_set_launches counts them; as names they would be "set.score.fix", "set.score.nofix" and
 // "set.fallback" (the set path's finish launch is the list path's and is counted there).
+// And the segmented form of that kernel (fdnn_sets.hip: one set per segment, up to 64 segments in a launch): counted by
+// fdnn_debug_sets_launches, apart from the set kernel's counter; as names "sets.score.fix", "sets.score.nofix" and
+// "sets.fallback".  Its row-pointer and list-writing helpers are not counted: they score nothing.
 #pragma once
 #include <atomic>
 

@@ -824,6 +824,94 @@ int set_to_host(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len
   return FDNN_OK;
 }
 
+// LazyOutputActivations with one node set per segment (fdnn_sets.hip): the set kernel's tile on every segment, at most
+// sets::kMaxSegs segments per launch, then the list path's finish kernel over the row pointer of the ragged blocks.  Where
+// the MFMA kernel's shape does not apply the list kernels serve the call over the sets written out as lists.
+int run_sets(fdnn_ctx *c, const SetsCall &sc, hipStream_t s) {
+  fdnn_model *m = c->m;
+  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
+  if (!sc.segs) return fail(FDNN_E_ARG, "null argument");
+  const std::vector<fdnn::sets::Seg> &segs = *sc.segs;
+  long long nnz = 0;
+  int count = 0;
+  for (size_t i = 0; i < segs.size(); ++i) {
+    const fdnn::sets::Seg &g = segs[i];
+    if (g.rows < 0 || g.row0 != count) return fail(FDNN_E_ARG, "segment " + std::to_string(i) + ": rows must follow the segment before");
+    if (g.len < 0 || g.len > m->hm.hdr.out_dim || g.set_off < 0)
+      return fail(FDNN_E_ARG, "segment " + std::to_string(i) + ": a node set has 0 .. output_dim nodes");
+    if (g.out_off != nnz) return fail(FDNN_E_ARG, "segment " + std::to_string(i) + ": blocks must follow each other");
+    count += g.rows;
+    nnz += static_cast<long long>(g.rows) * g.len;
+    if (nnz > INT32_MAX) return fail(FDNN_E_ARG, "segment " + std::to_string(i) + ": the sum of rows x len must fit an int32");
+  }
+  if (sc.first < 0 || sc.first + count > c->n) return fail(FDNN_E_ARG, "frame range outside the context");
+  if (count == 0) return FDNN_OK;
+  if (!sc.d_inactive || (nnz > 0 && (!sc.d_nodes || !sc.d_probs))) return fail(FDNN_E_ARG, "null set buffer");
+  fdnn::ListsParams g = output_layer_params(c, sc.first);
+  g.probs = sc.d_probs;
+  g.inactive = sc.d_inactive;
+  g.acc = sc.d_acc;
+  g.count = count;
+  g.nnz = int(nnz);
+  const bool mfma = fdnn::set_kernel_mode() != 2 && fdnn::set::shape_applies(g.K, g.rows, g.ldw, g.lda);
+  // the finish pass's row pointer [count + 1] and, for the fallback, where each row's set begins [count], side by side in
+  // the staging buffer: written on the device from the launch tables, so an enqueued call leaves no host memory behind.
+  // (A buffer that is too small is freed and allocated anew, which waits for the device: earlier calls have finished.)
+  HIP_TRY(c->d_srow.reserve(size_t(2) * size_t(count) + 1));
+  int32_t *const d_row_set = mfma ? nullptr : c->d_srow.p + count + 1;
+  const std::vector<fdnn::sets::Launch> launches = fdnn::sets::plan(segs, device_cus(m->device));
+  for (size_t i = 0; i < launches.size(); ++i)
+    fdnn::launch_sets_rows(launches[i], c->d_srow, d_row_set, i + 1 == launches.size() ? count : -1, int(nnz), s);
+  g.row_ptr = c->d_srow;
+  if (nnz > 0 && mfma) {
+    fdnn::SetParams p{};
+    p.w = g.w, p.a = g.a, p.bias = g.bias, p.wsum = g.wsum, p.fix_off = g.fix_off, p.fix_pairs = g.fix_pairs;
+    p.nodes = sc.d_nodes, p.probs = sc.d_probs, p.acc = sc.d_acc;
+    p.rows = g.rows, p.K = g.K, p.ldw = g.ldw, p.lda = g.lda;
+    p.coef = g.coef, p.rcp_coef = g.rcp_coef, p.fastdiv = g.fastdiv;
+    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
+    for (const fdnn::sets::Launch &l : launches) fdnn::launch_sets_score(p, l, s);
+  } else if (nnz > 0) {
+    HIP_TRY(c->d_snodes.reserve(size_t(nnz)));
+    fdnn::launch_sets_expand(sc.d_nodes, c->d_srow, d_row_set, count, c->d_snodes, s);
+    g.nodes = c->d_snodes;
+    g.epg = fdnn::lists_entries_per_group(nnz, device_cus(m->device));
+    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
+    fdnn::launch_lists_score(g, s);
+  }
+  {
+    ProfScope ps(m, s, FDNN_PROF_NORMALIZE);
+    fdnn::launch_lists_finish(g, s);
+  }
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+int sets_to_host(fdnn_ctx *c, int first, const std::vector<fdnn::sets::Seg> &segs, const int32_t *nodes, int n_nodes, float *probs,
+                 float *inactive, int32_t *acc, hipStream_t s) {
+  size_t nnz = 0, count = 0;
+  for (const fdnn::sets::Seg &g : segs) nnz += size_t(g.rows) * size_t(g.len), count += size_t(g.rows);
+  if (nnz > size_t(INT32_MAX)) return fail(FDNN_E_ARG, "the sum of rows x len must fit an int32");
+  HIP_TRY(c->d_linact.reserve(std::max<size_t>(count, 1)));
+  HIP_TRY(c->d_lnodes.reserve(std::max<size_t>(size_t(n_nodes), 1)));
+  HIP_TRY(c->d_lprobs.reserve(std::max<size_t>(nnz, 1)));
+  DevBuf<int32_t> d_acc;
+  if (acc) HIP_TRY(d_acc.reserve(std::max<size_t>(nnz, 1)));
+  if (n_nodes > 0) HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * size_t(n_nodes), hipMemcpyHostToDevice, s));
+  SetsCall sc;
+  sc.first = first, sc.segs = &segs, sc.d_nodes = c->d_lnodes, sc.d_probs = c->d_lprobs, sc.d_inactive = c->d_linact, sc.d_acc = acc ? d_acc.p : nullptr;
+  int rc = run_sets(c, sc, s);
+  if (rc) {
+    hipStreamSynchronize(s);
+    return rc;
+  }
+  if (nnz && probs) HIP_TRY(hipMemcpyAsync(probs, c->d_lprobs, sizeof(float) * nnz, hipMemcpyDeviceToHost, s));
+  if (count && inactive) HIP_TRY(hipMemcpyAsync(inactive, c->d_linact, sizeof(float) * count, hipMemcpyDeviceToHost, s));
+  if (nnz && acc) HIP_TRY(hipMemcpyAsync(acc, d_acc, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FDNN_OK;
+}
+
 bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks) { return choose_output(c, count, d_masks != nullptr, false, nullptr, true).fused; }
 
 // Device -> pageable host memory for large results (the 8000-float rows of a whole batch:
@@ -1146,6 +1234,14 @@ int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, 
     if (p.set_given) {  // one node set for every chunk: the chunk's rows land at probs + off * len
       rc = run_hidden(c, c->d_x, s, nullptr);
       if (!rc) rc = set_to_host(c, 0, cnt, p.set_nodes, p.set_len, p.probs + off * size_t(p.set_len), p.inactive + off, nullptr, s);
+      if (rc) hipStreamSynchronize(s);
+      continue;
+    }
+    if (p.sets) {  // the chunk's slice of the segments: its blocks are one contiguous range of the caller's probs
+      rc = run_hidden(c, c->d_x, s, nullptr);
+      const std::vector<fdnn::sets::Seg> segs = fdnn::sets::slice(*p.sets, int(off), int(off) + cnt);
+      if (!rc && !segs.empty())
+        rc = sets_to_host(c, 0, segs, p.nodes, p.sets->set_ptr[p.sets->n_segs], p.probs + size_t(segs[0].src_off), p.inactive + off, nullptr, s);
       if (rc) hipStreamSynchronize(s);
       continue;
     }

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -37,6 +38,7 @@
 #include <vector>
 
 #include "fdnn_internal.hpp"
+#include "fdnn_lists.hpp"
 #include "fdnn_server_plan.hpp"
 
 using fdnn::Buf;  // a slot's staging buffers: pinned host memory, or device memory (fdnn_buf.hpp)
@@ -74,6 +76,9 @@ struct Slot {
   Buf<float, true> d_comp;        // ... its compacted result rows [rows][stride]
   Buf<float> h_comp;              // ... and where they land on the host: ONE transfer per batch, behind the compaction
   Buf<float> h_raw;               // raw batches: the pieces' raw frames back to back; grows to the largest raw batch
+  Buf<int32_t> h_nodes;           // set batches: the pieces' sets back to back (pageable where pinned memory is refused) ...
+  Buf<int32_t, true> d_nodes;     // ... and on the device; both grow to the largest set batch
+  Buf<float> h_set;               // ... where its probs [nnz] and inactive values [rows] land: ONE transfer per batch (d_out holds both)
   BatchPlan batch;                // the current host batch: its pieces, where their frames are staged, how its rows return
   bool rows_on_host = false;      // its rows have been brought to h_out
   int pieces_left = 0;            // pieces not copied out yet
@@ -123,7 +128,7 @@ int alloc_host_side(fdnn_server *s) {
     const size_t n = size_t(s->max_frames);
     hipError_t e = sl.h_x.reserve(n * h.in_dim);
     if (e == hipSuccess) e = sl.h_mask.reserve(n * h.out_dim);
-    if (e == hipSuccess) e = sl.d_out.reserve(n * h.out_dim);
+    if (e == hipSuccess) e = sl.d_out.reserve(n * h.out_dim + n);  // (+ n: a set batch's inactive values behind its probs)
     // the slot's context was made lean: the device-side landing buffers of host batches live here
     if (e == hipSuccess && !sl.ctx->d_x) e = sl.ctx->d_x.reserve(n * h.in_dim);
     if (e == hipSuccess && !sl.ctx->d_mask) e = sl.ctx->d_mask.reserve(n * h.out_dim);
@@ -205,6 +210,45 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *las
   return rc;
 }
 
+// Enqueue one SET batch that is already on the device (kSet): the hidden layers as enqueue_batch runs them, then the pieces'
+// sets as the segments of ONE sets call per chunk (fdnn::run_sets) -- no output layer.  probs go to d_out [nnz], the
+// inactive values behind them [rows].
+int enqueue_set_batch(fdnn_server *s, Slot &sl, hipEvent_t after, hipStream_t *last_stream) {
+  const BatchPlan &b = sl.batch;
+  const int n = b.rows;
+  fdnn_ctx *c = sl.ctx;
+  c->n = n;
+  c->last = -1;
+  c->l0_chain_only = false;
+  const bool small = n <= kSmallBatch;
+  const std::vector<std::pair<int, int>> chunks = small ? std::vector<std::pair<int, int>>{{0, n}} : fdnn::frame_chunks(n, c->m);
+  hipStream_t cs = small ? sl.stream : s->s_main;
+  if (after) HIP_TRY(hipStreamWaitEvent(cs, after, 0));
+  fdnn::CtxUse use;
+  use.n_after = n;
+  HIP_TRY(use.enter(c, cs));
+  // the pieces as the tables of a sets call over the batch's rows
+  std::vector<int32_t> seg_rows, set_ptr;
+  for (const Piece &p : b.pieces) seg_rows.push_back(p.row0), set_ptr.push_back(p.set_off);
+  seg_rows.push_back(n), set_ptr.push_back(b.set_nodes);
+  const fdnn::sets::Tables t{seg_rows.data(), set_ptr.data(), int(b.pieces.size())};
+  const size_t D = size_t(s->m->hm.hdr.in_dim);
+  int rc = FDNN_OK;
+  for (const auto &ch : chunks) {
+    c->n = ch.second;
+    rc = fdnn::run_hidden(c, c->d_x + size_t(ch.first) * D, cs, nullptr);
+    if (rc) break;
+    const std::vector<fdnn::sets::Seg> segs = fdnn::sets::slice(t, ch.first, ch.first + ch.second);
+    fdnn::SetsCall sc;
+    sc.segs = &segs, sc.d_nodes = sl.d_nodes.p, sc.d_probs = sl.d_out.p + (segs.empty() ? 0 : segs[0].src_off);
+    sc.d_inactive = sl.d_out.p + size_t(b.nnz) + size_t(ch.first);
+    rc = fdnn::run_sets(c, sc, cs);
+    if (rc) break;
+  }
+  if (!rc) *last_stream = cs;
+  return rc;
+}
+
 // A batch carrying `ticket` failed: whatever of that request is still queued will never be packed (the packer would read
 // caller memory that the caller, told of the failure, is free to release).  Call with qmu held.
 void drop_queued_rest(fdnn_server *s, uint64_t ticket) {
@@ -249,7 +293,12 @@ void copy_ready_pieces(fdnn_server *s, std::unique_lock<std::mutex> &lk, Slot &s
     // bounce buffer and no second pass over the 32 KB per frame
     hipError_t ce = hipSuccess;
     const size_t stride = size_t(sl.batch.stride);  // (stable while the slot is in flight)
-    if (job.bits && stride > 0) {
+    if (job.set) {
+      // a set piece: its block of probs and its inactive values came to the slot's landing buffer with the batch
+      const size_t len = job.set->size();
+      if (len) std::memcpy(job.probs, sl.h_set.p + size_t(job.block_off), sizeof(float) * size_t(job.rows) * len);
+      std::memcpy(job.inactive, sl.h_set.p + size_t(sl.batch.nnz) + size_t(job.row0), sizeof(float) * size_t(job.rows));
+    } else if (job.bits && stride > 0) {
       // lazy rows, compacted: the batch's rows arrived in the slot's pinned buffer with the batch (one transfer, enqueued
       // behind the compaction); THIS thread -- the caller's own, normally, so that sixteen callers work side by side --
       // expands its rows into the caller's block (fdnn::lazy_expand_rows_from)
@@ -305,7 +354,10 @@ bool stage_one(fdnn_server *s, std::unique_lock<std::mutex> &lk) {
   } else {
     std::memcpy(sl.h_x.p + size_t(r0) * D, r.x + size_t(r.taken) * D, sizeof(float) * size_t(r.n) * D);
   }
-  if (kind == kBits && sl.h_bits.p) {  // (only bit-mask requests are in such a batch)
+  if (kind == kSet) {
+    const Piece &pc = sl.batch.pieces[size_t(i)];  // (stable while the slot is in flight)
+    if (!pc.set->empty()) std::memcpy(sl.h_nodes.p + size_t(pc.set_off), pc.set->data(), sizeof(int32_t) * pc.set->size());
+  } else if (kind == kBits && sl.h_bits.p) {  // (only bit-mask requests are in such a batch)
     std::memcpy(sl.h_bits.p + size_t(r0) * wpr, r.bits + size_t(r.taken) * wpr, sizeof(uint64_t) * size_t(r.n) * wpr);
   } else if (any_mask) {
     if (r.masks)
@@ -366,7 +418,7 @@ hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
   BatchPlan &b = sl.batch;
   // Whole rows of a batch that several callers share (1 GB of pinned memory per slot at most) go to the host in one transfer;
   // a single caller's batch, or one for which no pinned memory is to be had, leaves by per-caller copies from the device.
-  sl.rows_on_host = b.stride == 0 && b.taken.size() > 1 && frames * O * sizeof(float) <= (size_t(1) << 30) &&
+  sl.rows_on_host = b.kind != kSet && b.stride == 0 && b.taken.size() > 1 && frames * O * sizeof(float) <= (size_t(1) << 30) &&
                     sl.h_out.reserve(frames * O) == hipSuccess;
   if (b.kind == kBits) {
     // (advisor, round 5) no pinned memory to be had: pageable staging, the batch is not lost
@@ -384,6 +436,12 @@ hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
         b.stride = 0;
       }
     }
+  }
+  if (b.kind == kSet) {  // the sets up, probs and inactive values back: grown to the largest batch, pageable if need be
+    hipError_t e = sl.h_nodes.reserve(std::max<size_t>(size_t(b.set_nodes), 1), /*pageable_ok=*/true);
+    if (e == hipSuccess) e = sl.d_nodes.reserve(std::max<size_t>(size_t(b.set_nodes), 1));
+    if (e == hipSuccess) e = sl.h_set.reserve(size_t(b.nnz) + size_t(b.rows), /*pageable_ok=*/true);
+    if (e != hipSuccess) return e;
   }
   if (!b.raw) return hipSuccess;
   const hipError_t e = sl.h_raw.reserve(size_t(b.raw_frames) * size_t(b.spec->raw_dim));
@@ -421,6 +479,23 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
     if (e == hipSuccess) fdnn::splice_rows(*b.spec, int(D), c->d_raw, b.raw_frames, b.segs, 0, b.rows, c->d_x, sl.stream);
   } else {
     e = hipMemcpyAsync(c->d_x, sl.h_x.p, sizeof(float) * rows * D, hipMemcpyHostToDevice, sl.stream);
+  }
+  if (b.kind == kSet) {  // no masks and no output layer: the pieces' sets go up, probs and inactive values come back
+    if (e == hipSuccess && b.set_nodes > 0)
+      e = hipMemcpyAsync(sl.d_nodes.p, sl.h_nodes.p, sizeof(int32_t) * size_t(b.set_nodes), hipMemcpyHostToDevice, sl.stream);
+    if (e == hipSuccess) e = hipEventRecord(sl.staged, sl.stream);
+    if (e != hipSuccess) return e;
+    hipStream_t last = sl.stream;
+    *rc = enqueue_set_batch(s, sl, sl.staged, &last);
+    if (*rc) return hipSuccess;
+    if (last != sl.stream) {
+      e = hipEventRecord(sl.gemm_done, last);
+      if (e == hipSuccess) e = hipStreamWaitEvent(sl.stream, sl.gemm_done, 0);
+    }
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(sl.h_set.p, sl.d_out.p, sizeof(float) * (size_t(b.nnz) + rows), hipMemcpyDeviceToHost, sl.stream);
+    if (e == hipSuccess) e = hipEventRecord(sl.done, sl.stream);
+    return e;
   }
   if (e == hipSuccess && bits)
     e = hipMemcpyAsync(c->d_mask_bits, sl.h_bits.p, sizeof(uint64_t) * rows * wpr, hipMemcpyHostToDevice, sl.stream);
@@ -550,6 +625,25 @@ int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *r
 }
 
 }  // namespace fdnn
+
+namespace {
+
+// The common end of the set submit entry points: the set validated and copied (the caller may release it at once).
+int submit_set(fdnn_server *s, Request r, const int32_t *nodes, int len, float *probs, float *inactive, uint64_t *ticket) {
+  const int O = s->m->hm.hdr.out_dim;
+  if (len < 0 || (len > 0 && !nodes)) return fail(FDNN_E_ARG, "bad node set");
+  const int32_t row_ptr[2] = {0, len};
+  if (fdnn::lists::check(row_ptr, nodes, 1, O))
+    return fail(FDNN_E_ARG, "node set: the nodes must ascend strictly inside [0, " + std::to_string(O) + ")");
+  if (!inactive || (len > 0 && !probs)) return fail(FDNN_E_ARG, "null buffer");
+  if (static_cast<long long>(r.n) * len > INT32_MAX) return fail(FDNN_E_ARG, "n x len must fit an int32");
+  r.set = std::make_shared<const std::vector<int32_t>>(nodes, nodes + len);
+  r.set_probs = probs;
+  r.set_inactive = inactive;
+  return submit_host(s, std::move(r), ticket);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -698,6 +792,24 @@ int fdnn_server_submit_lazy_bits(fdnn_server *s, const float *x, int n, const ui
 int fdnn_server_submit_raw(fdnn_server *s, const float *raw, int n, const uint64_t *bits, float *out, uint64_t *ticket) {
   if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
   return fdnn::server_submit_raw_rows(s, s->m->splice, raw, n, 0, n, bits, out, ticket);
+}
+
+int fdnn_server_submit_lazy_set(fdnn_server *s, const float *x, int n, const int32_t *nodes, int len, float *probs, float *inactive,
+                                uint64_t *ticket) {
+  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
+  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
+  if (!x) return fail(FDNN_E_ARG, "null buffer");
+  return submit_set(s, Request{.x = x, .n = n}, nodes, len, probs, inactive, ticket);
+}
+
+int fdnn_server_submit_raw_set(fdnn_server *s, const float *raw, int n, const int32_t *nodes, int len, float *probs, float *inactive,
+                               uint64_t *ticket) {
+  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
+  const fdnn::SpliceRef spec = s->m->splice;
+  if (int rc = fdnn::splice_check(spec, -1)) return rc;
+  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
+  if (!raw) return fail(FDNN_E_ARG, "null buffer");
+  return submit_set(s, Request{.n = n, .raw = raw, .spec = spec, .raw_n = n, .raw_a = 0}, nodes, len, probs, inactive, ticket);
 }
 
 int fdnn_server_wait(fdnn_server *s, uint64_t ticket) {

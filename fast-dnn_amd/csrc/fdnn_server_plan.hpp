@@ -5,11 +5,15 @@
 #include <algorithm>
 #include <cstdint>
 #include <deque>
+#include <memory>
 #include <vector>
 
 #include "fdnn_splice_spec.hpp"
 
 namespace fdnn::plan {
+
+// A set submission's node set, copied at submit and shared by the request, its parts and their pieces (as SpliceRef is)
+using SetRef = std::shared_ptr<const std::vector<int32_t>>;
 
 struct Piece {  // one caller's rows inside a coalesced batch
   uint64_t ticket;
@@ -18,6 +22,12 @@ struct Piece {  // one caller's rows inside a coalesced batch
   bool last;       // the ticket's final piece
   int state = 0;   // 0 batch in flight, 1 rows ready in the slot's pinned buffer, 2 being copied out, 3 done
   const uint64_t *bits = nullptr;  // lazy submissions with bit masks: the caller's words of these rows (compacted return)
+  // set submissions (then out is null): the piece is one segment of the batch's sets call -- its set, where the set is
+  // staged among the batch's nodes, its block [rows][len] inside the batch's probs, and the caller's destinations of
+  // these rows (advanced by the frames earlier batches took)
+  SetRef set;
+  int set_off = 0, block_off = 0;
+  float *probs = nullptr, *inactive = nullptr;
 };
 
 struct Request {
@@ -34,6 +44,9 @@ struct Request {
   const float *raw = nullptr;
   SpliceRef spec;
   int raw_n = 0, raw_a = 0;
+  // set submissions (then out, masks and bits are null): ONE node set for all n rows; results probs [n][len], inactive [n]
+  SetRef set;
+  float *set_probs = nullptr, *set_inactive = nullptr;
 };
 
 // raw batches, per piece: the raw frames it references, [first, first + count) of its utterance, at frame `at` of the slot's buffer
@@ -55,8 +68,9 @@ inline int widest_row(const uint64_t *bits, int n, size_t O) {
 }
 
 // what a host batch carries: kinds do not share a batch, except that dense callers may ride in a byte-mask batch (all active)
-enum BatchKind { kDense = 0, kBytes = 1, kBits = 2 };
-inline int kind_of(const Request &r) { return r.bits ? kBits : r.masks ? kBytes : kDense; }
+// -- and set requests (kSet: no output layer runs, fdnn_sets.hip scores each piece's set) share batches only with set requests
+enum BatchKind { kDense = 0, kBytes = 1, kBits = 2, kSet = 3 };
+inline int kind_of(const Request &r) { return r.set ? kSet : r.bits ? kBits : r.masks ? kBytes : kDense; }
 
 struct BatchPlan {
   std::vector<Request> taken;  // per piece: the request with .taken = first frame, .n = frames in THIS batch
@@ -66,6 +80,7 @@ struct BatchPlan {
   SpliceRef spec;               // raw batches: one spec per batch
   int rows = 0, raw_frames = 0, most = 0, kind = kDense, stride = 0;  // stride: floats per compacted row (0: the rows leave whole)
   bool any_mask = false, raw = false;
+  int nnz = 0, set_nodes = 0;  // set batches: the floats of the batch's probs (sum of rows x len) and the nodes of its pieces' sets
 };
 
 // Takes requests off the front of the queue, whole or in part, until the batch is full (max_frames rows) or the next one may
@@ -81,7 +96,7 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
       b.kind = rk;
       b.raw = r.raw != nullptr;
       b.spec = r.spec;
-    } else if ((rk == kBits) != (b.kind == kBits) || (r.raw != nullptr) != b.raw || r.spec != b.spec)
+    } else if ((rk == kBits) != (b.kind == kBits) || (rk == kSet) != (b.kind == kSet) || (r.raw != nullptr) != b.raw || r.spec != b.spec)
       break;
     else if (rk == kBytes)
       b.kind = kBytes;
@@ -93,7 +108,18 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
     b.any_mask |= r.masks != nullptr;
     r.taken += take;
     const bool last = r.taken == r.n;
-    b.pieces.push_back(Piece{r.ticket, r.out + size_t(part.taken) * O, b.rows, take, last, 0, r.bits ? r.bits + size_t(part.taken) * wpr : nullptr});
+    b.pieces.push_back(Piece{r.ticket, r.out ? r.out + size_t(part.taken) * O : nullptr, b.rows, take, last, 0,
+                             r.bits ? r.bits + size_t(part.taken) * wpr : nullptr});
+    if (rk == kSet) {  // a later part of a split request continues at taken * len of the caller's probs
+      Piece &pc = b.pieces.back();
+      const size_t len = r.set->size();
+      pc.set = r.set;
+      pc.set_off = b.set_nodes, pc.block_off = b.nnz;
+      pc.probs = r.set_probs ? r.set_probs + size_t(part.taken) * len : nullptr;
+      pc.inactive = r.set_inactive + part.taken;
+      b.set_nodes += int(len);
+      b.nnz += take * int(len);
+    }
     if (b.raw) {  // the raw frames this piece's rows reference, and where they are staged
       const int u0 = r.raw_a + part.taken;  // the piece's first row as a frame of its utterance
       int fa, fb;

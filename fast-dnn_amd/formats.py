@@ -323,3 +323,21 @@ def lists_to_rows(row_ptr, nodes, probs, inactive, O: int) -> np.ndarray:
     rows = np.repeat(np.arange(n), np.diff(row_ptr))
     out[rows, np.asarray(nodes, dtype=np.int64)[:rows.size]] = np.asarray(probs, dtype=np.float32)[:rows.size]
     return out
+
+
+def sets_to_lists(seg_rows, set_ptr, nodes):
+    """Per-segment node sets (fdnn_ctx_lazy_output_sets: segment s = rows seg_rows[s] .. seg_rows[s + 1] - 1 with the set
+    nodes[set_ptr[s]:set_ptr[s + 1]]) -> (row_ptr int32 [rows + 1], list_nodes int32 [nnz]): the same call as lists, every
+    row's list its segment's set -- and row_ptr is where the sets call puts each row inside its flat probs."""
+    seg_rows = np.asarray(seg_rows, dtype=np.int64)
+    set_ptr = np.asarray(set_ptr, dtype=np.int64)
+    nodes = np.asarray(nodes, dtype=np.int32)
+    if seg_rows.ndim != 1 or seg_rows.shape != set_ptr.shape or seg_rows.size < 1:
+        raise ValueError("seg_rows and set_ptr must be [segments + 1]")
+    rows, lens = np.diff(seg_rows), np.diff(set_ptr)
+    row_len = np.repeat(lens, rows)
+    row_ptr = np.zeros(row_len.size + 1, dtype=np.int64)
+    np.cumsum(row_len, out=row_ptr[1:])
+    parts = [np.tile(nodes[set_ptr[s]:set_ptr[s + 1]], int(rows[s])) for s in range(rows.size)]
+    list_nodes = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+    return row_ptr.astype(np.int32), list_nodes

@@ -261,6 +261,34 @@ FDNN_API int fdnn_ctx_lazy_output_set_device(fdnn_ctx *c, int first, int count, 
                                              float *d_inactive, void *stream);
 FDNN_API int fdnn_calculate_lazy_set(fdnn_model *m, const float *x, int n, int dim, const int32_t *nodes, int len, float *probs,
                                      float *inactive);
+/* Lazy output for PER-SEGMENT NODE SETS: the set contract above with one set per segment of a row range, all segments in one
+ * call -- many utterances in one context, each with its own set (its transcript's states).  Up to 64 segments share one
+ * launch of the set kernel's tile (fdnn_sets.hip); LazyOutputActivations, dnn.cc:355-392.
+ *   seg_rows [n_segs + 1] int32, HOST memory in every form: non-decreasing; segment s = rows [seg_rows[s], seg_rows[s + 1])
+ *            of the context; seg_rows[0] >= 0, seg_rows[n_segs] <= frame count; empty segments allowed
+ *   set_ptr  [n_segs + 1] int32, HOST memory in every form: set_ptr[0] == 0, non-decreasing; segment s's set is
+ *            nodes[set_ptr[s] .. set_ptr[s + 1])
+ *   nodes    [set_ptr[n_segs]] int32, strictly ascending inside each segment's set, each in [0, output_dim)
+ *   probs    ragged: segment s's block starts at sum_{t < s} rows_t * len_t and is [rows_s][len_s] row-major
+ *   inactive [seg_rows[n_segs] - seg_rows[0]]: one 1 / total per row, in row order
+ * The sum of rows_s * len_s must fit an int32 (FDNN_E_ARG otherwise); n_segs == 0 is a no-op; a segment with len == 0 gives
+ * 1 / output_dim per row and no probs.  This is the list contract's CSR with row_ptr[r] = block start + r_local * len_s.
+ * A row's bytes depend on the row and its set only: they equal fdnn_ctx_lazy_output_set on that segment alone and
+ * fdnn_ctx_lazy_output_lists with the sets repeated per row (dnn.cc:355-392 in each).
+ * fdnn_ctx_lazy_output_sets         host buffers, host-synchronous; validates tables and sets (FDNN_E_ARG names the first
+ *   malformed segment, FDNN_E_STATE before the hidden layers).
+ * fdnn_ctx_lazy_output_sets_device  device buffers (d_nodes, d_probs, d_inactive), enqueued on `stream`, not synchronised,
+ *   ordered on the context like the other *_device entries; the tables are read before the call returns.  The tables are
+ *   checked, the sets are NOT: a node outside [0, output_dim) is never used as an address, it makes ITS segment's rows NaN
+ *   (entries and inactive values) and no other's.
+ * fdnn_calculate_lazy_sets          one call: pooled context, hidden layers + the sets; seg_rows must cover [0, n); a large n
+ *   goes chunk by chunk (fdnn_debug_frame_chunks), a segment cut by a chunk keeps its set. */
+FDNN_API int fdnn_ctx_lazy_output_sets(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *nodes,
+                                       float *probs, float *inactive);
+FDNN_API int fdnn_ctx_lazy_output_sets_device(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs,
+                                              const int32_t *d_nodes, float *d_probs, float *d_inactive, void *stream);
+FDNN_API int fdnn_calculate_lazy_sets(fdnn_model *m, const float *x, int n, int dim, const int32_t *seg_rows, const int32_t *set_ptr,
+                                      int n_segs, const int32_t *nodes, float *probs, float *inactive);
 /* Dense output layer over the context's hidden activations
  * (CalculateOutput, dnn.cc:428-454). */
 FDNN_API int fdnn_ctx_output(fdnn_ctx *c, float *out);
@@ -317,6 +345,18 @@ FDNN_API int fdnn_server_submit_lazy_bits(fdnn_server *s, const float *x, int n,
  * fdnn_calculate_raw / fdnn_calculate_lazy_bits_raw.  raw / bits / out must stay valid until the ticket completes.  A
  * submission is spliced by the model's spec at the time it was submitted. */
 FDNN_API int fdnn_server_submit_raw(fdnn_server *s, const float *raw, int n, const uint64_t *bits, float *out, uint64_t *ticket);
+/* One utterance with ITS OWN node set through the loop (the set contract of fdnn_ctx_lazy_output_set; LazyOutputActivations,
+ * dnn.cc:355-392, for many callers): set submissions are coalesced with one another, the hidden layers run once for the
+ * batch, and the pieces' sets are scored as the segments of one fdnn_ctx_lazy_output_sets-style call -- the dense output layer
+ * does not run at all, and only probs [n][len] and inactive [n] cross PCIe (32 KB for 100 frames x 80 nodes, against 3.2 MB
+ * of dense rows).  The results are byte-identical to fdnn_calculate_lazy_set on the same utterance.  The set is validated
+ * at submit (FDNN_E_ARG) and COPIED: the caller may release `nodes` at once; x or raw, probs and inactive must stay valid
+ * until the ticket completes.  len == 0: every row's inactive value is 1 / output_dim, probs is not written.
+ * fdnn_server_submit_raw_set takes raw feature frames [n][D], spliced on the device by the model's spec at submit time. */
+FDNN_API int fdnn_server_submit_lazy_set(fdnn_server *s, const float *x, int n, const int32_t *nodes, int len, float *probs,
+                                         float *inactive, uint64_t *ticket);
+FDNN_API int fdnn_server_submit_raw_set(fdnn_server *s, const float *raw, int n, const int32_t *nodes, int len, float *probs,
+                                        float *inactive, uint64_t *ticket);
 FDNN_API int fdnn_server_wait(fdnn_server *s, uint64_t ticket);
 FDNN_API int fdnn_server_drain(fdnn_server *s);
 FDNN_API int fdnn_server_stats(fdnn_server *s, uint64_t *batches, uint64_t *frames, uint64_t *requests,
@@ -477,6 +517,21 @@ FDNN_API int fdnn_debug_set_check(const int32_t *nodes, int len, int output_dim)
 FDNN_API int fdnn_debug_ctx_set_acc(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, int32_t *acc);
 FDNN_API int fdnn_debug_set_launches(unsigned long long *out, int cap);
 FDNN_API int fdnn_debug_set_kernel(int mode);
+
+/* Lazy output for per-segment node sets (LazyOutputActivations, dnn.cc:355-392), tests and tools.
+ * fdnn_debug_sets_check     the validator of the host entry points, host code, no device needed: 0, or -(s + 1) for the first
+ *   malformed segment s (malformed tables as a whole answer as segment 0); ctx_rows is the context's frame count.
+ * fdnn_debug_ctx_sets_acc   acc, ragged like probs: the int32 accumulators as the kernel holds them (a wave-uniform branch of
+ *   the same kernel, not a second one); otherwise as fdnn_ctx_lazy_output_sets (dnn.cc:355-392).
+ * fdnn_debug_sets_launches  process-wide counts since load, returns 3: out[0] launches of the segmented MFMA kernel without
+ *   the walk over saturating pairs, [1] with it, [2] calls served by the list kernels as fallback.  Not counted in
+ *   fdnn_debug_set_launches and not in the launch recorder's table (fdnn_note.hpp).  fdnn_debug_set_kernel's mode applies to
+ *   these entry points as well (dnn.cc:355-392 either way). */
+FDNN_API int fdnn_debug_sets_check(const int32_t *seg_rows, const int32_t *set_ptr, const int32_t *nodes, int n_segs, int output_dim,
+                                   int ctx_rows);
+FDNN_API int fdnn_debug_ctx_sets_acc(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *nodes,
+                                     int32_t *acc);
+FDNN_API int fdnn_debug_sets_launches(unsigned long long *out, int cap);
 
 /* Tests: write the word a fused soft-max workgroup raises (in host memory) when it gives up waiting for its frame tile's
  * siblings -- 1: as if a launch of this model had just done so (from the next call on the model runs the unfused soft-max

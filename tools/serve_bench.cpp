@@ -7,6 +7,10 @@
 //         fresh    = percall into a newly allocated, zero-filled result block per call (the reference shim's shape)
 //         lazy       = fdnn_calculate_lazy_bits per utterance (one-call lazy scoring, 40 % of the nodes active per frame)
 //         lazyserver = fdnn_server_submit_lazy_bits + fdnn_server_wait (bit-mask utterances coalesced, rows back compacted)
+//         set        = fdnn_calculate_lazy_set per utterance: each caller its own node set of SET_LEN nodes (environment, 80)
+//         setserver  = fdnn_server_submit_lazy_set + fdnn_server_wait (set utterances coalesced, no output layer, only
+//                      probs [frames][SET_LEN] + inactive [frames] back)
+// SET_LEN=k with lazy / lazyserver: the masks are those sets (the same k nodes in every frame of a caller) instead of 40 %.
 // INFLIGHT=k (environment, server modes): every caller keeps k utterances in flight (k result blocks per thread) instead of
 // waiting for each one before submitting the next.
 // Prints one JSON line.  Build: see tools/serve_bench.sh.
@@ -41,7 +45,9 @@ int main(int argc, char **argv) {
   const int D = fdnn_model_input_dim(m), O = fdnn_model_output_dim(m);
   fdnn_server *srv = nullptr;
   const bool lazy = mode == "lazy" || mode == "lazyserver";
-  if ((mode == "server" || mode == "lazyserver") && fdnn_server_create(m, max_frames, depth, &srv)) {
+  const bool sets = mode == "set" || mode == "setserver";
+  const int set_len = std::getenv("SET_LEN") ? std::atoi(std::getenv("SET_LEN")) : (sets ? 80 : 0);
+  if ((mode == "server" || mode == "lazyserver" || mode == "setserver") && fdnn_server_create(m, max_frames, depth, &srv)) {
     std::fprintf(stderr, "server: %s\n", fdnn_last_error());
     return 1;
   }
@@ -65,7 +71,31 @@ int main(int argc, char **argv) {
   // (FuncTest.java:121-154's statistics), as bits
   const size_t wpr = (size_t(O) + 63) / 64;
   std::vector<std::vector<uint64_t>> bits(static_cast<size_t>(T));
-  if (lazy) {
+  // set modes (and lazy modes with SET_LEN): per thread one ascending set of set_len nodes, drawn without replacement
+  std::vector<std::vector<int32_t>> nodes(static_cast<size_t>(T));
+  std::vector<std::vector<float>> probs(static_cast<size_t>(T)), inact(static_cast<size_t>(T));
+  if (set_len > 0) {
+    if (set_len > O || (sets && inflight > 1)) {
+      std::fprintf(stderr, "SET_LEN must be at most the output dimension; the set modes keep one utterance per caller in flight\n");
+      return 1;
+    }
+    for (int t = 0; t < T; ++t) {
+      std::vector<int32_t> perm(static_cast<size_t>(O));
+      for (int i = 0; i < O; ++i) perm[size_t(i)] = i;
+      std::shuffle(perm.begin(), perm.end(), rng);
+      nodes[size_t(t)].assign(perm.begin(), perm.begin() + set_len);
+      std::sort(nodes[size_t(t)].begin(), nodes[size_t(t)].end());
+      probs[size_t(t)].assign(size_t(F) * size_t(set_len), 0.0f);
+      inact[size_t(t)].assign(size_t(F), 0.0f);
+    }
+  }
+  if (lazy && set_len > 0) {
+    for (int t = 0; t < T; ++t) {
+      bits[size_t(t)].assign(size_t(F) * wpr, 0);
+      for (int f = 0; f < F; ++f)
+        for (int32_t i : nodes[size_t(t)]) bits[size_t(t)][size_t(f) * wpr + size_t(i >> 6)] |= uint64_t(1) << (i & 63);
+    }
+  } else if (lazy) {
     for (int t = 0; t < T; ++t) {
       std::vector<char> on(size_t(O), 0);
       std::vector<int> perm(static_cast<size_t>(O));
@@ -103,7 +133,16 @@ int main(int argc, char **argv) {
     }
     for (int u = 0; u < utts; ++u) {
       int rc;
-      if (srv && lazy) {
+      if (sets) {
+        const std::vector<int32_t> &nd = nodes[size_t(t)];
+        if (srv) {
+          uint64_t ticket = 0;
+          rc = fdnn_server_submit_lazy_set(srv, xs[size_t(t)].data(), F, nd.data(), set_len, probs[size_t(t)].data(), inact[size_t(t)].data(), &ticket);
+          if (!rc) rc = fdnn_server_wait(srv, ticket);
+        } else {
+          rc = fdnn_calculate_lazy_set(m, xs[size_t(t)].data(), F, D, nd.data(), set_len, probs[size_t(t)].data(), inact[size_t(t)].data());
+        }
+      } else if (srv && lazy) {
         uint64_t ticket = 0;
         rc = fdnn_server_submit_lazy_bits(srv, xs[size_t(t)].data(), F, bits[size_t(t)].data(), outs[size_t(t)].data(), &ticket);
         if (!rc) rc = fdnn_server_wait(srv, ticket);
@@ -134,6 +173,10 @@ int main(int argc, char **argv) {
   const double sec = run(U);
   double sum = 0.0;
   for (int i = 0; i < O; ++i) sum += outs[0][size_t(i)];
+  if (sets) {  // the same row as the lazy modes' row0_sum with SET_LEN: the listed nodes' probabilities + the others' inactive value
+    sum = double(O - set_len) * inact[0][0];
+    for (int j = 0; j < set_len; ++j) sum += probs[0][size_t(j)];
+  }
   uint64_t batches = 0, frames = 0, reqs = 0, coal = 0;
   if (srv) fdnn_server_stats(srv, &batches, &frames, &reqs, &coal);
   std::printf("{\"mode\": \"%s\", \"threads\": %d, \"frames_per_utt\": %d, \"utts\": %d, \"seconds\": %.4f, \"utts_per_s\": %.1f, "
