@@ -127,6 +127,10 @@ SIGNATURES = {
     "fdnn_debug_lists_check": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.c_int]),
     "fdnn_debug_ctx_lists_acc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, _c_i32p, _c_i32p]),
     "fdnn_debug_lists_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_model_set_lists_union": (C.c_int, [C.c_void_p, C.c_int]),
+    "fdnn_debug_lists_union_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_ctx_lists_union": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p]),
+    "fdnn_debug_lists_union_ref": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.c_int, C.c_int, _c_i32p, _c_i32p, _c_i32p]),
     "fdnn_ctx_lazy_output_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p]),
     "fdnn_ctx_lazy_output_set_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fdnn_calculate_lazy_set": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p]),
@@ -339,6 +343,33 @@ def lists_launches():
     return tuple(int(v) for v in buf)
 
 
+def lists_union_launches():
+    """Process-wide counts of the union path of the list calls since load (``fdnn_debug_lists_union_launches``): (union-build
+    launches, score launches without the pair walk, with it, calls with the switch on that the dot-product kernels served)."""
+    buf = (C.c_ulonglong * 4)()
+    if lib().fdnn_debug_lists_union_launches(buf, 4) != 4:
+        raise RuntimeError("fdnn_debug_lists_union_launches")
+    return tuple(int(v) for v in buf)
+
+
+def _union_buffers(rp, group_tiles):
+    rows = SET_FRAME_TILE * int(group_tiles)
+    groups = -(-(rp.size - 1) // rows) if group_tiles >= 1 else 0
+    nnz = int(rp[-1])
+    return np.full(max(groups, 0), -1, np.int32), np.full(nnz, -1, np.int32), np.full(nnz, -1, np.int32)
+
+
+def lists_union_ref(rowPtr, nodes, outputDimension: int, group_tiles: int):
+    """The unions of every ``32 * group_tiles`` rows' lists from the host restatement (``fdnn_debug_lists_union_ref``, no
+    device) -> (u_len [groups], u_nodes [nnz]: group q's union ascending from index rowPtr[q * 32 * group_tiles] on, -1
+    where no union reaches, pos [nnz]: every entry's rank in its group's union)."""
+    rp, nd = _lists(rowPtr, nodes)
+    u_len, u_nodes, pos = _union_buffers(rp, group_tiles)
+    _check(lib().fdnn_debug_lists_union_ref(rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p), rp.size - 1, int(outputDimension), int(group_tiles),
+                                            u_len.ctypes.data_as(_c_i32p), u_nodes.ctypes.data_as(_c_i32p), pos.ctypes.data_as(_c_i32p)))
+    return u_len, u_nodes, pos
+
+
 # The set kernel's tiles (fdnn_set.hpp: kNodeTile, kFrameTile; tests/test_lazy_set_host.py holds the two files together)
 SET_NODE_TILE = 64
 SET_FRAME_TILE = 32
@@ -482,6 +513,15 @@ class LazyContext:
         _check(lib().fdnn_debug_ctx_lists_acc(self.handle, int(first), rp.size - 1, rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p),
                                               acc.ctypes.data_as(_c_i32p)))
         return acc
+
+    def listsUnion(self, rowPtr, nodes, group_tiles: int, first: int = 0):
+        """Tests: the union-build kernel of the union path alone (``fdnn_debug_ctx_lists_union``) -> (u_len, u_nodes, pos) as
+        ``lists_union_ref`` lays them out."""
+        rp, nd = _lists(rowPtr, nodes)
+        u_len, u_nodes, pos = _union_buffers(rp, group_tiles)
+        _check(lib().fdnn_debug_ctx_lists_union(self.handle, int(first), rp.size - 1, rp.ctypes.data_as(_c_i32p), nd.ctypes.data_as(_c_i32p), int(group_tiles),
+                                                u_len.ctypes.data_as(_c_i32p), u_nodes.ctypes.data_as(_c_i32p), pos.ctypes.data_as(_c_i32p)))
+        return u_len, u_nodes, pos
 
     def calculateForOutputNodeSet(self, nodes, first: int = 0, count=None):
         """Lazy output for ONE node set shared by rows first .. first + count - 1 (``fdnn_ctx_lazy_output_set``; count: up
@@ -881,6 +921,13 @@ class QuantizedDnn:
 
     def setInputLayerFma(self, on: bool) -> None:
         _check(lib().fdnn_model_set_l0_fma(self.nativeDnnHandle, int(on)))
+
+    def setListsUnion(self, group_tiles: int) -> None:
+        """How the list calls (``calculateLazyLists``, ``LazyContext.calculateForOutputNodesLists`` and its device form) score
+        their entries (``fdnn_model_set_lists_union``): 0 (default) the dot-product kernels; 1 .. 8 the int8 MFMA over the
+        union of every ``32 * group_tiles`` consecutive rows' lists; -1 the same with the library's default group.  The
+        results are byte-identical either way; set it before the model is used from several threads."""
+        _check(lib().fdnn_model_set_lists_union(self.nativeDnnHandle, int(group_tiles)))
 
     def setInputLayerListCap(self, cap: int) -> None:
         """Tests: cap the flagged-output list of the int8-screened input layer (contexts created afterwards)."""

@@ -165,6 +165,14 @@ int fdnn_model_set_l0_fma(fdnn_model *m, int on) {
   return FDNN_OK;
 }
 
+int fdnn_model_set_lists_union(fdnn_model *m, int group_tiles) {
+  if (!m) return fail(FDNN_E_ARG, "null model");
+  const int g = lunion::group_tiles_of(group_tiles);
+  if (g < 0) return fail(FDNN_E_ARG, "group_tiles is 0 (off), 1 .. " + std::to_string(lunion::kMaxGroupTiles) + ", or -1 (the default group)");
+  m->lists_union = g;
+  return FDNN_OK;
+}
+
 int fdnn_device_shared(int device) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(FDNN_E_ARG, "no such device");
@@ -365,6 +373,69 @@ int fdnn_debug_lists_launches(unsigned long long *out, int cap) {
   fdnn::lists_launch_counts(v);
   for (int i = 0; i < 3 && i < cap; ++i) out[i] = v[i];
   return 3;
+}
+
+int fdnn_debug_lists_union_launches(unsigned long long *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  unsigned long long v[4];
+  fdnn::lists_union_launch_counts(v);
+  for (int i = 0; i < 4 && i < cap; ++i) out[i] = v[i];
+  return 4;
+}
+
+// The union-build kernel alone on validated host lists: words it does not write come back as -1.
+int fdnn_debug_ctx_lists_union(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, int group_tiles, int32_t *u_len,
+                               int32_t *u_nodes, int32_t *pos) {
+  if (!c || !row_ptr || !u_len) return fail(FDNN_E_ARG, "null argument");
+  if (group_tiles < 1 || group_tiles > lunion::kMaxGroupTiles) return fail(FDNN_E_ARG, "group_tiles is 1 .. " + std::to_string(lunion::kMaxGroupTiles));
+  if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
+  if (count == 0) return FDNN_OK;
+  const int O = c->m->hm.hdr.out_dim;
+  if (int rc = lists_validate(row_ptr, nodes, count, O)) return rc;
+  if (O > lunion::kMaxNodes) return fail(FDNN_E_ARG, "the union bitset holds " + std::to_string(lunion::kMaxNodes) + " nodes");
+  const size_t nnz = size_t(row_ptr[count]);
+  if (nnz > 0 && (!u_nodes || !pos)) return fail(FDNN_E_ARG, "null result buffer");
+  const lunion::Layout l = lunion::layout(static_cast<long long>(nnz), count, group_tiles);
+  if (nnz == 0) {
+    std::fill(u_len, u_len + l.n_groups, 0);
+    return FDNN_OK;
+  }
+  DeviceGuard g(c->m->device);
+  hipStream_t s = c->stream;
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  HIP_TRY(c->d_lrow.reserve(size_t(count) + 1));
+  HIP_TRY(c->d_lnodes.reserve(nnz));
+  HIP_TRY(c->d_lprobs.reserve(nnz));
+  HIP_TRY(c->d_union.reserve(l.words));
+  int32_t *const b = c->d_union.p;
+  HIP_TRY(hipMemcpyAsync(c->d_lrow, row_ptr, sizeof(int32_t) * (size_t(count) + 1), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(b, 0xff, sizeof(int32_t) * l.words, s));
+  const UnionParams u{c->d_lrow, c->d_lnodes, c->d_lprobs, nullptr, b + l.u_nodes, b + l.pos, b + l.u_len, b + l.work, b + l.counter,
+                      O, count, int(nnz), group_tiles, int(l.bound)};
+  HIP_TRY(launch_lists_union_build(u, l.n_groups, s));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(u_len, b + l.u_len, sizeof(int32_t) * size_t(l.n_groups), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(u_nodes, b + l.u_nodes, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(pos, b + l.pos, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FDNN_OK;
+}
+
+// The same in plain C++ (fdnn_lists_union.hpp: union_ref), no device; the lists are validated, nnz is row_ptr[count].
+int fdnn_debug_lists_union_ref(const int32_t *row_ptr, const int32_t *nodes, int count, int output_dim, int group_tiles, int32_t *u_len,
+                               int32_t *u_nodes, int32_t *pos) {
+  if (!row_ptr || !u_len || count < 0 || output_dim < 1) return fail(FDNN_E_ARG, "bad argument");
+  if (group_tiles < 1 || group_tiles > lunion::kMaxGroupTiles) return fail(FDNN_E_ARG, "group_tiles is 1 .. " + std::to_string(lunion::kMaxGroupTiles));
+  if (count == 0) return FDNN_OK;
+  if (int rc = lists_validate(row_ptr, nodes, count, output_dim)) return rc;
+  const int nnz = row_ptr[count];
+  if (nnz > 0 && (!u_nodes || !pos)) return fail(FDNN_E_ARG, "null result buffer");
+  std::fill(u_nodes, u_nodes + nnz, -1);
+  std::fill(pos, pos + nnz, -1);
+  lunion::union_ref(row_ptr, nodes, count, nnz, output_dim, group_tiles, u_len, u_nodes, pos);
+  return FDNN_OK;
 }
 
 // One-call form: hidden layers + lists on a pooled context, a large n chunk by chunk with its slice of the lists rebased.

@@ -66,6 +66,7 @@ struct fdnn_model {
   fdnn::DevBuf<unsigned long long> d_l0_stats;  // [4] device counters: [1] layer-0 outputs recomputed exactly, [2] fused soft-max tiles that gave up waiting
   int l0_jc = 0, l0_j_pad = 0, l0_h_ld = 0;
   int l0_fma = 0;
+  int lists_union = 0;  // fdnn_model_set_lists_union: 0 = list calls on the dot-product kernels, g in 1..8 = over unions of 32 g rows
   int l0_kernel = 0;  // fdnn_debug_set_l0_kernel
   int l0_list_cap = 0;  // fdnn_debug_set_l0_list_cap: > 0 caps the flagged-output list of contexts created afterwards (tests)
   fdnn::SpliceRef splice;  // fdnn_model_set_splice (null = no spec: the raw entry points refuse)
@@ -130,7 +131,10 @@ struct fdnn_ctx {
   fdnn::DevBuf<float> d_lprobs, d_linact;   // [nnz], [count]
   // set calls served by the list kernels (run_set's fallback): the set as lists, row_ptr [count + 1] and nodes [count * len]
   fdnn::DevBuf<int32_t> d_srow, d_snodes;
-  int last = -1;                  // d_act index holding the last hidden layer, -1 = not computed
+  // list calls scored over per-frame-group unions (fdnn_model_set_lists_union): unions, ranks, lengths, the work list and
+  // its counter in one buffer (lunion::Layout: O(nnz + count) words), allocated on the first such call and grown by the largest
+  fdnn::DevBuf<int32_t> d_union;
+  int last = -1;                 // d_act index holding the last hidden layer, -1 = not computed
   bool pooled = false;
   bool no_fuse = false;           // this call must not use the fused soft-max
   bool l0_chain_only = false;     // scoring loop, large batches: the soft-max scale of the previous batch runs under this

@@ -8,6 +8,7 @@
 #include "fdnn_ctx_layout.hpp"  // kMaxFrameTile, kPartialNodes, kL0ScreenCap, l0_split_plane_bytes
 #include "fdnn_note.hpp"
 #include "fdnn_select.hpp"
+#include "fdnn_lists_union.hpp"
 #include "fdnn_set.hpp"
 #include "fdnn_sets.hpp"
 
@@ -233,6 +234,24 @@ void launch_sets_rows(const sets::Launch &l, int32_t *row_ptr, int32_t *row_set,
 // the call (sets::row_ptr, sets::row_set, both on the device).  Counted as sets_launch_counts[2], once per call.
 void launch_sets_expand(const int32_t *nodes, const int32_t *row_ptr, const int32_t *row_set, int count, int32_t *rep, hipStream_t s);
 void sets_launch_counts(unsigned long long out[3]);  // MFMA launches without / with the pair walk, calls served by the list kernels
+
+// Lazy output by lists over per-frame-group node unions (fdnn_lists_union.hip; groups, buffers and the grid bound:
+// fdnn_lists_union.hpp).  build writes u_nodes / pos / u_len / work / counter from the caller's lists (and the NaN of an
+// entry whose node is outside the layer); score runs the set kernels' tile on every work item -- p carries the layer, a
+// and lda of the call's first row (its nodes, probs, acc, count, len and plan are not read) -- and gathers the listed
+// entries' e into probs; launch_lists_finish over the caller's row_ptr then owns the totals.
+struct UnionParams {
+  const int32_t *row_ptr;  // [count + 1] the caller's (not validated: values are clamped to [0, nnz])
+  const int32_t *nodes;    // [nnz] the caller's (not validated: set::node_ok before any use)
+  float *probs;            // [nnz]
+  int32_t *acc;            // [nnz] the int32 accumulators as the tile holds them (parity tests), or null
+  int32_t *u_nodes, *pos, *u_len, *work, *counter;  // lunion::Layout
+  int rows, count, nnz, group_tiles, bound;
+};
+hipError_t launch_lists_union_build(const UnionParams &u, int n_groups, hipStream_t s);  // zeroes the counter first
+void launch_lists_union_score(const SetParams &p, const UnionParams &u, int n_cu, hipStream_t s);
+void lists_union_note_fallback();  // a call with the switch on that the list kernels serve
+void lists_union_launch_counts(unsigned long long out[4]);  // build, score without / with the pair walk, fallback calls
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

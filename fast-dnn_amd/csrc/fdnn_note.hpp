@@ -13,6 +13,9 @@
 // And the segmented form of that kernel (fdnn_sets.hip: one set per segment, up to 64 segments in a launch): counted by
 // fdnn_debug_sets_launches, apart from the set kernel's counter; as names "sets.score.fix", "sets.score.nofix" and
 // "sets.fallback".  Its row-pointer and list-writing helpers are not counted: they score nothing.
+// And the union path of the list calls (fdnn_lists_union.hip, fdnn_model_set_lists_union): counted by
+// fdnn_debug_lists_union_launches; as names "lists.union.build", "lists.union.score.nofix", "lists.union.score.fix" and
+// "lists.union.fallback" (its finish launch is the list path's and is counted there).
 #pragma once
 #include <atomic>
 

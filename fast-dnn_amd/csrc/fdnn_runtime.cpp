@@ -717,7 +717,27 @@ int run_lists(fdnn_ctx *c, const ListsCall &lc, hipStream_t s) {
   g.count = lc.count;
   g.nnz = lc.nnz;
   g.epg = fdnn::lists_entries_per_group(lc.nnz, device_cus(m->device));
-  {
+  // fdnn_model_set_lists_union: the entries' e from the set kernels' tile over the union of every 32 g rows' lists
+  // (fdnn_lists_union.hip) where its shape applies -- the same bytes; else, and with the switch off, the dot-product kernels
+  const int group_tiles = m->lists_union;
+  const bool by_union = group_tiles > 0 && fdnn::lunion::shape_applies(g.K, g.rows, g.ldw, g.lda);
+  if (group_tiles > 0 && !by_union) fdnn::lists_union_note_fallback();
+  if (by_union && lc.nnz > 0) {
+    const fdnn::lunion::Layout l = fdnn::lunion::layout(lc.nnz, lc.count, group_tiles);
+    if (l.bound > INT32_MAX / 2) return fail(FDNN_E_ARG, "too many entries for one list call");
+    // (a buffer that is too small is freed and allocated anew, which waits for the device: earlier calls have finished)
+    HIP_TRY(c->d_union.reserve(l.words));
+    int32_t *const b = c->d_union.p;
+    const fdnn::UnionParams u{lc.d_row_ptr, lc.d_nodes, lc.d_probs, lc.d_acc, b + l.u_nodes, b + l.pos, b + l.u_len, b + l.work, b + l.counter,
+                              g.rows, lc.count, lc.nnz, group_tiles, int(l.bound)};
+    fdnn::SetParams p{};
+    p.w = g.w, p.a = g.a, p.bias = g.bias, p.wsum = g.wsum, p.fix_off = g.fix_off, p.fix_pairs = g.fix_pairs;
+    p.rows = g.rows, p.K = g.K, p.ldw = g.ldw, p.lda = g.lda;
+    p.coef = g.coef, p.rcp_coef = g.rcp_coef, p.fastdiv = g.fastdiv;
+    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
+    HIP_TRY(fdnn::launch_lists_union_build(u, l.n_groups, s));
+    fdnn::launch_lists_union_score(p, u, device_cus(m->device), s);
+  } else if (!by_union) {
     ProfScope ps(m, s, FDNN_PROF_OUTPUT);
     fdnn::launch_lists_score(g, s);
   }

@@ -2,6 +2,8 @@
 // fdnn_set.hip (one set for a row range) and fdnn_sets.hip (one set per segment, several segments in one launch) build a
 // SetView for their workgroup and call set_tile: the operations on a (row, node) pair are the same instructions in the same
 // order in both, which is what makes a row's bytes depend on the row and its set only.  How the tile works: fdnn_set.hip.
+// fdnn_lists_union.hip runs the same tile on the union of a frame group's lists and, through a store policy of its own,
+// hands back only the entries the caller listed.
 #pragma once
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
@@ -19,7 +21,8 @@ static_assert(kStWaves * kStSlice == set::kMaxK && set::kNodeTile == 64 && kStFT
 static_assert(kStLds <= 160 * 1024, "LDS");
 
 // What one workgroup scores: rows [0, count) at `a`, entries [m0, m0 + 64) of the set nodes[len], frame tiles
-// [t_begin, t_end) counted from a's first row; e of (row r, entry j) goes to probs[r * len + j].  Everything here is
+// [t_begin, t_end) counted from a's first row; e of (row r, entry j) goes where the store policy says (DenseStore:
+// probs[r * len + j]).  Everything here is
 // workgroup-uniform.  The layer itself (w, bias, wsum, the pair index, rows, K, ldw, coef) is read from SetParams.
 struct SetView {
   const int8_t *a;
@@ -34,9 +37,29 @@ struct SetView {
 // chunk c (16 bytes) of row r of a 256-byte-row LDS image lives at chunk position c ^ (r & 15) (as fdnn_small.hip)
 [[maybe_unused]] __device__ __forceinline__ int st_pos(int row, int chunk) { return (row << 8) + (((chunk ^ row) & 15) << 4); }
 
+// Where a tile's results go.  The tile hands every (row, entry) of the view it has scored to entry(): o = row * len + entry,
+// both counted inside the view, (f, jl) the same pair inside the 32 x 64 tile, `cur` the activation buffer the tile has just
+// consumed; and calls tile_done() once per frame tile, by every thread, between the last entry() and the barrier that
+// releases that buffer (f0: the tile's first row).
+//
+// DenseStore, the set kernels': e of (row r, entry j) to probs[r * len + j], nothing else.
+struct DenseStore {
+  __device__ __forceinline__ void entry(const SetView &v, size_t o, int, int, int, float e, int a32) const {
+    v.probs[o] = e;
+    if (v.acc != nullptr) v.acc[o] = a32;  // parity tests only (fdnn_debug_ctx_set_acc)
+  }
+  __device__ __forceinline__ void tile_done(const SetView &, int, int) const {}
+};
+
+// Byte offset, inside one activation buffer, of the 16 bytes that epilogue thread (f, jl / 4) owns in wave region 0: of the
+// eight partial chunks it has summed (one per region, same offset), this is the first.  No other thread reads or writes them.
+[[maybe_unused]] __device__ __forceinline__ int st_park(int f, int jl) {
+  return (jl >> 5) * 4096 + f * 128 + (((((jl >> 2) & 7) ^ f) & 7) << 4) + ((jl & 3) << 2);
+}
+
 // FIX: the layer has saturating pairs (the walk over a node's own list); FAST: validated 3-operation division
-template <bool FIX, bool FAST>
-__device__ __forceinline__ void set_tile(const SetParams &p, const SetView &v) {
+template <bool FIX, bool FAST, class Store = DenseStore>
+__device__ __forceinline__ void set_tile(const SetParams &p, const SetView &v, const Store &st = Store()) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -218,11 +241,11 @@ __device__ __forceinline__ void set_tile(const SetParams &p, const SetView &v) {
             const float y = z * 1.44269504088896340736f;
             e = __builtin_amdgcn_exp2f(y);
           }
-          v.probs[o + i] = e;
-          if (v.acc != nullptr) v.acc[o + i] = a32;  // parity tests only (fdnn_debug_ctx_set_acc)
+          st.entry(v, o + i, f, 32 * h + 4 * q + i, cur, e, a32);
         }
       }
     }
+    st.tile_done(v, f0, cur);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every partial is read: the buffer may be refilled
     asm volatile("" ::: "memory");

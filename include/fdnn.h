@@ -97,6 +97,15 @@ FDNN_API int fdnn_model_device(const fdnn_model *m);
  *                  built with its own Makefile's -march=native on an FMA host. */
 FDNN_API int fdnn_model_set_l0_fma(fdnn_model *m, int on);
 
+/* How the list entry points (fdnn_ctx_lazy_output_lists, _lists_device, fdnn_calculate_lazy_lists and what goes through
+ * them; LazyOutputActivations, dnn.cc:355-392) score their entries.
+ * 0 (default): the dot-product kernels, exactly as today.  g in 1..8: lists are scored on the int8 MFMA over the union of
+ * each group of 32 * g consecutive rows of the call (groups counted from `first`); -1: on, with the library's default g.
+ * Results are byte-identical either way.  Like fdnn_model_set_l0_fma: set before the model is used from several threads.
+ * A layer the MFMA tile's shape does not apply to (K > 2048, output_dim > 65536) is served by the dot-product kernels.
+ * Any other value is FDNN_E_ARG.  The scoring loop, device groups and the JNI shim do not look at the switch. */
+FDNN_API int fdnn_model_set_lists_union(fdnn_model *m, int group_tiles);
+
 /* ------------------------------------------------------------------ dense path
  * fdnn_calculate <- Java calculate(long, float[], int, int, int) /
  *   jni_dnn.cc:35-62 -> CalculationContext::Calculate (dnn.cc:162-165).
@@ -502,6 +511,23 @@ FDNN_API int fdnn_debug_launch_counts(unsigned long long *out, int cap);
 FDNN_API int fdnn_debug_lists_check(const int32_t *row_ptr, const int32_t *nodes, int count, int output_dim);
 FDNN_API int fdnn_debug_ctx_lists_acc(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, int32_t *acc);
 FDNN_API int fdnn_debug_lists_launches(unsigned long long *out, int cap);
+
+/* Lazy output by lists over per-frame-group node unions (fdnn_model_set_lists_union; LazyOutputActivations,
+ * dnn.cc:355-392), tests and tools.  With the switch on, fdnn_debug_ctx_lists_acc returns the accumulators the MFMA tile
+ * holds (a wave-uniform branch of the production kernel).
+ * fdnn_debug_lists_union_launches  process-wide counts since load, returns 4: out[0] union-build launches, [1] / [2] score
+ *   launches without / with the walk over saturating pairs, [3] calls that had the switch on and were served by the
+ *   dot-product kernels.  (Not in the launch recorder's table: see fdnn_note.hpp.)
+ * fdnn_debug_ctx_lists_union       host buffers, validated like fdnn_ctx_lazy_output_lists: runs the union-build kernel
+ *   alone for rows first .. first + count - 1 with groups of 32 * group_tiles rows (1..8) and copies back what it wrote:
+ *   u_len [ceil(count / (32 * group_tiles))] every group's union length; u_nodes [nnz] group q's union, ascending, from
+ *   index row_ptr[q * 32 * group_tiles] on, every word no union covers -1; pos [nnz] every entry's rank in its group's union.
+ * fdnn_debug_lists_union_ref       the same three arrays from the host restatement (fdnn_lists_union.hpp), no device. */
+FDNN_API int fdnn_debug_lists_union_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_ctx_lists_union(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, int group_tiles,
+                                        int32_t *u_len, int32_t *u_nodes, int32_t *pos);
+FDNN_API int fdnn_debug_lists_union_ref(const int32_t *row_ptr, const int32_t *nodes, int count, int output_dim, int group_tiles,
+                                        int32_t *u_len, int32_t *u_nodes, int32_t *pos);
 
 /* Lazy output for a shared node set (LazyOutputActivations, dnn.cc:355-392), tests and tools.
  * fdnn_debug_set_check     the validator of the host entry points, host code, no device needed: 0, or -1 for a set that is
