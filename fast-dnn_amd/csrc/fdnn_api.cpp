@@ -328,18 +328,31 @@ static int lists_validate(const int32_t *row_ptr, const int32_t *nodes, int coun
                               std::to_string(output_dim) + ")");
 }
 
-static int ctx_lists_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive,
-                          int32_t *acc) {
-  if (!c || !row_ptr) return fail(FDNN_E_ARG, "null argument");
+// The common front of the host forms of a lazy-entries call (lists, set, sets): the texts their callers see, whatever
+// run_lists / run_set / run_sets say of the same conditions to the device forms and the scoring loop.
+static int ctx_entries_front(const fdnn_ctx *c, bool args_given, int first, int count) {
+  if (!c || !args_given) return fail(FDNN_E_ARG, "null argument");
   if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
   if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
-  if (count == 0) return FDNN_OK;
-  if (int rc = lists_validate(row_ptr, nodes, count, c->m->hm.hdr.out_dim)) return rc;
-  if ((!acc && !inactive) || (row_ptr[count] > 0 && !acc && !probs)) return fail(FDNN_E_ARG, "null result buffer");
+  return FDNN_OK;
+}
+
+// Their common end: the result-buffer rule (the parity forms bring acc alone), then the host form on the context's stream.
+static int ctx_entries_to_host(fdnn_ctx *c, long long nnz, const HostEntries &h) {
+  if ((!h.acc && !h.inactive) || (nnz > 0 && !h.acc && !h.probs)) return fail(FDNN_E_ARG, "null result buffer");
   DeviceGuard g(c->m->device);
   CtxUse use;
   HIP_TRY(use.enter(c, c->stream));
-  return lists_to_host(c, first, count, row_ptr, nodes, probs, inactive, acc, c->stream);
+  return entries_to_host(c, h, c->stream);
+}
+
+static int ctx_lists_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive,
+                          int32_t *acc) {
+  if (int rc = ctx_entries_front(c, row_ptr != nullptr, first, count)) return rc;
+  if (count == 0) return FDNN_OK;
+  if (int rc = lists_validate(row_ptr, nodes, count, c->m->hm.hdr.out_dim)) return rc;
+  return ctx_entries_to_host(c, row_ptr[count], {.first = first, .count = count, .row_ptr = row_ptr, .nodes = nodes, .n_nodes = row_ptr[count],
+                                                 .probs = probs, .inactive = inactive, .acc = acc});
 }
 
 int fdnn_ctx_lazy_output_lists(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs,
@@ -367,21 +380,18 @@ int fdnn_debug_lists_check(const int32_t *row_ptr, const int32_t *nodes, int cou
   return lists::check(row_ptr, nodes, count, output_dim);
 }
 
-int fdnn_debug_lists_launches(unsigned long long *out, int cap) {
-  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
-  unsigned long long v[3];
-  fdnn::lists_launch_counts(v);
-  for (int i = 0; i < 3 && i < cap; ++i) out[i] = v[i];
-  return 3;
-}
-
-int fdnn_debug_lists_union_launches(unsigned long long *out, int cap) {
+// The first `cap` of a launcher's n (<= 4) counts (fdnn_launch.hpp: LaunchCounts) into out; returns n
+static int counts_out(unsigned long long *out, int cap, int n, void (*reader)(unsigned long long *)) {
   if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
   unsigned long long v[4];
-  fdnn::lists_union_launch_counts(v);
-  for (int i = 0; i < 4 && i < cap; ++i) out[i] = v[i];
-  return 4;
+  reader(v);
+  for (int i = 0; i < n && i < cap; ++i) out[i] = v[i];
+  return n;
 }
+
+int fdnn_debug_lists_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 3, fdnn::lists_launch_counts); }
+
+int fdnn_debug_lists_union_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 4, fdnn::lists_union_launch_counts); }
 
 // The union-build kernel alone on validated host lists: words it does not write come back as -1.
 int fdnn_debug_ctx_lists_union(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, int group_tiles, int32_t *u_len,
@@ -412,8 +422,7 @@ int fdnn_debug_ctx_lists_union(fdnn_ctx *c, int first, int count, const int32_t 
   HIP_TRY(hipMemcpyAsync(c->d_lrow, row_ptr, sizeof(int32_t) * (size_t(count) + 1), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemsetAsync(b, 0xff, sizeof(int32_t) * l.words, s));
-  const UnionParams u{c->d_lrow, c->d_lnodes, c->d_lprobs, nullptr, b + l.u_nodes, b + l.pos, b + l.u_len, b + l.work, b + l.counter,
-                      O, count, int(nnz), group_tiles, int(l.bound)};
+  const UnionParams u = union_params(l, b, {0, count, c->d_lrow, c->d_lnodes, int(nnz), c->d_lprobs}, O, group_tiles);
   HIP_TRY(launch_lists_union_build(u, l.n_groups, s));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(u_len, b + l.u_len, sizeof(int32_t) * size_t(l.n_groups), hipMemcpyDeviceToHost, s));
@@ -460,17 +469,12 @@ static int set_validate(const int32_t *nodes, int len, int output_dim) {
 }
 
 static int ctx_set_host(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive, int32_t *acc) {
-  if (!c) return fail(FDNN_E_ARG, "null argument");
-  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
-  if (first < 0 || count < 0 || first + count > c->n) return fail(FDNN_E_ARG, "frame index outside the context");
+  if (int rc = ctx_entries_front(c, true, first, count)) return rc;
   if (int rc = set_validate(nodes, len, c->m->hm.hdr.out_dim)) return rc;
   if (static_cast<long long>(count) * len > INT32_MAX) return fail(FDNN_E_ARG, "count x len must fit an int32");
   if (count == 0) return FDNN_OK;
-  if ((!acc && !inactive) || (len > 0 && !acc && !probs)) return fail(FDNN_E_ARG, "null result buffer");
-  DeviceGuard g(c->m->device);
-  CtxUse use;
-  HIP_TRY(use.enter(c, c->stream));
-  return set_to_host(c, first, count, nodes, len, probs, inactive, acc, c->stream);
+  return ctx_entries_to_host(c, len, {.first = first, .count = count, .len = len, .nodes = nodes, .n_nodes = len, .probs = probs,
+                                      .inactive = inactive, .acc = acc});
 }
 
 int fdnn_ctx_lazy_output_set(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive) {
@@ -498,13 +502,7 @@ int fdnn_debug_set_check(const int32_t *nodes, int len, int output_dim) {
   return lists::check(row_ptr, nodes, 1, output_dim);
 }
 
-int fdnn_debug_set_launches(unsigned long long *out, int cap) {
-  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
-  unsigned long long v[3];
-  fdnn::set_launch_counts(v);
-  for (int i = 0; i < 3 && i < cap; ++i) out[i] = v[i];
-  return 3;
-}
+int fdnn_debug_set_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 3, fdnn::set_launch_counts); }
 
 int fdnn_debug_set_kernel(int mode) {
   if (mode < 0 || mode > 2) return fail(FDNN_E_ARG, "mode is 0 (the default rule), 1 (the MFMA kernel) or 2 (the list kernels)");
@@ -537,8 +535,7 @@ static int sets_validate(const int32_t *seg_rows, const int32_t *set_ptr, const 
 
 static int ctx_sets_host(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *nodes, float *probs,
                          float *inactive, int32_t *acc) {
-  if (!c) return fail(FDNN_E_ARG, "null argument");
-  if (c->last < 0) return fail(FDNN_E_STATE, "calculateLazy before calculateUntilOutput");
+  if (int rc = ctx_entries_front(c, true, 0, 0)) return rc;  // (the row range is the tables': sets_validate)
   if (int rc = sets_validate(seg_rows, set_ptr, nodes, n_segs, c->m->hm.hdr.out_dim, c->n)) return rc;
   if (n_segs == 0) return FDNN_OK;
   const sets::Tables t{seg_rows, set_ptr, n_segs};
@@ -546,11 +543,9 @@ static int ctx_sets_host(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *se
   if (nnz > INT32_MAX) return fail(FDNN_E_ARG, "the sum of rows x len over the segments must fit an int32");
   const int count = seg_rows[n_segs] - seg_rows[0];
   if (count == 0) return FDNN_OK;
-  if ((!acc && !inactive) || (nnz > 0 && !acc && !probs)) return fail(FDNN_E_ARG, "null result buffer");
-  DeviceGuard g(c->m->device);
-  CtxUse use;
-  HIP_TRY(use.enter(c, c->stream));
-  return sets_to_host(c, seg_rows[0], sets::slice(t, seg_rows[0], seg_rows[n_segs]), nodes, set_ptr[n_segs], probs, inactive, acc, c->stream);
+  const std::vector<sets::Seg> segs = sets::slice(t, seg_rows[0], seg_rows[n_segs]);
+  return ctx_entries_to_host(c, nnz, {.first = seg_rows[0], .count = count, .segs = &segs, .nodes = nodes, .n_nodes = set_ptr[n_segs],
+                                      .probs = probs, .inactive = inactive, .acc = acc});
 }
 
 int fdnn_ctx_lazy_output_sets(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *nodes, float *probs,
@@ -567,7 +562,7 @@ int fdnn_debug_ctx_sets_acc(fdnn_ctx *c, const int32_t *seg_rows, const int32_t 
 int fdnn_ctx_lazy_output_sets_device(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *d_nodes,
                                      float *d_probs, float *d_inactive, void *stream) {
   if (!c) return fail(FDNN_E_ARG, "null argument");
-  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
+  if (int rc = lazy_state(c)) return rc;
   if (n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
   if (n_segs == 0) return FDNN_OK;
   if (!seg_rows || !set_ptr || seg_rows[0] < 0 || set_ptr[0] != 0) return fail(FDNN_E_ARG, "node sets, segment 0: malformed tables");
@@ -591,13 +586,7 @@ int fdnn_debug_sets_check(const int32_t *seg_rows, const int32_t *set_ptr, const
   return sets::check(seg_rows, set_ptr, nodes, n_segs, output_dim, ctx_rows);
 }
 
-int fdnn_debug_sets_launches(unsigned long long *out, int cap) {
-  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
-  unsigned long long v[3];
-  fdnn::sets_launch_counts(v);
-  for (int i = 0; i < 3 && i < cap; ++i) out[i] = v[i];
-  return 3;
-}
+int fdnn_debug_sets_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 3, fdnn::sets_launch_counts); }
 
 // One-call form: hidden layers + the sets on a pooled context, a large n chunk by chunk, every chunk with its slice of the
 // segments (a segment cut in two keeps its set).

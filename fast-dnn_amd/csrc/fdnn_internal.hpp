@@ -1,5 +1,5 @@
 // fdnn_internal.hpp -- what the runtime's translation units share: the model / context objects
-// behind the opaque C-ABI handles and the enqueue helpers over them (fdnn_runtime.cpp), used by
+// behind the opaque C-ABI handles and the enqueue helpers over them (fdnn_runtime.cpp, fdnn_lazy_entries.cpp), used by
 // the scoring C-ABI (fdnn_api.cpp), the debug / profiling / host-model calls (fdnn_debug.cpp),
 // the multi-stream server loop (fdnn_server.cpp) and the device group (fdnn_group.cpp).
 // Not installed; the boundary is include/fdnn.h.
@@ -150,6 +150,28 @@ struct fdnn_ctx {
 
 namespace fdnn {
 
+// Brackets one kernel launch with HIP events on the launch stream when profiling is on.
+struct ProfScope {
+  fdnn_model *m;
+  hipStream_t s;
+  int kind;
+  hipEvent_t a = nullptr, b = nullptr;
+  ProfScope(fdnn_model *m_, hipStream_t s_, int kind_) : m(m_), s(s_), kind(kind_) {
+    if (!m->profiling) return;
+    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
+      a = b = nullptr;
+      return;
+    }
+    hipEventRecord(a, s);
+  }
+  ~ProfScope() {
+    if (!a) return;
+    hipEventRecord(b, s);
+    std::lock_guard<std::mutex> lk(m->mu);
+    m->prof.push_back({kind, a, b});
+  }
+};
+
 struct Taps {
   float *l0_lin = nullptr;
   uint8_t *u8_acts = nullptr;   // device [n_hidden][n][H]
@@ -198,9 +220,6 @@ struct ListsCall {
   int32_t *d_acc = nullptr;            // [nnz]
 };
 int run_lists(fdnn_ctx *c, const ListsCall &lc, hipStream_t s);
-// The host form of the same: validated lists up, results back, synchronises s.  acc (parity tests) may be null.
-int lists_to_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive,
-                  int32_t *acc, hipStream_t s);
 // The same contract with ONE node set for rows [first, first + count) (fdnn_set.hip): d_nodes [len], d_probs [count][len],
 // d_inactive [count]; enqueued on s.  d_acc [count][len] (parity tests) may be null.
 struct SetCall {
@@ -212,8 +231,6 @@ struct SetCall {
   int32_t *d_acc = nullptr;
 };
 int run_set(fdnn_ctx *c, const SetCall &sc, hipStream_t s);
-// The host form: a validated set up, results back, synchronises s.  acc (parity tests) may be null.
-int set_to_host(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive, int32_t *acc, hipStream_t s);
 // The same contract with one node set per SEGMENT of rows [first, first + rows of segs) (fdnn_sets.hip): segs as
 // sets::slice returns them -- consecutive rows from 0, blocks from 0 --, d_nodes the sets that set_off indexes, d_probs the
 // ragged blocks, d_inactive one value per row; enqueued on s.  The launch tables travel as kernel arguments, the row pointer
@@ -227,10 +244,26 @@ struct SetsCall {
   int32_t *d_acc = nullptr;
 };
 int run_sets(fdnn_ctx *c, const SetsCall &sc, hipStream_t s);
-// The host form: segs of validated tables, all `n_nodes` nodes up, the slice's results back (probs: the slice's blocks, one
-// contiguous range), synchronises s.  acc (parity tests) may be null.
-int sets_to_host(fdnn_ctx *c, int first, const std::vector<fdnn::sets::Seg> &segs, const int32_t *nodes, int n_nodes, float *probs,
-                 float *inactive, int32_t *acc, hipStream_t s);
+// The three above are fdnn_lazy_entries.cpp's one driver with a score step each.  lazy_state: FDNN_E_STATE, in the words the
+// device forms return, unless the context's hidden layers have run.
+int lazy_state(const fdnn_ctx *c);
+// The host form of all three: validated lists (row_ptr), segments (segs: of validated tables, as sets::slice returns them) or
+// one set (neither: `len` nodes) for rows [first, first + count) and all `n_nodes` nodes up, results back -- probs: the
+// entries in call order, for segments the slice's blocks, one contiguous range -- and s synchronised.  acc (parity tests)
+// may be null.
+struct HostEntries {
+  int first = 0, count = 0;
+  const int32_t *row_ptr = nullptr;                    // [count + 1]
+  const std::vector<fdnn::sets::Seg> *segs = nullptr;
+  int len = 0;
+  const int32_t *nodes = nullptr;
+  int n_nodes = 0;
+  float *probs = nullptr, *inactive = nullptr;
+  int32_t *acc = nullptr;
+};
+int entries_to_host(fdnn_ctx *c, const HostEntries &h, hipStream_t s);
+// The union kernels' view of the lists in lc (first is not read) and of a buffer b laid out by l (fdnn_lists_union.hpp)
+UnionParams union_params(const lunion::Layout &l, int32_t *b, const ListsCall &lc, int rows, int group_tiles);
 int build_lists_index(fdnn_model *m);  // the per-node pair index of the output layer, from m->hm (model load / blob import)
 int device_cus(int device);            // CUs of a device, asked once (256 where the runtime cannot say)
 // Will run_output scale the soft-max inside the output kernel for such a call (dense, large batch)?  Then there is no

@@ -19,10 +19,9 @@
 //           + float(O - len) for the unlisted nodes' exp(0) (exact: O < 2^24); inactive = RN(1 / total), p = RN(e * inactive).
 //
 // A node outside [0, O) (device lists are not validated) is never used as an address: its e is NaN, and so is its row.
-#include <atomic>
-
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
+#include "fdnn_launch.hpp"
 
 namespace fdnn {
 namespace {
@@ -32,7 +31,7 @@ constexpr int kLsLanes = 16;                       // lanes per entry
 constexpr int kLsGroups = kLsThreads / kLsLanes;   // entries a workgroup scores side by side
 constexpr int kLsChunk = kLsLanes * 16 * 8;        // bytes of K a group holds in registers: 8 x 16 bytes per lane = 2048
 
-std::atomic<unsigned long long> g_lists_launches[3];  // score without / with the pair walk, finish (fdnn_debug_lists_launches)
+LaunchCounts<3> g_lists_launches;  // score without / with the pair walk, finish (fdnn_debug_lists_launches)
 
 // FIX: the layer has saturating pairs (the walk over the node's own list); FAST: validated 3-operation division
 template <bool FIX, bool FAST>
@@ -156,20 +155,15 @@ void launch_lists_score(const ListsParams &p, hipStream_t s) {
   const long long per_block = static_cast<long long>(kLsGroups) * p.epg;
   const unsigned blocks = static_cast<unsigned>((p.nnz + per_block - 1) / per_block);
   const bool fix = p.fix_off != nullptr && p.fix_pairs != nullptr;
-  g_lists_launches[fix ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
-  if (fix && p.fastdiv)
-    hipLaunchKernelGGL((lists_score_kernel<true, true>), dim3(blocks), dim3(kLsThreads), 0, s, p);
-  else if (fix)
-    hipLaunchKernelGGL((lists_score_kernel<true, false>), dim3(blocks), dim3(kLsThreads), 0, s, p);
-  else if (p.fastdiv)
-    hipLaunchKernelGGL((lists_score_kernel<false, true>), dim3(blocks), dim3(kLsThreads), 0, s, p);
-  else
-    hipLaunchKernelGGL((lists_score_kernel<false, false>), dim3(blocks), dim3(kLsThreads), 0, s, p);
+  g_lists_launches.bump(fix ? 1 : 0);
+  with_fix_fast(fix, p.fastdiv, [&](auto FIX, auto FAST) {
+    hipLaunchKernelGGL((lists_score_kernel<FIX(), FAST()>), dim3(blocks), dim3(kLsThreads), 0, s, p);
+  });
 }
 
 void launch_lists_finish(const ListsParams &p, hipStream_t s) {
   if (p.count <= 0) return;
-  g_lists_launches[2].fetch_add(1, std::memory_order_relaxed);
+  g_lists_launches.bump(2);
   const int rows_per_block = kLsThreads / 64;
   const dim3 grid((p.count + rows_per_block - 1) / rows_per_block);
   if (p.row_ptr != nullptr)
@@ -185,8 +179,6 @@ int lists_entries_per_group(long long nnz, int n_cu) {
   return static_cast<int>(want < 1 ? 1 : want > 8 ? 8 : want);
 }
 
-void lists_launch_counts(unsigned long long out[3]) {
-  for (int i = 0; i < 3; ++i) out[i] = g_lists_launches[i].load(std::memory_order_relaxed);
-}
+void lists_launch_counts(unsigned long long out[3]) { g_lists_launches.read(out); }
 
 }  // namespace fdnn

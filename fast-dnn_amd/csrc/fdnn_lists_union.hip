@@ -20,13 +20,13 @@
 //           the frame tile's rows' entries and copies probs[i] = e[row][pos[i] - m0] for those whose rank falls into its
 //           chunk.  Every entry is written exactly once, by the workgroup of its chunk, whatever order a device list has.
 //           The work list holds at most nnz / 64 + groups items (fdnn_lists_union.hpp); the grid is that bound or four
-//           workgroups per CU, whichever is less, and a workgroup walks the list with the grid's stride.
+//           workgroups per CU, whichever is less, and a workgroup walks the list with the grid's stride.  The launch is the
+//           set kernels' launch_set_tile.
 //   finish  the list path's own kernel over the caller's row_ptr (fdnn_lists.hip): the normative sum order.
 //
 // The accumulators are exact integers and the logit, the exp2 and the finish pass are the list path's instructions, so the
 // bytes are those of the dot-product kernels on the same lists.
 #include <algorithm>
-#include <atomic>
 
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
@@ -40,7 +40,7 @@ constexpr int kLuWaves = kLuThreads / 64;
 constexpr int kLuOrderedBit = 16;  // of a work item's chunk word: every row of the group ascends (chunks < kMaxNodes / 64 = 2^10)
 static_assert(lunion::kMaxNodes / set::kNodeTile <= 1 << kLuOrderedBit, "a chunk index stays below the flag");
 
-std::atomic<unsigned long long> g_union_launches[4];  // build, score without / with the pair walk, calls served by the list kernels
+LaunchCounts<4> g_union_launches;  // build, score without / with the pair walk, calls served by the list kernels
 
 __global__ __launch_bounds__(kLuThreads) void lists_union_build_kernel(UnionParams u) {
   __shared__ uint32_t bits[lunion::kMaxWords];
@@ -193,27 +193,13 @@ __global__ __launch_bounds__(kStThreads, 2) void lists_union_score_kernel(SetPar
   }
 }
 
-template <bool FIX, bool FAST>
-void launch_union_cfg(const SetParams &p, const UnionParams &u, int blocks, hipStream_t s) {
-  auto k = lists_union_score_kernel<FIX, FAST>;
-  static std::atomic<unsigned long long> attr_set{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long dev_bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kStLds);
-    attr_set.fetch_or(dev_bit, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(blocks)), dim3(kStThreads), kStLds, s, p, u);
-}
-
 }  // namespace
 
 hipError_t launch_lists_union_build(const UnionParams &u, int n_groups, hipStream_t s) {
   if (n_groups <= 0 || u.nnz <= 0) return hipSuccess;
   const hipError_t e = hipMemsetAsync(u.counter, 0, sizeof(int32_t), s);
   if (e != hipSuccess) return e;
-  g_union_launches[0].fetch_add(1, std::memory_order_relaxed);
+  g_union_launches.bump(0);
   hipLaunchKernelGGL(lists_union_build_kernel, dim3(n_groups), dim3(kLuThreads), 0, s, u);
   return hipSuccess;
 }
@@ -223,21 +209,12 @@ void launch_lists_union_score(const SetParams &p, const UnionParams &u, int n_cu
   // one workgroup fills a CU (128 KiB of LDS); a few rounds of them even out the groups' last, shorter items
   const int blocks = std::min(u.bound, 4 * (n_cu > 0 ? n_cu : 256));
   const bool fix = p.fix_off != nullptr && p.fix_pairs != nullptr;
-  g_union_launches[fix ? 2 : 1].fetch_add(1, std::memory_order_relaxed);
-  if (fix && p.fastdiv)
-    launch_union_cfg<true, true>(p, u, blocks, s);
-  else if (fix)
-    launch_union_cfg<true, false>(p, u, blocks, s);
-  else if (p.fastdiv)
-    launch_union_cfg<false, true>(p, u, blocks, s);
-  else
-    launch_union_cfg<false, false>(p, u, blocks, s);
+  g_union_launches.bump(fix ? 2 : 1);
+  with_fix_fast(fix, p.fastdiv, [&](auto FIX, auto FAST) { launch_set_tile<lists_union_score_kernel<FIX(), FAST()>>(blocks, s, p, u); });
 }
 
-void lists_union_note_fallback() { g_union_launches[3].fetch_add(1, std::memory_order_relaxed); }
+void lists_union_note_fallback() { g_union_launches.bump(3); }
 
-void lists_union_launch_counts(unsigned long long out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = g_union_launches[i].load(std::memory_order_relaxed);
-}
+void lists_union_launch_counts(unsigned long long out[4]) { g_union_launches.read(out); }
 
 }  // namespace fdnn

@@ -229,28 +229,6 @@ int make_ctx(fdnn_model *m, int n, fdnn_ctx **out, bool lean) {
   return FDNN_OK;
 }
 
-// Brackets one kernel launch with HIP events on the launch stream when profiling is on.
-struct ProfScope {
-  fdnn_model *m;
-  hipStream_t s;
-  int kind;
-  hipEvent_t a = nullptr, b = nullptr;
-  ProfScope(fdnn_model *m_, hipStream_t s_, int kind_) : m(m_), s(s_), kind(kind_) {
-    if (!m->profiling) return;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
-      a = b = nullptr;
-      return;
-    }
-    hipEventRecord(a, s);
-  }
-  ~ProfScope() {
-    if (!a) return;
-    hipEventRecord(b, s);
-    std::lock_guard<std::mutex> lk(m->mu);
-    m->prof.push_back({kind, a, b});
-  }
-};
-
 // one device-side u8 snapshot of the s8 activation buffer (taps only)
 int snapshot_acts(const fdnn_ctx *c, int buf, uint8_t *d_dst, hipStream_t s) {
   const BlobHeader &h = c->m->hm.hdr;
@@ -674,264 +652,6 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
   return FDNN_OK;
 }
 
-// LazyOutputActivations for the listed nodes only (fdnn_lists.hip): the score kernel over the flat entry array, then one
-// wave per row for the total and the scale.  Nothing of the masked output path runs.
-// What the list kernels and the set kernel read of the output layer (a context whose hidden layers have run).
-static fdnn::ListsParams output_layer_params(const fdnn_ctx *c, int first) {
-  const fdnn_model *m = c->m;
-  const BlobHeader &h = m->hm.hdr;
-  const QLayerDesc &d = h.q[h.n_q - 1];
-  const uint8_t *B = m->d_blob;
-  fdnn::ListsParams g{};
-  g.w = reinterpret_cast<const int8_t *>(B + d.off_w);
-  g.a = c->d_act[c->last] + size_t(first) * c->act_ld;
-  g.bias = reinterpret_cast<const float *>(B + d.off_bias);
-  g.wsum = reinterpret_cast<const int32_t *>(B + d.off_wsum);
-  if (d.n_fix > 0) {
-    g.fix_off = m->d_lfix_off;
-    g.fix_pairs = m->d_lfix_pairs;
-  }
-  g.rows = d.rows;
-  g.K = d.cols_pad - fdnn::kRowSkew;
-  g.ldw = d.cols_pad;
-  g.lda = c->act_ld;
-  g.coef = d.coef;
-  g.rcp_coef = d.rcp_coef;
-  g.fastdiv = d.fastdiv_ok;
-  return g;
-}
-
-int run_lists(fdnn_ctx *c, const ListsCall &lc, hipStream_t s) {
-  fdnn_model *m = c->m;
-  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
-  if (lc.first < 0 || lc.count < 0 || lc.first + lc.count > c->n) return fail(FDNN_E_ARG, "frame range outside the context");
-  if (lc.nnz < 0) return fail(FDNN_E_ARG, "negative entry count");
-  if (lc.count == 0) return FDNN_OK;
-  if (!lc.d_row_ptr || !lc.d_inactive || (lc.nnz > 0 && (!lc.d_nodes || !lc.d_probs))) return fail(FDNN_E_ARG, "null list buffer");
-  fdnn::ListsParams g = output_layer_params(c, lc.first);
-  g.row_ptr = lc.d_row_ptr;
-  g.nodes = lc.d_nodes;
-  g.probs = lc.d_probs;
-  g.inactive = lc.d_inactive;
-  g.acc = lc.d_acc;
-  g.count = lc.count;
-  g.nnz = lc.nnz;
-  g.epg = fdnn::lists_entries_per_group(lc.nnz, device_cus(m->device));
-  // fdnn_model_set_lists_union: the entries' e from the set kernels' tile over the union of every 32 g rows' lists
-  // (fdnn_lists_union.hip) where its shape applies -- the same bytes; else, and with the switch off, the dot-product kernels
-  const int group_tiles = m->lists_union;
-  const bool by_union = group_tiles > 0 && fdnn::lunion::shape_applies(g.K, g.rows, g.ldw, g.lda);
-  if (group_tiles > 0 && !by_union) fdnn::lists_union_note_fallback();
-  if (by_union && lc.nnz > 0) {
-    const fdnn::lunion::Layout l = fdnn::lunion::layout(lc.nnz, lc.count, group_tiles);
-    if (l.bound > INT32_MAX / 2) return fail(FDNN_E_ARG, "too many entries for one list call");
-    // (a buffer that is too small is freed and allocated anew, which waits for the device: earlier calls have finished)
-    HIP_TRY(c->d_union.reserve(l.words));
-    int32_t *const b = c->d_union.p;
-    const fdnn::UnionParams u{lc.d_row_ptr, lc.d_nodes, lc.d_probs, lc.d_acc, b + l.u_nodes, b + l.pos, b + l.u_len, b + l.work, b + l.counter,
-                              g.rows, lc.count, lc.nnz, group_tiles, int(l.bound)};
-    fdnn::SetParams p{};
-    p.w = g.w, p.a = g.a, p.bias = g.bias, p.wsum = g.wsum, p.fix_off = g.fix_off, p.fix_pairs = g.fix_pairs;
-    p.rows = g.rows, p.K = g.K, p.ldw = g.ldw, p.lda = g.lda;
-    p.coef = g.coef, p.rcp_coef = g.rcp_coef, p.fastdiv = g.fastdiv;
-    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
-    HIP_TRY(fdnn::launch_lists_union_build(u, l.n_groups, s));
-    fdnn::launch_lists_union_score(p, u, device_cus(m->device), s);
-  } else if (!by_union) {
-    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
-    fdnn::launch_lists_score(g, s);
-  }
-  {
-    ProfScope ps(m, s, FDNN_PROF_NORMALIZE);
-    fdnn::launch_lists_finish(g, s);
-  }
-  HIP_TRY(hipGetLastError());
-  return FDNN_OK;
-}
-
-int lists_to_host(fdnn_ctx *c, int first, int count, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive,
-                  int32_t *acc, hipStream_t s) {
-  const size_t nnz = size_t(row_ptr[count]);
-  // (a buffer that is too small is freed and allocated anew: the context's earlier list calls have been synchronised)
-  HIP_TRY(c->d_lrow.reserve(size_t(count) + 1));
-  HIP_TRY(c->d_linact.reserve(size_t(count)));
-  HIP_TRY(c->d_lnodes.reserve(std::max<size_t>(nnz, 1)));
-  HIP_TRY(c->d_lprobs.reserve(std::max<size_t>(nnz, 1)));
-  DevBuf<int32_t> d_acc;
-  if (acc) HIP_TRY(d_acc.reserve(std::max<size_t>(nnz, 1)));
-  HIP_TRY(hipMemcpyAsync(c->d_lrow, row_ptr, sizeof(int32_t) * (size_t(count) + 1), hipMemcpyHostToDevice, s));
-  if (nnz) HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, s));
-  int rc = run_lists(c, {first, count, c->d_lrow, c->d_lnodes, int(nnz), c->d_lprobs, c->d_linact, acc ? d_acc.p : nullptr}, s);
-  if (rc) {
-    hipStreamSynchronize(s);
-    return rc;
-  }
-  if (nnz && probs) HIP_TRY(hipMemcpyAsync(probs, c->d_lprobs, sizeof(float) * nnz, hipMemcpyDeviceToHost, s));
-  if (inactive) HIP_TRY(hipMemcpyAsync(inactive, c->d_linact, sizeof(float) * size_t(count), hipMemcpyDeviceToHost, s));
-  if (nnz && acc) HIP_TRY(hipMemcpyAsync(acc, d_acc, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FDNN_OK;
-}
-
-// LazyOutputActivations for ONE node set shared by rows [first, first + count) (fdnn_set.hip): e = exp(z) of the gathered
-// rows on the int8 MFMA, then the list path's finish kernel with the uniform row stride len.  Where the MFMA kernel's shape
-// does not apply (fdnn_set.hpp: shape_applies) the list kernels serve the call over lists synthesized from the set: the
-// same bytes by construction.
-int run_set(fdnn_ctx *c, const SetCall &sc, hipStream_t s) {
-  fdnn_model *m = c->m;
-  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
-  if (sc.first < 0 || sc.count < 0 || sc.first + sc.count > c->n) return fail(FDNN_E_ARG, "frame range outside the context");
-  if (sc.len < 0 || sc.len > m->hm.hdr.out_dim) return fail(FDNN_E_ARG, "a node set has 0 .. output_dim nodes");
-  const long long nnz = static_cast<long long>(sc.count) * sc.len;
-  if (nnz > INT32_MAX) return fail(FDNN_E_ARG, "count x len must fit an int32");
-  if (sc.count == 0) return FDNN_OK;
-  if (!sc.d_inactive || (sc.len > 0 && (!sc.d_nodes || !sc.d_probs))) return fail(FDNN_E_ARG, "null set buffer");
-  fdnn::ListsParams g = output_layer_params(c, sc.first);
-  g.probs = sc.d_probs;
-  g.inactive = sc.d_inactive;
-  g.acc = sc.d_acc;
-  g.count = sc.count;
-  g.nnz = int(nnz);
-  // the default rule (mode 0) is mode 1's: the MFMA kernel wherever its shape applies
-  const bool mfma = fdnn::set_kernel_mode() != 2 && fdnn::set::shape_applies(g.K, g.rows, g.ldw, g.lda);
-  if (sc.len > 0 && mfma) {
-    fdnn::SetParams p{};
-    p.w = g.w, p.a = g.a, p.bias = g.bias, p.wsum = g.wsum, p.fix_off = g.fix_off, p.fix_pairs = g.fix_pairs;
-    p.nodes = sc.d_nodes, p.probs = sc.d_probs, p.acc = sc.d_acc;
-    p.rows = g.rows, p.K = g.K, p.ldw = g.ldw, p.lda = g.lda, p.count = sc.count, p.len = sc.len;
-    p.coef = g.coef, p.rcp_coef = g.rcp_coef, p.fastdiv = g.fastdiv;
-    p.plan = fdnn::set::plan(sc.count, sc.len, device_cus(m->device));
-    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
-    fdnn::launch_set_score(p, s);
-  } else if (sc.len > 0) {
-    // (a buffer that is too small is freed and allocated anew, which waits for the device: earlier calls have finished)
-    HIP_TRY(c->d_srow.reserve(size_t(sc.count) + 1));
-    HIP_TRY(c->d_snodes.reserve(size_t(nnz)));
-    fdnn::launch_set_expand(sc.d_nodes, sc.len, sc.count, c->d_srow, c->d_snodes, s);
-    g.row_ptr = c->d_srow;
-    g.nodes = c->d_snodes;
-    g.epg = fdnn::lists_entries_per_group(nnz, device_cus(m->device));
-    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
-    fdnn::launch_lists_score(g, s);
-  }
-  if (!g.row_ptr) g.row_len = sc.len;  // the finish kernel's uniform rows: r * len .. (r + 1) * len
-  {
-    ProfScope ps(m, s, FDNN_PROF_NORMALIZE);
-    fdnn::launch_lists_finish(g, s);
-  }
-  HIP_TRY(hipGetLastError());
-  return FDNN_OK;
-}
-
-int set_to_host(fdnn_ctx *c, int first, int count, const int32_t *nodes, int len, float *probs, float *inactive, int32_t *acc, hipStream_t s) {
-  if (len < 0 || static_cast<long long>(count) * len > INT32_MAX) return fail(FDNN_E_ARG, "count x len must fit an int32");
-  const size_t nnz = size_t(count) * size_t(len);
-  HIP_TRY(c->d_linact.reserve(std::max<size_t>(size_t(count), 1)));
-  HIP_TRY(c->d_lnodes.reserve(std::max<size_t>(size_t(len), 1)));
-  HIP_TRY(c->d_lprobs.reserve(std::max<size_t>(nnz, 1)));
-  DevBuf<int32_t> d_acc;
-  if (acc) HIP_TRY(d_acc.reserve(std::max<size_t>(nnz, 1)));
-  if (len) HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * size_t(len), hipMemcpyHostToDevice, s));
-  int rc = run_set(c, {first, count, c->d_lnodes, len, c->d_lprobs, c->d_linact, acc ? d_acc.p : nullptr}, s);
-  if (rc) {
-    hipStreamSynchronize(s);
-    return rc;
-  }
-  if (nnz && probs) HIP_TRY(hipMemcpyAsync(probs, c->d_lprobs, sizeof(float) * nnz, hipMemcpyDeviceToHost, s));
-  if (inactive) HIP_TRY(hipMemcpyAsync(inactive, c->d_linact, sizeof(float) * size_t(count), hipMemcpyDeviceToHost, s));
-  if (nnz && acc) HIP_TRY(hipMemcpyAsync(acc, d_acc, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FDNN_OK;
-}
-
-// LazyOutputActivations with one node set per segment (fdnn_sets.hip): the set kernel's tile on every segment, at most
-// sets::kMaxSegs segments per launch, then the list path's finish kernel over the row pointer of the ragged blocks.  Where
-// the MFMA kernel's shape does not apply the list kernels serve the call over the sets written out as lists.
-int run_sets(fdnn_ctx *c, const SetsCall &sc, hipStream_t s) {
-  fdnn_model *m = c->m;
-  if (c->last < 0) return fail(FDNN_E_STATE, "lazy output requested before the hidden layers were computed");
-  if (!sc.segs) return fail(FDNN_E_ARG, "null argument");
-  const std::vector<fdnn::sets::Seg> &segs = *sc.segs;
-  long long nnz = 0;
-  int count = 0;
-  for (size_t i = 0; i < segs.size(); ++i) {
-    const fdnn::sets::Seg &g = segs[i];
-    if (g.rows < 0 || g.row0 != count) return fail(FDNN_E_ARG, "segment " + std::to_string(i) + ": rows must follow the segment before");
-    if (g.len < 0 || g.len > m->hm.hdr.out_dim || g.set_off < 0)
-      return fail(FDNN_E_ARG, "segment " + std::to_string(i) + ": a node set has 0 .. output_dim nodes");
-    if (g.out_off != nnz) return fail(FDNN_E_ARG, "segment " + std::to_string(i) + ": blocks must follow each other");
-    count += g.rows;
-    nnz += static_cast<long long>(g.rows) * g.len;
-    if (nnz > INT32_MAX) return fail(FDNN_E_ARG, "segment " + std::to_string(i) + ": the sum of rows x len must fit an int32");
-  }
-  if (sc.first < 0 || sc.first + count > c->n) return fail(FDNN_E_ARG, "frame range outside the context");
-  if (count == 0) return FDNN_OK;
-  if (!sc.d_inactive || (nnz > 0 && (!sc.d_nodes || !sc.d_probs))) return fail(FDNN_E_ARG, "null set buffer");
-  fdnn::ListsParams g = output_layer_params(c, sc.first);
-  g.probs = sc.d_probs;
-  g.inactive = sc.d_inactive;
-  g.acc = sc.d_acc;
-  g.count = count;
-  g.nnz = int(nnz);
-  const bool mfma = fdnn::set_kernel_mode() != 2 && fdnn::set::shape_applies(g.K, g.rows, g.ldw, g.lda);
-  // the finish pass's row pointer [count + 1] and, for the fallback, where each row's set begins [count], side by side in
-  // the staging buffer: written on the device from the launch tables, so an enqueued call leaves no host memory behind.
-  // (A buffer that is too small is freed and allocated anew, which waits for the device: earlier calls have finished.)
-  HIP_TRY(c->d_srow.reserve(size_t(2) * size_t(count) + 1));
-  int32_t *const d_row_set = mfma ? nullptr : c->d_srow.p + count + 1;
-  const std::vector<fdnn::sets::Launch> launches = fdnn::sets::plan(segs, device_cus(m->device));
-  for (size_t i = 0; i < launches.size(); ++i)
-    fdnn::launch_sets_rows(launches[i], c->d_srow, d_row_set, i + 1 == launches.size() ? count : -1, int(nnz), s);
-  g.row_ptr = c->d_srow;
-  if (nnz > 0 && mfma) {
-    fdnn::SetParams p{};
-    p.w = g.w, p.a = g.a, p.bias = g.bias, p.wsum = g.wsum, p.fix_off = g.fix_off, p.fix_pairs = g.fix_pairs;
-    p.nodes = sc.d_nodes, p.probs = sc.d_probs, p.acc = sc.d_acc;
-    p.rows = g.rows, p.K = g.K, p.ldw = g.ldw, p.lda = g.lda;
-    p.coef = g.coef, p.rcp_coef = g.rcp_coef, p.fastdiv = g.fastdiv;
-    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
-    for (const fdnn::sets::Launch &l : launches) fdnn::launch_sets_score(p, l, s);
-  } else if (nnz > 0) {
-    HIP_TRY(c->d_snodes.reserve(size_t(nnz)));
-    fdnn::launch_sets_expand(sc.d_nodes, c->d_srow, d_row_set, count, c->d_snodes, s);
-    g.nodes = c->d_snodes;
-    g.epg = fdnn::lists_entries_per_group(nnz, device_cus(m->device));
-    ProfScope ps(m, s, FDNN_PROF_OUTPUT);
-    fdnn::launch_lists_score(g, s);
-  }
-  {
-    ProfScope ps(m, s, FDNN_PROF_NORMALIZE);
-    fdnn::launch_lists_finish(g, s);
-  }
-  HIP_TRY(hipGetLastError());
-  return FDNN_OK;
-}
-
-int sets_to_host(fdnn_ctx *c, int first, const std::vector<fdnn::sets::Seg> &segs, const int32_t *nodes, int n_nodes, float *probs,
-                 float *inactive, int32_t *acc, hipStream_t s) {
-  size_t nnz = 0, count = 0;
-  for (const fdnn::sets::Seg &g : segs) nnz += size_t(g.rows) * size_t(g.len), count += size_t(g.rows);
-  if (nnz > size_t(INT32_MAX)) return fail(FDNN_E_ARG, "the sum of rows x len must fit an int32");
-  HIP_TRY(c->d_linact.reserve(std::max<size_t>(count, 1)));
-  HIP_TRY(c->d_lnodes.reserve(std::max<size_t>(size_t(n_nodes), 1)));
-  HIP_TRY(c->d_lprobs.reserve(std::max<size_t>(nnz, 1)));
-  DevBuf<int32_t> d_acc;
-  if (acc) HIP_TRY(d_acc.reserve(std::max<size_t>(nnz, 1)));
-  if (n_nodes > 0) HIP_TRY(hipMemcpyAsync(c->d_lnodes, nodes, sizeof(int32_t) * size_t(n_nodes), hipMemcpyHostToDevice, s));
-  SetsCall sc;
-  sc.first = first, sc.segs = &segs, sc.d_nodes = c->d_lnodes, sc.d_probs = c->d_lprobs, sc.d_inactive = c->d_linact, sc.d_acc = acc ? d_acc.p : nullptr;
-  int rc = run_sets(c, sc, s);
-  if (rc) {
-    hipStreamSynchronize(s);
-    return rc;
-  }
-  if (nnz && probs) HIP_TRY(hipMemcpyAsync(probs, c->d_lprobs, sizeof(float) * nnz, hipMemcpyDeviceToHost, s));
-  if (count && inactive) HIP_TRY(hipMemcpyAsync(inactive, c->d_linact, sizeof(float) * count, hipMemcpyDeviceToHost, s));
-  if (nnz && acc) HIP_TRY(hipMemcpyAsync(acc, d_acc, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FDNN_OK;
-}
-
 bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks) { return choose_output(c, count, d_masks != nullptr, false, nullptr, true).fused; }
 
 // Device -> pageable host memory for large results (the 8000-float rows of a whole batch:
@@ -1243,25 +963,23 @@ int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, 
     if (p.x) e = hipMemcpyAsync(c->d_x, p.x + off * D, sizeof(float) * size_t(cnt) * D, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && p.bits) e = hipMemcpyAsync(c->d_mask_bits, p.bits + off * wpr, sizeof(uint64_t) * size_t(cnt) * wpr, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) break;
-    if (p.row_ptr) {  // the chunk's slice of the lists as lists of its own (synchronises: `rebased` is free for the next chunk)
+    if (p.row_ptr || p.set_given || p.sets) {  // the chunk's entries through the host form, which synchronises
       rc = run_hidden(c, c->d_x, s, nullptr);
-      lists::rebase_rows(p.row_ptr, int(off), cnt, &rebased);
-      const size_t e0 = size_t(p.row_ptr[off]);
-      if (!rc) rc = lists_to_host(c, 0, cnt, rebased.data(), p.nodes + e0, p.probs + e0, p.inactive + off, nullptr, s);
-      if (rc) hipStreamSynchronize(s);
-      continue;
-    }
-    if (p.set_given) {  // one node set for every chunk: the chunk's rows land at probs + off * len
-      rc = run_hidden(c, c->d_x, s, nullptr);
-      if (!rc) rc = set_to_host(c, 0, cnt, p.set_nodes, p.set_len, p.probs + off * size_t(p.set_len), p.inactive + off, nullptr, s);
-      if (rc) hipStreamSynchronize(s);
-      continue;
-    }
-    if (p.sets) {  // the chunk's slice of the segments: its blocks are one contiguous range of the caller's probs
-      rc = run_hidden(c, c->d_x, s, nullptr);
-      const std::vector<fdnn::sets::Seg> segs = fdnn::sets::slice(*p.sets, int(off), int(off) + cnt);
-      if (!rc && !segs.empty())
-        rc = sets_to_host(c, 0, segs, p.nodes, p.sets->set_ptr[p.sets->n_segs], p.probs + size_t(segs[0].src_off), p.inactive + off, nullptr, s);
+      HostEntries he;
+      he.count = cnt, he.inactive = p.inactive + off;
+      std::vector<fdnn::sets::Seg> segs;
+      if (p.row_ptr) {  // the chunk's slice of the lists as lists of its own (`rebased` is free for the next chunk)
+        lists::rebase_rows(p.row_ptr, int(off), cnt, &rebased);
+        const size_t e0 = size_t(p.row_ptr[off]);
+        he.row_ptr = rebased.data(), he.nodes = p.nodes + e0, he.n_nodes = rebased[size_t(cnt)], he.probs = p.probs + e0;
+      } else if (p.set_given) {  // one node set for every chunk: the chunk's rows land at probs + off * len
+        he.len = he.n_nodes = p.set_len, he.nodes = p.set_nodes, he.probs = p.probs + off * size_t(p.set_len);
+      } else {  // the chunk's slice of the segments: its blocks are one contiguous range of the caller's probs
+        segs = fdnn::sets::slice(*p.sets, int(off), int(off) + cnt);
+        he.segs = &segs, he.nodes = p.nodes, he.n_nodes = p.sets->set_ptr[p.sets->n_segs];
+        if (!segs.empty()) he.probs = p.probs + size_t(segs[0].src_off);
+      }
+      if (!rc && (!p.sets || !segs.empty())) rc = entries_to_host(c, he, s);
       if (rc) hipStreamSynchronize(s);
       continue;
     }

@@ -21,7 +21,8 @@
 // Each of the 8 waves owns a 256-byte slice of K, requests its slice of W and of the first activation tile by LDS-DMA up
 // front, keeps W in registers (64 VGPRs of MFMA fragments) and streams activation tiles through a double buffer; the eight
 // partial 64 x 32 int32 tiles meet in LDS.  The tile itself is fdnn_set_tile.hpp's set_tile, shared with fdnn_sets.hip (one set per
-// segment of the row range): this kernel runs it on the whole call.
+// segment of the row range): this kernel runs it on the whole call.  So is its launch: that header's launch_set_tile (the
+// dynamic LDS limit, once per device) on the <FIX, FAST> instance fdnn_launch.hpp's with_fix_fast picks.
 #include <algorithm>
 #include <atomic>
 
@@ -32,7 +33,7 @@
 namespace fdnn {
 namespace {
 
-std::atomic<unsigned long long> g_set_launches[3];  // MFMA kernel without / with the pair walk, calls served by the list kernels
+LaunchCounts<3> g_set_launches;                     // MFMA kernel without / with the pair walk, calls served by the list kernels
 std::atomic<int> g_set_mode{0};                     // fdnn_debug_set_kernel
 
 // FIX: the layer has saturating pairs (the walk over a node's own list); FAST: validated 3-operation division
@@ -49,45 +50,22 @@ __global__ __launch_bounds__(256) void set_expand_kernel(const int32_t *nodes, i
   if (i <= count) row_ptr[i] = static_cast<int32_t>(i * len);
 }
 
-template <bool FIX, bool FAST>
-void launch_set_cfg(const SetParams &p, hipStream_t s) {
-  auto k = set_score_kernel<FIX, FAST>;
-  static std::atomic<unsigned long long> attr_set{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long dev_bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & dev_bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kStLds);
-    attr_set.fetch_or(dev_bit, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(k, dim3(p.plan.blocks), dim3(kStThreads), kStLds, s, p);
-}
-
 }  // namespace
 
 void launch_set_score(const SetParams &p, hipStream_t s) {
   if (p.plan.blocks <= 0) return;
   const bool fix = p.fix_off != nullptr && p.fix_pairs != nullptr;
-  g_set_launches[fix ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
-  if (fix && p.fastdiv)
-    launch_set_cfg<true, true>(p, s);
-  else if (fix)
-    launch_set_cfg<true, false>(p, s);
-  else if (p.fastdiv)
-    launch_set_cfg<false, true>(p, s);
-  else
-    launch_set_cfg<false, false>(p, s);
+  g_set_launches.bump(fix ? 1 : 0);
+  with_fix_fast(fix, p.fastdiv, [&](auto FIX, auto FAST) { launch_set_tile<set_score_kernel<FIX(), FAST()>>(p.plan.blocks, s, p); });
 }
 
 void launch_set_expand(const int32_t *nodes, int len, int count, int32_t *row_ptr, int32_t *rep, hipStream_t s) {
   const long long items = std::max<long long>(static_cast<long long>(count) * len, static_cast<long long>(count) + 1);
-  g_set_launches[2].fetch_add(1, std::memory_order_relaxed);
+  g_set_launches.bump(2);
   hipLaunchKernelGGL(set_expand_kernel, dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0, s, nodes, len, count, row_ptr, rep);
 }
 
-void set_launch_counts(unsigned long long out[3]) {
-  for (int i = 0; i < 3; ++i) out[i] = g_set_launches[i].load(std::memory_order_relaxed);
-}
+void set_launch_counts(unsigned long long out[3]) { g_set_launches.read(out); }
 
 int set_kernel_mode() { return g_set_mode.load(std::memory_order_relaxed); }
 void set_kernel_mode(int mode) { g_set_mode.store(mode, std::memory_order_relaxed); }

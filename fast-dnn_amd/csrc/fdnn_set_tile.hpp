@@ -7,6 +7,7 @@
 #pragma once
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
+#include "fdnn_launch.hpp"
 
 namespace fdnn {
 namespace {
@@ -19,6 +20,21 @@ constexpr int kStABuf = kStWaves * kStFT * kStSlice;     // one activation tile:
 constexpr int kStLds = 2 * kStABuf;
 static_assert(kStWaves * kStSlice == set::kMaxK && set::kNodeTile == 64 && kStFT == 32, "fdnn_set.hpp states this kernel's sizes");
 static_assert(kStLds <= 160 * 1024, "LDS");
+
+// The launch of a score kernel over set_tile: kStThreads threads and kStLds of dynamic LDS, whose limit is raised once per
+// device and kernel instance (the bit set below belongs to this instantiation, hence the kernel as a template argument).
+template <auto Kernel, class... Args>
+void launch_set_tile(unsigned blocks, hipStream_t s, const Args &...args) {
+  static std::atomic<unsigned long long> attr_set{0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const unsigned long long dev_bit = 1ull << (dev & 63);
+  if (!(attr_set.load(std::memory_order_acquire) & dev_bit)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kStLds);
+    attr_set.fetch_or(dev_bit, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(kStThreads), kStLds, s, args...);
+}
 
 // What one workgroup scores: rows [0, count) at `a`, entries [m0, m0 + 64) of the set nodes[len], frame tiles
 // [t_begin, t_end) counted from a's first row; e of (row r, entry j) goes where the store policy says (DenseStore:

@@ -7,7 +7,7 @@
 // fdnn_set.hip scores one set over a row range in two launches of 11 - 13 us: more than the work of a 100-frame utterance
 // with 80 nodes.  Callers that serve many utterances, each with its own set (forced alignment, keyword spotting, n-best
 // rescoring), would pay that per utterance.  Here a workgroup runs fdnn_set_tile.hpp's tile -- the very code of
-// set_score_kernel -- on the segment that sets::block_tile names for it:
+// set_score_kernel, launched by the same launch_set_tile -- on the segment that sets::block_tile names for it:
 //
 //   * the segment table (sets::Launch, up to 64 segments) is a kernel argument; the segment of a workgroup is found by a
 //     binary search over block_off on the scalar unit, and what the segment contributes to addresses (its first row, where
@@ -21,8 +21,6 @@
 // The total and the scale are the list path's finish kernel over the row pointer the call synthesizes (sets::row_ptr): the
 // bytes of a row are those of fdnn_ctx_lazy_output_set on its segment alone and of fdnn_ctx_lazy_output_lists with the sets
 // repeated per row.  Where the tile's shape does not apply, sets_expand_kernel writes those lists and the list kernels score.
-#include <atomic>
-
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
 #include "fdnn_set_tile.hpp"
@@ -30,7 +28,7 @@
 namespace fdnn {
 namespace {
 
-std::atomic<unsigned long long> g_sets_launches[3];  // MFMA kernel without / with the pair walk, calls served by the list kernels
+LaunchCounts<3> g_sets_launches;  // MFMA kernel without / with the pair walk, calls served by the list kernels
 
 // p: the layer, and a / nodes / probs / acc of the call's first row, whole node array and first block (count, len and plan
 // are not read); l: this launch's segments
@@ -66,34 +64,13 @@ __global__ __launch_bounds__(256) void sets_expand_kernel(const int32_t *nodes, 
   for (int j = threadIdx.x; j < len; j += 256) rep[b + j] = set[j];
 }
 
-template <bool FIX, bool FAST>
-void launch_sets_cfg(const SetParams &p, const sets::Launch &l, hipStream_t s) {
-  auto k = sets_score_kernel<FIX, FAST>;
-  static std::atomic<unsigned long long> attr_set{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long dev_bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & dev_bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kStLds);
-    attr_set.fetch_or(dev_bit, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(k, dim3(sets::blocks(l)), dim3(kStThreads), kStLds, s, p, l);
-}
-
 }  // namespace
 
 void launch_sets_score(const SetParams &p, const sets::Launch &l, hipStream_t s) {
   if (sets::blocks(l) <= 0) return;
   const bool fix = p.fix_off != nullptr && p.fix_pairs != nullptr;
-  g_sets_launches[fix ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
-  if (fix && p.fastdiv)
-    launch_sets_cfg<true, true>(p, l, s);
-  else if (fix)
-    launch_sets_cfg<true, false>(p, l, s);
-  else if (p.fastdiv)
-    launch_sets_cfg<false, true>(p, l, s);
-  else
-    launch_sets_cfg<false, false>(p, l, s);
+  g_sets_launches.bump(fix ? 1 : 0);
+  with_fix_fast(fix, p.fastdiv, [&](auto FIX, auto FAST) { launch_set_tile<sets_score_kernel<FIX(), FAST()>>(sets::blocks(l), s, p, l); });
 }
 
 void launch_sets_rows(const sets::Launch &l, int32_t *row_ptr, int32_t *row_set, int end_row, int end, hipStream_t s) {
@@ -102,13 +79,11 @@ void launch_sets_rows(const sets::Launch &l, int32_t *row_ptr, int32_t *row_set,
 }
 
 void launch_sets_expand(const int32_t *nodes, const int32_t *row_ptr, const int32_t *row_set, int count, int32_t *rep, hipStream_t s) {
-  g_sets_launches[2].fetch_add(1, std::memory_order_relaxed);
+  g_sets_launches.bump(2);
   if (count <= 0) return;
   hipLaunchKernelGGL(sets_expand_kernel, dim3(count), dim3(256), 0, s, nodes, row_ptr, row_set, rep);
 }
 
-void sets_launch_counts(unsigned long long out[3]) {
-  for (int i = 0; i < 3; ++i) out[i] = g_sets_launches[i].load(std::memory_order_relaxed);
-}
+void sets_launch_counts(unsigned long long out[3]) { g_sets_launches.read(out); }
 
 }  // namespace fdnn
