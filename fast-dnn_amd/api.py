@@ -179,6 +179,28 @@ SIGNATURES = {
                                        C.POINTER(C.c_int)]),
     "fdnn_host_sigmoid_lut": (C.c_int, [_c_u8p]),
     "fdnn_host_quantize": (C.c_int, [_c_f32p, C.c_int, C.c_int, C.c_float, _c_i8p, _c_f32p]),
+    "fdnn_float_model_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "fdnn_float_model_load_on": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "fdnn_float_model_free": (None, [C.c_void_p]),
+    "fdnn_float_model_input_dim": (C.c_int, [C.c_void_p]),
+    "fdnn_float_model_output_dim": (C.c_int, [C.c_void_p]),
+    "fdnn_float_model_layer_count": (C.c_int, [C.c_void_p]),
+    "fdnn_float_model_layer_dim": (C.c_int, [C.c_void_p, C.c_int]),
+    "fdnn_float_model_device": (C.c_int, [C.c_void_p]),
+    "fdnn_float_calculate": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_f32p]),
+    "fdnn_float_calculate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fdnn_debug_float_layer": (C.c_int, [C.c_void_p, C.c_int, _c_f32p, C.c_int, _c_f32p, _c_f32p]),
+    "fdnn_debug_float_layer_us": (C.c_int, [C.c_void_p, C.c_int, _c_f32p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "fdnn_debug_float_layer_ref": (C.c_int, [_c_f32p, _c_f32p, C.c_int, C.c_int, _c_f32p, C.c_int, _c_f32p]),
+    "fdnn_debug_float_input_ref": (C.c_int, [_c_f32p, _c_f32p, C.c_int, _c_f32p, C.c_int, _c_f32p, _c_f32p]),
+    "fdnn_debug_float_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "fdnn_debug_float_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_report_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "fdnn_report_free": (None, [C.c_void_p]),
+    "fdnn_report_reset": (C.c_int, [C.c_void_p]),
+    "fdnn_report_add_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "fdnn_report_add": (C.c_int, [C.c_void_p, _c_f32p, _c_f32p, C.c_int]),
+    "fdnn_report_read": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 JNI_SYMBOLS = [
@@ -1279,3 +1301,172 @@ def host_quantize(w, cutoff: float = 3.0):
     _check(lib().fdnn_host_quantize(w.ctypes.data_as(_c_f32p), w.shape[0], w.shape[1], cutoff, out.ctypes.data_as(_c_i8p),
                                     C.byref(mult)))
     return out, float(mult.value)
+
+
+# ------------------------------------------------------------------------------------------------ the unquantized net
+FLOAT_LAUNCH_KINDS = ("fgemm.sigmoid", "fgemm.exp", "fgemm.sigmoid.tap", "fgemm.exp.tap", "input_step", "report.rows", "report.nodes",
+                      "report.fold")
+
+
+def float_launches() -> dict:
+    """Process-wide launch counts of the float net's and the report's kernels since load (``fdnn_debug_float_launches``)."""
+    buf = (C.c_ulonglong * len(FLOAT_LAUNCH_KINDS))()
+    if lib().fdnn_debug_float_launches(buf, len(FLOAT_LAUNCH_KINDS)) != len(FLOAT_LAUNCH_KINDS):
+        raise RuntimeError("fdnn_debug_float_launches")
+    return dict(zip(FLOAT_LAUNCH_KINDS, (int(v) for v in buf)))
+
+
+def float_layer_ref(weights, bias, input) -> np.ndarray:
+    """The host restatement of one layer's sums (``fdnn_debug_float_layer_ref``, no device): per output, s = 0, for k
+    ascending s = fmaf(x[k], w[k], s), then s + bias.  weights [rows][K], input [n][K] -> [n][rows]."""
+    w, b, x = _f32(weights), _f32(bias), _f32(input)
+    if w.ndim != 2 or x.ndim != 2 or x.shape[1] != w.shape[1] or b.shape != (w.shape[0],):
+        raise ValueError("weights [rows][K], bias [rows], input [n][K]")
+    out = np.empty((x.shape[0], w.shape[0]), dtype=np.float32)
+    _check(lib().fdnn_debug_float_layer_ref(w.ctypes.data_as(_c_f32p), b.ctypes.data_as(_c_f32p), w.shape[0], w.shape[1],
+                                            x.ctypes.data_as(_c_f32p), x.shape[0], out.ctypes.data_as(_c_f32p)))
+    return out
+
+
+def float_input_ref(shift, scale, input):
+    """The host restatement of the input step (``fdnn_debug_float_input_ref``, no device) -> (x + shift, (x + shift) * scale)."""
+    sh, sc, x = _f32(shift), _f32(scale), _f32(input)
+    if x.ndim != 2 or sh.shape != (x.shape[1],) or sc.shape != sh.shape:
+        raise ValueError("shift [dim], scale [dim], input [n][dim]")
+    lin, act = np.empty_like(x), np.empty_like(x)
+    _check(lib().fdnn_debug_float_input_ref(sh.ctypes.data_as(_c_f32p), sc.ctypes.data_as(_c_f32p), x.shape[1], x.ctypes.data_as(_c_f32p),
+                                            x.shape[0], lin.ctypes.data_as(_c_f32p), act.ctypes.data_as(_c_f32p)))
+    return lin, act
+
+
+class FloatDnn:
+    """The UNQUANTIZED net (``suskun.nn.FeedForwardNetwork``) on one MI355X: fp32 GEMMs on the f32-input MFMA.  The yardstick
+    the quantized scorer is measured against, and a scorer in its own right."""
+
+    def __init__(self, handle: int):
+        self.nativeHandle = handle
+
+    @staticmethod
+    def loadFromFile(dnnFile: str, device: Optional[int] = None) -> "FloatDnn":
+        h = C.c_void_p()
+        path = os.path.abspath(dnnFile).encode()
+        if device is None:
+            _check(lib().fdnn_float_model_load(path, C.byref(h)))
+        else:
+            _check(lib().fdnn_float_model_load_on(path, int(device), C.byref(h)))
+        return FloatDnn(h.value)
+
+    def delete(self) -> None:
+        if self.nativeHandle:
+            lib().fdnn_float_model_free(self.nativeHandle)
+            self.nativeHandle = None
+
+    def inputDimension(self) -> int:
+        return lib().fdnn_float_model_input_dim(self.nativeHandle)
+
+    def outputDimension(self) -> int:
+        return lib().fdnn_float_model_output_dim(self.nativeHandle)
+
+    def layerCount(self) -> int:
+        return lib().fdnn_float_model_layer_count(self.nativeHandle)
+
+    def layerDimension(self, layerIndex: int) -> int:
+        return lib().fdnn_float_model_layer_dim(self.nativeHandle, int(layerIndex))
+
+    def device(self) -> int:
+        return lib().fdnn_float_model_device(self.nativeHandle)
+
+    def calculate(self, input) -> np.ndarray:
+        """``FeedForwardNetwork.calculate`` (:133-148): [n][inputDimension] -> soft-max rows [n][outputDimension]."""
+        x = _f32(input)
+        if x.shape[0] == 0:
+            return np.zeros((0, 0), dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.inputDimension():
+            raise ValueError(f"Input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        out = np.empty((x.shape[0], self.outputDimension()), dtype=np.float32)
+        _check(lib().fdnn_float_calculate(self.nativeHandle, x.ctypes.data_as(_c_f32p), x.shape[0], x.shape[1], out.ctypes.data_as(_c_f32p)))
+        return out
+
+    def calculateDevice(self, d_x: int, n: int, d_out: int, stream: int = 0) -> None:
+        """Device-resident form: raw device pointers (e.g. ``tensor.data_ptr()``), enqueued on ``stream``, not synchronised."""
+        _check(lib().fdnn_float_calculate_device(self.nativeHandle, C.c_void_p(d_x), int(n), C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def setChunk(self, rows: int) -> None:
+        """Frames per internal chunk (``fdnn_debug_float_set_chunk``; 0 = default).  Results never depend on it."""
+        _check(lib().fdnn_debug_float_set_chunk(self.nativeHandle, int(rows)))
+
+    def layer(self, j: int, input):
+        """ONE layer on the caller's rows (``fdnn_debug_float_layer``) -> (z, activation); j == -1 is the input step ->
+        (x + shift, (x + shift) * scale)."""
+        x = _f32(input)
+        width = self.inputDimension() if j < 0 else self.layerDimension(j)
+        if width < 0:
+            raise ValueError(f"layer index {j} outside -1 .. {self.layerCount() - 1}")
+        lin = np.empty((x.shape[0], width), dtype=np.float32)
+        act = np.empty_like(lin)
+        _check(lib().fdnn_debug_float_layer(self.nativeHandle, int(j), x.ctypes.data_as(_c_f32p), x.shape[0], lin.ctypes.data_as(_c_f32p),
+                                            act.ctypes.data_as(_c_f32p)))
+        return lin, act
+
+    def layerMicros(self, j: int, input, reps: int = 10) -> float:
+        """Device microseconds per run of layer j on the caller's rows: one upload, a warm-up run, ``reps`` runs back to back
+        between two events (``fdnn_debug_float_layer_us``; measurement only)."""
+        x = _f32(input)
+        us = C.c_double()
+        _check(lib().fdnn_debug_float_layer_us(self.nativeHandle, int(j), x.ctypes.data_as(_c_f32p), x.shape[0], int(reps), C.byref(us)))
+        return float(us.value)
+
+
+class _Accuracy(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("nan_rows", C.c_uint64), ("top1_agree", C.c_uint64), ("nodes_over", C.c_uint64),
+                ("sum_abs", C.c_double), ("max_abs", C.c_double), ("max_node_sum", C.c_double)]
+
+
+class AccuracyReport:
+    """``FuncTest.diff`` on the device (``fdnn_report_*``): accumulates over any number of ``add`` calls."""
+
+    def __init__(self, outputDimension: int, device: int = 0):
+        h = C.c_void_p()
+        _check(lib().fdnn_report_create(int(device), int(outputDimension), C.byref(h)))
+        self.h = h.value
+        self.O = int(outputDimension)
+
+    def delete(self) -> None:
+        if self.h:
+            lib().fdnn_report_free(self.h)
+            self.h = None
+
+    def reset(self) -> None:
+        _check(lib().fdnn_report_reset(self.h))
+
+    def add(self, reference, quantized) -> None:
+        r, q = _f32(reference), _f32(quantized)
+        if r.ndim != 2 or r.shape != q.shape or r.shape[1] != self.O:
+            raise ValueError(f"reference and quantized must both be [n][{self.O}]")
+        _check(lib().fdnn_report_add(self.h, r.ctypes.data_as(_c_f32p), q.ctypes.data_as(_c_f32p), r.shape[0]))
+
+    def addDevice(self, d_ref: int, d_q: int, n: int, stream: int = 0) -> None:
+        _check(lib().fdnn_report_add_device(self.h, C.c_void_p(d_ref), C.c_void_p(d_q), int(n), C.c_void_p(stream)))
+
+    def read(self, threshold: float = 0.1, nodeSums: bool = False) -> dict:
+        """The keys of ``convert.quantization_report`` plus ``nan_rows`` (rows with a NaN in either matrix: counted there, left
+        out of everything else); with ``nodeSums`` also ``node_sum`` [outputDimension] float64."""
+        a = _Accuracy()
+        ns = np.empty(self.O, dtype=np.float64) if nodeSums else None
+        _check(lib().fdnn_report_read(self.h, float(threshold), C.byref(a), ns.ctypes.data_as(C.POINTER(C.c_double)) if nodeSums else None))
+        used = int(a.frames) - int(a.nan_rows)
+        out = {
+            "frames": int(a.frames),
+            "nodes": self.O,
+            "nodes_over_0.1" if threshold == 0.1 else f"nodes_over_{threshold:g}": int(a.nodes_over),
+            "max_node_sum_abs_diff": float(a.max_node_sum),
+            "mean_abs_diff": float(a.sum_abs) / (used * self.O) if used else 0.0,
+            "max_abs_diff": float(a.max_abs),
+            "top1_agreement": int(a.top1_agree) / used if used else 0.0,
+            "nan_rows": int(a.nan_rows),
+            "sum_abs_diff": float(a.sum_abs),
+            "top1_agree_rows": int(a.top1_agree),
+        }
+        if nodeSums:
+            out["node_sum"] = ns
+        return out

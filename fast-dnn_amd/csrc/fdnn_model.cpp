@@ -1,6 +1,8 @@
 // fdnn_model.cpp -- .bin loader, quantizer and weight-blob packer (host only).
 #include "fdnn_model.hpp"
 
+#include "fdnn_float.hpp"
+
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -279,11 +281,17 @@ int pack(const std::vector<RawLayer> &layers, const std::vector<float> &shift, c
 
 }  // namespace
 
-int load_host_model(const std::string &path, float cutoff, HostModel *out, std::string *msg) {
-  if (!(cutoff > 0.0f)) {  // QuantizedDnn.java:55-57
-    *msg = "weight cut-off must be positive";
-    return FDNN_E_ARG;
-  }
+namespace {
+
+// What both loaders read from a .bin: the layers as fp32 (layer 0 padded to x4 input columns), shift and scale.
+struct RawModel {
+  std::vector<RawLayer> layers;
+  std::vector<float> shift, scale;
+  int in_dim_file = 0;
+};
+
+// The .bin reader and every rejection of a net this library does not run: one copy for the quantized and the float loader.
+int read_raw_model(const std::string &path, RawModel *rm, std::string *msg) {
   FILE *fp = std::fopen(path.c_str(), "rb");
   if (!fp) {
     *msg = "cannot open model file " + path;
@@ -306,7 +314,8 @@ int load_host_model(const std::string &path, float cutoff, HostModel *out, std::
     *msg = "model has " + std::to_string(n_affine) + " affine layers; need 4.." + std::to_string(kMaxQLayers + 1);
     return FDNN_E_FORMAT;
   }
-  std::vector<RawLayer> layers(static_cast<size_t>(n_affine));
+  std::vector<RawLayer> &layers = rm->layers;
+  layers.assign(static_cast<size_t>(n_affine), RawLayer());
   int in_dim_file = 0;
   for (int j = 0; j < n_affine; ++j) {
     RawLayer &L = layers[size_t(j)];
@@ -324,9 +333,11 @@ int load_host_model(const std::string &path, float cutoff, HostModel *out, std::
     L.bias.resize(size_t(L.out_dim));
     c.f32(L.bias.data(), size_t(L.out_dim));
   }
-  std::vector<float> shift(size_t(layers[0].in_pad), 0.0f), scale(size_t(layers[0].in_pad), 0.0f);
-  c.f32(shift.data(), size_t(in_dim_file));  // zero padded, float_dnn.cc:60-66
-  c.f32(scale.data(), size_t(in_dim_file));
+  rm->in_dim_file = in_dim_file;
+  rm->shift.assign(size_t(layers[0].in_pad), 0.0f);
+  rm->scale.assign(size_t(layers[0].in_pad), 0.0f);
+  c.f32(rm->shift.data(), size_t(in_dim_file));  // zero padded, float_dnn.cc:60-66
+  c.f32(rm->scale.data(), size_t(in_dim_file));
   if (!c.ok) {
     *msg = "model file truncated: " + path;
     return FDNN_E_FORMAT;
@@ -347,7 +358,29 @@ int load_host_model(const std::string &path, float cutoff, HostModel *out, std::
     *msg = "hidden width above 32768 overflows the int32 accumulator bound";
     return FDNN_E_FORMAT;
   }
-  return pack(layers, shift, scale, in_dim_file, cutoff, out, msg);
+  return FDNN_OK;
+}
+
+}  // namespace
+
+int load_host_model(const std::string &path, float cutoff, HostModel *out, std::string *msg) {
+  if (!(cutoff > 0.0f)) {  // QuantizedDnn.java:55-57
+    *msg = "weight cut-off must be positive";
+    return FDNN_E_ARG;
+  }
+  RawModel rm;
+  if (int rc = read_raw_model(path, &rm, msg)) return rc;
+  return pack(rm.layers, rm.shift, rm.scale, rm.in_dim_file, cutoff, out, msg);
+}
+
+// The fp32 net of the same file (fdnn_float.hpp): every file load_host_model takes, and no others.
+int load_float_host_model(const std::string &path, fl::FloatHostModel *out, std::string *msg) {
+  RawModel rm;
+  if (int rc = read_raw_model(path, &rm, msg)) return rc;
+  std::vector<fl::DenseLayer> dense;
+  for (const RawLayer &L : rm.layers) dense.push_back(fl::DenseLayer{L.out_dim, L.in_pad, L.w.data(), L.bias.data()});
+  fl::pack(dense, rm.shift.data(), rm.scale.data(), rm.in_dim_file, out);
+  return FDNN_OK;
 }
 
 int adopt_blob(std::vector<uint8_t> &&bytes, HostModel *out, std::string *msg) {

@@ -643,6 +643,77 @@ FDNN_API int fdnn_host_blob_check(const void *bytes, size_t size, int *input_dim
 FDNN_API int fdnn_host_sigmoid_lut(uint8_t *out1280); /* QuantizedSigmoid table, dnn.cc:100-115 */
 FDNN_API int fdnn_host_quantize(const float *w, int rows, int cols, float cutoff, int8_t *out, float *multiplier);
 
+/* ------------------------------------------------------------------ the unquantized net and the quantization report
+ * The reference's one notion of accuracy is the distance between QuantizedDnn and the fp32 net it was made from
+ * (FuncTest.diff, test/java/suskun/nn/FuncTest.java:59-74, against FeedForwardNetwork.calculate,
+ * FeedForwardNetwork.java:133-148).  Both halves run on the device here: fp32 GEMMs on the f32-input MFMA
+ * (fdnn_float.hip) and a report that accumulates over any number of calls.
+ *
+ * A layer's sum is, bit for bit, s = 0; for k ascending: s = fmaf(x[k], w[k], s); z = s + bias -- so a row's bytes depend
+ * on the row alone (not on n, its position, or the chunk size), and fdnn_debug_float_layer_ref restates it on the host.
+ * This is the fused chain, not Java's mul-then-add loop (:360-375): the two differ at the ulp level (DESIGN).
+ * Sigmoid (:398-402) and soft-max (:404-414, no max subtraction) are fp32: DESIGN gives their bounds against float64.
+ *
+ * fdnn_float_model_load / _load_on <- FeedForwardNetwork.loadFromBinary, FeedForwardNetwork.java:209-224: the same .bin, the
+ *   same rejections (FDNN_E_FORMAT) as fdnn_model_load; FDNN_E_DEVICE without a HIP device (no CPU path).
+ * fdnn_float_model_input_dim      the width of a caller's row: the file's, padded to x4 -- fdnn_model_input_dim's value.
+ * fdnn_float_model_layer_count    affine layers (:133-148 runs them all); fdnn_float_model_layer_dim(j) the nodes of layer j.
+ * fdnn_float_calculate            <- calculate(float[][]), :133-148.  Host buffers x [n][dim] -> out [n][output_dim],
+ *   host-synchronous; n == 0 is a no-op.  FDNN_E_ARG for a wrong dim or a null buffer.
+ * fdnn_float_calculate_device     device buffers, enqueued on `stream`, not synchronised.
+ * Calls on one float model are thread-safe: they are serialised on a mutex inside the model and, across streams, ordered
+ * behind each other on the device (the model owns one set of activation buffers: this is a yardstick, not a serving path).
+ * A large n goes through in chunks of fdnn_debug_float_set_chunk frames (0 = default, 4096); results never depend on it.
+ *
+ * fdnn_debug_float_layer          ONE layer j on a caller's host rows in [n][K_j] (K_0 = input_dim): lin [n][rows_j] receives
+ *   z, act [n][rows_j] the sigmoid (the soft-max probabilities for the last layer); either may be NULL.  j == -1 is the input
+ *   step (:121-128) on in [n][input_dim]: lin = x + shift, act = (x + shift) * scale.  fdnn_float_calculate is exactly the
+ *   composition of these calls.  FDNN_E_ARG for a j outside -1 .. layer_count - 1.
+ * fdnn_debug_float_layer_us       measurement only (tools/float_sweep.py), apart from the call the tests use: uploads in
+ *   [n][K_j] once, runs layer j (0 .. layer_count - 1) once to warm up and then `reps` times back to back between two
+ *   events; *us = device microseconds per run (the output layer's with its scale pass).  Copies nothing back.
+ * fdnn_debug_float_layer_ref      the host restatement of a layer's sums, no device: w [rows][K] dense, in [n][K], lin [n][rows].
+ * fdnn_debug_float_input_ref      the host restatement of the input step, no device; lin or act may be NULL.
+ * fdnn_debug_float_launches       process-wide launch counts since load, returns 8: fgemm sigmoid, exp, sigmoid + tap,
+ *   exp + tap, input step, report rows, report nodes, report fold.  (Not in the launch recorder's table: see fdnn_note.hpp.) */
+typedef struct fdnn_float_model fdnn_float_model;
+FDNN_API int fdnn_float_model_load(const char *path, fdnn_float_model **out);
+FDNN_API int fdnn_float_model_load_on(const char *path, int device, fdnn_float_model **out);
+FDNN_API void fdnn_float_model_free(fdnn_float_model *fm);
+FDNN_API int fdnn_float_model_input_dim(const fdnn_float_model *fm);
+FDNN_API int fdnn_float_model_output_dim(const fdnn_float_model *fm);
+FDNN_API int fdnn_float_model_layer_count(const fdnn_float_model *fm);
+FDNN_API int fdnn_float_model_layer_dim(const fdnn_float_model *fm, int index);
+FDNN_API int fdnn_float_model_device(const fdnn_float_model *fm);
+FDNN_API int fdnn_float_calculate(fdnn_float_model *fm, const float *x, int n, int dim, float *out);
+FDNN_API int fdnn_float_calculate_device(fdnn_float_model *fm, const float *d_x, int n, float *d_out, void *stream);
+FDNN_API int fdnn_debug_float_layer(fdnn_float_model *fm, int j, const float *in, int n, float *lin, float *act);
+FDNN_API int fdnn_debug_float_layer_us(fdnn_float_model *fm, int j, const float *in, int n, int reps, double *us);
+FDNN_API int fdnn_debug_float_layer_ref(const float *w, const float *bias, int rows, int K, const float *in, int n, float *lin);
+FDNN_API int fdnn_debug_float_input_ref(const float *shift, const float *scale, int dim, const float *x, int n, float *lin, float *act);
+FDNN_API int fdnn_debug_float_set_chunk(fdnn_float_model *fm, int rows);
+FDNN_API int fdnn_debug_float_launches(unsigned long long *out, int cap);
+
+/* The report (FuncTest.diff, FuncTest.java:59-74: per output node, |quantized - float| summed over the frames; the harness
+ * prints the nodes above 0.1).  Two [n][output_dim] fp32 matrices per call, `ref` and `q`; the accumulators live on the
+ * device (doubles and 64-bit counts, added to in a fixed order: the figures are a function of the sequence of calls).
+ * A row with a NaN in either matrix counts in nan_rows and is left out of every other figure.
+ * fdnn_report_add_device  device buffers, enqueued on `stream`;  fdnn_report_add  host rows, host-synchronous.
+ * fdnn_report_read        synchronises the device; nodes_over = nodes whose sum exceeds `threshold`; node_sum [output_dim]
+ *   receives the per-node sums unless NULL.  top1_agree counts rows whose arg max (first index on ties) is the same in both.
+ * Calls on one report are serialised on a mutex inside it. */
+typedef struct fdnn_report fdnn_report;
+typedef struct {
+  uint64_t frames, nan_rows, top1_agree, nodes_over;
+  double sum_abs, max_abs, max_node_sum;
+} fdnn_accuracy;
+FDNN_API int fdnn_report_create(int device, int output_dim, fdnn_report **out);
+FDNN_API void fdnn_report_free(fdnn_report *r);
+FDNN_API int fdnn_report_reset(fdnn_report *r);
+FDNN_API int fdnn_report_add_device(fdnn_report *r, const float *d_ref, const float *d_q, int n, void *stream);
+FDNN_API int fdnn_report_add(fdnn_report *r, const float *ref, const float *q, int n);
+FDNN_API int fdnn_report_read(fdnn_report *r, double threshold, fdnn_accuracy *acc, double *node_sum);
+
 #ifdef __cplusplus
 }
 #endif
