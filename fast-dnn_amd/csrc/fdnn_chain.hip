@@ -23,8 +23,9 @@
 // one lane, a barrier, and reads the rows with sc0 sc1 LDS-DMA loads (past its CU's vector L1).  The weight stages of
 // the next task do not depend on anybody: they are requested BEFORE the wait.
 //
-// The tile arithmetic (k-loop, pair-saturation corrections, epilogue) is the per-layer kernel's, operation for
-// operation (fdnn_gemm.hip): the bytes are identical by construction and by test.
+// The tile arithmetic (k-loop, epilogue) is the per-layer kernel's, operation for operation (fdnn_gemm.hip), and the
+// pair-saturation corrections are the one definition both share (fdnn_pair.hpp): the bytes are identical by construction
+// and by test.
 #include <atomic>
 #include <climits>
 #include <cstdlib>
@@ -180,10 +181,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
     // ================================================================ phase A: set-up, early loads, the wait
     v16i acc[2][NF];
     __amdgpu_buffer_rsrc_t rsrc_w, rsrc_a;
-    int fix_e = 0, fix_end = 0, fix_k_next = INT_MAX, fix_node0 = 0;
-    typedef const __attribute__((address_space(4))) uint64_t *FixPtr;
-    FixPtr ent_c = nullptr;
-    uint64_t fix_raw = 0, fix_raw_nxt = 0;  // {u16 k, s8 w0, s8 w1, s32 node}
+    FixCursor fx = {0, 0, INT_MAX, nullptr, 0, 0};
+    int fix_node0 = 0;
     int ldw_s, lda_s, KT;
     {
       const Dec d = decode(kp, task);
@@ -216,20 +215,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
         const __amdgpu_buffer_rsrc_t rsrc_bias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(L->bias + m0), 0, G_BM * 4, 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_bias, FDNN_LDS_PTR(aux + 3072), 16, lane * 16, 0, 0, 0);
       }
-      // pmaddubsw pair saturation (dnn.cc:337-340): the entry walk of fdnn_gemm.hip
-      ent_c = (FixPtr)(uintptr_t)L->fix_ent;
+      // pmaddubsw pair saturation (dnn.cc:337-340): the entry walk of fdnn_pair.hpp
+      fx.ent = fix_entries(L->fix_ent);
       fix_node0 = m0 + 64 * wm;
-      if (!NOFIX && ent_c) {
-        const int32_t *fix_grp = L->fix_grp;
-        const int grp = (m0 >> 6) + wm;
-        fix_e = __builtin_amdgcn_readfirstlane(fix_grp[grp]);
-        fix_end = __builtin_amdgcn_readfirstlane(fix_grp[grp + 1]);
-        if (fix_e < fix_end) {
-          fix_raw = ent_c[fix_e];
-          if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
-          fix_k_next = static_cast<int>(fix_raw & 0xffff);
-        }
-      }
+      if (!NOFIX && fx.ent) fx = fix_open(fx, L->fix_grp, (m0 >> 6) + wm);
     }
     // activation rows: sc0 sc1 (aux 17) -- they were written by other workgroups of this launch; weights: default policy
     auto stage_load = [&](int kt, int buf, int i) {
@@ -335,48 +324,34 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
       if (nb >= STAGES) nb -= STAGES;
       const char *wt = smem + buf * Cfg::STAGE;
       const char *at = wt + Cfg::W_BYTES;
-      while (!NOFIX && fix_k_next < (kt + 1) * BK) {  // rare: a risky pair lives in this k-step (screen, then the exact correction)
-        const int node = static_cast<int>(fix_raw >> 32) - fix_node0;         // 0..63
-        const int kl = static_cast<int>(fix_raw & 0xffff) - kt * BK;          // even, 0..BK-2
-        const int w0 = static_cast<int8_t>(fix_raw >> 16), w1 = static_cast<int8_t>(fix_raw >> 24);
+      while (!NOFIX && fx.k_next < (kt + 1) * BK) {  // rare: a risky pair lives in this k-step (screen, then the exact correction)
+        const PairEntry en = decode_entry(fx.raw);
+        const int kl = en.k - kt * BK;  // even, 0..BK-2
         {
-          const int wpk = (w0 & 0xff) | ((w1 & 0xff) << 8);
-          const int pbase = 128 * (w0 + w1) + 32768;
+          const PairScreen sc = pair_screen(en.w0, en.w1);
           bool fire = false;
 #pragma unroll
           for (int j = 0; j < (NF + 1) / 2; ++j) {
-            const int row = arow0 + 64 * j + lane;
-            const int v = *reinterpret_cast<const uint16_t *>(at + row * BK + (((kl >> 4) ^ swz<BK>(row)) << 4) + (kl & 15));
-            const int ps = __builtin_amdgcn_sdot4(v, wpk, pbase, false);  // p + 32768
+            const int v = static_cast<int>(pair_at<BK>(at, arow0 + 64 * j + lane, kl));
             const bool live = 64 * j + 64 <= 32 * NF || lane < 32 * NF - 64 * j;
-            fire |= live && static_cast<unsigned>(ps) > 65535u;
+            fire |= live && pair_fires(v, sc);
           }
           if (__ballot(fire) == 0ull) {
-            ++fix_e;
-            fix_raw = fix_raw_nxt;
-            fix_k_next = fix_e < fix_end ? static_cast<int>(fix_raw & 0xffff) : INT_MAX;
-            if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
+            fx = fix_advance(fx);
             continue;
           }
         }
-        const int rr = node & 31;
-        const int idx = (node >> 5) * 16 + (rr & 3) + 4 * (rr >> 3);  // mi*16 + reg
-        const bool mine = (lane >> 5) == ((rr >> 2) & 1);
+        const AccSlot slot = acc_slot(en.node - fix_node0);  // node 0..63 of this wave
+        const int idx = slot.idx;
+        const bool mine = (lane >> 5) == slot.half;
         int c[NF];
         uint32_t pair[NF];
 #pragma unroll
-        for (int ni = 0; ni < NF; ++ni) {
-          const int row = arow0 + 32 * ni + frow;
-          pair[ni] = *reinterpret_cast<const uint16_t *>(at + row * BK + (((kl >> 4) ^ swz<BK>(row)) << 4) + (kl & 15));
-        }
+        for (int ni = 0; ni < NF; ++ni) pair[ni] = pair_at<BK>(at, arow0 + 32 * ni + frow, kl);
 #pragma unroll
         for (int ni = 0; ni < NF; ++ni) asm volatile("" : "+v"(pair[ni]));
 #pragma unroll
-        for (int ni = 0; ni < NF; ++ni) {
-          const int a0 = static_cast<int>((pair[ni] & 0xff) ^ 0x80), a1 = static_cast<int>((pair[ni] >> 8) ^ 0x80);  // back to u8
-          const int prod = a0 * w0 + a1 * w1;
-          c[ni] = mine ? max(-32768, min(32767, prod)) - prod : 0;
-        }
+        for (int ni = 0; ni < NF; ++ni) c[ni] = mine ? pair_excess(pair[ni], en.w0, en.w1) : 0;
         int nz = 0;
 #pragma unroll
         for (int ni = 0; ni < NF; ++ni) nz |= c[ni];
@@ -389,10 +364,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
             }
           }
         }
-        ++fix_e;
-        fix_raw = fix_raw_nxt;
-        fix_k_next = fix_e < fix_end ? static_cast<int>(fix_raw & 0xffff) : INT_MAX;
-        if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
+        fx = fix_advance(fx);
       }
       if (!ROT) load_frags(wt, at, 0, 0);
 #pragma unroll

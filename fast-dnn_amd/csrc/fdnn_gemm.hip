@@ -231,32 +231,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
   const int frow = lane & 31, fch = lane >> 5;
   const int arow0 = wn * 32 * NF;  // this wave's first frame row inside the tile
 
-  // pmaddubsw saturation (dnn.cc:337-340).  The MFMA sum is exact; the reference
-  // saturates every ADJACENT pair a[2j]*w[2j] + a[2j+1]*w[2j+1] to int16.  Only the
-  // few (node, pair) entries listed at load time can saturate at all.  Those of this
-  // wave's 64 nodes are sorted by k; when the k-step holding an entry's columns is in
-  // LDS, the pair is recomputed from the staged activation bytes and sat16(p) - p is
-  // added to the accumulator that holds (node, frame).  The entry walk and the register
-  // select are wave-uniform; a layer without risky pairs has fix_k_next = INT_MAX.
-  //
-  int fix_e = 0, fix_end = 0, fix_k_next = INT_MAX;
-  // Entries are walked with SCALAR loads (constant address space: s_load_dwordx2 into SGPRs, two
-  // entries ahead): no LDS round trip and no v_readfirstlane per entry, and the scalar cache
-  // path does not queue behind the LDS-DMA loads as a vector load issued in the loop would
-  // (-4.5 % on a Gaussian-weight layer against an LDS copy of the list).
-  typedef const __attribute__((address_space(4))) uint64_t *FixPtr;
-  const FixPtr ent_c = (FixPtr)(uintptr_t)p.fix_ent;
-  uint64_t fix_raw = 0, fix_raw_nxt = 0;  // {u16 k, s8 w0, s8 w1, s32 node}
-  if (!NOFIX && p.fix_ent) {
-    const int grp = (m0 >> 6) + wm;
-    fix_e = __builtin_amdgcn_readfirstlane(p.fix_grp[grp]);
-    fix_end = __builtin_amdgcn_readfirstlane(p.fix_grp[grp + 1]);
-    if (fix_e < fix_end) {
-      fix_raw = ent_c[fix_e];
-      if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
-      fix_k_next = static_cast<int>(fix_raw & 0xffff);
-    }
-  }
+  // pmaddubsw saturation (dnn.cc:337-340): the walk over this wave's 64 nodes' entries (fdnn_pair.hpp)
+  FixCursor fx = {0, 0, INT_MAX, fix_entries(p.fix_ent), 0, 0};
+  if (!NOFIX && p.fix_ent) fx = fix_open(fx, p.fix_grp, (m0 >> 6) + wm);
   FDNN_TS(1);
   // Code placement: the k-loop is sensitive to where it lands in the instruction
   // stream (measured: the same instructions shifted by one dword ran 0.064 vs 0.049 ms
@@ -334,57 +311,37 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
     const char *at = wt + Cfg::W_BYTES;
 #if FDNN_GEMM_DEBUG & 64
     const long long tf0 = __builtin_readcyclecounter();
-    const int fe0 = fix_e;
+    const int fe0 = fx.e;
 #endif
-    while (!NOFIX && fix_k_next < (kt + 1) * BK) {  // rare: a risky pair lives in this k-step
-      const int node = static_cast<int>(fix_raw >> 32) - (m0 + 64 * wm);  // 0..63
-      const int kl = static_cast<int>(fix_raw & 0xffff) - kt * BK;          // even, 0..BK-2
-      const int w0 = static_cast<int8_t>(fix_raw >> 16), w1 = static_cast<int8_t>(fix_raw >> 24);
-      // Screen first.  A pair that CAN saturate almost never does (both activations must be
-      // close to 255: 0.2 % of the (pair, frame) combinations of the Gaussian bench net, under
-      // 1 % of the pairs for any of a wave's 160 frames), so the common case only has to prove
-      // "no frame of this wave saturates": one frame per lane (not per half-wave as the
-      // accumulator layout has it), the pair as one 16-bit LDS read, the pair product as one
-      // v_dot4c_i32_i8 on the staged s8 bytes (a = s8 + 128, so p = dot + 128*(w0+w1)), one
-      // range test.  Only when some lane fires does the wave run the exact correction below.
-      {
-        const int wpk = (w0 & 0xff) | ((w1 & 0xff) << 8);
-        const int pbase = 128 * (w0 + w1) + 32768;
+    while (!NOFIX && fx.k_next < (kt + 1) * BK) {  // rare: a risky pair lives in this k-step
+      const PairEntry en = decode_entry(fx.raw);
+      const int kl = en.k - kt * BK;  // even, 0..BK-2
+      {  // screen first: one frame per lane (fdnn_pair.hpp)
+        const PairScreen sc = pair_screen(en.w0, en.w1);
         bool fire = false;
 #pragma unroll
         for (int j = 0; j < (NF + 1) / 2; ++j) {
-          const int row = arow0 + 64 * j + lane;
-          const int v = *reinterpret_cast<const uint16_t *>(at + row * BK + (((kl >> 4) ^ swz<BK>(row)) << 4) + (kl & 15));
-          const int ps = __builtin_amdgcn_sdot4(v, wpk, pbase, false);  // p + 32768
+          const int v = static_cast<int>(pair_at<BK>(at, arow0 + 64 * j + lane, kl));
           const bool live = 64 * j + 64 <= 32 * NF || lane < 32 * NF - 64 * j;
-          fire |= live && static_cast<unsigned>(ps) > 65535u;
+          fire |= live && pair_fires(v, sc);
         }
         if (__ballot(fire) == 0ull) {
-          ++fix_e;
-          fix_raw = fix_raw_nxt;
-          fix_k_next = fix_e < fix_end ? static_cast<int>(fix_raw & 0xffff) : INT_MAX;
-          if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
+          fx = fix_advance(fx);
           continue;
         }
       }
-      const int rr = node & 31;
-      const int idx = (node >> 5) * 16 + (rr & 3) + 4 * (rr >> 3);  // mi*16 + reg
-      const bool mine = (lane >> 5) == ((rr >> 2) & 1);
+      const AccSlot slot = acc_slot(en.node - (m0 + 64 * wm));  // node 0..63 of this wave
+      const int idx = slot.idx;
+      const bool mine = (lane >> 5) == slot.half;
       int c[NF];
       uint32_t pair[NF];
 #pragma unroll
-      for (int ni = 0; ni < NF; ++ni) {  // all lanes read (no divergent branch): the NF gathers go out together
-        const int row = arow0 + 32 * ni + frow;
-        pair[ni] = *reinterpret_cast<const uint16_t *>(at + row * BK + (((kl >> 4) ^ swz<BK>(row)) << 4) + (kl & 15));
-      }
+      for (int ni = 0; ni < NF; ++ni)  // all lanes read (no divergent branch): the NF gathers go out together
+        pair[ni] = pair_at<BK>(at, arow0 + 32 * ni + frow, kl);
 #pragma unroll
       for (int ni = 0; ni < NF; ++ni) asm volatile("" : "+v"(pair[ni]));
 #pragma unroll
-      for (int ni = 0; ni < NF; ++ni) {
-        const int a0 = static_cast<int>((pair[ni] & 0xff) ^ 0x80), a1 = static_cast<int>((pair[ni] >> 8) ^ 0x80);  // back to u8
-        const int prod = a0 * w0 + a1 * w1;
-        c[ni] = mine ? max(-32768, min(32767, prod)) - prod : 0;
-      }
+      for (int ni = 0; ni < NF; ++ni) c[ni] = mine ? pair_excess(pair[ni], en.w0, en.w1) : 0;
       // saturation actually firing is rare (both activations of the pair must be near
       // 255): skip the register select when no lane has a non-zero correction
       int nz = 0;
@@ -399,15 +356,12 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
           }
         }
       }
-      ++fix_e;
-      fix_raw = fix_raw_nxt;
-      fix_k_next = fix_e < fix_end ? static_cast<int>(fix_raw & 0xffff) : INT_MAX;
-      if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
+      fx = fix_advance(fx);
     }
 #if FDNN_GEMM_DEBUG & 64
-    if (fix_e != fe0) {
+    if (fx.e != fe0) {
       ts_fix += __builtin_readcyclecounter() - tf0;
-      n_fix_done += fix_e - fe0;
+      n_fix_done += fx.e - fe0;
     }
 #endif
     // Fragments are double buffered in registers: the ds_read_b128s of sub-step

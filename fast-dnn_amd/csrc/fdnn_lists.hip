@@ -22,6 +22,7 @@
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
 #include "fdnn_launch.hpp"
+#include "fdnn_pair.hpp"
 
 namespace fdnn {
 namespace {
@@ -96,13 +97,9 @@ __global__ __launch_bounds__(kLsThreads) void lists_score_kernel(ListsParams p) 
         // activation pair comes from memory again (a line this group has just read)
         const int fe = p.fix_off[node + 1];
         for (int f = p.fix_off[node] + l16; f < fe; f += kLsLanes) {
-          const uint32_t raw = p.fix_pairs[f];
-          const int k = static_cast<int>(raw & 0xffffu);
-          const int w0 = static_cast<int8_t>(raw >> 16), w1 = static_cast<int8_t>(raw >> 24);
-          const uint32_t pair = *reinterpret_cast<const uint16_t *>(arow + k);  // k is even
-          const int a0 = static_cast<int>((pair & 0xff) ^ 0x80), a1 = static_cast<int>((pair >> 8) ^ 0x80);  // back to u8
-          const int prod = a0 * w0 + a1 * w1;
-          part += max(-32768, min(32767, prod)) - prod;
+          const PairEntry en = decode_pair(p.fix_pairs[f]);
+          const uint32_t pair = *reinterpret_cast<const uint16_t *>(arow + en.k);  // k is even
+          part += pair_excess(pair, en.w0, en.w1);
         }
       }
     }

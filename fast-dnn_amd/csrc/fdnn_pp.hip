@@ -139,10 +139,7 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
     asm volatile("" : "+v"(ln));
     if (grp == cg) {
       // ============================================================== COMPUTE role
-      int fix_e = 0, fix_end = 0, fix_k_next = INT_MAX;
-      typedef const __attribute__((address_space(4))) uint64_t *FixPtr;
-      const FixPtr ent_c = (FixPtr)(uintptr_t)p.fix_ent;
-      uint64_t fix_raw = 0, fix_raw_nxt = 0;
+      FixCursor fx = {0, 0, INT_MAX, fix_entries(p.fix_ent), 0, 0};
       const int fix_node0 = c_mt * kBM + 64 * wm;
       // my share of the stages I requested in my last support ticks (the second weight stage) has landed.  The BUILTIN, not
       // inline asm: the compiler's wait-count pass must see this wait -- otherwise it protects the first ring read of the
@@ -169,16 +166,7 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
               acc[a][b][g * 4 + 3] = ws4.w;
             }
           }
-        if (!NOFIX && p.fix_ent) {
-          const int gi = (c_mt * kBM >> 6) + wm;
-          fix_e = __builtin_amdgcn_readfirstlane(p.fix_grp[gi]);
-          fix_end = __builtin_amdgcn_readfirstlane(p.fix_grp[gi + 1]);
-          if (fix_e < fix_end) {
-            fix_raw = ent_c[fix_e];
-            if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
-            fix_k_next = static_cast<int>(fix_raw & 0xffff);
-          }
-        }
+        if (!NOFIX && p.fix_ent) fx = fix_open(fx, p.fix_grp, (c_mt * kBM >> 6) + wm);
       }
       // where the partner's finished blocks go (store duty): 16-byte chunk c of a 32 x 256-byte block; second pass c + 64.
       // Buffer stores through the compiler (write-through: sc0 sc1), not inline asm: with the store hidden in an asm block the
@@ -225,49 +213,35 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
         const int T = gt0 + kt;
         if (cvalid) {
           const char *at = ringA[T & 1];
-          while (!NOFIX && fix_k_next < (kt + 1) * kBK) {  // rare: a risky pair lives in this k-step (fdnn_gemm.hip's walk)
-            const int node = static_cast<int>(fix_raw >> 32) - fix_node0;
-            const int kl = static_cast<int>(fix_raw & 0xffff) - kt * kBK;
-            const int w0 = static_cast<int8_t>(fix_raw >> 16), w1 = static_cast<int8_t>(fix_raw >> 24);
+          while (!NOFIX && fx.k_next < (kt + 1) * kBK) {  // rare: a risky pair lives in this k-step (fdnn_pair.hpp's walk)
+            const PairEntry en = decode_entry(fx.raw);
+            const int kl = en.k - kt * kBK;
             {
-              const int wpk = (w0 & 0xff) | ((w1 & 0xff) << 8);
-              const int pbase = 128 * (w0 + w1) + 32768;
+              const PairScreen sc = pair_screen(en.w0, en.w1);
               bool fire = false;
 #pragma unroll
               for (int j = 0; j < (kNF + 1) / 2; ++j) {
                 const int row = 64 * j + lane;
                 const bool live = row < kHT;
-                const int rr_ = live ? row : 0;
-                const int v = *reinterpret_cast<const uint16_t *>(at + rr_ * kBK + (((kl >> 4) ^ swz<kBK>(rr_)) << 4) + (kl & 15));
-                const int ps = __builtin_amdgcn_sdot4(v, wpk, pbase, false);  // p + 32768
-                fire |= live && static_cast<unsigned>(ps) > 65535u;
+                const int v = static_cast<int>(pair_at<kBK>(at, live ? row : 0, kl));
+                fire |= live && pair_fires(v, sc);
               }
               if (__ballot(fire) == 0ull) {
-                ++fix_e;
-                fix_raw = fix_raw_nxt;
-                fix_k_next = fix_e < fix_end ? static_cast<int>(fix_raw & 0xffff) : INT_MAX;
-                if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
+                fx = fix_advance(fx);
                 continue;
               }
             }
-            const int rr = node & 31;
-            const int idx = (node >> 5) * 16 + (rr & 3) + 4 * (rr >> 3);  // mi * 16 + reg
-            const bool mine = (lane >> 5) == ((rr >> 2) & 1);
+            const AccSlot slot = acc_slot(en.node - fix_node0);  // node 0..63 of this wave
+            const int idx = slot.idx;
+            const bool mine = (lane >> 5) == slot.half;
             int c[kNF];
             uint32_t pr[kNF];
 #pragma unroll
-            for (int ni = 0; ni < kNF; ++ni) {
-              const int row = 32 * ni + frow;
-              pr[ni] = *reinterpret_cast<const uint16_t *>(at + row * kBK + (((kl >> 4) ^ swz<kBK>(row)) << 4) + (kl & 15));
-            }
+            for (int ni = 0; ni < kNF; ++ni) pr[ni] = pair_at<kBK>(at, 32 * ni + frow, kl);
 #pragma unroll
             for (int ni = 0; ni < kNF; ++ni) asm volatile("" : "+v"(pr[ni]));
 #pragma unroll
-            for (int ni = 0; ni < kNF; ++ni) {
-              const int a0 = static_cast<int>((pr[ni] & 0xff) ^ 0x80), a1 = static_cast<int>((pr[ni] >> 8) ^ 0x80);  // back to u8
-              const int prod = a0 * w0 + a1 * w1;
-              c[ni] = mine ? max(-32768, min(32767, prod)) - prod : 0;
-            }
+            for (int ni = 0; ni < kNF; ++ni) c[ni] = mine ? pair_excess(pr[ni], en.w0, en.w1) : 0;
             int nz = 0;
 #pragma unroll
             for (int ni = 0; ni < kNF; ++ni) nz |= c[ni];
@@ -280,10 +254,7 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
                 }
               }
             }
-            ++fix_e;
-            fix_raw = fix_raw_nxt;
-            fix_k_next = fix_e < fix_end ? static_cast<int>(fix_raw & 0xffff) : INT_MAX;
-            if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
+            fx = fix_advance(fx);
           }
 #pragma unroll
           for (int kk = 0; kk < 3; ++kk) {

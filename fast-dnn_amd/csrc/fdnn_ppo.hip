@@ -190,7 +190,7 @@ namespace {
     default: break;
   }
 }
-// element i of the five frame blocks += c[.] (the deferred difference of a saturating pair: fdnn_gemm.hip's walk)
+// element i of the five frame blocks += c[.] (the deferred difference of a saturating pair: fdnn_pair.hpp's walk)
 [[maybe_unused]] __device__ __forceinline__ void ppo_add(int i, const int (&c)[5]) {
   int t0, t1, t2, t3, t4;
   switch (i) {
@@ -321,10 +321,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(96))) void q
     if (grp == cg) {
       // ============================================================== COMPUTE role
       const int frow = ln & 31, fch = ln >> 5;
-      int fix_e = 0, fix_end = 0, fix_k_next = INT_MAX;
-      typedef const __attribute__((address_space(4))) uint64_t *FixPtr;
-      const FixPtr ent_c = (FixPtr)(uintptr_t)p.fix_ent;
-      uint64_t fix_raw = 0, fix_raw_nxt = 0;
+      FixCursor fx = {0, 0, INT_MAX, fix_entries(p.fix_ent), 0, 0};
       const int fix_node0 = my_mt * kBM + 64 * wm;
       __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): my share of the stages I requested in my last support ticks has landed (builtin: fdnn_pp.hip)
       asm volatile("" ::: "memory");
@@ -334,16 +331,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(96))) void q
 #pragma unroll
         for (int it = 0; it < 8 * kNF; ++it) ppo_init4(it, wa);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (!NOFIX && p.fix_ent) {
-          const int gi = (my_mt * kBM >> 6) + wm;
-          fix_e = __builtin_amdgcn_readfirstlane(p.fix_grp[gi]);
-          fix_end = __builtin_amdgcn_readfirstlane(p.fix_grp[gi + 1]);
-          if (fix_e < fix_end) {
-            fix_raw = ent_c[fix_e];
-            if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
-            fix_k_next = static_cast<int>(fix_raw & 0xffff);
-          }
-        }
+        if (!NOFIX && p.fix_ent) fx = fix_open(fx, p.fix_grp, (my_mt * kBM >> 6) + wm);
       }
 
       // ---- the exchange of the partner's half (e_half), one step per slot (a slot = the instructions behind a tick's barrier,
@@ -467,50 +455,34 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(96))) void q
         const int T = gt0 + kt;
         if (cvalid) {
           const char *at = ringA[T & 1];
-          // The saturating-pair walk (fdnn_gemm.hip's): for every listed pair of this k-step a screen -- three 16-bit LDS reads,
+          // The saturating-pair walk (fdnn_pair.hpp's): for every listed pair of this k-step a screen -- three 16-bit LDS reads,
           // a dot product, a ballot -- and, where a frame fires, the exact correction.  A screen is a latency chain that two
           // waves per SIMD hide from each other and a lone compute wave cannot: the FIRST due entry's reads are issued in
           // front of sub-step 0 and looked at behind its ten MFMAs (an int32 correction may come at any point of the phase).
           auto screen_read = [&](int j) {
-            const int kl = static_cast<int>(fix_raw & 0xffff) - kt * kBK;
             const int row = 64 * j + ln;
-            const int rr_ = row < kHT ? row : 0;
-            return static_cast<int>(*reinterpret_cast<const uint16_t *>(at + rr_ * kBK + (((kl >> 4) ^ swz<kBK>(rr_)) << 4) + (kl & 15)));
+            return static_cast<int>(pair_at<kBK>(at, row < kHT ? row : 0, entry_k(fx.raw) - kt * kBK));
           };
           auto walk_one = [&](int v0, int v1, int v2) {
-            const int node = static_cast<int>(fix_raw >> 32) - fix_node0;
-            const int kl = static_cast<int>(fix_raw & 0xffff) - kt * kBK;
-            const int w0 = static_cast<int8_t>(fix_raw >> 16), w1 = static_cast<int8_t>(fix_raw >> 24);
-            const int wpk = (w0 & 0xff) | ((w1 & 0xff) << 8);
-            const int pbase = 128 * (w0 + w1) + 32768;
+            const PairEntry en = decode_entry(fx.raw);
+            const int kl = en.k - kt * kBK;
+            const PairScreen sc = pair_screen(en.w0, en.w1);
             const int vs[3] = {v0, v1, v2};
             bool fire = false;
 #pragma unroll
-            for (int j = 0; j < (kNF + 1) / 2; ++j) {
-              const int ps = __builtin_amdgcn_sdot4(vs[j], wpk, pbase, false);  // p + 32768
-              fire |= 64 * j + ln < kHT && static_cast<unsigned>(ps) > 65535u;
-            }
+            for (int j = 0; j < (kNF + 1) / 2; ++j) fire |= 64 * j + ln < kHT && pair_fires(vs[j], sc);
             if (__ballot(fire) != 0ull) {
-              const int rr = node & 31;
-              const int idx = __builtin_amdgcn_readfirstlane((node >> 5) * 16 + (rr & 3) + 4 * (rr >> 3));  // mi * 16 + reg
-              const bool mine = (ln >> 5) == ((rr >> 2) & 1);
+              const AccSlot slot = acc_slot(en.node - fix_node0);  // node 0..63 of this wave
+              const int idx = __builtin_amdgcn_readfirstlane(slot.idx);
+              const bool mine = (ln >> 5) == slot.half;
               int c[kNF];
 #pragma unroll
-              for (int ni = 0; ni < kNF; ++ni) {
-                const int row = 32 * ni + frow;
-                const uint32_t pr = *reinterpret_cast<const uint16_t *>(at + row * kBK + (((kl >> 4) ^ swz<kBK>(row)) << 4) + (kl & 15));
-                const int a0 = static_cast<int>((pr & 0xff) ^ 0x80), a1 = static_cast<int>((pr >> 8) ^ 0x80);  // back to u8
-                const int prod = a0 * w0 + a1 * w1;
-                c[ni] = mine ? max(-32768, min(32767, prod)) - prod : 0;
-              }
+              for (int ni = 0; ni < kNF; ++ni) c[ni] = mine ? pair_excess(pair_at<kBK>(at, 32 * ni + frow, kl), en.w0, en.w1) : 0;
               ppo_add(idx, c);
             }
-            ++fix_e;
-            fix_raw = fix_raw_nxt;
-            fix_k_next = fix_e < fix_end ? static_cast<int>(fix_raw & 0xffff) : INT_MAX;
-            if (fix_e + 1 < fix_end) fix_raw_nxt = ent_c[fix_e + 1];
+            fx = fix_advance(fx);
           };
-          const bool due = !NOFIX && fix_k_next < (kt + 1) * kBK;
+          const bool due = !NOFIX && fx.k_next < (kt + 1) * kBK;
           int sv0 = 0, sv1 = 0, sv2 = 0;
           if (due) {
             sv0 = screen_read(0);
@@ -520,7 +492,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(96))) void q
           __builtin_amdgcn_sched_barrier(0);
           substep(true, true, T, 1, 1, 0);
           if (due) walk_one(sv0, sv1, sv2);
-          while (!NOFIX && fix_k_next < (kt + 1) * kBK) walk_one(screen_read(0), screen_read(1), screen_read(2));  // (further entries of the k-step)
+          while (!NOFIX && fx.k_next < (kt + 1) * kBK) walk_one(screen_read(0), screen_read(1), screen_read(2));  // (further entries of the k-step)
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int kk = 1; kk < 3; ++kk) substep(true, true, T, kk + 1, (kk + 1) & 1, kk & 1);

@@ -8,6 +8,7 @@
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
 #include "fdnn_launch.hpp"
+#include "fdnn_pair.hpp"
 
 namespace fdnn {
 namespace {
@@ -244,13 +245,9 @@ __device__ __forceinline__ void set_tile(const SetParams &p, const SetView &v, c
             if (FIX) {
               // saturating pairs (rare): the reference clamps a[2j]*w[2j] + a[2j+1]*w[2j+1] to int16 (dnn.cc:337-340)
               for (int x = fb[i]; x < fe[i]; ++x) {
-                const uint32_t raw = p.fix_pairs[x];
-                const int k = static_cast<int>(raw & 0xffffu);
-                const int w0 = static_cast<int8_t>(raw >> 16), w1 = static_cast<int8_t>(raw >> 24);
-                const uint32_t pair = *reinterpret_cast<const uint16_t *>(arow + k);  // k is even
-                const int a0 = static_cast<int>((pair & 0xff) ^ 0x80), a1 = static_cast<int>((pair >> 8) ^ 0x80);  // back to u8
-                const int prod = a0 * w0 + a1 * w1;
-                a32 += max(-32768, min(32767, prod)) - prod;
+                const PairEntry en = decode_pair(p.fix_pairs[x]);
+                const uint32_t pair = *reinterpret_cast<const uint16_t *>(arow + en.k);  // k is even
+                a32 += pair_excess(pair, en.w0, en.w1);
               }
             }
             const float z = dequant<FAST>(a32, p.coef, p.rcp_coef) + bias4[i];

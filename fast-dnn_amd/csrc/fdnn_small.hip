@@ -25,12 +25,13 @@
 //     kernel, operation for operation -- so a frame's bits do not depend on the batch it was scored in
 //     (tests/test_gpu_server.py compares coalesced batches with per-utterance calls bit for bit).
 //
-// pmaddubsw saturation (dnn.cc:337-340): the same sparse exact correction as in fdnn_gemm.hip, applied by the
-// wave whose K slice holds the pair, from the staged activation bytes.
+// pmaddubsw saturation (dnn.cc:337-340): the same sparse exact correction as in fdnn_gemm.hip (fdnn_pair.hpp), applied
+// by the wave whose K slice holds the pair, from the staged activation bytes.
 #include <atomic>
 
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
+#include "fdnn_pair.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -173,8 +174,7 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
   // inside the group, so they are one contiguous run.  Its start is found from an interpolated guess (k is spread
   // evenly: a walk from the group's first entry cost the last wave ~60 dependent scalar loads), and the run's first
   // kFixPre entries are fetched into SGPRs here, under the operand loads' flight time.
-  typedef const __attribute__((address_space(4))) uint64_t *FixPtr;
-  const FixPtr ent_c = (FixPtr)(uintptr_t)p.fix_ent;  // {u16 k, s8 w0, s8 w1, s32 node}
+  const FixPtr ent_c = fix_entries(p.fix_ent);  // FixEntry words (fdnn_pair.hpp)
   constexpr int kFixPre = 8;
   int fix_b = 0, fix_end = 0;
   uint64_t fix_pre[kFixPre];
@@ -187,8 +187,8 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
     const int g_begin = grp_c[grp];
     fix_end = grp_c[grp + 1];
     int e = g_begin + static_cast<int>(static_cast<long long>(fix_end - g_begin) * k0 / p.K);
-    while (e > g_begin && static_cast<int>(ent_c[e - 1] & 0xffff) >= k0) --e;
-    while (e < fix_end && static_cast<int>(ent_c[e] & 0xffff) < k0) ++e;
+    while (e > g_begin && entry_k(ent_c[e - 1]) >= k0) --e;
+    while (e < fix_end && entry_k(ent_c[e]) < k0) ++e;
     fix_b = e;
 #pragma unroll
     for (int i = 0; i < kFixPre; ++i)
@@ -244,27 +244,23 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
       }
       // saturating pairs (rare): the reference clamps a[2j]*w[2j] + a[2j+1]*w[2j+1] to int16 (dnn.cc:337-340)
       auto fix_one = [&](uint64_t raw) {
-        const int node = static_cast<int>(raw >> 32) - m0;
+        const PairEntry en = decode_entry(raw);
+        const int node = en.node - m0;
         if (node < 0 || node >= NT) return;  // NTM == 1: the other half of the 64-node group
-        const int kl = static_cast<int>(raw & 0xffff) - k0;  // even, 0..254
-        const int w0 = static_cast<int8_t>(raw >> 16), w1 = static_cast<int8_t>(raw >> 24);
+        const int kl = en.k - k0;  // even, 0..254
         const uint32_t pair = *reinterpret_cast<const uint16_t *>(at + sm_pos(frow, kl >> 4) + (kl & 15));
-        const int a0 = static_cast<int>((pair & 0xff) ^ 0x80), a1 = static_cast<int>((pair >> 8) ^ 0x80);  // back to u8
-        const int prod = a0 * w0 + a1 * w1;
-        const int rr = node & 31;
-        const bool mine = fch == ((rr >> 2) & 1);
-        const int c = mine ? max(-32768, min(32767, prod)) - prod : 0;
+        const AccSlot slot = acc_slot(node);
+        const int c = fch == slot.half ? pair_excess(pair, en.w0, en.w1) : 0;
         if (__ballot(c != 0) != 0ull) {
-          const int idx = (node >> 5) * 16 + (rr & 3) + 4 * (rr >> 3);
 #pragma unroll
           for (int i = 0; i < 16 * NTM; ++i)
-            if (idx == i) acc[i >> 4][i & 15] += c;
+            if (slot.idx == i) acc[i >> 4][i & 15] += c;
         }
       };
       bool more = true;
 #pragma unroll
       for (int i = 0; i < kFixPre; ++i) {
-        if (more && static_cast<int>(fix_pre[i] & 0xffff) < k0 + kSmSlice)
+        if (more && entry_k(fix_pre[i]) < k0 + kSmSlice)
           fix_one(fix_pre[i]);
         else
           more = false;
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
       if (more)  // a run longer than the prefetched entries (nets with weights near +-127 everywhere)
         for (int e = fix_b + kFixPre; e < fix_end; ++e) {
           const uint64_t raw = ent_c[e];
-          if (static_cast<int>(raw & 0xffff) >= k0 + kSmSlice) break;
+          if (entry_k(raw) >= k0 + kSmSlice) break;
           fix_one(raw);
         }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -1,7 +1,10 @@
 // fdnn_tile.hpp -- the int8 GEMM tile shared by the per-layer kernel (fdnn_gemm.hip) and the chained hidden-layer
-// kernel (fdnn_chain.hip): tile geometry / LDS map, the chunk swizzle and the fragment read.
+// kernel (fdnn_chain.hip), and by the role-split kernels' rings (fdnn_pp.hip, fdnn_ppo.hip): tile geometry / LDS map, the
+// chunk swizzle, the fragment read and the 16-bit read of an activation pair.  Including it brings the pair-saturation
+// arithmetic (fdnn_pair.hpp) along: every kernel built on this tile walks the saturating pairs.
 #pragma once
 #include "fdnn_device.hpp"
+#include "fdnn_pair.hpp"
 
 namespace fdnn {
 
@@ -42,6 +45,12 @@ __device__ __forceinline__ int swz(int row) {
 template <int BK>
 __device__ __forceinline__ v4i read_frag(const char *tile, int row, int chunk) {
   return *reinterpret_cast<const v4i *>(tile + row * BK + ((chunk ^ swz<BK>(row)) << 4));
+}
+
+// the two staged s8 bytes at columns kl, kl + 1 (kl even) of a tile row: what fdnn_pair.hpp's pair_fires / pair_excess take
+template <int BK>
+__device__ __forceinline__ uint32_t pair_at(const char *tile, int row, int kl) {
+  return *reinterpret_cast<const uint16_t *>(tile + row * BK + (((kl >> 4) ^ swz<BK>(row)) << 4) + (kl & 15));
 }
 
 }  // namespace fdnn

@@ -3,7 +3,8 @@ of the pair saturation.  Plain helper module: numpy only, no GPU, no fixture.
 
 Why: the library reproduces the reference's int16 saturation of every adjacent pair a[2j] w[2j] + a[2j+1] w[2j+1] with a
 sparse correction -- a screen per listed pair (one frame per lane, a ballot), the exact correction only when some lane
-fires -- and that walk is written out in seven kernels.  The Gaussian fixtures either never fire it or fire the same few
+fires -- and seven kernels walk it, each on a schedule of its own over one shared arithmetic (fdnn_pair.hpp, checked on
+the host by tests/host/pair_check.cpp).  The Gaussian fixtures either never fire it or fire the same few
 entries on every frame; the hot nets fire in almost every frame.  Here every listed entry fires on exactly the frames the
 caller switches it on in, and on no other.
 
