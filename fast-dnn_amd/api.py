@@ -146,6 +146,18 @@ SIGNATURES = {
     "fdnn_debug_sets_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_server_submit_lazy_set": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, C.POINTER(C.c_uint64)]),
     "fdnn_server_submit_raw_set": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, C.POINTER(C.c_uint64)]),
+    "fdnn_topk_rows_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_ctx_output_topk": (C.c_int, [C.c_void_p, C.c_int, _c_i32p, _c_f32p]),
+    "fdnn_ctx_output_topk_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_topk": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_int, _c_i32p, _c_f32p]),
+    "fdnn_calculate_topk_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_int, _c_i32p, _c_f32p]),
+    "fdnn_calculate_topk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_server_submit_topk": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, _c_f32p, C.POINTER(C.c_uint64)]),
+    "fdnn_server_submit_raw_topk": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, _c_f32p, C.POINTER(C.c_uint64)]),
+    "fdnn_debug_topk_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_set_topk_kernel": (C.c_int, [C.c_int]),
+    "fdnn_debug_topk_ref": (C.c_int, [_c_f32p, C.c_int, C.c_int, C.c_int, _c_i32p, _c_f32p]),
+    "fdnn_debug_topk_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_profile_begin": (C.c_int, [C.c_void_p]),
@@ -425,6 +437,64 @@ def set_kernel(mode: int) -> None:
     _check(lib().fdnn_debug_set_kernel(int(mode)))
 
 
+# The top-k selection's limits (fdnn_topk.hpp: kTopkMaxK, kTopkResidentWidth; tests/test_topk_host.py holds the two files
+# together and compares both with fdnn_debug_topk_limits)
+TOPK_MAX_K = 256
+TOPK_RESIDENT_WIDTH = 16384
+
+
+def topk_rows_device(d_rows: int, n: int, width: int, k: int, d_nodes: int, d_vals: int, stream: int = 0) -> None:
+    """The selection alone (``fdnn_topk_rows_device``) on device-resident fp32 rows [n][width] of the current device: the k
+    first-ranked nodes of every row and their values into d_nodes int32 [n][k] / d_vals float32 [n][k]; raw device pointers,
+    enqueued on ``stream``, not synchronised."""
+    _check(lib().fdnn_topk_rows_device(C.c_void_p(d_rows), int(n), int(width), int(k), C.c_void_p(d_nodes), C.c_void_p(d_vals), C.c_void_p(stream)))
+
+
+def topk_ref(rows, k: int):
+    """The same selection from the host restatement (``fdnn_debug_topk_ref``; host code, no device) on rows [n][width]
+    float32 (any bit patterns) -> (nodes int32 [n][k], vals float32 [n][k])."""
+    r = np.ascontiguousarray(rows, dtype=np.float32)
+    if r.ndim != 2:
+        raise ValueError("rows must be [n][width]")
+    nodes = np.empty((r.shape[0], int(k)), dtype=np.int32)
+    vals = np.empty((r.shape[0], int(k)), dtype=np.float32)
+    _check(lib().fdnn_debug_topk_ref(r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], int(k), nodes.ctypes.data_as(_c_i32p), vals.ctypes.data_as(_c_f32p)))
+    return nodes, vals
+
+
+def topk_launches():
+    """Process-wide counts since load: (launches of the resident form of the selection, of the streaming form)."""
+    buf = (C.c_ulonglong * 2)()
+    if lib().fdnn_debug_topk_launches(buf, 2) != 2:
+        raise RuntimeError("fdnn_debug_topk_launches")
+    return tuple(int(v) for v in buf)
+
+
+def set_topk_kernel(mode: int) -> None:
+    """Process-wide (``fdnn_debug_set_topk_kernel``): 0 the plan's rule, 1 resident where the width allows, 2 always streaming."""
+    _check(lib().fdnn_debug_set_topk_kernel(int(mode)))
+
+
+def topk_limits():
+    """(largest k, widest resident row) as the library was built (``fdnn_debug_topk_limits``)."""
+    a, b = C.c_int(), C.c_int()
+    _check(lib().fdnn_debug_topk_limits(C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
+def _topk_out(n: int, k: int, nodes, probs):
+    """The [n][k] result arrays of a top-k call, made or checked."""
+    if nodes is None:
+        nodes = np.empty((n, k), dtype=np.int32)
+    elif nodes.dtype != np.int32 or nodes.shape != (n, k) or not nodes.flags.c_contiguous:
+        raise ValueError(f"nodes must be a C-contiguous int32 array of shape {(n, k)}")
+    if probs is None:
+        probs = np.empty((n, k), dtype=np.float32)
+    elif probs.dtype != np.float32 or probs.shape != (n, k) or not probs.flags.c_contiguous:
+        raise ValueError(f"probs must be a C-contiguous float32 array of shape {(n, k)}")
+    return nodes, probs
+
+
 def _sets(segRows, setPtr, nodes):
     """(seg_rows, set_ptr, nodes) as C-contiguous int32 vectors of the shapes every sets entry point needs -> them, the
     segment count, the rows and the floats of probs."""
@@ -599,6 +669,17 @@ class LazyContext:
         _check(lib().fdnn_debug_ctx_sets_acc(self.handle, sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, nd.ctypes.data_as(_c_i32p),
                                              acc.ctypes.data_as(_c_i32p)))
         return acc
+
+    def calculateOutputTopK(self, k: int):
+        """The dense output layer over the context's frames, of which only the k first-ranked nodes of every frame and their
+        probabilities come back (``fdnn_ctx_output_topk``) -> (nodes int32 [frames][k], probs float32 [frames][k])."""
+        nodes, probs = _topk_out(self.inputVectorCount, int(k), None, None)
+        _check(lib().fdnn_ctx_output_topk(self.handle, int(k), nodes.ctypes.data_as(_c_i32p), probs.ctypes.data_as(_c_f32p)))
+        return nodes, probs
+
+    def calculateOutputTopKDevice(self, k: int, d_nodes: int, d_probs: int, stream: int = 0) -> None:
+        """The same into device buffers [frames][k], enqueued on ``stream``, not synchronised (``fdnn_ctx_output_topk_device``)."""
+        _check(lib().fdnn_ctx_output_topk_device(self.handle, int(k), C.c_void_p(d_nodes), C.c_void_p(d_probs), C.c_void_p(stream)))
 
     # device-resident forms (raw device pointers, e.g. ``tensor.data_ptr()``; enqueued on ``stream``)
     def calculateForOutputNodesBatchBits(self, bits, first: int = 0, out=None) -> np.ndarray:
@@ -854,6 +935,32 @@ class ScoringServer:
             raise ValueError(f"raw frames must be [n][{spec[1]}], got {r.shape}")
         return self._submit_set(lib().fdnn_server_submit_raw_set, r, r.shape[0], nodes, probs, inactive)
 
+    def submitTopK(self, x, k: int, nodes=None, probs=None):
+        """One utterance's k best nodes per frame through the loop (``fdnn_server_submit_topk``): coalesced with the other
+        callers' top-k submissions, the dense rows stay on the device -> (ticket, nodes int32 [n][k], probs float32 [n][k]),
+        valid after ``wait(ticket)``; the bytes of ``QuantizedDnn.calculateTopK``."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.dnn.inputDimension():
+            raise ValueError(f"Input vector size {x.shape[-1]} must be equal with network input size {self.dnn.inputDimension()}")
+        return self._submit_topk(lib().fdnn_server_submit_topk, x, int(k), nodes, probs)
+
+    def submitRawTopK(self, raw, k: int, nodes=None, probs=None):
+        """The same for raw feature frames [n][rawDim] of one utterance, spliced on the device by the model's splice spec at
+        submit time (``fdnn_server_submit_raw_topk``); the bytes of ``QuantizedDnn.calculateTopKRaw``."""
+        r = np.ascontiguousarray(raw, dtype=np.float32)
+        spec = self.dnn.spliceSpec()
+        if spec is not None and (r.ndim != 2 or r.shape[1] != spec[1]):
+            raise ValueError(f"raw frames must be [n][{spec[1]}], got {r.shape}")
+        return self._submit_topk(lib().fdnn_server_submit_raw_topk, r, int(k), nodes, probs)
+
+    def _submit_topk(self, fn, frames, k, nodes, probs):
+        n = frames.shape[0]
+        nodes, probs = _topk_out(n, k, nodes, probs)
+        t = C.c_uint64()
+        _check(fn(self.handle, frames.ctypes.data_as(_c_f32p), n, k, nodes.ctypes.data_as(_c_i32p), probs.ctypes.data_as(_c_f32p), C.byref(t)))
+        self._keep[int(t.value)] = (frames, nodes, probs)
+        return int(t.value), nodes, probs
+
     def _submit_set(self, fn, frames, n, nodes, probs, inactive):
         nd = _set(nodes)
         if probs is None:
@@ -1047,6 +1154,35 @@ class QuantizedDnn:
                                               sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, nd.ctypes.data_as(_c_i32p),
                                               probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p)))
         return probs, inactive
+
+    def calculateTopK(self, input, k: int):
+        """Dense scoring with a top-k return (``fdnn_calculate_topk``): the k first-ranked nodes of every frame's soft-max row
+        -- larger probability first, the lower node first among equal ones -- and their probabilities, chosen on the
+        device; only n x k x 8 bytes come back -> (nodes int32 [n][k], probs float32 [n][k]).  1 <= k <= min(O, 256)."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        nodes, probs = _topk_out(n, int(k), None, None)
+        _check(lib().fdnn_calculate_topk(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(), int(k),
+                                         nodes.ctypes.data_as(_c_i32p), probs.ctypes.data_as(_c_f32p)))
+        return nodes, probs
+
+    def calculateTopKRaw(self, raw, k: int):
+        """``calculateTopK`` on raw frames [n][rawDim] of one utterance, spliced on the device (``fdnn_calculate_topk_raw``)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError(f"raw frames must be [n][rawDim], got {r.shape}")
+        nodes, probs = _topk_out(r.shape[0], int(k), None, None)
+        _check(lib().fdnn_calculate_topk_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], int(k),
+                                             nodes.ctypes.data_as(_c_i32p), probs.ctypes.data_as(_c_f32p)))
+        return nodes, probs
+
+    def calculate_topk_device(self, d_x: int, n: int, k: int, d_nodes: int, d_probs: int, stream: int = 0) -> None:
+        """Device-resident form (``fdnn_calculate_topk_device``): d_x [n][inputDimension] -> d_nodes int32 [n][k], d_probs
+        float32 [n][k]; raw device pointers, enqueued on ``stream``, not synchronised."""
+        _check(lib().fdnn_calculate_topk_device(self.nativeDnnHandle, C.c_void_p(d_x), int(n), int(k), C.c_void_p(d_nodes), C.c_void_p(d_probs),
+                                                C.c_void_p(stream)))
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))

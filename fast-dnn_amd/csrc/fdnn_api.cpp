@@ -629,6 +629,105 @@ int fdnn_ctx_output(fdnn_ctx *c, float *out) {
   return copy_out(out, c->d_out, sizeof(float) * size_t(c->n) * c->m->hm.hdr.out_dim, c->stream);
 }
 
+// ---------------------------------------------------------------- dense output with a top-k return (fdnn_topk.hip)
+static int topk_k_check(int width, int k) {
+  if (fdnn::topk::args_ok(width, k)) return FDNN_OK;
+  return fail(FDNN_E_ARG, "k is 1 .. min(row width, " + std::to_string(fdnn::topk::kTopkMaxK) + ")");
+}
+
+int fdnn_topk_rows_device(const float *d_rows, int n, int width, int k, int32_t *d_nodes, float *d_vals, void *stream) {
+  if (n < 0 || width < 1) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = topk_k_check(width, k)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!d_rows || !d_nodes || !d_vals) return fail(FDNN_E_ARG, "null buffer");
+  fdnn::launch_topk(d_rows, n, width, k, d_nodes, d_vals, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+int fdnn_ctx_output_topk_device(fdnn_ctx *c, int k, int32_t *d_nodes, float *d_probs, void *stream) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (int rc = lazy_state(c)) return rc;
+  if (int rc = topk_k_check(c->m->hm.hdr.out_dim, k)) return rc;
+  if (c->n == 0) return FDNN_OK;
+  if (!d_nodes || !d_probs) return fail(FDNN_E_ARG, "null buffer");
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  if (!c->d_out) HIP_TRY(c->d_out.reserve(size_t(c->cap) * size_t(c->m->hm.hdr.out_dim)));  // (a lean context)
+  if (int rc = run_output(c, {.count = c->n, .d_out = c->d_out}, s)) return rc;
+  fdnn::launch_topk(c->d_out, c->n, c->m->hm.hdr.out_dim, k, d_nodes, d_probs, s);
+  return FDNN_OK;
+}
+
+int fdnn_ctx_output_topk(fdnn_ctx *c, int k, int32_t *nodes, float *probs) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (int rc = lazy_state(c)) return rc;
+  if (int rc = topk_k_check(c->m->hm.hdr.out_dim, k)) return rc;
+  if (c->n == 0) return FDNN_OK;
+  if (!nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  if (!c->d_out) HIP_TRY(c->d_out.reserve(size_t(c->cap) * size_t(c->m->hm.hdr.out_dim)));  // (a lean context)
+  return dense_pass(c, {.k = k, .nodes = nodes, .probs = probs}, c->stream, /*hidden=*/false);
+}
+
+int fdnn_calculate_topk(fdnn_model *m, const float *x, int n, int dim, int k, int32_t *nodes, float *probs) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = topk_k_check(m->hm.hdr.out_dim, k)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!x || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_topk", .x = x, .topk_k = k, .topk_nodes = nodes, .topk_probs = probs});
+}
+
+int fdnn_calculate_topk_raw(fdnn_model *m, const float *raw, int n, int raw_dim, int k, int32_t *nodes, float *probs) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  if (int rc = fdnn::splice_check(spec, raw_dim)) return rc;
+  if (int rc = topk_k_check(m->hm.hdr.out_dim, k)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!raw || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
+  const std::vector<SpliceSeg> segs{SpliceSeg{0, 0, 0, n - 1}};  // (the whole utterance's raw frames travel once, as fdnn_calculate_raw's)
+  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_topk_raw", .spec = spec.get(), .segs = &segs, .raw = raw, .raw_frames = n,
+                                             .topk_k = k, .topk_nodes = nodes, .topk_probs = probs});
+}
+
+int fdnn_calculate_topk_device(fdnn_model *m, const float *d_x, int n, int k, int32_t *d_nodes, float *d_probs, void *stream) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = topk_k_check(m->hm.hdr.out_dim, k)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!d_x || !d_nodes || !d_probs) return fail(FDNN_E_ARG, "null buffer");
+  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_topk_device", .d_x = d_x, .stream = static_cast<hipStream_t>(stream), .topk_k = k,
+                                             .d_topk_nodes = d_nodes, .d_topk_probs = d_probs});
+}
+
+int fdnn_debug_topk_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 2, fdnn::topk_launch_counts); }
+
+int fdnn_debug_set_topk_kernel(int mode) {
+  if (mode < 0 || mode > 2) return fail(FDNN_E_ARG, "mode is 0 (the plan's rule), 1 (resident where the width allows) or 2 (streaming)");
+  fdnn::topk_kernel_mode(mode);
+  return FDNN_OK;
+}
+
+// The selection in plain C++ (fdnn_topk.hpp: ref), no device
+int fdnn_debug_topk_ref(const float *rows, int n, int width, int k, int32_t *nodes, float *vals) {
+  if (n < 0 || width < 1) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = topk_k_check(width, k)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!rows || !nodes || !vals) return fail(FDNN_E_ARG, "null buffer");
+  fdnn::topk::ref(reinterpret_cast<const uint32_t *>(rows), n, width, k, nodes, reinterpret_cast<uint32_t *>(vals));
+  return FDNN_OK;
+}
+
+int fdnn_debug_topk_limits(int *max_k, int *resident_width) {
+  if (max_k) *max_k = fdnn::topk::kTopkMaxK;
+  if (resident_width) *resident_width = fdnn::topk::kTopkResidentWidth;
+  return FDNN_OK;
+}
+
 int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
   if (!c || !out) return fail(FDNN_E_ARG, "null argument");
   if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");

@@ -125,6 +125,7 @@ struct fdnn_ctx {
   fdnn::DevBuf<uint64_t> d_mask_bits;  // [n][ceil(O/64)] the batched lazy call's mask as bits (launch_mask_pack)
   bool mask_bits_packed = false;    // run_output has packed the current call's byte masks into d_mask_bits
   fdnn::DevBuf<float> d_comp;       // host lazy batches: compacted result rows (allocated on first use)
+  fdnn::DevBuf<int32_t> d_topk;     // host top-k calls: [n][k] nodes, then [n][k] values (allocated on first use, fdnn_topk.hip)
   // host list calls (fdnn_ctx_lazy_output_lists, fdnn_calculate_lazy_lists): staging of the lists and their results,
   // allocated on the first list call and grown by the largest one
   fdnn::DevBuf<int32_t> d_lrow, d_lnodes;   // [count + 1], [nnz]
@@ -274,6 +275,17 @@ int copy_out(void *dst, const void *d_src, size_t bytes, hipStream_t s);
 // The dense pass over the context's frames in c->d_x (c->n of them) into the host's `out`, synchronising s; re-runs what a
 // fused soft-max or chained launch that sat out its bounded wait left wrong.
 int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s);
+// The same pass with "what leaves the device" as the step that differs: the whole rows into out (k = 0), or the k
+// first-ranked nodes of every row and their values into nodes / probs [n][k] (fdnn_topk.hip) -- the rows stay in c->d_out.
+// hidden = false: the context holds the hidden activations already (fdnn_ctx_output_topk); the fused soft-max's re-run
+// applies, the chained launch's belongs to whoever ran the hidden layers.
+struct DenseTo {
+  float *out = nullptr;
+  int k = 0;
+  int32_t *nodes = nullptr;
+  float *probs = nullptr;
+};
+int dense_pass(fdnn_ctx *c, const DenseTo &to, hipStream_t s, bool hidden);
 // Lazy results of `count` frames (c->d_out) to a host caller, compacted over PCIe where that pays; d_bits / bits: the
 // frames' masks on the device / on the host.  Synchronises s.
 int lazy_copy_out(fdnn_ctx *c, int count, const uint64_t *d_bits, const uint64_t *bits, float *out, hipStream_t s);
@@ -363,6 +375,12 @@ struct ScorePass {
   float *d_out = nullptr;
   hipStream_t stream = nullptr;
   float *out = nullptr;
+  // or, of a dense pass, the topk_k first-ranked nodes of every row and their values, [n][topk_k] each (fdnn_topk.hip):
+  // to the host through dense_pass and its re-run rules (the rows never leave the device), or device buffers enqueued on
+  // `stream` (then the rows come from d_x)
+  int topk_k = 0;
+  int32_t *topk_nodes = nullptr, *d_topk_nodes = nullptr;
+  float *topk_probs = nullptr, *d_topk_probs = nullptr;
 };
 int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, const ScorePass &p);
 

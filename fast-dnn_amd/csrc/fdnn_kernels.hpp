@@ -11,6 +11,7 @@
 #include "fdnn_lists_union.hpp"
 #include "fdnn_set.hpp"
 #include "fdnn_sets.hpp"
+#include "fdnn_topk.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -252,6 +253,14 @@ hipError_t launch_lists_union_build(const UnionParams &u, int n_groups, hipStrea
 void launch_lists_union_score(const SetParams &p, const UnionParams &u, int n_cu, hipStream_t s);
 void lists_union_note_fallback();  // a call with the switch on that the list kernels serve
 void lists_union_launch_counts(unsigned long long out[4]);  // build, score without / with the pair walk, fallback calls
+
+// The dense output with a top-k return (fdnn_topk.hip; the order, the plan and the host restatement: fdnn_topk.hpp): of every
+// row of rows [n][width] the k first-ranked nodes and their values into nodes / vals [n][k].  The caller has checked
+// topk::args_ok(width, k).  The form is the plan's under fdnn_debug_set_topk_kernel's mode.
+void launch_topk(const float *d_rows, int n, int width, int k, int32_t *d_nodes, float *d_vals, hipStream_t s);
+void topk_launch_counts(unsigned long long out[2]);  // launches so far: resident form, streaming form
+int topk_kernel_mode();                              // fdnn_debug_set_topk_kernel: 0 the plan's rule, 1 resident where the width allows, 2 streaming
+void topk_kernel_mode(int mode);
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

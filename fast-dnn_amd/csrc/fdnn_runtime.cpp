@@ -817,39 +817,51 @@ void release_ctx(fdnn_ctx *c) {
   }
 }
 
-// The dense pass over the context's frames in c->d_x (c->n of them) into the host's `out`, synchronising s.
-int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) {
+// What leaves the device after a dense pass, synchronising s: the whole rows, or the selection of them (fdnn_topk.hip)
+// into the context's own pair buffer -- [n][k] nodes, then [n][k] values -- and its two halves to the caller's arrays.
+static int dense_leave(fdnn_ctx *c, const DenseTo &to, hipStream_t s) {
+  const size_t n = size_t(c->n), O = size_t(c->m->hm.hdr.out_dim);
+  if (to.k == 0) return copy_out(to.out, c->d_out, sizeof(float) * n * O, s);
+  const size_t nk = n * size_t(to.k);
+  HIP_TRY(c->d_topk.reserve(2 * nk));
+  fdnn::launch_topk(c->d_out, c->n, int(O), to.k, c->d_topk, reinterpret_cast<float *>(c->d_topk.p + nk), s);
+  HIP_TRY(hipMemcpyAsync(to.nodes, c->d_topk, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(to.probs, c->d_topk.p + nk, sizeof(float) * nk, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FDNN_OK;
+}
+
+// The dense pass over the context's frames (c->n of them) to a host caller, synchronising s: the hidden layers over c->d_x
+// (hidden = false: they have run, the context holds their activations), the output layer, then what leaves the device.
+int dense_pass(fdnn_ctx *c, const DenseTo &to, hipStream_t s, bool hidden) {
   fdnn_model *m = c->m;
-  const int n = c->n;
-  const size_t O = size_t(m->hm.hdr.out_dim);
   const unsigned long long unwritten_before = m->h_fuse_fault ? __atomic_load_n(m->h_fuse_fault.p, __ATOMIC_RELAXED) >> 32 : 0ull;
-  int rc = run_hidden(c, c->d_x, s, nullptr);
-  if (!rc) rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
-  if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
-  if (rc) hipStreamSynchronize(s);
-  // copy_out has synchronised: did a fused soft-max workgroup of THIS pass sit out its bounded wait?  fdnn_gemm.hip's
+  const auto pass = [&](bool with_hidden) {
+    int rc = with_hidden ? run_hidden(c, c->d_x, s, nullptr) : FDNN_OK;
+    if (!rc) rc = run_output(c, {.count = c->n, .d_out = c->d_out}, s);
+    if (!rc) rc = dense_leave(c, to, s);
+    if (rc) hipStreamSynchronize(s);
+    return rc;
+  };
+  int rc = pass(hidden);
+  // dense_leave has synchronised: did a fused soft-max workgroup of THIS pass sit out its bounded wait?  fdnn_gemm.hip's
   // tiles finish such a frame tile after the fact, fdnn_ppo.hip's leave the half's rows unwritten (and say so through the
   // same word): the output layer runs again -- unfused now, model_may_fuse has seen the word -- over the activations that
-  // are still in the context.  (The word's upper half counts such halves.  Callers of the *_device entry points observe
-  // fdnn_model_fuse_giveups after their own synchronisation: INTEGRATION.md.)
+  // are still in the context, before anything of it is handed out.  (The word's upper half counts such halves.  Callers of
+  // the *_device entry points observe fdnn_model_fuse_giveups after their own synchronisation: INTEGRATION.md.)
   if (!rc && m->h_fuse_fault && (__atomic_load_n(m->h_fuse_fault.p, __ATOMIC_RELAXED) >> 32) != unwritten_before) {
     const bool saved = c->no_fuse;
     c->no_fuse = true;  // (whatever FDNN_FUSE_NORM says)
-    rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
+    rc = pass(false);
     c->no_fuse = saved;
-    if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
-    if (rc) hipStreamSynchronize(s);
   }
-  // copy_out has synchronised: did this pass's chained launch run into its wait bound?  Then what it computed on may not have
+  // dense_leave has synchronised: did this pass's chained launch run into its wait bound?  Then what it computed on may not have
   // been written -- run the pass again, layer by layer (run_hidden sees the flag, re-zeroes the counters, stops chaining)
-  if (!rc && c->h_chain_fault && __atomic_load_n(c->h_chain_fault.p, __ATOMIC_RELAXED) != 0 && !c->chain_broken) {
-    rc = run_hidden(c, c->d_x, s, nullptr);
-    if (!rc) rc = run_output(c, {.count = n, .d_out = c->d_out}, s);
-    if (!rc) rc = copy_out(out, c->d_out, sizeof(float) * size_t(n) * O, s);
-    if (rc) hipStreamSynchronize(s);
-  }
+  if (!rc && hidden && c->h_chain_fault && __atomic_load_n(c->h_chain_fault.p, __ATOMIC_RELAXED) != 0 && !c->chain_broken) rc = pass(true);
   return rc;
 }
+
+int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s) { return dense_pass(c, {.out = out}, s, true); }
 
 // ---------------------------------------------------------------- raw feature frames
 int splice_check(const SpliceRef &spec, int raw_dim) {
@@ -947,7 +959,7 @@ int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, 
   fdnn_ctx *c = nullptr;
   int rc = acquire_ctx(m, cap, &c);
   if (rc) return rc;
-  hipStream_t s = p.d_out ? p.stream : c->stream;
+  hipStream_t s = (p.d_out || p.d_topk_nodes) ? p.stream : c->stream;
   std::vector<int32_t> rebased;
   CtxUse use;  // (also on the error paths: the context goes back to the pool)
   hipError_t e = use.enter(c, s);
@@ -985,6 +997,16 @@ int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, 
     }
     if (p.out && !p.bits) {
       rc = dense_pass_to_host(c, p.out + off * O, s);
+      continue;
+    }
+    if (p.topk_k && p.topk_nodes) {  // host top-k: n x k x 8 bytes cross PCIe
+      rc = dense_pass(c, {.k = p.topk_k, .nodes = p.topk_nodes + off * size_t(p.topk_k), .probs = p.topk_probs + off * size_t(p.topk_k)}, s, true);
+      continue;
+    }
+    if (p.topk_k) {  // device top-k: the rows stay in the context, the selection goes to the caller's buffers
+      rc = run_hidden(c, p.d_x + off * D, s, nullptr);
+      if (!rc) rc = run_output(c, {.count = cnt, .d_out = c->d_out}, s);
+      if (!rc) fdnn::launch_topk(c->d_out, cnt, int(O), p.topk_k, p.d_topk_nodes + off * size_t(p.topk_k), p.d_topk_probs + off * size_t(p.topk_k), s);
       continue;
     }
     const uint64_t *d_bits = p.bits ? c->d_mask_bits : p.d_bits ? p.d_bits + off * wpr : nullptr;

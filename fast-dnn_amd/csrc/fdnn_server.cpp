@@ -78,6 +78,8 @@ struct Slot {
   Buf<float> h_raw;               // raw batches: the pieces' raw frames back to back; grows to the largest raw batch
   Buf<int32_t> h_nodes;           // set batches: the pieces' sets back to back (pageable where pinned memory is refused) ...
   Buf<int32_t, true> d_nodes;     // ... and on the device; both grow to the largest set batch
+  Buf<int32_t, true> d_topk;      // top-k batches: [rows][k_b] nodes, then [rows][k_b] values (the dense rows stay in d_out) ...
+  Buf<int32_t> h_topk;            // ... and where both land on the host: ONE transfer per batch (pageable where pinned memory is refused)
   Buf<float> h_set;               // ... where its probs [nnz] and inactive values [rows] land: ONE transfer per batch (d_out holds both)
   BatchPlan batch;                // the current host batch: its pieces, where their frames are staged, how its rows return
   bool rows_on_host = false;      // its rows have been brought to h_out
@@ -150,6 +152,8 @@ struct BatchCall {
   hipEvent_t after = nullptr;  // (may be null) an event the compute must wait for: the batch's H2D copy
   float *d_comp = nullptr;     // bit-mask host batches: the rows compacted, `stride` floats each
   int stride = 0;
+  int32_t *d_topk = nullptr;   // top-k host batches: [n][topk_k] nodes, then [n][topk_k] values, selected from d_out
+  int topk_k = 0;
 };
 int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *last_stream) {
   const int n = b.n;
@@ -206,6 +210,9 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *las
   // bit-mask host batches: the rows compacted (active probabilities + one value per frame) for the trip over PCIe
   if (!rc && b.d_bits && b.d_comp && b.stride > 0)
     fdnn::launch_lazy_compact(b.d_out, b.d_bits, b.d_comp, n, s->m->hm.hdr.out_dim, b.stride, end);
+  // top-k host batches: one selection launch with the batch's k over the rows, which stay here
+  if (!rc && b.d_topk && b.topk_k > 0)
+    fdnn::launch_topk(b.d_out, n, s->m->hm.hdr.out_dim, b.topk_k, b.d_topk, reinterpret_cast<float *>(b.d_topk + size_t(n) * size_t(b.topk_k)), end);
   if (!rc) *last_stream = end;
   return rc;
 }
@@ -293,7 +300,16 @@ void copy_ready_pieces(fdnn_server *s, std::unique_lock<std::mutex> &lk, Slot &s
     // bounce buffer and no second pass over the 32 KB per frame
     hipError_t ce = hipSuccess;
     const size_t stride = size_t(sl.batch.stride);  // (stable while the slot is in flight)
-    if (job.set) {
+    if (job.topk) {
+      // a top-k piece: the batch's pairs came to the slot's landing buffer with the batch, k_b columns a row; this piece
+      // keeps the first k of its rows (the top k is a prefix of the top k_b)
+      const size_t kb = size_t(sl.batch.topk_k), k = size_t(job.topk), all = size_t(sl.batch.rows) * kb;
+      for (size_t r = 0; r < size_t(job.rows); ++r) {
+        const int32_t *src = sl.h_topk.p + (size_t(job.row0) + r) * kb;
+        std::memcpy(job.topk_nodes + r * k, src, sizeof(int32_t) * k);
+        std::memcpy(job.topk_probs + r * k, src + all, sizeof(float) * k);
+      }
+    } else if (job.set) {
       // a set piece: its block of probs and its inactive values came to the slot's landing buffer with the batch
       const size_t len = job.set->size();
       if (len) std::memcpy(job.probs, sl.h_set.p + size_t(job.block_off), sizeof(float) * size_t(job.rows) * len);
@@ -418,7 +434,7 @@ hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
   BatchPlan &b = sl.batch;
   // Whole rows of a batch that several callers share (1 GB of pinned memory per slot at most) go to the host in one transfer;
   // a single caller's batch, or one for which no pinned memory is to be had, leaves by per-caller copies from the device.
-  sl.rows_on_host = b.kind != kSet && b.stride == 0 && b.taken.size() > 1 && frames * O * sizeof(float) <= (size_t(1) << 30) &&
+  sl.rows_on_host = b.kind != kSet && b.kind != kTopk && b.stride == 0 && b.taken.size() > 1 && frames * O * sizeof(float) <= (size_t(1) << 30) &&
                     sl.h_out.reserve(frames * O) == hipSuccess;
   if (b.kind == kBits) {
     // (advisor, round 5) no pinned memory to be had: pageable staging, the batch is not lost
@@ -441,6 +457,11 @@ hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
     hipError_t e = sl.h_nodes.reserve(std::max<size_t>(size_t(b.set_nodes), 1), /*pageable_ok=*/true);
     if (e == hipSuccess) e = sl.d_nodes.reserve(std::max<size_t>(size_t(b.set_nodes), 1));
     if (e == hipSuccess) e = sl.h_set.reserve(size_t(b.nnz) + size_t(b.rows), /*pageable_ok=*/true);
+    if (e != hipSuccess) return e;
+  }
+  if (b.kind == kTopk) {  // the pairs of the batch: grown to the largest batch, the landing buffer pageable if need be
+    hipError_t e = sl.d_topk.reserve(2 * size_t(b.rows) * size_t(b.topk_k));
+    if (e == hipSuccess) e = sl.h_topk.reserve(2 * size_t(b.rows) * size_t(b.topk_k), /*pageable_ok=*/true);
     if (e != hipSuccess) return e;
   }
   if (!b.raw) return hipSuccess;
@@ -506,7 +527,8 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
   hipStream_t last = sl.stream;
   *rc = enqueue_batch(s, sl, {.d_x = c->d_x, .n = b.rows, .d_masks = !bits && b.any_mask ? c->d_mask : nullptr,
                               .d_bits = bits ? c->d_mask_bits : nullptr, .d_out = sl.d_out.p, .after = sl.staged,
-                              .d_comp = sl.d_comp.p, .stride = b.stride}, &last);
+                              .d_comp = sl.d_comp.p, .stride = b.stride, .d_topk = b.kind == kTopk ? sl.d_topk.p : nullptr,
+                              .topk_k = b.topk_k}, &last);
   if (*rc) return hipSuccess;
   if (last != sl.stream) {  // results leave on the slot's stream, behind the tail stream's scale pass
     e = hipEventRecord(sl.gemm_done, last);  // (gemm_done is free again: the scale pass already waits on its earlier record)
@@ -514,6 +536,8 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
   }
   if (e == hipSuccess && bits && b.stride > 0)  // compacted rows: to the host with the batch
     e = hipMemcpyAsync(sl.h_comp.p, sl.d_comp.p, sizeof(float) * rows * size_t(b.stride), hipMemcpyDeviceToHost, sl.stream);
+  else if (e == hipSuccess && b.kind == kTopk)  // the pairs: to the host with the batch, the rows never leave the device
+    e = hipMemcpyAsync(sl.h_topk.p, sl.d_topk.p, sizeof(int32_t) * 2 * rows * size_t(b.topk_k), hipMemcpyDeviceToHost, sl.stream);
   else if (e == hipSuccess && sl.rows_on_host)
     e = hipMemcpyAsync(sl.h_out.p, sl.d_out.p, sizeof(float) * rows * O, hipMemcpyDeviceToHost, sl.stream);
   if (e == hipSuccess) e = hipEventRecord(sl.done, sl.stream);
@@ -810,6 +834,24 @@ int fdnn_server_submit_raw_set(fdnn_server *s, const float *raw, int n, const in
   if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
   if (!raw) return fail(FDNN_E_ARG, "null buffer");
   return submit_set(s, Request{.n = n, .raw = raw, .spec = spec, .raw_n = n, .raw_a = 0}, nodes, len, probs, inactive, ticket);
+}
+
+int fdnn_server_submit_topk(fdnn_server *s, const float *x, int n, int k, int32_t *nodes, float *probs, uint64_t *ticket) {
+  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
+  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
+  if (!fdnn::topk::args_ok(s->m->hm.hdr.out_dim, k)) return fail(FDNN_E_ARG, "k is 1 .. min(output_dim, 256)");
+  if (!x || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
+  return submit_host(s, Request{.x = x, .n = n, .topk = k, .topk_nodes = nodes, .topk_probs = probs}, ticket);
+}
+
+int fdnn_server_submit_raw_topk(fdnn_server *s, const float *raw, int n, int k, int32_t *nodes, float *probs, uint64_t *ticket) {
+  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
+  const fdnn::SpliceRef spec = s->m->splice;
+  if (int rc = fdnn::splice_check(spec, -1)) return rc;
+  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
+  if (!fdnn::topk::args_ok(s->m->hm.hdr.out_dim, k)) return fail(FDNN_E_ARG, "k is 1 .. min(output_dim, 256)");
+  if (!raw || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
+  return submit_host(s, Request{.n = n, .raw = raw, .spec = spec, .raw_n = n, .raw_a = 0, .topk = k, .topk_nodes = nodes, .topk_probs = probs}, ticket);
 }
 
 int fdnn_server_wait(fdnn_server *s, uint64_t ticket) {

@@ -28,6 +28,11 @@ struct Piece {  // one caller's rows inside a coalesced batch
   SetRef set;
   int set_off = 0, block_off = 0;
   float *probs = nullptr, *inactive = nullptr;
+  // top-k submissions (then out is null): the piece's own k and the caller's [rows][k] destinations of these rows (advanced
+  // by the frames earlier batches took); the batch selects with its largest k and a piece keeps the first k columns
+  int topk = 0;
+  int32_t *topk_nodes = nullptr;
+  float *topk_probs = nullptr;
 };
 
 struct Request {
@@ -47,6 +52,10 @@ struct Request {
   // set submissions (then out, masks and bits are null): ONE node set for all n rows; results probs [n][len], inactive [n]
   SetRef set;
   float *set_probs = nullptr, *set_inactive = nullptr;
+  // top-k submissions (then out, masks, bits and set are null): the k first-ranked nodes of every row; results [n][topk] each
+  int topk = 0;
+  int32_t *topk_nodes = nullptr;
+  float *topk_probs = nullptr;
 };
 
 // raw batches, per piece: the raw frames it references, [first, first + count) of its utterance, at frame `at` of the slot's buffer
@@ -69,8 +78,9 @@ inline int widest_row(const uint64_t *bits, int n, size_t O) {
 
 // what a host batch carries: kinds do not share a batch, except that dense callers may ride in a byte-mask batch (all active)
 // -- and set requests (kSet: no output layer runs, fdnn_sets.hip scores each piece's set) share batches only with set requests
-enum BatchKind { kDense = 0, kBytes = 1, kBits = 2, kSet = 3 };
-inline int kind_of(const Request &r) { return r.set ? kSet : r.bits ? kBits : r.masks ? kBytes : kDense; }
+// -- and top-k requests (kTopk: a dense batch whose rows stay on the device, fdnn_topk.hip selects from them) only with top-k requests
+enum BatchKind { kDense = 0, kBytes = 1, kBits = 2, kSet = 3, kTopk = 4 };
+inline int kind_of(const Request &r) { return r.topk ? kTopk : r.set ? kSet : r.bits ? kBits : r.masks ? kBytes : kDense; }
 
 struct BatchPlan {
   std::vector<Request> taken;  // per piece: the request with .taken = first frame, .n = frames in THIS batch
@@ -81,6 +91,7 @@ struct BatchPlan {
   int rows = 0, raw_frames = 0, most = 0, kind = kDense, stride = 0;  // stride: floats per compacted row (0: the rows leave whole)
   bool any_mask = false, raw = false;
   int nnz = 0, set_nodes = 0;  // set batches: the floats of the batch's probs (sum of rows x len) and the nodes of its pieces' sets
+  int topk_k = 0;              // top-k batches: the largest k among its pieces (a smaller k's result is a prefix of it)
 };
 
 // Takes requests off the front of the queue, whole or in part, until the batch is full (max_frames rows) or the next one may
@@ -96,7 +107,7 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
       b.kind = rk;
       b.raw = r.raw != nullptr;
       b.spec = r.spec;
-    } else if ((rk == kBits) != (b.kind == kBits) || (rk == kSet) != (b.kind == kSet) || (r.raw != nullptr) != b.raw || r.spec != b.spec)
+    } else if ((rk == kBits) != (b.kind == kBits) || (rk == kSet) != (b.kind == kSet) || (rk == kTopk) != (b.kind == kTopk) || (r.raw != nullptr) != b.raw || r.spec != b.spec)
       break;
     else if (rk == kBytes)
       b.kind = kBytes;
@@ -119,6 +130,13 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
       pc.inactive = r.set_inactive + part.taken;
       b.set_nodes += int(len);
       b.nnz += take * int(len);
+    }
+    if (rk == kTopk) {  // a later part of a split request continues at taken * k of the caller's arrays
+      Piece &pc = b.pieces.back();
+      pc.topk = r.topk;
+      pc.topk_nodes = r.topk_nodes + size_t(part.taken) * size_t(r.topk);
+      pc.topk_probs = r.topk_probs + size_t(part.taken) * size_t(r.topk);
+      b.topk_k = std::max(b.topk_k, r.topk);
     }
     if (b.raw) {  // the raw frames this piece's rows reference, and where they are staged
       const int u0 = r.raw_a + part.taken;  // the piece's first row as a frame of its utterance

@@ -302,6 +302,38 @@ FDNN_API int fdnn_calculate_lazy_sets(fdnn_model *m, const float *x, int n, int 
  * (CalculateOutput, dnn.cc:428-454). */
 FDNN_API int fdnn_ctx_output(fdnn_ctx *c, float *out);
 FDNN_API int fdnn_ctx_output_device(fdnn_ctx *c, float *d_out, void *stream);
+/* ------------------------------------------------------------------ dense output with a top-k return (fdnn_topk.hip)
+ * The dense soft-max with the DEVICE choosing what to return: of every row the k first-ranked nodes and their
+ * probabilities, 1 <= k <= min(row width, 256) -- n x k x 8 bytes instead of n x output_dim x 4.  The contract, for a row
+ * p[0 .. W) of fp32 values:
+ *   key(v) = u ^ (u >> 31 ? 0xffffffff : 0x80000000) for the 32 bits u of v: the usual total order on floats,
+ *   -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, with no special case (rows of the unstabilised soft-max can hold inf / NaN);
+ *   node i ranks before node j when key(p[i]) > key(p[j]), or the keys are equal and i < j;
+ *   nodes[0 .. k) / vals[0 .. k) are the k first-ranked nodes in rank order and their values, the row's own 32 bits.
+ * The top k is a prefix of the top k + 1.  A result depends on its row and k only: not on n, the row's position, the entry
+ * point, the batch it rode in or the kernel form that served it.  Results are [n][k] row-major.  FDNN_E_ARG for k outside
+ * its range.  Nothing is routed here: the batcher (fdnn_model_enable_batcher), device groups and the JNI shim neither route
+ * to nor look at any of these entry points, and every other entry point keeps its bytes.
+ *
+ * fdnn_topk_rows_device       the selection alone on any device-resident [n][width] fp32 rows of the CURRENT device (behind
+ *   fdnn_calculate_device, fdnn_float_calculate_device or the lazy *_device forms, for instance; extends CalculateOutput,
+ *   dnn.cc:428-454).  Enqueued on `stream`, not synchronised; n == 0 is a no-op; FDNN_E_ARG for null pointers or width < 1.
+ * fdnn_ctx_output_topk        fdnn_ctx_output's computation (CalculateOutput, dnn.cc:428-454) into the context's own rows,
+ *   then the selection; host buffers, host-synchronous.  FDNN_E_STATE before the hidden layers.  Works unchanged on
+ *   fdnn_stream_ctx(s) after a hidden-only push.
+ * fdnn_ctx_output_topk_device the same with device buffers, enqueued on `stream`, ordered on the context like the other
+ *   *_device entries (CalculateOutput, dnn.cc:428-454).
+ * fdnn_calculate_topk         host to host on a pooled context, chunk by chunk like fdnn_calculate (Calculate,
+ *   dnn.cc:162-165): only n x k x 8 bytes cross PCIe.  Obeys the re-run rules of the dense host forms.
+ * fdnn_calculate_topk_raw     the same from raw feature frames, like fdnn_calculate_raw (Calculate, dnn.cc:162-165).
+ * fdnn_calculate_topk_device  device buffers, a pooled context for the intermediate rows; enqueued, not synchronised
+ *   (Calculate, dnn.cc:162-165). */
+FDNN_API int fdnn_topk_rows_device(const float *d_rows, int n, int width, int k, int32_t *d_nodes, float *d_vals, void *stream);
+FDNN_API int fdnn_ctx_output_topk(fdnn_ctx *c, int k, int32_t *nodes, float *probs);
+FDNN_API int fdnn_ctx_output_topk_device(fdnn_ctx *c, int k, int32_t *d_nodes, float *d_probs, void *stream);
+FDNN_API int fdnn_calculate_topk(fdnn_model *m, const float *x, int n, int dim, int k, int32_t *nodes, float *probs);
+FDNN_API int fdnn_calculate_topk_raw(fdnn_model *m, const float *raw, int n, int raw_dim, int k, int32_t *nodes, float *probs);
+FDNN_API int fdnn_calculate_topk_device(fdnn_model *m, const float *d_x, int n, int k, int32_t *d_nodes, float *d_probs, void *stream);
 /* Last hidden layer's u8 activations, n x hidden_dim (quantized_activations_). */
 FDNN_API int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out);
 
@@ -366,6 +398,15 @@ FDNN_API int fdnn_server_submit_lazy_set(fdnn_server *s, const float *x, int n, 
                                          float *inactive, uint64_t *ticket);
 FDNN_API int fdnn_server_submit_raw_set(fdnn_server *s, const float *raw, int n, const int32_t *nodes, int len, float *probs,
                                         float *inactive, uint64_t *ticket);
+/* One utterance's k best nodes per frame through the loop (the top-k contract above; CalculateOutput, dnn.cc:428-454, for
+ * many callers): top-k submissions are coalesced with one another (same rawness and spec), the batch runs as a dense batch,
+ * ONE selection launch with the largest k among its pieces runs over the rows -- which never leave the device --, one
+ * transfer brings the pairs to the host, and each caller gets the first k columns of its rows (the prefix property).
+ * Byte-identical to fdnn_calculate_topk / fdnn_calculate_topk_raw on the same utterance.  x or raw, nodes [n][k] and probs
+ * [n][k] must stay valid until the ticket completes.  fdnn_server_submit_raw_topk takes raw feature frames [n][D], spliced
+ * on the device by the model's spec at submit time. */
+FDNN_API int fdnn_server_submit_topk(fdnn_server *s, const float *x, int n, int k, int32_t *nodes, float *probs, uint64_t *ticket);
+FDNN_API int fdnn_server_submit_raw_topk(fdnn_server *s, const float *raw, int n, int k, int32_t *nodes, float *probs, uint64_t *ticket);
 FDNN_API int fdnn_server_wait(fdnn_server *s, uint64_t ticket);
 FDNN_API int fdnn_server_drain(fdnn_server *s);
 FDNN_API int fdnn_server_stats(fdnn_server *s, uint64_t *batches, uint64_t *frames, uint64_t *requests,
@@ -558,6 +599,19 @@ FDNN_API int fdnn_debug_sets_check(const int32_t *seg_rows, const int32_t *set_p
 FDNN_API int fdnn_debug_ctx_sets_acc(fdnn_ctx *c, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, const int32_t *nodes,
                                      int32_t *acc);
 FDNN_API int fdnn_debug_sets_launches(unsigned long long *out, int cap);
+
+/* Dense output with a top-k return (CalculateOutput, dnn.cc:428-454), tests and tools.
+ * fdnn_debug_topk_launches    process-wide counts since load, returns 2: out[0] launches of the resident form (the row kept
+ *   in LDS), [1] of the streaming form (the passes re-read the row).  Not in the launch recorder's table (fdnn_note.hpp).
+ * fdnn_debug_set_topk_kernel  process-wide: 0 the plan's rule (resident up to the resident width), 1 resident where the
+ *   width allows, 2 always streaming -- the same bytes either way (dnn.cc:428-454).
+ * fdnn_debug_topk_ref         the selection of fdnn_topk_rows_device from the host restatement (fdnn_topk.hpp) on host
+ *   rows, host code, no device needed (dnn.cc:428-454).
+ * fdnn_debug_topk_limits      the largest k and the widest resident row, as the kernels were built (dnn.cc:428-454). */
+FDNN_API int fdnn_debug_topk_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_set_topk_kernel(int mode);
+FDNN_API int fdnn_debug_topk_ref(const float *rows, int n, int width, int k, int32_t *nodes, float *vals);
+FDNN_API int fdnn_debug_topk_limits(int *max_k, int *resident_width);
 
 /* Tests: write the word a fused soft-max workgroup raises (in host memory) when it gives up waiting for its frame tile's
  * siblings -- 1: as if a launch of this model had just done so (from the next call on the model runs the unfused soft-max

@@ -10,6 +10,9 @@
 //         set        = fdnn_calculate_lazy_set per utterance: each caller its own node set of SET_LEN nodes (environment, 80)
 //         setserver  = fdnn_server_submit_lazy_set + fdnn_server_wait (set utterances coalesced, no output layer, only
 //                      probs [frames][SET_LEN] + inactive [frames] back)
+//         topk       = fdnn_calculate_topk per utterance: the TOPK_K (environment, 32) best nodes of every frame, chosen on the
+//                      device -- frames x TOPK_K x 8 bytes back instead of frames x output_dim x 4
+//         topkserver = fdnn_server_submit_topk + fdnn_server_wait (top-k utterances coalesced, the dense rows stay on the device)
 // SET_LEN=k with lazy / lazyserver: the masks are those sets (the same k nodes in every frame of a caller) instead of 40 %.
 // INFLIGHT=k (environment, server modes): every caller keeps k utterances in flight (k result blocks per thread) instead of
 // waiting for each one before submitting the next.
@@ -47,7 +50,9 @@ int main(int argc, char **argv) {
   const bool lazy = mode == "lazy" || mode == "lazyserver";
   const bool sets = mode == "set" || mode == "setserver";
   const int set_len = std::getenv("SET_LEN") ? std::atoi(std::getenv("SET_LEN")) : (sets ? 80 : 0);
-  if ((mode == "server" || mode == "lazyserver" || mode == "setserver") && fdnn_server_create(m, max_frames, depth, &srv)) {
+  const bool topk = mode == "topk" || mode == "topkserver";
+  const int topk_k = std::getenv("TOPK_K") ? std::atoi(std::getenv("TOPK_K")) : 32;
+  if ((mode == "server" || mode == "lazyserver" || mode == "setserver" || mode == "topkserver") && fdnn_server_create(m, max_frames, depth, &srv)) {
     std::fprintf(stderr, "server: %s\n", fdnn_last_error());
     return 1;
   }
@@ -87,6 +92,18 @@ int main(int argc, char **argv) {
       std::sort(nodes[size_t(t)].begin(), nodes[size_t(t)].end());
       probs[size_t(t)].assign(size_t(F) * size_t(set_len), 0.0f);
       inact[size_t(t)].assign(size_t(F), 0.0f);
+    }
+  }
+  std::vector<std::vector<int32_t>> top_nodes(static_cast<size_t>(T));  // top-k modes: per thread [F][topk_k] nodes and values
+  std::vector<std::vector<float>> top_probs(static_cast<size_t>(T));
+  if (topk) {
+    if (topk_k < 1 || topk_k > std::min(O, 256) || inflight > 1) {
+      std::fprintf(stderr, "TOPK_K is 1 .. min(output dimension, 256); the top-k modes keep one utterance per caller in flight\n");
+      return 1;
+    }
+    for (int t = 0; t < T; ++t) {
+      top_nodes[size_t(t)].assign(size_t(F) * size_t(topk_k), 0);
+      top_probs[size_t(t)].assign(size_t(F) * size_t(topk_k), 0.0f);
     }
   }
   if (lazy && set_len > 0) {
@@ -142,6 +159,14 @@ int main(int argc, char **argv) {
         } else {
           rc = fdnn_calculate_lazy_set(m, xs[size_t(t)].data(), F, D, nd.data(), set_len, probs[size_t(t)].data(), inact[size_t(t)].data());
         }
+      } else if (topk) {
+        if (srv) {
+          uint64_t ticket = 0;
+          rc = fdnn_server_submit_topk(srv, xs[size_t(t)].data(), F, topk_k, top_nodes[size_t(t)].data(), top_probs[size_t(t)].data(), &ticket);
+          if (!rc) rc = fdnn_server_wait(srv, ticket);
+        } else {
+          rc = fdnn_calculate_topk(m, xs[size_t(t)].data(), F, D, topk_k, top_nodes[size_t(t)].data(), top_probs[size_t(t)].data());
+        }
       } else if (srv && lazy) {
         uint64_t ticket = 0;
         rc = fdnn_server_submit_lazy_bits(srv, xs[size_t(t)].data(), F, bits[size_t(t)].data(), outs[size_t(t)].data(), &ticket);
@@ -176,6 +201,10 @@ int main(int argc, char **argv) {
   if (sets) {  // the same row as the lazy modes' row0_sum with SET_LEN: the listed nodes' probabilities + the others' inactive value
     sum = double(O - set_len) * inact[0][0];
     for (int j = 0; j < set_len; ++j) sum += probs[0][size_t(j)];
+  }
+  if (topk) {  // row 0's returned mass: the sum of its TOPK_K largest probabilities
+    sum = 0.0;
+    for (int j = 0; j < topk_k; ++j) sum += top_probs[0][size_t(j)];
   }
   uint64_t batches = 0, frames = 0, reqs = 0, coal = 0;
   if (srv) fdnn_server_stats(srv, &batches, &frames, &reqs, &coal);
