@@ -201,6 +201,7 @@ int fdnn_ctx_forward_hidden_device(fdnn_ctx *c, const float *d_x, void *stream) 
     c->last = 0;
     return FDNN_OK;
   }
+  if (int rc = check_frames_aligned(d_x)) return rc;
   DeviceGuard g(c->m->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   CtxUse use;
@@ -700,6 +701,7 @@ int fdnn_calculate_topk_device(fdnn_model *m, const float *d_x, int n, int k, in
   if (int rc = topk_k_check(m->hm.hdr.out_dim, k)) return rc;
   if (n == 0) return FDNN_OK;
   if (!d_x || !d_nodes || !d_probs) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_frames_aligned(d_x)) return rc;
   return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_topk_device", .d_x = d_x, .stream = static_cast<hipStream_t>(stream), .topk_k = k,
                                              .d_topk_nodes = d_nodes, .d_topk_probs = d_probs});
 }
@@ -746,6 +748,7 @@ int fdnn_calculate_device(fdnn_model *m, const float *d_x, int n, float *d_out, 
   if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
   if (n == 0) return FDNN_OK;
   if (!d_x || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_frames_aligned(d_x)) return rc;
   return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_device", .d_x = d_x, .d_out = d_out, .stream = static_cast<hipStream_t>(stream)});
 }
 
@@ -786,6 +789,7 @@ int fdnn_calculate_lazy_bits_device(fdnn_model *m, const float *d_x, int n, cons
   if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
   if (n == 0) return FDNN_OK;
   if (!d_x || !d_out || !d_bits) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_frames_aligned(d_x)) return rc;
   return score_chunks(m, frame_chunks(n, m),
                       {.who = "fdnn_calculate_lazy_bits_device", .d_x = d_x, .d_bits = d_bits, .d_out = d_out, .stream = static_cast<hipStream_t>(stream)});
 }

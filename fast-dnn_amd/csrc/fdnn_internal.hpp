@@ -310,6 +310,10 @@ bool hidden_layers_chain(const fdnn_model *m, int n);
 std::vector<std::pair<int, int>> stride_chunks(int n);  // kChunkFrames strides, no tail split: the host lazy forms
 // "input vector size ... must be equal with network input size ..." (QuantizedDnn.java:157-161)
 int check_input_width(const fdnn_model *m, int dim);
+// A caller's device frames [n][in_dim] must start on a 16-byte boundary: layer 0 reads them as 16-byte LDS-DMA pieces
+// (l0_small_kernel, fdnn_l0.hip), whose source address nothing establishes as free.  in_dim is a multiple of 4, so every row
+// and every chunk of rows keeps the alignment of the base.  FDNN_E_ARG before anything is launched.
+int check_frames_aligned(const float *d_x);
 // The second half of a call through a model's batcher: `submitted` is what the submit call returned, *ticket what it filled in.
 inline int batcher_wait(fdnn_server *b, int submitted, const uint64_t *ticket) { return submitted ? submitted : fdnn_server_wait(b, *ticket); }
 // fdnn_calculate on the model's own device (the group path calls this per shard).

@@ -950,6 +950,11 @@ int check_input_width(const fdnn_model *m, int dim) {
   return fail(FDNN_E_ARG, "input vector size " + std::to_string(dim) + " must be equal with network input size " + std::to_string(m->hm.hdr.in_dim));
 }
 
+int check_frames_aligned(const float *d_x) {
+  if ((reinterpret_cast<uintptr_t>(d_x) & 15) == 0) return FDNN_OK;
+  return fail(FDNN_E_ARG, "device frames must start on a 16-byte boundary (include/fdnn.h, Device buffers)");
+}
+
 int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, const ScorePass &p) {
   const BlobHeader &h = m->hm.hdr;
   const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64;

@@ -759,6 +759,7 @@ int fdnn_server_submit_device(fdnn_server *s, const float *d_x, int n, const int
   if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
   if (n <= 0 || n > s->max_frames) return fail(FDNN_E_ARG, "frame count must be in 1..max_frames of the server");
   if (!d_x || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = fdnn::check_frames_aligned(d_x)) return rc;
   DeviceGuard g(s->m->device);
   std::unique_lock<std::mutex> lk(s->mu);
   // next slot in submission order; its previous batch must have completed (that bounds the batches in flight)

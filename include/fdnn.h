@@ -30,6 +30,26 @@
  *     d_masks, d_out) are the caller's to order.
  *   - there is no CPU fallback: without a usable HIP device every entry point
  *     that computes returns FDNN_E_DEVICE.
+ *
+ * Device buffers (every d_* argument; tests/test_gpu_caller_buffers.py holds each line below on guarded buffers)
+ *   The kernels read and write the caller's memory directly.  Extent: exactly the array the entry point documents --
+ *   d_x [n][input_dim], d_raw [n][raw_dim], d_masks [count][output_dim] bytes, d_bits [count][ceil(output_dim / 64)]
+ *   words, d_out [n or count][output_dim] (row 0 of d_out / d_masks / d_bits is frame `first` of the call, not of the
+ *   context), d_row_ptr [count + 1], d_nodes [nnz or len], d_probs [nnz], [count][len] or [n][k], d_inactive [count],
+ *   d_nodes / d_vals of a top-k call [n][k], d_rows [n][width], d_ref / d_q [n][output_dim].  Nothing outside an input's
+ *   extent reaches a result, NOTHING outside an output's extent is written (no padded row of a partial frame tile, no
+ *   padded node of the last node tile), and every element of an output is written.  Inputs are never modified.
+ *   Alignment: the natural alignment of the ELEMENT (4 bytes for fp32 / int32, 1 for mask bytes, 8 for bit words) is all
+ *   any buffer needs -- a slice of a caller's tensor works as it is -- with one exception: d_x of the quantized net
+ *   (fdnn_calculate_device, fdnn_calculate_lazy_bits_device, fdnn_calculate_topk_device, fdnn_ctx_forward_hidden_device,
+ *   fdnn_server_submit_device) must start on a 16-BYTE boundary, because layer 0 moves the frames into LDS in 16-byte
+ *   DMA pieces; input_dim is a multiple of 4, so every row and every sub-range of rows of such a buffer qualifies.  Frames
+ *   that do not are FDNN_E_ARG before anything is launched.  (d_raw and the float net's d_x are read element by element:
+ *   element alignment.)  Some kernels take a faster path where a buffer happens to sit on a 16-byte boundary; results
+ *   are bit-identical wherever it sits.
+ *   Masks: a mask BYTE is active when it is non-zero, whatever the value (1, 0x80, 0xff alike); of a row's last bit word
+ *   only bits 0 .. output_dim % 64 - 1 are looked at when output_dim is no multiple of 64 -- bits past output_dim are
+ *   ignored by every entry point, device or host, and need not be cleared.
  */
 #ifndef FDNN_H
 #define FDNN_H
