@@ -53,7 +53,9 @@ __device__ __forceinline__ void store_wt(void *p, uint32_t v) {
 // float(sum) / (multiplier * 255)   -- dnn.cc:298-299, :311.  The fast form is
 // the Markstein sequence q = x*y, r = fma(-q, c, x), q' = fma(r, y, q) with
 // y = RN(1/c); it is enabled per layer only after launch_fastdiv_check has
-// compared it with IEEE division for every possible accumulator.
+// compared it with IEEE division for every accumulator the layer can produce:
+// the closed range +-(cols_pad / 2) * 32768, each adjacent pair being saturated
+// to int16 (2^26 at K = 4096, 2^29 at the widest layer the loader accepts).
 template <bool FAST>
 __device__ __forceinline__ float dequant(int acc, float coef, float rcp) {
   const float x = static_cast<float>(acc);  // v_cvt_f32_i32, RNE like cvtsi2ss

@@ -175,8 +175,10 @@ __global__ __launch_bounds__(256) void normalize_bg_kernel(const float *out, flo
 }
 
 // ---------------------------------------------------------------- load-time check of the fast division
-__global__ __launch_bounds__(256) void fastdiv_check_kernel(float coef, float rcp, unsigned long long *mismatch) {
-  const long long lo = -(1ll << 26), hi = (1ll << 26);
+// Every accumulator of a layer lies in [-bound, bound], bound = (cols_pad / 2) * 32768: pmaddubsw saturates each of the
+// cols / 2 adjacent pairs to int16 (dnn.cc:337-340).  The closed range is swept, so the verdict covers the layer's own K.
+__global__ __launch_bounds__(256) void fastdiv_check_kernel(float coef, float rcp, long long bound, unsigned long long *mismatch) {
+  const long long lo = -bound, hi = bound;
   unsigned long long bad = 0;
   for (long long a = lo + blockIdx.x * 256ll + threadIdx.x; a <= hi; a += static_cast<long long>(gridDim.x) * 256ll) {
     const float fast = dequant<true>(static_cast<int>(a), coef, rcp);
@@ -364,9 +366,9 @@ void launch_normalize(float *out, float *dst, const float *partial, int n, int p
   hipLaunchKernelGGL(normalize_kernel, dim3(n), dim3(256), 0, s, out, dst, partial, n, partial_ld, rows, n_partial);
 }
 
-void launch_fastdiv_check(float coef, float rcp, unsigned long long *d_mismatch, hipStream_t s) {
+void launch_fastdiv_check(float coef, float rcp, long long bound, unsigned long long *d_mismatch, hipStream_t s) {
   note_launch(kLn_fastdiv_check);
-  hipLaunchKernelGGL(fastdiv_check_kernel, dim3(2048), dim3(256), 0, s, coef, rcp, d_mismatch);
+  hipLaunchKernelGGL(fastdiv_check_kernel, dim3(2048), dim3(256), 0, s, coef, rcp, bound, d_mismatch);
 }
 
 void launch_xor80(const int8_t *in, uint8_t *out, size_t count, hipStream_t s) {

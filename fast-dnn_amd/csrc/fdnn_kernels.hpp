@@ -276,8 +276,10 @@ void launch_normalize(float *out, float *dst, const float *partial, int n, int p
                       bool background = false);
 
 // Exhaustive check of the 3-op division against IEEE division for every int32
-// accumulator in [-2^26, 2^26]; *d_mismatch receives the count.
-void launch_fastdiv_check(float coef, float rcp, unsigned long long *d_mismatch, hipStream_t s);
+// accumulator in the closed range [-bound, bound]; the caller passes the
+// layer's own bound, (cols_pad / 2) * 32768 (each adjacent pair saturates to
+// int16).  *d_mismatch receives the count of accumulators that differ.
+void launch_fastdiv_check(float coef, float rcp, long long bound, unsigned long long *d_mismatch, hipStream_t s);
 
 // s8 <-> u8 view of activations for taps / read-back.
 void launch_xor80(const int8_t *in, uint8_t *out, size_t count, hipStream_t s);

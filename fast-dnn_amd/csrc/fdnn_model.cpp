@@ -322,7 +322,8 @@ int read_raw_model(const std::string &path, RawModel *rm, std::string *msg) {
     L.in_dim = c.i32();
     L.out_dim = c.i32();
     if (!c.ok || L.in_dim <= 0 || L.out_dim <= 0 || L.in_dim > (1 << 20) || L.out_dim > (1 << 19)) {  // (2^19 output nodes = 2048 soft-max tiles of 256: normalize_row's tree)
-      *msg = "bad layer header at layer " + std::to_string(j);
+      *msg = "bad layer header at layer " + std::to_string(j) + ": " + std::to_string(L.in_dim) + " x " + std::to_string(L.out_dim) +
+             "; need 1.." + std::to_string(1 << 20) + " inputs and 1.." + std::to_string(1 << 19) + " outputs";
       return FDNN_E_FORMAT;
     }
     if (j == 0) in_dim_file = L.in_dim;

@@ -58,12 +58,15 @@ int upload_model(fdnn_model *m) {
   HIP_TRY(d_bad.fill(0));
   BlobHeader &h = m->hm.hdr;
   for (int qi = 0; qi < h.n_q; ++qi) {
-    // same coefficient as an earlier layer -> same verdict, skip the sweep
+    // same coefficient as an earlier layer -> same verdict, skip the sweep (every int8 layer has the hidden width for K:
+    // one cols_pad, one range)
     int same = -1;
     for (int pj = 0; pj < qi; ++pj)
       if (h.q[pj].coef == h.q[qi].coef) same = pj;
     if (same >= 0) continue;
-    fdnn::launch_fastdiv_check(h.q[qi].coef, h.q[qi].rcp_coef, d_bad + qi, nullptr);
+    // the layer's own accumulator range: cols_pad / 2 pairs, each saturated to int16 (2^26 at K = 4096, 2^29 at 32 768)
+    const long long acc_bound = static_cast<long long>(h.q[qi].cols_pad / 2) * 32768;
+    fdnn::launch_fastdiv_check(h.q[qi].coef, h.q[qi].rcp_coef, acc_bound, d_bad + qi, nullptr);
   }
   unsigned long long bad[fdnn::kMaxQLayers];
   HIP_TRY(hipMemcpy(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
