@@ -160,6 +160,13 @@ SIGNATURES = {
     "fdnn_debug_topk_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_scratch_count": (C.c_int, []),
+    "fdnn_debug_scratch_name": (C.c_char_p, [C.c_int]),
+    "fdnn_debug_ctx_scratch": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_ctx_scratch_words": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_ctx_scratch_poke": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_uint]),
+    "fdnn_debug_scratch_audit": (C.c_int, [C.c_int]),
+    "fdnn_debug_scratch_dirty": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_profile_begin": (C.c_int, [C.c_void_p]),
     "fdnn_profile_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "fdnn_model_set_splice": (C.c_int, [C.c_void_p, _c_i32p, C.c_int, C.c_int]),
@@ -343,6 +350,32 @@ def launch_counts(nonzero: bool = True) -> dict:
         raise RuntimeError("launch table changed size")
     names = list(launch_names())
     return {names[i]: int(buf[i]) for i in range(n) if buf[i] or not nonzero}
+
+
+def scratch_names() -> tuple:
+    """The self-rewinding scratch buffers of a context, in the library's table order (fdnn_ctx_layout.hpp): counters every
+    launch assumes zero and only the kernels put back to zero.  Needs no device."""
+    L = lib()
+    return tuple(L.fdnn_debug_scratch_name(i).decode() for i in range(L.fdnn_debug_scratch_count()))
+
+
+def scratch_audit(on: bool = True) -> None:
+    """Process-wide, off by default: while on, every context is audited (LazyContext.scratchState's count) when it goes back
+    to its model's pool and when it is destroyed, and the counts add up for scratch_dirty()."""
+    _check(lib().fdnn_debug_scratch_audit(1 if on else 0))
+
+
+def scratch_dirty() -> dict:
+    """Reads and resets the audit's totals -> {buffer name: non-zero words found, ..., "contexts": contexts audited,
+    "unreadable": contexts whose buffers could not be copied, "seconds": what the audits themselves took}."""
+    names = scratch_names()
+    buf = (C.c_ulonglong * (len(names) + 3))()
+    _check(lib().fdnn_debug_scratch_dirty(buf, len(names) + 3))
+    out = {k: int(buf[i]) for i, k in enumerate(names)}
+    out["contexts"] = int(buf[len(names)])
+    out["unreadable"] = int(buf[len(names) + 1])
+    out["seconds"] = int(buf[len(names) + 2]) * 1e-9
+    return out
 
 
 def _lists(rowPtr, nodes):
@@ -715,6 +748,31 @@ class LazyContext:
         _check(lib().fdnn_debug_chain_clocks(self.handle, buf.ctypes.data_as(C.POINTER(C.c_longlong)), int(cap_tasks)))
         k = int(buf[0] & 0xffffffff)
         return buf[8:8 + 10 * min(k, int(cap_tasks))].reshape(-1, 10)
+
+    def calculateOutput(self) -> np.ndarray:
+        """The dense output layer over the context's frames (``fdnn_ctx_output``) -> the soft-max rows [frames][outputDimension]."""
+        out = np.empty((self.inputVectorCount, self.dnn.outputDimension()), dtype=np.float32)
+        _check(lib().fdnn_ctx_output(self.handle, out.ctypes.data_as(_c_f32p)))
+        return out
+
+    def scratchState(self) -> dict:
+        """The scratch audit of this context (``fdnn_debug_ctx_scratch``): waits for its last work -> {buffer name: non-zero
+        words}, every value 0 between launches."""
+        names = scratch_names()
+        buf = (C.c_ulonglong * len(names))()
+        _check(lib().fdnn_debug_ctx_scratch(self.handle, buf, len(names)))
+        return {k: int(buf[i]) for i, k in enumerate(names)}
+
+    def scratchWords(self) -> dict:
+        """{buffer name: its length in 32-bit words}."""
+        names = scratch_names()
+        buf = (C.c_ulonglong * len(names))()
+        _check(lib().fdnn_debug_ctx_scratch_words(self.handle, buf, len(names)))
+        return {k: int(buf[i]) for i, k in enumerate(names)}
+
+    def scratchPoke(self, name: str, index: int, value: int) -> None:
+        """The audit's self-test only: writes one word of a scratch buffer.  Never launch on a context poked non-zero."""
+        _check(lib().fdnn_debug_ctx_scratch_poke(self.handle, scratch_names().index(name), int(index), int(value)))
 
     def hiddenActivations(self) -> np.ndarray:
         out = np.empty((self.inputVectorCount, self.dnn.hiddenDimension()), dtype=np.uint8)

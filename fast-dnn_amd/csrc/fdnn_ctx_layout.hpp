@@ -43,6 +43,32 @@ struct CtxLayout {
   size_t mask_pin, out_pin;    // host-mapped: int8, float
 };
 
+// The self-rewinding scratch: counter arrays that make_ctx zeroes once, that every launch assumes zero
+// on entry and that only the kernels themselves put back to zero before they end.  One row per buffer, 32-bit words each;
+// the scratch audit (fdnn_debug_ctx_scratch, fdnn_runtime.cpp: ctx_scratch_buf) counts non-zero words row by row.
+// kCtxScratchExempt: counter fields of the layout that are NOT self-rewinding, with who zeroes them before their next reader.
+struct CtxScratchRow {
+  const char *name;
+  size_t CtxLayout::*words;
+};
+constexpr int kCtxScratchCount = 5;
+enum CtxScratchId { kScrCount, kFuseCnt, kFuseFlag, kChainCtl, kChainDone };
+inline constexpr CtxScratchRow kCtxScratch[kCtxScratchCount] = {
+    {"scr_count", &CtxLayout::scr_count},    // written fdnn_l0.hip (screened) / fdnn_l0s.hip (whole-tile path); rewound by l0_fix_kernel, l0_fix_list_kernel
+    {"fuse_cnt", &CtxLayout::fuse_cnt},      // fdnn_gemm.hip: the frame tile's last leaver; fdnn_ppo.hip: the half's last gatherer
+    {"fuse_flag", &CtxLayout::fuse_flag},    // fdnn_gemm.hip: lowered by the frame tile's last workgroup
+    {"chain_ctl", &CtxLayout::chain_ctl},    // fdnn_chain.hip: the last workgroup out
+    {"chain_done", &CtxLayout::chain_done},  // fdnn_chain.hip: the last workgroup out
+};
+struct CtxScratchExempt {
+  const char *name;
+  size_t CtxLayout::*words;
+  const char *zeroed_by;
+};
+inline constexpr CtxScratchExempt kCtxScratchExempt[] = {
+    {"glist_count", &CtxLayout::glist_count, "the next launch's pre-pass (fdnn_l0s.hip: l0_digits_kernel), in stream order before the screening kernel"},
+};
+
 inline CtxLayout ctx_layout(const CtxShape &s) {
   CtxLayout l{};
   l.cap = sel::round_up_to(std::max(s.n, 1), 64);

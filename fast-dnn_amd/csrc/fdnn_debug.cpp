@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -44,7 +45,91 @@ int gemm_launch_name(bool output, int shape, int branch) {
 }
 }  // namespace fdnn
 
+// ---- the scratch audit (the table is kCtxScratch, fdnn_ctx_layout.hpp)
+namespace fdnn {
+namespace {
+std::atomic<int> g_scratch_audit_on{0};
+std::atomic<unsigned long long> g_scratch_dirty[kCtxScratchCount];
+std::atomic<unsigned long long> g_scratch_ctxs{0}, g_scratch_errors{0}, g_scratch_ns{0};  // (ns: what the audit itself cost, wait included)
+}  // namespace
+
+int ctx_scratch_dirty(fdnn_ctx *c, unsigned long long *out) {
+  DeviceGuard g(c->m->device);
+  ctx_wait_host(c);
+  const bool chain_faulted = c->h_chain_fault && __atomic_load_n(c->h_chain_fault.p, __ATOMIC_RELAXED) != 0;
+  // a role-split fused launch of this model left a half unwritten (fdnn_ppo.hip: the word's upper half counts them): the node
+  // tiles that gave up never gathered, so the half's two counters were not rewound -- run_output zeroes the array in stream
+  // order before every fused launch from then on
+  const bool ppo_gave_up = c->m->h_fuse_fault && (__atomic_load_n(c->m->h_fuse_fault.p, __ATOMIC_RELAXED) >> 32) != 0;
+  std::vector<uint32_t> host;
+  for (int i = 0; i < kCtxScratchCount; ++i) {
+    out[i] = 0;
+    const ScratchBuf b = ctx_scratch_buf(c, i);
+    if (!b.p || !b.words || (chain_faulted && (i == kChainCtl || i == kChainDone)) || (ppo_gave_up && i == kFuseCnt)) continue;
+    host.resize(b.words);
+    HIP_TRY(hipMemcpy(host.data(), b.p, sizeof(uint32_t) * b.words, hipMemcpyDeviceToHost));
+    out[i] = static_cast<unsigned long long>(std::count_if(host.begin(), host.end(), [](uint32_t w) { return w != 0; }));
+  }
+  return FDNN_OK;
+}
+
+void scratch_audit_event(fdnn_ctx *c) {
+  if (!g_scratch_audit_on.load(std::memory_order_relaxed) || !c || !c->m) return;
+  unsigned long long dirty[kCtxScratchCount];
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = ctx_scratch_dirty(c, dirty);
+  g_scratch_ns.fetch_add(static_cast<unsigned long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count()),
+                         std::memory_order_relaxed);
+  if (rc != FDNN_OK) {  // (a context that cannot be read is not a clean one)
+    g_scratch_errors.fetch_add(1, std::memory_order_relaxed);
+    return;
+  }
+  for (int i = 0; i < kCtxScratchCount; ++i) g_scratch_dirty[i].fetch_add(dirty[i], std::memory_order_relaxed);
+  g_scratch_ctxs.fetch_add(1, std::memory_order_relaxed);
+}
+}  // namespace fdnn
+
 extern "C" {
+
+int fdnn_debug_scratch_count(void) { return kCtxScratchCount; }
+
+const char *fdnn_debug_scratch_name(int index) { return index >= 0 && index < kCtxScratchCount ? kCtxScratch[index].name : nullptr; }
+
+int fdnn_debug_ctx_scratch(fdnn_ctx *c, unsigned long long *out, int n) {
+  if (!c || !out || n < kCtxScratchCount) return fail(FDNN_E_ARG, "bad argument");
+  return ctx_scratch_dirty(c, out);
+}
+
+int fdnn_debug_ctx_scratch_words(fdnn_ctx *c, unsigned long long *out, int n) {
+  if (!c || !out || n < kCtxScratchCount) return fail(FDNN_E_ARG, "bad argument");
+  for (int i = 0; i < kCtxScratchCount; ++i) out[i] = ctx_scratch_buf(c, i).words;
+  return FDNN_OK;
+}
+
+int fdnn_debug_ctx_scratch_poke(fdnn_ctx *c, int which, long long index, unsigned value) {
+  if (!c || which < 0 || which >= kCtxScratchCount) return fail(FDNN_E_ARG, "bad argument");
+  const ScratchBuf b = ctx_scratch_buf(c, which);
+  if (!b.p || index < 0 || static_cast<unsigned long long>(index) >= b.words) return fail(FDNN_E_ARG, "word index outside the buffer");
+  DeviceGuard g(c->m->device);
+  ctx_wait_host(c);
+  const uint32_t v = value;
+  HIP_TRY(hipMemcpy(b.p + index, &v, sizeof(v), hipMemcpyHostToDevice));
+  return FDNN_OK;
+}
+
+int fdnn_debug_scratch_audit(int on) {
+  g_scratch_audit_on.store(on ? 1 : 0, std::memory_order_relaxed);
+  return FDNN_OK;
+}
+
+int fdnn_debug_scratch_dirty(unsigned long long *out, int n) {
+  if (!out || n < kCtxScratchCount + 3) return fail(FDNN_E_ARG, "bad argument");
+  for (int i = 0; i < kCtxScratchCount; ++i) out[i] = g_scratch_dirty[i].exchange(0, std::memory_order_relaxed);
+  out[kCtxScratchCount] = g_scratch_ctxs.exchange(0, std::memory_order_relaxed);
+  out[kCtxScratchCount + 1] = g_scratch_errors.exchange(0, std::memory_order_relaxed);
+  out[kCtxScratchCount + 2] = g_scratch_ns.exchange(0, std::memory_order_relaxed);
+  return FDNN_OK;
+}
 
 int fdnn_debug_set_l0_kernel(fdnn_model *m, int kind) {
   if (!m) return fail(FDNN_E_ARG, "null model");

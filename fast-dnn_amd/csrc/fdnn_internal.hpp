@@ -187,6 +187,19 @@ struct Taps {
 // submissions bring their buffers; the host path allocates what it needs in alloc_host_side)
 int make_ctx(fdnn_model *m, int n, fdnn_ctx **out, bool lean = false);
 void destroy_ctx(fdnn_ctx *c);
+// The scratch audit.  ctx_scratch_buf: row `row` of kCtxScratch (fdnn_ctx_layout.hpp) in this context.
+// ctx_scratch_dirty: waits for the context's last work (ctx_wait_host), copies every row to the host and counts its non-zero
+// words into out[kCtxScratchCount]; the chain rows of a context whose h_chain_fault is raised count as clean (dirty by
+// design: run_hidden re-zeroes them), and so does fuse_cnt once a role-split fused launch of the model has left a half unwritten
+// (run_output zeroes it before every fused launch from then on).  scratch_audit_event: what release_ctx and destroy_ctx -- a scoring-loop slot's
+// teardown among its callers -- do while fdnn_debug_scratch_audit is on: the same count, added to the process's totals.
+struct ScratchBuf {
+  uint32_t *p;
+  size_t words;
+};
+ScratchBuf ctx_scratch_buf(fdnn_ctx *c, int row);
+int ctx_scratch_dirty(fdnn_ctx *c, unsigned long long *out);
+void scratch_audit_event(fdnn_ctx *c);
 int upload_model(fdnn_model *m);    // blob to the device, division check, then build_l0_image
 int build_l0_image(fdnn_model *m);  // the layer-0 weight images and the model's counters, from m->d_blob
 // Layer 0 of the context's n frames into d_act[0] (fdnn_debug_layer0* run it alone).

@@ -156,6 +156,7 @@ void destroy_ctx(fdnn_ctx *c) {
     fuse_chain_retire_stream(c->m->device, c->stream);
     hipStreamSynchronize(c->stream);
   }
+  scratch_audit_event(c);  // (fdnn_debug_scratch_audit: nothing unless switched on)
   if (c->done) hipEventDestroy(c->done);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
@@ -230,6 +231,19 @@ int make_ctx(fdnn_model *m, int n, fdnn_ctx **out, bool lean) {
   }
   *out = c;
   return FDNN_OK;
+}
+
+// Row `row` of the self-rewinding scratch table (kCtxScratch, fdnn_ctx_layout.hpp) in this context: the buffer make_ctx
+// allocated and zeroed for it, all of its words -- not only those some launch reaches.
+ScratchBuf ctx_scratch_buf(fdnn_ctx *c, int row) {
+  switch (row) {
+    case kScrCount: return {c->d_scr_count.p, c->d_scr_count.count};
+    case kFuseCnt: return {c->d_fuse_cnt.p, c->d_fuse_cnt.count};
+    case kFuseFlag: return {c->d_fuse_flag.p, c->d_fuse_flag.count};
+    case kChainCtl: return {c->d_chain_ctl.p, c->d_chain_ctl.count};
+    case kChainDone: return {c->d_chain_done.p, c->d_chain_done.count};
+    default: return {nullptr, 0};
+  }
 }
 
 // one device-side u8 snapshot of the s8 activation buffer (taps only)
@@ -803,6 +817,7 @@ void ctx_wait_host(fdnn_ctx *c) {
 
 void release_ctx(fdnn_ctx *c) {
   fdnn_model *m = c->m;
+  scratch_audit_event(c);  // (before another caller can draw it from the pool; nothing unless switched on)
   fdnn_ctx *victim = nullptr;
   {
     std::lock_guard<std::mutex> lk(m->mu);

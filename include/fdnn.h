@@ -684,6 +684,32 @@ FDNN_API int fdnn_model_chain_faults(fdnn_model *m, unsigned long long *faults);
  * stamps of timing builds from [4]).  Measurements only. */
 FDNN_API int fdnn_debug_device_counters(fdnn_model *m, unsigned long long *out, int n);
 
+/* The scratch audit (tests).  A context carries counter arrays that every launch assumes zero on entry
+ * and that only the kernels put back to zero: the table of them is fdnn_debug_scratch_count entries long, entry `index` is
+ * called fdnn_debug_scratch_name(index) (null outside the table).  All counts below are in table order, n at least the
+ * table's length.
+ * fdnn_debug_ctx_scratch        waits for the context's last work, copies every listed buffer to the host -- all of it, not
+ *                               only the words a launch reaches -- and writes the number of non-zero words per buffer.  A
+ *                               context whose chained launch faulted (fdnn_model_chain_faults) reports its chain counters clean:
+ *                               they are dirty by design until the next hidden pass re-zeroes them.  Likewise the fused
+ *                               soft-max exchange counters once a role-split fused launch of the model has given up
+ *                               (fdnn_model_fuse_giveups): the library zeroes them before every fused launch from then on.
+ * fdnn_debug_ctx_scratch_words  the buffers' lengths in 32-bit words.
+ * fdnn_debug_ctx_scratch_poke   writes one word (the audit's self-test only: never launch on a context poked non-zero).
+ * fdnn_debug_scratch_audit      process-wide, off by default (then nothing changes): while on, every context is counted the
+ *                               same way when it goes back to its model's pool and when it is destroyed -- pooled contexts,
+ *                               the debug entry points' own, a scoring loop's slots -- and the counts are added up.
+ * fdnn_debug_scratch_dirty      reads and resets those totals: out[0 .. count) non-zero words per buffer, out[count] contexts
+ *                               audited, out[count + 1] contexts that could not be read, out[count + 2] the nanoseconds
+ *                               the audits themselves took, their waits included; n at least count + 3. */
+FDNN_API int fdnn_debug_scratch_count(void);
+FDNN_API const char *fdnn_debug_scratch_name(int index);
+FDNN_API int fdnn_debug_ctx_scratch(fdnn_ctx *c, unsigned long long *out, int n);
+FDNN_API int fdnn_debug_ctx_scratch_words(fdnn_ctx *c, unsigned long long *out, int n);
+FDNN_API int fdnn_debug_ctx_scratch_poke(fdnn_ctx *c, int which, long long index, unsigned value);
+FDNN_API int fdnn_debug_scratch_audit(int on);
+FDNN_API int fdnn_debug_scratch_dirty(unsigned long long *out, int n);
+
 /* ------------------------------------------------------------------ per-kernel timing (bench / profiling only)
  * Between begin and end every kernel launch of this model is bracketed by HIP
  * events recorded on the stream it is launched on; end() synchronizes them and

@@ -556,6 +556,56 @@ def _masked_out_ok(got, masks, what):
 
 _MODELS = {}
 LAST_COUNTS = {}   # launches per name of the latest run_case span in this process
+LAST_AUDIT = {}    # the scratch audit of the latest run_case span (api.scratch_dirty()), a child's included
+AUDIT_TOTAL = {"cases": 0, "contexts": 0, "seconds": 0.0}  # over every span judged in this process
+
+
+class ScratchSpan:
+    """The scratch audit over a span of calls on one model: every context that goes back to the pool or
+    is destroyed inside the span -- the entry points' own, the pool's, a scoring loop's slots -- is counted, and close()
+    asserts that none of them held a non-zero counter, that at least one was looked at, and that the model's fault counters
+    stand where they stood.  `dnn` may be None (a span that loads its own model: pass it to close())."""
+
+    def __init__(self, dnn=None):
+        from fast_dnn_amd import api
+
+        api.scratch_dirty()  # (totals of whatever ran before are not this span's)
+        api.scratch_audit(True)
+        self.before = self._counters(dnn) if dnn is not None else (0, 0, 0)
+
+    @staticmethod
+    def _counters(dnn):
+        return dnn.chainFaults(), int(dnn.deviceCounters(4)[3]), dnn.fuseGiveups()
+
+    @staticmethod
+    def stop():
+        """Ends the span without judging it -> the totals."""
+        from fast_dnn_amd import api
+
+        api.scratch_audit(False)
+        return api.scratch_dirty()
+
+    def close(self, what, dnn=None, min_contexts=1):
+        after = self._counters(dnn) if dnn is not None else None
+        check_audit(what, self.stop(), min_contexts)
+        if after is not None:
+            assert after[0] == self.before[0] and after[1] == self.before[1], \
+                f"{what}: chained launches ran into their wait bound: chainFaults {self.before[0]} -> {after[0]}, device counter [3] {self.before[1]} -> {after[1]}"
+            assert after[2] == self.before[2], f"{what}: fused soft-max tiles gave up waiting: fuseGiveups {self.before[2]} -> {after[2]}"
+
+
+def check_audit(what, totals, min_contexts=1):
+    from fast_dnn_amd import api
+
+    LAST_AUDIT.clear()
+    LAST_AUDIT.update(totals)
+    AUDIT_TOTAL["cases"] += 1
+    AUDIT_TOTAL["contexts"] += totals["contexts"]
+    AUDIT_TOTAL["seconds"] += totals.get("seconds", 0.0)
+    dirty = {k: totals[k] for k in api.scratch_names() if totals[k]}
+    assert not dirty, f"{what}: scratch audit: counters left non-zero after their launch (buffer: words) {dirty} over {totals['contexts']} contexts"
+    assert totals["unreadable"] == 0, f"{what}: scratch audit: {totals['unreadable']} contexts could not be read"
+    assert totals["contexts"] >= min_contexts, f"{what}: scratch audit looked at {totals['contexts']} contexts (at least {min_contexts} expected): the check is blind"
 CHILD_COUNTS = {}  # case id -> launches per name of a span that ran in a child process (the parent's recorder does not see them)
 
 
@@ -603,14 +653,19 @@ def run_case(case, detail=None):
     dnn.setInputLayerKernel(case.l0_kernel)
     dnn.setInputLayerFma(case.fma)
     Oracle.set_l0_fma(case.fma)
+    span = None
     try:
         gen = F.generate_masks_fast if n * O > (1 << 24) else F.generate_masks  # (same statistics; the per-frame Python loop costs seconds there)
         masks = gen(n, O, 0.40, 0.03, seed=7 + n % 89) if case.entry not in ("taps", "l0", "l0_probe", "dense_host", "dense_device", "server", "raw") else None
+        span = ScratchSpan(dnn)
         api.launch_reset()
         got = _ENTRIES[case.entry](case, dnn, x, masks)
         LAST_COUNTS.clear()
         LAST_COUNTS.update(api.launch_counts())
         names = set(LAST_COUNTS)
+        # ---- every context the span used left its counters as it found them (the entries delete or release theirs)
+        closing, span = span, None
+        closing.close(case.id, dnn)
         # ---- the oracle, on the rows the case compares
         xs = x[idx]
         if detail is not None:
@@ -651,6 +706,8 @@ def run_case(case, detail=None):
             _masked_out_ok(got["lazy"][idx], masks[idx], case.id)
         return names
     finally:
+        if span is not None:
+            span.stop()
         api.set_fuse(-1)
         api.set_chain(-1)
         api.set_pp(-1)
@@ -782,6 +839,7 @@ def _run_load(case):
     want_blob = host.blob().copy()
     host.close()
     src = None
+    span = ScratchSpan()  # (the load itself makes no context: the span runs on over the checks below, which make several)
     api.launch_reset()
     if case.entry == "blob":
         src = api.QuantizedDnn.loadFromFile(p, device=0)
@@ -818,7 +876,9 @@ def _run_load(case):
         t, ran = launched(dnn.forwardTaps, x[:64])
         assert not any(".tdiv." in k for k in ran) and {"small.hid.nt32.tap", "small.out.tap"} <= ran, f"{case.id}: the load's division verdict sends this net to {sorted(ran)}"
         assert np.array_equal(t["acc_out"], wt["acc_out"][:64]) and np.array_equal(t["acc_hid"], wt["acc_hid"][:, :64])
+        span.close(case.id, dnn)  # (a model of this span: its fault counters started at zero)
     finally:
+        span.stop()
         api.launch_record(True)
         dnn.delete()
         if src is not None:
@@ -837,6 +897,7 @@ def run_case_in_child(case, timeout=600):
     res = json.loads(line)
     assert res["id"] == case.id and res["ok"], res
     CHILD_COUNTS[case.id] = {k: int(v) for k, v in res["counts"].items()}
+    check_audit(case.id + " (child)", res["audit"])
     return set(res["names"])
 
 
@@ -851,9 +912,9 @@ if __name__ == "__main__":
     for cid in sys.argv[2:]:
         try:
             got = run_case(by_id(cid))
-            print(json.dumps({"id": cid, "ok": True, "names": sorted(got), "counts": dict(LAST_COUNTS)}), flush=True)
+            print(json.dumps({"id": cid, "ok": True, "names": sorted(got), "counts": dict(LAST_COUNTS), "audit": dict(LAST_AUDIT)}), flush=True)
         except AssertionError as e:
-            print(json.dumps({"id": cid, "ok": False, "names": [], "counts": {}, "error": str(e)}), flush=True)
+            print(json.dumps({"id": cid, "ok": False, "names": [], "counts": {}, "audit": dict(LAST_AUDIT), "error": str(e)}), flush=True)
             rc = 1
     release_models()
     sys.exit(rc)

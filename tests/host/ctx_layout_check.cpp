@@ -283,11 +283,56 @@ void check_cover() {
   }
 }
 
+// The scratch audit's table (kCtxScratch) against the layout: every counter field of CtxLayout -- the uint32 arrays make_ctx
+// zeroes -- has a row in the table or an entry, with its reason, in the exemption list, and none has both; rows name distinct
+// fields, and their word counts are the layout's for every shape.  sizeof(CtxLayout) pins the field list: whoever adds a
+// field decides here whether it is a counter.  --names prints the table's names (tests/test_ctx_layout_host.py compares them
+// with the library's).
+void check_scratch_table(bool print) {
+  static_assert(sizeof(CtxLayout) == 4 * sizeof(int) + 20 * sizeof(size_t), "CtxLayout changed: is the new field a counter array? (kCounters below)");
+  size_t CtxLayout::*const kCounters[] = {&CtxLayout::scr_count, &CtxLayout::glist_count, &CtxLayout::fuse_cnt, &CtxLayout::fuse_flag,
+                                          &CtxLayout::chain_ctl, &CtxLayout::chain_done};
+  for (auto f : kCounters) {
+    int rows = 0, exempt = 0;
+    for (const CtxScratchRow &r : kCtxScratch) rows += r.words == f;
+    for (const CtxScratchExempt &e : kCtxScratchExempt) exempt += e.words == f;
+    CHECK(rows + exempt == 1);
+  }
+  int listed = 0;
+  for (const CtxScratchRow &r : kCtxScratch) {
+    CHECK(r.name && r.name[0]);
+    bool known = false;
+    for (auto f : kCounters) known = known || r.words == f;
+    CHECK(known);
+    for (const CtxScratchRow &o : kCtxScratch) CHECK(&o == &r || (o.words != r.words && std::strcmp(o.name, r.name) != 0));
+    if (print) std::printf("%s%s", listed ? " " : "", r.name);
+    ++listed;
+  }
+  if (print) std::printf("\n");
+  for (const CtxScratchExempt &e : kCtxScratchExempt) CHECK(e.name && e.name[0] && e.zeroed_by && e.zeroed_by[0]);
+  CHECK(listed == kCtxScratchCount && sizeof(kCounters) / sizeof(kCounters[0]) == kCtxScratchCount + sizeof(kCtxScratchExempt) / sizeof(kCtxScratchExempt[0]));
+  CHECK(kCtxScratch[kScrCount].words == &CtxLayout::scr_count && kCtxScratch[kFuseCnt].words == &CtxLayout::fuse_cnt &&
+        kCtxScratch[kFuseFlag].words == &CtxLayout::fuse_flag && kCtxScratch[kChainCtl].words == &CtxLayout::chain_ctl &&
+        kCtxScratch[kChainDone].words == &CtxLayout::chain_done);
+  // every listed buffer exists (non-empty) in every context, lean or not: the audit reads all of them
+  for (const Net &net : kNets)
+    for (int lean = 0; lean < 2; ++lean)
+      for (int n : kTableFrames) {
+        const CtxLayout l = ctx_layout(shape_of(net, n, lean != 0, 64, 0));
+        for (const CtxScratchRow &r : kCtxScratch) CHECK(l.*(r.words) > 0);
+      }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+  if (argc == 2 && std::strcmp(argv[1], "--names") == 0) {
+    check_scratch_table(true);
+    return 0;
+  }
   CHECK(argc == 2 || (argc == 4 && std::strcmp(argv[2], "--seed") == 0));
   if (argc == 4) g_seed = std::atoi(argv[3]);
+  check_scratch_table(false);
   if (!g_seed) check_table(argv[1]);
   check_cover();
   std::printf("ctx layout ok: %ld launch cases\n", g_cases);

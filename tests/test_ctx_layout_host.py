@@ -46,3 +46,18 @@ def test_chain_counter_slack_tiles_are_not_load_bearing(checker):
     argument is in ctx_layout_check.cpp), so the check passes: the sizing keeps them as slack, it does not rely on them."""
     run = subprocess.run([checker, TABLE, "--seed", "3"], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
+
+
+SCRATCH_NAMES = ("scr_count", "fuse_cnt", "fuse_flag", "chain_ctl", "chain_done")
+
+
+def test_every_counter_field_has_a_row_in_the_scratch_table(checker):
+    """The scratch audit's table (kCtxScratch, fdnn_ctx_layout.hpp): the checker holds that every counter field of CtxLayout is
+    either a row of it or an exemption with its reason (it runs with every invocation above as well); the names it prints
+    are the five self-rewinding buffers, and the built library reports the same table (no device needed)."""
+    from fast_dnn_amd import api
+
+    run = subprocess.run([checker, "--names"], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert tuple(run.stdout.split()) == SCRATCH_NAMES
+    assert api.scratch_names() == SCRATCH_NAMES

@@ -374,23 +374,32 @@ def test_fused_softmax_equals_the_scale_pass_and_its_give_up_path(net_model_path
     (FDNN_GEMM_DEBUG=4096): the in-phase tiles (the masked call here) store that part of exp(z) unscaled and their frame tile's
     last workgroup finishes them; the role-split dense kernel (fdnn_ppo.hip: the dense call here) leaves its half's rows
     unwritten, raises the model's fault word, and fdnn_calculate runs the output layer again, unfused.  Whichever call comes
-    first in a process meets the give-up (after it the model does not fuse any more): both orders."""
-    import subprocess, sys
+    first in a process meets the give-up (after it the model does not fuse any more): both orders.
+
+    Every child also runs the scratch audit over its contexts: after a pass in which in-phase tiles
+    gave up, the give-up flags and the exchange counters are zero again -- fdnn_gemm.hip's "nothing is left for a second
+    launch" -- on the lazy call's own context (AUDIT_CTX, read before anything else runs on the model in the lazy-first
+    order) and over every context of the process (AUDIT).  The role-split kernel's give-up leaves its half's two counters
+    unrewound by design (run_output zeroes the array before every later fused launch): the audit exempts fuse_cnt from then
+    on, and nothing else."""
+    import json, subprocess, sys
 
     code = f"""
-import sys, numpy as np
+import json, sys, numpy as np
 sys.path.insert(0, {os.path.dirname(os.path.dirname(os.path.abspath(__file__)))!r})
 from fast_dnn_amd import api, formats as F
 x = F.synth_features(10000, 432, seed=41)
 masks = F.generate_masks_fast(10000, 8000, 0.40, 0.03, seed=3)
 dnn = api.QuantizedDnn.loadFromFile({net_model_path!r})
 api.launch_record(True)
+api.scratch_audit(True)
 def dense():
     return dnn.calculate(x)
 def lazy():
     ctx = dnn.getNewLazyContext(10000)
     ctx.calculateUntilOutput(x)
     q_ = ctx.calculateForOutputNodesBatch(masks)
+    print("AUDIT_CTX", json.dumps(ctx.scratchState()))
     ctx.delete()
     return q_
 if sys.argv[2] == "dense-first":
@@ -399,6 +408,9 @@ else:
     q = lazy(); p = dense()
 print("GIVEUPS", dnn.fuseGiveups())
 print("RAN", " ".join(sorted(api.launch_counts())))
+print("FAULTS", dnn.chainFaults())
+api.scratch_audit(False)
+print("AUDIT", json.dumps(api.scratch_dirty()))
 dnn.delete()
 np.save(sys.argv[1], np.concatenate([p[::7], q[::7]]))
 """
@@ -415,6 +427,13 @@ np.save(sys.argv[1], np.concatenate([p[::7], q[::7]]))
         assert (gave_up > 0) == tag.startswith("giveup"), (tag, gave_up)
         if tag.startswith("giveup"):
             assert r.stderr.count("sat out its bounded wait") == 1
+        # the scratch audit: the lazy call's context, then every context the child released or destroyed
+        audit_ctx = json.loads(r.stdout.split("AUDIT_CTX")[1].split("\n")[0])
+        audit = json.loads(r.stdout.split("AUDIT ")[1].split("\n")[0])
+        assert set(audit_ctx) == set(api.scratch_names()) and not any(audit_ctx.values()), f"{tag}: the lazy call left counters non-zero on its context: {audit_ctx}"
+        assert not any(audit[k] for k in api.scratch_names()), f"{tag}: scratch audit: counters left non-zero (buffer: words) {audit}"
+        assert audit["contexts"] >= 2 and audit["unreadable"] == 0, f"{tag}: the audit looked at {audit['contexts']} contexts: {audit}"
+        assert int(r.stdout.split("FAULTS")[1].split()[0]) == 0, f"{tag}: a chained launch ran into its wait bound"
         # each side ran what its tag says: the fused instances (dense: the role-split kernel) without a scale pass, or
         # the plain / masked instances followed by the scale pass
         ran = set(r.stdout.split("RAN")[1].split("\n")[0].split())
