@@ -16,6 +16,7 @@
 #include "fdnn_lists.hpp"
 
 using namespace fdnn;
+using fdnn::pass::Pass;
 
 namespace fdnn {
 
@@ -29,7 +30,7 @@ int calculate_on_one_device(fdnn_model *m, const float *x, int n, int dim, int b
     uint64_t ticket = 0;
     return batcher_wait(m->batcher, fdnn_server_submit(m->batcher, x, n, nullptr, out, &ticket), &ticket);
   }
-  return score_chunks(m, {{0, n}}, {.who = "fdnn_calculate", .x = x, .out = out});
+  return score_chunks(m, {{0, n}}, Pass::host_dense("fdnn_calculate", x, out));
 }
 
 int calculate_raw_rows(fdnn_model *m, const SpliceRef &spec, const float *raw, int n, int a, int b, float *out) {
@@ -41,8 +42,7 @@ int calculate_raw_rows(fdnn_model *m, const SpliceRef &spec, const float *raw, i
   int fa, fb;  // the raw frames those rows reference travel once
   splice_halo(*spec, n, a, b, &fa, &fb);
   const std::vector<SpliceSeg> segs{SpliceSeg{a, a - fa, -fa, n - 1 - fa}};
-  return score_chunks(m, frame_chunks(b - a, m),
-                      {.who = "fdnn_calculate_raw", .spec = spec.get(), .segs = &segs, .raw = raw + size_t(fa) * size_t(spec->raw_dim), .raw_frames = fb - fa, .row0 = a, .out = out});
+  return score_chunks(m, frame_chunks(b - a, m), Pass::raw_dense("fdnn_calculate_raw", {spec.get(), &segs, raw + size_t(fa) * size_t(spec->raw_dim), fb - fa, a}, out));
 }
 
 }  // namespace fdnn
@@ -457,7 +457,7 @@ int fdnn_calculate_lazy_lists(fdnn_model *m, const float *x, int n, int dim, con
   if (int rc = check_input_width(m, dim)) return rc;
   if (int rc = lists_validate(row_ptr, nodes, n, m->hm.hdr.out_dim)) return rc;
   if (row_ptr[n] > 0 && !probs) return fail(FDNN_E_ARG, "null buffer");
-  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_lazy_lists", .x = x, .row_ptr = row_ptr, .nodes = nodes, .probs = probs, .inactive = inactive});
+  return score_chunks(m, frame_chunks(n, m), Pass::host_lists("fdnn_calculate_lazy_lists", x, row_ptr, nodes, probs, inactive));
 }
 
 // ---------------------------------------------------------------- lazy output for a shared node set (fdnn_set.hip)
@@ -519,8 +519,7 @@ int fdnn_calculate_lazy_set(fdnn_model *m, const float *x, int n, int dim, const
   if (n == 0) return FDNN_OK;
   if (!x || !inactive || (len > 0 && !probs)) return fail(FDNN_E_ARG, "null buffer");
   if (int rc = check_input_width(m, dim)) return rc;
-  return score_chunks(m, frame_chunks(n, m),
-                      {.who = "fdnn_calculate_lazy_set", .x = x, .probs = probs, .inactive = inactive, .set_nodes = nodes, .set_len = len, .set_given = true});
+  return score_chunks(m, frame_chunks(n, m), Pass::host_set("fdnn_calculate_lazy_set", x, nodes, len, probs, inactive));
 }
 
 // ---------------------------------------------------------------- lazy output for per-segment node sets (fdnn_sets.hip)
@@ -602,7 +601,7 @@ int fdnn_calculate_lazy_sets(fdnn_model *m, const float *x, int n, int dim, cons
   if (nnz > INT32_MAX) return fail(FDNN_E_ARG, "the sum of rows x len over the segments must fit an int32");
   if (!x || !inactive || (nnz > 0 && !probs)) return fail(FDNN_E_ARG, "null buffer");
   if (int rc = check_input_width(m, dim)) return rc;
-  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_lazy_sets", .x = x, .nodes = nodes, .probs = probs, .inactive = inactive, .sets = &t});
+  return score_chunks(m, frame_chunks(n, m), Pass::host_sets("fdnn_calculate_lazy_sets", x, t, nodes, probs, inactive));
 }
 
 int fdnn_ctx_lazy_output(fdnn_ctx *c, int frame, const int8_t *mask, float *out) {
@@ -681,7 +680,7 @@ int fdnn_calculate_topk(fdnn_model *m, const float *x, int n, int dim, int k, in
   if (n == 0) return FDNN_OK;
   if (!x || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
   if (int rc = check_input_width(m, dim)) return rc;
-  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_topk", .x = x, .topk_k = k, .topk_nodes = nodes, .topk_probs = probs});
+  return score_chunks(m, frame_chunks(n, m), Pass::host_topk("fdnn_calculate_topk", x, k, nodes, probs));
 }
 
 int fdnn_calculate_topk_raw(fdnn_model *m, const float *raw, int n, int raw_dim, int k, int32_t *nodes, float *probs) {
@@ -692,8 +691,7 @@ int fdnn_calculate_topk_raw(fdnn_model *m, const float *raw, int n, int raw_dim,
   if (n == 0) return FDNN_OK;
   if (!raw || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
   const std::vector<SpliceSeg> segs{SpliceSeg{0, 0, 0, n - 1}};  // (the whole utterance's raw frames travel once, as fdnn_calculate_raw's)
-  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_topk_raw", .spec = spec.get(), .segs = &segs, .raw = raw, .raw_frames = n,
-                                             .topk_k = k, .topk_nodes = nodes, .topk_probs = probs});
+  return score_chunks(m, frame_chunks(n, m), Pass::raw_topk("fdnn_calculate_topk_raw", {spec.get(), &segs, raw, n}, k, nodes, probs));
 }
 
 int fdnn_calculate_topk_device(fdnn_model *m, const float *d_x, int n, int k, int32_t *d_nodes, float *d_probs, void *stream) {
@@ -702,8 +700,7 @@ int fdnn_calculate_topk_device(fdnn_model *m, const float *d_x, int n, int k, in
   if (n == 0) return FDNN_OK;
   if (!d_x || !d_nodes || !d_probs) return fail(FDNN_E_ARG, "null buffer");
   if (int rc = check_frames_aligned(d_x)) return rc;
-  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_topk_device", .d_x = d_x, .stream = static_cast<hipStream_t>(stream), .topk_k = k,
-                                             .d_topk_nodes = d_nodes, .d_topk_probs = d_probs});
+  return score_chunks(m, frame_chunks(n, m), Pass::device_topk("fdnn_calculate_topk_device", d_x, k, d_nodes, d_probs), static_cast<hipStream_t>(stream));
 }
 
 int fdnn_debug_topk_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 2, fdnn::topk_launch_counts); }
@@ -749,7 +746,7 @@ int fdnn_calculate_device(fdnn_model *m, const float *d_x, int n, float *d_out, 
   if (n == 0) return FDNN_OK;
   if (!d_x || !d_out) return fail(FDNN_E_ARG, "null buffer");
   if (int rc = check_frames_aligned(d_x)) return rc;
-  return score_chunks(m, frame_chunks(n, m), {.who = "fdnn_calculate_device", .d_x = d_x, .d_out = d_out, .stream = static_cast<hipStream_t>(stream)});
+  return score_chunks(m, frame_chunks(n, m), Pass::device_dense("fdnn_calculate_device", d_x, d_out), static_cast<hipStream_t>(stream));
 }
 
 int fdnn_calculate(fdnn_model *m, const float *x, int n, int dim, int batch_hint, float *out) {
@@ -772,7 +769,7 @@ int fdnn_calculate_lazy_bits(fdnn_model *m, const float *x, int n, int dim, cons
     return batcher_wait(m->batcher, fdnn_server_submit_lazy_bits(m->batcher, x, n, bits, out, &ticket), &ticket);
   }
   // (very large calls: chunk by chunk, as the dense call)
-  return score_chunks(m, stride_chunks(n), {.who = "fdnn_calculate_lazy_bits", .x = x, .bits = bits, .out = out});
+  return score_chunks(m, fdnn::pass::stride_chunks(n), Pass::host_bits("fdnn_calculate_lazy_bits", x, bits, out));
 }
 
 int fdnn_calculate_lazy(fdnn_model *m, const float *x, int n, int dim, const int8_t *masks, float *out) {
@@ -790,8 +787,7 @@ int fdnn_calculate_lazy_bits_device(fdnn_model *m, const float *d_x, int n, cons
   if (n == 0) return FDNN_OK;
   if (!d_x || !d_out || !d_bits) return fail(FDNN_E_ARG, "null buffer");
   if (int rc = check_frames_aligned(d_x)) return rc;
-  return score_chunks(m, frame_chunks(n, m),
-                      {.who = "fdnn_calculate_lazy_bits_device", .d_x = d_x, .d_bits = d_bits, .d_out = d_out, .stream = static_cast<hipStream_t>(stream)});
+  return score_chunks(m, frame_chunks(n, m), Pass::device_bits("fdnn_calculate_lazy_bits_device", d_x, d_bits, d_out), static_cast<hipStream_t>(stream));
 }
 
 // ---------------------------------------------------------------- raw feature frames (the <Splice> block on the device)
@@ -864,8 +860,7 @@ int fdnn_calculate_raw_device(fdnn_model *m, const float *d_raw, int n, const in
     }
   }
   // each chunk's rows spliced into the context's frame buffer, then scored as usual
-  return score_chunks(m, frame_chunks(n, m),
-                      {.who = "fdnn_calculate_raw_device", .spec = spec.get(), .segs = &segs, .d_raw = d_raw, .raw_frames = n, .d_out = d_out, .stream = static_cast<hipStream_t>(stream)});
+  return score_chunks(m, frame_chunks(n, m), Pass::raw_device_dense("fdnn_calculate_raw_device", {spec.get(), &segs, d_raw, n}, d_out), static_cast<hipStream_t>(stream));
 }
 
 int fdnn_calculate_lazy_bits_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const uint64_t *bits, float *out) {
@@ -880,8 +875,8 @@ int fdnn_calculate_lazy_bits_raw(fdnn_model *m, const float *raw, int n, int raw
     return batcher_wait(m->batcher, server_submit_raw_rows(m->batcher, spec, raw, n, 0, n, bits, out, &ticket), &ticket);
   }
   const std::vector<SpliceSeg> segs{SpliceSeg{0, 0, 0, n - 1}};
-  return score_chunks(m, stride_chunks(n),  // (chunks as fdnn_calculate_lazy_bits)
-                      {.who = "fdnn_calculate_lazy_bits_raw", .spec = spec.get(), .segs = &segs, .raw = raw, .raw_frames = n, .bits = bits, .out = out});
+  return score_chunks(m, fdnn::pass::stride_chunks(n),  // (chunks as fdnn_calculate_lazy_bits)
+                      Pass::raw_bits("fdnn_calculate_lazy_bits_raw", {spec.get(), &segs, raw, n}, bits, out));
 }
 
 int fdnn_ctx_forward_hidden_raw(fdnn_ctx *c, const float *raw) {

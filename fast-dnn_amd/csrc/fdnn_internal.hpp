@@ -17,6 +17,7 @@
 #include "fdnn_buf.hpp"
 #include "fdnn_kernels.hpp"
 #include "fdnn_model.hpp"
+#include "fdnn_pass.hpp"
 #include "fdnn_splice_spec.hpp"  // SpliceSpec, SpliceRef, SpliceSeg, splice_halo
 
 namespace fdnn {
@@ -94,7 +95,7 @@ struct fdnn_ctx {
   bool done_valid = false;
   bool done_pending = false;      // work went to done_stream -- a stream that outlives this context's use of it (see
                                   // stream_is_durable) -- after the last record: recorded when ANOTHER stream asks (ctx_enter)
-  hipStream_t durable[3] = {nullptr, nullptr, nullptr};  // streams of the context's owner (the scoring loop's), besides `stream`
+  hipStream_t durable[2] = {nullptr, nullptr};  // streams of the context's owner (the scoring loop's), besides `stream`
   fdnn::DevBuf<float> d_x;        // [n][D]
   fdnn::DevBuf<float> d_raw;      // raw feature frames of the *_raw entry points (first raw call allocates)
   fdnn::DevBuf<float> d_xt;       // [4][l0_j_pad][xt_ld] layer-0 frame image (shifted, scaled, chain-major)
@@ -138,9 +139,6 @@ struct fdnn_ctx {
   int last = -1;                 // d_act index holding the last hidden layer, -1 = not computed
   bool pooled = false;
   bool no_fuse = false;           // this call must not use the fused soft-max
-  bool l0_chain_only = false;     // scoring loop, large batches: the soft-max scale of the previous batch runs under this
-                                  // batch's layer 0, which must then be the vector-pipe chain kernel (the matrix-pipe
-                                  // screened path fills the register file: nothing can run beside it)
   // per-frame lazy calls (the JNI contract): host-mapped pinned staging for kPinFrames masks and
   // result rows -- the output kernel reads the mask and the scale kernel writes the probabilities
   // straight through these, so a call is two launches and one stream sync, no copy commands
@@ -217,8 +215,6 @@ struct OutputCall {
                                       // small ones unpack them into the context's byte mask first
   float *d_out = nullptr;             // [count][O]: exp(z) rows, scaled in place unless d_final says otherwise
   float *d_final = nullptr;           // where the probabilities go (null: in place in d_out)
-  hipStream_t tail = nullptr;         // with gemm_done: the scale pass goes to this stream, behind that event recorded on
-  hipEvent_t gemm_done = nullptr;     // s, so that the HBM-bound pass can run under the next batch's layer 0
   const Taps *taps = nullptr;
 };
 int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s);
@@ -280,9 +276,6 @@ int entries_to_host(fdnn_ctx *c, const HostEntries &h, hipStream_t s);
 UnionParams union_params(const lunion::Layout &l, int32_t *b, const ListsCall &lc, int rows, int group_tiles);
 int build_lists_index(fdnn_model *m);  // the per-node pair index of the output layer, from m->hm (model load / blob import)
 int device_cus(int device);            // CUs of a device, asked once (256 where the runtime cannot say)
-// Will run_output scale the soft-max inside the output kernel for such a call (dense, large batch)?  Then there is no
-// scale pass to hide under the next batch's layer 0.
-bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks);
 // Device -> pageable host memory, pre-faulting large destinations; synchronises s.
 int copy_out(void *dst, const void *d_src, size_t bytes, hipStream_t s);
 // The dense pass over the context's frames in c->d_x (c->n of them) into the host's `out`, synchronising s; re-runs what a
@@ -306,21 +299,11 @@ int lazy_copy_out(fdnn_ctx *c, int count, const uint64_t *d_bits, const uint64_t
 void lazy_expand_rows(float *out, int count, size_t O, size_t stride, const uint64_t *bits);
 void lazy_expand_rows_from(float *out, const float *comp, int count, size_t O, size_t stride, const uint64_t *bits);  // rows in a buffer of their own
 void lazy_expand_force_scalar(bool on);  // fdnn_debug_lazy_expand: the scalar expansion where AVX-512 would be used
-// A pass over a very large batch runs as chunks (frames are independent: a chunk is a batch of its own, and the scratch
-// context only has to hold one).  kRoundFrames = 32 frame tiles of 320 = one workgroup per CU in the 2048-wide hidden
-// layers; a chunk is two rounds.  Measured, 125 000 frames (the 8-GPU shard of BASELINE configs[4]), fused soft-max:
-// 12.09 M frames/s as one batch (4 GB of result rows, 512 MB of activations per layer: the address-translation and Infinity
-// caches stop covering the working set), 12.87 M in chunks of one round, 13.14 M in chunks of two (tools/chunk_bench.py).
-// Returns (offset, count) pairs: chunks of kChunkFrames, then what is left as one more batch.  (Up to round 4 a small tail
-// past a whole round was always split off as a batch of its own; with chained hidden layers that is unnecessary: frame_chunks.)
-constexpr int kRoundFrames = 10240;
-constexpr int kChunkFrames = 2 * kRoundFrames;
-constexpr int kChunkTailSplit = 2048;
-// With a model: a chunk whose hidden layers will not run as one chained launch (hidden_layers_chain) gives up to
-// kChunkTailSplit frames past a whole round away as a batch of their own.  Without: as assume_chained says.
-std::vector<std::pair<int, int>> frame_chunks(int n, const fdnn_model *m = nullptr, bool assume_chained = true);
+// The chunks of an n-frame pass (fdnn_pass.hpp: pass::frame_chunks).  With a model: a chunk whose hidden layers will not run as
+// one chained launch (hidden_layers_chain) gives up to kChunkTailSplit frames past a whole round away as a batch of their own.
+// Without: as assume_chained says (fdnn_debug_frame_chunks_for).
+pass::Chunks frame_chunks(int n, const fdnn_model *m = nullptr, bool assume_chained = true);
 bool hidden_layers_chain(const fdnn_model *m, int n);
-std::vector<std::pair<int, int>> stride_chunks(int n);  // kChunkFrames strides, no tail split: the host lazy forms
 // "input vector size ... must be equal with network input size ..." (QuantizedDnn.java:157-161)
 int check_input_width(const fdnn_model *m, int dim);
 // A caller's device frames [n][in_dim] must start on a 16-byte boundary: layer 0 reads them as 16-byte LDS-DMA pieces
@@ -359,47 +342,14 @@ int group_calculate_raw(fdnn_group *g, const SpliceRef &spec, const float *raw, 
 int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *raw, int n, int a, int b, const uint64_t *bits,
                            float *out, uint64_t *ticket);
 
-// ---------------------------------------------------------------- one scoring pass for every pooled entry point
-// Hidden + output layers over `chunks` ((offset, count) pairs of the call's rows) on ONE pooled context, large enough for
-// the largest chunk, and one stream.  The struct says where the rows come from, which mask applies and where the results
-// go; one of each group, the rest null.  Pointers are to the call's row 0: the pass adds the chunk's offset.
-struct ScorePass {
-  const char *who = "";  // the entry point's name, for the text of a device error
-  // rows: as they are on the device, from the host (uploaded chunk by chunk), or raw frames spliced chunk by chunk into
-  // the context's frame buffer -- raw frames on the device, or on the host (uploaded once, before the first chunk)
-  const float *d_x = nullptr;
-  const float *x = nullptr;
-  const SpliceSpec *spec = nullptr;
-  const std::vector<SpliceSeg> *segs = nullptr;
-  const float *d_raw = nullptr, *raw = nullptr;
-  int raw_frames = 0;  // frames in the raw buffer
-  int row0 = 0;        // the splice row of the call's row 0
-  // mask: none, bits on the device, or bits on the host (uploaded chunk by chunk)
-  const uint64_t *d_bits = nullptr, *bits = nullptr;
-  // lists instead of a mask (host rows only): the call's row_ptr [n + 1] and nodes; results probs [nnz], inactive [n]
-  const int32_t *row_ptr = nullptr, *nodes = nullptr;
-  float *probs = nullptr, *inactive = nullptr;
-  // or one node set for every row (host rows only): set_given, set_nodes [set_len] (null for an empty set); results
-  // probs [n][set_len], inactive [n]
-  const int32_t *set_nodes = nullptr;
-  int set_len = 0;
-  bool set_given = false;
-  // or one node set per segment of the rows (host rows only): the call's tables, seg_rows covering [0, n), and all nodes;
-  // results probs (ragged blocks), inactive [n]
-  const fdnn::sets::Tables *sets = nullptr;
-  // results: device rows, enqueued on `stream` (the caller's) -- or host rows on the context's own stream, synchronised:
-  // dense through dense_pass_to_host and its re-run rules, with host bits through lazy_copy_out
-  float *d_out = nullptr;
-  hipStream_t stream = nullptr;
-  float *out = nullptr;
-  // or, of a dense pass, the topk_k first-ranked nodes of every row and their values, [n][topk_k] each (fdnn_topk.hip):
-  // to the host through dense_pass and its re-run rules (the rows never leave the device), or device buffers enqueued on
-  // `stream` (then the rows come from d_x)
-  int topk_k = 0;
-  int32_t *topk_nodes = nullptr, *d_topk_nodes = nullptr;
-  float *topk_probs = nullptr, *d_topk_probs = nullptr;
-};
-int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, const ScorePass &p);
+// ---------------------------------------------------------------- one scoring pass, one chunk loop
+// Hidden layers + what the pass's sink asks for, chunk by chunk, on context c and stream s; every pointer a chunk uses comes
+// from pass::chunk_view.  Per chunk: the rows in (spliced / uploaded / as they are), host bits up, the hidden layers, the sink's
+// step.  Host sinks synchronise s per chunk (also when they fail).  c->n is left at the last chunk's count.
+int run_chunks(fdnn_ctx *c, hipStream_t s, const pass::Chunks &chunks, const pass::Pass &p);
+// The pooled entry points: ONE pooled context, large enough for the largest chunk; the stream is the caller's where the
+// sink is on the device (pass::on_callers_stream), else the context's own; host raw frames travel once, before the loop.
+int score_chunks(fdnn_model *m, const pass::Chunks &chunks, const pass::Pass &p, hipStream_t callers = nullptr);
 
 // Ordering between the streams a context is used on.  An event record costs 3-4 us of queue time behind the kernel it
 // follows, so a context whose work went to a stream that is certain to exist later -- its own, its owner's, or the null

@@ -16,10 +16,6 @@ namespace {
 // sum of the output kernel's per-64-node partials in a fixed order.
 // dst == out scales in place; the per-frame lazy call passes a host-mapped dst instead, so the
 // probabilities land in the caller's pinned buffer without a copy command.
-#ifndef FDNN_NORM_BG_NT
-#define FDNN_NORM_BG_NT 1  // non-temporal loads / stores in the background scale kernel: its 640 MB stream through the
-                           // L2s that layer 0 (running beside it) keeps its operand images in; +2 % on the overlapped step
-#endif
 constexpr int kNormMaxTiles = 2048;  // 256-node tiles a row total can span (output layers up to 524 288 nodes)
 template <bool NT>
 __device__ __forceinline__ void normalize_row(const float *out, float *dst, const float *partial, int f, int partial_ld, int rows,
@@ -156,21 +152,6 @@ __global__ __launch_bounds__(256) void normalize_small_kernel(const float *out, 
   for (int q = 0; q < 8; ++q) {
     const int i = tid + 256 * q;
     if (i < groups) d4[i] = make_float4(v[q].x * inv, v[q].y * inv, v[q].z * inv, v[q].w * inv);
-  }
-}
-
-// The same pass as a BACKGROUND kernel for the server loop: a fixed, small grid of workgroups that
-// walk the rows, so that it holds one or two wave slots per SIMD for its whole life instead of
-// flooding every CU with thousands of short workgroups.  Launched on the low-priority tail stream
-// under the next batch's layer 0, whose 228-register waves need the rest of the register file: with
-// the one-workgroup-per-row grid the short workgroups grabbed every slot that came free and layer 0
-// starved until the scale pass was done (rocprofv3 timeline: 120 us overlap, layer 0 330 -> 430 us).
-__global__ __launch_bounds__(256) void normalize_bg_kernel(const float *out, float *dst, const float *partial, int n,
-                                                           int partial_ld, int rows, int n_partial) {
-  __shared__ float red[kNormMaxTiles];
-  for (int f = blockIdx.x; f < n; f += gridDim.x) {
-    normalize_row<(FDNN_NORM_BG_NT != 0)>(out, dst, partial, f, partial_ld, rows, n_partial, red);
-    __syncthreads();  // red[] is reused by the next row
   }
 }
 
@@ -343,18 +324,8 @@ void launch_mask_pack(const int8_t *mask, uint64_t *bits, int n, int rows, hipSt
   }
 }
 
-void launch_normalize(float *out, float *dst, const float *partial, int n, int partial_ld, int rows, int n_partial, hipStream_t s,
-                      bool background) {
+void launch_normalize(float *out, float *dst, const float *partial, int n, int partial_ld, int rows, int n_partial, hipStream_t s) {
   if (n <= 0) return;
-  if (background) {
-    static const int wgs = [] {
-      const char *e = FDNN_TUNE_ENV("FDNN_NORM_BG_WGS");
-      return e ? std::max(1, std::atoi(e)) : 256;  // sweep, 2 steps in flight: 192-256 best (+7-8 % over one stream), 512 +4 %, 1024 +2 %
-    }();
-    note_launch(kLn_norm_bg);
-    hipLaunchKernelGGL(normalize_bg_kernel, dim3(std::min(n, wgs)), dim3(256), 0, s, out, dst, partial, n, partial_ld, rows, n_partial);
-    return;
-  }
   const bool small_ok = n <= 1024 && (rows & 3) == 0 && rows <= 8192 && (n_partial >> 2) <= 64 &&
                         ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
   if (small_ok) {

@@ -271,9 +271,7 @@ void launch_mask_unpack(const uint64_t *bits, int8_t *mask, int n, int rows, hip
 void launch_lazy_compact(const float *out, const uint64_t *bits, float *comp, int n, int rows, int stride, hipStream_t s);
 
 // dst[f][:] = out[f][:] / sum_t partial[t][f]   (dst == out: in place; dst may be host-mapped)
-// background: a small fixed grid walking the rows (server loop: runs under the next batch's layer 0)
-void launch_normalize(float *out, float *dst, const float *partial, int n, int partial_ld, int rows, int n_partial, hipStream_t s,
-                      bool background = false);
+void launch_normalize(float *out, float *dst, const float *partial, int n, int partial_ld, int rows, int n_partial, hipStream_t s);
 
 // Exhaustive check of the 3-op division against IEEE division for every int32
 // accumulator in the closed range [-bound, bound]; the caller passes the

@@ -30,7 +30,7 @@ enum GemmBranch {
 };
 
 // G(output layer, shape, branch, name, ablation-only): the instances of fdnn_gemm.hip -- launch_cfg compiles exactly these
-// (92 rows, 23 of them in measurement builds only; with the 64 names below: 156, 34 of them ablation-only)
+// (92 rows, 23 of them in measurement builds only; with the 63 names below: 155, 33 of them ablation-only)
 #define FDNN_GEMM_LAUNCH_NAMES(G) \
   G(0, tdiv, tap, "gemm.hid.tdiv.tap", 0) \
   G(0, tdiv, prod, "gemm.hid.tdiv.prod", 0) \
@@ -181,7 +181,6 @@ enum GemmBranch {
   X(l0_fixlist_nb2_lpo8, "l0.fixlist.nb2.lpo8", 1) \
   X(l0_fixlist_nb5_lpo4, "l0.fixlist.nb5.lpo4", 1) \
   X(l0_fixlist_t512, "l0.fixlist.t512", 1) \
-  X(norm_bg, "norm.bg", 1) /* the scoring loop's overlapped scale pass: FDNN_SERVER_OVERLAP, measurement builds */ \
   X(norm_small, "norm.small", 0) \
   X(norm_rows, "norm.rows", 0) \
   X(maskpack_flat, "maskpack.flat", 0) \

@@ -329,7 +329,7 @@ void run_layer0(fdnn_ctx *c, const float *d_x, hipStream_t s, const Taps *taps) 
   l0.D = h.in_dim;
   l0.H = h.hidden;
   l0.fma = m->l0_fma;
-  l0.kernel = (c->l0_chain_only && m->l0_kernel == 0) ? 1 : m->l0_kernel;
+  l0.kernel = m->l0_kernel;
   l0.xt = c->d_xt;
   l0.wt = m->d_w0t;
   l0.park = c->d_l0park;
@@ -539,7 +539,7 @@ void fuse_chain_retire_stream(int device, hipStream_t s) {
   }
 }
 
-// The output layer's choice for `count` frames of this context: what run_output launches and what output_will_fuse answers.
+// The output layer's choice for `count` frames of this context: what run_output launches.
 static sel::LayerChoice choose_output(fdnn_ctx *c, int count, bool byte_mask, bool bit_mask, const Taps *taps, bool ctx_may_fuse) {
   fdnn_model *m = c->m;
   sel::LayerCall call{count};
@@ -654,22 +654,13 @@ int run_output(fdnn_ctx *c, const OutputCall &oc, hipStream_t s) {
       fdnn::launch_qgemm_output(g, ch.shape, s);
     }
   }
-  hipStream_t ns = s;
-  if (oc.tail && oc.gemm_done) {  // the scale pass goes to the tail stream, behind the GEMM (fused: nothing is left to run
-    HIP_TRY(hipEventRecord(oc.gemm_done, s));  // there, but the caller records its completion event on the tail stream)
-    HIP_TRY(hipStreamWaitEvent(oc.tail, oc.gemm_done, 0));
-    ns = oc.tail;
-  }
   if (!fused) {
-    ProfScope ps(m, ns, FDNN_PROF_NORMALIZE);
-    fdnn::launch_normalize(d_out, d_final ? d_final : d_out, c->d_partial, count, g.partial_ld, d.rows, d.rows_pad / fdnn::kPartialNodes, ns,
-                           ns != s);
+    ProfScope ps(m, s, FDNN_PROF_NORMALIZE);
+    fdnn::launch_normalize(d_out, d_final ? d_final : d_out, c->d_partial, count, g.partial_ld, d.rows, d.rows_pad / fdnn::kPartialNodes, s);
   }
   HIP_TRY(hipGetLastError());
   return FDNN_OK;
 }
-
-bool output_will_fuse(fdnn_ctx *c, int count, const int8_t *d_masks) { return choose_output(c, count, d_masks != nullptr, false, nullptr, true).fused; }
 
 // Device -> pageable host memory for large results (the 8000-float rows of a whole batch:
 // 320 MB for 10 000 frames).  hipMemcpy into resident pageable memory runs at ~45 GB/s, but a
@@ -739,43 +730,9 @@ bool hidden_layers_chain(const fdnn_model *m, int n) {
   return sel::plan_hidden(h.n_q - 1, [&](int i) { return layer_shape(h.q[i], false); }, n, true, sel::tuning(), {device_cus(m->device)}).chain;
 }
 
-std::vector<std::pair<int, int>> frame_chunks(int n, const fdnn_model *m, bool assume_chained) {
-  std::vector<std::pair<int, int>> out;
-  static const int kChunk = [] {  // FDNN_CHUNK_FRAMES: measurement switch (0 = never chunk; otherwise whole rounds)
-    const int v = sel::tuning().chunk_set ? sel::tuning().chunk_frames : kChunkFrames;
-    return v <= 0 ? 0 : std::max(kRoundFrames, v / kRoundFrames * kRoundFrames);
-  }();
-  // A batch whose hidden layers run as a launch per layer (chaining off, fewer than two int8 hidden layers, a layer without
-  // the validated division: hidden_layers_chain says) pays one more, nearly empty round of workgroups in every
-  // layer for a few frames past a whole round -- 11 000 frames as one batch 977 us, as 10 240 + 760: 754 + 150 (rounds 2-4;
-  // advisor, round 5: the split had been dropped for every configuration).  Such a tail (up to kChunkTailSplit frames) goes
-  // as a small batch of its own.
-  auto split_tail = [&](int off, int cnt) {
-    const int tail = cnt % kRoundFrames;
-    const bool chained = m ? hidden_layers_chain(m, cnt) : assume_chained;
-    if (!chained && cnt > kRoundFrames && tail > 0 && tail <= kChunkTailSplit) {
-      out.emplace_back(off, cnt - tail);
-      out.emplace_back(off + cnt - tail, tail);
-    } else {
-      out.emplace_back(off, cnt);
-    }
-  };
-  if (kChunk <= 0 || n <= kChunk) {
-    split_tail(0, n);
-    return out;
-  }
-  // Chunks of kChunk frames, what is left over as one more batch.  (Rounds 2-4 kept a batch to whole rounds of workgroups and
-  // split a small tail off as a batch of its own -- 11 000 frames as one batch cost a second, nearly empty round in every
-  // hidden layer: 977 us against 754 + 150.  From ~9 800 frames up the hidden layers now run as one chained launch whose
-  // tasks flow across the layers (fdnn_chain.hip), the partial round is gone -- 11 000 frames: layer 0 + hidden layers 534 ->
-  // 459 us -- and a tail costs less inside the batch than as a call of its own: tools/chain_sweep.py, tools/batch_sweep.py.)
-  int off = 0;
-  while (n - off > kChunk) {
-    out.emplace_back(off, kChunk);
-    off += kChunk;
-  }
-  split_tail(off, n - off);
-  return out;
+pass::Chunks frame_chunks(int n, const fdnn_model *m, bool assume_chained) {
+  static const int kChunk = pass::chunk_size(sel::tuning().chunk_set, sel::tuning().chunk_frames);  // FDNN_CHUNK_FRAMES: measurement switch
+  return pass::frame_chunks(n, kChunk, [&](int cnt) { return m ? hidden_layers_chain(m, cnt) : assume_chained; });
 }
 
 // A context's scratch is touched from two kinds of streams: the caller's (the *_device entry
@@ -785,7 +742,7 @@ std::vector<std::pair<int, int>> frame_chunks(int n, const fdnn_model *m, bool a
 // followed by calculateForOutputNodes() or hiddenActivations() reads finished activations
 // without the caller synchronising anything.  On one stream both calls are no-ops for the device.
 bool stream_is_durable(const fdnn_ctx *c, hipStream_t s) {
-  return s == nullptr || s == c->stream || s == c->durable[0] || s == c->durable[1] || s == c->durable[2];
+  return s == nullptr || s == c->stream || s == c->durable[0] || s == c->durable[1];
 }
 hipError_t ctx_enter(fdnn_ctx *c, hipStream_t s) {
   if (c->done_stream == s && (c->done_valid || c->done_pending)) return hipSuccess;  // same stream: already in order
@@ -957,12 +914,6 @@ int lazy_copy_out(fdnn_ctx *c, int count, const uint64_t *d_bits, const uint64_t
 }
 
 // ---------------------------------------------------------------- the scoring pass of every pooled entry point
-std::vector<std::pair<int, int>> stride_chunks(int n) {
-  std::vector<std::pair<int, int>> out;
-  for (int first = 0; first < n; first += kChunkFrames) out.emplace_back(first, std::min(kChunkFrames, n - first));
-  return out;
-}
-
 int check_input_width(const fdnn_model *m, int dim) {
   if (dim == m->hm.hdr.in_dim) return FDNN_OK;
   return fail(FDNN_E_ARG, "input vector size " + std::to_string(dim) + " must be equal with network input size " + std::to_string(m->hm.hdr.in_dim));
@@ -973,74 +924,95 @@ int check_frames_aligned(const float *d_x) {
   return fail(FDNN_E_ARG, "device frames must start on a 16-byte boundary (include/fdnn.h, Device buffers)");
 }
 
-int score_chunks(fdnn_model *m, const std::vector<std::pair<int, int>> &chunks, const ScorePass &p) {
-  const BlobHeader &h = m->hm.hdr;
-  const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64;
+// What each sink does with a chunk whose rows are in place (d_x: on the device, the caller's or the context's frame buffer).
+static int to_device_rows(fdnn_ctx *c, const float *d_x, int cnt, const int8_t *d_masks, const uint64_t *d_bits, float *d_out, hipStream_t s) {
+  int rc = run_hidden(c, d_x, s, nullptr);
+  if (!rc) rc = run_output(c, {.count = cnt, .d_masks = d_masks, .d_bits = d_bits, .d_out = d_out}, s);
+  return rc;
+}
+static int to_host_behind_bits(fdnn_ctx *c, const pass::ChunkView &v, hipStream_t s) {
+  int rc = to_device_rows(c, c->d_x, v.cnt, nullptr, c->d_mask_bits, c->d_out, s);
+  if (!rc) rc = lazy_copy_out(c, v.cnt, c->d_mask_bits, v.bits, v.rows, s);
+  if (rc) hipStreamSynchronize(s);
+  return rc;
+}
+// device top-k: the rows stay in the context, the selection goes to the caller's buffers
+static int to_device_topk(fdnn_ctx *c, const float *d_x, const pass::ChunkView &v, int k, hipStream_t s) {
+  int rc = to_device_rows(c, d_x, v.cnt, nullptr, nullptr, c->d_out, s);
+  if (!rc) fdnn::launch_topk(c->d_out, v.cnt, c->m->hm.hdr.out_dim, k, v.topk_nodes, v.topk_probs, s);
+  return rc;
+}
+// the chunk's entries through the host form, which synchronises (a sets chunk without a segment scores nothing)
+static int to_host_entries(fdnn_ctx *c, const pass::Sink &to, const pass::ChunkView &v, hipStream_t s) {
+  int rc = run_hidden(c, c->d_x, s, nullptr);
+  HostEntries he;
+  he.count = v.cnt, he.nodes = v.nodes, he.n_nodes = v.n_nodes, he.probs = v.probs, he.inactive = v.inactive;
+  if (to.kind == pass::Sink::host_lists) he.row_ptr = v.row_ptr.data();
+  else if (to.kind == pass::Sink::host_set) he.len = to.len;
+  else he.segs = &v.segs;
+  if (!rc && (to.kind != pass::Sink::host_sets || !v.segs.empty())) rc = entries_to_host(c, he, s);
+  if (rc) hipStreamSynchronize(s);
+  return rc;
+}
+static int to_device_sets(fdnn_ctx *c, const float *d_x, const pass::ChunkView &v, hipStream_t s) {
+  int rc = run_hidden(c, d_x, s, nullptr);
+  SetsCall sc;
+  sc.segs = &v.segs, sc.d_nodes = v.nodes, sc.d_probs = v.probs, sc.d_inactive = v.inactive;
+  if (!rc) rc = run_sets(c, sc, s);
+  return rc;
+}
+
+int run_chunks(fdnn_ctx *c, hipStream_t s, const pass::Chunks &chunks, const pass::Pass &p) {
+  using pass::Rows;
+  using pass::Sink;
+  const BlobHeader &h = c->m->hm.hdr;
+  const pass::Dims dims{size_t(h.in_dim), size_t(h.out_dim), (size_t(h.out_dim) + 63) / 64};
+  const pass::Raw &raw = p.rows.raw;
+  for (const auto &ch : chunks) {  // frames are independent: a chunk is a batch of its own
+    const pass::ChunkView v = pass::chunk_view(p, dims, ch.first, ch.second);
+    c->n = v.cnt;
+    hipError_t e = hipSuccess;
+    if (raw.spec) splice_rows(*raw.spec, h.in_dim, p.rows.kind == Rows::raw_host ? c->d_raw.p : raw.frames, raw.n_frames, *raw.segs, v.splice_row, v.cnt, c->d_x, s);
+    if (p.rows.kind == Rows::host) e = hipMemcpyAsync(c->d_x, v.x, sizeof(float) * size_t(v.cnt) * dims.D, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && p.mask.kind == pass::Mask::host_bits)
+      e = hipMemcpyAsync(c->d_mask_bits, v.bits, sizeof(uint64_t) * size_t(v.cnt) * dims.wpr, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string(p.who) + ": " + hipGetErrorString(e));
+    const float *d_x = p.rows.kind == Rows::device ? v.x : c->d_x.p;
+    int rc = FDNN_OK;
+    switch (p.sink.kind) {
+      case Sink::device_rows: rc = to_device_rows(c, d_x, v.cnt, v.bytes, v.bits, v.rows, s); break;
+      case Sink::host_dense: rc = dense_pass_to_host(c, v.rows, s); break;
+      case Sink::host_behind_bits: rc = to_host_behind_bits(c, v, s); break;
+      case Sink::host_topk: rc = dense_pass(c, {.k = p.sink.k, .nodes = v.topk_nodes, .probs = v.topk_probs}, s, true); break;  // n x k x 8 bytes cross PCIe
+      case Sink::device_topk: rc = to_device_topk(c, d_x, v, p.sink.k, s); break;
+      case Sink::host_lists:
+      case Sink::host_set:
+      case Sink::host_sets: rc = to_host_entries(c, p.sink, v, s); break;
+      case Sink::device_sets: rc = to_device_sets(c, d_x, v, s); break;
+    }
+    if (rc) return rc;
+  }
+  return FDNN_OK;
+}
+
+int score_chunks(fdnn_model *m, const pass::Chunks &chunks, const pass::Pass &p, hipStream_t callers) {
   DeviceGuard g(m->device);
   int cap = 0;  // the scratch only has to hold the largest chunk
   for (const auto &ch : chunks) cap = std::max(cap, ch.second);
   fdnn_ctx *c = nullptr;
   int rc = acquire_ctx(m, cap, &c);
   if (rc) return rc;
-  hipStream_t s = (p.d_out || p.d_topk_nodes) ? p.stream : c->stream;
-  std::vector<int32_t> rebased;
+  hipStream_t s = pass::on_callers_stream(p.sink.kind) ? callers : c->stream;
   CtxUse use;  // (also on the error paths: the context goes back to the pool)
   hipError_t e = use.enter(c, s);
-  if (e == hipSuccess && p.raw) {  // host raw frames travel once; every chunk splices its rows from them
-    rc = ctx_raw_reserve(c, size_t(p.raw_frames), p.spec->raw_dim);
-    if (!rc) e = hipMemcpyAsync(c->d_raw, p.raw, sizeof(float) * size_t(p.raw_frames) * size_t(p.spec->raw_dim), hipMemcpyHostToDevice, s);
+  const pass::Raw &raw = p.rows.raw;
+  if (e == hipSuccess && p.rows.kind == pass::Rows::raw_host) {  // host raw frames travel once; every chunk splices its rows from them
+    rc = ctx_raw_reserve(c, size_t(raw.n_frames), raw.spec->raw_dim);
+    if (rc) return rc;
+    e = hipMemcpyAsync(c->d_raw, raw.frames, sizeof(float) * size_t(raw.n_frames) * size_t(raw.spec->raw_dim), hipMemcpyHostToDevice, s);
   }
-  for (size_t i = 0; e == hipSuccess && !rc && i < chunks.size(); ++i) {  // frames are independent: a chunk is a batch of its own
-    const size_t off = size_t(chunks[i].first);
-    const int cnt = chunks[i].second;
-    c->n = cnt;
-    if (p.spec) splice_rows(*p.spec, h.in_dim, p.raw ? c->d_raw : p.d_raw, p.raw_frames, *p.segs, p.row0 + int(off), cnt, c->d_x, s);
-    if (p.x) e = hipMemcpyAsync(c->d_x, p.x + off * D, sizeof(float) * size_t(cnt) * D, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && p.bits) e = hipMemcpyAsync(c->d_mask_bits, p.bits + off * wpr, sizeof(uint64_t) * size_t(cnt) * wpr, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) break;
-    if (p.row_ptr || p.set_given || p.sets) {  // the chunk's entries through the host form, which synchronises
-      rc = run_hidden(c, c->d_x, s, nullptr);
-      HostEntries he;
-      he.count = cnt, he.inactive = p.inactive + off;
-      std::vector<fdnn::sets::Seg> segs;
-      if (p.row_ptr) {  // the chunk's slice of the lists as lists of its own (`rebased` is free for the next chunk)
-        lists::rebase_rows(p.row_ptr, int(off), cnt, &rebased);
-        const size_t e0 = size_t(p.row_ptr[off]);
-        he.row_ptr = rebased.data(), he.nodes = p.nodes + e0, he.n_nodes = rebased[size_t(cnt)], he.probs = p.probs + e0;
-      } else if (p.set_given) {  // one node set for every chunk: the chunk's rows land at probs + off * len
-        he.len = he.n_nodes = p.set_len, he.nodes = p.set_nodes, he.probs = p.probs + off * size_t(p.set_len);
-      } else {  // the chunk's slice of the segments: its blocks are one contiguous range of the caller's probs
-        segs = fdnn::sets::slice(*p.sets, int(off), int(off) + cnt);
-        he.segs = &segs, he.nodes = p.nodes, he.n_nodes = p.sets->set_ptr[p.sets->n_segs];
-        if (!segs.empty()) he.probs = p.probs + size_t(segs[0].src_off);
-      }
-      if (!rc && (!p.sets || !segs.empty())) rc = entries_to_host(c, he, s);
-      if (rc) hipStreamSynchronize(s);
-      continue;
-    }
-    if (p.out && !p.bits) {
-      rc = dense_pass_to_host(c, p.out + off * O, s);
-      continue;
-    }
-    if (p.topk_k && p.topk_nodes) {  // host top-k: n x k x 8 bytes cross PCIe
-      rc = dense_pass(c, {.k = p.topk_k, .nodes = p.topk_nodes + off * size_t(p.topk_k), .probs = p.topk_probs + off * size_t(p.topk_k)}, s, true);
-      continue;
-    }
-    if (p.topk_k) {  // device top-k: the rows stay in the context, the selection goes to the caller's buffers
-      rc = run_hidden(c, p.d_x + off * D, s, nullptr);
-      if (!rc) rc = run_output(c, {.count = cnt, .d_out = c->d_out}, s);
-      if (!rc) fdnn::launch_topk(c->d_out, cnt, int(O), p.topk_k, p.d_topk_nodes + off * size_t(p.topk_k), p.d_topk_probs + off * size_t(p.topk_k), s);
-      continue;
-    }
-    const uint64_t *d_bits = p.bits ? c->d_mask_bits : p.d_bits ? p.d_bits + off * wpr : nullptr;
-    rc = run_hidden(c, p.d_x ? p.d_x + off * D : c->d_x, s, nullptr);
-    if (!rc) rc = run_output(c, {.count = cnt, .d_bits = d_bits, .d_out = p.d_out ? p.d_out + off * O : c->d_out}, s);
-    if (!rc && p.out) rc = lazy_copy_out(c, cnt, d_bits, p.bits + off * wpr, p.out + off * O, s);
-    if (rc && p.out) hipStreamSynchronize(s);
-  }
-  if (rc) return rc;
   if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string(p.who) + ": " + hipGetErrorString(e));
-  return FDNN_OK;
+  return run_chunks(c, s, chunks, p);
 }
 
 // The host half of a compacted lazy return (lazy_compact_kernel): a compacted row is the row's inactive value followed by

@@ -7,11 +7,11 @@
 // On the GPU the same shape wants two things the per-call API cannot give:
 //
 //   * batches in flight.  A full-size batch fills the chip kernel by kernel, so consecutive
-//     batches are serialised on one compute stream; but the soft-max scale of batch i is a pure
-//     HBM pass with the matrix and vector pipes idle, and layer 0 of batch i+1 is a pure fp32
-//     VALU kernel with HBM idle.  The scale pass therefore goes to a tail stream, behind an event,
-//     and runs under the next batch's layer 0.  That needs per-batch scratch (a context per
-//     slot) and a completion handle per batch instead of "the stream is the handle": tickets.
+//     batches are serialised on one compute stream, while their copies in and out run on the
+//     slots' own streams.  That needs per-batch scratch (a context per slot) and a completion
+//     handle per batch instead of "the stream is the handle": tickets.  (Round 2 ran the soft-max
+//     scale pass of batch i on a tail stream under layer 0 of batch i+1; with the fused soft-max
+//     and the int8 screening of layer 0 that lost and is gone: profiles/LABBOOK.md.)
 //   * coalescing.  A 100-frame utterance is 1/100 of a launch that fills the chip.  Host-pointer
 //     submissions from any number of threads are queued, packed into one batch per slot (up to
 //     max_frames), scored once, and scattered back to the callers' buffers.  Frames are
@@ -64,7 +64,7 @@ struct TicketState {
 struct Slot {
   fdnn_ctx *ctx = nullptr;
   hipStream_t stream = nullptr;   // small batches: the whole batch; host batches: copies
-  hipEvent_t gemm_done = nullptr, tail_done = nullptr, staged = nullptr, done = nullptr;
+  hipEvent_t gemm_done = nullptr, staged = nullptr, done = nullptr;  // gemm_done: the compute stream's results, for the slot's stream
   uint64_t ticket = 0;            // device submissions: the ticket this slot last carried
   bool used = false;              // `done` has been recorded at least once
   // host submissions: staging, sized in max_frames units (h_x, h_mask, d_out with the host side, the rest on first use)
@@ -92,7 +92,7 @@ struct Slot {
 struct fdnn_server {
   fdnn_model *m = nullptr;
   int max_frames = 0, depth = 0;
-  hipStream_t s_main = nullptr, s_tail = nullptr;
+  hipStream_t s_main = nullptr;
   std::vector<Slot> slots;
   std::mutex mu;                  // submission order + slot table
   uint64_t next_ticket = 1;
@@ -140,81 +140,49 @@ int alloc_host_side(fdnn_server *s) {
   return FDNN_OK;
 }
 
-// Enqueue one batch that is already on the device.  Large batches: compute on the shared main
-// stream, soft-max scale on the tail stream; small ones: everything on the slot's stream.
-// Returns with *last_stream the stream the batch's last work went to.
+// Enqueue one batch that is already on the device, as the chunks of a pass (fdnn::run_chunks) on the slot's context.  Large
+// batches: chunk by chunk (fdnn::frame_chunks) on the shared main stream; small ones: one chunk on the slot's stream, so
+// that several of them overlap.  `after` (may be null): an event the compute must wait for, the batch's H2D copy.  behind(cs):
+// what the batch launches over all its rows behind the chunks.  Returns with *last_stream the stream the batch's last work went to.
+template <class Behind>
+int enqueue_pass(fdnn_server *s, Slot &sl, int n, hipEvent_t after, const fdnn::pass::Pass &p, hipStream_t *last_stream, Behind &&behind) {
+  fdnn_ctx *c = sl.ctx;
+  c->n = n;
+  c->last = -1;
+  const bool small = n <= kSmallBatch;
+  hipStream_t cs = small ? sl.stream : s->s_main;
+  if (after) HIP_TRY(hipStreamWaitEvent(cs, after, 0));
+  fdnn::CtxUse use;  // every way out notes the stream the batch ends on and puts the batch's frame count back
+  use.n_after = n;
+  HIP_TRY(use.enter(c, cs));
+  const int rc = fdnn::run_chunks(c, cs, small ? fdnn::pass::Chunks{{0, n}} : fdnn::frame_chunks(n, c->m), p);
+  if (rc) return rc;
+  behind(cs);
+  *last_stream = cs;
+  return FDNN_OK;
+}
+
 struct BatchCall {
   const float *d_x = nullptr;
   int n = 0;
   const int8_t *d_masks = nullptr;  // one mask or none
   const uint64_t *d_bits = nullptr;
   float *d_out = nullptr;
-  hipEvent_t after = nullptr;  // (may be null) an event the compute must wait for: the batch's H2D copy
+  hipEvent_t after = nullptr;  // (may be null) see enqueue_pass
   float *d_comp = nullptr;     // bit-mask host batches: the rows compacted, `stride` floats each
   int stride = 0;
   int32_t *d_topk = nullptr;   // top-k host batches: [n][topk_k] nodes, then [n][topk_k] values, selected from d_out
   int topk_k = 0;
 };
 int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *last_stream) {
-  const int n = b.n;
-  fdnn_ctx *c = sl.ctx;
-  c->n = n;
-  c->last = -1;
-  const bool small = n <= kSmallBatch;
-  // Large batches whose output layer cannot scale its own soft-max (odd widths, FDNN_FUSE_NORM=0; dense and batched-lazy
-  // batches of the usual shapes can, and have no scale pass at all): the scale pass runs in line behind the output GEMM.
-  // FDNN_SERVER_OVERLAP=1 restores round 2's arrangement -- the pass as a background kernel on the tail stream under
-  // the next batch's layer 0, which must then be the all-VALU chain kernel (the matrix-pipe kernels fill the register
-  // file) -- worth it while layer 0 took 270 us; with the int8 screening (140 us) the chain kernel's 325 us lose.
-  static const bool overlap = [] {
-    const char *e = FDNN_TUNE_ENV("FDNN_SERVER_OVERLAP");
-    return e ? std::atoi(e) != 0 : false;
-  }();
-  const std::vector<std::pair<int, int>> chunks = small ? std::vector<std::pair<int, int>>{} : fdnn::frame_chunks(n, c->m);
-  bool all_fused = !small;
-  for (const auto &ch : chunks) all_fused = all_fused && (b.d_bits || fdnn::output_will_fuse(c, ch.second, b.d_masks));  // (a short tail chunk may take the unfused kernels)
-  c->l0_chain_only = !small && overlap && !all_fused;  // see fdnn_ctx: an overlapped scale pass needs room beside layer 0
-  hipStream_t cs = small ? sl.stream : s->s_main;
-  if (b.after) HIP_TRY(hipStreamWaitEvent(cs, b.after, 0));
-  fdnn::CtxUse use;  // every way out notes the stream the batch ends on and puts the batch's frame count back
-  use.n_after = n;
-  HIP_TRY(use.enter(c, cs));
-  int rc = FDNN_OK;
-  hipStream_t &end = use.s;  // the stream the batch's last work goes to
-  if (small) {
-    rc = fdnn::run_hidden(c, b.d_x, cs, nullptr);
-    if (!rc) rc = fdnn::run_output(c, {.count = n, .d_masks = b.d_masks, .d_bits = b.d_bits, .d_out = b.d_out}, cs);
-  } else {
-    // very large batches go chunk by chunk (fdnn::frame_chunks), and the chunks overlap like batches do: chunk j's
-    // scale pass runs on the tail stream under chunk j+1's layer 0.  One context serves all chunks, so the compute
-    // stream may not overwrite the soft-max partial sums (chunk j+1's output GEMM) before chunk j's scale pass has
-    // read them: it waits for `tail_done` there.
-    const size_t D = size_t(s->m->hm.hdr.in_dim), O = size_t(s->m->hm.hdr.out_dim), wpr = (O + 63) / 64;
-    bool first = true;
-    end = overlap ? s->s_tail : cs;
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-      const auto &ch = chunks[ci];
-      c->n = ch.second;
-      rc = fdnn::run_hidden(c, b.d_x + size_t(ch.first) * D, cs, nullptr);
-      if (rc) break;
-      if (!first && overlap) HIP_TRY(hipStreamWaitEvent(cs, sl.tail_done, 0));
-      rc = fdnn::run_output(c, {.count = ch.second, .d_masks = b.d_masks ? b.d_masks + size_t(ch.first) * O : nullptr,
-                                .d_bits = b.d_bits ? b.d_bits + size_t(ch.first) * wpr : nullptr, .d_out = b.d_out + size_t(ch.first) * O,
-                                .tail = overlap ? s->s_tail : nullptr, .gemm_done = overlap ? sl.gemm_done : nullptr}, cs);
-      if (rc) break;
-      // (without the overlap everything is on the compute stream, in order; a record is 3-4 us of queue time)
-      if (overlap && ci + 1 < chunks.size()) HIP_TRY(hipEventRecord(sl.tail_done, s->s_tail));
-      first = false;
-    }
-  }
-  // bit-mask host batches: the rows compacted (active probabilities + one value per frame) for the trip over PCIe
-  if (!rc && b.d_bits && b.d_comp && b.stride > 0)
-    fdnn::launch_lazy_compact(b.d_out, b.d_bits, b.d_comp, n, s->m->hm.hdr.out_dim, b.stride, end);
-  // top-k host batches: one selection launch with the batch's k over the rows, which stay here
-  if (!rc && b.d_topk && b.topk_k > 0)
-    fdnn::launch_topk(b.d_out, n, s->m->hm.hdr.out_dim, b.topk_k, b.d_topk, reinterpret_cast<float *>(b.d_topk + size_t(n) * size_t(b.topk_k)), end);
-  if (!rc) *last_stream = end;
-  return rc;
+  const int n = b.n, O = s->m->hm.hdr.out_dim;
+  return enqueue_pass(s, sl, n, b.after, fdnn::pass::Pass::loop_rows(b.d_x, b.d_masks, b.d_bits, b.d_out), last_stream, [&](hipStream_t cs) {
+    // bit-mask host batches: the rows compacted (active probabilities + one value per frame) for the trip over PCIe
+    if (b.d_bits && b.d_comp && b.stride > 0) fdnn::launch_lazy_compact(b.d_out, b.d_bits, b.d_comp, n, O, b.stride, cs);
+    // top-k host batches: one selection launch with the batch's k over the rows, which stay here
+    if (b.d_topk && b.topk_k > 0)
+      fdnn::launch_topk(b.d_out, n, O, b.topk_k, b.d_topk, reinterpret_cast<float *>(b.d_topk + size_t(n) * size_t(b.topk_k)), cs);
+  });
 }
 
 // Enqueue one SET batch that is already on the device (kSet): the hidden layers as enqueue_batch runs them, then the pieces'
@@ -222,38 +190,13 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *las
 // inactive values behind them [rows].
 int enqueue_set_batch(fdnn_server *s, Slot &sl, hipEvent_t after, hipStream_t *last_stream) {
   const BatchPlan &b = sl.batch;
-  const int n = b.rows;
-  fdnn_ctx *c = sl.ctx;
-  c->n = n;
-  c->last = -1;
-  c->l0_chain_only = false;
-  const bool small = n <= kSmallBatch;
-  const std::vector<std::pair<int, int>> chunks = small ? std::vector<std::pair<int, int>>{{0, n}} : fdnn::frame_chunks(n, c->m);
-  hipStream_t cs = small ? sl.stream : s->s_main;
-  if (after) HIP_TRY(hipStreamWaitEvent(cs, after, 0));
-  fdnn::CtxUse use;
-  use.n_after = n;
-  HIP_TRY(use.enter(c, cs));
   // the pieces as the tables of a sets call over the batch's rows
   std::vector<int32_t> seg_rows, set_ptr;
   for (const Piece &p : b.pieces) seg_rows.push_back(p.row0), set_ptr.push_back(p.set_off);
-  seg_rows.push_back(n), set_ptr.push_back(b.set_nodes);
+  seg_rows.push_back(b.rows), set_ptr.push_back(b.set_nodes);
   const fdnn::sets::Tables t{seg_rows.data(), set_ptr.data(), int(b.pieces.size())};
-  const size_t D = size_t(s->m->hm.hdr.in_dim);
-  int rc = FDNN_OK;
-  for (const auto &ch : chunks) {
-    c->n = ch.second;
-    rc = fdnn::run_hidden(c, c->d_x + size_t(ch.first) * D, cs, nullptr);
-    if (rc) break;
-    const std::vector<fdnn::sets::Seg> segs = fdnn::sets::slice(t, ch.first, ch.first + ch.second);
-    fdnn::SetsCall sc;
-    sc.segs = &segs, sc.d_nodes = sl.d_nodes.p, sc.d_probs = sl.d_out.p + (segs.empty() ? 0 : segs[0].src_off);
-    sc.d_inactive = sl.d_out.p + size_t(b.nnz) + size_t(ch.first);
-    rc = fdnn::run_sets(c, sc, cs);
-    if (rc) break;
-  }
-  if (!rc) *last_stream = cs;
-  return rc;
+  return enqueue_pass(s, sl, b.rows, after, fdnn::pass::Pass::loop_sets(sl.ctx->d_x, t, sl.d_nodes.p, sl.d_out.p, sl.d_out.p + size_t(b.nnz)), last_stream,
+                      [](hipStream_t) {});
 }
 
 // A batch carrying `ticket` failed: whatever of that request is still queued will never be packed (the packer would read
@@ -530,8 +473,8 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
                               .d_comp = sl.d_comp.p, .stride = b.stride, .d_topk = b.kind == kTopk ? sl.d_topk.p : nullptr,
                               .topk_k = b.topk_k}, &last);
   if (*rc) return hipSuccess;
-  if (last != sl.stream) {  // results leave on the slot's stream, behind the tail stream's scale pass
-    e = hipEventRecord(sl.gemm_done, last);  // (gemm_done is free again: the scale pass already waits on its earlier record)
+  if (last != sl.stream) {  // results leave on the slot's stream, behind the main stream's compute
+    e = hipEventRecord(sl.gemm_done, last);
     if (e == hipSuccess) e = hipStreamWaitEvent(sl.stream, sl.gemm_done, 0);
   }
   if (e == hipSuccess && bits && b.stride > 0)  // compacted rows: to the host with the batch
@@ -682,12 +625,9 @@ int fdnn_server_create(fdnn_model *m, int max_frames, int depth, fdnn_server **o
   s->max_frames = max_frames;
   s->depth = depth;
   s->slots = std::vector<Slot>(size_t(depth));
-  // the compute stream outranks the tail stream: when layer 0 of batch i+1 and the scale pass of
-  // batch i are both runnable, the dispatcher must place layer 0's big workgroups first
-  int prio_least = 0, prio_greatest = 0;
+  int prio_least = 0, prio_greatest = 0;  // (the compute stream keeps the priority it had over the retired tail stream)
   hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
   hipError_t e = hipStreamCreateWithPriority(&s->s_main, hipStreamNonBlocking, prio_greatest);
-  if (e == hipSuccess) e = hipStreamCreateWithPriority(&s->s_tail, hipStreamNonBlocking, prio_least);
   int rc = FDNN_OK;
   for (Slot &sl : s->slots) {
     if (e != hipSuccess || rc) break;
@@ -695,10 +635,8 @@ int fdnn_server_create(fdnn_model *m, int max_frames, int depth, fdnn_server **o
     if (rc) break;
     e = hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking);
     sl.ctx->durable[0] = s->s_main;  // the loop's streams outlive the slot's context: its ordering records can wait until
-    sl.ctx->durable[1] = s->s_tail;  // another stream asks for them (fdnn::ctx_leave)
-    sl.ctx->durable[2] = sl.stream;
+    sl.ctx->durable[1] = sl.stream;  // another stream asks for them (fdnn::ctx_leave)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.gemm_done, hipEventDisableTiming | hipEventDisableSystemFence);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.tail_done, hipEventDisableTiming | hipEventDisableSystemFence);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.staged, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
   }
@@ -734,17 +672,14 @@ void fdnn_server_free(fdnn_server *s) {
   for (Slot &sl : s->slots)
     if (sl.stream) fdnn::fuse_chain_retire_stream(s->m->device, sl.stream);
   if (s->s_main) fdnn::fuse_chain_retire_stream(s->m->device, s->s_main);  // (the device's chain of fused launches may still name them)
-  if (s->s_tail) fdnn::fuse_chain_retire_stream(s->m->device, s->s_tail);
   if (s->s_main) hipStreamSynchronize(s->s_main);
-  if (s->s_tail) hipStreamSynchronize(s->s_tail);
   for (Slot &sl : s->slots) {
     if (sl.ctx) fdnn::destroy_ctx(sl.ctx);
-    for (hipEvent_t ev : {sl.gemm_done, sl.tail_done, sl.staged, sl.done})
+    for (hipEvent_t ev : {sl.gemm_done, sl.staged, sl.done})
       if (ev) hipEventDestroy(ev);
     if (sl.stream) hipStreamDestroy(sl.stream);
   }
   if (s->s_main) hipStreamDestroy(s->s_main);
-  if (s->s_tail) hipStreamDestroy(s->s_tail);
   delete s;  // (with the slots' staging buffers)
 }
 

@@ -547,7 +547,7 @@ FDNN_API int fdnn_debug_set_pp(int mode, int min_frames);
 FDNN_API int fdnn_debug_set_ppo(int mode);
 
 /* The launch recorder (tests and the tools under tools/): every host launch site of a compute kernel has a stable name for the
- * branch it takes ("gemm.out.ft320.fused_masked", "small.hid.nt64.prod", "chain.ft320.nofix", "l0.fixlist.lpo8", "norm.bg", ...),
+ * branch it takes ("gemm.out.ft320.fused_masked", "small.hid.nt64.prod", "chain.ft320.nofix", "l0.fixlist.lpo8", "norm.rows", ...),
  * kept in one static table that can be read with no device present.  fdnn_debug_launch_name_count: entries of the table;
  * fdnn_debug_launch_name: the name of entry `index` (null outside the table) and, where `flags` is not null, 1 if the branch
  * exists only in measurement builds (-DFDNN_ABLATION), 2 if the kernel runs at model load.  fdnn_debug_launch_record(1 / 0)

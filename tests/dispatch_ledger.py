@@ -6,7 +6,7 @@ which case covers which names:
   * CASES      every case names a net, a batch size, an entry point, the process-wide modes it sets, the names it exists
                for (`must`) and -- in EXPECT -- the exact set of names its recorded span launches;
   * EXCLUDED   names no case launches, each with the reason: ablation-only (the flag in the library's table), or
-               unreachable in the shipped build, with the file and lines that show it.  (156 names: 34 ablation-only,
+               unreachable in the shipped build, with the file and lines that show it.  (155 names: 33 ablation-only,
                4 excluded, 118 launched by the cases.)
 
 tests/test_dispatch_ledger_host.py (no GPU) asserts  union(EXPECT) | EXCLUDED == the library's table,  so a new launch

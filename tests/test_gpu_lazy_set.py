@@ -138,6 +138,23 @@ def test_set_against_the_oracle_through_every_entry_point(fixtures, name):
     ctx.delete()
 
 
+def test_one_call_form_in_two_chunks(fixtures):
+    """fdnn_calculate_lazy_set at the smallest n that api.frame_chunks cuts in two, on the tiny net: every chunk scores the
+    same set and its rows land at probs + off * len, its inactive values at off -- the bytes of the same rows as two calls."""
+    n = 20480 + 1
+    for chained in (True, False):
+        assert len(api.frame_chunks(n, chained)) == 2 and len(api.frame_chunks(n - 1, chained)) == 1
+    cut = api.frame_chunks(n, True)[1][0]
+    dnn = api.QuantizedDnn.loadFromFile(fixtures["tiny"])
+    nodes = np.arange(3, 100, 3, dtype=np.int32)  # 33 of the tiny net's 100 nodes
+    x = F.synth_features(n, 432, seed=1310)
+    probs, inactive = dnn.calculateLazySet(x, nodes)
+    a, b = dnn.calculateLazySet(x[:cut], nodes), dnn.calculateLazySet(x[cut:], nodes)
+    assert probs.shape == (n, nodes.size) and np.array_equal(probs.view(np.uint32), np.concatenate([a[0], b[0]]).view(np.uint32))
+    assert np.array_equal(inactive.view(np.uint32), np.concatenate([a[1], b[1]]).view(np.uint32))
+    dnn.delete()
+
+
 def test_a_layer_the_kernel_does_not_stage_goes_to_the_list_kernels(fixtures):
     """K = 2304 is more than the kernel stages: under the default rule and with the MFMA kernel 'forced' the call is served by
     the list kernels, within the same bars."""

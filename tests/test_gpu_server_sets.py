@@ -145,6 +145,26 @@ def test_large_coalesced_set_batches(dnn):
     srv.close()
 
 
+def test_a_set_batch_of_two_chunks(tiny_model_path):
+    """max_frames one above the chunk: a 20 481-frame request is ONE batch that the loop scores as two chunks on its main
+    stream, the cut inside its only segment (the second chunk's block continues at cut * len of the batch's probs, its
+    inactive values at cut) -- the bytes of the same rows as two calls."""
+    n = 20480 + 1
+    assert len(api.frame_chunks(n)) == 2 and len(api.frame_chunks(n - 1)) == 1
+    cut = api.frame_chunks(n)[1][0]
+    tiny = api.QuantizedDnn.loadFromFile(tiny_model_path)
+    nodes = np.arange(3, 100, 3, dtype=np.int32)  # 33 of the tiny net's 100 nodes
+    x = F.synth_features(n, 432, seed=950)
+    a, b = tiny.calculateLazySet(x[:cut], nodes), tiny.calculateLazySet(x[cut:], nodes)
+    srv = api.ScoringServer(tiny, max_frames=n, depth=1)
+    t, probs, inactive = srv.submitLazySet(x, nodes)
+    srv.wait(t)
+    assert same_bytes(probs, np.concatenate([a[0], b[0]])) and same_bytes(inactive, np.concatenate([a[1], b[1]]))
+    assert srv.stats()["batches"] == 1
+    srv.close()
+    tiny.delete()
+
+
 def test_raw_frames_with_a_set(mid_model_path):
     """submitRawSet on the toy splice spec: the bytes of submitLazySet on host-spliced rows."""
     api.set_kernel(1)

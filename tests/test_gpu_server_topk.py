@@ -107,6 +107,24 @@ def test_a_split_request_continues_at_taken_times_k(dnn):
     srv.close()
 
 
+def test_a_batch_of_two_chunks(tiny_model_path):
+    """max_frames one above the chunk: a 20 481-frame request is ONE batch that the loop scores as two chunks on its main
+    stream, with one selection launch over all rows behind them -- the bytes of the same rows as two calls."""
+    n, k = 20480 + 1, 32
+    assert len(api.frame_chunks(n)) == 2 and len(api.frame_chunks(n - 1)) == 1
+    cut = api.frame_chunks(n)[1][0]
+    tiny = api.QuantizedDnn.loadFromFile(tiny_model_path)
+    x = F.synth_features(n, 432, seed=1470)
+    a, b = tiny.calculateTopK(x[:cut], k), tiny.calculateTopK(x[cut:], k)
+    srv = api.ScoringServer(tiny, max_frames=n, depth=1)
+    t, nodes, probs = srv.submitTopK(x, k)
+    srv.wait(t)
+    assert same((nodes, probs), (np.concatenate([a[0], b[0]]), np.concatenate([a[1], b[1]])))
+    assert srv.stats()["batches"] == 1
+    srv.close()
+    tiny.delete()
+
+
 def test_raw_topk_submissions(mid_model_path):
     dnn = api.QuantizedDnn.loadFromFile(mid_model_path)
     try:

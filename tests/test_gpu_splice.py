@@ -258,6 +258,30 @@ def test_device_segment_table(mid):
     mid.setSplice([], 0)
 
 
+def test_device_raw_frames_in_two_chunks(tiny_model_path):
+    """fdnn_calculate_raw_device at the smallest n that api.frame_chunks cuts in two, on the tiny net: the second chunk's rows
+    are spliced from row `cut` on and land at d_out + cut * O -- the bytes of the same rows scored as two calls."""
+    import torch
+
+    n = 20480 + 1
+    for chained in (True, False):
+        assert len(api.frame_chunks(n, chained)) == 2 and len(api.frame_chunks(n - 1, chained)) == 1
+    cut = api.frame_chunks(n, True)[1][0]
+    tiny = api.QuantizedDnn.loadFromFile(tiny_model_path, device=0)
+    tiny.setSplice(*KALDI)
+    raw = raw_frames(n, 39, seed=600)
+    rows = spliced(raw, KALDI)
+    want = np.concatenate([tiny.calculate(rows[:cut]), tiny.calculate(rows[cut:])])
+    d_raw = torch.from_numpy(raw).cuda()
+    d_out = torch.full((n * tiny.outputDimension() + 4,), -7.0, dtype=torch.float32, device="cuda")
+    tiny.calculateRawDevice(d_raw.data_ptr(), n, d_out.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    got = d_out.cpu().numpy()
+    assert (got[n * tiny.outputDimension():] == -7.0).all()
+    assert np.array_equal(got[:n * tiny.outputDimension()].reshape(n, -1).view(np.uint32), want.view(np.uint32))
+    tiny.delete()
+
+
 def test_group_and_batcher(mid, mid_model_path, monkeypatch, tmp_path):
     monkeypatch.setenv("FDNN_GROUP_SPLIT_MIN", "64")
     monkeypatch.setenv("FDNN_GROUP_SHARD_MIN", "16")

@@ -125,6 +125,43 @@ def test_a_call_of_two_chunks_equals_two_calls(nets):
     assert np.array_equal(nodes[rows], want[0]) and np.array_equal(probs[rows].view(np.uint32), want[1])
 
 
+def test_raw_and_device_calls_of_two_chunks_equal_two_calls(nets):
+    """fdnn_calculate_topk_raw and fdnn_calculate_topk_device at the smallest n that api.frame_chunks cuts in two, on the tiny
+    net: the second chunk's rows are spliced from row `cut` on (raw) or read at d_x + cut * D (device), and its pairs land at
+    cut * k of the caller's arrays -- the bytes of the same rows scored as two calls."""
+    import torch
+
+    from fast_dnn_amd import convert as CV
+
+    dnn, _, _ = nets("tiny")
+    n, k = 20480 + 1, 32
+    for chained in (True, False):
+        assert len(api.frame_chunks(n, chained)) == 2 and len(api.frame_chunks(n - 1, chained)) == 1
+    cut = api.frame_chunks(n, True)[1][0]
+
+    def in_two_calls(rows):
+        a, b = dnn.calculateTopK(rows[:cut], k), dnn.calculateTopK(rows[cut:], k)
+        return np.concatenate([a[0], b[0]]), np.concatenate([a[1], b[1]]).view(np.uint32)
+
+    raw = (np.random.default_rng(79).standard_normal((n, 39)) * 3).astype(np.float32)
+    dnn.setSplice(*KALDI)
+    try:
+        got = dnn.calculateTopKRaw(raw, k)
+    finally:
+        dnn.setSplice([], 0)
+    assert same(got, in_two_calls(CV.splice_frames(raw, KALDI[0], 432)), k)
+    x = F.synth_features(n, 432, seed=1301)
+    dx = torch.from_numpy(x).cuda()
+    dn = torch.full((n * k + 4,), -7, dtype=torch.int32, device="cuda")
+    dp = torch.full((n * k + 4,), -7.0, dtype=torch.float32, device="cuda")
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    dnn.calculate_topk_device(dx.data_ptr(), n, k, dn.data_ptr(), dp.data_ptr(), st.cuda_stream)
+    st.synchronize()
+    assert (dn[n * k:] == -7).all() and (dp[n * k:] == -7.0).all()
+    assert same((dn[:n * k].cpu().numpy().reshape(n, k), dp[:n * k].cpu().numpy().reshape(n, k)), in_two_calls(x), k)
+
+
 def test_a_hidden_only_stream_push(nets):
     dnn, _, _ = nets("mid")
     dnn.setSplice(*KALDI)

@@ -2,7 +2,7 @@
 to assembly (hipcc --cuda-device-only -S) with exactly the flags csrc/Makefile gives that file -- they are taken from
 `make -n`, not restated here -- and one line per kernel is printed: the code object's metadata (registers, spills, scratch,
 LDS), the number of instructions and of MFMAs, and a hash of the instruction stream with comments, labels and directives
-stripped.  The 256-VGPR kernels sit on a register-allocation knife edge (profiles/LABBOOK.md): a source change that is
+stripped and branch targets named by their block alone (not by the function's ordinal in its file).  The 256-VGPR kernels sit on a register-allocation knife edge (profiles/LABBOOK.md): a source change that is
 meant to be neutral is checked by comparing two such listings before any GPU time is spent.
 
 usage: kernel_resources.py [--csrc DIR] [--jobs N] [fdnn_chain.hip ...] > listing.txt
@@ -52,7 +52,8 @@ def kernels_of(asm):
         elif t.startswith(".Lfunc_end"):
             body = None
         elif body is not None and t and not t.startswith(".") and not t.endswith(":"):
-            body.append(" ".join(t.split()))
+            # (.LBB<function>_<block>: the function's ordinal in its file is no part of its code -- removing a kernel renumbers the rest)
+            body.append(re.sub(r"\.LBB\d+_", ".LBB_", " ".join(t.split())))
     out = {}
     for k in meta.values():
         name = k.get("name")

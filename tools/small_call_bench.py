@@ -1,6 +1,7 @@
 """Device-resident small calls back to back on one stream: us per call (the `small_batch` leg of bench.py uses the
-same loop).  FRAMES="8 100" REPS=2000 python tools/small_call_bench.py"""
-import os, sys, time
+same loop), then the same call host to host (fdnn_calculate: pageable frames in, rows out, where host overhead shows) with a
+digest of its rows, so that two builds can be compared.  FRAMES="8 100" REPS=2000 python tools/small_call_bench.py"""
+import hashlib, os, sys, time
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import torch
 from fast_dnn_amd import api, formats as F
@@ -18,4 +19,9 @@ for n in [int(a) for a in os.environ.get("FRAMES", "8 100").split()]:
     for _ in range(reps): dnn.calculate_device(big.data_ptr(), n, out.data_ptr(), s)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / reps
-    print(f"n={n:5d}  {dt * 1e6:8.1f} us/call", flush=True)
+    xh = big[:n].cpu().numpy()
+    for _ in range(50): rows = dnn.calculate(xh)
+    t0 = time.perf_counter()
+    for _ in range(reps): rows = dnn.calculate(xh)
+    dh = (time.perf_counter() - t0) / reps
+    print(f"n={n:5d}  {dt * 1e6:8.1f} us/call  host to host {dh * 1e6:8.1f} us/call  rows sha256 {hashlib.sha256(rows.tobytes()).hexdigest()[:16]}", flush=True)
