@@ -158,6 +158,22 @@ SIGNATURES = {
     "fdnn_debug_set_topk_kernel": (C.c_int, [C.c_int]),
     "fdnn_debug_topk_ref": (C.c_int, [_c_f32p, C.c_int, C.c_int, C.c_int, _c_i32p, _c_f32p]),
     "fdnn_debug_topk_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fdnn_pool_create": (C.c_void_p, [_c_i32p, C.c_int, C.c_int]),
+    "fdnn_pool_free": (None, [C.c_void_p]),
+    "fdnn_pool_width": (C.c_int, [C.c_void_p]),
+    "fdnn_pool_classes": (C.c_int, [C.c_void_p]),
+    "fdnn_pool_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fdnn_ctx_output_pool": (C.c_int, [C.c_void_p, C.c_void_p, _c_f32p]),
+    "fdnn_ctx_output_pool_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_pool": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_f32p]),
+    "fdnn_calculate_pool_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_f32p]),
+    "fdnn_calculate_pool_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_server_submit_pool": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_void_p, _c_f32p, C.POINTER(C.c_uint64)]),
+    "fdnn_server_submit_raw_pool": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_void_p, _c_f32p, C.POINTER(C.c_uint64)]),
+    "fdnn_debug_pool_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_set_pool_kernel": (C.c_int, [C.c_int]),
+    "fdnn_debug_pool_ref": (C.c_int, [_c_f32p, C.c_int, _c_i32p, C.c_int, C.c_int, _c_f32p]),
+    "fdnn_debug_pool_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_debug_scratch_count": (C.c_int, []),
@@ -515,6 +531,91 @@ def topk_limits():
     return int(a.value), int(b.value)
 
 
+# The class pooling's limits (fdnn_pool.hpp: kPoolLanes, kPoolResidentWidth; tests/test_pool_host.py holds the two files
+# together and compares both with fdnn_debug_pool_limits)
+POOL_LANES = 16
+POOL_RESIDENT_WIDTH = 16384
+
+
+class ClassPool:
+    """A node -> class map registered once (``fdnn_pool_create``): ``class_of`` int32 [width], every entry -1 (in no class)
+    or a class in [0, n_classes); validated on the host, its CSR uploaded to the device that is current.  Immutable; threads, contexts and scoring loops may share it; it must outlive every call and ticket that uses it."""
+
+    def __init__(self, class_of, n_classes: int):
+        co = np.ascontiguousarray(class_of, dtype=np.int32)
+        if co.ndim != 1:
+            raise ValueError("class_of must be a vector [width]")
+        self.handle = lib().fdnn_pool_create(co.ctypes.data_as(_c_i32p), co.size, int(n_classes))
+        if not self.handle:
+            # (the C call returns no status: a map it takes is one pool_ref's validation takes -- then the device refused)
+            bad_map = co.size < 1 or not 1 <= int(n_classes) <= co.size or bool(((co < -1) | (co >= int(n_classes))).any())
+            raise FdnnError(FDNN_E_ARG if bad_map else FDNN_E_DEVICE, lib().fdnn_last_error().decode(errors="replace"))
+        self.class_of = co.copy()
+
+    def width(self) -> int:
+        return int(lib().fdnn_pool_width(self.handle))
+
+    def classes(self) -> int:
+        return int(lib().fdnn_pool_classes(self.handle))
+
+    def rows_device(self, d_rows: int, n: int, d_out: int, stream: int = 0) -> None:
+        """The pooling alone (``fdnn_pool_rows_device``) on device-resident fp32 rows [n][width] -> d_out float32
+        [n][classes]; raw device pointers, enqueued on ``stream``, not synchronised."""
+        _check(lib().fdnn_pool_rows_device(self.handle, C.c_void_p(d_rows), int(n), C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def delete(self) -> None:
+        if self.handle:
+            lib().fdnn_pool_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.delete()
+        except Exception:
+            pass
+
+
+def pool_ref(rows, class_of, n_classes: int):
+    """The pooling from the host restatement (``fdnn_debug_pool_ref``; host code, no device) on rows [n][width] float32 (any
+    bit patterns) under the map class_of [width] -> float32 [n][n_classes]."""
+    r = np.ascontiguousarray(rows, dtype=np.float32)
+    co = np.ascontiguousarray(class_of, dtype=np.int32)
+    if r.ndim != 2 or co.ndim != 1 or co.size != r.shape[1]:
+        raise ValueError("rows must be [n][width] and class_of [width]")
+    out = np.empty((r.shape[0], max(int(n_classes), 0)), dtype=np.float32)
+    _check(lib().fdnn_debug_pool_ref(r.ctypes.data_as(_c_f32p), r.shape[0], co.ctypes.data_as(_c_i32p), co.size, int(n_classes), out.ctypes.data_as(_c_f32p)))
+    return out
+
+
+def pool_launches():
+    """Process-wide counts since load: (launches of the resident form of the pooling, of the streaming form)."""
+    buf = (C.c_ulonglong * 2)()
+    if lib().fdnn_debug_pool_launches(buf, 2) != 2:
+        raise RuntimeError("fdnn_debug_pool_launches")
+    return tuple(int(v) for v in buf)
+
+
+def set_pool_kernel(mode: int) -> None:
+    """Process-wide (``fdnn_debug_set_pool_kernel``): 0 the plan's rule, 1 resident where the width allows, 2 always streaming."""
+    _check(lib().fdnn_debug_set_pool_kernel(int(mode)))
+
+
+def pool_limits():
+    """(partial sums of a class, widest resident row) as the library was built (``fdnn_debug_pool_limits``)."""
+    a, b = C.c_int(), C.c_int()
+    _check(lib().fdnn_debug_pool_limits(C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
+def _pool_out(n: int, classes: int, out):
+    """The [n][C] result array of a pool call, made or checked."""
+    if out is None:
+        return np.empty((n, classes), dtype=np.float32)
+    if out.dtype != np.float32 or out.shape != (n, classes) or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous float32 array of shape {(n, classes)}")
+    return out
+
+
 def _topk_out(n: int, k: int, nodes, probs):
     """The [n][k] result arrays of a top-k call, made or checked."""
     if nodes is None:
@@ -713,6 +814,17 @@ class LazyContext:
     def calculateOutputTopKDevice(self, k: int, d_nodes: int, d_probs: int, stream: int = 0) -> None:
         """The same into device buffers [frames][k], enqueued on ``stream``, not synchronised (``fdnn_ctx_output_topk_device``)."""
         _check(lib().fdnn_ctx_output_topk_device(self.handle, int(k), C.c_void_p(d_nodes), C.c_void_p(d_probs), C.c_void_p(stream)))
+
+    def calculateOutputPool(self, pool: "ClassPool") -> np.ndarray:
+        """The dense output layer over the context's frames, of which only the class sums under ``pool`` come back
+        (``fdnn_ctx_output_pool``) -> float32 [frames][classes]."""
+        out = _pool_out(self.inputVectorCount, pool.classes(), None)
+        _check(lib().fdnn_ctx_output_pool(self.handle, pool.handle, out.ctypes.data_as(_c_f32p)))
+        return out
+
+    def calculateOutputPoolDevice(self, pool: "ClassPool", d_out: int, stream: int = 0) -> None:
+        """The same into a device buffer [frames][classes], enqueued on ``stream``, not synchronised (``fdnn_ctx_output_pool_device``)."""
+        _check(lib().fdnn_ctx_output_pool_device(self.handle, pool.handle, C.c_void_p(d_out), C.c_void_p(stream)))
 
     # device-resident forms (raw device pointers, e.g. ``tensor.data_ptr()``; enqueued on ``stream``)
     def calculateForOutputNodesBatchBits(self, bits, first: int = 0, out=None) -> np.ndarray:
@@ -1011,6 +1123,32 @@ class ScoringServer:
             raise ValueError(f"raw frames must be [n][{spec[1]}], got {r.shape}")
         return self._submit_topk(lib().fdnn_server_submit_raw_topk, r, int(k), nodes, probs)
 
+    def submitPool(self, x, pool: "ClassPool", out=None):
+        """One utterance's class posteriors through the loop (``fdnn_server_submit_pool``): coalesced with the other callers'
+        submissions under the SAME pool, the dense rows stay on the device -> (ticket, out float32 [n][classes]), valid after
+        ``wait(ticket)``; the bytes of ``QuantizedDnn.calculatePool``."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.dnn.inputDimension():
+            raise ValueError(f"Input vector size {x.shape[-1]} must be equal with network input size {self.dnn.inputDimension()}")
+        return self._submit_pool(lib().fdnn_server_submit_pool, x, pool, out)
+
+    def submitRawPool(self, raw, pool: "ClassPool", out=None):
+        """The same for raw feature frames [n][rawDim] of one utterance, spliced on the device by the model's splice spec at
+        submit time (``fdnn_server_submit_raw_pool``); the bytes of ``QuantizedDnn.calculatePoolRaw``."""
+        r = np.ascontiguousarray(raw, dtype=np.float32)
+        spec = self.dnn.spliceSpec()
+        if spec is not None and (r.ndim != 2 or r.shape[1] != spec[1]):
+            raise ValueError(f"raw frames must be [n][{spec[1]}], got {r.shape}")
+        return self._submit_pool(lib().fdnn_server_submit_raw_pool, r, pool, out)
+
+    def _submit_pool(self, fn, frames, pool, out):
+        n = frames.shape[0]
+        out = _pool_out(n, pool.classes(), out)
+        t = C.c_uint64()
+        _check(fn(self.handle, frames.ctypes.data_as(_c_f32p), n, pool.handle, out.ctypes.data_as(_c_f32p), C.byref(t)))
+        self._keep[int(t.value)] = (frames, pool, out)
+        return int(t.value), out
+
     def _submit_topk(self, fn, frames, k, nodes, probs):
         n = frames.shape[0]
         nodes, probs = _topk_out(n, k, nodes, probs)
@@ -1241,6 +1379,35 @@ class QuantizedDnn:
         float32 [n][k]; raw device pointers, enqueued on ``stream``, not synchronised."""
         _check(lib().fdnn_calculate_topk_device(self.nativeDnnHandle, C.c_void_p(d_x), int(n), int(k), C.c_void_p(d_nodes), C.c_void_p(d_probs),
                                                 C.c_void_p(stream)))
+
+    def calculatePool(self, input, pool: "ClassPool") -> np.ndarray:
+        """Dense scoring pooled over a node -> class map (``fdnn_calculate_pool``): of every frame's soft-max row the sum over
+        each class of ``pool``, added on the device in the contract's order (include/fdnn.h); only n x classes x 4 bytes come
+        back -> float32 [n][classes]."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        out = _pool_out(n, pool.classes(), None)
+        _check(lib().fdnn_calculate_pool(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(), pool.handle,
+                                         out.ctypes.data_as(_c_f32p)))
+        return out
+
+    calculate_pool = calculatePool
+
+    def calculatePoolRaw(self, raw, pool: "ClassPool") -> np.ndarray:
+        """``calculatePool`` on raw frames [n][rawDim] of one utterance, spliced on the device (``fdnn_calculate_pool_raw``)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError(f"raw frames must be [n][rawDim], got {r.shape}")
+        out = _pool_out(r.shape[0], pool.classes(), None)
+        _check(lib().fdnn_calculate_pool_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], pool.handle, out.ctypes.data_as(_c_f32p)))
+        return out
+
+    def calculate_pool_device(self, d_x: int, n: int, pool: "ClassPool", d_out: int, stream: int = 0) -> None:
+        """Device-resident form (``fdnn_calculate_pool_device``): d_x [n][inputDimension] -> d_out float32 [n][classes]; raw
+        device pointers, enqueued on ``stream``, not synchronised."""
+        _check(lib().fdnn_calculate_pool_device(self.nativeDnnHandle, C.c_void_p(d_x), int(n), pool.handle, C.c_void_p(d_out), C.c_void_p(stream)))
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))

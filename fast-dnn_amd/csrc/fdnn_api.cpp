@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -724,6 +725,139 @@ int fdnn_debug_topk_ref(const float *rows, int n, int width, int k, int32_t *nod
 int fdnn_debug_topk_limits(int *max_k, int *resident_width) {
   if (max_k) *max_k = fdnn::topk::kTopkMaxK;
   if (resident_width) *resident_width = fdnn::topk::kTopkResidentWidth;
+  return FDNN_OK;
+}
+
+// ---------------------------------------------------------------- dense output pooled over a node -> class map (fdnn_pool.hip)
+fdnn_pool *fdnn_pool_create(const int32_t *class_of, int width, int n_classes) {
+  const long long bad = fdnn::pool::check_map(class_of, width, n_classes);
+  if (bad < 0) {
+    fail(FDNN_E_ARG, "a pool is class_of [width] with 1 <= n_classes <= width <= " + std::to_string(fdnn::pool::kMaxWidth));
+    return nullptr;
+  }
+  if (bad > 0) {
+    fail(FDNN_E_ARG, "class_of[" + std::to_string(bad - 1) + "] = " + std::to_string(class_of[bad - 1]) + " is neither -1 nor a class in [0, " + std::to_string(n_classes) + ")");
+    return nullptr;
+  }
+  std::unique_ptr<fdnn_pool> p(new (std::nothrow) fdnn_pool);
+  if (!p) {
+    fail(FDNN_E_NOMEM, "out of memory");
+    return nullptr;
+  }
+  p->width = width, p->n_classes = n_classes;
+  p->csr = fdnn::pool::build_csr(class_of, width, n_classes);
+  const size_t words = p->csr.class_ptr.size() + p->csr.member.size();
+  hipError_t e = hipGetDevice(&p->device);
+  if (e == hipSuccess) e = p->d_csr.reserve(words);
+  if (e == hipSuccess) e = hipMemcpy(p->d_csr.p, p->csr.class_ptr.data(), sizeof(int32_t) * p->csr.class_ptr.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !p->csr.member.empty())
+    e = hipMemcpy(p->d_csr.p + p->csr.class_ptr.size(), p->csr.member.data(), sizeof(int32_t) * p->csr.member.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    fail(e == hipErrorOutOfMemory ? FDNN_E_NOMEM : FDNN_E_DEVICE, std::string("fdnn_pool_create: ") + hipGetErrorString(e));
+    return nullptr;
+  }
+  return p.release();
+}
+
+void fdnn_pool_free(fdnn_pool *pool) {
+  if (!pool) return;
+  DeviceGuard g(pool->device);  // (the CSR is freed on the device it lives on)
+  delete pool;
+}
+
+int fdnn_pool_width(const fdnn_pool *pool) { return pool ? pool->width : fail(FDNN_E_ARG, "null pool"); }
+int fdnn_pool_classes(const fdnn_pool *pool) { return pool ? pool->n_classes : fail(FDNN_E_ARG, "null pool"); }
+
+int fdnn_pool_rows_device(const fdnn_pool *pool, const float *d_rows, int n, float *d_out, void *stream) {
+  if (!pool || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;
+  if (!d_rows || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  DeviceGuard g(pool->device);
+  fdnn::launch_pool(d_rows, n, pool->width, pool->d_class_ptr(), pool->d_member(), pool->n_classes, d_out, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+int fdnn_ctx_output_pool_device(fdnn_ctx *c, const fdnn_pool *pool, float *d_out, void *stream) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (int rc = fdnn::check_pool(c->m, pool)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (c->n == 0) return FDNN_OK;
+  if (!d_out) return fail(FDNN_E_ARG, "null buffer");
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  if (!c->d_out) HIP_TRY(c->d_out.reserve(size_t(c->cap) * size_t(c->m->hm.hdr.out_dim)));  // (a lean context)
+  if (int rc = run_output(c, {.count = c->n, .d_out = c->d_out}, s)) return rc;
+  fdnn::launch_pool(c->d_out, c->n, c->m->hm.hdr.out_dim, pool->d_class_ptr(), pool->d_member(), pool->n_classes, d_out, s);
+  return FDNN_OK;
+}
+
+int fdnn_ctx_output_pool(fdnn_ctx *c, const fdnn_pool *pool, float *out) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (int rc = fdnn::check_pool(c->m, pool)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (c->n == 0) return FDNN_OK;
+  if (!out) return fail(FDNN_E_ARG, "null buffer");
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  if (!c->d_out) HIP_TRY(c->d_out.reserve(size_t(c->cap) * size_t(c->m->hm.hdr.out_dim)));  // (a lean context)
+  return dense_pass(c, {.pool = pool, .pooled = out}, c->stream, /*hidden=*/false);
+}
+
+int fdnn_calculate_pool(fdnn_model *m, const float *x, int n, int dim, const fdnn_pool *pool, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = fdnn::check_pool(m, pool)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  return score_chunks(m, frame_chunks(n, m), Pass::host_pool("fdnn_calculate_pool", x, pool, pool->n_classes, out));
+}
+
+int fdnn_calculate_pool_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_pool *pool, float *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  if (int rc = fdnn::splice_check(spec, raw_dim)) return rc;
+  if (int rc = fdnn::check_pool(m, pool)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
+  const std::vector<SpliceSeg> segs{SpliceSeg{0, 0, 0, n - 1}};  // (the whole utterance's raw frames travel once, as fdnn_calculate_raw's)
+  return score_chunks(m, frame_chunks(n, m), Pass::raw_pool("fdnn_calculate_pool_raw", {spec.get(), &segs, raw, n}, pool, pool->n_classes, out));
+}
+
+int fdnn_calculate_pool_device(fdnn_model *m, const float *d_x, int n, const fdnn_pool *pool, float *d_out, void *stream) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = fdnn::check_pool(m, pool)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!d_x || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_frames_aligned(d_x)) return rc;
+  return score_chunks(m, frame_chunks(n, m), Pass::device_pool("fdnn_calculate_pool_device", d_x, pool, pool->n_classes, d_out), static_cast<hipStream_t>(stream));
+}
+
+int fdnn_debug_pool_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 2, fdnn::pool_launch_counts); }
+
+int fdnn_debug_set_pool_kernel(int mode) {
+  if (mode < 0 || mode > 2) return fail(FDNN_E_ARG, "mode is 0 (the plan's rule), 1 (resident where the width allows) or 2 (streaming)");
+  fdnn::pool_kernel_mode(mode);
+  return FDNN_OK;
+}
+
+// The pooling in plain C++ (fdnn_pool.hpp: check_map, build_csr, ref), no device
+int fdnn_debug_pool_ref(const float *rows, int n, const int32_t *class_of, int width, int n_classes, float *out) {
+  if (n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (fdnn::pool::check_map(class_of, width, n_classes) != 0) return fail(FDNN_E_ARG, "class_of [width] holds -1 or a class in [0, n_classes), 1 <= n_classes <= width");
+  if (n == 0) return FDNN_OK;
+  if (!rows || !out) return fail(FDNN_E_ARG, "null buffer");
+  const fdnn::pool::Csr csr = fdnn::pool::build_csr(class_of, width, n_classes);
+  fdnn::pool::ref(reinterpret_cast<const uint32_t *>(rows), n, width, csr.class_ptr.data(), csr.member.data(), n_classes, reinterpret_cast<uint32_t *>(out));
+  return FDNN_OK;
+}
+
+int fdnn_debug_pool_limits(int *lanes, int *resident_width) {
+  if (lanes) *lanes = fdnn::pool::kPoolLanes;
+  if (resident_width) *resident_width = fdnn::pool::kPoolResidentWidth;
   return FDNN_OK;
 }
 

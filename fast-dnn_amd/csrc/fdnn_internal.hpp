@@ -84,6 +84,16 @@ struct fdnn_model {
   std::vector<ProfRec> prof;
 };
 
+// A node -> class map as the pooling reads it (fdnn_pool.hpp: pool::build_csr), on the host and on the device that was
+// current at fdnn_pool_create.  Immutable from then on: threads, contexts and scoring loops share it.
+struct fdnn_pool {
+  int width = 0, n_classes = 0, device = 0;
+  fdnn::pool::Csr csr;
+  fdnn::DevBuf<int32_t> d_csr;  // class_ptr [C + 1], then member [nnz]
+  const int32_t *d_class_ptr() const { return d_csr.p; }
+  const int32_t *d_member() const { return d_csr.p + n_classes + 1; }
+};
+
 struct fdnn_ctx {
   fdnn_model *m = nullptr;
   int n = 0;              // frames in use
@@ -127,6 +137,7 @@ struct fdnn_ctx {
   bool mask_bits_packed = false;    // run_output has packed the current call's byte masks into d_mask_bits
   fdnn::DevBuf<float> d_comp;       // host lazy batches: compacted result rows (allocated on first use)
   fdnn::DevBuf<int32_t> d_topk;     // host top-k calls: [n][k] nodes, then [n][k] values (allocated on first use, fdnn_topk.hip)
+  fdnn::DevBuf<float> d_pool;       // host pool calls: [n][C] class sums (allocated on first use, fdnn_pool.hip; not in ctx_layout)
   // host list calls (fdnn_ctx_lazy_output_lists, fdnn_calculate_lazy_lists): staging of the lists and their results,
   // allocated on the first list call and grown by the largest one
   fdnn::DevBuf<int32_t> d_lrow, d_lnodes;   // [count + 1], [nnz]
@@ -282,7 +293,8 @@ int copy_out(void *dst, const void *d_src, size_t bytes, hipStream_t s);
 // fused soft-max or chained launch that sat out its bounded wait left wrong.
 int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s);
 // The same pass with "what leaves the device" as the step that differs: the whole rows into out (k = 0), or the k
-// first-ranked nodes of every row and their values into nodes / probs [n][k] (fdnn_topk.hip) -- the rows stay in c->d_out.
+// first-ranked nodes of every row and their values into nodes / probs [n][k] (fdnn_topk.hip), or the rows' class sums under
+// `pool` into pooled [n][C] (fdnn_pool.hip) -- the rows stay in c->d_out.
 // hidden = false: the context holds the hidden activations already (fdnn_ctx_output_topk); the fused soft-max's re-run
 // applies, the chained launch's belongs to whoever ran the hidden layers.
 struct DenseTo {
@@ -290,6 +302,8 @@ struct DenseTo {
   int k = 0;
   int32_t *nodes = nullptr;
   float *probs = nullptr;
+  const fdnn_pool *pool = nullptr;
+  float *pooled = nullptr;
 };
 int dense_pass(fdnn_ctx *c, const DenseTo &to, hipStream_t s, bool hidden);
 // Lazy results of `count` frames (c->d_out) to a host caller, compacted over PCIe where that pays; d_bits / bits: the
@@ -310,6 +324,9 @@ int check_input_width(const fdnn_model *m, int dim);
 // (l0_small_kernel, fdnn_l0.hip), whose source address nothing establishes as free.  in_dim is a multiple of 4, so every row
 // and every chunk of rows keeps the alignment of the base.  FDNN_E_ARG before anything is launched.
 int check_frames_aligned(const float *d_x);
+// A pool call's handle against the model it is used with: the map's width is the model's output_dim, the CSR lives on the
+// model's device, and the model leads no device group.  FDNN_E_ARG before anything is launched.
+int check_pool(const fdnn_model *m, const fdnn_pool *pool);
 // The second half of a call through a model's batcher: `submitted` is what the submit call returned, *ticket what it filled in.
 inline int batcher_wait(fdnn_server *b, int submitted, const uint64_t *ticket) { return submitted ? submitted : fdnn_server_wait(b, *ticket); }
 // fdnn_calculate on the model's own device (the group path calls this per shard).

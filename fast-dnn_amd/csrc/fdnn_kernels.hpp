@@ -12,6 +12,7 @@
 #include "fdnn_set.hpp"
 #include "fdnn_sets.hpp"
 #include "fdnn_topk.hpp"
+#include "fdnn_pool.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -261,6 +262,15 @@ void launch_topk(const float *d_rows, int n, int width, int k, int32_t *d_nodes,
 void topk_launch_counts(unsigned long long out[2]);  // launches so far: resident form, streaming form
 int topk_kernel_mode();                              // fdnn_debug_set_topk_kernel: 0 the plan's rule, 1 resident where the width allows, 2 streaming
 void topk_kernel_mode(int mode);
+
+// The dense output pooled over a node -> class map (fdnn_pool.hip; the map, the order of the additions, the plan and the host
+// restatement: fdnn_pool.hpp): of every row [width] of d_rows [n] the sums over the classes of the CSR d_class_ptr
+// [n_classes + 1], d_member [nnz] (as pool::build_csr makes it) into d_out [n][n_classes].  No-op unless n > 0.  The form is
+// the plan's under fdnn_debug_set_pool_kernel's mode.
+void launch_pool(const float *d_rows, int n, int width, const int32_t *d_class_ptr, const int32_t *d_member, int n_classes, float *d_out, hipStream_t s);
+void pool_launch_counts(unsigned long long out[2]);  // launches so far: resident form, streaming form
+int pool_kernel_mode();                              // fdnn_debug_set_pool_kernel: 0 the plan's rule, 1 resident where the width allows, 2 streaming
+void pool_kernel_mode(int mode);
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

@@ -16,6 +16,9 @@
 // And the union path of the list calls (fdnn_lists_union.hip, fdnn_model_set_lists_union): counted by
 // fdnn_debug_lists_union_launches; as names "lists.union.build", "lists.union.score.nofix", "lists.union.score.fix" and
 // "lists.union.fallback" (its finish launch is the list path's and is counted there).
+// And the two kernels that run BEHIND a dense pass on its finished rows, the top-k selection (fdnn_topk.hip:
+// fdnn_debug_topk_launches) and the class pooling (fdnn_pool.hip: fdnn_debug_pool_launches), each counted by form; as names
+// "topk.resident", "topk.streaming", "pool.resident" and "pool.streaming".
 #pragma once
 #include <atomic>
 

@@ -793,9 +793,18 @@ void release_ctx(fdnn_ctx *c) {
 }
 
 // What leaves the device after a dense pass, synchronising s: the whole rows, or the selection of them (fdnn_topk.hip)
-// into the context's own pair buffer -- [n][k] nodes, then [n][k] values -- and its two halves to the caller's arrays.
+// into the context's own pair buffer -- [n][k] nodes, then [n][k] values -- and its two halves to the caller's arrays, or
+// their class sums (fdnn_pool.hip) into the context's own [n][C] buffer and from there to the caller's in one transfer.
 static int dense_leave(fdnn_ctx *c, const DenseTo &to, hipStream_t s) {
   const size_t n = size_t(c->n), O = size_t(c->m->hm.hdr.out_dim);
+  if (to.pool) {
+    const size_t nc = n * size_t(to.pool->n_classes);
+    HIP_TRY(c->d_pool.reserve(nc));
+    fdnn::launch_pool(c->d_out, c->n, int(O), to.pool->d_class_ptr(), to.pool->d_member(), to.pool->n_classes, c->d_pool, s);
+    HIP_TRY(hipMemcpyAsync(to.pooled, c->d_pool, sizeof(float) * nc, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FDNN_OK;
+  }
   if (to.k == 0) return copy_out(to.out, c->d_out, sizeof(float) * n * O, s);
   const size_t nk = n * size_t(to.k);
   HIP_TRY(c->d_topk.reserve(2 * nk));
@@ -919,6 +928,15 @@ int check_input_width(const fdnn_model *m, int dim) {
   return fail(FDNN_E_ARG, "input vector size " + std::to_string(dim) + " must be equal with network input size " + std::to_string(m->hm.hdr.in_dim));
 }
 
+int check_pool(const fdnn_model *m, const fdnn_pool *pool) {
+  if (!pool) return fail(FDNN_E_ARG, "null pool");
+  if (m->group) return fail(FDNN_E_ARG, "pool calls do not run on a model that leads a device group");
+  if (pool->width != m->hm.hdr.out_dim)
+    return fail(FDNN_E_ARG, "pool width " + std::to_string(pool->width) + " is not the network's output size " + std::to_string(m->hm.hdr.out_dim));
+  if (pool->device != m->device) return fail(FDNN_E_ARG, "the pool was created on another device than the model's");
+  return FDNN_OK;
+}
+
 int check_frames_aligned(const float *d_x) {
   if ((reinterpret_cast<uintptr_t>(d_x) & 15) == 0) return FDNN_OK;
   return fail(FDNN_E_ARG, "device frames must start on a 16-byte boundary (include/fdnn.h, Device buffers)");
@@ -940,6 +958,12 @@ static int to_host_behind_bits(fdnn_ctx *c, const pass::ChunkView &v, hipStream_
 static int to_device_topk(fdnn_ctx *c, const float *d_x, const pass::ChunkView &v, int k, hipStream_t s) {
   int rc = to_device_rows(c, d_x, v.cnt, nullptr, nullptr, c->d_out, s);
   if (!rc) fdnn::launch_topk(c->d_out, v.cnt, c->m->hm.hdr.out_dim, k, v.topk_nodes, v.topk_probs, s);
+  return rc;
+}
+// device pool: the rows stay in the context, their class sums go to the caller's buffer
+static int to_device_pool(fdnn_ctx *c, const float *d_x, const pass::ChunkView &v, const fdnn_pool *pool, hipStream_t s) {
+  int rc = to_device_rows(c, d_x, v.cnt, nullptr, nullptr, c->d_out, s);
+  if (!rc) fdnn::launch_pool(c->d_out, v.cnt, c->m->hm.hdr.out_dim, pool->d_class_ptr(), pool->d_member(), pool->n_classes, v.pooled, s);
   return rc;
 }
 // the chunk's entries through the host form, which synchronises (a sets chunk without a segment scores nothing)
@@ -989,6 +1013,8 @@ int run_chunks(fdnn_ctx *c, hipStream_t s, const pass::Chunks &chunks, const pas
       case Sink::host_set:
       case Sink::host_sets: rc = to_host_entries(c, p.sink, v, s); break;
       case Sink::device_sets: rc = to_device_sets(c, d_x, v, s); break;
+      case Sink::host_pool: rc = dense_pass(c, {.pool = p.sink.pool, .pooled = v.pooled}, s, true); break;  // n x C x 4 bytes cross PCIe
+      case Sink::device_pool: rc = to_device_pool(c, d_x, v, p.sink.pool, s); break;
     }
     if (rc) return rc;
   }

@@ -80,6 +80,8 @@ struct Slot {
   Buf<int32_t, true> d_nodes;     // ... and on the device; both grow to the largest set batch
   Buf<int32_t, true> d_topk;      // top-k batches: [rows][k_b] nodes, then [rows][k_b] values (the dense rows stay in d_out) ...
   Buf<int32_t> h_topk;            // ... and where both land on the host: ONE transfer per batch (pageable where pinned memory is refused)
+  Buf<float, true> d_pool;        // pool batches: [rows][C] class sums (the dense rows stay in d_out) ...
+  Buf<float> h_pool;              // ... and where they land on the host: ONE transfer per batch (pageable where pinned memory is refused)
   Buf<float> h_set;               // ... where its probs [nnz] and inactive values [rows] land: ONE transfer per batch (d_out holds both)
   BatchPlan batch;                // the current host batch: its pieces, where their frames are staged, how its rows return
   bool rows_on_host = false;      // its rows have been brought to h_out
@@ -173,6 +175,8 @@ struct BatchCall {
   int stride = 0;
   int32_t *d_topk = nullptr;   // top-k host batches: [n][topk_k] nodes, then [n][topk_k] values, selected from d_out
   int topk_k = 0;
+  const fdnn_pool *pool = nullptr;  // pool host batches: the batch's handle and [n][C] class sums of d_out
+  float *d_pool = nullptr;
 };
 int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *last_stream) {
   const int n = b.n, O = s->m->hm.hdr.out_dim;
@@ -182,6 +186,8 @@ int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *las
     // top-k host batches: one selection launch with the batch's k over the rows, which stay here
     if (b.d_topk && b.topk_k > 0)
       fdnn::launch_topk(b.d_out, n, O, b.topk_k, b.d_topk, reinterpret_cast<float *>(b.d_topk + size_t(n) * size_t(b.topk_k)), cs);
+    // pool host batches: one pooling launch over the rows, which stay here
+    if (b.pool && b.d_pool) fdnn::launch_pool(b.d_out, n, O, b.pool->d_class_ptr(), b.pool->d_member(), b.pool->n_classes, b.d_pool, cs);
   });
 }
 
@@ -243,7 +249,11 @@ void copy_ready_pieces(fdnn_server *s, std::unique_lock<std::mutex> &lk, Slot &s
     // bounce buffer and no second pass over the 32 KB per frame
     hipError_t ce = hipSuccess;
     const size_t stride = size_t(sl.batch.stride);  // (stable while the slot is in flight)
-    if (job.topk) {
+    if (job.pooled) {
+      // a pool piece: the batch's class sums came to the slot's landing buffer with the batch, C columns a row
+      const size_t C = size_t(sl.batch.pool_classes);
+      std::memcpy(job.pooled, sl.h_pool.p + size_t(job.row0) * C, sizeof(float) * size_t(job.rows) * C);
+    } else if (job.topk) {
       // a top-k piece: the batch's pairs came to the slot's landing buffer with the batch, k_b columns a row; this piece
       // keeps the first k of its rows (the top k is a prefix of the top k_b)
       const size_t kb = size_t(sl.batch.topk_k), k = size_t(job.topk), all = size_t(sl.batch.rows) * kb;
@@ -377,7 +387,7 @@ hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
   BatchPlan &b = sl.batch;
   // Whole rows of a batch that several callers share (1 GB of pinned memory per slot at most) go to the host in one transfer;
   // a single caller's batch, or one for which no pinned memory is to be had, leaves by per-caller copies from the device.
-  sl.rows_on_host = b.kind != kSet && b.kind != kTopk && b.stride == 0 && b.taken.size() > 1 && frames * O * sizeof(float) <= (size_t(1) << 30) &&
+  sl.rows_on_host = b.kind != kSet && b.kind != kTopk && b.kind != kPool && b.stride == 0 && b.taken.size() > 1 && frames * O * sizeof(float) <= (size_t(1) << 30) &&
                     sl.h_out.reserve(frames * O) == hipSuccess;
   if (b.kind == kBits) {
     // (advisor, round 5) no pinned memory to be had: pageable staging, the batch is not lost
@@ -405,6 +415,11 @@ hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
   if (b.kind == kTopk) {  // the pairs of the batch: grown to the largest batch, the landing buffer pageable if need be
     hipError_t e = sl.d_topk.reserve(2 * size_t(b.rows) * size_t(b.topk_k));
     if (e == hipSuccess) e = sl.h_topk.reserve(2 * size_t(b.rows) * size_t(b.topk_k), /*pageable_ok=*/true);
+    if (e != hipSuccess) return e;
+  }
+  if (b.kind == kPool) {  // the class sums of the batch: grown to the largest batch, the landing buffer pageable if need be
+    hipError_t e = sl.d_pool.reserve(size_t(b.rows) * size_t(b.pool_classes));
+    if (e == hipSuccess) e = sl.h_pool.reserve(size_t(b.rows) * size_t(b.pool_classes), /*pageable_ok=*/true);
     if (e != hipSuccess) return e;
   }
   if (!b.raw) return hipSuccess;
@@ -471,7 +486,7 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
   *rc = enqueue_batch(s, sl, {.d_x = c->d_x, .n = b.rows, .d_masks = !bits && b.any_mask ? c->d_mask : nullptr,
                               .d_bits = bits ? c->d_mask_bits : nullptr, .d_out = sl.d_out.p, .after = sl.staged,
                               .d_comp = sl.d_comp.p, .stride = b.stride, .d_topk = b.kind == kTopk ? sl.d_topk.p : nullptr,
-                              .topk_k = b.topk_k}, &last);
+                              .topk_k = b.topk_k, .pool = b.kind == kPool ? b.pool : nullptr, .d_pool = b.kind == kPool ? sl.d_pool.p : nullptr}, &last);
   if (*rc) return hipSuccess;
   if (last != sl.stream) {  // results leave on the slot's stream, behind the main stream's compute
     e = hipEventRecord(sl.gemm_done, last);
@@ -481,6 +496,8 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
     e = hipMemcpyAsync(sl.h_comp.p, sl.d_comp.p, sizeof(float) * rows * size_t(b.stride), hipMemcpyDeviceToHost, sl.stream);
   else if (e == hipSuccess && b.kind == kTopk)  // the pairs: to the host with the batch, the rows never leave the device
     e = hipMemcpyAsync(sl.h_topk.p, sl.d_topk.p, sizeof(int32_t) * 2 * rows * size_t(b.topk_k), hipMemcpyDeviceToHost, sl.stream);
+  else if (e == hipSuccess && b.kind == kPool)  // the class sums: to the host with the batch, the rows never leave the device
+    e = hipMemcpyAsync(sl.h_pool.p, sl.d_pool.p, sizeof(float) * rows * size_t(b.pool_classes), hipMemcpyDeviceToHost, sl.stream);
   else if (e == hipSuccess && sl.rows_on_host)
     e = hipMemcpyAsync(sl.h_out.p, sl.d_out.p, sizeof(float) * rows * O, hipMemcpyDeviceToHost, sl.stream);
   if (e == hipSuccess) e = hipEventRecord(sl.done, sl.stream);
@@ -788,6 +805,24 @@ int fdnn_server_submit_raw_topk(fdnn_server *s, const float *raw, int n, int k, 
   if (!fdnn::topk::args_ok(s->m->hm.hdr.out_dim, k)) return fail(FDNN_E_ARG, "k is 1 .. min(output_dim, 256)");
   if (!raw || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
   return submit_host(s, Request{.n = n, .raw = raw, .spec = spec, .raw_n = n, .raw_a = 0, .topk = k, .topk_nodes = nodes, .topk_probs = probs}, ticket);
+}
+
+int fdnn_server_submit_pool(fdnn_server *s, const float *x, int n, const fdnn_pool *pool, float *out, uint64_t *ticket) {
+  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
+  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
+  if (int rc = fdnn::check_pool(s->m, pool)) return rc;
+  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
+  return submit_host(s, Request{.x = x, .n = n, .pool = pool, .pool_classes = pool->n_classes, .pooled = out}, ticket);
+}
+
+int fdnn_server_submit_raw_pool(fdnn_server *s, const float *raw, int n, const fdnn_pool *pool, float *out, uint64_t *ticket) {
+  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
+  const fdnn::SpliceRef spec = s->m->splice;
+  if (int rc = fdnn::splice_check(spec, -1)) return rc;
+  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
+  if (int rc = fdnn::check_pool(s->m, pool)) return rc;
+  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
+  return submit_host(s, Request{.n = n, .raw = raw, .spec = spec, .raw_n = n, .raw_a = 0, .pool = pool, .pool_classes = pool->n_classes, .pooled = out}, ticket);
 }
 
 int fdnn_server_wait(fdnn_server *s, uint64_t ticket) {

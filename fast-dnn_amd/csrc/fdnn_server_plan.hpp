@@ -10,6 +10,8 @@
 
 #include "fdnn_splice_spec.hpp"
 
+struct fdnn_pool;  // (fdnn_internal.hpp: a node -> class map's handle; only its address travels here)
+
 namespace fdnn::plan {
 
 // A set submission's node set, copied at submit and shared by the request, its parts and their pieces (as SpliceRef is)
@@ -33,6 +35,9 @@ struct Piece {  // one caller's rows inside a coalesced batch
   int topk = 0;
   int32_t *topk_nodes = nullptr;
   float *topk_probs = nullptr;
+  // pool submissions (then out is null): the caller's [rows][C] destination of these rows (advanced by the frames earlier
+  // batches took); C is the batch's
+  float *pooled = nullptr;
 };
 
 struct Request {
@@ -56,6 +61,11 @@ struct Request {
   int topk = 0;
   int32_t *topk_nodes = nullptr;
   float *topk_probs = nullptr;
+  // pool submissions (then out, masks, bits, set and topk are null): every row's class sums under the map behind `pool`, which
+  // has pool_classes classes; results pooled [n][pool_classes]
+  const fdnn_pool *pool = nullptr;
+  int pool_classes = 0;
+  float *pooled = nullptr;
 };
 
 // raw batches, per piece: the raw frames it references, [first, first + count) of its utterance, at frame `at` of the slot's buffer
@@ -79,8 +89,10 @@ inline int widest_row(const uint64_t *bits, int n, size_t O) {
 // what a host batch carries: kinds do not share a batch, except that dense callers may ride in a byte-mask batch (all active)
 // -- and set requests (kSet: no output layer runs, fdnn_sets.hip scores each piece's set) share batches only with set requests
 // -- and top-k requests (kTopk: a dense batch whose rows stay on the device, fdnn_topk.hip selects from them) only with top-k requests
-enum BatchKind { kDense = 0, kBytes = 1, kBits = 2, kSet = 3, kTopk = 4 };
-inline int kind_of(const Request &r) { return r.topk ? kTopk : r.set ? kSet : r.bits ? kBits : r.masks ? kBytes : kDense; }
+// -- and pool requests (kPool: a dense batch whose rows stay on the device, fdnn_pool.hip sums them by class) only with pool
+// requests of the SAME handle
+enum BatchKind { kDense = 0, kBytes = 1, kBits = 2, kSet = 3, kTopk = 4, kPool = 5 };
+inline int kind_of(const Request &r) { return r.pool ? kPool : r.topk ? kTopk : r.set ? kSet : r.bits ? kBits : r.masks ? kBytes : kDense; }
 
 struct BatchPlan {
   std::vector<Request> taken;  // per piece: the request with .taken = first frame, .n = frames in THIS batch
@@ -92,6 +104,8 @@ struct BatchPlan {
   bool any_mask = false, raw = false;
   int nnz = 0, set_nodes = 0;  // set batches: the floats of the batch's probs (sum of rows x len) and the nodes of its pieces' sets
   int topk_k = 0;              // top-k batches: the largest k among its pieces (a smaller k's result is a prefix of it)
+  const fdnn_pool *pool = nullptr;  // pool batches: the one handle of all its pieces ...
+  int pool_classes = 0;             // ... and its class count
 };
 
 // Takes requests off the front of the queue, whole or in part, until the batch is full (max_frames rows) or the next one may
@@ -107,7 +121,8 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
       b.kind = rk;
       b.raw = r.raw != nullptr;
       b.spec = r.spec;
-    } else if ((rk == kBits) != (b.kind == kBits) || (rk == kSet) != (b.kind == kSet) || (rk == kTopk) != (b.kind == kTopk) || (r.raw != nullptr) != b.raw || r.spec != b.spec)
+      b.pool = r.pool, b.pool_classes = r.pool_classes;
+    } else if ((rk == kBits) != (b.kind == kBits) || (rk == kSet) != (b.kind == kSet) || (rk == kTopk) != (b.kind == kTopk) || (rk == kPool) != (b.kind == kPool) || r.pool != b.pool || (r.raw != nullptr) != b.raw || r.spec != b.spec)
       break;
     else if (rk == kBytes)
       b.kind = kBytes;
@@ -138,6 +153,8 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
       pc.topk_probs = r.topk_probs + size_t(part.taken) * size_t(r.topk);
       b.topk_k = std::max(b.topk_k, r.topk);
     }
+    if (rk == kPool)  // a later part of a split request continues at taken * C of the caller's array
+      b.pieces.back().pooled = r.pooled + size_t(part.taken) * size_t(r.pool_classes);
     if (b.raw) {  // the raw frames this piece's rows reference, and where they are staged
       const int u0 = r.raw_a + part.taken;  // the piece's first row as a frame of its utterance
       int fa, fb;

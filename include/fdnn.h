@@ -36,13 +36,13 @@
  *   d_x [n][input_dim], d_raw [n][raw_dim], d_masks [count][output_dim] bytes, d_bits [count][ceil(output_dim / 64)]
  *   words, d_out [n or count][output_dim] (row 0 of d_out / d_masks / d_bits is frame `first` of the call, not of the
  *   context), d_row_ptr [count + 1], d_nodes [nnz or len], d_probs [nnz], [count][len] or [n][k], d_inactive [count],
- *   d_nodes / d_vals of a top-k call [n][k], d_rows [n][width], d_ref / d_q [n][output_dim].  Nothing outside an input's
+ *   d_nodes / d_vals of a top-k call [n][k], d_rows [n][width], d_out of a pool call [n][C], d_ref / d_q [n][output_dim].  Nothing outside an input's
  *   extent reaches a result, NOTHING outside an output's extent is written (no padded row of a partial frame tile, no
  *   padded node of the last node tile), and every element of an output is written.  Inputs are never modified.
  *   Alignment: the natural alignment of the ELEMENT (4 bytes for fp32 / int32, 1 for mask bytes, 8 for bit words) is all
  *   any buffer needs -- a slice of a caller's tensor works as it is -- with one exception: d_x of the quantized net
- *   (fdnn_calculate_device, fdnn_calculate_lazy_bits_device, fdnn_calculate_topk_device, fdnn_ctx_forward_hidden_device,
- *   fdnn_server_submit_device) must start on a 16-BYTE boundary, because layer 0 moves the frames into LDS in 16-byte
+ *   (fdnn_calculate_device, fdnn_calculate_lazy_bits_device, fdnn_calculate_topk_device, fdnn_calculate_pool_device,
+ *   fdnn_ctx_forward_hidden_device, fdnn_server_submit_device) must start on a 16-BYTE boundary, because layer 0 moves the frames into LDS in 16-byte
  *   DMA pieces; input_dim is a multiple of 4, so every row and every sub-range of rows of such a buffer qualifies.  Frames
  *   that do not are FDNN_E_ARG before anything is launched.  (d_raw and the float net's d_x are read element by element:
  *   element alignment.)  Some kernels take a faster path where a buffer happens to sit on a 16-byte boundary; results
@@ -354,6 +354,57 @@ FDNN_API int fdnn_ctx_output_topk_device(fdnn_ctx *c, int k, int32_t *d_nodes, f
 FDNN_API int fdnn_calculate_topk(fdnn_model *m, const float *x, int n, int dim, int k, int32_t *nodes, float *probs);
 FDNN_API int fdnn_calculate_topk_raw(fdnn_model *m, const float *raw, int n, int raw_dim, int k, int32_t *nodes, float *probs);
 FDNN_API int fdnn_calculate_topk_device(fdnn_model *m, const float *d_x, int n, int k, int32_t *d_nodes, float *d_probs, void *stream);
+/* ------------------------------------------------------------------ dense output pooled over a node -> class map (fdnn_pool.hip)
+ * The dense soft-max summed on the DEVICE over classes of output nodes -- the silence posterior of a frame, phone posteriors
+ * out of senones, coarse pruning by phone class: n x C x 4 bytes instead of n x output_dim x 4 (192 bytes a frame at 48
+ * phones against 32 000).  The reference has no such call; this extends CalculateOutput (dnn.cc:428-454), as top-k does.
+ *
+ * The map: class_of[0 .. W) of int32 with 1 <= C <= W classes; class_of[i] in [0, C) puts node i into that class, -1 leaves it
+ * out of every class, anything else is FDNN_E_ARG.  Classes may be empty.  fdnn_pool_create validates on the host, builds the
+ * CSR (class_ptr [C + 1], member [nnz], sorted by class, then by node) and uploads it to the device that is CURRENT at that
+ * moment.  A handle is immutable; threads, contexts and scoring loops may share it; it must outlive every call and every
+ * ticket that uses it.  A call whose pool width differs from the row width (the model's output_dim), whose pool lives on
+ * another device than the model, or whose model leads a device group is FDNN_E_ARG before anything is launched.
+ *
+ * The sum, for a row p[0 .. W) of fp32 values and a class c with members m_0 < m_1 < ... < m_{L-1}:
+ *   s_j = +0.0f;  for t = j, j + 16, j + 32, ... (t < L):  s_j = s_j + p[m_t]          j = 0 .. 15
+ *   q_c = (((s_0+s_1)+(s_2+s_3)) + ((s_4+s_5)+(s_6+s_7))) + (((s_8+s_9)+(s_10+s_11)) + ((s_12+s_13)+(s_14+s_15)))
+ * every + one fp32 addition, round to nearest even, denormals kept.  An empty class gives +0.0f; a singleton returns its
+ * value's own bits (-0 becomes +0); a class with a NaN member, or with +inf and -inf together, returns A NaN (payload
+ * unspecified).  q[r][c] is a function of row r and the map alone: not of n, the row's position, the entry point, the batch
+ * it rode in or the kernel form.  Each member passes through at most d_c = ceil(L_c / 16) + 4 additions, the first exact:
+ *   |q_c - sum_{i in c} p_i| <= d_c u / (1 - d_c u) * sum_{i in c} |p_i|,  u = 2^-24.
+ * The width of sixteen partials (one DPP row of a gfx950 wave) is frozen: results depend on it.  Results are [n][C]
+ * row-major; every element is written, nothing outside is, inputs are never modified.  Nothing is routed here: the batcher,
+ * device groups and the JNI shim neither route to nor look at any of these entry points, and every other entry point keeps
+ * its bytes.
+ *
+ * fdnn_pool_create / _free / _width / _classes   the handle (NULL from create: see fdnn_last_error; extends CalculateOutput,
+ *   dnn.cc:428-454).
+ * fdnn_pool_rows_device       the pooling alone on any device-resident [n][width] fp32 rows of the pool's device (rows 4-byte
+ *   aligned; extends CalculateOutput, dnn.cc:428-454).  Enqueued on `stream`, not synchronised; n == 0 is a no-op;
+ *   FDNN_E_ARG for null pointers or width != the pool's.
+ * fdnn_ctx_output_pool        fdnn_ctx_output's computation (CalculateOutput, dnn.cc:428-454) into the context's own rows,
+ *   then the pooling; host buffer, host-synchronous.  FDNN_E_STATE before the hidden layers.  Works unchanged on
+ *   fdnn_stream_ctx(s) after a hidden-only push.
+ * fdnn_ctx_output_pool_device the same with a device buffer, enqueued on `stream`, ordered on the context like the other
+ *   *_device entries (CalculateOutput, dnn.cc:428-454).
+ * fdnn_calculate_pool         host to host on a pooled context, chunk by chunk like fdnn_calculate (Calculate,
+ *   dnn.cc:162-165): only n x C x 4 bytes cross PCIe.  Obeys the re-run rules of the dense host forms.
+ * fdnn_calculate_pool_raw     the same from raw feature frames, like fdnn_calculate_raw (Calculate, dnn.cc:162-165).
+ * fdnn_calculate_pool_device  device buffers (d_x 16-byte aligned like its siblings, d_out element-aligned), a pooled context
+ *   for the intermediate rows; enqueued, not synchronised (Calculate, dnn.cc:162-165). */
+typedef struct fdnn_pool fdnn_pool;
+FDNN_API fdnn_pool *fdnn_pool_create(const int32_t *class_of, int width, int n_classes);
+FDNN_API void fdnn_pool_free(fdnn_pool *pool);
+FDNN_API int fdnn_pool_width(const fdnn_pool *pool);
+FDNN_API int fdnn_pool_classes(const fdnn_pool *pool);
+FDNN_API int fdnn_pool_rows_device(const fdnn_pool *pool, const float *d_rows, int n, float *d_out, void *stream);
+FDNN_API int fdnn_ctx_output_pool(fdnn_ctx *c, const fdnn_pool *pool, float *out);
+FDNN_API int fdnn_ctx_output_pool_device(fdnn_ctx *c, const fdnn_pool *pool, float *d_out, void *stream);
+FDNN_API int fdnn_calculate_pool(fdnn_model *m, const float *x, int n, int dim, const fdnn_pool *pool, float *out);
+FDNN_API int fdnn_calculate_pool_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_pool *pool, float *out);
+FDNN_API int fdnn_calculate_pool_device(fdnn_model *m, const float *d_x, int n, const fdnn_pool *pool, float *d_out, void *stream);
 /* Last hidden layer's u8 activations, n x hidden_dim (quantized_activations_). */
 FDNN_API int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out);
 
@@ -427,6 +478,15 @@ FDNN_API int fdnn_server_submit_raw_set(fdnn_server *s, const float *raw, int n,
  * on the device by the model's spec at submit time. */
 FDNN_API int fdnn_server_submit_topk(fdnn_server *s, const float *x, int n, int k, int32_t *nodes, float *probs, uint64_t *ticket);
 FDNN_API int fdnn_server_submit_raw_topk(fdnn_server *s, const float *raw, int n, int k, int32_t *nodes, float *probs, uint64_t *ticket);
+/* One utterance's class posteriors through the loop (the pool contract above; CalculateOutput, dnn.cc:428-454, for many
+ * callers): pool submissions share a batch only with pool submissions of the SAME handle, the same rawness and the same
+ * spec; the batch runs as a dense batch, ONE pooling launch runs over the rows -- which never leave the device --, one
+ * transfer brings [rows][C] to the host, and each caller gets its rows.  Byte-identical to fdnn_calculate_pool /
+ * fdnn_calculate_pool_raw on the same utterance.  x or raw, out [n][C] and the handle must stay valid until the ticket
+ * completes.  fdnn_server_submit_raw_pool takes raw feature frames [n][D], spliced on the device by the model's spec at
+ * submit time. */
+FDNN_API int fdnn_server_submit_pool(fdnn_server *s, const float *x, int n, const fdnn_pool *pool, float *out, uint64_t *ticket);
+FDNN_API int fdnn_server_submit_raw_pool(fdnn_server *s, const float *raw, int n, const fdnn_pool *pool, float *out, uint64_t *ticket);
 FDNN_API int fdnn_server_wait(fdnn_server *s, uint64_t ticket);
 FDNN_API int fdnn_server_drain(fdnn_server *s);
 FDNN_API int fdnn_server_stats(fdnn_server *s, uint64_t *batches, uint64_t *frames, uint64_t *requests,
@@ -632,6 +692,20 @@ FDNN_API int fdnn_debug_topk_launches(unsigned long long *out, int cap);
 FDNN_API int fdnn_debug_set_topk_kernel(int mode);
 FDNN_API int fdnn_debug_topk_ref(const float *rows, int n, int width, int k, int32_t *nodes, float *vals);
 FDNN_API int fdnn_debug_topk_limits(int *max_k, int *resident_width);
+
+/* Dense output pooled over a node -> class map (CalculateOutput, dnn.cc:428-454), tests and tools.
+ * fdnn_debug_pool_launches    process-wide counts since load, returns 2: out[0] launches of the resident form (the row kept
+ *   in LDS), [1] of the streaming form (members gathered from memory).  Not in the launch recorder's table (fdnn_note.hpp).
+ * fdnn_debug_set_pool_kernel  process-wide: 0 the plan's rule (resident up to the resident width), 1 resident where the
+ *   width allows, 2 always streaming -- the same bytes either way (dnn.cc:428-454).
+ * fdnn_debug_pool_ref         the pooling of fdnn_pool_rows_device from the host restatement (fdnn_pool.hpp) on host rows
+ *   [n][width] under the map class_of [width], out [n][n_classes]; host code, no device needed (dnn.cc:428-454).
+ * fdnn_debug_pool_limits      the number of partial sums of a class and the widest resident row, as the kernels were built
+ *   (dnn.cc:428-454). */
+FDNN_API int fdnn_debug_pool_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_set_pool_kernel(int mode);
+FDNN_API int fdnn_debug_pool_ref(const float *rows, int n, const int32_t *class_of, int width, int n_classes, float *out);
+FDNN_API int fdnn_debug_pool_limits(int *lanes, int *resident_width);
 
 /* Tests: write the word a fused soft-max workgroup raises (in host memory) when it gives up waiting for its frame tile's
  * siblings -- 1: as if a launch of this model had just done so (from the next call on the model runs the unfused soft-max

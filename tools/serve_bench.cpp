@@ -13,6 +13,10 @@
 //         topk       = fdnn_calculate_topk per utterance: the TOPK_K (environment, 32) best nodes of every frame, chosen on the
 //                      device -- frames x TOPK_K x 8 bytes back instead of frames x output_dim x 4
 //         topkserver = fdnn_server_submit_topk + fdnn_server_wait (top-k utterances coalesced, the dense rows stay on the device)
+//         pool       = fdnn_calculate_pool per utterance: every frame's soft-max summed on the device over POOL_C (environment,
+//                      48) classes of nodes (node i in class i mod POOL_C) -- frames x POOL_C x 4 bytes back
+//         poolserver = fdnn_server_submit_pool + fdnn_server_wait (pool utterances of the one handle coalesced, the dense rows
+//                      stay on the device)
 // SET_LEN=k with lazy / lazyserver: the masks are those sets (the same k nodes in every frame of a caller) instead of 40 %.
 // INFLIGHT=k (environment, server modes): every caller keeps k utterances in flight (k result blocks per thread) instead of
 // waiting for each one before submitting the next.
@@ -52,7 +56,9 @@ int main(int argc, char **argv) {
   const int set_len = std::getenv("SET_LEN") ? std::atoi(std::getenv("SET_LEN")) : (sets ? 80 : 0);
   const bool topk = mode == "topk" || mode == "topkserver";
   const int topk_k = std::getenv("TOPK_K") ? std::atoi(std::getenv("TOPK_K")) : 32;
-  if ((mode == "server" || mode == "lazyserver" || mode == "setserver" || mode == "topkserver") && fdnn_server_create(m, max_frames, depth, &srv)) {
+  const bool pooled = mode == "pool" || mode == "poolserver";
+  const int pool_c = std::getenv("POOL_C") ? std::atoi(std::getenv("POOL_C")) : 48;
+  if ((mode == "server" || mode == "lazyserver" || mode == "setserver" || mode == "topkserver" || mode == "poolserver") && fdnn_server_create(m, max_frames, depth, &srv)) {
     std::fprintf(stderr, "server: %s\n", fdnn_last_error());
     return 1;
   }
@@ -105,6 +111,17 @@ int main(int argc, char **argv) {
       top_nodes[size_t(t)].assign(size_t(F) * size_t(topk_k), 0);
       top_probs[size_t(t)].assign(size_t(F) * size_t(topk_k), 0.0f);
     }
+  }
+  fdnn_pool *pool = nullptr;  // pool modes: one handle for every caller, per thread [F][pool_c] class sums
+  std::vector<std::vector<float>> pool_out(static_cast<size_t>(T));
+  if (pooled) {
+    std::vector<int32_t> class_of(static_cast<size_t>(O));
+    for (int i = 0; i < O; ++i) class_of[size_t(i)] = pool_c > 0 ? i % pool_c : 0;
+    if (inflight > 1 || !(pool = fdnn_pool_create(class_of.data(), O, pool_c))) {
+      std::fprintf(stderr, "pool: %s (POOL_C is 1 .. output dimension; the pool modes keep one utterance per caller in flight)\n", fdnn_last_error());
+      return 1;
+    }
+    for (int t = 0; t < T; ++t) pool_out[size_t(t)].assign(size_t(F) * size_t(pool_c), 0.0f);
   }
   if (lazy && set_len > 0) {
     for (int t = 0; t < T; ++t) {
@@ -167,6 +184,14 @@ int main(int argc, char **argv) {
         } else {
           rc = fdnn_calculate_topk(m, xs[size_t(t)].data(), F, D, topk_k, top_nodes[size_t(t)].data(), top_probs[size_t(t)].data());
         }
+      } else if (pooled) {
+        if (srv) {
+          uint64_t ticket = 0;
+          rc = fdnn_server_submit_pool(srv, xs[size_t(t)].data(), F, pool, pool_out[size_t(t)].data(), &ticket);
+          if (!rc) rc = fdnn_server_wait(srv, ticket);
+        } else {
+          rc = fdnn_calculate_pool(m, xs[size_t(t)].data(), F, D, pool, pool_out[size_t(t)].data());
+        }
       } else if (srv && lazy) {
         uint64_t ticket = 0;
         rc = fdnn_server_submit_lazy_bits(srv, xs[size_t(t)].data(), F, bits[size_t(t)].data(), outs[size_t(t)].data(), &ticket);
@@ -206,6 +231,10 @@ int main(int argc, char **argv) {
     sum = 0.0;
     for (int j = 0; j < topk_k; ++j) sum += top_probs[0][size_t(j)];
   }
+  if (pooled) {  // row 0's class sums: every node is in a class, so they add up to the row's total
+    sum = 0.0;
+    for (int j = 0; j < pool_c; ++j) sum += pool_out[0][size_t(j)];
+  }
   uint64_t batches = 0, frames = 0, reqs = 0, coal = 0;
   if (srv) fdnn_server_stats(srv, &batches, &frames, &reqs, &coal);
   std::printf("{\"mode\": \"%s\", \"threads\": %d, \"frames_per_utt\": %d, \"utts\": %d, \"seconds\": %.4f, \"utts_per_s\": %.1f, "
@@ -213,6 +242,7 @@ int main(int argc, char **argv) {
               mode.c_str(), T, F, T * U, sec, T * U / sec, double(T) * U * F / sec, sum, failed.load(), (unsigned long long)batches,
               (unsigned long long)reqs);
   if (srv) fdnn_server_free(srv);
+  fdnn_pool_free(pool);
   fdnn_model_free(m);
   return failed.load() ? 1 : 0;
 }
