@@ -31,6 +31,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -78,13 +79,12 @@ struct Slot {
   Buf<float> h_raw;               // raw batches: the pieces' raw frames back to back; grows to the largest raw batch
   Buf<int32_t> h_nodes;           // set batches: the pieces' sets back to back (pageable where pinned memory is refused) ...
   Buf<int32_t, true> d_nodes;     // ... and on the device; both grow to the largest set batch
-  Buf<int32_t, true> d_topk;      // top-k batches: [rows][k_b] nodes, then [rows][k_b] values (the dense rows stay in d_out) ...
-  Buf<int32_t> h_topk;            // ... and where both land on the host: ONE transfer per batch (pageable where pinned memory is refused)
-  Buf<float, true> d_pool;        // pool batches: [rows][C] class sums (the dense rows stay in d_out) ...
-  Buf<float> h_pool;              // ... and where they land on the host: ONE transfer per batch (pageable where pinned memory is refused)
-  Buf<float> h_set;               // ... where its probs [nnz] and inactive values [rows] land: ONE transfer per batch (d_out holds both)
-  BatchPlan batch;                // the current host batch: its pieces, where their frames are staged, how its rows return
-  bool rows_on_host = false;      // its rows have been brought to h_out
+  // A batch has one form, so one pair serves every form whose results are not rows: 32-bit words, both grow to the largest batch
+  Buf<uint32_t, true> d_res;      // top-k batches: [rows][k_b] nodes, then [rows][k_b] values; pool batches: [rows][C] class sums (the dense rows stay in d_out)
+  Buf<uint32_t> h_land;           // where they, or a set batch's probs [nnz] and inactive values [rows] (d_out holds both), land on the host:
+                                  // ONE transfer per batch (pageable where pinned memory is refused)
+  BatchPlan batch;                // the current host batch: its pieces, where their frames are staged, its form
+  const void *landing = nullptr;  // where its one transfer lands (launch_batch): h_out, h_comp or h_land
   int pieces_left = 0;            // pieces not copied out yet
   bool in_flight = false;         // host batch enqueued, not yet scattered
 };
@@ -164,47 +164,6 @@ int enqueue_pass(fdnn_server *s, Slot &sl, int n, hipEvent_t after, const fdnn::
   return FDNN_OK;
 }
 
-struct BatchCall {
-  const float *d_x = nullptr;
-  int n = 0;
-  const int8_t *d_masks = nullptr;  // one mask or none
-  const uint64_t *d_bits = nullptr;
-  float *d_out = nullptr;
-  hipEvent_t after = nullptr;  // (may be null) see enqueue_pass
-  float *d_comp = nullptr;     // bit-mask host batches: the rows compacted, `stride` floats each
-  int stride = 0;
-  int32_t *d_topk = nullptr;   // top-k host batches: [n][topk_k] nodes, then [n][topk_k] values, selected from d_out
-  int topk_k = 0;
-  const fdnn_pool *pool = nullptr;  // pool host batches: the batch's handle and [n][C] class sums of d_out
-  float *d_pool = nullptr;
-};
-int enqueue_batch(fdnn_server *s, Slot &sl, const BatchCall &b, hipStream_t *last_stream) {
-  const int n = b.n, O = s->m->hm.hdr.out_dim;
-  return enqueue_pass(s, sl, n, b.after, fdnn::pass::Pass::loop_rows(b.d_x, b.d_masks, b.d_bits, b.d_out), last_stream, [&](hipStream_t cs) {
-    // bit-mask host batches: the rows compacted (active probabilities + one value per frame) for the trip over PCIe
-    if (b.d_bits && b.d_comp && b.stride > 0) fdnn::launch_lazy_compact(b.d_out, b.d_bits, b.d_comp, n, O, b.stride, cs);
-    // top-k host batches: one selection launch with the batch's k over the rows, which stay here
-    if (b.d_topk && b.topk_k > 0)
-      fdnn::launch_topk(b.d_out, n, O, b.topk_k, b.d_topk, reinterpret_cast<float *>(b.d_topk + size_t(n) * size_t(b.topk_k)), cs);
-    // pool host batches: one pooling launch over the rows, which stay here
-    if (b.pool && b.d_pool) fdnn::launch_pool(b.d_out, n, O, b.pool->d_class_ptr(), b.pool->d_member(), b.pool->n_classes, b.d_pool, cs);
-  });
-}
-
-// Enqueue one SET batch that is already on the device (kSet): the hidden layers as enqueue_batch runs them, then the pieces'
-// sets as the segments of ONE sets call per chunk (fdnn::run_sets) -- no output layer.  probs go to d_out [nnz], the
-// inactive values behind them [rows].
-int enqueue_set_batch(fdnn_server *s, Slot &sl, hipEvent_t after, hipStream_t *last_stream) {
-  const BatchPlan &b = sl.batch;
-  // the pieces as the tables of a sets call over the batch's rows
-  std::vector<int32_t> seg_rows, set_ptr;
-  for (const Piece &p : b.pieces) seg_rows.push_back(p.row0), set_ptr.push_back(p.set_off);
-  seg_rows.push_back(b.rows), set_ptr.push_back(b.set_nodes);
-  const fdnn::sets::Tables t{seg_rows.data(), set_ptr.data(), int(b.pieces.size())};
-  return enqueue_pass(s, sl, b.rows, after, fdnn::pass::Pass::loop_sets(sl.ctx->d_x, t, sl.d_nodes.p, sl.d_out.p, sl.d_out.p + size_t(b.nnz)), last_stream,
-                      [](hipStream_t) {});
-}
-
 // A batch carrying `ticket` failed: whatever of that request is still queued will never be packed (the packer would read
 // caller memory that the caller, told of the failure, is free to release).  Call with qmu held.
 void drop_queued_rest(fdnn_server *s, uint64_t ticket) {
@@ -245,41 +204,18 @@ void copy_ready_pieces(fdnn_server *s, std::unique_lock<std::mutex> &lk, Slot &s
     p.state = 2;
     const Piece job = p;  // the vector is stable while in_flight, but copy what the unlocked part needs anyway
     lk.unlock();
-    // straight from the slot's device buffer into the caller's memory, on the copying thread's own stream: no pinned
-    // bounce buffer and no second pass over the 32 KB per frame
     hipError_t ce = hipSuccess;
-    const size_t stride = size_t(sl.batch.stride);  // (stable while the slot is in flight)
-    if (job.pooled) {
-      // a pool piece: the batch's class sums came to the slot's landing buffer with the batch, C columns a row
-      const size_t C = size_t(sl.batch.pool_classes);
-      std::memcpy(job.pooled, sl.h_pool.p + size_t(job.row0) * C, sizeof(float) * size_t(job.rows) * C);
-    } else if (job.topk) {
-      // a top-k piece: the batch's pairs came to the slot's landing buffer with the batch, k_b columns a row; this piece
-      // keeps the first k of its rows (the top k is a prefix of the top k_b)
-      const size_t kb = size_t(sl.batch.topk_k), k = size_t(job.topk), all = size_t(sl.batch.rows) * kb;
-      for (size_t r = 0; r < size_t(job.rows); ++r) {
-        const int32_t *src = sl.h_topk.p + (size_t(job.row0) + r) * kb;
-        std::memcpy(job.topk_nodes + r * k, src, sizeof(int32_t) * k);
-        std::memcpy(job.topk_probs + r * k, src + all, sizeof(float) * k);
-      }
-    } else if (job.set) {
-      // a set piece: its block of probs and its inactive values came to the slot's landing buffer with the batch
-      const size_t len = job.set->size();
-      if (len) std::memcpy(job.probs, sl.h_set.p + size_t(job.block_off), sizeof(float) * size_t(job.rows) * len);
-      std::memcpy(job.inactive, sl.h_set.p + size_t(sl.batch.nnz) + size_t(job.row0), sizeof(float) * size_t(job.rows));
-    } else if (job.bits && stride > 0) {
-      // lazy rows, compacted: the batch's rows arrived in the slot's pinned buffer with the batch (one transfer, enqueued
-      // behind the compaction); THIS thread -- the caller's own, normally, so that sixteen callers work side by side --
-      // expands its rows into the caller's block (fdnn::lazy_expand_rows_from)
-      fdnn::lazy_expand_rows_from(job.out, sl.h_comp.p + size_t(job.row0) * stride, job.rows, O, stride, job.bits);
-    } else if (sl.rows_on_host) {
-      // whole rows of a coalesced batch: they came to the slot's pinned buffer with the batch; this thread moves its own
-      std::memcpy(job.out, sl.h_out.p + size_t(job.row0) * O, sizeof(float) * size_t(job.rows) * O);
-    } else {
+    if (sl.batch.form.leave == Form::by_caller_copies) {  // (the batch's form is stable while the slot is in flight)
+      // a single caller's whole rows: straight from the slot's device buffer into the caller's memory, on the copying
+      // thread's own stream -- no pinned bounce buffer and no second pass over the 32 KB per frame
       DeviceGuard dg(s->m->device);
-      ce = hipMemcpyAsync(job.out, sl.d_out.p + size_t(job.row0) * O, sizeof(float) * size_t(job.rows) * O, hipMemcpyDeviceToHost,
+      ce = hipMemcpyAsync(job.want.out, sl.d_out.p + size_t(job.row0) * O, sizeof(float) * size_t(job.rows) * O, hipMemcpyDeviceToHost,
                           hipStreamPerThread);
       if (ce == hipSuccess) ce = hipStreamSynchronize(hipStreamPerThread);
+    } else {
+      // the piece's part of the batch's one transfer, which came to the slot's landing buffer with the batch; compacted lazy
+      // rows are expanded by THIS thread -- the caller's own, normally, so that sixteen callers work side by side
+      scatter(sl.batch, job, sl.landing, O, fdnn::lazy_expand_rows_from);
     }
     lk.lock();
     sl.batch.pieces[i].state = 3;
@@ -311,28 +247,32 @@ bool stage_one(fdnn_server *s, std::unique_lock<std::mutex> &lk) {
   const int i = s->stage.next++;
   Slot &sl = *s->stage.sl;
   const Request r = sl.batch.taken[size_t(i)];
-  const int r0 = sl.batch.pieces[size_t(i)].row0, kind = sl.batch.kind;
-  const bool any_mask = sl.batch.any_mask;
+  const Piece &pc = sl.batch.pieces[size_t(i)];  // (the vector, the piece's rows and its Want are stable while the slot is in flight)
+  const Form::Upload upload = sl.batch.form.upload;
   lk.unlock();
   const fdnn::BlobHeader &h = s->m->hm.hdr;
-  const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64;
-  if (r.raw) {
-    const size_t RD = size_t(sl.batch.spec->raw_dim);
-    const RawSrc src = sl.batch.raw_src[size_t(i)];
-    std::memcpy(sl.h_raw.p + size_t(src.at) * RD, r.raw + size_t(src.first) * RD, sizeof(float) * size_t(src.count) * RD);
-  } else {
-    std::memcpy(sl.h_x.p + size_t(r0) * D, r.x + size_t(r.taken) * D, sizeof(float) * size_t(r.n) * D);
+  const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64, r0 = size_t(pc.row0), rows = size_t(pc.rows);
+  switch (r.frames.kind) {
+    case Frames::raw_frames: {
+      const size_t RD = size_t(sl.batch.spec->raw_dim);
+      const RawSrc src = sl.batch.raw_src[size_t(i)];
+      std::memcpy(sl.h_raw.p + size_t(src.at) * RD, r.frames.raw + size_t(src.first) * RD, sizeof(float) * size_t(src.count) * RD);
+      break;
+    }
+    case Frames::host_rows: std::memcpy(sl.h_x.p + r0 * D, r.frames.x + size_t(r.taken) * D, sizeof(float) * rows * D); break;
   }
-  if (kind == kSet) {
-    const Piece &pc = sl.batch.pieces[size_t(i)];  // (stable while the slot is in flight)
-    if (!pc.set->empty()) std::memcpy(sl.h_nodes.p + size_t(pc.set_off), pc.set->data(), sizeof(int32_t) * pc.set->size());
-  } else if (kind == kBits && sl.h_bits.p) {  // (only bit-mask requests are in such a batch)
-    std::memcpy(sl.h_bits.p + size_t(r0) * wpr, r.bits + size_t(r.taken) * wpr, sizeof(uint64_t) * size_t(r.n) * wpr);
-  } else if (any_mask) {
-    if (r.masks)
-      std::memcpy(sl.h_mask.p + size_t(r0) * O, r.masks + size_t(r.taken) * O, size_t(r.n) * O);
-    else
-      std::memset(sl.h_mask.p + size_t(r0) * O, 1, size_t(r.n) * O);  // dense caller inside a lazy batch: all active
+  switch (upload) {  // what goes up beside the frames: this piece's part of it
+    case Form::no_upload: break;
+    case Form::node_sets:
+      if (!pc.want.nodes->empty()) std::memcpy(sl.h_nodes.p + size_t(pc.set_off), pc.want.nodes->data(), sizeof(int32_t) * pc.want.nodes->size());
+      break;
+    case Form::bit_words: std::memcpy(sl.h_bits.p + r0 * wpr, pc.want.bits, sizeof(uint64_t) * rows * wpr); break;
+    case Form::byte_masks:
+      if (pc.want.kind == Want::rows_behind_bytes)
+        std::memcpy(sl.h_mask.p + r0 * O, pc.want.masks, rows * O);
+      else
+        std::memset(sl.h_mask.p + r0 * O, 1, rows * O);  // dense caller inside a byte-mask batch: all active
+      break;
   }
   lk.lock();
   if (++s->stage.done == s->stage.total) s->stage_cv.notify_all();
@@ -381,49 +321,50 @@ void plan_into_slot(fdnn_server *s, Slot &sl) {
   sl.in_flight = true;
 }
 
-// The staging buffers this batch needs beyond the slot's fixed ones, each by its own rule.
+// The staging buffers this batch needs beyond the slot's fixed ones, each by its own rule; the sizes are the form's.  Where
+// the room a form's transfer needs is refused, the batch is not lost: its rows leave by per-caller copies.
 hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
   const size_t O = size_t(s->m->hm.hdr.out_dim), frames = size_t(s->max_frames);
   BatchPlan &b = sl.batch;
-  // Whole rows of a batch that several callers share (1 GB of pinned memory per slot at most) go to the host in one transfer;
-  // a single caller's batch, or one for which no pinned memory is to be had, leaves by per-caller copies from the device.
-  sl.rows_on_host = b.kind != kSet && b.kind != kTopk && b.kind != kPool && b.stride == 0 && b.taken.size() > 1 && frames * O * sizeof(float) <= (size_t(1) << 30) &&
-                    sl.h_out.reserve(frames * O) == hipSuccess;
-  if (b.kind == kBits) {
-    // (advisor, round 5) no pinned memory to be had: pageable staging, the batch is not lost
-    if (sl.h_bits.reserve(frames * ((O + 63) / 64), /*pageable_ok=*/true) != hipSuccess) return hipErrorOutOfMemory;
-    const size_t need = frames * (O * 3 / 4 + 1);
-    if (b.stride > 0 && sl.d_comp.count < need) {
-      // both halves or neither, the old pair kept until the new one stands; a failure is not the batch's: its rows go back whole
-      Buf<float, true> d_new;
-      Buf<float> h_new;
-      if (d_new.reserve(need) == hipSuccess && h_new.reserve(need) == hipSuccess) {
-        sl.d_comp.swap(d_new);
-        sl.h_comp.swap(h_new);
-      } else {
-        (void)hipGetLastError();
-        b.stride = 0;
+  const Form &f = b.form;
+  hipError_t e = hipSuccess;
+  switch (b.kind) {
+    case Want::rows:
+    case Want::rows_behind_bytes: break;  // (byte masks are staged in h_mask, one of the fixed buffers)
+    case Want::rows_behind_bits: {
+      // (advisor, round 5) no pinned memory to be had: pageable staging, the batch is not lost
+      if (sl.h_bits.reserve(frames * ((O + 63) / 64), /*pageable_ok=*/true) != hipSuccess) return hipErrorOutOfMemory;
+      const size_t need = frames * (O * 3 / 4 + 1);
+      if (f.leave == Form::compacted_rows && sl.d_comp.count < need) {
+        // both halves or neither, the old pair kept until the new one stands; a failure is not the batch's: its rows go back whole
+        Buf<float, true> d_new;
+        Buf<float> h_new;
+        if (d_new.reserve(need) == hipSuccess && h_new.reserve(need) == hipSuccess) {
+          sl.d_comp.swap(d_new);
+          sl.h_comp.swap(h_new);
+        } else {
+          (void)hipGetLastError();
+          leave_by_caller_copies(b);
+        }
       }
+      break;
     }
+    case Want::set:  // the sets up, probs and inactive values back: grown to the largest batch, pageable if need be
+      e = sl.h_nodes.reserve(std::max<size_t>(size_t(b.set_nodes), 1), /*pageable_ok=*/true);
+      if (e == hipSuccess) e = sl.d_nodes.reserve(std::max<size_t>(size_t(b.set_nodes), 1));
+      if (e == hipSuccess) e = sl.h_land.reserve(f.words, /*pageable_ok=*/true);
+      break;
+    case Want::topk:
+    case Want::pool:  // the pairs or the class sums of the batch: grown to the largest batch, the landing buffer pageable if need be
+      e = sl.d_res.reserve(f.words);
+      if (e == hipSuccess) e = sl.h_land.reserve(f.words, /*pageable_ok=*/true);
+      break;
   }
-  if (b.kind == kSet) {  // the sets up, probs and inactive values back: grown to the largest batch, pageable if need be
-    hipError_t e = sl.h_nodes.reserve(std::max<size_t>(size_t(b.set_nodes), 1), /*pageable_ok=*/true);
-    if (e == hipSuccess) e = sl.d_nodes.reserve(std::max<size_t>(size_t(b.set_nodes), 1));
-    if (e == hipSuccess) e = sl.h_set.reserve(size_t(b.nnz) + size_t(b.rows), /*pageable_ok=*/true);
-    if (e != hipSuccess) return e;
-  }
-  if (b.kind == kTopk) {  // the pairs of the batch: grown to the largest batch, the landing buffer pageable if need be
-    hipError_t e = sl.d_topk.reserve(2 * size_t(b.rows) * size_t(b.topk_k));
-    if (e == hipSuccess) e = sl.h_topk.reserve(2 * size_t(b.rows) * size_t(b.topk_k), /*pageable_ok=*/true);
-    if (e != hipSuccess) return e;
-  }
-  if (b.kind == kPool) {  // the class sums of the batch: grown to the largest batch, the landing buffer pageable if need be
-    hipError_t e = sl.d_pool.reserve(size_t(b.rows) * size_t(b.pool_classes));
-    if (e == hipSuccess) e = sl.h_pool.reserve(size_t(b.rows) * size_t(b.pool_classes), /*pageable_ok=*/true);
-    if (e != hipSuccess) return e;
-  }
+  if (e != hipSuccess) return e;
+  // whole rows of a batch that several callers share land in pinned memory only
+  if (f.leave == Form::whole_rows && sl.h_out.reserve(frames * O) != hipSuccess) leave_by_caller_copies(b);
   if (!b.raw) return hipSuccess;
-  const hipError_t e = sl.h_raw.reserve(size_t(b.raw_frames) * size_t(b.spec->raw_dim));
+  e = sl.h_raw.reserve(size_t(b.raw_frames) * size_t(b.spec->raw_dim));
   if (e == hipSuccess && fdnn::ctx_raw_reserve(sl.ctx, size_t(b.raw_frames), b.spec->raw_dim)) return hipErrorOutOfMemory;
   return e;
 }
@@ -442,15 +383,19 @@ void stage_batch(fdnn_server *s, Slot &sl) {
   s->staging = false;
 }
 
-// Copy in, compute, copy back -- all asynchronous, in launch order against device submissions (s->mu).  *rc: what
-// enqueue_batch said; the rows leave the slot later, piece by piece (copy_ready_pieces).
+// Copy in, compute, copy back -- all asynchronous, in launch order against device submissions (s->mu), and one sequence for
+// every form: frames up, the form's upload, `staged`, the form's pass and what it launches behind it, the streams joined,
+// the form's one transfer, `done`.  *rc: what enqueue_pass said; the results leave the slot later, piece by piece
+// (copy_ready_pieces).
 hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
+  using fdnn::pass::Pass;
   const fdnn::BlobHeader &h = s->m->hm.hdr;
   const BatchPlan &b = sl.batch;
-  const size_t D = size_t(h.in_dim), O = size_t(h.out_dim), wpr = (O + 63) / 64, rows = size_t(b.rows);
+  const Form &f = b.form;
+  const size_t D = size_t(h.in_dim), rows = size_t(b.rows);
+  const int n = b.rows, O = h.out_dim;
   std::lock_guard<std::mutex> order(s->mu);
   fdnn_ctx *c = sl.ctx;
-  const bool bits = b.kind == kBits;
   hipError_t e;
   if (b.raw) {  // only the raw frames cross PCIe; the rows are spliced on the device, each piece within its utterance
     const size_t raw_floats = size_t(b.raw_frames) * size_t(b.spec->raw_dim);
@@ -459,47 +404,63 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
   } else {
     e = hipMemcpyAsync(c->d_x, sl.h_x.p, sizeof(float) * rows * D, hipMemcpyHostToDevice, sl.stream);
   }
-  if (b.kind == kSet) {  // no masks and no output layer: the pieces' sets go up, probs and inactive values come back
-    if (e == hipSuccess && b.set_nodes > 0)
-      e = hipMemcpyAsync(sl.d_nodes.p, sl.h_nodes.p, sizeof(int32_t) * size_t(b.set_nodes), hipMemcpyHostToDevice, sl.stream);
-    if (e == hipSuccess) e = hipEventRecord(sl.staged, sl.stream);
-    if (e != hipSuccess) return e;
-    hipStream_t last = sl.stream;
-    *rc = enqueue_set_batch(s, sl, sl.staged, &last);
-    if (*rc) return hipSuccess;
-    if (last != sl.stream) {
-      e = hipEventRecord(sl.gemm_done, last);
-      if (e == hipSuccess) e = hipStreamWaitEvent(sl.stream, sl.gemm_done, 0);
-    }
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(sl.h_set.p, sl.d_out.p, sizeof(float) * (size_t(b.nnz) + rows), hipMemcpyDeviceToHost, sl.stream);
-    if (e == hipSuccess) e = hipEventRecord(sl.done, sl.stream);
-    return e;
+  const void *h_up = nullptr;  // what goes up beside the frames, and the mask it is to the pass (one or none)
+  void *d_up = nullptr;
+  const int8_t *d_masks = nullptr;
+  const uint64_t *d_bits = nullptr;
+  switch (f.upload) {
+    case Form::no_upload: break;
+    case Form::byte_masks: h_up = sl.h_mask.p, d_up = c->d_mask.p, d_masks = c->d_mask.p; break;
+    case Form::bit_words: h_up = sl.h_bits.p, d_up = c->d_mask_bits.p, d_bits = c->d_mask_bits.p; break;
+    case Form::node_sets: h_up = sl.h_nodes.p, d_up = sl.d_nodes.p; break;
   }
-  if (e == hipSuccess && bits)
-    e = hipMemcpyAsync(c->d_mask_bits, sl.h_bits.p, sizeof(uint64_t) * rows * wpr, hipMemcpyHostToDevice, sl.stream);
-  else if (e == hipSuccess && b.any_mask)
-    e = hipMemcpyAsync(c->d_mask, sl.h_mask.p, rows * O, hipMemcpyHostToDevice, sl.stream);
+  if (e == hipSuccess && f.upload_bytes > 0) e = hipMemcpyAsync(d_up, h_up, f.upload_bytes, hipMemcpyHostToDevice, sl.stream);
   if (e == hipSuccess) e = hipEventRecord(sl.staged, sl.stream);
   if (e != hipSuccess) return e;
+  // loop_sets: no output layer runs; the pieces are the segments of ONE sets call per chunk (fdnn::run_sets) over the batch's
+  // rows, probs go to d_out [nnz], the inactive values behind them [rows]
+  std::vector<int32_t> seg_rows, set_ptr;
+  if (f.pass == Form::loop_sets) {
+    for (const Piece &p : b.pieces) seg_rows.push_back(p.row0), set_ptr.push_back(p.set_off);
+    seg_rows.push_back(b.rows), set_ptr.push_back(b.set_nodes);
+  }
+  const fdnn::sets::Tables t{seg_rows.data(), set_ptr.data(), int(b.pieces.size())};
+  const Pass pass = f.pass == Form::loop_sets ? Pass::loop_sets(c->d_x, t, sl.d_nodes.p, sl.d_out.p, sl.d_out.p + size_t(b.nnz))
+                                              : Pass::loop_rows(c->d_x, d_masks, d_bits, sl.d_out.p);
   hipStream_t last = sl.stream;
-  *rc = enqueue_batch(s, sl, {.d_x = c->d_x, .n = b.rows, .d_masks = !bits && b.any_mask ? c->d_mask : nullptr,
-                              .d_bits = bits ? c->d_mask_bits : nullptr, .d_out = sl.d_out.p, .after = sl.staged,
-                              .d_comp = sl.d_comp.p, .stride = b.stride, .d_topk = b.kind == kTopk ? sl.d_topk.p : nullptr,
-                              .topk_k = b.topk_k, .pool = b.kind == kPool ? b.pool : nullptr, .d_pool = b.kind == kPool ? sl.d_pool.p : nullptr}, &last);
+  *rc = enqueue_pass(s, sl, n, sl.staged, pass, &last, [&](hipStream_t cs) {
+    switch (f.behind) {  // one launch over all the rows, which stay on the device
+      case Form::nothing: break;
+      case Form::compact:  // the rows compacted (active probabilities + one value per frame) for the trip over PCIe
+        fdnn::launch_lazy_compact(sl.d_out.p, d_bits, sl.d_comp.p, n, O, b.stride, cs);
+        break;
+      case Form::select_topk: {  // one selection with the batch's k: [n][k_b] nodes, then [n][k_b] values
+        int32_t *nodes = reinterpret_cast<int32_t *>(sl.d_res.p);
+        fdnn::launch_topk(sl.d_out.p, n, O, b.topk_k, nodes, reinterpret_cast<float *>(nodes + rows * size_t(b.topk_k)), cs);
+        break;
+      }
+      case Form::pool_sums:  // [n][C] class sums
+        fdnn::launch_pool(sl.d_out.p, n, O, b.pool->d_class_ptr(), b.pool->d_member(), b.pool->n_classes, reinterpret_cast<float *>(sl.d_res.p), cs);
+        break;
+    }
+  });
   if (*rc) return hipSuccess;
   if (last != sl.stream) {  // results leave on the slot's stream, behind the main stream's compute
     e = hipEventRecord(sl.gemm_done, last);
     if (e == hipSuccess) e = hipStreamWaitEvent(sl.stream, sl.gemm_done, 0);
   }
-  if (e == hipSuccess && bits && b.stride > 0)  // compacted rows: to the host with the batch
-    e = hipMemcpyAsync(sl.h_comp.p, sl.d_comp.p, sizeof(float) * rows * size_t(b.stride), hipMemcpyDeviceToHost, sl.stream);
-  else if (e == hipSuccess && b.kind == kTopk)  // the pairs: to the host with the batch, the rows never leave the device
-    e = hipMemcpyAsync(sl.h_topk.p, sl.d_topk.p, sizeof(int32_t) * 2 * rows * size_t(b.topk_k), hipMemcpyDeviceToHost, sl.stream);
-  else if (e == hipSuccess && b.kind == kPool)  // the class sums: to the host with the batch, the rows never leave the device
-    e = hipMemcpyAsync(sl.h_pool.p, sl.d_pool.p, sizeof(float) * rows * size_t(b.pool_classes), hipMemcpyDeviceToHost, sl.stream);
-  else if (e == hipSuccess && sl.rows_on_host)
-    e = hipMemcpyAsync(sl.h_out.p, sl.d_out.p, sizeof(float) * rows * O, hipMemcpyDeviceToHost, sl.stream);
+  const void *src = nullptr;  // the one transfer: f.words 32-bit words to the host with the batch
+  void *dst = nullptr;
+  switch (f.leave) {
+    case Form::by_caller_copies: break;
+    case Form::whole_rows: src = sl.d_out.p, dst = sl.h_out.p; break;
+    case Form::compacted_rows: src = sl.d_comp.p, dst = sl.h_comp.p; break;
+    case Form::set_blocks: src = sl.d_out.p, dst = sl.h_land.p; break;
+    case Form::topk_pairs:
+    case Form::class_sums: src = sl.d_res.p, dst = sl.h_land.p; break;
+  }
+  sl.landing = dst;
+  if (e == hipSuccess && dst) e = hipMemcpyAsync(dst, src, sizeof(uint32_t) * f.words, hipMemcpyDeviceToHost, sl.stream);
   if (e == hipSuccess) e = hipEventRecord(sl.done, sl.stream);
   return e;
 }
@@ -593,41 +554,77 @@ int submit_host(fdnn_server *s, Request r, uint64_t *ticket) {
   return FDNN_OK;
 }
 
-}  // namespace
-
-namespace fdnn {
-
-int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *raw, int n, int a, int b, const uint64_t *bits,
-                           float *out, uint64_t *ticket) {
-  int rc = splice_check(spec, -1);
-  if (rc) return rc;
+// The one path of every host submit entry point.  First where the frames come from: rows x [n][D] (spec null), or rows
+// [a, b) of an n-frame raw utterance spliced by *spec.  Then what the entry's form needs: want(&w) fills w or fails.  Then
+// submit_host.  Two bad arguments at once fail in this order.
+using WantOut = std::optional<Want>;
+template <class MakeWant>
+int submit_frames(fdnn_server *s, const fdnn::SpliceRef *spec, const float *frames, int n, int a, int b, uint64_t *ticket, MakeWant &&want) {
+  if (spec)
+    if (int rc = fdnn::splice_check(*spec, -1)) return rc;
   if (n <= 0 || a < 0 || b > n || b <= a) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
-  const int most = bits ? widest_row(bits, b - a, size_t(s->m->hm.hdr.out_dim)) : 0;
-  return submit_host(s, Request{.out = out, .n = b - a, .bits = bits, .most = most, .raw = raw, .spec = spec, .raw_n = n, .raw_a = a},
-                     ticket);
+  if (!frames) return fail(FDNN_E_ARG, "null buffer");
+  WantOut w;
+  if (int rc = want(&w)) return rc;
+  return submit_host(s, Request(spec ? Frames::raw_rows(frames, *spec, n, a) : Frames::rows(frames), *w, b - a), ticket);
 }
 
-}  // namespace fdnn
+// ... for the extern "C" entries: n rows x, or (kRaw) a whole n-frame utterance under the model's splice spec as it is now
+constexpr bool kRows = false, kRaw = true;
+template <class MakeWant>
+int submit_entry(fdnn_server *s, bool raw, const float *frames, int n, uint64_t *ticket, MakeWant &&want) {
+  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
+  if (!raw) return submit_frames(s, nullptr, frames, n, 0, n, ticket, want);
+  const fdnn::SpliceRef spec = s->m->splice;
+  return submit_frames(s, &spec, frames, n, 0, n, ticket, want);
+}
 
-namespace {
-
-// The common end of the set submit entry points: the set validated and copied (the caller may release it at once).
-int submit_set(fdnn_server *s, Request r, const int32_t *nodes, int len, float *probs, float *inactive, uint64_t *ticket) {
+// A set submission's Want: the set validated and copied (the caller may release it at once).
+int want_set(fdnn_server *s, int n, const int32_t *nodes, int len, float *probs, float *inactive, WantOut *w) {
   const int O = s->m->hm.hdr.out_dim;
   if (len < 0 || (len > 0 && !nodes)) return fail(FDNN_E_ARG, "bad node set");
   const int32_t row_ptr[2] = {0, len};
   if (fdnn::lists::check(row_ptr, nodes, 1, O))
     return fail(FDNN_E_ARG, "node set: the nodes must ascend strictly inside [0, " + std::to_string(O) + ")");
   if (!inactive || (len > 0 && !probs)) return fail(FDNN_E_ARG, "null buffer");
-  if (static_cast<long long>(r.n) * len > INT32_MAX) return fail(FDNN_E_ARG, "n x len must fit an int32");
-  r.set = std::make_shared<const std::vector<int32_t>>(nodes, nodes + len);
-  r.set_probs = probs;
-  r.set_inactive = inactive;
-  return submit_host(s, std::move(r), ticket);
+  if (static_cast<long long>(n) * len > INT32_MAX) return fail(FDNN_E_ARG, "n x len must fit an int32");
+  *w = Want::set_to(std::make_shared<const std::vector<int32_t>>(nodes, nodes + len), probs, inactive);
+  return FDNN_OK;
+}
+
+int want_topk(fdnn_server *s, int k, int32_t *nodes, float *probs, WantOut *w) {
+  if (!fdnn::topk::args_ok(s->m->hm.hdr.out_dim, k)) return fail(FDNN_E_ARG, "k is 1 .. min(output_dim, 256)");
+  if (!nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
+  *w = Want::topk_to(k, nodes, probs);
+  return FDNN_OK;
+}
+
+int want_pool(fdnn_server *s, const fdnn_pool *pool, float *out, WantOut *w) {
+  if (int rc = fdnn::check_pool(s->m, pool)) return rc;
+  if (!out) return fail(FDNN_E_ARG, "null buffer");
+  *w = Want::pool_to(pool, pool->n_classes, out);
+  return FDNN_OK;
+}
+
+// rows, behind byte masks or bit words where the caller gives some (the widest row is counted here, on the submitting thread)
+int want_rows(fdnn_server *s, int n, const int8_t *masks, const uint64_t *bits, float *out, WantOut *w) {
+  if (!out) return fail(FDNN_E_ARG, "null buffer");
+  *w = bits    ? Want::rows_behind_bits_to(bits, widest_row(bits, n, size_t(s->m->hm.hdr.out_dim)), out)
+       : masks ? Want::rows_behind_bytes_to(masks, out)
+               : Want::rows_to(out);
+  return FDNN_OK;
 }
 
 }  // namespace
+
+namespace fdnn {
+
+int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *raw, int n, int a, int b, const uint64_t *bits,
+                           float *out, uint64_t *ticket) {
+  return submit_frames(s, &spec, raw, n, a, b, ticket, [&](WantOut *w) { return want_rows(s, b - a, nullptr, bits, out, w); });
+}
+
+}  // namespace fdnn
 
 extern "C" {
 
@@ -738,7 +735,7 @@ int fdnn_server_submit_device(fdnn_server *s, const float *d_x, int n, const int
   Slot &sl = s->slots[size_t(si)];
   if (sl.used) HIP_TRY(hipEventSynchronize(sl.done));
   hipStream_t last = nullptr;
-  int rc = enqueue_batch(s, sl, {.d_x = d_x, .n = n, .d_masks = d_masks, .d_out = d_out}, &last);
+  int rc = enqueue_pass(s, sl, n, nullptr, fdnn::pass::Pass::loop_rows(d_x, d_masks, nullptr, d_out), &last, [](hipStream_t) {});
   if (rc) return rc;
   HIP_TRY(hipEventRecord(sl.done, last));
   sl.used = true;
@@ -752,77 +749,41 @@ int fdnn_server_submit_device(fdnn_server *s, const float *d_x, int n, const int
 }
 
 int fdnn_server_submit(fdnn_server *s, const float *x, int n, const int8_t *masks, float *out, uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
-  return submit_host(s, Request{.x = x, .masks = masks, .out = out, .n = n}, ticket);
+  return submit_entry(s, kRows, x, n, ticket, [&](WantOut *w) { return want_rows(s, n, masks, nullptr, out, w); });
 }
 
 int fdnn_server_submit_lazy_bits(fdnn_server *s, const float *x, int n, const uint64_t *bits, float *out, uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (!x || !out || !bits) return fail(FDNN_E_ARG, "null buffer");
-  const int most = widest_row(bits, n, size_t(s->m->hm.hdr.out_dim));
-  return submit_host(s, Request{.x = x, .out = out, .n = n, .bits = bits, .most = most}, ticket);
+  return submit_entry(s, kRows, x, n, ticket, [&](WantOut *w) { return bits ? want_rows(s, n, nullptr, bits, out, w) : fail(FDNN_E_ARG, "null buffer"); });
 }
 
 int fdnn_server_submit_raw(fdnn_server *s, const float *raw, int n, const uint64_t *bits, float *out, uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  return fdnn::server_submit_raw_rows(s, s->m->splice, raw, n, 0, n, bits, out, ticket);
+  return submit_entry(s, kRaw, raw, n, ticket, [&](WantOut *w) { return want_rows(s, n, nullptr, bits, out, w); });
 }
 
 int fdnn_server_submit_lazy_set(fdnn_server *s, const float *x, int n, const int32_t *nodes, int len, float *probs, float *inactive,
                                 uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (!x) return fail(FDNN_E_ARG, "null buffer");
-  return submit_set(s, Request{.x = x, .n = n}, nodes, len, probs, inactive, ticket);
+  return submit_entry(s, kRows, x, n, ticket, [&](WantOut *w) { return want_set(s, n, nodes, len, probs, inactive, w); });
 }
 
 int fdnn_server_submit_raw_set(fdnn_server *s, const float *raw, int n, const int32_t *nodes, int len, float *probs, float *inactive,
                                uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  const fdnn::SpliceRef spec = s->m->splice;
-  if (int rc = fdnn::splice_check(spec, -1)) return rc;
-  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (!raw) return fail(FDNN_E_ARG, "null buffer");
-  return submit_set(s, Request{.n = n, .raw = raw, .spec = spec, .raw_n = n, .raw_a = 0}, nodes, len, probs, inactive, ticket);
+  return submit_entry(s, kRaw, raw, n, ticket, [&](WantOut *w) { return want_set(s, n, nodes, len, probs, inactive, w); });
 }
 
 int fdnn_server_submit_topk(fdnn_server *s, const float *x, int n, int k, int32_t *nodes, float *probs, uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (!fdnn::topk::args_ok(s->m->hm.hdr.out_dim, k)) return fail(FDNN_E_ARG, "k is 1 .. min(output_dim, 256)");
-  if (!x || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
-  return submit_host(s, Request{.x = x, .n = n, .topk = k, .topk_nodes = nodes, .topk_probs = probs}, ticket);
+  return submit_entry(s, kRows, x, n, ticket, [&](WantOut *w) { return want_topk(s, k, nodes, probs, w); });
 }
 
 int fdnn_server_submit_raw_topk(fdnn_server *s, const float *raw, int n, int k, int32_t *nodes, float *probs, uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  const fdnn::SpliceRef spec = s->m->splice;
-  if (int rc = fdnn::splice_check(spec, -1)) return rc;
-  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (!fdnn::topk::args_ok(s->m->hm.hdr.out_dim, k)) return fail(FDNN_E_ARG, "k is 1 .. min(output_dim, 256)");
-  if (!raw || !nodes || !probs) return fail(FDNN_E_ARG, "null buffer");
-  return submit_host(s, Request{.n = n, .raw = raw, .spec = spec, .raw_n = n, .raw_a = 0, .topk = k, .topk_nodes = nodes, .topk_probs = probs}, ticket);
+  return submit_entry(s, kRaw, raw, n, ticket, [&](WantOut *w) { return want_topk(s, k, nodes, probs, w); });
 }
 
 int fdnn_server_submit_pool(fdnn_server *s, const float *x, int n, const fdnn_pool *pool, float *out, uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (int rc = fdnn::check_pool(s->m, pool)) return rc;
-  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
-  return submit_host(s, Request{.x = x, .n = n, .pool = pool, .pool_classes = pool->n_classes, .pooled = out}, ticket);
+  return submit_entry(s, kRows, x, n, ticket, [&](WantOut *w) { return want_pool(s, pool, out, w); });
 }
 
 int fdnn_server_submit_raw_pool(fdnn_server *s, const float *raw, int n, const fdnn_pool *pool, float *out, uint64_t *ticket) {
-  if (!s || !ticket) return fail(FDNN_E_ARG, "null argument");
-  const fdnn::SpliceRef spec = s->m->splice;
-  if (int rc = fdnn::splice_check(spec, -1)) return rc;
-  if (n <= 0) return fail(FDNN_E_ARG, "frame count must be positive");
-  if (int rc = fdnn::check_pool(s->m, pool)) return rc;
-  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
-  return submit_host(s, Request{.n = n, .raw = raw, .spec = spec, .raw_n = n, .raw_a = 0, .pool = pool, .pool_classes = pool->n_classes, .pooled = out}, ticket);
+  return submit_entry(s, kRaw, raw, n, ticket, [&](WantOut *w) { return want_pool(s, pool, out, w); });
 }
 
 int fdnn_server_wait(fdnn_server *s, uint64_t ticket) {

@@ -1,11 +1,15 @@
 // fdnn_server_plan.hpp -- what one batch of the scoring loop (fdnn_server.cpp) contains: which queued requests, or parts of
-// them, share it, each piece's rows and caller pointers, and for raw submissions where a piece's raw frames are staged and how
-// its rows index them.  Arithmetic on the queue, free of HIP: tests/host/server_plan_check.cpp runs it under the sanitizers.
+// them, share it, each piece's rows and caller pointers, for raw submissions where a piece's raw frames are staged and how
+// its rows index them, the batch's FORM -- what goes up beside the frames, which pass runs, what is launched behind it,
+// the one transfer that brings the results to the host -- and how a piece's part of that transfer reaches its caller.
+// Arithmetic on the queue and on host memory, free of HIP: tests/host/server_plan_check.cpp runs it under the sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <deque>
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "fdnn_splice_spec.hpp"
@@ -17,55 +21,93 @@ namespace fdnn::plan {
 // A set submission's node set, copied at submit and shared by the request, its parts and their pieces (as SpliceRef is)
 using SetRef = std::shared_ptr<const std::vector<int32_t>>;
 
-struct Piece {  // one caller's rows inside a coalesced batch
-  uint64_t ticket;
-  float *out;      // caller's destination of these rows
-  int row0, rows;  // rows [row0, row0 + rows) of the batch
-  bool last;       // the ticket's final piece
-  int state = 0;   // 0 batch in flight, 1 rows ready in the slot's pinned buffer, 2 being copied out, 3 done
-  const uint64_t *bits = nullptr;  // lazy submissions with bit masks: the caller's words of these rows (compacted return)
-  // set submissions (then out is null): the piece is one segment of the batch's sets call -- its set, where the set is
-  // staged among the batch's nodes, its block [rows][len] inside the batch's probs, and the caller's destinations of
-  // these rows (advanced by the frames earlier batches took)
-  SetRef set;
-  int set_off = 0, block_off = 0;
-  float *probs = nullptr, *inactive = nullptr;
-  // top-k submissions (then out is null): the piece's own k and the caller's [rows][k] destinations of these rows (advanced
-  // by the frames earlier batches took); the batch selects with its largest k and a piece keeps the first k columns
-  int topk = 0;
-  int32_t *topk_nodes = nullptr;
-  float *topk_probs = nullptr;
-  // pool submissions (then out is null): the caller's [rows][C] destination of these rows (advanced by the frames earlier
-  // batches took); C is the batch's
-  float *pooled = nullptr;
-};
+// ---------------------------------------------------------------- the two parts of a request
+// Where a request's frames come from.  Built by name only.
+class Frames {
+  Frames() = default;
 
-struct Request {
-  uint64_t ticket = 0;            // (given by the scoring loop's submit_host)
-  const float *x = nullptr;
-  const int8_t *masks = nullptr;  // may be null
-  float *out = nullptr;
-  int n = 0;
-  int taken = 0;  // frames already packed into earlier batches
-  const uint64_t *bits = nullptr;  // fdnn_server_submit_lazy_bits: [n][ceil(O / 64)] (then masks is null)
-  int most = 0;                    // ... and the largest number of active nodes in any of its rows (counted by the submitter)
-  // raw submissions (then x is null): rows [raw_a, raw_a + n) of the raw_n-frame utterance at `raw`, spliced on the device by
-  // the spec the request was submitted with
+ public:
+  enum Kind { host_rows, raw_frames } kind = host_rows;
+  const float *x = nullptr;  // host_rows: [n][D]
+  // raw: rows [raw_a, raw_a + n) of the raw_n-frame utterance at `raw`, spliced on the device by the spec the request was
+  // submitted with
   const float *raw = nullptr;
   SpliceRef spec;
   int raw_n = 0, raw_a = 0;
-  // set submissions (then out, masks and bits are null): ONE node set for all n rows; results probs [n][len], inactive [n]
-  SetRef set;
-  float *set_probs = nullptr, *set_inactive = nullptr;
-  // top-k submissions (then out, masks, bits and set are null): the k first-ranked nodes of every row; results [n][topk] each
-  int topk = 0;
+  static Frames rows(const float *x) { Frames f; f.x = x; return f; }
+  static Frames raw_rows(const float *raw, const SpliceRef &spec, int raw_n, int raw_a) { Frames f; f.kind = raw_frames, f.raw = raw, f.spec = spec, f.raw_n = raw_n, f.raw_a = raw_a; return f; }
+};
+
+// What the caller wants back, for n rows.  One named constructor per kind, as fdnn::pass::Pass has: nothing reads a kind
+// off a pointer that is set or null.  The same type describes a request's n rows and a piece's rows (want_at).
+class Want {
+  Want() = default;
+
+ public:
+  enum Kind { rows = 0, rows_behind_bytes = 1, rows_behind_bits = 2, set = 3, topk = 4, pool = 5 } kind = rows;
+  // rows, rows_behind_bytes, rows_behind_bits: soft-max rows out [n][O]; behind byte masks [n][O] (non-zero = active) or bit
+  // words [n][ceil(O / 64)], and for bits the largest number of active nodes in any row (widest_row, counted by the submitter)
+  float *out = nullptr;
+  const int8_t *masks = nullptr;
+  const uint64_t *bits = nullptr;
+  int most = 0;
+  // set: ONE node set for all n rows; probs [n][len] (null when the set is empty), inactive [n]
+  SetRef nodes;
+  float *probs = nullptr, *inactive = nullptr;
+  // topk: the k first-ranked nodes of every row and their values, [n][k] each
+  int k = 0;
   int32_t *topk_nodes = nullptr;
   float *topk_probs = nullptr;
-  // pool submissions (then out, masks, bits, set and topk are null): every row's class sums under the map behind `pool`, which
-  // has pool_classes classes; results pooled [n][pool_classes]
-  const fdnn_pool *pool = nullptr;
-  int pool_classes = 0;
+  // pool: every row's class sums under the map behind `map`, which has `classes` classes; pooled [n][classes]
+  const fdnn_pool *map = nullptr;
+  int classes = 0;
   float *pooled = nullptr;
+
+  static Want rows_to(float *out) { Want w; w.out = out; return w; }
+  static Want rows_behind_bytes_to(const int8_t *masks, float *out) { Want w; w.kind = rows_behind_bytes, w.masks = masks, w.out = out; return w; }
+  static Want rows_behind_bits_to(const uint64_t *bits, int most, float *out) { Want w; w.kind = rows_behind_bits, w.bits = bits, w.most = most, w.out = out; return w; }
+  static Want set_to(SetRef nodes, float *probs, float *inactive) { Want w; w.kind = set, w.nodes = std::move(nodes), w.probs = probs, w.inactive = inactive; return w; }
+  static Want topk_to(int k, int32_t *nodes, float *probs) { Want w; w.kind = topk, w.k = k, w.topk_nodes = nodes, w.topk_probs = probs; return w; }
+  static Want pool_to(const fdnn_pool *map, int classes, float *pooled) { Want w; w.kind = pool, w.map = map, w.classes = classes, w.pooled = pooled; return w; }
+};
+
+// The Want of the rows behind the first `taken` of a request: the ONLY place where a caller's destination (and the masks that
+// go with its rows) is advanced by the rows that earlier batches took -- the counterpart of fdnn::pass::chunk_view.
+inline Want want_at(const Want &w, int taken, size_t O, size_t wpr) {
+  Want p = w;
+  const size_t t = size_t(taken);
+  switch (w.kind) {
+    case Want::rows: p.out += t * O; break;
+    case Want::rows_behind_bytes: p.out += t * O, p.masks += t * O; break;
+    case Want::rows_behind_bits: p.out += t * O, p.bits += t * wpr; break;
+    case Want::set:
+      if (p.probs) p.probs += t * w.nodes->size();
+      p.inactive += t;
+      break;
+    case Want::topk: p.topk_nodes += t * size_t(w.k), p.topk_probs += t * size_t(w.k); break;
+    case Want::pool: p.pooled += t * size_t(w.classes); break;
+  }
+  return p;
+}
+
+struct Request {
+  uint64_t ticket = 0;  // (given by the scoring loop's submit_host)
+  Frames frames;
+  Want want;
+  int n = 0;
+  int taken = 0;  // frames already packed into earlier batches
+  Request(Frames f, Want w, int rows) : frames(std::move(f)), want(std::move(w)), n(rows) {}
+};
+
+struct Piece {  // one caller's rows inside a coalesced batch
+  uint64_t ticket;
+  int row0, rows;  // rows [row0, row0 + rows) of the batch
+  bool last;       // the ticket's final piece
+  Want want;       // of these rows (want_at)
+  // set batches: the piece is one segment of the batch's sets call -- where its set is staged among the batch's nodes, and
+  // where its block [rows][len] starts inside the batch's probs
+  int set_off = 0, block_off = 0;
+  int state = 0;  // 0 batch in flight, 1 rows ready in the slot's landing buffer, 2 being copied out, 3 done
 };
 
 // raw batches, per piece: the raw frames it references, [first, first + count) of its utterance, at frame `at` of the slot's buffer
@@ -86,13 +128,25 @@ inline int widest_row(const uint64_t *bits, int n, size_t O) {
   return most;
 }
 
-// what a host batch carries: kinds do not share a batch, except that dense callers may ride in a byte-mask batch (all active)
-// -- and set requests (kSet: no output layer runs, fdnn_sets.hip scores each piece's set) share batches only with set requests
-// -- and top-k requests (kTopk: a dense batch whose rows stay on the device, fdnn_topk.hip selects from them) only with top-k requests
-// -- and pool requests (kPool: a dense batch whose rows stay on the device, fdnn_pool.hip sums them by class) only with pool
-// requests of the SAME handle
-enum BatchKind { kDense = 0, kBytes = 1, kBits = 2, kSet = 3, kTopk = 4, kPool = 5 };
-inline int kind_of(const Request &r) { return r.pool ? kPool : r.topk ? kTopk : r.set ? kSet : r.bits ? kBits : r.masks ? kBytes : kDense; }
+// ---------------------------------------------------------------- a batch and its form
+// What every step behind the plan needs to know of a batch, fixed when the batch is planned: the steps follow it and do not
+// ask for the batch's kind again.  `leave` names the row of the table:
+//
+//   leave             | behind the pass | the one transfer: source        | words (32 bit)
+//   by_caller_copies  | nothing         | none (a single caller's whole rows: copied from d_out by whoever waits)
+//   whole_rows        | nothing         | d_out                           | rows * O
+//   compacted_rows    | compact         | d_comp                          | rows * stride
+//   set_blocks        | nothing         | d_out                           | nnz + rows
+//   topk_pairs        | select_topk     | the device result buffer        | 2 * rows * topk_k
+//   class_sums        | pool_sums       | the device result buffer        | rows * pool_classes
+struct Form {
+  enum Upload { no_upload, byte_masks, bit_words, node_sets } upload = no_upload;  // what goes up beside the frames ...
+  size_t upload_bytes = 0;                                                         // ... and how much of it
+  enum PassKind { loop_rows, loop_sets } pass = loop_rows;                         // fdnn::pass::Pass::loop_rows / loop_sets
+  enum Behind { nothing, compact, select_topk, pool_sums } behind = nothing;       // launched over all rows behind the chunks
+  enum Leave { by_caller_copies, whole_rows, compacted_rows, set_blocks, topk_pairs, class_sums } leave = by_caller_copies;
+  size_t words = 0;  // of the one result transfer
+};
 
 struct BatchPlan {
   std::vector<Request> taken;  // per piece: the request with .taken = first frame, .n = frames in THIS batch
@@ -100,76 +154,176 @@ struct BatchPlan {
   std::vector<RawSrc> raw_src;  // raw batches: per piece
   std::vector<SpliceSeg> segs;  // raw batches: per piece (its own utterance's edges)
   SpliceRef spec;               // raw batches: one spec per batch
-  int rows = 0, raw_frames = 0, most = 0, kind = kDense, stride = 0;  // stride: floats per compacted row (0: the rows leave whole)
+  Want::Kind kind = Want::rows;  // of all its requests, except that rows ride in a rows_behind_bytes batch (may_join)
+  int rows = 0, raw_frames = 0, most = 0, stride = 0;  // stride: floats per compacted row (0: the rows leave whole)
   bool any_mask = false, raw = false;
   int nnz = 0, set_nodes = 0;  // set batches: the floats of the batch's probs (sum of rows x len) and the nodes of its pieces' sets
   int topk_k = 0;              // top-k batches: the largest k among its pieces (a smaller k's result is a prefix of it)
   const fdnn_pool *pool = nullptr;  // pool batches: the one handle of all its pieces ...
   int pool_classes = 0;             // ... and its class count
+  Form form;
 };
 
+// May this request join this (non-empty) batch?  Kinds do not share a batch, except that dense callers ride in a byte-mask
+// batch (all active), which makes the batch a byte-mask batch
+// -- bit-mask requests share only with bit-mask requests (one masked pass, the rows compacted)
+// -- set requests (no output layer runs, fdnn_sets.hip scores each piece's set) only with set requests
+// -- top-k requests (a dense batch whose rows stay on the device, fdnn_topk.hip selects from them) only with top-k requests
+// -- pool requests (a dense batch whose rows stay on the device, fdnn_pool.hip sums them by class) only with pool requests
+//    of the SAME handle
+// and in every case raw-frame requests only with raw-frame requests, under one spec object.
+inline bool may_join(const BatchPlan &b, const Request &r) {
+  if ((r.frames.kind == Frames::raw_frames) != b.raw || r.frames.spec != b.spec) return false;
+  switch (r.want.kind) {
+    case Want::rows:
+    case Want::rows_behind_bytes: return b.kind == Want::rows || b.kind == Want::rows_behind_bytes;
+    case Want::rows_behind_bits:
+    case Want::set:
+    case Want::topk: return b.kind == r.want.kind;
+    case Want::pool: return b.kind == Want::pool && b.pool == r.want.map;
+  }
+  return false;
+}
+
+// One row of the form table: how the batch's results leave, and with that what runs behind the pass and the transfer's size.
+inline void set_leave(BatchPlan &b, Form::Leave leave, size_t O) {
+  Form &f = b.form;
+  const size_t rows = size_t(b.rows);
+  f.leave = leave;
+  switch (leave) {
+    case Form::by_caller_copies: f.behind = Form::nothing, f.words = 0; break;
+    case Form::whole_rows: f.behind = Form::nothing, f.words = rows * O; break;
+    case Form::compacted_rows: f.behind = Form::compact, f.words = rows * size_t(b.stride); break;
+    case Form::set_blocks: f.behind = Form::nothing, f.words = size_t(b.nnz) + rows; break;
+    case Form::topk_pairs: f.behind = Form::select_topk, f.words = 2 * rows * size_t(b.topk_k); break;
+    case Form::class_sums: f.behind = Form::pool_sums, f.words = rows * size_t(b.pool_classes); break;
+  }
+}
+
+// The loop found no room for what the form's transfer needs (the compacted pair, or the pinned landing buffer of whole
+// rows): the batch's rows go back whole, copied from the device caller by caller.  Rows batches only.
+inline void leave_by_caller_copies(BatchPlan &b) {
+  b.stride = 0;
+  set_leave(b, Form::by_caller_copies, 0);
+}
+
 // Takes requests off the front of the queue, whole or in part, until the batch is full (max_frames rows) or the next one may
-// not join it.  A batch carries bit-mask requests only, or none (dense rows in a byte-mask batch get all-active masks);
-// raw-frame requests only, or none; and one spec object.  Request::taken advances in the queue; a finished request leaves it.
+// not join it (may_join), and fixes the batch's form.  Request::taken advances in the queue; a finished request leaves it.
 inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O) {
   BatchPlan b;
   const size_t wpr = (O + 63) / 64;
   while (!queue.empty() && b.rows < max_frames) {
     Request &r = queue.front();
-    const int rk = kind_of(r);
     if (b.rows == 0) {
-      b.kind = rk;
-      b.raw = r.raw != nullptr;
-      b.spec = r.spec;
-      b.pool = r.pool, b.pool_classes = r.pool_classes;
-    } else if ((rk == kBits) != (b.kind == kBits) || (rk == kSet) != (b.kind == kSet) || (rk == kTopk) != (b.kind == kTopk) || (rk == kPool) != (b.kind == kPool) || r.pool != b.pool || (r.raw != nullptr) != b.raw || r.spec != b.spec)
+      b.kind = r.want.kind;
+      b.raw = r.frames.kind == Frames::raw_frames;
+      b.spec = r.frames.spec;
+      b.pool = r.want.map, b.pool_classes = r.want.classes;
+    } else if (!may_join(b, r)) {
       break;
-    else if (rk == kBytes)
-      b.kind = kBytes;
-    b.most = std::max(b.most, r.most);
+    }
     const int take = std::min(r.n - r.taken, max_frames - b.rows);
     Request part = r;
     part.n = take;  // rows of this request in THIS batch
     b.taken.push_back(part);
-    b.any_mask |= r.masks != nullptr;
     r.taken += take;
     const bool last = r.taken == r.n;
-    b.pieces.push_back(Piece{r.ticket, r.out ? r.out + size_t(part.taken) * O : nullptr, b.rows, take, last, 0,
-                             r.bits ? r.bits + size_t(part.taken) * wpr : nullptr});
-    if (rk == kSet) {  // a later part of a split request continues at taken * len of the caller's probs
-      Piece &pc = b.pieces.back();
-      const size_t len = r.set->size();
-      pc.set = r.set;
-      pc.set_off = b.set_nodes, pc.block_off = b.nnz;
-      pc.probs = r.set_probs ? r.set_probs + size_t(part.taken) * len : nullptr;
-      pc.inactive = r.set_inactive + part.taken;
-      b.set_nodes += int(len);
-      b.nnz += take * int(len);
+    Piece pc{r.ticket, b.rows, take, last, want_at(r.want, part.taken, O, wpr)};
+    switch (r.want.kind) {  // what the batch accumulates across its pieces
+      case Want::rows: break;
+      case Want::rows_behind_bytes: b.kind = Want::rows_behind_bytes, b.any_mask = true; break;
+      case Want::rows_behind_bits: b.most = std::max(b.most, r.want.most); break;
+      case Want::set: {
+        const int len = int(r.want.nodes->size());
+        pc.set_off = b.set_nodes, pc.block_off = b.nnz;
+        b.set_nodes += len;
+        b.nnz += take * len;
+        break;
+      }
+      case Want::topk: b.topk_k = std::max(b.topk_k, r.want.k); break;
+      case Want::pool: break;
     }
-    if (rk == kTopk) {  // a later part of a split request continues at taken * k of the caller's arrays
-      Piece &pc = b.pieces.back();
-      pc.topk = r.topk;
-      pc.topk_nodes = r.topk_nodes + size_t(part.taken) * size_t(r.topk);
-      pc.topk_probs = r.topk_probs + size_t(part.taken) * size_t(r.topk);
-      b.topk_k = std::max(b.topk_k, r.topk);
-    }
-    if (rk == kPool)  // a later part of a split request continues at taken * C of the caller's array
-      b.pieces.back().pooled = r.pooled + size_t(part.taken) * size_t(r.pool_classes);
+    b.pieces.push_back(std::move(pc));
     if (b.raw) {  // the raw frames this piece's rows reference, and where they are staged
-      const int u0 = r.raw_a + part.taken;  // the piece's first row as a frame of its utterance
+      const int u0 = r.frames.raw_a + part.taken;  // the piece's first row as a frame of its utterance
       int fa, fb;
-      splice_halo(*r.spec, r.raw_n, u0, u0 + take, &fa, &fb);
+      splice_halo(*r.frames.spec, r.frames.raw_n, u0, u0 + take, &fa, &fb);
       b.raw_src.push_back(RawSrc{fa, fb - fa, b.raw_frames});
-      b.segs.push_back(SpliceSeg{b.rows, b.raw_frames + u0 - fa, b.raw_frames - fa, b.raw_frames + r.raw_n - 1 - fa});
+      b.segs.push_back(SpliceSeg{b.rows, b.raw_frames + u0 - fa, b.raw_frames - fa, b.raw_frames + r.frames.raw_n - 1 - fa});
       b.raw_frames += fb - fa;
     }
     b.rows += take;
     if (last) queue.pop_front();
   }
-  // compacted return (bit-mask batches): worth it while a row is at most 3/4 active nodes
-  const size_t stride = size_t(b.most) + 1;
-  b.stride = b.kind == kBits && stride * 4 <= O * 3 ? int(stride) : 0;
+  // Whole rows of a batch that several callers share go to the host in one transfer (1 GB of pinned memory per slot at
+  // most); a single caller's batch leaves by per-caller copies from the device.
+  const Form::Leave whole = b.taken.size() > 1 && size_t(max_frames) * O * sizeof(float) <= (size_t(1) << 30) ? Form::whole_rows : Form::by_caller_copies;
+  const size_t rows = size_t(b.rows);
+  Form &f = b.form;
+  switch (b.kind) {
+    case Want::rows: set_leave(b, whole, O); break;
+    case Want::rows_behind_bytes:
+      f.upload = Form::byte_masks, f.upload_bytes = rows * O;
+      set_leave(b, whole, O);
+      break;
+    case Want::rows_behind_bits: {
+      f.upload = Form::bit_words, f.upload_bytes = rows * wpr * sizeof(uint64_t);
+      // compacted return: worth it while a row is at most 3/4 active nodes
+      const size_t stride = size_t(b.most) + 1;
+      b.stride = stride * 4 <= O * 3 ? int(stride) : 0;
+      set_leave(b, b.stride > 0 ? Form::compacted_rows : whole, O);
+      break;
+    }
+    case Want::set:
+      f.upload = Form::node_sets, f.upload_bytes = size_t(b.set_nodes) * sizeof(int32_t);
+      f.pass = Form::loop_sets;
+      set_leave(b, Form::set_blocks, O);
+      break;
+    case Want::topk: set_leave(b, Form::topk_pairs, O); break;
+    case Want::pool: set_leave(b, Form::class_sums, O); break;
+  }
   return b;
+}
+
+// A piece's part of the batch's one transfer, from the slot's landing buffer (form.words 32-bit words, as the device wrote
+// them) into the caller's memory.  Compacted rows are expanded by `expand` -- fdnn::lazy_expand_rows_from's signature -- which
+// is handed the piece's first compacted row and the batch's stride.  (by_caller_copies: nothing has landed; the loop copies
+// from the device.)
+template <class Expand>
+inline void scatter(const BatchPlan &b, const Piece &p, const void *landing, size_t O, Expand &&expand) {
+  const Want &w = p.want;
+  const size_t row0 = size_t(p.row0), rows = size_t(p.rows), word = sizeof(uint32_t);
+  const auto at = [&](size_t i) { return static_cast<const char *>(landing) + i * word; };
+  switch (b.form.leave) {
+    case Form::by_caller_copies: break;
+    case Form::whole_rows:  // [rows][O]: this thread moves its own
+      std::memcpy(w.out, at(row0 * O), word * rows * O);
+      break;
+    case Form::compacted_rows: {  // [rows][stride]; THIS thread -- the caller's own, normally -- expands its rows into the caller's block
+      const size_t stride = size_t(b.stride);
+      expand(w.out, static_cast<const float *>(landing) + row0 * stride, p.rows, O, stride, w.bits);
+      break;
+    }
+    case Form::set_blocks: {  // the pieces' blocks [rows][len] back to back, then one inactive value per row of the batch
+      const size_t len = w.nodes->size();
+      if (len) std::memcpy(w.probs, at(size_t(p.block_off)), word * rows * len);
+      std::memcpy(w.inactive, at(size_t(b.nnz) + row0), word * rows);
+      break;
+    }
+    case Form::topk_pairs: {  // nodes [rows][k_b], then values [rows][k_b]: the piece keeps the first k of its rows' k_b columns
+      const size_t kb = size_t(b.topk_k), k = size_t(w.k), all = size_t(b.rows) * kb;
+      for (size_t r = 0; r < rows; ++r) {
+        std::memcpy(w.topk_nodes + r * k, at((row0 + r) * kb), word * k);
+        std::memcpy(w.topk_probs + r * k, at(all + (row0 + r) * kb), word * k);
+      }
+      break;
+    }
+    case Form::class_sums: {  // [rows][C]
+      const size_t C = size_t(b.pool_classes);
+      std::memcpy(w.pooled, at(row0 * C), word * rows * C);
+      break;
+    }
+  }
 }
 
 }  // namespace fdnn::plan

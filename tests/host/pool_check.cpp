@@ -1,5 +1,5 @@
 // pool_check.cpp -- fdnn_pool.hpp (the map and its CSR, the order of the additions, the plan, the host restatement) and the
-// kPool arm of the scoring loop's batch plan (fdnn_server_plan.hpp), alone and under the sanitizers
+// pool arm of the scoring loop's batch plan (fdnn_server_plan.hpp), alone and under the sanitizers
 // (tests/test_pool_host.py builds and runs this).  Must NOT be built with a flush-to-zero or fast-math flag.
 #include <cmath>
 #include <cstdio>
@@ -177,7 +177,7 @@ void plan_forms_and_lds() {
   CHECK(pool::plan(0, 8000, 0).launches == 0);
 }
 
-// ---- the kPool arm of plan_batch
+// ---- the pool arm of plan_batch
 constexpr size_t O = 70;
 struct Caller {
   std::vector<float> out, pooled;
@@ -187,14 +187,14 @@ const fdnn_pool *handle(int i) { return reinterpret_cast<const fdnn_pool *>(stat
 
 plan::Request dense_req(Caller &c, uint64_t ticket, int n) {
   c.out.resize(size_t(n) * O);
-  plan::Request r;
-  r.ticket = ticket, r.x = &c.x, r.out = c.out.data(), r.n = n;
+  plan::Request r(plan::Frames::rows(&c.x), plan::Want::rows_to(c.out.data()), n);
+  r.ticket = ticket;
   return r;
 }
 plan::Request pool_req(Caller &c, uint64_t ticket, int n, int h, int classes) {
   c.pooled.resize(size_t(n) * size_t(classes));
-  plan::Request r;
-  r.ticket = ticket, r.x = &c.x, r.n = n, r.pool = handle(h), r.pool_classes = classes, r.pooled = c.pooled.data();
+  plan::Request r(plan::Frames::rows(&c.x), plan::Want::pool_to(handle(h), classes, c.pooled.data()), n);
+  r.ticket = ticket;
   return r;
 }
 
@@ -203,46 +203,46 @@ void plan_arithmetic() {
   {  // two requests of one handle behind a dense one, then another handle: dense, pool (2 pieces), pool
     Caller c[4];
     std::deque<Request> q{dense_req(c[0], 1, 10), pool_req(c[1], 2, 7, 0, 48), pool_req(c[2], 3, 20, 0, 48), pool_req(c[3], 4, 5, 1, 48)};
-    CHECK(kind_of(q[0]) == kDense && kind_of(q[1]) == kPool && kPool == 5 && kTopk == 4);
+    CHECK(q[0].want.kind == Want::rows && q[1].want.kind == Want::pool && Want::pool == 5 && Want::topk == 4);
     BatchPlan b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kDense && b.pieces.size() == 1 && b.rows == 10 && b.pool == nullptr && q.size() == 3);
+    CHECK(b.kind == Want::rows && b.pieces.size() == 1 && b.rows == 10 && b.pool == nullptr && q.size() == 3);
     b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kPool && b.pieces.size() == 2 && b.rows == 27 && b.pool == handle(0) && b.pool_classes == 48 && b.stride == 0 && !b.any_mask);
-    CHECK(b.pieces[0].pooled == c[1].pooled.data() && b.pieces[1].pooled == c[2].pooled.data() && b.pieces[1].row0 == 7);
-    CHECK(b.pieces[0].out == nullptr && b.pieces[0].topk == 0 && !b.pieces[0].set && b.pieces[0].last);
+    CHECK(b.kind == Want::pool && b.pieces.size() == 2 && b.rows == 27 && b.pool == handle(0) && b.pool_classes == 48 && b.stride == 0 && !b.any_mask);
+    CHECK(b.pieces[0].want.pooled == c[1].pooled.data() && b.pieces[1].want.pooled == c[2].pooled.data() && b.pieces[1].row0 == 7);
+    CHECK(b.pieces[0].want.out == nullptr && b.pieces[0].want.k == 0 && !b.pieces[0].want.nodes && b.pieces[0].last);
     b = plan_batch(q, 1000, O);  // different handles are never coalesced, whatever their class counts
-    CHECK(b.kind == kPool && b.pieces.size() == 1 && b.pool == handle(1) && b.rows == 5 && q.empty());
+    CHECK(b.kind == Want::pool && b.pieces.size() == 1 && b.pool == handle(1) && b.rows == 5 && q.empty());
   }
   {  // a dense or top-k request behind pool ones does not join them, nor the other way round
     Caller c[3];
     Request tk = dense_req(c[2], 3, 4);
     std::vector<int32_t> nodes(4 * 3);
     std::vector<float> probs(4 * 3);
-    tk.out = nullptr, tk.topk = 3, tk.topk_nodes = nodes.data(), tk.topk_probs = probs.data();
+    tk.want = Want::topk_to(3, nodes.data(), probs.data());
     std::deque<Request> q{pool_req(c[0], 1, 4, 0, 2), dense_req(c[1], 2, 4), tk, pool_req(c[0], 4, 4, 0, 2)};
     BatchPlan b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kPool && b.pieces.size() == 1 && q.size() == 3);
+    CHECK(b.kind == Want::pool && b.pieces.size() == 1 && q.size() == 3);
     b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kDense && b.pieces.size() == 1 && b.pool == nullptr && b.pieces[0].pooled == nullptr);
+    CHECK(b.kind == Want::rows && b.pieces.size() == 1 && b.pool == nullptr && b.pieces[0].want.pooled == nullptr);
     b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kTopk && b.pieces.size() == 1 && b.pool == nullptr);
+    CHECK(b.kind == Want::topk && b.pieces.size() == 1 && b.pool == nullptr);
     b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kPool && b.pieces.size() == 1 && q.empty());
+    CHECK(b.kind == Want::pool && b.pieces.size() == 1 && q.empty());
   }
   {  // a request cut by max_frames continues at taken * C of the caller's array
     Caller c[2];
     std::deque<Request> q{pool_req(c[0], 1, 25, 0, 9), pool_req(c[1], 2, 3, 0, 9)};
     BatchPlan b = plan_batch(q, 10, O);
-    CHECK(b.kind == kPool && b.rows == 10 && b.pieces.size() == 1 && !b.pieces[0].last && q.front().taken == 10);
-    CHECK(b.pieces[0].pooled == c[0].pooled.data());
+    CHECK(b.kind == Want::pool && b.rows == 10 && b.pieces.size() == 1 && !b.pieces[0].last && q.front().taken == 10);
+    CHECK(b.pieces[0].want.pooled == c[0].pooled.data());
     b = plan_batch(q, 10, O);
-    CHECK(b.rows == 10 && b.pieces.size() == 1 && b.pieces[0].pooled == c[0].pooled.data() + 10 * 9);
+    CHECK(b.rows == 10 && b.pieces.size() == 1 && b.pieces[0].want.pooled == c[0].pooled.data() + 10 * 9);
     b = plan_batch(q, 10, O);  // the last 5 rows, and the next request's 3
     CHECK(b.rows == 8 && b.pieces.size() == 2 && b.pieces[0].last && b.pieces[0].rows == 5 && b.pool_classes == 9);
-    CHECK(b.pieces[0].pooled == c[0].pooled.data() + 20 * 9 && b.pieces[1].pooled == c[1].pooled.data() && b.pieces[1].row0 == 5);
+    CHECK(b.pieces[0].want.pooled == c[0].pooled.data() + 20 * 9 && b.pieces[1].want.pooled == c[1].pooled.data() && b.pieces[1].row0 == 5);
     for (const Piece &p : b.pieces)  // every destination the scatter writes is inside the caller's block: touch it
       for (int r = 0; r < p.rows; ++r)
-        for (int j = 0; j < b.pool_classes; ++j) p.pooled[size_t(r) * size_t(b.pool_classes) + size_t(j)] = 1.0f;
+        for (int j = 0; j < b.pool_classes; ++j) p.want.pooled[size_t(r) * size_t(b.pool_classes) + size_t(j)] = 1.0f;
     CHECK(q.empty());
   }
   {  // raw and plain pool requests of one handle do not share a batch
@@ -250,12 +250,12 @@ void plan_arithmetic() {
     auto sp = std::make_shared<SpliceSpec>();
     sp->offsets = {-1, 0, 1}, sp->raw_dim = 39, sp->left = 1, sp->right = 1;
     Request raw = pool_req(c[0], 1, 6, 0, 4);
-    raw.x = nullptr, raw.raw = &c[0].x, raw.spec = sp, raw.raw_n = 6;
+    raw.frames = Frames::raw_rows(&c[0].x, sp, 6, 0);
     std::deque<Request> q{raw, pool_req(c[1], 2, 6, 0, 4)};
     BatchPlan b = plan_batch(q, 100, O);
-    CHECK(b.kind == kPool && b.raw && b.pieces.size() == 1 && b.raw_frames == 6 && q.size() == 1);
+    CHECK(b.kind == Want::pool && b.raw && b.pieces.size() == 1 && b.raw_frames == 6 && q.size() == 1);
     b = plan_batch(q, 100, O);
-    CHECK(b.kind == kPool && !b.raw && b.pieces.size() == 1);
+    CHECK(b.kind == Want::pool && !b.raw && b.pieces.size() == 1);
   }
 }
 

@@ -1,5 +1,5 @@
 // sets_check.cpp -- the host half of lazy output for per-segment node sets (fdnn_sets.hpp) and the scoring loop's plan for
-// set submissions (fdnn_server_plan.hpp: kSet), checked without a GPU: the validator on every class of malformed tables; the
+// set submissions (fdnn_server_plan.hpp: Want::set), checked without a GPU: the validator on every class of malformed tables; the
 // launches of a call -- every (row, entry) of every segment covered by exactly one workgroup's tiles, no tile across a
 // segment, at most 64 segments per launch; the slices of a call reassembling to the unsliced layout; the row pointer; and
 // that set requests share batches only with set requests, a split request continuing at taken * len.  Built with
@@ -197,45 +197,45 @@ void server_plan() {
   const SetRef a = std::make_shared<const std::vector<int32_t>>(std::vector<int32_t>{1, 5, 9});
   const SetRef b = std::make_shared<const std::vector<int32_t>>(std::vector<int32_t>{});
   auto set_req = [&](uint64_t ticket, int n, const SetRef &set) {
-    Request r;
-    r.ticket = ticket, r.x = x, r.n = n, r.set = set, r.set_probs = probs, r.set_inactive = inact;
+    Request r(Frames::rows(x), Want::set_to(set, probs, inact), n);
+    r.ticket = ticket;
     return r;
   };
-  Request dense;
-  dense.ticket = 9, dense.x = x, dense.out = out, dense.n = 10;
-  Request bit = dense;
-  bit.ticket = 10, bit.bits = bits;
-  CHECK(kind_of(set_req(1, 5, a)) == kSet && kind_of(set_req(1, 5, b)) == kSet && kind_of(dense) == kDense && kind_of(bit) == kBits);
+  Request dense(Frames::rows(x), Want::rows_to(out), 10);
+  dense.ticket = 9;
+  Request bit(Frames::rows(x), Want::rows_behind_bits_to(bits, 0, out), 10);
+  bit.ticket = 10;
+  CHECK(set_req(1, 5, a).want.kind == Want::set && set_req(1, 5, b).want.kind == Want::set && dense.want.kind == Want::rows && bit.want.kind == Want::rows_behind_bits);
   std::deque<Request> q{set_req(1, 40, a), set_req(2, 100, b), set_req(3, 100, a), dense, set_req(4, 7, a), bit, set_req(5, 3, a)};
   BatchPlan p = plan_batch(q, 96, O);  // 40 of a, 56 of b
-  CHECK(p.kind == kSet && p.rows == 96 && p.pieces.size() == 2 && p.nnz == 40 * 3 && p.set_nodes == 3 && p.stride == 0);
-  CHECK(p.pieces[0].set == a && p.pieces[0].probs == probs && p.pieces[0].inactive == inact && p.pieces[0].block_off == 0 && p.pieces[0].last);
-  CHECK(p.pieces[0].out == nullptr);
-  CHECK(p.pieces[1].set == b && p.pieces[1].row0 == 40 && p.pieces[1].rows == 56 && !p.pieces[1].last && p.pieces[1].block_off == 120);
+  CHECK(p.kind == Want::set && p.rows == 96 && p.pieces.size() == 2 && p.nnz == 40 * 3 && p.set_nodes == 3 && p.stride == 0);
+  CHECK(p.pieces[0].want.nodes == a && p.pieces[0].want.probs == probs && p.pieces[0].want.inactive == inact && p.pieces[0].block_off == 0 && p.pieces[0].last);
+  CHECK(p.pieces[0].want.out == nullptr);
+  CHECK(p.pieces[1].want.nodes == b && p.pieces[1].row0 == 40 && p.pieces[1].rows == 56 && !p.pieces[1].last && p.pieces[1].block_off == 120);
   p = plan_batch(q, 96, O);  // the rest of b (44), 52 of ticket 3
-  CHECK(p.kind == kSet && p.rows == 96 && p.pieces.size() == 2);
-  CHECK(p.pieces[0].ticket == 2 && p.pieces[0].inactive == inact + 56 && p.pieces[0].last && p.pieces[0].set_off == 0 && p.pieces[0].block_off == 0);
-  CHECK(p.pieces[1].ticket == 3 && p.pieces[1].rows == 52 && p.pieces[1].probs == probs && p.pieces[1].set_off == 0 && p.nnz == 52 * 3);
+  CHECK(p.kind == Want::set && p.rows == 96 && p.pieces.size() == 2);
+  CHECK(p.pieces[0].ticket == 2 && p.pieces[0].want.inactive == inact + 56 && p.pieces[0].last && p.pieces[0].set_off == 0 && p.pieces[0].block_off == 0);
+  CHECK(p.pieces[1].ticket == 3 && p.pieces[1].rows == 52 && p.pieces[1].want.probs == probs && p.pieces[1].set_off == 0 && p.nnz == 52 * 3);
   p = plan_batch(q, 96, O);  // the rest of 3 continues at taken * len; the dense request behind it does not join
-  CHECK(p.kind == kSet && p.pieces.size() == 1 && p.rows == 48 && p.pieces[0].probs == probs + 52 * 3 && p.pieces[0].inactive == inact + 52);
+  CHECK(p.kind == Want::set && p.pieces.size() == 1 && p.rows == 48 && p.pieces[0].want.probs == probs + 52 * 3 && p.pieces[0].want.inactive == inact + 52);
   CHECK(p.pieces[0].last && p.nnz == 48 * 3 && p.set_nodes == 3);
   p = plan_batch(q, 96, O);
-  CHECK(p.kind == kDense && p.pieces.size() == 1 && p.nnz == 0 && !p.pieces[0].set);  // no set request rides in a dense batch
+  CHECK(p.kind == Want::rows && p.pieces.size() == 1 && p.nnz == 0 && !p.pieces[0].want.nodes);  // no set request rides in a dense batch
   p = plan_batch(q, 96, O);
-  CHECK(p.kind == kSet && p.pieces.size() == 1 && p.rows == 7);  // ... and no bit-mask request in a set batch
+  CHECK(p.kind == Want::set && p.pieces.size() == 1 && p.rows == 7);  // ... and no bit-mask request in a set batch
   p = plan_batch(q, 96, O);
-  CHECK(p.kind == kBits && p.pieces.size() == 1 && !p.pieces[0].set);
+  CHECK(p.kind == Want::rows_behind_bits && p.pieces.size() == 1 && !p.pieces[0].want.nodes);
   p = plan_batch(q, 96, O);
-  CHECK(p.kind == kSet && p.rows == 3 && q.empty());
+  CHECK(p.kind == Want::set && p.rows == 3 && q.empty());
   // raw set requests: the raw / spec rule on top, unchanged
   const SpliceRef spec = std::make_shared<const SpliceSpec>(SpliceSpec{{-1, 0, 1}, 13, 1, 1});
   Request raw = set_req(6, 20, a);
-  raw.x = nullptr, raw.raw = x, raw.spec = spec, raw.raw_n = 20;
+  raw.frames = Frames::raw_rows(x, spec, 20, 0);
   std::deque<Request> q2{raw, set_req(7, 5, a), raw};
   p = plan_batch(q2, 96, O);
-  CHECK(p.kind == kSet && p.raw && p.pieces.size() == 1 && p.raw_src.size() == 1 && p.segs.size() == 1 && p.nnz == 60);
+  CHECK(p.kind == Want::set && p.raw && p.pieces.size() == 1 && p.raw_src.size() == 1 && p.segs.size() == 1 && p.nnz == 60);
   p = plan_batch(q2, 96, O);
-  CHECK(p.kind == kSet && !p.raw && p.pieces.size() == 1);
+  CHECK(p.kind == Want::set && !p.raw && p.pieces.size() == 1);
 }
 
 }  // namespace

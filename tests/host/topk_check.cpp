@@ -1,4 +1,4 @@
-// topk_check.cpp -- the HIP-free half of the top-k return (fdnn_topk.hpp) and the kTopk arm of the scoring loop's batch plan
+// topk_check.cpp -- the HIP-free half of the top-k return (fdnn_topk.hpp) and the top-k arm of the scoring loop's batch plan
 // (fdnn_server_plan.hpp), checked without a GPU.  Built with -fsanitize=address,undefined and run as a child process by
 // tests/test_topk_host.py; exit status 0 = all cases hold.
 #include <algorithm>
@@ -130,7 +130,7 @@ void plan_forms_and_lds() {
   CHECK(topk::plan(0, 8000, 0).launches == 0);
 }
 
-// ---- the kTopk arm of plan_batch
+// ---- the top-k arm of plan_batch
 constexpr size_t O = 70;
 struct Caller {
   std::vector<float> out, probs;
@@ -140,14 +140,14 @@ struct Caller {
 
 plan::Request dense_req(Caller &c, uint64_t ticket, int n) {
   c.out.resize(size_t(n) * O);
-  plan::Request r;
-  r.ticket = ticket, r.x = &c.x, r.out = c.out.data(), r.n = n;
+  plan::Request r(plan::Frames::rows(&c.x), plan::Want::rows_to(c.out.data()), n);
+  r.ticket = ticket;
   return r;
 }
 plan::Request topk_req(Caller &c, uint64_t ticket, int n, int k) {
   c.nodes.resize(size_t(n) * k), c.probs.resize(size_t(n) * k);
-  plan::Request r;
-  r.ticket = ticket, r.x = &c.x, r.n = n, r.topk = k, r.topk_nodes = c.nodes.data(), r.topk_probs = c.probs.data();
+  plan::Request r(plan::Frames::rows(&c.x), plan::Want::topk_to(k, c.nodes.data(), c.probs.data()), n);
+  r.ticket = ticket;
   return r;
 }
 
@@ -156,42 +156,42 @@ void plan_arithmetic() {
   {  // k = 3, 32 and 7 behind a dense request: one dense batch, then one top-k batch with k_b = 32
     Caller c[4];
     std::deque<Request> q{dense_req(c[0], 1, 10), topk_req(c[1], 2, 7, 3), topk_req(c[2], 3, 20, 32), topk_req(c[3], 4, 5, 7)};
-    CHECK(kind_of(q[0]) == kDense && kind_of(q[1]) == kTopk);
+    CHECK(q[0].want.kind == Want::rows && q[1].want.kind == Want::topk);
     BatchPlan b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kDense && b.pieces.size() == 1 && b.rows == 10 && b.topk_k == 0 && q.size() == 3);
+    CHECK(b.kind == Want::rows && b.pieces.size() == 1 && b.rows == 10 && b.topk_k == 0 && q.size() == 3);
     b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kTopk && b.pieces.size() == 3 && b.rows == 32 && b.topk_k == 32 && b.stride == 0 && !b.any_mask && q.empty());
+    CHECK(b.kind == Want::topk && b.pieces.size() == 3 && b.rows == 32 && b.topk_k == 32 && b.stride == 0 && !b.any_mask && q.empty());
     const int ks[3] = {3, 32, 7}, row0[3] = {0, 7, 27};
     for (int i = 0; i < 3; ++i) {
       const Piece &p = b.pieces[size_t(i)];
-      CHECK(p.topk == ks[i] && p.row0 == row0[i] && p.out == nullptr && p.last && !p.set && p.bits == nullptr);
-      CHECK(p.topk_nodes == c[i + 1].nodes.data() && p.topk_probs == c[i + 1].probs.data());
+      CHECK(p.want.k == ks[i] && p.row0 == row0[i] && p.want.out == nullptr && p.last && !p.want.nodes && p.want.bits == nullptr);
+      CHECK(p.want.topk_nodes == c[i + 1].nodes.data() && p.want.topk_probs == c[i + 1].probs.data());
     }
   }
   {  // a dense request behind top-k ones does not join them either
     Caller c[2];
     std::deque<Request> q{topk_req(c[0], 1, 4, 5), dense_req(c[1], 2, 4)};
     BatchPlan b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kTopk && b.pieces.size() == 1 && b.topk_k == 5 && q.size() == 1);
+    CHECK(b.kind == Want::topk && b.pieces.size() == 1 && b.topk_k == 5 && q.size() == 1);
     b = plan_batch(q, 1000, O);
-    CHECK(b.kind == kDense && b.topk_k == 0 && b.pieces[0].topk == 0);
+    CHECK(b.kind == Want::rows && b.topk_k == 0 && b.pieces[0].want.k == 0);
   }
   {  // a request cut by max_frames continues at taken * k of the caller's arrays
     Caller c[2];
     std::deque<Request> q{topk_req(c[0], 1, 25, 9), topk_req(c[1], 2, 3, 200)};
     BatchPlan b = plan_batch(q, 10, O);
-    CHECK(b.kind == kTopk && b.rows == 10 && b.topk_k == 9 && b.pieces.size() == 1 && !b.pieces[0].last && q.front().taken == 10);
-    CHECK(b.pieces[0].topk_nodes == c[0].nodes.data() && b.pieces[0].topk_probs == c[0].probs.data());
+    CHECK(b.kind == Want::topk && b.rows == 10 && b.topk_k == 9 && b.pieces.size() == 1 && !b.pieces[0].last && q.front().taken == 10);
+    CHECK(b.pieces[0].want.topk_nodes == c[0].nodes.data() && b.pieces[0].want.topk_probs == c[0].probs.data());
     b = plan_batch(q, 10, O);
-    CHECK(b.rows == 10 && b.pieces.size() == 1 && b.pieces[0].topk_nodes == c[0].nodes.data() + 10 * 9 && b.pieces[0].topk_probs == c[0].probs.data() + 10 * 9);
+    CHECK(b.rows == 10 && b.pieces.size() == 1 && b.pieces[0].want.topk_nodes == c[0].nodes.data() + 10 * 9 && b.pieces[0].want.topk_probs == c[0].probs.data() + 10 * 9);
     b = plan_batch(q, 10, O);  // the last 5 rows, and the next request's 3 with the larger k
     CHECK(b.rows == 8 && b.pieces.size() == 2 && b.topk_k == 200 && b.pieces[0].last && b.pieces[0].rows == 5);
-    CHECK(b.pieces[0].topk_nodes == c[0].nodes.data() + 20 * 9 && b.pieces[0].topk == 9);
-    CHECK(b.pieces[1].topk_nodes == c[1].nodes.data() && b.pieces[1].row0 == 5 && b.pieces[1].topk == 200);
+    CHECK(b.pieces[0].want.topk_nodes == c[0].nodes.data() + 20 * 9 && b.pieces[0].want.k == 9);
+    CHECK(b.pieces[1].want.topk_nodes == c[1].nodes.data() && b.pieces[1].row0 == 5 && b.pieces[1].want.k == 200);
     // every destination the scatter writes is inside the caller's block: touch it
     for (const Piece &p : b.pieces)
       for (int r = 0; r < p.rows; ++r)
-        for (int j = 0; j < p.topk; ++j) p.topk_nodes[size_t(r) * p.topk + j] = 1, p.topk_probs[size_t(r) * p.topk + j] = 1.0f;
+        for (int j = 0; j < p.want.k; ++j) p.want.topk_nodes[size_t(r) * p.want.k + j] = 1, p.want.topk_probs[size_t(r) * p.want.k + j] = 1.0f;
     CHECK(q.empty());
   }
   {  // raw and plain top-k requests do not share a batch
@@ -199,12 +199,12 @@ void plan_arithmetic() {
     auto sp = std::make_shared<SpliceSpec>();
     sp->offsets = {-1, 0, 1}, sp->raw_dim = 39, sp->left = 1, sp->right = 1;
     Request raw = topk_req(c[0], 1, 6, 4);
-    raw.x = nullptr, raw.raw = &c[0].x, raw.spec = sp, raw.raw_n = 6;
+    raw.frames = Frames::raw_rows(&c[0].x, sp, 6, 0);
     std::deque<Request> q{raw, topk_req(c[1], 2, 6, 4)};
     BatchPlan b = plan_batch(q, 100, O);
-    CHECK(b.kind == kTopk && b.raw && b.pieces.size() == 1 && b.raw_frames == 6 && q.size() == 1);
+    CHECK(b.kind == Want::topk && b.raw && b.pieces.size() == 1 && b.raw_frames == 6 && q.size() == 1);
     b = plan_batch(q, 100, O);
-    CHECK(b.kind == kTopk && !b.raw && b.pieces.size() == 1);
+    CHECK(b.kind == Want::topk && !b.raw && b.pieces.size() == 1);
   }
 }
 

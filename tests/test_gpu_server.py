@@ -468,3 +468,63 @@ def test_four_kinds_of_submission_share_one_loop(mid_model_path):
     free1 = device_memory_free()
     assert free0 - free1 < LEAK_BOUND, f"{(free0 - free1) >> 20} MiB of device memory did not come back when the loop closed"
     dnn.delete()
+
+
+@pytest.mark.parametrize("depth", (1, 2))
+def test_every_form_of_submission_goes_through_one_slot(mid_model_path, depth):
+    """One caller thread per form of host submission -- dense, byte-masked, bit-masked, one node set, top-k (k = 5), pool
+    (C = 7), raw frames with bits, raw top-k and raw pool -- behind a barrier, three rounds each, 100 to 130 frames on a
+    96-frame loop: every request is split over two batches, and at depth 1 successive batches of different forms reuse ONE
+    slot's upload, result and landing buffers.  Whatever the packer puts together, every result has the bytes of the same
+    input through the per-call entry, and closing the loop gives its device memory back."""
+    dnn = api.QuantizedDnn.loadFromFile(mid_model_path)
+    dnn.setSplice(list(range(-5, 6)), 39)
+    O = dnn.outputDimension()
+    lens = (100, 104, 130, 108, 112, 116, 120, 124, 128)
+    xs = [F.synth_features(n, 432, seed=640 + i) for i, n in enumerate(lens[:6])]
+    raws = [np.random.default_rng(650 + i).standard_normal((n, 39)).astype(np.float32) * 3 for i, n in enumerate(lens[6:])]
+    masks = F.generate_masks(lens[1], O, 0.4, 0.03, seed=41)
+    bits = F.pack_mask_bits(F.generate_masks(lens[2], O, 0.4, 0.03, seed=42))
+    raw_bits = F.pack_mask_bits(F.generate_masks(lens[6], O, 0.4, 0.03, seed=43))
+    nodes = np.arange(3, O, 7, dtype=np.int32)
+    class_of = (np.arange(O) % 8 - 1).astype(np.int32)  # every eighth node in no class
+    pool = api.ClassPool(class_of, 7)
+    want = [(dnn.calculate(xs[0]),), (dnn.calculateLazy(xs[1], masks=masks),), (dnn.calculateLazy(xs[2], bits=bits),),
+            tuple(dnn.calculateLazySet(xs[3], nodes)), tuple(dnn.calculateTopK(xs[4], 5)), (dnn.calculatePool(xs[5], pool),),
+            (dnn.calculateLazyRaw(raws[0], raw_bits),), tuple(dnn.calculateTopKRaw(raws[1], 5)), (dnn.calculatePoolRaw(raws[2], pool),)]
+    free0 = device_memory_free()
+    srv = api.ScoringServer(dnn, max_frames=96, depth=depth, linger_us=2000)
+    submit = [lambda: srv.submit(xs[0]), lambda: srv.submit(xs[1], masks), lambda: srv.submitLazy(xs[2], bits),
+              lambda: srv.submitLazySet(xs[3], nodes), lambda: srv.submitTopK(xs[4], 5), lambda: srv.submitPool(xs[5], pool),
+              lambda: srv.submitRaw(raws[0], bits=raw_bits), lambda: srv.submitRawTopK(raws[1], 5), lambda: srv.submitRawPool(raws[2], pool)]
+    barrier = threading.Barrier(len(submit))
+    got, errors = [[] for _ in submit], []
+
+    def caller(k):
+        try:
+            barrier.wait()
+            for _ in range(3):
+                t, *outs = submit[k]()
+                srv.wait(t)
+                got[k].append(outs)
+        except Exception as e:  # noqa: BLE001
+            errors.append(e)
+
+    th = [threading.Thread(target=caller, args=(k,)) for k in range(len(submit))]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert not errors, errors
+    for k, rounds in enumerate(got):
+        assert len(rounds) == 3
+        for outs in rounds:
+            assert len(outs) == len(want[k])
+            for o, w in zip(outs, want[k]):
+                assert o.dtype == w.dtype and o.shape == w.shape and o.tobytes() == w.tobytes(), k
+    assert srv.stats()["requests"] == 27
+    srv.close()
+    free1 = device_memory_free()
+    assert free0 - free1 < LEAK_BOUND, f"{(free0 - free1) >> 20} MiB of device memory did not come back when the loop closed"
+    pool.delete()
+    dnn.delete()
