@@ -198,6 +198,21 @@ SIGNATURES = {
     "fdnn_stream_push": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_f32p, _c_i32p]),
     "fdnn_stream_ctx": (C.c_void_p, [C.c_void_p]),
     "fdnn_server_submit_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_void_p, _c_f32p, C.POINTER(C.c_uint64)]),
+    "fdnn_server_live_open": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "fdnn_server_live_close": (None, [C.c_void_p]),
+    "fdnn_server_live_reset": (C.c_int, [C.c_void_p]),
+    "fdnn_server_live_position": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "fdnn_server_live_push": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_f32p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "fdnn_server_live_push_topk": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_int, _c_i32p, _c_f32p, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_uint64)]),
+    "fdnn_server_live_push_pool": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_f32p, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_uint64)]),
+    "fdnn_server_live_push_set": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, C.POINTER(C.c_int),
+                                            C.POINTER(C.c_uint64)]),
+    "fdnn_debug_splice_table": (C.c_int, [_c_i32p, C.c_int, C.c_int, C.c_int, _c_f32p, C.c_int, _c_i32p, C.c_int, C.c_int, C.c_int, _c_f32p,
+                                          C.c_int]),
+    "fdnn_debug_live_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "fdnn_debug_server_hold": (C.c_int, [C.c_void_p, C.c_int]),
     "fdnn_host_model_load": (C.c_int, [C.c_char_p, C.c_float, C.POINTER(C.c_void_p)]),
     "fdnn_host_model_free": (None, [C.c_void_p]),
     "fdnn_host_model_layers": (C.c_int, [C.c_void_p]),
@@ -1188,10 +1203,123 @@ class ScoringServer:
         _check(lib().fdnn_server_stats(self.handle, *[C.byref(a) for a in v]))
         return dict(zip(("batches", "frames", "requests", "coalesced_requests"), (int(a.value) for a in v)))
 
+    def openLive(self, maxChunk: int) -> "LiveStream":
+        """A live utterance of this loop (``fdnn_server_live_open``): its pushes share batches with the other handles'."""
+        return LiveStream(self, maxChunk)
+
+    def hold(self, on: bool = True) -> None:
+        """Tests (``fdnn_debug_server_hold``): while on, the packer plans no batch and submissions queue up; switching it off
+        wakes the packer -- what was queued goes out together."""
+        _check(lib().fdnn_debug_server_hold(self.handle, 1 if on else 0))
+
     def close(self) -> None:
         if self.handle:
             lib().fdnn_server_free(self.handle)
             self.handle = None
+
+
+class LiveStream:
+    """One utterance at a time, pushed chunk by chunk through a scoring loop (``fdnn_server_live_*``).  A push returns at once
+    with ``(ticket, arrays)``: the arrays hold the rows the push completes and are valid after ``server.wait(ticket)``; a
+    push that completes no rows returns ``(None, empty arrays)`` and there is nothing to wait for.  The raw frames are copied
+    by the push.  ``end=True`` flushes the rest, right-clamped to the last frame.  Made by ``ScoringServer.openLive``; it
+    keeps the model's splice spec of that moment.  One thread at a time per handle."""
+
+    def __init__(self, server: ScoringServer, maxChunk: int):
+        h = C.c_void_p()
+        spec = server.dnn.spliceSpec()
+        _check(lib().fdnn_server_live_open(server.handle, int(maxChunk), C.byref(h)))
+        self.handle = h.value
+        self.server = server
+        self.maxChunk = int(maxChunk)
+        self.offsets, self.rawDim = spec
+        self.right = max(0, max(self.offsets))
+
+    def _raw(self, raw):
+        r = np.ascontiguousarray(raw, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != self.rawDim:
+            raise ValueError(f"raw frames must be [n][{self.rawDim}], got {r.shape}")
+        return r
+
+    def _done(self, n, t, bufs):
+        k, ticket = int(n.value), int(t.value) or None
+        if ticket is not None:
+            self.server._keep[ticket] = bufs
+        return (ticket,) + tuple(b[:k] for b in bufs)
+
+    def push(self, raw, end: bool = False):
+        """raw [n][rawDim] -> (ticket or None, the soft-max rows of the frames this push completes [k][outputDimension])."""
+        r = self._raw(raw)
+        out = np.empty((r.shape[0] + self.right, self.server.dnn.outputDimension()), dtype=np.float32)
+        n, t = C.c_int(0), C.c_uint64(0)
+        _check(lib().fdnn_server_live_push(self.handle, r.ctypes.data_as(_c_f32p), r.shape[0], int(bool(end)), out.ctypes.data_as(_c_f32p),
+                                           C.byref(n), C.byref(t)))
+        return self._done(n, t, (out,))
+
+    def pushTopK(self, raw, k: int, end: bool = False):
+        """-> (ticket or None, nodes int32 [rows][k], probs float32 [rows][k]): the bytes of ``calculateTopKRaw``."""
+        r = self._raw(raw)
+        nodes, probs = _topk_out(r.shape[0] + self.right, max(int(k), 0), None, None)
+        n, t = C.c_int(0), C.c_uint64(0)
+        _check(lib().fdnn_server_live_push_topk(self.handle, r.ctypes.data_as(_c_f32p), r.shape[0], int(bool(end)), int(k),
+                                                nodes.ctypes.data_as(_c_i32p), probs.ctypes.data_as(_c_f32p), C.byref(n), C.byref(t)))
+        return self._done(n, t, (nodes, probs))
+
+    def pushPool(self, raw, pool: "ClassPool", end: bool = False):
+        """-> (ticket or None, class sums float32 [rows][classes]): the bytes of ``calculatePoolRaw``."""
+        r = self._raw(raw)
+        out = np.empty((r.shape[0] + self.right, pool.classes()), dtype=np.float32)
+        n, t = C.c_int(0), C.c_uint64(0)
+        _check(lib().fdnn_server_live_push_pool(self.handle, r.ctypes.data_as(_c_f32p), r.shape[0], int(bool(end)), pool.handle,
+                                                out.ctypes.data_as(_c_f32p), C.byref(n), C.byref(t)))
+        return self._done(n, t, (out,))
+
+    def pushSet(self, raw, nodes, end: bool = False):
+        """-> (ticket or None, probs [rows][len], inactive [rows]): the bytes of ``calculateLazySet`` on the host-spliced rows."""
+        r = self._raw(raw)
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+        probs = np.empty((r.shape[0] + self.right, nd.size), dtype=np.float32)
+        inactive = np.empty(r.shape[0] + self.right, dtype=np.float32)
+        n, t = C.c_int(0), C.c_uint64(0)
+        _check(lib().fdnn_server_live_push_set(self.handle, r.ctypes.data_as(_c_f32p), r.shape[0], int(bool(end)), nd.ctypes.data_as(_c_i32p),
+                                               nd.size, probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p), C.byref(n), C.byref(t)))
+        return self._done(n, t, (probs, inactive))
+
+    def reset(self) -> None:
+        _check(lib().fdnn_server_live_reset(self.handle))
+
+    def position(self):
+        """(raw frames pushed, rows emitted) since the utterance started."""
+        p, e = C.c_int64(), C.c_int64()
+        _check(lib().fdnn_server_live_position(self.handle, C.byref(p), C.byref(e)))
+        return int(p.value), int(e.value)
+
+    def close(self) -> None:
+        if self.handle:
+            lib().fdnn_server_live_close(self.handle)
+            self.handle = None
+
+
+def splice_table(offsets, rawDim: int, inputDim: int, raw, segs, rows: int, use_table: bool, device: int = 0) -> np.ndarray:
+    """The splice alone (``fdnn_debug_splice_table``): raw [frames][rawDim], segs [n][4] = (row, center, lo, hi) -> rows
+    [rows][inputDim]; ``use_table`` picks the kernel that reads the segment table from device memory."""
+    off = np.ascontiguousarray(offsets, dtype=np.int32).ravel()
+    r = np.ascontiguousarray(raw, dtype=np.float32)
+    sg = np.ascontiguousarray(segs, dtype=np.int32)
+    if r.ndim != 2 or r.shape[1] != rawDim or sg.ndim != 2 or sg.shape[1] != 4:
+        raise ValueError("raw must be [frames][rawDim] and segs [n][4]")
+    x = np.empty((int(rows), int(inputDim)), dtype=np.float32)
+    _check(lib().fdnn_debug_splice_table(off.ctypes.data_as(_c_i32p), off.size, int(rawDim), int(inputDim), r.ctypes.data_as(_c_f32p), r.shape[0],
+                                         sg.ctypes.data_as(_c_i32p), sg.shape[0], int(rows), 1 if use_table else 0, x.ctypes.data_as(_c_f32p),
+                                         int(device)))
+    return x
+
+
+def live_launches() -> dict:
+    """Process-wide since load (``fdnn_debug_live_launches``): launches of the table splice kernel, the longest table given."""
+    a, b = C.c_ulonglong(0), C.c_ulonglong(0)
+    _check(lib().fdnn_debug_live_launches(C.byref(a), C.byref(b)))
+    return {"launches": int(a.value), "max_segs": int(b.value)}
 
 
 class QuantizedDnn:

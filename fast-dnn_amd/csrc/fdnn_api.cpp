@@ -15,6 +15,7 @@
 
 #include "fdnn_internal.hpp"
 #include "fdnn_lists.hpp"
+#include "fdnn_stream_plan.hpp"
 
 using namespace fdnn;
 using fdnn::pass::Pass;
@@ -1051,8 +1052,7 @@ struct fdnn_stream {
   int raw_dim = 0, max_chunk = 0, left = 0, right = 0;
   fdnn::DevBuf<float> d_buf[2];
   int cur = 0;
-  long long base = 0, len = 0, pushed = 0, emitted = 0;
-  bool ended = false;
+  fdnn::stream::Window w;  // where the utterance stands (fdnn_stream_plan.hpp: the arithmetic shared with the loop's live handles)
 };
 
 extern "C" {
@@ -1095,15 +1095,14 @@ void fdnn_stream_free(fdnn_stream *s) {
 
 int fdnn_stream_reset(fdnn_stream *s) {
   if (!s) return fail(FDNN_E_ARG, "null stream");
-  s->base = s->len = s->pushed = s->emitted = 0;
-  s->ended = false;
+  s->w = fdnn::stream::Window{};
   return FDNN_OK;
 }
 
 int fdnn_stream_position(const fdnn_stream *s, int64_t *pushed, int64_t *emitted) {
   if (!s) return fail(FDNN_E_ARG, "null stream");
-  if (pushed) *pushed = s->pushed;
-  if (emitted) *emitted = s->emitted;
+  if (pushed) *pushed = s->w.pushed;
+  if (emitted) *emitted = s->w.emitted;
   return FDNN_OK;
 }
 
@@ -1112,7 +1111,7 @@ fdnn_ctx *fdnn_stream_ctx(fdnn_stream *s) { return s ? s->c : nullptr; }
 int fdnn_stream_push(fdnn_stream *s, const float *raw, int n_raw, int end, float *out, int *n_out) {
   if (!s || !n_out) return fail(FDNN_E_ARG, "null argument");
   *n_out = 0;
-  if (s->ended) return fail(FDNN_E_STATE, "the stream has ended: fdnn_stream_reset starts the next utterance");
+  if (s->w.ended) return fail(FDNN_E_STATE, "the stream has ended: fdnn_stream_reset starts the next utterance");
   if (n_raw < 0 || n_raw > s->max_chunk) return fail(FDNN_E_ARG, "a push holds 0 .. max_chunk raw frames");
   if (n_raw > 0 && !raw) return fail(FDNN_E_ARG, "null raw frames");
   fdnn_model *m = s->m;
@@ -1123,30 +1122,26 @@ int fdnn_stream_push(fdnn_stream *s, const float *raw, int n_raw, int end, float
   CtxUse use;  // (left when the push returns: every way out below has synchronised or failed)
   HIP_TRY(use.enter(c, st));
   // keep what rows not emitted yet still read: frames from emitted - L on
-  const long long keep = std::max(s->base, s->emitted - s->left);
-  if (keep > s->base) {
-    const long long kept = s->base + s->len - keep;
-    if (kept > 0)
-      HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur ^ 1], s->d_buf[s->cur] + size_t(keep - s->base) * D, sizeof(float) * size_t(kept) * D,
+  fdnn::stream::Window &w = s->w;
+  const fdnn::stream::Keep k = fdnn::stream::keep_frames(w, s->left);
+  if (k.moved) {
+    if (k.kept > 0)
+      HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur ^ 1], s->d_buf[s->cur] + size_t(k.drop) * D, sizeof(float) * size_t(k.kept) * D,
                              hipMemcpyDeviceToDevice, st));
     s->cur ^= 1;
-    s->base = keep;
-    s->len = kept;
   }
+  const long long at = fdnn::stream::append_frames(w, n_raw);
   if (n_raw > 0)
-    HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur] + size_t(s->len) * D, raw, sizeof(float) * size_t(n_raw) * D, hipMemcpyHostToDevice, st));
-  s->len += n_raw;
-  s->pushed += n_raw;
+    HIP_TRY(hipMemcpyAsync(s->d_buf[s->cur] + size_t(at) * D, raw, sizeof(float) * size_t(n_raw) * D, hipMemcpyHostToDevice, st));
   // complete rows: t + R has arrived; at the end of the stream every row, right-clamped to the last frame
-  const long long upto = end ? s->pushed : std::max(s->emitted, s->pushed - s->right);
-  const int rows = int(upto - s->emitted);
+  const fdnn::stream::Rows done = fdnn::stream::complete_rows(w, s->right, end != 0);
+  const int rows = done.rows;
   int rc = FDNN_OK;
   c->n = rows;
   c->last = rows ? -1 : 0;
   if (rows > 0) {
-    const int lo = int(std::max(-s->base, -(1LL << 30)));  // global frame 0 -- the left clamp -- as a buffer index
-    const std::vector<fdnn::SpliceSeg> segs{fdnn::SpliceSeg{0, int(s->emitted - s->base), lo, int(s->pushed - 1 - s->base)}};
-    fdnn::splice_rows(*s->spec, m->hm.hdr.in_dim, s->d_buf[s->cur], int(s->len), segs, 0, rows, c->d_x, st);
+    const std::vector<fdnn::SpliceSeg> segs{done.seg};
+    fdnn::splice_rows(*s->spec, m->hm.hdr.in_dim, s->d_buf[s->cur], int(w.len), segs, 0, rows, c->d_x, st);
     if (out) {
       rc = dense_pass_to_host(c, out, st);  // (synchronises)
     } else {
@@ -1157,8 +1152,7 @@ int fdnn_stream_push(fdnn_stream *s, const float *raw, int n_raw, int end, float
     rc = fail(FDNN_E_DEVICE, "fdnn_stream_push: stream synchronisation");
   }
   if (rc) return rc;
-  s->emitted = upto;
-  s->ended = end != 0;
+  fdnn::stream::commit(w, done, end != 0);
   *n_out = rows;
   return FDNN_OK;
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "fdnn_internal.hpp"
+#include "fdnn_server_plan.hpp"
 
 using namespace fdnn;
 
@@ -400,6 +401,57 @@ int fdnn_debug_layer0_screen(fdnn_model *m, const float *x, int n, uint8_t *u8_o
   if (!m || !x || !u8_out || !t_out || !dd_out || n <= 0) return fail(FDNN_E_ARG, "bad argument");
   if (!m->d_w0d) return fail(FDNN_E_STATE, "this model's input layer has no int8 screening (input width outside 64..496)");
   return debug_layer0(m, x, n, u8_out, t_out, dd_out, recomputed);
+}
+
+// ---------------------------------------------------------------- the splice alone
+// Host in, host out.  use_table: the raw frames and the table go up in ONE buffer laid out as a live batch of the scoring loop
+// lays it out (fdnn::plan::live_table), and the table kernel runs; otherwise fdnn::splice_rows, as every other caller has it.
+int fdnn_debug_splice_table(const int *offsets, int count, int raw_dim, int input_dim, const float *raw, int raw_frames, const int32_t *segs,
+                            int n_segs, int rows, int use_table, float *x, int device) {
+  if (!offsets || !raw || !segs || !x) return fail(FDNN_E_ARG, "null argument");
+  if (count < 1 || count > fdnn::kSpliceMaxOffsets || raw_dim < 1 || input_dim < 4 || input_dim % 4 || input_dim < count * raw_dim)
+    return fail(FDNN_E_ARG, "splice: 1 .. 64 offsets, an input width that is a multiple of 4 and holds count x raw_dim");
+  if (raw_frames < 1 || rows < 1 || n_segs < 1 || n_segs > rows) return fail(FDNN_E_ARG, "splice: frames, rows and 1 .. rows segments");
+  auto spec = std::make_shared<fdnn::SpliceSpec>();
+  spec->offsets.assign(offsets, offsets + count);
+  spec->raw_dim = raw_dim;
+  fdnn::plan::BatchPlan b;
+  b.spec = spec, b.raw = b.live = true, b.rows = rows, b.raw_frames = raw_frames;
+  for (int g = 0; g < n_segs; ++g) {
+    const int32_t *w = segs + 4 * size_t(g);
+    // rows ascend from 0 inside [0, rows); a segment holds at least one frame of the buffer
+    const bool row_ok = g ? w[0] > b.segs.back().row : w[0] == 0;
+    if (!row_ok || w[0] >= rows || w[2] > w[3] || w[3] < 0 || w[2] >= raw_frames)
+      return fail(FDNN_E_ARG, "splice: segment " + std::to_string(g) + " is malformed");
+    b.segs.push_back(fdnn::SpliceSeg{w[0], w[1], w[2], w[3]});
+  }
+  DeviceGuard g(device);
+  if (!g.ok) return fail(FDNN_E_DEVICE, "hipSetDevice failed");
+  const fdnn::plan::LiveTable t = fdnn::plan::live_table(b);
+  const size_t raw_words = size_t(raw_frames) * size_t(raw_dim), x_words = size_t(rows) * size_t(input_dim);
+  std::vector<float> up(t.words, 0.0f);
+  std::memcpy(up.data(), raw, sizeof(float) * raw_words);
+  fdnn::plan::write_live_table(b, t, reinterpret_cast<int32_t *>(up.data()));
+  fdnn::DevBuf<float> d_up, d_x;
+  HIP_TRY(d_up.reserve(t.words));
+  HIP_TRY(d_x.reserve(x_words));
+  HIP_TRY(hipMemcpy(d_up, up.data(), sizeof(float) * t.words, hipMemcpyHostToDevice));
+  const int32_t *d_table = reinterpret_cast<const int32_t *>(d_up.p);
+  if (use_table)
+    fdnn::splice_rows_table(*spec, input_dim, d_up, raw_frames, d_table + t.segs_at, d_table + t.row_seg_at, n_segs, rows, d_x, nullptr);
+  else
+    fdnn::splice_rows(*spec, input_dim, d_up, raw_frames, b.segs, 0, rows, d_x, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(x, d_x, sizeof(float) * x_words, hipMemcpyDeviceToHost));
+  return FDNN_OK;
+}
+
+int fdnn_debug_live_launches(unsigned long long *launches, unsigned long long *max_segs) {
+  unsigned long long a = 0, b = 0;
+  fdnn::splice_table_counts(&a, &b);
+  if (launches) *launches = a;
+  if (max_segs) *max_segs = b;
+  return FDNN_OK;
 }
 
 // ---------------------------------------------------------------- per-kernel timing

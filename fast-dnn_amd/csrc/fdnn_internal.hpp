@@ -349,6 +349,10 @@ int ctx_raw_reserve(fdnn_ctx *c, size_t frames, int raw_dim);
 // ascending by row, the first at or before row0.  Tables longer than one launch's go as several launches.
 void splice_rows(const SpliceSpec &spec, int input_dim, const float *raw, int raw_frames, const std::vector<SpliceSeg> &segs,
                  int row0, int rows, float *d_x, hipStream_t s);
+// Splices rows [0, rows) through a segment table that is already in device memory (launch_splice_table: d_segs [n_segs][4],
+// d_row_seg [rows]): one launch whatever n_segs is.  The scoring loop's batches with a live piece, and nothing else.
+void splice_rows_table(const SpliceSpec &spec, int input_dim, const float *raw, int raw_frames, const int32_t *d_segs,
+                       const int32_t *d_row_seg, int n_segs, int rows, float *d_x, hipStream_t s);
 // Rows [a, b) of one n-frame utterance (host raw frames) into out[b - a][O], spliced by `spec`: through the model's batcher
 // when it has one, else the raw frames those rows reference travel once and are spliced and scored chunk by chunk.
 // fdnn_calculate_raw on one device, and a group replica's shard.

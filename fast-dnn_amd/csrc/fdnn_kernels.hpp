@@ -304,5 +304,15 @@ struct SpliceArgs {
 };
 // rows [row0, row0 + rows) into x[rows][input_dim] (x holds row row0 first); raw [raw_frames][raw_dim]
 void launch_splice(const float *raw, int raw_frames, float *x, int row0, int rows, const SpliceArgs &a, hipStream_t s);
+// The same rows [0, rows) from a segment table in DEVICE memory, one launch whatever its length (a live batch of the scoring
+// loop: one segment per push): d_segs [n_segs][4] = (row, center, lo, hi), 16-byte aligned; d_row_seg [rows], each row's
+// segment index.  Only the offsets travel as kernel arguments.  Counted by splice_table_counts, not by the launch recorder.
+struct SpliceOffsets {
+  int offsets[kSpliceMaxOffsets];
+  int count, raw_dim, input_dim;
+};
+void launch_splice_table(const float *raw, int raw_frames, float *x, int rows, const int32_t *d_segs, const int32_t *d_row_seg, int n_segs,
+                         const SpliceOffsets &a, hipStream_t s);
+void splice_table_counts(unsigned long long *launches, unsigned long long *max_segs);  // process-wide: launches, the longest table
 
 }  // namespace fdnn

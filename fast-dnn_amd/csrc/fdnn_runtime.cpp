@@ -893,6 +893,16 @@ void splice_rows(const SpliceSpec &spec, int input_dim, const float *raw, int ra
   }
 }
 
+void splice_rows_table(const SpliceSpec &spec, int input_dim, const float *raw, int raw_frames, const int32_t *d_segs,
+                       const int32_t *d_row_seg, int n_segs, int rows, float *d_x, hipStream_t s) {
+  fdnn::SpliceOffsets a{};
+  a.count = int(spec.offsets.size());
+  a.raw_dim = spec.raw_dim;
+  a.input_dim = input_dim;
+  std::copy(spec.offsets.begin(), spec.offsets.end(), a.offsets);
+  fdnn::launch_splice_table(raw, raw_frames, d_x, rows, d_segs, d_row_seg, n_segs, a, s);
+}
+
 // Lazy results to a host caller.  Every inactive node of a row reads the same 1 / total (dnn.cc:366-369, :389), so what
 // crosses PCIe is the active nodes' probabilities and that one value per frame (lazy_compact_kernel); the rows are
 // rebuilt on the host inside the caller's array: the compacted block lands in its tail, and the rows are expanded front to

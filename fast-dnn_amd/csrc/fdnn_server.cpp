@@ -41,6 +41,7 @@
 #include "fdnn_internal.hpp"
 #include "fdnn_lists.hpp"
 #include "fdnn_server_plan.hpp"
+#include "fdnn_stream_plan.hpp"
 
 using fdnn::Buf;  // a slot's staging buffers: pinned host memory, or device memory (fdnn_buf.hpp)
 using fdnn::DeviceGuard;
@@ -118,6 +119,7 @@ struct fdnn_server {
   bool staging = false;
   std::condition_variable stage_cv;
   bool stop = false;
+  bool hold = false;              // fdnn_debug_server_hold: the packer plans nothing, submissions queue up (under qmu)
   bool host_ready = false;
   int linger_us = 0;
   // statistics
@@ -281,7 +283,7 @@ bool stage_one(fdnn_server *s, std::unique_lock<std::mutex> &lk) {
 
 // The packer's steps, in packer_loop's order.  Work to pack (false: the loop ends with nothing queued).  Call with qmu held.
 bool wait_for_work(fdnn_server *s, std::unique_lock<std::mutex> &lk) {
-  s->qcv.wait(lk, [&] { return s->stop || !s->queue.empty(); });
+  s->qcv.wait(lk, [&] { return s->stop || (!s->hold && !s->queue.empty()); });
   if (s->stop && s->queue.empty()) return false;
   // lingering only pays while an earlier batch keeps the device busy: an idle server launches at once
   const bool gpu_busy = std::any_of(s->slots.begin(), s->slots.end(), [](const Slot &sl) { return sl.in_flight; });
@@ -364,8 +366,11 @@ hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
   // whole rows of a batch that several callers share land in pinned memory only
   if (f.leave == Form::whole_rows && sl.h_out.reserve(frames * O) != hipSuccess) leave_by_caller_copies(b);
   if (!b.raw) return hipSuccess;
-  e = sl.h_raw.reserve(size_t(b.raw_frames) * size_t(b.spec->raw_dim));
-  if (e == hipSuccess && fdnn::ctx_raw_reserve(sl.ctx, size_t(b.raw_frames), b.spec->raw_dim)) return hipErrorOutOfMemory;
+  // a live batch's segment table rides behind the raw frames, in the same buffers and the same copy (live_table): the room
+  // is asked for in whole raw frames
+  const size_t RD = size_t(b.spec->raw_dim), words = b.live ? live_table(b).words : size_t(b.raw_frames) * RD;
+  e = sl.h_raw.reserve(words);
+  if (e == hipSuccess && fdnn::ctx_raw_reserve(sl.ctx, (words + RD - 1) / RD, b.spec->raw_dim)) return hipErrorOutOfMemory;
   return e;
 }
 
@@ -398,9 +403,18 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
   fdnn_ctx *c = sl.ctx;
   hipError_t e;
   if (b.raw) {  // only the raw frames cross PCIe; the rows are spliced on the device, each piece within its utterance
-    const size_t raw_floats = size_t(b.raw_frames) * size_t(b.spec->raw_dim);
-    e = hipMemcpyAsync(c->d_raw, sl.h_raw.p, sizeof(float) * raw_floats, hipMemcpyHostToDevice, sl.stream);
-    if (e == hipSuccess) fdnn::splice_rows(*b.spec, int(D), c->d_raw, b.raw_frames, b.segs, 0, b.rows, c->d_x, sl.stream);
+    // A batch with a live piece has about one segment per push: its table goes up behind the frames, in the same copy, and
+    // ONE launch reads it from device memory.  Every other batch: the table by value, as ever (fdnn::splice_rows).
+    const LiveTable t = b.live ? live_table(b) : LiveTable{};
+    if (b.live) write_live_table(b, t, reinterpret_cast<int32_t *>(sl.h_raw.p));
+    const size_t raw_words = b.live ? t.words : size_t(b.raw_frames) * size_t(b.spec->raw_dim);
+    e = hipMemcpyAsync(c->d_raw, sl.h_raw.p, sizeof(float) * raw_words, hipMemcpyHostToDevice, sl.stream);
+    const int32_t *d_table = reinterpret_cast<const int32_t *>(c->d_raw.p);
+    if (e == hipSuccess && b.live)
+      fdnn::splice_rows_table(*b.spec, int(D), c->d_raw, b.raw_frames, d_table + t.segs_at, d_table + t.row_seg_at, int(b.segs.size()), b.rows,
+                              c->d_x, sl.stream);
+    else if (e == hipSuccess)
+      fdnn::splice_rows(*b.spec, int(D), c->d_raw, b.raw_frames, b.segs, 0, b.rows, c->d_x, sl.stream);
   } else {
     e = hipMemcpyAsync(c->d_x, sl.h_x.p, sizeof(float) * rows * D, hipMemcpyHostToDevice, sl.stream);
   }
@@ -559,14 +573,17 @@ int submit_host(fdnn_server *s, Request r, uint64_t *ticket) {
 // submit_host.  Two bad arguments at once fail in this order.
 using WantOut = std::optional<Want>;
 template <class MakeWant>
-int submit_frames(fdnn_server *s, const fdnn::SpliceRef *spec, const float *frames, int n, int a, int b, uint64_t *ticket, MakeWant &&want) {
+int submit_frames(fdnn_server *s, const fdnn::SpliceRef *spec, const float *frames, int n, int a, int b, uint64_t *ticket, MakeWant &&want,
+                  const WindowRef &window = nullptr) {
   if (spec)
     if (int rc = fdnn::splice_check(*spec, -1)) return rc;
   if (n <= 0 || a < 0 || b > n || b <= a) return fail(FDNN_E_ARG, "frame count must be positive");
   if (!frames) return fail(FDNN_E_ARG, "null buffer");
   WantOut w;
   if (int rc = want(&w)) return rc;
-  return submit_host(s, Request(spec ? Frames::raw_rows(frames, *spec, n, a) : Frames::rows(frames), *w, b - a), ticket);
+  // (window: a live push's own copy of its frames -- `frames` points into it, and the request keeps it alive)
+  const Frames f = window ? Frames::live_rows(window, *spec, n, a) : spec ? Frames::raw_rows(frames, *spec, n, a) : Frames::rows(frames);
+  return submit_host(s, Request(f, *w, b - a), ticket);
 }
 
 // ... for the extern "C" entries: n rows x, or (kRaw) a whole n-frame utterance under the model's splice spec as it is now
@@ -612,6 +629,50 @@ int want_rows(fdnn_server *s, int n, const int8_t *masks, const uint64_t *bits, 
   *w = bits    ? Want::rows_behind_bits_to(bits, widest_row(bits, n, size_t(s->m->hm.hdr.out_dim)), out)
        : masks ? Want::rows_behind_bytes_to(masks, out)
                : Want::rows_to(out);
+  return FDNN_OK;
+}
+
+}  // namespace
+
+// A live utterance of the loop (fdnn_server_live_*): where it stands, and its window -- the last L + R frames plus the last
+// push's new ones -- on the host.  Every push makes a new window (at most L + R + max_chunk frames, 156 B each) and hands it to
+// its request, so a queued push never reads the caller's memory or this handle: reset and close need not wait for anything.
+struct fdnn_live {
+  fdnn_server *s = nullptr;
+  fdnn::SpliceRef spec;  // the model's spec when the handle was opened: every push is spliced by it
+  int max_chunk = 0;
+  fdnn::stream::Window w;
+  WindowRef window;
+};
+
+namespace {
+
+// The one path of every live push.  The position arithmetic is fdnn_stream_push's (fdnn_stream_plan.hpp); the rows the push
+// completes are rows [a, a + rows) of the window, submitted as any raw rows are (submit_frames).  want(rows, &w): the entry's
+// Want for that many rows -- built for a push that completes none as well, so that a bad argument fails at the first push
+// and not at whichever push first has rows.  The handle moves on only when the push has been accepted.
+template <class MakeWant>
+int live_push(fdnn_live *l, const float *raw, int n_raw, int end, int *n_out, uint64_t *ticket, MakeWant &&want) {
+  if (!l || !n_out || !ticket) return fail(FDNN_E_ARG, "null argument");
+  *n_out = 0;
+  *ticket = 0;
+  if (l->w.ended) return fail(FDNN_E_STATE, "the utterance has ended: fdnn_server_live_reset starts the next one");
+  if (n_raw < 0 || n_raw > l->max_chunk) return fail(FDNN_E_ARG, "a push holds 0 .. max_chunk raw frames");
+  if (n_raw > 0 && !raw) return fail(FDNN_E_ARG, "null raw frames");
+  // the push's window: the kept frames and the new ones, copied (the caller may overwrite its frames at once)
+  fdnn::stream::HostPush p = fdnn::stream::host_push(l->w, l->window, *l->spec, raw, n_raw, end != 0);
+  const fdnn::stream::Rows &done = p.done;
+  if (done.rows > 0) {
+    const int rc = submit_frames(l->s, &l->spec, p.window->data(), done.raw_n, done.a, done.a + done.rows, ticket,
+                                 [&](WantOut *o) { return want(done.rows, o); }, p.window);
+    if (rc) return rc;
+  } else {  // nothing to score and nothing to wait for; the arguments are held to the same checks
+    WantOut o;
+    if (int rc = want(0, &o)) return rc;
+  }
+  l->w = p.after;
+  l->window = std::move(p.window);
+  *n_out = done.rows;
   return FDNN_OK;
 }
 
@@ -784,6 +845,66 @@ int fdnn_server_submit_pool(fdnn_server *s, const float *x, int n, const fdnn_po
 
 int fdnn_server_submit_raw_pool(fdnn_server *s, const float *raw, int n, const fdnn_pool *pool, float *out, uint64_t *ticket) {
   return submit_entry(s, kRaw, raw, n, ticket, [&](WantOut *w) { return want_pool(s, pool, out, w); });
+}
+
+int fdnn_server_live_open(fdnn_server *s, int max_chunk, fdnn_live **out) {
+  if (!s || !out) return fail(FDNN_E_ARG, "null argument");
+  *out = nullptr;
+  const fdnn::SpliceRef spec = s->m->splice;
+  if (int rc = fdnn::splice_check(spec, -1)) return rc;
+  if (max_chunk < 1) return fail(FDNN_E_ARG, "max_chunk must be positive");
+  fdnn_live *l = new fdnn_live();
+  l->s = s;
+  l->spec = spec;
+  l->max_chunk = max_chunk;
+  *out = l;
+  return FDNN_OK;
+}
+
+void fdnn_server_live_close(fdnn_live *l) { delete l; }  // (queued pushes own their frames)
+
+int fdnn_server_live_reset(fdnn_live *l) {
+  if (!l) return fail(FDNN_E_ARG, "null live handle");
+  l->w = fdnn::stream::Window{};
+  l->window.reset();
+  return FDNN_OK;
+}
+
+int fdnn_server_live_position(const fdnn_live *l, int64_t *pushed, int64_t *emitted) {
+  if (!l) return fail(FDNN_E_ARG, "null live handle");
+  if (pushed) *pushed = l->w.pushed;
+  if (emitted) *emitted = l->w.emitted;
+  return FDNN_OK;
+}
+
+int fdnn_server_live_push(fdnn_live *l, const float *raw, int n_raw, int end, float *out, int *n_out, uint64_t *ticket) {
+  return live_push(l, raw, n_raw, end, n_out, ticket, [&](int rows, WantOut *w) { return want_rows(l->s, rows, nullptr, nullptr, out, w); });
+}
+
+int fdnn_server_live_push_topk(fdnn_live *l, const float *raw, int n_raw, int end, int k, int32_t *nodes, float *probs, int *n_out,
+                               uint64_t *ticket) {
+  return live_push(l, raw, n_raw, end, n_out, ticket, [&](int, WantOut *w) { return want_topk(l->s, k, nodes, probs, w); });
+}
+
+int fdnn_server_live_push_pool(fdnn_live *l, const float *raw, int n_raw, int end, const fdnn_pool *pool, float *out, int *n_out,
+                               uint64_t *ticket) {
+  return live_push(l, raw, n_raw, end, n_out, ticket, [&](int, WantOut *w) { return want_pool(l->s, pool, out, w); });
+}
+
+int fdnn_server_live_push_set(fdnn_live *l, const float *raw, int n_raw, int end, const int32_t *nodes, int len, float *probs,
+                              float *inactive, int *n_out, uint64_t *ticket) {
+  return live_push(l, raw, n_raw, end, n_out, ticket,
+                   [&](int rows, WantOut *w) { return want_set(l->s, rows, nodes, len, probs, inactive, w); });
+}
+
+int fdnn_debug_server_hold(fdnn_server *s, int on) {
+  if (!s) return fail(FDNN_E_ARG, "null argument");
+  {
+    std::lock_guard<std::mutex> lk(s->qmu);
+    s->hold = on != 0;
+  }
+  s->qcv.notify_all();  // (switched off: the packer looks at the queue again)
+  return FDNN_OK;
 }
 
 int fdnn_server_wait(fdnn_server *s, uint64_t ticket) {

@@ -20,6 +20,8 @@ namespace fdnn::plan {
 
 // A set submission's node set, copied at submit and shared by the request, its parts and their pieces (as SpliceRef is)
 using SetRef = std::shared_ptr<const std::vector<int32_t>>;
+// A live push's window of raw frames [frames][raw_dim], copied at the push and shared the same way
+using WindowRef = std::shared_ptr<const std::vector<float>>;
 
 // ---------------------------------------------------------------- the two parts of a request
 // Where a request's frames come from.  Built by name only.
@@ -34,8 +36,17 @@ class Frames {
   const float *raw = nullptr;
   SpliceRef spec;
   int raw_n = 0, raw_a = 0;
+  // live pushes (fdnn_server_live_*): the "utterance" is the push's window -- the frames its handle had kept plus the new
+  // ones, copied at the push -- and the request, its parts and their batches own it: `raw` points into it.  Null otherwise:
+  // the caller keeps its frames valid.
+  WindowRef window;
   static Frames rows(const float *x) { Frames f; f.x = x; return f; }
   static Frames raw_rows(const float *raw, const SpliceRef &spec, int raw_n, int raw_a) { Frames f; f.kind = raw_frames, f.raw = raw, f.spec = spec, f.raw_n = raw_n, f.raw_a = raw_a; return f; }
+  static Frames live_rows(WindowRef window, const SpliceRef &spec, int raw_n, int raw_a) {
+    Frames f = raw_rows(window->data(), spec, raw_n, raw_a);
+    f.window = std::move(window);
+    return f;
+  }
 };
 
 // What the caller wants back, for n rows.  One named constructor per kind, as fdnn::pass::Pass has: nothing reads a kind
@@ -157,6 +168,8 @@ struct BatchPlan {
   Want::Kind kind = Want::rows;  // of all its requests, except that rows ride in a rows_behind_bytes batch (may_join)
   int rows = 0, raw_frames = 0, most = 0, stride = 0;  // stride: floats per compacted row (0: the rows leave whole)
   bool any_mask = false, raw = false;
+  bool live = false;  // raw batches: a piece is a live push -- the batch has about one segment per push, hundreds of them, and
+                      // is spliced through the segment table in device memory (live_table)
   int nnz = 0, set_nodes = 0;  // set batches: the floats of the batch's probs (sum of rows x len) and the nodes of its pieces' sets
   int topk_k = 0;              // top-k batches: the largest k among its pieces (a smaller k's result is a prefix of it)
   const fdnn_pool *pool = nullptr;  // pool batches: the one handle of all its pieces ...
@@ -245,6 +258,7 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
     }
     b.pieces.push_back(std::move(pc));
     if (b.raw) {  // the raw frames this piece's rows reference, and where they are staged
+      b.live |= r.frames.window != nullptr;
       const int u0 = r.frames.raw_a + part.taken;  // the piece's first row as a frame of its utterance
       int fa, fb;
       splice_halo(*r.frames.spec, r.frames.raw_n, u0, u0 + take, &fa, &fb);
@@ -283,6 +297,30 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
     case Want::pool: set_leave(b, Form::class_sums, O); break;
   }
   return b;
+}
+
+// A live batch's segment table, staged behind the raw frames in the slot's buffer and uploaded with them in the same copy.
+// In 32-bit words of that buffer: the raw frames [0, raw_frames * raw_dim); from `segs_at` (the next multiple of four words:
+// the kernel reads a segment as one 16-byte load) the segments as (row, center, lo, hi), four words each; from `row_seg_at`
+// one word per row of the batch, the index of the row's segment.  `words`: all of it.
+struct LiveTable {
+  size_t segs_at = 0, row_seg_at = 0, words = 0;
+};
+inline LiveTable live_table(const BatchPlan &b) {
+  LiveTable t;
+  t.segs_at = (size_t(b.raw_frames) * size_t(b.spec->raw_dim) + 3) & ~size_t(3);
+  t.row_seg_at = t.segs_at + 4 * b.segs.size();
+  t.words = t.row_seg_at + size_t(b.rows);
+  return t;
+}
+inline void write_live_table(const BatchPlan &b, const LiveTable &t, int32_t *buffer) {
+  for (size_t g = 0; g < b.segs.size(); ++g) {
+    const SpliceSeg &sg = b.segs[g];
+    int32_t *w = buffer + t.segs_at + 4 * g;
+    w[0] = sg.row, w[1] = sg.center, w[2] = sg.lo, w[3] = sg.hi;
+    const int end = g + 1 < b.segs.size() ? b.segs[g + 1].row : b.rows;
+    for (int r = sg.row; r < end; ++r) buffer[t.row_seg_at + size_t(r)] = int32_t(g);
+  }
 }
 
 // A piece's part of the batch's one transfer, from the slot's landing buffer (form.words 32-bit words, as the device wrote

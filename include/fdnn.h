@@ -487,6 +487,46 @@ FDNN_API int fdnn_server_submit_raw_topk(fdnn_server *s, const float *raw, int n
  * submit time. */
 FDNN_API int fdnn_server_submit_pool(fdnn_server *s, const float *x, int n, const fdnn_pool *pool, float *out, uint64_t *ticket);
 FDNN_API int fdnn_server_submit_raw_pool(fdnn_server *s, const float *raw, int n, const fdnn_pool *pool, float *out, uint64_t *ticket);
+/* Live utterances through the loop: many utterances arriving at once, each chunk by chunk (SURVEY 8(f) row 3 as a real-time
+ * recogniser meets it; see "Streams" above for one utterance on its own).  A live handle is the stream object of ONE
+ * utterance at a time; its pushes are scored by the loop, in batches shared with the other handles' pushes and with whole
+ * raw utterances (fdnn_server_submit_raw*) of the same spec, same kind of return and, for pool, same handle.  Over an
+ * utterance's pushes the rows are byte for byte those of fdnn_calculate_raw / fdnn_calculate_topk_raw /
+ * fdnn_calculate_pool_raw on the whole utterance, and for sets those of fdnn_calculate_lazy_set on the host-spliced rows,
+ * whatever the chunking and whatever else shared the batches.
+ * fdnn_server_live_open      max_chunk: the most raw frames one push may carry.  The handle keeps the model's spec of this
+ *   moment (FDNN_E_STATE when the model has none), as fdnn_stream_create does, and the last max(-o, 0) + max(o, 0) raw frames
+ *   on the HOST: a push re-stages them, 156 B per frame of 39 floats.
+ * fdnn_server_live_close     frees the handle.  Never waits: queued pushes own their frames, their tickets stay valid.  Close
+ *   every handle before fdnn_server_free.
+ * fdnn_server_live_reset     the next push starts a new utterance (also after a push with `end`, which closes the utterance:
+ *   a further push without a reset is FDNN_E_STATE).  Never waits either.
+ * fdnn_server_live_position  raw frames pushed and rows emitted since the utterance started.
+ * fdnn_server_live_push      n_raw (0 .. max_chunk) raw frames [n_raw][D].  Returns AT ONCE: *n_out is the number of rows this
+ *   push completes -- row t is complete once frame t + max(o, 0) has arrived; end != 0 flushes the rest, right-clamped to the
+ *   last frame (n_raw = 0 is a flush only) --, known when the call returns, and the rows themselves are in out
+ *   [*n_out][output_dim] once fdnn_server_wait(*ticket) has returned.  out must hold n_raw + max(o, 0) rows and stay valid
+ *   until then; `raw` is COPIED by the push, the caller may overwrite it at once (a feed's ring buffer does).  A push that
+ *   completes no rows queues nothing and sets *ticket = 0: there is then nothing to wait for (fdnn_server_wait refuses
+ *   ticket 0).  The buffers are checked all the same.
+ * fdnn_server_live_push_topk / _pool / _set   the same push with the return of fdnn_server_submit_raw_topk (nodes and probs
+ *   [*n_out][k]), fdnn_server_submit_raw_pool (out [*n_out][C]: the silence posterior out of a class map, for end-pointing)
+ *   and fdnn_server_submit_raw_set (probs [*n_out][len], inactive [*n_out]: one keyword's nodes; the set is copied), with
+ *   those entries' argument checks.  There is no bit-mask form: a recogniser does not have the masks of frames it has not
+ *   decoded.
+ * One handle is used by one thread at a time, like a context; different handles from any threads. */
+typedef struct fdnn_live fdnn_live;
+FDNN_API int fdnn_server_live_open(fdnn_server *s, int max_chunk, fdnn_live **out);
+FDNN_API void fdnn_server_live_close(fdnn_live *l);
+FDNN_API int fdnn_server_live_reset(fdnn_live *l);
+FDNN_API int fdnn_server_live_position(const fdnn_live *l, int64_t *pushed, int64_t *emitted);
+FDNN_API int fdnn_server_live_push(fdnn_live *l, const float *raw, int n_raw, int end, float *out, int *n_out, uint64_t *ticket);
+FDNN_API int fdnn_server_live_push_topk(fdnn_live *l, const float *raw, int n_raw, int end, int k, int32_t *nodes, float *probs, int *n_out,
+                                        uint64_t *ticket);
+FDNN_API int fdnn_server_live_push_pool(fdnn_live *l, const float *raw, int n_raw, int end, const fdnn_pool *pool, float *out, int *n_out,
+                                        uint64_t *ticket);
+FDNN_API int fdnn_server_live_push_set(fdnn_live *l, const float *raw, int n_raw, int end, const int32_t *nodes, int len, float *probs,
+                                       float *inactive, int *n_out, uint64_t *ticket);
 FDNN_API int fdnn_server_wait(fdnn_server *s, uint64_t ticket);
 FDNN_API int fdnn_server_drain(fdnn_server *s);
 FDNN_API int fdnn_server_stats(fdnn_server *s, uint64_t *batches, uint64_t *frames, uint64_t *requests,
@@ -706,6 +746,20 @@ FDNN_API int fdnn_debug_pool_launches(unsigned long long *out, int cap);
 FDNN_API int fdnn_debug_set_pool_kernel(int mode);
 FDNN_API int fdnn_debug_pool_ref(const float *rows, int n, const int32_t *class_of, int width, int n_classes, float *out);
 FDNN_API int fdnn_debug_pool_limits(int *lanes, int *resident_width);
+
+/* Splicing through a segment table in device memory (the scoring loop's live batches, fdnn_splice.hip), tests and tools.
+ * fdnn_debug_splice_table   the splice alone, host in and host out: raw [raw_frames][raw_dim] -> x [rows][input_dim] under the
+ *   `count` offsets; segs [n_segs][4] = (row, center, lo, hi), rows ascending from 0: row t of segment g reads the raw frames
+ *   clamp(center + (t - row) + o, lo, hi), never outside the buffer.  use_table = 0 runs the launches every other caller has
+ *   (the table by value, 96 segments a launch), use_table = 1 the kernel that reads the table from device memory: one launch.
+ * fdnn_debug_live_launches  process-wide since load: launches of that kernel, and the longest table it has been given.  Not
+ *   in the launch recorder's table (fdnn_note.hpp).
+ * fdnn_debug_server_hold    on != 0: the loop's packer plans no batch and host submissions queue up; 0: it wakes and packs
+ *   them.  Lets a test decide which submissions share a batch.  (fdnn_server_free packs whatever is still held.) */
+FDNN_API int fdnn_debug_splice_table(const int *offsets, int count, int raw_dim, int input_dim, const float *raw, int raw_frames,
+                                     const int32_t *segs, int n_segs, int rows, int use_table, float *x, int device);
+FDNN_API int fdnn_debug_live_launches(unsigned long long *launches, unsigned long long *max_segs);
+FDNN_API int fdnn_debug_server_hold(fdnn_server *s, int on);
 
 /* Tests: write the word a fused soft-max workgroup raises (in host memory) when it gives up waiting for its frame tile's
  * siblings -- 1: as if a launch of this model had just done so (from the next call on the model runs the unfused soft-max

@@ -1,6 +1,6 @@
 // serve_bench -- the serving shape, natively: T host threads, each scoring U utterances of F frames
 // (100 frames = 1 s of speech) through the C-ABI, buffers reused, no interpreter in the loop.
-//   serve_bench model.bin threads utts_per_thread frames mode [max_frames depth linger_us]
+//   serve_bench model.bin threads utts_per_thread frames mode [max_frames depth linger_us [c]]
 //   mode: percall  = fdnn_calculate per utterance (what the JNI calculate() does)
 //         server   = fdnn_server_submit + fdnn_server_wait (coalesced host submissions)
 //         batcher  = fdnn_calculate on a model with fdnn_model_enable_batcher
@@ -17,6 +17,12 @@
 //                      48) classes of nodes (node i in class i mod POOL_C) -- frames x POOL_C x 4 bytes back
 //         poolserver = fdnn_server_submit_pool + fdnn_server_wait (pool utterances of the one handle coalesced, the dense rows
 //                      stay on the device)
+//         live       = fdnn_stream_push: every feed its own stream, utterances of F raw frames (Kaldi +-5 x 39, set here) pushed in
+//                      chunks of c frames, host-synchronous push by push
+//         liveserver = fdnn_server_live_push + fdnn_server_wait: the same feeds through live handles of ONE scoring loop; a
+//                      thread pushes the next chunk of each of its feeds, then waits for their tickets
+//                      c is the trailing argument (default 10).  FEEDS=n (environment; default: one per thread): n feeds spread
+//                      over the threads -- a few hundred live utterances are handles, not threads.
 // SET_LEN=k with lazy / lazyserver: the masks are those sets (the same k nodes in every frame of a caller) instead of 40 %.
 // INFLIGHT=k (environment, server modes): every caller keeps k utterances in flight (k result blocks per thread) instead of
 // waiting for each one before submitting the next.
@@ -34,9 +40,124 @@
 
 #include "../include/fdnn.h"
 
+// The live modes: n feeds over T threads, every feed U utterances of F raw frames in chunks of c.  One JSON line; push_us is
+// the mean time from a feed's push to its rows being in the caller's memory.
+static int run_live(fdnn_model *m, const std::string &mode, int T, int U, int F, int max_frames, int depth, int linger, int c) {
+  const int feeds = std::max(T, std::getenv("FEEDS") ? std::atoi(std::getenv("FEEDS")) : T), RD = 39, R = 5;
+  int offsets[11];
+  for (int i = 0; i < 11; ++i) offsets[i] = i - 5;
+  if (c < 1 || fdnn_model_set_splice(m, offsets, 11, RD)) {
+    std::fprintf(stderr, "live: %s (c must be positive, the net's input must hold 11 x 39 columns)\n", fdnn_last_error());
+    return 1;
+  }
+  const int O = fdnn_model_output_dim(m);
+  const bool loop = mode == "liveserver";
+  // POOL_C=C (environment): class sums [rows][C] come back instead of dense rows (node i in class i mod C) -- the stream scores
+  // its hidden layers and pools through its context, the loop takes fdnn_server_live_push_pool
+  const int pool_c = std::getenv("POOL_C") ? std::atoi(std::getenv("POOL_C")) : 0;
+  fdnn_pool *pool = nullptr;
+  if (pool_c > 0) {
+    std::vector<int32_t> class_of(static_cast<size_t>(O));
+    for (int i = 0; i < O; ++i) class_of[size_t(i)] = i % pool_c;
+    if (!(pool = fdnn_pool_create(class_of.data(), O, pool_c))) {
+      std::fprintf(stderr, "pool: %s\n", fdnn_last_error());
+      return 1;
+    }
+  }
+  const int W = pool ? pool_c : O;  // floats per returned row
+  fdnn_server *srv = nullptr;
+  if (loop && (fdnn_server_create(m, max_frames, depth, &srv) || fdnn_server_set_linger_us(srv, linger))) {
+    std::fprintf(stderr, "server: %s\n", fdnn_last_error());
+    return 1;
+  }
+  std::vector<fdnn_stream *> streams(size_t(feeds), nullptr);
+  std::vector<fdnn_live *> lives(size_t(feeds), nullptr);
+  std::vector<std::vector<float>> raw(static_cast<size_t>(feeds)), out(static_cast<size_t>(feeds));
+  std::mt19937 rng(7);
+  std::normal_distribution<float> nd(0.0f, 3.0f);
+  for (int k = 0; k < feeds; ++k) {
+    raw[size_t(k)].resize(size_t(F) * RD);
+    for (float &v : raw[size_t(k)]) v = nd(rng);
+    out[size_t(k)].assign(size_t(c + R) * size_t(W), 0.0f);
+    if (loop ? fdnn_server_live_open(srv, c, &lives[size_t(k)]) : fdnn_stream_create(m, c, &streams[size_t(k)])) {
+      std::fprintf(stderr, "feed %d: %s\n", k, fdnn_last_error());
+      return 1;
+    }
+  }
+  std::atomic<int> failed{0};
+  std::atomic<long long> rows{0}, wait_ns{0}, pushes{0};
+  auto body = [&](int t, int utts) {
+    std::vector<uint64_t> tickets;
+    std::vector<std::chrono::steady_clock::time_point> pushed;
+    long long my_rows = 0, my_ns = 0, my_pushes = 0;
+    for (int u = 0; u < utts; ++u) {
+      for (int pos = 0; pos < F; pos += c) {
+        const int n = std::min(c, F - pos), end = pos + c >= F;
+        tickets.clear(), pushed.clear();
+        for (int k = t; k < feeds; k += T) {
+          int n_out = 0;
+          uint64_t ticket = 0;
+          const auto t0 = std::chrono::steady_clock::now();
+          const float *chunk = raw[size_t(k)].data() + size_t(pos) * RD;
+          float *o = out[size_t(k)].data();
+          int rc;
+          if (loop) {
+            rc = pool ? fdnn_server_live_push_pool(lives[size_t(k)], chunk, n, end, pool, o, &n_out, &ticket)
+                      : fdnn_server_live_push(lives[size_t(k)], chunk, n, end, o, &n_out, &ticket);
+          } else {
+            rc = fdnn_stream_push(streams[size_t(k)], chunk, n, end, pool ? nullptr : o, &n_out);
+            if (!rc && pool && n_out > 0) rc = fdnn_ctx_output_pool(fdnn_stream_ctx(streams[size_t(k)]), pool, o);
+          }
+          if (rc) ++failed;
+          my_rows += n_out, ++my_pushes;
+          if (!loop) my_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+          if (ticket) tickets.push_back(ticket), pushed.push_back(t0);
+        }
+        for (size_t i = 0; i < tickets.size(); ++i) {
+          if (fdnn_server_wait(srv, tickets[i])) ++failed;
+          my_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - pushed[i]).count();
+        }
+      }
+      for (int k = t; k < feeds; k += T)
+        if (loop ? fdnn_server_live_reset(lives[size_t(k)]) : fdnn_stream_reset(streams[size_t(k)])) ++failed;
+    }
+    rows += my_rows, wait_ns += my_ns, pushes += my_pushes;
+  };
+  auto run = [&](int utts) {
+    rows = 0, wait_ns = 0, pushes = 0;
+    std::vector<std::thread> th;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int t = 0; t < T; ++t) th.emplace_back(body, t, utts);
+    for (auto &x : th) x.join();
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  };
+  run(std::max(1, U / 10));  // warm-up
+  const double sec = run(U);
+  double sum = 0.0;  // the last row of feed 0's last push
+  for (int i = 0; i < W; ++i) sum += out[0][size_t(i)];
+  uint64_t batches = 0, frames = 0, reqs = 0, coal = 0;
+  unsigned long long launches = 0, max_segs = 0;
+  if (srv) fdnn_server_stats(srv, &batches, &frames, &reqs, &coal);
+  fdnn_debug_live_launches(&launches, &max_segs);
+  if (rows.load() != (long long)feeds * U * F) ++failed;  // every frame's row came back
+  std::printf("{\"mode\": \"%s\", \"pool_c\": %d, \"threads\": %d, \"feeds\": %d, \"frames_per_utt\": %d, \"chunk\": %d, \"utts\": %d, \"seconds\": %.4f, "
+              "\"frames_per_s\": %.1f, \"push_us\": %.1f, \"row0_sum\": %.6f, \"failed\": %d, \"batches\": %llu, \"requests\": %llu, "
+              "\"max_segs\": %llu}\n",
+              mode.c_str(), pool_c, T, feeds, F, c, feeds * U, sec, double(feeds) * U * F / sec, wait_ns.load() / 1e3 / double(std::max(1LL, pushes.load())),
+              sum, failed.load(), (unsigned long long)batches, (unsigned long long)reqs, max_segs);
+  for (int k = 0; k < feeds; ++k) {
+    fdnn_server_live_close(lives[size_t(k)]);
+    fdnn_stream_free(streams[size_t(k)]);
+  }
+  if (srv) fdnn_server_free(srv);
+  fdnn_pool_free(pool);
+  fdnn_model_free(m);
+  return failed.load() ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: serve_bench model threads utts frames percall|server|batcher [max_frames depth linger_us]\n");
+    std::fprintf(stderr, "usage: serve_bench model threads utts frames percall|server|batcher|live|liveserver|... [max_frames depth linger_us [c]]\n");
     return 2;
   }
   const char *path = argv[1];
@@ -49,6 +170,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "load: %s\n", fdnn_last_error());
     return 1;
   }
+  if (mode == "live" || mode == "liveserver") return run_live(m, mode, T, U, F, max_frames, depth, linger, argc > 9 ? std::atoi(argv[9]) : 10);
   const int D = fdnn_model_input_dim(m), O = fdnn_model_output_dim(m);
   fdnn_server *srv = nullptr;
   const bool lazy = mode == "lazy" || mode == "lazyserver";
