@@ -20,6 +20,10 @@ Fixtures
                    sha256 of every layer's u8 activations / accumulators, full
                    soft-max rows for 4 frames, saturation-event count
   sat.npz          small net driven into pmaddubsw saturation (features x50)
+
+The families of nets and inputs the GPU suite has grown since (switched nets, nets at the loader's limits, the ledger's
+named nets, hostile rows, other widths, lazy edge rows, the FMA flavour at every width, cut-offs 2 and 4) and the wider
+quantizer cases are recorded by tests/golden/make_family_golden.py -> tests/golden/families/*.npz, quantizer_wide.npz.
 """
 import hashlib
 import os

@@ -13,6 +13,7 @@ import pytest
 from fast_dnn_amd import api, formats as F
 from dispatch_ledger import chain_tile, launched
 from oracle.oracle import Oracle
+from ref_families import hostile_block
 
 pytestmark = pytest.mark.gpu
 TIGHT = 2e-6
@@ -480,17 +481,7 @@ def test_int8_screening_with_hostile_rows(net_model_path):
     rng = np.random.default_rng(5)
     n = 1280
     x = F.synth_features(n, 432, seed=31)
-    x[0:64, 7] = 1.0e6                                   # one dominant element
-    x[64:96] = 0.0                                        # empty rows
-    x[96:128] = (rng.standard_normal((32, 432)) * 1e-41).astype(np.float32)   # denormal inputs
-    x[128:160] *= np.float32(1e-12)
-    x[160:192] *= np.float32(1e12)
-    x[192, 3] = np.inf
-    x[193, 5] = -np.inf
-    x[194, 11] = np.nan
-    x[195] = np.float32(3.0e38)
-    x[200:264, :216] = -x[200:264, 216:]                  # (shift/scale sit between this and the layer, so only near-cancelling)
-    x[264:296] = np.round(x[264:296] * 4) / 4             # many exact ties in the products
+    hostile_block(x, rng, unit=32)   # (tests/ref_families.py: the same rows, 4 per kind, are recorded from the reference itself)
     dnn = api.QuantizedDnn.loadFromFile(net_model_path)
     dnn.setInputLayerKernel(4)
     got, recomputed = dnn.layer0(x)

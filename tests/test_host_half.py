@@ -43,6 +43,33 @@ def test_quantizer_edge_cases_match_reference():
         assert mult == ref or (np.isinf(mult) and np.isinf(ref)), name
 
 
+@pytest.mark.parametrize("name", [str(n) for n in golden("quantizer_wide.npz")["names"]])
+def test_quantizer_wide_cases_match_reference(name):
+    """The library's own quantizer against the reference's bytes (tests/golden/make_family_golden.py), not through the oracle:
+    cut-offs 0.5 .. inf, ties at k + 0.5, NaN / inf / 3e38 / denormal / -0 weights, all-denormal and constant layers, 20 columns."""
+    g = golden("quantizer_wide.npz")
+    wq, mult = api.host_quantize(g[f"{name}_w"], float(g[f"{name}_cut"]))
+    assert (wq == g[f"{name}_wq"]).all(), name
+    assert np.array_equal(np.float32(mult), g[f"{name}_mult"], equal_nan=True), (name, mult, float(g[f"{name}_mult"]))
+
+
+@pytest.mark.parametrize("name", ["cut2", "cut4"])
+def test_host_model_at_other_cutoffs_matches_reference(tmp_models, name):
+    """HostModel(path, cutoff) at the cut-offs tools/accuracy_report.py uses beside 3: int8 weights and multiplier of every int8
+    layer are what the reference recorded (tests/golden/families/cut2.npz, cut4.npz)."""
+    import ref_families as RF
+
+    fam = RF.FAMILIES[name]
+    g = golden(fam.fixture)
+    path = RF.model(fam, tmp_models)
+    assert F.sha256_file(path) == str(g["model_sha256"])
+    hm = api.HostModel(path, fam.cutoff)
+    assert [np.float32(hm.multiplier(j)) for j in range(1, hm.n_layers)] == list(g["mult"])
+    assert [RF.sha(hm.weights_q(j)) for j in range(1, hm.n_layers)] == list(g["wq_sha256"])
+    base = golden(RF.FAMILIES["plain"].fixture)   # and they are not the cut-off-3 ones
+    assert (g["mult"] != base["mult"]).all() and (g["wq_sha256"] != base["wq_sha256"]).all()
+
+
 def test_host_model_matches_golden_and_oracle(tiny_model_path):
     g = golden("tiny.npz")
     hm = api.HostModel(tiny_model_path)
