@@ -82,23 +82,16 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
   // the half-step sigmoid table: once per launch (the ring's epilogue tile never reaches it)
 #pragma unroll
   for (int piece = 0; piece < 3; ++piece)
-    if (piece % NW == wave) {
-      const int bytes = (kLut2Size + 15) & ~15;
-      const __amdgpu_buffer_rsrc_t rsrc_lut = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(kp->lut2), 0, bytes, 0x00020000);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_lut, FDNN_LDS_PTR(aux + piece * 1024), 16, lane * 16, piece * 1024, 0, 0);
-    }
+    if (piece % NW == wave) aux_table_piece(aux, kp->lut2, (kLut2Size + 15) & ~15, piece, lane);
 
-  static_assert(NW % 2 == 0 || NW == 1, "slab parity per wave needs an even wave count (or one wave)");
-  const int srow = lane / Cfg::LPR;
-  const int schunk = ((lane % Cfg::LPR) ^ swz<BK>(wave * Cfg::RPI + srow)) << 4;
-  const int voff_w = srow * kp->ldw + schunk;
-  const int voff_a = srow * kp->lda + schunk;
-  constexpr int NLD_W = Cfg::W_SLABS / NW, NLD_A = (Cfg::A_SLABS + NW - 1) / NW, NLD = NLD_W + NLD_A;
+  const int voff_w = stage_voff<Cfg>(lane, wave, kp->ldw);
+  const int voff_a = stage_voff<Cfg>(lane, wave, kp->lda);
+  constexpr int NLD_W = Cfg::NLD_W, NLD_A = Cfg::NLD_A, NLD = Cfg::NLD;
   constexpr bool ROT = STAGES == 2 && BK / 32 >= 4;
   constexpr int SUB = BK / 32;
   constexpr int ROT_D0 = (NLD + 1) / 2;
   constexpr int A_D0 = (NLD_A + 1) / 2;
-  constexpr int kTS = G_BM + 16;
+  constexpr int kTS = Cfg::TS;
   const int frow = lane & 31, fch = lane >> 5, half = lane >> 5;
   const int arow0 = wn * 32 * NF;
 
@@ -180,28 +173,28 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
     CH_TS(0);
     // ================================================================ phase A: set-up, early loads, the wait
     v16i acc[2][NF];
-    __amdgpu_buffer_rsrc_t rsrc_w, rsrc_a;
+    StageSrc src;  // (activation rows: sc0 sc1 loads -- they were written by other workgroups of this launch; weights: default policy)
     FixCursor fx = {0, 0, INT_MAX, nullptr, 0, 0};
     int fix_node0 = 0;
-    int ldw_s, lda_s, KT;
+    int KT;
     {
       const Dec d = decode(kp, task);
       const int m0 = d.mt * G_BM, f0 = d.nt * FT;
       typedef const __attribute__((address_space(4))) QChainLayer *LP;
       const LP L = reinterpret_cast<LP>(&kp->layer[0]) + d.l;
-      ldw_s = kp->ldw;
-      lda_s = kp->lda;
+      const int ldw_s = kp->ldw, lda_s = kp->lda;
       KT = kp->K / BK;
       const int8_t *a_in = kp->act[d.l & 1];
-      rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(L->w + static_cast<size_t>(m0) * ldw_s), 0, G_BM * ldw_s, 0x00020000);
-      rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(a_in + static_cast<size_t>(f0) * lda_s), 0, FT * lda_s, 0x00020000);
+      src = StageSrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(L->w + static_cast<size_t>(m0) * ldw_s), 0, G_BM * ldw_s, 0x00020000),
+                     __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(a_in + static_cast<size_t>(f0) * lda_s), 0, FT * lda_s, 0x00020000),
+                     voff_w, voff_a, ldw_s, lda_s};
       // 128 * sum_k w (the s8 = u8 - 128 offset): the accumulators' start values
       const int32_t *wsum = L->wsum;
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const int4 ws4 = *reinterpret_cast<const int4 *>(wsum + m0 + 64 * wm + 32 * a + 8 * g + 4 * (lane >> 5));
+          const int4 ws4 = acc_start(wsum, m0, wm, lane >> 5, a, g);
 #pragma unroll
           for (int b = 0; b < NF; ++b) {
             acc[a][b][g * 4 + 0] = ws4.x;
@@ -211,30 +204,13 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
           }
         }
       // this tile's biases: they do not depend on the layer before
-      if (wave == 3 % NW) {
-        const __amdgpu_buffer_rsrc_t rsrc_bias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(L->bias + m0), 0, G_BM * 4, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_bias, FDNN_LDS_PTR(aux + 3072), 16, lane * 16, 0, 0, 0);
-      }
+      if (wave == 3 % NW) aux_words(aux + 3072, L->bias + m0, G_BM, lane);
       // pmaddubsw pair saturation (dnn.cc:337-340): the entry walk of fdnn_pair.hpp
       fx.ent = fix_entries(L->fix_ent);
       fix_node0 = m0 + 64 * wm;
       if (!NOFIX && fx.ent) fx = fix_open(fx, L->fix_grp, (m0 >> 6) + wm);
     }
-    // activation rows: sc0 sc1 (aux 17) -- they were written by other workgroups of this launch; weights: default policy
-    auto stage_load = [&](int kt, int buf, int i) {
-      char *base = smem + buf * Cfg::STAGE;
-      const int koff = kt * BK;
-      const int odd = (NW == 1 && BK == 128) ? 64 : 0;
-      if (i < NLD_W) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, FDNN_LDS_PTR(base + (i * NW + wave) * 1024), 16, (i & 1) ? voff_w ^ odd : voff_w,
-                                                 (i * NW + wave) * Cfg::RPI * ldw_s + koff, 0, 0);
-      } else {
-        const int s = i - NLD_W;
-        if (Cfg::A_SLABS % NW == 0 || s * NW + wave < Cfg::A_SLABS)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, FDNN_LDS_PTR(base + Cfg::W_BYTES + (s * NW + wave) * 1024), 16,
-                                                   (s & 1) ? voff_a ^ odd : voff_a, (s * NW + wave) * Cfg::RPI * lda_s + koff, 0, FDNN_CHAIN_A_AUX);
-      }
-    };
+    auto stage_load = [&](int kt, int buf, int i) { fdnn::stage_load<Cfg, FDNN_CHAIN_A_AUX>(smem, src, wave, kt, buf, i); };
     if (FDNN_CHAIN_EARLY_W) {  // the weight halves of the first stages (ROT: both buffers) depend on nobody: before the wait
 #pragma unroll
       for (int s = 0; s < (ROT ? 2 : STAGES - 1); ++s)
@@ -286,7 +262,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
 
     asm volatile(".p2align 8");
     v4i a[2][2], b[2][NF];
-    auto load_frags = [&](const char *wt_, const char *at_, int kk, int set) {
+    auto load_frags = [&](const char *wt_, const char *at_, int kk, int set) {  // (fdnn_gemm.hip's reads: DESIGN.md section 3)
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi) a[set][mi] = read_frag<BK>(wt_, 64 * wm + 32 * mi + frow, kk * 2 + fch);
 #pragma unroll
@@ -324,6 +300,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
       if (nb >= STAGES) nb -= STAGES;
       const char *wt = smem + buf * Cfg::STAGE;
       const char *at = wt + Cfg::W_BYTES;
+      // (the walk's body is fdnn_gemm.hip's, line for line: DESIGN.md section 3 on why each kernel writes it out)
       while (!NOFIX && fx.k_next < (kt + 1) * BK) {  // rare: a risky pair lives in this k-step (screen, then the exact correction)
         const PairEntry en = decode_entry(fx.raw);
         const int kl = en.k - kt * BK;  // even, 0..BK-2
@@ -443,17 +420,12 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
             for (int qq = 0; qq < 4; ++qq) {
               const int av = acc[mi][ni][g * 4 + qq];
               const float lin = dequant<true>(av, coef, rcp_coef) + bj[qq];
-              const int u = static_cast<int>(lin * 200.0f);  // RN(lin*200) = 2*RN(lin*100) exactly; trunc -> half-step index
-              const int idx = max(-kLut2Half, min(kLut2Half, u)) + kLut2Half;
-              act[ni][qq] = lut[idx];
+              act[ni][qq] = lut[lut2_index(lin)];  // fdnn_act.hpp
             }
           }
 #pragma unroll
-          for (int ni = 0; ni < NF; ++ni) {
-            const uint32_t packed = static_cast<uint32_t>(act[ni][0]) | static_cast<uint32_t>(act[ni][1]) << 8 |
-                                    static_cast<uint32_t>(act[ni][2]) << 16 | static_cast<uint32_t>(act[ni][3]) << 24;
-            *reinterpret_cast<uint32_t *>(tile_s + (arow0 + 32 * ni + frow) * kTS + nbl) = packed;
-          }
+          for (int ni = 0; ni < NF; ++ni)
+            *reinterpret_cast<uint32_t *>(tile_s + (arow0 + 32 * ni + frow) * kTS + nbl) = pack4(act[ni][0], act[ni][1], act[ni][2], act[ni][3]);
         }
       }
       __syncthreads();
@@ -461,7 +433,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qchain_kernel(QChainParams p)
       int8_t *a_out = kp->act[(d.l & 1) ^ 1];
       const size_t lda = static_cast<size_t>(kp->lda);
       const int rows = kp->rows;
-      for (int item = tid; item < FT * (G_BM / 16); item += Cfg::THREADS) {
+      for (int item = tid; item < FT * (G_BM / 16); item += Cfg::THREADS) {  // (fdnn_gemm.hip's row store: DESIGN.md section 3)
         const int row = item / (G_BM / 16), ch = item % (G_BM / 16);
         const uint4 v = *reinterpret_cast<const uint4 *>(tile_s + row * kTS + ch * 16);
         if (m0 + ch * 16 < rows)  // rows is a multiple of 16

@@ -7,6 +7,7 @@
 
 #include <climits>
 
+#include "fdnn_act.hpp"  // the epilogue arithmetic: dequant, lut_index, lut2_index, pack4, logit_exp
 #include "fdnn_model.hpp"
 
 namespace fdnn {
@@ -30,7 +31,6 @@ __device__ __forceinline__ void glds16(const void *g, void *lds_wave_base) {
 #ifndef FDNN_WT
 #define FDNN_WT 35  // 1 hidden-layer activations, 2 output-layer exp(z), 32 soft-max scale; 4 / 8 / 16 = layer-0 park, activations, image: no effect measured
 #endif
-typedef float v2f_t __attribute__((ext_vector_type(2)));
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 // The s_nop is part of the store: a vector-memory store of more than 8 bytes reads its data registers a cycle after
 // issue, and a vector-ALU write to them in the very next slot corrupts what is stored.  For a store it emits itself the
@@ -48,36 +48,6 @@ __device__ __forceinline__ void store_wt(void *p, v2f_t v) {
 }
 __device__ __forceinline__ void store_wt(void *p, uint32_t v) {
   asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-}
-
-// float(sum) / (multiplier * 255)   -- dnn.cc:298-299, :311.  The fast form is
-// the Markstein sequence q = x*y, r = fma(-q, c, x), q' = fma(r, y, q) with
-// y = RN(1/c); it is enabled per layer only after launch_fastdiv_check has
-// compared it with IEEE division for every accumulator the layer can produce:
-// the closed range +-(cols_pad / 2) * 32768, each adjacent pair being saturated
-// to int16 (2^26 at K = 4096, 2^29 at the widest layer the loader accepts).
-template <bool FAST>
-__device__ __forceinline__ float dequant(int acc, float coef, float rcp) {
-  const float x = static_cast<float>(acc);  // v_cvt_f32_i32, RNE like cvtsi2ss
-  if (FAST) {
-    const float q = x * rcp;
-    const float r = fmaf(-q, coef, x);
-    return fmaf(r, rcp, q);
-  }
-  return x / coef;
-}
-
-// QuantizedSigmoid::get -- dnn.h:36-43: k = (int)round(x*100), table index
-// clamp(k,-640,640)+640 into the extended table.  round() is half away from
-// zero; the x86 build turns NaN / |t| >= 2^31 into INT_MIN (-> entry 0).
-__device__ __forceinline__ int lut_index(float lin) {
-  const float t = lin * 100.0f;
-  const float r0 = truncf(t);
-  // t - r0 is exact; select, do not branch (the epilogue runs this 32*NF times per lane)
-  const float r = r0 + ((fabsf(t - r0) >= 0.5f) ? copysignf(1.0f, t) : 0.0f);
-  int k = (fabsf(t) < 2147483648.0f) ? static_cast<int>(r) : INT_MIN;
-  k = max(-kLutHalf, min(kLutHalf, k));
-  return k + kLutHalf;
 }
 
 }  // namespace fdnn

@@ -26,6 +26,7 @@
 
 #include <climits>
 
+#include "fdnn_act.hpp"  // kLog2e
 #include "fdnn_float.hpp"
 #include "fdnn_launch.hpp"
 
@@ -42,8 +43,6 @@ constexpr int kTileFloats = kFrameTile * kLdsStride;      // one operand tile (k
 constexpr int kEStride = 65;                              // output epilogue: a wave's e [64 frames][64 nodes], rows 65 apart
 static_assert(kFrameTile == 128 && kNodeTile == 128 && kKStep == 32, "fgemm_kernel is written for 128 x 128 x 32");
 static_assert(4 * 64 * kEStride <= 4 * kTileFloats, "the output epilogue's e tiles reuse the operand buffers");
-
-constexpr float kLog2e = 1.44269504088896340736f;
 
 template <int ACT, bool TAP>
 __global__ __launch_bounds__(256) void fgemm_kernel(GemmParams p) {

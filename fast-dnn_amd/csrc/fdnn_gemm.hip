@@ -162,6 +162,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
   // one wave issues NLD 1-KB loads per stage: weight slabs wave, wave+NW, ... then activation
   // slabs wave, wave+NW, ...
   constexpr int NLD_W = Cfg::W_SLABS / NW, NLD = NLD_W + (Cfg::A_SLABS + NW - 1) / NW;
+  // (restates fdnn_tile.hpp's stage_voff / stage_load, which fdnn_chain.hip calls: through the helper the two one-wave
+  // instances come out with another instruction stream -- DESIGN.md section 3)
   auto stage_load = [&](int kt, int buf, int i) {
     char *base = smem + buf * Cfg::STAGE;
     const int koff = kt * BK;
@@ -189,22 +191,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
   // four 1-KiB pieces (three of table, one of biases) over however many waves there are
 #pragma unroll
   for (int piece = 0; piece < 3; ++piece)
-  if (!OUTPUT && piece % NW == wave) {
-    // The range of a 16-byte LDS-DMA access is checked as a whole: with num_records = the table
-    // size, the lane holding the table's last three (FAST) / last one (exact) entries read zeros --
-    // u8 128 instead of 255 for every activation with lin >= 6.395 (found by
-    // test_net_with_every_pair_saturating; rare on trained nets, never on the round-1 fixtures).
-    // The blob pads both tables to 16 bytes (fdnn_model.cpp: place(size + 15)).
-    const int bytes = ((FAST ? kLut2Size : kLutExt) + 15) & ~15;
-    const __amdgpu_buffer_rsrc_t rsrc_lut =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(FAST ? p.lut2 : p.lut), 0, bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_lut, FDNN_LDS_PTR(aux + piece * 1024), 16, lane * 16, piece * 1024, 0, 0);
-  }
-  if (wave == 3 % NW) {
-    const __amdgpu_buffer_rsrc_t rsrc_bias =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.bias + m0), 0, G_BM * 4, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_bias, FDNN_LDS_PTR(aux + 3072), 16, lane * 16, 0, 0, 0);
-  }
+    if (!OUTPUT && piece % NW == wave) aux_table_piece(aux, FAST ? p.lut2 : p.lut, ((FAST ? kLut2Size : kLutExt) + 15) & ~15, piece, lane);
+  if (wave == 3 % NW) aux_words(aux + 3072, p.bias + m0, G_BM, lane);
 #pragma unroll
   for (int s = 0; s < STAGES - 1; ++s)
     if (s < KT) stage(s, s);
@@ -218,7 +206,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const int4 ws4 = *reinterpret_cast<const int4 *>(p.wsum + m0 + 64 * wm + 32 * a + 8 * g + 4 * (lane >> 5));
+      const int4 ws4 = acc_start(p.wsum, m0, wm, lane >> 5, a, g);
 #pragma unroll
       for (int b = 0; b < NF; ++b) {
         acc[a][b][g * 4 + 0] = ws4.x;
@@ -256,6 +244,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
   constexpr int SUB = BK / 32;
   constexpr int ROT_D0 = (NLD + 1) / 2;  // loads issued right after the barrier; the rest before the next sub-step 0
   v4i a[2][2], b[2][NF];  // MFMA operand fragments, double buffered over the sub-steps
+  // (the same reads as fdnn_chain.hip's and fdnn_pp.hip's load_frags: DESIGN.md section 3 on why each kernel writes them out)
   auto load_frags = [&](const char *wt_, const char *at_, int kt_, int kk, int set) {
 #if !(FDNN_GEMM_DEBUG & 4)
     (void)kt_;
@@ -313,6 +302,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
     const long long tf0 = __builtin_readcyclecounter();
     const int fe0 = fx.e;
 #endif
+    // (the walk's body is fdnn_chain.hip's, line for line: DESIGN.md section 3 on why each kernel writes it out)
     while (!NOFIX && fx.k_next < (kt + 1) * BK) {  // rare: a risky pair lives in this k-step
       const PairEntry en = decode_entry(fx.raw);
       const int kl = en.k - kt * BK;  // even, 0..BK-2
@@ -434,7 +424,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
   const uint8_t *lut = reinterpret_cast<const uint8_t *>(aux);
   const float *bias_s = reinterpret_cast<const float *>(aux + 3072);
   char *tile_s = smem + 8192;  // hidden layers: s8 output tile [FT][kTS]
-  constexpr int kTS = G_BM + 16;  // row stride: 16-byte aligned, rows 16 apart share a bank (2-way at worst)
+  constexpr int kTS = Cfg::TS;
   __syncthreads();  // every wave is done with the ring: it becomes the output tile
   FDNN_TS(4);
   // D layout (32x32): column (frame) = lane&31, row (node) = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
@@ -529,9 +519,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
           const v4f_t b4 = *reinterpret_cast<const v4f_t *>(bias_s + (nb - m0));
           const float bj[4] = {b4.x, b4.y, b4.z, b4.w};
           const bool in4 = nb < p.rows;
-          typedef float v2f_e __attribute__((ext_vector_type(2)));
+          typedef v2f_t v2f_e;
           const v2f_e rcp2 = {p.rcp_coef, p.rcp_coef}, coef2 = {p.coef, p.coef};
-          const v2f_e log2e2 = {1.44269504088896340736f, 1.44269504088896340736f};
           float e[4];
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2) {  // the operations of the unfused dense instance, one for one
@@ -544,9 +533,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
               if (((nib >> (2 * h2)) & 1u) == 0) z.x = 0.0f;
               if (((nib >> (2 * h2 + 1)) & 1u) == 0) z.y = 0.0f;
             }
-            const v2f_e y = z * log2e2;
             const v2f_e keep = ANYW ? v2f_e{nb + 2 * h2 < p.rows ? 1.0f : 0.0f, nb + 2 * h2 + 1 < p.rows ? 1.0f : 0.0f} : v2f_e{in4 ? 1.0f : 0.0f, in4 ? 1.0f : 0.0f};
-            const v2f_e ex = v2f_e{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)} * keep;
+            const v2f_e ex = logit_exp(z) * keep;  // fdnn_act.hpp: the multiply by log2 e packed
             e[2 * h2] = ex.x;
             e[2 * h2 + 1] = ex.y;
           }
@@ -892,9 +880,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
               // x * y, two fma of the exact division, + bias, * log2 e, v_exp_f32), written on pairs so that the five
               // multiplies / fmas / adds go out as packed instructions -- left to itself the compiler packs the hidden
               // layers' epilogue but not this one (965 -> 485 vector instructions per lane and tile).
-              typedef float v2f_e __attribute__((ext_vector_type(2)));
+              typedef v2f_t v2f_e;
               const v2f_e rcp2 = {p.rcp_coef, p.rcp_coef}, coef2 = {p.coef, p.coef};
-              const v2f_e log2e2 = {1.44269504088896340736f, 1.44269504088896340736f};
 #pragma unroll
               for (int h2 = 0; h2 < 2; ++h2) {
                 const v2f_e x = {static_cast<float>(acc[mi][ni][g * 4 + 2 * h2]), static_cast<float>(acc[mi][ni][g * 4 + 2 * h2 + 1])};
@@ -905,14 +892,14 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
                   if (((mbits >> (16 * h2)) & 0xffu) == 0) z.x = 0.0f;
                   if (((mbits >> (16 * h2 + 8)) & 0xffu) == 0) z.y = 0.0f;
                 }
-                const v2f_e y = z * log2e2;
+                const v2f_e y = logit_log2(z);  // fdnn_act.hpp: logit_exp's multiply by log2 e, packed
                 if (ANYW || (FDNN_GEMM_DEBUG & 256)) {
-                  e[2 * h2] = nb + 2 * h2 < p.rows ? __builtin_amdgcn_exp2f(y.x) : 0.0f;
-                  e[2 * h2 + 1] = nb + 2 * h2 + 1 < p.rows ? __builtin_amdgcn_exp2f(y.y) : 0.0f;
+                  e[2 * h2] = nb + 2 * h2 < p.rows ? exp2_hw(y.x) : 0.0f;
+                  e[2 * h2 + 1] = nb + 2 * h2 + 1 < p.rows ? exp2_hw(y.y) : 0.0f;
                 } else {
                   // nodes past the layer's width (zero weights, zero bias: z = 0, e = 1) must not reach the row sum: one
                   // packed multiply by 0 / 1 per pair instead of a select per element
-                  const v2f_e ev = v2f_e{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)} * v2f_e{in4 ? 1.0f : 0.0f, in4 ? 1.0f : 0.0f};
+                  const v2f_e ev = exp2_hw(y) * v2f_e{in4 ? 1.0f : 0.0f, in4 ? 1.0f : 0.0f};
                   e[2 * h2] = ev.x;
                   e[2 * h2 + 1] = ev.y;
                 }
@@ -927,7 +914,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
               float z = dequant<FAST>(av, p.coef, p.rcp_coef) + bj[q];  // sum/coef, then += bias (dnn.cc:311, :446)
               if ((MASKED || !PLAIN) && ((mbits >> (8 * q)) & 0xffu) == 0) z = 0.0f;
               if (!PLAIN && TAP && live && nb + q < p.rows) p.tap_logit[static_cast<size_t>(f) * p.rows + nb + q] = z;
-              e[q] = ((PLAIN && !ANYW) ? in4 : (nb + q < p.rows)) ? __expf(z) : 0.0f;
+              e[q] = ((PLAIN && !ANYW) ? in4 : (nb + q < p.rows)) ? logit_exp(z) : 0.0f;
               psum[ni] += e[q];
             }
             *reinterpret_cast<float4 *>(wtile + frow * kOS + (nb - ncol0)) = make_float4(e[0], e[1], e[2], e[3]);
@@ -989,14 +976,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
           const int av = acc[mi][ni][g * 4 + q];
           if (TAP && f < p.n && nb + q < p.rows) p.tap_acc[static_cast<size_t>(f) * p.rows + nb + q] = av;
           const float lin = dequant<FAST>(av, p.coef, p.rcp_coef) + bj[q];
-          int idx;
-          if (FAST) {
-            // RN(lin*200) = 2*RN(lin*100) exactly; trunc -> half-step index (see fdnn_model.cpp)
-            const int u = static_cast<int>(lin * 200.0f);
-            idx = max(-kLut2Half, min(kLut2Half, u)) + kLut2Half;
-          } else {
-            idx = lut_index(lin);
-          }
+          const int idx = FAST ? lut2_index(lin) : lut_index(lin);  // fdnn_act.hpp
 #if FDNN_GEMM_DEBUG & 8
           act[ni][q] = static_cast<uint8_t>(idx);
 #else
@@ -1010,14 +990,12 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void qgemm_kernel(QGemmParams p) {
       // address-processing bound.
 #pragma unroll
       for (int ni = 0; ni < NF; ++ni) {
-        const uint32_t packed = static_cast<uint32_t>(act[ni][0]) | static_cast<uint32_t>(act[ni][1]) << 8 |
-                                static_cast<uint32_t>(act[ni][2]) << 16 | static_cast<uint32_t>(act[ni][3]) << 24;
-        *reinterpret_cast<uint32_t *>(tile_s + (arow0 + 32 * ni + frow) * kTS + (nb - m0)) = packed;
+        *reinterpret_cast<uint32_t *>(tile_s + (arow0 + 32 * ni + frow) * kTS + (nb - m0)) = pack4(act[ni][0], act[ni][1], act[ni][2], act[ni][3]);
       }
     }
   }
   if (!OUTPUT) {
-    // the s8 activation tile: FT rows x 256 bytes, written as 16 bytes per lane
+    // the s8 activation tile: FT rows x 256 bytes, written as 16 bytes per lane (fdnn_chain.hip's row store: DESIGN.md section 3)
     __syncthreads();
     for (int item = tid; item < FT * (G_BM / 16); item += Cfg::THREADS) {
       const int row = item / (G_BM / 16), ch = item % (G_BM / 16);

@@ -480,7 +480,7 @@ __global__ __launch_bounds__(256 * WN, 3 - WN) void l0_split_kernel(L0Params p, 
       // QuantizedSigmoid::get through the half-step table (fdnn_model.cpp): index trunc(2 t), clamped; the entry carries the
       // table byte and, in its upper half, a gate: 0.25f where the byte on the other side of the nearest half-integer is
       // the same, else 0
-      const int u = max(-kLut2Half, min(kLut2Half, static_cast<int>(tt[s][r] + tt[s][r])));  // (v_cvt_i32_f32 truncates, saturates, NaN -> 0)
+      const int u = lut2_clamp(static_cast<int>(tt[s][r] + tt[s][r]));  // (v_cvt_i32_f32 truncates, saturates, NaN -> 0)
       ent[s][r] = *reinterpret_cast<const uint32_t *>(half_b + 4 * u);
     }
   }
@@ -610,7 +610,7 @@ void l0_split_build_weights(const float *w, const float *wnorm, const uint8_t *l
   // upper half the float bits of the gate -- 0.25f where the entry on the other side of the nearest half-integer
   // (|u| ^ 1 with the sign of u; both neighbours for u = 0) holds the same byte, else 0.
   half->assign(l0_split_half_bytes() / 4, 0);
-  auto at = [&](int u) { return lut2[std::max(-kLut2Half, std::min(kLut2Half, u)) + kLut2Half]; };
+  auto at = [&](int u) { return lut2[lut2_clamp(u) + kLut2Half]; };
   for (int u = -kLut2Half; u <= kLut2Half; ++u) {
     const int mag = u < 0 ? -u : u;
     bool same;

@@ -113,8 +113,7 @@ __global__ __launch_bounds__(kLsThreads) void lists_score_kernel(ListsParams p) 
       if (ok) {
         acc = part + p.wsum[node];  // 128 * sum_k w[node][k]: the s8 = u8 - 128 activation offset
         const float z = dequant<FAST>(acc, p.coef, p.rcp_coef) + p.bias[node];
-        const float y = z * 1.44269504088896340736f;
-        e = __builtin_amdgcn_exp2f(y);
+        e = logit_exp(z);
       }
       p.probs[i] = e;
       if (p.acc != nullptr) p.acc[i] = acc;  // parity tests only (fdnn_debug_ctx_lists_acc): the same for every lane

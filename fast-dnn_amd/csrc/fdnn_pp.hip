@@ -213,6 +213,8 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
         const int T = gt0 + kt;
         if (cvalid) {
           const char *at = ringA[T & 1];
+          // (the corrections and the register select are fdnn_gemm.hip's, line for line; the screen reads row 0 for a dead lane.
+          // DESIGN.md section 3 on why each kernel writes the walk's body out)
           while (!NOFIX && fx.k_next < (kt + 1) * kBK) {  // rare: a risky pair lives in this k-step (fdnn_pair.hpp's walk)
             const PairEntry en = decode_entry(fx.raw);
             const int kl = en.k - kt * kBK;
@@ -348,8 +350,7 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
           for (int qq = 0; qq < 4; ++qq) {
             const int av = acc[mi][ni][g * 4 + qq];
             const float lin = dequant<true>(av, p.coef, p.rcp_coef) + bj[qq];
-            const int u = static_cast<int>(lin * 200.0f);  // RN(lin * 200) = 2 RN(lin * 100) exactly; trunc -> half-step index
-            idx[it - it0][qq] = max(-kLut2Half, min(kLut2Half, u)) + kLut2Half;
+            idx[it - it0][qq] = lut2_index(lin);  // fdnn_act.hpp
           }
         }
 #pragma unroll
@@ -367,8 +368,7 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
 #pragma unroll
         for (int it = it0; it < it1; ++it) {
           const int ni = it >> 3, mi = (it >> 2) & 1, g = it & 3;
-          const uint32_t packed = gb[it - it0][0] | gb[it - it0][1] << 8 | gb[it - it0][2] << 16 | gb[it - it0][3] << 24;
-          *reinterpret_cast<uint32_t *>(tile_s[ni & 1] + tile_w + 32 * mi + 8 * g) = packed;
+          *reinterpret_cast<uint32_t *>(tile_s[ni & 1] + tile_w + 32 * mi + 8 * g) = pack4(gb[it - it0][0], gb[it - it0][1], gb[it - it0][2], gb[it - it0][3]);
         }
 #else
         (void)it0;
@@ -397,10 +397,7 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
           }
           // last tick (my epilogue has read its last biases): my next half's accumulator start values and biases (1 KiB each, one wave each)
           if (kt == kKT - 1 && nvalid) {
-            if (wm == 0) {
-              const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(p.wsum + n_mt * kBM), 0, kBM * 4, 0x00020000);
-              __builtin_amdgcn_raw_ptr_buffer_load_lds(r, FDNN_LDS_PTR(wsum_s), 16, ln * 16, 0, 0, 0);
-            }
+            if (wm == 0) aux_words(wsum_s, p.wsum + n_mt * kBM, kBM, ln);
             bias_v = p.bias[n_mt * kBM + 64 * wm + ln];  // (parked in bias_s at the start of my compute phase, behind the wait I make there anyway)
           }
 #endif
@@ -474,12 +471,11 @@ __global__ __launch_bounds__(512, 2) void qpp_kernel(QGemmParams p) {
         for (int g = 0; g < 4; ++g) {
           const v4f_t b4 = *reinterpret_cast<const v4f_t *>(bias_l + 32 * mi + 8 * g);
           const float bj[4] = {b4.x, b4.y, b4.z, b4.w};
-          uint32_t packed = 0;
+          uint32_t packed = 0;  // (pack4's bytes, gathered into the word one by one)
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) {
             const float lin = dequant<true>(acc[mi][ni][g * 4 + qq], p.coef, p.rcp_coef) + bj[qq];
-            const int u = static_cast<int>(lin * 200.0f);
-            packed |= static_cast<uint32_t>(lut_s[max(-kLut2Half, min(kLut2Half, u)) + kLut2Half]) << (8 * qq);
+            packed |= static_cast<uint32_t>(lut_s[lut2_index(lin)]) << (8 * qq);
           }
           *reinterpret_cast<uint32_t *>(mine + frow * kTS + 32 * mi + 8 * g + 4 * half) = packed;
         }

@@ -214,6 +214,7 @@ namespace {
 // Four elements (one lane's four consecutive nodes of one frame): SoftMax::apply's first loop in fdnn_gemm.hip's FUSED
 // operations, one for one: x = float(acc); q0 = x rcp; r = fma(-q0, coef, x); z = fma(r, rcp, q0) + bias; e = exp2(z log2e) keep;
 // the lane's running sum takes them in order.  (Four chains side by side: a transcendental's result is not read by the next instruction.)
+// This restates fdnn_act.hpp's dequant<true> and logit_exp (0x3fb8aa3b is kLog2e) on hand-fixed registers: a change there is a change here.
 #define PPO_EXP4(R0, R1, R2, R3)                                                                                                     \
   asm volatile("v_accvgpr_read_b32 %[a0], a" #R0 "\n\tv_accvgpr_read_b32 %[a1], a" #R1 "\n\tv_accvgpr_read_b32 %[a2], a" #R2 "\n\tv_accvgpr_read_b32 %[a3], a" #R3 "\n\t" \
                "v_cvt_f32_i32 %[a0], %[a0]\n\tv_cvt_f32_i32 %[a1], %[a1]\n\tv_cvt_f32_i32 %[a2], %[a2]\n\tv_cvt_f32_i32 %[a3], %[a3]\n\t" \

@@ -8,7 +8,7 @@
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
 #include "fdnn_launch.hpp"
-#include "fdnn_pair.hpp"
+#include "fdnn_tile.hpp"  // row256_pos; brings fdnn_pair.hpp
 
 namespace fdnn {
 namespace {
@@ -50,9 +50,6 @@ struct SetView {
   int32_t *acc;
   int m0, t_begin, t_end;
 };
-
-// chunk c (16 bytes) of row r of a 256-byte-row LDS image lives at chunk position c ^ (r & 15) (as fdnn_small.hip)
-[[maybe_unused]] __device__ __forceinline__ int st_pos(int row, int chunk) { return (row << 8) + (((chunk ^ row) & 15) << 4); }
 
 // Where a tile's results go.  The tile hands every (row, entry) of the view it has scored to entry(): o = row * len + entry,
 // both counted inside the view, (f, jl) the same pair inside the 32 x 64 tile, `cur` the activation buffer the tile has just
@@ -150,7 +147,7 @@ __device__ __forceinline__ void set_tile(const SetParams &p, const SetView &v, c
   v4i wf[2][8];
   auto read_w = [&](int half, const char *src) {
 #pragma unroll
-    for (int s = 0; s < 8; ++s) wf[half][s] = *reinterpret_cast<const v4i *>(src + st_pos(frow, 2 * s + fch));
+    for (int s = 0; s < 8; ++s) wf[half][s] = *reinterpret_cast<const v4i *>(src + row256_pos(frow, 2 * s + fch));
   };
 
   // ---- prologue: W half 0 through the (not yet needed) second activation buffer into registers, the first activation
@@ -184,7 +181,7 @@ __device__ __forceinline__ void set_tile(const SetParams &p, const SetView &v, c
       v4i b[8];
       auto read_b = [&]() {
 #pragma unroll
-        for (int s = 0; s < 8; ++s) b[s] = *reinterpret_cast<const v4i *>(at + st_pos(frow, 2 * s + fch));
+        for (int s = 0; s < 8; ++s) b[s] = *reinterpret_cast<const v4i *>(at + row256_pos(frow, 2 * s + fch));
       };
       if (t == t_begin) {
         // in flight are this tile (8 loads) and W half 1 (8 loads, younger)
@@ -251,8 +248,7 @@ __device__ __forceinline__ void set_tile(const SetParams &p, const SetView &v, c
               }
             }
             const float z = dequant<FAST>(a32, p.coef, p.rcp_coef) + bias4[i];
-            const float y = z * 1.44269504088896340736f;
-            e = __builtin_amdgcn_exp2f(y);
+            e = logit_exp(z);
           }
           st.entry(v, o + i, f, 32 * h + 4 * q + i, cur, e, a32);
         }

@@ -31,7 +31,7 @@
 
 #include "fdnn_device.hpp"
 #include "fdnn_kernels.hpp"
-#include "fdnn_pair.hpp"
+#include "fdnn_tile.hpp"  // row256_pos, the table / bias LDS-DMA; brings fdnn_pair.hpp
 
 #include <algorithm>
 #include <cstdlib>
@@ -50,10 +50,6 @@ constexpr int kSmAuxOff = 2 * kSmABuf;             // table (3 KiB) | biases (25
 constexpr int kSmEOff = kSmAuxOff + 3584;
 constexpr int kSmLds = kSmEOff + 8192 + 64;
 static_assert(kSmLds <= 160 * 1024, "LDS");
-
-// chunk c (16 bytes) of row r of a 256-byte-row LDS image lives at chunk position c ^ (r & 15): the 16 lanes of a
-// ds_read_b128 group read 16 different rows at the same k and land on 16 different 16-byte slots
-[[maybe_unused]] __device__ __forceinline__ int sm_pos(int row, int chunk) { return (row << 8) + (((chunk ^ row) & 15) << 4); }
 
 // NTM: 32-node MFMA tiles per workgroup (1: hidden layers, 2: output layer).
 template <int NTM, bool OUTPUT, bool TAP, bool MASKED>
@@ -105,17 +101,11 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
   }
   // NB the sigmoid table's last 16-byte piece must be inside num_records as a whole (fdnn_gemm.hip)
   char *aux = smem + kSmAuxOff;
-  if (!OUTPUT && wave < 3) {
-    const int bytes = (kLut2Size + 15) & ~15;
-    const __amdgpu_buffer_rsrc_t rsrc_lut = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.lut2), 0, bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_lut, FDNN_LDS_PTR(aux + wave * 1024), 16, lane * 16, wave * 1024, 0, 0);
-  }
+  if (!OUTPUT && wave < 3) aux_table_piece(aux, p.lut2, (kLut2Size + 15) & ~15, wave, lane);
   if (wave == 3 && lane < NT / 4) {
-    const __amdgpu_buffer_rsrc_t rsrc_bias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.bias + m0), 0, NT * 4, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_bias, FDNN_LDS_PTR(smem + kSmBiasOff), 16, lane * 16, 0, 0, 0);
+    aux_words(smem + kSmBiasOff, p.bias + m0, NT, lane);
     // 128 * sum_k w[node][k] (the s8 = u8 - 128 activation offset) is added where the partial tiles meet
-    const __amdgpu_buffer_rsrc_t rsrc_wsum = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(p.wsum + m0), 0, NT * 4, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_wsum, FDNN_LDS_PTR(smem + kSmWsumOff), 16, lane * 16, 0, 0, 0);
+    aux_words(smem + kSmWsumOff, p.wsum + m0, NT, lane);
   }
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<int8_t *>(p.w + static_cast<size_t>(m0) * p.ldw), 0, NT * p.ldw, 0x00020000);
@@ -142,7 +132,7 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
   v4i wf[NTM][8];
   auto read_w = [&](int half, const char *src) {
 #pragma unroll
-    for (int s = 0; s < 8; ++s) wf[half][s] = *reinterpret_cast<const v4i *>(src + sm_pos(frow, 2 * s + fch));
+    for (int s = 0; s < 8; ++s) wf[half][s] = *reinterpret_cast<const v4i *>(src + row256_pos(frow, 2 * s + fch));
   };
 
   SM_TS(1);
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
       v4i b[8];
       auto read_b = [&]() {
 #pragma unroll
-        for (int s = 0; s < 8; ++s) b[s] = *reinterpret_cast<const v4i *>(at + sm_pos(frow, 2 * s + fch));
+        for (int s = 0; s < 8; ++s) b[s] = *reinterpret_cast<const v4i *>(at + row256_pos(frow, 2 * s + fch));
       };
       if (NTM == 2 && t == t_begin) {
         // first pass of the 64-node shape: in flight are this tile (8 loads) and W half 1 (8 loads, younger)
@@ -248,7 +238,7 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
         const int node = en.node - m0;
         if (node < 0 || node >= NT) return;  // NTM == 1: the other half of the 64-node group
         const int kl = en.k - k0;  // even, 0..254
-        const uint32_t pair = *reinterpret_cast<const uint16_t *>(at + sm_pos(frow, kl >> 4) + (kl & 15));
+        const uint32_t pair = *reinterpret_cast<const uint16_t *>(at + row256_pos(frow, kl >> 4) + (kl & 15));
         const AccSlot slot = acc_slot(node);
         const int c = fch == slot.half ? pair_excess(pair, en.w0, en.w1) : 0;
         if (__ballot(c != 0) != 0ull) {
@@ -304,14 +294,12 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
       const int sv[4] = {sum.x, sum.y, sum.z, sum.w};
       if (!OUTPUT) {
         // AddBias + QuantizedSigmoid (half-step table; the layer passed the exact-division and range checks at load)
-        uint32_t packed = 0;
+        uint32_t packed = 0;  // (pack4's bytes, gathered into the word one by one)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           if (TAP && ff < p.n && nb + i < p.rows) p.tap_acc[static_cast<size_t>(ff) * p.rows + nb + i] = sv[i];
           const float lin = dequant<true>(sv[i], p.coef, p.rcp_coef) + bj[i];
-          const int u = static_cast<int>(lin * 200.0f);
-          const int idx = max(-kLut2Half, min(kLut2Half, u)) + kLut2Half;
-          packed |= static_cast<uint32_t>(lut[idx]) << (8 * i);
+          packed |= static_cast<uint32_t>(lut[lut2_index(lin)]) << (8 * i);
         }
         if (nb < p.rows)  // rows is a multiple of 16
           *reinterpret_cast<uint32_t *>(p.act_out + static_cast<size_t>(ff) * p.act_ld + nb) = packed;
@@ -331,14 +319,11 @@ __global__ __launch_bounds__(kSmThreads, 2) void qgemm_small_kernel(QGemmParams 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           if (TAP && ff < p.n && nb + i < p.rows) p.tap_acc[static_cast<size_t>(ff) * p.rows + nb + i] = sv[i];
-          const float x = static_cast<float>(sv[i]);
-          const float q0 = x * p.rcp_coef;
-          const float r = fmaf(-q0, p.coef, x);
-          float z = fmaf(r, p.rcp_coef, q0) + bj[i];
+          float z = dequant<true>(sv[i], p.coef, p.rcp_coef) + bj[i];
           if (MASKED && ((mbits >> (8 * i)) & 0xffu) == 0) z = 0.0f;
           if (TAP && ff < p.n && nb + i < p.rows) p.tap_logit[static_cast<size_t>(ff) * p.rows + nb + i] = z;
-          const float y = z * 1.44269504088896340736f;
-          e4[i] = nb + i < p.rows ? __builtin_amdgcn_exp2f(y) : 0.0f;
+          const float ez = logit_exp(z);
+          e4[i] = nb + i < p.rows ? ez : 0.0f;
         }
         if (ff < p.n) {
           float *op = p.out + static_cast<size_t>(ff) * p.rows + nb;
