@@ -174,6 +174,26 @@ SIGNATURES = {
     "fdnn_debug_set_pool_kernel": (C.c_int, [C.c_int]),
     "fdnn_debug_pool_ref": (C.c_int, [_c_f32p, C.c_int, _c_i32p, C.c_int, C.c_int, _c_f32p]),
     "fdnn_debug_pool_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fdnn_loglik_create": (C.c_void_p, [_c_f32p, C.c_int, C.c_float, C.c_int]),
+    "fdnn_loglik_free": (None, [C.c_void_p]),
+    "fdnn_loglik_width": (C.c_int, [C.c_void_p]),
+    "fdnn_loglik_type": (C.c_int, [C.c_void_p]),
+    "fdnn_loglik_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fdnn_loglik_entries_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "fdnn_ctx_output_loglik": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_ctx_output_loglik_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_loglik": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_loglik_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_loglik_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_server_submit_loglik": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "fdnn_server_submit_raw_loglik": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "fdnn_server_live_push_loglik": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_uint64)]),
+    "fdnn_debug_loglik_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_set_loglik_kernel": (C.c_int, [C.c_int]),
+    "fdnn_debug_loglik_ref": (C.c_int, [_c_f32p, C.c_int, _c_f32p, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "fdnn_debug_loglik_entries_ref": (C.c_int, [_c_i32p, _c_f32p, C.c_longlong, _c_f32p, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "fdnn_debug_ln_ref": (C.c_int, [_c_f32p, C.c_longlong, _c_f32p]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_debug_scratch_count": (C.c_int, []),
@@ -631,6 +651,121 @@ def _pool_out(n: int, classes: int, out):
     return out
 
 
+# The output types of a score handle (include/fdnn.h: FDNN_LOGLIK_F32, FDNN_LOGLIK_F16)
+LOGLIK_F32 = 0
+LOGLIK_F16 = 1
+_LOGLIK_DTYPE = {LOGLIK_F32: np.float32, LOGLIK_F16: np.float16}
+
+
+def _loglik_args_bad(lp, floor, type) -> bool:
+    """What fdnn_loglik_create refuses as an argument (fdnn_loglik.hpp: check_handle), for the error code of a NULL handle."""
+    f = np.float32(floor)
+    return bool(lp.size < 1 or lp.size > (1 << 19) or type not in _LOGLIK_DTYPE or not np.isfinite(lp).all() or np.isnan(f) or f == np.inf
+                or (type == LOGLIK_F16 and np.isfinite(f) and f < np.float32(-65504.0)))
+
+
+class Loglik:
+    """A decoder-score handle registered once (``fdnn_loglik_create``): ``log_prior`` float32 [width], all finite; ``floor``
+    (-inf: none) and the output ``type`` (``LOGLIK_F32`` or ``LOGLIK_F16``).  The score of a row p is ln(p_i) - log_prior[i],
+    floored, by the ONE logarithm of include/fdnn.h (``ln_ref``); F16 results are ``numpy.float16``.  Note that the k best
+    probabilities are not the k best scores.  Immutable; threads, contexts and scoring loops may share it; it must outlive
+    every call and ticket that uses it."""
+
+    def __init__(self, log_prior, floor: float = -np.inf, type: int = LOGLIK_F32):
+        lp = np.ascontiguousarray(log_prior, dtype=np.float32)
+        if lp.ndim != 1:
+            raise ValueError("log_prior must be a vector [width]")
+        self.handle = lib().fdnn_loglik_create(lp.ctypes.data_as(_c_f32p), lp.size, C.c_float(float(floor)), int(type))
+        if not self.handle:
+            raise FdnnError(FDNN_E_ARG if _loglik_args_bad(lp, floor, int(type)) else FDNN_E_DEVICE, lib().fdnn_last_error().decode(errors="replace"))
+        self.log_prior, self.floor = lp.copy(), float(floor)
+        self.dtype = _LOGLIK_DTYPE[int(type)]
+
+    def width(self) -> int:
+        return int(lib().fdnn_loglik_width(self.handle))
+
+    def type(self) -> int:
+        return int(lib().fdnn_loglik_type(self.handle))
+
+    def rows_device(self, d_rows: int, n: int, d_out: int, stream: int = 0) -> None:
+        """The scores alone (``fdnn_loglik_rows_device``) of device-resident fp32 rows [n][width] -> d_out [n][width] of the
+        handle's type; raw device pointers, enqueued on ``stream``, not synchronised."""
+        _check(lib().fdnn_loglik_rows_device(self.handle, C.c_void_p(d_rows), int(n), C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def entries_device(self, d_nodes: int, d_p: int, count: int, d_out: int, stream: int = 0) -> None:
+        """The scores of a flat list of (node, probability) entries (``fdnn_loglik_entries_device``) -> d_out [count]; a node
+        outside [0, width) gives a NaN."""
+        _check(lib().fdnn_loglik_entries_device(self.handle, C.c_void_p(d_nodes), C.c_void_p(d_p), int(count), C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def delete(self) -> None:
+        if self.handle:
+            lib().fdnn_loglik_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.delete()
+        except Exception:
+            pass
+
+
+def ln_ref(x):
+    """The contract's logarithm (``fdnn_debug_ln_ref``, fdnn_loglik.hpp: ln) of float32 values of any shape, any bit patterns."""
+    v = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(v)
+    _check(lib().fdnn_debug_ln_ref(v.ctypes.data_as(_c_f32p), v.size, out.ctypes.data_as(_c_f32p)))
+    return out
+
+
+def loglik_ref(rows, log_prior, floor: float = -np.inf, type: int = LOGLIK_F32):
+    """The scores from the host restatement (``fdnn_debug_loglik_ref``; host code, no device) of rows [n][width] float32 (any
+    bit patterns) -> [n][width] float32 or float16."""
+    r = np.ascontiguousarray(rows, dtype=np.float32)
+    lp = np.ascontiguousarray(log_prior, dtype=np.float32)
+    if r.ndim != 2 or lp.ndim != 1 or lp.size != r.shape[1]:
+        raise ValueError("rows must be [n][width] and log_prior [width]")
+    out = np.empty(r.shape, dtype=_LOGLIK_DTYPE.get(int(type), np.float32))
+    _check(lib().fdnn_debug_loglik_ref(r.ctypes.data_as(_c_f32p), r.shape[0], lp.ctypes.data_as(_c_f32p), lp.size, C.c_float(float(floor)), int(type),
+                                       C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def loglik_entries_ref(nodes, p, log_prior, floor: float = -np.inf, type: int = LOGLIK_F32):
+    """The same for a flat list of (node, probability) entries (``fdnn_debug_loglik_entries_ref``) -> [count]."""
+    nd = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+    v = np.ascontiguousarray(p, dtype=np.float32).ravel()
+    lp = np.ascontiguousarray(log_prior, dtype=np.float32)
+    if nd.size != v.size or lp.ndim != 1:
+        raise ValueError("nodes and p must have one length, log_prior must be [width]")
+    out = np.empty(nd.size, dtype=_LOGLIK_DTYPE.get(int(type), np.float32))
+    _check(lib().fdnn_debug_loglik_entries_ref(nd.ctypes.data_as(_c_i32p), v.ctypes.data_as(_c_f32p), nd.size, lp.ctypes.data_as(_c_f32p), lp.size,
+                                               C.c_float(float(floor)), int(type), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def loglik_launches():
+    """Process-wide counts since load: launches of (the rows kernel's vector form, its scalar-access form, the entries kernel)."""
+    buf = (C.c_ulonglong * 3)()
+    if lib().fdnn_debug_loglik_launches(buf, 3) != 3:
+        raise RuntimeError("fdnn_debug_loglik_launches")
+    return tuple(int(v) for v in buf)
+
+
+def set_loglik_kernel(mode: int) -> None:
+    """Process-wide (``fdnn_debug_set_loglik_kernel``): 0 the plan's rule, 1 vector where allowed, 2 always scalar access."""
+    _check(lib().fdnn_debug_set_loglik_kernel(int(mode)))
+
+
+def _loglik_out(n: int, ll: "Loglik", out):
+    """The [n][width] result array of a loglik call, made or checked."""
+    shape = (n, ll.width())
+    if out is None:
+        return np.empty(shape, dtype=ll.dtype)
+    if out.dtype != ll.dtype or out.shape != shape or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous {np.dtype(ll.dtype).name} array of shape {shape}")
+    return out
+
+
 def _topk_out(n: int, k: int, nodes, probs):
     """The [n][k] result arrays of a top-k call, made or checked."""
     if nodes is None:
@@ -836,6 +971,18 @@ class LazyContext:
         out = _pool_out(self.inputVectorCount, pool.classes(), None)
         _check(lib().fdnn_ctx_output_pool(self.handle, pool.handle, out.ctypes.data_as(_c_f32p)))
         return out
+
+    def calculateOutputLoglik(self, ll: "Loglik") -> np.ndarray:
+        """The dense output layer over the context's frames as decoder scores under ``ll`` (``fdnn_ctx_output_loglik``) ->
+        float32 or float16 [frames][outputDimension]."""
+        out = _loglik_out(self.inputVectorCount, ll, None)
+        _check(lib().fdnn_ctx_output_loglik(self.handle, ll.handle, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def calculateOutputLoglikDevice(self, ll: "Loglik", d_out: int, stream: int = 0) -> None:
+        """The same into a device buffer [frames][outputDimension] of the handle's type, enqueued on ``stream``, not
+        synchronised (``fdnn_ctx_output_loglik_device``)."""
+        _check(lib().fdnn_ctx_output_loglik_device(self.handle, ll.handle, C.c_void_p(d_out), C.c_void_p(stream)))
 
     def calculateOutputPoolDevice(self, pool: "ClassPool", d_out: int, stream: int = 0) -> None:
         """The same into a device buffer [frames][classes], enqueued on ``stream``, not synchronised (``fdnn_ctx_output_pool_device``)."""
@@ -1164,6 +1311,32 @@ class ScoringServer:
         self._keep[int(t.value)] = (frames, pool, out)
         return int(t.value), out
 
+    def submitLoglik(self, x, ll: "Loglik", out=None):
+        """One utterance's decoder scores through the loop (``fdnn_server_submit_loglik``): coalesced with the other callers'
+        submissions under the SAME handle, the dense rows stay on the device -> (ticket, out float32 or float16
+        [n][outputDimension]), valid after ``wait(ticket)``; the bytes of ``QuantizedDnn.calculateLoglik``."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.dnn.inputDimension():
+            raise ValueError(f"Input vector size {x.shape[-1]} must be equal with network input size {self.dnn.inputDimension()}")
+        return self._submit_loglik(lib().fdnn_server_submit_loglik, x, ll, out)
+
+    def submitRawLoglik(self, raw, ll: "Loglik", out=None):
+        """The same for raw feature frames [n][rawDim] of one utterance, spliced on the device by the model's splice spec at
+        submit time (``fdnn_server_submit_raw_loglik``); the bytes of ``QuantizedDnn.calculateLoglikRaw``."""
+        r = np.ascontiguousarray(raw, dtype=np.float32)
+        spec = self.dnn.spliceSpec()
+        if spec is not None and (r.ndim != 2 or r.shape[1] != spec[1]):
+            raise ValueError(f"raw frames must be [n][{spec[1]}], got {r.shape}")
+        return self._submit_loglik(lib().fdnn_server_submit_raw_loglik, r, ll, out)
+
+    def _submit_loglik(self, fn, frames, ll, out):
+        n = frames.shape[0]
+        out = _loglik_out(n, ll, out)
+        t = C.c_uint64()
+        _check(fn(self.handle, frames.ctypes.data_as(_c_f32p), n, ll.handle, C.c_void_p(out.ctypes.data), C.byref(t)))
+        self._keep[int(t.value)] = (frames, ll, out)
+        return int(t.value), out
+
     def _submit_topk(self, fn, frames, k, nodes, probs):
         n = frames.shape[0]
         nodes, probs = _topk_out(n, k, nodes, probs)
@@ -1272,6 +1445,15 @@ class LiveStream:
         n, t = C.c_int(0), C.c_uint64(0)
         _check(lib().fdnn_server_live_push_pool(self.handle, r.ctypes.data_as(_c_f32p), r.shape[0], int(bool(end)), pool.handle,
                                                 out.ctypes.data_as(_c_f32p), C.byref(n), C.byref(t)))
+        return self._done(n, t, (out,))
+
+    def pushLoglik(self, raw, ll: "Loglik", end: bool = False):
+        """-> (ticket or None, decoder scores float32 or float16 [rows][outputDimension]): the bytes of ``calculateLoglikRaw``."""
+        r = self._raw(raw)
+        out = np.empty((r.shape[0] + self.right, ll.width()), dtype=ll.dtype)
+        n, t = C.c_int(0), C.c_uint64(0)
+        _check(lib().fdnn_server_live_push_loglik(self.handle, r.ctypes.data_as(_c_f32p), r.shape[0], int(bool(end)), ll.handle,
+                                                  C.c_void_p(out.ctypes.data), C.byref(n), C.byref(t)))
         return self._done(n, t, (out,))
 
     def pushSet(self, raw, nodes, end: bool = False):
@@ -1536,6 +1718,35 @@ class QuantizedDnn:
         """Device-resident form (``fdnn_calculate_pool_device``): d_x [n][inputDimension] -> d_out float32 [n][classes]; raw
         device pointers, enqueued on ``stream``, not synchronised."""
         _check(lib().fdnn_calculate_pool_device(self.nativeDnnHandle, C.c_void_p(d_x), int(n), pool.handle, C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def calculateLoglik(self, input, ll: "Loglik") -> np.ndarray:
+        """Dense scoring returned as decoder scores (``fdnn_calculate_loglik``): of every frame's soft-max row
+        ln(p_i) - log_prior[i], floored, computed on the device by the contract's logarithm (include/fdnn.h) -> float32 or
+        float16 [n][outputDimension]; an F16 handle halves the bytes that come back."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        out = _loglik_out(n, ll, None)
+        _check(lib().fdnn_calculate_loglik(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(), ll.handle,
+                                           C.c_void_p(out.ctypes.data)))
+        return out
+
+    calculate_loglik = calculateLoglik
+
+    def calculateLoglikRaw(self, raw, ll: "Loglik") -> np.ndarray:
+        """``calculateLoglik`` on raw frames [n][rawDim] of one utterance, spliced on the device (``fdnn_calculate_loglik_raw``)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError(f"raw frames must be [n][rawDim], got {r.shape}")
+        out = _loglik_out(r.shape[0], ll, None)
+        _check(lib().fdnn_calculate_loglik_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], ll.handle, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def calculate_loglik_device(self, d_x: int, n: int, ll: "Loglik", d_out: int, stream: int = 0) -> None:
+        """Device-resident form (``fdnn_calculate_loglik_device``): d_x [n][inputDimension] -> d_out [n][outputDimension] of the
+        handle's type; raw device pointers, enqueued on ``stream``, not synchronised."""
+        _check(lib().fdnn_calculate_loglik_device(self.nativeDnnHandle, C.c_void_p(d_x), int(n), ll.handle, C.c_void_p(d_out), C.c_void_p(stream)))
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))

@@ -862,6 +862,164 @@ int fdnn_debug_pool_limits(int *lanes, int *resident_width) {
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- dense output as decoder scores (fdnn_loglik.hip)
+fdnn_loglik *fdnn_loglik_create(const float *log_prior, int width, float floor, int type) {
+  const long long bad = fdnn::loglik::check_handle(log_prior, width, floor, type);
+  if (bad == -1) {
+    fail(FDNN_E_ARG, "a score handle is log_prior [width], 1 <= width <= " + std::to_string(fdnn::loglik::kMaxWidth) + ", of type FDNN_LOGLIK_F32 or FDNN_LOGLIK_F16");
+    return nullptr;
+  }
+  if (bad == -2) {
+    fail(FDNN_E_ARG, "the floor is -inf (none) or finite, and not below -65504 for FDNN_LOGLIK_F16");
+    return nullptr;
+  }
+  if (bad > 0) {
+    fail(FDNN_E_ARG, "log_prior[" + std::to_string(bad - 1) + "] is not finite");
+    return nullptr;
+  }
+  std::unique_ptr<fdnn_loglik> p(new (std::nothrow) fdnn_loglik);
+  if (!p) {
+    fail(FDNN_E_NOMEM, "out of memory");
+    return nullptr;
+  }
+  p->width = width, p->type = type, p->floor = floor;
+  p->log_prior.assign(log_prior, log_prior + width);
+  hipError_t e = hipGetDevice(&p->device);
+  if (e == hipSuccess) e = p->d_log_prior.reserve(size_t(width));
+  if (e == hipSuccess) e = hipMemcpy(p->d_log_prior.p, log_prior, sizeof(float) * size_t(width), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    fail(e == hipErrorOutOfMemory ? FDNN_E_NOMEM : FDNN_E_DEVICE, std::string("fdnn_loglik_create: ") + hipGetErrorString(e));
+    return nullptr;
+  }
+  return p.release();
+}
+
+void fdnn_loglik_free(fdnn_loglik *ll) {
+  if (!ll) return;
+  DeviceGuard g(ll->device);  // (the priors are freed on the device they live on)
+  delete ll;
+}
+
+int fdnn_loglik_width(const fdnn_loglik *ll) { return ll ? ll->width : fail(FDNN_E_ARG, "null score handle"); }
+int fdnn_loglik_type(const fdnn_loglik *ll) { return ll ? ll->type : fail(FDNN_E_ARG, "null score handle"); }
+
+int fdnn_loglik_rows_device(const fdnn_loglik *ll, const float *d_rows, int n, void *d_out, void *stream) {
+  if (!ll || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;
+  if (!d_rows || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  if ((reinterpret_cast<uintptr_t>(d_rows) & 3) || (reinterpret_cast<uintptr_t>(d_out) & (fdnn::loglik::elem_bytes(ll->type) - 1)))
+    return fail(FDNN_E_ARG, "buffers must have their elements' alignment");
+  DeviceGuard g(ll->device);
+  fdnn::launch_loglik_rows(d_rows, n, ll->width, ll->d_log_prior, ll->floor, ll->type, d_out, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+int fdnn_loglik_entries_device(const fdnn_loglik *ll, const int32_t *d_nodes, const float *d_p, long long count, void *d_out, void *stream) {
+  if (!ll || count < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (count == 0) return FDNN_OK;
+  if (!d_nodes || !d_p || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  if (((reinterpret_cast<uintptr_t>(d_nodes) | reinterpret_cast<uintptr_t>(d_p)) & 3) || (reinterpret_cast<uintptr_t>(d_out) & (fdnn::loglik::elem_bytes(ll->type) - 1)))
+    return fail(FDNN_E_ARG, "buffers must have their elements' alignment");
+  DeviceGuard g(ll->device);
+  fdnn::launch_loglik_entries(d_nodes, d_p, count, ll->width, ll->d_log_prior, ll->floor, ll->type, d_out, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+int fdnn_ctx_output_loglik_device(fdnn_ctx *c, const fdnn_loglik *ll, void *d_out, void *stream) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (int rc = fdnn::check_loglik(c->m, ll)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (c->n == 0) return FDNN_OK;
+  if (!d_out) return fail(FDNN_E_ARG, "null buffer");
+  DeviceGuard g(c->m->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  if (!c->d_out) HIP_TRY(c->d_out.reserve(size_t(c->cap) * size_t(c->m->hm.hdr.out_dim)));  // (a lean context)
+  if (int rc = run_output(c, {.count = c->n, .d_out = c->d_out}, s)) return rc;
+  fdnn::launch_loglik_rows(c->d_out, c->n, c->m->hm.hdr.out_dim, ll->d_log_prior, ll->floor, ll->type, d_out, s);
+  return FDNN_OK;
+}
+
+int fdnn_ctx_output_loglik(fdnn_ctx *c, const fdnn_loglik *ll, void *out) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  if (int rc = fdnn::check_loglik(c->m, ll)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (c->n == 0) return FDNN_OK;
+  if (!out) return fail(FDNN_E_ARG, "null buffer");
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, c->stream));
+  if (!c->d_out) HIP_TRY(c->d_out.reserve(size_t(c->cap) * size_t(c->m->hm.hdr.out_dim)));  // (a lean context)
+  return dense_pass(c, {.loglik = ll, .scores = out}, c->stream, /*hidden=*/false);
+}
+
+int fdnn_calculate_loglik(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, void *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = fdnn::check_loglik(m, ll)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  return score_chunks(m, frame_chunks(n, m), Pass::host_loglik("fdnn_calculate_loglik", x, ll, fdnn::loglik::elem_bytes(ll->type), out));
+}
+
+int fdnn_calculate_loglik_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, void *out) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  if (int rc = fdnn::splice_check(spec, raw_dim)) return rc;
+  if (int rc = fdnn::check_loglik(m, ll)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!raw || !out) return fail(FDNN_E_ARG, "null buffer");
+  const std::vector<SpliceSeg> segs{SpliceSeg{0, 0, 0, n - 1}};  // (the whole utterance's raw frames travel once, as fdnn_calculate_raw's)
+  return score_chunks(m, frame_chunks(n, m), Pass::raw_loglik("fdnn_calculate_loglik_raw", {spec.get(), &segs, raw, n}, ll, fdnn::loglik::elem_bytes(ll->type), out));
+}
+
+int fdnn_calculate_loglik_device(fdnn_model *m, const float *d_x, int n, const fdnn_loglik *ll, void *d_out, void *stream) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (int rc = fdnn::check_loglik(m, ll)) return rc;
+  if (n == 0) return FDNN_OK;
+  if (!d_x || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_frames_aligned(d_x)) return rc;
+  return score_chunks(m, frame_chunks(n, m), Pass::device_loglik("fdnn_calculate_loglik_device", d_x, ll, fdnn::loglik::elem_bytes(ll->type), d_out), static_cast<hipStream_t>(stream));
+}
+
+int fdnn_debug_loglik_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 3, fdnn::loglik_launch_counts); }
+
+int fdnn_debug_set_loglik_kernel(int mode) {
+  if (mode < 0 || mode > 2) return fail(FDNN_E_ARG, "mode is 0 (the plan's rule), 1 (vector where allowed) or 2 (scalar access)");
+  fdnn::loglik_kernel_mode(mode);
+  return FDNN_OK;
+}
+
+// The scores in plain C++ (fdnn_loglik.hpp: check_handle, ref, ref_entries, ln), no device
+int fdnn_debug_loglik_ref(const float *rows, int n, const float *log_prior, int width, float floor, int type, void *out) {
+  if (n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (fdnn::loglik::check_handle(log_prior, width, floor, type) != 0) return fail(FDNN_E_ARG, "log_prior [width] finite, the floor -inf or finite (F16: not below -65504), the type F32 or F16");
+  if (n == 0) return FDNN_OK;
+  if (!rows || !out) return fail(FDNN_E_ARG, "null buffer");
+  fdnn::loglik::ref(reinterpret_cast<const uint32_t *>(rows), n, width, log_prior, floor, type, out);
+  return FDNN_OK;
+}
+
+int fdnn_debug_loglik_entries_ref(const int32_t *nodes, const float *p, long long count, const float *log_prior, int width, float floor, int type, void *out) {
+  if (count < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (fdnn::loglik::check_handle(log_prior, width, floor, type) != 0) return fail(FDNN_E_ARG, "log_prior [width] finite, the floor -inf or finite (F16: not below -65504), the type F32 or F16");
+  if (count == 0) return FDNN_OK;
+  if (!nodes || !p || !out) return fail(FDNN_E_ARG, "null buffer");
+  fdnn::loglik::ref_entries(nodes, reinterpret_cast<const uint32_t *>(p), size_t(count), width, log_prior, floor, type, out);
+  return FDNN_OK;
+}
+
+int fdnn_debug_ln_ref(const float *x, long long count, float *out) {
+  if (count < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (count == 0) return FDNN_OK;
+  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
+  for (long long i = 0; i < count; ++i) out[i] = fdnn::loglik::ln(x[i]);
+  return FDNN_OK;
+}
+
 int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
   if (!c || !out) return fail(FDNN_E_ARG, "null argument");
   if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");

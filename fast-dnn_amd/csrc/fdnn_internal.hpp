@@ -94,6 +94,15 @@ struct fdnn_pool {
   const int32_t *d_member() const { return d_csr.p + n_classes + 1; }
 };
 
+// A decoder-score handle (fdnn_loglik.hpp): the log priors on the host and on the device that was current at
+// fdnn_loglik_create, the floor and the output type.  Immutable from then on: threads, contexts and scoring loops share it.
+struct fdnn_loglik {
+  int width = 0, type = 0, device = 0;
+  float floor = 0.0f;
+  std::vector<float> log_prior;
+  fdnn::DevBuf<float> d_log_prior;  // [width]
+};
+
 struct fdnn_ctx {
   fdnn_model *m = nullptr;
   int n = 0;              // frames in use
@@ -138,6 +147,7 @@ struct fdnn_ctx {
   fdnn::DevBuf<float> d_comp;       // host lazy batches: compacted result rows (allocated on first use)
   fdnn::DevBuf<int32_t> d_topk;     // host top-k calls: [n][k] nodes, then [n][k] values (allocated on first use, fdnn_topk.hip)
   fdnn::DevBuf<float> d_pool;       // host pool calls: [n][C] class sums (allocated on first use, fdnn_pool.hip; not in ctx_layout)
+  fdnn::DevBuf<uint32_t> d_loglik;  // host loglik calls: [n][O] scores, fp32 or fp16 (allocated on first use, fdnn_loglik.hip; not in ctx_layout)
   // host list calls (fdnn_ctx_lazy_output_lists, fdnn_calculate_lazy_lists): staging of the lists and their results,
   // allocated on the first list call and grown by the largest one
   fdnn::DevBuf<int32_t> d_lrow, d_lnodes;   // [count + 1], [nnz]
@@ -294,7 +304,8 @@ int copy_out(void *dst, const void *d_src, size_t bytes, hipStream_t s);
 int dense_pass_to_host(fdnn_ctx *c, float *out, hipStream_t s);
 // The same pass with "what leaves the device" as the step that differs: the whole rows into out (k = 0), or the k
 // first-ranked nodes of every row and their values into nodes / probs [n][k] (fdnn_topk.hip), or the rows' class sums under
-// `pool` into pooled [n][C] (fdnn_pool.hip) -- the rows stay in c->d_out.
+// `pool` into pooled [n][C] (fdnn_pool.hip), or the rows as decoder scores under `loglik` into scores [n][O] of the handle's
+// type (fdnn_loglik.hip) -- the rows stay in c->d_out.
 // hidden = false: the context holds the hidden activations already (fdnn_ctx_output_topk); the fused soft-max's re-run
 // applies, the chained launch's belongs to whoever ran the hidden layers.
 struct DenseTo {
@@ -304,6 +315,8 @@ struct DenseTo {
   float *probs = nullptr;
   const fdnn_pool *pool = nullptr;
   float *pooled = nullptr;
+  const fdnn_loglik *loglik = nullptr;
+  void *scores = nullptr;
 };
 int dense_pass(fdnn_ctx *c, const DenseTo &to, hipStream_t s, bool hidden);
 // Lazy results of `count` frames (c->d_out) to a host caller, compacted over PCIe where that pays; d_bits / bits: the
@@ -327,6 +340,9 @@ int check_frames_aligned(const float *d_x);
 // A pool call's handle against the model it is used with: the map's width is the model's output_dim, the CSR lives on the
 // model's device, and the model leads no device group.  FDNN_E_ARG before anything is launched.
 int check_pool(const fdnn_model *m, const fdnn_pool *pool);
+// The same for a decoder-score handle: its width is the model's output_dim, its priors live on the model's device, and the
+// model leads no device group.  FDNN_E_ARG before anything is launched.
+int check_loglik(const fdnn_model *m, const fdnn_loglik *ll);
 // The second half of a call through a model's batcher: `submitted` is what the submit call returned, *ticket what it filled in.
 inline int batcher_wait(fdnn_server *b, int submitted, const uint64_t *ticket) { return submitted ? submitted : fdnn_server_wait(b, *ticket); }
 // fdnn_calculate on the model's own device (the group path calls this per shard).

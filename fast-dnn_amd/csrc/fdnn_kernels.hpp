@@ -13,6 +13,7 @@
 #include "fdnn_sets.hpp"
 #include "fdnn_topk.hpp"
 #include "fdnn_pool.hpp"
+#include "fdnn_loglik.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -271,6 +272,17 @@ void launch_pool(const float *d_rows, int n, int width, const int32_t *d_class_p
 void pool_launch_counts(unsigned long long out[2]);  // launches so far: resident form, streaming form
 int pool_kernel_mode();                              // fdnn_debug_set_pool_kernel: 0 the plan's rule, 1 resident where the width allows, 2 streaming
 void pool_kernel_mode(int mode);
+
+// The dense output as decoder scores (fdnn_loglik.hip; the logarithm, the score, the plan and the host restatement:
+// fdnn_loglik.hpp): of every row [width] of d_rows [n] ln(p_i) - d_log_prior[i], floored, into d_out [n][width] of fp32
+// (type loglik::kF32) or fp16 (kF16).  Entries: of (d_nodes[j], d_p[j]) the same with the node's prior into d_out [count]; a
+// node outside [0, width) gives a NaN.  No-ops unless n / count > 0.  The rows' form is the plan's under
+// fdnn_debug_set_loglik_kernel's mode.
+void launch_loglik_rows(const float *d_rows, int n, int width, const float *d_log_prior, float floor, int type, void *d_out, hipStream_t s);
+void launch_loglik_entries(const int32_t *d_nodes, const float *d_p, long long count, int width, const float *d_log_prior, float floor, int type, void *d_out, hipStream_t s);
+void loglik_launch_counts(unsigned long long out[3]);  // launches so far: rows vector form, rows scalar form, entries
+int loglik_kernel_mode();                                // fdnn_debug_set_loglik_kernel: 0 the plan's rule, 1 vector where allowed, 2 scalar
+void loglik_kernel_mode(int mode);
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

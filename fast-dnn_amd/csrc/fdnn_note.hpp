@@ -18,7 +18,8 @@
 // "lists.union.fallback" (its finish launch is the list path's and is counted there).
 // And the two kernels that run BEHIND a dense pass on its finished rows, the top-k selection (fdnn_topk.hip:
 // fdnn_debug_topk_launches) and the class pooling (fdnn_pool.hip: fdnn_debug_pool_launches), each counted by form; as names
-// "topk.resident", "topk.streaming", "pool.resident" and "pool.streaming".
+// "topk.resident", "topk.streaming", "pool.resident" and "pool.streaming".  The decoder scores (fdnn_loglik.hip:
+// fdnn_debug_loglik_launches) likewise: "loglik.rows.vector", "loglik.rows.scalar" and "loglik.entries".
 // And the splice of a scoring-loop batch with a live piece, whose segment table is read from device memory (fdnn_splice.hip,
 // splice_table_kernel): counted by fdnn_debug_live_launches; as a name "splice.table".
 #pragma once

@@ -13,7 +13,8 @@
 #include "fdnn_sets.hpp"   // sets::Tables, sets::Seg, sets::slice
 #include "fdnn_splice_spec.hpp"
 
-struct fdnn_pool;  // (fdnn_internal.hpp: a node -> class map's handle; only its address travels here)
+struct fdnn_pool;    // (fdnn_internal.hpp: a node -> class map's handle; only its address travels here)
+struct fdnn_loglik;  // (fdnn_internal.hpp: a decoder-score handle; likewise)
 
 namespace fdnn::pass {
 
@@ -101,7 +102,9 @@ struct Sink {
     host_sets,         // per-segment sets (tables covering [0, n), all nodes) -> probs (ragged blocks), inactive [n]
     device_sets,       // the same with nodes, probs and inactive on the device (the scoring loop's)
     host_pool,         // every row's class sums under a node -> class map, [n][C], through dense_pass
-    device_pool        // the same into a device buffer; the rows stay in the context
+    device_pool,       // the same into a device buffer; the rows stay in the context
+    host_loglik,       // every row as decoder scores under a score handle, [n][O] fp32 or fp16, through dense_pass
+    device_loglik      // the same into a device buffer; the rows stay in the context
   } kind = device_rows;
   float *rows = nullptr;
   int k = 0;
@@ -114,11 +117,14 @@ struct Sink {
   const fdnn_pool *pool = nullptr;  // host_pool, device_pool: the map's handle, its class count C ...
   int pool_classes = 0;
   float *pooled = nullptr;          // ... and the class sums [n][C]
+  const fdnn_loglik *loglik = nullptr;  // host_loglik, device_loglik: the score handle, the bytes of one score ...
+  size_t score_bytes = 0;
+  void *scores = nullptr;               // ... and the scores [n][O]
 };
 
 // Device sinks are enqueued on the stream the caller names and not synchronised; host sinks run on the context's own stream
 // and return with their results in place.
-inline bool on_callers_stream(Sink::Kind k) { return k == Sink::device_rows || k == Sink::device_topk || k == Sink::device_sets || k == Sink::device_pool; }
+inline bool on_callers_stream(Sink::Kind k) { return k == Sink::device_rows || k == Sink::device_topk || k == Sink::device_sets || k == Sink::device_pool || k == Sink::device_loglik; }
 
 // One supported pairing of the three, built by name only: what the driver cannot serve cannot be written.
 class Pass {
@@ -129,6 +135,7 @@ class Pass {
   static Sink rows_to(Sink::Kind k, float *rows) { Sink s; s.kind = k, s.rows = rows; return s; }
   static Sink topk_to(Sink::Kind k, int n_best, int32_t *nodes, float *probs) { Sink s; s.kind = k, s.k = n_best, s.topk_nodes = nodes, s.topk_probs = probs; return s; }
   static Sink pool_to(Sink::Kind k, const fdnn_pool *pool, int classes, float *pooled) { Sink s; s.kind = k, s.pool = pool, s.pool_classes = classes, s.pooled = pooled; return s; }
+  static Sink loglik_to(Sink::Kind k, const fdnn_loglik *ll, size_t score_bytes, void *scores) { Sink s; s.kind = k, s.loglik = ll, s.score_bytes = score_bytes, s.scores = scores; return s; }
   static Sink entries_to(Sink::Kind k, const int32_t *nodes, float *probs, float *inactive) { Sink s; s.kind = k, s.nodes = nodes, s.probs = probs, s.inactive = inactive; return s; }
   static Sink sets_to(Sink::Kind k, const sets::Tables &t, const int32_t *nodes, float *probs, float *inactive) { Sink s = entries_to(k, nodes, probs, inactive); s.sets = t; return s; }
 
@@ -142,6 +149,7 @@ class Pass {
   static Pass host_bits(const char *who, const float *x, const uint64_t *bits, float *out) { return {who, rows_of(Rows::host, x), mask_of(Mask::host_bits, nullptr, bits), rows_to(Sink::host_behind_bits, out)}; }
   static Pass host_topk(const char *who, const float *x, int k, int32_t *nodes, float *probs) { return {who, rows_of(Rows::host, x), {}, topk_to(Sink::host_topk, k, nodes, probs)}; }
   static Pass host_pool(const char *who, const float *x, const fdnn_pool *pool, int classes, float *pooled) { return {who, rows_of(Rows::host, x), {}, pool_to(Sink::host_pool, pool, classes, pooled)}; }
+  static Pass host_loglik(const char *who, const float *x, const fdnn_loglik *ll, size_t score_bytes, void *scores) { return {who, rows_of(Rows::host, x), {}, loglik_to(Sink::host_loglik, ll, score_bytes, scores)}; }
   static Pass host_lists(const char *who, const float *x, const int32_t *row_ptr, const int32_t *nodes, float *probs, float *inactive) {
     Sink s = entries_to(Sink::host_lists, nodes, probs, inactive);
     s.row_ptr = row_ptr;
@@ -158,11 +166,13 @@ class Pass {
   static Pass raw_bits(const char *who, const Raw &raw, const uint64_t *bits, float *out) { return {who, rows_of(Rows::raw_host, raw), mask_of(Mask::host_bits, nullptr, bits), rows_to(Sink::host_behind_bits, out)}; }
   static Pass raw_topk(const char *who, const Raw &raw, int k, int32_t *nodes, float *probs) { return {who, rows_of(Rows::raw_host, raw), {}, topk_to(Sink::host_topk, k, nodes, probs)}; }
   static Pass raw_pool(const char *who, const Raw &raw, const fdnn_pool *pool, int classes, float *pooled) { return {who, rows_of(Rows::raw_host, raw), {}, pool_to(Sink::host_pool, pool, classes, pooled)}; }
+  static Pass raw_loglik(const char *who, const Raw &raw, const fdnn_loglik *ll, size_t score_bytes, void *scores) { return {who, rows_of(Rows::raw_host, raw), {}, loglik_to(Sink::host_loglik, ll, score_bytes, scores)}; }
   // rows or raw frames on the device
   static Pass device_dense(const char *who, const float *d_x, float *d_out) { return {who, rows_of(Rows::device, d_x), {}, rows_to(Sink::device_rows, d_out)}; }
   static Pass device_bits(const char *who, const float *d_x, const uint64_t *d_bits, float *d_out) { return {who, rows_of(Rows::device, d_x), mask_of(Mask::device_bits, nullptr, d_bits), rows_to(Sink::device_rows, d_out)}; }
   static Pass device_topk(const char *who, const float *d_x, int k, int32_t *d_nodes, float *d_probs) { return {who, rows_of(Rows::device, d_x), {}, topk_to(Sink::device_topk, k, d_nodes, d_probs)}; }
   static Pass device_pool(const char *who, const float *d_x, const fdnn_pool *pool, int classes, float *d_pooled) { return {who, rows_of(Rows::device, d_x), {}, pool_to(Sink::device_pool, pool, classes, d_pooled)}; }
+  static Pass device_loglik(const char *who, const float *d_x, const fdnn_loglik *ll, size_t score_bytes, void *d_scores) { return {who, rows_of(Rows::device, d_x), {}, loglik_to(Sink::device_loglik, ll, score_bytes, d_scores)}; }
   static Pass raw_device_dense(const char *who, const Raw &d_raw, float *d_out) { return {who, rows_of(Rows::raw_device, d_raw), {}, rows_to(Sink::device_rows, d_out)}; }
   // the scoring loop's batches, already on the device: one mask or none (bits win), or the pieces' sets
   static Pass loop_rows(const float *d_x, const int8_t *d_masks, const uint64_t *d_bits, float *d_out) {
@@ -188,6 +198,7 @@ struct ChunkView {
   int32_t *topk_nodes = nullptr;
   float *topk_probs = nullptr;
   float *pooled = nullptr;
+  void *scores = nullptr;
   // lists, set, sets: the chunk's entries as a call of its own
   std::vector<int32_t> row_ptr;  // lists: the chunk's slice rebased to 0 (lists::rebase_rows)
   std::vector<sets::Seg> segs;   // sets: the chunk's slice (sets::slice); its blocks are one contiguous range from probs on
@@ -208,6 +219,7 @@ inline ChunkView chunk_view(const Pass &p, const Dims &d, int off_, int cnt) {
   if (to.rows) v.rows = to.rows + off * d.O;
   if (to.k) v.topk_nodes = to.topk_nodes + off * size_t(to.k), v.topk_probs = to.topk_probs + off * size_t(to.k);
   if (to.pooled) v.pooled = to.pooled + off * size_t(to.pool_classes);
+  if (to.scores) v.scores = static_cast<char *>(to.scores) + off * d.O * to.score_bytes;
   if (to.inactive) v.inactive = to.inactive + off;
   if (to.kind == Sink::host_lists) {  // the chunk's slice of the lists as lists of its own
     lists::rebase_rows(to.row_ptr, off_, cnt, &v.row_ptr);

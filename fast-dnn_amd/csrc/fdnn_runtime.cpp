@@ -805,6 +805,14 @@ static int dense_leave(fdnn_ctx *c, const DenseTo &to, hipStream_t s) {
     HIP_TRY(hipStreamSynchronize(s));
     return FDNN_OK;
   }
+  if (to.loglik) {  // the rows as decoder scores (fdnn_loglik.hip) into the context's own [n][O] buffer, then one transfer
+    const size_t bytes = n * O * fdnn::loglik::elem_bytes(to.loglik->type);
+    HIP_TRY(c->d_loglik.reserve((bytes + 3) / 4));
+    fdnn::launch_loglik_rows(c->d_out, c->n, int(O), to.loglik->d_log_prior, to.loglik->floor, to.loglik->type, c->d_loglik.p, s);
+    HIP_TRY(hipMemcpyAsync(to.scores, c->d_loglik.p, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FDNN_OK;
+  }
   if (to.k == 0) return copy_out(to.out, c->d_out, sizeof(float) * n * O, s);
   const size_t nk = n * size_t(to.k);
   HIP_TRY(c->d_topk.reserve(2 * nk));
@@ -947,6 +955,15 @@ int check_pool(const fdnn_model *m, const fdnn_pool *pool) {
   return FDNN_OK;
 }
 
+int check_loglik(const fdnn_model *m, const fdnn_loglik *ll) {
+  if (!ll) return fail(FDNN_E_ARG, "null score handle");
+  if (m->group) return fail(FDNN_E_ARG, "loglik calls do not run on a model that leads a device group");
+  if (ll->width != m->hm.hdr.out_dim)
+    return fail(FDNN_E_ARG, "score handle width " + std::to_string(ll->width) + " is not the network's output size " + std::to_string(m->hm.hdr.out_dim));
+  if (ll->device != m->device) return fail(FDNN_E_ARG, "the score handle was created on another device than the model's");
+  return FDNN_OK;
+}
+
 int check_frames_aligned(const float *d_x) {
   if ((reinterpret_cast<uintptr_t>(d_x) & 15) == 0) return FDNN_OK;
   return fail(FDNN_E_ARG, "device frames must start on a 16-byte boundary (include/fdnn.h, Device buffers)");
@@ -974,6 +991,12 @@ static int to_device_topk(fdnn_ctx *c, const float *d_x, const pass::ChunkView &
 static int to_device_pool(fdnn_ctx *c, const float *d_x, const pass::ChunkView &v, const fdnn_pool *pool, hipStream_t s) {
   int rc = to_device_rows(c, d_x, v.cnt, nullptr, nullptr, c->d_out, s);
   if (!rc) fdnn::launch_pool(c->d_out, v.cnt, c->m->hm.hdr.out_dim, pool->d_class_ptr(), pool->d_member(), pool->n_classes, v.pooled, s);
+  return rc;
+}
+// device loglik: the rows stay in the context, their scores go to the caller's buffer
+static int to_device_loglik(fdnn_ctx *c, const float *d_x, const pass::ChunkView &v, const fdnn_loglik *ll, hipStream_t s) {
+  int rc = to_device_rows(c, d_x, v.cnt, nullptr, nullptr, c->d_out, s);
+  if (!rc) fdnn::launch_loglik_rows(c->d_out, v.cnt, c->m->hm.hdr.out_dim, ll->d_log_prior, ll->floor, ll->type, v.scores, s);
   return rc;
 }
 // the chunk's entries through the host form, which synchronises (a sets chunk without a segment scores nothing)
@@ -1025,6 +1048,8 @@ int run_chunks(fdnn_ctx *c, hipStream_t s, const pass::Chunks &chunks, const pas
       case Sink::device_sets: rc = to_device_sets(c, d_x, v, s); break;
       case Sink::host_pool: rc = dense_pass(c, {.pool = p.sink.pool, .pooled = v.pooled}, s, true); break;  // n x C x 4 bytes cross PCIe
       case Sink::device_pool: rc = to_device_pool(c, d_x, v, p.sink.pool, s); break;
+      case Sink::host_loglik: rc = dense_pass(c, {.loglik = p.sink.loglik, .scores = v.scores}, s, true); break;  // n x O x 4 or 2 bytes cross PCIe
+      case Sink::device_loglik: rc = to_device_loglik(c, d_x, v, p.sink.loglik, s); break;
     }
     if (rc) return rc;
   }

@@ -357,7 +357,8 @@ hipError_t reserve_buffers(fdnn_server *s, Slot &sl) {
       if (e == hipSuccess) e = sl.h_land.reserve(f.words, /*pageable_ok=*/true);
       break;
     case Want::topk:
-    case Want::pool:  // the pairs or the class sums of the batch: grown to the largest batch, the landing buffer pageable if need be
+    case Want::loglik:
+    case Want::pool:  // the pairs, the class sums or the scores of the batch: grown to the largest batch, the landing buffer pageable if need be
       e = sl.d_res.reserve(f.words);
       if (e == hipSuccess) e = sl.h_land.reserve(f.words, /*pageable_ok=*/true);
       break;
@@ -456,6 +457,9 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
       case Form::pool_sums:  // [n][C] class sums
         fdnn::launch_pool(sl.d_out.p, n, O, b.pool->d_class_ptr(), b.pool->d_member(), b.pool->n_classes, reinterpret_cast<float *>(sl.d_res.p), cs);
         break;
+      case Form::loglik_scores:  // [n][O] decoder scores of the batch's handle
+        fdnn::launch_loglik_rows(sl.d_out.p, n, O, b.score->d_log_prior, b.score->floor, b.score->type, sl.d_res.p, cs);
+        break;
     }
   });
   if (*rc) return hipSuccess;
@@ -471,6 +475,7 @@ hipError_t launch_batch(fdnn_server *s, Slot &sl, int *rc) {
     case Form::compacted_rows: src = sl.d_comp.p, dst = sl.h_comp.p; break;
     case Form::set_blocks: src = sl.d_out.p, dst = sl.h_land.p; break;
     case Form::topk_pairs:
+    case Form::scores:
     case Form::class_sums: src = sl.d_res.p, dst = sl.h_land.p; break;
   }
   sl.landing = dst;
@@ -620,6 +625,13 @@ int want_pool(fdnn_server *s, const fdnn_pool *pool, float *out, WantOut *w) {
   if (int rc = fdnn::check_pool(s->m, pool)) return rc;
   if (!out) return fail(FDNN_E_ARG, "null buffer");
   *w = Want::pool_to(pool, pool->n_classes, out);
+  return FDNN_OK;
+}
+
+int want_loglik(fdnn_server *s, const fdnn_loglik *ll, void *out, WantOut *w) {
+  if (int rc = fdnn::check_loglik(s->m, ll)) return rc;
+  if (!out) return fail(FDNN_E_ARG, "null buffer");
+  *w = Want::loglik_to(ll, fdnn::loglik::elem_bytes(ll->type), out);
   return FDNN_OK;
 }
 
@@ -847,6 +859,14 @@ int fdnn_server_submit_raw_pool(fdnn_server *s, const float *raw, int n, const f
   return submit_entry(s, kRaw, raw, n, ticket, [&](WantOut *w) { return want_pool(s, pool, out, w); });
 }
 
+int fdnn_server_submit_loglik(fdnn_server *s, const float *x, int n, const fdnn_loglik *ll, void *out, uint64_t *ticket) {
+  return submit_entry(s, kRows, x, n, ticket, [&](WantOut *w) { return want_loglik(s, ll, out, w); });
+}
+
+int fdnn_server_submit_raw_loglik(fdnn_server *s, const float *raw, int n, const fdnn_loglik *ll, void *out, uint64_t *ticket) {
+  return submit_entry(s, kRaw, raw, n, ticket, [&](WantOut *w) { return want_loglik(s, ll, out, w); });
+}
+
 int fdnn_server_live_open(fdnn_server *s, int max_chunk, fdnn_live **out) {
   if (!s || !out) return fail(FDNN_E_ARG, "null argument");
   *out = nullptr;
@@ -889,6 +909,11 @@ int fdnn_server_live_push_topk(fdnn_live *l, const float *raw, int n_raw, int en
 int fdnn_server_live_push_pool(fdnn_live *l, const float *raw, int n_raw, int end, const fdnn_pool *pool, float *out, int *n_out,
                                uint64_t *ticket) {
   return live_push(l, raw, n_raw, end, n_out, ticket, [&](int, WantOut *w) { return want_pool(l->s, pool, out, w); });
+}
+
+int fdnn_server_live_push_loglik(fdnn_live *l, const float *raw, int n_raw, int end, const fdnn_loglik *ll, void *out, int *n_out,
+                                 uint64_t *ticket) {
+  return live_push(l, raw, n_raw, end, n_out, ticket, [&](int, WantOut *w) { return want_loglik(l->s, ll, out, w); });
 }
 
 int fdnn_server_live_push_set(fdnn_live *l, const float *raw, int n_raw, int end, const int32_t *nodes, int len, float *probs,

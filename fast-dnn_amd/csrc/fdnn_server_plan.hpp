@@ -14,7 +14,8 @@
 
 #include "fdnn_splice_spec.hpp"
 
-struct fdnn_pool;  // (fdnn_internal.hpp: a node -> class map's handle; only its address travels here)
+struct fdnn_pool;    // (fdnn_internal.hpp: a node -> class map's handle; only its address travels here)
+struct fdnn_loglik;  // (fdnn_internal.hpp: a decoder-score handle; likewise)
 
 namespace fdnn::plan {
 
@@ -55,7 +56,7 @@ class Want {
   Want() = default;
 
  public:
-  enum Kind { rows = 0, rows_behind_bytes = 1, rows_behind_bits = 2, set = 3, topk = 4, pool = 5 } kind = rows;
+  enum Kind { rows = 0, rows_behind_bytes = 1, rows_behind_bits = 2, set = 3, topk = 4, pool = 5, loglik = 6 } kind = rows;
   // rows, rows_behind_bytes, rows_behind_bits: soft-max rows out [n][O]; behind byte masks [n][O] (non-zero = active) or bit
   // words [n][ceil(O / 64)], and for bits the largest number of active nodes in any row (widest_row, counted by the submitter)
   float *out = nullptr;
@@ -73,6 +74,10 @@ class Want {
   const fdnn_pool *map = nullptr;
   int classes = 0;
   float *pooled = nullptr;
+  // loglik: every row as decoder scores under the handle behind `score`, `score_bytes` (4 or 2) a score; scores [n][O]
+  const fdnn_loglik *score = nullptr;
+  size_t score_bytes = 0;
+  void *scores = nullptr;
 
   static Want rows_to(float *out) { Want w; w.out = out; return w; }
   static Want rows_behind_bytes_to(const int8_t *masks, float *out) { Want w; w.kind = rows_behind_bytes, w.masks = masks, w.out = out; return w; }
@@ -80,6 +85,7 @@ class Want {
   static Want set_to(SetRef nodes, float *probs, float *inactive) { Want w; w.kind = set, w.nodes = std::move(nodes), w.probs = probs, w.inactive = inactive; return w; }
   static Want topk_to(int k, int32_t *nodes, float *probs) { Want w; w.kind = topk, w.k = k, w.topk_nodes = nodes, w.topk_probs = probs; return w; }
   static Want pool_to(const fdnn_pool *map, int classes, float *pooled) { Want w; w.kind = pool, w.map = map, w.classes = classes, w.pooled = pooled; return w; }
+  static Want loglik_to(const fdnn_loglik *score, size_t score_bytes, void *scores) { Want w; w.kind = loglik, w.score = score, w.score_bytes = score_bytes, w.scores = scores; return w; }
 };
 
 // The Want of the rows behind the first `taken` of a request: the ONLY place where a caller's destination (and the masks that
@@ -97,6 +103,7 @@ inline Want want_at(const Want &w, int taken, size_t O, size_t wpr) {
       break;
     case Want::topk: p.topk_nodes += t * size_t(w.k), p.topk_probs += t * size_t(w.k); break;
     case Want::pool: p.pooled += t * size_t(w.classes); break;
+    case Want::loglik: p.scores = static_cast<char *>(w.scores) + t * O * w.score_bytes; break;
   }
   return p;
 }
@@ -150,12 +157,13 @@ inline int widest_row(const uint64_t *bits, int n, size_t O) {
 //   set_blocks        | nothing         | d_out                           | nnz + rows
 //   topk_pairs        | select_topk     | the device result buffer        | 2 * rows * topk_k
 //   class_sums        | pool_sums       | the device result buffer        | rows * pool_classes
+//   scores            | loglik_scores   | the device result buffer        | ceil(rows * O * score_bytes / 4)
 struct Form {
   enum Upload { no_upload, byte_masks, bit_words, node_sets } upload = no_upload;  // what goes up beside the frames ...
   size_t upload_bytes = 0;                                                         // ... and how much of it
   enum PassKind { loop_rows, loop_sets } pass = loop_rows;                         // fdnn::pass::Pass::loop_rows / loop_sets
-  enum Behind { nothing, compact, select_topk, pool_sums } behind = nothing;       // launched over all rows behind the chunks
-  enum Leave { by_caller_copies, whole_rows, compacted_rows, set_blocks, topk_pairs, class_sums } leave = by_caller_copies;
+  enum Behind { nothing, compact, select_topk, pool_sums, loglik_scores } behind = nothing;       // launched over all rows behind the chunks
+  enum Leave { by_caller_copies, whole_rows, compacted_rows, set_blocks, topk_pairs, class_sums, scores } leave = by_caller_copies;
   size_t words = 0;  // of the one result transfer
 };
 
@@ -174,6 +182,8 @@ struct BatchPlan {
   int topk_k = 0;              // top-k batches: the largest k among its pieces (a smaller k's result is a prefix of it)
   const fdnn_pool *pool = nullptr;  // pool batches: the one handle of all its pieces ...
   int pool_classes = 0;             // ... and its class count
+  const fdnn_loglik *score = nullptr;  // loglik batches: the one handle of all its pieces ...
+  size_t score_bytes = 0;              // ... and the bytes of one score
   Form form;
 };
 
@@ -184,6 +194,8 @@ struct BatchPlan {
 // -- top-k requests (a dense batch whose rows stay on the device, fdnn_topk.hip selects from them) only with top-k requests
 // -- pool requests (a dense batch whose rows stay on the device, fdnn_pool.hip sums them by class) only with pool requests
 //    of the SAME handle
+// -- loglik requests (a dense batch whose rows stay on the device, fdnn_loglik.hip turns them into decoder scores) only with
+//    loglik requests of the SAME handle
 // and in every case raw-frame requests only with raw-frame requests, under one spec object.
 inline bool may_join(const BatchPlan &b, const Request &r) {
   if ((r.frames.kind == Frames::raw_frames) != b.raw || r.frames.spec != b.spec) return false;
@@ -194,6 +206,7 @@ inline bool may_join(const BatchPlan &b, const Request &r) {
     case Want::set:
     case Want::topk: return b.kind == r.want.kind;
     case Want::pool: return b.kind == Want::pool && b.pool == r.want.map;
+    case Want::loglik: return b.kind == Want::loglik && b.score == r.want.score;
   }
   return false;
 }
@@ -210,6 +223,7 @@ inline void set_leave(BatchPlan &b, Form::Leave leave, size_t O) {
     case Form::set_blocks: f.behind = Form::nothing, f.words = size_t(b.nnz) + rows; break;
     case Form::topk_pairs: f.behind = Form::select_topk, f.words = 2 * rows * size_t(b.topk_k); break;
     case Form::class_sums: f.behind = Form::pool_sums, f.words = rows * size_t(b.pool_classes); break;
+    case Form::scores: f.behind = Form::loglik_scores, f.words = (rows * O * b.score_bytes + 3) / 4; break;
   }
 }
 
@@ -232,6 +246,7 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
       b.raw = r.frames.kind == Frames::raw_frames;
       b.spec = r.frames.spec;
       b.pool = r.want.map, b.pool_classes = r.want.classes;
+      b.score = r.want.score, b.score_bytes = r.want.score_bytes;
     } else if (!may_join(b, r)) {
       break;
     }
@@ -255,6 +270,7 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
       }
       case Want::topk: b.topk_k = std::max(b.topk_k, r.want.k); break;
       case Want::pool: break;
+      case Want::loglik: break;
     }
     b.pieces.push_back(std::move(pc));
     if (b.raw) {  // the raw frames this piece's rows reference, and where they are staged
@@ -295,6 +311,7 @@ inline BatchPlan plan_batch(std::deque<Request> &queue, int max_frames, size_t O
       break;
     case Want::topk: set_leave(b, Form::topk_pairs, O); break;
     case Want::pool: set_leave(b, Form::class_sums, O); break;
+    case Want::loglik: set_leave(b, Form::scores, O); break;
   }
   return b;
 }
@@ -361,6 +378,9 @@ inline void scatter(const BatchPlan &b, const Piece &p, const void *landing, siz
       std::memcpy(w.pooled, at(row0 * C), word * rows * C);
       break;
     }
+    case Form::scores:  // [rows][O] scores of score_bytes each: a piece's rows start at a byte, not a word, of the landing buffer
+      std::memcpy(w.scores, static_cast<const char *>(landing) + row0 * O * b.score_bytes, rows * O * b.score_bytes);
+      break;
   }
 }
 

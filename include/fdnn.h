@@ -405,6 +405,68 @@ FDNN_API int fdnn_ctx_output_pool_device(fdnn_ctx *c, const fdnn_pool *pool, flo
 FDNN_API int fdnn_calculate_pool(fdnn_model *m, const float *x, int n, int dim, const fdnn_pool *pool, float *out);
 FDNN_API int fdnn_calculate_pool_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_pool *pool, float *out);
 FDNN_API int fdnn_calculate_pool_device(fdnn_model *m, const float *d_x, int n, const fdnn_pool *pool, float *d_out, void *stream);
+/* ------------------------------------------------------------------ dense output as decoder scores (fdnn_loglik.hip)
+ * What a hybrid decoder consumes is not the posterior but the scaled log-likelihood ln p(s|x) - ln p(s).  These entries
+ * compute it on the DEVICE from the dense soft-max and return the whole row, as fp32 or -- scores fit fp16 where
+ * probabilities do not: a posterior of 1e-9 is 0 in fp16, its logarithm -20.7 an ordinary number -- as fp16, half the bytes
+ * of fdnn_calculate.  The reference has no such call; every entry below extends CalculateOutput (dnn.cc:428-454).
+ *
+ * The handle: fdnn_loglik_create(log_prior [W], W, floor, type).  Every log_prior[i] is finite; 1 <= W <= 2^19; floor is not
+ * a NaN and not +inf, -inf means no floor; type is FDNN_LOGLIK_F32 or FDNN_LOGLIK_F16; an F16 handle with a finite floor
+ * below -65504 is refused.  The priors are uploaded to the device that is CURRENT at creation.  A handle is immutable;
+ * threads, contexts and scoring loops may share it; it must outlive every call and every ticket that uses it.  A call whose
+ * handle width differs from the model's output_dim, whose handle lives on another device than the model, or whose model
+ * leads a device group is FDNN_E_ARG before anything is launched.
+ *
+ * The score of a row p[0 .. W):
+ *   s_i = ln(p_i) - log_prior[i]          one fp32 subtraction, round to nearest even
+ *   s_i = (s_i < floor) ? floor : s_i     a NaN stays a NaN
+ *   F16: the RN-even conversion of s_i    |s_i| >= 65520 becomes +-inf; fp16 denormals are kept
+ * ln is neither the hardware's nor the C library's logarithm but ONE fixed sequence of fp32 operations (fdnn_loglik.hpp:
+ * fmaf, single multiplications, additions and subtractions, integer operations; the Cephes scheme), the same bits on the
+ * host and on the device: NaN -> a NaN; any negative value, negative denormals included -> a NaN; +0 and -0 -> -inf;
+ * +inf -> +inf; denormals are not flushed.  Over ALL positive finite floats its worst error against float64 log is 0.8265
+ * ulp (bound kLnMaxUlp = 0.85), it is monotone, and ln(1) = +0 (tools/ln_sweep.cpp, profiles/ln_sweep.log).  It differs
+ * from the correctly rounded logarithm in 0.6 % of the floats in (0, 1]: compare with fdnn_debug_loglik_ref, not with a
+ * library's log.  s is a function of the row and the handle alone: not of n, the row's position, the entry point, the batch
+ * or the kernel form.  With a finite floor no -inf leaves the device.  FROZEN: results depend on the sequence.
+ * NOTE: the k best probabilities are NOT the k best scores -- subtracting the priors reorders the nodes; a top-k result
+ * turned into scores (fdnn_loglik_entries_device) holds the scores of the k most PROBABLE nodes.
+ * Results are [n][W] row-major of float (F32) or IEEE binary16 (F16); every element is written, nothing outside is, inputs
+ * are never modified.  The batcher, device groups and the JNI shim neither route to nor look at these entry points, and every
+ * other entry point keeps its bytes.
+ *
+ * fdnn_loglik_create / _free / _width / _type   the handle (NULL from create: see fdnn_last_error; dnn.cc:428-454).
+ * fdnn_loglik_rows_device     the scores alone of any device-resident [n][W] fp32 rows of the handle's device (rows 4-byte
+ *   aligned, d_out aligned to its element; where W % 4 == 0 and both start on a 16-byte boundary a faster form runs, same
+ *   bytes; dnn.cc:428-454).  Enqueued on `stream`, not synchronised; n == 0 is a no-op.
+ * fdnn_loglik_entries_device  for a flat list (d_nodes[j], d_p[j]), j < count: s_j = ln(p_j) - log_prior[node_j], the same
+ *   floor and type; a node outside [0, W) gives a NaN and reads nothing.  Turns the results of the top-k, lists, set and
+ *   sets calls into decoder scores on the device (dnn.cc:428-454).
+ * fdnn_ctx_output_loglik      fdnn_ctx_output's computation (CalculateOutput, dnn.cc:428-454) into the context's own rows,
+ *   then the scores; host buffer, host-synchronous.  FDNN_E_STATE before the hidden layers.  Works unchanged on
+ *   fdnn_stream_ctx(s) after a hidden-only push.
+ * fdnn_ctx_output_loglik_device  the same with a device buffer, enqueued on `stream` (dnn.cc:428-454).
+ * fdnn_calculate_loglik       host to host on a pooled context, chunk by chunk like fdnn_calculate (Calculate,
+ *   dnn.cc:162-165; CalculateOutput, dnn.cc:428-454): n x W x 4 or 2 bytes cross PCIe.  Obeys the re-run rules of the dense
+ *   host forms.
+ * fdnn_calculate_loglik_raw   the same from raw feature frames, like fdnn_calculate_raw (dnn.cc:428-454).
+ * fdnn_calculate_loglik_device  device buffers (d_x 16-byte aligned like its siblings, d_out element-aligned), a pooled
+ *   context for the intermediate rows; enqueued, not synchronised (dnn.cc:428-454). */
+#define FDNN_LOGLIK_F32 0
+#define FDNN_LOGLIK_F16 1
+typedef struct fdnn_loglik fdnn_loglik;
+FDNN_API fdnn_loglik *fdnn_loglik_create(const float *log_prior, int width, float floor, int type);
+FDNN_API void fdnn_loglik_free(fdnn_loglik *ll);
+FDNN_API int fdnn_loglik_width(const fdnn_loglik *ll);
+FDNN_API int fdnn_loglik_type(const fdnn_loglik *ll);
+FDNN_API int fdnn_loglik_rows_device(const fdnn_loglik *ll, const float *d_rows, int n, void *d_out, void *stream);
+FDNN_API int fdnn_loglik_entries_device(const fdnn_loglik *ll, const int32_t *d_nodes, const float *d_p, long long count, void *d_out, void *stream);
+FDNN_API int fdnn_ctx_output_loglik(fdnn_ctx *c, const fdnn_loglik *ll, void *out);
+FDNN_API int fdnn_ctx_output_loglik_device(fdnn_ctx *c, const fdnn_loglik *ll, void *d_out, void *stream);
+FDNN_API int fdnn_calculate_loglik(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, void *out);
+FDNN_API int fdnn_calculate_loglik_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, void *out);
+FDNN_API int fdnn_calculate_loglik_device(fdnn_model *m, const float *d_x, int n, const fdnn_loglik *ll, void *d_out, void *stream);
 /* Last hidden layer's u8 activations, n x hidden_dim (quantized_activations_). */
 FDNN_API int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out);
 
@@ -487,6 +549,14 @@ FDNN_API int fdnn_server_submit_raw_topk(fdnn_server *s, const float *raw, int n
  * submit time. */
 FDNN_API int fdnn_server_submit_pool(fdnn_server *s, const float *x, int n, const fdnn_pool *pool, float *out, uint64_t *ticket);
 FDNN_API int fdnn_server_submit_raw_pool(fdnn_server *s, const float *raw, int n, const fdnn_pool *pool, float *out, uint64_t *ticket);
+/* One utterance's decoder scores through the loop (the loglik contract above; CalculateOutput, dnn.cc:428-454, for many
+ * callers): loglik submissions share a batch only with loglik submissions of the SAME handle, the same rawness and the same
+ * spec; the batch runs as a dense batch, ONE score launch runs over the rows -- which never leave the device --, one transfer
+ * brings [rows][output_dim] scores of the handle's type to the host (half the dense batch's bytes for F16), and each caller
+ * gets its rows.  Byte-identical to fdnn_calculate_loglik / fdnn_calculate_loglik_raw on the same utterance.  x or raw, out
+ * [n][output_dim] and the handle must stay valid until the ticket completes. */
+FDNN_API int fdnn_server_submit_loglik(fdnn_server *s, const float *x, int n, const fdnn_loglik *ll, void *out, uint64_t *ticket);
+FDNN_API int fdnn_server_submit_raw_loglik(fdnn_server *s, const float *raw, int n, const fdnn_loglik *ll, void *out, uint64_t *ticket);
 /* Live utterances through the loop: many utterances arriving at once, each chunk by chunk (SURVEY 8(f) row 3 as a real-time
  * recogniser meets it; see "Streams" above for one utterance on its own).  A live handle is the stream object of ONE
  * utterance at a time; its pushes are scored by the loop, in batches shared with the other handles' pushes and with whole
@@ -527,6 +597,10 @@ FDNN_API int fdnn_server_live_push_pool(fdnn_live *l, const float *raw, int n_ra
                                         uint64_t *ticket);
 FDNN_API int fdnn_server_live_push_set(fdnn_live *l, const float *raw, int n_raw, int end, const int32_t *nodes, int len, float *probs,
                                        float *inactive, int *n_out, uint64_t *ticket);
+/* The same push with the return of fdnn_server_submit_raw_loglik: out [*n_out][output_dim] decoder scores of the handle's
+ * type (CalculateOutput, dnn.cc:428-454). */
+FDNN_API int fdnn_server_live_push_loglik(fdnn_live *l, const float *raw, int n_raw, int end, const fdnn_loglik *ll, void *out, int *n_out,
+                                          uint64_t *ticket);
 FDNN_API int fdnn_server_wait(fdnn_server *s, uint64_t ticket);
 FDNN_API int fdnn_server_drain(fdnn_server *s);
 FDNN_API int fdnn_server_stats(fdnn_server *s, uint64_t *batches, uint64_t *frames, uint64_t *requests,
@@ -746,6 +820,21 @@ FDNN_API int fdnn_debug_pool_launches(unsigned long long *out, int cap);
 FDNN_API int fdnn_debug_set_pool_kernel(int mode);
 FDNN_API int fdnn_debug_pool_ref(const float *rows, int n, const int32_t *class_of, int width, int n_classes, float *out);
 FDNN_API int fdnn_debug_pool_limits(int *lanes, int *resident_width);
+
+/* Dense output as decoder scores (CalculateOutput, dnn.cc:428-454), tests and tools.
+ * fdnn_debug_loglik_launches    process-wide counts since load, returns 3: out[0] launches of the rows kernel's vector form,
+ *   [1] of its scalar-access form, [2] of the entries kernel.  Not in the launch recorder's table (fdnn_note.hpp).
+ * fdnn_debug_set_loglik_kernel  process-wide: 0 the plan's rule (vector where width % 4 == 0 and both bases are 16-byte
+ *   aligned), 1 vector where allowed, 2 always scalar access -- the same bytes either way (dnn.cc:428-454).
+ * fdnn_debug_loglik_ref         the scores of fdnn_loglik_rows_device from the host restatement (fdnn_loglik.hpp) on host rows
+ *   [n][width], out [n][width] of the type; host code, no device needed (dnn.cc:428-454).
+ * fdnn_debug_loglik_entries_ref the same for fdnn_loglik_entries_device (dnn.cc:428-454).
+ * fdnn_debug_ln_ref             loglik::ln of count floats (dnn.cc:428-454). */
+FDNN_API int fdnn_debug_loglik_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_set_loglik_kernel(int mode);
+FDNN_API int fdnn_debug_loglik_ref(const float *rows, int n, const float *log_prior, int width, float floor, int type, void *out);
+FDNN_API int fdnn_debug_loglik_entries_ref(const int32_t *nodes, const float *p, long long count, const float *log_prior, int width, float floor, int type, void *out);
+FDNN_API int fdnn_debug_ln_ref(const float *x, long long count, float *out);
 
 /* Splicing through a segment table in device memory (the scoring loop's live batches, fdnn_splice.hip), tests and tools.
  * fdnn_debug_splice_table   the splice alone, host in and host out: raw [raw_frames][raw_dim] -> x [rows][input_dim] under the

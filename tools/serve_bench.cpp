@@ -17,6 +17,11 @@
 //                      48) classes of nodes (node i in class i mod POOL_C) -- frames x POOL_C x 4 bytes back
 //         poolserver = fdnn_server_submit_pool + fdnn_server_wait (pool utterances of the one handle coalesced, the dense rows
 //                      stay on the device)
+//         loglik       = fdnn_calculate_loglik per utterance: every frame's soft-max as decoder scores ln p - log prior (uniform
+//                        priors here, floor -30), computed on the device -- LOGLIK_TYPE (environment; 1 = fp16, the default,
+//                        0 = fp32): frames x output_dim x 2 or 4 bytes back
+//         loglikserver = fdnn_server_submit_loglik + fdnn_server_wait (loglik utterances of the one handle coalesced, the
+//                        dense rows stay on the device, ONE transfer of the batch's scores)
 //         live       = fdnn_stream_push: every feed its own stream, utterances of F raw frames (Kaldi +-5 x 39, set here) pushed in
 //                      chunks of c frames, host-synchronous push by push
 //         liveserver = fdnn_server_live_push + fdnn_server_wait: the same feeds through live handles of ONE scoring loop; a
@@ -30,6 +35,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -180,7 +186,9 @@ int main(int argc, char **argv) {
   const int topk_k = std::getenv("TOPK_K") ? std::atoi(std::getenv("TOPK_K")) : 32;
   const bool pooled = mode == "pool" || mode == "poolserver";
   const int pool_c = std::getenv("POOL_C") ? std::atoi(std::getenv("POOL_C")) : 48;
-  if ((mode == "server" || mode == "lazyserver" || mode == "setserver" || mode == "topkserver" || mode == "poolserver") && fdnn_server_create(m, max_frames, depth, &srv)) {
+  const bool scored = mode == "loglik" || mode == "loglikserver";
+  const int loglik_type = std::getenv("LOGLIK_TYPE") ? std::atoi(std::getenv("LOGLIK_TYPE")) : FDNN_LOGLIK_F16;
+  if ((mode == "server" || mode == "lazyserver" || mode == "setserver" || mode == "topkserver" || mode == "poolserver" || mode == "loglikserver") && fdnn_server_create(m, max_frames, depth, &srv)) {
     std::fprintf(stderr, "server: %s\n", fdnn_last_error());
     return 1;
   }
@@ -244,6 +252,17 @@ int main(int argc, char **argv) {
       return 1;
     }
     for (int t = 0; t < T; ++t) pool_out[size_t(t)].assign(size_t(F) * size_t(pool_c), 0.0f);
+  }
+  fdnn_loglik *ll = nullptr;  // loglik modes: one handle for every caller, per thread [F][O] scores of 2 or 4 bytes
+  std::vector<std::vector<uint16_t>> ll_out(static_cast<size_t>(T));
+  const float ll_prior = -std::log(float(O));
+  if (scored) {
+    const std::vector<float> log_prior(static_cast<size_t>(O), ll_prior);
+    if (inflight > 1 || !(ll = fdnn_loglik_create(log_prior.data(), O, -30.0f, loglik_type))) {
+      std::fprintf(stderr, "loglik: %s (LOGLIK_TYPE is 0 or 1; the loglik modes keep one utterance per caller in flight)\n", fdnn_last_error());
+      return 1;
+    }
+    for (int t = 0; t < T; ++t) ll_out[size_t(t)].assign(size_t(F) * size_t(O) * (loglik_type == FDNN_LOGLIK_F16 ? 1 : 2), 0);
   }
   if (lazy && set_len > 0) {
     for (int t = 0; t < T; ++t) {
@@ -314,6 +333,14 @@ int main(int argc, char **argv) {
         } else {
           rc = fdnn_calculate_pool(m, xs[size_t(t)].data(), F, D, pool, pool_out[size_t(t)].data());
         }
+      } else if (scored) {
+        if (srv) {
+          uint64_t ticket = 0;
+          rc = fdnn_server_submit_loglik(srv, xs[size_t(t)].data(), F, ll, ll_out[size_t(t)].data(), &ticket);
+          if (!rc) rc = fdnn_server_wait(srv, ticket);
+        } else {
+          rc = fdnn_calculate_loglik(m, xs[size_t(t)].data(), F, D, ll, ll_out[size_t(t)].data());
+        }
       } else if (srv && lazy) {
         uint64_t ticket = 0;
         rc = fdnn_server_submit_lazy_bits(srv, xs[size_t(t)].data(), F, bits[size_t(t)].data(), outs[size_t(t)].data(), &ticket);
@@ -357,6 +384,21 @@ int main(int argc, char **argv) {
     sum = 0.0;
     for (int j = 0; j < pool_c; ++j) sum += pool_out[0][size_t(j)];
   }
+  if (scored) {  // row 0's scores back to probabilities: exp(s + log prior) adds up to the row's total (fp16: to three digits)
+    sum = 0.0;
+    for (int j = 0; j < O; ++j) {
+      float sc;
+      if (loglik_type == FDNN_LOGLIK_F16) {
+        const uint16_t h = ll_out[0][size_t(j)];
+        const int e = (h >> 10) & 31, f = h & 1023;
+        sc = e == 0 ? std::ldexp(float(f), -24) : e == 31 ? (f ? NAN : INFINITY) : std::ldexp(float(f | 1024), e - 25);
+        if (h & 0x8000) sc = -sc;
+      } else {
+        std::memcpy(&sc, reinterpret_cast<const char *>(ll_out[0].data()) + 4 * size_t(j), 4);
+      }
+      sum += std::exp(double(sc) + double(ll_prior));
+    }
+  }
   uint64_t batches = 0, frames = 0, reqs = 0, coal = 0;
   if (srv) fdnn_server_stats(srv, &batches, &frames, &reqs, &coal);
   std::printf("{\"mode\": \"%s\", \"threads\": %d, \"frames_per_utt\": %d, \"utts\": %d, \"seconds\": %.4f, \"utts_per_s\": %.1f, "
@@ -365,6 +407,7 @@ int main(int argc, char **argv) {
               (unsigned long long)reqs);
   if (srv) fdnn_server_free(srv);
   fdnn_pool_free(pool);
+  fdnn_loglik_free(ll);
   fdnn_model_free(m);
   return failed.load() ? 1 : 0;
 }
