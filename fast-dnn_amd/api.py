@@ -193,6 +193,21 @@ SIGNATURES = {
     "fdnn_debug_set_loglik_kernel": (C.c_int, [C.c_int]),
     "fdnn_debug_loglik_ref": (C.c_int, [_c_f32p, C.c_int, _c_f32p, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "fdnn_debug_loglik_entries_ref": (C.c_int, [_c_i32p, _c_f32p, C.c_longlong, _c_f32p, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "fdnn_align_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_align_scratch_words": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.POINTER(C.c_longlong)]),
+    "fdnn_ctx_align": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_f32p, _c_f32p, _c_i32p, _c_f32p]),
+    "fdnn_ctx_align_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_f32p, _c_f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_align": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_f32p, _c_f32p, _c_i32p,
+                                       _c_f32p]),
+    "fdnn_calculate_align_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_f32p, _c_f32p,
+                                           _c_i32p, _c_f32p]),
+    "fdnn_debug_align_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_set_align_kernel": (C.c_int, [C.c_int]),
+    "fdnn_debug_align_limits": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "fdnn_debug_align_ref": (C.c_int, [_c_f32p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, C.c_int, C.c_float,
+                                       C.c_int, _c_f32p, _c_f32p, _c_i32p, _c_f32p]),
+    "fdnn_debug_align_sets": (C.c_int, [_c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p]),
     "fdnn_debug_ln_ref": (C.c_int, [_c_f32p, C.c_longlong, _c_f32p]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -756,6 +771,127 @@ def set_loglik_kernel(mode: int) -> None:
     _check(lib().fdnn_debug_set_loglik_kernel(int(mode)))
 
 
+ALIGN_SCORES = -1  # the ``type`` of an align call without a handle: the rows are scores already
+
+
+def _fp(a):
+    """A float32 array's pointer, or NULL for None."""
+    return None if a is None else a.ctypes.data_as(_c_f32p)
+
+
+def _align_tables(segRows, statePtr, states, selfLp, nextLp):
+    """(seg_rows, state_ptr, states, self_lp, next_lp) as C-contiguous vectors of the shapes every align entry point needs ->
+    them, the segment count and the rows."""
+    sr = np.ascontiguousarray(segRows, dtype=np.int32)
+    sp = np.ascontiguousarray(statePtr, dtype=np.int32)
+    st = np.ascontiguousarray(states, dtype=np.int32)
+    if sr.ndim != 1 or sp.ndim != 1 or st.ndim != 1 or sr.size != sp.size or sr.size < 1:
+        raise ValueError("segRows and statePtr must be [segments + 1] and states [statePtr[-1]]")
+    if int(sp.max()) > st.size:  # (the C side reads statePtr[segments] states)
+        raise ValueError(f"statePtr reaches {int(sp.max())} but there are {st.size} states")
+    lps = []
+    for lp in (selfLp, nextLp):
+        if lp is not None:
+            lp = np.ascontiguousarray(lp, dtype=np.float32)
+            if lp.shape != st.shape:
+                raise ValueError("selfLp and nextLp are [states] like the transcript")
+        lps.append(lp)
+    return sr, sp, st, lps[0], lps[1], sr.size - 1, max(int(sr[-1]) - int(sr[0]), 0)
+
+
+def _align_rows_tables(segT, rowOff, rowLd, statePtr):
+    t = np.ascontiguousarray(segT, dtype=np.int32)
+    off = np.ascontiguousarray(rowOff, dtype=np.int64)
+    ld = np.ascontiguousarray(rowLd, dtype=np.int32)
+    sp = np.ascontiguousarray(statePtr, dtype=np.int32)
+    if t.ndim != 1 or off.shape != t.shape or ld.shape != t.shape or sp.shape != (t.size + 1,):
+        raise ValueError("segT, rowOff and rowLd must be [segments] and statePtr [segments + 1]")
+    return t, off, ld, sp
+
+
+def align_sets(statePtr, states):
+    """The transcripts' node sets as the align calls build them (``fdnn_debug_align_sets``; host code): (set_ptr [segments + 1],
+    nodes, col [states]) -- each segment's distinct nodes, ascending, the form ``calculateLazySets`` takes, and the position of
+    every state's node in its segment's set."""
+    sp = np.ascontiguousarray(statePtr, dtype=np.int32)
+    st = np.ascontiguousarray(states, dtype=np.int32)
+    if sp.ndim != 1 or sp.size < 1 or st.ndim != 1 or int(sp.max()) > st.size:
+        raise ValueError("statePtr must be [segments + 1] and states [statePtr[-1]]")
+    set_ptr = np.zeros(sp.size, np.int32)
+    nodes = np.empty(max(st.size, 1), np.int32)
+    col = np.empty(max(st.size, 1), np.int32)
+    _check(lib().fdnn_debug_align_sets(sp.ctypes.data_as(_c_i32p), st.ctypes.data_as(_c_i32p), sp.size - 1, set_ptr.ctypes.data_as(_c_i32p),
+                                       nodes.ctypes.data_as(_c_i32p), col.ctypes.data_as(_c_i32p)))
+    return set_ptr, nodes[:int(set_ptr[-1])].copy(), col[:int(sp[-1])].copy()
+
+
+def align_ref(rows, segT, rowOff, rowLd, statePtr, col, stateNode=None, log_prior=None, floor: float = -np.inf, type: int = ALIGN_SCORES,
+              selfLp=None, nextLp=None):
+    """The recursion from the host restatement (``fdnn_debug_align_ref``; host code, no device): rows a flat float32 array (any
+    bit patterns), segment s = segT[s] rows of stride rowLd[s] beginning at element rowOff[s]; col [states]; with ``type``
+    LOGLIK_F32 / LOGLIK_F16 the rows are probabilities and stateNode [states], log_prior and floor make the scores, with
+    ALIGN_SCORES they are scores -> (path int32 [sum segT], total float32 [segments])."""
+    r = np.ascontiguousarray(rows, dtype=np.float32).ravel()
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, statePtr)
+    c = np.ascontiguousarray(col, dtype=np.int32)
+    nd = None if stateNode is None else np.ascontiguousarray(stateNode, dtype=np.int32)
+    lp = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float32)
+    sl = None if selfLp is None else np.ascontiguousarray(selfLp, dtype=np.float32)
+    nl = None if nextLp is None else np.ascontiguousarray(nextLp, dtype=np.float32)
+    if t.size and ((off + (t.astype(np.int64) - 1) * ld + ld > r.size).any() or (off < 0).any() or c.size < int(sp[-1])):
+        raise ValueError("a segment's rows run past the rows, or col is shorter than the transcripts")
+    path = np.empty(int(t.astype(np.int64).sum()), np.int32)
+    total = np.empty(t.size, np.float32)
+    _check(lib().fdnn_debug_align_ref(r.ctypes.data_as(_c_f32p), t.ctypes.data_as(_c_i32p), off.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                      ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, c.ctypes.data_as(_c_i32p),
+                                      None if nd is None else nd.ctypes.data_as(_c_i32p), _fp(lp), 0 if lp is None else lp.size, C.c_float(float(floor)),
+                                      int(type), _fp(sl), _fp(nl), path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
+    return path, total
+
+
+def align_scratch_words(segT, statePtr) -> int:
+    """The 32-bit scratch words ``align_rows_device`` needs for these tables under the current kernel mode
+    (``fdnn_align_scratch_words``): the back-pointer words of the segments that do not fit LDS."""
+    t = np.ascontiguousarray(segT, dtype=np.int32)
+    sp = np.ascontiguousarray(statePtr, dtype=np.int32)
+    words = C.c_longlong(0)
+    _check(lib().fdnn_align_scratch_words(t.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, C.byref(words)))
+    return int(words.value)
+
+
+def align_rows_device(ll, d_rows: int, segT, rowOff, rowLd, statePtr, d_col: int, d_state_node: int, d_self_lp: int, d_next_lp: int, d_scratch: int,
+                      scratch_words: int, d_path: int, d_total: int, stream: int = 0) -> None:
+    """The recursion alone on device-resident fp32 rows (``fdnn_align_rows_device``): host tables as ``align_ref``, device
+    pointers for everything they index; ``ll`` a ``Loglik`` (the rows are probabilities) or None (they are scores).  Enqueued on
+    ``stream``, not synchronised."""
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, statePtr)
+    _check(lib().fdnn_align_rows_device(None if ll is None else ll.handle, C.c_void_p(d_rows), t.ctypes.data_as(_c_i32p),
+                                        off.ctypes.data_as(C.POINTER(C.c_longlong)), ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size,
+                                        C.c_void_p(d_col), C.c_void_p(d_state_node), C.c_void_p(d_self_lp), C.c_void_p(d_next_lp), C.c_void_p(d_scratch),
+                                        int(scratch_words), C.c_void_p(d_path), C.c_void_p(d_total), C.c_void_p(stream)))
+
+
+def align_launches():
+    """Process-wide counts since load: (launches of the align kernel's wave form, of its workgroup form)."""
+    buf = (C.c_ulonglong * 2)()
+    if lib().fdnn_debug_align_launches(buf, 2) != 2:
+        raise RuntimeError("fdnn_debug_align_launches")
+    return tuple(int(v) for v in buf)
+
+
+def set_align_kernel(mode: int) -> None:
+    """Process-wide (``fdnn_debug_set_align_kernel``): 0 the plan's rule, 1 the wave form where allowed, 2 always the workgroup form."""
+    _check(lib().fdnn_debug_set_align_kernel(int(mode)))
+
+
+def align_limits() -> dict:
+    """The align kernels' limits as built (``fdnn_debug_align_limits``)."""
+    buf = (C.c_int * 6)()
+    if lib().fdnn_debug_align_limits(buf, 6) != 6:
+        raise RuntimeError("fdnn_debug_align_limits")
+    return dict(zip(("max_states", "segs_per_launch", "wave_states", "frames_in_flight", "lds_bp_words", "scratch_cap_mib"), (int(v) for v in buf)))
+
+
 def _loglik_out(n: int, ll: "Loglik", out):
     """The [n][width] result array of a loglik call, made or checked."""
     shape = (n, ll.width())
@@ -978,6 +1114,23 @@ class LazyContext:
         out = _loglik_out(self.inputVectorCount, ll, None)
         _check(lib().fdnn_ctx_output_loglik(self.handle, ll.handle, C.c_void_p(out.ctypes.data)))
         return out
+
+    def align(self, ll: "Loglik", segRows, statePtr, states, selfLp=None, nextLp=None):
+        """Forced alignment over rows of the context (``fdnn_ctx_align``): segment s = rows [segRows[s], segRows[s + 1]) with the
+        transcript states[statePtr[s] .. statePtr[s + 1]) and optional transition scores -> (path int32 [rows], total float32
+        [segments]); a segment without a finite total has -1 everywhere."""
+        sr, sp, st, sl, nl, n_segs, rows = _align_tables(segRows, statePtr, states, selfLp, nextLp)
+        path = np.empty(rows, np.int32)
+        total = np.empty(n_segs, np.float32)
+        _check(lib().fdnn_ctx_align(self.handle, ll.handle, sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, st.ctypes.data_as(_c_i32p),
+                                    _fp(sl), _fp(nl), path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
+        return path, total
+
+    def alignDevice(self, ll: "Loglik", segRows, statePtr, states, d_path: int, d_total: int, selfLp=None, nextLp=None, stream: int = 0) -> None:
+        """The same with device result buffers, enqueued on ``stream`` and not synchronised (``fdnn_ctx_align_device``)."""
+        sr, sp, st, sl, nl, n_segs, _ = _align_tables(segRows, statePtr, states, selfLp, nextLp)
+        _check(lib().fdnn_ctx_align_device(self.handle, ll.handle, sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs,
+                                           st.ctypes.data_as(_c_i32p), _fp(sl), _fp(nl), C.c_void_p(d_path), C.c_void_p(d_total), C.c_void_p(stream)))
 
     def calculateOutputLoglikDevice(self, ll: "Loglik", d_out: int, stream: int = 0) -> None:
         """The same into a device buffer [frames][outputDimension] of the handle's type, enqueued on ``stream``, not
@@ -1747,6 +1900,37 @@ class QuantizedDnn:
         """Device-resident form (``fdnn_calculate_loglik_device``): d_x [n][inputDimension] -> d_out [n][outputDimension] of the
         handle's type; raw device pointers, enqueued on ``stream``, not synchronised."""
         _check(lib().fdnn_calculate_loglik_device(self.nativeDnnHandle, C.c_void_p(d_x), int(n), ll.handle, C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def calculateAlign(self, input, ll: "Loglik", segRows, statePtr, states, selfLp=None, nextLp=None):
+        """Forced alignment in one call (``fdnn_calculate_align``; segRows must cover [0, frames)): hidden layers, the
+        transcripts' node sets, the recursion on the device -> (path int32 [frames], total float32 [segments]), as
+        ``LazyContext.align``.  Many utterances per call is the batched form.  Host frames only: there is no device-frames
+        form (no ``calculate_align_device``) -- the C-ABI has no entry for it."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        sr, sp, st, sl, nl, n_segs, _ = _align_tables(segRows, statePtr, states, selfLp, nextLp)
+        path = np.empty(n, np.int32)
+        total = np.empty(n_segs, np.float32)
+        _check(lib().fdnn_calculate_align(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(), ll.handle,
+                                          sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, st.ctypes.data_as(_c_i32p), _fp(sl), _fp(nl),
+                                          path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
+        return path, total
+
+    def calculateAlignRaw(self, raw, ll: "Loglik", segRows, statePtr, states, selfLp=None, nextLp=None):
+        """``calculateAlign`` on raw frames [n][rawDim], spliced on the device, every segment an utterance of its own
+        (``fdnn_calculate_align_raw``)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError("raw must be [frames][rawDim]")
+        sr, sp, st, sl, nl, n_segs, _ = _align_tables(segRows, statePtr, states, selfLp, nextLp)
+        path = np.empty(r.shape[0], np.int32)
+        total = np.empty(n_segs, np.float32)
+        _check(lib().fdnn_calculate_align_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], ll.handle,
+                                              sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, st.ctypes.data_as(_c_i32p), _fp(sl), _fp(nl),
+                                              path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
+        return path, total
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))

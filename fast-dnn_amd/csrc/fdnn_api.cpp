@@ -1020,6 +1020,192 @@ int fdnn_debug_ln_ref(const float *x, long long count, float *out) {
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- forced alignment (fdnn_align.hip)
+// The recursion alone.  The tables are host memory and are checked (the plan is made from them); what they index is on the
+// device and is not: a column or node out of range gives a NaN emission, so a total that is not finite and an all -1 path.
+static int align_rows_tables(const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr, int n_segs) {
+  if (n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
+  if (n_segs == 0) return FDNN_OK;
+  if (!seg_T || !row_off || !row_ld || !state_ptr || state_ptr[0] != 0) return fail(FDNN_E_ARG, "align, segment 0: malformed tables");
+  long long rows = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const long long S = static_cast<long long>(state_ptr[s + 1]) - state_ptr[s];
+    if (seg_T[s] < 1 || row_ld[s] < 1 || row_off[s] < 0 || S < 1 || S > fdnn::align::kMaxStates || (rows += seg_T[s]) > INT32_MAX)
+      return fail(FDNN_E_ARG, "align, segment " + std::to_string(s) + ": a segment has T >= 1 rows of stride >= 1 at an offset >= 0 and 1 .. " +
+                                  std::to_string(fdnn::align::kMaxStates) + " states");
+  }
+  return FDNN_OK;
+}
+
+int fdnn_align_scratch_words(const int32_t *seg_T, const int32_t *state_ptr, int n_segs, long long *words) {
+  if (!words) return fail(FDNN_E_ARG, "null argument");
+  const std::vector<long long> off(size_t(std::max(n_segs, 0)), 0);
+  const std::vector<int32_t> ld(size_t(std::max(n_segs, 0)), 1);
+  if (int rc = align_rows_tables(seg_T, off.data(), ld.data(), state_ptr, n_segs)) return rc;
+  *words = fdnn::align::plan(seg_T, off.data(), ld.data(), state_ptr, n_segs, fdnn::align_kernel_mode()).scratch_words;
+  return FDNN_OK;
+}
+
+int fdnn_align_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                           const int32_t *state_ptr, int n_segs, const int32_t *d_col, const int32_t *d_state_node, const float *d_self_lp,
+                           const float *d_next_lp, void *d_scratch, long long scratch_words, int32_t *d_path, float *d_total, void *stream) {
+  if (int rc = align_rows_tables(seg_T, row_off, row_ld, state_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  if (!d_rows || !d_col || !d_path || !d_total || (ll && !d_state_node)) return fail(FDNN_E_ARG, "null buffer");
+  const uintptr_t all = reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_col) | reinterpret_cast<uintptr_t>(d_state_node) |
+                        reinterpret_cast<uintptr_t>(d_self_lp) | reinterpret_cast<uintptr_t>(d_next_lp) | reinterpret_cast<uintptr_t>(d_path) |
+                        reinterpret_cast<uintptr_t>(d_total);
+  if ((all & 3) || (reinterpret_cast<uintptr_t>(d_scratch) & 7)) return fail(FDNN_E_ARG, "buffers must have their elements' alignment, the scratch 8 bytes");
+  const fdnn::align::Plan p = fdnn::align::plan(seg_T, row_off, row_ld, state_ptr, n_segs, fdnn::align_kernel_mode());
+  if (p.scratch_words * 4 > fdnn::align::kMaxScratchBytes)
+    return fail(FDNN_E_ARG, "align: the back-pointer words of the call are above " + std::to_string(fdnn::align::kMaxScratchBytes) + " bytes");
+  if (p.scratch_words > 0 && (!d_scratch || scratch_words < p.scratch_words))
+    return fail(FDNN_E_ARG, "align: the call needs " + std::to_string(p.scratch_words) + " scratch words (fdnn_align_scratch_words)");
+  fdnn::AlignArgs a;
+  a.d_rows = d_rows, a.d_col = d_col, a.d_state_node = d_state_node, a.d_self_lp = d_self_lp, a.d_next_lp = d_next_lp;
+  a.d_scratch = static_cast<uint32_t *>(d_scratch), a.d_path = d_path, a.d_total = d_total;
+  if (ll) a.d_log_prior = ll->d_log_prior, a.width = ll->width, a.floor = ll->floor, a.type = ll->type;
+  int dev = 0;
+  if (ll) dev = ll->device;
+  else if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  DeviceGuard g(dev);
+  fdnn::launch_align(p, a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+// The front of every align call through a model: the handle, then the tables (align_prepare names the first bad segment)
+static int align_front(const fdnn_model *m, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                       const float *self_lp, const float *next_lp, int ctx_rows, fdnn::AlignJob *j) {
+  if (int rc = fdnn::check_loglik(m, ll)) return rc;
+  if (n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
+  j->ll = ll, j->seg_rows = seg_rows, j->state_ptr = state_ptr, j->states = states, j->self_lp = self_lp, j->next_lp = next_lp, j->n_segs = n_segs;
+  return fdnn::align_prepare(j, m->hm.hdr.out_dim, ctx_rows);
+}
+
+static int ctx_align(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                     const float *self_lp, const float *next_lp, int32_t *path, float *total, bool host, hipStream_t s) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  fdnn::AlignJob j;
+  if (int rc = align_front(c->m, ll, seg_rows, state_ptr, n_segs, states, self_lp, next_lp, c->n, &j)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  if (!path || !total) return fail(FDNN_E_ARG, "null result buffer");
+  const std::vector<sets::Seg> segs = sets::slice(j.tables(), seg_rows[0], seg_rows[n_segs]);
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  int rc = fdnn::align_stage(c, j, s);
+  SetsCall sc;
+  sc.first = seg_rows[0], sc.segs = &segs, sc.d_nodes = c->d_al_int, sc.d_probs = c->d_al_probs, sc.d_inactive = c->d_al_inact;
+  if (!rc) rc = run_sets(c, sc, s);
+  if (!rc) rc = fdnn::align_finish(c, j, path, total, host, s);
+  if (rc && host) hipStreamSynchronize(s);
+  return rc;
+}
+
+int fdnn_ctx_align(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                   const float *self_lp, const float *next_lp, int32_t *path, float *total) {
+  return ctx_align(c, ll, seg_rows, state_ptr, n_segs, states, self_lp, next_lp, path, total, true, c ? c->stream : nullptr);
+}
+
+int fdnn_ctx_align_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                          const float *self_lp, const float *next_lp, int32_t *d_path, float *d_total, void *stream) {
+  return ctx_align(c, ll, seg_rows, state_ptr, n_segs, states, self_lp, next_lp, d_path, d_total, false, static_cast<hipStream_t>(stream));
+}
+
+// One-call forms: hidden layers + the transcripts' sets chunk by chunk into the context's buffers (a segment cut by a chunk
+// keeps its set), the recursion ONCE behind the last chunk, inside the same use of the context.
+static int calculate_align(fdnn_model *m, const Pass &p, fdnn::AlignJob &j, int32_t *path, float *total, int n) {
+  return score_chunks(m, frame_chunks(n, m), p, nullptr, [&](fdnn_ctx *c, hipStream_t s) { return fdnn::align_stage(c, j, s); },
+                      [&](fdnn_ctx *c, hipStream_t s) {
+                        const int rc = fdnn::align_finish(c, j, path, total, true, s);
+                        if (rc) hipStreamSynchronize(s);
+                        return rc;
+                      });
+}
+
+int fdnn_calculate_align(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr,
+                         int n_segs, const int32_t *states, const float *self_lp, const float *next_lp, int32_t *path, float *total) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  fdnn::AlignJob j;
+  if (int rc = align_front(m, ll, seg_rows, state_ptr, n_segs, states, self_lp, next_lp, n, &j)) return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!x || !path || !total) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  const sets::Tables t = j.tables();
+  return calculate_align(m, Pass::host_align("fdnn_calculate_align", x, t), j, path, total, n);
+}
+
+int fdnn_calculate_align_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                             const int32_t *state_ptr, int n_segs, const int32_t *states, const float *self_lp, const float *next_lp, int32_t *path,
+                             float *total) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  if (int rc = fdnn::splice_check(spec, raw_dim)) return rc;
+  fdnn::AlignJob j;
+  if (int rc = align_front(m, ll, seg_rows, state_ptr, n_segs, states, self_lp, next_lp, n, &j)) return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!raw || !path || !total) return fail(FDNN_E_ARG, "null buffer");
+  // every segment is an utterance of its own: its edges repeat its own first and last frame
+  std::vector<SpliceSeg> segs;
+  for (int s = 0; s < n_segs; ++s) segs.push_back(SpliceSeg{seg_rows[s], seg_rows[s], seg_rows[s], seg_rows[s + 1] - 1});
+  const sets::Tables t = j.tables();
+  return calculate_align(m, Pass::raw_align("fdnn_calculate_align_raw", {spec.get(), &segs, raw, n}, t), j, path, total, n);
+}
+
+int fdnn_debug_align_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 2, fdnn::align_launch_counts); }
+
+int fdnn_debug_set_align_kernel(int mode) {
+  if (mode < 0 || mode > 2) return fail(FDNN_E_ARG, "mode is 0 (the plan's rule), 1 (the wave form where allowed) or 2 (the workgroup form)");
+  fdnn::align_kernel_mode(mode);
+  return FDNN_OK;
+}
+
+int fdnn_debug_align_limits(int *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  const int v[6] = {fdnn::align::kMaxStates, fdnn::align::kMaxSegs, fdnn::align::kWaveStates, fdnn::align::kFramesInFlight, fdnn::align::kBpLdsWords,
+                    int(fdnn::align::kMaxScratchBytes >> 20)};
+  for (int i = 0; i < 6 && i < cap; ++i) out[i] = v[i];
+  return 6;
+}
+
+// The recursion in plain C++ (fdnn_align.hpp: ref), no device: segment s = rows [T_s] of stride row_ld[s] at row_off[s].
+// type: FDNN_LOGLIK_F32 / _F16 with log_prior [width], floor and state_node, or -1: the rows are scores.
+int fdnn_debug_align_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr, int n_segs,
+                         const int32_t *col, const int32_t *state_node, const float *log_prior, int width, float floor, int type, const float *self_lp,
+                         const float *next_lp, int32_t *path, float *total) {
+  if (int rc = align_rows_tables(seg_T, row_off, row_ld, state_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  if (type != fdnn::align::kScores && (fdnn::loglik::check_handle(log_prior, width, floor, type) != 0 || !state_node))
+    return fail(FDNN_E_ARG, "log_prior [width] finite, the floor -inf or finite (F16: not below -65504), the type F32, F16 or -1 (scores)");
+  if (!rows || !col || !path || !total) return fail(FDNN_E_ARG, "null buffer");
+  size_t at = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const int b = state_ptr[s], S = state_ptr[s + 1] - b;
+    uint32_t tb;
+    fdnn::align::ref(reinterpret_cast<const uint32_t *>(rows) + row_off[s], seg_T[s], row_ld[s], col + b, state_node ? state_node + b : nullptr, S, log_prior,
+                     width, floor, type, self_lp ? self_lp + b : nullptr, next_lp ? next_lp + b : nullptr, path + at, &tb);
+    std::memcpy(total + s, &tb, 4);
+    at += size_t(seg_T[s]);
+  }
+  return FDNN_OK;
+}
+
+int fdnn_debug_align_sets(const int32_t *state_ptr, const int32_t *states, int n_segs, int32_t *set_ptr, int32_t *nodes, int32_t *col) {
+  if (n_segs < 0 || !state_ptr || !set_ptr || state_ptr[0] != 0) return fail(FDNN_E_ARG, "bad argument");
+  for (int s = 0; s < n_segs; ++s)
+    if (state_ptr[s + 1] < state_ptr[s]) return fail(FDNN_E_ARG, "state_ptr must not decrease");
+  if (n_segs && state_ptr[n_segs] > 0 && (!states || !nodes || !col)) return fail(FDNN_E_ARG, "null buffer");
+  const fdnn::align::Sets st = fdnn::align::build_sets(state_ptr, states, n_segs);
+  std::copy(st.set_ptr.begin(), st.set_ptr.end(), set_ptr);
+  std::copy(st.nodes.begin(), st.nodes.end(), nodes);  // (nodes holds state_ptr[n_segs] entries: a set is no longer than its transcript)
+  std::copy(st.col.begin(), st.col.end(), col);
+  return FDNN_OK;
+}
+
 int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
   if (!c || !out) return fail(FDNN_E_ARG, "null argument");
   if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -148,6 +149,13 @@ struct fdnn_ctx {
   fdnn::DevBuf<int32_t> d_topk;     // host top-k calls: [n][k] nodes, then [n][k] values (allocated on first use, fdnn_topk.hip)
   fdnn::DevBuf<float> d_pool;       // host pool calls: [n][C] class sums (allocated on first use, fdnn_pool.hip; not in ctx_layout)
   fdnn::DevBuf<uint32_t> d_loglik;  // host loglik calls: [n][O] scores, fp32 or fp16 (allocated on first use, fdnn_loglik.hip; not in ctx_layout)
+  // align calls (fdnn_align.hip; allocated on first use and grown by the largest call, not in ctx_layout): the transcripts'
+  // node sets, columns and nodes [n_nodes | n_states | n_states], their transition scores [n_states | n_states], the sets'
+  // probabilities (ragged blocks) and inactive values, the take words that do not fit LDS, and the results [sum T | n_segs]
+  fdnn::DevBuf<int32_t> d_al_int;
+  fdnn::DevBuf<float> d_al_lp, d_al_probs, d_al_inact;
+  fdnn::DevBuf<uint32_t> d_al_bp;
+  fdnn::DevBuf<int32_t> d_al_res;
   // host list calls (fdnn_ctx_lazy_output_lists, fdnn_calculate_lazy_lists): staging of the lists and their results,
   // allocated on the first list call and grown by the largest one
   fdnn::DevBuf<int32_t> d_lrow, d_lnodes;   // [count + 1], [nnz]
@@ -379,6 +387,31 @@ int group_calculate_raw(fdnn_group *g, const SpliceRef &spec, const float *raw, 
 int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *raw, int n, int a, int b, const uint64_t *bits,
                            float *out, uint64_t *ticket);
 
+// ---------------------------------------------------------------- forced alignment (fdnn_align.hip)
+// One align call's validated host tables and what is derived from them before anything is launched (align_prepare): the
+// transcripts' node sets and columns (align::build_sets), the sets call's tables over the call's rows and the launch plan.
+struct AlignJob {
+  const fdnn_loglik *ll = nullptr;
+  const int32_t *seg_rows = nullptr, *state_ptr = nullptr, *states = nullptr;
+  const float *self_lp = nullptr, *next_lp = nullptr;
+  int n_segs = 0;
+  align::Sets sets;
+  std::vector<int32_t> seg_T, row_ld;
+  std::vector<long long> row_off;  // segment s's block in the ragged probabilities
+  long long nnz = 0;
+  int rows = 0;                    // seg_rows[n_segs] - seg_rows[0]
+  align::Plan plan;
+  sets::Tables tables() const { return {seg_rows, sets.set_ptr.data(), n_segs}; }
+};
+// FDNN_E_ARG naming the first bad segment (align::check with need_path: T < S is refused), the sum of rows x len past an
+// int32 or the take words past align::kMaxScratchBytes; else fills j from its table pointers.  Nothing is launched.
+int align_prepare(AlignJob *j, int output_dim, int ctx_rows);
+// The context's align buffers made large enough and the tables uploaded on s (the host tables are read before it returns).
+int align_stage(fdnn_ctx *c, const AlignJob &j, hipStream_t s);
+// The recursion over the probabilities that the sets calls left in c->d_al_probs, then: host = true -- ONE transfer of path
+// [rows] and total [n_segs] and s synchronised; false -- both copied to the caller's device buffers on s.
+int align_finish(fdnn_ctx *c, const AlignJob &j, int32_t *path, float *total, bool host, hipStream_t s);
+
 // ---------------------------------------------------------------- one scoring pass, one chunk loop
 // Hidden layers + what the pass's sink asks for, chunk by chunk, on context c and stream s; every pointer a chunk uses comes
 // from pass::chunk_view.  Per chunk: the rows in (spliced / uploaded / as they are), host bits up, the hidden layers, the sink's
@@ -386,7 +419,11 @@ int server_submit_raw_rows(fdnn_server *s, const SpliceRef &spec, const float *r
 int run_chunks(fdnn_ctx *c, hipStream_t s, const pass::Chunks &chunks, const pass::Pass &p);
 // The pooled entry points: ONE pooled context, large enough for the largest chunk; the stream is the caller's where the
 // sink is on the device (pass::on_callers_stream), else the context's own; host raw frames travel once, before the loop.
-int score_chunks(fdnn_model *m, const pass::Chunks &chunks, const pass::Pass &p, hipStream_t callers = nullptr);
+// before / after: steps on the same context and stream inside the same use of it, ahead of the first chunk and behind the
+// last (the align calls: tables up, recursion and results down).
+using CtxStep = std::function<int(fdnn_ctx *, hipStream_t)>;
+int score_chunks(fdnn_model *m, const pass::Chunks &chunks, const pass::Pass &p, hipStream_t callers = nullptr, const CtxStep &before = {},
+                 const CtxStep &after = {});
 
 // Ordering between the streams a context is used on.  An event record costs 3-4 us of queue time behind the kernel it
 // follows, so a context whose work went to a stream that is certain to exist later -- its own, its owner's, or the null

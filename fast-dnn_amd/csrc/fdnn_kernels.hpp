@@ -14,6 +14,7 @@
 #include "fdnn_topk.hpp"
 #include "fdnn_pool.hpp"
 #include "fdnn_loglik.hpp"
+#include "fdnn_align.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -283,6 +284,28 @@ void launch_loglik_entries(const int32_t *d_nodes, const float *d_p, long long c
 void loglik_launch_counts(unsigned long long out[3]);  // launches so far: rows vector form, rows scalar form, entries
 int loglik_kernel_mode();                                // fdnn_debug_set_loglik_kernel: 0 the plan's rule, 1 vector where allowed, 2 scalar
 void loglik_kernel_mode(int mode);
+
+// Forced alignment (fdnn_align.hip; the emission, the step, the plan and the host restatement: fdnn_align.hpp): the launches
+// of a plan (align::plan over the call's host tables) over device-resident rows.  type: loglik::kF32 / kF16 -- the rows are
+// probabilities, d_state_node [states] and d_log_prior [width] make the scores -- or align::kScores -- the rows are scores,
+// d_state_node and d_log_prior are not read.  d_self_lp / d_next_lp may be null (+0).  d_scratch: p.scratch_words 32-bit
+// words on an 8-byte boundary (null when there are none).  d_path [sum of T] int32, d_total [n_segs].
+struct AlignArgs {
+  const float *d_rows = nullptr;
+  const int32_t *d_col = nullptr, *d_state_node = nullptr;
+  const float *d_log_prior = nullptr;
+  int width = 0;
+  float floor = 0.0f;
+  int type = align::kScores;
+  const float *d_self_lp = nullptr, *d_next_lp = nullptr;
+  uint32_t *d_scratch = nullptr;
+  int32_t *d_path = nullptr;
+  float *d_total = nullptr;
+};
+void launch_align(const align::Plan &p, const AlignArgs &a, hipStream_t s);
+void align_launch_counts(unsigned long long out[2]);  // launches so far: wave form, workgroup form
+int align_kernel_mode();                               // fdnn_debug_set_align_kernel: 0 the plan's rule, 1 wave where allowed, 2 workgroup
+void align_kernel_mode(int mode);
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

@@ -104,7 +104,9 @@ struct Sink {
     host_pool,         // every row's class sums under a node -> class map, [n][C], through dense_pass
     device_pool,       // the same into a device buffer; the rows stay in the context
     host_loglik,       // every row as decoder scores under a score handle, [n][O] fp32 or fp16, through dense_pass
-    device_loglik      // the same into a device buffer; the rows stay in the context
+    device_loglik,     // the same into a device buffer; the rows stay in the context
+    align_sets         // per-segment sets (tables covering [0, n)) into the CONTEXT's align buffers: nodes, probs and inactive
+                       // are the context's (fdnn_internal.hpp: d_al_*), the recursion runs behind the last chunk
   } kind = device_rows;
   float *rows = nullptr;
   int k = 0;
@@ -160,6 +162,8 @@ class Pass {
     s.len = len;
     return {who, rows_of(Rows::host, x), {}, s};
   }
+  static Pass host_align(const char *who, const float *x, const sets::Tables &t) { return {who, rows_of(Rows::host, x), {}, sets_to(Sink::align_sets, t, nullptr, nullptr, nullptr)}; }
+  static Pass raw_align(const char *who, const Raw &raw, const sets::Tables &t) { return {who, rows_of(Rows::raw_host, raw), {}, sets_to(Sink::align_sets, t, nullptr, nullptr, nullptr)}; }
   static Pass host_sets(const char *who, const float *x, const sets::Tables &t, const int32_t *nodes, float *probs, float *inactive) { return {who, rows_of(Rows::host, x), {}, sets_to(Sink::host_sets, t, nodes, probs, inactive)}; }
   // raw frames on the host
   static Pass raw_dense(const char *who, const Raw &raw, float *out) { return {who, rows_of(Rows::raw_host, raw), {}, rows_to(Sink::host_dense, out)}; }
@@ -231,6 +235,9 @@ inline ChunkView chunk_view(const Pass &p, const Dims &d, int off_, int cnt) {
     v.segs = sets::slice(to.sets, off_, off_ + cnt);
     v.nodes = to.nodes, v.n_nodes = to.sets.set_ptr[to.sets.n_segs];
     v.probs = to.probs + (v.segs.empty() ? 0 : size_t(v.segs[0].src_off));
+  } else if (to.kind == Sink::align_sets) {  // the bases are the context's: the driver adds the slice's src_off
+    v.segs = sets::slice(to.sets, off_, off_ + cnt);
+    v.n_nodes = to.sets.set_ptr[to.sets.n_segs];
   }
   return v;
 }

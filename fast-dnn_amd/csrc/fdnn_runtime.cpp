@@ -1019,6 +1019,18 @@ static int to_device_sets(fdnn_ctx *c, const float *d_x, const pass::ChunkView &
   return rc;
 }
 
+// align: the chunk's slice of the sets into the context's align buffers (align_stage has put the nodes there); the blocks of
+// a call's slices follow each other in d_al_probs as they do in a host caller's probs
+static int to_align_sets(fdnn_ctx *c, const pass::ChunkView &v, hipStream_t s) {
+  int rc = run_hidden(c, c->d_x, s, nullptr);
+  SetsCall sc;
+  sc.segs = &v.segs, sc.d_nodes = c->d_al_int, sc.d_inactive = c->d_al_inact;
+  sc.d_probs = c->d_al_probs.p + (v.segs.empty() ? 0 : size_t(v.segs[0].src_off));
+  if (!rc && !v.segs.empty()) rc = run_sets(c, sc, s);
+  if (rc) hipStreamSynchronize(s);
+  return rc;
+}
+
 int run_chunks(fdnn_ctx *c, hipStream_t s, const pass::Chunks &chunks, const pass::Pass &p) {
   using pass::Rows;
   using pass::Sink;
@@ -1050,13 +1062,14 @@ int run_chunks(fdnn_ctx *c, hipStream_t s, const pass::Chunks &chunks, const pas
       case Sink::device_pool: rc = to_device_pool(c, d_x, v, p.sink.pool, s); break;
       case Sink::host_loglik: rc = dense_pass(c, {.loglik = p.sink.loglik, .scores = v.scores}, s, true); break;  // n x O x 4 or 2 bytes cross PCIe
       case Sink::device_loglik: rc = to_device_loglik(c, d_x, v, p.sink.loglik, s); break;
+      case Sink::align_sets: rc = to_align_sets(c, v, s); break;
     }
     if (rc) return rc;
   }
   return FDNN_OK;
 }
 
-int score_chunks(fdnn_model *m, const pass::Chunks &chunks, const pass::Pass &p, hipStream_t callers) {
+int score_chunks(fdnn_model *m, const pass::Chunks &chunks, const pass::Pass &p, hipStream_t callers, const CtxStep &before, const CtxStep &after) {
   DeviceGuard g(m->device);
   int cap = 0;  // the scratch only has to hold the largest chunk
   for (const auto &ch : chunks) cap = std::max(cap, ch.second);
@@ -1073,7 +1086,72 @@ int score_chunks(fdnn_model *m, const pass::Chunks &chunks, const pass::Pass &p,
     e = hipMemcpyAsync(c->d_raw, raw.frames, sizeof(float) * size_t(raw.n_frames) * size_t(raw.spec->raw_dim), hipMemcpyHostToDevice, s);
   }
   if (e != hipSuccess) return fail(FDNN_E_DEVICE, std::string(p.who) + ": " + hipGetErrorString(e));
-  return run_chunks(c, s, chunks, p);
+  if (before)
+    if ((rc = before(c, s))) return rc;
+  rc = run_chunks(c, s, chunks, p);
+  if (!rc && after) rc = after(c, s);
+  return rc;
+}
+
+// ---------------------------------------------------------------- forced alignment (fdnn_align.hip)
+int align_prepare(AlignJob *j, int output_dim, int ctx_rows) {
+  align::Why why;
+  const int bad = align::check(j->seg_rows, j->state_ptr, j->states, j->self_lp, j->next_lp, j->n_segs, output_dim, ctx_rows, true, &why);
+  if (bad) return fail(FDNN_E_ARG, "align, segment " + std::to_string(-bad - 1) + ": " + align::why_text(why));
+  const int n = j->n_segs;
+  j->sets = align::build_sets(j->state_ptr, j->states, n);
+  j->seg_T.resize(size_t(n)), j->row_ld.resize(size_t(n)), j->row_off.resize(size_t(n));
+  j->nnz = 0;
+  for (int s = 0; s < n; ++s) {
+    j->seg_T[size_t(s)] = j->seg_rows[s + 1] - j->seg_rows[s];
+    j->row_ld[size_t(s)] = j->sets.set_ptr[size_t(s) + 1] - j->sets.set_ptr[size_t(s)];
+    j->row_off[size_t(s)] = j->nnz;
+    j->nnz += static_cast<long long>(j->seg_T[size_t(s)]) * j->row_ld[size_t(s)];
+    if (j->nnz > INT32_MAX) return fail(FDNN_E_ARG, "align, segment " + std::to_string(s) + ": the sum of rows x distinct nodes over the segments must fit an int32");
+  }
+  j->rows = n ? j->seg_rows[n] - j->seg_rows[0] : 0;
+  j->plan = align::plan(j->seg_T.data(), j->row_off.data(), j->row_ld.data(), j->state_ptr, n, align_kernel_mode());
+  if (j->plan.scratch_words * 4 > align::kMaxScratchBytes)
+    return fail(FDNN_E_ARG, "align: the back-pointer words of the call (" + std::to_string(j->plan.scratch_words * 4) + " bytes) are above " + std::to_string(align::kMaxScratchBytes));
+  return FDNN_OK;
+}
+
+int align_stage(fdnn_ctx *c, const AlignJob &j, hipStream_t s) {
+  const size_t n_nodes = j.sets.nodes.size(), n_states = j.sets.col.size();
+  HIP_TRY(c->d_al_int.reserve(n_nodes + 2 * n_states));
+  HIP_TRY(c->d_al_lp.reserve(2 * n_states));
+  HIP_TRY(c->d_al_probs.reserve(std::max<size_t>(size_t(j.nnz), 1)));
+  HIP_TRY(c->d_al_inact.reserve(std::max<size_t>(size_t(j.rows), 1)));
+  HIP_TRY(c->d_al_bp.reserve(std::max<size_t>(size_t(j.plan.scratch_words), 2)));
+  HIP_TRY(c->d_al_res.reserve(size_t(j.rows) + size_t(j.n_segs)));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int, j.sets.nodes.data(), sizeof(int32_t) * n_nodes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int.p + n_nodes, j.sets.col.data(), sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int.p + n_nodes + n_states, j.states, sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  if (j.self_lp) HIP_TRY(hipMemcpyAsync(c->d_al_lp, j.self_lp, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  if (j.next_lp) HIP_TRY(hipMemcpyAsync(c->d_al_lp.p + n_states, j.next_lp, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  return FDNN_OK;
+}
+
+int align_finish(fdnn_ctx *c, const AlignJob &j, int32_t *path, float *total, bool host, hipStream_t s) {
+  const size_t n_nodes = j.sets.nodes.size(), n_states = j.sets.col.size(), rows = size_t(j.rows), n = size_t(j.n_segs);
+  AlignArgs a;
+  a.d_rows = c->d_al_probs, a.d_col = c->d_al_int.p + n_nodes, a.d_state_node = c->d_al_int.p + n_nodes + n_states;
+  a.d_log_prior = j.ll->d_log_prior, a.width = j.ll->width, a.floor = j.ll->floor, a.type = j.ll->type;
+  a.d_self_lp = j.self_lp ? c->d_al_lp.p : nullptr, a.d_next_lp = j.next_lp ? c->d_al_lp.p + n_states : nullptr;
+  a.d_scratch = c->d_al_bp, a.d_path = c->d_al_res, a.d_total = reinterpret_cast<float *>(c->d_al_res.p + rows);
+  launch_align(j.plan, a, s);
+  HIP_TRY(hipGetLastError());
+  if (!host) {
+    HIP_TRY(hipMemcpyAsync(path, c->d_al_res, sizeof(int32_t) * rows, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(total, c->d_al_res.p + rows, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    return FDNN_OK;
+  }
+  std::vector<int32_t> land(rows + n);  // one transfer: 4 bytes a frame and 4 a segment
+  HIP_TRY(hipMemcpyAsync(land.data(), c->d_al_res, sizeof(int32_t) * (rows + n), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::memcpy(path, land.data(), sizeof(int32_t) * rows);
+  std::memcpy(total, land.data() + rows, sizeof(float) * n);
+  return FDNN_OK;
 }
 
 // The host half of a compacted lazy return (lazy_compact_kernel): a compacted row is the row's inactive value followed by

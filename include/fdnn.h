@@ -467,6 +467,73 @@ FDNN_API int fdnn_ctx_output_loglik_device(fdnn_ctx *c, const fdnn_loglik *ll, v
 FDNN_API int fdnn_calculate_loglik(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, void *out);
 FDNN_API int fdnn_calculate_loglik_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, void *out);
 FDNN_API int fdnn_calculate_loglik_device(fdnn_model *m, const float *d_x, int n, const fdnn_loglik *ll, void *d_out, void *stream);
+/* ------------------------------------------------------------------ forced alignment (fdnn_align.hip)
+ * The best monotone path of a transcript's states over an utterance's rows, and its score, on the DEVICE: what the lazy paths
+ * for per-utterance node sets were built for.  Instead of rows x len probabilities per utterance, 4 bytes per frame leave
+ * the device.  The reference has no such call; every entry below extends LazyOutputActivations (dnn.cc:355-392).
+ *
+ * A SEGMENT is one utterance: T >= 1 consecutive rows and a transcript states[0 .. S) of output-node numbers, 1 <= S <=
+ * 16384, each in [0, output_dim), in any order, repeats allowed.  Optional transition scores self_lp[0 .. S) and
+ * next_lp[0 .. S): next_lp[S - 1] is never read, every value that is read is finite, NULL is an array of +0.0f (the same
+ * bytes).  The tables of a call are host memory:
+ *   seg_rows  [n_segs + 1]  rising strictly; segment s = rows [seg_rows[s], seg_rows[s + 1])
+ *   state_ptr [n_segs + 1]  state_ptr[0] == 0; segment s's transcript = states[state_ptr[s] .. state_ptr[s + 1])
+ *   states, self_lp, next_lp [state_ptr[n_segs]]
+ *   path [seg_rows[n_segs] - seg_rows[0]] int32 in row order, total [n_segs] float
+ * The emission of state j in row t is what fdnn_loglik_entries_device returns for (states[j], p), p the lazy-contract
+ * probability of that node in that row under the segment's node set -- the transcript's distinct nodes, ascending:
+ *   e(t, j) = score(p, log_prior[states[j]], floor); an F16 handle's value is rounded to fp16 and widened exactly.
+ * The recursion, in fp32, every + rounded once, nothing contracted (fdnn_align.hpp):
+ *   d[0][0] = e(0, 0);   d[0][j] = -inf for j > 0
+ *   stay = d[t-1][j] + self_lp[j];   move = d[t-1][j-1] + next_lp[j-1]   (j = 0: -inf)
+ *   take = move > stay               (false on a tie and for a NaN on either side: stay)
+ *   d[t][j] = (take ? move : stay) + e(t, j);   total = d[T-1][S-1]
+ *   path: j = S-1; for t = T-1 .. 1: path[t] = j; if take[t][j]: j -= 1;  path[0] = j
+ * Total not finite (-inf: T < S or no path with a finite score; +inf; a NaN): every element of path is -1; a NaN total is
+ * 0x7fc00000.  Otherwise path[0] = 0, path[T-1] = S-1 and steps are 0 or 1.  Among paths of equal score the one whose moves
+ * come earliest is returned.  Additions and comparisons only: path and total are a function of the scores and the transcript
+ * alone -- not of the kernel form, the chunking or the entry point -- and equal fdnn_debug_align_ref byte for byte.
+ * FDNN_E_ARG before anything is launched, naming the first bad segment: malformed tables, a node outside [0, output_dim), a
+ * transcript without or with more than 16384 states, T < S (host-table forms), a transition score that is read and is not
+ * finite, a handle whose width or device is not the model's, a model that leads a device group, back-pointer words of one
+ * call above 2^30 bytes.  FDNN_E_STATE before the hidden layers have run.  The batcher, the scoring loop, device groups and
+ * the JNI shim neither route to nor look at these entry points, and every other entry point keeps its bytes.
+ *
+ * fdnn_align_rows_device   the recursion alone on any device-resident fp32 rows (dnn.cc:355-392): segment s has seg_T[s]
+ *   rows of stride row_ld[s] elements beginning row_off[s] elements into d_rows (host tables); state j of the call reads
+ *   column d_col[j] of its segment's rows.  With ll == NULL the rows are scores already, e(t, j) = rows[t ld + col[j]], and
+ *   d_state_node is not read; with a handle they are probabilities and d_state_node[j] names the prior.  A column outside
+ *   [0, row_ld) or a node outside [0, W) gives a NaN emission and reads nothing: the total is a NaN (the last state's) or
+ *   -inf (the move out of a NaN is never taken), the path -1 everywhere.  T < S is not refused here: -1 everywhere, total -inf.  d_self_lp / d_next_lp may be NULL.  d_scratch: at least the 32-bit words fdnn_align_scratch_words names
+ *   for the same tables, on an 8-byte boundary (NULL when 0); its contents mean nothing before or after.  d_path [sum T],
+ *   d_total [n_segs].  Enqueued on `stream`, not synchronised.
+ * fdnn_align_scratch_words the scratch of that call: the back-pointer words of the segments that do not fit LDS
+ *   (dnn.cc:355-392).
+ * fdnn_ctx_align           host tables and host results, host-synchronous, over rows of a context whose hidden layers have
+ *   run (dnn.cc:355-392): the transcripts' node sets, fdnn_ctx_lazy_output_sets' computation into a context-owned device
+ *   buffer, the recursion, then ONE transfer of path and total.  Works unchanged on fdnn_stream_ctx(s) after a hidden-only
+ *   push.
+ * fdnn_ctx_align_device    the same with device result buffers, enqueued on `stream`; the host tables are read before it
+ *   returns (dnn.cc:355-392).
+ * fdnn_calculate_align     one call on a pooled context (dnn.cc:355-392): seg_rows must cover [0, n); a large n goes chunk
+ *   by chunk (fdnn_debug_frame_chunks) like fdnn_calculate_lazy_sets, a segment cut by a chunk keeps its set, the chunks'
+ *   probabilities stay on the device and the recursion runs ONCE behind the last chunk: a cut segment's path is the uncut one.
+ * fdnn_calculate_align_raw the same from raw feature frames [n][raw_dim] (dnn.cc:355-392); every segment is an utterance of
+ *   its own: its edge rows repeat its own first and last frame. */
+FDNN_API int fdnn_align_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                                    const int32_t *state_ptr, int n_segs, const int32_t *d_col, const int32_t *d_state_node, const float *d_self_lp,
+                                    const float *d_next_lp, void *d_scratch, long long scratch_words, int32_t *d_path, float *d_total, void *stream);
+FDNN_API int fdnn_align_scratch_words(const int32_t *seg_T, const int32_t *state_ptr, int n_segs, long long *words);
+FDNN_API int fdnn_ctx_align(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                            const float *self_lp, const float *next_lp, int32_t *path, float *total);
+FDNN_API int fdnn_ctx_align_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                   const int32_t *states, const float *self_lp, const float *next_lp, int32_t *d_path, float *d_total, void *stream);
+FDNN_API int fdnn_calculate_align(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                  const int32_t *state_ptr, int n_segs, const int32_t *states, const float *self_lp, const float *next_lp,
+                                  int32_t *path, float *total);
+FDNN_API int fdnn_calculate_align_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                      const int32_t *state_ptr, int n_segs, const int32_t *states, const float *self_lp, const float *next_lp,
+                                      int32_t *path, float *total);
 /* Last hidden layer's u8 activations, n x hidden_dim (quantized_activations_). */
 FDNN_API int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out);
 
@@ -835,6 +902,28 @@ FDNN_API int fdnn_debug_set_loglik_kernel(int mode);
 FDNN_API int fdnn_debug_loglik_ref(const float *rows, int n, const float *log_prior, int width, float floor, int type, void *out);
 FDNN_API int fdnn_debug_loglik_entries_ref(const int32_t *nodes, const float *p, long long count, const float *log_prior, int width, float floor, int type, void *out);
 FDNN_API int fdnn_debug_ln_ref(const float *x, long long count, float *out);
+
+/* Forced alignment (LazyOutputActivations, dnn.cc:355-392), tests and tools.
+ * fdnn_debug_align_launches    process-wide counts since load, returns 2: out[0] launches of the wave form, [1] of the
+ *   workgroup form.  Not in the launch recorder's table (fdnn_note.hpp).
+ * fdnn_debug_set_align_kernel  process-wide: 0 the plan's rule (one wave per segment where S <= 1024, else 256 threads), 1 the
+ *   wave form where allowed, 2 always the workgroup form -- the same bytes either way (dnn.cc:355-392).
+ * fdnn_debug_align_limits      returns 6: out[0] the longest transcript, [1] segments per launch, [2] the wave form's longest
+ *   transcript, [3] rows in flight, [4] the back-pointer words of a segment that stay in LDS, [5] the scratch cap of a call
+ *   in MiB (dnn.cc:355-392).
+ * fdnn_debug_align_ref         fdnn_align_rows_device from the host restatement (fdnn_align.hpp) on host rows and host
+ *   col / state_node / transition arrays; type FDNN_LOGLIK_F32 / _F16 with log_prior [width] and floor, or -1: the rows are
+ *   scores and state_node, log_prior are not read; host code, no device needed (dnn.cc:355-392).
+ * fdnn_debug_align_sets        the transcripts' node sets as the align calls build them: set_ptr [n_segs + 1], nodes (room
+ *   for state_ptr[n_segs]) -- each segment's distinct nodes, ascending, the form fdnn_calculate_lazy_sets takes -- and col
+ *   [state_ptr[n_segs]], nodes[set_ptr[s] + col[j]] == states[j]; host code (dnn.cc:355-392). */
+FDNN_API int fdnn_debug_align_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_set_align_kernel(int mode);
+FDNN_API int fdnn_debug_align_limits(int *out, int cap);
+FDNN_API int fdnn_debug_align_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr,
+                                  int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior, int width, float floor, int type,
+                                  const float *self_lp, const float *next_lp, int32_t *path, float *total);
+FDNN_API int fdnn_debug_align_sets(const int32_t *state_ptr, const int32_t *states, int n_segs, int32_t *set_ptr, int32_t *nodes, int32_t *col);
 
 /* Splicing through a segment table in device memory (the scoring loop's live batches, fdnn_splice.hip), tests and tools.
  * fdnn_debug_splice_table   the splice alone, host in and host out: raw [raw_frames][raw_dim] -> x [rows][input_dim] under the
