@@ -208,6 +208,23 @@ SIGNATURES = {
     "fdnn_debug_align_ref": (C.c_int, [_c_f32p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, C.c_int, C.c_float,
                                        C.c_int, _c_f32p, _c_f32p, _c_i32p, _c_f32p]),
     "fdnn_debug_align_sets": (C.c_int, [_c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p]),
+    "fdnn_align_graph_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, _c_i32p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_align_graph_scratch_words": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.POINTER(C.c_longlong)]),
+    "fdnn_ctx_align_graph": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_i32p,
+                                       _c_f32p]),
+    "fdnn_ctx_align_graph_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_align_graph": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p,
+                                             _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_f32p]),
+    "fdnn_calculate_align_graph_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p,
+                                                 _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_f32p]),
+    "fdnn_debug_align_graph_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_set_align_graph_kernel": (C.c_int, [C.c_int]),
+    "fdnn_debug_align_graph_limits": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "fdnn_debug_align_graph_ref": (C.c_int, [_c_f32p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, C.c_int,
+                                             C.c_float, C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_f32p]),
     "fdnn_debug_ln_ref": (C.c_int, [_c_f32p, C.c_longlong, _c_f32p]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -892,6 +909,212 @@ def align_limits() -> dict:
     return dict(zip(("max_states", "segs_per_launch", "wave_states", "frames_in_flight", "lds_bp_words", "scratch_cap_mib"), (int(v) for v in buf)))
 
 
+# ---------------------------------------------------------------- alignment graphs (fdnn_align_graph.hip)
+# A GRAPH is a dict of one segment's tables: states [S] (output nodes), arc_ptr [S + 1] from 0, arc_src / arc_lp [arcs] (the
+# sources are state indices of the graph), start_lp / final_lp [S] or None (state 0 / state S - 1).  pack_graphs makes a call's
+# tables of several: a dict with statePtr, states, arcPtr (global), arcSrc (local), arcLp, startLp, finalLp.
+def _ip(a):
+    """An int32 array's pointer, or NULL for None."""
+    return None if a is None else a.ctypes.data_as(_c_i32p)
+
+
+def chain_graph(states, self_lp=None, next_lp=None) -> dict:
+    """The chain of ``calculateAlign`` as a graph: state j is entered from j (self_lp[j], listed first) and from j - 1
+    (next_lp[j - 1]); state 0 has the self-loop alone; None scores are +0; start and final are the defaults (state 0, state
+    S - 1).  On emissions that are neither a NaN nor +inf it gives ``calculateAlign``'s bytes."""
+    st = np.ascontiguousarray(states, dtype=np.int32).ravel()
+    S = st.size
+    if S < 1:
+        raise ValueError("a chain has at least one state")
+    sl = np.zeros(S, np.float32) if self_lp is None else np.ascontiguousarray(self_lp, dtype=np.float32).ravel()
+    nl = np.zeros(S, np.float32) if next_lp is None else np.ascontiguousarray(next_lp, dtype=np.float32).ravel()
+    if sl.size != S or nl.size != S:
+        raise ValueError("self_lp and next_lp are [states]")
+    j = np.arange(S, dtype=np.int32)
+    src = np.concatenate([[0], np.stack([j[1:], j[1:] - 1], axis=1).ravel()]).astype(np.int32)
+    lp = np.concatenate([sl[:1], np.stack([sl[1:], nl[:-1]], axis=1).ravel()]).astype(np.float32)
+    ptr = np.concatenate([[0], 1 + 2 * j]).astype(np.int32)
+    return dict(states=st, arc_ptr=ptr, arc_src=src, arc_lp=lp, start_lp=None, final_lp=None)
+
+
+def optional_silence_graph(words, sil_node: int, self_lp: float = 0.0, next_lp: float = 0.0, sil_self_lp: float = 0.0, enter_sil_lp: float = 0.0,
+                           leave_sil_lp: float = 0.0, skip_sil_lp: float = 0.0) -> dict:
+    """A transcript with OPTIONAL silence: ``words`` is a list of node lists, one chain each; there is one silence state (node
+    ``sil_node``) before each word and one after the last.  State order: sil, word 0's states, sil, word 1's states, .., sil.
+    Every state has a self-loop, listed first.  Inside a word state j is entered from j - 1.  A word's first state is
+    entered from the previous word's last state (skip_sil_lp, listed before the silence) and from the silence before it
+    (leave_sil_lp); a silence is entered from the last state of the word before it (enter_sil_lp); the leading silence has its
+    self-loop alone.  The path starts in the leading silence or the first word's first state and ends in the last word's last
+    state or the trailing silence (start and final values +0 there, -inf elsewhere)."""
+    if not len(words) or any(not len(w) for w in words):
+        raise ValueError("words is a non-empty list of non-empty node lists")
+    states, ptr, src, lp = [], [0], [], []
+    prev_last = -1  # the last state of the previous word
+    for w in words:
+        sil = len(states)
+        states.append(int(sil_node))
+        src.append(sil), lp.append(sil_self_lp)
+        if prev_last >= 0:
+            src.append(prev_last), lp.append(enter_sil_lp)
+        ptr.append(len(src))
+        for i, node in enumerate(w):
+            j = len(states)
+            states.append(int(node))
+            src.append(j), lp.append(self_lp)
+            if i:
+                src.append(j - 1), lp.append(next_lp)
+            else:
+                if prev_last >= 0:
+                    src.append(prev_last), lp.append(skip_sil_lp)
+                src.append(sil), lp.append(leave_sil_lp)
+            ptr.append(len(src))
+        prev_last = len(states) - 1
+    sil = len(states)
+    states.append(int(sil_node))
+    src.extend([sil, prev_last]), lp.extend([sil_self_lp, enter_sil_lp])
+    ptr.append(len(src))
+    S = len(states)
+    start = np.full(S, -np.inf, np.float32)
+    final = np.full(S, -np.inf, np.float32)
+    start[[0, 1]] = 0.0
+    final[[S - 2, S - 1]] = 0.0
+    return dict(states=np.array(states, np.int32), arc_ptr=np.array(ptr, np.int32), arc_src=np.array(src, np.int32), arc_lp=np.array(lp, np.float32),
+                start_lp=start, final_lp=final)
+
+
+def pack_graphs(graphs) -> dict:
+    """A call's tables from a list of graphs: statePtr [segments + 1], states, arcPtr [states + 1] GLOBAL (from 0, running
+    over the segments), arcSrc LOCAL to each segment, arcLp, and startLp / finalLp [states] -- None when every graph has
+    None, else the defaults (state 0 / the last state) written out where a graph has None."""
+    sp, ap, st, src, lp, start, final = [0], [0], [], [], [], [], []
+    any_start = any(g.get("start_lp") is not None for g in graphs)
+    any_final = any(g.get("final_lp") is not None for g in graphs)
+    for g in graphs:
+        s = np.ascontiguousarray(g["states"], dtype=np.int32).ravel()
+        p = np.ascontiguousarray(g["arc_ptr"], dtype=np.int64).ravel()
+        if p.size != s.size + 1 or p[0] != 0:
+            raise ValueError("a graph's arc_ptr is [states + 1] and begins at 0")
+        st.append(s), sp.append(sp[-1] + s.size)
+        ap.extend((ap[-1] + p[1:]).tolist())
+        src.append(np.ascontiguousarray(g["arc_src"], dtype=np.int32).ravel())
+        lp.append(np.ascontiguousarray(g["arc_lp"], dtype=np.float32).ravel())
+        if src[-1].size != p[-1] or lp[-1].size != p[-1]:
+            raise ValueError("a graph's arc_src and arc_lp are [arc_ptr[-1]]")
+        for out, key, at in ((start, "start_lp", 0), (final, "final_lp", s.size - 1)):
+            v = g.get(key)
+            if v is None:
+                v = np.full(s.size, -np.inf, np.float32)
+                v[at] = 0.0
+            v = np.ascontiguousarray(v, dtype=np.float32).ravel()
+            if v.size != s.size:
+                raise ValueError("a graph's start_lp and final_lp are [states]")
+            out.append(v)
+    cat = lambda parts, t: np.concatenate(parts).astype(t) if parts else np.zeros(0, t)
+    return dict(statePtr=np.array(sp, np.int32), states=cat(st, np.int32), arcPtr=np.array(ap, np.int32), arcSrc=cat(src, np.int32),
+                arcLp=cat(lp, np.float32), startLp=cat(start, np.float32) if any_start else None, finalLp=cat(final, np.float32) if any_final else None)
+
+
+def _graph_tables(g):
+    """A packed call's tables as C-contiguous vectors, shapes checked -> (sp, st, ap, src, lp, start, final)."""
+    sp = np.ascontiguousarray(g["statePtr"], dtype=np.int32)
+    st = np.ascontiguousarray(g["states"], dtype=np.int32)
+    ap = np.ascontiguousarray(g["arcPtr"], dtype=np.int32)
+    src = np.ascontiguousarray(g["arcSrc"], dtype=np.int32)
+    lp = np.ascontiguousarray(g["arcLp"], dtype=np.float32)
+    if sp.ndim != 1 or sp.size < 1 or st.ndim != 1 or int(sp.max()) > st.size or ap.shape != (st.size + 1,):
+        raise ValueError("statePtr must be [segments + 1], states [statePtr[-1]] and arcPtr [states + 1]")
+    if src.ndim != 1 or lp.shape != src.shape or (ap.size and int(ap.max()) > src.size):
+        raise ValueError("arcSrc and arcLp are [arcPtr[-1]]")
+    ends = []
+    for key in ("startLp", "finalLp"):
+        v = g.get(key)
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.float32)
+            if v.shape != st.shape:
+                raise ValueError("startLp and finalLp are [states]")
+        ends.append(v)
+    return sp, st, ap, src, lp, ends[0], ends[1]
+
+
+def _graph_call_tables(segRows, g):
+    sr = np.ascontiguousarray(segRows, dtype=np.int32)
+    sp, st, ap, src, lp, start, final = _graph_tables(g)
+    if sr.ndim != 1 or sr.size != sp.size:
+        raise ValueError("segRows and statePtr must be [segments + 1]")
+    return sr, sp, st, ap, src, lp, start, final, sr.size - 1, max(int(sr[-1]) - int(sr[0]), 0)
+
+
+def align_graph_ref(rows, segT, rowOff, rowLd, graphs, col, stateNode=None, log_prior=None, floor: float = -np.inf, type: int = ALIGN_SCORES):
+    """The graph recursion from the host restatement (``fdnn_debug_align_graph_ref``; host code, no device): rows, segT, rowOff,
+    rowLd, col, stateNode, log_prior, floor and type as ``align_ref``; ``graphs`` a packed call (``pack_graphs``; its states
+    are not read: col and stateNode say what a state reads) -> (path int32 [sum segT], total float32 [segments])."""
+    r = np.ascontiguousarray(rows, dtype=np.float32).ravel()
+    sp, _, ap, src, alp, start, final = _graph_tables(graphs)
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, sp)
+    c = np.ascontiguousarray(col, dtype=np.int32)
+    nd = None if stateNode is None else np.ascontiguousarray(stateNode, dtype=np.int32)
+    lp = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float32)
+    if t.size and ((off + (t.astype(np.int64) - 1) * ld + ld > r.size).any() or (off < 0).any() or c.size < int(sp[-1])):
+        raise ValueError("a segment's rows run past the rows, or col is shorter than the graphs")
+    path = np.empty(int(t.astype(np.int64).sum()), np.int32)
+    total = np.empty(t.size, np.float32)
+    _check(lib().fdnn_debug_align_graph_ref(r.ctypes.data_as(_c_f32p), t.ctypes.data_as(_c_i32p), off.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                            ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, c.ctypes.data_as(_c_i32p), _ip(nd), _fp(lp),
+                                            0 if lp is None else lp.size, C.c_float(float(floor)), int(type), _ip(ap), _ip(src), _fp(alp), _fp(start),
+                                            _fp(final), path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
+    return path, total
+
+
+def align_graph_scratch_words(segT, statePtr) -> int:
+    """The 32-bit scratch words ``align_graph_rows_device`` needs for these tables under the current kernel mode
+    (``fdnn_align_graph_scratch_words``): the back-pointers of the segments whose do not fit LDS."""
+    t = np.ascontiguousarray(segT, dtype=np.int32)
+    sp = np.ascontiguousarray(statePtr, dtype=np.int32)
+    words = C.c_longlong(0)
+    _check(lib().fdnn_align_graph_scratch_words(t.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, C.byref(words)))
+    return int(words.value)
+
+
+def align_graph_rows_device(ll, d_rows: int, segT, rowOff, rowLd, statePtr, arcPtr, d_col: int, d_state_node: int, d_arc_ptr: int, d_arc_src: int,
+                            d_arc_lp: int, d_start_lp: int, d_final_lp: int, d_scratch: int, scratch_words: int, d_path: int, d_total: int,
+                            stream: int = 0) -> None:
+    """The graph recursion alone on device-resident fp32 rows (``fdnn_align_graph_rows_device``): host tables segT, rowOff,
+    rowLd, statePtr and arcPtr, device pointers for everything they index (0 for NULL start / final values); ``ll`` a
+    ``Loglik`` or None (the rows are scores).  Enqueued on ``stream``, not synchronised."""
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, statePtr)
+    ap = np.ascontiguousarray(arcPtr, dtype=np.int32)
+    if ap.shape != (int(sp[-1]) + 1,):
+        raise ValueError("arcPtr must be [states + 1]")
+    _check(lib().fdnn_align_graph_rows_device(None if ll is None else ll.handle, C.c_void_p(d_rows), t.ctypes.data_as(_c_i32p),
+                                              off.ctypes.data_as(C.POINTER(C.c_longlong)), ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p),
+                                              ap.ctypes.data_as(_c_i32p), t.size, C.c_void_p(d_col), C.c_void_p(d_state_node), C.c_void_p(d_arc_ptr),
+                                              C.c_void_p(d_arc_src), C.c_void_p(d_arc_lp), C.c_void_p(d_start_lp), C.c_void_p(d_final_lp),
+                                              C.c_void_p(d_scratch), int(scratch_words), C.c_void_p(d_path), C.c_void_p(d_total), C.c_void_p(stream)))
+
+
+def align_graph_launches():
+    """Process-wide counts since load: (launches of the align-graph kernel's wave form, of its workgroup form)."""
+    buf = (C.c_ulonglong * 2)()
+    if lib().fdnn_debug_align_graph_launches(buf, 2) != 2:
+        raise RuntimeError("fdnn_debug_align_graph_launches")
+    return tuple(int(v) for v in buf)
+
+
+def set_align_graph_kernel(mode: int) -> None:
+    """Process-wide (``fdnn_debug_set_align_graph_kernel``): 0 the plan's rule (the wave form up to 64 states), 1 the wave form
+    where allowed (up to 256), 2 always the workgroup form."""
+    _check(lib().fdnn_debug_set_align_graph_kernel(int(mode)))
+
+
+def align_graph_limits() -> dict:
+    """The align-graph kernels' limits as built (``fdnn_debug_align_graph_limits``)."""
+    buf = (C.c_int * 8)()
+    if lib().fdnn_debug_align_graph_limits(buf, 8) != 8:
+        raise RuntimeError("fdnn_debug_align_graph_limits")
+    return dict(zip(("max_states", "segs_per_launch", "wave_states", "max_arcs", "lds_arcs", "lds_bp_words", "scratch_cap_mib", "wave_rule_states"),
+                    (int(v) for v in buf)))
+
+
 def _loglik_out(n: int, ll: "Loglik", out):
     """The [n][width] result array of a loglik call, made or checked."""
     shape = (n, ll.width())
@@ -1131,6 +1354,23 @@ class LazyContext:
         sr, sp, st, sl, nl, n_segs, _ = _align_tables(segRows, statePtr, states, selfLp, nextLp)
         _check(lib().fdnn_ctx_align_device(self.handle, ll.handle, sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs,
                                            st.ctypes.data_as(_c_i32p), _fp(sl), _fp(nl), C.c_void_p(d_path), C.c_void_p(d_total), C.c_void_p(stream)))
+
+    def alignGraph(self, ll: "Loglik", segRows, graphs):
+        """The best path over alignment graphs, over rows of the context (``fdnn_ctx_align_graph``): segment s = rows
+        [segRows[s], segRows[s + 1]) with graph s of the packed call ``graphs`` (``pack_graphs``) -> (path int32 [rows], total
+        float32 [segments]); a segment without a finite total has -1 everywhere."""
+        sr, sp, st, ap, src, lp, start, final, n_segs, rows = _graph_call_tables(segRows, graphs)
+        path = np.empty(rows, np.int32)
+        total = np.empty(n_segs, np.float32)
+        _check(lib().fdnn_ctx_align_graph(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                          path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
+        return path, total
+
+    def alignGraphDevice(self, ll: "Loglik", segRows, graphs, d_path: int, d_total: int, stream: int = 0) -> None:
+        """The same with device result buffers, enqueued on ``stream`` and not synchronised (``fdnn_ctx_align_graph_device``)."""
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        _check(lib().fdnn_ctx_align_graph_device(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start),
+                                                 _fp(final), C.c_void_p(d_path), C.c_void_p(d_total), C.c_void_p(stream)))
 
     def calculateOutputLoglikDevice(self, ll: "Loglik", d_out: int, stream: int = 0) -> None:
         """The same into a device buffer [frames][outputDimension] of the handle's type, enqueued on ``stream``, not
@@ -1930,6 +2170,37 @@ class QuantizedDnn:
         _check(lib().fdnn_calculate_align_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], ll.handle,
                                               sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), n_segs, st.ctypes.data_as(_c_i32p), _fp(sl), _fp(nl),
                                               path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
+        return path, total
+
+    def calculateAlignGraph(self, input, ll: "Loglik", segRows, graphs):
+        """The best path over alignment graphs in one call (``fdnn_calculate_align_graph``; segRows must cover [0, frames)):
+        hidden layers, the graphs' node sets, the recursion on the device -> (path int32 [frames], total float32 [segments]),
+        as ``LazyContext.alignGraph``.  ``graphs`` is a packed call (``pack_graphs`` over ``chain_graph`` /
+        ``optional_silence_graph`` / hand-written graphs)."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        path = np.empty(n, np.int32)
+        total = np.empty(n_segs, np.float32)
+        _check(lib().fdnn_calculate_align_graph(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(), ll.handle,
+                                                _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                                path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
+        return path, total
+
+    def calculateAlignGraphRaw(self, raw, ll: "Loglik", segRows, graphs):
+        """``calculateAlignGraph`` on raw frames [n][rawDim], spliced on the device, every segment an utterance of its own
+        (``fdnn_calculate_align_graph_raw``)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError("raw must be [frames][rawDim]")
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        path = np.empty(r.shape[0], np.int32)
+        total = np.empty(n_segs, np.float32)
+        _check(lib().fdnn_calculate_align_graph_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], ll.handle, _ip(sr), _ip(sp),
+                                                    n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                                    path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
         return path, total
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:

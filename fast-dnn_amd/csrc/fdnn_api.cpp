@@ -1206,6 +1206,202 @@ int fdnn_debug_align_sets(const int32_t *state_ptr, const int32_t *states, int n
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- alignment graphs (fdnn_align_graph.hip)
+// The recursion alone.  The tables are host memory and are checked (the plan is made from them, and its arc counts bound
+// every arc index on the device); what they index is on the device and is not: a source, column or node out of range gives a
+// NaN, which is never taken.
+static int align_graph_rows_tables(const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr, const int32_t *arc_ptr,
+                                   int n_segs) {
+  if (int rc = align_rows_tables(seg_T, row_off, row_ld, state_ptr, n_segs)) return rc;
+  if (n_segs == 0 || !arc_ptr) return FDNN_OK;  // (fdnn_align_graph_scratch_words: the scratch does not depend on the arcs)
+  if (arc_ptr[0] != 0) return fail(FDNN_E_ARG, "align graph, segment 0: arc_ptr begins at 0");
+  for (int s = 0; s < n_segs; ++s) {
+    for (int i = state_ptr[s]; i < state_ptr[s + 1]; ++i)
+      if (arc_ptr[i + 1] < arc_ptr[i]) return fail(FDNN_E_ARG, "align graph, segment " + std::to_string(s) + ": arc_ptr must not decrease");
+    if (arc_ptr[state_ptr[s + 1]] - arc_ptr[state_ptr[s]] > fdnn::align_graph::kMaxArcs)
+      return fail(FDNN_E_ARG, "align graph, segment " + std::to_string(s) + ": a segment has at most " + std::to_string(fdnn::align_graph::kMaxArcs) + " arcs");
+  }
+  return FDNN_OK;
+}
+
+int fdnn_align_graph_scratch_words(const int32_t *seg_T, const int32_t *state_ptr, int n_segs, long long *words) {
+  if (!words) return fail(FDNN_E_ARG, "null argument");
+  const std::vector<long long> off(size_t(std::max(n_segs, 0)), 0);
+  const std::vector<int32_t> ld(size_t(std::max(n_segs, 0)), 1);
+  if (int rc = align_graph_rows_tables(seg_T, off.data(), ld.data(), state_ptr, nullptr, n_segs)) return rc;
+  *words = fdnn::align_graph::plan(seg_T, off.data(), ld.data(), state_ptr, nullptr, n_segs, fdnn::align_graph_kernel_mode()).scratch_words;
+  return FDNN_OK;
+}
+
+int fdnn_align_graph_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                                 const int32_t *state_ptr, const int32_t *arc_ptr, int n_segs, const int32_t *d_col, const int32_t *d_state_node,
+                                 const int32_t *d_arc_ptr, const int32_t *d_arc_src, const float *d_arc_lp, const float *d_start_lp,
+                                 const float *d_final_lp, void *d_scratch, long long scratch_words, int32_t *d_path, float *d_total, void *stream) {
+  if (n_segs > 0 && !arc_ptr) return fail(FDNN_E_ARG, "align graph, segment 0: malformed tables");
+  if (int rc = align_graph_rows_tables(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  const bool arcs = arc_ptr[state_ptr[n_segs]] > 0;
+  if (!d_rows || !d_col || !d_arc_ptr || (arcs && (!d_arc_src || !d_arc_lp)) || !d_path || !d_total || (ll && !d_state_node))
+    return fail(FDNN_E_ARG, "null buffer");
+  const uintptr_t all = reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_col) | reinterpret_cast<uintptr_t>(d_state_node) |
+                        reinterpret_cast<uintptr_t>(d_arc_ptr) | reinterpret_cast<uintptr_t>(d_arc_src) | reinterpret_cast<uintptr_t>(d_arc_lp) |
+                        reinterpret_cast<uintptr_t>(d_start_lp) | reinterpret_cast<uintptr_t>(d_final_lp) | reinterpret_cast<uintptr_t>(d_scratch) |
+                        reinterpret_cast<uintptr_t>(d_path) | reinterpret_cast<uintptr_t>(d_total);
+  if (all & 3) return fail(FDNN_E_ARG, "buffers must have their elements' alignment, the scratch 4 bytes");
+  const fdnn::align_graph::Plan p = fdnn::align_graph::plan(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs, fdnn::align_graph_kernel_mode());
+  if (p.scratch_words * 4 > fdnn::align_graph::kMaxScratchBytes)
+    return fail(FDNN_E_ARG, "align graph: the back-pointers of the call are above " + std::to_string(fdnn::align_graph::kMaxScratchBytes) + " bytes");
+  if (p.scratch_words > 0 && (!d_scratch || scratch_words < p.scratch_words))
+    return fail(FDNN_E_ARG, "align graph: the call needs " + std::to_string(p.scratch_words) + " scratch words (fdnn_align_graph_scratch_words)");
+  fdnn::AlignGraphArgs a;
+  a.d_rows = d_rows, a.d_col = d_col, a.d_state_node = d_state_node, a.d_arc_ptr = d_arc_ptr, a.d_arc_src = d_arc_src, a.d_arc_lp = d_arc_lp;
+  a.d_start_lp = d_start_lp, a.d_final_lp = d_final_lp;
+  a.d_scratch = static_cast<uint32_t *>(d_scratch), a.d_path = d_path, a.d_total = d_total;
+  if (ll) a.d_log_prior = ll->d_log_prior, a.width = ll->width, a.floor = ll->floor, a.type = ll->type;
+  int dev = 0;
+  if (ll) dev = ll->device;
+  else if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  DeviceGuard g(dev);
+  fdnn::launch_align_graph(p, a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+// The front of every align-graph call through a model: the handle, then the tables (align_graph_prepare names the first bad segment)
+static int align_graph_front(const fdnn_model *m, const fdnn_loglik *ll, const fdnn::align_graph::Tables &t, int ctx_rows, fdnn::AlignGraphJob *j) {
+  if (int rc = fdnn::check_loglik(m, ll)) return rc;
+  if (t.n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
+  j->ll = ll, j->t = t;
+  return fdnn::align_graph_prepare(j, m->hm.hdr.out_dim, ctx_rows);
+}
+
+static fdnn::align_graph::Tables graph_tables(const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr,
+                                              const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp) {
+  fdnn::align_graph::Tables t;
+  t.seg_rows = seg_rows, t.state_ptr = state_ptr, t.states = states, t.arc_ptr = arc_ptr, t.arc_src = arc_src, t.arc_lp = arc_lp;
+  t.start_lp = start_lp, t.final_lp = final_lp, t.n_segs = n_segs;
+  return t;
+}
+
+static int ctx_align_graph(fdnn_ctx *c, const fdnn_loglik *ll, const fdnn::align_graph::Tables &t, int32_t *path, float *total, bool host, hipStream_t s) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  fdnn::AlignGraphJob j;
+  if (int rc = align_graph_front(c->m, ll, t, c->n, &j)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (t.n_segs == 0) return FDNN_OK;
+  if (!path || !total) return fail(FDNN_E_ARG, "null result buffer");
+  const std::vector<sets::Seg> segs = sets::slice(j.tables(), t.seg_rows[0], t.seg_rows[t.n_segs]);
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  int rc = fdnn::align_graph_stage(c, j, s);
+  SetsCall sc;
+  sc.first = t.seg_rows[0], sc.segs = &segs, sc.d_nodes = c->d_al_int, sc.d_probs = c->d_al_probs, sc.d_inactive = c->d_al_inact;
+  if (!rc) rc = run_sets(c, sc, s);
+  if (!rc) rc = fdnn::align_graph_finish(c, j, path, total, host, s);
+  if (rc && host) hipStreamSynchronize(s);
+  return rc;
+}
+
+int fdnn_ctx_align_graph(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                         const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, int32_t *path,
+                         float *total) {
+  return ctx_align_graph(c, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), path, total, true,
+                         c ? c->stream : nullptr);
+}
+
+int fdnn_ctx_align_graph_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                                const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp,
+                                int32_t *d_path, float *d_total, void *stream) {
+  return ctx_align_graph(c, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), d_path, d_total, false,
+                         static_cast<hipStream_t>(stream));
+}
+
+// One-call forms: hidden layers + the graphs' node sets chunk by chunk into the context's buffers (the sibling's sink), the
+// recursion ONCE behind the last chunk, inside the same use of the context.
+static int calculate_align_graph(fdnn_model *m, const Pass &p, fdnn::AlignGraphJob &j, int32_t *path, float *total, int n) {
+  return score_chunks(m, frame_chunks(n, m), p, nullptr, [&](fdnn_ctx *c, hipStream_t s) { return fdnn::align_graph_stage(c, j, s); },
+                      [&](fdnn_ctx *c, hipStream_t s) {
+                        const int rc = fdnn::align_graph_finish(c, j, path, total, true, s);
+                        if (rc) hipStreamSynchronize(s);
+                        return rc;
+                      });
+}
+
+int fdnn_calculate_align_graph(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr,
+                               int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                               const float *start_lp, const float *final_lp, int32_t *path, float *total) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  fdnn::AlignGraphJob j;
+  if (int rc = align_graph_front(m, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), n, &j)) return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!x || !path || !total) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  const sets::Tables t = j.tables();
+  return calculate_align_graph(m, Pass::host_align("fdnn_calculate_align_graph", x, t), j, path, total, n);
+}
+
+int fdnn_calculate_align_graph_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                   const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src,
+                                   const float *arc_lp, const float *start_lp, const float *final_lp, int32_t *path, float *total) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  if (int rc = fdnn::splice_check(spec, raw_dim)) return rc;
+  fdnn::AlignGraphJob j;
+  if (int rc = align_graph_front(m, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), n, &j)) return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!raw || !path || !total) return fail(FDNN_E_ARG, "null buffer");
+  // every segment is an utterance of its own: its edges repeat its own first and last frame
+  std::vector<SpliceSeg> segs;
+  for (int s = 0; s < n_segs; ++s) segs.push_back(SpliceSeg{seg_rows[s], seg_rows[s], seg_rows[s], seg_rows[s + 1] - 1});
+  const sets::Tables t = j.tables();
+  return calculate_align_graph(m, Pass::raw_align("fdnn_calculate_align_graph_raw", {spec.get(), &segs, raw, n}, t), j, path, total, n);
+}
+
+int fdnn_debug_align_graph_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 2, fdnn::align_graph_launch_counts); }
+
+int fdnn_debug_set_align_graph_kernel(int mode) {
+  if (mode < 0 || mode > 2) return fail(FDNN_E_ARG, "mode is 0 (the plan's rule), 1 (the wave form where allowed) or 2 (the workgroup form)");
+  fdnn::align_graph_kernel_mode(mode);
+  return FDNN_OK;
+}
+
+int fdnn_debug_align_graph_limits(int *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  const int v[8] = {fdnn::align_graph::kMaxStates, fdnn::align_graph::kMaxSegs, fdnn::align_graph::kWaveStates, fdnn::align_graph::kMaxArcs,
+                    fdnn::align_graph::kArcLdsArcs, fdnn::align_graph::kBpLdsWords, int(fdnn::align_graph::kMaxScratchBytes >> 20),
+                    fdnn::align_graph::kWaveRuleStates};
+  for (int i = 0; i < 8 && i < cap; ++i) out[i] = v[i];
+  return 8;
+}
+
+// The recursion in plain C++ (fdnn_align_graph.hpp: ref), no device: rows, tables and handle values as fdnn_debug_align_ref,
+// the graph's tables as fdnn_align_graph_rows_device takes them, all on the host.
+int fdnn_debug_align_graph_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr,
+                               int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior, int width, float floor, int type,
+                               const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp,
+                               int32_t *path, float *total) {
+  if (n_segs > 0 && !arc_ptr) return fail(FDNN_E_ARG, "align graph, segment 0: malformed tables");
+  if (int rc = align_graph_rows_tables(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  if (type != fdnn::align::kScores && (fdnn::loglik::check_handle(log_prior, width, floor, type) != 0 || !state_node))
+    return fail(FDNN_E_ARG, "log_prior [width] finite, the floor -inf or finite (F16: not below -65504), the type F32, F16 or -1 (scores)");
+  if (!rows || !col || !path || !total || (arc_ptr[state_ptr[n_segs]] > 0 && (!arc_src || !arc_lp))) return fail(FDNN_E_ARG, "null buffer");
+  size_t at = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const int b = state_ptr[s], S = state_ptr[s + 1] - b;
+    uint32_t tb;
+    fdnn::align_graph::ref(reinterpret_cast<const uint32_t *>(rows) + row_off[s], seg_T[s], row_ld[s], col + b, state_node ? state_node + b : nullptr, S,
+                           log_prior, width, floor, type, arc_ptr + b, arc_src, arc_lp, start_lp ? start_lp + b : nullptr,
+                           final_lp ? final_lp + b : nullptr, path + at, &tb);
+    std::memcpy(total + s, &tb, 4);
+    at += size_t(seg_T[s]);
+  }
+  return FDNN_OK;
+}
+
 int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
   if (!c || !out) return fail(FDNN_E_ARG, "null argument");
   if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");

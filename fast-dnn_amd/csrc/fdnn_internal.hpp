@@ -156,6 +156,10 @@ struct fdnn_ctx {
   fdnn::DevBuf<float> d_al_lp, d_al_probs, d_al_inact;
   fdnn::DevBuf<uint32_t> d_al_bp;
   fdnn::DevBuf<int32_t> d_al_res;
+  // align-graph calls (fdnn_align_graph.hip) share the align buffers above and add the graphs' tables: arc_ptr [n_states + 1]
+  // | arc_src [arcs], and arc_lp [arcs] | start_lp [n_states] | final_lp [n_states]
+  fdnn::DevBuf<int32_t> d_ag_int;
+  fdnn::DevBuf<float> d_ag_lp;
   // host list calls (fdnn_ctx_lazy_output_lists, fdnn_calculate_lazy_lists): staging of the lists and their results,
   // allocated on the first list call and grown by the largest one
   fdnn::DevBuf<int32_t> d_lrow, d_lnodes;   // [count + 1], [nnz]
@@ -411,6 +415,30 @@ int align_stage(fdnn_ctx *c, const AlignJob &j, hipStream_t s);
 // The recursion over the probabilities that the sets calls left in c->d_al_probs, then: host = true -- ONE transfer of path
 // [rows] and total [n_segs] and s synchronised; false -- both copied to the caller's device buffers on s.
 int align_finish(fdnn_ctx *c, const AlignJob &j, int32_t *path, float *total, bool host, hipStream_t s);
+
+// ---------------------------------------------------------------- alignment graphs (fdnn_align_graph.hip)
+// One align-graph call's validated host tables and what is derived from them before anything is launched
+// (align_graph_prepare): as AlignJob, with the graph's plan.  The sets step is the sibling's (Sink::align_sets into the
+// context's align buffers); only the finishing recursion differs.
+struct AlignGraphJob {
+  const fdnn_loglik *ll = nullptr;
+  align_graph::Tables t;
+  align::Sets sets;
+  std::vector<int32_t> seg_T, row_ld;
+  std::vector<long long> row_off;  // segment s's block in the ragged probabilities
+  long long nnz = 0;
+  int rows = 0;                    // seg_rows[n_segs] - seg_rows[0]
+  align_graph::Plan plan;
+  sets::Tables tables() const { return {t.seg_rows, sets.set_ptr.data(), t.n_segs}; }
+};
+// FDNN_E_ARG naming the first bad segment (align_graph::check), the sum of rows x len past an int32 or the back-pointers past
+// align_graph::kMaxScratchBytes; else fills j from its table pointers.  Nothing is launched.
+int align_graph_prepare(AlignGraphJob *j, int output_dim, int ctx_rows);
+// The context's buffers made large enough and the tables uploaded on s (the host tables are read before it returns).
+int align_graph_stage(fdnn_ctx *c, const AlignGraphJob &j, hipStream_t s);
+// The recursion over the probabilities that the sets calls left in c->d_al_probs, then: host = true -- ONE transfer of path
+// [rows] and total [n_segs] and s synchronised; false -- both copied to the caller's device buffers on s.
+int align_graph_finish(fdnn_ctx *c, const AlignGraphJob &j, int32_t *path, float *total, bool host, hipStream_t s);
 
 // ---------------------------------------------------------------- one scoring pass, one chunk loop
 // Hidden layers + what the pass's sink asks for, chunk by chunk, on context c and stream s; every pointer a chunk uses comes

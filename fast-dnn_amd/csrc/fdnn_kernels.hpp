@@ -15,6 +15,7 @@
 #include "fdnn_pool.hpp"
 #include "fdnn_loglik.hpp"
 #include "fdnn_align.hpp"
+#include "fdnn_align_graph.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -306,6 +307,29 @@ void launch_align(const align::Plan &p, const AlignArgs &a, hipStream_t s);
 void align_launch_counts(unsigned long long out[2]);  // launches so far: wave form, workgroup form
 int align_kernel_mode();                               // fdnn_debug_set_align_kernel: 0 the plan's rule, 1 wave where allowed, 2 workgroup
 void align_kernel_mode(int mode);
+
+// Alignment graphs (fdnn_align_graph.hip; the step, the plan and the host restatement: fdnn_align_graph.hpp): the launches of
+// a plan (align_graph::plan over the call's host tables) over device-resident rows.  rows, type, d_col, d_state_node,
+// d_log_prior as AlignArgs.  d_arc_ptr [states + 1], d_arc_src, d_arc_lp [arcs]: device copies of the host tables the plan was
+// made from (the plan's counts bound every arc index).  d_start_lp / d_final_lp [states] may be null (state 0 / the last
+// state).  d_scratch: p.scratch_words 32-bit words (null when there are none).  d_path [sum of T] int32, d_total [n_segs].
+struct AlignGraphArgs {
+  const float *d_rows = nullptr;
+  const int32_t *d_col = nullptr, *d_state_node = nullptr;
+  const float *d_log_prior = nullptr;
+  int width = 0;
+  float floor = 0.0f;
+  int type = align::kScores;
+  const int32_t *d_arc_ptr = nullptr, *d_arc_src = nullptr;
+  const float *d_arc_lp = nullptr, *d_start_lp = nullptr, *d_final_lp = nullptr;
+  uint32_t *d_scratch = nullptr;
+  int32_t *d_path = nullptr;
+  float *d_total = nullptr;
+};
+void launch_align_graph(const align_graph::Plan &p, const AlignGraphArgs &a, hipStream_t s);
+void align_graph_launch_counts(unsigned long long out[2]);  // launches so far: wave form, workgroup form
+int align_graph_kernel_mode();  // fdnn_debug_set_align_graph_kernel: 0 the plan's rule, 1 wave where allowed, 2 workgroup
+void align_graph_kernel_mode(int mode);
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

@@ -534,6 +534,79 @@ FDNN_API int fdnn_calculate_align(fdnn_model *m, const float *x, int n, int dim,
 FDNN_API int fdnn_calculate_align_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
                                       const int32_t *state_ptr, int n_segs, const int32_t *states, const float *self_lp, const float *next_lp,
                                       int32_t *path, float *total);
+/* ------------------------------------------------------------------ alignment graphs (fdnn_align_graph.hip)
+ * The best path over ANY arc set of a segment's states, and its score, on the device: optional silence between words,
+ * pronunciation variants, absent leading or trailing silence, a keyword looped against a filler -- what the chain above leaves
+ * out.  The reference has no such call; every entry below extends LazyOutputActivations (dnn.cc:355-392).  THE CONTRACT IS
+ * STATED ONCE, in csrc/fdnn_align_graph.hpp; in short:
+ *
+ * A segment has T >= 1 rows and a graph of 1 <= S <= 16384 states.  State j has an output node states[j] (repeats are
+ * normal) and the incoming arcs arc_ptr[j] .. arc_ptr[j + 1], in the order the caller wrote them; an arc has a source
+ * arc_src[a], a state index local to the segment in [0, S) (self-loops, forward, skip and backward arcs alike) and a finite
+ * score arc_lp[a].  Every arc consumes a frame.  The tables follow the chain's:
+ *   seg_rows [n_segs + 1], state_ptr [n_segs + 1], states [N], N = state_ptr[n_segs]
+ *   arc_ptr  [N + 1]   arc_ptr[0] == 0, non-decreasing (a segment's arcs are contiguous); at most 2^17 arcs per segment
+ *   arc_src, arc_lp [arc_ptr[N]]
+ *   start_lp, final_lp [N] or NULL, each value finite or -inf; NULL start_lp = +0.0f for the segment's state 0 and -inf
+ *     elsewhere, NULL final_lp = +0.0f for its state S - 1 and -inf elsewhere
+ *   path [seg_rows[n_segs] - seg_rows[0]] int32 in row order, total [n_segs] float
+ * The emission e(t, j) is the chain's.  In fp32, every + rounded once, nothing contracted:
+ *   d[0][j] = start_lp[j] + e(0, j)
+ *   t >= 1: best = -inf, from = -1; for each arc a of j in order: cand = d[t-1][arc_src[a]] + arc_lp[a];
+ *           if (cand > best) best = cand, from = arc_src[a];    d[t][j] = best + e(t, j), bp[t][j] = from
+ *   total:  the best of d[T-1][j] + final_lp[j] over j ascending, taken only where above the best so far; end = its state
+ *   path:   j = end; for t = T-1 .. 1: path[t] = j, j = bp[t][j];  path[0] = j
+ * A tie and a NaN are never taken: among equal candidates the EARLIEST arc of a state's list wins, among equal final states
+ * the lowest; the total is never a NaN (unlike the chain's).  A total that is not finite (-inf: no path; +inf) gives -1 in
+ * every frame.  A state without arcs is reachable at t = 0 only.  With state j's arcs (j with self_lp[j], then j - 1 with
+ * next_lp[j - 1]) and NULL start_lp / final_lp the result is fdnn_calculate_align's byte for byte wherever no emission is a
+ * NaN or +inf, T < S included.  Path and total are a function of the scores and the graph alone -- not of the kernel form,
+ * the chunking or the entry point -- and equal fdnn_debug_align_graph_ref byte for byte.
+ * FDNN_E_ARG before anything is launched, naming the first bad segment: the chain's row, state and node reasons (not T < S:
+ * a graph may skip), a malformed arc_ptr, more than 2^17 arcs, a source outside [0, S), an arc score that is not finite, a
+ * start or final value that is a NaN or +inf, no start or no final state with a finite value, the chain's handle and
+ * device-group reasons, back-pointers of one call above 2^30 bytes.  FDNN_E_STATE before the hidden layers have run.  The
+ * batcher, the scoring loop, device groups and the JNI shim neither route to nor look at these entry points, and every other
+ * entry point keeps its bytes.
+ *
+ * fdnn_align_graph_rows_device   the recursion alone on any device-resident fp32 rows (dnn.cc:355-392): seg_T, row_off,
+ *   row_ld, state_ptr and arc_ptr are host tables (the plan is made from them, and the host arc_ptr bounds every arc index on
+ *   the device); d_col, d_state_node [N] as fdnn_align_rows_device; d_arc_ptr [N + 1], d_arc_src, d_arc_lp [arcs] device copies
+ *   of the graph; d_start_lp / d_final_lp [N] or NULL.  A source outside [0, S) makes that candidate a NaN and reads nothing;
+ *   a column or node out of range makes the emission a NaN.  d_scratch: at least the 32-bit words
+ *   fdnn_align_graph_scratch_words names, on a 4-byte boundary (NULL when 0).  d_path [sum T], d_total [n_segs].  Enqueued on
+ *   `stream`, not synchronised.
+ * fdnn_align_graph_scratch_words the scratch of that call: the back-pointers (16 bits a frame and state) of the segments
+ *   whose do not fit LDS (dnn.cc:355-392).
+ * fdnn_ctx_align_graph           host tables and host results, host-synchronous, over rows of a context whose hidden layers
+ *   have run (dnn.cc:355-392): the graphs' node sets, fdnn_ctx_lazy_output_sets' computation into a context-owned buffer, the
+ *   recursion, then ONE transfer of path and total.
+ * fdnn_ctx_align_graph_device    the same with device result buffers, enqueued on `stream`; the host tables are read before
+ *   it returns (dnn.cc:355-392).
+ * fdnn_calculate_align_graph     one call on a pooled context (dnn.cc:355-392): seg_rows must cover [0, n); a large n goes
+ *   chunk by chunk like fdnn_calculate_align, and the recursion runs ONCE behind the last chunk: a cut segment's path is the
+ *   uncut one.
+ * fdnn_calculate_align_graph_raw the same from raw feature frames [n][raw_dim] (dnn.cc:355-392); every segment is an
+ *   utterance of its own. */
+FDNN_API int fdnn_align_graph_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off,
+                                          const int32_t *row_ld, const int32_t *state_ptr, const int32_t *arc_ptr, int n_segs, const int32_t *d_col,
+                                          const int32_t *d_state_node, const int32_t *d_arc_ptr, const int32_t *d_arc_src, const float *d_arc_lp,
+                                          const float *d_start_lp, const float *d_final_lp, void *d_scratch, long long scratch_words, int32_t *d_path,
+                                          float *d_total, void *stream);
+FDNN_API int fdnn_align_graph_scratch_words(const int32_t *seg_T, const int32_t *state_ptr, int n_segs, long long *words);
+FDNN_API int fdnn_ctx_align_graph(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                  const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp,
+                                  const float *final_lp, int32_t *path, float *total);
+FDNN_API int fdnn_ctx_align_graph_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                         const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                                         const float *start_lp, const float *final_lp, int32_t *d_path, float *d_total, void *stream);
+FDNN_API int fdnn_calculate_align_graph(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                        const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src,
+                                        const float *arc_lp, const float *start_lp, const float *final_lp, int32_t *path, float *total);
+FDNN_API int fdnn_calculate_align_graph_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                            const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr,
+                                            const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, int32_t *path,
+                                            float *total);
 /* Last hidden layer's u8 activations, n x hidden_dim (quantized_activations_). */
 FDNN_API int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out);
 
@@ -924,6 +997,26 @@ FDNN_API int fdnn_debug_align_ref(const float *rows, const int32_t *seg_T, const
                                   int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior, int width, float floor, int type,
                                   const float *self_lp, const float *next_lp, int32_t *path, float *total);
 FDNN_API int fdnn_debug_align_sets(const int32_t *state_ptr, const int32_t *states, int n_segs, int32_t *set_ptr, int32_t *nodes, int32_t *col);
+
+/* Alignment graphs (LazyOutputActivations, dnn.cc:355-392), tests and tools.
+ * fdnn_debug_align_graph_launches    process-wide counts since load, returns 2: out[0] launches of the wave form, [1] of the
+ *   workgroup form.  A counter of their own: not in the launch recorder's table (fdnn_note.hpp), apart from the chain's.
+ * fdnn_debug_set_align_graph_kernel  process-wide: 0 the plan's rule (one wave per segment where S <= 64, else 256
+ *   threads), 1 the wave form where allowed (S <= 256), 2 always the workgroup form -- the same bytes either way
+ *   (dnn.cc:355-392).
+ * fdnn_debug_align_graph_limits      returns 8: out[0] the most states, [1] segments per launch, [2] the wave form's most
+ *   states, [3] the most arcs of a segment, [4] the arcs of a segment the wave form stages in LDS, [5] the back-pointer
+ *   words of a segment that stay in LDS, [6] the scratch cap of a call in MiB, [7] the most states at which the rule takes
+ *   the wave form (dnn.cc:355-392).
+ * fdnn_debug_align_graph_ref         fdnn_align_graph_rows_device from the host restatement (fdnn_align_graph.hpp) on host
+ *   rows and host arrays; type as fdnn_debug_align_ref; host code, no device needed (dnn.cc:355-392). */
+FDNN_API int fdnn_debug_align_graph_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_set_align_graph_kernel(int mode);
+FDNN_API int fdnn_debug_align_graph_limits(int *out, int cap);
+FDNN_API int fdnn_debug_align_graph_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                                        const int32_t *state_ptr, int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior,
+                                        int width, float floor, int type, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                                        const float *start_lp, const float *final_lp, int32_t *path, float *total);
 
 /* Splicing through a segment table in device memory (the scoring loop's live batches, fdnn_splice.hip), tests and tools.
  * fdnn_debug_splice_table   the splice alone, host in and host out: raw [raw_frames][raw_dim] -> x [rows][input_dim] under the
