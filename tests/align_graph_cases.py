@@ -11,6 +11,7 @@ A graph is a dict (api.chain_graph / api.optional_silence_graph / by hand): stat
 final_lp.  Everything is seeded; totals are compared as bits."""
 import numpy as np
 
+import align_cases as AC
 from fast_dnn_amd import api
 
 
@@ -117,3 +118,65 @@ def silence_case(seed, words=6, per_word=6, T=129, width=64, integers=False):
 
 def silence_states(g):
     return np.nonzero(np.asarray(g["states"]) == 0)[0]
+
+
+# ------------------------------------------------------------------ through the model (tests/test_gpu_align_graph.py and
+# tests/test_gpu_signal_nets.py): optional-silence transcripts from a net's rows, the restatement composed over the lazy sets
+# call's bytes, and the condition under which the comparison is not blind
+FAR = -1000.0  # an arc score no emission makes up for (the handles' floor is -20)
+
+
+def silence_node(dense):
+    """The node that is the argmax of the most rows: a silence that the scores do favour on some frames."""
+    return int(np.bincount(dense.argmax(axis=1)).argmax())
+
+
+def silence_graphs(dense, seg_rows, seed, words_per_seg=None):
+    """Per segment an optional-silence transcript: the silence is silence_node(dense), the words are three states each from the
+    runs of the rows' argmax without the silence (padded with random nodes), arc scores ln U(0.05, 0.95).  So that the
+    comparison is not blind whatever the scores say, entering the silence after word 0 costs FAR (it is SKIPPED) and so does
+    the skip over the silence after word 1 (that silence is TAKEN); every other silence is left to the scores."""
+    rng = np.random.default_rng(seed)
+    O, sil = dense.shape[1], silence_node(dense)
+    graphs = []
+    for a, b in zip(seg_rows[:-1], seg_rows[1:]):
+        best = dense[a:b].argmax(axis=1)
+        runs = [int(v) for v in best[np.concatenate([[True], best[1:] != best[:-1]])] if v != sil]
+        n_words = words_per_seg or max(3, (b - a) // 12)
+        pad = [int(v) if v != sil else (int(v) + 1) % O for v in rng.integers(0, O, max(0, 3 * n_words - len(runs)))]
+        nodes = runs[:3 * n_words] + pad
+        words = [nodes[3 * w:3 * w + 3] for w in range(n_words)]
+        g = api.optional_silence_graph(words, sil)
+        g["arc_lp"] = np.log(rng.uniform(0.05, 0.95, g["arc_lp"].size)).astype(np.float32)
+        ptr = g["arc_ptr"]
+        g["arc_lp"][ptr[4] + 1] = FAR  # state 4 = the silence after word 0: its arc from word 0's last state
+        g["arc_lp"][ptr[9] + 1] = FAR  # state 9 = word 2's first state: its arc from word 1's last state, the skip
+        graphs.append(g)
+    return graphs
+
+
+def composed(dnn, x, lp, handle, seg_rows, packed):
+    """The restatement over the lazy sets call's bytes -> (path, total)."""
+    ptr, states = packed["statePtr"], packed["states"]
+    set_ptr, nodes, col = api.align_sets(ptr, states)
+    probs = dnn.calculateLazySets(x, seg_rows, set_ptr, nodes)[0]
+    T, ln = np.diff(seg_rows), np.diff(set_ptr)
+    off = np.concatenate([[0], np.cumsum(T.astype(np.int64) * ln)[:-1]])
+    entry_nodes = np.concatenate([np.tile(nodes[set_ptr[s]:set_ptr[s + 1]], T[s]) for s in range(T.size)])
+    e = api.loglik_entries_ref(entry_nodes, probs, lp, handle[0], handle[1]).astype(np.float32)
+    return api.align_graph_ref(e, T, off, ln, packed, col), (e, T, off, ln, col)
+
+
+def not_blind(net, want, pieces, seg_rows, graphs):
+    """On the restatement alone: the paths take some silences and skip others, and differ from the forced-silence chain's.
+    Silences 4 and 8 are planted; what the scores decide about the others is printed."""
+    e, T, off, ln, col = pieces
+    sp = np.concatenate([[0], np.cumsum([len(g["states"]) for g in graphs])]).astype(np.int32)
+    chain = api.align_ref(e, T, off, ln, sp, col)  # every silence forced: the chain over the same states
+    for s, g in enumerate(graphs):
+        p = want[0][seg_rows[s]:seg_rows[s + 1]]
+        sil = np.arange(0, len(g["states"]), 4)  # the silence before each three-state word and the one after the last
+        took = [int(j) for j in sil if (p == j).any()]
+        frac = AC.differ(p, chain[0][seg_rows[s]:seg_rows[s + 1]])
+        print(f"{net} segment {s}: T {p.size} S {len(g['states'])}, silences taken {took} of {sil.tolist()}, {frac:.0%} of the frames off the forced-silence chain")
+        assert 8 in took and 4 not in took and 0 < len(took) < sil.size and frac > 0

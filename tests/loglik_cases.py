@@ -76,3 +76,18 @@ def same_bytes(a, b):
     ua, ub = (a.view(np.uint16), b.view(np.uint16)) if a.dtype == np.float16 else (a.view(np.uint32), b.view(np.uint32))
     na, nb = np.isnan(a), np.isnan(b)
     return bool((na == nb).all() and (ua[~na] == ub[~nb]).all())
+
+
+def assert_log_of_rows(dense, lp, s32, s16):
+    """Against something independent of the library's logarithm: float64 log of the dense rows minus the priors, within
+    kLnMaxUlp (0.85) ulps of ln plus the subtraction's half ulp (fp32 scores `s32`, no floor), and that rounded once more to
+    fp16 (`s16`: half an fp16 ulp) -- wherever the row's entry is positive.  -> the largest |s32 - exact| / bound."""
+    ok = dense > 0
+    s = np.asarray(s32).astype(np.float64)
+    exact = np.log(dense.astype(np.float64), where=ok, out=np.zeros(dense.shape)) - lp.astype(np.float64)[None, :]
+    ln_ulp = np.spacing(np.abs(np.log(dense.astype(np.float64), where=ok, out=np.ones(dense.shape))).astype(np.float32)).astype(np.float64)
+    bound = 0.85 * ln_ulp + 0.5 * np.spacing(np.abs(exact).astype(np.float32)).astype(np.float64)
+    assert (np.abs(s - exact)[ok] <= bound[ok]).all()
+    h = np.asarray(s16).astype(np.float64)
+    assert (np.abs(h - s)[ok] <= 0.5 * np.spacing(np.abs(s).astype(np.float16)).astype(np.float64)[ok] * 1.0000001).all()
+    return float((np.abs(s - exact)[ok] / bound[ok]).max()) if ok.any() else 0.0

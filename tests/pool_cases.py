@@ -19,8 +19,8 @@ def lanes():
     return api.pool_limits()[0]
 
 
-def map_of(kind, width, seed=0):
-    """(class_of int32 [width], n_classes) of the kind at this width."""
+def map_of(kind, width, seed=0, classes=None):
+    """(class_of int32 [width], n_classes) of the kind at this width (classes: how many an `interleaved` map has, 48 unless given)."""
     rng = np.random.default_rng(77 * width + 13 * len(kind) + seed)
     i = np.arange(width, dtype=np.int64)
     if kind == "one":
@@ -28,7 +28,7 @@ def map_of(kind, width, seed=0):
     if kind == "identity":
         return i.astype(np.int32), width
     if kind == "interleaved":
-        C = min(width, 48)
+        C = min(width, classes or 48)
         return (i % C).astype(np.int32), C
     if kind == "blocks":  # contiguous, uneven blocks
         C = min(width, 5)
@@ -110,6 +110,13 @@ def pool_literal(row, member):
 
 def depth(size):
     return -(-size // lanes()) + 4
+
+
+def oracle_bound(size, exact, bar):
+    """The allowed |q_c - exact| of a class of `size` members against the float64 sum `exact` of the oracle's probabilities:
+    the absolute bar per probability plus the derived bound of the additions, d u / (1 - d u) (exact + size bar), d = depth(size)."""
+    d = depth(size)
+    return size * bar + d * U / (1 - d * U) * (exact + size * bar)
 
 
 def same_bytes(got, want):

@@ -2,9 +2,9 @@
 module: numpy only, no GPU, no fixture.
 
 Every GPU test holds a kernel to the oracle; this table names the nets and inputs those tests trust, built ONLY from the
-helpers they use (formats.synth_net / synth_features / generate_masks, sat_switch, limit_nets, dispatch_ledger.net_path), so
-that what is recorded from the reference (tests/golden/make_family_golden.py -> tests/golden/families/*.npz) is what the suite
-relies on.  Users:
+helpers they use (formats.synth_net / synth_features / generate_masks, sat_switch, limit_nets, signal_nets,
+dispatch_ledger.net_path), so that what is recorded from the reference (tests/golden/make_family_golden.py ->
+tests/golden/families/*.npz) is what the suite relies on.  Users:
 
   tests/golden/make_family_golden.py     drives the compiled reference, asserts each family's property on its data, stores it
   tests/test_oracle_families.py          the oracle against the stored data (everywhere)
@@ -94,7 +94,7 @@ class Family:
     blocks: tuple = (10,)      # frame-block sizes: blocking never changes a result, every block size is held to the one fixture
     cutoff: float = 3.0
     fma: bool = False          # layer 0 as the reference computes it when its mul + add fuse
-    inputs: str = "synth"      # synth | x50 | hostile | switch (sat_switch.features under crowded_switches)
+    inputs: str = "synth"      # synth | x50 | hostile | switch (sat_switch.features under crowded_switches) | signal (signal_nets.features)
     lazy: bool = False         # masks: row 0 all off, row 1 only the last node on, row 2 all on, the rest generate_masks(.., 0.4, 0.05)
     sample: int = 0            # > 0: too large to store -- integer state as sha256, float state at `sample` seeded columns
     props: tuple = ()          # the conditions of properties()
@@ -103,7 +103,7 @@ class Family:
 
     @property
     def fixture(self):
-        return "families/" + self.name.replace("/", "_") + ".npz"
+        return "families/" + self.name.replace("/", "_").replace("signal.", "signal_", 1) + ".npz"
 
 
 FAMILIES = {}
@@ -154,6 +154,22 @@ _fam("fma.hostile", PLAIN, 31, 64, blocks=(10, 1), fma=True, inputs="hostile", p
 _fam("cut2", PLAIN, 101, 40, cutoff=2.0, props=("cutoff",))
 _fam("cut4", PLAIN, 101, 40, cutoff=4.0, props=("cutoff",))
 
+
+def _signal_families():
+    """tests/signal_nets.py's grid, both modes: the first min(n, 64) rows of each case's own features.  The wide ones keep hashes
+    and 256 sampled columns.  k1024 stays out of the GPU file: the reference's sequential fp32 row total is 2.7e-6 off the
+    float64 soft-max on these rows (3.5e-6 over all 641), more than the 2e-6 that file allows between the library and the
+    recorded rows; tests/test_gpu_signal_nets.py holds the library to float64 of the oracle's logits on that net instead."""
+    import signal_nets as SN
+
+    for name, mode in SN.cases():
+        topo, n, kw = SN.recipe(name, mode)
+        _fam(f"signal.{name}" + ("" if mode == "gauss" else ".nosat"), ("synth", topo, kw), SN.FEATURE_SEED, min(n, 64), inputs="signal",
+             sample=256 if topo[1] >= 512 else 0, props=("signal",), gpu=name != "k1024")
+
+
+_signal_families()
+
 NAMES = tuple(FAMILIES)
 CASES = tuple((n, b) for n in NAMES for b in FAMILIES[n].blocks)    # (family, frame-block size)
 CASE_IDS = tuple(f"{n}-b{b}" for n, b in CASES)
@@ -198,6 +214,8 @@ def features(fam, in_dim):
         import sat_switch as SW
 
         x = SW.features(fam.rows, SW.crowded_switches(fam.rows, fam.seed), fam.seed)
+    elif fam.inputs == "signal":
+        x = F.synth_features(fam.rows, in_dim, seed=fam.seed, pad_from=None)
     else:
         x = F.synth_features(fam.rows, in_dim, seed=fam.seed)
         if fam.inputs == "x50":
@@ -341,6 +359,10 @@ def record(fam, ref_t, model_sha, x, m=None):
             import limit_nets as LN
 
             g["acc_planted"] = ref_t["acc_hid"][1][:, :LN.ACC_ROWS]
+    if "signal" in fam.props:
+        import limit_nets as LN
+
+        g["signal"] = np.array(LN.signal_stats(ref_t["u8_acts"][-1]), np.float64)   # distinct rows, median node range, byte values
     if m is not None:
         g["masks"] = m
         g["lazy"] = ref_t["lazy"]
@@ -487,6 +509,15 @@ def properties(fam, g, wq=None, plain_l0=None, base=None):
             off = g["masks"] == 0
             for f in range(3, lz.shape[0]):
                 assert np.unique(lz[f][off[f]]).size == 1, f"{fam.name}: masked-out entries of row {f} are not one value"
+        elif prop == "signal":  # tests/signal_nets.py's condition on the last hidden layer of the recorded rows
+            import signal_nets as SN
+
+            frames, med, values = (float(v) for v in g["signal"])
+            if not fam.sample:  # (a sampled family keeps hashes: its figures are the generator's, from the full layer)
+                assert LN.signal_stats(g["u8_acts"][-1]) == (frames, med, values), f"{fam.name}: the recorded signal figures are not the data's"
+            assert frames == int(g["rows"]) and values >= SN.MIN_VALUES and med >= SN.MIN_RANGE, \
+                f"{fam.name}: {frames} distinct rows of {int(g['rows'])}, {values} byte values, median node range {med} at the last hidden layer"
+            out["signal"] = [frames, med, values]
         elif prop == "cutoff":
             assert (g["mult"] != base["mult"]).all() and (g["wq_sha256"] != base["wq_sha256"]).all(), \
                 f"{fam.name}: multipliers or quantized weights are the cut-off-3 ones"

@@ -11,6 +11,7 @@ import loglik_cases as LL
 from fast_dnn_amd import api, convert, formats as F
 
 pytestmark = pytest.mark.gpu
+transcripts, composed, same, seg_rows_of = AC.transcripts, AC.composed, AC.same, AC.seg_rows_of  # (shared with tests/test_gpu_signal_nets.py)
 KALDI = (list(range(-5, 6)), 39)
 NETS = {"tiny": (33, 1), "mid": (100, 3), "full": (64, 2)}  # net -> frames, segments
 HANDLES = ((-20.0, api.LOGLIK_F32), (-20.0, api.LOGLIK_F16))
@@ -36,46 +37,6 @@ def nets(fixtures):
     yield get
     for dnn, _, _ in cache.values():
         dnn.delete()
-
-
-def transcripts(dense, seg_rows, seed):
-    """Per segment: the runs of the rows' argmax, thinned (early runs are kept more often than late ones, so the best path is
-    far from the uniform segmentation) and salted with random nodes; S < T, repeats occur."""
-    rng = np.random.default_rng(seed)
-    O = dense.shape[1]
-    ptr, states = [0], []
-    for a, b in zip(seg_rows[:-1], seg_rows[1:]):
-        best = dense[a:b].argmax(axis=1)
-        runs = best[np.concatenate([[True], best[1:] != best[:-1]])]
-        keep = rng.random(runs.size) < np.linspace(0.9, 0.05, runs.size)
-        keep[0] = True
-        st = runs[keep].tolist()
-        for _ in range(max(2, (b - a) // 5)):
-            st.insert(int(rng.integers(0, len(st) + 1)), int(rng.integers(0, O)))
-        st.insert(min(2, len(st)), st[0])  # a repeat
-        st = st[:max(1, (b - a) // 2)]
-        states.extend(st)
-        ptr.append(len(states))
-    return np.array(ptr, np.int32), np.array(states, np.int32)
-
-
-def composed(dnn, x, lp, handle, seg_rows, ptr, states, sl, nl):
-    """The restatement over the lazy sets call's bytes -> (path, total)."""
-    set_ptr, nodes, col = api.align_sets(ptr, states)
-    probs = dnn.calculateLazySets(x, seg_rows, set_ptr, nodes)[0]
-    T, ln = np.diff(seg_rows), np.diff(set_ptr)
-    off = np.concatenate([[0], np.cumsum(T.astype(np.int64) * ln)[:-1]])
-    entry_nodes = np.concatenate([np.tile(nodes[set_ptr[s]:set_ptr[s + 1]], T[s]) for s in range(T.size)])
-    e = api.loglik_entries_ref(entry_nodes, probs, lp, handle[0], handle[1]).astype(np.float32)
-    return api.align_ref(e, T, off, ln, ptr, col, selfLp=sl, nextLp=nl)
-
-
-def same(got, want):
-    return np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
-
-
-def seg_rows_of(n, n_segs):
-    return np.array([0] + [n * (s + 1) // n_segs + (3 if s + 1 < n_segs else 0) for s in range(n_segs)], np.int32)
 
 
 @pytest.mark.parametrize("net", list(NETS))

@@ -7,16 +7,19 @@ import numpy as np
 import pytest
 
 import align_cases as AC
+import align_graph_cases as GC
 import lazy_lists_cases as LC
 import loglik_cases as LL
 from fast_dnn_amd import api, convert, formats as F
 
 pytestmark = pytest.mark.gpu
+FAR = GC.FAR
+silence_node, silence_graphs, composed, not_blind = GC.silence_node, GC.silence_graphs, GC.composed, GC.not_blind  # (shared with tests/test_gpu_signal_nets.py)
+same, seg_rows_of = AC.same, AC.seg_rows_of
 KALDI = (list(range(-5, 6)), 39)
 NETS = {"tiny": (33, 1), "mid": (100, 3), "full": (64, 2)}  # net -> frames, segments
 HANDLES = ((-20.0, api.LOGLIK_F32), (-20.0, api.LOGLIK_F16))
 SIL = 0  # the silence node of the hand-written graphs (the transcripts from a net's rows take the rows' most frequent argmax)
-FAR = -1000.0  # an arc score no emission makes up for (the handles' floor is -20)
 
 
 @pytest.fixture(scope="module")
@@ -39,70 +42,6 @@ def nets(fixtures):
     yield get
     for dnn, _, _ in cache.values():
         dnn.delete()
-
-
-def silence_node(dense):
-    """The node that is the argmax of the most rows: a silence that the scores do favour on some frames."""
-    return int(np.bincount(dense.argmax(axis=1)).argmax())
-
-
-def silence_graphs(dense, seg_rows, seed, words_per_seg=None):
-    """Per segment an optional-silence transcript: the silence is silence_node(dense), the words are three states each from the
-    runs of the rows' argmax without the silence (padded with random nodes), arc scores ln U(0.05, 0.95).  So that the
-    comparison is not blind whatever the scores say, entering the silence after word 0 costs FAR (it is SKIPPED) and so does
-    the skip over the silence after word 1 (that silence is TAKEN); every other silence is left to the scores."""
-    rng = np.random.default_rng(seed)
-    O, sil = dense.shape[1], silence_node(dense)
-    graphs = []
-    for a, b in zip(seg_rows[:-1], seg_rows[1:]):
-        best = dense[a:b].argmax(axis=1)
-        runs = [int(v) for v in best[np.concatenate([[True], best[1:] != best[:-1]])] if v != sil]
-        n_words = words_per_seg or max(3, (b - a) // 12)
-        pad = [int(v) if v != sil else (int(v) + 1) % O for v in rng.integers(0, O, max(0, 3 * n_words - len(runs)))]
-        nodes = runs[:3 * n_words] + pad
-        words = [nodes[3 * w:3 * w + 3] for w in range(n_words)]
-        g = api.optional_silence_graph(words, sil)
-        g["arc_lp"] = np.log(rng.uniform(0.05, 0.95, g["arc_lp"].size)).astype(np.float32)
-        ptr = g["arc_ptr"]
-        g["arc_lp"][ptr[4] + 1] = FAR  # state 4 = the silence after word 0: its arc from word 0's last state
-        g["arc_lp"][ptr[9] + 1] = FAR  # state 9 = word 2's first state: its arc from word 1's last state, the skip
-        graphs.append(g)
-    return graphs
-
-
-def composed(dnn, x, lp, handle, seg_rows, packed):
-    """The restatement over the lazy sets call's bytes -> (path, total)."""
-    ptr, states = packed["statePtr"], packed["states"]
-    set_ptr, nodes, col = api.align_sets(ptr, states)
-    probs = dnn.calculateLazySets(x, seg_rows, set_ptr, nodes)[0]
-    T, ln = np.diff(seg_rows), np.diff(set_ptr)
-    off = np.concatenate([[0], np.cumsum(T.astype(np.int64) * ln)[:-1]])
-    entry_nodes = np.concatenate([np.tile(nodes[set_ptr[s]:set_ptr[s + 1]], T[s]) for s in range(T.size)])
-    e = api.loglik_entries_ref(entry_nodes, probs, lp, handle[0], handle[1]).astype(np.float32)
-    return api.align_graph_ref(e, T, off, ln, packed, col), (e, T, off, ln, col)
-
-
-def same(got, want):
-    return np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
-
-
-def seg_rows_of(n, n_segs):
-    return np.array([0] + [n * (s + 1) // n_segs + (3 if s + 1 < n_segs else 0) for s in range(n_segs)], np.int32)
-
-
-def not_blind(net, want, pieces, seg_rows, graphs):
-    """On the restatement alone: the paths take some silences and skip others, and differ from the forced-silence chain's.
-    Silences 4 and 8 are planted; what the scores decide about the others is printed."""
-    e, T, off, ln, col = pieces
-    sp = np.concatenate([[0], np.cumsum([len(g["states"]) for g in graphs])]).astype(np.int32)
-    chain = api.align_ref(e, T, off, ln, sp, col)  # every silence forced: the chain over the same states
-    for s, g in enumerate(graphs):
-        p = want[0][seg_rows[s]:seg_rows[s + 1]]
-        sil = np.arange(0, len(g["states"]), 4)  # the silence before each three-state word and the one after the last
-        took = [int(j) for j in sil if (p == j).any()]
-        frac = AC.differ(p, chain[0][seg_rows[s]:seg_rows[s + 1]])
-        print(f"{net} segment {s}: T {p.size} S {len(g['states'])}, silences taken {took} of {sil.tolist()}, {frac:.0%} of the frames off the forced-silence chain")
-        assert 8 in took and 4 not in took and 0 < len(took) < sil.size and frac > 0
 
 
 @pytest.mark.parametrize("net", list(NETS))

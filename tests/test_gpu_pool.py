@@ -213,8 +213,7 @@ def test_against_the_oracle_on_every_row(nets, fixtures, net):
         worst = 0.0
         for c, m in enumerate(PC.members(co, C)):
             exact = p[:, m].sum(1)
-            d = PC.depth(m.size)
-            bound = m.size * LC.TIGHT + d * PC.U / (1 - d * PC.U) * (exact + m.size * LC.TIGHT)
+            bound = PC.oracle_bound(m.size, exact, LC.TIGHT)
             err = np.abs(q[:, c] - exact)
             worst = max(worst, float((err / np.maximum(bound, 1e-300)).max()) if m.size else 0.0)
             assert (err <= bound).all(), (net, mk, c, m.size, float(err.max()), float(bound.min()))

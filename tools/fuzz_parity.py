@@ -20,6 +20,16 @@ tmp = os.environ.get("TMPDIR", "/tmp")
 TIGHT = 2e-6
 t0 = time.time()
 worst = 0.0
+with_signal = 0  # cases whose frames differ at the last hidden layer (tests/signal_nets.py's condition; information only)
+
+
+def keeps_signal(u8):
+    """tests/signal_nets.py's signal condition on one hidden layer's bytes [n][H]: every row distinct, >= 200 distinct byte
+    values, the median over the nodes of (max - min) over the frames >= 48 bytes."""
+    rng_ = u8.max(axis=0).astype(np.int32) - u8.min(axis=0).astype(np.int32)
+    return bool(len(np.unique(u8, axis=0)) == u8.shape[0] and len(np.unique(u8)) >= 200 and np.median(rng_) >= 48)
+
+
 for case in range(cases):
     in_dim = int(rng.choice([4, 8, 12, 40, 44, 64, 100, 132, 256, 432, 496]))  # (64 .. 496: the int8 screening of layer 0 from 640 frames up)
     hidden = int(rng.choice([16, 32, 48, 64, 96, 128, 192, 256, 272, 512, 1024]))
@@ -44,6 +54,7 @@ for case in range(cases):
     dnn = api.QuantizedDnn.loadFromFile(path)
     dnn.setInputLayerFma(fma)
     want, wt = orc.calculate(x, taps=True)
+    with_signal += keeps_signal(wt["u8_acts"][-1])
     taps = dnn.forwardTaps(x)
     for k in ("u8_acts", "acc_hid", "acc_out"):
         assert np.array_equal(taps[k], wt[k]), (tag, k)
@@ -85,4 +96,6 @@ for case in range(cases):
         print(f"{case + 1} cases, worst soft-max error {worst:.2e}, {time.time() - t0:.0f} s", flush=True)
 _names = api.launch_names()
 print(f"launched {len(api.launch_counts())} distinct kernel instances of the {sum(1 for f in _names.values() if not f & api.LAUNCH_ABLATION)} the shipped library can launch (tests/dispatch_ledger.py covers them case by case)")
+print(f"signal: {with_signal} of {cases} cases kept their signal at the last hidden layer (all rows distinct, >= 200 byte values, median node range >= 48); "
+      "the others are judged on frames that look alike -- tests/test_gpu_signal_nets.py is where the small nets keep it")
 print(f"fuzz ok: {cases} cases in {time.time() - t0:.0f} s, worst soft-max error {worst:.2e}")
