@@ -225,6 +225,25 @@ SIGNATURES = {
     "fdnn_debug_align_graph_limits": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "fdnn_debug_align_graph_ref": (C.c_int, [_c_f32p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, C.c_int,
                                              C.c_float, C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_f32p]),
+    "fdnn_fb_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, _c_i32p, _c_i32p, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_fb_scratch_words": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "fdnn_fb_transpose": (C.c_int, [_c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_i32p, _c_i32p, _c_f32p]),
+    "fdnn_ctx_fb": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_ctx_fb_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_fb": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p,
+                                    _c_f32p, _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_calculate_fb_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p,
+                                        _c_f32p, _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_debug_fb_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_set_fb_kernel": (C.c_int, [C.c_int]),
+    "fdnn_debug_fb_limits": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "fdnn_debug_fb_ref": (C.c_int, [_c_f32p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, C.c_int, C.c_float,
+                                    C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_debug_fb_math_ref": (C.c_int, [C.c_int, _c_f32p, _c_f32p, _c_f32p, C.c_longlong]),
+    "fdnn_debug_fb_math_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "fdnn_debug_ln_ref": (C.c_int, [_c_f32p, C.c_longlong, _c_f32p]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -1115,6 +1134,136 @@ def align_graph_limits() -> dict:
                     (int(v) for v in buf)))
 
 
+# ---------------------------------------------------------------- alignment graphs, summed (fdnn_fb.hip)
+# The graphs are the alignment graphs' (chain_graph, optional_silence_graph, pack_graphs); the results are the total
+# likelihood ln(sum over paths) per segment and the occupancies gamma, flat float32 [sum of T S]: segment s's block is
+# row-major [T_s][S_s] (``fb_gamma_blocks`` cuts it).
+FB_EXP_NEG, FB_LADD = 0, 1
+
+
+def fb_transpose(graphs) -> dict:
+    """The transposed tables of a packed call (``fdnn_fb_transpose``; host code): a stable counting sort of every segment's arcs
+    by source -> dict(tPtr [states + 1] global, tSrc [arcs] the DESTINATION local to the segment, tLp [arcs])."""
+    sp, _, ap, src, lp, _, _ = _graph_tables(graphs)
+    tp = np.zeros(ap.size, np.int32)
+    ts = np.zeros(src.size, np.int32)
+    tl = np.zeros(src.size, np.float32)
+    _check(lib().fdnn_fb_transpose(_ip(sp), sp.size - 1, _ip(ap), _ip(src), _fp(lp), _ip(tp), _ip(ts), _fp(tl)))
+    return dict(tPtr=tp, tSrc=ts, tLp=tl)
+
+
+def fb_gamma_blocks(gamma, segT, statePtr):
+    """The flat occupancies cut into one [T][S] view per segment."""
+    t = np.asarray(segT, dtype=np.int64)
+    S = np.diff(np.asarray(statePtr, dtype=np.int64))
+    off = np.concatenate([[0], np.cumsum(t * S)])
+    return [gamma[off[s]:off[s + 1]].reshape(int(t[s]), int(S[s])) for s in range(t.size)]
+
+
+def fb_ref(rows, segT, rowOff, rowLd, graphs, col, stateNode=None, log_prior=None, floor: float = -np.inf, type: int = ALIGN_SCORES,
+           want_gamma: bool = True, transposed=None):
+    """Forward-backward from the host restatement (``fdnn_debug_fb_ref``; host code, no device): the arguments of
+    ``align_graph_ref``; ``transposed`` the dict of ``fb_transpose`` (made here when None) -> (total float32 [segments], gamma
+    float32 [sum of T S], or None unless ``want_gamma``)."""
+    r = np.ascontiguousarray(rows, dtype=np.float32).ravel()
+    sp, _, ap, src, alp, start, final = _graph_tables(graphs)
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, sp)
+    c = np.ascontiguousarray(col, dtype=np.int32)
+    nd = None if stateNode is None else np.ascontiguousarray(stateNode, dtype=np.int32)
+    lp = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float32)
+    if t.size and ((off + (t.astype(np.int64) - 1) * ld + ld > r.size).any() or (off < 0).any() or c.size < int(sp[-1])):
+        raise ValueError("a segment's rows run past the rows, or col is shorter than the graphs")
+    total = np.empty(t.size, np.float32)
+    gamma = tp = ts = tl = None
+    if want_gamma:
+        tr = fb_transpose(graphs) if transposed is None else transposed
+        tp = np.ascontiguousarray(tr["tPtr"], dtype=np.int32)
+        ts = np.ascontiguousarray(tr["tSrc"], dtype=np.int32)
+        tl = np.ascontiguousarray(tr["tLp"], dtype=np.float32)
+        if tp.shape != ap.shape or ts.shape != src.shape or tl.shape != src.shape:
+            raise ValueError("the transposed tables have the shapes of the arc tables")
+        gamma = np.empty(int((t.astype(np.int64) * np.diff(sp.astype(np.int64))).sum()), np.float32)
+    _check(lib().fdnn_debug_fb_ref(r.ctypes.data_as(_c_f32p), t.ctypes.data_as(_c_i32p), off.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                   ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, c.ctypes.data_as(_c_i32p), _ip(nd), _fp(lp),
+                                   0 if lp is None else lp.size, C.c_float(float(floor)), int(type), _ip(ap), _ip(src), _fp(alp), _fp(start),
+                                   _fp(final), _ip(tp), _ip(ts), _fp(tl), total.ctypes.data_as(_c_f32p), _fp(gamma)))
+    return total, gamma
+
+
+def fb_scratch_words(segT, statePtr, want_gamma: bool = True) -> int:
+    """The fp32 scratch words ``fb_rows_device`` needs for these tables (``fdnn_fb_scratch_words``): the lattice, T S words a
+    segment where gamma is wanted, else 0."""
+    t = np.ascontiguousarray(segT, dtype=np.int32)
+    sp = np.ascontiguousarray(statePtr, dtype=np.int32)
+    words = C.c_longlong(0)
+    _check(lib().fdnn_fb_scratch_words(t.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, int(bool(want_gamma)), C.byref(words)))
+    return int(words.value)
+
+
+def fb_rows_device(ll, d_rows: int, segT, rowOff, rowLd, statePtr, arcPtr, tPtr, d_col: int, d_state_node: int, d_arc_ptr: int, d_arc_src: int,
+                   d_arc_lp: int, d_start_lp: int, d_final_lp: int, d_t_ptr: int, d_t_src: int, d_t_lp: int, d_scratch: int, scratch_words: int,
+                   d_total: int, d_gamma: int, stream: int = 0) -> None:
+    """The sweeps alone on device-resident fp32 rows (``fdnn_fb_rows_device``): host tables segT, rowOff, rowLd, statePtr,
+    arcPtr and tPtr (None without gamma), device pointers for everything they index (0 for NULL); ``d_gamma`` 0 = forward
+    only; ``ll`` a ``Loglik`` or None (the rows are scores).  Enqueued on ``stream``, not synchronised."""
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, statePtr)
+    ap = np.ascontiguousarray(arcPtr, dtype=np.int32)
+    tp = None if tPtr is None else np.ascontiguousarray(tPtr, dtype=np.int32)
+    if ap.shape != (int(sp[-1]) + 1,) or (tp is not None and tp.shape != ap.shape):
+        raise ValueError("arcPtr and tPtr must be [states + 1]")
+    _check(lib().fdnn_fb_rows_device(None if ll is None else ll.handle, C.c_void_p(d_rows), t.ctypes.data_as(_c_i32p),
+                                     off.ctypes.data_as(C.POINTER(C.c_longlong)), ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p),
+                                     ap.ctypes.data_as(_c_i32p), _ip(tp), t.size, C.c_void_p(d_col), C.c_void_p(d_state_node), C.c_void_p(d_arc_ptr),
+                                     C.c_void_p(d_arc_src), C.c_void_p(d_arc_lp), C.c_void_p(d_start_lp), C.c_void_p(d_final_lp), C.c_void_p(d_t_ptr),
+                                     C.c_void_p(d_t_src), C.c_void_p(d_t_lp), C.c_void_p(d_scratch), int(scratch_words), C.c_void_p(d_total),
+                                     C.c_void_p(d_gamma), C.c_void_p(stream)))
+
+
+def fb_launches():
+    """Process-wide counts since load: launches (forward wave form, forward workgroup form, backward wave, backward workgroup)."""
+    buf = (C.c_ulonglong * 4)()
+    if lib().fdnn_debug_fb_launches(buf, 4) != 4:
+        raise RuntimeError("fdnn_debug_fb_launches")
+    return tuple(int(v) for v in buf)
+
+
+def set_fb_kernel(mode: int) -> None:
+    """Process-wide (``fdnn_debug_set_fb_kernel``): 0 the plan's rule, 1 the wave form where allowed (up to 256 states), 2
+    always the workgroup form."""
+    _check(lib().fdnn_debug_set_fb_kernel(int(mode)))
+
+
+def fb_limits() -> dict:
+    """The forward-backward kernels' limits as built (``fdnn_debug_fb_limits``)."""
+    buf = (C.c_int * 8)()
+    if lib().fdnn_debug_fb_limits(buf, 8) != 8:
+        raise RuntimeError("fdnn_debug_fb_limits")
+    return dict(zip(("max_states", "segs_per_launch", "wave_states", "max_arcs", "lds_arcs", "partials", "scratch_cap_mib", "wave_rule_states"),
+                    (int(v) for v in buf)))
+
+
+def fb_math_ref(op: int, a, b=None):
+    """The stated functions on the host (``fdnn_debug_fb_math_ref``): op FB_EXP_NEG -> exp_neg(a), FB_LADD -> ladd(a, b)."""
+    x = np.ascontiguousarray(a, dtype=np.float32).ravel()
+    y = None if b is None else np.ascontiguousarray(b, dtype=np.float32).ravel()
+    if y is not None and y.size != x.size:
+        raise ValueError("a and b have one size")
+    out = np.empty(x.size, np.float32)
+    _check(lib().fdnn_debug_fb_math_ref(int(op), _fp(x), _fp(y), _fp(out), x.size))
+    return out
+
+
+def fb_math_device(op: int, d_a: int, d_b: int, d_out: int, n: int, stream: int = 0) -> None:
+    """The same over device arrays in a trivial kernel (``fdnn_debug_fb_math_device``), enqueued on ``stream``."""
+    _check(lib().fdnn_debug_fb_math_device(int(op), C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+
+def _fb_out(n_segs: int, segRows, sp, want_gamma: bool):
+    total = np.empty(n_segs, np.float32)
+    words = int((np.diff(segRows.astype(np.int64)) * np.diff(sp.astype(np.int64))).sum()) if n_segs else 0
+    return total, (np.empty(words, np.float32) if want_gamma else None)
+
+
 def _loglik_out(n: int, ll: "Loglik", out):
     """The [n][width] result array of a loglik call, made or checked."""
     shape = (n, ll.width())
@@ -1371,6 +1520,24 @@ class LazyContext:
         sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
         _check(lib().fdnn_ctx_align_graph_device(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start),
                                                  _fp(final), C.c_void_p(d_path), C.c_void_p(d_total), C.c_void_p(stream)))
+
+    def forwardBackward(self, ll: "Loglik", segRows, graphs, want_gamma: bool = True):
+        """The total likelihood ln(sum over paths) and the state occupancies of alignment graphs, over rows of the context
+        (``fdnn_ctx_fb``): segment s = rows [segRows[s], segRows[s + 1]) with graph s of the packed call ``graphs`` -> (total
+        float32 [segments], gamma float32 [sum of T S] -- ``fb_gamma_blocks`` cuts it -- or None unless ``want_gamma``:
+        forward only)."""
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        total, gamma = _fb_out(n_segs, sr, sp, want_gamma)
+        _check(lib().fdnn_ctx_fb(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                 _fp(total), _fp(gamma)))
+        return total, gamma
+
+    def forwardBackwardDevice(self, ll: "Loglik", segRows, graphs, d_total: int, d_gamma: int = 0, stream: int = 0) -> None:
+        """The same with device result buffers (``d_gamma`` 0: forward only), enqueued on ``stream`` and not synchronised
+        (``fdnn_ctx_fb_device``)."""
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        _check(lib().fdnn_ctx_fb_device(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                        C.c_void_p(d_total), C.c_void_p(d_gamma), C.c_void_p(stream)))
 
     def calculateOutputLoglikDevice(self, ll: "Loglik", d_out: int, stream: int = 0) -> None:
         """The same into a device buffer [frames][outputDimension] of the handle's type, enqueued on ``stream``, not
@@ -2202,6 +2369,32 @@ class QuantizedDnn:
                                                     n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
                                                     path.ctypes.data_as(_c_i32p), total.ctypes.data_as(_c_f32p)))
         return path, total
+
+    def calculateForwardBackward(self, input, ll: "Loglik", segRows, graphs, want_gamma: bool = True):
+        """The total likelihood and the state occupancies of alignment graphs in one call (``fdnn_calculate_fb``; segRows must
+        cover [0, frames)): hidden layers, the graphs' node sets, the forward and backward sweeps on the device -> (total
+        float32 [segments], gamma float32 [sum of T S] or None), as ``LazyContext.forwardBackward``."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        total, gamma = _fb_out(n_segs, sr, sp, want_gamma)
+        _check(lib().fdnn_calculate_fb(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(), ll.handle,
+                                       _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final), _fp(total), _fp(gamma)))
+        return total, gamma
+
+    def calculateForwardBackwardRaw(self, raw, ll: "Loglik", segRows, graphs, want_gamma: bool = True):
+        """``calculateForwardBackward`` on raw frames [n][rawDim], spliced on the device, every segment an utterance of its own
+        (``fdnn_calculate_fb_raw``)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError("raw must be [frames][rawDim]")
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        total, gamma = _fb_out(n_segs, sr, sp, want_gamma)
+        _check(lib().fdnn_calculate_fb_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], ll.handle, _ip(sr), _ip(sp), n_segs,
+                                           _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final), _fp(total), _fp(gamma)))
+        return total, gamma
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))

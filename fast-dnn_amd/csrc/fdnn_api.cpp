@@ -1402,6 +1402,236 @@ int fdnn_debug_align_graph_ref(const float *rows, const int32_t *seg_T, const lo
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- alignment graphs, summed (fdnn_fb.hip)
+// The sweeps alone.  The host tables are checked as the sibling's (the plan is made from them, and its arc counts bound every
+// arc index on the device, either direction); what they index is on the device and is not.
+static int fb_t_ptr_ok(const int32_t *state_ptr, const int32_t *arc_ptr, const int32_t *t_ptr, int n_segs) {
+  if (t_ptr[0] != 0) return fail(FDNN_E_ARG, "forward-backward, segment 0: t_ptr begins at 0");
+  for (int s = 0; s < n_segs; ++s) {
+    for (int i = state_ptr[s]; i < state_ptr[s + 1]; ++i)
+      if (t_ptr[i + 1] < t_ptr[i]) return fail(FDNN_E_ARG, "forward-backward, segment " + std::to_string(s) + ": t_ptr must not decrease");
+    if (t_ptr[state_ptr[s]] != arc_ptr[state_ptr[s]] || t_ptr[state_ptr[s + 1]] != arc_ptr[state_ptr[s + 1]])
+      return fail(FDNN_E_ARG, "forward-backward, segment " + std::to_string(s) + ": a segment's transposed arcs occupy the range of its arcs");
+  }
+  return FDNN_OK;
+}
+
+int fdnn_fb_scratch_words(const int32_t *seg_T, const int32_t *state_ptr, int n_segs, int want_gamma, long long *words) {
+  if (!words) return fail(FDNN_E_ARG, "null argument");
+  const std::vector<long long> off(size_t(std::max(n_segs, 0)), 0);
+  const std::vector<int32_t> ld(size_t(std::max(n_segs, 0)), 1);
+  if (int rc = align_graph_rows_tables(seg_T, off.data(), ld.data(), state_ptr, nullptr, n_segs)) return rc;
+  const long long w = fdnn::fb::plan(seg_T, off.data(), ld.data(), state_ptr, nullptr, n_segs, want_gamma != 0, fdnn::fb_kernel_mode()).scratch_words;
+  if (w * 4 > fdnn::fb::kMaxScratchBytes)
+    return fail(FDNN_E_ARG, "forward-backward: the lattice of the call is above " + std::to_string(fdnn::fb::kMaxScratchBytes) + " bytes");
+  *words = w;
+  return FDNN_OK;
+}
+
+int fdnn_fb_transpose(const int32_t *state_ptr, int n_segs, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, int32_t *t_ptr,
+                      int32_t *t_src, float *t_lp) {
+  if (n_segs < 0 || !state_ptr || !arc_ptr || !t_ptr || state_ptr[0] != 0 || arc_ptr[0] != 0) return fail(FDNN_E_ARG, "bad argument");
+  for (int s = 0; s < n_segs; ++s)
+    if (state_ptr[s + 1] < state_ptr[s]) return fail(FDNN_E_ARG, "state_ptr must not decrease");
+  t_ptr[0] = 0;
+  if (n_segs == 0) return FDNN_OK;
+  for (int i = 0; i < state_ptr[n_segs]; ++i)
+    if (arc_ptr[i + 1] < arc_ptr[i]) return fail(FDNN_E_ARG, "arc_ptr must not decrease");
+  if (arc_ptr[state_ptr[n_segs]] > 0 && (!arc_src || !arc_lp || !t_src || !t_lp)) return fail(FDNN_E_ARG, "null buffer");
+  const int bad = fdnn::fb::transpose(state_ptr, n_segs, arc_ptr, arc_src, arc_lp, t_ptr, t_src, t_lp);
+  if (bad) return fail(FDNN_E_ARG, "forward-backward, segment " + std::to_string(-bad - 1) + ": an arc's source is outside [0, S)");
+  return FDNN_OK;
+}
+
+int fdnn_fb_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                        const int32_t *state_ptr, const int32_t *arc_ptr, const int32_t *t_ptr, int n_segs, const int32_t *d_col,
+                        const int32_t *d_state_node, const int32_t *d_arc_ptr, const int32_t *d_arc_src, const float *d_arc_lp, const float *d_start_lp,
+                        const float *d_final_lp, const int32_t *d_t_ptr, const int32_t *d_t_src, const float *d_t_lp, void *d_scratch,
+                        long long scratch_words, float *d_total, float *d_gamma, void *stream) {
+  if (n_segs > 0 && !arc_ptr) return fail(FDNN_E_ARG, "forward-backward, segment 0: malformed tables");
+  if (int rc = align_graph_rows_tables(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  const bool arcs = arc_ptr[state_ptr[n_segs]] > 0, want = d_gamma != nullptr;
+  if (want) {
+    if (!t_ptr) return fail(FDNN_E_ARG, "forward-backward: gamma needs the transposed tables (fdnn_fb_transpose)");
+    if (int rc = fb_t_ptr_ok(state_ptr, arc_ptr, t_ptr, n_segs)) return rc;
+  }
+  if (!d_rows || !d_col || !d_arc_ptr || (arcs && (!d_arc_src || !d_arc_lp)) || !d_total || (ll && !d_state_node) ||
+      (want && (!d_t_ptr || (arcs && (!d_t_src || !d_t_lp)))))
+    return fail(FDNN_E_ARG, "null buffer");
+  const uintptr_t all = reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_col) | reinterpret_cast<uintptr_t>(d_state_node) |
+                        reinterpret_cast<uintptr_t>(d_arc_ptr) | reinterpret_cast<uintptr_t>(d_arc_src) | reinterpret_cast<uintptr_t>(d_arc_lp) |
+                        reinterpret_cast<uintptr_t>(d_start_lp) | reinterpret_cast<uintptr_t>(d_final_lp) | reinterpret_cast<uintptr_t>(d_t_ptr) |
+                        reinterpret_cast<uintptr_t>(d_t_src) | reinterpret_cast<uintptr_t>(d_t_lp) | reinterpret_cast<uintptr_t>(d_scratch) |
+                        reinterpret_cast<uintptr_t>(d_total) | reinterpret_cast<uintptr_t>(d_gamma);
+  if (all & 3) return fail(FDNN_E_ARG, "buffers must have their elements' alignment, the scratch 4 bytes");
+  fdnn::fb::Plan p = fdnn::fb::plan(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs, want, fdnn::fb_kernel_mode());
+  if (p.scratch_words * 4 > fdnn::fb::kMaxScratchBytes)
+    return fail(FDNN_E_ARG, "forward-backward: the lattice of the call is above " + std::to_string(fdnn::fb::kMaxScratchBytes) + " bytes");
+  if (p.scratch_words > 0 && (!d_scratch || scratch_words < p.scratch_words))
+    return fail(FDNN_E_ARG, "forward-backward: the call needs " + std::to_string(p.scratch_words) + " scratch words (fdnn_fb_scratch_words)");
+  fdnn::FbArgs a;
+  a.d_rows = d_rows, a.d_col = d_col, a.d_state_node = d_state_node, a.d_arc_ptr = d_arc_ptr, a.d_arc_src = d_arc_src, a.d_arc_lp = d_arc_lp;
+  a.d_start_lp = d_start_lp, a.d_final_lp = d_final_lp, a.d_t_ptr = d_t_ptr, a.d_t_src = d_t_src, a.d_t_lp = d_t_lp;
+  a.d_scratch = static_cast<float *>(d_scratch), a.d_total = d_total, a.d_gamma = d_gamma;
+  if (ll) a.d_log_prior = ll->d_log_prior, a.width = ll->width, a.floor = ll->floor, a.type = ll->type;
+  int dev = 0;
+  if (ll) dev = ll->device;
+  else if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  DeviceGuard g(dev);
+  fdnn::launch_fb(p, a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+// The front of every forward-backward call through a model: the handle, then the tables (fb_prepare names the first bad segment)
+static int fb_front(const fdnn_model *m, const fdnn_loglik *ll, const fdnn::align_graph::Tables &t, bool want_gamma, int ctx_rows, fdnn::FbJob *j) {
+  if (int rc = fdnn::check_loglik(m, ll)) return rc;
+  if (t.n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
+  j->ll = ll, j->t = t, j->want_gamma = want_gamma;
+  return fdnn::fb_prepare(j, m->hm.hdr.out_dim, ctx_rows);
+}
+
+static int ctx_fb(fdnn_ctx *c, const fdnn_loglik *ll, const fdnn::align_graph::Tables &t, float *total, float *gamma, bool host, hipStream_t s) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  fdnn::FbJob j;
+  if (int rc = fb_front(c->m, ll, t, gamma != nullptr, c->n, &j)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (t.n_segs == 0) return FDNN_OK;
+  if (!total) return fail(FDNN_E_ARG, "null result buffer");
+  const std::vector<sets::Seg> segs = sets::slice(j.tables(), t.seg_rows[0], t.seg_rows[t.n_segs]);
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  int rc = fdnn::fb_stage(c, j, s);
+  SetsCall sc;
+  sc.first = t.seg_rows[0], sc.segs = &segs, sc.d_nodes = c->d_al_int, sc.d_probs = c->d_al_probs, sc.d_inactive = c->d_al_inact;
+  if (!rc) rc = run_sets(c, sc, s);
+  if (!rc) rc = fdnn::fb_finish(c, j, total, gamma, host, s);
+  if (rc && host) hipStreamSynchronize(s);
+  return rc;
+}
+
+int fdnn_ctx_fb(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, float *total,
+                float *gamma) {
+  return ctx_fb(c, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), total, gamma, true,
+                c ? c->stream : nullptr);
+}
+
+int fdnn_ctx_fb_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                       const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, float *d_total,
+                       float *d_gamma, void *stream) {
+  return ctx_fb(c, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), d_total, d_gamma, false,
+                static_cast<hipStream_t>(stream));
+}
+
+// One-call forms: hidden layers + the graphs' node sets chunk by chunk into the context's buffers (the sibling's sink), the
+// sweeps ONCE behind the last chunk, inside the same use of the context.
+static int calculate_fb(fdnn_model *m, const Pass &p, fdnn::FbJob &j, float *total, float *gamma, int n) {
+  return score_chunks(m, frame_chunks(n, m), p, nullptr, [&](fdnn_ctx *c, hipStream_t s) { return fdnn::fb_stage(c, j, s); },
+                      [&](fdnn_ctx *c, hipStream_t s) {
+                        const int rc = fdnn::fb_finish(c, j, total, gamma, true, s);
+                        if (rc) hipStreamSynchronize(s);
+                        return rc;
+                      });
+}
+
+int fdnn_calculate_fb(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                      const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp,
+                      const float *final_lp, float *total, float *gamma) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  fdnn::FbJob j;
+  if (int rc = fb_front(m, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), gamma != nullptr, n, &j))
+    return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!x || !total) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  const sets::Tables t = j.tables();
+  return calculate_fb(m, Pass::host_align("fdnn_calculate_fb", x, t), j, total, gamma, n);
+}
+
+int fdnn_calculate_fb_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr,
+                          int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp,
+                          const float *final_lp, float *total, float *gamma) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  if (int rc = fdnn::splice_check(spec, raw_dim)) return rc;
+  fdnn::FbJob j;
+  if (int rc = fb_front(m, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), gamma != nullptr, n, &j))
+    return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!raw || !total) return fail(FDNN_E_ARG, "null buffer");
+  // every segment is an utterance of its own: its edges repeat its own first and last frame
+  std::vector<SpliceSeg> segs;
+  for (int s = 0; s < n_segs; ++s) segs.push_back(SpliceSeg{seg_rows[s], seg_rows[s], seg_rows[s], seg_rows[s + 1] - 1});
+  const sets::Tables t = j.tables();
+  return calculate_fb(m, Pass::raw_align("fdnn_calculate_fb_raw", {spec.get(), &segs, raw, n}, t), j, total, gamma, n);
+}
+
+int fdnn_debug_fb_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 4, fdnn::fb_launch_counts); }
+
+int fdnn_debug_set_fb_kernel(int mode) {
+  if (mode < 0 || mode > 2) return fail(FDNN_E_ARG, "mode is 0 (the plan's rule), 1 (the wave form where allowed) or 2 (the workgroup form)");
+  fdnn::fb_kernel_mode(mode);
+  return FDNN_OK;
+}
+
+int fdnn_debug_fb_limits(int *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  const int v[8] = {fdnn::fb::kMaxStates, fdnn::fb::kMaxSegs, fdnn::fb::kWaveStates, fdnn::fb::kMaxArcs, fdnn::fb::kArcLdsArcs, fdnn::fb::kPartials,
+                    int(fdnn::fb::kMaxScratchBytes >> 20), fdnn::fb::kWaveRuleStates};
+  for (int i = 0; i < 8 && i < cap; ++i) out[i] = v[i];
+  return 8;
+}
+
+// The recursion in plain C++ (fdnn_fb.hpp: ref), no device: rows, tables and handle values as fdnn_debug_align_graph_ref, the
+// transposed tables as fdnn_fb_rows_device takes them, all on the host; gamma (and then the transposed tables) may be null.
+int fdnn_debug_fb_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr, int n_segs,
+                      const int32_t *col, const int32_t *state_node, const float *log_prior, int width, float floor, int type, const int32_t *arc_ptr,
+                      const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, const int32_t *t_ptr,
+                      const int32_t *t_src, const float *t_lp, float *total, float *gamma) {
+  if (n_segs > 0 && !arc_ptr) return fail(FDNN_E_ARG, "forward-backward, segment 0: malformed tables");
+  if (int rc = align_graph_rows_tables(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  if (type != fdnn::align::kScores && (fdnn::loglik::check_handle(log_prior, width, floor, type) != 0 || !state_node))
+    return fail(FDNN_E_ARG, "log_prior [width] finite, the floor -inf or finite (F16: not below -65504), the type F32, F16 or -1 (scores)");
+  const bool arcs = arc_ptr[state_ptr[n_segs]] > 0;
+  if (!rows || !col || !total || (arcs && (!arc_src || !arc_lp))) return fail(FDNN_E_ARG, "null buffer");
+  if (gamma) {
+    if (!t_ptr || (arcs && (!t_src || !t_lp))) return fail(FDNN_E_ARG, "forward-backward: gamma needs the transposed tables (fdnn_fb_transpose)");
+    if (int rc = fb_t_ptr_ok(state_ptr, arc_ptr, t_ptr, n_segs)) return rc;
+  }
+  size_t at = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const int b = state_ptr[s], S = state_ptr[s + 1] - b;
+    uint32_t tb;
+    fdnn::fb::ref(reinterpret_cast<const uint32_t *>(rows) + row_off[s], seg_T[s], row_ld[s], col + b, state_node ? state_node + b : nullptr, S, log_prior,
+                  width, floor, type, arc_ptr + b, arc_src, arc_lp, start_lp ? start_lp + b : nullptr, final_lp ? final_lp + b : nullptr,
+                  gamma ? t_ptr + b : nullptr, t_src, t_lp, &tb, gamma ? reinterpret_cast<uint32_t *>(gamma) + at : nullptr);
+    std::memcpy(total + s, &tb, 4);
+    at += size_t(seg_T[s]) * size_t(S);
+  }
+  return FDNN_OK;
+}
+
+// op 0: out[i] = exp_neg(a[i]) (b is not read); op 1: out[i] = ladd(a[i], b[i]) -- the header's functions on the host
+int fdnn_debug_fb_math_ref(int op, const float *a, const float *b, float *out, long long n) {
+  if ((op != 0 && op != 1) || n < 0 || (n && (!a || !out || (op == 1 && !b)))) return fail(FDNN_E_ARG, "bad argument");
+  for (long long i = 0; i < n; ++i) out[i] = op == 0 ? fdnn::fb::exp_neg(a[i]) : fdnn::fb::ladd(a[i], b[i]);
+  return FDNN_OK;
+}
+
+// the same in a trivial kernel over device arrays, enqueued on `stream`
+int fdnn_debug_fb_math_device(int op, const float *d_a, const float *d_b, float *d_out, long long n, void *stream) {
+  if ((op != 0 && op != 1) || n < 0 || n > (1ll << 31) || (n && (!d_a || !d_out || (op == 1 && !d_b)))) return fail(FDNN_E_ARG, "bad argument");
+  fdnn::launch_fb_math(op, d_a, d_b, d_out, n, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
 int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
   if (!c || !out) return fail(FDNN_E_ARG, "null argument");
   if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");

@@ -160,6 +160,10 @@ struct fdnn_ctx {
   // | arc_src [arcs], and arc_lp [arcs] | start_lp [n_states] | final_lp [n_states]
   fdnn::DevBuf<int32_t> d_ag_int;
   fdnn::DevBuf<float> d_ag_lp;
+  // forward-backward calls (fdnn_fb.hip) share both sets of buffers above -- the lattice is the scratch d_al_bp -- and add the
+  // transposed tables t_ptr [n_states + 1] | t_src [arcs], t_lp [arcs], and the results total [n_segs] | gamma [sum T S]
+  fdnn::DevBuf<int32_t> d_fb_int;
+  fdnn::DevBuf<float> d_fb_lp, d_fb_res;
   // host list calls (fdnn_ctx_lazy_output_lists, fdnn_calculate_lazy_lists): staging of the lists and their results,
   // allocated on the first list call and grown by the largest one
   fdnn::DevBuf<int32_t> d_lrow, d_lnodes;   // [count + 1], [nnz]
@@ -439,6 +443,31 @@ int align_graph_stage(fdnn_ctx *c, const AlignGraphJob &j, hipStream_t s);
 // The recursion over the probabilities that the sets calls left in c->d_al_probs, then: host = true -- ONE transfer of path
 // [rows] and total [n_segs] and s synchronised; false -- both copied to the caller's device buffers on s.
 int align_graph_finish(fdnn_ctx *c, const AlignGraphJob &j, int32_t *path, float *total, bool host, hipStream_t s);
+
+// ---------------------------------------------------------------- alignment graphs, summed (fdnn_fb.hip)
+// One forward-backward call's validated host tables and what is derived from them before anything is launched (fb_prepare):
+// as AlignGraphJob, with the transposed tables (only where gamma is wanted) and fb's plan.
+struct FbJob {
+  const fdnn_loglik *ll = nullptr;
+  align_graph::Tables t;
+  bool want_gamma = false;
+  align::Sets sets;
+  std::vector<int32_t> seg_T, row_ld, t_ptr, t_src;
+  std::vector<float> t_lp;
+  std::vector<long long> row_off;  // segment s's block in the ragged probabilities
+  long long nnz = 0;
+  int rows = 0;                    // seg_rows[n_segs] - seg_rows[0]
+  fb::Plan plan;
+  sets::Tables tables() const { return {t.seg_rows, sets.set_ptr.data(), t.n_segs}; }
+};
+// FDNN_E_ARG naming the first bad segment (align_graph::check), the sum of rows x len past an int32 or the lattice past
+// fb::kMaxScratchBytes; else fills j from its table pointers and want_gamma.  Nothing is launched.
+int fb_prepare(FbJob *j, int output_dim, int ctx_rows);
+// The context's buffers made large enough and the tables uploaded on s (the host tables are read before it returns).
+int fb_stage(fdnn_ctx *c, const FbJob &j, hipStream_t s);
+// The sweeps over the probabilities that the sets calls left in c->d_al_probs, then: host = true -- ONE transfer of total
+// [n_segs], and of gamma [sum T S] where asked, and s synchronised; false -- copied to the caller's device buffers on s.
+int fb_finish(fdnn_ctx *c, const FbJob &j, float *total, float *gamma, bool host, hipStream_t s);
 
 // ---------------------------------------------------------------- one scoring pass, one chunk loop
 // Hidden layers + what the pass's sink asks for, chunk by chunk, on context c and stream s; every pointer a chunk uses comes

@@ -16,6 +16,7 @@
 #include "fdnn_loglik.hpp"
 #include "fdnn_align.hpp"
 #include "fdnn_align_graph.hpp"
+#include "fdnn_fb.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -330,6 +331,33 @@ void launch_align_graph(const align_graph::Plan &p, const AlignGraphArgs &a, hip
 void align_graph_launch_counts(unsigned long long out[2]);  // launches so far: wave form, workgroup form
 int align_graph_kernel_mode();  // fdnn_debug_set_align_graph_kernel: 0 the plan's rule, 1 wave where allowed, 2 workgroup
 void align_graph_kernel_mode(int mode);
+
+// Alignment graphs, summed (fdnn_fb.hip; the two stated functions, the recursion, the plan and the host restatement:
+// fdnn_fb.hpp): the launches of a plan (fb::plan over the call's host tables) over device-resident rows -- every launch
+// forward, then, where d_gamma is not null, every launch backward.  rows, type, d_col, d_state_node, d_log_prior, the arc
+// tables and d_start_lp / d_final_lp as AlignGraphArgs.  d_t_ptr [states + 1], d_t_src, d_t_lp [arcs]: device copies of the
+// transposed tables (fb::transpose), read only when d_gamma is not null.  d_scratch: p.scratch_words fp32 words, the
+// lattice (null when there are none).  d_total [n_segs], d_gamma [p.gamma_words] or null: forward only.
+struct FbArgs {
+  const float *d_rows = nullptr;
+  const int32_t *d_col = nullptr, *d_state_node = nullptr;
+  const float *d_log_prior = nullptr;
+  int width = 0;
+  float floor = 0.0f;
+  int type = align::kScores;
+  const int32_t *d_arc_ptr = nullptr, *d_arc_src = nullptr;
+  const float *d_arc_lp = nullptr, *d_start_lp = nullptr, *d_final_lp = nullptr;
+  const int32_t *d_t_ptr = nullptr, *d_t_src = nullptr;
+  const float *d_t_lp = nullptr;
+  float *d_scratch = nullptr;
+  float *d_total = nullptr, *d_gamma = nullptr;
+};
+void launch_fb(const fb::Plan &p, const FbArgs &a, hipStream_t s);
+// out[i] = exp_neg(a[i]) (op 0) or ladd(a[i], b[i]) (op 1): the stated functions in a trivial kernel (fdnn_debug_fb_math_device)
+void launch_fb_math(int op, const float *d_a, const float *d_b, float *d_out, long long n, hipStream_t s);
+void fb_launch_counts(unsigned long long out[4]);  // launches so far: forward wave, forward workgroup, backward wave, backward workgroup
+int fb_kernel_mode();  // fdnn_debug_set_fb_kernel: 0 the plan's rule, 1 wave where allowed, 2 workgroup
+void fb_kernel_mode(int mode);
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

@@ -1227,6 +1227,98 @@ int align_graph_finish(fdnn_ctx *c, const AlignGraphJob &j, int32_t *path, float
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- alignment graphs, summed (fdnn_fb.hip)
+int fb_prepare(FbJob *j, int output_dim, int ctx_rows) {
+  align_graph::Why why;
+  const int bad = align_graph::check(j->t, output_dim, ctx_rows, &why);
+  if (bad) return fail(FDNN_E_ARG, "forward-backward, segment " + std::to_string(-bad - 1) + ": " + align_graph::why_text(why));
+  const int n = j->t.n_segs;
+  j->sets = align::build_sets(j->t.state_ptr, j->t.states, n);
+  j->seg_T.resize(size_t(n)), j->row_ld.resize(size_t(n)), j->row_off.resize(size_t(n));
+  j->nnz = 0;
+  for (int s = 0; s < n; ++s) {
+    j->seg_T[size_t(s)] = j->t.seg_rows[s + 1] - j->t.seg_rows[s];
+    j->row_ld[size_t(s)] = j->sets.set_ptr[size_t(s) + 1] - j->sets.set_ptr[size_t(s)];
+    j->row_off[size_t(s)] = j->nnz;
+    j->nnz += static_cast<long long>(j->seg_T[size_t(s)]) * j->row_ld[size_t(s)];
+    if (j->nnz > INT32_MAX)
+      return fail(FDNN_E_ARG, "forward-backward, segment " + std::to_string(s) + ": the sum of rows x distinct nodes over the segments must fit an int32");
+  }
+  j->rows = n ? j->t.seg_rows[n] - j->t.seg_rows[0] : 0;
+  if (j->want_gamma && n) {
+    const size_t n_states = size_t(j->t.state_ptr[n]), n_arcs = size_t(j->t.arc_ptr[n_states]);
+    j->t_ptr.assign(n_states + 1, 0), j->t_src.assign(n_arcs, 0), j->t_lp.assign(n_arcs, 0.0f);
+    if (fb::transpose(j->t.state_ptr, n, j->t.arc_ptr, j->t.arc_src, j->t.arc_lp, j->t_ptr.data(), j->t_src.data(), j->t_lp.data()))
+      return fail(FDNN_E_ARG, "forward-backward: malformed arc tables");  // (the validator has passed: not reached)
+  }
+  j->plan = fb::plan(j->seg_T.data(), j->row_off.data(), j->row_ld.data(), j->t.state_ptr, j->t.arc_ptr, n, j->want_gamma, fb_kernel_mode());
+  if (j->plan.scratch_words * 4 > fb::kMaxScratchBytes)
+    return fail(FDNN_E_ARG, "forward-backward: the lattice of the call (" + std::to_string(j->plan.scratch_words * 4) + " bytes) is above " +
+                                std::to_string(fb::kMaxScratchBytes));
+  return FDNN_OK;
+}
+
+int fb_stage(fdnn_ctx *c, const FbJob &j, hipStream_t s) {
+  const size_t n_nodes = j.sets.nodes.size(), n_states = j.sets.col.size(), n_arcs = size_t(j.t.arc_ptr[n_states]), n = size_t(j.t.n_segs);
+  const size_t arcs1 = std::max<size_t>(n_arcs, 1);
+  HIP_TRY(c->d_al_int.reserve(n_nodes + 2 * n_states));
+  HIP_TRY(c->d_ag_int.reserve(n_states + 1 + arcs1));
+  HIP_TRY(c->d_ag_lp.reserve(arcs1 + 2 * n_states));
+  HIP_TRY(c->d_al_probs.reserve(std::max<size_t>(size_t(j.nnz), 1)));
+  HIP_TRY(c->d_al_inact.reserve(std::max<size_t>(size_t(j.rows), 1)));
+  HIP_TRY(c->d_al_bp.reserve(std::max<size_t>(size_t(j.plan.scratch_words), 2)));
+  HIP_TRY(c->d_fb_res.reserve(n + (j.want_gamma ? size_t(j.plan.gamma_words) : 0)));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int, j.sets.nodes.data(), sizeof(int32_t) * n_nodes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int.p + n_nodes, j.sets.col.data(), sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int.p + n_nodes + n_states, j.t.states, sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_ag_int, j.t.arc_ptr, sizeof(int32_t) * (n_states + 1), hipMemcpyHostToDevice, s));
+  if (n_arcs) {
+    HIP_TRY(hipMemcpyAsync(c->d_ag_int.p + n_states + 1, j.t.arc_src, sizeof(int32_t) * n_arcs, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->d_ag_lp, j.t.arc_lp, sizeof(float) * n_arcs, hipMemcpyHostToDevice, s));
+  }
+  float *tail = c->d_ag_lp.p + arcs1;
+  if (j.t.start_lp) HIP_TRY(hipMemcpyAsync(tail, j.t.start_lp, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  if (j.t.final_lp) HIP_TRY(hipMemcpyAsync(tail + n_states, j.t.final_lp, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  if (j.want_gamma) {
+    HIP_TRY(c->d_fb_int.reserve(n_states + 1 + arcs1));
+    HIP_TRY(c->d_fb_lp.reserve(arcs1));
+    HIP_TRY(hipMemcpyAsync(c->d_fb_int, j.t_ptr.data(), sizeof(int32_t) * (n_states + 1), hipMemcpyHostToDevice, s));
+    if (n_arcs) {
+      HIP_TRY(hipMemcpyAsync(c->d_fb_int.p + n_states + 1, j.t_src.data(), sizeof(int32_t) * n_arcs, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(c->d_fb_lp, j.t_lp.data(), sizeof(float) * n_arcs, hipMemcpyHostToDevice, s));
+    }
+  }
+  return FDNN_OK;
+}
+
+int fb_finish(fdnn_ctx *c, const FbJob &j, float *total, float *gamma, bool host, hipStream_t s) {
+  const size_t n_nodes = j.sets.nodes.size(), n_states = j.sets.col.size(), n = size_t(j.t.n_segs);
+  const size_t n_arcs = size_t(j.t.arc_ptr[n_states]), words = j.want_gamma ? size_t(j.plan.gamma_words) : 0;
+  float *tail = c->d_ag_lp.p + std::max<size_t>(n_arcs, 1);
+  FbArgs a;
+  a.d_rows = c->d_al_probs, a.d_col = c->d_al_int.p + n_nodes, a.d_state_node = c->d_al_int.p + n_nodes + n_states;
+  a.d_log_prior = j.ll->d_log_prior, a.width = j.ll->width, a.floor = j.ll->floor, a.type = j.ll->type;
+  a.d_arc_ptr = c->d_ag_int, a.d_arc_src = c->d_ag_int.p + n_states + 1, a.d_arc_lp = c->d_ag_lp;
+  a.d_start_lp = j.t.start_lp ? tail : nullptr, a.d_final_lp = j.t.final_lp ? tail + n_states : nullptr;
+  if (j.want_gamma) {
+    a.d_t_ptr = c->d_fb_int, a.d_t_src = c->d_fb_int.p + n_states + 1, a.d_t_lp = c->d_fb_lp;
+    a.d_scratch = reinterpret_cast<float *>(c->d_al_bp.p), a.d_gamma = c->d_fb_res.p + n;
+  }
+  a.d_total = c->d_fb_res;
+  launch_fb(j.plan, a, s);
+  HIP_TRY(hipGetLastError());
+  if (!host) {
+    HIP_TRY(hipMemcpyAsync(total, c->d_fb_res, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    if (words) HIP_TRY(hipMemcpyAsync(gamma, c->d_fb_res.p + n, sizeof(float) * words, hipMemcpyDeviceToDevice, s));
+    return FDNN_OK;
+  }
+  // one transfer of the totals (4 bytes a segment) and one of gamma where asked, straight into the caller's arrays
+  HIP_TRY(hipMemcpyAsync(total, c->d_fb_res, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+  if (words) HIP_TRY(hipMemcpyAsync(gamma, c->d_fb_res.p + n, sizeof(float) * words, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FDNN_OK;
+}
+
 // The host half of a compacted lazy return (lazy_compact_kernel): a compacted row is the row's inactive value followed by
 // its active nodes' probabilities in node order; expanding it = every node reads the next active value or the inactive one.
 // With AVX-512 that is one expanding load per 16 nodes (the mask's 16 bits select which lanes take the next values from

@@ -607,6 +607,77 @@ FDNN_API int fdnn_calculate_align_graph_raw(fdnn_model *m, const float *raw, int
                                             const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr,
                                             const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, int32_t *path,
                                             float *total);
+/* ------------------------------------------------------------------ alignment graphs, summed (fdnn_fb.hip)
+ * The likelihood of a segment's WHOLE graph, ln of the sum over its paths, and the state occupancies gamma[t][j], the
+ * posterior of being in state j at frame t, on the device: a keyword graph against a filler graph, an utterance's
+ * confidence, a choice between transcripts, soft boundaries, statistics over soft alignments.  The reference has no such
+ * call; every entry below extends LazyOutputActivations (dnn.cc:355-392).  THE CONTRACT IS STATED ONCE, in csrc/fdnn_fb.hpp;
+ * in short:
+ *
+ * The inputs are the alignment graphs' above, checked by the same validator.  In fp32, every + and - rounded once, nothing
+ * contracted, with two stated functions -- exp_neg(x), exp on (-inf, 0] by one fixed sequence of operations (a NaN and
+ * x < -87 give +0, no result is a denormal), and ladd(a, b) = hi + ln(1 + exp_neg(lo - hi)) with the frozen logarithm of the
+ * decoder scores (lo == -inf gives hi, hi == +inf gives +inf) --:
+ *   alpha[0][j] = start_lp[j] + e(0, j)
+ *   t >= 1: acc = -inf; for each arc a of j in order: cand = alpha[t-1][arc_src[a]] + arc_lp[a]; a NaN is never added;
+ *           acc = ladd(acc, cand);   alpha[t][j] = acc + e(t, j)
+ *   total:  the terms alpha[T-1][j] + final_lp[j], a NaN skipped, state j dealt to partial j mod 256 and added there in
+ *           ascending j, then the tree step = 128 .. 1: partial[i] = ladd(partial[i], partial[i + step]); total = partial[0]
+ *   bb:     the same recursion on the transposed graph in reversed time from final_lp (fdnn_fb_transpose: a stable counting
+ *           sort of a segment's arcs by source), bb[t][i] including i's own emission
+ *   gamma[t][j] = exp_neg(min(0, ((alpha[t][j] + bb[t][j]) - e(t, j)) - total)), row-major [t][j] per segment, segment s at
+ *           the sum of T S over the segments before it
+ *   total [n_segs] float, gamma [sum of T S] float or NULL
+ * The total is never a NaN; -inf means no path; a total that is not finite gives gamma = +0 everywhere.  gamma == NULL means
+ * forward only: no transposed tables, no backward launch, no lattice, four bytes per segment leave the device.  On any
+ * input total >= fdnn_debug_align_graph_ref's best-path total, and on a graph with exactly one path of finite score the two
+ * are equal as bits.  The order of a state's arcs is part of the input.  Total and gamma are a function of the scores and
+ * the graph alone -- not of the kernel form, the chunking or the entry point -- and equal fdnn_debug_fb_ref byte for byte.
+ * FDNN_E_ARG before anything is launched: the alignment graphs' reasons, and a lattice (4 bytes a frame and state, only
+ * where gamma is asked) above 2^30 bytes.  FDNN_E_STATE before the hidden layers have run.  The batcher, the scoring loop,
+ * device groups and the JNI shim neither route to nor look at these entry points, and every other entry point keeps its
+ * bytes.
+ *
+ * fdnn_fb_rows_device     the sweeps alone on any device-resident fp32 rows (dnn.cc:355-392): seg_T, row_off, row_ld,
+ *   state_ptr, arc_ptr and t_ptr are host tables (the plan is made from them; the host arc_ptr / t_ptr bound every arc index
+ *   on the device); d_col, d_state_node, the device copies of the graph and d_start_lp / d_final_lp as
+ *   fdnn_align_graph_rows_device; d_t_ptr [N + 1], d_t_src, d_t_lp [arcs] device copies of the transposed tables.  A source or
+ *   destination outside [0, S) makes that candidate a NaN and reads nothing.  d_gamma may be NULL: t_ptr and the d_t_ tables
+ *   are then not read and no scratch is needed.  d_scratch: at least the fp32 words fdnn_fb_scratch_words names (NULL when
+ *   0).  d_total [n_segs], d_gamma [sum T S].  Enqueued on `stream`, not synchronised.
+ * fdnn_fb_scratch_words   the scratch of that call: T S words a segment where gamma is wanted, else 0 (dnn.cc:355-392);
+ *   above 2^30 bytes FDNN_E_ARG.
+ * fdnn_fb_transpose       host code: t_ptr [N + 1], t_src [arcs] (the DESTINATION, local to the segment), t_lp [arcs] from a
+ *   call's arc tables (dnn.cc:355-392); FDNN_E_ARG for a source outside [0, S).  The one definition of the backward order.
+ * fdnn_ctx_fb             host tables and host results, host-synchronous, over rows of a context whose hidden layers have run
+ *   (dnn.cc:355-392): the graphs' node sets into a context-owned buffer, the sweeps, then one transfer of total and one of
+ *   gamma where it is not NULL.
+ * fdnn_ctx_fb_device      the same with device result buffers, enqueued on `stream`; the host tables are read before it
+ *   returns (dnn.cc:355-392).
+ * fdnn_calculate_fb       one call on a pooled context (dnn.cc:355-392): seg_rows must cover [0, n); a large n goes chunk by
+ *   chunk, and the sweeps run ONCE behind the last chunk: a cut segment's results are the uncut ones.
+ * fdnn_calculate_fb_raw   the same from raw feature frames [n][raw_dim] (dnn.cc:355-392); every segment is an utterance of
+ *   its own. */
+FDNN_API int fdnn_fb_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                                 const int32_t *state_ptr, const int32_t *arc_ptr, const int32_t *t_ptr, int n_segs, const int32_t *d_col,
+                                 const int32_t *d_state_node, const int32_t *d_arc_ptr, const int32_t *d_arc_src, const float *d_arc_lp,
+                                 const float *d_start_lp, const float *d_final_lp, const int32_t *d_t_ptr, const int32_t *d_t_src, const float *d_t_lp,
+                                 void *d_scratch, long long scratch_words, float *d_total, float *d_gamma, void *stream);
+FDNN_API int fdnn_fb_scratch_words(const int32_t *seg_T, const int32_t *state_ptr, int n_segs, int want_gamma, long long *words);
+FDNN_API int fdnn_fb_transpose(const int32_t *state_ptr, int n_segs, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                               int32_t *t_ptr, int32_t *t_src, float *t_lp);
+FDNN_API int fdnn_ctx_fb(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                         const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp,
+                         float *total, float *gamma);
+FDNN_API int fdnn_ctx_fb_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp,
+                                const float *final_lp, float *d_total, float *d_gamma, void *stream);
+FDNN_API int fdnn_calculate_fb(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr,
+                               int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                               const float *start_lp, const float *final_lp, float *total, float *gamma);
+FDNN_API int fdnn_calculate_fb_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                   const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src,
+                                   const float *arc_lp, const float *start_lp, const float *final_lp, float *total, float *gamma);
 /* Last hidden layer's u8 activations, n x hidden_dim (quantized_activations_). */
 FDNN_API int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out);
 
@@ -1017,6 +1088,30 @@ FDNN_API int fdnn_debug_align_graph_ref(const float *rows, const int32_t *seg_T,
                                         const int32_t *state_ptr, int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior,
                                         int width, float floor, int type, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
                                         const float *start_lp, const float *final_lp, int32_t *path, float *total);
+
+/* Alignment graphs, summed (LazyOutputActivations, dnn.cc:355-392), tests and tools.
+ * fdnn_debug_fb_launches     process-wide counts since load, returns 4: out[0] forward launches of the wave form, [1] forward
+ *   of the workgroup form, [2] backward of the wave form, [3] backward of the workgroup form.  A counter of their own: not
+ *   in the launch recorder's table (fdnn_note.hpp).
+ * fdnn_debug_set_fb_kernel   process-wide: 0 the plan's rule (one wave per segment where S <= 64, else 256 threads), 1 the
+ *   wave form where allowed (S <= 256), 2 always the workgroup form -- the same bytes either way (dnn.cc:355-392).
+ * fdnn_debug_fb_limits       returns 8: out[0] the most states, [1] segments per launch, [2] the wave form's most states,
+ *   [3] the most arcs of a segment, [4] the arcs of a segment the wave form stages in LDS, [5] the total's partial sums,
+ *   [6] the scratch cap of a call in MiB, [7] the most states at which the rule takes the wave form (dnn.cc:355-392).
+ * fdnn_debug_fb_ref          fdnn_fb_rows_device from the host restatement (fdnn_fb.hpp) on host rows and host arrays; type
+ *   as fdnn_debug_align_ref; gamma, and then t_ptr, t_src, t_lp, may be NULL; host code, no device needed (dnn.cc:355-392).
+ * fdnn_debug_fb_math_ref     the two stated functions on host arrays: op 0 out[i] = exp_neg(a[i]) (b not read), op 1 out[i] =
+ *   ladd(a[i], b[i]); host code (dnn.cc:355-392).
+ * fdnn_debug_fb_math_device  the same on device arrays in a trivial kernel, enqueued on `stream` (dnn.cc:355-392). */
+FDNN_API int fdnn_debug_fb_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_set_fb_kernel(int mode);
+FDNN_API int fdnn_debug_fb_limits(int *out, int cap);
+FDNN_API int fdnn_debug_fb_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr,
+                               int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior, int width, float floor, int type,
+                               const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp,
+                               const int32_t *t_ptr, const int32_t *t_src, const float *t_lp, float *total, float *gamma);
+FDNN_API int fdnn_debug_fb_math_ref(int op, const float *a, const float *b, float *out, long long n);
+FDNN_API int fdnn_debug_fb_math_device(int op, const float *d_a, const float *d_b, float *d_out, long long n, void *stream);
 
 /* Splicing through a segment table in device memory (the scoring loop's live batches, fdnn_splice.hip), tests and tools.
  * fdnn_debug_splice_table   the splice alone, host in and host out: raw [raw_frames][raw_dim] -> x [rows][input_dim] under the
