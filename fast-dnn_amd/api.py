@@ -244,6 +244,21 @@ SIGNATURES = {
                                     C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p]),
     "fdnn_debug_fb_math_ref": (C.c_int, [C.c_int, _c_f32p, _c_f32p, _c_f32p, C.c_longlong]),
     "fdnn_debug_fb_math_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "fdnn_fb_frames_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, _c_i32p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "fdnn_fb_frames_scratch_words": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.POINTER(C.c_longlong)]),
+    "fdnn_ctx_fb_frames": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, C.c_int,
+                                     _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_ctx_fb_frames_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p,
+                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_calculate_fb_frames": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p,
+                                           _c_f32p, _c_f32p, _c_f32p, C.c_int, _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_calculate_fb_frames_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p,
+                                               _c_f32p, _c_f32p, _c_f32p, C.c_int, _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_debug_fb_frames_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_fb_frames_ref": (C.c_int, [_c_f32p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, C.c_int,
+                                           C.c_float, C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, C.c_int, _c_f32p, _c_f32p, _c_f32p]),
     "fdnn_debug_ln_ref": (C.c_int, [_c_f32p, C.c_longlong, _c_f32p]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -1258,6 +1273,75 @@ def fb_math_device(op: int, d_a: int, d_b: int, d_out: int, n: int, stream: int 
     _check(lib().fdnn_debug_fb_math_device(int(op), C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
 
 
+# ---------------------------------------------------------------- alignment graphs, summed, frame by frame (fdnn_fb_frames.hip)
+# The frames form: forward only.  ``free_start`` lets a path begin at any frame; ``alpha_in`` float32 [states of the call] is
+# the recursion's row from the frame before the call's first row (None: the call begins the stream); the results are
+# frame_total float32 [rows of the call] and alpha_out float32 [states], what the next call takes as ``alpha_in``.
+def fb_frames_ref(rows, segT, rowOff, rowLd, graphs, col, stateNode=None, log_prior=None, floor: float = -np.inf, type: int = ALIGN_SCORES,
+                  free_start: bool = False, alpha_in=None):
+    """The frames form from the host restatement (``fdnn_debug_fb_frames_ref``; host code, no device): the arguments of
+    ``fb_ref`` -> (frame_total float32 [sum of T], alpha_out float32 [states])."""
+    r = np.ascontiguousarray(rows, dtype=np.float32).ravel()
+    sp, _, ap, src, alp, start, final = _graph_tables(graphs)
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, sp)
+    c = np.ascontiguousarray(col, dtype=np.int32)
+    nd = None if stateNode is None else np.ascontiguousarray(stateNode, dtype=np.int32)
+    lp = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float32)
+    ain = _carry_in(alpha_in, int(sp[-1]))
+    if t.size and ((off + (t.astype(np.int64) - 1) * ld + ld > r.size).any() or (off < 0).any() or c.size < int(sp[-1])):
+        raise ValueError("a segment's rows run past the rows, or col is shorter than the graphs")
+    frame_total, alpha_out = np.empty(int(t.sum()), np.float32), np.empty(int(sp[-1]), np.float32)
+    _check(lib().fdnn_debug_fb_frames_ref(r.ctypes.data_as(_c_f32p), t.ctypes.data_as(_c_i32p), off.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                          ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, c.ctypes.data_as(_c_i32p), _ip(nd), _fp(lp),
+                                          0 if lp is None else lp.size, C.c_float(float(floor)), int(type), _ip(ap), _ip(src), _fp(alp), _fp(start),
+                                          _fp(final), int(bool(free_start)), _fp(ain), _fp(alpha_out), _fp(frame_total)))
+    return frame_total, alpha_out
+
+
+def _carry_in(alpha_in, n_states: int):
+    if alpha_in is None:
+        return None
+    a = np.ascontiguousarray(alpha_in, dtype=np.float32)
+    if a.shape != (n_states,):
+        raise ValueError("alpha_in must be [states of the call]")
+    return a
+
+
+def fb_frames_scratch_words(segT, statePtr) -> int:
+    """The fp32 scratch words ``fb_frames_rows_device`` needs (``fdnn_fb_frames_scratch_words``): the lattice, the sum of T S."""
+    t = np.ascontiguousarray(segT, dtype=np.int32)
+    sp = np.ascontiguousarray(statePtr, dtype=np.int32)
+    words = C.c_longlong(0)
+    _check(lib().fdnn_fb_frames_scratch_words(t.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, C.byref(words)))
+    return int(words.value)
+
+
+def fb_frames_rows_device(ll, d_rows: int, segT, rowOff, rowLd, statePtr, arcPtr, d_col: int, d_state_node: int, d_arc_ptr: int, d_arc_src: int,
+                          d_arc_lp: int, d_start_lp: int, d_final_lp: int, free_start: bool, d_alpha_in: int, d_alpha_out: int, d_scratch: int,
+                          scratch_words: int, d_frame_total: int, stream: int = 0) -> None:
+    """The sweep and the row totals alone on device-resident fp32 rows (``fdnn_fb_frames_rows_device``): host tables segT,
+    rowOff, rowLd, statePtr and arcPtr, device pointers for everything they index (0 for NULL); ``ll`` a ``Loglik`` or None
+    (the rows are scores).  Enqueued on ``stream``, not synchronised."""
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, statePtr)
+    ap = np.ascontiguousarray(arcPtr, dtype=np.int32)
+    if ap.shape != (int(sp[-1]) + 1,):
+        raise ValueError("arcPtr must be [states + 1]")
+    _check(lib().fdnn_fb_frames_rows_device(None if ll is None else ll.handle, C.c_void_p(d_rows), t.ctypes.data_as(_c_i32p),
+                                            off.ctypes.data_as(C.POINTER(C.c_longlong)), ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p),
+                                            ap.ctypes.data_as(_c_i32p), t.size, C.c_void_p(d_col), C.c_void_p(d_state_node), C.c_void_p(d_arc_ptr),
+                                            C.c_void_p(d_arc_src), C.c_void_p(d_arc_lp), C.c_void_p(d_start_lp), C.c_void_p(d_final_lp),
+                                            int(bool(free_start)), C.c_void_p(d_alpha_in), C.c_void_p(d_alpha_out), C.c_void_p(d_scratch),
+                                            int(scratch_words), C.c_void_p(d_frame_total), C.c_void_p(stream)))
+
+
+def fb_frames_launches():
+    """Process-wide counts since load: launches (sweep wave form, sweep workgroup form, row totals)."""
+    buf = (C.c_ulonglong * 3)()
+    if lib().fdnn_debug_fb_frames_launches(buf, 3) != 3:
+        raise RuntimeError("fdnn_debug_fb_frames_launches")
+    return tuple(int(v) for v in buf)
+
+
 def _fb_out(n_segs: int, segRows, sp, want_gamma: bool):
     total = np.empty(n_segs, np.float32)
     words = int((np.diff(segRows.astype(np.int64)) * np.diff(sp.astype(np.int64))).sum()) if n_segs else 0
@@ -1538,6 +1622,26 @@ class LazyContext:
         sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
         _check(lib().fdnn_ctx_fb_device(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
                                         C.c_void_p(d_total), C.c_void_p(d_gamma), C.c_void_p(stream)))
+
+    def fbFrames(self, ll: "Loglik", segRows, graphs, free_start: bool = False, alpha_in=None):
+        """The frames form of ``forwardBackward``, forward only, over rows of the context (``fdnn_ctx_fb_frames``) ->
+        (frame_total float32 [rows], alpha_out float32 [states]): the graph's likelihood at every frame, and the last row
+        for the next call's ``alpha_in``."""
+        sr, sp, st, ap, src, lp, start, final, n_segs, rows = _graph_call_tables(segRows, graphs)
+        ain = _carry_in(alpha_in, int(sp[-1]))
+        frame_total, alpha_out = np.empty(rows, np.float32), np.empty(int(sp[-1]), np.float32)
+        _check(lib().fdnn_ctx_fb_frames(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                        int(bool(free_start)), _fp(ain), _fp(alpha_out), _fp(frame_total)))
+        return frame_total, alpha_out
+
+    def fbFramesDevice(self, ll: "Loglik", segRows, graphs, d_frame_total: int, free_start: bool = False, d_alpha_in: int = 0, d_alpha_out: int = 0,
+                       stream: int = 0) -> None:
+        """The same with device carry arrays and device results (0 for none), enqueued on ``stream`` and not synchronised
+        (``fdnn_ctx_fb_frames_device``)."""
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        _check(lib().fdnn_ctx_fb_frames_device(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start),
+                                               _fp(final), int(bool(free_start)), C.c_void_p(d_alpha_in), C.c_void_p(d_alpha_out),
+                                               C.c_void_p(d_frame_total), C.c_void_p(stream)))
 
     def calculateOutputLoglikDevice(self, ll: "Loglik", d_out: int, stream: int = 0) -> None:
         """The same into a device buffer [frames][outputDimension] of the handle's type, enqueued on ``stream``, not
@@ -2395,6 +2499,36 @@ class QuantizedDnn:
         _check(lib().fdnn_calculate_fb_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], ll.handle, _ip(sr), _ip(sp), n_segs,
                                            _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final), _fp(total), _fp(gamma)))
         return total, gamma
+
+    def calculateFbFrames(self, input, ll: "Loglik", segRows, graphs, free_start: bool = False, alpha_in=None):
+        """The likelihood of alignment graphs at every frame in one call (``fdnn_calculate_fb_frames``; segRows must cover
+        [0, frames)): hidden layers, the graphs' node sets, the forward sweep and the row totals on the device ->
+        (frame_total float32 [frames], alpha_out float32 [states]), as ``LazyContext.fbFrames``."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        ain = _carry_in(alpha_in, int(sp[-1]))
+        frame_total, alpha_out = np.empty(n, np.float32), np.empty(int(sp[-1]), np.float32)
+        _check(lib().fdnn_calculate_fb_frames(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(), ll.handle,
+                                              _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                              int(bool(free_start)), _fp(ain), _fp(alpha_out), _fp(frame_total)))
+        return frame_total, alpha_out
+
+    def calculateFbFramesRaw(self, raw, ll: "Loglik", segRows, graphs, free_start: bool = False, alpha_in=None):
+        """``calculateFbFrames`` on raw frames [n][rawDim], spliced on the device, every segment an utterance of its own
+        (``fdnn_calculate_fb_frames_raw``)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError("raw must be [frames][rawDim]")
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        ain = _carry_in(alpha_in, int(sp[-1]))
+        frame_total, alpha_out = np.empty(r.shape[0], np.float32), np.empty(int(sp[-1]), np.float32)
+        _check(lib().fdnn_calculate_fb_frames_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], ll.handle, _ip(sr), _ip(sp),
+                                                  n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final), int(bool(free_start)),
+                                                  _fp(ain), _fp(alpha_out), _fp(frame_total)))
+        return frame_total, alpha_out
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))

@@ -1632,6 +1632,185 @@ int fdnn_debug_fb_math_device(int op, const float *d_a, const float *d_b, float 
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- alignment graphs, summed, frame by frame (fdnn_fb_frames.hip)
+// The sweep and the row totals alone.  The host tables are checked as the sibling's; the lattice is always needed.
+static int fb_frames_plan(const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr, const int32_t *arc_ptr,
+                          int n_segs, fdnn::fb_frames::Plan *p) {
+  *p = fdnn::fb_frames::plan(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs, fdnn::fb_kernel_mode());
+  if (p->scratch_words * 4 > fdnn::fb_frames::kMaxScratchBytes)
+    return fail(FDNN_E_ARG, "fb frames: the lattice of the call is above " + std::to_string(fdnn::fb_frames::kMaxScratchBytes) + " bytes");
+  return FDNN_OK;
+}
+
+int fdnn_fb_frames_scratch_words(const int32_t *seg_T, const int32_t *state_ptr, int n_segs, long long *words) {
+  if (!words) return fail(FDNN_E_ARG, "null argument");
+  const std::vector<long long> off(size_t(std::max(n_segs, 0)), 0);
+  const std::vector<int32_t> ld(size_t(std::max(n_segs, 0)), 1);
+  if (int rc = align_graph_rows_tables(seg_T, off.data(), ld.data(), state_ptr, nullptr, n_segs)) return rc;
+  fdnn::fb_frames::Plan p;
+  if (int rc = fb_frames_plan(seg_T, off.data(), ld.data(), state_ptr, nullptr, n_segs, &p)) return rc;
+  *words = p.scratch_words;
+  return FDNN_OK;
+}
+
+int fdnn_fb_frames_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                               const int32_t *state_ptr, const int32_t *arc_ptr, int n_segs, const int32_t *d_col, const int32_t *d_state_node,
+                               const int32_t *d_arc_ptr, const int32_t *d_arc_src, const float *d_arc_lp, const float *d_start_lp,
+                               const float *d_final_lp, int free_start, const float *d_alpha_in, float *d_alpha_out, void *d_scratch,
+                               long long scratch_words, float *d_frame_total, void *stream) {
+  if (free_start != 0 && free_start != 1) return fail(FDNN_E_ARG, "fb frames: free_start is 0 or 1");
+  if (n_segs > 0 && !arc_ptr) return fail(FDNN_E_ARG, "fb frames, segment 0: malformed tables");
+  if (int rc = align_graph_rows_tables(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  const bool arcs = arc_ptr[state_ptr[n_segs]] > 0;
+  if (!d_rows || !d_col || !d_arc_ptr || (arcs && (!d_arc_src || !d_arc_lp)) || !d_frame_total || (ll && !d_state_node))
+    return fail(FDNN_E_ARG, "null buffer");
+  const uintptr_t all = reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_col) | reinterpret_cast<uintptr_t>(d_state_node) |
+                        reinterpret_cast<uintptr_t>(d_arc_ptr) | reinterpret_cast<uintptr_t>(d_arc_src) | reinterpret_cast<uintptr_t>(d_arc_lp) |
+                        reinterpret_cast<uintptr_t>(d_start_lp) | reinterpret_cast<uintptr_t>(d_final_lp) | reinterpret_cast<uintptr_t>(d_alpha_in) |
+                        reinterpret_cast<uintptr_t>(d_alpha_out) | reinterpret_cast<uintptr_t>(d_scratch) | reinterpret_cast<uintptr_t>(d_frame_total);
+  if (all & 3) return fail(FDNN_E_ARG, "buffers must have their elements' alignment, the scratch 4 bytes");
+  fdnn::fb_frames::Plan p;
+  if (int rc = fb_frames_plan(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs, &p)) return rc;
+  if (!d_scratch || scratch_words < p.scratch_words)
+    return fail(FDNN_E_ARG, "fb frames: the call needs " + std::to_string(p.scratch_words) + " scratch words (fdnn_fb_frames_scratch_words)");
+  fdnn::FbFramesArgs a;
+  a.d_rows = d_rows, a.d_col = d_col, a.d_state_node = d_state_node, a.d_arc_ptr = d_arc_ptr, a.d_arc_src = d_arc_src, a.d_arc_lp = d_arc_lp;
+  a.d_start_lp = d_start_lp, a.d_final_lp = d_final_lp, a.free_start = free_start != 0, a.d_alpha_in = d_alpha_in, a.d_alpha_out = d_alpha_out;
+  a.d_scratch = static_cast<float *>(d_scratch), a.d_frame_total = d_frame_total;
+  if (ll) a.d_log_prior = ll->d_log_prior, a.width = ll->width, a.floor = ll->floor, a.type = ll->type;
+  int dev = 0;
+  if (ll) dev = ll->device;
+  else if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  DeviceGuard g(dev);
+  fdnn::launch_fb_frames(p, a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+// The front of every frames-form call through a model: the handle, then the tables (fb_frames_prepare names the first bad segment)
+static int fb_frames_front(const fdnn_model *m, const fdnn_loglik *ll, const fdnn::align_graph::Tables &t, int free_start, const float *alpha_in,
+                           int ctx_rows, fdnn::FbFramesJob *j) {
+  if (int rc = fdnn::check_loglik(m, ll)) return rc;
+  if (t.n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
+  if (free_start != 0 && free_start != 1) return fail(FDNN_E_ARG, "fb frames: free_start is 0 or 1");
+  j->ll = ll, j->t = t, j->free_start = free_start != 0, j->alpha_in = alpha_in;
+  return fdnn::fb_frames_prepare(j, m->hm.hdr.out_dim, ctx_rows);
+}
+
+static int ctx_fb_frames(fdnn_ctx *c, const fdnn_loglik *ll, const fdnn::align_graph::Tables &t, int free_start, const float *alpha_in, float *alpha_out,
+                         float *frame_total, bool host, hipStream_t s) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  fdnn::FbFramesJob j;
+  if (int rc = fb_frames_front(c->m, ll, t, free_start, alpha_in, c->n, &j)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (t.n_segs == 0) return FDNN_OK;
+  if (!frame_total) return fail(FDNN_E_ARG, "null result buffer");
+  if ((reinterpret_cast<uintptr_t>(alpha_in) | reinterpret_cast<uintptr_t>(alpha_out) | reinterpret_cast<uintptr_t>(frame_total)) & 3)
+    return fail(FDNN_E_ARG, "buffers must have their elements' alignment");
+  const std::vector<sets::Seg> segs = sets::slice(j.tables(), t.seg_rows[0], t.seg_rows[t.n_segs]);
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  int rc = fdnn::fb_frames_stage(c, j, host, s);
+  SetsCall sc;
+  sc.first = t.seg_rows[0], sc.segs = &segs, sc.d_nodes = c->d_al_int, sc.d_probs = c->d_al_probs, sc.d_inactive = c->d_al_inact;
+  if (!rc) rc = run_sets(c, sc, s);
+  if (!rc) rc = fdnn::fb_frames_finish(c, j, alpha_out, frame_total, host, s);
+  if (rc && host) hipStreamSynchronize(s);
+  return rc;
+}
+
+int fdnn_ctx_fb_frames(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                       const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, int free_start,
+                       const float *alpha_in, float *alpha_out, float *frame_total) {
+  return ctx_fb_frames(c, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), free_start, alpha_in,
+                       alpha_out, frame_total, true, c ? c->stream : nullptr);
+}
+
+int fdnn_ctx_fb_frames_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                              const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp,
+                              int free_start, const float *d_alpha_in, float *d_alpha_out, float *d_frame_total, void *stream) {
+  return ctx_fb_frames(c, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), free_start, d_alpha_in,
+                       d_alpha_out, d_frame_total, false, static_cast<hipStream_t>(stream));
+}
+
+// One-call forms: hidden layers + the graphs' node sets chunk by chunk into the context's buffers (the sibling's sink), the
+// sweep and the row totals ONCE behind the last chunk, inside the same use of the context.
+static int calculate_fb_frames(fdnn_model *m, const Pass &p, fdnn::FbFramesJob &j, float *alpha_out, float *frame_total, int n) {
+  return score_chunks(m, frame_chunks(n, m), p, nullptr, [&](fdnn_ctx *c, hipStream_t s) { return fdnn::fb_frames_stage(c, j, true, s); },
+                      [&](fdnn_ctx *c, hipStream_t s) {
+                        const int rc = fdnn::fb_frames_finish(c, j, alpha_out, frame_total, true, s);
+                        if (rc) hipStreamSynchronize(s);
+                        return rc;
+                      });
+}
+
+int fdnn_calculate_fb_frames(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr,
+                             int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                             const float *start_lp, const float *final_lp, int free_start, const float *alpha_in, float *alpha_out,
+                             float *frame_total) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  fdnn::FbFramesJob j;
+  if (int rc = fb_frames_front(m, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), free_start,
+                               alpha_in, n, &j))
+    return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!x || !frame_total) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = check_input_width(m, dim)) return rc;
+  const sets::Tables t = j.tables();
+  return calculate_fb_frames(m, Pass::host_align("fdnn_calculate_fb_frames", x, t), j, alpha_out, frame_total, n);
+}
+
+int fdnn_calculate_fb_frames_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                 const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src,
+                                 const float *arc_lp, const float *start_lp, const float *final_lp, int free_start, const float *alpha_in,
+                                 float *alpha_out, float *frame_total) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  if (int rc = fdnn::splice_check(spec, raw_dim)) return rc;
+  fdnn::FbFramesJob j;
+  if (int rc = fb_frames_front(m, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), free_start,
+                               alpha_in, n, &j))
+    return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!raw || !frame_total) return fail(FDNN_E_ARG, "null buffer");
+  // every segment is an utterance of its own: its edges repeat its own first and last frame
+  std::vector<SpliceSeg> segs;
+  for (int s = 0; s < n_segs; ++s) segs.push_back(SpliceSeg{seg_rows[s], seg_rows[s], seg_rows[s], seg_rows[s + 1] - 1});
+  const sets::Tables t = j.tables();
+  return calculate_fb_frames(m, Pass::raw_align("fdnn_calculate_fb_frames_raw", {spec.get(), &segs, raw, n}, t), j, alpha_out, frame_total, n);
+}
+
+int fdnn_debug_fb_frames_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 3, fdnn::fb_frames_launch_counts); }
+
+// The recursion in plain C++ (fdnn_fb_frames.hpp: ref), no device: rows, tables and handle values as fdnn_debug_fb_ref, the
+// carry arrays on the host.
+int fdnn_debug_fb_frames_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr,
+                             int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior, int width, float floor, int type,
+                             const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp,
+                             int free_start, const float *alpha_in, float *alpha_out, float *frame_total) {
+  if (free_start != 0 && free_start != 1) return fail(FDNN_E_ARG, "fb frames: free_start is 0 or 1");
+  if (n_segs > 0 && !arc_ptr) return fail(FDNN_E_ARG, "fb frames, segment 0: malformed tables");
+  if (int rc = align_graph_rows_tables(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  if (type != fdnn::align::kScores && (fdnn::loglik::check_handle(log_prior, width, floor, type) != 0 || !state_node))
+    return fail(FDNN_E_ARG, "log_prior [width] finite, the floor -inf or finite (F16: not below -65504), the type F32, F16 or -1 (scores)");
+  if (!rows || !col || !frame_total || (arc_ptr[state_ptr[n_segs]] > 0 && (!arc_src || !arc_lp))) return fail(FDNN_E_ARG, "null buffer");
+  size_t at = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const int b = state_ptr[s], S = state_ptr[s + 1] - b;
+    fdnn::fb_frames::ref(reinterpret_cast<const uint32_t *>(rows) + row_off[s], seg_T[s], row_ld[s], col + b, state_node ? state_node + b : nullptr, S,
+                         log_prior, width, floor, type, arc_ptr + b, arc_src, arc_lp, start_lp ? start_lp + b : nullptr,
+                         final_lp ? final_lp + b : nullptr, free_start != 0, alpha_in ? reinterpret_cast<const uint32_t *>(alpha_in) + b : nullptr,
+                         alpha_out ? reinterpret_cast<uint32_t *>(alpha_out) + b : nullptr, reinterpret_cast<uint32_t *>(frame_total) + at);
+    at += size_t(seg_T[s]);
+  }
+  return FDNN_OK;
+}
+
 int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
   if (!c || !out) return fail(FDNN_E_ARG, "null argument");
   if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");

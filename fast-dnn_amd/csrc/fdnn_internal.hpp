@@ -469,6 +469,32 @@ int fb_stage(fdnn_ctx *c, const FbJob &j, hipStream_t s);
 // [n_segs], and of gamma [sum T S] where asked, and s synchronised; false -- copied to the caller's device buffers on s.
 int fb_finish(fdnn_ctx *c, const FbJob &j, float *total, float *gamma, bool host, hipStream_t s);
 
+// ---------------------------------------------------------------- alignment graphs, summed, frame by frame (fdnn_fb_frames.hip)
+// One frames-form call's validated host tables and what is derived from them before anything is launched
+// (fb_frames_prepare): as FbJob without the transposed tables, with fb_frames' plan.  The sets step is the sibling's.
+struct FbFramesJob {
+  const fdnn_loglik *ll = nullptr;
+  align_graph::Tables t;
+  bool free_start = false;
+  const float *alpha_in = nullptr;  // [states of the call] or null: host memory (host = true below) or device memory
+  align::Sets sets;
+  std::vector<int32_t> seg_T, row_ld;
+  std::vector<long long> row_off;  // segment s's block in the ragged probabilities
+  long long nnz = 0;
+  int rows = 0;                    // seg_rows[n_segs] - seg_rows[0]
+  fb_frames::Plan plan;
+  sets::Tables tables() const { return {t.seg_rows, sets.set_ptr.data(), t.n_segs}; }
+};
+// FDNN_E_ARG naming the first bad segment (align_graph::check), the sum of rows x len past an int32 or the lattice past
+// fb_frames::kMaxScratchBytes; else fills j from its table pointers.  Nothing is launched.
+int fb_frames_prepare(FbFramesJob *j, int output_dim, int ctx_rows);
+// The context's buffers made large enough, the tables and (host = true) alpha_in uploaded on s.
+int fb_frames_stage(fdnn_ctx *c, const FbFramesJob &j, bool host, hipStream_t s);
+// The sweep and the row totals over the probabilities that the sets calls left in c->d_al_probs, then: host = true -- ONE
+// transfer of frame_total [rows] and, where asked, alpha_out [states], and s synchronised; false -- copied to the caller's
+// device buffers on s.
+int fb_frames_finish(fdnn_ctx *c, const FbFramesJob &j, float *alpha_out, float *frame_total, bool host, hipStream_t s);
+
 // ---------------------------------------------------------------- one scoring pass, one chunk loop
 // Hidden layers + what the pass's sink asks for, chunk by chunk, on context c and stream s; every pointer a chunk uses comes
 // from pass::chunk_view.  Per chunk: the rows in (spliced / uploaded / as they are), host bits up, the hidden layers, the sink's

@@ -17,6 +17,7 @@
 #include "fdnn_align.hpp"
 #include "fdnn_align_graph.hpp"
 #include "fdnn_fb.hpp"
+#include "fdnn_fb_frames.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -358,6 +359,28 @@ void launch_fb_math(int op, const float *d_a, const float *d_b, float *d_out, lo
 void fb_launch_counts(unsigned long long out[4]);  // launches so far: forward wave, forward workgroup, backward wave, backward workgroup
 int fb_kernel_mode();  // fdnn_debug_set_fb_kernel: 0 the plan's rule, 1 wave where allowed, 2 workgroup
 void fb_kernel_mode(int mode);
+
+// Alignment graphs, summed, frame by frame (fdnn_fb_frames.hip; the contract, the plan and the host restatement:
+// fdnn_fb_frames.hpp): per launch of the plan the forward sweep, then the row totals over the lattice it left.  rows .. the
+// arc tables and d_start_lp / d_final_lp as FbArgs.  d_alpha_in / d_alpha_out [states of the call] or null; d_scratch:
+// p.scratch_words fp32 words, the lattice; d_frame_total [p.total_rows].  The forms follow fb_kernel_mode().
+struct FbFramesArgs {
+  const float *d_rows = nullptr;
+  const int32_t *d_col = nullptr, *d_state_node = nullptr;
+  const float *d_log_prior = nullptr;
+  int width = 0;
+  float floor = 0.0f;
+  int type = align::kScores;
+  const int32_t *d_arc_ptr = nullptr, *d_arc_src = nullptr;
+  const float *d_arc_lp = nullptr, *d_start_lp = nullptr, *d_final_lp = nullptr;
+  bool free_start = false;
+  const float *d_alpha_in = nullptr;
+  float *d_alpha_out = nullptr;
+  float *d_scratch = nullptr;
+  float *d_frame_total = nullptr;
+};
+void launch_fb_frames(const fb_frames::Plan &p, const FbFramesArgs &a, hipStream_t s);
+void fb_frames_launch_counts(unsigned long long out[3]);  // launches so far: sweep wave, sweep workgroup, row totals
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

@@ -1319,6 +1319,80 @@ int fb_finish(fdnn_ctx *c, const FbJob &j, float *total, float *gamma, bool host
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- alignment graphs, summed, frame by frame (fdnn_fb_frames.hip)
+int fb_frames_prepare(FbFramesJob *j, int output_dim, int ctx_rows) {
+  align_graph::Why why;
+  const int bad = align_graph::check(j->t, output_dim, ctx_rows, &why);
+  if (bad) return fail(FDNN_E_ARG, "fb frames, segment " + std::to_string(-bad - 1) + ": " + align_graph::why_text(why));
+  const int n = j->t.n_segs;
+  j->sets = align::build_sets(j->t.state_ptr, j->t.states, n);
+  j->seg_T.resize(size_t(n)), j->row_ld.resize(size_t(n)), j->row_off.resize(size_t(n));
+  j->nnz = 0;
+  for (int s = 0; s < n; ++s) {
+    j->seg_T[size_t(s)] = j->t.seg_rows[s + 1] - j->t.seg_rows[s];
+    j->row_ld[size_t(s)] = j->sets.set_ptr[size_t(s) + 1] - j->sets.set_ptr[size_t(s)];
+    j->row_off[size_t(s)] = j->nnz;
+    j->nnz += static_cast<long long>(j->seg_T[size_t(s)]) * j->row_ld[size_t(s)];
+    if (j->nnz > INT32_MAX)
+      return fail(FDNN_E_ARG, "fb frames, segment " + std::to_string(s) + ": the sum of rows x distinct nodes over the segments must fit an int32");
+  }
+  j->rows = n ? j->t.seg_rows[n] - j->t.seg_rows[0] : 0;
+  j->plan = fb_frames::plan(j->seg_T.data(), j->row_off.data(), j->row_ld.data(), j->t.state_ptr, j->t.arc_ptr, n, fb_kernel_mode());
+  if (j->plan.scratch_words * 4 > fb_frames::kMaxScratchBytes)
+    return fail(FDNN_E_ARG, "fb frames: the lattice of the call (" + std::to_string(j->plan.scratch_words * 4) + " bytes) is above " +
+                                std::to_string(fb_frames::kMaxScratchBytes));
+  return FDNN_OK;
+}
+
+// d_fb_res holds frame_total [rows], then alpha_out [states], then alpha_in [states]
+int fb_frames_stage(fdnn_ctx *c, const FbFramesJob &j, bool host, hipStream_t s) {
+  const size_t n_nodes = j.sets.nodes.size(), n_states = j.sets.col.size(), n_arcs = size_t(j.t.arc_ptr[n_states]);
+  const size_t arcs1 = std::max<size_t>(n_arcs, 1);
+  HIP_TRY(c->d_al_int.reserve(n_nodes + 2 * n_states));
+  HIP_TRY(c->d_ag_int.reserve(n_states + 1 + arcs1));
+  HIP_TRY(c->d_ag_lp.reserve(arcs1 + 2 * n_states));
+  HIP_TRY(c->d_al_probs.reserve(std::max<size_t>(size_t(j.nnz), 1)));
+  HIP_TRY(c->d_al_inact.reserve(std::max<size_t>(size_t(j.rows), 1)));
+  HIP_TRY(c->d_al_bp.reserve(std::max<size_t>(size_t(j.plan.scratch_words), 2)));
+  HIP_TRY(c->d_fb_res.reserve(size_t(j.rows) + 2 * n_states));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int, j.sets.nodes.data(), sizeof(int32_t) * n_nodes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int.p + n_nodes, j.sets.col.data(), sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int.p + n_nodes + n_states, j.t.states, sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_ag_int, j.t.arc_ptr, sizeof(int32_t) * (n_states + 1), hipMemcpyHostToDevice, s));
+  if (n_arcs) {
+    HIP_TRY(hipMemcpyAsync(c->d_ag_int.p + n_states + 1, j.t.arc_src, sizeof(int32_t) * n_arcs, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->d_ag_lp, j.t.arc_lp, sizeof(float) * n_arcs, hipMemcpyHostToDevice, s));
+  }
+  float *tail = c->d_ag_lp.p + arcs1;
+  if (j.t.start_lp) HIP_TRY(hipMemcpyAsync(tail, j.t.start_lp, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  if (j.t.final_lp) HIP_TRY(hipMemcpyAsync(tail + n_states, j.t.final_lp, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  if (j.alpha_in && host)
+    HIP_TRY(hipMemcpyAsync(c->d_fb_res.p + size_t(j.rows) + n_states, j.alpha_in, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  return FDNN_OK;
+}
+
+int fb_frames_finish(fdnn_ctx *c, const FbFramesJob &j, float *alpha_out, float *frame_total, bool host, hipStream_t s) {
+  const size_t n_nodes = j.sets.nodes.size(), n_states = j.sets.col.size(), rows = size_t(j.rows);
+  const size_t n_arcs = size_t(j.t.arc_ptr[n_states]);
+  float *tail = c->d_ag_lp.p + std::max<size_t>(n_arcs, 1);
+  FbFramesArgs a;
+  a.d_rows = c->d_al_probs, a.d_col = c->d_al_int.p + n_nodes, a.d_state_node = c->d_al_int.p + n_nodes + n_states;
+  a.d_log_prior = j.ll->d_log_prior, a.width = j.ll->width, a.floor = j.ll->floor, a.type = j.ll->type;
+  a.d_arc_ptr = c->d_ag_int, a.d_arc_src = c->d_ag_int.p + n_states + 1, a.d_arc_lp = c->d_ag_lp;
+  a.d_start_lp = j.t.start_lp ? tail : nullptr, a.d_final_lp = j.t.final_lp ? tail + n_states : nullptr;
+  a.free_start = j.free_start;
+  a.d_alpha_in = !j.alpha_in ? nullptr : (host ? c->d_fb_res.p + rows + n_states : j.alpha_in);
+  a.d_alpha_out = alpha_out ? c->d_fb_res.p + rows : nullptr;
+  a.d_scratch = reinterpret_cast<float *>(c->d_al_bp.p), a.d_frame_total = c->d_fb_res;
+  launch_fb_frames(j.plan, a, s);
+  HIP_TRY(hipGetLastError());
+  const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  HIP_TRY(hipMemcpyAsync(frame_total, c->d_fb_res, sizeof(float) * rows, kind, s));
+  if (alpha_out) HIP_TRY(hipMemcpyAsync(alpha_out, c->d_fb_res.p + rows, sizeof(float) * n_states, kind, s));
+  if (host) HIP_TRY(hipStreamSynchronize(s));
+  return FDNN_OK;
+}
+
 // The host half of a compacted lazy return (lazy_compact_kernel): a compacted row is the row's inactive value followed by
 // its active nodes' probabilities in node order; expanding it = every node reads the next active value or the inactive one.
 // With AVX-512 that is one expanding load per 16 nodes (the mask's 16 bits select which lanes take the next values from

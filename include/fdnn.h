@@ -678,6 +678,64 @@ FDNN_API int fdnn_calculate_fb(fdnn_model *m, const float *x, int n, int dim, co
 FDNN_API int fdnn_calculate_fb_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
                                    const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src,
                                    const float *arc_lp, const float *start_lp, const float *final_lp, float *total, float *gamma);
+/* ------------------------------------------------------------------ alignment graphs, summed, frame by frame (fdnn_fb_frames.hip)
+ * The FRAMES FORM of the summed alignment graphs above, forward only: the graph's likelihood at EVERY frame, a start that may
+ * be free, and a row carried from one call to the next -- a keyword graph against a filler scored push by push, end-pointing.
+ * Every entry below extends LazyOutputActivations (dnn.cc:355-392).  THE CONTRACT IS STATED ONCE, in
+ * csrc/fdnn_fb_frames.hpp, which calls the arithmetic of csrc/fdnn_fb.hpp; in short:
+ *
+ * The inputs are those of the summed graphs, checked by the same validator, and
+ *   free_start   0 or 1: with 1 a path may begin at any frame
+ *   alpha_in     NULL, or one float per state of the call, laid out like `states`: the recursion's row from the frame before
+ *                this call's first row
+ *   alpha_out    NULL, or the same shape: the last row's alpha, for the next call
+ *   frame_total  one float per row of the call; segment s begins at the sum of T over the segments before it
+ * Frame 0 without alpha_in is the start row, alpha[0][j] = start_lp[j] + e(0, j).  Every other frame, and frame 0 with
+ * alpha_in (prev = alpha_in): acc = -inf; the arcs go through the candidate step in the caller's order; then, with
+ * free_start, acc = ladd(acc, start_lp[j]) -- the start term LAST --; alpha[t][j] = acc + e(t, j).  frame_total[t] is the
+ * total's order (256 partials, the tree) over alpha[t][.] + final_lp.  A NaN in alpha_in is a NaN candidate and is never added.
+ * frame_total is never a NaN.  Anchored and without alpha_in, frame_total[t] has the bytes of fdnn_debug_fb_ref's total on
+ * the segment cut to t + 1 rows, so frame_total[T - 1] is fdnn_calculate_fb's total.  A segment cut at ANY frame into two
+ * calls, the second taking the first's alpha_out as alpha_in, gives the uncut call's frame_total and alpha_out byte for
+ * byte.  Results are a function of the scores, the graph and alpha_in alone -- not of the kernel form (fdnn_debug_set_fb_kernel
+ * forces these kernels too), the chunking or the entry point -- and equal fdnn_debug_fb_frames_ref byte for byte.
+ * FDNN_E_ARG before anything is launched: the alignment graphs' reasons, free_start outside {0, 1}, and a lattice (4 bytes a
+ * frame and state, always needed) above 2^30 bytes.  Nothing is routed to these entry points.
+ *
+ * fdnn_fb_frames_rows_device     the sweep and the row totals alone on any device-resident fp32 rows (dnn.cc:355-392): the
+ *   host tables and the device copies as fdnn_fb_rows_device without the transposed ones; d_alpha_in / d_alpha_out device
+ *   arrays [states of the call] or NULL; d_scratch at least the words fdnn_fb_frames_scratch_words names; d_frame_total
+ *   [sum of T].  Enqueued on `stream`, not synchronised.
+ * fdnn_fb_frames_scratch_words   the lattice of that call: the sum of T S; above 2^30 bytes FDNN_E_ARG (dnn.cc:355-392).
+ * fdnn_ctx_fb_frames             host tables, host carry arrays and host results, host-synchronous, over rows of a context
+ *   whose hidden layers have run (dnn.cc:355-392).
+ * fdnn_ctx_fb_frames_device      the same with device carry arrays and device results, enqueued on `stream`; the host tables
+ *   are read before it returns (dnn.cc:355-392).
+ * fdnn_calculate_fb_frames       one call on a pooled context (dnn.cc:355-392): seg_rows must cover [0, n); a large n goes
+ *   chunk by chunk and the sweep runs ONCE behind the last chunk.
+ * fdnn_calculate_fb_frames_raw   the same from raw feature frames [n][raw_dim]; every segment is an utterance of its own
+ *   (dnn.cc:355-392). */
+FDNN_API int fdnn_fb_frames_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off,
+                                        const int32_t *row_ld, const int32_t *state_ptr, const int32_t *arc_ptr, int n_segs, const int32_t *d_col,
+                                        const int32_t *d_state_node, const int32_t *d_arc_ptr, const int32_t *d_arc_src, const float *d_arc_lp,
+                                        const float *d_start_lp, const float *d_final_lp, int free_start, const float *d_alpha_in,
+                                        float *d_alpha_out, void *d_scratch, long long scratch_words, float *d_frame_total, void *stream);
+FDNN_API int fdnn_fb_frames_scratch_words(const int32_t *seg_T, const int32_t *state_ptr, int n_segs, long long *words);
+FDNN_API int fdnn_ctx_fb_frames(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp,
+                                const float *final_lp, int free_start, const float *alpha_in, float *alpha_out, float *frame_total);
+FDNN_API int fdnn_ctx_fb_frames_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                       const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                                       const float *start_lp, const float *final_lp, int free_start, const float *d_alpha_in, float *d_alpha_out,
+                                       float *d_frame_total, void *stream);
+FDNN_API int fdnn_calculate_fb_frames(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                      const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src,
+                                      const float *arc_lp, const float *start_lp, const float *final_lp, int free_start, const float *alpha_in,
+                                      float *alpha_out, float *frame_total);
+FDNN_API int fdnn_calculate_fb_frames_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                          const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr,
+                                          const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, int free_start,
+                                          const float *alpha_in, float *alpha_out, float *frame_total);
 /* Last hidden layer's u8 activations, n x hidden_dim (quantized_activations_). */
 FDNN_API int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out);
 
@@ -1112,6 +1170,19 @@ FDNN_API int fdnn_debug_fb_ref(const float *rows, const int32_t *seg_T, const lo
                                const int32_t *t_ptr, const int32_t *t_src, const float *t_lp, float *total, float *gamma);
 FDNN_API int fdnn_debug_fb_math_ref(int op, const float *a, const float *b, float *out, long long n);
 FDNN_API int fdnn_debug_fb_math_device(int op, const float *d_a, const float *d_b, float *d_out, long long n, void *stream);
+
+/* Alignment graphs, summed, frame by frame (LazyOutputActivations, dnn.cc:355-392), tests and tools.
+ * fdnn_debug_fb_frames_launches  process-wide counts since load, returns 3: out[0] sweep launches of the wave form, [1] of
+ *   the workgroup form, [2] row-total launches -- one behind every sweep launch.  A counter of their own.
+ * fdnn_debug_fb_frames_ref       fdnn_fb_frames_rows_device from the host restatement (fdnn_fb_frames.hpp) on host rows and
+ *   host arrays; type as fdnn_debug_align_ref; alpha_in and alpha_out may be NULL; host code, no device needed
+ *   (dnn.cc:355-392). */
+FDNN_API int fdnn_debug_fb_frames_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_fb_frames_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                                      const int32_t *state_ptr, int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior,
+                                      int width, float floor, int type, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                                      const float *start_lp, const float *final_lp, int free_start, const float *alpha_in, float *alpha_out,
+                                      float *frame_total);
 
 /* Splicing through a segment table in device memory (the scoring loop's live batches, fdnn_splice.hip), tests and tools.
  * fdnn_debug_splice_table   the splice alone, host in and host out: raw [raw_frames][raw_dim] -> x [rows][input_dim] under the
