@@ -21,7 +21,10 @@
 //     A NaN in alpha_in makes a NaN candidate, which accumulate never adds.
 //   frame_total[t] = total_of(alpha[t][.], final_lp, S): the existing order -- 256 partials, state j in partial j mod 256 in
 //     ascending j, then the tree.
-//   alpha_out = alpha[T-1][.], as bits.
+//   alpha_out = alpha[T-1][.], as bits.  Where that alpha is a NaN it is SOME NaN: payload and sign are not part of the
+//     contract (the host's and the device's inf - inf need not share a sign bit); frame_total is never one, so its bits are.
+//   alpha_out may be the very buffer alpha_in points to: every sweep loads its segment's carry row into d before it stores
+//     anything, stores alpha_out last, and touches no other segment's states.  A partial overlap is not allowed.
 //
 // CONSEQUENCES (each is tested)
 //   (a) free_start = 0 and no alpha_in: rows 0 .. t are fb::ref's recursion on the segment cut to t + 1 rows -- row t depends

@@ -688,7 +688,10 @@ FDNN_API int fdnn_calculate_fb_raw(fdnn_model *m, const float *raw, int n, int r
  *   free_start   0 or 1: with 1 a path may begin at any frame
  *   alpha_in     NULL, or one float per state of the call, laid out like `states`: the recursion's row from the frame before
  *                this call's first row
- *   alpha_out    NULL, or the same shape: the last row's alpha, for the next call
+ *   alpha_out    NULL, or the same shape: the last row's alpha, for the next call, as bits -- where that alpha is a NaN (the
+ *                emission is one, or +inf met -inf) it is SOME NaN: its payload and sign are not part of the contract.
+ *                alpha_out may be the very buffer alpha_in points to (a segment's sweep loads its carry row before it stores
+ *                anything and touches no other segment's states); a partial overlap of the two is not allowed
  *   frame_total  one float per row of the call; segment s begins at the sum of T over the segments before it
  * Frame 0 without alpha_in is the start row, alpha[0][j] = start_lp[j] + e(0, j).  Every other frame, and frame 0 with
  * alpha_in (prev = alpha_in): acc = -inf; the arcs go through the candidate step in the caller's order; then, with

@@ -11,7 +11,7 @@ import fb_cases as FC
 from conftest import ROOT
 from fast_dnn_amd import api
 from test_fb_host import host_compiler
-from test_gpu_fb_frames_rows import HANDLES, SHAPES, shapes_call
+from test_gpu_fb_frames_rows import HANDLES, SHAPES, frames_of, plants, shapes_call
 
 INT_NAMES = ("fdnn_fb_frames_rows_device", "fdnn_fb_frames_scratch_words", "fdnn_ctx_fb_frames", "fdnn_ctx_fb_frames_device", "fdnn_calculate_fb_frames",
              "fdnn_calculate_fb_frames_raw", "fdnn_debug_fb_frames_ref", "fdnn_debug_fb_frames_launches")
@@ -98,3 +98,59 @@ def test_the_gpu_cases_are_not_blind(S, handle):
     anchored, free = (c.ref(handle, priors(67), f)[0][-33:] for f in (False, True))
     assert (anchored.view(np.uint32)[1:] != free.view(np.uint32)[1:]).mean() >= 0.5
     assert np.unique(anchored.view(np.uint32)).size > 16 and np.isfinite(anchored).all()
+
+
+def test_the_planted_cases_are_not_blind():
+    """A condition on the planted INPUTS of tests/test_gpu_fb_frames_rows.py, from the restatement alone.  Every planted
+    segment's frame_total differs in bytes, in a frame at or after the plant, from the same call with clean values in the
+    planted ones' place, anchored and free alike -- else a kernel that ignored the plant would pass.  And over the whole file
+    at least half of the planted segments, counted under either start, keep a finite frame_total at their last frame -- else
+    most of the comparisons would be of -inf with -inf."""
+    from loglik_cases import priors
+
+    finite = total = 0
+    for name, p in plants().items():
+        lp = priors(67) if p.handle is not None else None
+        assert p.at, name
+        for free in (False, True):
+            got = p.call.ref(p.handle, lp, free, p.alpha_in)[0].view(np.uint32)
+            clean = p.clean.ref(p.handle, lp, free, p.clean_in)[0].view(np.uint32)
+            assert not np.isnan(got.view(np.float32)).any() and np.isfinite(clean.view(np.float32)).all(), name
+            for seg, t0 in p.at.items():
+                frames = frames_of(p.call, seg)
+                assert (got[frames][t0:] != clean[frames][t0:]).any(), (name, seg, free)
+                assert np.array_equal(got[frames][:t0], clean[frames][:t0]), (name, seg, free)  # and in none before it
+                finite += bool(np.isfinite(got.view(np.float32)[frames][-1]))
+                total += 1
+            first = frames_of(p.call, 0)
+            assert 0 not in p.at and np.array_equal(got[first], clean[first]), (name, free)  # the clean segment is clean
+    print(f"{finite} of {total} planted (segment, start) pairs end finite")
+    assert 2 * finite >= total
+
+
+def test_the_lower_clamp_of_the_device_arc_offsets_shows_in_the_bytes():
+    """The planted device arc offset BELOW a segment's first arc, from the restatement alone (a kernel without the lower bound
+    would read outside the segment's arcs, so no device run may try it).  Such a kernel steps state j over the arcs
+    min(ptr[j], arcs) .. min(ptr[j + 1], arcs) of the call's table counted from the segment's first arc: the negative
+    offset reaches the arcs of the segment BEFORE it.  The restatement over exactly those arcs differs in bytes from the
+    restatement over clamped() in every planted segment, so the case holds the kernels to the lower bound too."""
+    p = plants()["device arc offsets below and above the segment"]
+    packed = api.pack_graphs(p.call.graphs)
+    for seg in p.at:
+        rows, col, g, _ = p.call.parts[seg]
+        s0, S = int(packed["statePtr"][seg]), len(col)
+        arc0, arcs = int(packed["arcPtr"][s0]), len(g["arc_src"])
+        ptr = packed["arcPtr"][s0:s0 + S + 1].astype(np.int64) - arc0
+        for at, value in p.call.device_ptr.items():
+            if s0 <= at <= s0 + S:
+                ptr[at - s0] = value - arc0
+        assert ptr.min() < 0 and ptr.max() > arcs and arc0 + ptr.min() >= 0  # one below, one above, and inside the call's table
+        q = np.minimum(ptr, arcs)  # the upper bound alone
+        take = [arc0 + np.arange(q[j], max(q[j], q[j + 1])) for j in range(S)]
+        at = np.concatenate(take).astype(np.int64)
+        loose = dict(g, arc_ptr=np.concatenate([[0], np.cumsum([t.size for t in take])]).astype(np.int32), arc_src=packed["arcSrc"][at], arc_lp=packed["arcLp"][at])
+        for free in (False, True):
+            one = lambda graph: api.fb_frames_ref(rows, [rows.shape[0]], [0], [rows.shape[1]], api.pack_graphs([graph]), col, free_start=free)[0]
+            want, without = one(p.call.ref_graphs[seg]), one(loose)
+            assert not np.array_equal(want.view(np.uint32), without.view(np.uint32)), (seg, free)
+            assert np.array_equal(want.view(np.uint32), p.call.ref(free=free)[0].view(np.uint32)[frames_of(p.call, seg)])  # (the case's own expectation)

@@ -116,3 +116,40 @@ def test_two_chunks_that_cut_a_segment_give_the_uncut_bytes(nets):
     sp = packed["statePtr"]
     assert same((got[0][a:b], got[1][sp[1]:sp[2]]), alone) and np.isfinite(alone[0][-1])
     ll.delete()
+
+
+def test_the_carry_row_in_place_through_the_context(nets):
+    """fbFramesDevice with d_alpha_out == d_alpha_in, ONE buffer (fdnn.h: allowed): a stream's second call gives the
+    two-buffer call's frame_total and carry row byte for byte -- which are the uncut call's --, anchored and free, in both
+    forced forms, on a side stream."""
+    import torch
+
+    dnn, x, dense = nets("tiny")
+    n, O = dense.shape
+    one = api.pack_graphs(GC.silence_graphs(dense, np.array([0, n]), 35))
+    S, cut = int(one["statePtr"][-1]), n // 2
+    ll = api.Loglik(LL.priors(O), -20.0, api.LOGLIK_F16)
+    ctx = dnn.getNewLazyContext(n)
+    ctx.calculateUntilOutput(x)
+    st = torch.cuda.Stream()
+    try:
+        for free in (False, True):
+            whole = ctx.fbFrames(ll, [0, n], one, free)
+            assert not np.isnan(whole[0]).any() and np.isfinite(whole[0][-1])
+            for mode in (1, 2):
+                api.set_fb_kernel(mode)
+                outs = []
+                for in_place in (False, True):
+                    d_tot = torch.full((n,), -7.0, dtype=torch.float32, device="cuda")
+                    d_a = torch.full((S,), -7.0, dtype=torch.float32, device="cuda")
+                    d_b = d_a if in_place else torch.full((S,), -7.0, dtype=torch.float32, device="cuda")
+                    torch.cuda.synchronize()
+                    ctx.fbFramesDevice(ll, [0, cut], one, d_tot.data_ptr(), free, 0, d_a.data_ptr(), st.cuda_stream)
+                    ctx.fbFramesDevice(ll, [cut, n], one, d_tot.data_ptr() + 4 * cut, free, d_a.data_ptr(), d_b.data_ptr(), st.cuda_stream)
+                    st.synchronize()
+                    outs.append((d_tot.cpu().numpy(), d_b.cpu().numpy()))
+                assert same(outs[1], outs[0]) and same(outs[1], whole), (free, mode)
+    finally:
+        api.set_fb_kernel(0)
+        ll.delete()
+        ctx.delete()

@@ -412,3 +412,39 @@ def test_argument_errors_launch_nothing():
     assert call(gamma=None, tp=None, d_tp=None, d_ts=None, d_tl=None, scratch=None, words=0) == api.FDNN_OK  # forward only needs none of them
     torch.cuda.synchronize()
     assert tuple(b - a for a, b in zip(before, api.fb_launches())) == (1, 0, 0, 0)
+
+
+@pytest.mark.parametrize("S", (5, 300))
+def test_nan_and_infinite_row_values(S):
+    """NaN and +-inf in the ROW VALUES themselves (the cases above reach a NaN through a bad column alone), each beside a clean
+    segment in the same launch: total and gamma are never a NaN by the contract, so the comparison stays byte for byte.  One
+    state's column a NaN from frame 3 on (the skip arcs go round it), a whole frame of NaN, of +inf and of -inf, and +inf on
+    a state whose final_lp is -inf (that term of the total is a NaN and is skipped).  Not blind: every planted segment's
+    total differs in bytes from the clean rows'."""
+    import torch
+
+    rng = np.random.default_rng(60 + S)
+    g = skip_chain(S, rng)
+    g["start_lp"] = np.log(rng.uniform(0.05, 0.95, S)).astype(np.float32)
+    g["final_lp"] = np.log(rng.uniform(0.05, 0.95, S)).astype(np.float32)
+    closed = dict(g, final_lp=g["final_lp"].copy())
+    closed["final_lp"][1] = -np.inf
+    T, ld, t0 = 9, S + 3, 3
+    col = rng.permutation(ld)[:S].tolist()  # a column of its own for every state
+    clean = AC.scores(T, ld, 61) * SCALE
+    c, d = Call().add(clean, col, g), Call().add(clean, col, g)
+    for kind in ("nan column", "nan frame", "+inf frame", "-inf frame", "+inf meets -inf final", "+inf meets -inf final, last frame"):
+        rows = clean.copy()
+        if kind == "nan column":
+            rows[t0:, col[int(np.argmax(FC.ref_one(clean[:t0 + 1], col, g)[1][-1]))]] = np.nan  # the state most occupied at t0
+        elif kind.startswith("+inf meets"):
+            rows[T - 1 if kind.endswith("last frame") else t0, col[1]] = np.inf
+        else:
+            rows[t0, :] = dict((("nan frame", np.nan), ("+inf frame", np.inf), ("-inf frame", -np.inf)))[kind]
+        c.add(rows, col, closed if kind.startswith("+inf meets") else g, gap=1)
+        d.add(clean, col, closed if kind.startswith("+inf meets") else g, gap=1)
+    want = all_forms(torch, c, wave_launches=(1, 0) if S <= WAVE_STATES else (0, 1))
+    assert not np.isnan(want[0]).any() and not np.isnan(want[1]).any()
+    assert np.isfinite(want[0][:2]).all() and np.isneginf(want[0][[2, 4]]).all() and np.isposinf(want[0][[3, 5]]).all() and np.isfinite(want[0][6])
+    ref = d.ref()[0]
+    assert (want[0].view(np.uint32)[1:6] != ref.view(np.uint32)[1:6]).all() and want[0].view(np.uint32)[0] == ref.view(np.uint32)[0]
