@@ -259,6 +259,23 @@ SIGNATURES = {
     "fdnn_debug_fb_frames_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "fdnn_debug_fb_frames_ref": (C.c_int, [_c_f32p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, C.c_int,
                                            C.c_float, C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, C.c_int, _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_align_frames_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, _c_i32p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _c_i32p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fdnn_ctx_align_frames": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, C.c_int,
+                                        _c_i32p, _c_f32p, _c_i32p, _c_f32p, _c_i32p, _c_f32p, _c_i32p, _c_i32p]),
+    "fdnn_ctx_align_frames_device": (C.c_int, [C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p,
+                                               C.c_int, _c_i32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "fdnn_calculate_align_frames": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p,
+                                              _c_f32p, _c_f32p, _c_f32p, C.c_int, _c_i32p, _c_f32p, _c_i32p, _c_f32p, _c_i32p, _c_f32p, _c_i32p, _c_i32p]),
+    "fdnn_calculate_align_frames_raw": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_i32p,
+                                                  _c_f32p, _c_f32p, _c_f32p, C.c_int, _c_i32p, _c_f32p, _c_i32p, _c_f32p, _c_i32p, _c_f32p, _c_i32p,
+                                                  _c_i32p]),
+    "fdnn_debug_align_frames_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_align_frames_ref": (C.c_int, [_c_f32p, _c_i32p, C.POINTER(C.c_longlong), _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_i32p, _c_f32p, C.c_int,
+                                              C.c_float, C.c_int, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, C.c_int, _c_i32p, _c_f32p, _c_i32p, _c_f32p,
+                                              _c_i32p, _c_f32p, _c_i32p, _c_i32p]),
     "fdnn_debug_ln_ref": (C.c_int, [_c_f32p, C.c_longlong, _c_f32p]),
     "fdnn_model_fuse_giveups": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_device_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -1342,6 +1359,85 @@ def fb_frames_launches():
     return tuple(int(v) for v in buf)
 
 
+# ---------------------------------------------------------------- alignment graphs, best path, frame by frame (fdnn_align_frames.hip)
+# The frames form of the best path: per frame its score, the state it ends in and the frame it BEGAN at.  ``free_start`` lets a
+# path begin at any frame; ``frame_base`` int32 [segments] (None: zeros) is the caller's number of each segment's first row, in
+# which begin frames are reported; ``carry`` = (d float32 [states], begin int32 [states]) is the recursion's row from the
+# frame before the call's first row (None: the call begins the stream).  Every call returns
+# (frame_best float32 [rows], frame_end int32 [rows], frame_begin int32 [rows], carry_out), carry_out what the next call takes.
+def _frames_carry(carry, n_states: int):
+    if carry is None:
+        return None, None
+    d, b = np.ascontiguousarray(carry[0], dtype=np.float32), np.ascontiguousarray(carry[1], dtype=np.int32)
+    if d.shape != (n_states,) or b.shape != (n_states,):
+        raise ValueError("carry must be (d float32 [states of the call], begin int32 [states of the call])")
+    return d, b
+
+
+def _frame_base(frame_base, n_segs: int):
+    if frame_base is None:
+        return None
+    fb = np.ascontiguousarray(frame_base, dtype=np.int32)
+    if fb.shape != (n_segs,):
+        raise ValueError("frame_base must be [segments]")
+    return fb
+
+
+def _frames_out(rows: int, n_states: int):
+    return (np.empty(rows, np.float32), np.empty(rows, np.int32), np.empty(rows, np.int32)), (np.empty(n_states, np.float32), np.empty(n_states, np.int32))
+
+
+def align_frames_ref(rows, segT, rowOff, rowLd, graphs, col, stateNode=None, log_prior=None, floor: float = -np.inf, type: int = ALIGN_SCORES,
+                     free_start: bool = False, frame_base=None, carry=None):
+    """The frames form from the host restatement (``fdnn_debug_align_frames_ref``; host code, no device): the arguments of
+    ``align_graph_ref`` -> (frame_best, frame_end, frame_begin, (d_out, begin_out))."""
+    r = np.ascontiguousarray(rows, dtype=np.float32).ravel()
+    sp, _, ap, src, alp, start, final = _graph_tables(graphs)
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, sp)
+    c = np.ascontiguousarray(col, dtype=np.int32)
+    nd = None if stateNode is None else np.ascontiguousarray(stateNode, dtype=np.int32)
+    lp = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float32)
+    din, bin_ = _frames_carry(carry, int(sp[-1]))
+    fb = _frame_base(frame_base, t.size)
+    if t.size and ((off + (t.astype(np.int64) - 1) * ld + ld > r.size).any() or (off < 0).any() or c.size < int(sp[-1])):
+        raise ValueError("a segment's rows run past the rows, or col is shorter than the graphs")
+    (best, end, begin), (dout, bout) = _frames_out(int(t.sum()), int(sp[-1]))
+    _check(lib().fdnn_debug_align_frames_ref(r.ctypes.data_as(_c_f32p), t.ctypes.data_as(_c_i32p), off.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                             ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), t.size, c.ctypes.data_as(_c_i32p), _ip(nd), _fp(lp),
+                                             0 if lp is None else lp.size, C.c_float(float(floor)), int(type), _ip(ap), _ip(src), _fp(alp), _fp(start),
+                                             _fp(final), int(bool(free_start)), _ip(fb), _fp(din), _ip(bin_), _fp(dout), _ip(bout), _fp(best), _ip(end),
+                                             _ip(begin)))
+    return best, end, begin, (dout, bout)
+
+
+def align_frames_rows_device(ll, d_rows: int, segT, rowOff, rowLd, statePtr, arcPtr, d_col: int, d_state_node: int, d_arc_ptr: int, d_arc_src: int,
+                             d_arc_lp: int, d_start_lp: int, d_final_lp: int, free_start: bool, frame_base, d_d_in: int, d_begin_in: int, d_d_out: int,
+                             d_begin_out: int, d_frame_best: int, d_frame_end: int, d_frame_begin: int, stream: int = 0) -> None:
+    """The sweep alone on device-resident fp32 rows (``fdnn_align_frames_rows_device``): host tables segT, rowOff, rowLd,
+    statePtr, arcPtr and frame_base (None: zeros), device pointers for everything else (0 for NULL); ``ll`` a ``Loglik`` or
+    None (the rows are scores).  Enqueued on ``stream``, not synchronised."""
+    t, off, ld, sp = _align_rows_tables(segT, rowOff, rowLd, statePtr)
+    ap = np.ascontiguousarray(arcPtr, dtype=np.int32)
+    if ap.shape != (int(sp[-1]) + 1,):
+        raise ValueError("arcPtr must be [states + 1]")
+    fb = _frame_base(frame_base, t.size)
+    _check(lib().fdnn_align_frames_rows_device(None if ll is None else ll.handle, C.c_void_p(d_rows), t.ctypes.data_as(_c_i32p),
+                                               off.ctypes.data_as(C.POINTER(C.c_longlong)), ld.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p),
+                                               ap.ctypes.data_as(_c_i32p), t.size, C.c_void_p(d_col), C.c_void_p(d_state_node), C.c_void_p(d_arc_ptr),
+                                               C.c_void_p(d_arc_src), C.c_void_p(d_arc_lp), C.c_void_p(d_start_lp), C.c_void_p(d_final_lp),
+                                               int(bool(free_start)), _ip(fb), C.c_void_p(d_d_in), C.c_void_p(d_begin_in), C.c_void_p(d_d_out),
+                                               C.c_void_p(d_begin_out), C.c_void_p(d_frame_best), C.c_void_p(d_frame_end), C.c_void_p(d_frame_begin),
+                                               C.c_void_p(stream)))
+
+
+def align_frames_launches():
+    """Process-wide counts since load: launches of the frames-form best-path kernels (wave form, workgroup form)."""
+    buf = (C.c_ulonglong * 2)()
+    if lib().fdnn_debug_align_frames_launches(buf, 2) != 2:
+        raise RuntimeError("fdnn_debug_align_frames_launches")
+    return tuple(int(v) for v in buf)
+
+
 def _fb_out(n_segs: int, segRows, sp, want_gamma: bool):
     total = np.empty(n_segs, np.float32)
     words = int((np.diff(segRows.astype(np.int64)) * np.diff(sp.astype(np.int64))).sum()) if n_segs else 0
@@ -1642,6 +1738,30 @@ class LazyContext:
         _check(lib().fdnn_ctx_fb_frames_device(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start),
                                                _fp(final), int(bool(free_start)), C.c_void_p(d_alpha_in), C.c_void_p(d_alpha_out),
                                                C.c_void_p(d_frame_total), C.c_void_p(stream)))
+
+    def alignFrames(self, ll: "Loglik", segRows, graphs, free_start: bool = False, frame_base=None, carry=None):
+        """The frames form of ``alignGraph`` over rows of the context (``fdnn_ctx_align_frames``) -> (frame_best float32 [rows],
+        frame_end int32 [rows], frame_begin int32 [rows], (d_out, begin_out)): at every frame the best path's score, the
+        state it ends in and the frame it began at (in ``frame_base``'s numbering), and the last row for the next call's
+        ``carry``."""
+        sr, sp, st, ap, src, lp, start, final, n_segs, rows = _graph_call_tables(segRows, graphs)
+        din, bin_ = _frames_carry(carry, int(sp[-1]))
+        fb = _frame_base(frame_base, n_segs)
+        (best, end, begin), (dout, bout) = _frames_out(rows, int(sp[-1]))
+        _check(lib().fdnn_ctx_align_frames(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                           int(bool(free_start)), _ip(fb), _fp(din), _ip(bin_), _fp(dout), _ip(bout), _fp(best), _ip(end), _ip(begin)))
+        return best, end, begin, (dout, bout)
+
+    def alignFramesDevice(self, ll: "Loglik", segRows, graphs, d_frame_best: int, d_frame_end: int, d_frame_begin: int, free_start: bool = False,
+                          frame_base=None, d_d_in: int = 0, d_begin_in: int = 0, d_d_out: int = 0, d_begin_out: int = 0, stream: int = 0) -> None:
+        """The same with device carry arrays and device results (0 for none; ``frame_base`` stays a host table), enqueued on
+        ``stream`` and not synchronised (``fdnn_ctx_align_frames_device``)."""
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        fb = _frame_base(frame_base, n_segs)
+        _check(lib().fdnn_ctx_align_frames_device(self.handle, ll.handle, _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start),
+                                                  _fp(final), int(bool(free_start)), _ip(fb), C.c_void_p(d_d_in), C.c_void_p(d_begin_in),
+                                                  C.c_void_p(d_d_out), C.c_void_p(d_begin_out), C.c_void_p(d_frame_best), C.c_void_p(d_frame_end),
+                                                  C.c_void_p(d_frame_begin), C.c_void_p(stream)))
 
     def calculateOutputLoglikDevice(self, ll: "Loglik", d_out: int, stream: int = 0) -> None:
         """The same into a device buffer [frames][outputDimension] of the handle's type, enqueued on ``stream``, not
@@ -2529,6 +2649,39 @@ class QuantizedDnn:
                                                   n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final), int(bool(free_start)),
                                                   _fp(ain), _fp(alpha_out), _fp(frame_total)))
         return frame_total, alpha_out
+
+    def calculateAlignFrames(self, input, ll: "Loglik", segRows, graphs, free_start: bool = False, frame_base=None, carry=None):
+        """The best path over alignment graphs at every frame in one call (``fdnn_calculate_align_frames``; segRows must cover
+        [0, frames)): hidden layers, the graphs' node sets, the sweep on the device -> (frame_best, frame_end, frame_begin,
+        (d_out, begin_out)), as ``LazyContext.alignFrames``."""
+        x = _f32(input)
+        n = x.shape[0]
+        if n and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        din, bin_ = _frames_carry(carry, int(sp[-1]))
+        fb = _frame_base(frame_base, n_segs)
+        (best, end, begin), (dout, bout) = _frames_out(n, int(sp[-1]))
+        _check(lib().fdnn_calculate_align_frames(self.nativeDnnHandle, x.ctypes.data_as(_c_f32p), n, x.shape[1] if n else self.inputDimension(), ll.handle,
+                                                 _ip(sr), _ip(sp), n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final),
+                                                 int(bool(free_start)), _ip(fb), _fp(din), _ip(bin_), _fp(dout), _ip(bout), _fp(best), _ip(end),
+                                                 _ip(begin)))
+        return best, end, begin, (dout, bout)
+
+    def calculateAlignFramesRaw(self, raw, ll: "Loglik", segRows, graphs, free_start: bool = False, frame_base=None, carry=None):
+        """``calculateAlignFrames`` on raw frames [n][rawDim], spliced on the device, every segment an utterance of its own
+        (``fdnn_calculate_align_frames_raw``)."""
+        r = _f32(raw)
+        if r.ndim != 2:
+            raise ValueError("raw must be [frames][rawDim]")
+        sr, sp, st, ap, src, lp, start, final, n_segs, _ = _graph_call_tables(segRows, graphs)
+        din, bin_ = _frames_carry(carry, int(sp[-1]))
+        fb = _frame_base(frame_base, n_segs)
+        (best, end, begin), (dout, bout) = _frames_out(r.shape[0], int(sp[-1]))
+        _check(lib().fdnn_calculate_align_frames_raw(self.nativeDnnHandle, r.ctypes.data_as(_c_f32p), r.shape[0], r.shape[1], ll.handle, _ip(sr), _ip(sp),
+                                                     n_segs, _ip(st), _ip(ap), _ip(src), _fp(lp), _fp(start), _fp(final), int(bool(free_start)),
+                                                     _ip(fb), _fp(din), _ip(bin_), _fp(dout), _ip(bout), _fp(best), _ip(end), _ip(begin)))
+        return best, end, begin, (dout, bout)
 
     def calculate_lazy_bits_device(self, d_x: int, n: int, d_bits: int, d_out: int, stream: int = 0) -> None:
         _check(lib().fdnn_calculate_lazy_bits_device(self.nativeDnnHandle, C.c_void_p(d_x), n, C.c_void_p(d_bits), C.c_void_p(d_out), C.c_void_p(stream)))

@@ -1811,6 +1811,205 @@ int fdnn_debug_fb_frames_ref(const float *rows, const int32_t *seg_T, const long
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- alignment graphs, best path, frame by frame (fdnn_align_frames.hip)
+static int align_frames_flags(int free_start, const void *d_in, const void *begin_in) {
+  if (free_start != 0 && free_start != 1) return fail(FDNN_E_ARG, "align frames: free_start is 0 or 1");
+  if ((d_in == nullptr) != (begin_in == nullptr)) return fail(FDNN_E_ARG, "align frames: d_in and begin_in are both given or both NULL");
+  return FDNN_OK;
+}
+
+static int align_frames_states(const int32_t *state_ptr, int n_segs) {
+  const int big = fdnn::align_frames::too_many_states(state_ptr, n_segs);
+  if (big >= 0)
+    return fail(FDNN_E_ARG, "align frames, segment " + std::to_string(big) + ": a graph has at most " + std::to_string(fdnn::align_frames::kMaxStates) + " states");
+  return FDNN_OK;
+}
+
+// The sweep alone.  The host tables are checked as the sibling's; there is no scratch.
+int fdnn_align_frames_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                                  const int32_t *state_ptr, const int32_t *arc_ptr, int n_segs, const int32_t *d_col, const int32_t *d_state_node,
+                                  const int32_t *d_arc_ptr, const int32_t *d_arc_src, const float *d_arc_lp, const float *d_start_lp,
+                                  const float *d_final_lp, int free_start, const int32_t *frame_base, const float *d_d_in, const int32_t *d_begin_in,
+                                  float *d_d_out, int32_t *d_begin_out, float *d_frame_best, int32_t *d_frame_end, int32_t *d_frame_begin, void *stream) {
+  if (int rc = align_frames_flags(free_start, d_d_in, d_begin_in)) return rc;
+  if (n_segs > 0 && !arc_ptr) return fail(FDNN_E_ARG, "align frames, segment 0: malformed tables");
+  if (int rc = align_rows_tables(seg_T, row_off, row_ld, state_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  if (int rc = align_frames_states(state_ptr, n_segs)) return rc;  // (before arc_ptr is read over the states)
+  if (int rc = align_graph_rows_tables(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs)) return rc;
+  const bool arcs = arc_ptr[state_ptr[n_segs]] > 0;
+  if (!d_rows || !d_col || !d_arc_ptr || (arcs && (!d_arc_src || !d_arc_lp)) || !d_frame_best || !d_frame_end || !d_frame_begin || (ll && !d_state_node))
+    return fail(FDNN_E_ARG, "null buffer");
+  const uintptr_t all = reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_col) | reinterpret_cast<uintptr_t>(d_state_node) |
+                        reinterpret_cast<uintptr_t>(d_arc_ptr) | reinterpret_cast<uintptr_t>(d_arc_src) | reinterpret_cast<uintptr_t>(d_arc_lp) |
+                        reinterpret_cast<uintptr_t>(d_start_lp) | reinterpret_cast<uintptr_t>(d_final_lp) | reinterpret_cast<uintptr_t>(d_d_in) |
+                        reinterpret_cast<uintptr_t>(d_begin_in) | reinterpret_cast<uintptr_t>(d_d_out) | reinterpret_cast<uintptr_t>(d_begin_out) |
+                        reinterpret_cast<uintptr_t>(d_frame_best) | reinterpret_cast<uintptr_t>(d_frame_end) | reinterpret_cast<uintptr_t>(d_frame_begin);
+  if (all & 3) return fail(FDNN_E_ARG, "buffers must have their elements' alignment");
+  const fdnn::align_graph::Plan p = fdnn::align_frames::plan(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs, fdnn::align_graph_kernel_mode());
+  fdnn::AlignFramesArgs a;
+  a.d_rows = d_rows, a.d_col = d_col, a.d_state_node = d_state_node, a.d_arc_ptr = d_arc_ptr, a.d_arc_src = d_arc_src, a.d_arc_lp = d_arc_lp;
+  a.d_start_lp = d_start_lp, a.d_final_lp = d_final_lp, a.free_start = free_start != 0, a.frame_base = frame_base;
+  a.d_d_in = d_d_in, a.d_begin_in = d_begin_in, a.d_d_out = d_d_out, a.d_begin_out = d_begin_out;
+  a.d_frame_best = d_frame_best, a.d_frame_end = d_frame_end, a.d_frame_begin = d_frame_begin;
+  if (ll) a.d_log_prior = ll->d_log_prior, a.width = ll->width, a.floor = ll->floor, a.type = ll->type;
+  int dev = 0;
+  if (ll) dev = ll->device;
+  else if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  DeviceGuard g(dev);
+  fdnn::launch_align_frames(p, a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+// The carry and result arrays of a call through a model
+struct AlignFramesIo {
+  int free_start;
+  const int32_t *frame_base;
+  const float *d_in;
+  const int32_t *begin_in;
+  fdnn::AlignFramesOut out;
+};
+
+// The front of every such call: the handle, the flags, then the tables (align_frames_prepare names the first bad segment)
+static int align_frames_front(const fdnn_model *m, const fdnn_loglik *ll, const fdnn::align_graph::Tables &t, const AlignFramesIo &io, int ctx_rows,
+                              fdnn::AlignFramesJob *j) {
+  if (int rc = fdnn::check_loglik(m, ll)) return rc;
+  if (t.n_segs < 0) return fail(FDNN_E_ARG, "negative segment count");
+  if (int rc = align_frames_flags(io.free_start, io.d_in, io.begin_in)) return rc;
+  j->ll = ll, j->t = t, j->free_start = io.free_start != 0, j->frame_base = io.frame_base, j->d_in = io.d_in, j->begin_in = io.begin_in;
+  return fdnn::align_frames_prepare(j, m->hm.hdr.out_dim, ctx_rows);
+}
+
+static int align_frames_results(const AlignFramesIo &io) {
+  if (!io.out.frame_best || !io.out.frame_end || !io.out.frame_begin) return fail(FDNN_E_ARG, "null result buffer");
+  if ((reinterpret_cast<uintptr_t>(io.d_in) | reinterpret_cast<uintptr_t>(io.begin_in) | reinterpret_cast<uintptr_t>(io.out.d_out) |
+       reinterpret_cast<uintptr_t>(io.out.begin_out) | reinterpret_cast<uintptr_t>(io.out.frame_best) | reinterpret_cast<uintptr_t>(io.out.frame_end) |
+       reinterpret_cast<uintptr_t>(io.out.frame_begin)) & 3)
+    return fail(FDNN_E_ARG, "buffers must have their elements' alignment");
+  return FDNN_OK;
+}
+
+static int ctx_align_frames(fdnn_ctx *c, const fdnn_loglik *ll, const fdnn::align_graph::Tables &t, const AlignFramesIo &io, bool host, hipStream_t s) {
+  if (!c) return fail(FDNN_E_ARG, "null argument");
+  fdnn::AlignFramesJob j;
+  if (int rc = align_frames_front(c->m, ll, t, io, c->n, &j)) return rc;
+  if (int rc = lazy_state(c)) return rc;
+  if (t.n_segs == 0) return FDNN_OK;
+  if (int rc = align_frames_results(io)) return rc;
+  const std::vector<sets::Seg> segs = sets::slice(j.tables(), t.seg_rows[0], t.seg_rows[t.n_segs]);
+  DeviceGuard g(c->m->device);
+  CtxUse use;
+  HIP_TRY(use.enter(c, s));
+  int rc = fdnn::align_frames_stage(c, j, host, s);
+  SetsCall sc;
+  sc.first = t.seg_rows[0], sc.segs = &segs, sc.d_nodes = c->d_al_int, sc.d_probs = c->d_al_probs, sc.d_inactive = c->d_al_inact;
+  if (!rc) rc = run_sets(c, sc, s);
+  if (!rc) rc = fdnn::align_frames_finish(c, j, io.out, host, s);
+  if (rc && host) hipStreamSynchronize(s);
+  return rc;
+}
+
+int fdnn_ctx_align_frames(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs, const int32_t *states,
+                          const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, int free_start,
+                          const int32_t *frame_base, const float *d_in, const int32_t *begin_in, float *d_out, int32_t *begin_out, float *frame_best,
+                          int32_t *frame_end, int32_t *frame_begin) {
+  return ctx_align_frames(c, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp),
+                          {free_start, frame_base, d_in, begin_in, {d_out, begin_out, frame_best, frame_end, frame_begin}}, true, c ? c->stream : nullptr);
+}
+
+int fdnn_ctx_align_frames_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                 const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp,
+                                 const float *final_lp, int free_start, const int32_t *frame_base, const float *d_d_in, const int32_t *d_begin_in,
+                                 float *d_d_out, int32_t *d_begin_out, float *d_frame_best, int32_t *d_frame_end, int32_t *d_frame_begin, void *stream) {
+  return ctx_align_frames(c, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp),
+                          {free_start, frame_base, d_d_in, d_begin_in, {d_d_out, d_begin_out, d_frame_best, d_frame_end, d_frame_begin}}, false,
+                          static_cast<hipStream_t>(stream));
+}
+
+// One-call forms: hidden layers + the graphs' node sets chunk by chunk into the context's buffers (the sibling's sink), the
+// sweep ONCE behind the last chunk, inside the same use of the context.
+static int calculate_align_frames(fdnn_model *m, const Pass &p, fdnn::AlignFramesJob &j, const fdnn::AlignFramesOut &o, int n) {
+  return score_chunks(m, frame_chunks(n, m), p, nullptr, [&](fdnn_ctx *c, hipStream_t s) { return fdnn::align_frames_stage(c, j, true, s); },
+                      [&](fdnn_ctx *c, hipStream_t s) {
+                        const int rc = fdnn::align_frames_finish(c, j, o, true, s);
+                        if (rc) hipStreamSynchronize(s);
+                        return rc;
+                      });
+}
+
+int fdnn_calculate_align_frames(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr,
+                                int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                                const float *start_lp, const float *final_lp, int free_start, const int32_t *frame_base, const float *d_in,
+                                const int32_t *begin_in, float *d_out, int32_t *begin_out, float *frame_best, int32_t *frame_end, int32_t *frame_begin) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const AlignFramesIo io{free_start, frame_base, d_in, begin_in, {d_out, begin_out, frame_best, frame_end, frame_begin}};
+  fdnn::AlignFramesJob j;
+  if (int rc = align_frames_front(m, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), io, n, &j))
+    return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!x) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = align_frames_results(io)) return rc;
+  if (int rc = check_input_width(m, dim)) return rc;
+  const sets::Tables t = j.tables();
+  return calculate_align_frames(m, Pass::host_align("fdnn_calculate_align_frames", x, t), j, io.out, n);
+}
+
+int fdnn_calculate_align_frames_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                    const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src,
+                                    const float *arc_lp, const float *start_lp, const float *final_lp, int free_start, const int32_t *frame_base,
+                                    const float *d_in, const int32_t *begin_in, float *d_out, int32_t *begin_out, float *frame_best, int32_t *frame_end,
+                                    int32_t *frame_begin) {
+  if (!m || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const fdnn::SpliceRef spec = m->splice;
+  if (int rc = fdnn::splice_check(spec, raw_dim)) return rc;
+  const AlignFramesIo io{free_start, frame_base, d_in, begin_in, {d_out, begin_out, frame_best, frame_end, frame_begin}};
+  fdnn::AlignFramesJob j;
+  if (int rc = align_frames_front(m, ll, graph_tables(seg_rows, state_ptr, n_segs, states, arc_ptr, arc_src, arc_lp, start_lp, final_lp), io, n, &j))
+    return rc;
+  if (n_segs == 0 ? n != 0 : (seg_rows[0] != 0 || seg_rows[n_segs] != n)) return fail(FDNN_E_ARG, "seg_rows must cover the rows [0, n)");
+  if (n == 0) return FDNN_OK;
+  if (!raw) return fail(FDNN_E_ARG, "null buffer");
+  if (int rc = align_frames_results(io)) return rc;
+  // every segment is an utterance of its own: its edges repeat its own first and last frame
+  std::vector<SpliceSeg> segs;
+  for (int s = 0; s < n_segs; ++s) segs.push_back(SpliceSeg{seg_rows[s], seg_rows[s], seg_rows[s], seg_rows[s + 1] - 1});
+  const sets::Tables t = j.tables();
+  return calculate_align_frames(m, Pass::raw_align("fdnn_calculate_align_frames_raw", {spec.get(), &segs, raw, n}, t), j, io.out, n);
+}
+
+int fdnn_debug_align_frames_launches(unsigned long long *out, int cap) { return counts_out(out, cap, 2, fdnn::align_frames_launch_counts); }
+
+// The recursion in plain C++ (fdnn_align_frames.hpp: ref), no device: rows, tables and handle values as
+// fdnn_debug_align_graph_ref, the carry arrays on the host.
+int fdnn_debug_align_frames_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld, const int32_t *state_ptr,
+                                int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior, int width, float floor, int type,
+                                const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp,
+                                int free_start, const int32_t *frame_base, const float *d_in, const int32_t *begin_in, float *d_out, int32_t *begin_out,
+                                float *frame_best, int32_t *frame_end, int32_t *frame_begin) {
+  if (int rc = align_frames_flags(free_start, d_in, begin_in)) return rc;
+  if (n_segs > 0 && !arc_ptr) return fail(FDNN_E_ARG, "align frames, segment 0: malformed tables");
+  if (int rc = align_graph_rows_tables(seg_T, row_off, row_ld, state_ptr, arc_ptr, n_segs)) return rc;
+  if (n_segs == 0) return FDNN_OK;
+  if (type != fdnn::align::kScores && (fdnn::loglik::check_handle(log_prior, width, floor, type) != 0 || !state_node))
+    return fail(FDNN_E_ARG, "log_prior [width] finite, the floor -inf or finite (F16: not below -65504), the type F32, F16 or -1 (scores)");
+  if (!rows || !col || !frame_best || !frame_end || !frame_begin || (arc_ptr[state_ptr[n_segs]] > 0 && (!arc_src || !arc_lp)))
+    return fail(FDNN_E_ARG, "null buffer");
+  size_t at = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const int b = state_ptr[s], S = state_ptr[s + 1] - b;
+    fdnn::align_frames::ref(reinterpret_cast<const uint32_t *>(rows) + row_off[s], seg_T[s], row_ld[s], col + b, state_node ? state_node + b : nullptr, S,
+                            log_prior, width, floor, type, arc_ptr + b, arc_src, arc_lp, start_lp ? start_lp + b : nullptr,
+                            final_lp ? final_lp + b : nullptr, free_start != 0, frame_base ? frame_base[s] : 0,
+                            d_in ? reinterpret_cast<const uint32_t *>(d_in) + b : nullptr, begin_in ? begin_in + b : nullptr,
+                            d_out ? reinterpret_cast<uint32_t *>(d_out) + b : nullptr, begin_out ? begin_out + b : nullptr,
+                            reinterpret_cast<uint32_t *>(frame_best) + at, frame_end + at, frame_begin + at);
+    at += size_t(seg_T[s]);
+  }
+  return FDNN_OK;
+}
+
 int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out) {
   if (!c || !out) return fail(FDNN_E_ARG, "null argument");
   if (c->last < 0) return fail(FDNN_E_STATE, "hidden layers not computed yet");

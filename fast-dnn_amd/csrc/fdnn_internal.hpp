@@ -495,6 +495,40 @@ int fb_frames_stage(fdnn_ctx *c, const FbFramesJob &j, bool host, hipStream_t s)
 // device buffers on s.
 int fb_frames_finish(fdnn_ctx *c, const FbFramesJob &j, float *alpha_out, float *frame_total, bool host, hipStream_t s);
 
+// ---------------------------------------------------------------- alignment graphs, best path, frame by frame (fdnn_align_frames.hip)
+// One call's validated host tables and what is derived from them before anything is launched (align_frames_prepare): as
+// AlignGraphJob with align_frames' plan, which needs no scratch.  The sets step is the sibling's.
+struct AlignFramesJob {
+  const fdnn_loglik *ll = nullptr;
+  align_graph::Tables t;
+  bool free_start = false;
+  const int32_t *frame_base = nullptr;  // host [segments] or null
+  const float *d_in = nullptr;          // [states of the call] or null, with begin_in: host memory (host = true below) or device memory
+  const int32_t *begin_in = nullptr;
+  align::Sets sets;
+  std::vector<int32_t> seg_T, row_ld;
+  std::vector<long long> row_off;  // segment s's block in the ragged probabilities
+  long long nnz = 0;
+  int rows = 0;                    // seg_rows[n_segs] - seg_rows[0]
+  align_graph::Plan plan;
+  sets::Tables tables() const { return {t.seg_rows, sets.set_ptr.data(), t.n_segs}; }
+};
+// The caller's results and carry-out arrays: host or device memory alike
+struct AlignFramesOut {
+  float *d_out = nullptr;
+  int32_t *begin_out = nullptr;
+  float *frame_best = nullptr;
+  int32_t *frame_end = nullptr, *frame_begin = nullptr;
+};
+// FDNN_E_ARG naming the first bad segment (align_graph::check; more than align_frames::kMaxStates states) or the sum of rows x
+// len past an int32; else fills j from its table pointers.  Nothing is launched.
+int align_frames_prepare(AlignFramesJob *j, int output_dim, int ctx_rows);
+// The context's buffers made large enough, the tables and (host = true) the carry row uploaded on s.
+int align_frames_stage(fdnn_ctx *c, const AlignFramesJob &j, bool host, hipStream_t s);
+// The sweep over the probabilities that the sets calls left in c->d_al_probs, then: host = true -- ONE transfer of the three
+// per-frame arrays and the carry row, and s synchronised; false -- copied to the caller's device buffers on s.
+int align_frames_finish(fdnn_ctx *c, const AlignFramesJob &j, const AlignFramesOut &o, bool host, hipStream_t s);
+
 // ---------------------------------------------------------------- one scoring pass, one chunk loop
 // Hidden layers + what the pass's sink asks for, chunk by chunk, on context c and stream s; every pointer a chunk uses comes
 // from pass::chunk_view.  Per chunk: the rows in (spliced / uploaded / as they are), host bits up, the hidden layers, the sink's

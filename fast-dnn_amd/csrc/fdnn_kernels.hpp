@@ -18,6 +18,7 @@
 #include "fdnn_align_graph.hpp"
 #include "fdnn_fb.hpp"
 #include "fdnn_fb_frames.hpp"
+#include "fdnn_align_frames.hpp"
 
 // Run-time switches.  The DEPLOYMENT switches (FDNN_BATCHER, FDNN_DEVICES, FDNN_FUSE_NORM,
 // FDNN_GROUP_*, FDNN_JNI_KEEP_MB, FDNN_CHAIN, FDNN_CHUNK_FRAMES) are read with std::getenv; those that bear on which kernel
@@ -381,6 +382,32 @@ struct FbFramesArgs {
 };
 void launch_fb_frames(const fb_frames::Plan &p, const FbFramesArgs &a, hipStream_t s);
 void fb_frames_launch_counts(unsigned long long out[3]);  // launches so far: sweep wave, sweep workgroup, row totals
+
+// Alignment graphs, best path, frame by frame (fdnn_align_frames.hip; the contract, the plan and the host restatement:
+// fdnn_align_frames.hpp): ONE launch per launch of the plan (align_frames::plan), no scratch.  rows .. the arc tables and
+// d_start_lp / d_final_lp as AlignGraphArgs.  frame_base: a HOST table [segments of the call] or null (zeros), passed to the
+// kernels by value.  d_d_in + d_begin_in / d_d_out / d_begin_out [states of the call] or null; the three results
+// [sum of T].  The forms follow align_graph_kernel_mode().
+struct AlignFramesArgs {
+  const float *d_rows = nullptr;
+  const int32_t *d_col = nullptr, *d_state_node = nullptr;
+  const float *d_log_prior = nullptr;
+  int width = 0;
+  float floor = 0.0f;
+  int type = align::kScores;
+  const int32_t *d_arc_ptr = nullptr, *d_arc_src = nullptr;
+  const float *d_arc_lp = nullptr, *d_start_lp = nullptr, *d_final_lp = nullptr;
+  bool free_start = false;
+  const int32_t *frame_base = nullptr;
+  const float *d_d_in = nullptr;
+  const int32_t *d_begin_in = nullptr;
+  float *d_d_out = nullptr;
+  int32_t *d_begin_out = nullptr;
+  float *d_frame_best = nullptr;
+  int32_t *d_frame_end = nullptr, *d_frame_begin = nullptr;
+};
+void launch_align_frames(const align_graph::Plan &p, const AlignFramesArgs &a, hipStream_t s);
+void align_frames_launch_counts(unsigned long long out[2]);  // launches so far: wave form, workgroup form
 
 // bits[f][w] bit b = mask[f][64 w + b] != 0  (words per row = ceil(rows / 64); bits past the row are zero).  The lazy
 // contract's byte masks (80 MB for 10 000 frames x 8000 nodes) are read once here, at HBM speed, instead of inside the

@@ -1393,6 +1393,99 @@ int fb_frames_finish(fdnn_ctx *c, const FbFramesJob &j, float *alpha_out, float 
   return FDNN_OK;
 }
 
+// ---------------------------------------------------------------- alignment graphs, best path, frame by frame (fdnn_align_frames.hip)
+int align_frames_prepare(AlignFramesJob *j, int output_dim, int ctx_rows) {
+  align_graph::Why why;
+  const int bad = align_graph::check(j->t, output_dim, ctx_rows, &why);
+  if (bad) return fail(FDNN_E_ARG, "align frames, segment " + std::to_string(-bad - 1) + ": " + align_graph::why_text(why));
+  const int n = j->t.n_segs;
+  const int big = align_frames::too_many_states(j->t.state_ptr, n);
+  if (big >= 0)
+    return fail(FDNN_E_ARG, "align frames, segment " + std::to_string(big) + ": a graph has at most " + std::to_string(align_frames::kMaxStates) + " states");
+  j->sets = align::build_sets(j->t.state_ptr, j->t.states, n);
+  j->seg_T.resize(size_t(n)), j->row_ld.resize(size_t(n)), j->row_off.resize(size_t(n));
+  j->nnz = 0;
+  for (int s = 0; s < n; ++s) {
+    j->seg_T[size_t(s)] = j->t.seg_rows[s + 1] - j->t.seg_rows[s];
+    j->row_ld[size_t(s)] = j->sets.set_ptr[size_t(s) + 1] - j->sets.set_ptr[size_t(s)];
+    j->row_off[size_t(s)] = j->nnz;
+    j->nnz += static_cast<long long>(j->seg_T[size_t(s)]) * j->row_ld[size_t(s)];
+    if (j->nnz > INT32_MAX)
+      return fail(FDNN_E_ARG, "align frames, segment " + std::to_string(s) + ": the sum of rows x distinct nodes over the segments must fit an int32");
+  }
+  j->rows = n ? j->t.seg_rows[n] - j->t.seg_rows[0] : 0;
+  j->plan = align_frames::plan(j->seg_T.data(), j->row_off.data(), j->row_ld.data(), j->t.state_ptr, j->t.arc_ptr, n, align_graph_kernel_mode());
+  return FDNN_OK;
+}
+
+// d_al_res holds frame_best, frame_end, frame_begin [rows each], then d_out, begin_out, d_in, begin_in [states each]
+int align_frames_stage(fdnn_ctx *c, const AlignFramesJob &j, bool host, hipStream_t s) {
+  const size_t n_nodes = j.sets.nodes.size(), n_states = j.sets.col.size(), n_arcs = size_t(j.t.arc_ptr[n_states]);
+  const size_t arcs1 = std::max<size_t>(n_arcs, 1), rows = size_t(j.rows);
+  HIP_TRY(c->d_al_int.reserve(n_nodes + 2 * n_states));
+  HIP_TRY(c->d_ag_int.reserve(n_states + 1 + arcs1));
+  HIP_TRY(c->d_ag_lp.reserve(arcs1 + 2 * n_states));
+  HIP_TRY(c->d_al_probs.reserve(std::max<size_t>(size_t(j.nnz), 1)));
+  HIP_TRY(c->d_al_inact.reserve(std::max<size_t>(rows, 1)));
+  HIP_TRY(c->d_al_res.reserve(3 * rows + 4 * n_states));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int, j.sets.nodes.data(), sizeof(int32_t) * n_nodes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int.p + n_nodes, j.sets.col.data(), sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_al_int.p + n_nodes + n_states, j.t.states, sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_ag_int, j.t.arc_ptr, sizeof(int32_t) * (n_states + 1), hipMemcpyHostToDevice, s));
+  if (n_arcs) {
+    HIP_TRY(hipMemcpyAsync(c->d_ag_int.p + n_states + 1, j.t.arc_src, sizeof(int32_t) * n_arcs, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->d_ag_lp, j.t.arc_lp, sizeof(float) * n_arcs, hipMemcpyHostToDevice, s));
+  }
+  float *tail = c->d_ag_lp.p + arcs1;
+  if (j.t.start_lp) HIP_TRY(hipMemcpyAsync(tail, j.t.start_lp, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  if (j.t.final_lp) HIP_TRY(hipMemcpyAsync(tail + n_states, j.t.final_lp, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+  if (j.d_in && host) {
+    int32_t *in = c->d_al_res.p + 3 * rows + 2 * n_states;
+    HIP_TRY(hipMemcpyAsync(in, j.d_in, sizeof(float) * n_states, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(in + n_states, j.begin_in, sizeof(int32_t) * n_states, hipMemcpyHostToDevice, s));
+  }
+  return FDNN_OK;
+}
+
+int align_frames_finish(fdnn_ctx *c, const AlignFramesJob &j, const AlignFramesOut &o, bool host, hipStream_t s) {
+  const size_t n_nodes = j.sets.nodes.size(), n_states = j.sets.col.size(), rows = size_t(j.rows);
+  const size_t n_arcs = size_t(j.t.arc_ptr[n_states]);
+  float *tail = c->d_ag_lp.p + std::max<size_t>(n_arcs, 1);
+  int32_t *res = c->d_al_res.p, *carry = res + 3 * rows;
+  AlignFramesArgs a;
+  a.d_rows = c->d_al_probs, a.d_col = c->d_al_int.p + n_nodes, a.d_state_node = c->d_al_int.p + n_nodes + n_states;
+  a.d_log_prior = j.ll->d_log_prior, a.width = j.ll->width, a.floor = j.ll->floor, a.type = j.ll->type;
+  a.d_arc_ptr = c->d_ag_int, a.d_arc_src = c->d_ag_int.p + n_states + 1, a.d_arc_lp = c->d_ag_lp;
+  a.d_start_lp = j.t.start_lp ? tail : nullptr, a.d_final_lp = j.t.final_lp ? tail + n_states : nullptr;
+  a.free_start = j.free_start, a.frame_base = j.frame_base;
+  if (j.d_in) {
+    a.d_d_in = host ? reinterpret_cast<const float *>(carry + 2 * n_states) : j.d_in;
+    a.d_begin_in = host ? carry + 3 * n_states : j.begin_in;
+  }
+  a.d_d_out = o.d_out ? reinterpret_cast<float *>(carry) : nullptr, a.d_begin_out = o.begin_out ? carry + n_states : nullptr;
+  a.d_frame_best = reinterpret_cast<float *>(res), a.d_frame_end = res + rows, a.d_frame_begin = res + 2 * rows;
+  launch_align_frames(j.plan, a, s);
+  HIP_TRY(hipGetLastError());
+  if (!host) {
+    HIP_TRY(hipMemcpyAsync(o.frame_best, res, 4 * rows, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(o.frame_end, res + rows, 4 * rows, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(o.frame_begin, res + 2 * rows, 4 * rows, hipMemcpyDeviceToDevice, s));
+    if (o.d_out) HIP_TRY(hipMemcpyAsync(o.d_out, carry, 4 * n_states, hipMemcpyDeviceToDevice, s));
+    if (o.begin_out) HIP_TRY(hipMemcpyAsync(o.begin_out, carry + n_states, 4 * n_states, hipMemcpyDeviceToDevice, s));
+    return FDNN_OK;
+  }
+  const bool carry_out = o.d_out || o.begin_out;
+  std::vector<int32_t> land(3 * rows + (carry_out ? 2 * n_states : 0));  // one transfer: 12 bytes a frame and 8 a state
+  HIP_TRY(hipMemcpyAsync(land.data(), res, sizeof(int32_t) * land.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::memcpy(o.frame_best, land.data(), 4 * rows);
+  std::memcpy(o.frame_end, land.data() + rows, 4 * rows);
+  std::memcpy(o.frame_begin, land.data() + 2 * rows, 4 * rows);
+  if (o.d_out) std::memcpy(o.d_out, land.data() + 3 * rows, 4 * n_states);
+  if (o.begin_out) std::memcpy(o.begin_out, land.data() + 3 * rows + n_states, 4 * n_states);
+  return FDNN_OK;
+}
+
 // The host half of a compacted lazy return (lazy_compact_kernel): a compacted row is the row's inactive value followed by
 // its active nodes' probabilities in node order; expanding it = every node reads the next active value or the inactive one.
 // With AVX-512 that is one expanding load per 16 nodes (the mask's 16 bits select which lanes take the next values from

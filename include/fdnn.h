@@ -739,6 +739,72 @@ FDNN_API int fdnn_calculate_fb_frames_raw(fdnn_model *m, const float *raw, int n
                                           const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr,
                                           const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, int free_start,
                                           const float *alpha_in, float *alpha_out, float *frame_total);
+/* ------------------------------------------------------------------ alignment graphs, best path, frame by frame (fdnn_align_frames.hip)
+ * The FRAMES FORM of the best path over alignment graphs: at EVERY frame the best path's score, the state it ends in and THE
+ * FRAME IT BEGAN AT, with a start that may be free and a row carried from one call to the next -- "keyword from frame b to
+ * frame t, score s" after every push, which a sum over paths cannot say.  Every entry below extends LazyOutputActivations
+ * (dnn.cc:355-392).  THE CONTRACT IS STATED ONCE, in csrc/fdnn_align_frames.hpp, which calls the arithmetic of
+ * csrc/fdnn_align_graph.hpp; in short:
+ *
+ * The inputs are those of the alignment graphs, checked by the same validator (here at most 8192 states a graph), and
+ *   free_start   0 or 1: with 1 a path may begin at any frame
+ *   frame_base   NULL (zeros), or one int32 per segment, ALWAYS A HOST TABLE: the caller's number for the segment's first row
+ *                in this call; begin frames are reported in that numbering
+ *   d_in, begin_in    both NULL or both given (else FDNN_E_ARG): one float and one int32 per state of the call, laid out like
+ *                `states`: the recursion's row from the frame before this call's first row; begin_in values are opaque
+ *   d_out, begin_out  NULL, or the same shape: the last row, for the next call -- where a d is a NaN it is SOME NaN.  Each may
+ *                be the very buffer of its _in twin; a partial overlap is not allowed
+ *   frame_best, frame_end, frame_begin   one float / int32 / int32 per row of the call; segment s begins at the sum of T
+ *                over the segments before it
+ * Frame 0 without carry is the start row, d = start_lp[j] + e(0, j), begin = frame_base where start_lp[j] > -inf, else -1.
+ * Every other frame, and frame 0 with carry: the arcs go through the candidate step in the caller's order (the earliest
+ * arc wins a tie) and the state takes the begin of the source taken; then, with free_start, the start term LAST: where
+ * start_lp[j] is ABOVE the best candidate the path begins here, begin = frame_base + t (a tie keeps the running path);
+ * d = best + e(t, j).  Per frame the final selection of the alignment graphs over d + final_lp (the lowest state wins a
+ * tie): frame_best its score (never a NaN), frame_end its state or -1, frame_begin that state's begin or -1.
+ * Anchored and uncarried, frame_best[t] has the bytes of fdnn_debug_align_graph_ref's total on the segment cut to t + 1 rows.
+ * A segment cut at ANY frame into two calls (carry handed on, frame_base advanced by the cut) gives the uncut call's bytes.
+ * With free_start and a finite frame_best[t], fdnn_calculate_align_graph on rows frame_begin[t] .. t gives that score as its
+ * total and a path that ends in frame_end[t]: that call is how the path itself is had.  Results equal
+ * fdnn_debug_align_frames_ref byte for byte, whatever the kernel form (fdnn_debug_set_align_graph_kernel forces these kernels
+ * too), the chunking or the entry point.  One launch per form and 64 segments; no scratch.  FDNN_E_ARG before anything is
+ * launched.  Nothing is routed to these entry points.
+ *
+ * fdnn_align_frames_rows_device   the sweep alone on any device-resident fp32 rows (dnn.cc:355-392): the host tables and the
+ *   device copies as fdnn_align_graph_rows_device; the carry arrays and results on the device.  Enqueued on `stream`.
+ * fdnn_ctx_align_frames           host tables, host carry arrays and host results, host-synchronous, over rows of a context
+ *   whose hidden layers have run (dnn.cc:355-392).
+ * fdnn_ctx_align_frames_device    the same with device carry arrays and device results, enqueued on `stream`; the host tables
+ *   are read before it returns (dnn.cc:355-392).
+ * fdnn_calculate_align_frames     one call on a pooled context (dnn.cc:355-392): seg_rows must cover [0, n); a large n goes
+ *   chunk by chunk and the sweep runs ONCE behind the last chunk.
+ * fdnn_calculate_align_frames_raw the same from raw feature frames [n][raw_dim]; every segment is an utterance of its own
+ *   (dnn.cc:355-392). */
+FDNN_API int fdnn_align_frames_rows_device(const fdnn_loglik *ll, const float *d_rows, const int32_t *seg_T, const long long *row_off,
+                                           const int32_t *row_ld, const int32_t *state_ptr, const int32_t *arc_ptr, int n_segs, const int32_t *d_col,
+                                           const int32_t *d_state_node, const int32_t *d_arc_ptr, const int32_t *d_arc_src, const float *d_arc_lp,
+                                           const float *d_start_lp, const float *d_final_lp, int free_start, const int32_t *frame_base,
+                                           const float *d_d_in, const int32_t *d_begin_in, float *d_d_out, int32_t *d_begin_out, float *d_frame_best,
+                                           int32_t *d_frame_end, int32_t *d_frame_begin, void *stream);
+FDNN_API int fdnn_ctx_align_frames(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                   const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp, const float *start_lp,
+                                   const float *final_lp, int free_start, const int32_t *frame_base, const float *d_in, const int32_t *begin_in,
+                                   float *d_out, int32_t *begin_out, float *frame_best, int32_t *frame_end, int32_t *frame_begin);
+FDNN_API int fdnn_ctx_align_frames_device(fdnn_ctx *c, const fdnn_loglik *ll, const int32_t *seg_rows, const int32_t *state_ptr, int n_segs,
+                                          const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                                          const float *start_lp, const float *final_lp, int free_start, const int32_t *frame_base,
+                                          const float *d_d_in, const int32_t *d_begin_in, float *d_d_out, int32_t *d_begin_out, float *d_frame_best,
+                                          int32_t *d_frame_end, int32_t *d_frame_begin, void *stream);
+FDNN_API int fdnn_calculate_align_frames(fdnn_model *m, const float *x, int n, int dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                         const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr, const int32_t *arc_src,
+                                         const float *arc_lp, const float *start_lp, const float *final_lp, int free_start, const int32_t *frame_base,
+                                         const float *d_in, const int32_t *begin_in, float *d_out, int32_t *begin_out, float *frame_best,
+                                         int32_t *frame_end, int32_t *frame_begin);
+FDNN_API int fdnn_calculate_align_frames_raw(fdnn_model *m, const float *raw, int n, int raw_dim, const fdnn_loglik *ll, const int32_t *seg_rows,
+                                             const int32_t *state_ptr, int n_segs, const int32_t *states, const int32_t *arc_ptr,
+                                             const int32_t *arc_src, const float *arc_lp, const float *start_lp, const float *final_lp, int free_start,
+                                             const int32_t *frame_base, const float *d_in, const int32_t *begin_in, float *d_out, int32_t *begin_out,
+                                             float *frame_best, int32_t *frame_end, int32_t *frame_begin);
 /* Last hidden layer's u8 activations, n x hidden_dim (quantized_activations_). */
 FDNN_API int fdnn_ctx_read_hidden(fdnn_ctx *c, uint8_t *out);
 
@@ -1186,6 +1252,20 @@ FDNN_API int fdnn_debug_fb_frames_ref(const float *rows, const int32_t *seg_T, c
                                       int width, float floor, int type, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
                                       const float *start_lp, const float *final_lp, int free_start, const float *alpha_in, float *alpha_out,
                                       float *frame_total);
+
+/* Alignment graphs, best path, frame by frame (LazyOutputActivations, dnn.cc:355-392), tests and tools.
+ * fdnn_debug_align_frames_launches  process-wide counts since load, returns 2: out[0] launches of the wave form, [1] of the
+ *   workgroup form.  A counter of their own: the align-graph kernels' counts do not move.
+ * fdnn_debug_align_frames_ref       fdnn_align_frames_rows_device from the host restatement (fdnn_align_frames.hpp) on host
+ *   rows and host arrays; type as fdnn_debug_align_ref; the carry arrays may be NULL; host code, no device needed
+ *   (dnn.cc:355-392). */
+FDNN_API int fdnn_debug_align_frames_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_align_frames_ref(const float *rows, const int32_t *seg_T, const long long *row_off, const int32_t *row_ld,
+                                         const int32_t *state_ptr, int n_segs, const int32_t *col, const int32_t *state_node, const float *log_prior,
+                                         int width, float floor, int type, const int32_t *arc_ptr, const int32_t *arc_src, const float *arc_lp,
+                                         const float *start_lp, const float *final_lp, int free_start, const int32_t *frame_base, const float *d_in,
+                                         const int32_t *begin_in, float *d_out, int32_t *begin_out, float *frame_best, int32_t *frame_end,
+                                         int32_t *frame_begin);
 
 /* Splicing through a segment table in device memory (the scoring loop's live batches, fdnn_splice.hip), tests and tools.
  * fdnn_debug_splice_table   the splice alone, host in and host out: raw [raw_frames][raw_dim] -> x [rows][input_dim] under the
