@@ -354,6 +354,22 @@ SIGNATURES = {
     "fdnn_report_add_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "fdnn_report_add": (C.c_int, [C.c_void_p, _c_f32p, _c_f32p, C.c_int]),
     "fdnn_report_read": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_double)]),
+    "fdnn_half_model_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "fdnn_half_model_load_on": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "fdnn_half_model_free": (None, [C.c_void_p]),
+    "fdnn_half_model_input_dim": (C.c_int, [C.c_void_p]),
+    "fdnn_half_model_output_dim": (C.c_int, [C.c_void_p]),
+    "fdnn_half_model_layer_count": (C.c_int, [C.c_void_p]),
+    "fdnn_half_model_layer_dim": (C.c_int, [C.c_void_p, C.c_int]),
+    "fdnn_half_model_device": (C.c_int, [C.c_void_p]),
+    "fdnn_half_calculate": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_f32p]),
+    "fdnn_half_calculate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fdnn_debug_half_layer": (C.c_int, [C.c_void_p, C.c_int, _c_f32p, C.c_int, _c_f32p, _c_f32p]),
+    "fdnn_debug_half_layer_us": (C.c_int, [C.c_void_p, C.c_int, _c_f32p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "fdnn_debug_half_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "fdnn_debug_half_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_half_pack": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_longlong), C.c_int]),
+    "fdnn_debug_half_extents": (C.c_int, [_c_i32p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
 }
 
 JNI_SYMBOLS = [
@@ -3105,3 +3121,116 @@ class AccuracyReport:
         if nodeSums:
             out["node_sum"] = ns
         return out
+
+
+# ------------------------------------------------------------------------------------------------ the half-precision net
+HALF_LAUNCH_KINDS = ("hgemm.sigmoid", "hgemm.exp", "hgemm.sigmoid.tap", "hgemm.exp.tap", "input_step")
+
+
+def half_launches() -> dict:
+    """Process-wide launch counts of the half net's kernels since load (``fdnn_debug_half_launches``)."""
+    buf = (C.c_ulonglong * len(HALF_LAUNCH_KINDS))()
+    if lib().fdnn_debug_half_launches(buf, len(HALF_LAUNCH_KINDS)) != len(HALF_LAUNCH_KINDS):
+        raise RuntimeError("fdnn_debug_half_launches")
+    return dict(zip(HALF_LAUNCH_KINDS, (int(v) for v in buf)))
+
+
+def half_pack(dnnFile: str) -> dict:
+    """The half net's packed blob of a .bin, no device (``fdnn_debug_half_pack``) -> blob (uint8), layers (dicts of off_w,
+    off_bias, rows, rows_pad, K, K_pad), off_shift, off_scale."""
+    path = os.path.abspath(dnnFile).encode()
+    count = lib().fdnn_debug_half_pack(path, None, 0, None, 0)
+    _check(min(count, 0))
+    desc = (C.c_longlong * count)()
+    lib().fdnn_debug_half_pack(path, None, 0, desc, count)
+    blob = np.empty(int(desc[count - 1]), dtype=np.uint8)
+    _check(min(lib().fdnn_debug_half_pack(path, blob.ctypes.data_as(C.c_void_p), blob.size, desc, count), 0))
+    keys = ("off_w", "off_bias", "rows", "rows_pad", "K", "K_pad")
+    layers = [dict(zip(keys, (int(v) for v in desc[6 * j:6 * j + 6]))) for j in range((count - 3) // 6)]
+    return {"blob": blob, "layers": layers, "off_shift": int(desc[count - 3]), "off_scale": int(desc[count - 2])}
+
+
+def half_extents(shape, n: int, chunk: int = 0) -> dict:
+    """What a call of n frames reserves and touches, no device (``fdnn_debug_half_extents``); shape = (k0_pad, act_ld,
+    out_rows, out_rows_pad)."""
+    out = (C.c_longlong * 7)()
+    _check(lib().fdnn_debug_half_extents((C.c_int32 * 4)(*shape), int(n), int(chunk), out))
+    return dict(zip(("xs", "act", "partial", "xs_touched", "act_touched", "partial_touched", "tiled"), (int(v) for v in out)))
+
+
+class HalfDnn:
+    """The HALF-PRECISION net on one MI355X: the .bin's weights rounded once to fp16, fp16 activations, fp32 sums on the fp16
+    MFMA, fp32 sigmoid and soft-max (contract: csrc/fdnn_half.hpp).  Mirrors ``FloatDnn``."""
+
+    def __init__(self, handle: int):
+        self.nativeHandle = handle
+
+    @staticmethod
+    def loadFromFile(dnnFile: str, device: Optional[int] = None) -> "HalfDnn":
+        h = C.c_void_p()
+        path = os.path.abspath(dnnFile).encode()
+        if device is None:
+            _check(lib().fdnn_half_model_load(path, C.byref(h)))
+        else:
+            _check(lib().fdnn_half_model_load_on(path, int(device), C.byref(h)))
+        return HalfDnn(h.value)
+
+    def delete(self) -> None:
+        if self.nativeHandle:
+            lib().fdnn_half_model_free(self.nativeHandle)
+            self.nativeHandle = None
+
+    def inputDimension(self) -> int:
+        return lib().fdnn_half_model_input_dim(self.nativeHandle)
+
+    def outputDimension(self) -> int:
+        return lib().fdnn_half_model_output_dim(self.nativeHandle)
+
+    def layerCount(self) -> int:
+        return lib().fdnn_half_model_layer_count(self.nativeHandle)
+
+    def layerDimension(self, layerIndex: int) -> int:
+        return lib().fdnn_half_model_layer_dim(self.nativeHandle, int(layerIndex))
+
+    def device(self) -> int:
+        return lib().fdnn_half_model_device(self.nativeHandle)
+
+    def calculate(self, input) -> np.ndarray:
+        """[n][inputDimension] -> soft-max rows [n][outputDimension], fp32."""
+        x = _f32(input)
+        if x.shape[0] == 0:
+            return np.zeros((0, 0), dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.inputDimension():
+            raise ValueError(f"Input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        out = np.empty((x.shape[0], self.outputDimension()), dtype=np.float32)
+        _check(lib().fdnn_half_calculate(self.nativeHandle, x.ctypes.data_as(_c_f32p), x.shape[0], x.shape[1], out.ctypes.data_as(_c_f32p)))
+        return out
+
+    def calculateDevice(self, d_x: int, n: int, d_out: int, stream: int = 0) -> None:
+        """Device-resident form: raw device pointers (e.g. ``tensor.data_ptr()``), enqueued on ``stream``, not synchronised."""
+        _check(lib().fdnn_half_calculate_device(self.nativeHandle, C.c_void_p(d_x), int(n), C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def setChunk(self, rows: int) -> None:
+        """Frames per internal chunk (``fdnn_debug_half_set_chunk``; 0 = default).  Results never depend on it."""
+        _check(lib().fdnn_debug_half_set_chunk(self.nativeHandle, int(rows)))
+
+    def layer(self, j: int, input):
+        """ONE layer on the caller's rows, rounded to fp16 by the call (``fdnn_debug_half_layer``) -> (z fp32, the stored halves
+        widened to fp32; the probabilities for the last layer); j == -1 is the input step -> (x + shift, the halves of
+        (x + shift) * scale)."""
+        x = _f32(input)
+        width = self.inputDimension() if j < 0 else self.layerDimension(j)
+        if width < 0:
+            raise ValueError(f"layer index {j} outside -1 .. {self.layerCount() - 1}")
+        lin = np.empty((x.shape[0], width), dtype=np.float32)
+        act = np.empty_like(lin)
+        _check(lib().fdnn_debug_half_layer(self.nativeHandle, int(j), x.ctypes.data_as(_c_f32p), x.shape[0], lin.ctypes.data_as(_c_f32p),
+                                           act.ctypes.data_as(_c_f32p)))
+        return lin, act
+
+    def layerMicros(self, j: int, input, reps: int = 10) -> float:
+        """Device microseconds per run of layer j on the caller's rows (``fdnn_debug_half_layer_us``; measurement only)."""
+        x = _f32(input)
+        us = C.c_double()
+        _check(lib().fdnn_debug_half_layer_us(self.nativeHandle, int(j), x.ctypes.data_as(_c_f32p), x.shape[0], int(reps), C.byref(us)))
+        return float(us.value)

@@ -7,45 +7,14 @@
 
 #include "fdnn_float.hpp"
 #include "fdnn_internal.hpp"
+#include "fdnn_stream_order.hpp"
 
 using fdnn::DevBuf;
+using fdnn::device_ok;
 using fdnn::DeviceGuard;
 using fdnn::fail;
+using fdnn::StreamOrder;
 namespace fl = fdnn::fl;
-
-namespace {
-
-// One set of buffers serves every call of an object: a call on another stream waits (on the device) for the one before.
-struct StreamOrder {
-  hipEvent_t ev = nullptr;
-  hipStream_t last = nullptr;
-  bool valid = false;
-  ~StreamOrder() {
-    if (ev) hipEventDestroy(ev);
-  }
-  hipError_t enter(hipStream_t s) {
-    if (!ev) {
-      hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-      if (e != hipSuccess) return e;
-    }
-    return valid && last != s ? hipStreamWaitEvent(s, ev, 0) : hipSuccess;
-  }
-  hipError_t leave(hipStream_t s) {
-    last = s;
-    valid = true;
-    return hipEventRecord(ev, s);
-  }
-};
-
-int device_ok(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return fail(FDNN_E_DEVICE, "no HIP device available: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(FDNN_E_ARG, "device index out of range");
-  return FDNN_OK;
-}
-
-}  // namespace
 
 struct fdnn_float_model {
   fl::FloatHostModel hm;

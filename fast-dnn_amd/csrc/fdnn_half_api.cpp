@@ -1,0 +1,329 @@
+// fdnn_half_api.cpp -- C-ABI of the half-precision net (include/fdnn.h, last section; contract: fdnn_half.hpp): the model
+// object, the chunk loop over fdnn_half.hip's launches, the host ends of the per-layer debug call.
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <mutex>
+
+#include "fdnn_half.hpp"
+#include "fdnn_internal.hpp"
+#include "fdnn_stream_order.hpp"
+
+using fdnn::DevBuf;
+using fdnn::device_ok;
+using fdnn::DeviceGuard;
+using fdnn::fail;
+namespace hf = fdnn::hf;
+
+struct fdnn_half_model {
+  hf::HalfHostModel hm;
+  hf::Shape shape;
+  int device = 0;
+  int chunk = 0;  // fdnn_debug_half_set_chunk (0 = default)
+  std::mutex mu;
+  fdnn::StreamOrder order;
+  DevBuf<uint8_t> d_blob;
+  DevBuf<uint16_t> d_xs, d_act[2];  // hf::counts: f16 [cap][k0_pad], [cap][act_ld]
+  DevBuf<float> d_partial;
+  DevBuf<float> d_x, d_out;         // the host entry points' copies: [n][in_dim], [n][O]
+  DevBuf<uint16_t> d_in, d_dbg;     // fdnn_debug_half_layer: f16 [n][K_pad], [n][ldo]
+  DevBuf<float> d_lin, d_prob;      // ... z [n][rows], and the last layer's rows [n][O]
+  const uint16_t *w(int j) const { return reinterpret_cast<const uint16_t *>(d_blob.p + hm.layers[size_t(j)].off_w); }
+  const float *bias(int j) const { return reinterpret_cast<const float *>(d_blob.p + hm.layers[size_t(j)].off_bias); }
+  const float *shift() const { return reinterpret_cast<const float *>(d_blob.p + hm.off_shift); }
+  const float *scale() const { return reinterpret_cast<const float *>(d_blob.p + hm.off_scale); }
+  int n_layers() const { return int(hm.layers.size()); }
+};
+
+namespace {
+
+int reserve_call(fdnn_half_model *m, int n) {
+  const hf::Counts c = hf::counts(m->shape, n, hf::chunk_rows(m->chunk));
+  HIP_TRY(m->d_xs.reserve(c.xs));
+  HIP_TRY(m->d_act[0].reserve(c.act));
+  HIP_TRY(m->d_act[1].reserve(c.act));
+  HIP_TRY(m->d_partial.reserve(c.partial));
+  return FDNN_OK;
+}
+
+// One layer over m frames of one chunk.  A hidden layer writes halves to act (rows ldo apart); the last one e and the
+// partials to probs [m][rows], then the scale pass.
+void run_layer(fdnn_half_model *hm, int j, const uint16_t *in, int lda, int m, int cap, uint16_t *act, int ldo, float *probs, float *tap,
+               hipStream_t s) {
+  const hf::LayerDesc &d = hm->hm.layers[size_t(j)];
+  const bool last = j + 1 == hm->n_layers();
+  hf::GemmParams p{};
+  p.a = in;
+  p.w = hm->w(j);
+  p.bias = hm->bias(j);
+  p.act = last ? nullptr : act;
+  p.e = last ? probs : nullptr;
+  p.tap = tap;
+  p.partial = last ? hm->d_partial.p : nullptr;
+  p.n = m;
+  p.rows = d.rows;
+  p.rows_pad = d.rows_pad;
+  p.K_pad = d.K_pad;
+  p.lda = lda;
+  p.ldo = last ? d.rows : ldo;
+  p.partial_ld = cap;
+  hf::launch_hgemm(p, last ? hf::kExp : hf::kSigmoid, s);
+  if (last) fdnn::launch_normalize(probs, probs, hm->d_partial, m, cap, d.rows, d.rows_pad / hf::kPartialNodes, s);
+}
+
+// The whole net on device rows d_x [n][in_dim] -> d_out [n][O], chunk by chunk.
+int run_net(fdnn_half_model *hm, const float *d_x, int n, float *d_out, hipStream_t s) {
+  if (int rc = reserve_call(hm, n)) return rc;
+  const int chunk = hf::chunk_rows(hm->chunk), cap = std::min(n, chunk), L = hm->n_layers();
+  const int D = hm->hm.in_dim, O = hm->hm.out_dim();
+  for (int i = 0; i < hf::n_chunks(n, chunk); ++i) {
+    int first, m;
+    hf::chunk_range(n, chunk, i, &first, &m);
+    hf::launch_half_input_step(d_x + size_t(first) * D, hm->shift(), hm->scale(), hm->d_xs, nullptr, m, D, hm->shape.k0_pad, s);
+    const uint16_t *in = hm->d_xs;
+    int lda = hm->shape.k0_pad;
+    for (int j = 0; j < L; ++j) {
+      const bool last = j + 1 == L;
+      const int ldo = last ? O : hm->hm.layers[size_t(j) + 1].K_pad;
+      run_layer(hm, j, in, lda, m, cap, hm->d_act[j & 1].p, ldo, last ? d_out + size_t(first) * O : nullptr, nullptr, s);
+      in = hm->d_act[j & 1].p;
+      lda = ldo;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return FDNN_OK;
+}
+
+// fdnn_debug_half_layer and its timing twin: a hidden layer's output row length, the caller's fp32 rows [n][K] rounded to
+// halves into d_in [n][K_pad] (pad columns +0, as every activation buffer has them), and the layer over them chunk by chunk.
+int layer_ldo(const fdnn_half_model *hm, int j) { return int(hf::align_up(size_t(hm->hm.layers[size_t(j)].rows), hf::kKStep)); }
+
+int layer_upload(fdnn_half_model *hm, int j, const float *in, int n, bool tap) {
+  const hf::LayerDesc &d = hm->hm.layers[size_t(j)];
+  const bool last = j + 1 == hm->n_layers();
+  if (int rc = reserve_call(hm, n)) return rc;
+  std::vector<uint16_t> padded(size_t(n) * size_t(d.K_pad), 0);
+  for (int f = 0; f < n; ++f)
+    for (int k = 0; k < d.K; ++k) padded[size_t(f) * d.K_pad + k] = hf::half_bits(in[size_t(f) * d.K + k]);
+  HIP_TRY(hm->d_in.reserve(padded.size()));
+  if (tap) HIP_TRY(hm->d_lin.reserve(size_t(n) * d.rows));
+  if (last) HIP_TRY(hm->d_prob.reserve(size_t(n) * d.rows));
+  else HIP_TRY(hm->d_dbg.reserve(size_t(n) * layer_ldo(hm, j)));
+  HIP_TRY(hipMemcpy(hm->d_in, padded.data(), sizeof(uint16_t) * padded.size(), hipMemcpyHostToDevice));
+  return FDNN_OK;
+}
+
+void layer_launch(fdnn_half_model *hm, int j, int n, bool tap) {
+  const hf::LayerDesc &d = hm->hm.layers[size_t(j)];
+  const bool last = j + 1 == hm->n_layers();
+  const int chunk = hf::chunk_rows(hm->chunk), cap = std::min(n, chunk), ldo = layer_ldo(hm, j);
+  for (int i = 0; i < hf::n_chunks(n, chunk); ++i) {
+    int first, m;
+    hf::chunk_range(n, chunk, i, &first, &m);
+    run_layer(hm, j, hm->d_in + size_t(first) * d.K_pad, d.K_pad, m, cap, last ? nullptr : hm->d_dbg + size_t(first) * ldo, ldo,
+              last ? hm->d_prob + size_t(first) * d.rows : nullptr, tap ? hm->d_lin + size_t(first) * d.rows : nullptr, nullptr);
+  }
+}
+
+// Halves [n][ld] on the device -> the caller's fp32 [n][cols], widened on the host (exact).
+int halves_to_host(const uint16_t *d_src, int n, int ld, int cols, float *dst) {
+  std::vector<uint16_t> h(size_t(n) * size_t(ld));
+  HIP_TRY(hipMemcpy(h.data(), d_src, sizeof(uint16_t) * h.size(), hipMemcpyDeviceToHost));  // (the null stream's work first)
+  for (int f = 0; f < n; ++f)
+    for (int k = 0; k < cols; ++k) dst[size_t(f) * cols + k] = hf::half_value(h[size_t(f) * ld + k]);
+  return FDNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdnn_half_model_load_on(const char *path, int device, fdnn_half_model **out) {
+  if (!path || !out) return fail(FDNN_E_ARG, "null argument");
+  *out = nullptr;
+  std::unique_ptr<fdnn_half_model> hm(new fdnn_half_model());
+  std::string msg;
+  if (int rc = fdnn::load_half_host_model(path, &hm->hm, &msg)) return fail(rc, msg);
+  if (int rc = device_ok(device)) return rc;
+  hm->device = device;
+  hm->shape = hf::shape_of(hm->hm);
+  DeviceGuard g(device);
+  if (!g.ok) return fail(FDNN_E_DEVICE, "hipSetDevice failed");
+  HIP_TRY(hm->d_blob.reserve(hm->hm.blob.size()));
+  HIP_TRY(hipMemcpy(hm->d_blob, hm->hm.blob.data(), hm->hm.blob.size(), hipMemcpyHostToDevice));
+  *out = hm.release();
+  return FDNN_OK;
+}
+
+int fdnn_half_model_load(const char *path, fdnn_half_model **out) { return fdnn_half_model_load_on(path, 0, out); }
+
+void fdnn_half_model_free(fdnn_half_model *hm) {
+  if (!hm) return;
+  DeviceGuard g(hm->device);
+  hipDeviceSynchronize();
+  delete hm;
+}
+
+int fdnn_half_model_input_dim(const fdnn_half_model *hm) { return hm ? hm->hm.in_dim : -1; }
+int fdnn_half_model_output_dim(const fdnn_half_model *hm) { return hm ? hm->hm.out_dim() : -1; }
+int fdnn_half_model_layer_count(const fdnn_half_model *hm) { return hm ? hm->n_layers() : -1; }
+int fdnn_half_model_layer_dim(const fdnn_half_model *hm, int index) {
+  return hm && index >= 0 && index < hm->n_layers() ? hm->hm.layers[size_t(index)].rows : -1;
+}
+int fdnn_half_model_device(const fdnn_half_model *hm) { return hm ? hm->device : -1; }
+
+int fdnn_debug_half_set_chunk(fdnn_half_model *hm, int rows) {
+  if (!hm || rows < 0 || rows > fdnn::fl::kMaxChunk)
+    return fail(FDNN_E_ARG, "chunk rows are 0 (default) .. " + std::to_string(fdnn::fl::kMaxChunk));
+  std::lock_guard<std::mutex> lk(hm->mu);
+  hm->chunk = rows;
+  return FDNN_OK;
+}
+
+int fdnn_half_calculate_device(fdnn_half_model *hm, const float *d_x, int n, float *d_out, void *stream) {
+  if (!hm || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (n == 0) return FDNN_OK;
+  if (!d_x || !d_out) return fail(FDNN_E_ARG, "null buffer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(hm->mu);
+  DeviceGuard g(hm->device);
+  HIP_TRY(hm->order.enter(s));
+  if (int rc = run_net(hm, d_x, n, d_out, s)) return rc;
+  HIP_TRY(hm->order.leave(s));
+  return FDNN_OK;
+}
+
+int fdnn_half_calculate(fdnn_half_model *hm, const float *x, int n, int dim, float *out) {
+  if (!hm || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  if (dim != hm->hm.in_dim)
+    return fail(FDNN_E_ARG, "input vector size " + std::to_string(dim) + " must be equal with network input size " + std::to_string(hm->hm.in_dim));
+  if (n == 0) return FDNN_OK;
+  if (!x || !out) return fail(FDNN_E_ARG, "null buffer");
+  std::lock_guard<std::mutex> lk(hm->mu);
+  DeviceGuard g(hm->device);
+  const size_t D = size_t(dim), O = size_t(hm->hm.out_dim());
+  HIP_TRY(hm->order.enter(nullptr));
+  HIP_TRY(hm->d_x.reserve(size_t(n) * D));
+  HIP_TRY(hm->d_out.reserve(size_t(n) * O));
+  HIP_TRY(hipMemcpyAsync(hm->d_x, x, sizeof(float) * size_t(n) * D, hipMemcpyHostToDevice, nullptr));
+  if (int rc = run_net(hm, hm->d_x, n, hm->d_out, nullptr)) return rc;
+  HIP_TRY(hipMemcpyAsync(out, hm->d_out, sizeof(float) * size_t(n) * O, hipMemcpyDeviceToHost, nullptr));
+  HIP_TRY(hm->order.leave(nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return FDNN_OK;
+}
+
+int fdnn_debug_half_layer(fdnn_half_model *hm, int j, const float *in, int n, float *lin, float *act) {
+  if (!hm || n < 0) return fail(FDNN_E_ARG, "bad argument");
+  const int L = hm->n_layers();
+  if (j < -1 || j >= L) return fail(FDNN_E_ARG, "layer index " + std::to_string(j) + " outside -1 .. " + std::to_string(L - 1));
+  if (n == 0) return FDNN_OK;
+  if (!in) return fail(FDNN_E_ARG, "null buffer");
+  std::lock_guard<std::mutex> lk(hm->mu);
+  DeviceGuard g(hm->device);
+  HIP_TRY(hm->order.enter(nullptr));
+  if (j < 0) {
+    const int D = hm->hm.in_dim, ld = hm->shape.k0_pad;
+    HIP_TRY(hm->d_x.reserve(size_t(n) * D));
+    HIP_TRY(hm->d_lin.reserve(size_t(n) * D));
+    HIP_TRY(hm->d_dbg.reserve(size_t(n) * ld));
+    HIP_TRY(hipMemcpyAsync(hm->d_x, in, sizeof(float) * size_t(n) * D, hipMemcpyHostToDevice, nullptr));
+    hf::launch_half_input_step(hm->d_x, hm->shift(), hm->scale(), hm->d_dbg, hm->d_lin, n, D, ld, nullptr);
+    HIP_TRY(hipGetLastError());
+    if (lin) HIP_TRY(hipMemcpyAsync(lin, hm->d_lin, sizeof(float) * size_t(n) * D, hipMemcpyDeviceToHost, nullptr));
+    if (act)
+      if (int rc = halves_to_host(hm->d_dbg, n, ld, D, act)) return rc;
+  } else {
+    const hf::LayerDesc &d = hm->hm.layers[size_t(j)];
+    if (int rc = layer_upload(hm, j, in, n, lin != nullptr)) return rc;
+    layer_launch(hm, j, n, lin != nullptr);
+    HIP_TRY(hipGetLastError());
+    if (lin) HIP_TRY(hipMemcpyAsync(lin, hm->d_lin, sizeof(float) * size_t(n) * d.rows, hipMemcpyDeviceToHost, nullptr));
+    if (act && j + 1 == L) HIP_TRY(hipMemcpyAsync(act, hm->d_prob, sizeof(float) * size_t(n) * d.rows, hipMemcpyDeviceToHost, nullptr));
+    else if (act)
+      if (int rc = halves_to_host(hm->d_dbg, n, layer_ldo(hm, j), d.rows, act)) return rc;
+  }
+  HIP_TRY(hm->order.leave(nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return FDNN_OK;
+}
+
+int fdnn_debug_half_layer_us(fdnn_half_model *hm, int j, const float *in, int n, int reps, double *us) {
+  if (!hm || !in || !us || n < 1 || reps < 1) return fail(FDNN_E_ARG, "bad argument");
+  const int L = hm->n_layers();
+  if (j < 0 || j >= L) return fail(FDNN_E_ARG, "layer index " + std::to_string(j) + " outside 0 .. " + std::to_string(L - 1));
+  std::lock_guard<std::mutex> lk(hm->mu);
+  DeviceGuard g(hm->device);
+  HIP_TRY(hm->order.enter(nullptr));
+  if (int rc = layer_upload(hm, j, in, n, false)) return rc;
+  struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() {
+      if (a) hipEventDestroy(a);
+      if (b) hipEventDestroy(b);
+    }
+  } ev;
+  HIP_TRY(hipEventCreate(&ev.a));
+  HIP_TRY(hipEventCreate(&ev.b));
+  layer_launch(hm, j, n, false);  // warm-up
+  HIP_TRY(hipEventRecord(ev.a, nullptr));
+  for (int r = 0; r < reps; ++r) layer_launch(hm, j, n, false);
+  HIP_TRY(hipEventRecord(ev.b, nullptr));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hm->order.leave(nullptr));
+  HIP_TRY(hipEventSynchronize(ev.b));
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+  *us = 1000.0 * double(ms) / reps;
+  return FDNN_OK;
+}
+
+int fdnn_debug_half_launches(unsigned long long *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  unsigned long long v[hf::kLaunchKinds];
+  hf::launch_counts(v);
+  for (int i = 0; i < hf::kLaunchKinds && i < cap; ++i) out[i] = v[i];
+  return hf::kLaunchKinds;
+}
+
+// ---------------------------------------------------------------- no device: what the host tests read
+int fdnn_debug_half_pack(const char *path, void *blob, size_t cap, long long *desc, int desc_cap) {
+  if (!path) return fail(FDNN_E_ARG, "null argument");
+  hf::HalfHostModel hm;
+  std::string msg;
+  if (int rc = fdnn::load_half_host_model(path, &hm, &msg)) return fail(rc, msg);
+  std::vector<long long> d;
+  for (const hf::LayerDesc &l : hm.layers)
+    for (long long v : {(long long)l.off_w, (long long)l.off_bias, (long long)l.rows, (long long)l.rows_pad, (long long)l.K, (long long)l.K_pad}) d.push_back(v);
+  d.push_back((long long)hm.off_shift);
+  d.push_back((long long)hm.off_scale);
+  d.push_back((long long)hm.blob.size());
+  if (blob && cap >= hm.blob.size()) std::memcpy(blob, hm.blob.data(), hm.blob.size());
+  for (int i = 0; desc && i < desc_cap && i < int(d.size()); ++i) desc[i] = d[size_t(i)];
+  return int(d.size());
+}
+
+int fdnn_debug_half_extents(const int *shape4, int n, int chunk_setting, long long *out7) {
+  if (!shape4 || !out7 || n < 1) return fail(FDNN_E_ARG, "bad argument");
+  const hf::Shape s{shape4[0], shape4[1], shape4[2], shape4[3]};
+  const int chunk = hf::chunk_rows(chunk_setting);
+  const hf::Counts c = hf::counts(s, n, chunk);
+  long long xs = 0, act = 0, partial = 0, covered = 0, grid_ok = 1;
+  for (int i = 0; i < hf::n_chunks(n, chunk); ++i) {
+    int first, m;
+    hf::chunk_range(n, chunk, i, &first, &m);
+    if (first != covered || m < 1 || m > c.cap) grid_ok = 0;
+    covered += m;
+    unsigned gx, gy;
+    hf::gemm_grid(m, s.out_rows_pad, &gx, &gy);
+    if (size_t(gx) * hf::kFrameTile < size_t(m) || size_t(gx - 1) * hf::kFrameTile >= size_t(m) || int(gy) * hf::kNodeTile != s.out_rows_pad) grid_ok = 0;
+    xs = std::max(xs, (long long)hf::rows_extent(m, s.k0_pad, s.k0_pad));
+    act = std::max(act, (long long)hf::rows_extent(m, s.act_ld, s.act_ld));
+    partial = std::max(partial, (long long)hf::partial_extent(m, c.cap, s.out_rows_pad / hf::kPartialNodes));
+  }
+  const long long v[7] = {(long long)c.xs, (long long)c.act, (long long)c.partial, xs, act, partial, covered == n ? grid_ok : 0};
+  std::memcpy(out7, v, sizeof(v));
+  return FDNN_OK;
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 
 #include "fdnn_act.hpp"
 #include "fdnn_float.hpp"
+#include "fdnn_half.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -371,6 +372,15 @@ int load_float_host_model(const std::string &path, fl::FloatHostModel *out, std:
   for (const RawLayer &L : rm.layers) dense.push_back(fl::DenseLayer{L.out_dim, L.in_pad, L.w.data(), L.bias.data()});
   fl::pack(dense, rm.shift.data(), rm.scale.data(), rm.in_dim_file, out);
   return FDNN_OK;
+}
+
+// The half net of the same file (fdnn_half.hpp): every file load_host_model takes, unless a weight rounds to an infinite fp16.
+int load_half_host_model(const std::string &path, hf::HalfHostModel *out, std::string *msg) {
+  RawModel rm;
+  if (int rc = read_raw_model(path, &rm, msg)) return rc;
+  std::vector<fl::DenseLayer> dense;
+  for (const RawLayer &L : rm.layers) dense.push_back(fl::DenseLayer{L.out_dim, L.in_pad, L.w.data(), L.bias.data()});
+  return hf::pack(dense, rm.shift.data(), rm.scale.data(), rm.in_dim_file, out, msg) ? FDNN_OK : FDNN_E_FORMAT;
 }
 
 int adopt_blob(std::vector<uint8_t> &&bytes, HostModel *out, std::string *msg) {

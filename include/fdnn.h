@@ -1462,6 +1462,54 @@ FDNN_API int fdnn_report_add_device(fdnn_report *r, const float *d_ref, const fl
 FDNN_API int fdnn_report_add(fdnn_report *r, const float *ref, const float *q, int n);
 FDNN_API int fdnn_report_read(fdnn_report *r, double threshold, fdnn_accuracy *acc, double *node_sum);
 
+/* ------------------------------------------------------------------ the half-precision net
+ * The middle path between the two nets above: the SAME .bin with its weights rounded once to fp16 and fp16 activations, on
+ * v_mfma_f32_32x32x16_f16 with fp32 sums, fp32 sigmoid and soft-max (fdnn_half.hip).  The contract -- roundings, padding,
+ * subnormal halves, the float64 bound a sum is held to, and why there is no byte-for-byte host restatement of a sum -- is
+ * stated once, in fast-dnn_amd/csrc/fdnn_half.hpp.  Probabilities leave as fp32 [n][output_dim], so every *_rows_device
+ * return form and fdnn_report_add_device take them as they are.
+ *
+ * fdnn_half_model_load / _load_on   the same .bin and the same rejections as fdnn_float_model_load, and FDNN_E_FORMAT,
+ *   naming the layer and the node, when a weight rounds to an infinite fp16.  FDNN_E_DEVICE without a HIP device.
+ * fdnn_half_model_*                 as fdnn_float_model_*.
+ * fdnn_half_calculate               host buffers x [n][dim] -> out [n][output_dim], host-synchronous; n == 0 is a no-op.
+ *   FDNN_E_ARG for a wrong dim or a null buffer.  Exactly the composition of the fdnn_debug_half_layer calls.
+ * fdnn_half_calculate_device        device buffers, enqueued on `stream`, not synchronised.
+ * Calls on one half model are serialised on a mutex inside it and, across streams, ordered behind each other on the device
+ * (the model owns its activation buffers).  A large n goes through in chunks of fdnn_debug_half_set_chunk frames
+ * (0 = default, 4096); a row's bytes depend on the row and the model alone.
+ *
+ * fdnn_debug_half_layer             ONE layer j on a caller's host rows in [n][K_j], fp32, rounded to fp16 by the call: lin
+ *   [n][rows_j] receives the fp32 z, act [n][rows_j] the stored halves widened to fp32 (the probabilities for the last
+ *   layer); either may be NULL.  j == -1 is the input step on in [n][input_dim]: lin = x + shift, act = the halves of
+ *   (x + shift) * scale.  FDNN_E_ARG for a j outside -1 .. layer_count - 1.
+ * fdnn_debug_half_layer_us          measurement only (tools/half_sweep.py): as fdnn_debug_float_layer_us.
+ * fdnn_debug_half_launches          process-wide launch counts since load, returns 5: hgemm sigmoid, exp, sigmoid + tap,
+ *   exp + tap, input step.
+ * fdnn_debug_half_pack              no device: loads `path` as the half net and copies the packed blob to blob[cap] (where it
+ *   fits) and to desc, per layer, off_w, off_bias, rows, rows_pad, K, K_pad, then off_shift, off_scale and the blob's size;
+ *   returns the number of desc entries, or the load's error.
+ * fdnn_debug_half_extents           no device: for shape4 = {k0_pad, act_ld, out_rows, out_rows_pad}, n frames and a chunk
+ *   setting, out7 = the element counts of xs, act, partial that a call reserves, one past the last element its launches
+ *   touch in each, and 1 if the chunks tile [0, n) and every grid covers exactly its chunk. */
+typedef struct fdnn_half_model fdnn_half_model;
+FDNN_API int fdnn_half_model_load(const char *path, fdnn_half_model **out);
+FDNN_API int fdnn_half_model_load_on(const char *path, int device, fdnn_half_model **out);
+FDNN_API void fdnn_half_model_free(fdnn_half_model *hm);
+FDNN_API int fdnn_half_model_input_dim(const fdnn_half_model *hm);
+FDNN_API int fdnn_half_model_output_dim(const fdnn_half_model *hm);
+FDNN_API int fdnn_half_model_layer_count(const fdnn_half_model *hm);
+FDNN_API int fdnn_half_model_layer_dim(const fdnn_half_model *hm, int index);
+FDNN_API int fdnn_half_model_device(const fdnn_half_model *hm);
+FDNN_API int fdnn_half_calculate(fdnn_half_model *hm, const float *x, int n, int dim, float *out);
+FDNN_API int fdnn_half_calculate_device(fdnn_half_model *hm, const float *d_x, int n, float *d_out, void *stream);
+FDNN_API int fdnn_debug_half_layer(fdnn_half_model *hm, int j, const float *in, int n, float *lin, float *act);
+FDNN_API int fdnn_debug_half_layer_us(fdnn_half_model *hm, int j, const float *in, int n, int reps, double *us);
+FDNN_API int fdnn_debug_half_set_chunk(fdnn_half_model *hm, int rows);
+FDNN_API int fdnn_debug_half_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_half_pack(const char *path, void *blob, size_t cap, long long *desc, int desc_cap);
+FDNN_API int fdnn_debug_half_extents(const int *shape4, int n, int chunk_setting, long long *out7);
+
 #ifdef __cplusplus
 }
 #endif

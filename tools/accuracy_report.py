@@ -2,11 +2,12 @@
 """Quantization error of the scorer against the fp32 net (the reference's FuncTest.diff notion:
 per output node, |quantized - float| summed over the frames; nodes above 0.1 get printed there).
 
-    python tools/accuracy_report.py model.bin [features.bin] [--frames N] [--cutoffs 2,3,4] [--device | --host]
+    python tools/accuracy_report.py model.bin [features.bin] [--frames N] [--cutoffs 2,3,4] [--net half] [--device | --host]
 
 --device (the default where a GPU is present): the float forward (api.FloatDnn), the quantized forward and the report
 (api.AccuracyReport) all run on the device, chunk by chunk over the WHOLE feature file (or --frames synthetic frames);
 nothing but the figures comes back.  --cutoffs a,b,c prints one report line per weight cut-off from ONE float pass.
+--net half adds the half-precision net (api.HalfDnn) to the same pass: its line is printed beside the quantized ones.
 --host is the numpy path (convert.float_forward, convert.quantization_report): a few thousand frames per second, so it
 looks at the first --frames frames only (default 1000).  The quantized forward needs the GPU either way.
 """
@@ -41,6 +42,9 @@ def device_report(a, x):
         sys.exit(f"accuracy_report: Input vector size {x.shape[1]} must be equal with network input size {fdnn.inputDimension()}")
     qdnns = [api.QuantizedDnn.loadFromFile(a.model, c) for c in a.cutoffs]
     reps = [api.AccuracyReport(O) for _ in a.cutoffs]
+    if a.net == "half":  # the half net through the same report, against the same float rows
+        qdnns.append(api.HalfDnn.loadFromFile(a.model))
+        reps.append(api.AccuracyReport(O))
     s = torch.cuda.current_stream().cuda_stream
     d_ref = torch.empty((min(CHUNK, len(x)), O), dtype=torch.float32, device="cuda")
     d_q = torch.empty_like(d_ref)
@@ -49,12 +53,12 @@ def device_report(a, x):
         m = d_x.shape[0]
         fdnn.calculateDevice(d_x.data_ptr(), m, d_ref.data_ptr(), s)  # one float pass serves every cut-off
         for dnn, rep in zip(qdnns, reps):
-            dnn.calculate_device(d_x.data_ptr(), m, d_q.data_ptr(), s)
+            (dnn.calculateDevice if isinstance(dnn, api.HalfDnn) else dnn.calculate_device)(d_x.data_ptr(), m, d_q.data_ptr(), s)
             rep.addDevice(d_ref.data_ptr(), d_q.data_ptr(), m, s)
         torch.cuda.synchronize()  # d_x is released below
-    for cutoff, dnn, rep in zip(a.cutoffs, qdnns, reps):
+    for cutoff, dnn, rep in zip(a.cutoffs + [None], qdnns, reps):
         out = rep.read(0.1)
-        print(json.dumps({"cutoff": cutoff, "path": "device", **out}))
+        print(json.dumps({"net": "half", "path": "device", **out} if cutoff is None else {"cutoff": cutoff, "path": "device", **out}))
         rep.delete()
         dnn.delete()
     fdnn.delete()
@@ -78,6 +82,7 @@ def main() -> None:
     ap.add_argument("features", nargs="?")
     ap.add_argument("--frames", type=int, default=None, help="synthetic frames when no feature file is given; with --host, the frames looked at (default 1000)")
     ap.add_argument("--cutoffs", default="3", help="weight cut-offs of fdnn_model_load, comma separated (default 3)")
+    ap.add_argument("--net", choices=("quantized", "half"), default="quantized", help="half: also report the half-precision net (device path)")
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument("--device", action="store_true", help="everything on the device (default where a GPU is present)")
     mode.add_argument("--host", action="store_true", help="the float forward and the report in numpy")

@@ -1,0 +1,169 @@
+"""The half-precision net on the device (fdnn_half.hip), measured -- the method of tools/float_sweep.py:
+  layers   hgemm_kernel alone per layer shape of the bench net (fdnn_debug_half_layer_us; the output layer's figure includes
+           the soft-max scale pass): microseconds, TF/s (2 n K rows FLOP over that time) and the share of the fp16 MFMA peak
+           (v_mfma_f32_32x32x16_f16: 32768 FLOP per 32 cycles and SIMD = 4096 FLOP per clock and CU)
+  forward  fdnn_half_calculate_device beside fdnn_float_calculate_device and fdnn_calculate_device on the same frames:
+           alternated in one process, warm-up, then ROUNDS blocks each; the median block, the spread (max - min) / median
+  trace    per-launch kernel times from a rocprofv3 run of its own:
+               rocprofv3 --kernel-trace --output-format csv -d DIR -o k -- python tools/half_sweep.py --trace-run 10000
+               python tools/half_sweep.py --trace DIR --frames 10000
+           the launches of a pass are matched to the layers by their order behind the input step; TF/s from the shapes.
+
+  python tools/half_sweep.py [--batches 1000,10000] [--out FILE.json]"""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from fast_dnn_amd import api  # noqa: E402
+from fast_dnn_amd import formats as F  # noqa: E402
+
+ROUNDS = 5
+CHUNK = 4096  # the nets' default chunk
+FLOP_PER_CLOCK_CU = 4096.0
+
+
+def stats(v):
+    med = float(np.median(v))
+    return {"median": med, "spread": round((max(v) - min(v)) / med, 3)}
+
+
+def timed(f, reps):
+    import torch
+
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        f()
+    e1.record()
+    e1.synchronize()
+    return 1000.0 * e0.elapsed_time(e1) / reps  # microseconds per call
+
+
+def model_path():
+    return F.ensure_model_file(os.path.join(os.environ.get("TMPDIR", "/tmp"), "fdnn_net_seed1_gauss.bin"), F.NET_TOPOLOGY, seed=1, mode="gauss")
+
+
+def peak_tflops():
+    import torch
+
+    p = torch.cuda.get_device_properties(0)
+    khz = getattr(p, "clock_rate", 2400000)  # (kHz; the MI355X's 2.4 GHz where the binding does not say)
+    return FLOP_PER_CLOCK_CU * p.multi_processor_count * khz * 1e3 / 1e12, p.multi_processor_count, khz / 1e6
+
+
+def trace_run(n):
+    import torch
+
+    hdnn = api.HalfDnn.loadFromFile(model_path())
+    x = torch.from_numpy(F.synth_features(n, hdnn.inputDimension(), seed=500 + n)).cuda()
+    out = torch.empty((n, hdnn.outputDimension()), dtype=torch.float32, device="cuda")
+    for _ in range(8):
+        hdnn.calculateDevice(x.data_ptr(), n, out.data_ptr(), 0)
+    torch.cuda.synchronize()
+    hdnn.delete()
+
+
+def trace_digest(directory, n):
+    files = glob.glob(directory + "/**/*kernel_trace.csv", recursive=True)
+    if not files:
+        sys.exit("half_sweep: no *kernel_trace.csv under " + directory)
+    rows = sorted(csv.DictReader(open(files[0])), key=lambda r: int(r["Start_Timestamp"]))
+    topo = list(F.NET_TOPOLOGY)
+    topo[0] = -(-topo[0] // 4) * 4
+    chunks = [min(CHUNK, n - f) for f in range(0, n, CHUNK)]
+    groups, idx, passes = {}, 0, -1
+    for r in rows:
+        if "input_step" in r["Kernel_Name"]:
+            idx, passes = 0, passes + 1
+        elif "hgemm_kernel" in r["Kernel_Name"]:
+            groups.setdefault((idx, chunks[passes % len(chunks)]), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+            idx += 1
+    print("| layer | frames | K x rows | launches | us mean | min | max | TF/s |\n|---|---|---|---|---|---|---|---|")
+    for (j, m), v in sorted(groups.items()):
+        v = v[len(v) // 2:]  # the first half is warm-up
+        mean = sum(v) / len(v)
+        print(f"| {j} | {m} | {topo[j]} x {topo[j + 1]} | {len(v)} | {mean:.1f} | {min(v):.1f} | {max(v):.1f} | {2.0 * m * topo[j] * topo[j + 1] / mean / 1e6:.0f} |")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--batches", default="1000,10000")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--trace-run", type=int, default=0, help="only run 8 forwards of this many frames (under rocprofv3)")
+    ap.add_argument("--trace", default=None, help="digest the kernel trace under this directory")
+    ap.add_argument("--frames", type=int, default=10000, help="frames of the traced forwards")
+    args = ap.parse_args()
+    if args.trace:
+        return trace_digest(args.trace, args.frames)
+    if args.trace_run:
+        return trace_run(args.trace_run)
+    import torch
+
+    path = model_path()
+    nets = {"float": api.FloatDnn.loadFromFile(path), "half": api.HalfDnn.loadFromFile(path), "quantized": api.QuantizedDnn.loadFromFile(path)}
+    hdnn = nets["half"]
+    D, O, L = hdnn.inputDimension(), hdnn.outputDimension(), hdnn.layerCount()
+    peak, cus, ghz = peak_tflops()
+    print(json.dumps({"what": "peak", "fp16_mfma_tflops": round(peak, 1), "cus": cus, "ghz": ghz}), flush=True)
+    s = torch.cuda.current_stream().cuda_stream
+    shapes = {"layer0": (0, D, hdnn.layerDimension(0)), "hidden": (1, hdnn.layerDimension(0), hdnn.layerDimension(1)),
+              "output": (L - 1, hdnn.layerDimension(L - 2), O)}
+    results = []
+    for n in [int(v) for v in args.batches.split(",")]:
+        rng = np.random.default_rng(n)
+        ins = {k: (F.synth_features(n, D, seed=500 + n) if k == "layer0" else rng.random((n, K), dtype=np.float32)) for k, (_, K, _) in shapes.items()}
+        us = {k: [] for k in shapes}
+        for _ in range(ROUNDS):
+            for k, (j, _, _) in shapes.items():
+                us[k].append(hdnn.layerMicros(j, ins[k], reps=10))
+        for k, (j, K, rows) in shapes.items():
+            st = stats(us[k])
+            tf = 2.0 * n * K * rows / st["median"] / 1e6
+            results.append({"what": "layer", "layer": k, "frames": n, "K": K, "rows": rows, "us": round(st["median"], 1), "spread": st["spread"],
+                            "tflops": round(tf, 1), "of_peak": round(tf / peak, 3)})
+            print(json.dumps(results[-1]), flush=True)
+        x = torch.from_numpy(ins["layer0"]).cuda()
+        outs = {k: torch.empty((n, O), dtype=torch.float32, device="cuda") for k in nets}
+        runs = {"float": lambda: nets["float"].calculateDevice(x.data_ptr(), n, outs["float"].data_ptr(), s),
+                "half": lambda: hdnn.calculateDevice(x.data_ptr(), n, outs["half"].data_ptr(), s),
+                "quantized": lambda: nets["quantized"].calculate_device(x.data_ptr(), n, outs["quantized"].data_ptr(), s)}
+        reps = {"float": 3, "half": 10, "quantized": 20}
+        for f in runs.values():
+            for _ in range(2):
+                f()
+        torch.cuda.synchronize()
+        us = {k: [] for k in runs}
+        for _ in range(ROUNDS):
+            for k, f in runs.items():
+                us[k].append(timed(f, reps[k]))
+        for k in runs:
+            st = stats(us[k])
+            results.append({"what": "forward", "net": k, "frames": n, "us": round(st["median"], 1), "spread": st["spread"],
+                            "frames_per_s": round(n / st["median"] * 1e6)})
+            print(json.dumps(results[-1]), flush=True)
+    print("\n| frames | layer | K x rows | us | TF/s | of peak | spread |\n|---|---|---|---|---|---|---|")
+    for r in results:
+        if r["what"] == "layer":
+            print(f"| {r['frames']} | {r['layer']} | {r['K']} x {r['rows']} | {r['us']} | {r['tflops']} | {r['of_peak']} | {r['spread']} |")
+    print("\n| frames | net | us | frames/s | spread |\n|---|---|---|---|---|")
+    for r in results:
+        if r["what"] == "forward":
+            print(f"| {r['frames']} | {r['net']} | {r['us']} | {r['frames_per_s']} | {r['spread']} |")
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump(results, fh, indent=1)
+    for d in nets.values():
+        d.delete()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
