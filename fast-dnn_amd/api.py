@@ -368,6 +368,9 @@ SIGNATURES = {
     "fdnn_debug_half_layer_us": (C.c_int, [C.c_void_p, C.c_int, _c_f32p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "fdnn_debug_half_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "fdnn_debug_half_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_half_model_set_small": (C.c_int, [C.c_void_p, C.c_int]),
+    "fdnn_debug_half_small_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_half_small_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p]),
     "fdnn_debug_half_pack": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_longlong), C.c_int]),
     "fdnn_debug_half_extents": (C.c_int, [_c_i32p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
 }
@@ -3135,6 +3138,26 @@ def half_launches() -> dict:
     return dict(zip(HALF_LAUNCH_KINDS, (int(v) for v in buf)))
 
 
+HALF_SMALL_LAUNCH_KINDS = ("small.sigmoid", "small.exp", "small.sigmoid.tap", "small.exp.tap")
+
+
+def half_small_launches() -> dict:
+    """Process-wide launch counts of the half net's small-batch kernel since load (``fdnn_debug_half_small_launches``);
+    ``half_launches`` does not count them."""
+    buf = (C.c_ulonglong * len(HALF_SMALL_LAUNCH_KINDS))()
+    if lib().fdnn_debug_half_small_launches(buf, len(HALF_SMALL_LAUNCH_KINDS)) != len(HALF_SMALL_LAUNCH_KINDS):
+        raise RuntimeError("fdnn_debug_half_small_launches")
+    return dict(zip(HALF_SMALL_LAUNCH_KINDS, (int(v) for v in buf)))
+
+
+def half_small_plan(n: int, setting: int, rows_pad: int, act: int) -> tuple:
+    """No device (``fdnn_debug_half_small_plan``): (applies, workgroups, frame tiles) of a layer of rows_pad rows in form act
+    (0 sigmoid, 1 exp) in a call of n frames under ``setSmall(setting)``."""
+    out = (C.c_int32 * 3)()
+    _check(lib().fdnn_debug_half_small_plan(int(n), int(setting), int(rows_pad), int(act), out))
+    return bool(out[0]), int(out[1]), int(out[2])
+
+
 def half_pack(dnnFile: str) -> dict:
     """The half net's packed blob of a .bin, no device (``fdnn_debug_half_pack``) -> blob (uint8), layers (dicts of off_w,
     off_bias, rows, rows_pad, K, K_pad), off_shift, off_scale."""
@@ -3213,6 +3236,11 @@ class HalfDnn:
     def setChunk(self, rows: int) -> None:
         """Frames per internal chunk (``fdnn_debug_half_set_chunk``; 0 = default).  Results never depend on it."""
         _check(lib().fdnn_debug_half_set_chunk(self.nativeHandle, int(rows)))
+
+    def setSmall(self, max_frames: int) -> None:
+        """Calls of 1 .. max_frames frames (at most 128; 0 = off, the default) take the small-batch kernel
+        (``fdnn_half_model_set_small``).  Results never depend on it: the kernel gives the tiled kernel's bytes."""
+        _check(lib().fdnn_half_model_set_small(self.nativeHandle, int(max_frames)))
 
     def layer(self, j: int, input):
         """ONE layer on the caller's rows, rounded to fp16 by the call (``fdnn_debug_half_layer``) -> (z fp32, the stored halves

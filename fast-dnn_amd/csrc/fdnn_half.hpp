@@ -217,5 +217,24 @@ void launch_half_input_step(const float *x, const float *shift, const float *sca
 constexpr int kLaunchKinds = 5;
 void launch_counts(unsigned long long out[kLaunchKinds]);
 
+// ---------------------------------------------------------------- the small-batch kernel (fdnn_half_small.hip)
+// A call of 1 .. kSmallMaxFrames frames may take hsmall_kernel instead of hgemm_kernel: one workgroup per node tile and
+// all the call's frames, the weights streamed through a deep LDS ring.  THE CONTRACT above holds unchanged: the same
+// instruction, operand roles, k order and epilogue, so a row has the bytes hgemm_kernel gives it.
+constexpr int kSmallMaxFrames = 128;
+#ifndef FDNN_HSMALL_HIDDEN_TILES
+#define FDNN_HSMALL_HIDDEN_TILES 1  // (a build switch for the measurement of section 33 only)
+#endif
+constexpr int kSmallHiddenTiles = FDNN_HSMALL_HIDDEN_TILES;  // 32-node tiles per hidden workgroup; the output form has 2: a 64-node partial
+// The rule.  n is the CALL's frame count, setting the model's (0 = off): every chunk of a small call is small.
+inline bool small_applies(int n, int setting) { return n >= 1 && n <= setting && setting <= kSmallMaxFrames; }
+inline int small_frame_tiles(int m) { return (m + 31) / 32; }
+// Workgroups of hsmall_kernel over a layer: one per node tile, whatever the frame count.
+inline unsigned small_grid(int rows_pad, Act act) { return unsigned(rows_pad / (32 * (act == kExp ? 2 : kSmallHiddenTiles))); }
+void launch_hsmall(const GemmParams &p, Act act, ihipStream_t *s);
+// small sigmoid, exp, sigmoid + tap, exp + tap
+constexpr int kSmallLaunchKinds = 4;
+void small_launch_counts(unsigned long long out[kSmallLaunchKinds]);
+
 }  // namespace hf
 }  // namespace fdnn

@@ -20,6 +20,7 @@ struct fdnn_half_model {
   hf::Shape shape;
   int device = 0;
   int chunk = 0;  // fdnn_debug_half_set_chunk (0 = default)
+  int small = 0;  // fdnn_half_model_set_small: calls of 1 .. small frames take hsmall_kernel (0 = off)
   std::mutex mu;
   fdnn::StreamOrder order;
   DevBuf<uint8_t> d_blob;
@@ -46,10 +47,11 @@ int reserve_call(fdnn_half_model *m, int n) {
   return FDNN_OK;
 }
 
-// One layer over m frames of one chunk.  A hidden layer writes halves to act (rows ldo apart); the last one e and the
-// partials to probs [m][rows], then the scale pass.
-void run_layer(fdnn_half_model *hm, int j, const uint16_t *in, int lda, int m, int cap, uint16_t *act, int ldo, float *probs, float *tap,
-               hipStream_t s) {
+// One layer over m frames of one chunk of a call of n frames.  A hidden layer writes halves to act (rows ldo apart); the
+// last one e and the partials to probs [m][rows], then the scale pass.  The one place that picks the GEMM's launcher:
+// hf::small_applies on the CALL's n, so every chunk of a small call is small (m <= n <= kSmallMaxFrames).
+void run_layer(fdnn_half_model *hm, int j, const uint16_t *in, int lda, int m, int n, int cap, uint16_t *act, int ldo, float *probs,
+               float *tap, hipStream_t s) {
   const hf::LayerDesc &d = hm->hm.layers[size_t(j)];
   const bool last = j + 1 == hm->n_layers();
   hf::GemmParams p{};
@@ -67,7 +69,8 @@ void run_layer(fdnn_half_model *hm, int j, const uint16_t *in, int lda, int m, i
   p.lda = lda;
   p.ldo = last ? d.rows : ldo;
   p.partial_ld = cap;
-  hf::launch_hgemm(p, last ? hf::kExp : hf::kSigmoid, s);
+  if (hf::small_applies(n, hm->small)) hf::launch_hsmall(p, last ? hf::kExp : hf::kSigmoid, s);
+  else hf::launch_hgemm(p, last ? hf::kExp : hf::kSigmoid, s);
   if (last) fdnn::launch_normalize(probs, probs, hm->d_partial, m, cap, d.rows, d.rows_pad / hf::kPartialNodes, s);
 }
 
@@ -85,7 +88,7 @@ int run_net(fdnn_half_model *hm, const float *d_x, int n, float *d_out, hipStrea
     for (int j = 0; j < L; ++j) {
       const bool last = j + 1 == L;
       const int ldo = last ? O : hm->hm.layers[size_t(j) + 1].K_pad;
-      run_layer(hm, j, in, lda, m, cap, hm->d_act[j & 1].p, ldo, last ? d_out + size_t(first) * O : nullptr, nullptr, s);
+      run_layer(hm, j, in, lda, m, n, cap, hm->d_act[j & 1].p, ldo, last ? d_out + size_t(first) * O : nullptr, nullptr, s);
       in = hm->d_act[j & 1].p;
       lda = ldo;
     }
@@ -120,7 +123,7 @@ void layer_launch(fdnn_half_model *hm, int j, int n, bool tap) {
   for (int i = 0; i < hf::n_chunks(n, chunk); ++i) {
     int first, m;
     hf::chunk_range(n, chunk, i, &first, &m);
-    run_layer(hm, j, hm->d_in + size_t(first) * d.K_pad, d.K_pad, m, cap, last ? nullptr : hm->d_dbg + size_t(first) * ldo, ldo,
+    run_layer(hm, j, hm->d_in + size_t(first) * d.K_pad, d.K_pad, m, n, cap, last ? nullptr : hm->d_dbg + size_t(first) * ldo, ldo,
               last ? hm->d_prob + size_t(first) * d.rows : nullptr, tap ? hm->d_lin + size_t(first) * d.rows : nullptr, nullptr);
   }
 }
@@ -177,6 +180,14 @@ int fdnn_debug_half_set_chunk(fdnn_half_model *hm, int rows) {
     return fail(FDNN_E_ARG, "chunk rows are 0 (default) .. " + std::to_string(fdnn::fl::kMaxChunk));
   std::lock_guard<std::mutex> lk(hm->mu);
   hm->chunk = rows;
+  return FDNN_OK;
+}
+
+int fdnn_half_model_set_small(fdnn_half_model *hm, int max_frames) {
+  if (!hm || max_frames < 0 || max_frames > hf::kSmallMaxFrames)
+    return fail(FDNN_E_ARG, "small-batch frames are 0 (off) .. " + std::to_string(hf::kSmallMaxFrames));
+  std::lock_guard<std::mutex> lk(hm->mu);
+  hm->small = max_frames;
   return FDNN_OK;
 }
 
@@ -286,7 +297,24 @@ int fdnn_debug_half_launches(unsigned long long *out, int cap) {
   return hf::kLaunchKinds;
 }
 
+int fdnn_debug_half_small_launches(unsigned long long *out, int cap) {
+  if (!out || cap < 0) return fail(FDNN_E_ARG, "bad argument");
+  unsigned long long v[hf::kSmallLaunchKinds];
+  hf::small_launch_counts(v);
+  for (int i = 0; i < hf::kSmallLaunchKinds && i < cap; ++i) out[i] = v[i];
+  return hf::kSmallLaunchKinds;
+}
+
 // ---------------------------------------------------------------- no device: what the host tests read
+int fdnn_debug_half_small_plan(int n, int setting, int rows_pad, int act, int *out3) {
+  if (!out3 || rows_pad < 1 || rows_pad % hf::kPartialNodes || (act != hf::kSigmoid && act != hf::kExp)) return fail(FDNN_E_ARG, "bad argument");
+  const bool applies = hf::small_applies(n, setting);
+  out3[0] = applies ? 1 : 0;
+  out3[1] = applies ? int(hf::small_grid(rows_pad, hf::Act(act))) : 0;
+  out3[2] = applies ? hf::small_frame_tiles(n) : 0;
+  return FDNN_OK;
+}
+
 int fdnn_debug_half_pack(const char *path, void *blob, size_t cap, long long *desc, int desc_cap) {
   if (!path) return fail(FDNN_E_ARG, "null argument");
   hf::HalfHostModel hm;

@@ -1486,6 +1486,16 @@ FDNN_API int fdnn_report_read(fdnn_report *r, double threshold, fdnn_accuracy *a
  * fdnn_debug_half_layer_us          measurement only (tools/half_sweep.py): as fdnn_debug_float_layer_us.
  * fdnn_debug_half_launches          process-wide launch counts since load, returns 5: hgemm sigmoid, exp, sigmoid + tap,
  *   exp + tap, input step.
+ * fdnn_half_model_set_small        opt-in, off by default: a call of 1 .. max_frames frames (max_frames 1 .. 128; 0 = off) runs its
+ *   layers on the small-batch kernel (csrc/fdnn_half_small.hip): one workgroup per node tile and all the call's frames, the
+ *   weights streamed through a deep LDS ring.  The contract of csrc/fdnn_half.hpp holds unchanged -- "a row's bytes are a
+ *   function of the row and the model alone" -- so every entry point returns the bytes it returns with the setting off.  The rule
+ *   looks at the CALL's n: every chunk of such a call is small.  FDNN_E_ARG outside 0 .. 128, the model unchanged.
+ * fdnn_debug_half_small_launches    process-wide launch counts of that kernel since load, returns 4: small sigmoid, exp,
+ *   sigmoid + tap, exp + tap.  fdnn_debug_half_launches does not count them.
+ * fdnn_debug_half_small_plan        no device: out3 = whether a call of n frames under `setting` is small, and if so the
+ *   workgroups of a layer of rows_pad rows (a multiple of 64) in form act (0 sigmoid, 1 exp) and the call's frame tiles of 32;
+ *   0, 0, 0 where it is not.
  * fdnn_debug_half_pack              no device: loads `path` as the half net and copies the packed blob to blob[cap] (where it
  *   fits) and to desc, per layer, off_w, off_bias, rows, rows_pad, K, K_pad, then off_shift, off_scale and the blob's size;
  *   returns the number of desc entries, or the load's error.
@@ -1507,6 +1517,9 @@ FDNN_API int fdnn_debug_half_layer(fdnn_half_model *hm, int j, const float *in, 
 FDNN_API int fdnn_debug_half_layer_us(fdnn_half_model *hm, int j, const float *in, int n, int reps, double *us);
 FDNN_API int fdnn_debug_half_set_chunk(fdnn_half_model *hm, int rows);
 FDNN_API int fdnn_debug_half_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_half_model_set_small(fdnn_half_model *hm, int max_frames);
+FDNN_API int fdnn_debug_half_small_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_half_small_plan(int n, int setting, int rows_pad, int act, int *out3);
 FDNN_API int fdnn_debug_half_pack(const char *path, void *blob, size_t cap, long long *desc, int desc_cap);
 FDNN_API int fdnn_debug_half_extents(const int *shape4, int n, int chunk_setting, long long *out7);
 

@@ -9,6 +9,12 @@
                python tools/half_sweep.py --trace DIR --frames 10000
            the launches of a pass are matched to the layers by their order behind the input step; TF/s from the shapes.
 
+  small    the small-batch kernel (fdnn_half_small.hip; setSmall) beside the tiled one on the same model at 1 .. 128 frames:
+           per layer shape and for the forward, alternated block by block in one process, with the quantized scorer's forward;
+           beside each layer the time to stream its weights once at the HBM peak (bench.py's roofline figure).  The leg ends
+           with the condition of DESIGN section 33: small no slower than tiled by more than the larger spread, at every n.
+               python tools/half_sweep.py --small [--batches 1,10,32,100,128]
+
   python tools/half_sweep.py [--batches 1000,10000] [--out FILE.json]"""
 import argparse
 import csv
@@ -28,6 +34,8 @@ from fast_dnn_amd import formats as F  # noqa: E402
 ROUNDS = 5
 CHUNK = 4096  # the nets' default chunk
 FLOP_PER_CLOCK_CU = 4096.0
+HBM_PEAK_GBS = 8000.0  # bench.py's roofline figure
+SMALL_BATCHES = "1,10,32,100,128"
 
 
 def stats(v):
@@ -93,9 +101,78 @@ def trace_digest(directory, n):
         print(f"| {j} | {m} | {topo[j]} x {topo[j + 1]} | {len(v)} | {mean:.1f} | {min(v):.1f} | {max(v):.1f} | {2.0 * m * topo[j] * topo[j + 1] / mean / 1e6:.0f} |")
 
 
+def small_leg(batches, out):
+    import torch
+
+    path = model_path()
+    hdnn, qdnn = api.HalfDnn.loadFromFile(path), api.QuantizedDnn.loadFromFile(path)
+    D, O, L = hdnn.inputDimension(), hdnn.outputDimension(), hdnn.layerCount()
+    s = torch.cuda.current_stream().cuda_stream
+    shapes = {"layer0": (0, D, hdnn.layerDimension(0)), "hidden": (1, hdnn.layerDimension(0), hdnn.layerDimension(1)),
+              "output": (L - 1, hdnn.layerDimension(L - 2), O)}
+    forms = {"tiled": 0, "small": 128}
+    results, ok = [], True
+    for n in batches:
+        rng = np.random.default_rng(n)
+        ins = {k: (F.synth_features(n, D, seed=500 + n) if k == "layer0" else rng.random((n, K), dtype=np.float32)) for k, (_, K, _) in shapes.items()}
+        us = {(k, f): [] for k in shapes for f in forms}
+        for _ in range(ROUNDS):
+            for k, (j, _, _) in shapes.items():
+                for f, setting in forms.items():
+                    hdnn.setSmall(setting)
+                    us[k, f].append(hdnn.layerMicros(j, ins[k], reps=20))
+        for k, (j, K, rows) in shapes.items():
+            st = {f: stats(us[k, f]) for f in forms}
+            results.append({"what": "layer", "layer": k, "frames": n, "K": K, "rows": rows, "tiled_us": round(st["tiled"]["median"], 1),
+                            "tiled_spread": st["tiled"]["spread"], "small_us": round(st["small"]["median"], 1), "small_spread": st["small"]["spread"],
+                            "weights_at_hbm_peak_us": round(2.0 * K * rows / HBM_PEAK_GBS / 1e3, 2)})
+            print(json.dumps(results[-1]), flush=True)
+        x = torch.from_numpy(ins["layer0"]).cuda()
+        outs = {k: torch.empty((n, O), dtype=torch.float32, device="cuda") for k in ("tiled", "small", "quantized")}
+
+        def half(form):
+            hdnn.setSmall(forms[form])
+            hdnn.calculateDevice(x.data_ptr(), n, outs[form].data_ptr(), s)
+
+        runs = {"tiled": lambda: half("tiled"), "small": lambda: half("small"),
+                "quantized": lambda: qdnn.calculate_device(x.data_ptr(), n, outs["quantized"].data_ptr(), s)}
+        for f in runs.values():
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        if not torch.equal(outs["tiled"].view(torch.int32), outs["small"].view(torch.int32)):
+            sys.exit(f"half_sweep: the small form's bytes differ from the tiled form's at n = {n}")
+        us = {k: [] for k in runs}
+        for _ in range(ROUNDS):
+            for k, f in runs.items():
+                us[k].append(timed(f, 20))
+        st = {k: stats(us[k]) for k in runs}
+        margin = max(st["tiled"]["spread"], st["small"]["spread"])
+        holds = st["small"]["median"] <= st["tiled"]["median"] * (1.0 + margin)
+        ok = ok and holds
+        results.append({"what": "forward", "frames": n, **{k + "_us": round(st[k]["median"], 1) for k in runs}, **{k + "_spread": st[k]["spread"] for k in runs},
+                        "small_no_slower": holds})
+        print(json.dumps(results[-1]), flush=True)
+    print("\n| frames | layer | K x rows | tiled us | spread | small us | spread | weights at HBM peak us |\n|---|---|---|---|---|---|---|---|")
+    for r in results:
+        if r["what"] == "layer":
+            print(f"| {r['frames']} | {r['layer']} | {r['K']} x {r['rows']} | {r['tiled_us']} | {r['tiled_spread']} | {r['small_us']} | {r['small_spread']} | {r['weights_at_hbm_peak_us']} |")
+    print("\n| frames | tiled us | spread | small us | spread | quantized us | spread | small no slower |\n|---|---|---|---|---|---|---|---|")
+    for r in results:
+        if r["what"] == "forward":
+            print(f"| {r['frames']} | {r['tiled_us']} | {r['tiled_spread']} | {r['small_us']} | {r['small_spread']} | {r['quantized_us']} | {r['quantized_spread']} | {r['small_no_slower']} |")
+    if out:
+        with open(out, "w") as fh:
+            json.dump(results, fh, indent=1)
+    hdnn.delete()
+    qdnn.delete()
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--batches", default="1000,10000")
+    ap.add_argument("--batches", default=None, help="frame counts (default 1000,10000; with --small " + SMALL_BATCHES + ")")
+    ap.add_argument("--small", action="store_true", help="the small-batch kernel beside the tiled one at 1 .. 128 frames")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-run", type=int, default=0, help="only run 8 forwards of this many frames (under rocprofv3)")
     ap.add_argument("--trace", default=None, help="digest the kernel trace under this directory")
@@ -105,6 +182,8 @@ def main():
         return trace_digest(args.trace, args.frames)
     if args.trace_run:
         return trace_run(args.trace_run)
+    if args.small:
+        return small_leg([int(v) for v in (args.batches or SMALL_BATCHES).split(",")], args.out)
     import torch
 
     path = model_path()
@@ -117,7 +196,7 @@ def main():
     shapes = {"layer0": (0, D, hdnn.layerDimension(0)), "hidden": (1, hdnn.layerDimension(0), hdnn.layerDimension(1)),
               "output": (L - 1, hdnn.layerDimension(L - 2), O)}
     results = []
-    for n in [int(v) for v in args.batches.split(",")]:
+    for n in [int(v) for v in (args.batches or "1000,10000").split(",")]:
         rng = np.random.default_rng(n)
         ins = {k: (F.synth_features(n, D, seed=500 + n) if k == "layer0" else rng.random((n, K), dtype=np.float32)) for k, (_, K, _) in shapes.items()}
         us = {k: [] for k in shapes}
