@@ -373,6 +373,14 @@ SIGNATURES = {
     "fdnn_debug_half_small_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p]),
     "fdnn_debug_half_pack": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_longlong), C.c_int]),
     "fdnn_debug_half_extents": (C.c_int, [_c_i32p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "fdnn_half_calculate_lazy_sets": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_f32p, _c_f32p]),
+    "fdnn_half_calculate_lazy_set": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p]),
+    "fdnn_half_calculate_lazy_sets_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_i32p, _c_i32p, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]),
+    "fdnn_debug_half_set_layer": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, _c_f32p]),
+    "fdnn_debug_half_set_layer_us": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, _c_i32p, _c_i32p, C.c_int, _c_i32p, C.c_int, C.POINTER(C.c_double)]),
+    "fdnn_debug_half_set_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    "fdnn_debug_half_set_plan": (C.c_int, [_c_i32p, _c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p]),
 }
 
 JNI_SYMBOLS = [
@@ -3158,6 +3166,30 @@ def half_small_plan(n: int, setting: int, rows_pad: int, act: int) -> tuple:
     return bool(out[0]), int(out[1]), int(out[2])
 
 
+HALF_SET_LAUNCH_KINDS = ("set.score", "set.score.tap", "set.gather")
+
+
+def half_set_launches() -> dict:
+    """Process-wide launch counts of the half net's set kernels since load (``fdnn_debug_half_set_launches``): the
+    resident-tile kernel without and with the logit tap, and the gather of the fallback."""
+    buf = (C.c_ulonglong * len(HALF_SET_LAUNCH_KINDS))()
+    if lib().fdnn_debug_half_set_launches(buf, len(HALF_SET_LAUNCH_KINDS)) != len(HALF_SET_LAUNCH_KINDS):
+        raise RuntimeError("fdnn_debug_half_set_launches")
+    return dict(zip(HALF_SET_LAUNCH_KINDS, (int(v) for v in buf)))
+
+
+def half_set_plan(segRows, setPtr, K_pad: int, rows_pad: int = 8064, n_cu: int = 256) -> tuple:
+    """No device (``fdnn_debug_half_set_plan``): (applies, launches, workgroups, frame tiles per workgroup) of the half net's
+    set step on these tables for an output layer of K_pad x rows_pad."""
+    sr = np.ascontiguousarray(segRows, dtype=np.int32)
+    sp = np.ascontiguousarray(setPtr, dtype=np.int32)
+    if sr.ndim != 1 or sp.ndim != 1 or sr.size != sp.size or sr.size < 1:
+        raise ValueError("segRows and setPtr must be [segments + 1]")
+    out = (C.c_int32 * 4)()
+    _check(lib().fdnn_debug_half_set_plan(sr.ctypes.data_as(_c_i32p), sp.ctypes.data_as(_c_i32p), sr.size - 1, int(K_pad), int(rows_pad), int(n_cu), out))
+    return bool(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+
 def half_pack(dnnFile: str) -> dict:
     """The half net's packed blob of a .bin, no device (``fdnn_debug_half_pack``) -> blob (uint8), layers (dicts of off_w,
     off_bias, rows, rows_pad, K, K_pad), off_shift, off_scale."""
@@ -3255,6 +3287,67 @@ class HalfDnn:
         _check(lib().fdnn_debug_half_layer(self.nativeHandle, int(j), x.ctypes.data_as(_c_f32p), x.shape[0], lin.ctypes.data_as(_c_f32p),
                                            act.ctypes.data_as(_c_f32p)))
         return lin, act
+
+    def _frames(self, input):
+        x = _f32(input)
+        if x.shape[0] and (x.ndim != 2 or x.shape[1] != self.inputDimension()):
+            raise ValueError(f"input vector size {x.shape[-1]} must be equal with network input size {self.inputDimension()}")
+        return x, x.shape[0], x.shape[1] if x.shape[0] else self.inputDimension()
+
+    def calculateLazySets(self, input, segRows, setPtr, nodes):
+        """The output layer on one node set per segment of the frames (``fdnn_half_calculate_lazy_sets``; segRows must cover
+        [0, frames); contract: csrc/fdnn_half_set.hpp) -> (probs flat: the ragged [rows_s][len_s] blocks, inactive [frames])."""
+        x, n, dim = self._frames(input)
+        sr, sp, nd, n_segs, _, nnz = _sets(segRows, setPtr, nodes)
+        probs = np.empty(nnz, dtype=np.float32)
+        inactive = np.empty(n, dtype=np.float32)
+        _check(lib().fdnn_half_calculate_lazy_sets(self.nativeHandle, x.ctypes.data_as(_c_f32p), n, dim, sr.ctypes.data_as(_c_i32p),
+                                                   sp.ctypes.data_as(_c_i32p), n_segs, nd.ctypes.data_as(_c_i32p), probs.ctypes.data_as(_c_f32p),
+                                                   inactive.ctypes.data_as(_c_f32p)))
+        return probs, inactive
+
+    def calculateLazySet(self, input, nodes):
+        """ONE node set for every frame (``fdnn_half_calculate_lazy_set``) -> (probs [frames][len], inactive [frames])."""
+        x, n, dim = self._frames(input)
+        nd = _set(nodes)
+        probs = np.empty((n, nd.size), dtype=np.float32)
+        inactive = np.empty(n, dtype=np.float32)
+        _check(lib().fdnn_half_calculate_lazy_set(self.nativeHandle, x.ctypes.data_as(_c_f32p), n, dim, nd.ctypes.data_as(_c_i32p), nd.size,
+                                                  probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p)))
+        return probs, inactive
+
+    def calculateLazySetsDevice(self, d_x: int, n: int, segRows, setPtr, d_nodes: int, d_probs: int, d_inactive: int, stream: int = 0) -> None:
+        """Device-resident form (``fdnn_half_calculate_lazy_sets_device``): raw device pointers, the two tables on the host;
+        enqueued on ``stream``, not synchronised.  The sets are not validated: a bad node makes its own segment's rows NaN."""
+        sr = np.ascontiguousarray(segRows, dtype=np.int32)
+        sp = np.ascontiguousarray(setPtr, dtype=np.int32)
+        if sr.ndim != 1 or sp.ndim != 1 or sr.size != sp.size or sr.size < 1:
+            raise ValueError("segRows and setPtr must be [segments + 1]")
+        _check(lib().fdnn_half_calculate_lazy_sets_device(self.nativeHandle, C.c_void_p(d_x), int(n), sr.ctypes.data_as(_c_i32p),
+                                                          sp.ctypes.data_as(_c_i32p), sr.size - 1, C.c_void_p(d_nodes), C.c_void_p(d_probs),
+                                                          C.c_void_p(d_inactive), C.c_void_p(stream)))
+
+    def setLayer(self, input, nodes):
+        """The output layer ALONE on the caller's last hidden rows, rounded to fp16 by the call, for one node set
+        (``fdnn_debug_half_set_layer``) -> (z [n][len], probs [n][len], inactive [n])."""
+        x = _f32(input)
+        nd = _set(nodes)
+        z = np.empty((x.shape[0], nd.size), dtype=np.float32)
+        probs = np.empty_like(z)
+        inactive = np.empty(x.shape[0], dtype=np.float32)
+        _check(lib().fdnn_debug_half_set_layer(self.nativeHandle, x.ctypes.data_as(_c_f32p), x.shape[0], nd.ctypes.data_as(_c_i32p), nd.size,
+                                               z.ctypes.data_as(_c_f32p), probs.ctypes.data_as(_c_f32p), inactive.ctypes.data_as(_c_f32p)))
+        return z, probs, inactive
+
+    def setLayerMicros(self, input, segRows, setPtr, nodes, reps: int = 10) -> float:
+        """Device microseconds per run of the set step alone on the caller's last hidden rows (``fdnn_debug_half_set_layer_us``;
+        measurement only)."""
+        x = _f32(input)
+        sr, sp, nd, n_segs, _, _ = _sets(segRows, setPtr, nodes)
+        us = C.c_double()
+        _check(lib().fdnn_debug_half_set_layer_us(self.nativeHandle, x.ctypes.data_as(_c_f32p), x.shape[0], sr.ctypes.data_as(_c_i32p),
+                                                  sp.ctypes.data_as(_c_i32p), n_segs, nd.ctypes.data_as(_c_i32p), int(reps), C.byref(us)))
+        return float(us.value)
 
     def layerMicros(self, j: int, input, reps: int = 10) -> float:
         """Device microseconds per run of layer j on the caller's rows (``fdnn_debug_half_layer_us``; measurement only)."""

@@ -1501,7 +1501,30 @@ FDNN_API int fdnn_report_read(fdnn_report *r, double threshold, fdnn_accuracy *a
  *   returns the number of desc entries, or the load's error.
  * fdnn_debug_half_extents           no device: for shape4 = {k0_pad, act_ld, out_rows, out_rows_pad}, n frames and a chunk
  *   setting, out7 = the element counts of xs, act, partial that a call reserves, one past the last element its launches
- *   touch in each, and 1 if the chunks tile [0, n) and every grid covers exactly its chunk. */
+ *   touch in each, and 1 if the chunks tile [0, n) and every grid covers exactly its chunk.
+ *
+ * Lazy output for per-segment node sets (csrc/fdnn_half_set.hip; the contract is stated once, in csrc/fdnn_half_set.hpp): the
+ * tables of fdnn_calculate_lazy_sets -- seg_rows and set_ptr [n_segs + 1] in HOST memory in every form, sets strictly
+ * ascending inside [0, output_dim), empty segments and sets allowed, probs ragged ([rows_s][len_s] blocks one after the
+ * other), inactive one value per row.  The hidden layers run as in fdnn_half_calculate; the output layer runs on the listed
+ * nodes only, every unlisted node counting exp(0) = 1 in the total.  A row's bytes depend on the row, its set and the model
+ * alone; a listed node's logit has the bytes of the dense form's.  The blocks are device rows like any other: with row_off =
+ * the block's start and row_ld = len_s they feed fdnn_align_rows_device and its siblings unchanged.
+ * fdnn_half_calculate_lazy_sets         host buffers, synchronous; seg_rows must cover [0, n).  FDNN_E_ARG names the first
+ *   malformed segment.
+ * fdnn_half_calculate_lazy_set          one segment: nodes [len] for every row, probs [n][len].
+ * fdnn_half_calculate_lazy_sets_device  device x, nodes, probs and inactive, enqueued on `stream` and ordered on the model like
+ *   fdnn_half_calculate_device.  The tables are checked, the sets are not: a node outside [0, output_dim) makes the rows of
+ *   its own segment NaN and no others.
+ * fdnn_debug_half_set_layer             the output layer alone on a caller's host rows in [n][K], rounded to fp16 by the call
+ *   (the twin of fdnn_debug_half_layer): z [n][len] receives the logits unless NULL, probs [n][len] and inactive [n] the results.
+ * fdnn_debug_half_set_layer_us          measurement only (tools/half_set_sweep.py): device microseconds per run of the set step
+ *   alone -- row pointer, score, finish -- on a caller's host rows and tables, as fdnn_debug_half_layer_us.
+ * fdnn_debug_half_set_launches          process-wide launch counts since load, returns 3: set score, set score + tap, and the
+ *   gather of the fallback (a last hidden width above 2048 runs the dense exp launch and copies the listed entries).
+ * fdnn_debug_half_set_plan              no device: for tables over rows [seg_rows[0], seg_rows[n_segs]), an output layer of
+ *   K_pad x rows_pad and n_cu compute units, out4 = whether the resident-tile kernel applies, the launches (at most 64
+ *   segments each), the workgroups of all of them, and the frame tiles of 32 a workgroup walks. */
 typedef struct fdnn_half_model fdnn_half_model;
 FDNN_API int fdnn_half_model_load(const char *path, fdnn_half_model **out);
 FDNN_API int fdnn_half_model_load_on(const char *path, int device, fdnn_half_model **out);
@@ -1522,6 +1545,18 @@ FDNN_API int fdnn_debug_half_small_launches(unsigned long long *out, int cap);
 FDNN_API int fdnn_debug_half_small_plan(int n, int setting, int rows_pad, int act, int *out3);
 FDNN_API int fdnn_debug_half_pack(const char *path, void *blob, size_t cap, long long *desc, int desc_cap);
 FDNN_API int fdnn_debug_half_extents(const int *shape4, int n, int chunk_setting, long long *out7);
+FDNN_API int fdnn_half_calculate_lazy_sets(fdnn_half_model *hm, const float *x, int n, int dim, const int32_t *seg_rows, const int32_t *set_ptr,
+                                           int n_segs, const int32_t *nodes, float *probs, float *inactive);
+FDNN_API int fdnn_half_calculate_lazy_set(fdnn_half_model *hm, const float *x, int n, int dim, const int32_t *nodes, int len, float *probs,
+                                          float *inactive);
+FDNN_API int fdnn_half_calculate_lazy_sets_device(fdnn_half_model *hm, const float *d_x, int n, const int32_t *seg_rows, const int32_t *set_ptr,
+                                                  int n_segs, const int32_t *d_nodes, float *d_probs, float *d_inactive, void *stream);
+FDNN_API int fdnn_debug_half_set_layer(fdnn_half_model *hm, const float *in, int n, const int32_t *nodes, int len, float *z, float *probs,
+                                       float *inactive);
+FDNN_API int fdnn_debug_half_set_layer_us(fdnn_half_model *hm, const float *in, int n, const int32_t *seg_rows, const int32_t *set_ptr, int n_segs,
+                                          const int32_t *nodes, int reps, double *us);
+FDNN_API int fdnn_debug_half_set_launches(unsigned long long *out, int cap);
+FDNN_API int fdnn_debug_half_set_plan(const int32_t *seg_rows, const int32_t *set_ptr, int n_segs, int K_pad, int rows_pad, int n_cu, int *out4);
 
 #ifdef __cplusplus
 }
