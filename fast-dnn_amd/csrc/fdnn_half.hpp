@@ -236,5 +236,26 @@ void launch_hsmall(const GemmParams &p, Act act, ihipStream_t *s);
 constexpr int kSmallLaunchKinds = 4;
 void small_launch_counts(unsigned long long out[kSmallLaunchKinds]);
 
+// ---------------------------------------------------------------- the mid-batch kernel (fdnn_half_mid.hip)
+// A call of up to kMidMaxFrames frames that is not small may take hmid_kernel instead of hgemm_kernel: 64 frames x 64 nodes
+// per workgroup, two workgroups to a CU, the operands requested two stages ahead.  THE CONTRACT above holds unchanged: a row
+// has the bytes hgemm_kernel gives it.
+constexpr int kMidMaxFrames = 4096;  // the default chunk: such a call is one chunk unless the chunk was set smaller
+constexpr int kMidFrameTile = 64;    // frames per workgroup
+constexpr int kMidNodeTile = 64;     // nodes per workgroup: one soft-max partial
+// The rule.  n is the CALL's frame count, the settings the model's (0 = off).  The small kernel keeps its own range.
+inline bool mid_applies(int n, int small_setting, int mid_setting) {
+  return n >= 1 && n <= mid_setting && mid_setting <= kMidMaxFrames && !small_applies(n, small_setting);
+}
+// Grid of hmid_kernel over m frames: (frame tiles, node tiles).  Frames past m are neither read from memory nor written.
+inline void mid_grid(int m, int rows_pad, unsigned *gx, unsigned *gy) {
+  *gx = unsigned((m + kMidFrameTile - 1) / kMidFrameTile);
+  *gy = unsigned(rows_pad / kMidNodeTile);
+}
+void launch_hmid(const GemmParams &p, Act act, ihipStream_t *s);
+// mid sigmoid, exp, sigmoid + tap, exp + tap
+constexpr int kMidLaunchKinds = 4;
+void mid_launch_counts(unsigned long long out[kMidLaunchKinds]);
+
 }  // namespace hf
 }  // namespace fdnn

@@ -1496,6 +1496,17 @@ FDNN_API int fdnn_report_read(fdnn_report *r, double threshold, fdnn_accuracy *a
  * fdnn_debug_half_small_plan        no device: out3 = whether a call of n frames under `setting` is small, and if so the
  *   workgroups of a layer of rows_pad rows (a multiple of 64) in form act (0 sigmoid, 1 exp) and the call's frame tiles of 32;
  *   0, 0, 0 where it is not.
+ * fdnn_half_model_set_mid          opt-in, off by default: a call of up to max_frames frames (max_frames 1 .. 4096; 0 = off) that
+ *   is not small runs its layers on the mid-batch kernel (csrc/fdnn_half_mid.hip): 64 frames x 64 nodes per workgroup, two
+ *   workgroups to a CU, the operands requested two stages ahead through an LDS ring.  The small kernel keeps precedence inside
+ *   its own range.  The contract holds unchanged, so every entry point -- the lazy set calls' hidden layers and their dense
+ *   fallback included -- returns the bytes it returns with the setting off.  The rule looks at the CALL's n: every chunk of
+ *   such a call is mid.  FDNN_E_ARG outside 0 .. 4096, the model unchanged.
+ * fdnn_debug_half_mid_launches     process-wide launch counts of that kernel since load into out4: mid sigmoid, exp,
+ *   sigmoid + tap, exp + tap.  The other two counter calls do not count them.
+ * fdnn_debug_half_mid_plan         no device: out3 = whether a call of n frames under the two settings is mid, and if so the
+ *   grid of a layer of rows_pad rows (a multiple of 64) in form act (0 sigmoid, 1 exp): frame tiles of 64, node tiles of
+ *   64; 0, 0, 0 where it is not.
  * fdnn_debug_half_pack              no device: loads `path` as the half net and copies the packed blob to blob[cap] (where it
  *   fits) and to desc, per layer, off_w, off_bias, rows, rows_pad, K, K_pad, then off_shift, off_scale and the blob's size;
  *   returns the number of desc entries, or the load's error.
@@ -1543,6 +1554,9 @@ FDNN_API int fdnn_debug_half_launches(unsigned long long *out, int cap);
 FDNN_API int fdnn_half_model_set_small(fdnn_half_model *hm, int max_frames);
 FDNN_API int fdnn_debug_half_small_launches(unsigned long long *out, int cap);
 FDNN_API int fdnn_debug_half_small_plan(int n, int setting, int rows_pad, int act, int *out3);
+FDNN_API int fdnn_half_model_set_mid(fdnn_half_model *hm, int max_frames);
+FDNN_API int fdnn_debug_half_mid_launches(unsigned long long *out4);
+FDNN_API int fdnn_debug_half_mid_plan(int n, int small_setting, int mid_setting, int rows_pad, int act, int *out3);
 FDNN_API int fdnn_debug_half_pack(const char *path, void *blob, size_t cap, long long *desc, int desc_cap);
 FDNN_API int fdnn_debug_half_extents(const int *shape4, int n, int chunk_setting, long long *out7);
 FDNN_API int fdnn_half_calculate_lazy_sets(fdnn_half_model *hm, const float *x, int n, int dim, const int32_t *seg_rows, const int32_t *set_ptr,

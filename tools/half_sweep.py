@@ -15,6 +15,12 @@
            with the condition of DESIGN section 33: small no slower than tiled by more than the larger spread, at every n.
                python tools/half_sweep.py --small [--batches 1,10,32,100,128]
 
+  mid      the mid-batch kernel (fdnn_half_mid.hip; setMid) beside the tiled one on the same model at 129 .. 4096 frames:
+           first the two forwards' bytes must be equal; then per layer shape (with the share of the fp16 MFMA peak) and for
+           the forward, alternated block by block in one process.  The leg ends with the condition of DESIGN section 35: mid
+           no slower than tiled by more than the larger spread at every n up to 1000; larger n are reported.
+               python tools/half_sweep.py --mid [--batches 129,256,512,1000,2048,4096]
+
   python tools/half_sweep.py [--batches 1000,10000] [--out FILE.json]"""
 import argparse
 import csv
@@ -36,6 +42,7 @@ CHUNK = 4096  # the nets' default chunk
 FLOP_PER_CLOCK_CU = 4096.0
 HBM_PEAK_GBS = 8000.0  # bench.py's roofline figure
 SMALL_BATCHES = "1,10,32,100,128"
+MID_BATCHES = "129,256,512,1000,2048,4096"
 
 
 def stats(v):
@@ -169,10 +176,85 @@ def small_leg(batches, out):
     return 0 if ok else 1
 
 
+def mid_leg(batches, out):
+    import torch
+
+    hdnn = api.HalfDnn.loadFromFile(model_path())
+    D, O, L = hdnn.inputDimension(), hdnn.outputDimension(), hdnn.layerCount()
+    peak, cus, ghz = peak_tflops()
+    print(json.dumps({"what": "peak", "fp16_mfma_tflops": round(peak, 1), "cus": cus, "ghz": ghz}), flush=True)
+    s = torch.cuda.current_stream().cuda_stream
+    shapes = {"layer0": (0, D, hdnn.layerDimension(0)), "hidden": (1, hdnn.layerDimension(0), hdnn.layerDimension(1)),
+              "output": (L - 1, hdnn.layerDimension(L - 2), O)}
+    forms = {"tiled": 0, "mid": 4096}
+    results, ok = [], True
+
+    def holds(st):  # mid no slower than tiled by more than the larger of the two spreads
+        return st["mid"]["median"] <= st["tiled"]["median"] * (1.0 + max(st["tiled"]["spread"], st["mid"]["spread"]))
+
+    for n in batches:
+        rng = np.random.default_rng(n)
+        ins = {k: (F.synth_features(n, D, seed=500 + n) if k == "layer0" else rng.random((n, K), dtype=np.float32)) for k, (_, K, _) in shapes.items()}
+        x = torch.from_numpy(ins["layer0"]).cuda()
+        outs = {f: torch.empty((n, O), dtype=torch.float32, device="cuda") for f in forms}
+
+        def forward(form):
+            hdnn.setMid(forms[form])
+            hdnn.calculateDevice(x.data_ptr(), n, outs[form].data_ptr(), s)
+
+        for f in forms:
+            for _ in range(3):
+                forward(f)
+        torch.cuda.synchronize()
+        if not torch.equal(outs["tiled"].view(torch.int32), outs["mid"].view(torch.int32)):
+            sys.exit(f"half_sweep: the mid form's bytes differ from the tiled form's at n = {n}")
+        us = {(k, f): [] for k in shapes for f in forms}
+        for _ in range(ROUNDS):
+            for k, (j, _, _) in shapes.items():
+                for f, setting in forms.items():
+                    hdnn.setMid(setting)
+                    us[k, f].append(hdnn.layerMicros(j, ins[k], reps=20))
+        for k, (j, K, rows) in shapes.items():
+            st = {f: stats(us[k, f]) for f in forms}
+            good = holds(st)
+            ok = ok and (good or n > 1000)
+            share = {f: round(2.0 * n * K * rows / st[f]["median"] / 1e6 / peak, 3) for f in forms}
+            results.append({"what": "layer", "layer": k, "frames": n, "K": K, "rows": rows, "tiled_us": round(st["tiled"]["median"], 1),
+                            "tiled_spread": st["tiled"]["spread"], "mid_us": round(st["mid"]["median"], 1), "mid_spread": st["mid"]["spread"],
+                            "tiled_of_peak": share["tiled"], "mid_of_peak": share["mid"], "mid_no_slower": good})
+            print(json.dumps(results[-1]), flush=True)
+        fus = {f: [] for f in forms}
+        for _ in range(ROUNDS):
+            for f in forms:
+                fus[f].append(timed(lambda: forward(f), 20))
+        st = {f: stats(fus[f]) for f in forms}
+        good = holds(st)
+        ok = ok and (good or n > 1000)
+        results.append({"what": "forward", "frames": n, **{f + "_us": round(st[f]["median"], 1) for f in forms}, **{f + "_spread": st[f]["spread"] for f in forms},
+                        "mid_frames_per_s": round(n / st["mid"]["median"] * 1e6), "mid_no_slower": good})
+        print(json.dumps(results[-1]), flush=True)
+    print("\n| frames | layer | K x rows | tiled us | spread | of peak | mid us | spread | of peak | mid no slower |\n|---|---|---|---|---|---|---|---|---|---|")
+    for r in results:
+        if r["what"] == "layer":
+            print(f"| {r['frames']} | {r['layer']} | {r['K']} x {r['rows']} | {r['tiled_us']} | {r['tiled_spread']} | {r['tiled_of_peak']} | {r['mid_us']} | {r['mid_spread']} | {r['mid_of_peak']} | {r['mid_no_slower']} |")
+    print("\n| frames | tiled us | spread | mid us | spread | mid frames/s | mid no slower |\n|---|---|---|---|---|---|---|")
+    for r in results:
+        if r["what"] == "forward":
+            print(f"| {r['frames']} | {r['tiled_us']} | {r['tiled_spread']} | {r['mid_us']} | {r['mid_spread']} | {r['mid_frames_per_s']} | {r['mid_no_slower']} |")
+    print("\nthe condition (mid no slower than tiled at every size up to 1000 frames, per layer and for the forward):", "holds" if ok else "FAILS")
+    if out:
+        with open(out, "w") as fh:
+            json.dump(results, fh, indent=1)
+    hdnn.setMid(0)
+    hdnn.delete()
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--batches", default=None, help="frame counts (default 1000,10000; with --small " + SMALL_BATCHES + ")")
     ap.add_argument("--small", action="store_true", help="the small-batch kernel beside the tiled one at 1 .. 128 frames")
+    ap.add_argument("--mid", action="store_true", help="the mid-batch kernel beside the tiled one at 129 .. 4096 frames")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-run", type=int, default=0, help="only run 8 forwards of this many frames (under rocprofv3)")
     ap.add_argument("--trace", default=None, help="digest the kernel trace under this directory")
@@ -184,6 +266,8 @@ def main():
         return trace_run(args.trace_run)
     if args.small:
         return small_leg([int(v) for v in (args.batches or SMALL_BATCHES).split(",")], args.out)
+    if args.mid:
+        return mid_leg([int(v) for v in (args.batches or MID_BATCHES).split(",")], args.out)
     import torch
 
     path = model_path()
