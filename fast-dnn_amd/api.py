@@ -374,6 +374,9 @@ SIGNATURES = {
     "fdnn_half_model_set_mid": (C.c_int, [C.c_void_p, C.c_int]),
     "fdnn_debug_half_mid_launches": (C.c_int, [C.POINTER(C.c_ulonglong)]),
     "fdnn_debug_half_mid_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p]),
+    "fdnn_half_model_set_large": (C.c_int, [C.c_void_p, C.c_int]),
+    "fdnn_debug_half_large_launches": (C.c_int, [C.POINTER(C.c_ulonglong)]),
+    "fdnn_debug_half_large_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p]),
     "fdnn_debug_half_pack": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_longlong), C.c_int]),
     "fdnn_debug_half_extents": (C.c_int, [_c_i32p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
     "fdnn_half_calculate_lazy_sets": (C.c_int, [C.c_void_p, _c_f32p, C.c_int, C.c_int, _c_i32p, _c_i32p, C.c_int, _c_i32p, _c_f32p, _c_f32p]),
@@ -3188,6 +3191,26 @@ def half_mid_plan(n: int, small_setting: int, mid_setting: int, rows_pad: int, a
     return bool(out[0]), int(out[1]), int(out[2])
 
 
+HALF_LARGE_LAUNCH_KINDS = ("large.sigmoid", "large.exp", "large.sigmoid.tap", "large.exp.tap")
+
+
+def half_large_launches() -> dict:
+    """Process-wide launch counts of the half net's large-batch kernel since load (``fdnn_debug_half_large_launches``);
+    ``half_launches``, ``half_small_launches`` and ``half_mid_launches`` do not count them."""
+    buf = (C.c_ulonglong * len(HALF_LARGE_LAUNCH_KINDS))()
+    _check(lib().fdnn_debug_half_large_launches(buf))
+    return dict(zip(HALF_LARGE_LAUNCH_KINDS, (int(v) for v in buf)))
+
+
+def half_large_plan(n: int, small_setting: int, mid_setting: int, large_setting: int, rows_pad: int, act: int) -> tuple:
+    """No device (``fdnn_debug_half_large_plan``): (applies, frame tiles, node tiles) of a layer of rows_pad rows in form act
+    (0 sigmoid, 1 exp) in a call of n frames under ``setSmall(small_setting)``, ``setMid(mid_setting)`` and
+    ``setLarge(large_setting)``."""
+    out = (C.c_int32 * 3)()
+    _check(lib().fdnn_debug_half_large_plan(int(n), int(small_setting), int(mid_setting), int(large_setting), int(rows_pad), int(act), out))
+    return bool(out[0]), int(out[1]), int(out[2])
+
+
 HALF_SET_LAUNCH_KINDS = ("set.score", "set.score.tap", "set.gather")
 
 
@@ -3300,6 +3323,12 @@ class HalfDnn:
         """Calls of up to max_frames frames (at most 4096; 0 = off, the default) that ``setSmall`` does not take run on the
         mid-batch kernel (``fdnn_half_model_set_mid``).  Results never depend on it: the kernel gives the tiled kernel's bytes."""
         _check(lib().fdnn_half_model_set_mid(self.nativeHandle, int(max_frames)))
+
+    def setLarge(self, min_frames: int) -> None:
+        """Calls of min_frames frames or more (1 .. 65536; 0 = off, the default) that neither ``setSmall`` nor ``setMid`` takes run
+        on the large-batch kernel (``fdnn_half_model_set_large``).  Results never depend on it: the kernel gives the tiled
+        kernel's bytes."""
+        _check(lib().fdnn_half_model_set_large(self.nativeHandle, int(min_frames)))
 
     def layer(self, j: int, input):
         """ONE layer on the caller's rows, rounded to fp16 by the call (``fdnn_debug_half_layer``) -> (z fp32, the stored halves

@@ -257,5 +257,20 @@ void launch_hmid(const GemmParams &p, Act act, ihipStream_t *s);
 constexpr int kMidLaunchKinds = 4;
 void mid_launch_counts(unsigned long long out[kMidLaunchKinds]);
 
+// ---------------------------------------------------------------- the large-batch kernel (fdnn_half_large.hip)
+// A call of large_setting frames or more that is neither small nor mid may take hlarge_kernel instead of hgemm_kernel: the
+// same 256 x 128 tile and grid (gemm_grid), the operands requested 128 k ahead through a three-stage LDS ring.  THE CONTRACT
+// above holds unchanged: a row has the bytes hgemm_kernel gives it.
+constexpr int kLargeMaxSetting = fl::kMaxChunk;  // fdnn_half_model_set_large takes 0 (off) .. this
+// The rule.  n is the CALL's frame count, the settings the model's (0 = off): small, then mid, then large, then tiled.  Every
+// chunk of a large call is large, the tail included.
+inline bool large_applies(int n, int small_setting, int mid_setting, int large_setting) {
+  return large_setting >= 1 && n >= large_setting && !small_applies(n, small_setting) && !mid_applies(n, small_setting, mid_setting);
+}
+void launch_hlarge(const GemmParams &p, Act act, ihipStream_t *s);
+// large sigmoid, exp, sigmoid + tap, exp + tap
+constexpr int kLargeLaunchKinds = 4;
+void large_launch_counts(unsigned long long out[kLargeLaunchKinds]);
+
 }  // namespace hf
 }  // namespace fdnn

@@ -26,6 +26,7 @@ struct fdnn_half_model {
   int chunk = 0;  // fdnn_debug_half_set_chunk (0 = default)
   int small = 0;  // fdnn_half_model_set_small: calls of 1 .. small frames take hsmall_kernel (0 = off)
   int mid = 0;    // fdnn_half_model_set_mid: calls of up to mid frames that are not small take hmid_kernel (0 = off)
+  int large = 0;  // fdnn_half_model_set_large: calls of large frames and more that are neither take hlarge_kernel (0 = off)
   std::mutex mu;
   fdnn::StreamOrder order;
   DevBuf<uint8_t> d_blob;
@@ -58,8 +59,8 @@ int reserve_call(fdnn_half_model *m, int n) {
 
 // One layer over m frames of one chunk of a call of n frames.  A hidden layer writes halves to act (rows ldo apart); the
 // last one e and the partials to probs [m][rows], then the scale pass.  The one place that picks the GEMM's launcher:
-// hf::small_applies, then hf::mid_applies, on the CALL's n, so every chunk of a small call is small (m <= n <=
-// kSmallMaxFrames) and every chunk of a mid call is mid.
+// hf::small_applies, then hf::mid_applies, then hf::large_applies, on the CALL's n, so every chunk of a small call is small
+// (m <= n <= kSmallMaxFrames), every chunk of a mid call is mid and every chunk of a large call is large, the tail included.
 void run_layer(fdnn_half_model *hm, int j, const uint16_t *in, int lda, int m, int n, int cap, uint16_t *act, int ldo, float *probs,
                float *tap, hipStream_t s, bool normalize = true) {
   const hf::LayerDesc &d = hm->hm.layers[size_t(j)];
@@ -81,6 +82,7 @@ void run_layer(fdnn_half_model *hm, int j, const uint16_t *in, int lda, int m, i
   p.partial_ld = cap;
   if (hf::small_applies(n, hm->small)) hf::launch_hsmall(p, last ? hf::kExp : hf::kSigmoid, s);
   else if (hf::mid_applies(n, hm->small, hm->mid)) hf::launch_hmid(p, last ? hf::kExp : hf::kSigmoid, s);
+  else if (hf::large_applies(n, hm->small, hm->mid, hm->large)) hf::launch_hlarge(p, last ? hf::kExp : hf::kSigmoid, s);
   else hf::launch_hgemm(p, last ? hf::kExp : hf::kSigmoid, s);
   if (last && normalize) fdnn::launch_normalize(probs, probs, hm->d_partial, m, cap, d.rows, d.rows_pad / hf::kPartialNodes, s);
 }
@@ -317,6 +319,14 @@ int fdnn_half_model_set_mid(fdnn_half_model *hm, int max_frames) {
   return FDNN_OK;
 }
 
+int fdnn_half_model_set_large(fdnn_half_model *hm, int min_frames) {
+  if (!hm || min_frames < 0 || min_frames > hf::kLargeMaxSetting)
+    return fail(FDNN_E_ARG, "large-batch frames are 0 (off) .. " + std::to_string(hf::kLargeMaxSetting));
+  std::lock_guard<std::mutex> lk(hm->mu);
+  hm->large = min_frames;
+  return FDNN_OK;
+}
+
 int fdnn_half_calculate_device(fdnn_half_model *hm, const float *d_x, int n, float *d_out, void *stream) {
   if (!hm || n < 0) return fail(FDNN_E_ARG, "bad argument");
   if (n == 0) return FDNN_OK;
@@ -434,6 +444,12 @@ int fdnn_debug_half_small_launches(unsigned long long *out, int cap) {
 int fdnn_debug_half_mid_launches(unsigned long long *out4) {
   if (!out4) return fail(FDNN_E_ARG, "bad argument");
   hf::mid_launch_counts(out4);
+  return FDNN_OK;
+}
+
+int fdnn_debug_half_large_launches(unsigned long long *out4) {
+  if (!out4) return fail(FDNN_E_ARG, "bad argument");
+  hf::large_launch_counts(out4);
   return FDNN_OK;
 }
 
@@ -592,6 +608,17 @@ int fdnn_debug_half_mid_plan(int n, int small_setting, int mid_setting, int rows
   const bool applies = hf::mid_applies(n, small_setting, mid_setting);
   unsigned gx = 0, gy = 0;
   if (applies) hf::mid_grid(n, rows_pad, &gx, &gy);
+  out3[0] = applies ? 1 : 0;
+  out3[1] = int(gx);
+  out3[2] = int(gy);
+  return FDNN_OK;
+}
+
+int fdnn_debug_half_large_plan(int n, int small_setting, int mid_setting, int large_setting, int rows_pad, int act, int *out3) {
+  if (!out3 || rows_pad < 1 || rows_pad % hf::kNodeTile || (act != hf::kSigmoid && act != hf::kExp)) return fail(FDNN_E_ARG, "bad argument");
+  const bool applies = hf::large_applies(n, small_setting, mid_setting, large_setting);
+  unsigned gx = 0, gy = 0;
+  if (applies) hf::gemm_grid(n, rows_pad, &gx, &gy);
   out3[0] = applies ? 1 : 0;
   out3[1] = int(gx);
   out3[2] = int(gy);

@@ -1507,6 +1507,18 @@ FDNN_API int fdnn_report_read(fdnn_report *r, double threshold, fdnn_accuracy *a
  * fdnn_debug_half_mid_plan         no device: out3 = whether a call of n frames under the two settings is mid, and if so the
  *   grid of a layer of rows_pad rows (a multiple of 64) in form act (0 sigmoid, 1 exp): frame tiles of 64, node tiles of
  *   64; 0, 0, 0 where it is not.
+ * fdnn_half_model_set_large        opt-in, off by default: a call of min_frames frames or more (min_frames 1 .. 65536; 0 = off) that
+ *   is neither small nor mid runs its layers on the large-batch kernel (csrc/fdnn_half_large.hip): the tiled kernel's 256
+ *   frames x 128 nodes per workgroup and its grid, the operands requested 128 k ahead through a three-stage LDS ring of
+ *   direct global-to-LDS loads, one workgroup to a CU.  The order of precedence is small, mid, large, tiled.  The contract
+ *   holds unchanged, so every entry point -- the lazy set calls' hidden layers and their dense fallback included -- returns
+ *   the bytes it returns with the setting off.  The rule looks at the CALL's n: every chunk of such a call is large, the
+ *   tail included.  FDNN_E_ARG outside 0 .. 65536, the model unchanged.
+ * fdnn_debug_half_large_launches   process-wide launch counts of that kernel since load into out4: large sigmoid, exp,
+ *   sigmoid + tap, exp + tap.  The other three counter calls do not count them.
+ * fdnn_debug_half_large_plan       no device: out3 = whether a call of n frames under the three settings is large, and if so
+ *   the grid of a layer of rows_pad rows (a multiple of 128) in form act (0 sigmoid, 1 exp): frame tiles of 256, node tiles
+ *   of 128; 0, 0, 0 where it is not.
  * fdnn_debug_half_pack              no device: loads `path` as the half net and copies the packed blob to blob[cap] (where it
  *   fits) and to desc, per layer, off_w, off_bias, rows, rows_pad, K, K_pad, then off_shift, off_scale and the blob's size;
  *   returns the number of desc entries, or the load's error.
@@ -1557,6 +1569,9 @@ FDNN_API int fdnn_debug_half_small_plan(int n, int setting, int rows_pad, int ac
 FDNN_API int fdnn_half_model_set_mid(fdnn_half_model *hm, int max_frames);
 FDNN_API int fdnn_debug_half_mid_launches(unsigned long long *out4);
 FDNN_API int fdnn_debug_half_mid_plan(int n, int small_setting, int mid_setting, int rows_pad, int act, int *out3);
+FDNN_API int fdnn_half_model_set_large(fdnn_half_model *hm, int min_frames);
+FDNN_API int fdnn_debug_half_large_launches(unsigned long long *out4);
+FDNN_API int fdnn_debug_half_large_plan(int n, int small_setting, int mid_setting, int large_setting, int rows_pad, int act, int *out3);
 FDNN_API int fdnn_debug_half_pack(const char *path, void *blob, size_t cap, long long *desc, int desc_cap);
 FDNN_API int fdnn_debug_half_extents(const int *shape4, int n, int chunk_setting, long long *out7);
 FDNN_API int fdnn_half_calculate_lazy_sets(fdnn_half_model *hm, const float *x, int n, int dim, const int32_t *seg_rows, const int32_t *set_ptr,

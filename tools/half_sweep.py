@@ -21,6 +21,13 @@
            no slower than tiled by more than the larger spread at every n up to 1000; larger n are reported.
                python tools/half_sweep.py --mid [--batches 129,256,512,1000,2048,4096]
 
+  large    the large-batch kernel (fdnn_half_large.hip; setLarge) beside the tiled one on the same model: first the two forwards'
+           bytes must be equal; then per layer shape at --layer-batches (one chunk each) and the forward at --batches, with the
+           share of the fp16 MFMA peak, setLarge(0) and setLarge(1) alternated block by block in one process.  The leg ends
+           with the condition of DESIGN section 36: the hidden form and the forward no slower than tiled by more than the
+           larger spread at every size; layer 0 and the output form are reported the same way.
+               python tools/half_sweep.py --large [--layer-batches 1808,2048,4096] [--batches 4096,10000,20480]
+
   python tools/half_sweep.py [--batches 1000,10000] [--out FILE.json]"""
 import argparse
 import csv
@@ -43,6 +50,8 @@ FLOP_PER_CLOCK_CU = 4096.0
 HBM_PEAK_GBS = 8000.0  # bench.py's roofline figure
 SMALL_BATCHES = "1,10,32,100,128"
 MID_BATCHES = "129,256,512,1000,2048,4096"
+LARGE_LAYER_BATCHES = "1808,2048,4096"  # the tail chunk of a 10 000-frame call, half a chunk, a chunk
+LARGE_BATCHES = "4096,10000,20480"
 
 
 def stats(v):
@@ -250,11 +259,85 @@ def mid_leg(batches, out):
     return 0 if ok else 1
 
 
+def large_leg(layer_batches, batches, out):
+    import torch
+
+    hdnn = api.HalfDnn.loadFromFile(model_path())
+    D, O, L = hdnn.inputDimension(), hdnn.outputDimension(), hdnn.layerCount()
+    peak, cus, ghz = peak_tflops()
+    print(json.dumps({"what": "peak", "fp16_mfma_tflops": round(peak, 1), "cus": cus, "ghz": ghz}), flush=True)
+    s = torch.cuda.current_stream().cuda_stream
+    shapes = {"layer0": (0, D, hdnn.layerDimension(0)), "hidden": (1, hdnn.layerDimension(0), hdnn.layerDimension(1)),
+              "output": (L - 1, hdnn.layerDimension(L - 2), O)}
+    forms = {"tiled": 0, "large": 1}
+    flop_per_frame = 2.0 * sum(K * rows for K, rows in zip([D] + [hdnn.layerDimension(j) for j in range(L - 1)], [hdnn.layerDimension(j) for j in range(L)]))
+    results, ok = [], True
+
+    def row(st, n, flop, extra):  # large no slower than tiled by more than the larger of the two spreads
+        good = st["large"]["median"] <= st["tiled"]["median"] * (1.0 + max(st["tiled"]["spread"], st["large"]["spread"]))
+        r = {"frames": n, **extra, **{f + "_us": round(st[f]["median"], 1) for f in forms}, **{f + "_spread": st[f]["spread"] for f in forms},
+             **{f + "_of_peak": round(flop / st[f]["median"] / 1e6 / peak, 3) for f in forms}, "large_no_slower": good}
+        results.append(r)
+        print(json.dumps(r), flush=True)
+        return good
+
+    for n in batches:  # the forwards first: their bytes must be equal before anything is timed
+        x = torch.from_numpy(F.synth_features(n, D, seed=500 + n)).cuda()
+        outs = {f: torch.empty((n, O), dtype=torch.float32, device="cuda") for f in forms}
+
+        def forward(form):
+            hdnn.setLarge(forms[form])
+            hdnn.calculateDevice(x.data_ptr(), n, outs[form].data_ptr(), s)
+
+        for f in forms:
+            for _ in range(3):
+                forward(f)
+        torch.cuda.synchronize()
+        if not torch.equal(outs["tiled"].view(torch.int32), outs["large"].view(torch.int32)):
+            sys.exit(f"half_sweep: the large form's bytes differ from the tiled form's at n = {n}")
+        fus = {f: [] for f in forms}
+        for _ in range(ROUNDS):
+            for f in forms:
+                fus[f].append(timed(lambda: forward(f), 20))
+        st = {f: stats(fus[f]) for f in forms}
+        ok = row(st, n, flop_per_frame * n, {"what": "forward", "large_frames_per_s": round(n / st["large"]["median"] * 1e6)}) and ok
+    for n in layer_batches:
+        rng = np.random.default_rng(n)
+        ins = {k: (F.synth_features(n, D, seed=500 + n) if k == "layer0" else rng.random((n, K), dtype=np.float32)) for k, (_, K, _) in shapes.items()}
+        us = {(k, f): [] for k in shapes for f in forms}
+        for _ in range(ROUNDS):
+            for k, (j, _, _) in shapes.items():
+                for f, setting in forms.items():
+                    hdnn.setLarge(setting)
+                    us[k, f].append(hdnn.layerMicros(j, ins[k], reps=20))
+        for k, (j, K, rows) in shapes.items():
+            good = row({f: stats(us[k, f]) for f in forms}, n, 2.0 * n * K * rows, {"what": "layer", "layer": k, "K": K, "rows": rows})
+            ok = ok and (good or k != "hidden")
+    head = "tiled us | spread | of peak | large us | spread | of peak | large no slower |"
+    print("\n| frames | layer | K x rows | " + head + "\n|---|---|---|---|---|---|---|---|---|---|")
+    for r in results:
+        if r["what"] == "layer":
+            print(f"| {r['frames']} | {r['layer']} | {r['K']} x {r['rows']} | {r['tiled_us']} | {r['tiled_spread']} | {r['tiled_of_peak']} | {r['large_us']} | {r['large_spread']} | {r['large_of_peak']} | {r['large_no_slower']} |")
+    print("\n| frames | " + head + " large frames/s |\n|---|---|---|---|---|---|---|---|---|")
+    for r in results:
+        if r["what"] == "forward":
+            print(f"| {r['frames']} | {r['tiled_us']} | {r['tiled_spread']} | {r['tiled_of_peak']} | {r['large_us']} | {r['large_spread']} | {r['large_of_peak']} | {r['large_no_slower']} | {r['large_frames_per_s']} |")
+    print("\nthe condition (the hidden form and the forward no slower than tiled at every size):", "holds" if ok else "FAILS")
+    if out:
+        with open(out, "w") as fh:
+            json.dump(results, fh, indent=1)
+    hdnn.setLarge(0)
+    hdnn.delete()
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--batches", default=None, help="frame counts (default 1000,10000; with --small " + SMALL_BATCHES + ")")
     ap.add_argument("--small", action="store_true", help="the small-batch kernel beside the tiled one at 1 .. 128 frames")
     ap.add_argument("--mid", action="store_true", help="the mid-batch kernel beside the tiled one at 129 .. 4096 frames")
+    ap.add_argument("--large", action="store_true", help="the large-batch kernel beside the tiled one")
+    ap.add_argument("--layer-batches", default=LARGE_LAYER_BATCHES, help="with --large: frame counts of the per-layer rows")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-run", type=int, default=0, help="only run 8 forwards of this many frames (under rocprofv3)")
     ap.add_argument("--trace", default=None, help="digest the kernel trace under this directory")
@@ -268,6 +351,8 @@ def main():
         return small_leg([int(v) for v in (args.batches or SMALL_BATCHES).split(",")], args.out)
     if args.mid:
         return mid_leg([int(v) for v in (args.batches or MID_BATCHES).split(",")], args.out)
+    if args.large:
+        return large_leg([int(v) for v in args.layer_batches.split(",")], [int(v) for v in (args.batches or LARGE_BATCHES).split(",")], args.out)
     import torch
 
     path = model_path()
